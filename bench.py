@@ -33,7 +33,8 @@ record: the stand-alone covariance builder (GB/s written, leaf evaluations/s: SU
 (src/inference_smc_anneal_data.jl:63-67: where fit_smc! spends its time) and the marginal predictive pass at m = 2n
 (src/GP.jl:731-758).  `--no-extra-legs` skips them.
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  `--dump-outputs DIR` also writes what the last timed step returned (logpdf and info of every
+particle, float64) as DIR/<name>.npy, for comparing two builds output for output on the same seeded inputs.
 """
 from __future__ import annotations
 
@@ -431,6 +432,28 @@ def bench_series(pkg, n):
     return pkg.prior.synthetic_series(n, seed=2048, shuffle=True)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: what the timed path handed its caller in the last timed step, one DIR/<name>.npy per array (float64), so
+    that two builds run with the same arguments (hence the same seeded inputs) can be compared output for output.  Should the
+    arrays pass 64 MB in all, the same fixed, seeded sample of their elements is written instead, with its indices as
+    DIR/sample_index.npy."""
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64).ravel() for k, v in arrays.items()}
+    length = len(next(iter(arrays.values())))
+    assert all(len(v) == length for v in arrays.values())
+    if 8 * len(arrays) * length > DUMP_LIMIT_BYTES:
+        keep = DUMP_LIMIT_BYTES // (8 * (len(arrays) + 1))
+        idx = np.sort(np.random.default_rng(0).choice(length, size=keep, replace=False))
+        arrays = {k: v[idx] for k, v in arrays.items()}
+        arrays["sample_index"] = idx.astype(np.float64)
+    for k, v in arrays.items():
+        np.save(out_dir / f"{k}.npy", v)
+
+
 def free_port():
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as s:
         s.bind(("127.0.0.1", 0))
@@ -565,6 +588,8 @@ def run_single_process(args):
         torch.cuda.synchronize(d)
     dt = time.perf_counter() - t0
     eng0.set_profiling(False)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"logpdf": lp, "info": info})
     # self-check: the gathered vector equals every device's own sweep of its shard
     ok = True
     for d, e in enumerate(multi.engines):
@@ -607,7 +632,11 @@ def main():
     ap.add_argument("--no-extra-legs", action="store_true", help="skip the covariance-builder / gradient / predictive legs (N = 1)")
     ap.add_argument("--single-process", action="store_true", help="one host process drives all --gpus devices (agp_init_multi)")
     ap.add_argument("--dump-logweights", default=None, help="rank 0 writes the complete (all-gathered) log-weight vector of the last step to this .npy file")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one returned (logpdf, info of every particle) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.single_process:
         return run_single_process(args)
@@ -807,6 +836,13 @@ def main():
         sync()
     if args.dump_logweights and rank == 0:
         np.save(args.dump_logweights, d_all.cpu().numpy() if world > 1 else lp)
+    if args.dump_outputs:
+        infos = [info]
+        if world > 1:
+            infos = [None] * world
+            dist.all_gather_object(infos, info)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, {"logpdf": d_all.cpu().numpy() if world > 1 else lp, "info": np.concatenate(infos)})
     if world > 1:
         nb = torch.tensor([n_bad], dtype=torch.int64)
         dist.all_reduce(nb)

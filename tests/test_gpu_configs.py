@@ -319,6 +319,33 @@ def test_bench_single_process_mode():
     assert out["config"]["particles_total"] == 64 and out["value"] > 0 and out["roofline"]["achieved"] > 0
 
 
+def test_bench_dump_outputs(tmp_path):
+    """`--dump-outputs DIR` writes the last timed step's logpdf and info vectors (float64, whole population) after exactly
+    --steps timed steps; the same arguments give the same inputs, so a rerun with another step count dumps the same bits, the
+    rank split and the single-process launch agree with it to fp64 rounding, and logpdf matches --dump-logweights."""
+    common = ["--warmup", "1", "--n-obs", "700", "--particles", "64", "--no-cpu-baseline", "--no-extra-legs"]
+    runs = {"s3": (["--gpus", "1", "--steps", "3", "--dump-logweights", str(tmp_path / "lw.npy")], None),
+            "s5": (["--gpus", "1", "--steps", "5"], None),
+            "two_ranks": (["--gpus", "2", "--steps", "3"], {"AGP_BENCH_SHARE_GPU": "1"}),
+            "single_process": (["--single-process", "--gpus", "1", "--steps", "3"], None)}
+    dumps = {}
+    for name, (argv, env) in runs.items():
+        out = _bench_line(argv + common + ["--dump-outputs", str(tmp_path / name)], env)
+        assert out["steps"] == int(argv[argv.index("--steps") + 1])
+        assert sorted(p.name for p in (tmp_path / name).iterdir()) == ["info.npy", "logpdf.npy"]
+        dumps[name] = {k: np.load(tmp_path / name / f"{k}.npy") for k in ("logpdf", "info")}
+        for v in dumps[name].values():
+            assert v.dtype == np.float64 and v.shape == (64,)
+    ref = dumps["s3"]
+    ok = ref["info"] == 0
+    assert ok.sum() > 32 and np.isfinite(ref["logpdf"][ok]).all()
+    assert np.array_equal(ref["logpdf"], np.load(tmp_path / "lw.npy"), equal_nan=True)
+    assert np.array_equal(dumps["s5"]["logpdf"], ref["logpdf"], equal_nan=True)
+    for name, d in dumps.items():
+        assert np.array_equal(d["info"], ref["info"]), name
+        assert lp_err(d["logpdf"][ok], ref["logpdf"][ok]).max() <= 1e-12, name
+
+
 def _n_devices():
     import torch
     return torch.cuda.device_count()

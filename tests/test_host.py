@@ -312,3 +312,11 @@ def test_no_waterfalled_buffer_accesses():
     spec = importlib.util.spec_from_file_location("check_isa", Path(__file__).resolve().parent.parent / "tools" / "check_isa.py")
     mod = importlib.util.module_from_spec(spec); spec.loader.exec_module(mod)
     assert mod.main() == 0
+
+
+def test_bench_rejects_an_empty_timed_region():
+    """bench.py times exactly --steps steps: zero (or a negative warm-up) is refused before any device work."""
+    import subprocess
+    for argv in (["--steps", "0"], ["--warmup", "-1"]):
+        r = subprocess.run([sys.executable, str(ROOT / "bench.py")] + argv, capture_output=True, text=True, timeout=120)
+        assert r.returncode == 2 and "--steps must be >= 1" in r.stderr, r.stderr
