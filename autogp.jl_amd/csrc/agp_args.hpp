@@ -249,4 +249,14 @@ constexpr int FFT_N = 4096;                // transform length of the spectral v
 constexpr int LDS_TAPE_NODES = 8;
 constexpr int FFT_BUF = FFT_N + FFT_N / 16;
 
+// k_poison_rows (NaN-poison mode of the store's sweeps): per buffer b, slot u's doubles [row start(i0[u]), pitch) in slot[u]
+struct PoisonRowsArgs {
+  double* base[4];
+  long long pitch[4];        // doubles per slot
+  long long unit[4];         // doubles per tile row (A: per tile)
+  int tri[4];                // 1: packed lower triangle (row i starts at tile i(i+1)/2)
+  int nt_cap;
+  const int* slot;
+  const int* i0;
+};
 }  // namespace agp

@@ -183,9 +183,11 @@ __device__ __forceinline__ void factor_diag_tile(const CholArgs& a, int p, int t
   // The last tile row of a series is ragged: rows from n1 on are identity padding (cov_finalize), whose 16 x 16 blocks factor to
   // themselves — identity L, identity inverse, zero panel, alpha 0, bit for bit what the steps below would produce.  Only the
   // nbk block steps that hold data are run (n = 144: one of the eight steps of tile 1, ~28 us of a 125-us value sweep).  n1 = 0:
-  // a dense-input factorisation, whose padding this function knows nothing about — all steps.
+  // a dense-input factorisation, whose padding this function knows nothing about — all steps.  rows_real <= 0 (a diagonal tile
+  // wholly past n1) cannot occur: only the training block's columns reach this kernel (agp_predict.hip, agp_store.hip) — were one
+  // to, it is factored in full like any tile whose padding is not known, never overwritten with identity.
   const int rows_real = a.n1 > 0 ? a.n1 - tk * NB : NB;
-  const int nbk = rows_real >= NB ? NSB : rows_real <= 16 ? 1 : (rows_real + 15) >> 4;
+  const int nbk = (rows_real >= NB || rows_real <= 0) ? NSB : rows_real <= 16 ? 1 : (rows_real + 15) >> 4;
   AGP_DPROBE(2);
   if (w == 0) factor16(0);
   AGP_DPROBE(3);
@@ -1349,6 +1351,21 @@ __global__ __launch_bounds__(256) void k_copy_rows(double* __restrict__ dst, lon
   double* d = dst + r * dpitch;
   const long long stride = (long long)gridDim.x * blockDim.x;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < width; i += stride) d[i] = s[i];
+}
+
+// NaN-poison mode (AGP_POISON): the tile rows >= i0[u] of store slot slot[u] — what the sweep recomputes — are filled with NaN bits
+// in each resident buffer b = blockIdx.z (packed lower triangle: row i at tile i(i+1)/2; otherwise by tile row).  Extension sweep:
+// A, W, vec, partial; predictive pass on a resident factor: its L^-T (tile column i of Z is packed row i) and the rows' running
+// sums.  An entry with slot or i0 < 0 is skipped; i0 is clamped to the slot's capacity, every write stays below its slot's end.
+__global__ __launch_bounds__(256) void k_poison_rows(PoisonRowsArgs a) {
+  const int u = blockIdx.y, b = blockIdx.z;
+  if (a.slot[u] < 0 || a.i0[u] < 0) return;
+  const int r0 = min(a.i0[u], a.nt_cap);
+  const long long start = a.tri[b] ? (long long)r0 * (r0 + 1) / 2 * a.unit[b] : (long long)r0 * a.unit[b];
+  double* d = a.base[b] + (long long)a.slot[u] * a.pitch[b];
+  const double nanv = __longlong_as_double(-1ll);
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long i = start + (long long)blockIdx.x * blockDim.x + threadIdx.x; i < a.pitch[b]; i += stride) d[i] = nanv;
 }
 
 // out[p] = lp[rep[p]]: the distinct particles' results expanded to the caller's population order (device-resident

@@ -54,7 +54,17 @@ void latch_async_info(agp_ctx* c, Slot* s) {
   s->async_P = 0;
 }
 
-Slot* acquire_slot(agp_ctx* c) {
+hipError_t malloc_values(PoisonCtl& pz, void** p, size_t bytes) {
+  hipError_t e = hipMalloc(p, bytes);
+  if (e == hipSuccess && pz.active() && bytes > 0) {
+    e = hipMemset(*p, POISON_BYTE, bytes);
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    if (e == hipSuccess) pz.count(bytes);
+  }
+  return e;
+}
+
+static Slot* claim_slot(agp_ctx* c) {
   std::unique_lock<std::mutex> g(c->mu);
   for (;;) {
     Slot* waiting = nullptr;
@@ -67,6 +77,7 @@ Slot* acquire_slot(agp_ctx* c) {
     }
     if ((int)c->slots.size() < c->max_slots) {
       Slot* s = new Slot();
+      s->attach(&c->poison);
       s->busy = true;
       c->slots.push_back(s);
       return s;
@@ -86,6 +97,20 @@ Slot* acquire_slot(agp_ctx* c) {
     }
     c->cv.wait(g);
   }
+}
+
+Slot* acquire_slot(agp_ctx* c) {
+  Slot* s = claim_slot(c);
+  if (c->poison.active()) {
+    // NaN-poison mode: whatever the slot's value buffers hold from an earlier call reads as NaN in this one.  (Complete before
+    // the call starts: a device-output call may run its sweep on the caller's stream instead of the slot's.  The slot's earlier
+    // work has completed: synchronous calls drain their streams, an asynchronous hand-back was waited for above.)
+    bool any = false;
+    s->for_each_dev([&](DevBuf& b) { if (b.poisoned() && b.p) { (void)b.poison_async(s->stream); any = true; } });
+    if (any) (void)hipStreamSynchronize(s->stream);
+    if (s->h_out.p) { std::memset(s->h_out.p, POISON_BYTE, s->h_out.cap); c->poison.count(s->h_out.cap); }
+  }
+  return s;
 }
 
 void release_slot(agp_ctx* c, Slot* s, bool async_done) {
@@ -1738,6 +1763,10 @@ static int init_body(agp_ctx** out, int device_id) {
   if (const char* e = getenv("AGP_COALESCE_US")) c->coalesce_us = std::max(0, atoi(e));
   if (const char* e = getenv("AGP_FLOW")) c->flow = atoi(e);
   if (const char* e = getenv("AGP_EXTEND_FRAC")) c->store.max_frac = std::max(0.0, std::min(0.8, atof(e)));
+  if (const char* e = getenv("AGP_POISON")) c->poison.on = atoi(e) != 0;      // checking switch: no path changes
+  for (DevBuf* b : {&c->store.A, &c->store.W, &c->store.vec, &c->store.partial, &c->store.info, &c->store.ready, &c->store.tflag,
+                    &c->store.flowq, &c->store.Z, &c->store.zalpha, &c->store.zdinv, &c->comm_in, &c->comm_out, &c->comm_all})
+    b->pz = &c->poison;
   if (const char* e = getenv("AGP_REFERENCE_ARITHMETIC")) { if (atoi(e) != 0) apply_reference_arithmetic(c); }      // (overrides the switches above)
   *out = c;
   return AGP_OK;
@@ -1995,7 +2024,7 @@ static int set_data_body(agp_ctx* c, const double* ts, const double* xs, int64_t
   // padded to a whole tile so kernels may read (and ignore) the tail
   const int64_t npad = ((n_max + NB - 1) / NB) * NB + NB;
   HIPCHK(c, hipMalloc((void**)&c->d_ts, sizeof(double) * npad));
-  HIPCHK(c, hipMalloc((void**)&c->d_xs, sizeof(double) * npad));
+  HIPCHK(c, malloc_values(c->poison, (void**)&c->d_xs, sizeof(double) * npad));
   HIPCHK(c, hipMemset(c->d_ts, 0, sizeof(double) * npad));
   HIPCHK(c, hipMemset(c->d_xs, 0, sizeof(double) * npad));
   if (n_max > 0) {
@@ -2036,7 +2065,7 @@ static int set_data_body(agp_ctx* c, const double* ts, const double* xs, int64_t
     std::vector<int64_t>& lat = lf.index;
     if (regular || lattice) {
       HIPCHK(c, hipMalloc((void**)&c->d_ts_s, sizeof(double) * npad));
-      HIPCHK(c, hipMalloc((void**)&c->d_xs_s, sizeof(double) * npad));
+      HIPCHK(c, malloc_values(c->poison, (void**)&c->d_xs_s, sizeof(double) * npad));
       HIPCHK(c, hipMemset(c->d_ts_s, 0, sizeof(double) * npad));
       HIPCHK(c, hipMemset(c->d_xs_s, 0, sizeof(double) * npad));
       HIPCHK(c, hipMemcpy(c->d_ts_s, tss.data(), sizeof(double) * n_max, hipMemcpyHostToDevice));
@@ -2074,7 +2103,7 @@ static int set_data_body(agp_ctx* c, const double* ts, const double* xs, int64_t
           tw[2 * (size_t)k] = (double)cosl(ang); tw[2 * (size_t)k + 1] = (double)sinl(ang);
         }
         double* d_tw = nullptr;
-        HIPCHK(c, hipMalloc((void**)&d_tw, sizeof(double) * tw.size()));
+        HIPCHK(c, malloc_values(c->poison, (void**)&d_tw, sizeof(double) * tw.size()));
         HIPCHK(c, hipMemcpy(d_tw, tw.data(), sizeof(double) * tw.size(), hipMemcpyHostToDevice));
         c->d_fft_tw = d_tw;
       }
@@ -2114,7 +2143,7 @@ static int set_data_body(agp_ctx* c, const double* ts, const double* xs, int64_t
           }
           for (int64_t od = n_max; od < npad + 256; ++od) Bv[(size_t)od] = Bv[(size_t)n_max - 1];
           HIPCHK(c, hipMalloc((void**)&c->d_ts_s, sizeof(double) * npad));
-          HIPCHK(c, hipMalloc((void**)&c->d_xs_s, sizeof(double) * npad));
+          HIPCHK(c, malloc_values(c->poison, (void**)&c->d_xs_s, sizeof(double) * npad));
           HIPCHK(c, hipMemset(c->d_ts_s, 0, sizeof(double) * npad));
           HIPCHK(c, hipMemset(c->d_xs_s, 0, sizeof(double) * npad));
           HIPCHK(c, hipMemcpy(c->d_ts_s, tss.data(), sizeof(double) * n_max, hipMemcpyHostToDevice));
@@ -2160,7 +2189,7 @@ static int set_data_body(agp_ctx* c, const double* ts, const double* xs, int64_t
     if (bytes <= ((size_t)4 << 30)) {
       if (bytes > c->logdt_cap) {
         if (c->d_logdt) { HIPCHK(c, hipFree(c->d_logdt)); c->d_logdt = nullptr; c->logdt_cap = 0; }
-        HIPCHK(c, hipMalloc((void**)&c->d_logdt, bytes));
+        HIPCHK(c, malloc_values(c->poison, (void**)&c->d_logdt, bytes));
         c->logdt_cap = bytes;
       }
       launch_logdt_tiles(0, (unsigned)ntiles, c->d_ts, c->d_logdt);

@@ -32,9 +32,30 @@
 using namespace agp;
 
 
+// NaN-poison mode (AGP_POISON=1, per context; a checking switch, not a path).  Every buffer says what its contents are:
+//   values — floating-point values only (factor tiles, inverse blocks, vectors, partials, tables, outputs): in poison mode every
+//            fresh allocation, and every slot buffer when its slot is claimed, is filled with byte 0xFF (each double a NaN), so
+//            a read of memory the call has not written turns into a NaN in the result instead of a stale finite number;
+//   never  — anything that becomes an address, index, count, loop bound or spin-wait flag (times, ranks, keys, programs, headers,
+//            maps, particle lists, info / ready / retry flags, queue counters): never poisoned — a poisoned index is an
+//            out-of-bounds access.
+// There is no default: a new buffer that does not say which it holds does not compile.
+enum class Fill { values, never };
+struct PoisonCtl {
+  int on = 0;                              // env AGP_POISON (agp_init)
+  std::atomic<int64_t> bytes{0}, fills{0}; // what was poisoned so far (agp_get_poison_stats)
+  bool active() const { return on != 0; }
+  void count(size_t b) { bytes += (int64_t)b; fills += 1; }
+};
+constexpr int POISON_BYTE = 0xFF;
+
 struct DevBuf {
   void* p = nullptr;
   size_t cap = 0;
+  Fill fill;
+  PoisonCtl* pz = nullptr;                 // the owning context's switch (set by the owner: Slot::attach, init_body, store_resize)
+  explicit DevBuf(Fill f, PoisonCtl* z = nullptr) : fill(f), pz(z) {}
+  bool poisoned() const { return fill == Fill::values && pz && pz->active(); }
   hipError_t ensure(size_t bytes) {
     if (bytes <= cap) return hipSuccess;
     if (p) { hipError_t e = hipFree(p); p = nullptr; cap = 0; if (e != hipSuccess) return e; }
@@ -42,22 +63,42 @@ struct DevBuf {
     hipError_t e = hipMalloc(&p, want);
     if (e != hipSuccess) { e = hipMalloc(&p, bytes); want = bytes; }
     if (e == hipSuccess) cap = want;
+    if (e == hipSuccess && poisoned()) {
+      // (complete before any stream of the context uses the buffer: the slots' streams do not wait for the null stream)
+      e = hipMemset(p, POISON_BYTE, cap);
+      if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+      if (e == hipSuccess) pz->count(cap);
+    }
+    return e;
+  }
+  // the whole allocation on `st` (a slot being claimed)
+  hipError_t poison_async(hipStream_t st) {
+    if (!p || !poisoned()) return hipSuccess;
+    hipError_t e = hipMemsetAsync(p, POISON_BYTE, cap, st);
+    if (e == hipSuccess) pz->count(cap);
     return e;
   }
   void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
   template <typename T> T* as() { return reinterpret_cast<T*>(p); }
 };
 
+// (poison mode) a bare device allocation of VALUES outside the DevBufs (agp_set_data's tables, probes, the multi-device shards)
+hipError_t malloc_values(PoisonCtl& pz, void** p, size_t bytes);
+
 // pinned host staging (truly asynchronous copies, one per direction and call)
 struct HostBuf {
   void* p = nullptr;
   size_t cap = 0;
+  Fill fill;
+  PoisonCtl* pz = nullptr;
+  explicit HostBuf(Fill f) : fill(f) {}
   hipError_t ensure(size_t bytes) {
     if (bytes <= cap) return hipSuccess;
     if (p) { (void)hipHostFree(p); p = nullptr; cap = 0; }
     const size_t want = bytes + bytes / 4 + 4096;
     hipError_t e = hipHostMalloc(&p, want, hipHostMallocDefault);
     if (e == hipSuccess) cap = want;
+    if (e == hipSuccess && fill == Fill::values && pz && pz->active()) { std::memset(p, POISON_BYTE, cap); pz->count(cap); }
     return e;
   }
   void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
@@ -118,15 +159,35 @@ struct PinnedUploads {
 
 struct Slot {
   hipStream_t stream = nullptr;
-  DevBuf stage;             // one upload per sweep: [hdr | prm | noise | map | ops]
-  HostBuf h_stage, h_out;   // its pinned source, and the pinned landing zone of [logpdf | info]
-  HostBuf h_stage2;         // pinned source of the gradient programs (the sweep's stage copy may still be reading h_stage)
-  DevBuf up_blob, up_blob2; // device landing zones of PinnedUploads' blobs (h_stage / h_stage2)
-  HostBuf h_pl;             // pinned source of the gradient sweeps' particle lists
-  DevBuf A, W, vec, partial, info, out_lp, out_info, hdr, ops, prm, noise, noise_pred, tt, mu1, mu2,
-      pred_mean, pred_var, pred_cov, dense, map, ready, code, diag_add,
-      Z, alpha, tsol, tretry, gpart, ghdr, gops, glc, grc, gpoff, gprm, gmap, goff, dgrad, dgnoise, plist, tflag, flowq, lagtab,
-      pl_rank, pl_tl, pl_prog;
+  // Classification (see Fill).  No slot buffer carries data from one call to the next: every entry writes what it reads
+  // (programs, parameters and tables are uploaded, factors recomputed or gathered from the store) — so every `values` buffer is
+  // poisoned again when the slot is claimed (acquire_slot).
+  DevBuf stage{Fill::never};              // one upload per sweep: [hdr | prm | noise | map | ops]
+  HostBuf h_stage{Fill::never}, h_out{Fill::values};   // its pinned source, and the pinned landing zone of [logpdf | info]
+  HostBuf h_stage2{Fill::never};          // pinned source of the gradient programs (the sweep's stage copy may still be reading h_stage)
+  DevBuf up_blob{Fill::never}, up_blob2{Fill::never};  // device landing zones of PinnedUploads' blobs (h_stage / h_stage2): addresses
+  HostBuf h_pl{Fill::never};              // pinned source of the gradient sweeps' particle lists
+  // floating-point values
+  DevBuf A{Fill::values}, W{Fill::values}, vec{Fill::values}, partial{Fill::values}, out_lp{Fill::values},
+      noise{Fill::values}, noise_pred{Fill::values}, mu1{Fill::values}, mu2{Fill::values}, pred_mean{Fill::values},
+      pred_var{Fill::values}, pred_cov{Fill::values}, dense{Fill::values}, diag_add{Fill::values}, Z{Fill::values},
+      alpha{Fill::values}, tsol{Fill::values}, gpart{Fill::values}, dgrad{Fill::values}, dgnoise{Fill::values}, lagtab{Fill::values};
+  // addresses, indices, counts, programs (their parameters included: uploaded whole), times, flags
+  DevBuf info{Fill::never}, out_info{Fill::never}, hdr{Fill::never}, ops{Fill::never}, prm{Fill::never}, tt{Fill::never}, map{Fill::never},
+      ready{Fill::never}, code{Fill::never}, tretry{Fill::never}, ghdr{Fill::never}, gops{Fill::never}, glc{Fill::never},
+      grc{Fill::never}, gpoff{Fill::never}, gprm{Fill::never}, gmap{Fill::never}, goff{Fill::never}, plist{Fill::never},
+      tflag{Fill::never}, flowq{Fill::never}, pl_rank{Fill::never}, pl_tl{Fill::never}, pl_prog{Fill::never};
+  template <class F> void for_each_dev(F&& f) {
+    for (DevBuf* b : {&stage, &up_blob, &up_blob2, &A, &W, &vec, &partial, &out_lp, &out_info, &noise, &noise_pred, &mu1, &mu2,
+                      &pred_mean, &pred_var, &pred_cov, &dense, &diag_add, &Z, &alpha, &tsol, &gpart, &dgrad, &dgnoise, &lagtab,
+                      &info, &hdr, &ops, &prm, &tt, &map, &ready, &code, &tretry, &ghdr, &gops, &glc, &grc, &gpoff, &gprm, &gmap,
+                      &goff, &plist, &tflag, &flowq, &pl_rank, &pl_tl, &pl_prog})
+      f(*b);
+  }
+  void attach(PoisonCtl* z) {
+    for_each_dev([z](DevBuf& b) { b.pz = z; });
+    for (HostBuf* b : {&h_stage, &h_out, &h_stage2, &h_pl, &h_async_info}) b->pz = z;
+  }
   std::vector<hipEvent_t> events;
   hipStream_t gq[3] = {nullptr, nullptr, nullptr};     // gradient sweeps: the contraction's launch classes run side by side
   hipEvent_t gq_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -135,15 +196,12 @@ struct Slot {
   // recorded behind the call's last launch, has completed
   hipEvent_t done = nullptr;
   bool pending = false;
-  HostBuf h_async_info;     // pinned copy of the call's info words, read when the slot is next claimed
+  HostBuf h_async_info{Fill::never};     // pinned copy of the call's info words, read when the slot is next claimed
   int async_P = 0;
   void release() {
     if (done) { (void)hipEventDestroy(done); done = nullptr; }
-    for (DevBuf* b : {&A, &W, &vec, &partial, &info, &out_lp, &out_info, &hdr, &ops, &prm, &noise,
-                      &noise_pred, &tt, &mu1, &mu2, &pred_mean, &pred_var, &pred_cov, &dense, &map, &ready, &code, &diag_add,
-                      &Z, &alpha, &tsol, &tretry, &gpart, &ghdr, &gops, &glc, &grc, &gpoff, &gprm, &gmap, &goff, &dgrad, &dgnoise, &plist, &tflag, &flowq, &lagtab, &pl_rank, &pl_tl, &pl_prog})
-      b->release();
-    stage.release(); h_stage.release(); h_stage2.release(); h_out.release(); h_async_info.release(); up_blob.release(); up_blob2.release(); h_pl.release();
+    for_each_dev([](DevBuf& b) { b.release(); });
+    h_stage.release(); h_stage2.release(); h_out.release(); h_async_info.release(); h_pl.release();
     for (auto e : events) (void)hipEventDestroy(e);
     events.clear();
     for (auto& q : gq) { if (q) (void)hipStreamDestroy(q); q = nullptr; }
@@ -267,6 +325,7 @@ struct agp_ctx {
   int flow = -1;        // dataflow schedule (whole factorisation in one launch of persistent workgroups): -1 auto, 0, 1; env AGP_FLOW
   long long* d_flow_trace = nullptr;   // agp_debug_flow_trace: 8 x int64 per work item of the next dataflow sweep
   size_t flow_trace_items = 0;
+  PoisonCtl poison;     // NaN-poison mode (checking switch, env AGP_POISON; see Fill)
   int fuse_mode = -1;   // -1 auto (fuse when the batch has >= 256 particles), 0 never, 1 always; env AGP_FUSE
   double timing[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};    // [8..11]: gradient sweep: L^-T chain, K^-1 tiles, contraction, alpha + reduction
   std::vector<double> upd_ms, trsm_ms;   // per-launch durations of the last profiled call
@@ -298,10 +357,12 @@ struct agp_ctx {
     int nt_cap = 0;                     // tile rows a slot can hold
     std::atomic<int> n_slots{0};        // (read without the lock by the gates of the structured sweeps)
     long long strideA = 0;              // doubles per slot
-    DevBuf A, W, vec, partial, info, ready, tflag, flowq;
+    // factors (values); LAPACK info, published block columns, dataflow flags and queue counter (never)
+    DevBuf A{Fill::values}, W{Fill::values}, vec{Fill::values}, partial{Fill::values};
+    DevBuf info{Fill::never}, ready{Fill::never}, tflag{Fill::never}, flowq{Fill::never};
     // L^-T of the resident factors, kept by the predictive passes that start from them (allocated on their first use): Z in A's layout,
     // the rows' running alpha = Z beta and diag(K^-1), and how many tile columns of Z each slot holds (<= its factor's tile rows)
-    DevBuf Z, zalpha, zdinv;
+    DevBuf Z{Fill::values}, zalpha{Fill::values}, zdinv{Fill::values};
     std::vector<int32_t> zrows;
     void z_release() { Z.release(); zalpha.release(); zdinv.release(); std::fill(zrows.begin(), zrows.end(), 0); }
     std::vector<std::string> key;       // per slot; empty = free
@@ -331,6 +392,7 @@ struct agp_ctx {
     std::unordered_map<std::string, int> index;
     uint64_t clock = 0;
     int64_t hits = 0, misses = 0, tile_rows_reused = 0, tile_rows_total = 0;
+    int64_t growth_copies = 0;          // resizes that copied resident factors into the new allocation (agp_extend_stats2)
     double max_frac = 0.45;             // share of the device memory the store may take
     std::atomic<size_t> footprint{0};   // bytes the store holds right now (read by ws_limit_bytes without the lock)
     size_t failed_bytes = 0;            // size of the last (re)allocation that failed: not retried at that size or above
@@ -342,7 +404,7 @@ struct agp_ctx {
   int comm_rank = 0, comm_size = 1;
   hipStream_t comm_stream = nullptr;
   std::mutex comm_mu;                   // one collective at a time per context
-  DevBuf comm_in, comm_out, comm_all;   // padded shard, padded gather, compact vector
+  DevBuf comm_in{Fill::values}, comm_out{Fill::values}, comm_all{Fill::values};   // padded shard, padded gather, compact vector (log-weights)
   // ---- asynchronous device-output calls (agp_logpdf_batch_device on a caller stream) return before their kernels ran: a
   //      negative info word (the bounded in-kernel wait gave up) is latched here when the slot is next claimed and
   //      reported by the next device-output call / agp_wait ----

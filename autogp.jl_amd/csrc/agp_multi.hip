@@ -277,8 +277,8 @@ int agp_debug_compact_shards(agp_ctx* c, const double* padded, int32_t P, int32_
   HIPCHK(c, hipSetDevice(c->device));
   const int mx = (P + n_ranks - 1) / n_ranks;
   double *d_in = nullptr, *d_out = nullptr;
-  HIPCHK(c, hipMalloc((void**)&d_in, sizeof(double) * (size_t)mx * n_ranks));
-  HIPCHK(c, hipMalloc((void**)&d_out, sizeof(double) * (size_t)P));
+  HIPCHK(c, malloc_values(c->poison, (void**)&d_in, sizeof(double) * (size_t)mx * n_ranks));
+  HIPCHK(c, malloc_values(c->poison, (void**)&d_out, sizeof(double) * (size_t)P));
   HIPCHK(c, hipMemcpy(d_in, padded, sizeof(double) * (size_t)mx * n_ranks, hipMemcpyHostToDevice));
   launch_compact_shards(0, d_in, mx, P, n_ranks, d_out);
   HIPCHK(c, hipGetLastError());

@@ -336,6 +336,8 @@ int predict_core(agp_ctx* c, int64_t n, const double* ts_pred, int64_t m, int32_
       launch_flow(dcov, 2 * c->n_cu, st, ca);
       HIPCHK(c, hipGetLastError());
     } else if (n_hit > 0) {
+      // (invariant of every branch here: only the training block's nt1 columns are factored, so the diagonal-tile kernel sees
+      // tiles with n1 - tk * NB > 0 rows of data; the query rows below them are panel solves, never a diagonal step)
       // per-column launches restricted to the rows some particle still has to compute
       int i0min = nt1;
       for (int q = 0; q < Pc; ++q) i0min = std::min(i0min, (int)i0v[(size_t)p0 + q]);
@@ -358,6 +360,24 @@ int predict_core(agp_ctx* c, int64_t n, const double* ts_pred, int64_t m, int32_
       }
       // (the kernel advances the slots' running sums on the device; their column counts are committed on the host only after the
       // LAST chunk: any return in between must not leave sums that already include columns the host does not know of)
+      if (zstore && c->poison.active()) {
+        // NaN-poison mode: what the chain forms again — tile columns >= zi0 of the entry's Z (column i of Z is packed row i) and the
+        // running sums of rows >= zi0 (rows below it start from theirs) — reads NaN until written.  Copies (zi0 < 0) are skipped.
+        agp_ctx::FactorStore& fs = c->store;
+        PoisonRowsArgs pa = {};
+        double* bases[3] = {fs.Z.as<double>(), fs.zalpha.as<double>(), fs.zdinv.as<double>()};
+        const long long pitch[3] = {fs.strideA, (long long)fs.nt_cap * NB, (long long)fs.nt_cap * NB};
+        const long long unit[3] = {NB2, NB, NB};
+        for (int b = 0; b < 3; ++b) { pa.base[b] = bases[b]; pa.pitch[b] = pitch[b]; pa.unit[b] = unit[b]; pa.tri[b] = b == 0; }
+        pa.nt_cap = fs.nt_cap; pa.slot = d_src + p0; pa.i0 = d_zi0 + p0;
+        launch_poison_rows(st, 256, Pc, 3, pa);
+        HIPCHK(c, hipGetLastError());
+        for (int q = p0; q < p0 + Pc; ++q) {
+          if (src_slot[(size_t)q] < 0 || zi0v[(size_t)q] < 0) continue;
+          const long long r0 = std::min<long long>(zi0v[(size_t)q], fs.nt_cap);
+          c->poison.count(sizeof(double) * (size_t)((fs.strideA - r0 * (r0 + 1) / 2 * NB2) + 2 * (fs.nt_cap - r0) * NB));
+        }
+      }
       if (zstore) zguard.armed = true;
       launch_trtri_chain(st, 8 * ((Pc + 7) / 8) * nt1, ga);
       if (zstore && p0 + chunk >= P) {
@@ -988,7 +1008,7 @@ int agp_debug_mfma_peak(agp_ctx* c, int32_t iters, int32_t wg_per_cu, double* ou
   wg_per_cu &= 255;
   const int nblk = prop.multiProcessorCount * (wg_per_cu > 0 ? wg_per_cu : 2);
   double* d_out = nullptr; long long* d_cyc = nullptr;
-  HIPCHK(c, hipMalloc((void**)&d_out, sizeof(double) * 256 * (size_t)nblk));
+  HIPCHK(c, malloc_values(c->poison, (void**)&d_out, sizeof(double) * 256 * (size_t)nblk));
   HIPCHK(c, hipMalloc((void**)&d_cyc, sizeof(long long) * (size_t)nblk));
   hipEvent_t e0, e1;
   HIPCHK(c, hipEventCreate(&e0)); HIPCHK(c, hipEventCreate(&e1));
@@ -1148,9 +1168,9 @@ int agp_debug_math(agp_ctx* c, int32_t which, const double* x, const double* g, 
   if (!c || !x || !y || n <= 0 || (which == 3 && !g)) return fail(c, AGP_ERR_ARG, "bad arguments");
   HIPCHK(c, hipSetDevice(c->device));
   double *dx = nullptr, *dg = nullptr, *dy = nullptr;
-  HIPCHK(c, hipMalloc((void**)&dx, sizeof(double) * n));
-  HIPCHK(c, hipMalloc((void**)&dg, sizeof(double) * n));
-  HIPCHK(c, hipMalloc((void**)&dy, sizeof(double) * n));
+  HIPCHK(c, malloc_values(c->poison, (void**)&dx, sizeof(double) * n));
+  HIPCHK(c, malloc_values(c->poison, (void**)&dg, sizeof(double) * n));
+  HIPCHK(c, malloc_values(c->poison, (void**)&dy, sizeof(double) * n));
   HIPCHK(c, hipMemcpy(dx, x, sizeof(double) * n, hipMemcpyHostToDevice));
   if (g) HIPCHK(c, hipMemcpy(dg, g, sizeof(double) * n, hipMemcpyHostToDevice));
   launch_math_probe(which, dx, dg, dy, n);
@@ -1164,9 +1184,9 @@ int agp_debug_mfma_probe(agp_ctx* c, const double* A, const double* B, double* D
   if (!c || !A || !B || !D) return fail(c, AGP_ERR_ARG, "null pointer");
   HIPCHK(c, hipSetDevice(c->device));
   double *dA = nullptr, *dB = nullptr, *dD = nullptr;
-  HIPCHK(c, hipMalloc((void**)&dA, 64 * 8));
-  HIPCHK(c, hipMalloc((void**)&dB, 64 * 8));
-  HIPCHK(c, hipMalloc((void**)&dD, 256 * 8));
+  HIPCHK(c, malloc_values(c->poison, (void**)&dA, 64 * 8));
+  HIPCHK(c, malloc_values(c->poison, (void**)&dB, 64 * 8));
+  HIPCHK(c, malloc_values(c->poison, (void**)&dD, 256 * 8));
   HIPCHK(c, hipMemcpy(dA, A, 64 * 8, hipMemcpyHostToDevice));
   HIPCHK(c, hipMemcpy(dB, B, 64 * 8, hipMemcpyHostToDevice));
   launch_mfma_probe(dA, dB, dD);

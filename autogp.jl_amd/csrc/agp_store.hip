@@ -34,7 +34,9 @@ int store_resize(agp_ctx* c, int nt_cap, int n_slots) {
   // (an allocation of this size already failed: do not retry the multi-GB allocations and copies on every call —
   // agp_extend_reset / agp_set_data on another series clear the memo)
   if (fs.failed_bytes && want_bytes >= fs.failed_bytes) return fail(c, AGP_ERR_HIP, "factor store: an allocation of this size failed before");
-  DevBuf A, W, vec, partial, info, ready;
+  // (a fresh allocation is poisoned in AGP_POISON mode before the resident prefix is copied in: the remainder of each slot reads NaN)
+  DevBuf A(Fill::values, &c->poison), W(Fill::values, &c->poison), vec(Fill::values, &c->poison), partial(Fill::values, &c->poison);
+  DevBuf info(Fill::never, &c->poison), ready(Fill::never, &c->poison);
   // (a failed (re)allocation leaves the store as it was: the caller then runs without caching)
   auto bail = [&](hipError_t e, const char* what) {
     A.release(); W.release(); vec.release(); partial.release(); info.release(); ready.release();
@@ -67,6 +69,7 @@ int store_resize(agp_ctx* c, int nt_cap, int n_slots) {
     STORECHK(cp(partial, (size_t)nt_cap * 16, fs.partial, (size_t)fs.nt_cap * 16, (size_t)nto * 16));
     STORECHK(hipMemcpy(info.p, fs.info.p, sizeof(int) * (size_t)keep, hipMemcpyDeviceToDevice));
     STORECHK(hipDeviceSynchronize());
+    if (std::any_of(fs.key.begin(), fs.key.begin() + keep, [](const std::string& k) { return !k.empty(); })) ++fs.growth_copies;
   }
 #undef STORECHK
   fs.A.release(); fs.W.release(); fs.vec.release(); fs.partial.release(); fs.info.release(); fs.ready.release();
@@ -249,7 +252,7 @@ int extend_impl(agp_ctx* c, int64_t n, int32_t P, const int32_t* op_off, const u
   // (the slot's running row sums cover exactly zrows columns: fewer surviving rows of L than that and the resident Z starts over)
   for (int u = 0; u < U; ++u) if (i0[u] < fs.zrows[(size_t)slot[u]]) fs.zrows[(size_t)slot[u]] = 0;
   // from here on the touched slots are in flux: forget them on any failure
-  auto poison = [&]() {
+  auto forget_touched = [&]() {
     for (int u = 0; u < U; ++u) {
       const int sl = slot[u];
       if (!fs.key[sl].empty()) fs.index.erase(fs.key[sl]);
@@ -289,7 +292,7 @@ int extend_impl(agp_ctx* c, int64_t n, int32_t P, const int32_t* op_off, const u
   int rc = compile_batch(c, U, uo.data(), uops.data(), up.data(), uprm.data(), bt, false, false, ge_tab, /*fuse_hint=*/true,
                          /*flow_limit=*/c->flow != 0 && U <= FLOW_MAX_PARTICLES, rankm, rankm ? tab_units : 1, rank_extra,
                          /*never_fuse=*/small_series);
-  if (rc) { poison(); return rc; }
+  if (rc) { forget_touched(); return rc; }
   if (cltw) { std::lock_guard<std::mutex> g(c->mu); ++c->n_clt_sweeps; }
   int i0min = nt;
   for (int u = 0; u < U; ++u) i0min = std::min(i0min, (int)i0[u]);
@@ -314,7 +317,7 @@ int extend_impl(agp_ctx* c, int64_t n, int32_t P, const int32_t* op_off, const u
   const size_t o_tops = al16(o_tprm + sizeof(double) * bt.tprm.size());
   const size_t stage_bytes = al16(o_tops + bt.tops.size() + 4);
   auto hipfail = [&](hipError_t e, const char* what) {
-    poison();
+    forget_touched();
     return fail(c, AGP_ERR_HIP, std::string("HIP error in the extension sweep (") + what + "): " + hipGetErrorString(e));
   };
 #define EXTCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return hipfail(e_, #expr); } while (0)
@@ -360,6 +363,22 @@ int extend_impl(agp_ctx* c, int64_t n, int32_t P, const int32_t* op_off, const u
       launch_lag_tables(st, la, tab_gstride / 256, bt.n_lag_tables);
       EXTCHK(hipGetLastError());
     }
+    if (c->poison.active()) {
+      // NaN-poison mode: the tile rows this sweep recomputes (>= i0; a from-scratch entry: the whole slot) read NaN until written.
+      // (The resident L^-T of the predictive passes, zrows, is poisoned by the pass that extends it: agp_predict.hip.)
+      PoisonRowsArgs pa = {};
+      double* bases[4] = {fs.A.as<double>(), fs.W.as<double>(), fs.vec.as<double>(), fs.partial.as<double>()};
+      const long long pitch[4] = {fs.strideA, (long long)fs.nt_cap * NSB * 256, (long long)fs.nt_cap * NB, 2LL * fs.nt_cap};
+      const long long unit[4] = {NB2, NSB * 256, NB, 2};
+      for (int b = 0; b < 4; ++b) { pa.base[b] = bases[b]; pa.pitch[b] = pitch[b]; pa.unit[b] = unit[b]; pa.tri[b] = b == 0; }
+      pa.nt_cap = fs.nt_cap; pa.slot = d_slot; pa.i0 = d_i0;
+      launch_poison_rows(st, 256, U, 4, pa);
+      EXTCHK(hipGetLastError());
+      for (int u = 0; u < U; ++u) {
+        const long long r0 = std::min<long long>(i0[u], fs.nt_cap);
+        c->poison.count(sizeof(double) * (size_t)((fs.strideA - r0 * (r0 + 1) / 2 * NB2) + (fs.nt_cap - r0) * (NSB * 256LL + NB + 2)));
+      }
+    }
     launch_init_extend(st, U, fs.vec.as<double>(), fs.nt_cap * NB, n_pad, c->d_xs, (int)n, d_slot, d_i0, fs.info.as<int>(), fs.ready.as<int>());
     CovArgs cv = {};
     cv.tt = c->d_ts; cv.n1 = (int)n; cv.n1_pad = n_pad; cv.m2 = 0; cv.nt = nt;
@@ -380,6 +399,7 @@ int extend_impl(agp_ctx* c, int64_t n, int32_t P, const int32_t* op_off, const u
     set_cov(ca, cv);
     ca.lag = rankm ? 1 : 0;
     ca.n_fused = nf; ca.slot = d_slot; ca.i0 = d_i0;
+    // (ca.nt = ceil(n / NB) tile rows, all of them data: every diagonal tile the kernels factor holds n - tk * NB > 0 rows)
     // an extension touches every block column (the new rows' tiles of the old columns, then the new columns): one
     // dataflow launch instead of nt small per-column launches, whatever the amount of work
     if (c->flow > 0 || (c->flow < 0 && U <= FLOW_MAX_PARTICLES && (nt >= 3 || use_flow(c, U, nt)))) {
@@ -411,7 +431,7 @@ int extend_impl(agp_ctx* c, int64_t n, int32_t P, const int32_t* op_off, const u
   const double* hl = static_cast<const double*>(s->h_out.p);
   const int32_t* hinfo = reinterpret_cast<const int32_t*>(hl + U);
   for (int u = 0; u < U; ++u)
-    if (hinfo[u] < 0) { poison(); return fail(c, AGP_ERR_HIP, "in-kernel panel solve timed out waiting for its diagonal factor"); }
+    if (hinfo[u] < 0) { forget_touched(); return fail(c, AGP_ERR_HIP, "in-kernel panel solve timed out waiting for its diagonal factor"); }
   for (int u = 0; u < U; ++u) {
     const int sl = slot[u];
     fs.key[sl] = keys[u]; fs.index[keys[u]] = sl; fs.n_cached[sl] = n; fs.info_h[sl] = hinfo[u];
@@ -466,15 +486,16 @@ int agp_extend_stats(agp_ctx* c, int64_t* out4) {
 
 int agp_extend_stats2(agp_ctx* c, int64_t* out, int32_t n_out) {
   if (!c || !out || n_out < 0) return fail(c, AGP_ERR_ARG, "null pointer");
-  int64_t v[8];
+  int64_t v[10];
   {
     std::lock_guard<std::mutex> g(c->store.mu);
     v[0] = c->store.hits; v[1] = c->store.misses; v[2] = c->store.tile_rows_reused; v[3] = c->store.tile_rows_total;
     v[4] = c->store.evicted_before_reuse; v[5] = c->store.n_slots.load(); v[6] = c->n_callers.load();
     v[7] = 0;
     for (const std::string& k : c->store.key) v[7] += k.empty() ? 0 : 1;
+    v[8] = c->store.nt_cap; v[9] = c->store.growth_copies;
   }
-  for (int i = 0; i < n_out && i < 8; ++i) out[i] = v[i];
+  for (int i = 0; i < n_out && i < 10; ++i) out[i] = v[i];
   return AGP_OK;
 }
 
@@ -518,6 +539,13 @@ int agp_get_compact_stats(agp_ctx* c, int32_t* lags_per_ordinal, int64_t* table_
   if (lags_per_ordinal) *lags_per_ordinal = on ? c->clt_W : 0;
   if (table_entries) *table_entries = on ? (int64_t)c->clt_W * c->n_max : 0;
   if (n_sweeps) *n_sweeps = c->n_clt_sweeps;
+  return AGP_OK;
+}
+
+int agp_get_poison_stats(agp_ctx* c, int64_t* bytes, int64_t* fills) {
+  if (!c) return fail(nullptr, AGP_ERR_ARG, "null context");
+  if (bytes) *bytes = c->poison.bytes.load();
+  if (fills) *fills = c->poison.fills.load();
   return AGP_OK;
 }
 

@@ -31,7 +31,7 @@ EXPORTED_SYMBOLS = [
     "agp_shard_range", "agp_comm_get_unique_id", "agp_comm_init_rank", "agp_comm_info", "agp_init_multi", "agp_set_data_multi",
     "agp_allgather_logweights", "agp_allgather_logweights_device", "agp_logpdf_batch_multi", "agp_logpdf_batch_extend_multi",
     "agp_debug_compact_shards", "agp_logpdf_batch_extend", "agp_extend_stats", "agp_extend_reset", "agp_extend_reserve",
-    "agp_predict_reuse_stats", "agp_grad_reuse_stats", "agp_set_factor_cache", "agp_wait", "agp_comm_count", "agp_get_lag_stats", "agp_get_lattice_stats", "agp_get_compact_stats", "agp_set_lattice", "agp_probe_lattice", "agp_set_reference_arithmetic", "agp_shard_plan", "agp_get_coalesce_timing", "agp_set_lag_tables", "agp_set_grad_lag_domain", "agp_get_grad_lag_domain_stats", "agp_get_grad_toeplitz_stats", "agp_get_grad_structured_stats", "agp_get_predict_structured_stats", "agp_get_toeplitz_stats", "agp_set_lag_rank_tables", "agp_get_lag_rank_stats", "agp_get_lag_predict_stats",
+    "agp_predict_reuse_stats", "agp_grad_reuse_stats", "agp_set_factor_cache", "agp_wait", "agp_comm_count", "agp_get_lag_stats", "agp_get_lattice_stats", "agp_get_compact_stats", "agp_set_lattice", "agp_probe_lattice", "agp_set_reference_arithmetic", "agp_shard_plan", "agp_get_coalesce_timing", "agp_set_lag_tables", "agp_set_grad_lag_domain", "agp_get_grad_lag_domain_stats", "agp_get_grad_toeplitz_stats", "agp_get_grad_structured_stats", "agp_get_predict_structured_stats", "agp_get_toeplitz_stats", "agp_set_lag_rank_tables", "agp_get_lag_rank_stats", "agp_get_lag_predict_stats", "agp_get_poison_stats",
     "agp_logpdf_grad_batch_multi", "agp_predict_batch_multi", "agp_extend_stats2",
 ]
 COMM_ID_BYTES = 128
@@ -149,6 +149,7 @@ def load_library(path=None):
     lib.agp_get_lattice_stats.argtypes = [vp, i32p, C.POINTER(C.c_int64), C.POINTER(C.c_double)]; lib.agp_get_lattice_stats.restype = C.c_int
     lib.agp_get_compact_stats.argtypes = [vp, i32p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]; lib.agp_get_compact_stats.restype = C.c_int
     lib.agp_set_lattice.argtypes = [vp, C.c_int32]; lib.agp_set_lattice.restype = C.c_int
+    lib.agp_get_poison_stats.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]; lib.agp_get_poison_stats.restype = C.c_int
     lib.agp_set_reference_arithmetic.argtypes = [vp, C.c_int32]; lib.agp_set_reference_arithmetic.restype = C.c_int
     lib.agp_probe_lattice.argtypes = [dp, C.c_int64, i32p, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_int64)]; lib.agp_probe_lattice.restype = C.c_int
     lib.agp_set_grad_lag_domain.argtypes = [vp, C.c_int32]; lib.agp_set_grad_lag_domain.restype = C.c_int
@@ -342,12 +343,12 @@ class GPEngine:
         return out, info
 
     def extend_stats(self):
-        """dict(extended, from_scratch, tile_rows_reused, tile_rows_total, evicted_before_reuse, slots, callers, occupied)
-        (agp_extend_stats2)."""
-        out = (C.c_int64 * 8)()
-        self._check(self._lib.agp_extend_stats2(self._ctx, out, 8))
-        return dict(zip(("extended", "from_scratch", "tile_rows_reused", "tile_rows_total", "evicted_before_reuse", "slots", "callers", "occupied"),
-                        [int(v) for v in out]))
+        """dict(extended, from_scratch, tile_rows_reused, tile_rows_total, evicted_before_reuse, slots, callers, occupied,
+        capacity_tile_rows, growth_copies) (agp_extend_stats2)."""
+        out = (C.c_int64 * 10)()
+        self._check(self._lib.agp_extend_stats2(self._ctx, out, 10))
+        return dict(zip(("extended", "from_scratch", "tile_rows_reused", "tile_rows_total", "evicted_before_reuse", "slots", "callers", "occupied",
+                         "capacity_tile_rows", "growth_copies"), [int(v) for v in out]))
 
     def predict_reuse_stats(self):
         """dict(reused, factored): particles a predictive pass served from a resident factor / factored itself."""
@@ -379,6 +380,12 @@ class GPEngine:
         w = C.c_int32(); e = C.c_int64(); k = C.c_int64()
         self._check(self._lib.agp_get_compact_stats(self._ctx, C.byref(w), C.byref(e), C.byref(k)))
         return {"lags_per_ordinal": int(w.value), "table_entries": int(e.value), "sweeps": int(k.value)}
+
+    def poison_stats(self):
+        """dict(bytes, fills): device / pinned memory this context filled with NaN bits so far (AGP_POISON=1 at construction)."""
+        b = C.c_int64(); f = C.c_int64()
+        self._check(self._lib.agp_get_poison_stats(self._ctx, C.byref(b), C.byref(f)))
+        return {"bytes": int(b.value), "fills": int(f.value)}
 
     def set_lattice(self, on):
         """Admit lattices with gaps at the next set_data (off: regular grids only)."""

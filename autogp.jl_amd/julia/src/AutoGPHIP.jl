@@ -176,12 +176,13 @@ end
 
 "(particles a predictive call served from a resident factor, particles whose K11 it factored itself): after
 `logpdf_batch(...; extend=true)` on a prefix, `predict_marginal` / `predict_mvn` on the same prefix reuse L11 and alpha."
-"(extended, from_scratch, tile_rows_reused, tile_rows_total, evicted_before_reuse, slots, callers, occupied) of the factor store"
+"(extended, from_scratch, tile_rows_reused, tile_rows_total, evicted_before_reuse, slots, callers, occupied, capacity_tile_rows, growth_copies) of the factor store"
 function extend_stats(eng::Engine)
-    out = zeros(Int64, 8)
-    GC.@preserve out check(eng, ccall((:agp_extend_stats2, LIB), Cint, (Ptr{Cvoid}, Ptr{Int64}, Int32), eng.ptr, out, 8))
+    out = zeros(Int64, 10)
+    GC.@preserve out check(eng, ccall((:agp_extend_stats2, LIB), Cint, (Ptr{Cvoid}, Ptr{Int64}, Int32), eng.ptr, out, 10))
     return (extended = out[1], from_scratch = out[2], tile_rows_reused = out[3], tile_rows_total = out[4],
-            evicted_before_reuse = out[5], slots = out[6], callers = out[7], occupied = out[8])
+            evicted_before_reuse = out[5], slots = out[6], callers = out[7], occupied = out[8],
+            capacity_tile_rows = out[9], growth_copies = out[10])
 end
 
 function predict_reuse_stats(eng::Engine)
@@ -426,6 +427,12 @@ function compact_stats(eng::Engine)
     w = Ref{Int32}(0); ne = Ref{Int64}(0); ns = Ref{Int64}(0)
     check(eng, ccall((:agp_get_compact_stats, LIB), Cint, (Ptr{Cvoid}, Ref{Int32}, Ref{Int64}, Ref{Int64}), eng.ptr, w, ne, ns))
     return (lags_per_ordinal = Int(w[]), table_entries = Int(ne[]), sweeps = Int(ns[]))
+end
+"(bytes, fills): memory the engine filled with NaN bits so far (checking mode AGP_POISON=1; results are unchanged by it)"
+function poison_stats(eng::Engine)
+    b = Ref{Int64}(0); f = Ref{Int64}(0)
+    check(eng, ccall((:agp_get_poison_stats, LIB), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}), eng.ptr, b, f))
+    return (bytes = Int(b[]), fills = Int(f[]))
 end
 "(kind, n_lattice, spacing) of the resident series: kind 0 irregular, 1 regular grid, 2 lattice with gaps (calendar indices), 3 a longer lattice served by compact tables"
 function lattice_stats(eng::Engine)

@@ -118,12 +118,13 @@ int agp_logpdf_batch_extend(agp_ctx* ctx, int64_t n, int32_t P,
 /* out4 = { particles extended from a resident factor, particles factored from scratch,
  *          tile rows reused, tile rows a from-scratch sweep would have computed } since agp_init / the last reset */
 int agp_extend_stats(agp_ctx* ctx, int64_t* out4);
-/* The same and more, up to n_out <= 8 values: out[0..3] as agp_extend_stats; out[4] = evicted_before_reuse — lookups (extension,
+/* The same and more, up to n_out <= 10 values: out[0..3] as agp_extend_stats; out[4] = evicted_before_reuse — lookups (extension,
  * gradient or predictive sweeps) whose factor HAD been resident and was dropped for room before anything started from it: the cliff
  * of a store too small for its population (the gradient call of a leapfrog step refactoring what the value call before it had just
  * computed).  0 in a healthy run; factors nobody comes back for (the last state of a move, rejected proposals) are not counted.  The
  * library remembers the last 8192 such keys.  out[5] = slots the store holds; out[6] = distinct threads seen by the single-particle
- * entries since the last agp_set_data of another series / agp_extend_reset; out[7] = occupied slots. */
+ * entries since the last agp_set_data of another series / agp_extend_reset; out[7] = occupied slots; out[8] = tile rows a slot can
+ * hold; out[9] = resizes that copied resident factors into the new allocation (since the context was created). */
 int agp_extend_stats2(agp_ctx* ctx, int64_t* out, int32_t n_out);
 /* forget every resident factor (release_memory != 0 also frees the store) */
 int agp_extend_reset(agp_ctx* ctx, int release_memory);
@@ -206,6 +207,12 @@ int agp_set_lag_tables(agp_ctx* ctx, int32_t on);
 int agp_get_lattice_stats(agp_ctx* ctx, int32_t* kind, int64_t* n_lattice, double* spacing);
 int agp_get_compact_stats(agp_ctx* ctx, int32_t* lags_per_ordinal, int64_t* table_entries, int64_t* n_sweeps);
 int agp_set_lattice(agp_ctx* ctx, int32_t on);
+/* NaN-poison mode (env AGP_POISON=1 at agp_init; per context; a checking switch, not a path: results are bit for bit those of a
+ * context without it).  Every fresh device allocation of floating-point values, every such workspace buffer when a call claims
+ * it and the factor-store rows an extension sweep recomputes are filled with byte 0xFF (NaN), so a kernel that reads memory its
+ * call has not written produces a NaN instead of a stale finite number.  Buffers holding addresses, indices, counts, times or
+ * flags are never poisoned.  bytes / fills: what has been poisoned so far on this context (0 / 0 when the mode is off). */
+int agp_get_poison_stats(agp_ctx* ctx, int64_t* bytes, int64_t* fills);
 /* The admission test alone, on n time points in any order (host code only: no context, no device): kind as above, the lattice's
  * length and spacing, and per point its lattice index (index_out, nullable; -1 when kind = 0). */
 int agp_probe_lattice(const double* ts, int64_t n, int32_t* kind, int64_t* n_lattice, double* spacing, int64_t* index_out);
