@@ -333,21 +333,23 @@ def effective_sample_size(log_weights):
 # test sizes only).  Parameters are the TRANSFORMED ones, ordered as in the postfix parameter array of
 # tree_to_program (ChangePoint contributes d/dlocation, d/dscale at its own position).
 # --------------------------------------------------------------------------
-def eval_cov_grad(tree, ts):
-    """Returns (K, [dK/dtheta_0, dK/dtheta_1, ...]) with theta in program-parameter order."""
+def eval_cov_grad(tree, ts, ts2=None):
+    """Returns (K, [dK/dtheta_0, dK/dtheta_1, ...]) with theta in program-parameter order.  With `ts2` the rectangular block
+    of rows `ts` and columns `ts2` (gp_logpdf_grad_scales walks large matrices a block of rows at a time)."""
     ts = np.asarray(ts, dtype=np.float64)
-    n = ts.shape[0]
+    ts2 = ts if ts2 is None else np.asarray(ts2, dtype=np.float64)
+    shape = (ts.shape[0], ts2.shape[0])
     tag = tree[0]
-    ta, tb = ts[:, None], ts[None, :]
+    ta, tb = ts[:, None], ts2[None, :]
     if tag == "WN":
         E = (ta == tb).astype(np.float64)
         return E * float(tree[1]), [E]
     if tag == "C":
-        return np.full((n, n), float(tree[1])), [np.ones((n, n))]
+        return np.full(shape, float(tree[1])), [np.ones(shape)]
     if tag == "LIN":
         c, b, a = float(tree[1]), float(tree[2]), float(tree[3])
         P = (ta - c) * (tb - c)
-        return b + a * P, [-a * (ta + tb - 2 * c), np.ones((n, n)), P]
+        return b + a * P, [-a * (ta + tb - 2 * c), np.ones(shape), P]
     if tag == "SE":
         l, a = float(tree[1]), float(tree[2])
         d2 = (ta - tb) ** 2
@@ -364,30 +366,35 @@ def eval_cov_grad(tree, ts):
     if tag == "PER":
         l, p, a = float(tree[1]), float(tree[2]), float(tree[3])
         d = np.abs(ta - tb)
-        s, c = np.sin(np.pi * d / p), np.cos(np.pi * d / p)
+        freq = math.pi / p              # the argument rounded as the reference forms it, sin(freq * dx) (src/GP.jl:331-336)
+        s, c = np.sin(freq * d), np.cos(freq * d)
         e = np.exp(-2 * s * s / l ** 2)
         return a * e, [a * e * 4 * s * s / l ** 3, a * e * 4 * s * c * np.pi * d / (l ** 2 * p ** 2), e]
     if tag == "+":
-        Kl, Gl = eval_cov_grad(tree[1], ts); Kr, Gr = eval_cov_grad(tree[2], ts)
+        Kl, Gl = eval_cov_grad(tree[1], ts, ts2); Kr, Gr = eval_cov_grad(tree[2], ts, ts2)
         return Kl + Kr, Gl + Gr
     if tag == "*":
-        Kl, Gl = eval_cov_grad(tree[1], ts); Kr, Gr = eval_cov_grad(tree[2], ts)
+        Kl, Gl = eval_cov_grad(tree[1], ts, ts2); Kr, Gr = eval_cov_grad(tree[2], ts, ts2)
         return Kl * Kr, [g * Kr for g in Gl] + [g * Kl for g in Gr]
     if tag == "CP":
         loc, sc = float(tree[3]), float(tree[4])
-        Kl, Gl = eval_cov_grad(tree[1], ts); Kr, Gr = eval_cov_grad(tree[2], ts)
-        z = (loc - ts) / sc
-        sg = 0.5 * (1 + np.tanh(z))
-        dsg_dloc = 0.5 * (1 - np.tanh(z) ** 2) / sc
-        dsg_dsc = -dsg_dloc * (loc - ts) / sc
-        S1 = sg[:, None] * sg[None, :]; S2 = (1 - sg)[:, None] * (1 - sg)[None, :]
+        Kl, Gl = eval_cov_grad(tree[1], ts, ts2); Kr, Gr = eval_cov_grad(tree[2], ts, ts2)
+
+        def sig(t):
+            z = (loc - t) / sc
+            sg = 0.5 * (1 + np.tanh(z))
+            dsg_dloc = 0.5 * (1 - np.tanh(z) ** 2) / sc
+            return sg, dsg_dloc, -dsg_dloc * (loc - t) / sc
+        sa, dla, dsa = sig(ts)
+        sb, dlb, dsb = (sa, dla, dsa) if ts2 is ts else sig(ts2)
+        S1 = sa[:, None] * sb[None, :]; S2 = (1 - sa)[:, None] * (1 - sb)[None, :]
         K = S1 * Kl + S2 * Kr
 
-        def dS(dv):
-            d1 = dv[:, None] * sg[None, :] + sg[:, None] * dv[None, :]
-            d2 = -dv[:, None] * (1 - sg)[None, :] - (1 - sg)[:, None] * dv[None, :]
+        def dS(da, db):
+            d1 = da[:, None] * sb[None, :] + sa[:, None] * db[None, :]
+            d2 = -da[:, None] * (1 - sb)[None, :] - (1 - sa)[:, None] * db[None, :]
             return d1 * Kl + d2 * Kr
-        return K, [S1 * g for g in Gl] + [S2 * g for g in Gr] + [dS(dsg_dloc), dS(dsg_dsc)]
+        return K, [S1 * g for g in Gl] + [S2 * g for g in Gr] + [dS(dla, dlb), dS(dsa, dsb)]
     raise ValueError(tag)
 
 
@@ -425,3 +432,45 @@ def gp_logpdf_grad_longdouble(tree, noise, ts, xs):
     alpha = Kinv @ xs.astype(np.longdouble)
     G = 0.5 * (np.outer(alpha, alpha) - Kinv)
     return (np.array([float(np.sum(G * dK.astype(np.longdouble))) for dK in dKs]), float(np.trace(G)))
+
+
+def gp_logpdf_grad_scales(tree, noise, ts, xs, block_elems=1 << 22):
+    """(logpdf, g, g_noise, S, S_noise): gp_logpdf_grad's gradient together with every component's natural error scale
+
+        S_k     = 1/2 sum_ab (|alpha_a alpha_b| + |K^-1_ab|) |dK_ab / dtheta_k|
+        S_noise = 1/2 sum_a  (alpha_a^2 + K^-1_aa),
+
+    the sum of the magnitudes of the terms that make up g_k (so |g_k| <= S_k): a computation that forms alpha and K^-1 to a few
+    units of rounding relative to their own entries errs by a small multiple of eps S_k in component k, whatever the size of the
+    particle's other components.  Same eval_cov_grad, same parameter order as gp_logpdf_grad; the contractions run over blocks of
+    rows of about `block_elems` matrix entries (large n: the derivative matrices are never all held at once)."""
+    ts = np.asarray(ts, dtype=np.float64); xs = np.asarray(xs, dtype=np.float64)
+    n = ts.shape[0]
+    ops, prm = tree_to_program(tree)
+    if n == 0:
+        z = np.zeros(prm.size)
+        return 0.0, z, 0.0, z.copy(), 0.0
+    rows = max(1, block_elems // n)
+    K = np.empty((n, n))
+    for r0 in range(0, n, rows):
+        K[r0:r0 + rows] = eval_cov_grad(tree, ts[r0:r0 + rows], ts)[0]
+    K[np.diag_indices(n)] += noise
+    cf = sla.cho_factor(K, lower=True, check_finite=False, overwrite_a=True)
+    alpha = sla.cho_solve(cf, xs)
+    Kinv = sla.cho_solve(cf, np.eye(n), overwrite_b=True)
+    lp = float(-0.5 * (n * math.log(2 * math.pi) + 2 * np.sum(np.log(np.diag(cf[0]))) + xs @ alpha))
+    del cf, K
+    g = np.zeros(prm.size); S = np.zeros(prm.size)
+    aa = np.abs(alpha)
+    for r0 in range(0, n, rows):
+        r1 = min(n, r0 + rows)
+        _, dKs = eval_cov_grad(tree, ts[r0:r1], ts)
+        Gb = 0.5 * (np.outer(alpha[r0:r1], alpha) - Kinv[r0:r1])
+        Ab = 0.5 * (np.outer(aa[r0:r1], aa) + np.abs(Kinv[r0:r1]))
+        for k, dK in enumerate(dKs):
+            g[k] += float(np.sum(Gb * dK))
+            S[k] += float(np.sum(Ab * np.abs(dK)))
+    dg = np.diag(Kinv)
+    gn = float(np.sum(0.5 * (alpha * alpha - dg)))
+    Sn = float(np.sum(0.5 * (alpha * alpha + np.abs(dg))))
+    return lp, g, gn, S, Sn

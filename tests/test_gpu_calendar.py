@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from oracle import fast as F
+from oracle import gradcheck as GC
 from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -162,6 +163,9 @@ def test_calendar_gradient(pkg, freq, n):
             assert abs(lp[i] - lpo) <= LP_TOL * max(1.0, abs(lpo))
             worst = max(worst, np.abs(grads[i] - go).max() / sc, abs(gn[i] - gno) / sc)
             assert np.abs(grads[i] - grads2[i]).max() <= 1e-8 * sc and abs(gn[i] - gn2[i]) <= 1e-8 * sc, i
+            ref = GC.reference(nodes[i].to_tuple(), float(noises[i]), ts, xs)
+            GC.assert_grad_components(grads[i], gn[i], ref, particle_wide=False, ctx=i)
+            GC.assert_grad_components(grads[i], gn[i], ref, against=(grads2[i], gn2[i]), particle_wide=False, ctx=i)
         assert worst <= GRAD_TOL, worst
         # a prefix in the caller's order (data annealing) bins the same lags
         m = (2 * n) // 3
@@ -172,6 +176,7 @@ def test_calendar_gradient(pkg, freq, n):
             lpo, go, gno = O.gp_logpdf_grad(nodes[i].to_tuple(), float(noises[i]), ts[:m], xs[:m])
             sc = max(1.0, np.abs(go).max(), abs(gno))
             assert np.abs(grads[i] - go).max() <= GRAD_TOL * sc and abs(gn[i] - gno) <= GRAD_TOL * sc, i
+            GC.assert_grad_components(grads[i], gn[i], GC.reference(nodes[i].to_tuple(), float(noises[i]), ts[:m], xs[:m]), ctx=i)
     finally:
         a.close(); b.close()
 

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 from oracle import fast as F
+from oracle import gradcheck as GC
 
 pytestmark = pytest.mark.gpu
 LP_TOL = 1e-8
@@ -378,8 +379,10 @@ def test_gradient_from_resident_factor(pkg, monkeypatch, env, n):
         # (on this regular grid the sweep that factors itself reads stationary subtrees from rank lag tables, the store's factors
         # come from the general path: the two agree to the rounding of t_i - t_j, 1e-10 as everywhere in test_gpu_lag.py)
         assert lp_err(got[0][:24][ok], base[0][ok]).max() <= 1e-10
+        refs = GC.references(nodes, noises, ts, xs)
         for i in np.flatnonzero(ok):
             assert grad_err(got[1][i], base[1][i]) <= 1e-9 and abs(got[2][i] - base[2][i]) <= 1e-9 * max(1.0, abs(base[2][i]))
+            GC.assert_grad_components(got[1][i], got[2][i], refs[i], against=(base[1][i], base[2][i]), particle_wide=False, ctx=i)
         assert got[0][25] == got[0][2] and np.array_equal(got[1][25], got[1][2])          # the duplicate
         for i in (0, 5, 17):
             if not ok[i]:
@@ -387,6 +390,7 @@ def test_gradient_from_resident_factor(pkg, monkeypatch, env, n):
             lp, g, gn = O.gp_logpdf_grad(nodes[i].to_tuple(), float(noises[i]), ts, xs)
             assert abs(got[0][i] - lp) <= LP_TOL * max(1.0, abs(lp))
             assert grad_err(got[1][i], np.asarray(g)) <= 1e-7 and abs(got[2][i] - gn) <= 1e-7 * max(1.0, abs(gn))
+            GC.assert_grad_components(got[1][i], got[2][i], refs[i], ctx=i)
     finally:
         e.close()
 
@@ -412,6 +416,9 @@ def test_single_particle_calls_use_the_store(pkg, monkeypatch):
         assert e.grad_reuse_stats() == {"reused": 1, "factored": 0} and e0.grad_reuse_stats()["reused"] == 0
         assert abs(ga[0] - gb[0]) <= 1e-11 * abs(gb[0]) and grad_err(np.asarray(ga[1]), np.asarray(gb[1])) <= 1e-9
         assert abs(ga[2] - gb[2]) <= 1e-9 * max(1.0, abs(gb[2]))
+        ref = GC.reference(k.to_tuple(), 0.06, ts, xs)
+        GC.assert_grad_components(ga[1], ga[2], ref, against=(gb[1], gb[2]), particle_wide=False)
+        GC.assert_grad_components(ga[1], ga[2], ref)
         tp = np.linspace(0, 1.2, 50)
         pa = e.predict_batch([k], [0.06], tp); pb = e0.predict_batch([k], [0.06], tp)
         assert e.predict_reuse_stats()["reused"] == 1

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from oracle import fast as F
+from oracle import gradcheck as GC
 
 pytestmark = pytest.mark.gpu
 LP_TOL = 1e-8
@@ -605,6 +606,9 @@ def test_gradient_lag_domain_vs_elementwise_and_oracle(pkg, monkeypatch, n_max, 
             lpo, go, gno = O.gp_logpdf_grad(k.to_tuple(), float(noises[i]), ts[:n], xs[:n])
             sc = max(1.0, np.abs(go).max(), abs(gno))
             assert np.abs(g[i] - go).max() <= 1e-7 * sc and abs(gn[i] - gno) <= 1e-7 * sc, (i, k, g[i], go)
+            ref = GC.reference(k.to_tuple(), float(noises[i]), ts[:n], xs[:n])
+            GC.assert_grad_components(g[i], gn[i], ref, ctx=(i, k))
+            GC.assert_grad_components(g[i], gn[i], ref, against=(g2[i], gn2[i]), particle_wide=False, ctx=(i, k))
     finally:
         eng.close()
 
@@ -656,9 +660,13 @@ def test_gradient_toeplitz_lag_sums(pkg, case):
             assert a.grad_reuse_stats()["reused"] > 0
         lp2, g2, gn2, info2 = b.logpdf_grad_batch(kernels, noises, n=n, check=False)
         assert np.array_equal(info, info2) and (info == 0).mean() >= 0.9
+        refs = GC.references(kernels, noises, ts[:n], xs[:n])
         for i in np.flatnonzero(info == 0):
             sc = max(1.0, np.abs(g2[i]).max(), abs(gn2[i]))
             assert np.abs(g[i] - g2[i]).max() <= 1e-9 * sc and abs(gn[i] - gn2[i]) <= 1e-9 * sc, (case, i, kernels[i], g[i], g2[i])
+            GC.assert_grad_components(g[i], gn[i], refs[i], against=(g2[i], gn2[i]), particle_wide=False, ctx=(case, i, kernels[i]))
+            # (every case against the oracle per component, population_2048 included; the particle-wide check where it was)
+            GC.assert_grad_components(g[i], gn[i], refs[i], particle_wide=oracle_check, ctx=(case, i, kernels[i]))
             if oracle_check:
                 lpo, go, gno = O.gp_logpdf_grad(kernels[i].to_tuple(), float(noises[i]), ts[:n], xs[:n])
                 sc = max(1.0, np.abs(go).max(), abs(gno))
@@ -717,7 +725,10 @@ def test_gradient_structured_sweep(pkg, monkeypatch, case):
         assert np.array_equal(info, info2)
         ok = info == 0
         assert lp_err(lp[ok], lp2[ok]).max() <= 1e-10
+        refs = GC.references(kernels, noises, ts[:n], xs[:n])
         for i in np.flatnonzero(ok):
+            GC.assert_grad_components(g[i], gn[i], refs[i], particle_wide=False, ctx=(case, i, kernels[i]))
+            GC.assert_grad_components(g[i], gn[i], refs[i], against=(g2[i], gn2[i]), particle_wide=False, ctx=(case, i, kernels[i]))
             sc = max(1.0, np.abs(g2[i]).max(), abs(gn2[i]))
             # (prior-sampled kernels at n = 2048 include periods / length scales of a few grid spacings: both contractions carry ~1e-8
             # there — tools/gpu_grad_toeplitz_check.py prints the population's worst case for every variant)
@@ -760,7 +771,11 @@ def test_gradient_lag_domain_population_and_switches(pkg, monkeypatch):
         lp3, g3, gn3, info3 = h.logpdf_grad_batch(nodes, noises, check=False)
         assert a.grad_lag_domain_particles() >= 40 and b.grad_lag_domain_particles() == 0 and h.grad_lag_domain_particles() >= 40
         assert np.array_equal(info, info2) and np.array_equal(info, info3)
+        refs = GC.references(nodes, noises, ts, xs)
         for i in np.flatnonzero(info == 0):
+            GC.assert_grad_components(g[i], gn[i], refs[i], particle_wide=False, ctx=(i, nodes[i]))
+            GC.assert_grad_components(g[i], gn[i], refs[i], against=(g2[i], gn2[i]), particle_wide=False, ctx=(i, nodes[i]))
+            GC.assert_grad_components(g3[i], gn3[i], refs[i], against=(g2[i], gn2[i]), particle_wide=False, ctx=(i, nodes[i]))
             sc = max(1.0, np.abs(g2[i]).max(), abs(gn2[i]))
             assert np.abs(g[i] - g2[i]).max() <= 1e-9 * sc and abs(gn[i] - gn2[i]) <= 1e-9 * sc, (i, nodes[i])
             assert np.abs(g3[i] - g2[i]).max() <= 1e-9 * sc and abs(gn3[i] - gn2[i]) <= 1e-9 * sc, (i, nodes[i])
@@ -802,9 +817,11 @@ def test_gradient_polynomial_class_above_2048_points(pkg, n_max):
         lp2, g2, gn2, info2 = b.logpdf_grad_batch(kernels, noises, check=False)
         assert np.array_equal(info, info2) and (info == 0).all()
         assert lp_err(lp, lp2).max() <= 1e-10
+        refs = GC.references(kernels, noises, ts, xs)
         for i in range(len(kernels)):
             sc = max(1.0, np.abs(g2[i]).max(), abs(gn2[i]))
             assert np.abs(g[i] - g2[i]).max() <= 1e-7 * sc and abs(gn[i] - gn2[i]) <= 1e-7 * sc, (n_max, i)
+            GC.assert_grad_components(g[i], gn[i], refs[i], against=(g2[i], gn2[i]), particle_wide=False, ctx=(n_max, i))
     finally:
         a.close(); b.close()
 
@@ -829,6 +846,7 @@ def test_class_aware_leapfrog_pairs(pkg, monkeypatch):
     try:
         ref.set_data(ts, xs)
         r_lp, r_g, r_gn, r_info = ref.logpdf_grad_batch(nodes, noises, check=False)
+        refs = GC.references(nodes, noises, ts, xs)
         eng.set_lag_tables(3)                    # ... and level 3 = level 2 whatever it is: the size heuristics are not under test
         eng.set_data(ts, xs)
         eng.extend_reserve(n, 2 * T)             # (Python threads arrive slowly: many small coalesced batches, the store must hold the population)
@@ -862,6 +880,7 @@ def test_class_aware_leapfrog_pairs(pkg, monkeypatch):
                 assert abs(vals[i] - r_lp[i]) <= 1e-10 * max(1.0, abs(r_lp[i])), i
                 assert abs(lp - r_lp[i]) <= 1e-10 * max(1.0, abs(r_lp[i])), i
                 assert (np.abs(g - r_g[i]).max() if len(g) else 0.0) <= 1e-7 * sc and abs(gn - r_gn[i]) <= 1e-7 * sc, i
+                GC.assert_grad_components(g, gn, refs[i], against=(r_g[i], r_gn[i]), particle_wide=False, ctx=i)
         for i in range(0, T, 23):
             if r_info[i] != 0:
                 continue
@@ -869,6 +888,7 @@ def test_class_aware_leapfrog_pairs(pkg, monkeypatch):
             sc = max(1.0, np.abs(go).max() if len(go) else 0.0, abs(gno))
             assert abs(grads[i][0] - lpo) <= LP_TOL * max(1.0, abs(lpo))
             assert (np.abs(grads[i][1] - go).max() if len(go) else 0.0) <= 1e-7 * sc and abs(grads[i][2] - gno) <= 1e-7 * sc
+            GC.assert_grad_components(grads[i][1], grads[i][2], refs[i], ctx=i)
         # The annealing prefixes fit_smc! runs its HMC moves on (src/inference_smc_anneal_data.jl:240-252): a series handed over in TIME
         # ORDER, a prefix of it — n consecutive grid points, so the class stays structured — and no agp_extend_reserve (the store sizes
         # itself by the callers).  Same counters: the class is never factored densely, nobody is factored twice.
@@ -876,6 +896,7 @@ def test_class_aware_leapfrog_pairs(pkg, monkeypatch):
         n_pre = 384
         ref.set_data(ts2, xs2); eng.extend_reset(release_memory=True); eng.set_data(ts2, xs2)
         p_lp, p_g, p_gn, p_info = ref.logpdf_grad_batch(nodes, noises, n=n_pre, check=False)
+        p_refs = GC.references(nodes, noises, ts2[:n_pre], xs2[:n_pre])
         k_t0, k_s0, g0 = eng.toeplitz_particles(), eng.grad_structured_particles(), eng.grad_reuse_stats()
         vals = phase(lambda nd, z, check: eng.logpdf(nd, z, n=n_pre, check=check))
         k_t1 = eng.toeplitz_particles()
@@ -894,5 +915,6 @@ def test_class_aware_leapfrog_pairs(pkg, monkeypatch):
             sc = max(1.0, np.abs(p_g[i]).max() if len(p_g[i]) else 0.0, abs(p_gn[i]))
             assert abs(vals[i] - p_lp[i]) <= 1e-10 * max(1.0, abs(p_lp[i])) and abs(lp - p_lp[i]) <= 1e-10 * max(1.0, abs(p_lp[i])), i
             assert (np.abs(g - p_g[i]).max() if len(g) else 0.0) <= 1e-7 * sc and abs(gn - p_gn[i]) <= 1e-7 * sc, i
+            GC.assert_grad_components(g, gn, p_refs[i], against=(p_g[i], p_gn[i]), particle_wide=False, ctx=i)
     finally:
         ref.close(); eng.close()

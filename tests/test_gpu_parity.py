@@ -14,6 +14,7 @@ import pytest
 import scipy.linalg as sla
 
 from conftest import to_tuple
+from oracle import gradcheck as GC
 from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -258,6 +259,9 @@ def test_gamma_exponential_table_path(pkg, engine, monkeypatch):
         direct.close()
 
 
+_REFS = {}       # oracle gradients (with their per-component scales) shared by the parametrisations of one test
+
+
 @pytest.mark.parametrize("env", [{"AGP_SPLIT_DIAG": "0"}, {"AGP_SPLIT_DIAG": "1"}, {"AGP_FUSE": "0"}, {"AGP_FUSE": "1"},
                                  {"AGP_DEDUP": "0", "AGP_GE_TABLE": "0"}, {"AGP_RIGHT_LOOKING": "0"}, {"AGP_RIGHT_LOOKING": "1"},
                                  {"AGP_SPLIT_DIAG": "0", "AGP_RIGHT_LOOKING": "0"}, {"AGP_FLOW": "0"}, {"AGP_FLOW": "1"},
@@ -286,10 +290,13 @@ def test_runtime_switches_agree_with_default(pkg, engine, monkeypatch, env):
             assert lp_err(a[ok], b[ok]).max() <= tol
         ga = engine.logpdf_grad_batch(nodes[:40], noises[:40], check=False)
         gb = other.logpdf_grad_batch(nodes[:40], noises[:40], check=False)
+        if "switches" not in _REFS:
+            _REFS["switches"] = GC.references(nodes[:40], noises[:40], ts, xs)
         for i in range(40):
             if ga[3][i] == 0:
                 sc = max(1.0, np.abs(ga[1][i]).max(), abs(ga[2][i]))
                 assert np.abs(ga[1][i] - gb[1][i]).max() <= 1e-9 * sc and abs(ga[2][i] - gb[2][i]) <= 1e-9 * sc
+                GC.assert_grad_components(ga[1][i], ga[2][i], _REFS["switches"][i], against=(gb[1][i], gb[2][i]), particle_wide=False, ctx=(env, i))
     finally:
         other.close()
 
@@ -412,21 +419,7 @@ def test_predictive_likelihood_identity_on_gpu(pkg, engine):
 
 
 GRAD_TOL = 1e-7     # |g_gpu - g_ref| <= GRAD_TOL * max(1, |g_ref|_inf): both sides form K^-1 in fp64
-
-
-def assert_grad_close(g, gn, go, gno, tree, noise, ts, xs, ctx, tol=GRAD_TOL):
-    """north_star's gradient bound: tol of the gradient's scale against the double-precision oracle.  Above it the 80-bit
-    arbiter (oracle.gp_logpdf_grad_longdouble) decides: the device may be no further from IT than tol, or than 4x the
-    double-precision oracle's own distance (both form K^-1 with an error of cond(K) eps)."""
-    sc = max(1.0, np.abs(go).max() if go.size else 0.0, abs(gno))
-    e = max(np.abs(g - go).max() if go.size else 0.0, abs(gn - gno)) / sc
-    if e <= tol:
-        return e
-    gl, gnl = O.gp_logpdf_grad_longdouble(tree, noise, ts, xs)
-    ed = max(np.abs(g - gl).max() if gl.size else 0.0, abs(gn - gnl)) / sc
-    eo = max(np.abs(go - gl).max() if gl.size else 0.0, abs(gno - gnl)) / sc
-    assert ed <= max(tol, 4.0 * eo), (ctx, e, ed, eo)
-    return ed
+# (and per component, |g_k - ref_k| <= GRAD_TOL * S_k with the 80-bit arbiter deciding misses: oracle/gradcheck.py)
 
 
 def test_logpdf_gradient(pkg, engine):
@@ -452,6 +445,7 @@ def test_logpdf_gradient(pkg, engine):
             assert g.shape == go.shape
             assert np.abs(g - go).max() <= GRAD_TOL * sc, (n, k, g, go)
             assert abs(gnz - gno) <= GRAD_TOL * sc, (n, k)
+            GC.assert_grad_components(g, gnz, GC.reference(k.to_tuple(), 0.2, ts, xs), ctx=(n, k))
     # prior-sampled population, P >= 256 (fused build + cost sorting + scatter back to caller order)
     ts, xs = pkg.prior.synthetic_series(256, seed=5, shuffle=True)
     nodes, noises = pkg.prior.sample_particles(np.random.default_rng(5), 260, max_depth=4, max_size=15)
@@ -462,7 +456,7 @@ def test_logpdf_gradient(pkg, engine):
             continue
         lpo, go, gno = O.gp_logpdf_grad(nodes[i].to_tuple(), float(noises[i]), ts, xs)
         assert abs(lp[i] - lpo) <= LP_TOL * max(1.0, abs(lpo))
-        assert_grad_close(grads[i], gn[i], go, gno, nodes[i].to_tuple(), float(noises[i]), ts, xs, (i, nodes[i]))
+        GC.assert_grad_components(grads[i], gn[i], GC.reference(nodes[i].to_tuple(), float(noises[i]), ts, xs), ctx=(i, nodes[i]))
     # n = 0: zero gradient
     lp, grads, gn, info = engine.logpdf_grad_batch(kernels[:3], [0.1] * 3, n=0)
     assert (lp == 0).all() and all((g == 0).all() for g in grads) and (gn == 0).all()
@@ -494,7 +488,7 @@ def test_logpdf_gradient_large_trees_and_chunks(pkg, engine):
     lp, grads, gn, info = engine.logpdf_grad_batch(kernels, noises)
     refs = [O.gp_logpdf_grad(k.to_tuple(), 0.3, ts, xs) for k in kernels]
     for k, g, gnz, (lpo, go, gno) in zip(kernels, grads, gn, refs):
-        assert_grad_close(g, gnz, go, gno, k.to_tuple(), 0.3, ts, xs, k)
+        GC.assert_grad_components(g, gnz, GC.reference(k.to_tuple(), 0.3, ts, xs), ctx=k)
     # chunked workspace: L + Z for two particles at a time (nt = 2 -> 3 tiles)
     engine.set_workspace_limit(2 * 2 * 3 * 128 * 128 * 8)
     try:
@@ -911,6 +905,7 @@ def test_reference_arithmetic_is_call_order_stable(pkg):
             sc = max(1.0, np.abs(go).max(), abs(gno))
             assert abs(lp6[i] - lpo) <= LP_TOL * max(1.0, abs(lpo))
             assert np.abs(grads[i] - go).max() <= GRAD_TOL * sc and abs(gn[i] - gno) <= GRAD_TOL * sc
+            GC.assert_grad_components(grads[i], gn[i], GC.reference(k.to_tuple(), float(z), ts, xs), ctx=(i, k))
             mu, cv = O.predict_mvn(k.to_tuple(), float(z), ts, xs, tq)
             assert np.abs(m6[i] - mu).max() <= 1e-8 * max(1.0, np.abs(mu).max())
             assert np.abs(v6[i] - np.diag(cv)).max() <= 1e-8 * max(1.0, np.abs(cv).max())

@@ -20,6 +20,7 @@ import numpy as np
 import pytest
 
 from oracle import fast as F
+from oracle import gradcheck as GC
 from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -482,18 +483,6 @@ def test_poison_threaded_callers(pkg, monkeypatch):
 
 # ---- 8. the clean engine against the oracle at the ragged shapes ---------------------------------------------------------
 
-def assert_grad_close(g, gn, go, gno, tree, noise, ts, xs, ctx, tol=GRAD_TOL):
-    """As tests/test_gpu_parity.py: tol of the gradient's scale against the fp64 oracle, the 80-bit oracle arbitrating."""
-    sc = max(1.0, np.abs(go).max() if go.size else 0.0, abs(gno))
-    e = max(np.abs(g - go).max() if go.size else 0.0, abs(gn - gno)) / sc
-    if e <= tol:
-        return
-    gl, gnl = O.gp_logpdf_grad_longdouble(tree, noise, ts, xs)
-    ed = max(np.abs(g - gl).max() if gl.size else 0.0, abs(gn - gnl)) / sc
-    eo = max(np.abs(go - gl).max() if gl.size else 0.0, abs(gno - gnl)) / sc
-    assert ed <= max(tol, 4.0 * eo), (ctx, e, ed, eo)
-
-
 # (test_logpdf_batch_vs_oracle already checks the value entry at 1, 2, 17, 127, 128, 129 and 256 points)
 VALUE_SHAPES = [n for n in SHAPES if n not in (1, 2, 17, 127, 128, 129, 256)]
 
@@ -501,7 +490,7 @@ VALUE_SHAPES = [n for n in SHAPES if n not in (1, 2, 17, 127, 128, 129, 256)]
 @pytest.mark.parametrize("n", SHAPES)
 def test_ragged_shapes_vs_oracle(pkg, engine, n):
     """Value (where no existing test covers the shape), gradient and predictive pass of the clean engine against the oracle:
-    LP_TOL, assert_grad_close, 1e-8.  n <= 17: well-conditioned particles also against the 60-digit oracle."""
+    LP_TOL, gradcheck.assert_grad_components (GRAD_TOL of the particle's scale and of every component's own), 1e-8.  n <= 17: well-conditioned particles also against the 60-digit oracle."""
     ts, xs = pkg.prior.synthetic_series(max(n, 2), seed=500 + n, shuffle=True)
     ts, xs = ts[:n], xs[:n]
     nodes, noises = pkg.prior.sample_particles(np.random.default_rng(500 + n), 12, max_depth=3, max_size=15)
@@ -518,9 +507,9 @@ def test_ragged_shapes_vs_oracle(pkg, engine, n):
     for i in range(6):
         if ginfo[i] != 0:
             continue
-        lpo, go, gno = O.gp_logpdf_grad(nodes[i].to_tuple(), float(noises[i]), ts, xs)
-        assert abs(glp[i] - lpo) <= LP_TOL * max(1.0, abs(lpo))
-        assert_grad_close(grads[i], gn[i], go, gno, nodes[i].to_tuple(), float(noises[i]), ts, xs, (n, i))
+        ref = GC.reference(nodes[i].to_tuple(), float(noises[i]), ts, xs)
+        assert abs(glp[i] - ref.lp) <= LP_TOL * max(1.0, abs(ref.lp))
+        GC.assert_grad_components(grads[i], gn[i], ref, tau=GRAD_TOL, ctx=(n, i))
     # (predictions: fixed, well-conditioned kernels — the oracle's LU solves carry cond(K) eps of their own)
     G = pkg
     pk = [G.Linear(0.3, 0.2, 0.5) + G.Periodic(0.4, 0.25, 0.6) * G.SquaredExponential(0.5, 1.0),

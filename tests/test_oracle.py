@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import to_tuple
+from oracle import gradcheck as GC
 from oracle import oracle as O
 from oracle import oracle_mp as M
 
@@ -172,7 +173,9 @@ def test_gradient_oracle_vs_finite_differences():
                           ("+", ("*", ("+", BASE[2], BASE[3]), ("+", BASE[4], BASE[5])), ("CP", BASE[1], BASE[0], 0.6, 0.1))]
     for tree in trees:
         lp, g, gn = O.gp_logpdf_grad(tree, 0.2, ts, xs)
+        ref = GC.reference(tree, 0.2, ts, xs)
         assert lp == pytest.approx(O.gp_logpdf(tree, 0.2, ts, xs), rel=1e-12)
+        assert np.abs(ref.all_g - np.append(g, gn)).max() <= 1e-14 * ref.particle_scale and (np.abs(ref.all_g) <= ref.all_S).all()
         ops, prm = O.tree_to_program(tree)
         assert g.shape == prm.shape
         for k in range(prm.size):
@@ -180,13 +183,17 @@ def test_gradient_oracle_vs_finite_differences():
             pp = prm.copy(); pp[k] += h; pm = prm.copy(); pm[k] -= h
             fd = (O.gp_logpdf(O.program_to_tree(ops, pp), 0.2, ts, xs) - O.gp_logpdf(O.program_to_tree(ops, pm), 0.2, ts, xs)) / (2 * h)
             assert g[k] == pytest.approx(fd, rel=2e-5, abs=2e-6), (tree, k)
+            # per component: central differences err by ~h^2 + eps |logpdf| / h (~1e-9 S_k measured), far below 1e-7 S_k
+            assert abs(g[k] - fd) <= 1e-7 * ref.S[k], (tree, k, abs(g[k] - fd) / ref.S[k])
         fdn = (O.gp_logpdf(tree, 0.2 + 1e-6, ts, xs) - O.gp_logpdf(tree, 0.2 - 1e-6, ts, xs)) / 2e-6
         assert gn == pytest.approx(fdn, rel=2e-5, abs=2e-6)
+        assert abs(gn - fdn) <= 1e-7 * ref.Sn
     # mpmath central difference (h = 1e-12 is affordable at 60 digits)
     import mpmath as mp
     tree = ("*", ("GE", 0.42, 0.58, 3.2), ("PER", 0.96, 0.21, 1.1))
     t12, x12 = ts[:12], xs[:12]
     lp, g, gn = O.gp_logpdf_grad(tree, 0.1, t12, x12)
+    ref = GC.reference(tree, 0.1, t12, x12)
     ops, prm = O.tree_to_program(tree)
     for k in range(prm.size):
         def f(v):
@@ -196,7 +203,79 @@ def test_gradient_oracle_vs_finite_differences():
         h = mp.mpf("1e-15")
         fd = (f(mp.mpf(float(prm[k])) + h) - f(mp.mpf(float(prm[k])) - h)) / (2 * h)
         assert abs(g[k] - float(fd)) <= 1e-8 * max(1.0, abs(float(fd))), k
+        assert abs(g[k] - float(fd)) <= 1e-12 * ref.S[k], (k, abs(g[k] - float(fd)) / ref.S[k])       # (h^2 ~ 1e-30: exact to fp64)
 
+
+
+def test_gradient_scales_pin_the_oracle_per_component(pkg):
+    """oracle.gp_logpdf_grad_scales: the gradient is gp_logpdf_grad's, every |g_k| <= S_k, the row-blocked contraction of large n
+    equals the one-block one, and the fp64 oracle meets 1e-13 S_k against the 80-bit arbiter for every component of a prior
+    population at n = 256 (measured: 1e-14) -- six orders of magnitude below the tolerance of the device checks (1e-7 S_k)."""
+    ts, xs = pkg.prior.synthetic_series(256, seed=256, shuffle=True)
+    nodes, noises = pkg.prior.sample_particles(np.random.default_rng(256), 16, max_size=31)
+    worst = 0.0
+    for nd, nz in zip(nodes, noises):
+        tree = nd.to_tuple()
+        lp, g, gn = O.gp_logpdf_grad(tree, float(nz), ts, xs)
+        ref = GC.reference(tree, float(nz), ts, xs)
+        blk = O.gp_logpdf_grad_scales(tree, float(nz), ts, xs, block_elems=7 * 256 + 5)
+        sc = ref.particle_scale
+        assert abs(ref.lp - lp) <= 1e-12 * max(1.0, abs(lp))
+        assert np.abs(ref.all_g - np.append(g, gn)).max() <= 1e-14 * sc
+        assert np.abs(np.append(blk[1], blk[2]) - ref.all_g).max() <= 1e-14 * sc
+        assert np.allclose(np.append(blk[3], blk[4]), ref.all_S, rtol=1e-13, atol=0)
+        assert (np.abs(ref.all_g) <= ref.all_S * (1 + 1e-13)).all() and (ref.all_S > 0).all()
+        e = np.abs(ref.all_g - ref.arbiter()) / ref.all_S
+        assert e.max() <= 1e-13, (nd, e)
+        worst = max(worst, e.max())
+    assert worst > 0.0
+
+
+def test_gradient_checker_sees_small_components(pkg):
+    """The per-component check is strictly more sensitive than the particle-wide one: on a prior particle whose smallest S_k is
+    >= 1e5 below max(1, |g|_inf, |d/dnoise|), moving that one component by 1e-3 S_k passes the particle-wide criterion and fails
+    gradcheck.assert_grad_components (even after the 80-bit arbiter has been consulted); the unperturbed oracle passes both, a
+    component with S_k = 0 passes only as exactly 0 (to 2^-52 of the particle's scale), and a device-vs-device comparison fails
+    the same perturbation at TAU_PATHS."""
+    ts, xs = pkg.prior.synthetic_series(256, seed=256, shuffle=True)
+    nodes, noises = pkg.prior.sample_particles(np.random.default_rng(256), 16, max_size=31)
+    ref = None
+    for nd, nz in zip(nodes, noises):
+        r = GC.reference(nd.to_tuple(), float(nz), ts, xs)
+        if r.S.size and r.S.min() <= 1e-5 * r.particle_scale:
+            ref = r
+            break
+    assert ref is not None
+    sc = ref.particle_scale
+    k = int(np.argmin(ref.S))
+    bad = ref.g.copy()
+    bad[k] += 1e-3 * ref.S[k]
+
+    def old_criterion(g, gn):
+        return max(np.abs(g - ref.g).max(), abs(gn - ref.gn)) <= GC.TAU_ORACLE * sc
+    assert old_criterion(bad, ref.gn)
+    assert GC.assert_grad_components(ref.g, ref.gn, ref) == 0.0
+    with pytest.raises(AssertionError, match="per component"):
+        GC.assert_grad_components(bad, ref.gn, ref, ctx="perturbed")
+    with pytest.raises(AssertionError, match="per component"):
+        GC.assert_grad_components(bad, ref.gn, ref, against=(ref.g, ref.gn))
+    assert GC.component_ratios(bad, ref.gn, ref)[k] == pytest.approx(1e-3, rel=1e-6)
+    # the noise derivative is checked against its own scale too
+    with pytest.raises(AssertionError, match="per component"):
+        GC.assert_grad_components(ref.g, ref.gn + 1e-6 * ref.Sn, ref)
+    # S_k = 0: a ChangePoint at the prior's scale of 0.001 between two grid points, far from every point: tanh is saturated
+    t = np.linspace(0.0, 1.0, 20)                      # (0.5 lies half-way between t_9 and t_10: |loc - t| / scale >= 26)
+    x = np.sin(7 * t)
+    cp = ("CP", ("SE", 0.2, 1.0), ("SE", 0.1, 0.5), 0.5, 0.001)
+    zr = GC.reference(cp, 0.1, t, x)
+    z = np.flatnonzero(zr.all_S == 0)
+    assert set(z) >= {4, 5}, zr.all_S                  # d/dlocation, d/dscale
+    assert GC.assert_grad_components(zr.g, zr.gn, zr) == 0.0
+    off = zr.g.copy(); off[4] = 2.0 ** -52 * zr.particle_scale
+    GC.assert_grad_components(off, zr.gn, zr)
+    off[4] = 4.0 * 2.0 ** -52 * zr.particle_scale
+    with pytest.raises(AssertionError, match="per component"):
+        GC.assert_grad_components(off, zr.gn, zr)
 
 def test_fast_oracle_matches_numpy_oracle(pkg, golden):
     """oracle/fast.py (C assembly + LAPACK dpotrf/dtrtrs, the large-n checker and the bench's CPU baseline) against
