@@ -46,6 +46,7 @@ struct CovArgs {
   int csplit;            // 4: a tile is shared by four workgroups (grid.z; 32 columns each) — launches of a few large trees,
                          // whose length is ONE workgroup's walk over its tile (launch_cov); otherwise one workgroup per tile
   CltArgs clt;           // compact tables (lagr then holds the points' keys)
+  const double* noise_q; // [P] added on the diagonal of the prediction block (agp_predict_logpdf_batch); null everywhere else
 };
 
 struct LagArgs {
@@ -129,6 +130,7 @@ struct CholArgs {
   const int32_t* lagr;  // rank tables (sweeps in the caller's order; see cov_prologue): ranks of the resident points, null = sorted sweep
   int lag_stride;       // ... doubles per table
   CltArgs clt;          // compact tables (lagr then holds the points' keys; lag_stride = doubles per table in LDS)
+  const double* noise_q; // fused evaluation: [P] noise on the prediction block's diagonal (see CovArgs), null = none
 };
 // LDS byte budget of the update kernel: GEMM double buffers and the potrf block store alias.
 constexpr int U_SLAB = KB * LDS_STRIDE;                // doubles per slab buffer

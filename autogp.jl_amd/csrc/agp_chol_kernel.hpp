@@ -183,9 +183,9 @@ __device__ __forceinline__ void factor_diag_tile(const CholArgs& a, int p, int t
   // The last tile row of a series is ragged: rows from n1 on are identity padding (cov_finalize), whose 16 x 16 blocks factor to
   // themselves — identity L, identity inverse, zero panel, alpha 0, bit for bit what the steps below would produce.  Only the
   // nbk block steps that hold data are run (n = 144: one of the eight steps of tile 1, ~28 us of a 125-us value sweep).  n1 = 0:
-  // a dense-input factorisation, whose padding this function knows nothing about — all steps.  rows_real <= 0 (a diagonal tile
-  // wholly past n1) cannot occur: only the training block's columns reach this kernel (agp_predict.hip, agp_store.hip) — were one
-  // to, it is factored in full like any tile whose padding is not known, never overwritten with identity.
+  // a dense-input factorisation, whose padding this function knows nothing about — all steps.  rows_real <= 0: a diagonal tile of
+  // the prediction block (the predictive log-density factors every block column of the joint matrix, agp_predict.hip) — factored in
+  // full, its padding rows included, never overwritten with identity.
   const int rows_real = a.n1 > 0 ? a.n1 - tk * NB : NB;
   const int nbk = (rows_real >= NB || rows_real <= 0) ? NSB : rows_real <= 16 ? 1 : (rows_real + 15) >> 4;
   AGP_DPROBE(2);
@@ -472,7 +472,9 @@ __device__ __forceinline__ void chol_tile(const CholArgs& a, const int p_, const
     if (AGP_EXP_TABLE && !LAGM && tid < AGP_EXP_TAB_N) etab[tid] = fm::c_exp_tab[tid];      // (lag sweeps evaluate no exponential)
     // (program, parameters, time points and lag tables travel in ONE round trip; the prologue's barrier publishes all of it)
     cov_prologue<LAGM>(a.tt, a.code, ti, tk, h, ops, prm, tpt, sig, tid, a.lagtab, a.nt, LAGM ? a.lagr : nullptr, lstride, xrk, true, a.clt, cbl);
-    const double noise = a.noise[p];
+    // (DM = 2: no diagonal element; Schur mode: every tile it evaluates lies in the prediction block, whose diagonal carries no noise
+    // in the passes that run it)
+    const double noise = !FACTOR ? 0.0 : DM == 2 ? a.noise[p] : diag_noise(a.noise, a.noise_q, p, tk, a.n1_pad);
     // GammaExp leaves read log|dt| from the data set's table (L2 / Infinity-Cache resident: every particle reads
     // the same 128 KiB tile); the loads are issued at the top of the pass and consumed by the first such leaf
     const bool use_tab = TAB && (h.flags & 1) != 0;
@@ -924,7 +926,7 @@ __device__ __forceinline__ void chol_diag_tile(const CholArgs& a, const int p_, 
     double* etab = rvec;                     // exp table in the (still unused) forward-solve scratch
     if (AGP_EXP_TABLE && !LAGM && tid < AGP_EXP_TAB_N) etab[tid] = fm::c_exp_tab[tid];
     cov_prologue<LAGM>(a.tt, a.code, tk, tk, h, ops, prm, tpt, sig, tid, a.lagtab, a.nt, LAGM ? a.lagr : nullptr, lstride, xrk, true, a.clt, cbl);
-    const double noise = a.noise[p];
+    const double noise = diag_noise(a.noise, a.noise_q, p, tk, a.n1_pad);
     const bool use_tab = TAB && (h.flags & 1) != 0;
     const double* __restrict__ ltile = a.logdt + tile_off(tk, tk);      // only dereferenced when use_tab
     double ltn[4] = {0.0, 0.0, 0.0, 0.0};          // table values, fetched one pass ahead (see chol_tile)
@@ -1342,6 +1344,28 @@ __global__ void k_finish_logpdf(const double* partial, const int* info, int nt, 
   out_info[o] = inf;
 }
 
+// Predictive log-density (agp_predict_logpdf_batch): the joint matrix [ts; pad; ts_pred; pad] factored through ALL its block
+// columns with noise_pred on the query diagonal and [x - mu1; y* - mu2] in the forward solve — the query columns' partials are then
+// log|Sigma*| and (y* - mu*)' Sigma*^-1 (y* - mu*), Sigma* = K22 - K21 K11^-1 K12 + noise_pred I (src/GP.jl:753-757):
+//   logpdf = -1/2 (m log 2pi + sum_{k >= nt1} (ld_k + ss_k))
+// info: a pivot of K11 (1..n) as it stands; padded pivot n1_pad + k of the query block -> n + k.  map: sorted -> caller's order.
+__global__ void k_finish_pred_logpdf(const double* partial, const int* info, int nt1, int nt, int P, int m, int n, int n1_pad,
+                                     const int* map, double* out_logpdf, int* out_info) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= P) return;
+  double ld = 0.0, ss = 0.0;
+  for (int k = nt1; k < nt; ++k) {
+    ld += partial[((long long)p * nt + k) * 2];
+    ss += partial[((long long)p * nt + k) * 2 + 1];
+  }
+  int inf = info[p];
+  if (inf > n1_pad) inf = inf - n1_pad + n;
+  const double lp = -0.5 * ((double)m * 1.8378770664093454835606594728112 + ld + ss);
+  const int o = map[p];
+  out_logpdf[o] = (inf != 0) ? __builtin_nan("") : lp;
+  out_info[o] = inf;
+}
+
 // row r (blockIdx.y) of a pitched buffer -> row r of another (pitches and width in doubles; width even or odd):
 // the factor store's growth copy (a slot's resident prefix is contiguous, slots are ~GiB apart).
 __global__ __launch_bounds__(256) void k_copy_rows(double* __restrict__ dst, long long dpitch, const double* __restrict__ src,
@@ -1460,6 +1484,13 @@ __global__ void k_init_vec(double* vec, int ldv, int P, const double* xs, const 
   double v = 0.0;
   if (g < n1) v = xs[g] - (mu1 ? mu1[g] : 0.0);
   vec[(long long)p * ldv + g] = v;
+}
+
+// y* - mu2 into the query segment [off, off + m) of every particle's forward-solve vector (after k_init_vec)
+__global__ void k_init_query_vec(double* vec, int ldv, int off, int m, const double* y, const double* mu2) {
+  const int g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= m) return;
+  vec[(long long)blockIdx.y * ldv + off + g] = y[g] - (mu2 ? mu2[g] : 0.0);
 }
 
 // Predictive read-out (src/GP.jl:753-757): mean = mu2 + K21 K11^-1 (x - mu1),

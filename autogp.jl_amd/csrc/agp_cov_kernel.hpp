@@ -249,13 +249,20 @@ __device__ __forceinline__ void eval_program(const ProgHdr& h, const OpT* __rest
   for (int e = 0; e < E; ++e) out[e] = st[0][e];
 }
 
-// noise on the training diagonal (src/GP.jl:667), identity on padding rows / columns
+// noise on the diagonal of a tile (diag_noise), identity on padding rows / columns
 __device__ __forceinline__ double cov_finalize(double v, int gi, int gj, int n1, int n1_pad, int m2, double noise) {
   const bool vi = (gi < n1) || (gi >= n1_pad && gi < n1_pad + m2);
   const bool vj = (gj < n1) || (gj >= n1_pad && gj < n1_pad + m2);
   double r = (vi && vj) ? v : 0.0;
-  if (gi == gj) r = vi ? (r + (gi < n1 ? noise : 0.0)) : 1.0;
+  if (gi == gj) r = vi ? (r + noise) : 1.0;
   return r;
+}
+// What cov_finalize adds on the diagonal of block column tk (a diagonal tile lies wholly in the training block or wholly in the
+// prediction block: n1_pad is a multiple of NB): the particle's noise in the training block (src/GP.jl:667); in the prediction
+// block noise_q[p] where the pass scores query values (agp_predict_logpdf_batch: noise_pred) and 0.0 in every other pass.
+__device__ __forceinline__ double diag_noise(const double* noise, const double* noise_q, int p, int tk, int n1_pad) {
+  const double* q = tk * NB < n1_pad ? noise : noise_q;
+  return q != nullptr ? q[p] : 0.0;
 }
 
 #ifndef AGP_COV_E
@@ -305,7 +312,7 @@ __global__ __launch_bounds__(256, AGP_COV_WGS) void k_cov_tiles(CovArgs a) {
   const int r0 = 2 * rp;
   const double tr0 = tpt[r0], tr1 = tpt[r0 + 1];
   const int gi0 = ti * NB + r0;
-  const double noise = a.noise[p];
+  const double noise = diag_noise(a.noise, a.noise_q, p, tj, a.n1_pad);
   double* __restrict__ T = a.A + (long long)(a.slot != nullptr ? a.slot[p] : p) * a.strideA + tile_off(ti, tj);
 
   const bool use_tab = (h.flags & 1) != 0;

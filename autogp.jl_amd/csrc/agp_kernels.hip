@@ -110,6 +110,14 @@ void launch_finish_logpdf(hipStream_t st, const double* partial, const int* info
                           double* out_logpdf, int* out_info, const int* slot, int ntp) {
   hipLaunchKernelGGL(k_finish_logpdf, dim3((P + 63) / 64), dim3(64), 0, st, partial, info, nt, P, n, map, out_logpdf, out_info, slot, ntp);
 }
+void launch_init_query_vec(hipStream_t st, int P, double* vec, int ldv, int off, int m, const double* y, const double* mu2) {
+  hipLaunchKernelGGL(k_init_query_vec, dim3((m + 255) / 256, P), dim3(256), 0, st, vec, ldv, off, m, y, mu2);
+}
+void launch_finish_pred_logpdf(hipStream_t st, const double* partial, const int* info, int nt1, int nt, int P, int m, int n,
+                               int n1_pad, const int* map, double* out_logpdf, int* out_info) {
+  hipLaunchKernelGGL(k_finish_pred_logpdf, dim3((P + 63) / 64), dim3(64), 0, st, partial, info, nt1, nt, P, m, n, n1_pad, map,
+                     out_logpdf, out_info);
+}
 void launch_init_extend(hipStream_t st, int U, double* vec, int ldv, int n_pad, const double* xs, int n, const int* slot,
                         const int* i0, int* info, int* ready) {
   hipLaunchKernelGGL(k_init_extend, dim3((n_pad + 255) / 256, U), dim3(256), 0, st, vec, ldv, n_pad, xs, n, slot, i0, info, ready);

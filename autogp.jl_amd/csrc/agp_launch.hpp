@@ -26,6 +26,10 @@ void launch_trsm(int grid, hipStream_t st, const CholArgs& ca);                 
 void launch_init_vec(hipStream_t st, int ldv, int P, double* vec, const double* xs, const double* mu1, int n1, int* info, int* ready);
 void launch_finish_logpdf(hipStream_t st, const double* partial, const int* info, int nt, int P, int n, const int* map,
                           double* out_logpdf, int* out_info, const int* slot = nullptr, int ntp = 0);
+// predictive log-density (agp_predict_logpdf_batch): y* - mu2 into the query segment; the query columns' partials -> logpdf, info
+void launch_init_query_vec(hipStream_t st, int P, double* vec, int ldv, int off, int m, const double* y, const double* mu2);
+void launch_finish_pred_logpdf(hipStream_t st, const double* partial, const int* info, int nt1, int nt, int P, int m, int n,
+                               int n1_pad, const int* map, double* out_logpdf, int* out_info);
 void launch_init_extend(hipStream_t st, int U, double* vec, int ldv, int n_pad, const double* xs, int n, const int* slot,
                         const int* i0, int* info, int* ready);
 void launch_init_flow_flags(hipStream_t st, int P, int* tflag, int ntri_stride, int ntri, const int* slot, const int* i0);

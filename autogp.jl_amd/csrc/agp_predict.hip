@@ -469,6 +469,162 @@ int predict_core(agp_ctx* c, int64_t n, const double* ts_pred, int64_t m, int32_
   return AGP_OK;
 }
 
+// Predictive log-density (src/api.jl:686-699, test/experiment_hmc.jl:125): logpdf(MvNormal(node, noise, ts[1:n], xs[1:n], ts_pred;
+// noise_pred, mean), y_pred) for a compiled batch.  predict_core's joint matrix [K11 + noise I, K12; K21, K22 + noise_pred I] is
+// factored through ALL nt1 + nt2 block columns with [x - mu1; y_pred - mu2] in the forward solve: the query block of the factor is
+// the Cholesky factor of Sigma* = K22 - K21 K11^-1 K12 + noise_pred I and its forward solve L22^-1 (y* - mu*), so the query columns'
+// partials are log|Sigma*| and the Mahalanobis term themselves (k_finish_pred_logpdf) — no Schur step, no read-out, and no
+// difference of two large log-likelihoods.  (No duplicate-query shortcut: it yields diag(Sigma*), not Sigma*.)
+int predict_logpdf_core(agp_ctx* c, int64_t n, const double* ts_pred, const double* y_pred, int64_t m, int32_t P, Batch& bt,
+                        const double* noise, const double* noise_pred, const double* mean_train, const double* mean_pred,
+                        double* out_lp, int32_t* out_info, const PredLattice* pl) {
+  const int n1_pad = round_up(n, NB), m_pad = round_up(m, NB);
+  const bool lagr = pl != nullptr && pl->on;
+  const int nt1 = n1_pad / NB, nt = nt1 + m_pad / NB;
+  const int ntot = n1_pad + m_pad;
+  const int ntiles = nt * (nt + 1) / 2;
+  const long long strideA = (long long)ntiles * NB2;
+  const int chunk = (int)std::max<int64_t>(1, std::min<int64_t>(P, ws_limit_bytes(c) / (strideA * 8)));
+
+  SlotGuard sg(c);
+  Slot* s = sg.s;
+  if (!s->stream) HIPCHK(c, hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
+  hipStream_t st = s->stream;
+
+  std::vector<double> tt((size_t)ntot, 0.0);
+  std::copy(c->h_ts.begin(), c->h_ts.begin() + n, tt.begin());
+  std::copy(ts_pred, ts_pred + m, tt.begin() + n1_pad);
+  std::vector<double> npred(P), noise_sorted(P);
+  for (int q = 0; q < P; ++q) {
+    const int p = bt.order[q];
+    noise_sorted[q] = noise[p];
+    npred[q] = noise_pred ? noise_pred[p] : noise[p];
+  }
+  HIPCHK(c, s->A.ensure((size_t)strideA * 8 * chunk));
+  HIPCHK(c, s->W.ensure(sizeof(double) * NSB * 256 * (size_t)chunk * nt));     // (the dataflow schedule keeps every column's inverse blocks)
+  HIPCHK(c, s->vec.ensure(sizeof(double) * (size_t)ntot * chunk));
+  HIPCHK(c, s->partial.ensure(sizeof(double) * 2 * (size_t)nt * chunk));
+  HIPCHK(c, s->info.ensure(sizeof(int) * (size_t)P));
+  HIPCHK(c, s->ready.ensure(sizeof(int) * (size_t)P));
+  HIPCHK(c, s->hdr.ensure(sizeof(ProgHdr) * (size_t)P));
+  HIPCHK(c, s->ops.ensure(bt.ops.size()));
+  HIPCHK(c, s->prm.ensure(sizeof(double) * std::max<size_t>(1, bt.prm.size())));
+  HIPCHK(c, s->noise.ensure(sizeof(double) * (size_t)P));
+  HIPCHK(c, s->noise_pred.ensure(sizeof(double) * (size_t)P));
+  HIPCHK(c, s->tt.ensure(sizeof(double) * (size_t)ntot));
+  HIPCHK(c, s->pred_mean.ensure(sizeof(double) * (size_t)m));      // y_pred (the read-out buffers are idle in this pass)
+  HIPCHK(c, s->map.ensure(sizeof(int32_t) * (size_t)P));
+  HIPCHK(c, s->out_lp.ensure(sizeof(double) * (size_t)P));
+  HIPCHK(c, s->out_info.ensure(sizeof(int32_t) * (size_t)P));
+  PinnedUploads up;
+  if (mean_train && n > 0) {
+    HIPCHK(c, s->mu1.ensure(sizeof(double) * (size_t)n));
+    up.add(s->mu1.p, mean_train, sizeof(double) * n);
+  }
+  if (mean_pred) {
+    HIPCHK(c, s->mu2.ensure(sizeof(double) * (size_t)m));
+    up.add(s->mu2.p, mean_pred, sizeof(double) * m);
+  }
+  up.add(s->hdr.p, bt.hdr.data(), sizeof(ProgHdr) * P);
+  up.add(s->ops.p, bt.ops.data(), bt.ops.size());
+  up.add(s->prm.p, bt.prm.data(), sizeof(double) * bt.prm.size());
+  up.add(s->noise.p, noise_sorted.data(), sizeof(double) * P);
+  up.add(s->noise_pred.p, npred.data(), sizeof(double) * P);
+  up.add(s->tt.p, tt.data(), sizeof(double) * ntot);
+  up.add(s->pred_mean.p, y_pred, sizeof(double) * m);
+  up.add(s->map.p, bt.order.data(), sizeof(int32_t) * P);
+  if (lagr) {
+    // (as predict_core: ranks of the joint points, lag times, one rank table per stationary subtree of the batch)
+    auto al16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
+    const size_t o_tprm = al16(sizeof(LagTabHdr) * bt.thdr.size());
+    const size_t o_tops = al16(o_tprm + sizeof(double) * bt.tprm.size());
+    const size_t prog_bytes = al16(o_tops + bt.tops.size() + 4);
+    std::vector<char> hp(prog_bytes, 0);
+    if (!bt.thdr.empty()) {
+      std::memcpy(hp.data(), bt.thdr.data(), sizeof(LagTabHdr) * bt.thdr.size());
+      std::memcpy(hp.data() + o_tprm, bt.tprm.data(), sizeof(double) * bt.tprm.size());
+      std::memcpy(hp.data() + o_tops, bt.tops.data(), bt.tops.size());
+    }
+    HIPCHK(c, s->pl_prog.ensure(prog_bytes));
+    HIPCHK(c, s->pl_rank.ensure(sizeof(int32_t) * pl->rank.size()));
+    HIPCHK(c, s->pl_tl.ensure(sizeof(double) * pl->tl.size()));
+    up.add(s->pl_prog.p, hp.data(), prog_bytes);
+    up.add(s->pl_rank.p, pl->rank.data(), sizeof(int32_t) * pl->rank.size());
+    up.add(s->pl_tl.p, pl->tl.data(), sizeof(double) * pl->tl.size());
+    HIPCHK(c, up.flush(s->h_stage, s->up_blob, st));
+    if (bt.n_lag_tables > 0) {
+      HIPCHK(c, s->lagtab.ensure(sizeof(double) * (size_t)bt.n_lag_tables * pl->rank_units * 256));
+      LagArgs la = {};
+      la.tt = s->pl_tl.as<double>(); la.thdr = s->pl_prog.as<LagTabHdr>();
+      la.tprm = reinterpret_cast<const double*>(static_cast<char*>(s->pl_prog.p) + o_tprm);
+      la.tops = reinterpret_cast<const uint8_t*>(static_cast<char*>(s->pl_prog.p) + o_tops);
+      la.n_tables = bt.n_lag_tables; la.tab = s->lagtab.as<double>();
+      la.nt = 2 * pl->rank_units; la.full = 1; la.stride = pl->rank_units * 256;
+      launch_lag_tables(st, la, pl->rank_units, bt.n_lag_tables);
+      HIPCHK(c, hipGetLastError());
+    }
+    std::lock_guard<std::mutex> g(c->mu);
+    ++c->n_lag_pred;
+  } else {
+    HIPCHK(c, up.flush(s->h_stage, s->up_blob, st));
+  }
+
+  for (int p0 = 0; p0 < P; p0 += chunk) {
+    const int Pc = std::min(chunk, P - p0);
+    launch_init_vec(st, ntot, Pc, s->vec.as<double>(), c->d_xs, (mean_train && n > 0) ? s->mu1.as<double>() : (const double*)nullptr,
+                    (int)n, s->info.as<int>() + p0, s->ready.as<int>() + p0);
+    launch_init_query_vec(st, Pc, s->vec.as<double>(), ntot, n1_pad, (int)m, s->pred_mean.as<double>(),
+                          mean_pred ? s->mu2.as<double>() : (const double*)nullptr);
+    CovArgs cv = {};
+    cv.tt = s->tt.as<double>(); cv.n1 = (int)n; cv.n1_pad = n1_pad; cv.m2 = (int)m; cv.nt = nt;
+    cv.hdr = s->hdr.as<ProgHdr>() + p0; cv.ops = s->ops.as<uint8_t>(); cv.prm = s->prm.as<double>();
+    cv.noise = s->noise.as<double>() + p0; cv.noise_q = s->noise_pred.as<double>() + p0;
+    cv.A = s->A.as<double>(); cv.strideA = strideA; cv.P = Pc;
+    if (lagr) { cv.lagtab = s->lagtab.as<double>(); cv.lagr = s->pl_rank.as<int32_t>(); cv.lag_stride = pl->rank_units * 256; }
+    const int nf = std::max(0, std::min(Pc, bt.n_fused - p0));
+    const int dcov = nf > 0 ? bt.max_depth_fused : 0;
+    cv.p_off = nf;
+    HIPCHK(c, launch_cov(st, cv, ntiles, Pc - nf, bt.max_cp, bt.max_depth));
+
+    CholArgs ca = {};
+    ca.A = s->A.as<double>(); ca.strideA = strideA; ca.W = s->W.as<double>();
+    ca.vec = s->vec.as<double>(); ca.ldv = ntot; ca.partial = s->partial.as<double>();
+    ca.info = s->info.as<int>() + p0; ca.P = Pc; ca.nt = nt; ca.k = 0; ca.nt1 = nt;      // (every block column is factored)
+    set_cov(ca, cv);
+    ca.lag = lagr ? 1 : 0;
+    ca.n_fused = nf;
+    ca.ready = s->ready.as<int>() + p0;
+    // (one schedule whatever the batch: a particle's log-density does not depend on the particles around it — the per-column
+    // launches only where the dataflow schedule is switched off, AGP_FLOW=0)
+    if (c->flow != 0) {
+      const int ntri = nt * (nt + 1) / 2;
+      HIPCHK(c, s->tflag.ensure(sizeof(int) * (size_t)Pc * ntri));
+      HIPCHK(c, s->flowq.ensure(sizeof(int) * 8 * 8));
+      ca.tflag = s->tflag.as<int>(); ca.ntri = ntri; ca.qnext = s->flowq.as<int>();
+      ca.wsteps = nt;
+      HIPCHK(c, hipMemsetAsync(ca.tflag, 0, sizeof(int) * (size_t)Pc * ntri, st));
+      HIPCHK(c, hipMemsetAsync(ca.qnext, 0, sizeof(int) * 8, st));
+      launch_flow(dcov, 2 * c->n_cu, st, ca);
+      HIPCHK(c, hipGetLastError());
+    } else {
+      HIPCHK(c, run_factor(st, ca, nt, dcov, nullptr, nullptr, use_split_diag(c, ca.P)));
+    }
+    launch_finish_pred_logpdf(st, ca.partial, ca.info, nt1, nt, Pc, (int)m, (int)n, n1_pad, s->map.as<int32_t>() + p0,
+                              s->out_lp.as<double>(), s->out_info.as<int32_t>());
+    HIPCHK(c, hipGetLastError());
+  }
+  // (results are in the caller's order already; blocking copies: nothing in flight towards the locals on an error return)
+  std::vector<int32_t> info(P);
+  HIPCHK(c, hipStreamSynchronize(st));
+  HIPCHK(c, hipMemcpy(out_lp, s->out_lp.p, sizeof(double) * P, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(info.data(), s->out_info.p, sizeof(int32_t) * P, hipMemcpyDeviceToHost));
+  for (int p = 0; p < P; ++p) {
+    if (info[p] < 0) return fail(c, AGP_ERR_HIP, "in-kernel panel solve timed out waiting for its diagonal factor");
+    if (out_info) out_info[p] = info[p];
+  }
+  return AGP_OK;
+}
+
 }  // namespace
 
 namespace {
@@ -848,6 +1004,91 @@ static int predict_batch_body(agp_ctx* c, int64_t n, const double* ts_pred, int6
     std::memcpy(out_var + (size_t)p * m, uvar.data() + u * m, sizeof(double) * (size_t)m);
     if (out_cov) std::memcpy(out_cov + (size_t)p * m * m, ucov.data() + u * m * m, sizeof(double) * (size_t)m * m);
     if (out_info) out_info[p] = uinfo[u];
+  }
+  return AGP_OK;
+}
+
+static int predict_logpdf_body(agp_ctx* c, int64_t n, const double* ts_pred, const double* y_pred, int64_t m, int32_t P,
+                               const int32_t* op_off, const uint8_t* ops, const int32_t* prm_off, const double* prm,
+                               const double* noise, const double* noise_pred, const double* mean_train, const double* mean_pred,
+                               double* out_logpdf, int32_t* out_info);
+int agp_predict_logpdf_batch(agp_ctx* c, int64_t n, const double* ts_pred, const double* y_pred, int64_t m, int32_t P,
+                             const int32_t* op_off, const uint8_t* ops, const int32_t* prm_off, const double* prm,
+                             const double* noise, const double* noise_pred, const double* mean_train, const double* mean_pred,
+                             double* out_logpdf, int32_t* out_info) {
+  return abi_guard(c, [&] { return predict_logpdf_body(c, n, ts_pred, y_pred, m, P, op_off, ops, prm_off, prm, noise, noise_pred,
+                                                       mean_train, mean_pred, out_logpdf, out_info); });
+}
+static int predict_logpdf_body(agp_ctx* c, int64_t n, const double* ts_pred, const double* y_pred, int64_t m, int32_t P,
+                               const int32_t* op_off, const uint8_t* ops, const int32_t* prm_off, const double* prm,
+                               const double* noise, const double* noise_pred, const double* mean_train, const double* mean_pred,
+                               double* out_logpdf, int32_t* out_info) {
+  if (!c) return fail(nullptr, AGP_ERR_ARG, "null context");
+  if (P < 0 || n < 0 || m < 0) return fail(c, AGP_ERR_ARG, "negative size");
+  if (n > c->n_max) return fail(c, AGP_ERR_NODATA, "n exceeds the data uploaded with agp_set_data");
+  if (P == 0) return AGP_OK;
+  if (!out_logpdf) return fail(c, AGP_ERR_ARG, "null pointer argument");
+  if (m == 0) {
+    // the empty vector has density 1 under every particle (the reference scores [] as 0.)
+    for (int p = 0; p < P; ++p) { out_logpdf[p] = 0.0; if (out_info) out_info[p] = 0; }
+    return AGP_OK;
+  }
+  if (!op_off || !ops || !prm_off || !prm || !noise || !ts_pred || !y_pred) return fail(c, AGP_ERR_ARG, "null pointer argument");
+  HIPCHK(c, hipSetDevice(c->device));
+  // identical particles (a resampled population, src/inference_smc_anneal_data.jl:198-204) are evaluated once, as in agp_predict_batch
+  std::vector<int> rep(P), uniq;
+  bool sane = true;
+  for (int p = 0; p < P && sane; ++p)
+    sane = op_off[p + 1] >= op_off[p] && prm_off[p + 1] >= prm_off[p] && op_off[p] >= 0 && prm_off[p] >= 0;
+  if (c->dedup && P > 1 && sane) {
+    std::unordered_map<std::string, int> seen;
+    seen.reserve((size_t)P * 2);
+    for (int p = 0; p < P; ++p) {
+      const int no = op_off[p + 1] - op_off[p], np = prm_off[p + 1] - prm_off[p];
+      const int32_t lens[2] = {no, np};
+      std::string key(reinterpret_cast<const char*>(lens), sizeof lens);
+      key.append(reinterpret_cast<const char*>(ops + op_off[p]), (size_t)no);
+      key.append(reinterpret_cast<const char*>(prm + prm_off[p]), sizeof(double) * (size_t)np);
+      key.append(reinterpret_cast<const char*>(noise + p), sizeof(double));
+      if (noise_pred) key.append(reinterpret_cast<const char*>(noise_pred + p), sizeof(double));
+      auto it = seen.find(key);
+      if (it == seen.end()) { seen.emplace(std::move(key), (int)uniq.size()); rep[p] = (int)uniq.size(); uniq.push_back(p); }
+      else rep[p] = it->second;
+    }
+  } else {
+    for (int p = 0; p < P; ++p) { rep[p] = p; uniq.push_back(p); }
+  }
+  const int U = (int)uniq.size();
+  std::vector<int32_t> uo(U + 1, 0), up(U + 1, 0), uinfo(U, 0);
+  std::vector<uint8_t> uops; std::vector<double> uprm, unoise(U), unp(noise_pred ? U : 0), ulp(U);
+  if (U == P) {
+    uo.assign(op_off, op_off + P + 1); up.assign(prm_off, prm_off + P + 1);
+  }
+  for (int u = 0; u < U; ++u) {
+    const int p = uniq[u];
+    if (U < P) {
+      uops.insert(uops.end(), ops + op_off[p], ops + op_off[p + 1]);
+      uprm.insert(uprm.end(), prm + prm_off[p], prm + prm_off[p + 1]);
+      uo[u + 1] = (int32_t)uops.size(); up[u + 1] = (int32_t)uprm.size();
+    }
+    unoise[u] = noise[p];
+    if (noise_pred) unp[u] = noise_pred[p];
+  }
+  if (uprm.empty()) uprm.push_back(0.0);
+  const uint8_t* cops = U < P ? uops.data() : ops;
+  const double* cprm = U < P ? uprm.data() : prm;
+  PredLattice pl;
+  predict_lattice(c, n, ts_pred, m, pl);
+  const bool ff = c->flow != 0;      // (predict_logpdf_core's schedule)
+  Batch bt;
+  int rc = compile_batch(c, U, uo.data(), cops, up.data(), cprm, bt, false, false, false, ff, ff, pl.on, pl.on ? pl.rank_units : 1, pl.on);
+  if (rc) return rc;
+  rc = predict_logpdf_core(c, n, ts_pred, y_pred, m, U, bt, unoise.data(), noise_pred ? unp.data() : nullptr, mean_train, mean_pred,
+                           ulp.data(), uinfo.data(), &pl);
+  if (rc) return rc;
+  for (int p = 0; p < P; ++p) {
+    out_logpdf[p] = ulp[(size_t)rep[p]];
+    if (out_info) out_info[p] = uinfo[(size_t)rep[p]];
   }
   return AGP_OK;
 }

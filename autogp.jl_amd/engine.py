@@ -32,7 +32,7 @@ EXPORTED_SYMBOLS = [
     "agp_allgather_logweights", "agp_allgather_logweights_device", "agp_logpdf_batch_multi", "agp_logpdf_batch_extend_multi",
     "agp_debug_compact_shards", "agp_logpdf_batch_extend", "agp_extend_stats", "agp_extend_reset", "agp_extend_reserve",
     "agp_predict_reuse_stats", "agp_grad_reuse_stats", "agp_set_factor_cache", "agp_wait", "agp_comm_count", "agp_get_lag_stats", "agp_get_lattice_stats", "agp_get_compact_stats", "agp_set_lattice", "agp_probe_lattice", "agp_set_reference_arithmetic", "agp_shard_plan", "agp_get_coalesce_timing", "agp_set_lag_tables", "agp_set_grad_lag_domain", "agp_get_grad_lag_domain_stats", "agp_get_grad_toeplitz_stats", "agp_get_grad_structured_stats", "agp_get_predict_structured_stats", "agp_get_toeplitz_stats", "agp_set_lag_rank_tables", "agp_get_lag_rank_stats", "agp_get_lag_predict_stats", "agp_get_poison_stats",
-    "agp_logpdf_grad_batch_multi", "agp_predict_batch_multi", "agp_extend_stats2",
+    "agp_logpdf_grad_batch_multi", "agp_predict_batch_multi", "agp_extend_stats2", "agp_predict_logpdf_batch",
 ]
 COMM_ID_BYTES = 128
 
@@ -105,6 +105,8 @@ def load_library(path=None):
     lib.agp_predict_batch.argtypes = [vp, C.c_int64, dp, C.c_int64, C.c_int32, ip, u8p, ip, dp, dp, dp, dp, dp,
                                       dp, dp, dp, ip]
     lib.agp_predict_batch.restype = C.c_int
+    lib.agp_predict_logpdf_batch.argtypes = [vp, C.c_int64, dp, dp, C.c_int64, C.c_int32, ip, u8p, ip, dp, dp, dp, dp, dp, dp, ip]
+    lib.agp_predict_logpdf_batch.restype = C.c_int
     lib.agp_infer_gp_sum.argtypes = [vp, C.c_int64, dp, C.c_int64, C.c_int32, ip, u8p, ip, dp, C.c_double, C.c_double, dp, dp, ip]
     lib.agp_infer_gp_sum.restype = C.c_int
     lib.agp_cov_matrix.argtypes = [vp, dp, C.c_int64, u8p, C.c_int32, dp, C.c_int32, C.c_double, dp]
@@ -505,6 +507,29 @@ class GPEngine:
             raise PosDefException(int(info[p]), p)
         return mean, var, cov, info
 
+    def predict_logpdf_batch(self, nodes, noises, ts_pred, y_pred, n=None, noise_pred=None, mean_train=None, mean_pred=None,
+                             check=True):
+        """logpdf(MvNormal(node, noise, ts[1:n], xs[1:n], ts_pred; noise_pred, mean), y_pred) per particle (src/api.jl:693,
+        test/experiment_hmc.jl:125) without forming the predictive covariance.  Returns (logp[P], info[P]); info = n + k: the
+        predictive covariance's leading minor k is not positive definite (logp NaN wherever info != 0)."""
+        n = self.n_max if n is None else int(n)
+        op_off, ops, prm_off, prm = _gp.encode_batch(nodes)
+        P = op_off.shape[0] - 1
+        noises = _f64(noises); ts_pred = _f64(ts_pred); y_pred = _f64(y_pred); m = ts_pred.shape[0]
+        if y_pred.shape != (m,):
+            raise ValueError(f"y_pred has shape {y_pred.shape}, ts_pred {ts_pred.shape}")
+        npred = None if noise_pred is None else _f64(np.broadcast_to(noise_pred, (P,)))
+        mt = None if mean_train is None else _f64(mean_train)
+        mp_ = None if mean_pred is None else _f64(mean_pred)
+        logp = np.empty(P); info = np.zeros(P, dtype=np.int32)
+        self._check(self._lib.agp_predict_logpdf_batch(self._ctx, n, _dp(ts_pred), _dp(y_pred), m, P, _ip(op_off), _u8(ops),
+                                                       _ip(prm_off), _dp(prm), _dp(noises), _dp(npred), _dp(mt), _dp(mp_),
+                                                       _dp(logp), _ip(info)))
+        if check and (info > 0).any():
+            p = int(np.argmax(info > 0))
+            raise PosDefException(int(info[p]), p)
+        return logp, info
+
     # -- sum-of-GPs posterior (src/GP.jl:904-993) ---------------------------------------------
     def infer_gp_sum(self, nodes, noise, ts_pred, n=None, noise_pred=None, check=True):
         """Returns (mean[(M+1)p], cov[(M+1)p, (M+1)p], indexes_F (list of slices), indexes_X (slice))."""
@@ -800,12 +825,35 @@ class MvNormal:
         mu, var, cov, _ = eng.predict_batch([node], [noise], ts_pred, noise_pred=noise_pred, mean_train=mt,
                                             mean_pred=mp_, want_cov=True)
         self.mu, self.var, self.Sigma = mu[0], var[0], cov[0]
+        self._score = (eng, node, float(noise), ts, xs, ts_pred, noise_pred, mt, mp_)
 
     def mean(self):
         return self.mu
 
     def cov(self):
         return self.Sigma
+
+    def logpdf(self, y):
+        """Distributions.logpdf(d, y) (src/api.jl:693), on the GPU from the joint factorisation (agp_predict_logpdf_batch).
+        Raises PosDefException like the reference."""
+        eng, node, noise, ts, xs, ts_pred, noise_pred, mt, mp_ = self._score
+        eng.set_data(ts, xs)
+        lp, _ = eng.predict_logpdf_batch([node], [noise], ts_pred, y, noise_pred=noise_pred, mean_train=mt, mean_pred=mp_)
+        return float(lp[0])
+
+
+def predict_proba(engine, nodes, noises, log_weights, ts_pred, y, y_transform=(1.0, 0.0), noise_pred=None):
+    """AutoGP.predict_proba(model, ds, y) (src/api.jl:686-699) on the engine's resident (scaled) series: per particle its
+    normalised weight and the log-density of the RAW observations y at ts_pred (already in the engine's time scale) under the
+    un-transformed predictive.  y_transform = (slope, intercept) of the series' linear transform (scaled = slope * raw +
+    intercept); the predictive of the raw values is the scaled one mapped back, whose density gains m log|slope|.
+    Returns a dict of arrays {"particle", "weight", "logp"} (the reference's DataFrame columns)."""
+    slope, intercept = (float(v) for v in y_transform)
+    y = _f64(y)
+    lp, _ = engine.predict_logpdf_batch(nodes, noises, ts_pred, slope * y + intercept, noise_pred=noise_pred)
+    lw = _f64(log_weights)
+    w = np.exp(lw - lw.max()); w /= w.sum()
+    return {"particle": np.arange(1, len(nodes) + 1), "weight": w, "logp": lp + y.shape[0] * np.log(abs(slope))}
 
 
 def infer_gp_sum(nodes, noise, ts, xs, ts_pred, noise_pred=None, engine=None):

@@ -358,6 +358,46 @@ function predict_marginal(eng::Engine, node::GP.Node, noise::Float64, ts_pred::V
     return mu, var
 end
 
+"""
+Predictive log-density of held-out values for a population — `Distributions.logpdf.(components, [y])` of `predict_proba`
+(src/api.jl:686-699) and the held-out likelihood of test/experiment_hmc.jl:125, on the (scaled) resident series.  The covariance
+is never formed: the joint matrix is factored once per particle.  Returns (logp, info); logp[i] is NaN where info[i] != 0
+(info in 1..n: K11 is not positive definite; n + k: leading minor k of the predictive covariance is not).
+"""
+function predict_logpdf_batch(eng::Engine, nodes::Vector{<:GP.Node}, noises::Vector{Float64}, ts_pred::Vector{Float64},
+        y::Vector{Float64}; n::Integer=eng.n_max, noise_pred::Union{Nothing,Vector{Float64}}=nothing,
+        mean_train::Union{Nothing,Vector{Float64}}=nothing, mean_pred::Union{Nothing,Vector{Float64}}=nothing)
+    P = length(nodes); m = length(ts_pred)
+    length(y) == m || throw(DimensionMismatch("y has $(length(y)) values, ts_pred $(m)"))
+    op_off, ops, prm_off, prm = encode_batch(nodes)
+    logp = Vector{Float64}(undef, P); info = zeros(Int32, P)
+    npv = isnothing(noise_pred) ? Float64[] : noise_pred
+    mt = isnothing(mean_train) ? Float64[] : mean_train
+    mp = isnothing(mean_pred) ? Float64[] : mean_pred
+    GC.@preserve ops prm op_off prm_off ts_pred y noises npv mt mp logp info check(eng, ccall((:agp_predict_logpdf_batch, LIB), Cint,
+        (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}, Int64, Int32, Ptr{Int32}, Ptr{UInt8}, Ptr{Int32}, Ptr{Float64},
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
+        eng.ptr, n, ts_pred, y, m, P, op_off, ops, prm_off, prm, noises,
+        isempty(npv) ? Ptr{Float64}(C_NULL) : pointer(npv),
+        isempty(mt) ? Ptr{Float64}(C_NULL) : pointer(mt),
+        isempty(mp) ? Ptr{Float64}(C_NULL) : pointer(mp),
+        logp, info))
+    return logp, info
+end
+
+"""
+`Distributions.logpdf(MvNormal(node, noise, ts, xs, ts_pred; noise_pred, mean), y)` (test/experiment_hmc.jl:125) for one particle
+on the resident series; throws `PosDefException` like the reference's factorisation.
+"""
+function predict_logpdf(eng::Engine, node::GP.Node, noise::Float64, ts_pred::Vector{Float64}, y::Vector{Float64};
+        n::Integer=eng.n_max, noise_pred::Union{Nothing,Float64}=nothing,
+        mean_train::Union{Nothing,Vector{Float64}}=nothing, mean_pred::Union{Nothing,Vector{Float64}}=nothing)
+    logp, info = predict_logpdf_batch(eng, [node], [noise], ts_pred, y; n=n,
+        noise_pred=isnothing(noise_pred) ? nothing : [noise_pred], mean_train=mean_train, mean_pred=mean_pred)
+    info[1] != 0 && throw(LinearAlgebra.PosDefException(info[1]))
+    return logp[1]
+end
+
 "Sum-of-GPs posterior — replaces GP.infer_gp_sum (src/GP.jl:904-993); returns the same named tuple."
 function infer_gp_sum(eng::Engine, nodes::Vector{<:GP.Node}, noise::Float64, ts_pred::Vector{Float64};
         n::Integer=eng.n_max, noise_pred::Union{Nothing,Float64}=nothing)

@@ -375,6 +375,22 @@ int agp_predict_batch(agp_ctx* ctx, int64_t n, const double* ts_pred, int64_t m,
                       double* out_mean, double* out_var, double* out_cov,
                       int32_t* out_info);
 
+/* Predictive log-density of held-out values (src/api.jl:686-699 predict_proba, test/experiment_hmc.jl:125):
+ * out_logpdf[p] = logpdf(MvNormal(node_p, noise[p], ts[1:n], xs[1:n], ts_pred; noise_pred, mean), y_pred) for P particles on the
+ * resident (ts, xs)[1:n] — the predictive of agp_predict_batch, scored without forming its covariance.  The joint matrix of the
+ * training and query points is factored through all its block columns with noise_pred on the query diagonal; the query block's
+ * log-det and Mahalanobis partials are the result.  noise_pred may be NULL (= noise); mean_train (n) / mean_pred (m) NULL = 0.
+ * m == 0: logpdf 0 (the reference scores [] as 0); n == 0: the prior predictive N(y_pred; mean_pred, K22 + noise_pred I).
+ * out_info[p] (may be NULL): 0; 1..n: K11 is not positive definite (first failing minor); n + k: K11 is, leading minor k of the
+ * predictive covariance is not.  out_logpdf[p] is NaN whenever out_info[p] != 0; no particle affects another.  Identical particles
+ * are evaluated once (AGP_DEDUP=0 disables).  Errors (negative return): m, n or P < 0, n > the uploaded series, a NULL input. */
+int agp_predict_logpdf_batch(agp_ctx* ctx, int64_t n, const double* ts_pred, const double* y_pred, int64_t m, int32_t P,
+                             const int32_t* op_off, const uint8_t* ops,
+                             const int32_t* prm_off, const double* prm,
+                             const double* noise, const double* noise_pred,
+                             const double* mean_train, const double* mean_pred,
+                             double* out_logpdf, int32_t* out_info);
+
 /* infer_gp_sum(nodes, noise, ts, xs, ts_pred; noise_pred) (src/GP.jl:904-993) on the resident (ts, xs)[1:n]:
  * posterior of Z = [F_1(T*); ...; F_M(T*); X(T*)] for the sum-of-GPs model.  The M component kernels are
  * given as CSR-packed postfix programs (op_off / prm_off have M+1 entries).  out_mean: (M+1)*p;
