@@ -1560,7 +1560,8 @@ __global__ void k_mfma_probe(const double* A, const double* B, double* D) {
 }
 
 
-// element-wise probe of csrc/agp_math.hpp on the device: which = 0 exp_f, 1 sin2_f, 2 log_f, 3 pow_f(x, g)
+// element-wise probe of csrc/agp_math.hpp on the device: which = 0 exp_f, 1 sin2_f, 2 log_f, 3 pow_f(x, g); 4 the device
+// library's erfc (what k_mixture_quantile's normcdf calls), 5 sqrt (k_mixture_pack's sigma)
 __global__ void k_math_probe(int which, const double* x, const double* g, double* y, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -1568,7 +1569,9 @@ __global__ void k_math_probe(int which, const double* x, const double* g, double
   if (which == 0) r = fm::exp_f(x[i]);
   else if (which == 1) r = fm::sin2_f(x[i]);
   else if (which == 2) r = fm::log_f(x[i]);
-  else r = fm::pow_f(x[i], g[i]);
+  else if (which == 3) r = fm::pow_f(x[i], g[i]);
+  else if (which == 4) r = erfc(x[i]);
+  else r = __builtin_sqrt(x[i]);
   y[i] = r;
 }
 

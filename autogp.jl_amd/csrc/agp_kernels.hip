@@ -4,6 +4,7 @@
 #include "agp_cov_kernel.hpp"
 #include "agp_chol_kernel.hpp"
 #include "agp_toep_kernel.hpp"
+#include "agp_quantile_kernel.hpp"
 #include "agp_comm.hpp"
 
 namespace agp {
@@ -156,6 +157,16 @@ void launch_compact_shards(hipStream_t st, const double* padded, int mx, int P, 
 void launch_mfma_probe(const double* A, const double* B, double* D) { hipLaunchKernelGGL(k_mfma_probe, dim3(1), dim3(64), 0, 0, A, B, D); }
 void launch_math_probe(int which, const double* x, const double* g, double* y, int n) {
   hipLaunchKernelGGL(k_math_probe, dim3((n + 255) / 256), dim3(256), 0, 0, which, x, g, y, n);
+}
+void launch_mixture_pack(hipStream_t st, const double* means, const double* vars, int P, int Pp, int m, double* cm, double* cs) {
+  const long long nel = (long long)m * Pp;
+  hipLaunchKernelGGL(k_mixture_pack, dim3((unsigned)((nel + 255) / 256)), dim3(256), 0, st, means, vars, P, Pp, m, cm, cs);
+}
+void launch_mixture_quantile(hipStream_t st, const double* cm, const double* cs, const double* cw, int Pp, int m, const double* q,
+                             int nq, double tol, long long max_iter, double* out_x, int32_t* out_conv, int32_t* out_iters) {
+  const long long nw = (long long)m * nq;
+  hipLaunchKernelGGL(k_mixture_quantile, dim3((unsigned)((nw + MQ_WAVES - 1) / MQ_WAVES)), dim3(64 * MQ_WAVES), 0, st, cm, cs, cw, Pp, m,
+                     q, nq, tol, max_iter, out_x, out_conv, out_iters);
 }
 void launch_mfma_peak(int nblk, double* out, long long* cycles, int iters, int mode) {
   hipLaunchKernelGGL(k_mfma_peak, dim3(nblk), dim3(256), 0, 0, out, cycles, iters, mode);

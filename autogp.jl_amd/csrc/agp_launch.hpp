@@ -45,6 +45,10 @@ void launch_compact_shards(hipStream_t st, const double* padded, int mx, int P, 
 void launch_mfma_probe(const double* A, const double* B, double* D);
 void launch_math_probe(int which, const double* x, const double* g, double* y, int n);
 void launch_mfma_peak(int nblk, double* out, long long* cycles, int iters, int mode);
+// mixture quantiles (agp_quantile.hip): components to one row per point (sigma = sqrt(var)), then one wave per (point, q)
+void launch_mixture_pack(hipStream_t st, const double* means, const double* vars, int P, int Pp, int m, double* cm, double* cs);
+void launch_mixture_quantile(hipStream_t st, const double* cm, const double* cs, const double* cw, int Pp, int m, const double* q,
+                             int nq, double tol, long long max_iter, double* out_x, int32_t* out_conv, int32_t* out_iters);
 
 // ---- agp_kernels_grad.hip --------------------------------------------------------------------------------------------
 hipError_t kernels_init_grad();

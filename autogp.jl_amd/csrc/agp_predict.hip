@@ -1406,7 +1406,7 @@ int agp_debug_flow_trace(agp_ctx* c, int32_t enable, int64_t max_items, int64_t*
 #endif  // AGP_EXPERIMENTS
 
 int agp_debug_math(agp_ctx* c, int32_t which, const double* x, const double* g, double* y, int32_t n) {
-  if (!c || !x || !y || n <= 0 || (which == 3 && !g)) return fail(c, AGP_ERR_ARG, "bad arguments");
+  if (!c || !x || !y || n <= 0 || which < 0 || which > 5 || (which == 3 && !g)) return fail(c, AGP_ERR_ARG, "bad arguments");
   HIPCHK(c, hipSetDevice(c->device));
   double *dx = nullptr, *dg = nullptr, *dy = nullptr;
   HIPCHK(c, malloc_values(c->poison, (void**)&dx, sizeof(double) * n));

@@ -33,6 +33,7 @@ EXPORTED_SYMBOLS = [
     "agp_debug_compact_shards", "agp_logpdf_batch_extend", "agp_extend_stats", "agp_extend_reset", "agp_extend_reserve",
     "agp_predict_reuse_stats", "agp_grad_reuse_stats", "agp_set_factor_cache", "agp_wait", "agp_comm_count", "agp_get_lag_stats", "agp_get_lattice_stats", "agp_get_compact_stats", "agp_set_lattice", "agp_probe_lattice", "agp_set_reference_arithmetic", "agp_shard_plan", "agp_get_coalesce_timing", "agp_set_lag_tables", "agp_set_grad_lag_domain", "agp_get_grad_lag_domain_stats", "agp_get_grad_toeplitz_stats", "agp_get_grad_structured_stats", "agp_get_predict_structured_stats", "agp_get_toeplitz_stats", "agp_set_lag_rank_tables", "agp_get_lag_rank_stats", "agp_get_lag_predict_stats", "agp_get_poison_stats",
     "agp_logpdf_grad_batch_multi", "agp_predict_batch_multi", "agp_extend_stats2", "agp_predict_logpdf_batch",
+    "agp_mixture_quantile", "agp_predict_quantile_batch",
 ]
 COMM_ID_BYTES = 128
 
@@ -107,6 +108,11 @@ def load_library(path=None):
     lib.agp_predict_batch.restype = C.c_int
     lib.agp_predict_logpdf_batch.argtypes = [vp, C.c_int64, dp, dp, C.c_int64, C.c_int32, ip, u8p, ip, dp, dp, dp, dp, dp, dp, ip]
     lib.agp_predict_logpdf_batch.restype = C.c_int
+    lib.agp_mixture_quantile.argtypes = [vp, C.c_int64, C.c_int32, dp, dp, dp, dp, C.c_int64, C.c_double, C.c_int64, dp, ip, ip]
+    lib.agp_mixture_quantile.restype = C.c_int
+    lib.agp_predict_quantile_batch.argtypes = [vp, C.c_int64, dp, C.c_int64, C.c_int32, ip, u8p, ip, dp, dp, dp, dp, dp, dp,
+                                               C.c_double, C.c_double, dp, C.c_int64, C.c_double, C.c_int64, dp, ip, ip, ip]
+    lib.agp_predict_quantile_batch.restype = C.c_int
     lib.agp_infer_gp_sum.argtypes = [vp, C.c_int64, dp, C.c_int64, C.c_int32, ip, u8p, ip, dp, C.c_double, C.c_double, dp, dp, ip]
     lib.agp_infer_gp_sum.restype = C.c_int
     lib.agp_cov_matrix.argtypes = [vp, dp, C.c_int64, u8p, C.c_int32, dp, C.c_int32, C.c_double, dp]
@@ -530,6 +536,49 @@ class GPEngine:
             raise PosDefException(int(info[p]), p)
         return logp, info
 
+    # -- mixture quantiles (src/api.jl:547-596) -----------------------------------------------
+    def mixture_quantile(self, means, vars, weights, q, tol=1e-5, max_iter=10**6):
+        """Statistics.quantile(::MixtureModel, q; tol, max_iter) (src/api.jl:559-596) per point: means / vars of shape (P, m) (the
+        layout predict_batch returns), weights (P,), q a scalar or a vector.  Returns (x, converged, iters), each of shape (m, nq)
+        — (m,) for a scalar q; the reference's `success` is converged.all()."""
+        means = _f64(means); vars = _f64(vars); weights = _f64(weights)
+        if means.ndim != 2 or vars.shape != means.shape or weights.shape != (means.shape[0],):
+            raise ValueError(f"means {means.shape}, vars {vars.shape}, weights {weights.shape}: expected (P, m), (P, m), (P,)")
+        P, m = means.shape
+        qa = _f64(np.atleast_1d(q)); nq = qa.shape[0]
+        x = np.empty((nq, m)); conv = np.zeros((nq, m), dtype=np.int32); iters = np.zeros((nq, m), dtype=np.int32)
+        self._check(self._lib.agp_mixture_quantile(self._ctx, m, P, _dp(means), _dp(vars), _dp(weights), _dp(qa), nq, float(tol),
+                                                   int(max_iter), _dp(x), _ip(conv), _ip(iters)))
+        return _quantile_shape(q, x, conv, iters)
+
+    def predict_quantile_batch(self, nodes, noises, ts_pred, weights, q, n=None, noise_pred=None, mean_train=None, mean_pred=None,
+                               y_transform=(1.0, 0.0), tol=1e-5, max_iter=10**6, check=True):
+        """predict_quantile (src/api.jl:547-557) on the resident series: the mixture, with `weights`, of every particle's marginal
+        predictive mapped to the raw space of y_transform = (slope, intercept), searched per point by the device.  Returns (x,
+        converged, iters, info), x / converged / iters shaped as mixture_quantile's; info = n + j: the raw marginal variance at
+        query j (1-based) is negative or NaN.  If any info != 0, x is NaN (PosDefException when check)."""
+        n = self.n_max if n is None else int(n)
+        op_off, ops, prm_off, prm = _gp.encode_batch(nodes)
+        P = op_off.shape[0] - 1
+        noises = _f64(noises); ts_pred = _f64(ts_pred); m = ts_pred.shape[0]; weights = _f64(weights)
+        if weights.shape != (P,):
+            raise ValueError(f"weights has shape {weights.shape}, expected ({P},)")
+        npred = None if noise_pred is None else _f64(np.broadcast_to(noise_pred, (P,)))
+        mt = None if mean_train is None else _f64(mean_train)
+        mp_ = None if mean_pred is None else _f64(mean_pred)
+        slope, intercept = (float(v) for v in y_transform)
+        qa = _f64(np.atleast_1d(q)); nq = qa.shape[0]
+        x = np.empty((nq, m)); conv = np.zeros((nq, m), dtype=np.int32); iters = np.zeros((nq, m), dtype=np.int32)
+        info = np.zeros(P, dtype=np.int32)
+        self._check(self._lib.agp_predict_quantile_batch(self._ctx, n, _dp(ts_pred), m, P, _ip(op_off), _u8(ops), _ip(prm_off), _dp(prm),
+                                                         _dp(noises), _dp(npred), _dp(mt), _dp(mp_), _dp(weights), slope, intercept,
+                                                         _dp(qa), nq, float(tol), int(max_iter), _dp(x), _ip(conv), _ip(iters),
+                                                         _ip(info)))
+        if check and (info > 0).any():
+            p = int(np.argmax(info > 0))
+            raise PosDefException(int(info[p]), p)
+        return _quantile_shape(q, x, conv, iters) + (info,)
+
     # -- sum-of-GPs posterior (src/GP.jl:904-993) ---------------------------------------------
     def infer_gp_sum(self, nodes, noise, ts_pred, n=None, noise_pred=None, check=True):
         """Returns (mean[(M+1)p], cov[(M+1)p, (M+1)p], indexes_F (list of slices), indexes_X (slice))."""
@@ -723,6 +772,49 @@ def probe_lattice(ts):
     return {"kind": int(k.value), "n_lattice": int(g.value), "spacing": float(h.value), "index": idx}
 
 
+def _quantile_shape(q, x, conv, iters):
+    """(nq, m) C-order results of the quantile entries -> (m, nq), or (m,) for a scalar q."""
+    x, conv, iters = x.T.copy(), conv.T.astype(bool), iters.T.copy()
+    if np.ndim(q) == 0:
+        return x[:, 0], conv[:, 0], iters[:, 0]
+    return x, conv, iters
+
+
+def raw_components(mean, var, info, n, y_transform=(1.0, 0.0)):
+    """agp_predict_quantile_batch's step between its two passes, on the host: predict_mvn's raw-space transform (src/api.jl:513-520)
+    mean (P, m) -> (mean - intercept) / slope, var -> (1 / slope^2) * var, and info = n + j (1-based) where a particle's raw
+    variance at query j is negative or NaN or its raw mean not finite.  Returns (mean_raw, var_raw, info)."""
+    slope, intercept = (float(v) for v in y_transform)
+    mr = (np.asarray(mean, dtype=np.float64) - intercept) / slope
+    vr = (1.0 / (slope * slope)) * np.asarray(var, dtype=np.float64)
+    info = np.array(info, dtype=np.int32, copy=True)
+    bad = ~(np.isfinite(mr) & (vr >= 0.0))
+    for p in np.flatnonzero((info == 0) & bad.any(axis=1)):
+        info[p] = int(n) + int(np.argmax(bad[p])) + 1
+    return mr, vr, info
+
+
+def predict_quantile_multi(multi, nodes, noises, ts_pred, weights, q, n=None, noise_pred=None, mean_train=None, mean_pred=None,
+                           y_transform=(1.0, 0.0), tol=1e-5, max_iter=10**6, check=True):
+    """GPEngine.predict_quantile_batch over several devices: the marginal pass split by agp_predict_batch_multi, the components
+    gathered on the host and searched on the first device (agp_mixture_quantile).  Same results."""
+    engines = multi.engines if isinstance(multi, GPEngineMulti) else list(multi)
+    n = engines[0].n_max if n is None else int(n)
+    for v in np.atleast_1d(q):
+        if not 0.0 < float(v) < 1.0:
+            raise AGPError("quantile must be in (0, 1)")
+    mean, var, _, info = predict_batch_multi(engines, nodes, noises, ts_pred, n=n, noise_pred=noise_pred, mean_train=mean_train,
+                                             mean_pred=mean_pred, check=False)
+    mr, vr, info = raw_components(mean, var, info, n, y_transform)
+    if check and (info > 0).any():
+        p = int(np.argmax(info > 0))
+        raise PosDefException(int(info[p]), p)
+    if (info != 0).any():
+        shape = (len(ts_pred),) + (() if np.ndim(q) == 0 else (len(np.atleast_1d(q)),))
+        return np.full(shape, np.nan), np.zeros(shape, dtype=bool), np.zeros(shape, dtype=np.int32), info
+    return engines[0].mixture_quantile(mr, vr, weights, q, tol=tol, max_iter=max_iter) + (info,)
+
+
 class GPEngineMulti:
     """One host process driving several GPUs (agp_init_multi): what a single Julia process would hold.
     `engines[i]` is the per-device GPEngine (rank i of the node communicator)."""
@@ -778,6 +870,10 @@ class GPEngineMulti:
     def predict_batch(self, nodes, noises, ts_pred, **kw):
         """agp_predict_batch_multi over the node's devices."""
         return predict_batch_multi(self.engines, nodes, noises, ts_pred, **kw)
+
+    def predict_quantile_batch(self, nodes, noises, ts_pred, weights, q, **kw):
+        """GPEngine.predict_quantile_batch over the node's devices (predict_quantile_multi)."""
+        return predict_quantile_multi(self, nodes, noises, ts_pred, weights, q, **kw)
 
 
 # ------------------------------------------------------------------------------------------
@@ -854,6 +950,22 @@ def predict_proba(engine, nodes, noises, log_weights, ts_pred, y, y_transform=(1
     lw = _f64(log_weights)
     w = np.exp(lw - lw.max()); w /= w.sum()
     return {"particle": np.arange(1, len(nodes) + 1), "weight": w, "logp": lp + y.shape[0] * np.log(abs(slope))}
+
+
+def predict_quantile(engine, nodes, noises, log_weights, ts_pred, q, y_transform=(1.0, 0.0), noise_pred=None, tol=1e-5,
+                     max_iter=10**6):
+    """AutoGP.predict_quantile(model, ds, q; noise_pred, tol, max_iter) (src/api.jl:547-596) on the engine's resident (scaled)
+    series: the quantile q of the weighted mixture of every particle's posterior predictive at ts_pred (already in the engine's
+    time scale), in the RAW space of y_transform = (slope, intercept) (scaled = slope * raw + intercept).  Weights are the
+    particle_weights route: exp of Gen.normalize_weights(log_weights).  `engine` is a GPEngine or a GPEngineMulti.
+    Returns (x, success): x of shape (m,) and a bool for a scalar q; (m, nq) and an (nq,) bool array for a vector q.  Raises
+    PosDefException when a particle has no predictive (as predict_batch)."""
+    from .dist import normalize_weights
+    w = np.exp(normalize_weights(log_weights)[1])
+    npred = None if noise_pred is None else float(noise_pred)
+    x, conv, _, _ = engine.predict_quantile_batch(nodes, noises, ts_pred, w, q, noise_pred=npred, y_transform=y_transform, tol=tol,
+                                                  max_iter=max_iter)
+    return x, (bool(conv.all()) if np.ndim(q) == 0 else conv.all(axis=0))
 
 
 def infer_gp_sum(nodes, noise, ts, xs, ts_pred, noise_pred=None, engine=None):

@@ -398,6 +398,51 @@ function predict_logpdf(eng::Engine, node::GP.Node, noise::Float64, ts_pred::Vec
     return logp[1]
 end
 
+"""
+Quantiles of a Gaussian mixture per point — `Statistics.quantile(::MixtureModel, q; tol, max_iter)` (src/api.jl:559-596) on the
+mixtures of `Normal(means[i, p], sqrt(vars[i, p]))` with `weights[p]` (means / vars m×P).  Returns (x, converged, iters), each m×nq;
+the reference's `success` is `all(converged)`.
+"""
+function mixture_quantile(eng::Engine, means::Matrix{Float64}, vars::Matrix{Float64}, weights::Vector{Float64}, q::Vector{Float64};
+        tol::Real=1e-5, max_iter::Integer=10^6)
+    m, P = size(means)
+    size(vars) == (m, P) && length(weights) == P || throw(DimensionMismatch("means $(size(means)), vars $(size(vars)), weights $(length(weights))"))
+    nq = length(q)
+    x = Matrix{Float64}(undef, m, nq); conv = zeros(Int32, m, nq); iters = zeros(Int32, m, nq)
+    GC.@preserve means vars weights q x conv iters check(eng, ccall((:agp_mixture_quantile, LIB), Cint,
+        (Ptr{Cvoid}, Int64, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Float64, Int64, Ptr{Float64},
+         Ptr{Int32}, Ptr{Int32}),
+        eng.ptr, m, P, means, vars, weights, q, nq, Float64(tol), Int64(max_iter), x, conv, iters))
+    return x, conv .!= 0, iters
+end
+
+"""
+`AutoGP.predict_quantile(model, ds, q; noise_pred, tol, max_iter)` (src/api.jl:547-557) for a population on the (scaled) resident
+series: the marginal predictive of every particle mapped to the raw space of the linear `y_transform` (slope, intercept), the
+mixture with `weights` (`AutoGP.particle_weights(model)`), searched per point on the device.  Returns (x, success) like the
+reference; throws `PosDefException` where a particle has no predictive.
+"""
+function predict_quantile(eng::Engine, nodes::Vector{<:GP.Node}, noises::Vector{Float64}, weights::Vector{Float64},
+        ts_pred::Vector{Float64}, q::Real; n::Integer=eng.n_max, noise_pred::Union{Nothing,Float64}=nothing,
+        y_slope::Float64=1.0, y_intercept::Float64=0.0, tol::Real=1e-5, max_iter::Integer=10^6)
+    (0 < q < 1) || error("Quantile must be in (0,1).")
+    P = length(nodes); m = length(ts_pred)
+    op_off, ops, prm_off, prm = encode_batch(nodes)
+    qv = [Float64(q)]
+    x = Vector{Float64}(undef, m); conv = zeros(Int32, m); iters = zeros(Int32, m); info = zeros(Int32, P)
+    npv = isnothing(noise_pred) ? Float64[] : fill(noise_pred, P)
+    GC.@preserve ops prm op_off prm_off ts_pred noises npv weights qv x conv iters info check(eng, ccall((:agp_predict_quantile_batch, LIB), Cint,
+        (Ptr{Cvoid}, Int64, Ptr{Float64}, Int64, Int32, Ptr{Int32}, Ptr{UInt8}, Ptr{Int32}, Ptr{Float64},
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Float64, Float64, Ptr{Float64}, Int64, Float64, Int64,
+         Ptr{Float64}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}),
+        eng.ptr, n, ts_pred, m, P, op_off, ops, prm_off, prm, noises,
+        isempty(npv) ? Ptr{Float64}(C_NULL) : pointer(npv), Ptr{Float64}(C_NULL), Ptr{Float64}(C_NULL),
+        weights, y_slope, y_intercept, qv, 1, Float64(tol), Int64(max_iter), x, conv, iters, info))
+    k = findfirst(!=(0), info)
+    isnothing(k) || throw(LinearAlgebra.PosDefException(info[k]))
+    return x, all(!=(0), conv)
+end
+
 "Sum-of-GPs posterior — replaces GP.infer_gp_sum (src/GP.jl:904-993); returns the same named tuple."
 function infer_gp_sum(eng::Engine, nodes::Vector{<:GP.Node}, noise::Float64, ts_pred::Vector{Float64};
         n::Integer=eng.n_max, noise_pred::Union{Nothing,Float64}=nothing)

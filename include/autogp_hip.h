@@ -391,6 +391,42 @@ int agp_predict_logpdf_batch(agp_ctx* ctx, int64_t n, const double* ts_pred, con
                              const double* mean_train, const double* mean_pred,
                              double* out_logpdf, int32_t* out_info);
 
+/* Quantiles of a Gaussian mixture, per point: Statistics.quantile(::MixtureModel, q; tol, max_iter) (src/api.jl:559-596) applied to
+ * the mixture over components p of Normal(means[p*m + i], sqrt(vars[p*m + i])) with weights[p], at every point i < m and every
+ * q[k], k < nq.  means / vars are column-major m x P (particle p's m values contiguous: the layout agp_predict_batch writes
+ * out_mean / out_var in).  out_x[k*m + i]: the search's x; out_converged[k*m + i] (may be NULL): 1 if |cdf(x) - q| < tol held
+ * within max_iter checks (the reference's `success` is the AND over all points); out_iters[k*m + i] (may be NULL, saturates at
+ * INT32_MAX): the updates applied to x.  The reference's vectorised loop is reproduced bit for bit: start at 0 with
+ * (x_min, x_max) = (-Inf, Inf), double until bracketed, then bisect; a point stops when it converges, at max_iter, when an
+ * update leaves x unchanged (every later iteration would repeat it: the x of max_iter iterations, not converged), or — tol <= 0 —
+ * once a cycle of its state is found, after the updates that take it to where max_iter would end.
+ * cdf = sum over w_p != 0 of w_p normcdf((x - mu_p) / sigma_p), normcdf(z) = erfc(-z / sqrt 2) / 2; sigma_p == 0 is a step (0 below
+ * mu_p, 1 above, 1/2 at x == mu_p).  A point's result depends only on its P components (in their order), q, tol and max_iter.
+ * tol <= 0 and max_iter <= 0 are accepted (max_iter <= 0: x = 0, not converged).  m == 0 or nq == 0: nothing written.
+ * Errors (negative return): P < 1; m, nq < 0; a q outside (0, 1) or NaN; weights not finite, negative or not summing to 1 (rtol
+ * sqrt(eps)); at a positive weight, a non-finite mean or a negative or NaN variance; a NULL input; m*P or m*nq >= 2^31. */
+int agp_mixture_quantile(agp_ctx* ctx, int64_t m, int32_t P, const double* means, const double* vars, const double* weights,
+                         const double* q, int64_t nq, double tol, int64_t max_iter, double* out_x, int32_t* out_converged,
+                         int32_t* out_iters);
+
+/* predict_quantile(model, ds, q; noise_pred, tol, max_iter) (src/api.jl:547-557) on the resident (ts, xs)[1:n]: the marginal pass of
+ * agp_predict_batch (out_cov = NULL; arguments n .. mean_pred as there), then predict_mvn's raw-space transform (src/api.jl:513-520)
+ * of a linear y_transform, mu_raw = (mu - y_intercept) / y_slope and var_raw = (1 / y_slope^2) * var, then agp_mixture_quantile
+ * with `weights` (the particle weights, P).  The m x P means and variances are staged through host memory between the two passes.
+ * out_info[p] (may be NULL): 0; 1..n: K11 is not positive definite (agp_predict_batch's info); n + j: the raw marginal variance at
+ * query j (1-based) is negative or NaN, or the raw mean there is not finite.  If any particle's info != 0, out_x is NaN everywhere
+ * and nothing is converged (the reference throws).  Deviation: the reference builds MvNormal(mu, cov) from every particle's full
+ * m x m predictive covariance, which throws PosDefException when that matrix is singular (e.g. duplicate query points with
+ * noise_pred = 0); this entry, like predict_marginal, never forms it and so does not raise that error.  Errors as
+ * agp_mixture_quantile (y_slope must be finite and non-zero, y_intercept finite) plus agp_predict_batch's. */
+int agp_predict_quantile_batch(agp_ctx* ctx, int64_t n, const double* ts_pred, int64_t m, int32_t P,
+                               const int32_t* op_off, const uint8_t* ops,
+                               const int32_t* prm_off, const double* prm,
+                               const double* noise, const double* noise_pred,
+                               const double* mean_train, const double* mean_pred, const double* weights,
+                               double y_slope, double y_intercept, const double* q, int64_t nq, double tol, int64_t max_iter,
+                               double* out_x, int32_t* out_converged, int32_t* out_iters, int32_t* out_info);
+
 /* infer_gp_sum(nodes, noise, ts, xs, ts_pred; noise_pred) (src/GP.jl:904-993) on the resident (ts, xs)[1:n]:
  * posterior of Z = [F_1(T*); ...; F_M(T*); X(T*)] for the sum-of-GPs model.  The M component kernels are
  * given as CSR-packed postfix programs (op_off / prm_off have M+1 entries).  out_mean: (M+1)*p;
@@ -508,7 +544,8 @@ int agp_debug_cholesky(agp_ctx* ctx, const double* K, int64_t n, double* out_L, 
 int agp_debug_mfma_probe(agp_ctx* ctx, const double* A, const double* B, double* D);
 
 /* Element-wise probe of the device math used by the covariance kernels (csrc/agp_math.hpp):
- * which = 0 exp, 1 sin^2, 2 log, 3 pow(x, g). */
+ * which = 0 exp, 1 sin^2, 2 log, 3 pow(x, g), 4 erfc (the device library's, as the mixture-quantile kernel calls it),
+ * 5 sqrt (the mixture-quantile kernels' sigma). */
 int agp_debug_math(agp_ctx* ctx, int32_t which, const double* x, const double* g, double* y, int32_t n);
 
 /* fp64 MFMA issue-rate microbenchmark (16 independent accumulators per wave, wg_per_cu
