@@ -560,6 +560,41 @@ std::string particle_key(const uint8_t* ops, int no, const double* prm, int np, 
   key.append(reinterpret_cast<const char*>(&noise), sizeof(double));
   return key;
 }
+
+bool distinct_particles(int P, const int32_t* op_off, const uint8_t* ops, const int32_t* prm_off, const double* prm, const double* noise,
+                        const double* noise_pred, std::vector<int>& rep, std::vector<int>& uniq, std::vector<std::string>* keys) {
+  rep.clear(); uniq.clear();
+  if (keys) keys->clear();
+  for (int p = 0; p < P; ++p)
+    if (op_off[p + 1] < op_off[p] || prm_off[p + 1] < prm_off[p] || op_off[p] < 0 || prm_off[p] < 0) return false;
+  std::unordered_map<std::string, int> seen;
+  seen.reserve((size_t)P * 2);
+  rep.resize((size_t)P);
+  for (int p = 0; p < P; ++p) {
+    std::string key = particle_key(ops + op_off[p], op_off[p + 1] - op_off[p], prm + prm_off[p], prm_off[p + 1] - prm_off[p], noise[p]);
+    if (noise_pred) key.append(reinterpret_cast<const char*>(noise_pred + p), sizeof(double));
+    const auto it = seen.try_emplace(std::move(key), (int)uniq.size());
+    rep[(size_t)p] = it.first->second;
+    if (it.second) { uniq.push_back(p); if (keys) keys->push_back(it.first->first); }
+  }
+  return true;
+}
+
+void pack_particles(const std::vector<int>& ix, const int32_t* op_off, const uint8_t* ops, const int32_t* prm_off, const double* prm,
+                    const double* noise, const double* noise_pred, SubBatch& S) {
+  const size_t B = ix.size();
+  S.op_off.assign(B + 1, 0); S.prm_off.assign(B + 1, 0); S.ops.clear(); S.prm.clear();
+  S.noise.resize(B); S.noise_pred.resize(noise_pred ? B : 0);
+  for (size_t b = 0; b < B; ++b) {
+    const int p = ix[b];
+    S.ops.insert(S.ops.end(), ops + op_off[p], ops + op_off[p + 1]);
+    S.prm.insert(S.prm.end(), prm + prm_off[p], prm + prm_off[p + 1]);
+    S.op_off[b + 1] = (int32_t)S.ops.size(); S.prm_off[b + 1] = (int32_t)S.prm.size();
+    S.noise[b] = noise[p];
+    if (noise_pred) S.noise_pred[b] = noise_pred[p];
+  }
+  if (S.prm.empty()) S.prm.push_back(0.0);
+}
 // Factor-store lookup for a compiled batch (sorted order q -> caller index bt.order[q]): src_slot[q] = the slot that holds
 // the POSITIVE DEFINITE factor of particle q for exactly the prefix n (else -1), i0v[q] = nt for those (no tile row left to
 // compute).  Returns the number found; `lk` is held on return iff it is > 0 (the caller copies the factors out, then
@@ -644,39 +679,27 @@ static int toeplitz_sweep(agp_ctx* c, int64_t n, int32_t rank0, int P, const int
   Slot* s = sg.s;
   if (!s->stream) HIPCHK(c, hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
   hipStream_t st = s->stream;
-  auto al16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
-  const size_t o_tprm = al16(sizeof(LagTabHdr) * bt.thdr.size());
-  const size_t o_tops = al16(o_tprm + sizeof(double) * bt.tprm.size());
-  const size_t prog_bytes = al16(o_tops + bt.tops.size() + 4);
-  std::vector<char> hp(prog_bytes, 0);
-  if (!bt.thdr.empty()) {
-    std::memcpy(hp.data(), bt.thdr.data(), sizeof(LagTabHdr) * bt.thdr.size());
-    std::memcpy(hp.data() + o_tprm, bt.tprm.data(), sizeof(double) * bt.tprm.size());
-    std::memcpy(hp.data() + o_tops, bt.tops.data(), bt.tops.size());
-  }
+  const LagProgLayout lpl(bt);
   std::vector<double> nz((size_t)P);
   for (int q = 0; q < P; ++q) nz[(size_t)q] = noise[bt.order[q]];
   HIPCHK(c, s->hdr.ensure(sizeof(ProgHdr) * (size_t)P));
   HIPCHK(c, s->ops.ensure(bt.ops.size() + 4));
   HIPCHK(c, s->prm.ensure(sizeof(double) * std::max<size_t>(1, bt.prm.size())));
   HIPCHK(c, s->noise.ensure(sizeof(double) * (size_t)P));
-  HIPCHK(c, s->pl_prog.ensure(prog_bytes));
   HIPCHK(c, s->out_lp.ensure(sizeof(double) * (size_t)P + sizeof(int32_t) * (size_t)P));
   PinnedUploads up;
   up.add(s->hdr.p, bt.hdr.data(), sizeof(ProgHdr) * (size_t)P);
   up.add(s->ops.p, bt.ops.data(), bt.ops.size());
   up.add(s->prm.p, bt.prm.data(), sizeof(double) * bt.prm.size());
   up.add(s->noise.p, nz.data(), sizeof(double) * (size_t)P);
-  up.add(s->pl_prog.p, hp.data(), prog_bytes);
+  HIPCHK(c, lpl.upload(up, s->pl_prog));
   HIPCHK(c, up.flush(s->h_stage, s->up_blob, st));
   const int stride = rank_units * 256;
   if (bt.n_lag_tables > 0) {
     HIPCHK(c, s->lagtab.ensure(sizeof(double) * (size_t)bt.n_lag_tables * stride));
     LagArgs la = {};
-    la.tt = c->d_ts_s; la.thdr = s->pl_prog.as<LagTabHdr>();
-    la.tprm = reinterpret_cast<const double*>(static_cast<char*>(s->pl_prog.p) + o_tprm);
-    la.tops = reinterpret_cast<const uint8_t*>(static_cast<char*>(s->pl_prog.p) + o_tops);
-    la.n_tables = bt.n_lag_tables; la.tab = s->lagtab.as<double>();
+    la.tt = c->d_ts_s; la.tab = s->lagtab.as<double>();
+    lpl.point(la, s->pl_prog.p);
     la.nt = (int)((c->n_max + NB - 1) / NB); la.full = 1; la.stride = stride;
     launch_lag_tables(st, la, rank_units, bt.n_lag_tables);
     HIPCHK(c, hipGetLastError());
@@ -719,16 +742,7 @@ static int toeplitz_grad_sweep(agp_ctx* c, int64_t n, int32_t rank0, int P, cons
   Slot* s = sg.s;
   if (!s->stream) HIPCHK(c, hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
   hipStream_t st = s->stream;
-  auto al16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
-  const size_t o_tprm = al16(sizeof(LagTabHdr) * bt.thdr.size());
-  const size_t o_tops = al16(o_tprm + sizeof(double) * bt.tprm.size());
-  const size_t prog_bytes = al16(o_tops + bt.tops.size() + 4);
-  std::vector<char> hp(prog_bytes, 0);
-  if (!bt.thdr.empty()) {
-    std::memcpy(hp.data(), bt.thdr.data(), sizeof(LagTabHdr) * bt.thdr.size());
-    std::memcpy(hp.data() + o_tprm, bt.tprm.data(), sizeof(double) * bt.tprm.size());
-    std::memcpy(hp.data() + o_tops, bt.tops.data(), bt.tops.size());
-  }
+  const LagProgLayout lpl(bt);
   const int n_pad = round_up(n, NB);
   const int n_prm_total = prm_off[P];
   std::vector<double> nz((size_t)P);
@@ -740,7 +754,6 @@ static int toeplitz_grad_sweep(agp_ctx* c, int64_t n, int32_t rank0, int P, cons
   HIPCHK(c, s->ops.ensure(bt.ops.size() + 4));
   HIPCHK(c, s->prm.ensure(sizeof(double) * std::max<size_t>(1, bt.prm.size())));
   HIPCHK(c, s->noise.ensure(sizeof(double) * (size_t)P));
-  HIPCHK(c, s->pl_prog.ensure(prog_bytes));
   HIPCHK(c, s->out_lp.ensure(sizeof(double) * (size_t)P + sizeof(int32_t) * (size_t)P));
   HIPCHK(c, s->A.ensure((size_t)Lstride * 8 * chunk));
   HIPCHK(c, s->tsol.ensure(sizeof(double) * 4 * (size_t)n_pad * chunk));
@@ -761,7 +774,7 @@ static int toeplitz_grad_sweep(agp_ctx* c, int64_t n, int32_t rank0, int P, cons
   up.add(s->ops.p, bt.ops.data(), bt.ops.size());
   up.add(s->prm.p, bt.prm.data(), sizeof(double) * bt.prm.size());
   up.add(s->noise.p, nz.data(), sizeof(double) * (size_t)P);
-  up.add(s->pl_prog.p, hp.data(), prog_bytes);
+  HIPCHK(c, lpl.upload(up, s->pl_prog));
   up.add(s->ghdr.p, bt.ghdr.data(), sizeof(GProgHdr) * (size_t)P);
   up.add(s->gops.p, bt.gops.data(), bt.gops.size());
   up.add(s->glc.p, bt.glc.data(), bt.glc.size());
@@ -780,10 +793,8 @@ static int toeplitz_grad_sweep(agp_ctx* c, int64_t n, int32_t rank0, int P, cons
   if (bt.n_lag_tables > 0) {
     HIPCHK(c, s->lagtab.ensure(sizeof(double) * (size_t)bt.n_lag_tables * stride));
     LagArgs la = {};
-    la.tt = c->d_ts_s; la.thdr = s->pl_prog.as<LagTabHdr>();
-    la.tprm = reinterpret_cast<const double*>(static_cast<char*>(s->pl_prog.p) + o_tprm);
-    la.tops = reinterpret_cast<const uint8_t*>(static_cast<char*>(s->pl_prog.p) + o_tops);
-    la.n_tables = bt.n_lag_tables; la.tab = s->lagtab.as<double>();
+    la.tt = c->d_ts_s; la.tab = s->lagtab.as<double>();
+    lpl.point(la, s->pl_prog.p);
     la.nt = (int)((c->n_max + NB - 1) / NB); la.full = 1; la.stride = stride;
     launch_lag_tables(st, la, rank_units, bt.n_lag_tables);
     HIPCHK(c, hipGetLastError());
@@ -895,53 +906,44 @@ int logpdf_batch_impl(agp_ctx* c, int64_t n, int32_t P, const int32_t* op_off, c
     // measured with 128 threads, 106 class particles: 294 -> 262 HMC iterations/s with the value sweep's own, lower threshold)
     const bool pays = tl_dense_via_store ? struct_grad_pays(n_cls_v, n) : struct_value_pays(n_cls_v, n);          // (agp_host.hpp: shared with agp_shard_plan)
     if (sane && !part[1].empty() && (c->toeplitz >= 2 || pays)) {
-      auto gather = [&](const std::vector<int>& ix, std::vector<int32_t>& oo, std::vector<uint8_t>& so, std::vector<int32_t>& po,
-                        std::vector<double>& sp, std::vector<double>& nz) {
-        oo.assign(ix.size() + 1, 0); po.assign(ix.size() + 1, 0); nz.resize(ix.size()); so.clear(); sp.clear();
-        for (size_t b = 0; b < ix.size(); ++b) {
-          const int p = ix[b];
-          so.insert(so.end(), ops + op_off[p], ops + op_off[p + 1]);
-          sp.insert(sp.end(), prm + prm_off[p], prm + prm_off[p + 1]);
-          oo[b + 1] = (int32_t)so.size(); po[b + 1] = (int32_t)sp.size(); nz[b] = noise[p];
-        }
-        if (sp.empty()) sp.push_back(0.0);
-      };
       // the two sub-sweeps (own slots and streams)
       const bool via_store = tl_dense_via_store;          // (read here: the structured half may run on a helper thread)
-      struct Sub { std::vector<int32_t> oo, po, info; std::vector<uint8_t> so; std::vector<double> sp, nz, lp; int rc = 0; } sT, sD;
-      gather(part[1], sT.oo, sT.so, sT.po, sT.sp, sT.nz);
-      sT.lp.resize(part[1].size()); sT.info.assign(part[1].size(), 0);
+      SubBatch sT, sD;
+      pack_particles(part[1], op_off, ops, prm_off, prm, noise, nullptr, sT);
+      sT.outputs(false);
       auto structured = [&] {
-        return toeplitz_sweep(c, n, value_rank0, (int)part[1].size(), sT.oo.data(), sT.so.data(), sT.po.data(), sT.sp.data(), sT.nz.data(), sT.lp.data(),
-                              sT.info.data());
+        return toeplitz_sweep(c, n, value_rank0, sT.size(), sT.op_off.data(), sT.ops.data(), sT.prm_off.data(), sT.prm.data(), sT.noise.data(),
+                              sT.lp.data(), sT.info.data());
       };
       // (measured: 107 recursions beside the dense kernels at n = 4096: 18.1 -> 13.8 ms; 423 of them at n = 2048 fill every SIMD
       // with their own waves and only delay the dense kernels: 8.6 -> 9.2 ms — those go first, alone)
       // (the same in the coalesced entry's class-aware mode: value sweeps of the HMC replay 11.9 ms either way)
       const bool side_by_side = part[1].size() <= 256;
       std::unique_ptr<Beside> side;
-      if (side_by_side) side.reset(new Beside(structured)); else sT.rc = structured();
+      int rcT = 0;
+      if (side_by_side) side.reset(new Beside(structured)); else rcT = structured();
       auto dense = [&](const std::vector<int>& ix) {
         if (ix.empty()) return 0;
-        gather(ix, sD.oo, sD.so, sD.po, sD.sp, sD.nz);
-        sD.lp.resize(ix.size()); sD.info.assign(ix.size(), 0);
+        pack_particles(ix, op_off, ops, prm_off, prm, noise, nullptr, sD);
+        sD.outputs(false);
         TlFlag nested(tl_in_toeplitz);
         int rc0;
         if (via_store) {
           TlClear plain(tl_dense_via_store);
-          rc0 = extend_impl(c, n, (int)ix.size(), sD.oo.data(), sD.so.data(), sD.po.data(), sD.sp.data(), sD.nz.data(), sD.lp.data(), sD.info.data());
+          rc0 = extend_impl(c, n, sD.size(), sD.op_off.data(), sD.ops.data(), sD.prm_off.data(), sD.prm.data(), sD.noise.data(), sD.lp.data(),
+                            sD.info.data());
         } else {
-          rc0 = logpdf_batch_impl(c, n, (int)ix.size(), sD.oo.data(), sD.so.data(), sD.po.data(), sD.sp.data(), sD.nz.data(), sD.lp.data(),
-                                  sD.info.data(), nullptr, nullptr, nullptr, false, nullptr, allow_lag);
+          rc0 = logpdf_batch_impl(c, n, sD.size(), sD.op_off.data(), sD.ops.data(), sD.prm_off.data(), sD.prm.data(), sD.noise.data(),
+                                  sD.lp.data(), sD.info.data(), nullptr, nullptr, nullptr, false, nullptr, allow_lag);
         }
         if (rc0) return rc0;
         for (size_t b2 = 0; b2 < ix.size(); ++b2) { h_out_lp[ix[b2]] = sD.lp[b2]; if (h_out_info) h_out_info[ix[b2]] = sD.info[b2]; }
         return 0;
       };
       const int rcD = dense(part[0]);
-      if (side) sT.rc = side->join();
+      if (side) rcT = side->join();
       if (rcD) return rcD;
-      if (sT.rc) return sT.rc;
+      if (rcT) return rcT;
       std::vector<int> refused;
       int64_t n_done = 0;
       for (size_t b2 = 0; b2 < part[1].size(); ++b2) {
@@ -1096,50 +1098,40 @@ int logpdf_batch_impl(agp_ctx* c, int64_t n, int32_t P, const int32_t* op_off, c
         h_out_lp && !d_user_lp && !d_user_info && !use_user_stream && (!store_live || c->toeplitz)) {
       std::vector<int> part[2];
       for (int q = 0; q < P; ++q) part[((bt.ghdr[q].flags & GFLAG_LAGTOEP) && !resident[(size_t)q]) ? 1 : 0].push_back(bt.order[q]);
-      struct Sub { std::vector<int32_t> oo, po, info; std::vector<uint8_t> so; std::vector<double> sp, nz, lp, grad, gn; int rc = 0; } sT, sD;
-      auto gather = [&](const std::vector<int>& ix, Sub& S) {
-        S.oo.assign(ix.size() + 1, 0); S.po.assign(ix.size() + 1, 0); S.nz.resize(ix.size()); S.so.clear(); S.sp.clear();
-        for (size_t b = 0; b < ix.size(); ++b) {
-          const int p = ix[b];
-          S.so.insert(S.so.end(), ops + op_off[p], ops + op_off[p + 1]);
-          S.sp.insert(S.sp.end(), prm + prm_off[p], prm + prm_off[p + 1]);
-          S.oo[b + 1] = (int32_t)S.so.size(); S.po[b + 1] = (int32_t)S.sp.size(); S.nz[b] = noise[p];
-        }
-        S.grad.assign(std::max<size_t>(1, S.sp.size()), 0.0);
-        if (S.sp.empty()) S.sp.push_back(0.0);
-        S.lp.assign(ix.size(), 0.0); S.gn.assign(ix.size(), 0.0); S.info.assign(ix.size(), 0);
-      };
-      auto scatter = [&](const std::vector<int>& ix, const Sub& S, std::vector<int>* refused) {
+      SubBatch sT, sD;
+      auto scatter = [&](const std::vector<int>& ix, const SubBatch& S, std::vector<int>* refused) {
         for (size_t b = 0; b < ix.size(); ++b) {
           const int p = ix[b];
           if (refused && S.info[b] != 0) { refused->push_back(p); continue; }
           h_out_lp[p] = S.lp[b];
           if (h_out_info) h_out_info[p] = S.info[b];
-          std::copy(S.grad.begin() + S.po[b], S.grad.begin() + S.po[b + 1], go->grad + prm_off[p]);
-          go->gnoise[p] = S.gn[b];
+          std::copy(S.grad.begin() + S.prm_off[b], S.grad.begin() + S.prm_off[b + 1], go->grad + prm_off[p]);
+          go->gnoise[p] = S.gnoise[b];
         }
       };
       auto dense = [&](const std::vector<int>& ix) {
         if (ix.empty()) return 0;
-        gather(ix, sD);
-        GradOut dgo{sD.grad.data(), sD.gn.data()};
+        pack_particles(ix, op_off, ops, prm_off, prm, noise, nullptr, sD);
+        sD.outputs(true);
+        GradOut dgo{sD.grad.data(), sD.gnoise.data()};
         TlFlag nested(tl_in_tgrad);
-        const int rc0 = logpdf_batch_impl(c, n, (int)ix.size(), sD.oo.data(), sD.so.data(), sD.po.data(), sD.sp.data(), sD.nz.data(), sD.lp.data(),
-                                          sD.info.data(), nullptr, nullptr, nullptr, false, &dgo, allow_lag);
+        const int rc0 = logpdf_batch_impl(c, n, sD.size(), sD.op_off.data(), sD.ops.data(), sD.prm_off.data(), sD.prm.data(), sD.noise.data(),
+                                          sD.lp.data(), sD.info.data(), nullptr, nullptr, nullptr, false, &dgo, allow_lag);
         if (rc0) return rc0;
         scatter(ix, sD, nullptr);
         return 0;
       };
-      gather(part[1], sT);
+      pack_particles(part[1], op_off, ops, prm_off, prm, noise, nullptr, sT);
+      sT.outputs(true);
       Beside side([&] {
-        return toeplitz_grad_sweep(c, n, toep_rank0, (int)part[1].size(), sT.oo.data(), sT.so.data(), sT.po.data(), sT.sp.data(), sT.nz.data(),
-                                   sT.lp.data(), sT.info.data(), sT.grad.data(), sT.gn.data());
+        return toeplitz_grad_sweep(c, n, toep_rank0, sT.size(), sT.op_off.data(), sT.ops.data(), sT.prm_off.data(), sT.prm.data(), sT.noise.data(),
+                                   sT.lp.data(), sT.info.data(), sT.grad.data(), sT.gnoise.data());
       });
       const int rcD = dense(part[0]);
-      sT.rc = side.join();
+      const int rcT = side.join();
       if (lagr) { std::lock_guard<std::mutex> g(c->mu); if (!part[0].empty()) --c->n_lag_rank_sweeps; }          // (one sweep, as far as the counters go)
       if (rcD) return rcD;
-      if (sT.rc) return sT.rc;
+      if (rcT) return rcT;
       std::vector<int> refused;
       scatter(part[1], sT, &refused);
       {
@@ -1242,18 +1234,15 @@ int logpdf_batch_impl(agp_ctx* c, int64_t n, int32_t P, const int32_t* op_off, c
       HIPCHK(c, s->flowq.ensure(sizeof(int) * 8 * 8));
     }
     // ---- one pinned-memory upload: [hdr | prm | noise (sorted) | map | ops], 16-byte aligned sections ----
-    auto al16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
     const size_t o_hdr = 0;
-    const size_t o_prm = al16(o_hdr + sizeof(ProgHdr) * (size_t)P);
-    const size_t o_noise = al16(o_prm + sizeof(double) * std::max<size_t>(1, bt.prm.size()));
-    const size_t o_map = al16(o_noise + sizeof(double) * (size_t)P);
-    const size_t o_ops = al16(o_map + sizeof(int32_t) * (size_t)P);
-    const size_t o_src = al16(o_ops + bt.ops.size() + 4);                       // resident-factor slots / first rows (n_hit > 0)
-    const size_t o_i0 = al16(o_src + (n_hit > 0 ? sizeof(int32_t) * (size_t)P : 0));
-    const size_t o_thdr = al16(o_i0 + (n_hit > 0 ? sizeof(int32_t) * (size_t)P : 0));      // lag-table programs (lag sweeps)
-    const size_t o_tprm = al16(o_thdr + sizeof(LagTabHdr) * bt.thdr.size());
-    const size_t o_tops = al16(o_tprm + sizeof(double) * bt.tprm.size());
-    const size_t stage_bytes = al16(o_tops + bt.tops.size() + 4);
+    const size_t o_prm = align16(o_hdr + sizeof(ProgHdr) * (size_t)P);
+    const size_t o_noise = align16(o_prm + sizeof(double) * std::max<size_t>(1, bt.prm.size()));
+    const size_t o_map = align16(o_noise + sizeof(double) * (size_t)P);
+    const size_t o_ops = align16(o_map + sizeof(int32_t) * (size_t)P);
+    const size_t o_src = align16(o_ops + bt.ops.size() + 4);                    // resident-factor slots / first rows (n_hit > 0)
+    const size_t o_i0 = align16(o_src + (n_hit > 0 ? sizeof(int32_t) * (size_t)P : 0));
+    const LagProgLayout lpl(bt, o_i0 + (n_hit > 0 ? sizeof(int32_t) * (size_t)P : 0));      // lag-table programs (lag sweeps)
+    const size_t stage_bytes = lpl.end;
     HIPCHK(c, s->stage.ensure(stage_bytes));
     HIPCHK(c, s->h_stage.ensure(stage_bytes));
     {
@@ -1268,11 +1257,7 @@ int logpdf_batch_impl(agp_ctx* c, int64_t n, int32_t P, const int32_t* op_off, c
         std::memcpy(h + o_src, src_slot.data(), sizeof(int32_t) * (size_t)P);
         std::memcpy(h + o_i0, i0v.data(), sizeof(int32_t) * (size_t)P);
       }
-      if (!bt.thdr.empty()) {
-        std::memcpy(h + o_thdr, bt.thdr.data(), sizeof(LagTabHdr) * bt.thdr.size());
-        std::memcpy(h + o_tprm, bt.tprm.data(), sizeof(double) * bt.tprm.size());
-        std::memcpy(h + o_tops, bt.tops.data(), bt.tops.size());
-      }
+      lpl.pack(h);
     }
     char* dstage = static_cast<char*>(s->stage.p);
     ProgHdr* d_hdr = reinterpret_cast<ProgHdr*>(dstage + o_hdr);
@@ -1308,9 +1293,8 @@ int logpdf_batch_impl(agp_ctx* c, int64_t n, int32_t P, const int32_t* op_off, c
       // the sweep's lag tables: every stationary leaf of every particle at the 255 lags of each of the nt block diagonals
       // (sorted sweep) / at every lag 0 .. n_max-1 of the series (rank tables)
       LagArgs la = {};
-      la.tt = (cltw || clts) ? c->d_clt_tt : lagr ? c->d_ts_lat : c->d_ts_s; la.thdr = reinterpret_cast<const LagTabHdr*>(dstage + o_thdr);
-      la.tops = reinterpret_cast<const uint8_t*>(dstage + o_tops); la.tprm = reinterpret_cast<const double*>(dstage + o_tprm);
-      la.n_tables = bt.n_lag_tables;
+      la.tt = (cltw || clts) ? c->d_clt_tt : lagr ? c->d_ts_lat : c->d_ts_s;
+      lpl.point(la, dstage);
       if (rankm) {
         // (compact tables: entry e at the "time" d_clt_tt[e] = its lattice lag x h, every entry of the padded table is evaluated)
         HIPCHK(c, s->lagtab.ensure(sizeof(double) * (size_t)bt.n_lag_tables * tab_gstride));
@@ -1640,31 +1624,23 @@ int logpdf_batch_impl(agp_ctx* c, int64_t n, int32_t P, const int32_t* op_off, c
     for (int p = 0; p < P; ++p) if (toep_retry[(size_t)p] != 0) rp.push_back(p);
     if (!rp.empty()) {
       const int B = (int)rp.size();
-      std::vector<int32_t> bo(B + 1, 0), bp(B + 1, 0), binfo(B, 0);
-      std::vector<uint8_t> bops; std::vector<double> bprm, bnoise(B), blp(B), bgn(B);
-      for (int b = 0; b < B; ++b) {
-        const int p = rp[b];
-        bops.insert(bops.end(), ops + op_off[p], ops + op_off[p + 1]);
-        bprm.insert(bprm.end(), prm + prm_off[p], prm + prm_off[p + 1]);
-        bo[b + 1] = (int32_t)bops.size(); bp[b + 1] = (int32_t)bprm.size();
-        bnoise[b] = noise[p];
-      }
-      std::vector<double> bgrad(std::max<size_t>(1, bprm.size()));
-      if (bprm.empty()) bprm.push_back(0.0);
-      GradOut bgo{bgrad.data(), bgn.data()};
+      SubBatch S;
+      pack_particles(rp, op_off, ops, prm_off, prm, noise, nullptr, S);
+      S.outputs(true);
+      GradOut bgo{S.grad.data(), S.gnoise.data()};
       if (store_lk.owns_lock()) store_lk.unlock();
       sg.release();
       int rc2;
       {
         TlFlag nested(tl_no_toep);
-        rc2 = logpdf_batch_impl(c, n, B, bo.data(), bops.data(), bp.data(), bprm.data(), bnoise.data(), blp.data(), binfo.data(),
-                                nullptr, nullptr, nullptr, false, &bgo, allow_lag);
+        rc2 = logpdf_batch_impl(c, n, B, S.op_off.data(), S.ops.data(), S.prm_off.data(), S.prm.data(), S.noise.data(), S.lp.data(),
+                                S.info.data(), nullptr, nullptr, nullptr, false, &bgo, allow_lag);
       }
       if (rc2) return rc2;
       for (int b = 0; b < B; ++b) {
         const int p = rp[b];
-        std::copy(bgrad.begin() + bp[b], bgrad.begin() + bp[b + 1], go->grad + prm_off[p]);
-        go->gnoise[p] = bgn[b];
+        std::copy(S.grad.begin() + S.prm_off[b], S.grad.begin() + S.prm_off[b + 1], go->grad + prm_off[p]);
+        go->gnoise[p] = S.gnoise[b];
       }
       std::lock_guard<std::mutex> g(c->mu);
       c->n_toep_particles -= B;
@@ -1679,26 +1655,19 @@ int logpdf_batch_impl(agp_ctx* c, int64_t n, int32_t P, const int32_t* op_off, c
     for (int p = 0; p < P; ++p) if (h_info[p] > 0) bad.push_back(p);
     if (!bad.empty()) {
       const int B = (int)bad.size();
-      std::vector<int32_t> bo(B + 1, 0), bp(B + 1, 0), binfo(B);
-      std::vector<uint8_t> bops; std::vector<double> bprm, bnoise(B), blp(B);
-      for (int b = 0; b < B; ++b) {
-        const int p = bad[b];
-        bops.insert(bops.end(), ops + op_off[p], ops + op_off[p + 1]);
-        bprm.insert(bprm.end(), prm + prm_off[p], prm + prm_off[p + 1]);
-        bo[b + 1] = (int32_t)bops.size(); bp[b + 1] = (int32_t)bprm.size();
-        bnoise[b] = noise[p];
-      }
-      if (bprm.empty()) bprm.push_back(0.0);
+      SubBatch S;
+      pack_particles(bad, op_off, ops, prm_off, prm, noise, nullptr, S);
+      S.outputs(false);
       // (the results are on the host: hand the slot back first — sixteen concurrent callers that each kept theirs while waiting
       // for a second one would wait for ever)
       sg.release();
-      const int rc2 = logpdf_batch_impl(c, n, B, bo.data(), bops.data(), bp.data(), bprm.data(), bnoise.data(), blp.data(), binfo.data(),
-                                        nullptr, nullptr, nullptr, false, nullptr, /*allow_lag=*/false);
+      const int rc2 = logpdf_batch_impl(c, n, B, S.op_off.data(), S.ops.data(), S.prm_off.data(), S.prm.data(), S.noise.data(), S.lp.data(),
+                                        S.info.data(), nullptr, nullptr, nullptr, false, nullptr, /*allow_lag=*/false);
       if (rc2) return rc2;
       for (int b = 0; b < B; ++b) {
         // (a matrix that is indefinite to rounding may factor in one order and not in the other: the caller's order decides)
-        h_out_info[bad[b]] = binfo[b];
-        if (h_out_lp) h_out_lp[bad[b]] = blp[b];
+        h_out_info[bad[b]] = S.info[b];
+        if (h_out_lp) h_out_lp[bad[b]] = S.lp[b];
       }
     }
   }
@@ -2207,56 +2176,30 @@ static int set_data_body(agp_ctx* c, const double* ts, const double* xs, int64_t
 static int logpdf_batch_dedup(agp_ctx* c, int64_t n, int32_t P, const int32_t* op_off, const uint8_t* ops,
                               const int32_t* prm_off, const double* prm, const double* noise, double* out_logpdf,
                               int32_t* out_info, GradOut* go) {
-  if (!c || !c->dedup || P < 2 || !op_off || !ops || !prm_off || !prm || !noise)
-    return logpdf_batch_impl(c, n, P, op_off, ops, prm_off, prm, noise, out_logpdf, out_info, nullptr, nullptr,
-                             nullptr, false, go);
-  for (int p = 0; p < P; ++p)     // malformed offsets are diagnosed by the sweep itself
-    if (op_off[p + 1] < op_off[p] || prm_off[p + 1] < prm_off[p] || op_off[p] < 0 || prm_off[p] < 0)
-      return logpdf_batch_impl(c, n, P, op_off, ops, prm_off, prm, noise, out_logpdf, out_info, nullptr, nullptr,
-                               nullptr, false, go);
+  auto plain = [&] {
+    return logpdf_batch_impl(c, n, P, op_off, ops, prm_off, prm, noise, out_logpdf, out_info, nullptr, nullptr, nullptr, false, go);
+  };
+  if (!c || !c->dedup || P < 2 || !op_off || !ops || !prm_off || !prm || !noise) return plain();
   HostProf hp_dd(1);
-  std::unordered_map<std::string, int> seen;
-  seen.reserve((size_t)P * 2);
-  std::vector<int> rep(P), uniq;
-  std::string key;
-  for (int p = 0; p < P; ++p) {
-    const int no = op_off[p + 1] - op_off[p], np = prm_off[p + 1] - prm_off[p];
-    const int32_t lens[2] = {no, np};          // length-delimited fields: (a ops, b prm) never collides with (a+8, b-1)
-    key.assign(reinterpret_cast<const char*>(lens), sizeof lens);
-    key.append(reinterpret_cast<const char*>(ops + op_off[p]), (size_t)no);
-    key.append(reinterpret_cast<const char*>(prm + prm_off[p]), sizeof(double) * (size_t)np);
-    key.append(reinterpret_cast<const char*>(noise + p), sizeof(double));
-    auto it = seen.find(key);
-    if (it == seen.end()) { seen.emplace(key, (int)uniq.size()); rep[p] = (int)uniq.size(); uniq.push_back(p); }
-    else rep[p] = it->second;
-  }
+  std::vector<int> rep, uniq;
+  if (!distinct_particles(P, op_off, ops, prm_off, prm, noise, nullptr, rep, uniq)) return plain();     // malformed offsets are diagnosed by the sweep itself
   const int U = (int)uniq.size();
   { std::lock_guard<std::mutex> g(c->mu); c->n_particles_seen += P; c->n_particles_run += U; }
   hp_dd.stop();
-  if (U == P)
-    return logpdf_batch_impl(c, n, P, op_off, ops, prm_off, prm, noise, out_logpdf, out_info, nullptr, nullptr,
-                             nullptr, false, go);
-  std::vector<int32_t> uo(U + 1, 0), up(U + 1, 0), uinfo(U);
-  std::vector<uint8_t> uops; std::vector<double> uprm, unoise(U), ulp(U), ugn(go ? U : 0);
-  for (int u = 0; u < U; ++u) {
-    const int p = uniq[u];
-    uops.insert(uops.end(), ops + op_off[p], ops + op_off[p + 1]);
-    uprm.insert(uprm.end(), prm + prm_off[p], prm + prm_off[p + 1]);
-    uo[u + 1] = (int32_t)uops.size(); up[u + 1] = (int32_t)uprm.size();
-    unoise[u] = noise[p];
-  }
-  std::vector<double> ugrad(go ? std::max<size_t>(1, uprm.size()) : 0);
-  if (uprm.empty()) uprm.push_back(0.0);
-  GradOut ugo{ugrad.data(), ugn.data()};
-  const int rc = logpdf_batch_impl(c, n, U, uo.data(), uops.data(), up.data(), uprm.data(), unoise.data(), ulp.data(),
-                                   uinfo.data(), nullptr, nullptr, nullptr, false, go ? &ugo : nullptr);
+  if (U == P) return plain();
+  SubBatch S;
+  pack_particles(uniq, op_off, ops, prm_off, prm, noise, nullptr, S);
+  S.outputs(go != nullptr);
+  GradOut ugo{S.grad.data(), S.gnoise.data()};
+  const int rc = logpdf_batch_impl(c, n, U, S.op_off.data(), S.ops.data(), S.prm_off.data(), S.prm.data(), S.noise.data(), S.lp.data(),
+                                   S.info.data(), nullptr, nullptr, nullptr, false, go ? &ugo : nullptr);
   if (rc) return rc;
   for (int p = 0; p < P; ++p) {
     const int u = rep[p];
-    out_logpdf[p] = ulp[u]; out_info[p] = uinfo[u];
+    out_logpdf[p] = S.lp[u]; out_info[p] = S.info[u];
     if (go) {
-      go->gnoise[p] = ugn[u];
-      std::copy(ugrad.begin() + up[u], ugrad.begin() + up[u + 1], go->grad + prm_off[p]);
+      go->gnoise[p] = S.gnoise[u];
+      std::copy(S.grad.begin() + S.prm_off[u], S.grad.begin() + S.prm_off[u + 1], go->grad + prm_off[p]);
     }
   }
   return AGP_OK;

@@ -475,6 +475,59 @@ int compile_batch(agp_ctx* c, int P, const int32_t* op_off, const uint8_t* ops, 
                   bool fuse_hint = false, bool flow_limit = false, bool lag = false, int lag_units = 1, int rank_extra = 0,
                   bool never_fuse = false);
 
+inline size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
+
+// The lag-table programs of a compiled batch as one device blob [thdr | tprm | tops + 4], sections 16-byte aligned from `base` on
+// (a buffer of their own: base 0; or the tail of a sweep's staging blob).
+struct LagProgLayout {
+  const Batch& bt;
+  size_t o_thdr, o_tprm, o_tops, end;
+  explicit LagProgLayout(const Batch& b, size_t base = 0)
+      : bt(b), o_thdr(align16(base)), o_tprm(align16(o_thdr + sizeof(LagTabHdr) * b.thdr.size())),
+        o_tops(align16(o_tprm + sizeof(double) * b.tprm.size())), end(align16(o_tops + b.tops.size() + 4)) {}
+  // the three sections into the host image of the blob (padding is left as it is)
+  void pack(char* h) const {
+    if (bt.thdr.empty()) return;
+    std::memcpy(h + o_thdr, bt.thdr.data(), sizeof(LagTabHdr) * bt.thdr.size());
+    std::memcpy(h + o_tprm, bt.tprm.data(), sizeof(double) * bt.tprm.size());
+    std::memcpy(h + o_tops, bt.tops.data(), bt.tops.size());
+  }
+  // a buffer of their own: the zero-padded blob through `up`
+  hipError_t upload(PinnedUploads& up, DevBuf& dev) const {
+    std::vector<char> h(end, 0);
+    pack(h.data());
+    const hipError_t e = dev.ensure(end);
+    if (e == hipSuccess) up.add(dev.p, h.data(), end);
+    return e;
+  }
+  // the programs of k_lag_tables, the blob on the device at `dev` (tt, tab, nt, full and stride are the caller's)
+  void point(LagArgs& la, const void* dev) const {
+    const char* d = static_cast<const char*>(dev);
+    la.thdr = reinterpret_cast<const LagTabHdr*>(d + o_thdr);
+    la.tprm = reinterpret_cast<const double*>(d + o_tprm);
+    la.tops = reinterpret_cast<const uint8_t*>(d + o_tops);
+    la.n_tables = bt.n_lag_tables;
+  }
+};
+
+// Some particles of a caller's batch packed into a batch of their own, in the order of the index list: offsets, concatenated
+// programs / parameters (an empty parameter array holds one 0.0: never a null pointer), noises; noise_pred when the caller passes
+// one.  lp / info / grad / gnoise: the sub-batch's outputs, sized by outputs().
+struct SubBatch {
+  std::vector<int32_t> op_off, prm_off;
+  std::vector<uint8_t> ops;
+  std::vector<double> prm, noise, noise_pred;
+  std::vector<double> lp, grad, gnoise;
+  std::vector<int32_t> info;
+  int size() const { return (int)noise.size(); }
+  void outputs(bool with_grad) {
+    lp.assign(noise.size(), 0.0); info.assign(noise.size(), 0);
+    if (with_grad) { grad.assign(prm.size(), 0.0); gnoise.assign(noise.size(), 0.0); }
+  }
+};
+void pack_particles(const std::vector<int>& ix, const int32_t* op_off, const uint8_t* ops, const int32_t* prm_off, const double* prm,
+                    const double* noise, const double* noise_pred, SubBatch& S);
+
 // A tile evaluation longer than this (cost model op_cost_us: measured per-leaf cost of one 128x128 tile with two workgroups per
 // CU) would set the duration of the short launches; such particles get their tiles from k_cov_tiles.  Measured: per-column
 // launches 25 vs 35 us: 29.28 vs 29.6 ms at 512 particles; dataflow schedule 35 / 70 / 150 / 1000 us: config 2 0.99 / 0.92 / 0.92 /
@@ -614,6 +667,12 @@ bool toeplitz_class(const uint8_t* ops, int n_ops);
 
 // key of a particle in the factor store: the bits of (program, parameters, noise)
 std::string particle_key(const uint8_t* ops, int no, const double* prm, int np, double noise);
+
+// Distinct particles of a batch (a resampled population holds copies of its survivors), keyed by particle_key (+ the bits of
+// noise_pred[p] when given): uniq = the first particle of each, in the caller's order; rep[p] = the position in uniq of p's;
+// keys (optional) = uniq's keys.  False, with everything empty, on offsets that are negative or decreasing: the caller decides.
+bool distinct_particles(int P, const int32_t* op_off, const uint8_t* ops, const int32_t* prm_off, const double* prm, const double* noise,
+                        const double* noise_pred, std::vector<int>& rep, std::vector<int>& uniq, std::vector<std::string>* keys = nullptr);
 
 hipError_t run_factor_extend(hipStream_t st, CholArgs ca, int dcov, bool split_diag, int i0min, int nfac = -1);
 int extend_impl(agp_ctx* c, int64_t n, int32_t P, const int32_t* op_off, const uint8_t* ops, const int32_t* prm_off,

@@ -97,22 +97,15 @@ int agp_shard_plan(int64_t n, int32_t P, const int32_t* op_off, const uint8_t* o
     // On a lattice WITH gaps the class keeps its dense factor, L^-T and K^-1; only its contraction runs over the lattice's lags
     // (measured on 2048 business days: 100.9 -> 96.5 ms per 512-particle gradient sweep)
     const double lagdom_gaps = sweep == 1 ? dense - 0.15 : dense;
-    std::unordered_map<std::string, int> seen;
-    seen.reserve((size_t)P * 2);
-    std::vector<int> rep((size_t)P);
+    std::vector<int> rep, uniq;
+    (void)distinct_particles(P, op_off, ops, prm_off, prm, noise, nullptr, rep, uniq);      // (offsets checked above)
     std::vector<double> cost((size_t)P, 0.0);
     std::vector<char> is_cls((size_t)P, 0);
-    std::vector<int> uniq;
     int64_t n_cls = 0;
-    for (int p = 0; p < P; ++p) {
-      const int no = op_off[p + 1] - op_off[p], np = prm_off[p + 1] - prm_off[p];
-      auto it = seen.emplace(particle_key(ops + op_off[p], no, prm + prm_off[p], np, noise[p]), p);
-      rep[(size_t)p] = it.first->second;
-      if (it.second) {
-        uniq.push_back(p);
-        is_cls[(size_t)p] = (kind != 0 && sweep >= 1 && no <= AGP_MAX_OPS_DEV && toeplitz_class(ops + op_off[p], no)) ? 1 : 0;
-        n_cls += is_cls[(size_t)p];
-      }
+    for (int p : uniq) {
+      const int no = op_off[p + 1] - op_off[p];
+      is_cls[(size_t)p] = (kind != 0 && sweep >= 1 && no <= AGP_MAX_OPS_DEV && toeplitz_class(ops + op_off[p], no)) ? 1 : 0;
+      n_cls += is_cls[(size_t)p];
     }
     // The structured sweeps are admitted by the ENGINE's own tests (agp_host.hpp: struct_*_admits — the same predicates the sweeps
     // apply), on the class particles ONE rank will hold (~ n_cls / n_ranks): a class the engine would refuse is priced densely,
@@ -129,15 +122,16 @@ int agp_shard_plan(int64_t n, int32_t P, const int32_t* op_off, const uint8_t* o
       cost[(size_t)p] = !is_cls[(size_t)p] ? (sweep == 3 ? 1.0 : dense)
                         : structured ? std::min(toep, dense)
                         : sweep == 3 ? 1.0 : sweep == 1 ? toep_solves : dense;
-    std::stable_sort(uniq.begin(), uniq.end(), [&](int a, int b) { return cost[(size_t)a] > cost[(size_t)b]; });
+    std::vector<int> by_cost = uniq;
+    std::stable_sort(by_cost.begin(), by_cost.end(), [&](int a, int b) { return cost[(size_t)a] > cost[(size_t)b]; });
     std::vector<double> load((size_t)n_ranks, 0.0);
-    for (int p : uniq) {
+    for (int p : by_cost) {
       int best = 0;
       for (int r = 1; r < n_ranks; ++r) if (load[(size_t)r] < load[(size_t)best]) best = r;
       owner_out[p] = best;
       load[(size_t)best] += cost[(size_t)p];
     }
-    for (int p = 0; p < P; ++p) owner_out[p] = owner_out[rep[(size_t)p]];
+    for (int p = 0; p < P; ++p) owner_out[p] = owner_out[uniq[(size_t)rep[(size_t)p]]];
     if (cost_out) for (int p = 0; p < P; ++p) cost_out[p] = cost[(size_t)p];
     if (rank_cost_out) for (int r = 0; r < n_ranks; ++r) rank_cost_out[r] = load[(size_t)r];
   } catch (...) { return fail(nullptr, AGP_ERR_HOST, "host allocation failed"); }
@@ -462,26 +456,13 @@ int agp_logpdf_batch_extend_multi(agp_ctx* const* ctxs, int32_t n_dev, int64_t n
 // contexts need not share a communicator (several contexts of ONE device work too: that is how a one-GPU box tests the split).
 namespace {
 
-struct ShardPack {
-  std::vector<int> idx;
-  std::vector<int32_t> oo, po;
-  std::vector<uint8_t> so;
-  std::vector<double> sp, nz;
-};
-
+// the particles device d owns, packed (an empty program array holds one byte: never a null pointer)
 void pack_shard(int32_t P, const int32_t* op_off, const uint8_t* ops, const int32_t* prm_off, const double* prm, const double* noise,
-                const int32_t* owner, int d, ShardPack& S) {
-  S.idx.clear(); S.so.clear(); S.sp.clear(); S.nz.clear();
-  for (int p = 0; p < P; ++p) if (owner[p] == d) S.idx.push_back(p);
-  S.oo.assign(S.idx.size() + 1, 0); S.po.assign(S.idx.size() + 1, 0);
-  for (size_t b = 0; b < S.idx.size(); ++b) {
-    const int p = S.idx[b];
-    S.so.insert(S.so.end(), ops + op_off[p], ops + op_off[p + 1]);
-    S.sp.insert(S.sp.end(), prm + prm_off[p], prm + prm_off[p + 1]);
-    S.oo[b + 1] = (int32_t)S.so.size(); S.po[b + 1] = (int32_t)S.sp.size(); S.nz.push_back(noise[p]);
-  }
-  if (S.sp.empty()) S.sp.push_back(0.0);
-  if (S.so.empty()) S.so.push_back(0);
+                const double* noise_pred, const int32_t* owner, int d, std::vector<int>& idx, SubBatch& S) {
+  idx.clear();
+  for (int p = 0; p < P; ++p) if (owner[p] == d) idx.push_back(p);
+  pack_particles(idx, op_off, ops, prm_off, prm, noise, noise_pred, S);
+  if (S.ops.empty()) S.ops.push_back(0);
 }
 
 int check_ctx_list(agp_ctx* const* ctxs, int32_t n_dev) {
@@ -543,19 +524,19 @@ int grad_batch_multi_impl(agp_ctx* const* ctxs, int32_t n_dev, int64_t n, int32_
   std::vector<int> rcs((size_t)n_dev, AGP_OK);
   auto shard = [&](int d) noexcept {
     try {
-      ShardPack S;
-      pack_shard(P, op_off, ops, prm_off, prm, noise, owner.data(), d, S);
-      const int Pl = (int)S.idx.size();
+      std::vector<int> idx;
+      SubBatch S;
+      pack_shard(P, op_off, ops, prm_off, prm, noise, nullptr, owner.data(), d, idx, S);
+      const int Pl = S.size();
       if (Pl == 0) return;
-      std::vector<double> lp((size_t)Pl), gn((size_t)Pl), gr(std::max<size_t>(1, (size_t)S.po[(size_t)Pl]), 0.0);
-      std::vector<int32_t> inf((size_t)Pl, 0);
-      rcs[(size_t)d] = agp_logpdf_grad_batch(ctxs[d], n, Pl, S.oo.data(), S.so.data(), S.po.data(), S.sp.data(), S.nz.data(), lp.data(), gr.data(),
-                                             gn.data(), inf.data());
+      S.outputs(true);
+      rcs[(size_t)d] = agp_logpdf_grad_batch(ctxs[d], n, Pl, S.op_off.data(), S.ops.data(), S.prm_off.data(), S.prm.data(), S.noise.data(),
+                                             S.lp.data(), S.grad.data(), S.gnoise.data(), S.info.data());
       if (rcs[(size_t)d]) return;
       for (int b = 0; b < Pl; ++b) {          // (disjoint index sets: the shards write without a lock)
-        const int p = S.idx[(size_t)b];
-        out_logpdf[p] = lp[(size_t)b]; out_grad_noise[p] = gn[(size_t)b]; out_info[p] = inf[(size_t)b];
-        std::copy(gr.begin() + S.po[(size_t)b], gr.begin() + S.po[(size_t)b + 1], out_grad + prm_off[p]);
+        const int p = idx[(size_t)b];
+        out_logpdf[p] = S.lp[(size_t)b]; out_grad_noise[p] = S.gnoise[(size_t)b]; out_info[p] = S.info[(size_t)b];
+        std::copy(S.grad.begin() + S.prm_off[(size_t)b], S.grad.begin() + S.prm_off[(size_t)b + 1], out_grad + prm_off[p]);
       }
     } catch (...) { rcs[(size_t)d] = AGP_ERR_HOST; }
   };
@@ -594,20 +575,19 @@ int predict_batch_multi_impl(agp_ctx* const* ctxs, int32_t n_dev, int64_t n, con
   std::vector<int> rcs((size_t)n_dev, AGP_OK);
   auto shard = [&](int d) noexcept {
     try {
-      ShardPack S;
-      pack_shard(P, op_off, ops, prm_off, prm, noise, owner.data(), d, S);
-      const int Pl = (int)S.idx.size();
+      std::vector<int> idx;
+      SubBatch S;
+      pack_shard(P, op_off, ops, prm_off, prm, noise, noise_pred, owner.data(), d, idx, S);
+      const int Pl = S.size();
       if (Pl == 0) return;
-      std::vector<double> nzp;
-      if (noise_pred) { nzp.resize((size_t)Pl); for (int b = 0; b < Pl; ++b) nzp[(size_t)b] = noise_pred[S.idx[(size_t)b]]; }
       std::vector<double> mean((size_t)Pl * (size_t)m), var((size_t)Pl * (size_t)m), cov(out_cov ? (size_t)Pl * (size_t)m * (size_t)m : 0);
       std::vector<int32_t> inf((size_t)Pl, 0);
-      rcs[(size_t)d] = agp_predict_batch(ctxs[d], n, ts_pred, m, Pl, S.oo.data(), S.so.data(), S.po.data(), S.sp.data(), S.nz.data(),
-                                         noise_pred ? nzp.data() : nullptr, mean_train, mean_pred, mean.data(), var.data(),
+      rcs[(size_t)d] = agp_predict_batch(ctxs[d], n, ts_pred, m, Pl, S.op_off.data(), S.ops.data(), S.prm_off.data(), S.prm.data(), S.noise.data(),
+                                         noise_pred ? S.noise_pred.data() : nullptr, mean_train, mean_pred, mean.data(), var.data(),
                                          out_cov ? cov.data() : nullptr, inf.data());
       if (rcs[(size_t)d]) return;
       for (int b = 0; b < Pl; ++b) {
-        const size_t p = (size_t)S.idx[(size_t)b];
+        const size_t p = (size_t)idx[(size_t)b];
         std::copy(mean.begin() + (size_t)b * m, mean.begin() + (size_t)(b + 1) * m, out_mean + p * (size_t)m);
         std::copy(var.begin() + (size_t)b * m, var.begin() + (size_t)(b + 1) * m, out_var + p * (size_t)m);
         if (out_cov) std::copy(cov.begin() + (size_t)b * m * m, cov.begin() + (size_t)(b + 1) * m * m, out_cov + p * (size_t)m * (size_t)m);

@@ -82,6 +82,92 @@ void split_queries(agp_ctx* c, int64_t n, const double* ts_pred, int64_t m, bool
   if ((int64_t)dq.size() * 3 < n || (int64_t)dq.size() < NB) { dq.clear(); di.clear(); fq.clear(); }
 }
 
+// What predict_core and predict_logpdf_core stage alike for a compiled batch: the joint point list [ts(1:n), pad, tsJ(1:mJ), pad], the
+// programs, the noises in sorted order (noise_pred defaults to noise), the means of the training and of the query points; and the
+// buffers both size alike for chunks of `chunk` particles.
+int stage_joint(agp_ctx* c, Slot* s, PinnedUploads& up, int64_t n, const double* tsJ, int64_t mJ, int P, int chunk, const Batch& bt,
+                const double* noise, const double* noise_pred, const double* mean_train, const double* meanJ,
+                std::vector<double>& noise_sorted, std::vector<double>& npred) {
+  const int n1_pad = round_up(n, NB), ntot = n1_pad + round_up(mJ, NB), nt = ntot / NB;
+  std::vector<double> tt((size_t)ntot, 0.0);
+  std::copy(c->h_ts.begin(), c->h_ts.begin() + n, tt.begin());
+  std::copy(tsJ, tsJ + mJ, tt.begin() + n1_pad);
+  noise_sorted.resize((size_t)P); npred.resize((size_t)P);
+  for (int q = 0; q < P; ++q) {
+    const int p = bt.order[q];
+    noise_sorted[q] = noise[p];
+    npred[q] = noise_pred ? noise_pred[p] : noise[p];
+  }
+  HIPCHK(c, s->vec.ensure(sizeof(double) * (size_t)ntot * chunk));
+  HIPCHK(c, s->partial.ensure(sizeof(double) * 2 * (size_t)nt * chunk));
+  HIPCHK(c, s->info.ensure(sizeof(int) * (size_t)P));
+  HIPCHK(c, s->ready.ensure(sizeof(int) * (size_t)P));
+  HIPCHK(c, s->hdr.ensure(sizeof(ProgHdr) * (size_t)P));
+  HIPCHK(c, s->ops.ensure(bt.ops.size()));
+  HIPCHK(c, s->prm.ensure(sizeof(double) * std::max<size_t>(1, bt.prm.size())));
+  HIPCHK(c, s->noise.ensure(sizeof(double) * (size_t)P));
+  HIPCHK(c, s->noise_pred.ensure(sizeof(double) * (size_t)P));
+  HIPCHK(c, s->tt.ensure(sizeof(double) * (size_t)ntot));
+  if (mean_train && n > 0) {
+    HIPCHK(c, s->mu1.ensure(sizeof(double) * (size_t)n));
+    up.add(s->mu1.p, mean_train, sizeof(double) * n);
+  }
+  if (meanJ && mJ > 0) {
+    HIPCHK(c, s->mu2.ensure(sizeof(double) * (size_t)mJ));
+    up.add(s->mu2.p, meanJ, sizeof(double) * mJ);
+  }
+  up.add(s->hdr.p, bt.hdr.data(), sizeof(ProgHdr) * P);
+  up.add(s->ops.p, bt.ops.data(), bt.ops.size());
+  up.add(s->prm.p, bt.prm.data(), sizeof(double) * bt.prm.size());
+  up.add(s->noise.p, noise_sorted.data(), sizeof(double) * P);
+  up.add(s->noise_pred.p, npred.data(), sizeof(double) * P);
+  up.add(s->tt.p, tt.data(), sizeof(double) * ntot);
+  return AGP_OK;
+}
+
+// Query points on the lattice: `up` goes out with the ranks of the joint points (padded joint layout), the lag times and the table
+// programs; then one rank table of R lags per stationary subtree of the batch.
+int flush_lattice(agp_ctx* c, Slot* s, hipStream_t st, PinnedUploads& up, const Batch& bt, const PredLattice& pl,
+                  const std::vector<int32_t>& rank) {
+  const LagProgLayout lpl(bt);
+  HIPCHK(c, lpl.upload(up, s->pl_prog));
+  HIPCHK(c, s->pl_rank.ensure(sizeof(int32_t) * rank.size()));
+  HIPCHK(c, s->pl_tl.ensure(sizeof(double) * pl.tl.size()));
+  up.add(s->pl_rank.p, rank.data(), sizeof(int32_t) * rank.size());
+  up.add(s->pl_tl.p, pl.tl.data(), sizeof(double) * pl.tl.size());
+  HIPCHK(c, up.flush(s->h_stage, s->up_blob, st));
+  if (bt.n_lag_tables > 0) {
+    HIPCHK(c, s->lagtab.ensure(sizeof(double) * (size_t)bt.n_lag_tables * pl.rank_units * 256));
+    LagArgs la = {};
+    la.tt = s->pl_tl.as<double>(); la.tab = s->lagtab.as<double>();
+    lpl.point(la, s->pl_prog.p);
+    la.nt = 2 * pl.rank_units; la.full = 1; la.stride = pl.rank_units * 256;      // (every entry of the table is live)
+    launch_lag_tables(st, la, pl.rank_units, bt.n_lag_tables);
+    HIPCHK(c, hipGetLastError());
+  }
+  std::lock_guard<std::mutex> g(c->mu);
+  ++c->n_lag_pred;
+  return AGP_OK;
+}
+
+// The dataflow schedule over the joint matrix of ca.P particles: block columns [0, wsteps) factored, every row of them (tile rows below
+// ca.i0[p], when given, hold a resident factor already).
+int launch_joint_flow(agp_ctx* c, Slot* s, hipStream_t st, CholArgs& ca, int dcov, int wsteps) {
+  const int ntri = ca.nt * (ca.nt + 1) / 2;
+  HIPCHK(c, s->tflag.ensure(sizeof(int) * (size_t)ca.P * ntri));
+  HIPCHK(c, s->flowq.ensure(sizeof(int) * 8 * 8));
+  ca.tflag = s->tflag.as<int>(); ca.ntri = ntri; ca.qnext = s->flowq.as<int>();
+  ca.wsteps = wsteps;
+  if (ca.i0)
+    launch_init_flow_flags(st, ca.P, ca.tflag, ntri, ntri, (const int*)nullptr, ca.i0);
+  else
+    HIPCHK(c, hipMemsetAsync(ca.tflag, 0, sizeof(int) * (size_t)ca.P * ntri, st));
+  HIPCHK(c, hipMemsetAsync(ca.qnext, 0, sizeof(int) * 8, st));
+  launch_flow(dcov, 2 * c->n_cu, st, ca);
+  HIPCHK(c, hipGetLastError());
+  return AGP_OK;
+}
+
 int predict_core(agp_ctx* c, int64_t n, const double* ts_pred, int64_t m, int32_t P, Batch& bt,
                  const double* noise, const double* noise_pred, const uint8_t* pred_code, const double* diag_add,
                  const double* mean_train, const double* mean_pred, double* out_mean, double* out_var,
@@ -133,17 +219,6 @@ int predict_core(agp_ctx* c, int64_t n, const double* ts_pred, int64_t m, int32_
   const int64_t bytes_pp = (strideA + strideZ) * 8;
   const int chunk = (int)std::max<int64_t>(1, std::min<int64_t>(P, ws_limit_bytes(c) / bytes_pp));
 
-  // joint point list [ts(1:n), pad, ts_pred, pad]
-  std::vector<double> tt((size_t)ntot, 0.0);
-  std::copy(c->h_ts.begin(), c->h_ts.begin() + n, tt.begin());
-  std::copy(tsJ, tsJ + mJ, tt.begin() + n1_pad);
-  std::vector<double> npred(P), noise_sorted(P);
-  for (int q = 0; q < P; ++q) {
-    const int p = bt.order[q];
-    noise_sorted[q] = noise[p];
-    npred[q] = noise_pred ? noise_pred[p] : noise[p];
-  }
-
   HIPCHK(c, s->A.ensure((size_t)strideA * 8 * chunk));
   if (diag_path) {
     HIPCHK(c, s->Z.ensure((size_t)strideZ * 8 * chunk));
@@ -151,34 +226,12 @@ int predict_core(agp_ctx* c, int64_t n, const double* ts_pred, int64_t m, int32_
     HIPCHK(c, s->gpart.ensure(sizeof(double) * (size_t)ntot * chunk));      // diag(K11^-1) (the gradient path's scratch, idle here)
   }
   HIPCHK(c, s->W.ensure(sizeof(double) * NSB * 256 * (size_t)chunk * std::max(1, nt1)));     // (the dataflow schedule keeps every column's inverse blocks)
-  HIPCHK(c, s->vec.ensure(sizeof(double) * (size_t)ntot * chunk));
-  HIPCHK(c, s->partial.ensure(sizeof(double) * 2 * (size_t)nt * chunk));
-  HIPCHK(c, s->info.ensure(sizeof(int) * (size_t)P));
-  HIPCHK(c, s->ready.ensure(sizeof(int) * (size_t)P));
-  HIPCHK(c, s->hdr.ensure(sizeof(ProgHdr) * (size_t)P));
-  HIPCHK(c, s->ops.ensure(bt.ops.size()));
-  HIPCHK(c, s->prm.ensure(sizeof(double) * std::max<size_t>(1, bt.prm.size())));
-  HIPCHK(c, s->noise.ensure(sizeof(double) * (size_t)P));
-  HIPCHK(c, s->noise_pred.ensure(sizeof(double) * (size_t)P));
-  HIPCHK(c, s->tt.ensure(sizeof(double) * (size_t)ntot));
   HIPCHK(c, s->pred_mean.ensure(sizeof(double) * (size_t)std::max<int64_t>(1, mJ) * chunk));
   HIPCHK(c, s->pred_var.ensure(sizeof(double) * (size_t)std::max<int64_t>(1, mJ) * chunk));
   if (out_cov) HIPCHK(c, s->pred_cov.ensure(sizeof(double) * (size_t)m * m * chunk));
   PinnedUploads up;
-  if (mean_train && n > 0) {
-    HIPCHK(c, s->mu1.ensure(sizeof(double) * (size_t)n));
-    up.add(s->mu1.p, mean_train, sizeof(double) * n);
-  }
-  if (mean_pred && mJ > 0) {
-    HIPCHK(c, s->mu2.ensure(sizeof(double) * (size_t)mJ));
-    up.add(s->mu2.p, meanJ, sizeof(double) * mJ);
-  }
-  up.add(s->hdr.p, bt.hdr.data(), sizeof(ProgHdr) * P);
-  up.add(s->ops.p, bt.ops.data(), bt.ops.size());
-  up.add(s->prm.p, bt.prm.data(), sizeof(double) * bt.prm.size());
-  up.add(s->noise.p, noise_sorted.data(), sizeof(double) * P);
-  up.add(s->noise_pred.p, npred.data(), sizeof(double) * P);
-  up.add(s->tt.p, tt.data(), sizeof(double) * ntot);
+  std::vector<double> noise_sorted, npred;
+  if (const int rc = stage_joint(c, s, up, n, tsJ, mJ, P, chunk, bt, noise, noise_pred, mean_train, meanJ, noise_sorted, npred)) return rc;
   if (pred_code) {
     std::vector<uint8_t> code((size_t)ntot, 0);
     std::copy(pred_code, pred_code + m, code.begin() + n1_pad);
@@ -232,21 +285,9 @@ int predict_core(agp_ctx* c, int64_t n, const double* ts_pred, int64_t m, int32_
     if (zstore) { up.add(d + 2 * P, zi0v.data(), sizeof(int32_t) * P); d_zi0 = d + 2 * P; }
     d_src = d; d_i0 = d + P;
   }
-  if (!lagr) HIPCHK(c, up.flush(s->h_stage, s->up_blob, st));
-
-  if (lagr) {
-    // ranks of the joint points, lag times, table programs; one table of R lags per stationary subtree of the batch
-    auto al16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
-    const size_t o_tprm = al16(sizeof(LagTabHdr) * bt.thdr.size());
-    const size_t o_tops = al16(o_tprm + sizeof(double) * bt.tprm.size());
-    const size_t prog_bytes = al16(o_tops + bt.tops.size() + 4);
-    std::vector<char> hp(prog_bytes, 0);
-    if (!bt.thdr.empty()) {
-      std::memcpy(hp.data(), bt.thdr.data(), sizeof(LagTabHdr) * bt.thdr.size());
-      std::memcpy(hp.data() + o_tprm, bt.tprm.data(), sizeof(double) * bt.tprm.size());
-      std::memcpy(hp.data() + o_tops, bt.tops.data(), bt.tops.size());
-    }
-    HIPCHK(c, s->pl_prog.ensure(prog_bytes));
+  if (!lagr) {
+    HIPCHK(c, up.flush(s->h_stage, s->up_blob, st));
+  } else {
     // (the joint layout keeps the queries that are not training points only)
     std::vector<int32_t> rankF;
     if (diag_path) {
@@ -254,26 +295,7 @@ int predict_core(agp_ctx* c, int64_t n, const double* ts_pred, int64_t m, int32_
       std::copy(pl->rank.begin(), pl->rank.begin() + n1_pad, rankF.begin());
       for (int64_t g = 0; g < mJ; ++g) rankF[(size_t)n1_pad + g] = pl->rank[(size_t)n1_pad + fq[(size_t)g]];
     }
-    const std::vector<int32_t>& rankJ = diag_path ? rankF : pl->rank;
-    HIPCHK(c, s->pl_rank.ensure(sizeof(int32_t) * rankJ.size()));
-    HIPCHK(c, s->pl_tl.ensure(sizeof(double) * pl->tl.size()));
-    up.add(s->pl_prog.p, hp.data(), prog_bytes);
-    up.add(s->pl_rank.p, rankJ.data(), sizeof(int32_t) * rankJ.size());
-    up.add(s->pl_tl.p, pl->tl.data(), sizeof(double) * pl->tl.size());
-    HIPCHK(c, up.flush(s->h_stage, s->up_blob, st));
-    if (bt.n_lag_tables > 0) {
-      HIPCHK(c, s->lagtab.ensure(sizeof(double) * (size_t)bt.n_lag_tables * pl->rank_units * 256));
-      LagArgs la = {};
-      la.tt = s->pl_tl.as<double>(); la.thdr = s->pl_prog.as<LagTabHdr>();
-      la.tprm = reinterpret_cast<const double*>(static_cast<char*>(s->pl_prog.p) + o_tprm);
-      la.tops = reinterpret_cast<const uint8_t*>(static_cast<char*>(s->pl_prog.p) + o_tops);
-      la.n_tables = bt.n_lag_tables; la.tab = s->lagtab.as<double>();
-      la.nt = 2 * pl->rank_units; la.full = 1; la.stride = pl->rank_units * 256;      // (every entry of the table is live)
-      launch_lag_tables(st, la, pl->rank_units, bt.n_lag_tables);
-      HIPCHK(c, hipGetLastError());
-    }
-    std::lock_guard<std::mutex> g(c->mu);
-    ++c->n_lag_pred;
+    if (const int rc = flush_lattice(c, s, st, up, bt, *pl, diag_path ? rankF : pl->rank)) return rc;
   }
 
   const double* h_mean = nullptr; const double* h_var = nullptr; const double* h_alpha = nullptr; const double* h_dinv = nullptr;      // in the slot's pinned landing zone
@@ -323,18 +345,7 @@ int predict_core(agp_ctx* c, int64_t n, const double* ts_pred, int64_t m, int32_
     if (n_hit > 0) ca.i0 = d_i0 + p0;
     if (nt1 > 0 && use_flow(c, Pc, nt, nt1)) {
       // dataflow schedule over the block columns of the training block (all rows: V = L^-1 K12 comes out of the same tiles)
-      const int ntri = nt * (nt + 1) / 2;
-      HIPCHK(c, s->tflag.ensure(sizeof(int) * (size_t)Pc * ntri));
-      HIPCHK(c, s->flowq.ensure(sizeof(int) * 8 * 8));
-      ca.tflag = s->tflag.as<int>(); ca.ntri = ntri; ca.qnext = s->flowq.as<int>();
-      ca.wsteps = nt1;
-      if (n_hit > 0)
-        launch_init_flow_flags(st, Pc, ca.tflag, ntri, ntri, (const int*)nullptr, ca.i0);
-      else
-        HIPCHK(c, hipMemsetAsync(ca.tflag, 0, sizeof(int) * (size_t)Pc * ntri, st));
-      HIPCHK(c, hipMemsetAsync(ca.qnext, 0, sizeof(int) * 8, st));
-      launch_flow(dcov, 2 * c->n_cu, st, ca);
-      HIPCHK(c, hipGetLastError());
+      if (const int rc = launch_joint_flow(c, s, st, ca, dcov, nt1)) return rc;
     } else if (n_hit > 0) {
       // (invariant of every branch here: only the training block's nt1 columns are factored, so the diagonal-tile kernel sees
       // tiles with n1 - tk * NB > 0 rows of data; the query rows below them are panel solves, never a diagonal step)
@@ -491,82 +502,21 @@ int predict_logpdf_core(agp_ctx* c, int64_t n, const double* ts_pred, const doub
   if (!s->stream) HIPCHK(c, hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
   hipStream_t st = s->stream;
 
-  std::vector<double> tt((size_t)ntot, 0.0);
-  std::copy(c->h_ts.begin(), c->h_ts.begin() + n, tt.begin());
-  std::copy(ts_pred, ts_pred + m, tt.begin() + n1_pad);
-  std::vector<double> npred(P), noise_sorted(P);
-  for (int q = 0; q < P; ++q) {
-    const int p = bt.order[q];
-    noise_sorted[q] = noise[p];
-    npred[q] = noise_pred ? noise_pred[p] : noise[p];
-  }
   HIPCHK(c, s->A.ensure((size_t)strideA * 8 * chunk));
   HIPCHK(c, s->W.ensure(sizeof(double) * NSB * 256 * (size_t)chunk * nt));     // (the dataflow schedule keeps every column's inverse blocks)
-  HIPCHK(c, s->vec.ensure(sizeof(double) * (size_t)ntot * chunk));
-  HIPCHK(c, s->partial.ensure(sizeof(double) * 2 * (size_t)nt * chunk));
-  HIPCHK(c, s->info.ensure(sizeof(int) * (size_t)P));
-  HIPCHK(c, s->ready.ensure(sizeof(int) * (size_t)P));
-  HIPCHK(c, s->hdr.ensure(sizeof(ProgHdr) * (size_t)P));
-  HIPCHK(c, s->ops.ensure(bt.ops.size()));
-  HIPCHK(c, s->prm.ensure(sizeof(double) * std::max<size_t>(1, bt.prm.size())));
-  HIPCHK(c, s->noise.ensure(sizeof(double) * (size_t)P));
-  HIPCHK(c, s->noise_pred.ensure(sizeof(double) * (size_t)P));
-  HIPCHK(c, s->tt.ensure(sizeof(double) * (size_t)ntot));
   HIPCHK(c, s->pred_mean.ensure(sizeof(double) * (size_t)m));      // y_pred (the read-out buffers are idle in this pass)
   HIPCHK(c, s->map.ensure(sizeof(int32_t) * (size_t)P));
   HIPCHK(c, s->out_lp.ensure(sizeof(double) * (size_t)P));
   HIPCHK(c, s->out_info.ensure(sizeof(int32_t) * (size_t)P));
   PinnedUploads up;
-  if (mean_train && n > 0) {
-    HIPCHK(c, s->mu1.ensure(sizeof(double) * (size_t)n));
-    up.add(s->mu1.p, mean_train, sizeof(double) * n);
-  }
-  if (mean_pred) {
-    HIPCHK(c, s->mu2.ensure(sizeof(double) * (size_t)m));
-    up.add(s->mu2.p, mean_pred, sizeof(double) * m);
-  }
-  up.add(s->hdr.p, bt.hdr.data(), sizeof(ProgHdr) * P);
-  up.add(s->ops.p, bt.ops.data(), bt.ops.size());
-  up.add(s->prm.p, bt.prm.data(), sizeof(double) * bt.prm.size());
-  up.add(s->noise.p, noise_sorted.data(), sizeof(double) * P);
-  up.add(s->noise_pred.p, npred.data(), sizeof(double) * P);
-  up.add(s->tt.p, tt.data(), sizeof(double) * ntot);
+  std::vector<double> noise_sorted, npred;
+  if (const int rc = stage_joint(c, s, up, n, ts_pred, m, P, chunk, bt, noise, noise_pred, mean_train, mean_pred, noise_sorted, npred)) return rc;
   up.add(s->pred_mean.p, y_pred, sizeof(double) * m);
   up.add(s->map.p, bt.order.data(), sizeof(int32_t) * P);
-  if (lagr) {
-    // (as predict_core: ranks of the joint points, lag times, one rank table per stationary subtree of the batch)
-    auto al16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
-    const size_t o_tprm = al16(sizeof(LagTabHdr) * bt.thdr.size());
-    const size_t o_tops = al16(o_tprm + sizeof(double) * bt.tprm.size());
-    const size_t prog_bytes = al16(o_tops + bt.tops.size() + 4);
-    std::vector<char> hp(prog_bytes, 0);
-    if (!bt.thdr.empty()) {
-      std::memcpy(hp.data(), bt.thdr.data(), sizeof(LagTabHdr) * bt.thdr.size());
-      std::memcpy(hp.data() + o_tprm, bt.tprm.data(), sizeof(double) * bt.tprm.size());
-      std::memcpy(hp.data() + o_tops, bt.tops.data(), bt.tops.size());
-    }
-    HIPCHK(c, s->pl_prog.ensure(prog_bytes));
-    HIPCHK(c, s->pl_rank.ensure(sizeof(int32_t) * pl->rank.size()));
-    HIPCHK(c, s->pl_tl.ensure(sizeof(double) * pl->tl.size()));
-    up.add(s->pl_prog.p, hp.data(), prog_bytes);
-    up.add(s->pl_rank.p, pl->rank.data(), sizeof(int32_t) * pl->rank.size());
-    up.add(s->pl_tl.p, pl->tl.data(), sizeof(double) * pl->tl.size());
+  if (!lagr) {
     HIPCHK(c, up.flush(s->h_stage, s->up_blob, st));
-    if (bt.n_lag_tables > 0) {
-      HIPCHK(c, s->lagtab.ensure(sizeof(double) * (size_t)bt.n_lag_tables * pl->rank_units * 256));
-      LagArgs la = {};
-      la.tt = s->pl_tl.as<double>(); la.thdr = s->pl_prog.as<LagTabHdr>();
-      la.tprm = reinterpret_cast<const double*>(static_cast<char*>(s->pl_prog.p) + o_tprm);
-      la.tops = reinterpret_cast<const uint8_t*>(static_cast<char*>(s->pl_prog.p) + o_tops);
-      la.n_tables = bt.n_lag_tables; la.tab = s->lagtab.as<double>();
-      la.nt = 2 * pl->rank_units; la.full = 1; la.stride = pl->rank_units * 256;
-      launch_lag_tables(st, la, pl->rank_units, bt.n_lag_tables);
-      HIPCHK(c, hipGetLastError());
-    }
-    std::lock_guard<std::mutex> g(c->mu);
-    ++c->n_lag_pred;
-  } else {
-    HIPCHK(c, up.flush(s->h_stage, s->up_blob, st));
+  } else if (const int rc = flush_lattice(c, s, st, up, bt, *pl, pl->rank)) {
+    return rc;
   }
 
   for (int p0 = 0; p0 < P; p0 += chunk) {
@@ -597,15 +547,7 @@ int predict_logpdf_core(agp_ctx* c, int64_t n, const double* ts_pred, const doub
     // (one schedule whatever the batch: a particle's log-density does not depend on the particles around it — the per-column
     // launches only where the dataflow schedule is switched off, AGP_FLOW=0)
     if (c->flow != 0) {
-      const int ntri = nt * (nt + 1) / 2;
-      HIPCHK(c, s->tflag.ensure(sizeof(int) * (size_t)Pc * ntri));
-      HIPCHK(c, s->flowq.ensure(sizeof(int) * 8 * 8));
-      ca.tflag = s->tflag.as<int>(); ca.ntri = ntri; ca.qnext = s->flowq.as<int>();
-      ca.wsteps = nt;
-      HIPCHK(c, hipMemsetAsync(ca.tflag, 0, sizeof(int) * (size_t)Pc * ntri, st));
-      HIPCHK(c, hipMemsetAsync(ca.qnext, 0, sizeof(int) * 8, st));
-      launch_flow(dcov, 2 * c->n_cu, st, ca);
-      HIPCHK(c, hipGetLastError());
+      if (const int rc = launch_joint_flow(c, s, st, ca, dcov, nt)) return rc;
     } else {
       HIPCHK(c, run_factor(st, ca, nt, dcov, nullptr, nullptr, use_split_diag(c, ca.P)));
     }
@@ -653,16 +595,6 @@ int toeplitz_predict_sweep(agp_ctx* c, int64_t n, int32_t rank0, int mF, const P
   Slot* s = sg.s;
   if (!s->stream) HIPCHK(c, hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
   hipStream_t st = s->stream;
-  auto al16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
-  const size_t o_tprm = al16(sizeof(LagTabHdr) * bt.thdr.size());
-  const size_t o_tops = al16(o_tprm + sizeof(double) * bt.tprm.size());
-  const size_t prog_bytes = al16(o_tops + bt.tops.size() + 4);
-  std::vector<char> hp(prog_bytes, 0);
-  if (!bt.thdr.empty()) {
-    std::memcpy(hp.data(), bt.thdr.data(), sizeof(LagTabHdr) * bt.thdr.size());
-    std::memcpy(hp.data() + o_tprm, bt.tprm.data(), sizeof(double) * bt.tprm.size());
-    std::memcpy(hp.data() + o_tops, bt.tops.data(), bt.tops.size());
-  }
   const int n_pad = round_up(n, NB), mF_pad = std::max(NB, round_up(mF, NB));
   const int N = (int)n + mF;
   std::vector<double> nz((size_t)P);
@@ -674,7 +606,6 @@ int toeplitz_predict_sweep(agp_ctx* c, int64_t n, int32_t rank0, int mF, const P
   HIPCHK(c, s->ops.ensure(bt.ops.size() + 4));
   HIPCHK(c, s->prm.ensure(sizeof(double) * std::max<size_t>(1, bt.prm.size())));
   HIPCHK(c, s->noise.ensure(sizeof(double) * (size_t)P));
-  HIPCHK(c, s->pl_prog.ensure(prog_bytes));
   HIPCHK(c, s->pl_tl.ensure(sizeof(double) * pl.tl.size()));
   HIPCHK(c, s->out_lp.ensure(sizeof(double) * (size_t)P + sizeof(int32_t) * (size_t)P));
   HIPCHK(c, s->A.ensure((size_t)Lstride * 8 * chunk));
@@ -687,7 +618,8 @@ int toeplitz_predict_sweep(agp_ctx* c, int64_t n, int32_t rank0, int mF, const P
   up.add(s->ops.p, bt.ops.data(), bt.ops.size());
   up.add(s->prm.p, bt.prm.data(), sizeof(double) * bt.prm.size());
   up.add(s->noise.p, nz.data(), sizeof(double) * (size_t)P);
-  up.add(s->pl_prog.p, hp.data(), prog_bytes);
+  const LagProgLayout lpl(bt);
+  HIPCHK(c, lpl.upload(up, s->pl_prog));
   up.add(s->pl_tl.p, pl.tl.data(), sizeof(double) * pl.tl.size());
   if (xs_sorted_host) {
     HIPCHK(c, s->mu1.ensure(sizeof(double) * (size_t)n));
@@ -696,10 +628,8 @@ int toeplitz_predict_sweep(agp_ctx* c, int64_t n, int32_t rank0, int mF, const P
   HIPCHK(c, up.flush(s->h_stage, s->up_blob, st));
   if (bt.n_lag_tables > 0) {
     LagArgs la = {};
-    la.tt = s->pl_tl.as<double>(); la.thdr = s->pl_prog.as<LagTabHdr>();
-    la.tprm = reinterpret_cast<const double*>(static_cast<char*>(s->pl_prog.p) + o_tprm);
-    la.tops = reinterpret_cast<const uint8_t*>(static_cast<char*>(s->pl_prog.p) + o_tops);
-    la.n_tables = bt.n_lag_tables; la.tab = s->lagtab.as<double>();
+    la.tt = s->pl_tl.as<double>(); la.tab = s->lagtab.as<double>();
+    lpl.point(la, s->pl_prog.p);
     la.nt = 2 * pl.rank_units; la.full = 1; la.stride = stride;
     launch_lag_tables(st, la, pl.rank_units, bt.n_lag_tables);
     HIPCHK(c, hipGetLastError());
@@ -873,50 +803,43 @@ static int predict_batch_body(agp_ctx* c, int64_t n, const double* ts_pred, int6
     // (two sequential passes over the joint grid: ~1.2 us per point + ~1 us per training point, whatever the class's size)
     if (ok && (int)part[1].size() >= STRUCT_PRED_MIN_CLASS) {
       const int32_t rank0_abs = c->h_rank[0] - (plq.rank[0] - lo);          // rank of the first training point in the resident series
-      auto gather = [&](const std::vector<int>& ix, std::vector<int32_t>& oo, std::vector<uint8_t>& so, std::vector<int32_t>& po,
-                        std::vector<double>& sp, std::vector<double>& nz, std::vector<double>& nzp) {
-        oo.assign(ix.size() + 1, 0); po.assign(ix.size() + 1, 0); nz.resize(ix.size()); nzp.resize(ix.size()); so.clear(); sp.clear();
-        for (size_t b = 0; b < ix.size(); ++b) {
-          const int p = ix[b];
-          so.insert(so.end(), ops + op_off[p], ops + op_off[p + 1]);
-          sp.insert(sp.end(), prm + prm_off[p], prm + prm_off[p + 1]);
-          oo[b + 1] = (int32_t)so.size(); po[b + 1] = (int32_t)sp.size(); nz[b] = noise[p]; nzp[b] = noise_pred ? noise_pred[p] : noise[p];
-        }
-        if (sp.empty()) sp.push_back(0.0);
-      };
-      struct Sub { std::vector<int32_t> oo, po, info; std::vector<uint8_t> so; std::vector<double> sp, nz, nzp, mean, var; int rc = 0; } sT, sD;
-      gather(part[1], sT.oo, sT.so, sT.po, sT.sp, sT.nz, sT.nzp);
-      sT.mean.resize(part[1].size() * (size_t)m); sT.var.resize(part[1].size() * (size_t)m); sT.info.assign(part[1].size(), 0);
+      // (noise_pred defaults to noise in the sub-batches)
+      const double* nzp = noise_pred ? noise_pred : noise;
+      SubBatch sT, sD;
+      pack_particles(part[1], op_off, ops, prm_off, prm, noise, nzp, sT);
+      std::vector<double> tmean(part[1].size() * (size_t)m), tvar(part[1].size() * (size_t)m), dmean, dvar;
+      std::vector<int32_t> tinfo(part[1].size(), 0), dinfo;
       Beside side([&] {
-        return toeplitz_predict_sweep(c, n, rank0_abs, mF, plq, qkind, xq, (int)part[1].size(), sT.oo.data(), sT.so.data(), sT.po.data(),
-                                       sT.sp.data(), sT.nz.data(), sT.nzp.data(), sT.mean.data(), sT.var.data(), sT.info.data(),
+        return toeplitz_predict_sweep(c, n, rank0_abs, mF, plq, qkind, xq, sT.size(), sT.op_off.data(), sT.ops.data(), sT.prm_off.data(),
+                                       sT.prm.data(), sT.noise.data(), sT.noise_pred.data(), tmean.data(), tvar.data(), tinfo.data(),
                                        mean_train ? xres.data() : nullptr, mean_pred);
       });
       auto dense = [&](const std::vector<int>& ix) {
         if (ix.empty()) return 0;
-        gather(ix, sD.oo, sD.so, sD.po, sD.sp, sD.nz, sD.nzp);
-        sD.mean.resize(ix.size() * (size_t)m); sD.var.resize(ix.size() * (size_t)m); sD.info.assign(ix.size(), 0);
+        pack_particles(ix, op_off, ops, prm_off, prm, noise, nzp, sD);
+        dmean.resize(ix.size() * (size_t)m); dvar.resize(ix.size() * (size_t)m); dinfo.assign(ix.size(), 0);
         TlFlag nested(tl_in_tpredict);
-        const int rc0 = agp_predict_batch(c, n, ts_pred, m, (int32_t)ix.size(), sD.oo.data(), sD.so.data(), sD.po.data(), sD.sp.data(), sD.nz.data(),
-                                          sD.nzp.data(), mean_train, mean_pred, sD.mean.data(), sD.var.data(), nullptr, sD.info.data());
+        const int rc0 = agp_predict_batch(c, n, ts_pred, m, sD.size(), sD.op_off.data(), sD.ops.data(), sD.prm_off.data(), sD.prm.data(),
+                                          sD.noise.data(), sD.noise_pred.data(), mean_train, mean_pred, dmean.data(), dvar.data(), nullptr,
+                                          dinfo.data());
         if (rc0) return rc0;
         for (size_t b = 0; b < ix.size(); ++b) {
-          std::memcpy(out_mean + (size_t)ix[b] * m, sD.mean.data() + b * (size_t)m, sizeof(double) * (size_t)m);
-          std::memcpy(out_var + (size_t)ix[b] * m, sD.var.data() + b * (size_t)m, sizeof(double) * (size_t)m);
-          if (out_info) out_info[ix[b]] = sD.info[b];
+          std::memcpy(out_mean + (size_t)ix[b] * m, dmean.data() + b * (size_t)m, sizeof(double) * (size_t)m);
+          std::memcpy(out_var + (size_t)ix[b] * m, dvar.data() + b * (size_t)m, sizeof(double) * (size_t)m);
+          if (out_info) out_info[ix[b]] = dinfo[b];
         }
         return 0;
       };
       const int rcD = dense(part[0]);
-      sT.rc = side.join();
+      const int rcT = side.join();
       if (rcD) return rcD;
-      if (sT.rc) return sT.rc;
+      if (rcT) return rcT;
       std::vector<int> refused;
       int64_t done = 0;
       for (size_t b = 0; b < part[1].size(); ++b) {
-        if (sT.info[b] != 0) { refused.push_back(part[1][b]); continue; }
-        std::memcpy(out_mean + (size_t)part[1][b] * m, sT.mean.data() + b * (size_t)m, sizeof(double) * (size_t)m);
-        std::memcpy(out_var + (size_t)part[1][b] * m, sT.var.data() + b * (size_t)m, sizeof(double) * (size_t)m);
+        if (tinfo[b] != 0) { refused.push_back(part[1][b]); continue; }
+        std::memcpy(out_mean + (size_t)part[1][b] * m, tmean.data() + b * (size_t)m, sizeof(double) * (size_t)m);
+        std::memcpy(out_var + (size_t)part[1][b] * m, tvar.data() + b * (size_t)m, sizeof(double) * (size_t)m);
         if (out_info) out_info[part[1][b]] = 0;
         ++done;
       }
@@ -926,28 +849,8 @@ static int predict_batch_body(agp_ctx* c, int64_t n, const double* ts_pred, int6
   }
   // A resampled population holds copies of the survivors (src/inference_smc_anneal_data.jl:198-204) and the reference
   // predicts particle by particle (src/api.jl:508-520): each distinct (program, parameters, noise, noise_pred) runs once.
-  std::vector<int> rep(P), uniq;
-  if (c->dedup && P > 1) {
-    bool sane = true;
-    for (int p = 0; p < P && sane; ++p)
-      sane = op_off[p + 1] >= op_off[p] && prm_off[p + 1] >= prm_off[p] && op_off[p] >= 0 && prm_off[p] >= 0;
-    if (sane) {
-      std::unordered_map<std::string, int> seen;
-      seen.reserve((size_t)P * 2);
-      for (int p = 0; p < P; ++p) {
-        const int no = op_off[p + 1] - op_off[p], np = prm_off[p + 1] - prm_off[p];
-        const int32_t lens[2] = {no, np};
-        std::string key(reinterpret_cast<const char*>(lens), sizeof lens);
-        key.append(reinterpret_cast<const char*>(ops + op_off[p]), (size_t)no);
-        key.append(reinterpret_cast<const char*>(prm + prm_off[p]), sizeof(double) * (size_t)np);
-        key.append(reinterpret_cast<const char*>(noise + p), sizeof(double));
-        if (noise_pred) key.append(reinterpret_cast<const char*>(noise_pred + p), sizeof(double));
-        auto it = seen.find(key);
-        if (it == seen.end()) { seen.emplace(std::move(key), (int)uniq.size()); rep[p] = (int)uniq.size(); uniq.push_back(p); }
-        else rep[p] = it->second;
-      }
-    }
-  }
+  std::vector<int> rep, uniq;
+  if (c->dedup && P > 1) (void)distinct_particles(P, op_off, ops, prm_off, prm, noise, noise_pred, rep, uniq);      // (malformed offsets: no dedup)
   const int U = (int)uniq.size();
   // (a store that holds nothing is not consulted: no key strings are built)
   const bool want_keys = c->predict_reuse && n > 0 && !mean_train && c->store.n_slots > 0;
@@ -959,51 +862,34 @@ static int predict_batch_body(agp_ctx* c, int64_t n, const double* ts_pred, int6
     split_queries(c, n, ts_pred, m, !out_cov && !c->ref_arith, dq, di, fq);
     if (!dq.empty()) m_joint = (int64_t)fq.size();
   }
-  if (U == 0 || U == P) {
+  const int nt1_ = (int)((n + NB - 1) / NB), nt_ = nt1_ + (int)((m_joint + NB - 1) / NB);
+  auto run = [&](int Pb, const int32_t* oo, const uint8_t* so, const int32_t* po, const double* sp, const double* nz, const double* nzp,
+                 double* om, double* ov, double* oc, int32_t* oi) {
     Batch bt;
-    const int nt1_ = (int)((n + NB - 1) / NB), nt_ = nt1_ + (int)((m_joint + NB - 1) / NB);
-    const bool ff = n > 0 && use_flow(c, P, nt_, nt1_);
-    const bool fh = ff;
-    int rc = compile_batch(c, P, op_off, ops, prm_off, prm, bt, false, false, false, fh, ff, pl.on, pl.on ? pl.rank_units : 1, pl.on);
+    const bool ff = n > 0 && use_flow(c, Pb, nt_, nt1_);
+    int rc = compile_batch(c, Pb, oo, so, po, sp, bt, false, false, false, ff, ff, pl.on, pl.on ? pl.rank_units : 1, pl.on);
     if (rc) return rc;
     std::vector<std::string> keys;
     if (want_keys)
-      for (int p = 0; p < P; ++p)
-        keys.push_back(particle_key(ops + op_off[p], op_off[p + 1] - op_off[p], prm + prm_off[p], prm_off[p + 1] - prm_off[p], noise[p]));
-    return predict_core(c, n, ts_pred, m, P, bt, noise, noise_pred, nullptr, nullptr, mean_train, mean_pred, out_mean,
-                        out_var, out_cov, out_info, want_keys ? &keys : nullptr, &pl);
-  }
-  std::vector<int32_t> uo(U + 1, 0), up(U + 1, 0), uinfo(U, 0);
-  std::vector<uint8_t> uops; std::vector<double> uprm, unoise(U), unp(noise_pred ? U : 0);
-  for (int u = 0; u < U; ++u) {
-    const int p = uniq[u];
-    uops.insert(uops.end(), ops + op_off[p], ops + op_off[p + 1]);
-    uprm.insert(uprm.end(), prm + prm_off[p], prm + prm_off[p + 1]);
-    uo[u + 1] = (int32_t)uops.size(); up[u + 1] = (int32_t)uprm.size();
-    unoise[u] = noise[p];
-    if (noise_pred) unp[u] = noise_pred[p];
-  }
-  if (uprm.empty()) uprm.push_back(0.0);
+      for (int u = 0; u < Pb; ++u) keys.push_back(particle_key(so + oo[u], oo[u + 1] - oo[u], sp + po[u], po[u + 1] - po[u], nz[u]));
+    return predict_core(c, n, ts_pred, m, Pb, bt, nz, nzp, nullptr, nullptr, mean_train, mean_pred, om, ov, oc, oi,
+                        want_keys ? &keys : nullptr, &pl);
+  };
+  if (U == 0 || U == P)
+    return run(P, op_off, ops, prm_off, prm, noise, noise_pred, out_mean, out_var, out_cov, out_info);
+  SubBatch S;
+  pack_particles(uniq, op_off, ops, prm_off, prm, noise, noise_pred, S);
+  S.outputs(false);
   std::vector<double> umean((size_t)U * m), uvar((size_t)U * m), ucov(out_cov ? (size_t)U * m * m : 0);
-  Batch bt;
-  const int nt1_ = (int)((n + NB - 1) / NB), nt_ = nt1_ + (int)((m_joint + NB - 1) / NB);
-  const bool ff = n > 0 && use_flow(c, U, nt_, nt1_);
-  const bool fh = ff;
-  int rc = compile_batch(c, U, uo.data(), uops.data(), up.data(), uprm.data(), bt, false, false, false, fh, ff, pl.on, pl.on ? pl.rank_units : 1, pl.on);
-  if (rc) return rc;
-  std::vector<std::string> keys;
-  if (want_keys)
-    for (int u = 0; u < U; ++u)
-      keys.push_back(particle_key(uops.data() + uo[u], uo[u + 1] - uo[u], uprm.data() + up[u], up[u + 1] - up[u], unoise[u]));
-  rc = predict_core(c, n, ts_pred, m, U, bt, unoise.data(), noise_pred ? unp.data() : nullptr, nullptr, nullptr, mean_train,
-                    mean_pred, umean.data(), uvar.data(), out_cov ? ucov.data() : nullptr, uinfo.data(), want_keys ? &keys : nullptr, &pl);
+  const int rc = run(U, S.op_off.data(), S.ops.data(), S.prm_off.data(), S.prm.data(), S.noise.data(), noise_pred ? S.noise_pred.data() : nullptr,
+                     umean.data(), uvar.data(), out_cov ? ucov.data() : nullptr, S.info.data());
   if (rc) return rc;
   for (int p = 0; p < P; ++p) {
     const size_t u = (size_t)rep[p];
     std::memcpy(out_mean + (size_t)p * m, umean.data() + u * m, sizeof(double) * (size_t)m);
     std::memcpy(out_var + (size_t)p * m, uvar.data() + u * m, sizeof(double) * (size_t)m);
     if (out_cov) std::memcpy(out_cov + (size_t)p * m * m, ucov.data() + u * m * m, sizeof(double) * (size_t)m * m);
-    if (out_info) out_info[p] = uinfo[u];
+    if (out_info) out_info[p] = S.info[u];
   }
   return AGP_OK;
 }
@@ -1036,59 +922,30 @@ static int predict_logpdf_body(agp_ctx* c, int64_t n, const double* ts_pred, con
   if (!op_off || !ops || !prm_off || !prm || !noise || !ts_pred || !y_pred) return fail(c, AGP_ERR_ARG, "null pointer argument");
   HIPCHK(c, hipSetDevice(c->device));
   // identical particles (a resampled population, src/inference_smc_anneal_data.jl:198-204) are evaluated once, as in agp_predict_batch
-  std::vector<int> rep(P), uniq;
-  bool sane = true;
-  for (int p = 0; p < P && sane; ++p)
-    sane = op_off[p + 1] >= op_off[p] && prm_off[p + 1] >= prm_off[p] && op_off[p] >= 0 && prm_off[p] >= 0;
-  if (c->dedup && P > 1 && sane) {
-    std::unordered_map<std::string, int> seen;
-    seen.reserve((size_t)P * 2);
-    for (int p = 0; p < P; ++p) {
-      const int no = op_off[p + 1] - op_off[p], np = prm_off[p + 1] - prm_off[p];
-      const int32_t lens[2] = {no, np};
-      std::string key(reinterpret_cast<const char*>(lens), sizeof lens);
-      key.append(reinterpret_cast<const char*>(ops + op_off[p]), (size_t)no);
-      key.append(reinterpret_cast<const char*>(prm + prm_off[p]), sizeof(double) * (size_t)np);
-      key.append(reinterpret_cast<const char*>(noise + p), sizeof(double));
-      if (noise_pred) key.append(reinterpret_cast<const char*>(noise_pred + p), sizeof(double));
-      auto it = seen.find(key);
-      if (it == seen.end()) { seen.emplace(std::move(key), (int)uniq.size()); rep[p] = (int)uniq.size(); uniq.push_back(p); }
-      else rep[p] = it->second;
-    }
-  } else {
-    for (int p = 0; p < P; ++p) { rep[p] = p; uniq.push_back(p); }
-  }
-  const int U = (int)uniq.size();
-  std::vector<int32_t> uo(U + 1, 0), up(U + 1, 0), uinfo(U, 0);
-  std::vector<uint8_t> uops; std::vector<double> uprm, unoise(U), unp(noise_pred ? U : 0), ulp(U);
-  if (U == P) {
-    uo.assign(op_off, op_off + P + 1); up.assign(prm_off, prm_off + P + 1);
-  }
-  for (int u = 0; u < U; ++u) {
-    const int p = uniq[u];
-    if (U < P) {
-      uops.insert(uops.end(), ops + op_off[p], ops + op_off[p + 1]);
-      uprm.insert(uprm.end(), prm + prm_off[p], prm + prm_off[p + 1]);
-      uo[u + 1] = (int32_t)uops.size(); up[u + 1] = (int32_t)uprm.size();
-    }
-    unoise[u] = noise[p];
-    if (noise_pred) unp[u] = noise_pred[p];
-  }
-  if (uprm.empty()) uprm.push_back(0.0);
-  const uint8_t* cops = U < P ? uops.data() : ops;
-  const double* cprm = U < P ? uprm.data() : prm;
+  // (malformed offsets, c->dedup off: every particle — compile_batch diagnoses the offsets)
+  std::vector<int> rep, uniq;
+  if (c->dedup && P > 1) (void)distinct_particles(P, op_off, ops, prm_off, prm, noise, noise_pred, rep, uniq);
+  const bool packed = !uniq.empty() && (int)uniq.size() < P;
+  SubBatch S;
+  if (packed) pack_particles(uniq, op_off, ops, prm_off, prm, noise, noise_pred, S);
+  const int U = packed ? (int)uniq.size() : P;
+  const int32_t* bo = packed ? S.op_off.data() : op_off; const int32_t* bpo = packed ? S.prm_off.data() : prm_off;
+  const uint8_t* bops = packed ? S.ops.data() : ops; const double* bprm = packed ? S.prm.data() : prm;
+  const double* bnz = packed ? S.noise.data() : noise; const double* bnzp = packed && noise_pred ? S.noise_pred.data() : noise_pred;
+  std::vector<double> ulp((size_t)U);
+  std::vector<int32_t> uinfo((size_t)U, 0);
   PredLattice pl;
   predict_lattice(c, n, ts_pred, m, pl);
   const bool ff = c->flow != 0;      // (predict_logpdf_core's schedule)
   Batch bt;
-  int rc = compile_batch(c, U, uo.data(), cops, up.data(), cprm, bt, false, false, false, ff, ff, pl.on, pl.on ? pl.rank_units : 1, pl.on);
+  int rc = compile_batch(c, U, bo, bops, bpo, bprm, bt, false, false, false, ff, ff, pl.on, pl.on ? pl.rank_units : 1, pl.on);
   if (rc) return rc;
-  rc = predict_logpdf_core(c, n, ts_pred, y_pred, m, U, bt, unoise.data(), noise_pred ? unp.data() : nullptr, mean_train, mean_pred,
-                           ulp.data(), uinfo.data(), &pl);
+  rc = predict_logpdf_core(c, n, ts_pred, y_pred, m, U, bt, bnz, bnzp, mean_train, mean_pred, ulp.data(), uinfo.data(), &pl);
   if (rc) return rc;
   for (int p = 0; p < P; ++p) {
-    out_logpdf[p] = ulp[(size_t)rep[p]];
-    if (out_info) out_info[p] = uinfo[(size_t)rep[p]];
+    const size_t u = packed ? (size_t)rep[p] : (size_t)p;
+    out_logpdf[p] = ulp[u];
+    if (out_info) out_info[p] = uinfo[u];
   }
   return AGP_OK;
 }

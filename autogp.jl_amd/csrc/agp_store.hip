@@ -132,29 +132,14 @@ int extend_impl(agp_ctx* c, int64_t n, int32_t P, const int32_t* op_off, const u
   auto plain = [&]() { return agp_logpdf_batch(c, n, P, op_off, ops, prm_off, prm, noise, out_lp, out_info); };
   HIPCHK(c, hipSetDevice(c->device));
 
-  // distinct particles (a resampled population holds copies)
+  // distinct particles (a resampled population holds copies; the offsets were checked above)
   HostProf hp_k(10);
-  std::unordered_map<std::string, int> seen;
-  seen.reserve((size_t)P * 2);
-  std::vector<int> rep(P), uniq;
+  std::vector<int> rep, uniq;
   std::vector<std::string> keys;
-  for (int p = 0; p < P; ++p) {
-    std::string key = particle_key(ops + op_off[p], op_off[p + 1] - op_off[p], prm + prm_off[p], prm_off[p + 1] - prm_off[p], noise[p]);
-    auto it = seen.find(key);
-    if (it == seen.end()) { seen.emplace(key, (int)uniq.size()); rep[p] = (int)uniq.size(); uniq.push_back(p); keys.push_back(std::move(key)); }
-    else rep[p] = it->second;
-  }
+  (void)distinct_particles(P, op_off, ops, prm_off, prm, noise, nullptr, rep, uniq, &keys);
   const int U = (int)uniq.size();
-  std::vector<int32_t> uo(U + 1, 0), up(U + 1, 0);
-  std::vector<uint8_t> uops; std::vector<double> uprm, unoise(U);
-  for (int u = 0; u < U; ++u) {
-    const int p = uniq[u];
-    uops.insert(uops.end(), ops + op_off[p], ops + op_off[p + 1]);
-    uprm.insert(uprm.end(), prm + prm_off[p], prm + prm_off[p + 1]);
-    uo[u + 1] = (int32_t)uops.size(); up[u + 1] = (int32_t)uprm.size();
-    unoise[u] = noise[p];
-  }
-  if (uprm.empty()) uprm.push_back(0.0);
+  SubBatch S;
+  pack_particles(uniq, op_off, ops, prm_off, prm, noise, nullptr, S);
 
   const int n_pad = round_up(n, NB), nt = n_pad / NB;
   agp_ctx::FactorStore& fs = c->store;
@@ -289,7 +274,7 @@ int extend_impl(agp_ctx* c, int64_t n, int32_t P, const int32_t* op_off, const u
   // threads 3 171 -> 3 376; from three tile rows on fusing wins again (n = 300: 602 vs 563).  The rule reads the resident series
   // alone — not this sweep's prefix or population — so an extension and a from-scratch sweep of the entry keep one arithmetic.)
   const bool small_series = (c->n_max + NB - 1) / NB <= 2;
-  int rc = compile_batch(c, U, uo.data(), uops.data(), up.data(), uprm.data(), bt, false, false, ge_tab, /*fuse_hint=*/true,
+  int rc = compile_batch(c, U, S.op_off.data(), S.ops.data(), S.prm_off.data(), S.prm.data(), bt, false, false, ge_tab, /*fuse_hint=*/true,
                          /*flow_limit=*/c->flow != 0 && U <= FLOW_MAX_PARTICLES, rankm, rankm ? tab_units : 1, rank_extra,
                          /*never_fuse=*/small_series);
   if (rc) { forget_touched(); return rc; }
@@ -303,19 +288,16 @@ int extend_impl(agp_ctx* c, int64_t n, int32_t P, const int32_t* op_off, const u
   Slot* s = sg.s;
   if (!s->stream) HIPCHK(c, hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
   hipStream_t st = s->stream;
-  auto al16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
   const size_t o_hdr = 0;
-  const size_t o_prm = al16(o_hdr + sizeof(ProgHdr) * (size_t)U);
-  const size_t o_noise = al16(o_prm + sizeof(double) * std::max<size_t>(1, bt.prm.size()));
-  const size_t o_map = al16(o_noise + sizeof(double) * (size_t)U);
-  const size_t o_slot = al16(o_map + sizeof(int32_t) * (size_t)U);
-  const size_t o_i0 = al16(o_slot + sizeof(int32_t) * (size_t)U);
-  const size_t o_ops = al16(o_i0 + sizeof(int32_t) * (size_t)U);
-  const size_t o_rep = al16(o_ops + bt.ops.size() + 4);                  // caller particle -> distinct particle (d_out_caller)
-  const size_t o_thdr = al16(o_rep + (d_out_caller ? sizeof(int32_t) * (size_t)P : 0));      // lag-table programs (rank tables)
-  const size_t o_tprm = al16(o_thdr + sizeof(LagTabHdr) * bt.thdr.size());
-  const size_t o_tops = al16(o_tprm + sizeof(double) * bt.tprm.size());
-  const size_t stage_bytes = al16(o_tops + bt.tops.size() + 4);
+  const size_t o_prm = align16(o_hdr + sizeof(ProgHdr) * (size_t)U);
+  const size_t o_noise = align16(o_prm + sizeof(double) * std::max<size_t>(1, bt.prm.size()));
+  const size_t o_map = align16(o_noise + sizeof(double) * (size_t)U);
+  const size_t o_slot = align16(o_map + sizeof(int32_t) * (size_t)U);
+  const size_t o_i0 = align16(o_slot + sizeof(int32_t) * (size_t)U);
+  const size_t o_ops = align16(o_i0 + sizeof(int32_t) * (size_t)U);
+  const size_t o_rep = align16(o_ops + bt.ops.size() + 4);               // caller particle -> distinct particle (d_out_caller)
+  const LagProgLayout lpl(bt, o_rep + (d_out_caller ? sizeof(int32_t) * (size_t)P : 0));      // lag-table programs (rank tables)
+  const size_t stage_bytes = lpl.end;
   auto hipfail = [&](hipError_t e, const char* what) {
     forget_touched();
     return fail(c, AGP_ERR_HIP, std::string("HIP error in the extension sweep (") + what + "): " + hipGetErrorString(e));
@@ -332,18 +314,14 @@ int extend_impl(agp_ctx* c, int64_t n, int32_t P, const int32_t* op_off, const u
     double* hn = reinterpret_cast<double*>(h + o_noise);
     int32_t* hs = reinterpret_cast<int32_t*>(h + o_slot);
     int32_t* hi = reinterpret_cast<int32_t*>(h + o_i0);
-    for (int q = 0; q < U; ++q) { const int u = bt.order[q]; hn[q] = unoise[u]; hs[q] = slot[u]; hi[q] = i0[u]; }
+    for (int q = 0; q < U; ++q) { const int u = bt.order[q]; hn[q] = S.noise[u]; hs[q] = slot[u]; hi[q] = i0[u]; }
     std::memcpy(h + o_map, bt.order.data(), sizeof(int32_t) * (size_t)U);
     std::memcpy(h + o_ops, bt.ops.data(), bt.ops.size());
     if (d_out_caller) {
       int32_t* hr = reinterpret_cast<int32_t*>(h + o_rep);
       for (int p = 0; p < P; ++p) hr[p] = rep[p];
     }
-    if (!bt.thdr.empty()) {
-      std::memcpy(h + o_thdr, bt.thdr.data(), sizeof(LagTabHdr) * bt.thdr.size());
-      std::memcpy(h + o_tprm, bt.tprm.data(), sizeof(double) * bt.tprm.size());
-      std::memcpy(h + o_tops, bt.tops.data(), bt.tops.size());
-    }
+    lpl.pack(h);
   }
   char* dstage = static_cast<char*>(s->stage.p);
   EXTCHK(hipMemcpyAsync(dstage, s->h_stage.p, stage_bytes, hipMemcpyHostToDevice, st));
@@ -356,9 +334,9 @@ int extend_impl(agp_ctx* c, int64_t n, int32_t P, const int32_t* op_off, const u
     if (rankm && bt.n_lag_tables > 0) {
       EXTCHK(s->lagtab.ensure(sizeof(double) * (size_t)bt.n_lag_tables * tab_gstride));
       LagArgs la = {};
-      la.tt = cltw ? c->d_clt_tt : c->d_ts_lat; la.thdr = reinterpret_cast<const LagTabHdr*>(dstage + o_thdr);
-      la.tops = reinterpret_cast<const uint8_t*>(dstage + o_tops); la.tprm = reinterpret_cast<const double*>(dstage + o_tprm);
-      la.n_tables = bt.n_lag_tables; la.tab = s->lagtab.as<double>(); la.nt = cltw ? tab_gstride / NB : (int)((c->n_lat + NB - 1) / NB);
+      la.tt = cltw ? c->d_clt_tt : c->d_ts_lat;
+      lpl.point(la, dstage);
+      la.tab = s->lagtab.as<double>(); la.nt = cltw ? tab_gstride / NB : (int)((c->n_lat + NB - 1) / NB);
       la.full = 1; la.stride = tab_gstride;
       launch_lag_tables(st, la, tab_gstride / 256, bt.n_lag_tables);
       EXTCHK(hipGetLastError());
