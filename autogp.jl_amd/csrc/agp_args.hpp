@@ -161,10 +161,24 @@ struct PredArgs {
   const double* mu2;        // [m] or null
   const double* noise_pred; // [P]
   const double* diag_add;   // [m] extra diagonal term per prediction point (infer_gp_sum) or null
+  const uint8_t* np_code;   // [m] query codes (infer_gp_sum_batch) or null: noise_pred then goes on the code-0 rows only, after
+                            // diag_add (A + 0 + (diag_add + noise_pred), the single entry's order); null: A + noise_pred + diag_add
   int nt1, n1_pad, m, P;
   double* out_mean;         // [P][m]
   double* out_var;          // [P][m]
   double* out_cov;          // [P][m*m] or null
+};
+
+// predict_sum's read-out (k_sum_readout, agp_sum_kernel.hpp)
+struct SumReadArgs {
+  double* mean;            // [P][m] in: predictive means (k_pred_extract), out: raw means
+  const double* var;       // [P][m] predictive variances
+  int m, p_rows;           // joint rows (M + 1) p; the F_1 rows are [0, p_rows)
+  double slope, intercept, shift, ivar;      // y_transform; shift = intercept / slope; ivar = 1 / slope^2
+  const double* z;         // [nq] ndtri(q)
+  int nq;
+  double* x;               // [P][m][nq]
+  int32_t* bad;            // [P] smallest failing row + 1, or untouched
 };
 
 struct GradArgs {

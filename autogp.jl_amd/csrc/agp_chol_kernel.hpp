@@ -1495,17 +1495,23 @@ __global__ void k_init_query_vec(double* vec, int ldv, int off, int m, const dou
 
 // Predictive read-out (src/GP.jl:753-757): mean = mu2 + K21 K11^-1 (x - mu1),
 // cov = sym(K22 - K21 K11^-1 K12) + noise_pred I, var = diag(cov).
+// With np_code (infer_gp_sum_batch): the row term is 0 and noise_pred joins diag_add on the observable (code 0) rows only.
 __global__ void k_pred_extract(PredArgs a) {
   const int p = blockIdx.y;
   const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   const double* Ap = a.A + (long long)p * a.strideA;
-  const double np = a.noise_pred[p];
+  const double np = a.np_code ? 0.0 : a.noise_pred[p];
+  const double npo = a.np_code ? a.noise_pred[p] : 0.0;
+  auto dadd = [&](int g) {
+    if (a.np_code) return a.diag_add[g] + (a.np_code[g] == 0 ? npo : 0.0);
+    return a.diag_add ? a.diag_add[g] : 0.0;
+  };
   if (idx < a.m) {
     const int g = (int)idx;
     const double r = a.vec[(long long)p * a.ldv + a.n1_pad + g];
     a.out_mean[(long long)p * a.m + g] = (a.mu2 ? a.mu2[g] : 0.0) - r;
     const int t = a.nt1 + g / NB, o = g % NB;
-    a.out_var[(long long)p * a.m + g] = Ap[tile_off(t, t) + (long long)o * NB + o] + np + (a.diag_add ? a.diag_add[g] : 0.0);
+    a.out_var[(long long)p * a.m + g] = Ap[tile_off(t, t) + (long long)o * NB + o] + np + dadd(g);
   }
   if (a.out_cov) {
     const long long mm = (long long)a.m * a.m;
@@ -1514,7 +1520,7 @@ __global__ void k_pred_extract(PredArgs a) {
       const int hi = r > c ? r : c, lo = r > c ? c : r;
       const int ti = a.nt1 + hi / NB, tj = a.nt1 + lo / NB;
       double v = Ap[tile_off(ti, tj) + (long long)(lo % NB) * NB + (hi % NB)];
-      if (r == c) v += np + (a.diag_add ? a.diag_add[r] : 0.0);
+      if (r == c) v += np + dadd(r);
       a.out_cov[(long long)p * mm + idx] = v;
     }
   }

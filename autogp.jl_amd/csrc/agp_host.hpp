@@ -171,7 +171,8 @@ struct Slot {
   DevBuf A{Fill::values}, W{Fill::values}, vec{Fill::values}, partial{Fill::values}, out_lp{Fill::values},
       noise{Fill::values}, noise_pred{Fill::values}, mu1{Fill::values}, mu2{Fill::values}, pred_mean{Fill::values},
       pred_var{Fill::values}, pred_cov{Fill::values}, dense{Fill::values}, diag_add{Fill::values}, Z{Fill::values},
-      alpha{Fill::values}, tsol{Fill::values}, gpart{Fill::values}, dgrad{Fill::values}, dgnoise{Fill::values}, lagtab{Fill::values};
+      alpha{Fill::values}, tsol{Fill::values}, gpart{Fill::values}, dgrad{Fill::values}, dgnoise{Fill::values}, lagtab{Fill::values},
+      sum_x{Fill::values}, sum_z{Fill::values};
   // addresses, indices, counts, programs (their parameters included: uploaded whole), times, flags
   DevBuf info{Fill::never}, out_info{Fill::never}, hdr{Fill::never}, ops{Fill::never}, prm{Fill::never}, tt{Fill::never}, map{Fill::never},
       ready{Fill::never}, code{Fill::never}, tretry{Fill::never}, ghdr{Fill::never}, gops{Fill::never}, glc{Fill::never},
@@ -179,7 +180,7 @@ struct Slot {
       tflag{Fill::never}, flowq{Fill::never}, pl_rank{Fill::never}, pl_tl{Fill::never}, pl_prog{Fill::never};
   template <class F> void for_each_dev(F&& f) {
     for (DevBuf* b : {&stage, &up_blob, &up_blob2, &A, &W, &vec, &partial, &out_lp, &out_info, &noise, &noise_pred, &mu1, &mu2,
-                      &pred_mean, &pred_var, &pred_cov, &dense, &diag_add, &Z, &alpha, &tsol, &gpart, &dgrad, &dgnoise, &lagtab,
+                      &pred_mean, &pred_var, &pred_cov, &dense, &diag_add, &Z, &alpha, &tsol, &gpart, &dgrad, &dgnoise, &lagtab, &sum_x, &sum_z,
                       &info, &hdr, &ops, &prm, &tt, &map, &ready, &code, &tretry, &ghdr, &gops, &glc, &grc, &gpoff, &gprm, &gmap,
                       &goff, &plist, &tflag, &flowq, &pl_rank, &pl_tl, &pl_prog})
       f(*b);

@@ -5,6 +5,7 @@
 #include "agp_chol_kernel.hpp"
 #include "agp_toep_kernel.hpp"
 #include "agp_quantile_kernel.hpp"
+#include "agp_sum_kernel.hpp"
 #include "agp_comm.hpp"
 
 namespace agp {
@@ -167,6 +168,9 @@ void launch_mixture_quantile(hipStream_t st, const double* cm, const double* cs,
   const long long nw = (long long)m * nq;
   hipLaunchKernelGGL(k_mixture_quantile, dim3((unsigned)((nw + MQ_WAVES - 1) / MQ_WAVES)), dim3(64 * MQ_WAVES), 0, st, cm, cs, cw, Pp, m,
                      q, nq, tol, max_iter, out_x, out_conv, out_iters);
+}
+void launch_sum_readout(hipStream_t st, int P, const SumReadArgs& a) {
+  hipLaunchKernelGGL(k_sum_readout, dim3((unsigned)((a.m + 255) / 256), P), dim3(256), 0, st, a);
 }
 void launch_mfma_peak(int nblk, double* out, long long* cycles, int iters, int mode) {
   hipLaunchKernelGGL(k_mfma_peak, dim3(nblk), dim3(256), 0, 0, out, cycles, iters, mode);

@@ -49,6 +49,8 @@ void launch_mfma_peak(int nblk, double* out, long long* cycles, int iters, int m
 void launch_mixture_pack(hipStream_t st, const double* means, const double* vars, int P, int Pp, int m, double* cm, double* cs);
 void launch_mixture_quantile(hipStream_t st, const double* cm, const double* cs, const double* cw, int Pp, int m, const double* q,
                              int nq, double tol, long long max_iter, double* out_x, int32_t* out_conv, int32_t* out_iters);
+// predict_sum's read-out (agp_predict.hip): raw transform, F_1 intercept, marginal quantiles on a chunk's device marginals
+void launch_sum_readout(hipStream_t st, int P, const SumReadArgs& a);
 
 // ---- agp_kernels_grad.hip --------------------------------------------------------------------------------------------
 hipError_t kernels_init_grad();

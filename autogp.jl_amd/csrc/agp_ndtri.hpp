@@ -1,0 +1,67 @@
+// Inverse of the standard normal CDF in fp64, host and device: Wichura's algorithm AS 241 (PPND16, Applied Statistics 37 (1988)
+// 477-484), three rational approximations of degree 7 / 7 (|p - 1/2| <= 0.425, then in r = sqrt(-log(min(p, 1 - p))) for r <= 5 and
+// r > 5).  Used by predict_sum's read-out (agp_predict_sum_batch): quantile(Normal(mu, sigma), q) = mu + sigma * ndtri(q), evaluated
+// as fma(sigma, ndtri(q), mu) — sigma == 0 gives mu exactly.
+//
+// Measured error (tests/test_sum_decomposition_cpu.py: this header compiled with g++ against mpmath at 40 digits, q in
+// [1e-300, 1 - 1e-16] log- and linearly spaced): at most 7.2e-16 relative to |ndtri(q)| (in the far tail, q ~ 1e-197), stated as
+// AGP_NDTRI_REL_BOUND = 1e-15; near q = 1/2, where ndtri(q) passes through 0, the bound holds on an absolute scale of 1/8.
+// The reference evaluates Distributions' quantile through SpecialFunctions.erfcinv, which the tests cannot run: parity with it is
+// to rounding (a few ulps), not bit for bit.
+#pragma once
+#include <math.h>
+
+#if defined(__HIPCC__)
+#define AGP_NDTRI_FN __host__ __device__ inline
+#else
+#define AGP_NDTRI_FN inline
+#endif
+
+namespace agp {
+
+constexpr double AGP_NDTRI_REL_BOUND = 1e-15;
+
+AGP_NDTRI_FN double ndtri(double p) {
+  if (!(p > 0.0 && p < 1.0)) {
+    if (p == 0.0) return -HUGE_VAL;
+    if (p == 1.0) return HUGE_VAL;
+    return NAN;
+  }
+  const double q = p - 0.5;
+  if (fabs(q) <= 0.425) {
+    const double r = 0.180625 - q * q;
+    const double num = (((((((2.5090809287301226727e+3 * r + 3.3430575583588128105e+4) * r + 6.7265770927008700853e+4) * r +
+                            4.5921953931549871457e+4) * r + 1.3731693765509461125e+4) * r + 1.9715909503065514427e+3) * r +
+                         1.3314166789178437745e+2) * r + 3.3871328727963666080e+0);
+    const double den = (((((((5.2264952788528545610e+3 * r + 2.8729085735721942674e+4) * r + 3.9307895800092710610e+4) * r +
+                            2.1213794301586595867e+4) * r + 5.3941960214247511077e+3) * r + 6.8718700749205790830e+2) * r +
+                         4.2313330701600911252e+1) * r + 1.0);
+    return q * num / den;
+  }
+  // (1 - p is exact for p >= 1/2)
+  double r = q < 0.0 ? p : 1.0 - p;
+  r = sqrt(-log(r));
+  double v;
+  if (r <= 5.0) {
+    r -= 1.6;
+    const double num = (((((((7.74545014278341407640e-4 * r + 2.27238449892691845833e-2) * r + 2.41780725177450611770e-1) * r +
+                            1.27045825245236838258e+0) * r + 3.64784832476320460504e+0) * r + 5.76949722146069140550e+0) * r +
+                         4.63033784615654529590e+0) * r + 1.42343711074968357734e+0);
+    const double den = (((((((1.05075007164441684324e-9 * r + 5.47593808499534494600e-4) * r + 1.51986665636164571966e-2) * r +
+                            1.48103976427480074590e-1) * r + 6.89767334985100004550e-1) * r + 1.67638483018380384940e+0) * r +
+                         2.05319162663775882187e+0) * r + 1.0);
+    v = num / den;
+  } else {
+    r -= 5.0;
+    const double num = (((((((2.01033439929228813265e-7 * r + 2.71155556874348757815e-5) * r + 1.24266094738807843860e-3) * r +
+                            2.65321895265761230930e-2) * r + 2.96560571828504891230e-1) * r + 1.78482653991729133580e+0) * r +
+                         5.46378491116411436990e+0) * r + 6.65790464350110377720e+0);
+    const double den = (((((((2.04426310338993978564e-15 * r + 1.42151175831644588870e-7) * r + 1.84631831751005468180e-5) * r +
+                            7.86869131145613259100e-4) * r + 1.48753612908506148525e-2) * r + 1.36929880922735805310e-1) * r +
+                         5.99832206555887937690e-1) * r + 1.0);
+    v = num / den;
+  }
+  return q < 0.0 ? -v : v;
+}
+
+}  // namespace agp

@@ -1,5 +1,6 @@
 // Host side of the C ABI, unit 2: predictive entries (src/GP.jl:731-758, 904-993), matrix assembly and the probe entries.
 #include "agp_host.hpp"
+#include "agp_ndtri.hpp"
 #ifdef AGP_EXPERIMENTS
 #include "experiments/agp_experiments_abi.h"
 #include "experiments/agp_experiments.hpp"   // ablation kernels of the update GEMM (measurement builds only: libautogp_hip_exp.so)
@@ -168,11 +169,24 @@ int launch_joint_flow(agp_ctx* c, Slot* s, hipStream_t st, CholArgs& ca, int dco
   return AGP_OK;
 }
 
+// What the batched sum-of-GPs entries (agp_infer_gp_sum_batch, agp_predict_sum_batch) ask of predict_core on top of pred_code /
+// diag_add: each particle's noise_pred on the observable (code 0) query rows only, the dataflow schedule whatever the batch
+// (AGP_FLOW=0: the per-column launches) — a particle's bits then do not depend on the batch, its order, copies or chunking — and,
+// for predict_sum, the device read-out k_sum_readout: out_mean receives raw means, out_var is not written, out_x [P][m][nq] the
+// marginal quantiles, and a particle whose raw marginals fail at row j (0-based) gets info n + j + 1.
+struct SumPass {
+  bool readout = false;
+  int64_t p_rows = 0;                    // query points per component (the F_1 rows)
+  double slope = 1.0, intercept = 0.0;
+  std::vector<double> z;                 // ndtri(q)
+  double* out_x = nullptr;
+};
+
 int predict_core(agp_ctx* c, int64_t n, const double* ts_pred, int64_t m, int32_t P, Batch& bt,
                  const double* noise, const double* noise_pred, const uint8_t* pred_code, const double* diag_add,
                  const double* mean_train, const double* mean_pred, double* out_mean, double* out_var,
                  double* out_cov, int32_t* out_info, const std::vector<std::string>* keys = nullptr,
-                 const PredLattice* pl = nullptr) {
+                 const PredLattice* pl = nullptr, const SumPass* sum = nullptr) {
   const int n1_pad = round_up(n, NB);           // 0 when n == 0
   const bool lagr = pl != nullptr && pl->on;
   // ---- query points that ARE training points, no covariance requested ----------------------------------------------
@@ -229,6 +243,13 @@ int predict_core(agp_ctx* c, int64_t n, const double* ts_pred, int64_t m, int32_
   HIPCHK(c, s->pred_mean.ensure(sizeof(double) * (size_t)std::max<int64_t>(1, mJ) * chunk));
   HIPCHK(c, s->pred_var.ensure(sizeof(double) * (size_t)std::max<int64_t>(1, mJ) * chunk));
   if (out_cov) HIPCHK(c, s->pred_cov.ensure(sizeof(double) * (size_t)m * m * chunk));
+  const bool ro = sum && sum->readout;
+  const int nq = ro ? (int)sum->z.size() : 0;
+  if (ro) {
+    HIPCHK(c, s->sum_x.ensure(sizeof(double) * (size_t)std::max<int64_t>(1, mJ) * std::max(1, nq) * chunk));
+    HIPCHK(c, s->sum_z.ensure(sizeof(double) * (size_t)std::max(1, nq)));
+    HIPCHK(c, s->out_info.ensure(sizeof(int32_t) * (size_t)P));
+  }
   PinnedUploads up;
   std::vector<double> noise_sorted, npred;
   if (const int rc = stage_joint(c, s, up, n, tsJ, mJ, P, chunk, bt, noise, noise_pred, mean_train, meanJ, noise_sorted, npred)) return rc;
@@ -242,6 +263,7 @@ int predict_core(agp_ctx* c, int64_t n, const double* ts_pred, int64_t m, int32_
     HIPCHK(c, s->diag_add.ensure(sizeof(double) * (size_t)mJ));
     up.add(s->diag_add.p, daddJ, sizeof(double) * mJ);
   }
+  if (nq > 0) up.add(s->sum_z.p, sum->z.data(), sizeof(double) * nq);
 
   const int32_t* d_src = nullptr; const int32_t* d_i0 = nullptr;
   // Resident L^-T: a pass that starts from resident factors AND serves observed points from alpha / diag(K11^-1) keeps Z = L^-T in
@@ -298,14 +320,16 @@ int predict_core(agp_ctx* c, int64_t n, const double* ts_pred, int64_t m, int32_
     if (const int rc = flush_lattice(c, s, st, up, bt, *pl, diag_path ? rankF : pl->rank)) return rc;
   }
 
+  if (ro) HIPCHK(c, hipMemsetAsync(s->out_info.p, 0x7f, sizeof(int32_t) * (size_t)P, st));      // (no failing row: 0x7f7f7f7f)
   const double* h_mean = nullptr; const double* h_var = nullptr; const double* h_alpha = nullptr; const double* h_dinv = nullptr;      // in the slot's pinned landing zone
+  const double* h_x = nullptr;
   for (int p0 = 0; p0 < P; p0 += chunk) {
     const int Pc = std::min(chunk, P - p0);
     {
       const size_t nm = (size_t)std::max<int64_t>(1, mJ) * Pc, nd = diag_path ? (size_t)ntot * Pc : 0;
-      HIPCHK(c, s->h_out.ensure(sizeof(double) * (2 * nm + 2 * nd)));
+      HIPCHK(c, s->h_out.ensure(sizeof(double) * (2 * nm + 2 * nd + nm * nq)));
       double* hz = static_cast<double*>(s->h_out.p);
-      h_mean = hz; h_var = hz + nm; h_alpha = hz + 2 * nm; h_dinv = hz + 2 * nm + nd;
+      h_mean = hz; h_var = hz + nm; h_alpha = hz + 2 * nm; h_dinv = hz + 2 * nm + nd; h_x = hz + 2 * nm + 2 * nd;
     }
     launch_init_vec(st, ntot, Pc, s->vec.as<double>(), c->d_xs, (mean_train && n > 0) ? s->mu1.as<double>() : (const double*)nullptr, (int)n, s->info.as<int>() + p0, s->ready.as<int>() + p0);
     if (n_hit > 0) {
@@ -343,7 +367,7 @@ int predict_core(agp_ctx* c, int64_t n, const double* ts_pred, int64_t m, int32_
     ca.ready = s->ready.as<int>() + p0;
     if (n_hit > 0 || diag_path) ca.wsteps = nt1;      // panel solves of the prediction rows / the chains of Z read every column's inverse blocks
     if (n_hit > 0) ca.i0 = d_i0 + p0;
-    if (nt1 > 0 && use_flow(c, Pc, nt, nt1)) {
+    if (nt1 > 0 && (sum ? c->flow != 0 : use_flow(c, Pc, nt, nt1))) {
       // dataflow schedule over the block columns of the training block (all rows: V = L^-1 K12 comes out of the same tiles)
       if (const int rc = launch_joint_flow(c, s, st, ca, dcov, nt1)) return rc;
     } else if (n_hit > 0) {
@@ -428,14 +452,26 @@ int predict_core(agp_ctx* c, int64_t n, const double* ts_pred, int64_t m, int32_
     pa.mu2 = mean_pred ? s->mu2.as<double>() : nullptr; pa.noise_pred = s->noise_pred.as<double>() + p0;
     pa.nt1 = nt1; pa.n1_pad = n1_pad; pa.m = (int)mJ; pa.P = Pc;
     pa.diag_add = diag_add ? s->diag_add.as<double>() : nullptr;
+    pa.np_code = sum ? s->code.as<uint8_t>() + n1_pad : nullptr;
     pa.out_mean = s->pred_mean.as<double>(); pa.out_var = s->pred_var.as<double>();
     pa.out_cov = out_cov ? s->pred_cov.as<double>() : nullptr;
     const long long nel = out_cov ? (long long)mJ * mJ : (long long)mJ;
     launch_pred_extract(st, nel, Pc, pa);
     HIPCHK(c, hipGetLastError());
+    if (ro) {
+      SumReadArgs ra = {};
+      ra.mean = s->pred_mean.as<double>(); ra.var = s->pred_var.as<double>(); ra.m = (int)mJ; ra.p_rows = (int)sum->p_rows;
+      ra.slope = sum->slope; ra.intercept = sum->intercept; ra.shift = sum->intercept / sum->slope;
+      ra.ivar = 1.0 / (sum->slope * sum->slope);
+      ra.z = s->sum_z.as<double>(); ra.nq = nq; ra.x = s->sum_x.as<double>(); ra.bad = s->out_info.as<int32_t>() + p0;
+      launch_sum_readout(st, Pc, ra);
+      HIPCHK(c, hipGetLastError());
+      if (nq > 0)
+        HIPCHK(c, hipMemcpyAsync(const_cast<double*>(h_x), s->sum_x.p, sizeof(double) * mJ * nq * Pc, hipMemcpyDeviceToHost, st));
+    }
     // results come back in sorted order: scatter to the caller's particle order
     HIPCHK(c, hipMemcpyAsync(const_cast<double*>(h_mean), s->pred_mean.p, sizeof(double) * mJ * Pc, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(const_cast<double*>(h_var), s->pred_var.p, sizeof(double) * mJ * Pc, hipMemcpyDeviceToHost, st));
+    if (!ro) HIPCHK(c, hipMemcpyAsync(const_cast<double*>(h_var), s->pred_var.p, sizeof(double) * mJ * Pc, hipMemcpyDeviceToHost, st));
     }
     HIPCHK(c, hipStreamSynchronize(st));
     for (int q = 0; q < Pc; ++q) {
@@ -454,7 +490,8 @@ int predict_core(agp_ctx* c, int64_t n, const double* ts_pred, int64_t m, int32_
         continue;
       }
       std::memcpy(out_mean + o * m, h_mean + (size_t)q * m, sizeof(double) * m);
-      std::memcpy(out_var + o * m, h_var + (size_t)q * m, sizeof(double) * m);
+      if (!ro) std::memcpy(out_var + o * m, h_var + (size_t)q * m, sizeof(double) * m);
+      if (nq > 0) std::memcpy(sum->out_x + o * m * nq, h_x + (size_t)q * m * nq, sizeof(double) * m * nq);
       if (out_cov)
         HIPCHK(c, hipMemcpyAsync(out_cov + o * m * m, s->pred_cov.as<double>() + (size_t)q * m * m,
                                  sizeof(double) * m * m, hipMemcpyDeviceToHost, st));
@@ -463,17 +500,21 @@ int predict_core(agp_ctx* c, int64_t n, const double* ts_pred, int64_t m, int32_
   }
   {
     // always inspected: a caller that passes out_info = NULL must still never receive unmarked garbage
-    std::vector<int32_t> info_sorted(P);
+    std::vector<int32_t> info_sorted(P), bad_sorted(ro ? P : 0);
     HIPCHK(c, hipStreamSynchronize(st));
     HIPCHK(c, hipMemcpy(info_sorted.data(), s->info.p, sizeof(int32_t) * P, hipMemcpyDeviceToHost));      // (blocking: nothing in flight towards the local on an error return)
+    if (ro) HIPCHK(c, hipMemcpy(bad_sorted.data(), s->out_info.p, sizeof(int32_t) * P, hipMemcpyDeviceToHost));
     for (int q = 0; q < P; ++q) {
       if (info_sorted[q] < 0) return fail(c, AGP_ERR_HIP, "in-kernel panel solve timed out waiting for its diagonal factor");
       const int p = bt.order[q];
+      // (predict_sum: a factor that failed comes first; then the first row of raw marginals that fails)
+      if (ro && info_sorted[q] == 0 && bad_sorted[q] >= 1 && bad_sorted[q] <= m) info_sorted[q] = (int32_t)(n + bad_sorted[q]);
       if (out_info) out_info[p] = info_sorted[q];
       if (info_sorted[q] != 0) {
         const double nanv = std::nan("");
-        for (int64_t g = 0; g < m; ++g) { out_mean[(size_t)p * m + g] = nanv; out_var[(size_t)p * m + g] = nanv; }
+        for (int64_t g = 0; g < m; ++g) { out_mean[(size_t)p * m + g] = nanv; if (out_var) out_var[(size_t)p * m + g] = nanv; }
         if (out_cov) for (int64_t g = 0; g < m * m; ++g) out_cov[(size_t)p * m * m + g] = nanv;
+        if (nq > 0) std::fill(sum->out_x + (size_t)p * m * nq, sum->out_x + (size_t)(p + 1) * m * nq, nanv);
       }
     }
   }
@@ -1005,6 +1046,150 @@ static int infer_gp_sum_body(agp_ctx* c, int64_t n, const double* ts_pred, int64
                     var.data(), out_cov, &info);
   if (out_info) *out_info = info;
   return rc;
+}
+
+// infer_gp_sum for a population (agp_infer_gp_sum_batch) and predict_sum's numbers (agp_predict_sum_batch, sp->readout): particle
+// pp's components are CSR entries [pp M, (pp + 1) M).  Each particle's composite program is the single entry's; identical particles
+// (program, parameters, noise, noise_pred: a resampled population) run once; predict_core runs the batch with codes, the
+// single entry's diagonal terms (noise_pred on the observable rows only, see SumPass) and the pinned schedule.
+static int sum_batch_body(agp_ctx* c, int64_t n, const double* ts_pred, int64_t p, int32_t P, int32_t M, const int32_t* op_off,
+                          const uint8_t* ops, const int32_t* prm_off, const double* prm, const double* noise, const double* noise_pred,
+                          double* out_mean, double* out_var, double* out_cov, int32_t* out_info, SumPass* sp) {
+  if (!c) return fail(nullptr, AGP_ERR_ARG, "null context");
+  if (P < 1) return fail(c, AGP_ERR_ARG, "P must be >= 1");
+  if (M < 1 || M > 200) return fail(c, AGP_ERR_ARG, "M must be in 1..200");
+  if (p < 0 || n < 0) return fail(c, AGP_ERR_ARG, "negative size");
+  if (n > c->n_max) return fail(c, AGP_ERR_NODATA, "n exceeds the data uploaded with agp_set_data");
+  const int64_t nq = (int64_t)sp->z.size();
+  const int64_t ma = (int64_t)(M + 1) * p;
+  const int64_t lim = (int64_t)1 << 31;
+  if ((int64_t)P * ma >= lim || (out_cov && ma > 0 && (int64_t)P * ma >= lim / ma) || (nq > 0 && (int64_t)P * ma >= lim / nq))
+    return fail(c, AGP_ERR_ARG, "an output exceeds 2^31 elements");
+  if (p == 0) return AGP_OK;
+  if (!op_off || !ops || !prm_off || !prm || !noise || !ts_pred || !out_mean || (!sp->readout && !out_var) || (nq > 0 && !sp->out_x))
+    return fail(c, AGP_ERR_ARG, "null pointer argument");
+  HIPCHK(c, hipSetDevice(c->device));
+  // composite programs, per particle: K_1 SEL_1 *  K_2 SEL_2 * +  ...  K_M SEL_M * +   (as agp_infer_gp_sum)
+  std::vector<int32_t> coff((size_t)P + 1, 0), cpoff((size_t)P + 1, 0);
+  std::vector<uint8_t> cops; std::vector<double> cprm;
+  char buf[256];
+  for (int32_t pp = 0; pp < P; ++pp) {
+    const size_t o0 = cops.size();
+    for (int i = 0; i < M; ++i) {
+      const int64_t k = (int64_t)pp * M + i;
+      if (op_off[k] < 0 || prm_off[k] < 0 || op_off[k + 1] < op_off[k] || prm_off[k + 1] < prm_off[k]) {
+        snprintf(buf, sizeof buf, "particle %d: malformed offsets of component %d", (int)pp, i + 1);
+        return fail(c, AGP_ERR_ARG, buf);
+      }
+      for (int q = op_off[k]; q < op_off[k + 1]; ++q) {
+        if (ops[q] > OP_CP) { snprintf(buf, sizeof buf, "particle %d: unknown opcode", (int)pp); return fail(c, AGP_ERR_PROGRAM, buf); }
+        cops.push_back(ops[q]);
+      }
+      cprm.insert(cprm.end(), prm + prm_off[k], prm + prm_off[k + 1]);
+      cops.push_back((uint8_t)OP_SEL); cprm.push_back((double)(i + 1));
+      cops.push_back((uint8_t)OP_TIMES);
+      if (i > 0) cops.push_back((uint8_t)OP_PLUS);
+      if (cops.size() - o0 > (size_t)AGP_MAX_OPS) {
+        snprintf(buf, sizeof buf, "particle %d: composite program longer than AGP_MAX_OPS (%d) nodes", (int)pp, AGP_MAX_OPS);
+        return fail(c, AGP_ERR_PROGRAM, buf);
+      }
+    }
+    coff[(size_t)pp + 1] = (int32_t)cops.size(); cpoff[(size_t)pp + 1] = (int32_t)cprm.size();
+  }
+  // noise_pred NULL: each particle's own noise (src/GP.jl:913)
+  std::vector<double> npv(noise, noise + P);
+  if (noise_pred) npv.assign(noise_pred, noise_pred + P);
+  std::vector<int> rep, uniq;
+  if (c->dedup && P > 1) (void)distinct_particles(P, coff.data(), cops.data(), cpoff.data(), cprm.data(), noise, npv.data(), rep, uniq);
+  const bool packed = !uniq.empty() && (int)uniq.size() < P;
+  if (!packed) { uniq.resize((size_t)P); for (int pp = 0; pp < P; ++pp) uniq[(size_t)pp] = pp; }
+  SubBatch S;
+  pack_particles(uniq, coff.data(), cops.data(), cpoff.data(), cprm.data(), noise, npv.data(), S);
+  const int U = S.size();
+  { std::lock_guard<std::mutex> g(c->mu); c->n_particles_seen += P; c->n_particles_run += U; }      // (agp_get_dedup_stats)
+  // query points: F_1(T*) ... F_M(T*) (codes 1..M), then X(T*) (code 0); JITTER on every row (noise_pred: k_pred_extract)
+  std::vector<double> tq((size_t)ma), dadd((size_t)ma, 1e-8);
+  std::vector<uint8_t> code((size_t)ma);
+  for (int i = 0; i <= M; ++i)
+    for (int64_t j = 0; j < p; ++j) {
+      tq[(size_t)i * p + j] = ts_pred[j];
+      code[(size_t)i * p + j] = (uint8_t)(i < M ? i + 1 : 0);
+    }
+  const bool ff = c->flow != 0;      // (predict_core's schedule for this pass)
+  Batch bt;
+  int rc = compile_batch(c, U, S.op_off.data(), S.ops.data(), S.prm_off.data(), S.prm.data(), bt, /*allow_sel=*/true, false, false, ff, ff);
+  if (rc) {
+    // name the caller's particle: the first distinct particle that does not compile on its own
+    for (int u = 0; u < U; ++u) {
+      Batch b1;
+      const int32_t o1[2] = {0, S.op_off[(size_t)u + 1] - S.op_off[(size_t)u]}, q1[2] = {0, S.prm_off[(size_t)u + 1] - S.prm_off[(size_t)u]};
+      const double zero = 0.0;
+      const double* pp1 = q1[1] > 0 ? S.prm.data() + S.prm_off[(size_t)u] : &zero;
+      if (compile_batch(c, 1, o1, S.ops.data() + S.op_off[(size_t)u], q1, pp1, b1, true) == 0) continue;
+      std::string e;
+      { std::lock_guard<std::mutex> g(c->mu); e = c->err; }
+      if (e.rfind("particle 0: ", 0) == 0) e = e.substr(12);
+      snprintf(buf, sizeof buf, "particle %d: ", uniq[(size_t)u]);
+      return fail(c, AGP_ERR_PROGRAM, buf + e);
+    }
+    return rc;
+  }
+  const size_t ue = (size_t)ma;
+  std::vector<double> umean(packed ? U * ue : 0), uvar(packed && out_var ? U * ue : 0), ucov(packed && out_cov ? U * ue * ue : 0),
+      ux(packed && nq > 0 ? U * ue * (size_t)nq : 0);
+  std::vector<int32_t> uinfo((size_t)U, 0);
+  double* x_caller = sp->out_x;
+  if (packed && nq > 0) sp->out_x = ux.data();
+  rc = predict_core(c, n, tq.data(), ma, U, bt, S.noise.data(), S.noise_pred.data(), code.data(), dadd.data(), nullptr, nullptr,
+                    packed ? umean.data() : out_mean, packed ? (out_var ? uvar.data() : nullptr) : out_var,
+                    packed ? (out_cov ? ucov.data() : nullptr) : out_cov, uinfo.data(), nullptr, nullptr, sp);
+  sp->out_x = x_caller;
+  if (rc) return rc;
+  for (int pp = 0; pp < P; ++pp) {
+    const size_t u = packed ? (size_t)rep[(size_t)pp] : (size_t)pp;
+    if (out_info) out_info[pp] = uinfo[u];
+    if (!packed) continue;
+    std::memcpy(out_mean + (size_t)pp * ue, umean.data() + u * ue, sizeof(double) * ue);
+    if (out_var) std::memcpy(out_var + (size_t)pp * ue, uvar.data() + u * ue, sizeof(double) * ue);
+    if (out_cov) std::memcpy(out_cov + (size_t)pp * ue * ue, ucov.data() + u * ue * ue, sizeof(double) * ue * ue);
+    if (nq > 0) std::memcpy(x_caller + (size_t)pp * ue * nq, ux.data() + u * ue * nq, sizeof(double) * ue * nq);
+  }
+  return AGP_OK;
+}
+
+int agp_infer_gp_sum_batch(agp_ctx* c, int64_t n, const double* ts_pred, int64_t p, int32_t P, int32_t M, const int32_t* op_off,
+                           const uint8_t* ops, const int32_t* prm_off, const double* prm, const double* noise, const double* noise_pred,
+                           double* out_mean, double* out_var, double* out_cov, int32_t* out_info) {
+  SumPass sp;      // (no read-out: the pinned schedule and the observable-rows noise_pred only)
+  sp.p_rows = p;
+  return abi_guard(c, [&] { return sum_batch_body(c, n, ts_pred, p, P, M, op_off, ops, prm_off, prm, noise, noise_pred, out_mean, out_var,
+                                                  out_cov, out_info, &sp); });
+}
+
+static int predict_sum_body(agp_ctx* c, int64_t n, const double* ts_pred, int64_t p, int32_t P, int32_t M, const int32_t* op_off,
+                            const uint8_t* ops, const int32_t* prm_off, const double* prm, const double* noise, const double* noise_pred,
+                            double y_slope, double y_intercept, const double* q, int64_t nq, double* out_mean, double* out_x,
+                            int32_t* out_info) {
+  if (!c) return fail(nullptr, AGP_ERR_ARG, "null context");
+  if (nq < 0) return fail(c, AGP_ERR_ARG, "negative size");
+  if (nq > 0 && !q) return fail(c, AGP_ERR_ARG, "null q");
+  for (int64_t k = 0; k < nq; ++k)
+    if (!(q[k] > 0.0 && q[k] < 1.0)) return fail(c, AGP_ERR_ARG, "quantile must be in (0, 1)");
+  if (!(std::isfinite(y_slope) && y_slope != 0.0 && std::isfinite(y_intercept)))
+    return fail(c, AGP_ERR_ARG, "y_transform must have a finite non-zero slope and a finite intercept");
+  SumPass sp;
+  sp.readout = true; sp.p_rows = p; sp.slope = y_slope; sp.intercept = y_intercept; sp.out_x = out_x;
+  sp.z.resize((size_t)nq);
+  for (int64_t k = 0; k < nq; ++k) sp.z[(size_t)k] = ndtri(q[k]);
+  return sum_batch_body(c, n, ts_pred, p, P, M, op_off, ops, prm_off, prm, noise, noise_pred, out_mean, nullptr, nullptr, out_info, &sp);
+}
+
+int agp_predict_sum_batch(agp_ctx* c, int64_t n, const double* ts_pred, int64_t p, int32_t P, int32_t M, const int32_t* op_off,
+                          const uint8_t* ops, const int32_t* prm_off, const double* prm, const double* noise, const double* noise_pred,
+                          double y_slope, double y_intercept, const double* q, int64_t nq, double* out_mean, double* out_x,
+                          int32_t* out_info) {
+  return abi_guard(c, [&] { return predict_sum_body(c, n, ts_pred, p, P, M, op_off, ops, prm_off, prm, noise, noise_pred, y_slope,
+                                                    y_intercept, q, nq, out_mean, out_x, out_info); });
 }
 
 static int cov_matrix_body(agp_ctx* c, const double* ts, int64_t n, const uint8_t* ops, int32_t n_ops, const double* prm,

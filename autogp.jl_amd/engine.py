@@ -33,7 +33,7 @@ EXPORTED_SYMBOLS = [
     "agp_debug_compact_shards", "agp_logpdf_batch_extend", "agp_extend_stats", "agp_extend_reset", "agp_extend_reserve",
     "agp_predict_reuse_stats", "agp_grad_reuse_stats", "agp_set_factor_cache", "agp_wait", "agp_comm_count", "agp_get_lag_stats", "agp_get_lattice_stats", "agp_get_compact_stats", "agp_set_lattice", "agp_probe_lattice", "agp_set_reference_arithmetic", "agp_shard_plan", "agp_get_coalesce_timing", "agp_set_lag_tables", "agp_set_grad_lag_domain", "agp_get_grad_lag_domain_stats", "agp_get_grad_toeplitz_stats", "agp_get_grad_structured_stats", "agp_get_predict_structured_stats", "agp_get_toeplitz_stats", "agp_set_lag_rank_tables", "agp_get_lag_rank_stats", "agp_get_lag_predict_stats", "agp_get_poison_stats",
     "agp_logpdf_grad_batch_multi", "agp_predict_batch_multi", "agp_extend_stats2", "agp_predict_logpdf_batch",
-    "agp_mixture_quantile", "agp_predict_quantile_batch",
+    "agp_mixture_quantile", "agp_predict_quantile_batch", "agp_infer_gp_sum_batch", "agp_predict_sum_batch",
 ]
 COMM_ID_BYTES = 128
 
@@ -115,6 +115,11 @@ def load_library(path=None):
     lib.agp_predict_quantile_batch.restype = C.c_int
     lib.agp_infer_gp_sum.argtypes = [vp, C.c_int64, dp, C.c_int64, C.c_int32, ip, u8p, ip, dp, C.c_double, C.c_double, dp, dp, ip]
     lib.agp_infer_gp_sum.restype = C.c_int
+    lib.agp_infer_gp_sum_batch.argtypes = [vp, C.c_int64, dp, C.c_int64, C.c_int32, C.c_int32, ip, u8p, ip, dp, dp, dp, dp, dp, dp, ip]
+    lib.agp_infer_gp_sum_batch.restype = C.c_int
+    lib.agp_predict_sum_batch.argtypes = [vp, C.c_int64, dp, C.c_int64, C.c_int32, C.c_int32, ip, u8p, ip, dp, dp, dp, C.c_double,
+                                          C.c_double, dp, C.c_int64, dp, dp, ip]
+    lib.agp_predict_sum_batch.restype = C.c_int
     lib.agp_cov_matrix.argtypes = [vp, dp, C.c_int64, u8p, C.c_int32, dp, C.c_int32, C.c_double, dp]
     lib.agp_cov_matrix.restype = C.c_int
     lib.agp_debug_cholesky.argtypes = [vp, dp, C.c_int64, dp, ip]; lib.agp_debug_cholesky.restype = C.c_int
@@ -594,6 +599,53 @@ class GPEngine:
             raise PosDefException(info.value)
         return mean, cov, [slice(i * p, (i + 1) * p) for i in range(M)], slice(M * p, ma)
 
+    def _sum_batch_args(self, split_nodes, noises, ts_pred, n, noise_pred):
+        """CSR programs of P particles x M components (split_nodes: P lists of M nodes), noises, ts_pred, noise_pred per particle."""
+        split_nodes = [list(c) for c in split_nodes]
+        P = len(split_nodes)
+        M = len(split_nodes[0]) if P else 0
+        if any(len(c) != M for c in split_nodes):
+            raise ValueError("every particle must have the same number of components")
+        op_off, ops, prm_off, prm = _gp.encode_batch([nd for c in split_nodes for nd in c])
+        noises = _f64(noises)
+        if noises.shape != (P,):
+            raise ValueError(f"noises has shape {noises.shape}, expected ({P},)")
+        npred = None if noise_pred is None else _f64(np.broadcast_to(noise_pred, (P,)))
+        n = self.n_max if n is None else int(n)
+        return n, P, M, op_off, ops, prm_off, prm, noises, _f64(ts_pred), npred
+
+    def infer_gp_sum_batch(self, split_nodes, noises, ts_pred, n=None, noise_pred=None, want_cov=False, check=True):
+        """GP.infer_gp_sum per particle (src/GP.jl:904-993) in one call: split_nodes holds each particle's M component kernels (e.g.
+        split_kernel_sop of its kernel), noises its noise; noise_pred None = each particle's own noise.  Returns (mean (P, (M+1)p),
+        var (P, (M+1)p), cov (P, (M+1)p, (M+1)p) or None, info (P,), indexes_F (list of slices), indexes_X (slice))."""
+        n, P, M, op_off, ops, prm_off, prm, noises, ts_pred, npred = self._sum_batch_args(split_nodes, noises, ts_pred, n, noise_pred)
+        p = ts_pred.shape[0]; ma = (M + 1) * p
+        mean = np.empty((P, ma)); var = np.empty((P, ma)); cov = np.empty((P, ma, ma)) if want_cov else None
+        info = np.zeros(P, dtype=np.int32)
+        self._check(self._lib.agp_infer_gp_sum_batch(self._ctx, n, _dp(ts_pred), p, P, M, _ip(op_off), _u8(ops), _ip(prm_off), _dp(prm),
+                                                     _dp(noises), _dp(npred), _dp(mean), _dp(var), _dp(cov), _ip(info)))
+        if check and (info > 0).any():
+            q = int(np.argmax(info > 0))
+            raise PosDefException(int(info[q]), q)
+        return mean, var, cov, info, [slice(i * p, (i + 1) * p) for i in range(M)], slice(M * p, ma)
+
+    def predict_sum_batch(self, split_nodes, noises, ts_pred, q=(), n=None, noise_pred=None, y_transform=(1.0, 0.0), check=True):
+        """predict_sum's numbers (src/api.jl:898-1034) per particle: raw means of the rows (F_1 .. F_M, X) with predict_mvn_sum's
+        intercept correction on F_1, and their marginal quantiles, computed on the device.  y_transform = (slope, intercept).
+        Returns (mean (P, (M+1)p), x (P, (M+1)p, nq), info (P,)); info = n + j: joint row j (1-based) has no raw marginal."""
+        n, P, M, op_off, ops, prm_off, prm, noises, ts_pred, npred = self._sum_batch_args(split_nodes, noises, ts_pred, n, noise_pred)
+        p = ts_pred.shape[0]; ma = (M + 1) * p
+        qa = _f64(np.atleast_1d(np.asarray(q, dtype=np.float64))); nq = qa.shape[0]
+        slope, intercept = (float(v) for v in y_transform)
+        mean = np.empty((P, ma)); x = np.empty((P, ma, nq)); info = np.zeros(P, dtype=np.int32)
+        self._check(self._lib.agp_predict_sum_batch(self._ctx, n, _dp(ts_pred), p, P, M, _ip(op_off), _u8(ops), _ip(prm_off), _dp(prm),
+                                                    _dp(noises), _dp(npred), slope, intercept, _dp(qa) if nq else None, nq, _dp(mean),
+                                                    _dp(x) if nq else None, _ip(info)))
+        if check and (info > 0).any():
+            k = int(np.argmax(info > 0))
+            raise PosDefException(int(info[k]), k)
+        return mean, x, info
+
     # -- matrix assembly (src/GP.jl:666-668) -------------------------------------------------
     def cov_matrix(self, node, noise, ts):
         ts = _f64(ts); n = ts.shape[0]
@@ -923,6 +975,15 @@ class MvNormal:
         self.mu, self.var, self.Sigma = mu[0], var[0], cov[0]
         self._score = (eng, node, float(noise), ts, xs, ts_pred, noise_pred, mt, mp_)
 
+    @classmethod
+    def from_moments(cls, mu, Sigma):
+        """An MvNormal(mu, Sigma) of given moments (predict_mvn_sum's components); it has no logpdf route."""
+        d = cls.__new__(cls)
+        d.mu = np.asarray(mu, dtype=np.float64); d.Sigma = np.asarray(Sigma, dtype=np.float64)
+        d.var = np.diagonal(d.Sigma).copy()
+        d._score = None
+        return d
+
     def mean(self):
         return self.mu
 
@@ -932,6 +993,8 @@ class MvNormal:
     def logpdf(self, y):
         """Distributions.logpdf(d, y) (src/api.jl:693), on the GPU from the joint factorisation (agp_predict_logpdf_batch).
         Raises PosDefException like the reference."""
+        if self._score is None:
+            raise NotImplementedError("logpdf of an MvNormal built from its moments")
         eng, node, noise, ts, xs, ts_pred, noise_pred, mt, mp_ = self._score
         eng.set_data(ts, xs)
         lp, _ = eng.predict_logpdf_batch([node], [noise], ts_pred, y, noise_pred=noise_pred, mean_train=mt, mean_pred=mp_)
@@ -975,6 +1038,54 @@ def infer_gp_sum(nodes, noise, ts, xs, ts_pred, noise_pred=None, engine=None):
     eng.set_data(ts, xs)
     mean, cov, iF, iX = eng.infer_gp_sum(nodes, noise, ts_pred, noise_pred=noise_pred)
     return mean, cov, {"F": iF, "X": iX}
+
+
+def predict_mvn_sum(engine, nodes, noises, log_weights, ts_pred, LeafType, y_transform=(1.0, 0.0), noise_pred=None):
+    """AutoGP.predict_mvn_sum(model, ds, T; noise_pred) (src/api.jl:978-1034) on the engine's resident (scaled) series: each particle's
+    kernel split by split_kernel_sop(node, LeafType), infer_gp_sum of the two parts (one batched call), mapped to the RAW space of
+    y_transform = (slope, intercept) with the intercept counted once (on F_1).  Returns (components, weights, indexes): one
+    MvNormal per particle, the normalised particle weights, and {"Y": slice, "F": [slice, slice]}."""
+    from .dist import normalize_weights
+    slope, intercept = (float(v) for v in y_transform)
+    split = [_gp.split_kernel_sop(nd, LeafType) for nd in nodes]
+    npred = None if noise_pred is None else float(noise_pred)
+    mean, _, cov, _, iF, iX = engine.infer_gp_sum_batch(split, noises, ts_pred, noise_pred=npred, want_cov=True)
+    comps = []
+    for mu, S in zip(mean, cov):
+        mr = (mu - intercept) / slope
+        mr[iF[0]] += intercept / slope
+        comps.append(MvNormal.from_moments(mr, (1.0 / (slope * slope)) * S))
+    w = np.exp(normalize_weights(log_weights)[1])
+    return comps, w, {"Y": iX, "F": iF}
+
+
+def predict_sum(engine, nodes, noises, log_weights, ts_pred, LeafType, y_transform=(1.0, 0.0), noise_pred=None, quantiles=(),
+                ds=None):
+    """AutoGP.predict_sum(model, ds, T; quantiles, noise_pred) (src/api.jl:898-936): the columns ds, y_mean, component, particle,
+    weight, y_<q> of the reference's DataFrame (a dict of arrays), in its row order — per particle, component 0 (the observable),
+    then 1 (the addends with a LeafType factor), then 2 (the others).  Means and quantiles come from the device read-out
+    (GPEngine.predict_sum_batch).  `ds` labels the rows (default: ts_pred)."""
+    from .dist import normalize_weights
+    split = [_gp.split_kernel_sop(nd, LeafType) for nd in nodes]
+    npred = None if noise_pred is None else float(noise_pred)
+    qs = [float(v) for v in quantiles]
+    ts_pred = _f64(ts_pred); p = ts_pred.shape[0]
+    mean, x, _ = engine.predict_sum_batch(split, noises, ts_pred, q=qs, noise_pred=npred, y_transform=y_transform)
+    P = len(nodes)
+    w = np.exp(normalize_weights(log_weights)[1])
+    blocks = [slice(2 * p, 3 * p), slice(0, p), slice(p, 2 * p)]         # Y, F_1, F_2
+    rows = [(k, c, blk) for k in range(P) for c, blk in enumerate(blocks)]
+    labels = ts_pred if ds is None else np.asarray(ds)
+    out = {
+        "ds": np.concatenate([labels for _ in rows]) if rows else labels[:0],
+        "y_mean": np.concatenate([mean[k, blk] for k, _, blk in rows]) if rows else np.zeros(0),
+        "component": np.repeat([c for _, c, _ in rows], p).astype(np.int64),
+        "particle": np.repeat([k + 1 for k, _, _ in rows], p).astype(np.int64),
+        "weight": np.repeat([w[k] for k, _, _ in rows], p),
+    }
+    for j, qv in enumerate(qs):
+        out[f"y_{qv!r}"] = np.concatenate([x[k, blk, j] for k, _, blk in rows]) if rows else np.zeros(0)
+    return out
 
 
 def quantile(dist: MvNormal, p):

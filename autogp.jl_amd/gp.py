@@ -237,3 +237,67 @@ def from_tuple(t) -> Node:
     if tag == "*": return Times(from_tuple(t[1]), from_tuple(t[2]))
     if tag == "CP": return ChangePoint(from_tuple(t[1]), from_tuple(t[2]), t[3], t[4])
     raise ValueError(tag)
+
+
+# -- sum-of-products decomposition (src/GP.jl:520-660) ------------------------------------------------------------------
+# The tree shapes below are the reference's, term for term: they decide the postfix program of every split component and so
+# the device arithmetic of infer_gp_sum / predict_sum.
+
+def _extract_operand(node: BinaryOpNode) -> Node:
+    """The dummy that replaces a removed operand: Constant(1) inside Times, Constant(0) inside Plus and ChangePoint."""
+    return Constant(1) if isinstance(node, Times) else Constant(0)
+
+
+def _extract_helper(node: Node, leaf_type, retain: bool):
+    if isinstance(node, LeafNode):
+        return (node if retain else None) if isinstance(node, leaf_type) else (None if retain else node)
+    left = _extract_helper(node.left, leaf_type, retain)
+    right = _extract_helper(node.right, leaf_type, retain)
+    left = _extract_operand(node) if left is None else left
+    right = _extract_operand(node) if right is None else right
+    return type(node)(left, right, *node.params())
+
+
+def extract_kernel(node: Node, leaf_type, retain: bool = True) -> Node:
+    """GP.extract_kernel(node, T; retain) (src/GP.jl:520-561): keep only the leaves of type `leaf_type` (retain=False: remove
+    them), each removed leaf replaced by Constant(1) under Times and Constant(0) under Plus / ChangePoint; Constant(0) if no
+    leaf is kept."""
+    k = _extract_helper(node, leaf_type, retain)
+    return Constant(0) if k is None else k
+
+
+def _merge_split_operand(node: Node, a, b):
+    """merge_split_operand (src/GP.jl:640-655): Plus -> a + b (or the one present); ChangePoint -> ChangePoint(a, b, ...) with
+    Constant(0) for a missing side; None when both are missing."""
+    if a is None and b is None:
+        return None
+    if isinstance(node, ChangePoint):
+        return ChangePoint(Constant(0) if a is None else a, Constant(0) if b is None else b, node.location, node.scale)
+    if a is None:
+        return b
+    if b is None:
+        return a
+    return Plus(a, b)
+
+
+def _split_helper(node: Node, leaf_type):
+    if isinstance(node, LeafNode):
+        return (node, None) if isinstance(node, leaf_type) else (None, node)
+    la, lb = _split_helper(node.left, leaf_type)
+    ra, rb = _split_helper(node.right, leaf_type)
+    if isinstance(node, Times):
+        def mult(a, b):
+            return None if a is None or b is None else Times(a, b)
+        plus = Plus(node.left, node.right)
+        l_sop = _merge_split_operand(plus, mult(la, ra), mult(la, rb))
+        l_sop = _merge_split_operand(plus, l_sop, mult(lb, ra))
+        return l_sop, mult(lb, rb)
+    return _merge_split_operand(node, la, ra), _merge_split_operand(node, lb, rb)
+
+
+def split_kernel_sop(node: Node, leaf_type):
+    """GP.split_kernel_sop(node, T) (src/GP.jl:563-638): (k_T, k_nT), the addends of the sum-of-products expansion of `node` that
+    hold a leaf of type `leaf_type` and those that do not, Constant(0) for an empty side.  A product expands as
+    ((a a' + a b') + b a', b b') for operands split into (a, b) and (a', b')."""
+    a, b = _split_helper(node, leaf_type)
+    return (Constant(0) if a is None else a, Constant(0) if b is None else b)

@@ -45,10 +45,10 @@ end
 
 destroy!(e::Engine) = (e.ptr != C_NULL && ccall((:agp_destroy, LIB), Cvoid, (Ptr{Cvoid},), e.ptr); e.ptr = C_NULL; nothing)
 
-"One engine per GPU."
 "the level the library starts from: AGP_LAG (0 .. 3), 1 when unset"
 default_lag_level() = Int32(clamp(something(tryparse(Int, get(ENV, "AGP_LAG", "1")), 1), 0, 3))
 
+"One engine per GPU."
 function Engine(device::Integer=0)
     ref = Ref{Ptr{Cvoid}}(C_NULL)
     rc = ccall((:agp_init, LIB), Cint, (Ref{Ptr{Cvoid}}, Cint), ref, device)
@@ -174,8 +174,6 @@ function logpdf_batch(eng::Engine, nodes::Vector{<:GP.Node}, noises::Vector{Floa
     return out, info
 end
 
-"(particles a predictive call served from a resident factor, particles whose K11 it factored itself): after
-`logpdf_batch(...; extend=true)` on a prefix, `predict_marginal` / `predict_mvn` on the same prefix reuse L11 and alpha."
 "(extended, from_scratch, tile_rows_reused, tile_rows_total, evicted_before_reuse, slots, callers, occupied, capacity_tile_rows, growth_copies) of the factor store"
 function extend_stats(eng::Engine)
     out = zeros(Int64, 10)
@@ -185,6 +183,8 @@ function extend_stats(eng::Engine)
             capacity_tile_rows = out[9], growth_copies = out[10])
 end
 
+"(particles a predictive call served from a resident factor, particles whose K11 it factored itself): after
+`logpdf_batch(...; extend=true)` on a prefix, `predict_marginal` / `predict_mvn` on the same prefix reuse L11 and alpha."
 function predict_reuse_stats(eng::Engine)
     out = Vector{Int64}(undef, 2)
     GC.@preserve out check(eng, ccall((:agp_predict_reuse_stats, LIB), Cint, (Ptr{Cvoid}, Ptr{Int64}), eng.ptr, out))
@@ -457,6 +457,63 @@ function infer_gp_sum(eng::Engine, nodes::Vector{<:GP.Node}, noise::Float64, ts_
     info[] > 0 && throw(LinearAlgebra.PosDefException(info[]))
     mvn = Distributions.MvNormal(mu, LinearAlgebra.Symmetric(cov))
     return (mvn=mvn, indexes=(F=[((i-1)*p+1):(i*p) for i in 1:M], X=(M*p+1):(M*p+p)))
+end
+
+"CSR programs of P particles x M components (`splits[k]`: the component kernels of particle k, e.g. `GP.split_kernel_sop(node, T)`)."
+function encode_splits(splits::AbstractVector)
+    P = length(splits); M = P == 0 ? 0 : length(splits[1])
+    all(s -> length(s) == M, splits) || error("every particle must have the same number of components")
+    nodes = GP.Node[nd for s in splits for nd in s]
+    return (P, M, encode_batch(nodes)...)
+end
+
+"""
+`GP.infer_gp_sum` for every particle of a population in one call (`AutoGP.predict_mvn_sum`, src/api.jl:978-1034, calls it once per
+particle): `splits[k]` holds particle k's component kernels, made with AutoGP's own `GP.split_kernel_sop`.  `noise_pred` nothing =
+each particle's own noise.  Returns (mean, var, cov, info, indexes): mean / var of size ((M+1)p, P), cov of size ((M+1)p, (M+1)p,
+P) when `want_cov`, else nothing; throws `PosDefException` where a particle's training block is not positive definite.
+"""
+function infer_gp_sum_batch(eng::Engine, splits::AbstractVector, noises::Vector{Float64}, ts_pred::Vector{Float64};
+        n::Integer=eng.n_max, noise_pred::Union{Nothing,Float64}=nothing, want_cov::Bool=false)
+    P, M, op_off, ops, prm_off, prm = encode_splits(splits)
+    p = length(ts_pred); ma = (M + 1) * p
+    mu = Matrix{Float64}(undef, ma, P); var = Matrix{Float64}(undef, ma, P); info = zeros(Int32, P)
+    cov = want_cov ? Array{Float64}(undef, ma, ma, P) : Float64[]
+    npv = isnothing(noise_pred) ? Float64[] : fill(noise_pred, P)
+    GC.@preserve op_off ops prm_off prm ts_pred noises npv mu var cov info check(eng, ccall((:agp_infer_gp_sum_batch, LIB), Cint,
+        (Ptr{Cvoid}, Int64, Ptr{Float64}, Int64, Int32, Int32, Ptr{Int32}, Ptr{UInt8}, Ptr{Int32}, Ptr{Float64},
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
+        eng.ptr, n, ts_pred, p, P, M, op_off, ops, prm_off, prm, noises,
+        isempty(npv) ? Ptr{Float64}(C_NULL) : pointer(npv), mu, var, want_cov ? pointer(cov) : Ptr{Float64}(C_NULL), info))
+    k = findfirst(!=(0), info)
+    isnothing(k) || throw(LinearAlgebra.PosDefException(info[k]))
+    return (mean=mu, var=var, cov=want_cov ? cov : nothing, info=info,
+            indexes=(F=[((i-1)*p+1):(i*p) for i in 1:M], X=(M*p+1):(M*p+p)))
+end
+
+"""
+The numbers of `AutoGP.predict_sum(model, ds, T; quantiles, noise_pred)` (src/api.jl:898-936) on the (scaled) resident series:
+per particle the raw-space means of the rows (F_1 .. F_M, X) of the linear `y_transform` (slope, intercept), with
+`predict_mvn_sum`'s intercept correction on F_1, and their marginal quantiles, all formed on the device.  Returns (mean, x, info):
+mean of size ((M+1)p, P), x of size (length(quantiles), (M+1)p, P); throws `PosDefException` where a particle has no predictive.
+"""
+function predict_sum_batch(eng::Engine, splits::AbstractVector, noises::Vector{Float64}, ts_pred::Vector{Float64};
+        quantiles::Vector{Float64}=Float64[], n::Integer=eng.n_max, noise_pred::Union{Nothing,Float64}=nothing,
+        y_slope::Float64=1.0, y_intercept::Float64=0.0)
+    all(q -> 0 < q < 1, quantiles) || error("Quantile must be in (0,1).")
+    P, M, op_off, ops, prm_off, prm = encode_splits(splits)
+    p = length(ts_pred); ma = (M + 1) * p; nq = length(quantiles)
+    mu = Matrix{Float64}(undef, ma, P); x = Array{Float64}(undef, nq, ma, P); info = zeros(Int32, P)
+    npv = isnothing(noise_pred) ? Float64[] : fill(noise_pred, P)
+    GC.@preserve op_off ops prm_off prm ts_pred noises npv quantiles mu x info check(eng, ccall((:agp_predict_sum_batch, LIB), Cint,
+        (Ptr{Cvoid}, Int64, Ptr{Float64}, Int64, Int32, Int32, Ptr{Int32}, Ptr{UInt8}, Ptr{Int32}, Ptr{Float64},
+         Ptr{Float64}, Ptr{Float64}, Float64, Float64, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
+        eng.ptr, n, ts_pred, p, P, M, op_off, ops, prm_off, prm, noises,
+        isempty(npv) ? Ptr{Float64}(C_NULL) : pointer(npv), y_slope, y_intercept,
+        nq == 0 ? Ptr{Float64}(C_NULL) : pointer(quantiles), nq, mu, nq == 0 ? Ptr{Float64}(C_NULL) : pointer(x), info))
+    k = findfirst(!=(0), info)
+    isnothing(k) || throw(LinearAlgebra.PosDefException(info[k]))
+    return mu, x, info
 end
 
 # ------------------------------------------------------------------------------------------------------------------

@@ -436,6 +436,37 @@ int agp_infer_gp_sum(agp_ctx* ctx, int64_t n, const double* ts_pred, int64_t p, 
                      const int32_t* op_off, const uint8_t* ops, const int32_t* prm_off, const double* prm,
                      double noise, double noise_pred, double* out_mean, double* out_cov, int32_t* out_info);
 
+/* infer_gp_sum for every particle of a population (src/api.jl:978-1034 calls GP.infer_gp_sum once per particle on the
+ * split_kernel_sop of its kernel): particle p's components are CSR entries [p*M, (p+1)*M) (op_off / prm_off have P*M+1 entries), M
+ * common to all particles.  Outputs in the reference's index order (F_1 .. F_M, X), per particle: out_mean and out_var P*(M+1)*p,
+ * out_cov P*((M+1)p)^2 column-major or NULL (the marginal pass).  noise_pred NULL = each particle's own noise (the reference's
+ * default).  Per particle the numbers are agp_infer_gp_sum's — noise[p] on the training diagonal, JITTER 1e-8 on every query row,
+ * noise_pred[p] on the observable (X) rows only — with the dataflow schedule whatever the batch (the per-column one with AGP_FLOW=0):
+ * a particle's bits do not depend on the batch size, order, copies or workspace chunking.  Identical particles (composite program,
+ * parameters, noise, noise_pred) run once and share the first copy's bits.  n == 0 is the prior.  out_info[p] (may be NULL): 0, or
+ * 1..n: the training block is not positive definite; a particle with info != 0 gets NaN in its own outputs only.  p == 0 writes
+ * nothing.  Errors (negative return; the message names the particle where there is one): P < 1, M outside 1..200, p < 0,
+ * n > n_max, malformed offsets, an unknown opcode, a composite program over AGP_MAX_OPS nodes (split trees can grow: (l+p)*(l+p)
+ * expands), a NULL input, an output of 2^31 elements or more. */
+int agp_infer_gp_sum_batch(agp_ctx* ctx, int64_t n, const double* ts_pred, int64_t p, int32_t P, int32_t M,
+                           const int32_t* op_off, const uint8_t* ops, const int32_t* prm_off, const double* prm,
+                           const double* noise, const double* noise_pred,
+                           double* out_mean, double* out_var, double* out_cov, int32_t* out_info);
+
+/* predict_sum's numbers (src/api.jl:898-936 on top of predict_mvn_sum, 978-1034): the marginal pass of agp_infer_gp_sum_batch (no
+ * covariance), then on the device predict_mvn_sum's raw-space transform of a linear y_transform, mu_raw = (mu - b)/a with + b/a on
+ * the F_1 rows (the intercept counted once) and var_raw = (1/a^2) var (a = y_slope, b = y_intercept), then
+ * quantile(Normal(mu_raw, sqrt(var_raw)), q[k]) per row (src/GP.jl:1006-1012) = fma(sqrt(var_raw), ndtri(q[k]), mu_raw), ndtri by
+ * AS 241 (csrc/agp_ndtri.hpp: parity with the reference's erfcinv to rounding).  out_mean P*(M+1)*p raw means; out_x
+ * P*(M+1)*p*nq, row-major per particle ((row, k) at row*nq + k); nq == 0: out_x is not written and may be NULL.  out_info[p]: as
+ * agp_infer_gp_sum_batch, or n + j: joint row j (1-based) has a raw variance that is negative or NaN or a raw mean that is not
+ * finite (the particle's outputs are NaN).  Errors: agp_infer_gp_sum_batch's, a q outside (0, 1) or NaN, y_slope not finite or
+ * zero, y_intercept not finite. */
+int agp_predict_sum_batch(agp_ctx* ctx, int64_t n, const double* ts_pred, int64_t p, int32_t P, int32_t M,
+                          const int32_t* op_off, const uint8_t* ops, const int32_t* prm_off, const double* prm,
+                          const double* noise, const double* noise_pred, double y_slope, double y_intercept,
+                          const double* q, int64_t nq, double* out_mean, double* out_x, int32_t* out_info);
+
 /* compute_cov_matrix_vectorized(node, noise, ts) (src/GP.jl:666-668) on explicit ts:
  * out_K is n x n column-major (full symmetric).  Parity / debugging entry. */
 int agp_cov_matrix(agp_ctx* ctx, const double* ts, int64_t n,
