@@ -181,6 +181,30 @@ struct SumReadArgs {
   int32_t* bad;            // [P] smallest failing row + 1, or untouched
 };
 
+// posterior predictive samples (agp_sample_kernel.hpp).  Column j of Z / entry j of col is the j-th sample of the call in chunk order.
+constexpr int SMP_G = 32;      // samples per workgroup of k_pred_sample
+struct SampleNormArgs {
+  double* Z;               // [m_pad][ldz] (row i, column j), 0 in padding rows and columns
+  int m, m_pad, ldz, S;    // S live columns
+  const int32_t* col;      // [S] sample index s of column j
+  uint64_t seed;
+  const double* zin;       // [S][m] the caller's normals z[s * m + i], or null: Philox4x64-10 + ndtri
+};
+struct SampleReadArgs {
+  const double* A;         // the chunk's factors (packed lower tiles), particle q of the chunk at A + q strideA
+  long long strideA;
+  const double* vec;       // a = L11^-1 (x - mu1) in rows [0, n1_pad) of particle q's vector at vec + q ldv
+  int ldv;
+  const double* mu2;       // [m] or null
+  const double* Z;         // SampleNormArgs::Z
+  int ldz;
+  const int32_t* col;      // [S] output column of column j
+  const int32_t* grp;      // [groups][4]: {particle of the chunk, first column j0, columns (<= SMP_G), 0}
+  int nt1, m;
+  double zsign, slope, intercept;      // zsign = sign(slope)
+  double* out;             // [S][m]
+};
+
 struct GradArgs {
   const double* A;       // packed lower tiles of L
   double* Z;             // packed buffer holding Z(r,k), r <= k, in the slot of lower tile (k,r)

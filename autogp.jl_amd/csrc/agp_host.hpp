@@ -172,16 +172,16 @@ struct Slot {
       noise{Fill::values}, noise_pred{Fill::values}, mu1{Fill::values}, mu2{Fill::values}, pred_mean{Fill::values},
       pred_var{Fill::values}, pred_cov{Fill::values}, dense{Fill::values}, diag_add{Fill::values}, Z{Fill::values},
       alpha{Fill::values}, tsol{Fill::values}, gpart{Fill::values}, dgrad{Fill::values}, dgnoise{Fill::values}, lagtab{Fill::values},
-      sum_x{Fill::values}, sum_z{Fill::values};
+      sum_x{Fill::values}, sum_z{Fill::values}, smp_z{Fill::values}, smp_x{Fill::values}, smp_zin{Fill::values};
   // addresses, indices, counts, programs (their parameters included: uploaded whole), times, flags
   DevBuf info{Fill::never}, out_info{Fill::never}, hdr{Fill::never}, ops{Fill::never}, prm{Fill::never}, tt{Fill::never}, map{Fill::never},
       ready{Fill::never}, code{Fill::never}, tretry{Fill::never}, ghdr{Fill::never}, gops{Fill::never}, glc{Fill::never},
       grc{Fill::never}, gpoff{Fill::never}, gprm{Fill::never}, gmap{Fill::never}, goff{Fill::never}, plist{Fill::never},
-      tflag{Fill::never}, flowq{Fill::never}, pl_rank{Fill::never}, pl_tl{Fill::never}, pl_prog{Fill::never};
+      tflag{Fill::never}, flowq{Fill::never}, pl_rank{Fill::never}, pl_tl{Fill::never}, pl_prog{Fill::never}, smp_idx{Fill::never};
   template <class F> void for_each_dev(F&& f) {
     for (DevBuf* b : {&stage, &up_blob, &up_blob2, &A, &W, &vec, &partial, &out_lp, &out_info, &noise, &noise_pred, &mu1, &mu2,
                       &pred_mean, &pred_var, &pred_cov, &dense, &diag_add, &Z, &alpha, &tsol, &gpart, &dgrad, &dgnoise, &lagtab, &sum_x, &sum_z,
-                      &info, &hdr, &ops, &prm, &tt, &map, &ready, &code, &tretry, &ghdr, &gops, &glc, &grc, &gpoff, &gprm, &gmap,
+                      &smp_z, &smp_x, &smp_zin, &smp_idx, &info, &hdr, &ops, &prm, &tt, &map, &ready, &code, &tretry, &ghdr, &gops, &glc, &grc, &gpoff, &gprm, &gmap,
                       &goff, &plist, &tflag, &flowq, &pl_rank, &pl_tl, &pl_prog})
       f(*b);
   }
@@ -674,6 +674,31 @@ std::string particle_key(const uint8_t* ops, int no, const double* prm, int np, 
 // keys (optional) = uniq's keys.  False, with everything empty, on offsets that are negative or decreasing: the caller decides.
 bool distinct_particles(int P, const int32_t* op_off, const uint8_t* ops, const int32_t* prm_off, const double* prm, const double* noise,
                         const double* noise_pred, std::vector<int>& rep, std::vector<int>& uniq, std::vector<std::string>* keys = nullptr);
+
+// The joint predictive factorisation of agp_predict_logpdf_batch (agp_predict.hip), shared with agp_predict_sample_batch
+// (agp_sample.hip): argument-checked inputs -> dedup, compile, the joint matrix [K11 + noise I, K12; K21, K22 + noise_pred I] factored
+// through every block column with [x - mu1; y_pred - mu2] (y_pred null: [x - mu1; 0]) in the forward solve, chunk by chunk of
+// distinct particles.  out_logpdf / out_info: per caller particle (info n + k: leading minor k of the predictive covariance).
+// The hooks (all optional) see the pass from inside; none of them changes the log-density's arithmetic:
+//   plan(U, rep, order)        after compilation: U distinct particles, rep[p] = caller p's distinct index (empty: identity),
+//                              order[q] = distinct index at sorted position q (chunks are runs of sorted positions)
+//   stage(s, up, chunk)        extra uploads onto the pass's own, chunk = distinct particles per chunk
+//   chunk(s, st, ca, p0, Pc)   sorted positions [p0, p0 + Pc) are factored in ca.A (particle p0 + i at ca.A + i strideA, a = L11^-1 (x -
+//                              mu1) in ca.vec); work launched on st runs before the next chunk overwrites A
+//   done(s)                    the stream has drained; the slot is still the pass's (copy results out of its buffers here)
+struct JointHooks {
+  std::function<int(int, const std::vector<int>&, const std::vector<int32_t>&)> plan;
+  std::function<int(Slot*, PinnedUploads&, int)> stage;
+  std::function<int(Slot*, hipStream_t, const CholArgs&, int, int)> chunk;
+  std::function<int(Slot*)> done;
+};
+int predict_joint_batch(agp_ctx* c, int64_t n, const double* ts_pred, const double* y_pred, int64_t m, int32_t P,
+                        const int32_t* op_off, const uint8_t* ops, const int32_t* prm_off, const double* prm,
+                        const double* noise, const double* noise_pred, const double* mean_train, const double* mean_pred,
+                        double* out_logpdf, int32_t* out_info, JointHooks* hooks);
+
+// the mixture weights of agp_predict_quantile_batch / agp_predict_sample_batch (agp_quantile.hip): finite, >= 0, summing to 1
+int check_weights(agp_ctx* c, int32_t P, const double* w);
 
 hipError_t run_factor_extend(hipStream_t st, CholArgs ca, int dcov, bool split_diag, int i0min, int nfac = -1);
 int extend_impl(agp_ctx* c, int64_t n, int32_t P, const int32_t* op_off, const uint8_t* ops, const int32_t* prm_off,

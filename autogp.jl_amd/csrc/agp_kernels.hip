@@ -6,6 +6,7 @@
 #include "agp_toep_kernel.hpp"
 #include "agp_quantile_kernel.hpp"
 #include "agp_sum_kernel.hpp"
+#include "agp_sample_kernel.hpp"
 #include "agp_comm.hpp"
 
 namespace agp {
@@ -171,6 +172,13 @@ void launch_mixture_quantile(hipStream_t st, const double* cm, const double* cs,
 }
 void launch_sum_readout(hipStream_t st, int P, const SumReadArgs& a) {
   hipLaunchKernelGGL(k_sum_readout, dim3((unsigned)((a.m + 255) / 256), P), dim3(256), 0, st, a);
+}
+void launch_philox_normals(hipStream_t st, const SampleNormArgs& a) {
+  const unsigned gy = (unsigned)(a.m_pad / 4 < 4096 ? a.m_pad / 4 : 4096);
+  hipLaunchKernelGGL(k_philox_normals, dim3((unsigned)((a.ldz + 255) / 256), gy), dim3(256), 0, st, a);
+}
+void launch_pred_sample(hipStream_t st, int n_groups, int nt2, const SampleReadArgs& a) {
+  hipLaunchKernelGGL(k_pred_sample, dim3((unsigned)n_groups, (unsigned)nt2), dim3(256), 0, st, a);
 }
 void launch_mfma_peak(int nblk, double* out, long long* cycles, int iters, int mode) {
   hipLaunchKernelGGL(k_mfma_peak, dim3(nblk), dim3(256), 0, 0, out, cycles, iters, mode);

@@ -51,6 +51,10 @@ void launch_mixture_quantile(hipStream_t st, const double* cm, const double* cs,
                              int nq, double tol, long long max_iter, double* out_x, int32_t* out_conv, int32_t* out_iters);
 // predict_sum's read-out (agp_predict.hip): raw transform, F_1 intercept, marginal quantiles on a chunk's device marginals
 void launch_sum_readout(hipStream_t st, int P, const SumReadArgs& a);
+// posterior predictive samples (agp_sample.hip): the normals of every sample column, then per chunk one workgroup per (group of
+// SMP_G samples of one particle, query tile row)
+void launch_philox_normals(hipStream_t st, const SampleNormArgs& a);
+void launch_pred_sample(hipStream_t st, int n_groups, int nt2, const SampleReadArgs& a);
 
 // ---- agp_kernels_grad.hip --------------------------------------------------------------------------------------------
 hipError_t kernels_init_grad();

@@ -527,9 +527,10 @@ int predict_core(agp_ctx* c, int64_t n, const double* ts_pred, int64_t m, int32_
 // the Cholesky factor of Sigma* = K22 - K21 K11^-1 K12 + noise_pred I and its forward solve L22^-1 (y* - mu*), so the query columns'
 // partials are log|Sigma*| and the Mahalanobis term themselves (k_finish_pred_logpdf) — no Schur step, no read-out, and no
 // difference of two large log-likelihoods.  (No duplicate-query shortcut: it yields diag(Sigma*), not Sigma*.)
+// y_pred == nullptr (agp_predict_sample_batch): the query part of the right-hand side is 0.  `hooks` (nullable): see JointHooks.
 int predict_logpdf_core(agp_ctx* c, int64_t n, const double* ts_pred, const double* y_pred, int64_t m, int32_t P, Batch& bt,
                         const double* noise, const double* noise_pred, const double* mean_train, const double* mean_pred,
-                        double* out_lp, int32_t* out_info, const PredLattice* pl) {
+                        double* out_lp, int32_t* out_info, const PredLattice* pl, JointHooks* hooks) {
   const int n1_pad = round_up(n, NB), m_pad = round_up(m, NB);
   const bool lagr = pl != nullptr && pl->on;
   const int nt1 = n1_pad / NB, nt = nt1 + m_pad / NB;
@@ -552,8 +553,10 @@ int predict_logpdf_core(agp_ctx* c, int64_t n, const double* ts_pred, const doub
   PinnedUploads up;
   std::vector<double> noise_sorted, npred;
   if (const int rc = stage_joint(c, s, up, n, ts_pred, m, P, chunk, bt, noise, noise_pred, mean_train, mean_pred, noise_sorted, npred)) return rc;
-  up.add(s->pred_mean.p, y_pred, sizeof(double) * m);
+  if (y_pred) up.add(s->pred_mean.p, y_pred, sizeof(double) * m);
   up.add(s->map.p, bt.order.data(), sizeof(int32_t) * P);
+  if (hooks && hooks->stage)
+    if (const int rc = hooks->stage(s, up, chunk)) return rc;
   if (!lagr) {
     HIPCHK(c, up.flush(s->h_stage, s->up_blob, st));
   } else if (const int rc = flush_lattice(c, s, st, up, bt, *pl, pl->rank)) {
@@ -564,8 +567,9 @@ int predict_logpdf_core(agp_ctx* c, int64_t n, const double* ts_pred, const doub
     const int Pc = std::min(chunk, P - p0);
     launch_init_vec(st, ntot, Pc, s->vec.as<double>(), c->d_xs, (mean_train && n > 0) ? s->mu1.as<double>() : (const double*)nullptr,
                     (int)n, s->info.as<int>() + p0, s->ready.as<int>() + p0);
-    launch_init_query_vec(st, Pc, s->vec.as<double>(), ntot, n1_pad, (int)m, s->pred_mean.as<double>(),
-                          mean_pred ? s->mu2.as<double>() : (const double*)nullptr);
+    if (y_pred)
+      launch_init_query_vec(st, Pc, s->vec.as<double>(), ntot, n1_pad, (int)m, s->pred_mean.as<double>(),
+                            mean_pred ? s->mu2.as<double>() : (const double*)nullptr);
     CovArgs cv = {};
     cv.tt = s->tt.as<double>(); cv.n1 = (int)n; cv.n1_pad = n1_pad; cv.m2 = (int)m; cv.nt = nt;
     cv.hdr = s->hdr.as<ProgHdr>() + p0; cv.ops = s->ops.as<uint8_t>(); cv.prm = s->prm.as<double>();
@@ -595,6 +599,8 @@ int predict_logpdf_core(agp_ctx* c, int64_t n, const double* ts_pred, const doub
     launch_finish_pred_logpdf(st, ca.partial, ca.info, nt1, nt, Pc, (int)m, (int)n, n1_pad, s->map.as<int32_t>() + p0,
                               s->out_lp.as<double>(), s->out_info.as<int32_t>());
     HIPCHK(c, hipGetLastError());
+    if (hooks && hooks->chunk)      // (before the next chunk overwrites A)
+      if (const int rc = hooks->chunk(s, st, ca, p0, Pc)) return rc;
   }
   // (results are in the caller's order already; blocking copies: nothing in flight towards the locals on an error return)
   std::vector<int32_t> info(P);
@@ -605,6 +611,8 @@ int predict_logpdf_core(agp_ctx* c, int64_t n, const double* ts_pred, const doub
     if (info[p] < 0) return fail(c, AGP_ERR_HIP, "in-kernel panel solve timed out waiting for its diagonal factor");
     if (out_info) out_info[p] = info[p];
   }
+  if (hooks && hooks->done)
+    if (const int rc = hooks->done(s)) return rc;
   return AGP_OK;
 }
 
@@ -961,6 +969,16 @@ static int predict_logpdf_body(agp_ctx* c, int64_t n, const double* ts_pred, con
     return AGP_OK;
   }
   if (!op_off || !ops || !prm_off || !prm || !noise || !ts_pred || !y_pred) return fail(c, AGP_ERR_ARG, "null pointer argument");
+  return predict_joint_batch(c, n, ts_pred, y_pred, m, P, op_off, ops, prm_off, prm, noise, noise_pred, mean_train, mean_pred,
+                             out_logpdf, out_info, nullptr);
+}
+
+}  // extern "C"
+
+int predict_joint_batch(agp_ctx* c, int64_t n, const double* ts_pred, const double* y_pred, int64_t m, int32_t P,
+                        const int32_t* op_off, const uint8_t* ops, const int32_t* prm_off, const double* prm,
+                        const double* noise, const double* noise_pred, const double* mean_train, const double* mean_pred,
+                        double* out_logpdf, int32_t* out_info, JointHooks* hooks) {
   HIPCHK(c, hipSetDevice(c->device));
   // identical particles (a resampled population, src/inference_smc_anneal_data.jl:198-204) are evaluated once, as in agp_predict_batch
   // (malformed offsets, c->dedup off: every particle — compile_batch diagnoses the offsets)
@@ -981,7 +999,9 @@ static int predict_logpdf_body(agp_ctx* c, int64_t n, const double* ts_pred, con
   Batch bt;
   int rc = compile_batch(c, U, bo, bops, bpo, bprm, bt, false, false, false, ff, ff, pl.on, pl.on ? pl.rank_units : 1, pl.on);
   if (rc) return rc;
-  rc = predict_logpdf_core(c, n, ts_pred, y_pred, m, U, bt, bnz, bnzp, mean_train, mean_pred, ulp.data(), uinfo.data(), &pl);
+  if (hooks && hooks->plan)
+    if ((rc = hooks->plan(U, packed ? rep : std::vector<int>(), bt.order))) return rc;
+  rc = predict_logpdf_core(c, n, ts_pred, y_pred, m, U, bt, bnz, bnzp, mean_train, mean_pred, ulp.data(), uinfo.data(), &pl, hooks);
   if (rc) return rc;
   for (int p = 0; p < P; ++p) {
     const size_t u = packed ? (size_t)rep[p] : (size_t)p;
@@ -990,6 +1010,8 @@ static int predict_logpdf_body(agp_ctx* c, int64_t n, const double* ts_pred, con
   }
   return AGP_OK;
 }
+
+extern "C" {
 
 // infer_gp_sum (src/GP.jl:904-993): posterior over Z = [F_1(T*); ...; F_M(T*); X(T*)] given X(T) = xs, for the
 // sum-of-GPs model X = sum_i F_i + noise.  The joint prior covariance over [X(T); Z] is the single program

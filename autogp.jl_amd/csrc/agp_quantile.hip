@@ -6,8 +6,6 @@
 
 #include <cfloat>
 
-namespace {
-
 // MixtureModel's isprobvec (from memory): finite, non-negative weights whose sum isapprox 1 (rtol sqrt(eps))
 int check_weights(agp_ctx* c, int32_t P, const double* w) {
   if (!w) return fail(c, AGP_ERR_ARG, "null weights");
@@ -20,6 +18,8 @@ int check_weights(agp_ctx* c, int32_t P, const double* w) {
     return fail(c, AGP_ERR_ARG, "weights must sum to 1");
   return AGP_OK;
 }
+
+namespace {
 
 // the checks both entries share (predict_quantile's own: 0 < q < 1)
 int check_common(agp_ctx* c, int64_t m, int32_t P, const double* weights, const double* q, int64_t nq) {

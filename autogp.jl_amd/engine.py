@@ -34,6 +34,7 @@ EXPORTED_SYMBOLS = [
     "agp_predict_reuse_stats", "agp_grad_reuse_stats", "agp_set_factor_cache", "agp_wait", "agp_comm_count", "agp_get_lag_stats", "agp_get_lattice_stats", "agp_get_compact_stats", "agp_set_lattice", "agp_probe_lattice", "agp_set_reference_arithmetic", "agp_shard_plan", "agp_get_coalesce_timing", "agp_set_lag_tables", "agp_set_grad_lag_domain", "agp_get_grad_lag_domain_stats", "agp_get_grad_toeplitz_stats", "agp_get_grad_structured_stats", "agp_get_predict_structured_stats", "agp_get_toeplitz_stats", "agp_set_lag_rank_tables", "agp_get_lag_rank_stats", "agp_get_lag_predict_stats", "agp_get_poison_stats",
     "agp_logpdf_grad_batch_multi", "agp_predict_batch_multi", "agp_extend_stats2", "agp_predict_logpdf_batch",
     "agp_mixture_quantile", "agp_predict_quantile_batch", "agp_infer_gp_sum_batch", "agp_predict_sum_batch",
+    "agp_predict_sample_batch",
 ]
 COMM_ID_BYTES = 128
 
@@ -113,6 +114,9 @@ def load_library(path=None):
     lib.agp_predict_quantile_batch.argtypes = [vp, C.c_int64, dp, C.c_int64, C.c_int32, ip, u8p, ip, dp, dp, dp, dp, dp, dp,
                                                C.c_double, C.c_double, dp, C.c_int64, C.c_double, C.c_int64, dp, ip, ip, ip]
     lib.agp_predict_quantile_batch.restype = C.c_int
+    lib.agp_predict_sample_batch.argtypes = [vp, C.c_int64, dp, C.c_int64, C.c_int32, ip, u8p, ip, dp, dp, dp, dp, dp, dp,
+                                             C.c_double, C.c_double, C.c_int64, C.c_uint64, ip, dp, dp, ip, ip]
+    lib.agp_predict_sample_batch.restype = C.c_int
     lib.agp_infer_gp_sum.argtypes = [vp, C.c_int64, dp, C.c_int64, C.c_int32, ip, u8p, ip, dp, C.c_double, C.c_double, dp, dp, ip]
     lib.agp_infer_gp_sum.restype = C.c_int
     lib.agp_infer_gp_sum_batch.argtypes = [vp, C.c_int64, dp, C.c_int64, C.c_int32, C.c_int32, ip, u8p, ip, dp, dp, dp, dp, dp, dp, ip]
@@ -584,6 +588,43 @@ class GPEngine:
             raise PosDefException(int(info[p]), p)
         return _quantile_shape(q, x, conv, iters) + (info,)
 
+    # -- posterior predictive samples (src/api.jl:497-522 + Distributions' rand) -------------------------------------------
+    def predict_sample_batch(self, nodes, noises, ts_pred, weights, n_samples, seed=0, n=None, noise_pred=None, mean_train=None,
+                             mean_pred=None, y_transform=(1.0, 0.0), component=None, z=None, check=True):
+        """rand(MixtureModel(MvNormal_p, weights), n_samples) of every particle's predictive at ts_pred on the resident series, in the
+        raw space of y_transform = (slope, intercept) (agp_predict_sample_batch).  component (n_samples,) and z (m, n_samples) are
+        optional: the components / standard normals to use instead of the seeded draws.  Returns (x, component, info): x of shape
+        (m, n_samples) (column s is sample s), the component of each sample, info[P] (n + k: leading minor k of a predictive covariance
+        is not positive definite; x is NaN everywhere if any info != 0, PosDefException when check)."""
+        n = self.n_max if n is None else int(n)
+        op_off, ops, prm_off, prm = _gp.encode_batch(nodes)
+        P = op_off.shape[0] - 1
+        noises = _f64(noises); ts_pred = _f64(ts_pred); m = ts_pred.shape[0]; weights = _f64(weights)
+        S = int(n_samples)
+        if weights.shape != (P,):
+            raise ValueError(f"weights has shape {weights.shape}, expected ({P},)")
+        npred = None if noise_pred is None else _f64(np.broadcast_to(noise_pred, (P,)))
+        mt = None if mean_train is None else _f64(mean_train)
+        mp_ = None if mean_pred is None else _f64(mean_pred)
+        cin = None if component is None else np.ascontiguousarray(component, dtype=np.int32)
+        if cin is not None and cin.shape != (S,):
+            raise ValueError(f"component has shape {cin.shape}, expected ({S},)")
+        zin = None
+        if z is not None:
+            z = np.asarray(z, dtype=np.float64)
+            if z.shape != (m, S):
+                raise ValueError(f"z has shape {z.shape}, expected ({m}, {S})")
+            zin = np.ascontiguousarray(z.T)          # (sample s's m normals contiguous)
+        slope, intercept = (float(v) for v in y_transform)
+        xt = np.empty((max(S, 0), m)); comp = np.zeros(max(S, 0), dtype=np.int32); info = np.zeros(P, dtype=np.int32)
+        self._check(self._lib.agp_predict_sample_batch(self._ctx, n, _dp(ts_pred), m, P, _ip(op_off), _u8(ops), _ip(prm_off), _dp(prm),
+                                                       _dp(noises), _dp(npred), _dp(mt), _dp(mp_), _dp(weights), slope, intercept,
+                                                       S, int(seed) & (2**64 - 1), _ip(cin), _dp(zin), _dp(xt), _ip(comp), _ip(info)))
+        if check and (info > 0).any():
+            p = int(np.argmax(info > 0))
+            raise PosDefException(int(info[p]), p)
+        return xt.T, comp, info
+
     # -- sum-of-GPs posterior (src/GP.jl:904-993) ---------------------------------------------
     def infer_gp_sum(self, nodes, noise, ts_pred, n=None, noise_pred=None, check=True):
         """Returns (mean[(M+1)p], cov[(M+1)p, (M+1)p], indexes_F (list of slices), indexes_X (slice))."""
@@ -709,10 +750,11 @@ class GPEngine:
         self._check(self._lib.agp_set_profiling(self._ctx, 1 if on else 0))
 
     def timing(self):
-        out = np.zeros(12)
-        self._check(self._lib.agp_get_timing(self._ctx, _dp(out), 12))
+        out = np.zeros(14)
+        self._check(self._lib.agp_get_timing(self._ctx, _dp(out), 14))
         keys = ["total_ms", "cov_build_ms", "chol_update_ms", "chol_trsm_ms", "finish_ms", "n_update_launches",
-                "n_trsm_launches", "h2d_ms", "grad_trtri_ms", "grad_kinv_ms", "grad_contract_ms", "grad_alpha_finish_ms"]
+                "n_trsm_launches", "h2d_ms", "grad_trtri_ms", "grad_kinv_ms", "grad_contract_ms", "grad_alpha_finish_ms",
+                "sample_normals_ms", "sample_readout_ms"]
         return dict(zip(keys, out.tolist()))
 
     def launch_times(self, which=0, n=64):
@@ -990,6 +1032,19 @@ class MvNormal:
     def cov(self):
         return self.Sigma
 
+    def rand(self, n_samples=None, seed=0):
+        """rand(d) / rand(d, n_samples) on the GPU (agp_predict_sample_batch with one particle of weight 1): one vector of length m for
+        n_samples=None, else (m, n_samples), column s being sample s.  With empty ts / xs this is the prior MvNormal the tutorials
+        sample synthetic data from.  The draws are not Julia's RNG stream; the distribution is the contract.  Raises
+        PosDefException like the reference."""
+        if self._score is None:
+            raise NotImplementedError("rand of an MvNormal built from its moments")
+        eng, node, noise, ts, xs, ts_pred, noise_pred, mt, mp_ = self._score
+        eng.set_data(ts, xs)
+        x, _, _ = eng.predict_sample_batch([node], [noise], ts_pred, [1.0], 1 if n_samples is None else n_samples, seed=seed,
+                                           noise_pred=noise_pred, mean_train=mt, mean_pred=mp_)
+        return x[:, 0].copy() if n_samples is None else x
+
     def logpdf(self, y):
         """Distributions.logpdf(d, y) (src/api.jl:693), on the GPU from the joint factorisation (agp_predict_logpdf_batch).
         Raises PosDefException like the reference."""
@@ -1029,6 +1084,21 @@ def predict_quantile(engine, nodes, noises, log_weights, ts_pred, q, y_transform
     x, conv, _, _ = engine.predict_quantile_batch(nodes, noises, ts_pred, w, q, noise_pred=npred, y_transform=y_transform, tol=tol,
                                                   max_iter=max_iter)
     return x, (bool(conv.all()) if np.ndim(q) == 0 else conv.all(axis=0))
+
+
+def predict_rand(engine, nodes, noises, log_weights, ts_pred, n_samples=None, seed=0, y_transform=(1.0, 0.0), noise_pred=None):
+    """rand(predict_mvn(model, ds; noise_pred), n_samples) (src/api.jl:497-522 + Distributions' rand) on the engine's resident (scaled)
+    series: samples of the weighted mixture of every particle's posterior predictive at ts_pred (already in the engine's time scale),
+    in the RAW space of y_transform = (slope, intercept) (scaled = slope * raw + intercept).  Weights are the particle_weights route:
+    exp of Gen.normalize_weights(log_weights).  Returns one vector of length m for n_samples=None, else (m, n_samples).  The draws are
+    a counter-based stream of `seed` (not Julia's RNG); the distribution is the contract.  Raises PosDefException when a particle has
+    no predictive (the reference throws building its MvNormal)."""
+    from .dist import normalize_weights
+    w = np.exp(normalize_weights(log_weights)[1])
+    npred = None if noise_pred is None else float(noise_pred)
+    x, _, _ = engine.predict_sample_batch(nodes, noises, ts_pred, w, 1 if n_samples is None else n_samples, seed=seed,
+                                          noise_pred=npred, y_transform=y_transform)
+    return x[:, 0].copy() if n_samples is None else x
 
 
 def infer_gp_sum(nodes, noise, ts, xs, ts_pred, noise_pred=None, engine=None):

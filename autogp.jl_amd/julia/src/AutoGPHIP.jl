@@ -443,6 +443,32 @@ function predict_quantile(eng::Engine, nodes::Vector{<:GP.Node}, noises::Vector{
     return x, all(!=(0), conv)
 end
 
+"""
+`rand(AutoGP.predict_mvn(model, ds; noise_pred), N)` (src/api.jl:497-522 + Distributions' `rand`) for a population on the (scaled)
+resident series: `N` samples of the mixture, with `weights` (`AutoGP.particle_weights(model)`), of every particle's predictive at
+`ts_pred`, in the raw space of the linear `y_transform` (slope, intercept).  Returns an m×N matrix (a vector of length m for
+`N = nothing`).  The draws come from a counter-based stream of `seed`, not from Julia's RNG: the distribution is the contract.
+Throws `PosDefException` where a particle has no predictive.
+"""
+function predict_rand(eng::Engine, nodes::Vector{<:GP.Node}, noises::Vector{Float64}, weights::Vector{Float64},
+        ts_pred::Vector{Float64}, N::Union{Nothing,Integer}=nothing; seed::Integer=0, n::Integer=eng.n_max,
+        noise_pred::Union{Nothing,Float64}=nothing, y_slope::Float64=1.0, y_intercept::Float64=0.0)
+    P = length(nodes); m = length(ts_pred); S = isnothing(N) ? 1 : Int(N)
+    op_off, ops, prm_off, prm = encode_batch(nodes)
+    x = Matrix{Float64}(undef, m, S); info = zeros(Int32, P)
+    npv = isnothing(noise_pred) ? Float64[] : fill(noise_pred, P)
+    GC.@preserve ops prm op_off prm_off ts_pred noises npv weights x info check(eng, ccall((:agp_predict_sample_batch, LIB), Cint,
+        (Ptr{Cvoid}, Int64, Ptr{Float64}, Int64, Int32, Ptr{Int32}, Ptr{UInt8}, Ptr{Int32}, Ptr{Float64},
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Float64, Float64, Int64, UInt64, Ptr{Int32},
+         Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Int32}),
+        eng.ptr, n, ts_pred, m, P, op_off, ops, prm_off, prm, noises,
+        isempty(npv) ? Ptr{Float64}(C_NULL) : pointer(npv), Ptr{Float64}(C_NULL), Ptr{Float64}(C_NULL),
+        weights, y_slope, y_intercept, S, UInt64(seed), Ptr{Int32}(C_NULL), Ptr{Float64}(C_NULL), x, Ptr{Int32}(C_NULL), info))
+    k = findfirst(!=(0), info)
+    isnothing(k) || throw(LinearAlgebra.PosDefException(info[k]))
+    return isnothing(N) ? x[:, 1] : x
+end
+
 "Sum-of-GPs posterior — replaces GP.infer_gp_sum (src/GP.jl:904-993); returns the same named tuple."
 function infer_gp_sum(eng::Engine, nodes::Vector{<:GP.Node}, noise::Float64, ts_pred::Vector{Float64};
         n::Integer=eng.n_max, noise_pred::Union{Nothing,Float64}=nothing)

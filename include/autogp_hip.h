@@ -427,6 +427,40 @@ int agp_predict_quantile_batch(agp_ctx* ctx, int64_t n, const double* ts_pred, i
                                double y_slope, double y_intercept, const double* q, int64_t nq, double tol, int64_t max_iter,
                                double* out_x, int32_t* out_converged, int32_t* out_iters, int32_t* out_info);
 
+/* Posterior predictive samples: rand(MixtureModel(MvNormal_p, weights), S) of predict_mvn (src/api.jl:497-522) on the resident
+ * (ts, xs)[1:n] — rand(predict_mvn(model, ds; noise_pred), S).  Arguments n .. mean_pred as agp_predict_logpdf_batch (noise_pred NULL
+ * = each particle's noise, mean_train / mean_pred NULL = 0; n == 0 samples the prior K22 + noise_pred I).  Sample s is the column
+ * out_x[s*m .. s*m + m) (Julia's m x S result of rand(d, S)):
+ *     x_s = (mu*_c - y_intercept) / y_slope + (L22_c z_s) / |y_slope|,      c = c_s,  L22_c = chol(Sigma*_c)
+ * — MvNormal((mu - b) / a, Sigma / a^2) of predict_mvn's raw-space transform, whose Cholesky factor is L22 / |a|.  mu*_c = mu2 + L21 a
+ * and L22_c come from the joint factor of agp_predict_logpdf_batch's pass (the query right-hand side 0); no covariance is formed.
+ *   component c_s: component[s] when given (S entries, each in [0, P) at a positive weight); else the inverse CDF of the cumulative
+ *     weights (particle order, fp64 sums) at the uniform u_s: the first p with u_s < cum[p]; the last particle of positive weight when
+ *     rounding leaves u_s >= cum[P-1] (a weight-0 particle is never drawn).  out_component[s] (may be NULL) receives c_s.
+ *   normals z_s: z[s*m + i] when z is given (m*S entries); else z[s, i] = ndtri(u) (AS 241, as agp_predict_sum_batch).
+ *   uniforms: Philox4x64-10 (Random123's constants, numpy.random.Philox) under the key (seed, 0); a 64-bit output word w gives
+ *     u = ((w >> 11) + 0.5) * 2^-53 in fp64 (the one word that rounds to 1 gives 1 - 2^-53).  u_s is word 0 of the block of counter
+ *     (s, 0, 0, 0); the u of z[s, i] is word i % 4 of the block (i / 4, s, 1, 0).
+ * The bits of x[:, s] depend only on seed, s and the inputs of its component (its program, parameters, noise, noise_pred, the data,
+ * ts_pred, the means and the transform): not on S, P, the particle order, copies, the workspace chunking or the other samples.
+ * The draws are not Julia's RNG stream: the distribution, and the algebra given (c, z), are the contract.
+ * m == 0 or S == 0: nothing is written.  out_info[p] (may be NULL): 0; 1..n: K11 is not positive definite (first failing minor); n + k:
+ * leading minor k of the predictive covariance is not (agp_predict_logpdf_batch's convention).  If any particle's info != 0, out_x is
+ * NaN everywhere (the reference throws PosDefException building that particle's MvNormal).  Identical particles are factored once
+ * (AGP_DEDUP=0 disables); a sample drawn to any copy reads the shared factor.  Errors (negative return): P < 1; n, m or S < 0;
+ * n > the uploaded series; weights not finite, negative or not summing to 1 (rtol sqrt(eps)); y_slope not finite or 0, y_intercept not
+ * finite; a given component outside [0, P) or at weight 0; m*S >= 2^31; a NULL input. */
+int agp_predict_sample_batch(agp_ctx* ctx, int64_t n, const double* ts_pred, int64_t m, int32_t P,
+                             const int32_t* op_off, const uint8_t* ops,
+                             const int32_t* prm_off, const double* prm,
+                             const double* noise, const double* noise_pred,
+                             const double* mean_train, const double* mean_pred, const double* weights,
+                             double y_slope, double y_intercept,
+                             int64_t S, uint64_t seed, const int32_t* component /* S or NULL */,
+                             const double* z /* m*S or NULL */,
+                             double* out_x /* m*S column-major */, int32_t* out_component /* S or NULL */,
+                             int32_t* out_info /* P or NULL */);
+
 /* infer_gp_sum(nodes, noise, ts, xs, ts_pred; noise_pred) (src/GP.jl:904-993) on the resident (ts, xs)[1:n]:
  * posterior of Z = [F_1(T*); ...; F_M(T*); X(T*)] for the sum-of-GPs model.  The M component kernels are
  * given as CSR-packed postfix programs (op_off / prm_off have M+1 entries).  out_mean: (M+1)*p;
@@ -592,7 +626,8 @@ int agp_debug_compact_shards(agp_ctx* ctx, const double* padded, int32_t P, int3
 /* When enabled, batch calls bracket their phases with HIP events on the launch stream.
  * agp_get_timing fills out[0..7] = { total_ms, cov_build_ms, chol_update_ms, chol_trsm_ms,
  * finish_ms, n_update_launches, n_trsm_launches, h2d_d2h_ms } for the last batch call; a value+gradient sweep also
- * fills out[8..11] = { L^-T chain ms, K^-1 tiles ms, contraction ms, alpha + reductions ms } (n_out up to 16). */
+ * fills out[8..11] = { L^-T chain ms, K^-1 tiles ms, contraction ms, alpha + reductions ms }, agp_predict_sample_batch
+ * out[12..13] = { normals ms, read-out ms } (n_out up to 16). */
 int agp_set_profiling(agp_ctx* ctx, int enabled);
 int agp_get_timing(agp_ctx* ctx, double* out, int32_t n_out);
 /* per-launch durations (ms) of the last profiled batch call: which = 0 update kernel, 1 trsm kernel;
