@@ -1728,6 +1728,7 @@ static int init_body(agp_ctx** out, int device_id) {
   if (const char* e = getenv("AGP_RIGHT_LOOKING")) c->right_looking = atoi(e);
   if (const char* e = getenv("AGP_DEDUP")) c->dedup = atoi(e) != 0;
   if (const char* e = getenv("AGP_PREDICT_REUSE")) c->predict_reuse = atoi(e) != 0;
+  if (const char* e = getenv("AGP_REMOVE_UPDATE")) c->remove_update = std::max(0, std::min(2, atoi(e)));
   if (const char* e = getenv("AGP_FACTOR_CACHE")) c->factor_cache = atoi(e) != 0;
   if (const char* e = getenv("AGP_COALESCE_US")) c->coalesce_us = std::max(0, atoi(e));
   if (const char* e = getenv("AGP_FLOW")) c->flow = atoi(e);
@@ -1958,11 +1959,15 @@ int agp_probe_lattice(const double* ts, int64_t n, int32_t* kind, int64_t* n_lat
   return AGP_OK;
 }
 
-static int set_data_body(agp_ctx* c, const double* ts, const double* xs, int64_t n_max);
+static int set_data_body(agp_ctx* c, const double* ts, const double* xs, int64_t n_max, const std::vector<uint8_t>* keep = nullptr);
 int agp_set_data(agp_ctx* c, const double* ts, const double* xs, int64_t n_max) {
   return abi_guard(c, [&] { return set_data_body(c, ts, xs, n_max); });
 }
-static int set_data_body(agp_ctx* c, const double* ts, const double* xs, int64_t n_max) {
+extern "C++" int set_data_after_remove(agp_ctx* c, const double* ts, const double* xs, int64_t n_max, const std::vector<uint8_t>& touched) {
+  return set_data_body(c, ts, xs, n_max, &touched);
+}
+// keep (agp_remove_data): slots whose factors were updated to the new series by the caller
+static int set_data_body(agp_ctx* c, const double* ts, const double* xs, int64_t n_max, const std::vector<uint8_t>* keep) {
   if (!c) return fail(nullptr, AGP_ERR_ARG, "null context");
   if (n_max < 0 || (n_max > 0 && (!ts || !xs))) return fail(c, AGP_ERR_ARG, "bad data arguments");
   HIPCHK(c, hipSetDevice(c->device));
@@ -1974,7 +1979,7 @@ static int set_data_body(agp_ctx* c, const double* ts, const double* xs, int64_t
     const bool prefix = c->n_max > 0 && n_max >= c->n_max &&
                         std::memcmp(ts, c->h_ts.data(), sizeof(double) * (size_t)c->n_max) == 0 &&
                         std::memcmp(xs, c->h_xs.data(), sizeof(double) * (size_t)c->n_max) == 0;
-    if (!prefix) {
+    if (!prefix && !keep) {
       c->store.forget(); c->store.ghost_clear();
       { std::lock_guard<std::mutex> gk(c->mu); c->schur_keys.clear(); }
       std::lock_guard<std::mutex> q(c->qmu);          // (another series: another population of callers)
@@ -2147,7 +2152,16 @@ static int set_data_body(agp_ctx* c, const double* ts, const double* xs, int64_t
     if (same && c->lag_ok)
       same = tlat_was.size() <= c->h_ts_lat.size() &&
              std::memcmp(tlat_was.data(), c->h_ts_lat.data(), sizeof(double) * tlat_was.size()) == 0;
-    if (!same) c->store.forget();
+    if (!same && !keep) c->store.forget();
+    if (!same && keep) {
+      // (a removal: the factors it did not reach are prefixes of the old AND the new series — they stay only under the append rule)
+      agp_ctx::FactorStore& fs = c->store;
+      for (int sl = 0; sl < fs.n_slots; ++sl) {
+        if ((size_t)sl < keep->size() && (*keep)[(size_t)sl]) continue;
+        if (!fs.key[(size_t)sl].empty()) fs.index.erase(fs.key[(size_t)sl]);
+        fs.key[(size_t)sl].clear(); fs.n_cached[(size_t)sl] = 0; fs.zrows[(size_t)sl] = 0; fs.used[(size_t)sl] = 0;
+      }
+    }
   }
   // log|t_i - t_j| over the resident points, shared by the GammaExp leaves of every particle (OP_GE_TAB)
   c->logdt_ok = false;

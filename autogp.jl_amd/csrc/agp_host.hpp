@@ -258,6 +258,8 @@ struct agp_ctx {
   int64_t grad_reused = 0, grad_factored = 0;   // gradient sweeps likewise
   int factor_cache = 1;    // 1: coalesced agp_logpdf batches leave their factors in the store (a later call on a longer prefix extends
                            // them, a gradient call at the same parameters skips the factorisation); env AGP_FACTOR_CACHE, agp_set_factor_cache
+  int remove_update = 1;   // 1: agp_remove_data updates the resident factors it touches where remove_admits says it pays; 0: always drops them; 2: always updates them (measurement); env AGP_REMOVE_UPDATE
+  int64_t rm_updated = 0, rm_dropped = 0, rm_rows = 0, rm_panels = 0;   // agp_get_remove_stats (under mu)
   int predict_reuse = 1;   // 1: predictive passes take L11 / alpha of a particle from the factor store when it holds them; env AGP_PREDICT_REUSE
   int dedup = 1;        // evaluate identical particles of a host-output sweep once; env AGP_DEDUP
   int64_t n_particles_seen = 0, n_particles_run = 0;
@@ -608,6 +610,22 @@ inline bool use_right_looking(const agp_ctx* c, int P) {
   return c->right_looking > 0 || (c->right_looking < 0 && P <= RIGHT_LOOKING_MAX_PARTICLES);
 }
 
+// agp_remove_data: update a resident factor or drop it, from (t, r, runs) alone — t rows of the trailing triangle from the first
+// removed position on, r removed rows in all, in `runs` contiguous runs.  Measured on MI355X against agp_set_data + one
+// agp_logpdf_batch_extend on a build of the parent commit (tools/gpu_remove_perf.py, profiles/remove_data_perf.txt; update / baseline
+// at 64 and 512 particles): the update is admitted only where it took at most 0.8 of the baseline at both populations, for the
+// SHORTEST series a given t can belong to (a leading removal: n = t + r) —
+//   one run, t = 2047, r = 1: 0.70 / 0.37;  t = 2040, r = 8: 0.75 / 0.43;  t = 2016, r = 32: 0.98 / 0.58 (refused);
+//   t = 511, r = 1: 1.41 / 0.98 (refused: four panel steps cost what four block columns of the factorisation cost);
+//   8 runs at n = 2048: 3.0 / 1.7 (refused: every run is one shifted copy of the trailing factor).
+// The update's cost grows with t^2 and the baseline's with n^3 >= t^3, so longer trailing triangles only widen the margin.  Removals
+// in the middle of n = 2048 (t ~ 1020) took 0.23 .. 0.58 up to r = 32, but a rule that sees t alone must also hold for n = t + r,
+// which was not measured between 512 and 2048: refused until it is.
+constexpr int64_t REMOVE_MIN_TRAIL = 2040;
+constexpr int64_t REMOVE_MAX_ROWS = 8;
+constexpr int REMOVE_MAX_RUNS = 1;
+inline bool remove_admits(int64_t t, int64_t r, int runs) { return t >= REMOVE_MIN_TRAIL && r <= REMOVE_MAX_ROWS && runs <= REMOVE_MAX_RUNS; }
+
 struct GradOut {
   double* grad;      // host, caller's parameter layout (prm_off), d logpdf / d parameter
   double* gnoise;    // host [P], d logpdf / d noise
@@ -705,6 +723,11 @@ int extend_impl(agp_ctx* c, int64_t n, int32_t P, const int32_t* op_off, const u
                 const double* prm, const double* noise, double* out_lp, int32_t* out_info,
                 double* d_out_caller = nullptr, bool* wrote_device = nullptr);
 
+
+// agp_set_data's body for agp_remove_data (agp_remove.hip): the reduced series replaces the resident one, the factors of the slots
+// flagged in `touched` (already updated to the reduced series) stay whatever the series' evaluation mode becomes — they agree with a
+// from-scratch factor to rounding, not to the bit — and the other resident factors stay under agp_set_data's own rule for an append.
+int set_data_after_remove(agp_ctx* c, const double* ts, const double* xs, int64_t n_max, const std::vector<uint8_t>& touched);
 
 int store_lookup(agp_ctx* c, const std::vector<std::string>& keys, const std::vector<int32_t>& order, int P, int64_t n, int nt,
                  std::vector<int32_t>& src_slot, std::vector<int32_t>& i0v, std::unique_lock<std::mutex>& lk);

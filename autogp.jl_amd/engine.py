@@ -35,6 +35,7 @@ EXPORTED_SYMBOLS = [
     "agp_logpdf_grad_batch_multi", "agp_predict_batch_multi", "agp_extend_stats2", "agp_predict_logpdf_batch",
     "agp_mixture_quantile", "agp_predict_quantile_batch", "agp_infer_gp_sum_batch", "agp_predict_sum_batch",
     "agp_predict_sample_batch",
+    "agp_remove_data", "agp_get_remove_stats", "agp_set_remove_update", "agp_remove_data_multi",
 ]
 COMM_ID_BYTES = 128
 
@@ -148,6 +149,10 @@ def load_library(path=None):
     lib.agp_extend_stats.argtypes = [vp, C.POINTER(C.c_int64)]; lib.agp_extend_stats.restype = C.c_int
     lib.agp_extend_reset.argtypes = [vp, C.c_int]; lib.agp_extend_reset.restype = C.c_int
     lib.agp_extend_stats2.argtypes = [vp, C.POINTER(C.c_int64), C.c_int32]; lib.agp_extend_stats2.restype = C.c_int
+    lib.agp_remove_data.argtypes = [vp, C.POINTER(C.c_int64), C.c_int64]; lib.agp_remove_data.restype = C.c_int
+    lib.agp_get_remove_stats.argtypes = [vp, C.POINTER(C.c_int64), C.c_int32]; lib.agp_get_remove_stats.restype = C.c_int
+    lib.agp_set_remove_update.argtypes = [vp, C.c_int32]; lib.agp_set_remove_update.restype = C.c_int
+    lib.agp_remove_data_multi.argtypes = [C.POINTER(vp), C.c_int32, C.POINTER(C.c_int64), C.c_int64]; lib.agp_remove_data_multi.restype = C.c_int
     lib.agp_predict_reuse_stats.argtypes = [vp, C.POINTER(C.c_int64)]; lib.agp_predict_reuse_stats.restype = C.c_int
     lib.agp_grad_reuse_stats.argtypes = [vp, C.POINTER(C.c_int64)]; lib.agp_grad_reuse_stats.restype = C.c_int
     lib.agp_set_factor_cache.argtypes = [vp, C.c_int32]; lib.agp_set_factor_cache.restype = C.c_int
@@ -210,6 +215,20 @@ def _u8(a):
 
 def _f64(a):
     return np.ascontiguousarray(np.asarray(a, dtype=np.float64))
+
+
+def check_remove_indexes(indexes, n_max):
+    """The positions of remove_data as a contiguous int64 vector: distinct, ascending, inside [0, n_max) and not empty (the
+    reference's "No such time points"); raises ValueError before any library call."""
+    raw = np.asarray(indexes)
+    if raw.ndim != 1 or raw.size == 0:
+        raise ValueError("no such time points: indexes must be a non-empty vector of positions")
+    if raw.dtype.kind not in "iu":
+        raise ValueError("indexes must be integers")
+    idx = np.ascontiguousarray(raw, dtype=np.int64)
+    if idx[0] < 0 or idx[-1] >= int(n_max) or (idx.size > 1 and (np.diff(idx) <= 0).any()) or (idx < 0).any() or (idx >= int(n_max)).any():
+        raise ValueError(f"indexes must be distinct ascending positions in [0, {int(n_max)})")
+    return idx
 
 
 class GPEngine:
@@ -299,6 +318,26 @@ class GPEngine:
             raise ValueError("ts and xs must be equal-length vectors")
         self._check(self._lib.agp_set_data(self._ctx, _dp(ts), _dp(xs), ts.shape[0]))
         self.n_max = ts.shape[0]
+
+    def remove_data(self, indexes):
+        """remove_data! (src/api.jl:449-468): delete the observations at the given 0-based ascending positions of the resident series.
+        Resident factors that contain removed positions are updated on the device (or dropped where refactoring is cheaper), so
+        logpdf_batch_extend at the new n_max starts from them.  Returns the new n_max."""
+        idx = check_remove_indexes(indexes, getattr(self, "n_max", 0))
+        self._check(self._lib.agp_remove_data(self._ctx, idx.ctypes.data_as(C.POINTER(C.c_int64)), idx.size))
+        self.n_max -= int(idx.size)
+        return self.n_max
+
+    def remove_stats(self):
+        """dict(updated, dropped, rows_removed, panel_steps) of remove_data since the engine was created (agp_get_remove_stats)."""
+        out = (C.c_int64 * 4)()
+        self._check(self._lib.agp_get_remove_stats(self._ctx, out, 4))
+        return dict(zip(("updated", "dropped", "rows_removed", "panel_steps"), [int(v) for v in out]))
+
+    def set_remove_update(self, on):
+        """0: remove_data always drops the factors it touches; 1: the admission rule decides; 2: always updates (measurement)
+        (env AGP_REMOVE_UPDATE)."""
+        self._check(self._lib.agp_set_remove_update(self._ctx, int(on)))
 
     # -- value path (src/Model.jl:135-136) ---------------------------------------------------
     def logpdf(self, node, noise, n=None, check=True):
@@ -941,6 +980,15 @@ class GPEngineMulti:
         self.n_max = ts.shape[0]
         for e in self.engines:
             e.n_max = self.n_max
+
+    def remove_data(self, indexes):
+        """GPEngine.remove_data on every device (agp_remove_data_multi).  Returns the new n_max."""
+        idx = check_remove_indexes(indexes, getattr(self, "n_max", 0))
+        self._check(self._lib.agp_remove_data_multi(self._arr, self._n, idx.ctypes.data_as(C.POINTER(C.c_int64)), idx.size))
+        self.n_max -= int(idx.size)
+        for e in self.engines:
+            e.n_max = self.n_max
+        return self.n_max
 
     def logpdf_batch(self, nodes, noises, n=None, check=True, programs=None, extend=False):
         """extend=True: every device runs its shard as an extension sweep (agp_logpdf_batch_extend_multi)."""

@@ -92,6 +92,25 @@ function set_data!(eng::Engine, ts::Vector{Float64}, xs::Vector{Float64})
 end
 set_data!(pool::EnginePool, ts::Vector{Float64}, xs::Vector{Float64}) = (foreach(e -> set_data!(e, ts, xs), pool.engines); pool)
 
+"remove_data! (src/api.jl:449-468): delete the observations at the 1-based ascending positions `idx` of the resident series.  Resident
+factors that contain removed positions are updated on the device (or dropped where refactoring is cheaper), so
+`logpdf_batch(...; extend=true)` on the reduced series starts from them."
+function remove_data!(eng::Engine, idx::AbstractVector{<:Integer})
+    isempty(idx) && error("No such time points.")
+    idx0 = Int64[i - 1 for i in idx]
+    GC.@preserve idx0 check(eng, ccall((:agp_remove_data, LIB), Cint, (Ptr{Cvoid}, Ptr{Int64}, Int64), eng.ptr, idx0, length(idx0)))
+    keep = setdiff(1:eng.n_max, idx)
+    eng.ts = eng.ts[keep]; eng.xs = eng.xs[keep]; eng.n_max = length(keep)
+    return eng
+end
+
+"(updated, dropped, rows_removed, panel_steps) of `remove_data!` since the engine was created"
+function remove_stats(eng::Engine)
+    out = zeros(Int64, 4)
+    GC.@preserve out check(eng, ccall((:agp_get_remove_stats, LIB), Cint, (Ptr{Cvoid}, Ptr{Int64}, Int32), eng.ptr, out, 4))
+    return (updated = out[1], dropped = out[2], rows_removed = out[3], panel_steps = out[4])
+end
+
 "Is (ts, xs) the prefix of the resident series?  O(n) comparisons next to an O(n^3) factorisation."
 function is_resident_prefix(eng::Engine, ts::AbstractVector{<:Real}, xs::AbstractVector{<:Real})
     n = length(ts)

@@ -154,6 +154,17 @@ class OnlineStream:
         self.history.append(st)
         return st
 
+    def remove(self, indexes):
+        """remove_data! (src/api.jl:449-468): delete the observations at `indexes` (0-based ascending positions of the resident series)
+        through the evaluator's engine, then re-score the block on the reduced series with unchanged parameters — the reference's
+        smc_step! after deleteat!.  The evaluator extends by default, so the factors remove_data updated are started from.  Returns
+        the statistics of the step (step(n_new, last=True): weights move, nothing is resampled)."""
+        engine = getattr(self.evaluate, "engine", None)
+        if engine is None or not hasattr(engine, "remove_data"):
+            raise RuntimeError("remove needs an evaluator with an engine (EngineEvaluator)")
+        n_new = engine.remove_data(indexes)
+        return self.step(int(n_new), last=True)
+
     def log_ml_estimate(self):
         """log_marginal_likelihood_estimate (Gen.log_ml_estimate; src/api.jl:130): log_ml_est + logsumexp(w) - log P."""
         lw = self.log_weights

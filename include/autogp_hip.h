@@ -128,6 +128,23 @@ int agp_extend_stats(agp_ctx* ctx, int64_t* out4);
 int agp_extend_stats2(agp_ctx* ctx, int64_t* out, int32_t n_out);
 /* forget every resident factor (release_memory != 0 also frees the store) */
 int agp_extend_reset(agp_ctx* ctx, int release_memory);
+
+/* remove_data! (src/api.jl:449-468): delete observations from the resident series and keep the resident factors.
+ * idx: k distinct positions (0-based, ascending) of the resident series, in the caller's order.  The survivors keep their order
+ * (deleteat!); the reduced series goes through agp_set_data's own grid / lattice detection and tables.  A resident factor of prefix
+ * n_f that contains removed positions is UPDATED on the device to the factor of the reduced prefix (n_f minus the removed positions
+ * below n_f; a rank-r update of the trailing triangle per contiguous run, csrc/agp_remove_kernel.hpp), or dropped where refactoring
+ * is cheaper (remove_admits, csrc/agp_host.hpp) — its key stays (program, parameters, noise), so agp_logpdf_batch_extend at the new
+ * n (the reference's smc_step! after the deletion) starts from it; factors on prefixes below idx[0] are untouched.  An updated
+ * factor agrees with a from-scratch one to rounding (1e-8 relative on the log-density), not to the bit; its resident L^-T is
+ * released.  A factor whose updated diagonal is not finite and positive is dropped (the next sweep reports the particle's info).
+ * AGP_ERR_ARG: k <= 0, positions unsorted, duplicate or out of range ("no such time points"); AGP_ERR_NODATA before agp_set_data.
+ * Under reference arithmetic nothing is resident: the call only edits the series. */
+int agp_remove_data(agp_ctx* ctx, const int64_t* idx, int64_t k);
+/* up to n_out <= 4 values since agp_init: factors updated, factors dropped, rows removed, panel steps run */
+int agp_get_remove_stats(agp_ctx* ctx, int64_t* out, int32_t n_out);
+/* env AGP_REMOVE_UPDATE [1]; 0 = agp_remove_data always drops the factors it touches */
+int agp_set_remove_update(agp_ctx* ctx, int32_t on);
 /* pre-size the store for series of up to n_cap observations and n_slots particles.  OPTIONAL: the store sizes itself — twice the
  * largest batch to begin with, and from there DRIVEN BY PRESSURE: it grows (keeping its contents, within its 45 % share of device
  * memory) rather than evict a factor that is still waiting for its first use — stored within the last 64 sweeps, nothing has started
@@ -552,6 +569,8 @@ int agp_comm_count(agp_ctx* ctx, int32_t* out_n_ranks);
  * (ncclCommInitAll).  out[i] is the context of device_ids[i] and rank i; destroy each with agp_destroy. */
 int agp_init_multi(agp_ctx** out /* n_dev */, const int32_t* device_ids, int32_t n_dev);
 int agp_set_data_multi(agp_ctx* const* ctxs, int32_t n_dev, const double* ts, const double* xs, int64_t n_max);
+/* agp_remove_data on every context */
+int agp_remove_data_multi(agp_ctx* const* ctxs, int32_t n_dev, const int64_t* idx, int64_t k);
 
 /* All-gather of the log-weight vector.  Host form: inout_lw has P entries, this rank's block [lo, hi) filled on
  * entry, all P filled on return (every rank calls it; n_ranks == 1 is a no-op).  Device form: d_local holds the
