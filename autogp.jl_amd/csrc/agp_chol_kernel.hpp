@@ -217,10 +217,35 @@ __device__ __forceinline__ void factor_diag_tile(const CholArgs& a, int p, int t
       }
     }
     if (w == 3 && l < 16) {
-      double t = 0.0;
+      // alpha_jb = W r_jb, then ONE step of refinement against the block itself: rho = r_jb - L(jb,jb) alpha, alpha += W rho.
+      // W r alone leaves |L alpha - r| at the roundings of W AND of the product (three roundings against a division's one at a
+      // 1 x 1 block: 1.9 gamma_1, tests/test_gpu_factor_probe.py); the corrected alpha has substitution's componentwise residual.
+      // (lanes 0 .. 15 of this wave hold the block's rows; values travel between them through v_readlane)
+      const double* Lb = sm + blk_idx(jb, jb) * 256;
+      double wr[16];
 #pragma unroll
-      for (int q = 0; q < 16; ++q) t = fma(Wl[q * 16 + l], rvec[jb * 16 + q], t);
-      avec[jb * 16 + l] = t;
+      for (int q = 0; q < 16; ++q) wr[q] = Wl[q * 16 + l];
+      double t0 = 0.0, t1 = 0.0;
+#pragma unroll
+      for (int q = 0; q < 16; q += 2) {
+        t0 = fma(wr[q], rvec[jb * 16 + q], t0);
+        t1 = fma(wr[q + 1], rvec[jb * 16 + q + 1], t1);
+      }
+      const double a0 = t0 + t1;
+      double r0 = rvec[jb * 16 + l], r1 = 0.0;
+#pragma unroll
+      for (int q = 0; q < 16; q += 2) {
+        r0 = fma(-Lb[q * 16 + l], readlane_d(a0, q), r0);
+        r1 = fma(-Lb[(q + 1) * 16 + l], readlane_d(a0, q + 1), r1);
+      }
+      const double rho = r0 + r1;
+      double c0 = 0.0, c1 = 0.0;
+#pragma unroll
+      for (int q = 0; q < 16; q += 2) {
+        c0 = fma(wr[q], readlane_d(rho, q), c0);
+        c1 = fma(wr[q + 1], readlane_d(rho, q + 1), c1);
+      }
+      avec[jb * 16 + l] = a0 + (c0 + c1);
     }
     __syncthreads();
     if (jb == 0) AGP_DPROBE(5);
@@ -1567,8 +1592,12 @@ __global__ void k_mfma_probe(const double* A, const double* B, double* D) {
 
 
 // element-wise probe of csrc/agp_math.hpp on the device: which = 0 exp_f, 1 sin2_f, 2 log_f, 3 pow_f(x, g); 4 the device
-// library's erfc (what k_mixture_quantile's normcdf calls), 5 sqrt (k_mixture_pack's sigma)
+// library's erfc (what k_mixture_quantile's normcdf calls), 5 sqrt (k_mixture_pack's sigma); 6 exp_t on an LDS copy of c_exp_tab,
+// staged as the covariance kernels stage it; 7 / 8 the sine / cosine output of sincos_pi_f
 __global__ void k_math_probe(int which, const double* x, const double* g, double* y, int n) {
+  __shared__ double etab[AGP_EXP_TAB_N];
+  if (threadIdx.x < AGP_EXP_TAB_N) etab[threadIdx.x] = fm::c_exp_tab[threadIdx.x];
+  __syncthreads();
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   double r;
@@ -1577,7 +1606,13 @@ __global__ void k_math_probe(int which, const double* x, const double* g, double
   else if (which == 2) r = fm::log_f(x[i]);
   else if (which == 3) r = fm::pow_f(x[i], g[i]);
   else if (which == 4) r = erfc(x[i]);
-  else r = __builtin_sqrt(x[i]);
+  else if (which == 5) r = __builtin_sqrt(x[i]);
+  else if (which == 6) r = fm::exp_t(x[i], etab);
+  else {
+    double sn, cs;
+    fm::sincos_pi_f(x[i], &sn, &cs);
+    r = which == 7 ? sn : cs;
+  }
   y[i] = r;
 }
 

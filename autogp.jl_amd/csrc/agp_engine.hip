@@ -475,11 +475,8 @@ hipError_t run_factor(hipStream_t st, CholArgs ca, int nfac, int dcov, Prof* pf,
   // Schur-mode update) and the remaining columns run right-looking, where every trailing tile is an independent
   // short update instead of a few long K-loops on a mostly idle GPU.
   int k_switch = nfac;
-  if (!right_looking && hybrid_blocks > 0 && dcov == 0 && nfac == ca.nt && !split_diag) {
-    for (int k = 1; k < nfac; ++k)
-      if ((long long)ca.P * (ca.nt - k) < hybrid_blocks) { k_switch = k; break; }
-    if (k_switch >= nfac - 1) k_switch = nfac;       // a single trailing column gains nothing
-  }
+  if (!right_looking && hybrid_blocks > 0 && dcov == 0 && nfac == ca.nt && !split_diag)
+    k_switch = hybrid_switch_column(ca.P, ca.nt, nfac, hybrid_blocks);
   for (int k = 0; k < nfac; ++k) {
     ca.k = k;
     if (k == k_switch) {

@@ -579,6 +579,16 @@ struct Prof;      // HIP-event marks of a profiled sweep (agp_engine.hip)
 hipError_t run_factor(hipStream_t st, CholArgs ca, int nfac, int dcov, Prof* pf, double* counts,
                       bool split_diag = false, bool right_looking = false, int hybrid_blocks = 0);
 
+// run_factor's hybrid rule: the block column from which a full factorisation (nfac = nt, resident tiles, mixed launches) goes on
+// right-looking — the first one that offers fewer than hybrid_blocks workgroups; nfac = it never switches.
+inline int hybrid_switch_column(int P, int nt, int nfac, int hybrid_blocks) {
+  int k_switch = nfac;
+  for (int k = 1; k < nfac; ++k)
+    if ((long long)P * (nt - k) < hybrid_blocks) { k_switch = k; break; }
+  if (k_switch >= nfac - 1) k_switch = nfac;       // a single trailing column gains nothing
+  return k_switch;
+}
+
 // Medium populations — more particles than the right-looking schedule serves, fewer than fill the GPU with the tiles
 // of one block column — take the dataflow schedule.
 // Measured on MI355X (tools/gpu_flow_perf.py, profiles/r02_flow_perf.txt): it beats the per-column launches (right-looking,

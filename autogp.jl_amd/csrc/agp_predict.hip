@@ -1304,6 +1304,76 @@ int agp_debug_cholesky(agp_ctx* c, const double* K, int64_t n, double* out_L, in
   return AGP_OK;
 }
 
+// Factor P caller-supplied matrices with ONE chosen schedule and hand back everything the diagonal tiles produce (see
+// include/autogp_hip.h).  The schedules are the sweeps' own host functions (run_factor, launch_joint_flow) and predicates
+// (use_flow, use_split_diag, use_right_looking, hybrid_switch_column): nothing of a schedule is restated here.
+int agp_debug_factor_batch(agp_ctx* c, const double* K, const double* y, int64_t n, int32_t P, int32_t schedule,
+                           double* out_L, double* out_beta, double* out_partial, int32_t* out_info) {
+  if (!c) return fail(nullptr, AGP_ERR_ARG, "null context");
+  if (n <= 0 || P <= 0 || !K || !out_L || !out_info) return fail(c, AGP_ERR_ARG, "bad arguments");
+  if (schedule < -1 || schedule > 4) return fail(c, AGP_ERR_ARG, "unknown schedule (-1 .. 4)");
+  if (n > 8192 || (int64_t)P * n * n > ((int64_t)1 << 28)) return fail(c, AGP_ERR_ARG, "debug probe: batch too large");
+  HIPCHK(c, hipSetDevice(c->device));
+  const int n_pad = round_up(n, NB), nt = n_pad / NB, ntiles = nt * (nt + 1) / 2;
+  if (schedule == 3 && hybrid_switch_column(P, nt, nt, HYBRID_BLOCKS) >= nt)
+    return fail(c, AGP_ERR_ARG, "hybrid schedule: no switch column for this (P, nt); it would run the mixed launches throughout");
+  SlotGuard sg(c);
+  Slot* s = sg.s;
+  if (!s->stream) HIPCHK(c, hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
+  hipStream_t st = s->stream;
+  const long long strideA = (long long)ntiles * NB2;
+  const long long nel = (long long)n * n;
+  const int wsteps = nt;      // every block column keeps its inverse blocks, as in the sweeps with the dataflow schedule admitted
+  HIPCHK(c, s->A.ensure(sizeof(double) * (size_t)strideA * P));
+  HIPCHK(c, s->W.ensure(sizeof(double) * NSB * 256 * (size_t)P * wsteps));
+  HIPCHK(c, s->vec.ensure(sizeof(double) * (size_t)n_pad * P));
+  HIPCHK(c, s->partial.ensure(sizeof(double) * 2 * (size_t)nt * P));
+  HIPCHK(c, s->info.ensure(sizeof(int) * (size_t)P));
+  HIPCHK(c, s->ready.ensure(sizeof(int) * (size_t)P));
+  HIPCHK(c, s->dense.ensure(sizeof(double) * (size_t)nel * P));
+  HIPCHK(c, hipMemcpyAsync(s->dense.p, K, sizeof(double) * nel * P, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemsetAsync(s->vec.p, 0, sizeof(double) * (size_t)n_pad * P, st));
+  if (y)
+    HIPCHK(c, hipMemcpy2DAsync(s->vec.p, sizeof(double) * n_pad, y, sizeof(double) * n, sizeof(double) * n, P, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemsetAsync(s->info.p, 0, sizeof(int) * (size_t)P, st));
+  HIPCHK(c, hipMemsetAsync(s->ready.p, 0, sizeof(int) * (size_t)P, st));
+  for (int p = 0; p < P; ++p)
+    launch_pack_dense(st, s->dense.as<double>() + (size_t)p * nel, (int)n, nt, strideA, s->A.as<double>() + (size_t)p * strideA);
+  HIPCHK(c, hipGetLastError());
+  CholArgs ca = {};
+  ca.A = s->A.as<double>(); ca.strideA = strideA; ca.W = s->W.as<double>(); ca.wsteps = wsteps; ca.vec = s->vec.as<double>();
+  ca.ldv = n_pad; ca.partial = s->partial.as<double>(); ca.info = s->info.as<int>(); ca.P = P; ca.nt = nt;
+  ca.k = 0; ca.nt1 = nt; ca.ready = s->ready.as<int>();      // (n1 = 0: dense input, the padding is factored like data; n_fused = 0)
+  bool flow = schedule == 4, split = schedule == 1, rl = schedule == 2;
+  int hybrid = schedule == 3 ? HYBRID_BLOCKS : 0;
+  if (schedule < 0) {      // logpdf_batch_impl's choice for a batch without resident factors
+    flow = use_flow(c, P, nt); split = use_split_diag(c, P); rl = use_right_looking(c, P); hybrid = HYBRID_BLOCKS;
+  }
+  if (flow) {
+    int rc = launch_joint_flow(c, s, st, ca, 0, wsteps);
+    if (rc) return rc;
+  } else {
+    HIPCHK(c, run_factor(st, ca, nt, 0, nullptr, nullptr, split, rl, hybrid));
+  }
+  for (int p = 0; p < P; ++p)
+    launch_unpack_dense(st, s->A.as<double>() + (size_t)p * strideA, (int)n, 1, s->dense.as<double>() + (size_t)p * nel);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(out_L, s->dense.p, sizeof(double) * nel * P, hipMemcpyDeviceToHost, st));
+  if (out_beta)
+    HIPCHK(c, hipMemcpy2DAsync(out_beta, sizeof(double) * n, s->vec.p, sizeof(double) * n_pad, sizeof(double) * n, P, hipMemcpyDeviceToHost, st));
+  std::vector<double> part((size_t)2 * nt * P);
+  HIPCHK(c, hipMemcpyAsync(part.data(), s->partial.p, sizeof(double) * part.size(), hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(out_info, s->info.p, sizeof(int) * (size_t)P, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  if (out_partial)
+    for (int p = 0; p < P; ++p) {      // block columns in k_finish_logpdf's order
+      double ld = 0.0, ss = 0.0;
+      for (int k = 0; k < nt; ++k) { ld += part[((size_t)p * nt + k) * 2]; ss += part[((size_t)p * nt + k) * 2 + 1]; }
+      out_partial[2 * p] = ld; out_partial[2 * p + 1] = ss;
+    }
+  return AGP_OK;
+}
+
 int agp_debug_mfma_peak(agp_ctx* c, int32_t iters, int32_t wg_per_cu, double* out_tflops, double* out_ghz) {
   if (!c || !out_tflops || !out_ghz) return fail(c, AGP_ERR_ARG, "null pointer");
   HIPCHK(c, hipSetDevice(c->device));
@@ -1470,7 +1540,7 @@ int agp_debug_flow_trace(agp_ctx* c, int32_t enable, int64_t max_items, int64_t*
 #endif  // AGP_EXPERIMENTS
 
 int agp_debug_math(agp_ctx* c, int32_t which, const double* x, const double* g, double* y, int32_t n) {
-  if (!c || !x || !y || n <= 0 || which < 0 || which > 5 || (which == 3 && !g)) return fail(c, AGP_ERR_ARG, "bad arguments");
+  if (!c || !x || !y || n <= 0 || which < 0 || which > 8 || (which == 3 && !g)) return fail(c, AGP_ERR_ARG, "bad arguments");
   HIPCHK(c, hipSetDevice(c->device));
   double *dx = nullptr, *dg = nullptr, *dy = nullptr;
   HIPCHK(c, malloc_values(c->poison, (void**)&dx, sizeof(double) * n));

@@ -36,6 +36,7 @@ EXPORTED_SYMBOLS = [
     "agp_mixture_quantile", "agp_predict_quantile_batch", "agp_infer_gp_sum_batch", "agp_predict_sum_batch",
     "agp_predict_sample_batch",
     "agp_remove_data", "agp_get_remove_stats", "agp_set_remove_update", "agp_remove_data_multi",
+    "agp_debug_factor_batch",
 ]
 COMM_ID_BYTES = 128
 
@@ -128,6 +129,7 @@ def load_library(path=None):
     lib.agp_cov_matrix.argtypes = [vp, dp, C.c_int64, u8p, C.c_int32, dp, C.c_int32, C.c_double, dp]
     lib.agp_cov_matrix.restype = C.c_int
     lib.agp_debug_cholesky.argtypes = [vp, dp, C.c_int64, dp, ip]; lib.agp_debug_cholesky.restype = C.c_int
+    lib.agp_debug_factor_batch.argtypes = [vp, dp, dp, C.c_int64, C.c_int32, C.c_int32, dp, dp, dp, ip]; lib.agp_debug_factor_batch.restype = C.c_int
     lib.agp_debug_mfma_probe.argtypes = [vp, dp, dp, dp]; lib.agp_debug_mfma_probe.restype = C.c_int
     lib.agp_debug_mfma_peak.argtypes = [vp, C.c_int32, C.c_int32, dp, dp]; lib.agp_debug_mfma_peak.restype = C.c_int
     lib.agp_debug_math.argtypes = [vp, C.c_int32, dp, dp, dp, C.c_int32]; lib.agp_debug_math.restype = C.c_int
@@ -742,6 +744,25 @@ class GPEngine:
         L = np.empty((n, n), dtype=np.float64, order="F"); info = C.c_int32()
         self._check(self._lib.agp_debug_cholesky(self._ctx, _dp(K), n, _dp(L), C.byref(info)))
         return np.asarray(L), info.value
+
+    def debug_factor_batch(self, K, y=None, schedule=-1):
+        """Factor the symmetric matrices K (P, n, n) with one schedule of the batched Cholesky (agp_debug_factor_batch: 0 mixed
+        per-column launches, 1 split, 2 right-looking, 3 hybrid, 4 dataflow, -1 logpdf_batch's choice) -> L (P, n, n) lower,
+        beta = L^-1 y (P, n), partial (P, 2) = [log det, beta'beta], info (P)."""
+        K = np.ascontiguousarray(K, dtype=np.float64)
+        if K.ndim != 3 or K.shape[1] != K.shape[2]:
+            raise ValueError("K must have shape (P, n, n)")
+        P, n = K.shape[0], K.shape[1]
+        if y is not None:
+            y = np.ascontiguousarray(y, dtype=np.float64)
+            if y.shape != (P, n):
+                raise ValueError("y must have shape (P, n)")
+        Lt = np.empty((P, n, n), dtype=np.float64); beta = np.empty((P, n), dtype=np.float64)
+        part = np.empty((P, 2), dtype=np.float64); info = np.zeros(P, dtype=np.int32)
+        self._check(self._lib.agp_debug_factor_batch(self._ctx, _dp(K), _dp(y), n, P, int(schedule), _dp(Lt), _dp(beta), _dp(part),
+                                                     _ip(info)))
+        # (column-major blocks: the transpose of each block is the row-major lower factor)
+        return np.ascontiguousarray(Lt.transpose(0, 2, 1)), beta, part, info
 
     def debug_mfma_probe(self, A, B):
         A = _f64(A).reshape(16, 4); B = _f64(B).reshape(4, 16); D = np.empty((16, 16))

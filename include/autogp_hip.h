@@ -624,12 +624,35 @@ int agp_predict_batch_multi(agp_ctx* const* ctxs, int32_t n_dev, int64_t n, cons
  * out_L receives the lower factor (n x n column-major, upper part zero). */
 int agp_debug_cholesky(agp_ctx* ctx, const double* K, int64_t n, double* out_L, int32_t* out_info);
 
+/* Factor P caller-supplied matrices (K: P blocks of n x n) with ONE chosen schedule of the batched Cholesky and return what the
+ * diagonal tiles produce.  The tiles are packed from K (prebuilt tiles: no covariance is evaluated), the forward-solve vector is
+ * seeded with y (P x n; NULL: zeros) and the factorisation runs through the host functions the sweeps call:
+ *   schedule  0  one mixed launch per block column (diagonal + sub-diagonal tiles)
+ *             1  split: diagonal-tile launch + sub-diagonal launch per block column
+ *             2  right-looking: diagonal tile, panel solve, update of every trailing tile, per block column
+ *             3  hybrid: mixed launches, then one catch-up launch and right-looking columns (AGP_ERR_ARG when the rule finds no
+ *                switch column for (P, nt = ceil(n / 128)): nt < 3, or P (nt - 1) >= 512)
+ *             4  the dataflow schedule (one launch of persistent workgroups)
+ *            -1  what agp_logpdf_batch takes for (P, nt) under the context's settings (AGP_FLOW, AGP_SPLIT_DIAG, ...)
+ * A schedule is never replaced by another one.  K must be symmetric, every entry given: element (r, c) of a block is read at
+ * K[c * n + r] for r >= c (the lower triangle of a column-major matrix = the upper triangle of a row-major one); the diagonal
+ * 128 x 128 tiles are packed with both triangles, and which of the two a schedule's diagonal kernel reads is its own business.
+ * out_L: P x n x n, the lower factors (column-major, zero above the diagonal); out_beta (P x n, nullable): L^-1 y;
+ * out_partial (P x 2, nullable): log det K = 2 sum log L_ii and beta' beta, the block columns' partials added in
+ * agp_logpdf_batch's order; out_info (P): LAPACK info per matrix (0, or the 1-based index of the first non-positive pivot, whose
+ * outputs are then meaningless).  A failed matrix leaves the others' outputs untouched, bit for bit. */
+int agp_debug_factor_batch(agp_ctx* ctx, const double* K /* P*n*n */, const double* y /* P*n or NULL */,
+                           int64_t n, int32_t P, int32_t schedule,
+                           double* out_L /* P*n*n, lower */, double* out_beta /* P*n or NULL */,
+                           double* out_partial /* P*2: logdet, beta'beta; or NULL */, int32_t* out_info /* P */);
+
 /* Probe of the fp64 MFMA fragment layout: D = A(16x4) * B(4x16), row-major host arrays. */
 int agp_debug_mfma_probe(agp_ctx* ctx, const double* A, const double* B, double* D);
 
 /* Element-wise probe of the device math used by the covariance kernels (csrc/agp_math.hpp):
  * which = 0 exp, 1 sin^2, 2 log, 3 pow(x, g), 4 erfc (the device library's, as the mixture-quantile kernel calls it),
- * 5 sqrt (the mixture-quantile kernels' sigma). */
+ * 5 sqrt (the mixture-quantile kernels' sigma), 6 exp through the 128-entry table (exp_t, read from a copy in LDS as the
+ * covariance kernels do), 7 / 8 the sine / cosine of sincos_pi_f. */
 int agp_debug_math(agp_ctx* ctx, int32_t which, const double* x, const double* g, double* y, int32_t n);
 
 /* fp64 MFMA issue-rate microbenchmark (16 independent accumulators per wave, wg_per_cu

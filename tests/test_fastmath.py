@@ -1,35 +1,17 @@
 """CPU validation of csrc/agp_math.hpp (the fp64 exp / sin^2 / pow used by the covariance kernels):
 the header is host+device, so it is compiled here with g++ and checked against mpmath."""
 import ctypes
-import subprocess
-from pathlib import Path
 
 import mpmath as mp
 import numpy as np
 import pytest
 
-ROOT = Path(__file__).resolve().parent.parent
-SRC = r'''
-#include "agp_math.hpp"
-extern "C" {
-void v_exp(const double* x, double* y, int n) { for (int i = 0; i < n; ++i) y[i] = agp::fm::exp_f(x[i]); }
-void v_exp_t(const double* x, double* y, int n) { for (int i = 0; i < n; ++i) y[i] = agp::fm::exp_t(x[i], agp::fm::EXP_TAB); }
-void v_sin2(const double* x, double* y, int n) { for (int i = 0; i < n; ++i) y[i] = agp::fm::sin2_f(x[i]); }
-void v_sincos(const double* x, double* y, int n) { for (int i = 0; i < n; ++i) agp::fm::sincos_pi_f(x[i], y + 2 * i, y + 2 * i + 1); }
-void v_log(const double* x, double* y, int n) { for (int i = 0; i < n; ++i) y[i] = agp::fm::log_f(x[i]); }
-void v_pow(const double* x, const double* g, double* y, int n) { for (int i = 0; i < n; ++i) y[i] = agp::fm::pow_f(x[i], g[i]); }
-}
-'''
+import _fastmath_cases as CASES
 
 
 @pytest.fixture(scope="module")
 def lib(tmp_path_factory):
-    d = tmp_path_factory.mktemp("fm")
-    (d / "fm.cpp").write_text(SRC)
-    so = d / "libfm.so"
-    subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-I", str(ROOT / "autogp.jl_amd" / "csrc"),
-                    "-o", str(so), str(d / "fm.cpp")], check=True)
-    return ctypes.CDLL(str(so))
+    return CASES.build_host_lib(tmp_path_factory.mktemp("fm"))
 
 
 def call1(fn, x):
@@ -47,9 +29,7 @@ def ulps(got, ref):
 
 def test_exp(lib):
     mp.mp.dps = 40
-    rng = np.random.default_rng(0)
-    x = np.concatenate([-rng.random(1500) * 50, -np.exp(rng.uniform(-40, 6.5, 1500)), rng.random(500) * 12,
-                        [0.0, -1e-300, -700.0, -1e-17, 11.5]])
+    x = CASES.exp_inputs()
     u = ulps(call1(lib.v_exp, x), [mp.exp(mp.mpf(float(v))) for v in x])
     assert u.max() < 1.6, u.max()
     assert call1(lib.v_exp, np.array([-746.0, -1000.0, -1e9]))[0:3].tolist() == [0.0, 0.0, 0.0]
@@ -61,10 +41,7 @@ def test_exp_table(lib):
     """exp_t (128-entry table of 2^(j/128) + degree-5 polynomial: the version the covariance evaluation uses on the device):
     same accuracy class as exp_f on the same domain, same underflow behaviour; the table itself is correctly rounded."""
     mp.mp.dps = 40
-    rng = np.random.default_rng(1)
-    x = np.concatenate([-rng.random(3000) * 50, -np.exp(rng.uniform(-40, 6.5, 3000)), rng.random(800) * 12,
-                        np.arange(-1280, 1281) * (np.log(2) / 256),          # ties of the table index
-                        [0.0, -1e-300, -700.0, -1e-17, 11.5, 700.0]])
+    x = CASES.exp_table_inputs()
     u = ulps(call1(lib.v_exp_t, x), [mp.exp(mp.mpf(float(v))) for v in x])
     assert u.max() < 1.6, u.max()
     assert call1(lib.v_exp_t, np.array([-746.0, -1000.0, -1e9]))[0:3].tolist() == [0.0, 0.0, 0.0]
@@ -78,8 +55,7 @@ def test_exp_table(lib):
 
 def test_sin2(lib):
     mp.mp.dps = 60
-    rng = np.random.default_rng(1)
-    x = np.concatenate([rng.random(2000) * 4, rng.random(2000) * 700, rng.random(500) * 1e5, [0.0, 1e-9, np.pi, np.pi / 2]])
+    x = CASES.sin2_inputs()
     got = call1(lib.v_sin2, x)
     ref = [mp.sin(mp.mpf(float(v))) ** 2 for v in x]
     # near multiples of pi the value is ~0 and only absolute accuracy (relative to 1) is meaningful
@@ -92,8 +68,7 @@ def test_sin2(lib):
 def test_sincos_pi(lib):
     """sin(x)^2 = s^2 and sin(x) cos(x) = s c after the reduction by pi (Periodic-kernel derivatives)."""
     mp.mp.dps = 60
-    rng = np.random.default_rng(5)
-    x = np.concatenate([rng.random(2000) * 4, rng.random(2000) * 700, rng.random(500) * 1e5, [0.0, 1e-9, np.pi, np.pi / 2]])
+    x = CASES.sincos_inputs()
     y = np.empty(2 * x.size)
     lib.v_sincos(x.ctypes.data_as(ctypes.c_void_p), y.ctypes.data_as(ctypes.c_void_p), ctypes.c_int(x.size))
     s, c = y[0::2], y[1::2]
@@ -105,12 +80,10 @@ def test_sincos_pi(lib):
 
 def test_log_pow(lib):
     mp.mp.dps = 40
-    rng = np.random.default_rng(2)
-    x = np.concatenate([np.exp(rng.uniform(-30, 8, 3000)), [1.0, 0.5, 2.0, 1e-310, 5e-324, 1.4142135623730951, 0.7071067811865476]])
+    x, uu, gg = CASES.log_pow_inputs()
     u = ulps(call1(lib.v_log, x), [mp.log(mp.mpf(float(v))) for v in x])
     assert u[np.abs(x - 1.0) > 1e-3].max() < 1.1
     # pow on the kernels' domain: u = |dx|/l in (0, ~200], gamma in (0, 2]
-    uu = np.exp(rng.uniform(-25, 5.3, 4000)); gg = 2.0 / (1.0 + np.exp(-rng.standard_normal(4000)))
     got = np.empty_like(uu)
     lib.v_pow(uu.ctypes.data_as(ctypes.c_void_p), gg.ctypes.data_as(ctypes.c_void_p), got.ctypes.data_as(ctypes.c_void_p),
               ctypes.c_int(uu.size))
