@@ -205,6 +205,26 @@ struct SampleReadArgs {
   double* out;             // [S][m]
 };
 
+// mixture moments (agp_mixmom_kernel.hpp): one chunk of components in the pass's order, and the running sums about the pivot
+struct MixMomArgs {
+  const double* mean;      // [Pc][m] component means (the predictive's scaled space)
+  const double* var;       // component p's variance at point i: var[p * v_pstride + i * v_istride] ([Pc][m], or the diagonals of cov)
+  long long v_pstride, v_istride;
+  const double* cov;       // [Pc][m*m] column-major symmetric, or null (marginal pass)
+  const double* w;         // [Pc] weights
+  int m, Pc, space;        // space 0: normal components, 1: MvLogNormal(N(mu_r, C_r))
+  int pivot;               // >= 0: this chunk starts the sums, about the component mean of its particle `pivot`; < 0: it continues them
+  double slope, intercept, ivar;      // mu_r = (mu - intercept) / slope, C_r = ivar * C (ivar = 1 / slope^2)
+  double* e;               // [Pc][m] the components' means in the output space (k_mixmom_marginal writes, k_mixmom_cov reads)
+  double* s;               // [m] pivot
+  double* s1;              // [m] S1 = sum w (e - s)
+  double* s2d;             // [m] diagonal of S2 (marginal pass)
+  double* acc;             // [m*m] lower triangle of S2 = sum w (C + (e - s)(e - s)'), column-major
+  double* out_mean;        // [m]
+  double* out_var;         // [m]
+  double* out_cov;         // [m*m] or null
+};
+
 struct GradArgs {
   const double* A;       // packed lower tiles of L
   double* Z;             // packed buffer holding Z(r,k), r <= k, in the slot of lower tile (k,r)

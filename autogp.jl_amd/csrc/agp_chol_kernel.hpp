@@ -1593,7 +1593,8 @@ __global__ void k_mfma_probe(const double* A, const double* B, double* D) {
 
 // element-wise probe of csrc/agp_math.hpp on the device: which = 0 exp_f, 1 sin2_f, 2 log_f, 3 pow_f(x, g); 4 the device
 // library's erfc (what k_mixture_quantile's normcdf calls), 5 sqrt (k_mixture_pack's sigma); 6 exp_t on an LDS copy of c_exp_tab,
-// staged as the covariance kernels stage it; 7 / 8 the sine / cosine output of sincos_pi_f
+// staged as the covariance kernels stage it; 7 / 8 the sine / cosine output of sincos_pi_f; 9 the device library's expm1 (what the
+// log-normal components of k_mixmom_marginal / k_mixmom_cov call)
 __global__ void k_math_probe(int which, const double* x, const double* g, double* y, int n) {
   __shared__ double etab[AGP_EXP_TAB_N];
   if (threadIdx.x < AGP_EXP_TAB_N) etab[threadIdx.x] = fm::c_exp_tab[threadIdx.x];
@@ -1608,6 +1609,7 @@ __global__ void k_math_probe(int which, const double* x, const double* g, double
   else if (which == 4) r = erfc(x[i]);
   else if (which == 5) r = __builtin_sqrt(x[i]);
   else if (which == 6) r = fm::exp_t(x[i], etab);
+  else if (which == 9) r = expm1(x[i]);
   else {
     double sn, cs;
     fm::sincos_pi_f(x[i], &sn, &cs);

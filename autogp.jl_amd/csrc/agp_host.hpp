@@ -172,7 +172,8 @@ struct Slot {
       noise{Fill::values}, noise_pred{Fill::values}, mu1{Fill::values}, mu2{Fill::values}, pred_mean{Fill::values},
       pred_var{Fill::values}, pred_cov{Fill::values}, dense{Fill::values}, diag_add{Fill::values}, Z{Fill::values},
       alpha{Fill::values}, tsol{Fill::values}, gpart{Fill::values}, dgrad{Fill::values}, dgnoise{Fill::values}, lagtab{Fill::values},
-      sum_x{Fill::values}, sum_z{Fill::values}, smp_z{Fill::values}, smp_x{Fill::values}, smp_zin{Fill::values};
+      sum_x{Fill::values}, sum_z{Fill::values}, smp_z{Fill::values}, smp_x{Fill::values}, smp_zin{Fill::values},
+      mix_w{Fill::values}, mix_e{Fill::values}, mix_s{Fill::values}, mix_acc{Fill::values}, mix_out{Fill::values};
   // addresses, indices, counts, programs (their parameters included: uploaded whole), times, flags
   DevBuf info{Fill::never}, out_info{Fill::never}, hdr{Fill::never}, ops{Fill::never}, prm{Fill::never}, tt{Fill::never}, map{Fill::never},
       ready{Fill::never}, code{Fill::never}, tretry{Fill::never}, ghdr{Fill::never}, gops{Fill::never}, glc{Fill::never},
@@ -181,7 +182,7 @@ struct Slot {
   template <class F> void for_each_dev(F&& f) {
     for (DevBuf* b : {&stage, &up_blob, &up_blob2, &A, &W, &vec, &partial, &out_lp, &out_info, &noise, &noise_pred, &mu1, &mu2,
                       &pred_mean, &pred_var, &pred_cov, &dense, &diag_add, &Z, &alpha, &tsol, &gpart, &dgrad, &dgnoise, &lagtab, &sum_x, &sum_z,
-                      &smp_z, &smp_x, &smp_zin, &smp_idx, &info, &hdr, &ops, &prm, &tt, &map, &ready, &code, &tretry, &ghdr, &gops, &glc, &grc, &gpoff, &gprm, &gmap,
+                      &smp_z, &smp_x, &smp_zin, &mix_w, &mix_e, &mix_s, &mix_acc, &mix_out, &smp_idx, &info, &hdr, &ops, &prm, &tt, &map, &ready, &code, &tretry, &ghdr, &gops, &glc, &grc, &gpoff, &gprm, &gmap,
                       &goff, &plist, &tflag, &flowq, &pl_rank, &pl_tl, &pl_prog})
       f(*b);
   }
@@ -263,6 +264,7 @@ struct agp_ctx {
   int predict_reuse = 1;   // 1: predictive passes take L11 / alpha of a particle from the factor store when it holds them; env AGP_PREDICT_REUSE
   int dedup = 1;        // evaluate identical particles of a host-output sweep once; env AGP_DEDUP
   int64_t n_particles_seen = 0, n_particles_run = 0;
+  int64_t n_mix_passes = 0, n_mix_chunks = 0;      // (agp_get_mixture_stats)
   int split_diag = -1;  // diagonal tiles in their own specialised launch: -1 auto (when they fill the GPU), 0, 1; env AGP_SPLIT_DIAG
   int ge_table = 1;     // GammaExp leaves read log|dt| from a table built by agp_set_data (env AGP_GE_TABLE)
   // Sorted regular grid (agp_set_data): when the resident time points, put in ascending order, are equally spaced, value
@@ -724,6 +726,37 @@ int predict_joint_batch(agp_ctx* c, int64_t n, const double* ts_pred, const doub
                         const int32_t* op_off, const uint8_t* ops, const int32_t* prm_off, const double* prm,
                         const double* noise, const double* noise_pred, const double* mean_train, const double* mean_pred,
                         double* out_logpdf, int32_t* out_info, JointHooks* hooks);
+
+// Mixture moments over the chunks of a pass (agp_mixmom.hip; kernels: agp_mixmom_kernel.hpp).  The caller fills the first block; the
+// pass calls mix_stage before its uploads go out, mix_chunk per chunk of its particle order (while the chunk's device means and
+// variances / covariances are live) and mix_finish once: the slot then holds [mean | var | cov] in mix_out, copied to the outputs.
+struct MixPass {
+  int space = 0;
+  double slope = 1.0, intercept = 0.0;
+  bool cov = false;                      // the m x m covariance is wanted (else mean and var only)
+  std::vector<double> w;                 // weights of the pass's particles, in ITS caller's order (predict_core: before sorting)
+  double* out_mean = nullptr; double* out_var = nullptr; double* out_cov = nullptr;      // host: m, m, m*m
+  // the pass's state
+  int64_t m = 0;
+  int q_first = 0;                       // first position of the pass's order with a positive weight: its mean is the pivot
+  bool started = false;
+  bool profiling = false;                // the context's flag when the pass began
+  int n_chunks = 0;                      // chunks the running sums took in
+  std::vector<double> w_pass;            // weights in the pass's order
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;      // (profiling) [0]: the whole pass, then one pair per accumulated chunk
+  ~MixPass() { for (auto& e : ev) { if (e.first) (void)hipEventDestroy(e.first); if (e.second) (void)hipEventDestroy(e.second); } }
+};
+int mix_stage(agp_ctx* c, Slot* s, hipStream_t st, PinnedUploads& up, MixPass& mp, int64_t m, const std::vector<double>& w_pass);
+// positions [p0, p0 + Pc) of the pass: d_mean [Pc][m]; d_var [Pc][m] (d_cov null) or d_cov [Pc][m*m] (variances: its diagonals)
+int mix_chunk(agp_ctx* c, Slot* s, hipStream_t st, MixPass& mp, int p0, int Pc, const double* d_mean, const double* d_var,
+              const double* d_cov);
+int mix_finish(agp_ctx* c, Slot* s, hipStream_t st, MixPass& mp);
+// agp_predict_mixture_batch's covariance pass (agp_predict.hip): agp_predict_batch's dense pass with want_cov, the per-particle
+// covariances reduced by `mp` on the device instead of copied out.  weights: per caller particle (copies are added onto their
+// representative); out_info per caller particle.
+int predict_mixture_cov(agp_ctx* c, int64_t n, const double* ts_pred, int64_t m, int32_t P, const int32_t* op_off, const uint8_t* ops,
+                        const int32_t* prm_off, const double* prm, const double* noise, const double* noise_pred,
+                        const double* mean_train, const double* mean_pred, const double* weights, MixPass& mp, int32_t* out_info);
 
 // the mixture weights of agp_predict_quantile_batch / agp_predict_sample_batch (agp_quantile.hip): finite, >= 0, summing to 1
 int check_weights(agp_ctx* c, int32_t P, const double* w);

@@ -7,6 +7,7 @@
 #include "agp_quantile_kernel.hpp"
 #include "agp_sum_kernel.hpp"
 #include "agp_sample_kernel.hpp"
+#include "agp_mixmom_kernel.hpp"
 #include "agp_comm.hpp"
 
 namespace agp {
@@ -179,6 +180,21 @@ void launch_philox_normals(hipStream_t st, const SampleNormArgs& a) {
 }
 void launch_pred_sample(hipStream_t st, int n_groups, int nt2, const SampleReadArgs& a) {
   hipLaunchKernelGGL(k_pred_sample, dim3((unsigned)n_groups, (unsigned)nt2), dim3(256), 0, st, a);
+}
+void launch_mixmom_chunk(hipStream_t st, const MixMomArgs& a) {
+  if (a.m <= 0 || a.Pc <= 0) return;
+  hipLaunchKernelGGL(k_mixmom_marginal, dim3((unsigned)((a.m + 255) / 256)), dim3(256), 0, st, a);
+  if (a.cov)
+    hipLaunchKernelGGL(k_mixmom_cov, dim3((unsigned)((a.m + MIXMOM_TI - 1) / MIXMOM_TI), (unsigned)((a.m + MIXMOM_TJ - 1) / MIXMOM_TJ)),
+                       dim3(MIXMOM_TI, MIXMOM_TJ), 0, st, a);
+}
+void launch_mixmom_finish(hipStream_t st, const MixMomArgs& a) {
+  if (a.m <= 0) return;
+  if (a.out_cov)
+    hipLaunchKernelGGL(k_mixmom_finish_cov, dim3((unsigned)((a.m + MIXMOM_TI - 1) / MIXMOM_TI), (unsigned)((a.m + MIXMOM_TJ - 1) / MIXMOM_TJ)),
+                       dim3(MIXMOM_TI, MIXMOM_TJ), 0, st, a);
+  else
+    hipLaunchKernelGGL(k_mixmom_finish_marginal, dim3((unsigned)((a.m + 255) / 256)), dim3(256), 0, st, a);
 }
 void launch_mfma_peak(int nblk, double* out, long long* cycles, int iters, int mode) {
   hipLaunchKernelGGL(k_mfma_peak, dim3(nblk), dim3(256), 0, 0, out, cycles, iters, mode);

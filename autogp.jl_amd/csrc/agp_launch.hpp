@@ -55,6 +55,10 @@ void launch_sum_readout(hipStream_t st, int P, const SumReadArgs& a);
 // SMP_G samples of one particle, query tile row)
 void launch_philox_normals(hipStream_t st, const SampleNormArgs& a);
 void launch_pred_sample(hipStream_t st, int n_groups, int nt2, const SampleReadArgs& a);
+// mixture moments (agp_mixmom.hip): one chunk of components onto the running sums (a.cov null: S1 and the diagonal only), then the
+// finish (a.out_cov null: the marginal one)
+void launch_mixmom_chunk(hipStream_t st, const MixMomArgs& a);
+void launch_mixmom_finish(hipStream_t st, const MixMomArgs& a);
 
 // ---- agp_kernels_grad.hip --------------------------------------------------------------------------------------------
 hipError_t kernels_init_grad();

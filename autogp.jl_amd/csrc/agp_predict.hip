@@ -186,9 +186,12 @@ int predict_core(agp_ctx* c, int64_t n, const double* ts_pred, int64_t m, int32_
                  const double* noise, const double* noise_pred, const uint8_t* pred_code, const double* diag_add,
                  const double* mean_train, const double* mean_pred, double* out_mean, double* out_var,
                  double* out_cov, int32_t* out_info, const std::vector<std::string>* keys = nullptr,
-                 const PredLattice* pl = nullptr, const SumPass* sum = nullptr) {
+                 const PredLattice* pl = nullptr, const SumPass* sum = nullptr, MixPass* mix = nullptr) {
   const int n1_pad = round_up(n, NB);           // 0 when n == 0
   const bool lagr = pl != nullptr && pl->on;
+  // `mix` (nullable; agp_predict_mixture_batch): the chunk's device means and covariances go into the mixture's running sums
+  // (mix_chunk) instead of out_cov — the pass forms every particle's covariance (want_cov) and copies none of them out
+  const bool want_cov = out_cov != nullptr || (mix && mix->cov);
   // ---- query points that ARE training points, no covariance requested ----------------------------------------------
   // For t*_j == t_i the cross-covariance row is K21[j,:] = K11[i,:] - noise e_i^T (src/GP.jl:743-747 evaluates the kernel
   // on the joint list; the noise sits on K11's diagonal only), so with alpha = K11^-1 (y - mu1):
@@ -197,7 +200,7 @@ int predict_core(agp_ctx* c, int64_t n, const double* ts_pred, int64_t m, int32_
   // joint path spends n^2 flops PER SUCH POINT on V = L^-1 K12 (the reference's query set is train + test + future,
   // scripts/online.jl:41-43: n of its points are of this kind).  The other query points take the joint path below.
   std::vector<int32_t> dq, di, fq;      // duplicates: position in ts_pred, training index; the remaining queries
-  split_queries(c, n, ts_pred, m, !out_cov && !pred_code && !c->ref_arith, dq, di, fq);
+  split_queries(c, n, ts_pred, m, !want_cov && !pred_code && !c->ref_arith, dq, di, fq);
   const bool diag_path = !dq.empty();
   const int64_t mJ = diag_path ? (int64_t)fq.size() : m;      // query points of the joint matrix
   std::vector<double> tsF, meanF, daddF;
@@ -242,7 +245,7 @@ int predict_core(agp_ctx* c, int64_t n, const double* ts_pred, int64_t m, int32_
   HIPCHK(c, s->W.ensure(sizeof(double) * NSB * 256 * (size_t)chunk * std::max(1, nt1)));     // (the dataflow schedule keeps every column's inverse blocks)
   HIPCHK(c, s->pred_mean.ensure(sizeof(double) * (size_t)std::max<int64_t>(1, mJ) * chunk));
   HIPCHK(c, s->pred_var.ensure(sizeof(double) * (size_t)std::max<int64_t>(1, mJ) * chunk));
-  if (out_cov) HIPCHK(c, s->pred_cov.ensure(sizeof(double) * (size_t)m * m * chunk));
+  if (want_cov) HIPCHK(c, s->pred_cov.ensure(sizeof(double) * (size_t)m * m * chunk));
   const bool ro = sum && sum->readout;
   const int nq = ro ? (int)sum->z.size() : 0;
   if (ro) {
@@ -264,6 +267,11 @@ int predict_core(agp_ctx* c, int64_t n, const double* ts_pred, int64_t m, int32_
     up.add(s->diag_add.p, daddJ, sizeof(double) * mJ);
   }
   if (nq > 0) up.add(s->sum_z.p, sum->z.data(), sizeof(double) * nq);
+  if (mix) {
+    std::vector<double> w_pass((size_t)P);
+    for (int q = 0; q < P; ++q) w_pass[(size_t)q] = mix->w[(size_t)bt.order[q]];
+    if (const int rc = mix_stage(c, s, st, up, *mix, m, w_pass)) return rc;
+  }
 
   const int32_t* d_src = nullptr; const int32_t* d_i0 = nullptr;
   // Resident L^-T: a pass that starts from resident factors AND serves observed points from alpha / diag(K11^-1) keeps Z = L^-T in
@@ -353,7 +361,7 @@ int predict_core(agp_ctx* c, int64_t n, const double* ts_pred, int64_t m, int32_
     const int nf = std::max(0, std::min(Pc, bt.n_fused - p0));
     const int dcov = nf > 0 ? bt.max_depth_fused : 0;
     cv.p_off = nf;
-    cv.skip_pred_offdiag = out_cov ? 0 : 1;
+    cv.skip_pred_offdiag = want_cov ? 0 : 1;
     cv.i0 = n_hit > 0 ? d_i0 + p0 : nullptr;
     HIPCHK(c, launch_cov(st, cv, ntiles, Pc - nf, bt.max_cp, bt.max_depth));
 
@@ -432,8 +440,8 @@ int predict_core(agp_ctx* c, int64_t n, const double* ts_pred, int64_t m, int32_
       // passes K22 through.
       // without a covariance request only the diagonal tiles are updated: mean and marginal variances cost
       // n^3/3 + n^2 m instead of n^3/3 + n^2 m + n m^2
-      ca.schur_diag_only = out_cov ? 0 : 1;
-      const int T = out_cov ? nt2 * (nt2 + 1) / 2 : nt2;
+      ca.schur_diag_only = want_cov ? 0 : 1;
+      const int T = want_cov ? nt2 * (nt2 + 1) / 2 : nt2;
       const int Pg = (Pc + 7) / 8;
       int dcov_s = dcov;
       if (lagr && nf > 0) {
@@ -454,10 +462,12 @@ int predict_core(agp_ctx* c, int64_t n, const double* ts_pred, int64_t m, int32_
     pa.diag_add = diag_add ? s->diag_add.as<double>() : nullptr;
     pa.np_code = sum ? s->code.as<uint8_t>() + n1_pad : nullptr;
     pa.out_mean = s->pred_mean.as<double>(); pa.out_var = s->pred_var.as<double>();
-    pa.out_cov = out_cov ? s->pred_cov.as<double>() : nullptr;
-    const long long nel = out_cov ? (long long)mJ * mJ : (long long)mJ;
+    pa.out_cov = want_cov ? s->pred_cov.as<double>() : nullptr;
+    const long long nel = want_cov ? (long long)mJ * mJ : (long long)mJ;
     launch_pred_extract(st, nel, Pc, pa);
     HIPCHK(c, hipGetLastError());
+    if (mix)      // (before the next chunk overwrites pred_mean / pred_cov)
+      if (const int rc = mix_chunk(c, s, st, *mix, p0, Pc, pa.out_mean, pa.out_var, pa.out_cov)) return rc;
     if (ro) {
       SumReadArgs ra = {};
       ra.mean = s->pred_mean.as<double>(); ra.var = s->pred_var.as<double>(); ra.m = (int)mJ; ra.p_rows = (int)sum->p_rows;
@@ -469,12 +479,12 @@ int predict_core(agp_ctx* c, int64_t n, const double* ts_pred, int64_t m, int32_
       if (nq > 0)
         HIPCHK(c, hipMemcpyAsync(const_cast<double*>(h_x), s->sum_x.p, sizeof(double) * mJ * nq * Pc, hipMemcpyDeviceToHost, st));
     }
-    // results come back in sorted order: scatter to the caller's particle order
-    HIPCHK(c, hipMemcpyAsync(const_cast<double*>(h_mean), s->pred_mean.p, sizeof(double) * mJ * Pc, hipMemcpyDeviceToHost, st));
-    if (!ro) HIPCHK(c, hipMemcpyAsync(const_cast<double*>(h_var), s->pred_var.p, sizeof(double) * mJ * Pc, hipMemcpyDeviceToHost, st));
+    // results come back in sorted order: scatter to the caller's particle order (a mixture pass returns no per-particle marginals)
+    if (!mix) HIPCHK(c, hipMemcpyAsync(const_cast<double*>(h_mean), s->pred_mean.p, sizeof(double) * mJ * Pc, hipMemcpyDeviceToHost, st));
+    if (!ro && !mix) HIPCHK(c, hipMemcpyAsync(const_cast<double*>(h_var), s->pred_var.p, sizeof(double) * mJ * Pc, hipMemcpyDeviceToHost, st));
     }
     HIPCHK(c, hipStreamSynchronize(st));
-    for (int q = 0; q < Pc; ++q) {
+    for (int q = 0; q < Pc && !mix; ++q) {
       const size_t o = (size_t)bt.order[p0 + q];
       if (diag_path) {
         double* om = out_mean + o * m; double* ov = out_var + o * m;
@@ -498,6 +508,8 @@ int predict_core(agp_ctx* c, int64_t n, const double* ts_pred, int64_t m, int32_
     }
     HIPCHK(c, hipStreamSynchronize(st));
   }
+  if (mix)
+    if (const int rc = mix_finish(c, s, st, *mix)) return rc;
   {
     // always inspected: a caller that passes out_info = NULL must still never receive unmarked garbage
     std::vector<int32_t> info_sorted(P), bad_sorted(ro ? P : 0);
@@ -512,7 +524,7 @@ int predict_core(agp_ctx* c, int64_t n, const double* ts_pred, int64_t m, int32_
       if (out_info) out_info[p] = info_sorted[q];
       if (info_sorted[q] != 0) {
         const double nanv = std::nan("");
-        for (int64_t g = 0; g < m; ++g) { out_mean[(size_t)p * m + g] = nanv; if (out_var) out_var[(size_t)p * m + g] = nanv; }
+        for (int64_t g = 0; g < m && out_mean; ++g) { out_mean[(size_t)p * m + g] = nanv; if (out_var) out_var[(size_t)p * m + g] = nanv; }
         if (out_cov) for (int64_t g = 0; g < m * m; ++g) out_cov[(size_t)p * m * m + g] = nanv;
         if (nq > 0) std::fill(sum->out_x + (size_t)p * m * nq, sum->out_x + (size_t)(p + 1) * m * nq, nanv);
       }
@@ -778,6 +790,11 @@ thread_local bool tl_in_tpredict = false;
 
 }  // namespace
 
+int predict_dense(agp_ctx* c, int64_t n, const double* ts_pred, int64_t m, int32_t P, const int32_t* op_off, const uint8_t* ops,
+                  const int32_t* prm_off, const double* prm, const double* noise, const double* noise_pred, const double* mean_train,
+                  const double* mean_pred, double* out_mean, double* out_var, double* out_cov, int32_t* out_info, const double* weights,
+                  MixPass* mix);
+
 extern "C" {
 
 static int predict_batch_body(agp_ctx* c, int64_t n, const double* ts_pred, int64_t m, int32_t P,
@@ -896,51 +913,8 @@ static int predict_batch_body(agp_ctx* c, int64_t n, const double* ts_pred, int6
       return dense(refused);
     }
   }
-  // A resampled population holds copies of the survivors (src/inference_smc_anneal_data.jl:198-204) and the reference
-  // predicts particle by particle (src/api.jl:508-520): each distinct (program, parameters, noise, noise_pred) runs once.
-  std::vector<int> rep, uniq;
-  if (c->dedup && P > 1) (void)distinct_particles(P, op_off, ops, prm_off, prm, noise, noise_pred, rep, uniq);      // (malformed offsets: no dedup)
-  const int U = (int)uniq.size();
-  // (a store that holds nothing is not consulted: no key strings are built)
-  const bool want_keys = c->predict_reuse && n > 0 && !mean_train && c->store.n_slots > 0;
-  PredLattice pl;
-  predict_lattice(c, n, ts_pred, m, pl);
-  int64_t m_joint = m;       // query points predict_core keeps in the joint matrix (it makes the same split)
-  {
-    std::vector<int32_t> dq, di, fq;
-    split_queries(c, n, ts_pred, m, !out_cov && !c->ref_arith, dq, di, fq);
-    if (!dq.empty()) m_joint = (int64_t)fq.size();
-  }
-  const int nt1_ = (int)((n + NB - 1) / NB), nt_ = nt1_ + (int)((m_joint + NB - 1) / NB);
-  auto run = [&](int Pb, const int32_t* oo, const uint8_t* so, const int32_t* po, const double* sp, const double* nz, const double* nzp,
-                 double* om, double* ov, double* oc, int32_t* oi) {
-    Batch bt;
-    const bool ff = n > 0 && use_flow(c, Pb, nt_, nt1_);
-    int rc = compile_batch(c, Pb, oo, so, po, sp, bt, false, false, false, ff, ff, pl.on, pl.on ? pl.rank_units : 1, pl.on);
-    if (rc) return rc;
-    std::vector<std::string> keys;
-    if (want_keys)
-      for (int u = 0; u < Pb; ++u) keys.push_back(particle_key(so + oo[u], oo[u + 1] - oo[u], sp + po[u], po[u + 1] - po[u], nz[u]));
-    return predict_core(c, n, ts_pred, m, Pb, bt, nz, nzp, nullptr, nullptr, mean_train, mean_pred, om, ov, oc, oi,
-                        want_keys ? &keys : nullptr, &pl);
-  };
-  if (U == 0 || U == P)
-    return run(P, op_off, ops, prm_off, prm, noise, noise_pred, out_mean, out_var, out_cov, out_info);
-  SubBatch S;
-  pack_particles(uniq, op_off, ops, prm_off, prm, noise, noise_pred, S);
-  S.outputs(false);
-  std::vector<double> umean((size_t)U * m), uvar((size_t)U * m), ucov(out_cov ? (size_t)U * m * m : 0);
-  const int rc = run(U, S.op_off.data(), S.ops.data(), S.prm_off.data(), S.prm.data(), S.noise.data(), noise_pred ? S.noise_pred.data() : nullptr,
-                     umean.data(), uvar.data(), out_cov ? ucov.data() : nullptr, S.info.data());
-  if (rc) return rc;
-  for (int p = 0; p < P; ++p) {
-    const size_t u = (size_t)rep[p];
-    std::memcpy(out_mean + (size_t)p * m, umean.data() + u * m, sizeof(double) * (size_t)m);
-    std::memcpy(out_var + (size_t)p * m, uvar.data() + u * m, sizeof(double) * (size_t)m);
-    if (out_cov) std::memcpy(out_cov + (size_t)p * m * m, ucov.data() + u * m * m, sizeof(double) * (size_t)m * m);
-    if (out_info) out_info[p] = S.info[u];
-  }
-  return AGP_OK;
+  return predict_dense(c, n, ts_pred, m, P, op_off, ops, prm_off, prm, noise, noise_pred, mean_train, mean_pred, out_mean, out_var, out_cov,
+                       out_info, nullptr, nullptr);
 }
 
 static int predict_logpdf_body(agp_ctx* c, int64_t n, const double* ts_pred, const double* y_pred, int64_t m, int32_t P,
@@ -1009,6 +983,79 @@ int predict_joint_batch(agp_ctx* c, int64_t n, const double* ts_pred, const doub
     if (out_info) out_info[p] = uinfo[u];
   }
   return AGP_OK;
+}
+
+// The dense pass of agp_predict_batch.  `mix` (nullable, with the caller particles' `weights`; agp_predict_mixture_batch's covariance
+// pass): the same pass with a covariance request, the per-particle covariances reduced on the device (predict_core's MixPass) and no
+// per-particle output but out_info.
+int predict_dense(agp_ctx* c, int64_t n, const double* ts_pred, int64_t m, int32_t P, const int32_t* op_off, const uint8_t* ops,
+                  const int32_t* prm_off, const double* prm, const double* noise, const double* noise_pred, const double* mean_train,
+                  const double* mean_pred, double* out_mean, double* out_var, double* out_cov, int32_t* out_info, const double* weights,
+                  MixPass* mix) {
+  const bool want_cov = out_cov != nullptr || (mix && mix->cov);
+  // A resampled population holds copies of the survivors (src/inference_smc_anneal_data.jl:198-204) and the reference
+  // predicts particle by particle (src/api.jl:508-520): each distinct (program, parameters, noise, noise_pred) runs once.
+  std::vector<int> rep, uniq;
+  if (c->dedup && P > 1) (void)distinct_particles(P, op_off, ops, prm_off, prm, noise, noise_pred, rep, uniq);      // (malformed offsets: no dedup)
+  const int U = (int)uniq.size();
+  const bool packed = U != 0 && U != P;
+  if (mix) {
+    // (copies: their weights are added, in the caller's order, onto the representative)
+    mix->w.assign((size_t)(packed ? U : P), 0.0);
+    for (int p = 0; p < P; ++p) mix->w[packed ? (size_t)rep[p] : (size_t)p] += weights[p];
+    std::lock_guard<std::mutex> g(c->mu);
+    c->n_particles_seen += P; c->n_particles_run += packed ? U : P;      // (agp_get_dedup_stats)
+  }
+  // (a store that holds nothing is not consulted: no key strings are built)
+  const bool want_keys = c->predict_reuse && n > 0 && !mean_train && c->store.n_slots > 0;
+  PredLattice pl;
+  predict_lattice(c, n, ts_pred, m, pl);
+  int64_t m_joint = m;       // query points predict_core keeps in the joint matrix (it makes the same split)
+  {
+    std::vector<int32_t> dq, di, fq;
+    split_queries(c, n, ts_pred, m, !want_cov && !c->ref_arith, dq, di, fq);
+    if (!dq.empty()) m_joint = (int64_t)fq.size();
+  }
+  const int nt1_ = (int)((n + NB - 1) / NB), nt_ = nt1_ + (int)((m_joint + NB - 1) / NB);
+  auto run = [&](int Pb, const int32_t* oo, const uint8_t* so, const int32_t* po, const double* sp, const double* nz, const double* nzp,
+                 double* om, double* ov, double* oc, int32_t* oi) {
+    Batch bt;
+    const bool ff = n > 0 && use_flow(c, Pb, nt_, nt1_);
+    int rc = compile_batch(c, Pb, oo, so, po, sp, bt, false, false, false, ff, ff, pl.on, pl.on ? pl.rank_units : 1, pl.on);
+    if (rc) return rc;
+    std::vector<std::string> keys;
+    if (want_keys)
+      for (int u = 0; u < Pb; ++u) keys.push_back(particle_key(so + oo[u], oo[u + 1] - oo[u], sp + po[u], po[u + 1] - po[u], nz[u]));
+    return predict_core(c, n, ts_pred, m, Pb, bt, nz, nzp, nullptr, nullptr, mean_train, mean_pred, om, ov, oc, oi,
+                        want_keys ? &keys : nullptr, &pl, nullptr, mix);
+  };
+  if (!packed)
+    return run(P, op_off, ops, prm_off, prm, noise, noise_pred, out_mean, out_var, out_cov, out_info);
+  SubBatch S;
+  pack_particles(uniq, op_off, ops, prm_off, prm, noise, noise_pred, S);
+  S.outputs(false);
+  std::vector<double> umean(mix ? 0 : (size_t)U * m), uvar(mix ? 0 : (size_t)U * m), ucov(out_cov ? (size_t)U * m * m : 0);
+  const int rc = run(U, S.op_off.data(), S.ops.data(), S.prm_off.data(), S.prm.data(), S.noise.data(), noise_pred ? S.noise_pred.data() : nullptr,
+                     mix ? nullptr : umean.data(), mix ? nullptr : uvar.data(), out_cov ? ucov.data() : nullptr, S.info.data());
+  if (rc) return rc;
+  for (int p = 0; p < P; ++p) {
+    const size_t u = (size_t)rep[p];
+    if (!mix) {
+      std::memcpy(out_mean + (size_t)p * m, umean.data() + u * m, sizeof(double) * (size_t)m);
+      std::memcpy(out_var + (size_t)p * m, uvar.data() + u * m, sizeof(double) * (size_t)m);
+    }
+    if (out_cov) std::memcpy(out_cov + (size_t)p * m * m, ucov.data() + u * m * m, sizeof(double) * (size_t)m * m);
+    if (out_info) out_info[p] = S.info[u];
+  }
+  return AGP_OK;
+}
+
+int predict_mixture_cov(agp_ctx* c, int64_t n, const double* ts_pred, int64_t m, int32_t P, const int32_t* op_off, const uint8_t* ops,
+                        const int32_t* prm_off, const double* prm, const double* noise, const double* noise_pred,
+                        const double* mean_train, const double* mean_pred, const double* weights, MixPass& mp, int32_t* out_info) {
+  HIPCHK(c, hipSetDevice(c->device));
+  return predict_dense(c, n, ts_pred, m, P, op_off, ops, prm_off, prm, noise, noise_pred, mean_train, mean_pred, nullptr, nullptr, nullptr,
+                       out_info, weights, &mp);
 }
 
 extern "C" {
@@ -1540,7 +1587,7 @@ int agp_debug_flow_trace(agp_ctx* c, int32_t enable, int64_t max_items, int64_t*
 #endif  // AGP_EXPERIMENTS
 
 int agp_debug_math(agp_ctx* c, int32_t which, const double* x, const double* g, double* y, int32_t n) {
-  if (!c || !x || !y || n <= 0 || which < 0 || which > 8 || (which == 3 && !g)) return fail(c, AGP_ERR_ARG, "bad arguments");
+  if (!c || !x || !y || n <= 0 || which < 0 || which > 9 || (which == 3 && !g)) return fail(c, AGP_ERR_ARG, "bad arguments");
   HIPCHK(c, hipSetDevice(c->device));
   double *dx = nullptr, *dg = nullptr, *dy = nullptr;
   HIPCHK(c, malloc_values(c->poison, (void**)&dx, sizeof(double) * n));

@@ -34,7 +34,7 @@ EXPORTED_SYMBOLS = [
     "agp_predict_reuse_stats", "agp_grad_reuse_stats", "agp_set_factor_cache", "agp_wait", "agp_comm_count", "agp_get_lag_stats", "agp_get_lattice_stats", "agp_get_compact_stats", "agp_set_lattice", "agp_probe_lattice", "agp_set_reference_arithmetic", "agp_shard_plan", "agp_get_coalesce_timing", "agp_set_lag_tables", "agp_set_grad_lag_domain", "agp_get_grad_lag_domain_stats", "agp_get_grad_toeplitz_stats", "agp_get_grad_structured_stats", "agp_get_predict_structured_stats", "agp_get_toeplitz_stats", "agp_set_lag_rank_tables", "agp_get_lag_rank_stats", "agp_get_lag_predict_stats", "agp_get_poison_stats",
     "agp_logpdf_grad_batch_multi", "agp_predict_batch_multi", "agp_extend_stats2", "agp_predict_logpdf_batch",
     "agp_mixture_quantile", "agp_predict_quantile_batch", "agp_infer_gp_sum_batch", "agp_predict_sum_batch",
-    "agp_predict_sample_batch",
+    "agp_predict_sample_batch", "agp_mixture_moments", "agp_predict_mixture_batch", "agp_get_mixture_stats",
     "agp_remove_data", "agp_get_remove_stats", "agp_set_remove_update", "agp_remove_data_multi",
     "agp_debug_factor_batch",
 ]
@@ -119,6 +119,11 @@ def load_library(path=None):
     lib.agp_predict_sample_batch.argtypes = [vp, C.c_int64, dp, C.c_int64, C.c_int32, ip, u8p, ip, dp, dp, dp, dp, dp, dp,
                                              C.c_double, C.c_double, C.c_int64, C.c_uint64, ip, dp, dp, ip, ip]
     lib.agp_predict_sample_batch.restype = C.c_int
+    lib.agp_mixture_moments.argtypes = [vp, C.c_int64, C.c_int32, dp, dp, dp, dp, C.c_int32, dp, dp, dp]
+    lib.agp_mixture_moments.restype = C.c_int
+    lib.agp_predict_mixture_batch.argtypes = [vp, C.c_int64, dp, C.c_int64, C.c_int32, ip, u8p, ip, dp, dp, dp, dp, dp, dp,
+                                              C.c_double, C.c_double, C.c_int32, dp, dp, dp, ip]
+    lib.agp_predict_mixture_batch.restype = C.c_int
     lib.agp_infer_gp_sum.argtypes = [vp, C.c_int64, dp, C.c_int64, C.c_int32, ip, u8p, ip, dp, C.c_double, C.c_double, dp, dp, ip]
     lib.agp_infer_gp_sum.restype = C.c_int
     lib.agp_infer_gp_sum_batch.argtypes = [vp, C.c_int64, dp, C.c_int64, C.c_int32, C.c_int32, ip, u8p, ip, dp, dp, dp, dp, dp, dp, ip]
@@ -143,6 +148,7 @@ def load_library(path=None):
     lib.agp_get_coalesce_timing.argtypes = [vp, dp]; lib.agp_get_coalesce_timing.restype = C.c_int
     lib.agp_get_coalesce_stats.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]; lib.agp_get_coalesce_stats.restype = C.c_int
     lib.agp_get_dedup_stats.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]; lib.agp_get_dedup_stats.restype = C.c_int
+    lib.agp_get_mixture_stats.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]; lib.agp_get_mixture_stats.restype = C.c_int
     lib.agp_logpdf_batch_extend.argtypes = [vp, C.c_int64, C.c_int32, ip, u8p, ip, dp, dp, dp, ip]
     lib.agp_logpdf_batch_extend.restype = C.c_int
     if hasattr(lib, "agp_debug_flow_trace"):
@@ -666,6 +672,55 @@ class GPEngine:
             raise PosDefException(int(info[p]), p)
         return xt.T, comp, info
 
+    # -- mixture moments (Distributions.mean / var / cov of predict_mvn's MixtureModel) ------------------------------------
+    def mixture_moments(self, means, weights, vars=None, covs=None, space=0, want_cov=None):
+        """mean / var / cov of MixtureModel(components, weights) (agp_mixture_moments): means (P, m), and either vars (P, m) (marginal
+        moments) or covs (P, m, m).  space 0: normal components; 1: MvLogNormal(N(means, covs)) components.  Returns (mean (m,),
+        var (m,), cov (m, m) or None); cov when covs is given unless want_cov=False."""
+        means = _f64(means); weights = _f64(weights)
+        if means.ndim != 2 or weights.shape != (means.shape[0],):
+            raise ValueError(f"means {means.shape}, weights {weights.shape}: expected (P, m), (P,)")
+        P, m = means.shape
+        if covs is not None:
+            covs = _f64(covs)
+            if covs.shape != (P, m, m):
+                raise ValueError(f"covs has shape {covs.shape}, expected ({P}, {m}, {m})")
+        if vars is not None:
+            vars = _f64(vars)
+            if vars.shape != (P, m):
+                raise ValueError(f"vars has shape {vars.shape}, expected ({P}, {m})")
+        want_cov = covs is not None if want_cov is None else bool(want_cov)
+        mean = np.empty(m); var = np.empty(m); cov = np.empty((m, m)) if want_cov else None
+        self._check(self._lib.agp_mixture_moments(self._ctx, m, P, _dp(means), _dp(vars), _dp(covs), _dp(weights), int(space),
+                                                  _dp(mean), _dp(var), _dp(cov)))
+        return mean, var, cov
+
+    def predict_mixture_batch(self, nodes, noises, ts_pred, weights, n=None, noise_pred=None, mean_train=None, mean_pred=None,
+                              y_transform=(1.0, 0.0), space=0, want_cov=False, check=True):
+        """mean / var / cov of predict_mvn's MixtureModel on the resident series (agp_predict_mixture_batch), in the raw space of
+        y_transform = (slope, intercept); space 1: of its MvLogNormal re-wrap.  want_cov: the fused covariance pass (no per-particle
+        covariance leaves the device).  Returns (mean (m,), var (m,), cov (m, m) or None, info (P,)); everything is NaN if any info != 0
+        (PosDefException when check)."""
+        n = self.n_max if n is None else int(n)
+        op_off, ops, prm_off, prm = _gp.encode_batch(nodes)
+        P = op_off.shape[0] - 1
+        noises = _f64(noises); ts_pred = _f64(ts_pred); m = ts_pred.shape[0]; weights = _f64(weights)
+        if weights.shape != (P,):
+            raise ValueError(f"weights has shape {weights.shape}, expected ({P},)")
+        npred = None if noise_pred is None else _f64(np.broadcast_to(noise_pred, (P,)))
+        mt = None if mean_train is None else _f64(mean_train)
+        mp_ = None if mean_pred is None else _f64(mean_pred)
+        slope, intercept = (float(v) for v in y_transform)
+        mean = np.empty(m); var = np.empty(m); cov = np.empty((m, m)) if want_cov else None
+        info = np.zeros(P, dtype=np.int32)
+        self._check(self._lib.agp_predict_mixture_batch(self._ctx, n, _dp(ts_pred), m, P, _ip(op_off), _u8(ops), _ip(prm_off), _dp(prm),
+                                                        _dp(noises), _dp(npred), _dp(mt), _dp(mp_), _dp(weights), slope, intercept,
+                                                        int(space), _dp(mean), _dp(var), _dp(cov), _ip(info)))
+        if check and (info > 0).any():
+            p = int(np.argmax(info > 0))
+            raise PosDefException(int(info[p]), p)
+        return mean, var, cov, info
+
     # -- sum-of-GPs posterior (src/GP.jl:904-993) ---------------------------------------------
     def infer_gp_sum(self, nodes, noise, ts_pred, n=None, noise_pred=None, check=True):
         """Returns (mean[(M+1)p], cov[(M+1)p, (M+1)p], indexes_F (list of slices), indexes_X (slice))."""
@@ -810,11 +865,11 @@ class GPEngine:
         self._check(self._lib.agp_set_profiling(self._ctx, 1 if on else 0))
 
     def timing(self):
-        out = np.zeros(14)
-        self._check(self._lib.agp_get_timing(self._ctx, _dp(out), 14))
+        out = np.zeros(16)
+        self._check(self._lib.agp_get_timing(self._ctx, _dp(out), 16))
         keys = ["total_ms", "cov_build_ms", "chol_update_ms", "chol_trsm_ms", "finish_ms", "n_update_launches",
                 "n_trsm_launches", "h2d_ms", "grad_trtri_ms", "grad_kinv_ms", "grad_contract_ms", "grad_alpha_finish_ms",
-                "sample_normals_ms", "sample_readout_ms"]
+                "sample_normals_ms", "sample_readout_ms", "mixture_pass_ms", "mixture_accumulate_ms"]
         return dict(zip(keys, out.tolist()))
 
     def launch_times(self, which=0, n=64):
@@ -834,6 +889,12 @@ class GPEngine:
         """(particles submitted, particles evaluated) over the host-output batch calls so far."""
         a = C.c_int64(); b = C.c_int64()
         self._check(self._lib.agp_get_dedup_stats(self._ctx, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def mixture_stats(self):
+        """(mixture-moment passes finished, chunks of components their running sums took in) so far."""
+        a = C.c_int64(); b = C.c_int64()
+        self._check(self._lib.agp_get_mixture_stats(self._ctx, C.byref(a), C.byref(b)))
         return a.value, b.value
 
     def set_workspace_limit(self, nbytes: int):
@@ -1168,6 +1229,105 @@ def predict_rand(engine, nodes, noises, log_weights, ts_pred, n_samples=None, se
     x, _, _ = engine.predict_sample_batch(nodes, noises, ts_pred, w, 1 if n_samples is None else n_samples, seed=seed,
                                           noise_pred=npred, y_transform=y_transform)
     return x[:, 0].copy() if n_samples is None else x
+
+
+class MixtureModel:
+    """The Distributions.MixtureModel that AutoGP.predict_mvn(model, ds; noise_pred) returns (src/api.jl:497-522), on the engine's
+    resident (scaled) series: components = every particle's posterior predictive MvNormal at ts_pred mapped to the RAW space of
+    y_transform, probs = the normalised particle weights.  mean / var / cov are reduced over the particles on the device
+    (agp_predict_mixture_batch) when first asked for."""
+
+    def __init__(self, engine, nodes, noises, log_weights, ts_pred, y_transform=(1.0, 0.0), noise_pred=None, space=0):
+        from .dist import normalize_weights
+        self._engine = engine
+        self._nodes = list(nodes); self._noises = _f64(noises); self._log_weights = _f64(log_weights)
+        self._ts_pred = _f64(ts_pred)
+        self._y_transform = tuple(float(v) for v in y_transform)
+        self._noise_pred = None if noise_pred is None else float(noise_pred)
+        self._space = int(space)
+        self._components = None
+        self.probs = np.exp(normalize_weights(self._log_weights)[1])
+        self._marginal = None       # (mean, var)
+        self._full = None           # (mean, var, cov)
+
+    @classmethod
+    def from_components(cls, components, probs, engine=None, space=0):
+        """MixtureModel(components, probs) of given MvNormal moments (predict_mvn_sum's return value): its moments come from
+        agp_mixture_moments."""
+        d = cls.__new__(cls)
+        d._engine = engine or default_engine()
+        d._components = list(components)
+        d.probs = _f64(probs)
+        d._space = int(space)
+        d._nodes = None
+        d._marginal = d._full = None
+        return d
+
+    def _moments(self, want_cov):
+        if self._full is None and (want_cov or self._marginal is None):
+            if self._components is not None:
+                mu = np.stack([np.asarray(cm.mu, dtype=np.float64) for cm in self._components])
+                S = np.stack([np.asarray(cm.Sigma, dtype=np.float64) for cm in self._components])
+                mean, var, cov = self._engine.mixture_moments(mu, self.probs, covs=S, space=self._space, want_cov=want_cov)
+            else:
+                mean, var, cov, _ = self._engine.predict_mixture_batch(self._nodes, self._noises, self._ts_pred, self.probs,
+                                                                       noise_pred=self._noise_pred, y_transform=self._y_transform,
+                                                                       space=self._space, want_cov=want_cov)
+            if want_cov:
+                self._full = (mean, var, cov)
+            else:
+                self._marginal = (mean, var)
+        return self._full if self._full is not None else self._marginal
+
+    def mean(self):
+        return self._moments(False)[0]
+
+    def var(self):
+        return self._moments(False)[1]
+
+    def cov(self):
+        return self._moments(True)[2]
+
+    def lognormal(self):
+        """MixtureModel(MvLogNormal.(components), probs): the direct-space view of a model fitted on log(y)
+        (docs/src/tutorials/iclaims.md); its mean / var / cov are the log-normal mixture's (space = 1)."""
+        if self._components is not None:
+            return MixtureModel.from_components(self._components, self.probs, engine=self._engine, space=1)
+        return MixtureModel(self._engine, self._nodes, self._noises, self._log_weights, self._ts_pred, self._y_transform,
+                            self._noise_pred, space=1)
+
+    def _resident(self, what):
+        if self._nodes is None or self._space != 0:
+            raise NotImplementedError(f"{what} of a MixtureModel built from moments or of its log-normal view")
+
+    def logpdf(self, y):
+        """Distributions.logpdf(d, y): logsumexp over the particles of log w_p + logpdf(component_p, y) (predict_proba's columns)."""
+        self._resident("logpdf")
+        r = predict_proba(self._engine, self._nodes, self._noises, self._log_weights, self._ts_pred, y, y_transform=self._y_transform,
+                          noise_pred=self._noise_pred)
+        keep = r["weight"] > 0.0
+        t = np.log(r["weight"][keep]) + r["logp"][keep]
+        hi = t.max()
+        return float(hi + np.log(np.exp(t - hi).sum())) if np.isfinite(hi) else float(hi)
+
+    def quantile(self, q, tol=1e-5, max_iter=10**6):
+        """predict_quantile's (x, success)."""
+        self._resident("quantile")
+        return predict_quantile(self._engine, self._nodes, self._noises, self._log_weights, self._ts_pred, q,
+                                y_transform=self._y_transform, noise_pred=self._noise_pred, tol=tol, max_iter=max_iter)
+
+    def rand(self, n_samples=None, seed=0):
+        """predict_rand's samples."""
+        self._resident("rand")
+        return predict_rand(self._engine, self._nodes, self._noises, self._log_weights, self._ts_pred, n_samples=n_samples, seed=seed,
+                            y_transform=self._y_transform, noise_pred=self._noise_pred)
+
+
+def predict_mvn(engine, nodes, noises, log_weights, ts_pred, y_transform=(1.0, 0.0), noise_pred=None):
+    """AutoGP.predict_mvn(model, ds; noise_pred) (src/api.jl:497-522) on the engine's resident (scaled) series: the MixtureModel of
+    every particle's posterior predictive at ts_pred (already in the engine's time scale) in the RAW space of y_transform = (slope,
+    intercept) (scaled = slope * raw + intercept), weighted by exp of Gen.normalize_weights(log_weights)."""
+    return MixtureModel(engine, nodes, noises, log_weights, ts_pred, y_transform=y_transform, noise_pred=noise_pred)
 
 
 def infer_gp_sum(nodes, noise, ts, xs, ts_pred, noise_pred=None, engine=None):

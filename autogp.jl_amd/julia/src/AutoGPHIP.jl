@@ -488,6 +488,35 @@ function predict_rand(eng::Engine, nodes::Vector{<:GP.Node}, noises::Vector{Floa
     return isnothing(N) ? x[:, 1] : x
 end
 
+"""
+`Distributions.mean`, `var` and `cov` of `AutoGP.predict_mvn(model, ds; noise_pred)` (src/api.jl:497-522) for a population on the
+(scaled) resident series: the moments of the mixture, with `weights` (`AutoGP.particle_weights(model)`), of every particle's
+predictive at `ts_pred` in the raw space of the linear `y_transform` (slope, intercept), reduced over the particles on the device.
+`lognormal=true`: of `MixtureModel(MvLogNormal.(components), weights)`, the direct-space view of a model fitted on `log.(y)`.
+`want_cov=false` runs the marginal pass (`cov` is `nothing`).  Returns `(mean, var, cov)`; throws `PosDefException` where a particle
+has no predictive.
+"""
+function predict_mvn_moments(eng::Engine, nodes::Vector{<:GP.Node}, noises::Vector{Float64}, weights::Vector{Float64},
+        ts_pred::Vector{Float64}; n::Integer=eng.n_max, noise_pred::Union{Nothing,Float64}=nothing,
+        y_slope::Float64=1.0, y_intercept::Float64=0.0, lognormal::Bool=false, want_cov::Bool=true)
+    P = length(nodes); m = length(ts_pred)
+    op_off, ops, prm_off, prm = encode_batch(nodes)
+    mean = Vector{Float64}(undef, m); var = Vector{Float64}(undef, m); info = zeros(Int32, P)
+    cov = want_cov ? Matrix{Float64}(undef, m, m) : Matrix{Float64}(undef, 0, 0)
+    npv = isnothing(noise_pred) ? Float64[] : fill(noise_pred, P)
+    GC.@preserve ops prm op_off prm_off ts_pred noises npv weights mean var cov info check(eng, ccall((:agp_predict_mixture_batch, LIB), Cint,
+        (Ptr{Cvoid}, Int64, Ptr{Float64}, Int64, Int32, Ptr{Int32}, Ptr{UInt8}, Ptr{Int32}, Ptr{Float64},
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Float64, Float64, Int32,
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
+        eng.ptr, n, ts_pred, m, P, op_off, ops, prm_off, prm, noises,
+        isempty(npv) ? Ptr{Float64}(C_NULL) : pointer(npv), Ptr{Float64}(C_NULL), Ptr{Float64}(C_NULL),
+        weights, y_slope, y_intercept, Int32(lognormal ? 1 : 0), mean, var,
+        want_cov ? pointer(cov) : Ptr{Float64}(C_NULL), info))
+    k = findfirst(!=(0), info)
+    isnothing(k) || throw(LinearAlgebra.PosDefException(info[k]))
+    return mean, var, (want_cov ? cov : nothing)
+end
+
 "Sum-of-GPs posterior — replaces GP.infer_gp_sum (src/GP.jl:904-993); returns the same named tuple."
 function infer_gp_sum(eng::Engine, nodes::Vector{<:GP.Node}, noise::Float64, ts_pred::Vector{Float64};
         n::Integer=eng.n_max, noise_pred::Union{Nothing,Float64}=nothing)

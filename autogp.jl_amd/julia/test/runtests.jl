@@ -106,6 +106,28 @@ kernels() = GP.Node[
         @test maxrel(Distributions.mean(d2), Distributions.mean(Distributions.MvNormal(k, noise, ts, xs, tp))) <= 1e-8
     end
 
+    @testset "moments of predict_mvn's MixtureModel, and of its MvLogNormal re-wrap" begin
+        # (predict_mvn builds exactly this: MixtureModel of the particles' MvNormals with the particle weights, src/api.jl:508-521)
+        tp = vcat(ts[1:25:end], collect(range(1.0, 1.2; length=20)))
+        ks = GP.Node[k for k in kernels()[1:4]]
+        nz = fill(noise, length(ks))
+        w = collect(1.0:length(ks)); w ./= sum(w)
+        comps = [Distributions.MvNormal(k, noise, ts, xs, tp) for k in ks]
+        r = Distributions.MixtureModel(comps, w)
+        mu, v, C = H.predict_mvn_moments(eng, ks, nz, w, tp)
+        @test maxrel(mu, Distributions.mean(r)) <= 1e-8
+        @test maxrel(v, Distributions.var(r)) <= 1e-8
+        @test maxrel(C, Matrix(Distributions.cov(r))) <= 1e-8
+        @test C == C' && v == diag(C)
+        mu0, v0, C0 = H.predict_mvn_moments(eng, ks, nz, w, tp; want_cov=false)
+        @test isnothing(C0) && maxrel(mu0, Distributions.mean(r)) <= 1e-8 && maxrel(v0, Distributions.var(r)) <= 1e-8
+        rl = Distributions.MixtureModel([Distributions.MvLogNormal(c) for c in comps], w)
+        mul, vl, Cl = H.predict_mvn_moments(eng, ks, nz, w, tp; lognormal=true)
+        @test maxrel(mul, Distributions.mean(rl)) <= 1e-8
+        @test maxrel(vl, Distributions.var(rl)) <= 1e-8
+        @test maxrel(Cl, Matrix(Distributions.cov(rl))) <= 1e-8
+    end
+
     @testset "infer_gp_sum" begin
         nodes = GP.Node[GP.Linear(0.1, 0.3, 0.7), GP.Periodic(0.96, 0.21, 1.1), GP.SquaredExponential(0.3, 0.5)]
         tp = collect(range(0.0, 1.2; length=25))

@@ -478,6 +478,47 @@ int agp_predict_sample_batch(agp_ctx* ctx, int64_t n, const double* ts_pred, int
                              double* out_x /* m*S column-major */, int32_t* out_component /* S or NULL */,
                              int32_t* out_info /* P or NULL */);
 
+/* Moments of a mixture, Distributions.mean / var / cov of MixtureModel(components, weights): components p of mean means[p*m + i] and
+ * covariance covs[p*m*m + j*m + i] (P blocks of m x m, column-major, symmetric: the lower triangle is read), weights[p].  means / vars
+ * are column-major m x P (agp_predict_batch's layout).  covs NULL: the marginal moments from vars[p*m + i] (out_cov must be NULL); covs
+ * given: the variances are its diagonals and vars is not read (may be NULL).  With e_p the component means,
+ *     out_mean = sum w_p e_p,   out_cov = sum w_p (C_p + (e_p - mean)(e_p - mean)') (m x m, exactly symmetric),   out_var = diag(out_cov)
+ * (out_var and the diagonal of out_cov are the same bits).  space 0: normal components N(means, covs).  space 1:
+ * MvLogNormal(N(means, covs)) components (the direct-space view of a model fitted on log y): e_i = exp(mu_i + C_ii / 2),
+ * C_p,ij = e_i e_j expm1(C_ij) (Distributions' MvLogNormal; src/Transforms.jl:87-91 on the diagonal).  A component mean past the
+ * range of a double is Inf, which is the reference's behaviour and no error: out_mean is then Inf at that point — NaN if it is the
+ * pivot's mean that overflowed (Inf - Inf) — and out_var and that row and column of out_cov are NaN, as (e - mean)^2 is with
+ * mean = Inf.  The sums run on the device about a pivot (the first component of positive weight), sequentially in particle
+ * order, with no atomics: the bits do not depend on agp_set_workspace_limit.  A component of weight 0 contributes nothing, whatever
+ * it holds.  m == 0 writes nothing.  Errors (negative return): P < 1; m < 0; space outside {0, 1}; weights not finite, negative or
+ * not summing to 1 (rtol sqrt(eps)); covs NULL with out_cov given; a NULL input; m*P >= 2^31, or m*m >= 2^31 with out_cov. */
+int agp_mixture_moments(agp_ctx* ctx, int64_t m, int32_t P, const double* means, const double* vars, const double* covs,
+                        const double* weights, int32_t space,
+                        double* out_mean /* m */, double* out_var /* m */, double* out_cov /* m*m or NULL */);
+
+/* mean / var / cov of predict_mvn(model, ds; noise_pred) (src/api.jl:497-522) on the resident (ts, xs)[1:n]: the MixtureModel over the
+ * particles' posterior predictives with `weights`, after predict_mvn's raw-space transform of a linear y_transform,
+ * mu_raw = (mu - y_intercept) / y_slope and C_raw = (1 / y_slope^2) C, in `space` (agp_mixture_moments: 0 the mixture itself, 1 its
+ * MixtureModel(MvLogNormal.(components), weights) re-wrap).  Arguments n .. mean_pred as agp_predict_quantile_batch (n == 0: the prior).
+ *   out_cov == NULL (marginal pass): agp_predict_batch's marginal pass (structured, lattice, store-reuse, duplicate-query and dedup
+ *     paths), its m x P means and variances staged through host memory, then agp_mixture_moments' reduction on the device.
+ *   out_cov != NULL (covariance pass): agp_predict_batch's pass with a covariance request; each chunk's covariances are added into
+ *     the m x m running sums on the device and never leave it, nor do the per-particle marginals: m*m + 2m doubles come back instead
+ *     of P*m*m.  Identical particles are
+ *     evaluated once and their weights added onto the first copy (AGP_DEDUP=0 disables; agp_get_dedup_stats counts them).
+ * out_info[p] (may be NULL): agp_predict_batch's.  If any particle's info != 0 — a particle of weight 0 included — every output is NaN
+ * (the reference throws building that particle's MvNormal).  m == 0 writes nothing.  With profiling on, agp_get_timing's out[14..15]
+ * = { the pass without the accumulation ms, the accumulation kernels ms } (marginal pass: of the staged reduction only).
+ * Errors as agp_mixture_moments (y_slope must be finite and non-zero, y_intercept finite) plus agp_predict_batch's. */
+int agp_predict_mixture_batch(agp_ctx* ctx, int64_t n, const double* ts_pred, int64_t m, int32_t P,
+                              const int32_t* op_off, const uint8_t* ops,
+                              const int32_t* prm_off, const double* prm,
+                              const double* noise, const double* noise_pred,
+                              const double* mean_train, const double* mean_pred, const double* weights,
+                              double y_slope, double y_intercept, int32_t space,
+                              double* out_mean /* m */, double* out_var /* m */, double* out_cov /* m*m or NULL: marginal pass */,
+                              int32_t* out_info /* P or NULL */);
+
 /* infer_gp_sum(nodes, noise, ts, xs, ts_pred; noise_pred) (src/GP.jl:904-993) on the resident (ts, xs)[1:n]:
  * posterior of Z = [F_1(T*); ...; F_M(T*); X(T*)] for the sum-of-GPs model.  The M component kernels are
  * given as CSR-packed postfix programs (op_off / prm_off have M+1 entries).  out_mean: (M+1)*p;
@@ -652,7 +693,8 @@ int agp_debug_mfma_probe(agp_ctx* ctx, const double* A, const double* B, double*
 /* Element-wise probe of the device math used by the covariance kernels (csrc/agp_math.hpp):
  * which = 0 exp, 1 sin^2, 2 log, 3 pow(x, g), 4 erfc (the device library's, as the mixture-quantile kernel calls it),
  * 5 sqrt (the mixture-quantile kernels' sigma), 6 exp through the 128-entry table (exp_t, read from a copy in LDS as the
- * covariance kernels do), 7 / 8 the sine / cosine of sincos_pi_f. */
+ * covariance kernels do), 7 / 8 the sine / cosine of sincos_pi_f, 9 expm1 (the device library's, as the mixture-moment kernels
+ * call it). */
 int agp_debug_math(agp_ctx* ctx, int32_t which, const double* x, const double* g, double* y, int32_t n);
 
 /* fp64 MFMA issue-rate microbenchmark (16 independent accumulators per wave, wg_per_cu
@@ -669,7 +711,7 @@ int agp_debug_compact_shards(agp_ctx* ctx, const double* padded, int32_t P, int3
  * agp_get_timing fills out[0..7] = { total_ms, cov_build_ms, chol_update_ms, chol_trsm_ms,
  * finish_ms, n_update_launches, n_trsm_launches, h2d_d2h_ms } for the last batch call; a value+gradient sweep also
  * fills out[8..11] = { L^-T chain ms, K^-1 tiles ms, contraction ms, alpha + reductions ms }, agp_predict_sample_batch
- * out[12..13] = { normals ms, read-out ms } (n_out up to 16). */
+ * out[12..13] = { normals ms, read-out ms }, agp_predict_mixture_batch out[14..15] = { pass ms, accumulation ms } (n_out up to 16). */
 int agp_set_profiling(agp_ctx* ctx, int enabled);
 int agp_get_timing(agp_ctx* ctx, double* out, int32_t n_out);
 /* per-launch durations (ms) of the last profiled batch call: which = 0 update kernel, 1 trsm kernel;
@@ -687,6 +729,9 @@ int agp_get_coalesce_timing(agp_ctx* ctx, double* out4);
  * the result to its duplicates (a resampled SMC population, src/inference_smc_anneal_data.jl:198-204, holds
  * many copies).  Counters: particles submitted / particles actually evaluated.  env AGP_DEDUP=0 disables. */
 int agp_get_dedup_stats(agp_ctx* ctx, int64_t* n_particles, int64_t* n_evaluated);
+/* Mixture-moment passes (agp_mixture_moments, agp_predict_mixture_batch) since agp_init: how many finished and how many chunks of
+ * components their running sums took in (more chunks than passes: agp_set_workspace_limit split a pass). */
+int agp_get_mixture_stats(agp_ctx* ctx, int64_t* n_passes, int64_t* n_chunks);
 
 /* Cap (bytes) on matrix workspace per call; larger batches are processed in chunks. 0 = default. */
 int agp_set_workspace_limit(agp_ctx* ctx, int64_t bytes);
