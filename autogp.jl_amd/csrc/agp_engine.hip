@@ -31,6 +31,14 @@ int fail(agp_ctx* c, int code, const std::string& msg) {
   return code;
 }
 
+int check_resident(agp_ctx* c, int64_t n) {
+  return n > c->n_max ? fail(c, AGP_ERR_NODATA, "n exceeds the data uploaded with agp_set_data") : AGP_OK;
+}
+int check_y_transform(agp_ctx* c, double slope, double intercept) {
+  if (std::isfinite(slope) && slope != 0.0 && std::isfinite(intercept)) return AGP_OK;
+  return fail(c, AGP_ERR_ARG, "y_transform must have a finite non-zero slope and a finite intercept");
+}
+
 // Reference arithmetic: every structure-exploiting or state-dependent path off, ONE schedule.  A particle's results then depend on
 // (program, parameters, noise, data, n) alone — not on the batch it travels in, on what the factor store holds, on the order of
 // the calls or on the other switches: prebuilt tiles from k_cov_tiles (each element from its own t_i - t_j, GammaExp by pow as the
@@ -319,17 +327,12 @@ int emit_grad(const std::vector<CNode>& nodes, int id, Batch& bt, int prm_base, 
   return me;
 }
 
-int compile_batch(agp_ctx* c, int P, const int32_t* op_off, const uint8_t* ops, const int32_t* prm_off,
-                  const double* prm, Batch& bt, bool allow_sel, bool want_grad, bool ge_tab,
-                  bool fuse_hint, bool flow_limit, bool lag, int lag_units, int rank_extra, bool never_fuse) {
-  // (lag_units: LDS footprint of one lag table in 256-double units — 1 on a sorted sweep, n_max / 256 for rank tables; rank_extra > 0:
-  // rank / compact tables — that many units for the tile's ranks or keys (in k_cov_tiles: and the exponential table behind them; also
-  // when n_max <= 256) and, with compact tables, the B entries the tile stages)
+int compile_batch(agp_ctx* c, const Particles& pp, Batch& bt, const CompileOpts& o) {
+  const int P = pp.P;
   std::vector<Compiled> cps(P);
   std::vector<double> cost(P, 0.0);
   for (int p = 0; p < P; ++p) {
-    const char* e = compile_program(ops + op_off[p], op_off[p + 1] - op_off[p], prm + prm_off[p],
-                                    prm_off[p + 1] - prm_off[p], cps[p], allow_sel, ge_tab && !lag, lag);
+    const char* e = compile_program(pp.program(p), pp.n_ops(p), pp.params(p), pp.n_prm(p), cps[p], o.allow_sel, o.ge_tab && !o.lag, o.lag);
     if (e) {
       char buf[256];
       snprintf(buf, sizeof buf, "particle %d: %s", p, e);
@@ -339,19 +342,17 @@ int compile_batch(agp_ctx* c, int P, const int32_t* op_off, const uint8_t* ops, 
   }
   // Sort: fused particles first, most expensive evaluation first (their workgroups are dispatched
   // first inside every launch); particles whose tiles are prebuilt go last.
-  // (fuse_hint: the caller will run the dataflow schedule, which evaluates tiles in-kernel whatever the batch size)
-  // (never_fuse: the factor store's sweeps over a series of at most two tile rows, see extend_impl)
-  const bool fuse_on = !never_fuse && (c->fuse_mode == 1 || (c->fuse_mode < 0 && (P >= 256 || fuse_hint)));
+  const bool fuse_on = !o.never_fuse && (c->fuse_mode == 1 || (c->fuse_mode < 0 && (P >= 256 || o.fuse_hint)));
   // (the dataflow schedule has no launch tail for a long evaluation to hold up: its limit is higher — measured 35 / 70 /
   // 150 / 1000 us: config 2 0.99 / 0.92 / 0.92 / 0.91 ms, 2048 x 64 4.47 / 4.45 / 4.61 / 4.62 ms, config 4 62.9 / 61.9 / 63.6 / 63.6 ms)
-  const double fuse_limit = flow_limit ? (lag ? FLOW_LAG_FUSE_MAX_US : FLOW_FUSE_MAX_US) : (lag ? LAG_FUSE_MAX_US : FUSE_MAX_US);
+  const double fuse_limit = o.flow_limit ? (o.lag ? FLOW_LAG_FUSE_MAX_US : FLOW_FUSE_MAX_US) : (o.lag ? LAG_FUSE_MAX_US : FUSE_MAX_US);
   // (lag sweeps: the same price limit with the lag leaves' price — a 30-leaf tree still costs ~80 us per tile in interpreter
   // latency, measured: fusing everything made every diagonal-tile launch wait 110 us for the largest tree and forced the
   // depth-8 instantiation on the whole batch, 29.4 -> 31.0 ms per 512-particle sweep; a program that carries direct
   // stationary leaves there — see compile_program — must be prebuilt: the GM = 2 instantiations have no transcendental code)
   auto lag_ok = [&](int p) { bool direct = false; for (uint8_t o : cps[p].ops) direct |= (o == OP_SE || o == OP_GE || o == OP_PER || o == OP_GE_TAB); return !direct; };
   auto fusable = [&](int p) {
-    if (lag) return fuse_on && cost[p] <= fuse_limit && lag_ok(p) && cps[p].n_cp + cps[p].n_lag * lag_units + rank_extra <= U_MAX_CP;
+    if (o.lag) return fuse_on && cost[p] <= fuse_limit && lag_ok(p) && cps[p].n_cp + cps[p].n_lag * o.lag_units + o.rank_extra <= U_MAX_CP;
     return fuse_on && cost[p] <= fuse_limit && cps[p].n_cp <= U_MAX_CP;
   };
   bt.order.resize(P);
@@ -382,8 +383,8 @@ int compile_batch(agp_ctx* c, int P, const int32_t* op_off, const uint8_t* ops, 
     bt.hdr[q] = h;
     bt.ops.insert(bt.ops.end(), cp.ops.begin(), cp.ops.end());
     bt.prm.insert(bt.prm.end(), cp.prm.begin(), cp.prm.end());
-    const int lds_units = cp.n_cp + cp.n_lag * lag_units + rank_extra;      // LDS tables of any kind (per-point + lag), 256 doubles each
-    bt.max_cp = std::max(bt.max_cp, rank_extra > 0 ? cp.n_cp + 1 : lds_units);      // (k_cov_tiles reads rank / compact tables, and B, in place)
+    const int lds_units = cp.n_cp + cp.n_lag * o.lag_units + o.rank_extra;      // LDS tables of any kind (per-point + lag), 256 doubles each
+    bt.max_cp = std::max(bt.max_cp, o.rank_extra > 0 ? cp.n_cp + 1 : lds_units);      // (k_cov_tiles reads rank / compact tables, and B, in place)
     bt.max_depth = std::max(bt.max_depth, cp.depth_need);
     if (fusable(bt.order[q])) {
       bt.n_fused = q + 1;
@@ -391,7 +392,7 @@ int compile_batch(agp_ctx* c, int P, const int32_t* op_off, const uint8_t* ops, 
       bt.max_depth_fused = std::max(bt.max_depth_fused, cp.depth_need);
     }
   }
-  if (want_grad) {
+  if (o.want_grad) {
     bt.ghdr.resize(P);
     for (int q = 0; q < P; ++q) {
       const Compiled& cp = cps[bt.order[q]];
@@ -548,50 +549,6 @@ hipError_t run_factor(hipStream_t st, CholArgs ca, int nfac, int dcov, Prof* pf,
 
 // Core of agp_logpdf_batch{,_device} and agp_logpdf_grad_batch.  d_out_* may be caller device
 // buffers (user_stream path) or null (results copied to host h_out_*).
-std::string particle_key(const uint8_t* ops, int no, const double* prm, int np, double noise) {
-  std::string key;
-  const int32_t lens[2] = {no, np};
-  key.assign(reinterpret_cast<const char*>(lens), sizeof lens);
-  key.append(reinterpret_cast<const char*>(ops), (size_t)no);
-  key.append(reinterpret_cast<const char*>(prm), sizeof(double) * (size_t)np);
-  key.append(reinterpret_cast<const char*>(&noise), sizeof(double));
-  return key;
-}
-
-bool distinct_particles(int P, const int32_t* op_off, const uint8_t* ops, const int32_t* prm_off, const double* prm, const double* noise,
-                        const double* noise_pred, std::vector<int>& rep, std::vector<int>& uniq, std::vector<std::string>* keys) {
-  rep.clear(); uniq.clear();
-  if (keys) keys->clear();
-  for (int p = 0; p < P; ++p)
-    if (op_off[p + 1] < op_off[p] || prm_off[p + 1] < prm_off[p] || op_off[p] < 0 || prm_off[p] < 0) return false;
-  std::unordered_map<std::string, int> seen;
-  seen.reserve((size_t)P * 2);
-  rep.resize((size_t)P);
-  for (int p = 0; p < P; ++p) {
-    std::string key = particle_key(ops + op_off[p], op_off[p + 1] - op_off[p], prm + prm_off[p], prm_off[p + 1] - prm_off[p], noise[p]);
-    if (noise_pred) key.append(reinterpret_cast<const char*>(noise_pred + p), sizeof(double));
-    const auto it = seen.try_emplace(std::move(key), (int)uniq.size());
-    rep[(size_t)p] = it.first->second;
-    if (it.second) { uniq.push_back(p); if (keys) keys->push_back(it.first->first); }
-  }
-  return true;
-}
-
-void pack_particles(const std::vector<int>& ix, const int32_t* op_off, const uint8_t* ops, const int32_t* prm_off, const double* prm,
-                    const double* noise, const double* noise_pred, SubBatch& S) {
-  const size_t B = ix.size();
-  S.op_off.assign(B + 1, 0); S.prm_off.assign(B + 1, 0); S.ops.clear(); S.prm.clear();
-  S.noise.resize(B); S.noise_pred.resize(noise_pred ? B : 0);
-  for (size_t b = 0; b < B; ++b) {
-    const int p = ix[b];
-    S.ops.insert(S.ops.end(), ops + op_off[p], ops + op_off[p + 1]);
-    S.prm.insert(S.prm.end(), prm + prm_off[p], prm + prm_off[p + 1]);
-    S.op_off[b + 1] = (int32_t)S.ops.size(); S.prm_off[b + 1] = (int32_t)S.prm.size();
-    S.noise[b] = noise[p];
-    if (noise_pred) S.noise_pred[b] = noise_pred[p];
-  }
-  if (S.prm.empty()) S.prm.push_back(0.0);
-}
 // Factor-store lookup for a compiled batch (sorted order q -> caller index bt.order[q]): src_slot[q] = the slot that holds
 // the POSITIVE DEFINITE factor of particle q for exactly the prefix n (else -1), i0v[q] = nt for those (no tile row left to
 // compute).  Returns the number found; `lk` is held on return iff it is > 0 (the caller copies the factors out, then
@@ -665,12 +622,14 @@ bool toeplitz_class(const uint8_t* ops, int n_ops) {
 
 // The class's particles of one value sweep over the whole (regular, sorted) series: rank-layout lag tables, then one workgroup
 // per particle.  Outputs in the sub-batch's order; info 1 = refused (not positive definite to rounding).
-static int toeplitz_sweep(agp_ctx* c, int64_t n, int32_t rank0, int P, const int32_t* op_off, const uint8_t* ops, const int32_t* prm_off,
-                          const double* prm, const double* noise, double* out_lp, int32_t* out_info) {
+static int toeplitz_sweep(agp_ctx* c, int64_t n, int32_t rank0, const Particles& pp, double* out_lp, int32_t* out_info) {
+  const int P = pp.P;
   HIPCHK(c, hipSetDevice(c->device));          // (may run on a helper thread: the device is per thread)
   Batch bt;
   const int rank_units = (int)((c->n_max + 255) / 256);
-  int rc = compile_batch(c, P, op_off, ops, prm_off, prm, bt, false, false, false, false, false, true, rank_units, true);
+  CompileOpts co;
+  co.lag = true; co.lag_units = rank_units; co.rank_extra = 1;
+  int rc = compile_batch(c, pp, bt, co);
   if (rc) return rc;
   SlotGuard sg(c);
   Slot* s = sg.s;
@@ -678,7 +637,7 @@ static int toeplitz_sweep(agp_ctx* c, int64_t n, int32_t rank0, int P, const int
   hipStream_t st = s->stream;
   const LagProgLayout lpl(bt);
   std::vector<double> nz((size_t)P);
-  for (int q = 0; q < P; ++q) nz[(size_t)q] = noise[bt.order[q]];
+  for (int q = 0; q < P; ++q) nz[(size_t)q] = pp.noise[bt.order[q]];
   HIPCHK(c, s->hdr.ensure(sizeof(ProgHdr) * (size_t)P));
   HIPCHK(c, s->ops.ensure(bt.ops.size() + 4));
   HIPCHK(c, s->prm.ensure(sizeof(double) * std::max<size_t>(1, bt.prm.size())));
@@ -725,13 +684,15 @@ static int toeplitz_sweep(agp_ctx* c, int64_t n, int32_t rank0, int P, const int
 // the columns of L and the forward-solved right-hand sides, a backward substitution turns them into T^-1 [x, e_first, 1, t], and
 // k_lag_grad (GFLAG_LAGTSOL) forms alpha, the lag sums of K^-1 (Gohberg-Semencul + W S W') and the gradient — no dense factor.
 // Outputs in the sub-batch's order; info 1 = refused.
-static int toeplitz_grad_sweep(agp_ctx* c, int64_t n, int32_t rank0, int P, const int32_t* op_off, const uint8_t* ops, const int32_t* prm_off,
-                               const double* prm, const double* noise, double* out_lp, int32_t* out_info, double* out_grad,
-                               double* out_gnoise) {
+static int toeplitz_grad_sweep(agp_ctx* c, int64_t n, int32_t rank0, const Particles& pp, double* out_lp, int32_t* out_info,
+                               double* out_grad, double* out_gnoise) {
+  const int P = pp.P;
   HIPCHK(c, hipSetDevice(c->device));          // (runs on a helper thread: the device is per thread)
   Batch bt;
   const int rank_units = (int)((c->n_max + 255) / 256);
-  int rc = compile_batch(c, P, op_off, ops, prm_off, prm, bt, false, true, false, false, false, true, rank_units, true);
+  CompileOpts co;
+  co.want_grad = true; co.lag = true; co.lag_units = rank_units; co.rank_extra = 1;
+  int rc = compile_batch(c, pp, bt, co);
   if (rc) return rc;
   if (bt.g_max_nodes > 64) return fail(c, AGP_ERR_PROGRAM, "gradient supports kernel trees of up to 64 nodes");
   for (int q = 0; q < P; ++q) bt.ghdr[q].flags |= GFLAG_LAGDOM | GFLAG_LAGTOEP | GFLAG_LAGTSOL;
@@ -741,10 +702,10 @@ static int toeplitz_grad_sweep(agp_ctx* c, int64_t n, int32_t rank0, int P, cons
   hipStream_t st = s->stream;
   const LagProgLayout lpl(bt);
   const int n_pad = round_up(n, NB);
-  const int n_prm_total = prm_off[P];
+  const int n_prm_total = pp.prm_off[P];
   std::vector<double> nz((size_t)P);
   std::vector<int32_t> goff((size_t)P), plist((size_t)P);
-  for (int q = 0; q < P; ++q) { nz[(size_t)q] = noise[bt.order[q]]; goff[(size_t)q] = prm_off[bt.order[q]]; plist[(size_t)q] = q; }
+  for (int q = 0; q < P; ++q) { nz[(size_t)q] = pp.noise[bt.order[q]]; goff[(size_t)q] = pp.prm_off[bt.order[q]]; plist[(size_t)q] = q; }
   const long long Lstride = (long long)n * (n + 1) / 2;
   const int chunk = (int)std::max<int64_t>(1, std::min<int64_t>(P, ws_limit_bytes(c) / (Lstride * 8)));
   HIPCHK(c, s->hdr.ensure(sizeof(ProgHdr) * (size_t)P));
@@ -861,15 +822,14 @@ struct TlClear {          // a thread-local switch cleared for a scope (the stor
 // (set around the repeat of particles whose Toeplitz downdate was rejected: the nested sweep takes L^-T for them)
 static thread_local bool tl_no_toep = false;
 
-int logpdf_batch_impl(agp_ctx* c, int64_t n, int32_t P, const int32_t* op_off, const uint8_t* ops,
-                      const int32_t* prm_off, const double* prm, const double* noise,
-                      double* h_out_lp, int32_t* h_out_info, double* d_user_lp, int32_t* d_user_info,
-                      hipStream_t user_stream, bool use_user_stream, GradOut* go, bool allow_lag) {
+int logpdf_batch_impl(agp_ctx* c, int64_t n, const Particles& pp, double* h_out_lp, int32_t* h_out_info, double* d_user_lp,
+                      int32_t* d_user_info, hipStream_t user_stream, bool use_user_stream, GradOut* go, bool allow_lag) {
+  const int P = pp.P;
   if (!c) return fail(nullptr, AGP_ERR_ARG, "null context");
   if (P < 0 || n < 0) return fail(c, AGP_ERR_ARG, "negative size");
   if (P == 0) return AGP_OK;
-  if (!op_off || !ops || !prm_off || !prm || !noise) return fail(c, AGP_ERR_ARG, "null program/noise pointer");
-  if (n > c->n_max) return fail(c, AGP_ERR_NODATA, "n exceeds the data uploaded with agp_set_data");
+  if (!pp.complete()) return fail(c, AGP_ERR_ARG, "null program/noise pointer");
+  if (const int rc = check_resident(c, n)) return rc;
   HIPCHK(c, hipSetDevice(c->device));
 
   // Structured value sweep (opt-in): on a regular grid, the particles whose kernel is a sum of stationary subtrees and Linear
@@ -889,12 +849,11 @@ int logpdf_batch_impl(agp_ctx* c, int64_t n, int32_t P, const int32_t* op_off, c
   if (!go && c->toeplitz && !tl_in_toeplitz && allow_lag && c->lag_enable && c->lag_ok && c->lag_contig && n > 0 && value_consecutive && c->n_max <= 4096 &&
       h_out_lp && !d_user_lp && !d_user_info && !use_user_stream && !c->profiling) {
     std::vector<int> part[2];
-    bool sane = true;
     // (malformed offsets are left to compile_batch's diagnosis on the plain path: the split below indexes with them)
-    for (int p = 0; p < P && sane; ++p)
-      sane = op_off[p] >= 0 && prm_off[p] >= 0 && op_off[p + 1] >= op_off[p] && prm_off[p + 1] >= prm_off[p] && op_off[p + 1] - op_off[p] <= AGP_MAX_OPS_DEV;
+    bool sane = offsets_sane(pp);
+    for (int p = 0; p < P && sane; ++p) sane = pp.n_ops(p) <= AGP_MAX_OPS_DEV;
     if (sane)
-      for (int p = 0; p < P; ++p) part[toeplitz_class(ops + op_off[p], op_off[p + 1] - op_off[p]) ? 1 : 0].push_back(p);
+      for (int p = 0; p < P; ++p) part[toeplitz_class(pp.program(p), pp.n_ops(p)) ? 1 : 0].push_back(p);
     // (worth it when the class's share of a dense sweep costs more than the n sequential steps of the recursion:
     // ~50 us per particle at n = 2048 against ~0.7 us per step + ~0.4 ms of sub-batch overheads; level 3 forces it)
     const int64_t n_cls_v = (int64_t)part[1].size();
@@ -906,11 +865,10 @@ int logpdf_batch_impl(agp_ctx* c, int64_t n, int32_t P, const int32_t* op_off, c
       // the two sub-sweeps (own slots and streams)
       const bool via_store = tl_dense_via_store;          // (read here: the structured half may run on a helper thread)
       SubBatch sT, sD;
-      pack_particles(part[1], op_off, ops, prm_off, prm, noise, nullptr, sT);
+      pack_particles(part[1], pp, sT);
       sT.outputs(false);
       auto structured = [&] {
-        return toeplitz_sweep(c, n, value_rank0, sT.size(), sT.op_off.data(), sT.ops.data(), sT.prm_off.data(), sT.prm.data(), sT.noise.data(),
-                              sT.lp.data(), sT.info.data());
+        return toeplitz_sweep(c, n, value_rank0, sT.view(), sT.lp.data(), sT.info.data());
       };
       // (measured: 107 recursions beside the dense kernels at n = 4096: 18.1 -> 13.8 ms; 423 of them at n = 2048 fill every SIMD
       // with their own waves and only delay the dense kernels: 8.6 -> 9.2 ms — those go first, alone)
@@ -921,17 +879,16 @@ int logpdf_batch_impl(agp_ctx* c, int64_t n, int32_t P, const int32_t* op_off, c
       if (side_by_side) side.reset(new Beside(structured)); else rcT = structured();
       auto dense = [&](const std::vector<int>& ix) {
         if (ix.empty()) return 0;
-        pack_particles(ix, op_off, ops, prm_off, prm, noise, nullptr, sD);
+        pack_particles(ix, pp, sD);
         sD.outputs(false);
         TlFlag nested(tl_in_toeplitz);
         int rc0;
         if (via_store) {
           TlClear plain(tl_dense_via_store);
-          rc0 = extend_impl(c, n, sD.size(), sD.op_off.data(), sD.ops.data(), sD.prm_off.data(), sD.prm.data(), sD.noise.data(), sD.lp.data(),
+          rc0 = extend_impl(c, n, sD.view(), sD.lp.data(),
                             sD.info.data());
         } else {
-          rc0 = logpdf_batch_impl(c, n, sD.size(), sD.op_off.data(), sD.ops.data(), sD.prm_off.data(), sD.prm.data(), sD.noise.data(),
-                                  sD.lp.data(), sD.info.data(), nullptr, nullptr, nullptr, false, nullptr, allow_lag);
+          rc0 = logpdf_batch_impl(c, n, sD.view(), sD.lp.data(), sD.info.data(), nullptr, nullptr, nullptr, false, nullptr, allow_lag);
         }
         if (rc0) return rc0;
         for (size_t b2 = 0; b2 < ix.size(); ++b2) { h_out_lp[ix[b2]] = sD.lp[b2]; if (h_out_info) h_out_info[ix[b2]] = sD.info[b2]; }
@@ -955,7 +912,7 @@ int logpdf_batch_impl(agp_ctx* c, int64_t n, int32_t P, const int32_t* op_off, c
           for (size_t b2 = 0; b2 < part[1].size(); ++b2)
             if (sT.info[b2] == 0) {
               const int p = part[1][b2];
-              c->schur_keys.insert(particle_key(ops + op_off[p], op_off[p + 1] - op_off[p], prm + prm_off[p], prm_off[p + 1] - prm_off[p], noise[p]));
+              c->schur_keys.insert(particle_key(pp, p));
             }
         }
       }
@@ -968,7 +925,7 @@ int logpdf_batch_impl(agp_ctx* c, int64_t n, int32_t P, const int32_t* op_off, c
   if (tl_dense_via_store && !go && h_out_lp && h_out_info) {
     // (no structured split for this batch: the whole of it goes through the store, as the coalesced entry does by default)
     TlClear plain(tl_dense_via_store);
-    return extend_impl(c, n, P, op_off, ops, prm_off, prm, noise, h_out_lp, h_out_info);
+    return extend_impl(c, n, pp, h_out_lp, h_out_info);
   }
   Batch bt;
   std::vector<std::vector<int32_t>> pls;     // per-group particle orders of the gradient contraction
@@ -1006,7 +963,10 @@ int logpdf_batch_impl(agp_ctx* c, int64_t n, int32_t P, const int32_t* op_off, c
   const int rank_extra = (cltw || clts) ? (256 + clt_nB + 511) / 512 : lagr ? 1 : 0;
   const bool sorted = lag || clts;          // the sweep runs on the sorted copy of the series (d_ts_s / d_xs_s)
   HostProf hp_cb(2);
-  int rc = compile_batch(c, P, op_off, ops, prm_off, prm, bt, false, go != nullptr, ge_tab, flow_hint, flow_hint, lag || rankm, rankm ? tab_units : 1, rank_extra);
+  CompileOpts co;
+  co.want_grad = go != nullptr; co.ge_tab = ge_tab; co.fuse_hint = co.flow_limit = flow_hint;
+  co.lag = lag || rankm; co.lag_units = rankm ? tab_units : 1; co.rank_extra = rank_extra;
+  int rc = compile_batch(c, pp, bt, co);
   hp_cb.stop();
   if (rc) return rc;
   HostProf hp_cls(3);
@@ -1074,7 +1034,7 @@ int logpdf_batch_impl(agp_ctx* c, int64_t n, int32_t P, const int32_t* op_off, c
       for (int q = 0; q < P; ++q) {
         if (!(bt.ghdr[q].flags & GFLAG_LAGTOEP)) continue;
         const int p = bt.order[q];
-        auto it = fs.index.find(particle_key(ops + op_off[p], op_off[p + 1] - op_off[p], prm + prm_off[p], prm_off[p + 1] - prm_off[p], noise[p]));
+        auto it = fs.index.find(particle_key(pp, p));
         if (it != fs.index.end() && fs.n_cached[(size_t)it->second] == n && fs.info_h[(size_t)it->second] == 0) { resident[(size_t)q] = 1; --n_struct; }
       }
     }
@@ -1087,7 +1047,7 @@ int logpdf_batch_impl(agp_ctx* c, int64_t n, int32_t P, const int32_t* op_off, c
         for (int q = 0; q < P && !sticky; ++q) {
           if (!(bt.ghdr[q].flags & GFLAG_LAGTOEP) || resident[(size_t)q]) continue;
           const int p = bt.order[q];
-          sticky = c->schur_keys.erase(particle_key(ops + op_off[p], op_off[p + 1] - op_off[p], prm + prm_off[p], prm_off[p + 1] - prm_off[p], noise[p])) > 0;
+          sticky = c->schur_keys.erase(particle_key(pp, p)) > 0;
         }
     }
     const bool struct_pays = c->grad_struct >= 2 || sticky || struct_grad_pays(n_struct, n);
@@ -1102,27 +1062,25 @@ int logpdf_batch_impl(agp_ctx* c, int64_t n, int32_t P, const int32_t* op_off, c
           if (refused && S.info[b] != 0) { refused->push_back(p); continue; }
           h_out_lp[p] = S.lp[b];
           if (h_out_info) h_out_info[p] = S.info[b];
-          std::copy(S.grad.begin() + S.prm_off[b], S.grad.begin() + S.prm_off[b + 1], go->grad + prm_off[p]);
+          std::copy(S.grad.begin() + S.prm_off[b], S.grad.begin() + S.prm_off[b + 1], go->grad + pp.prm_off[p]);
           go->gnoise[p] = S.gnoise[b];
         }
       };
       auto dense = [&](const std::vector<int>& ix) {
         if (ix.empty()) return 0;
-        pack_particles(ix, op_off, ops, prm_off, prm, noise, nullptr, sD);
+        pack_particles(ix, pp, sD);
         sD.outputs(true);
         GradOut dgo{sD.grad.data(), sD.gnoise.data()};
         TlFlag nested(tl_in_tgrad);
-        const int rc0 = logpdf_batch_impl(c, n, sD.size(), sD.op_off.data(), sD.ops.data(), sD.prm_off.data(), sD.prm.data(), sD.noise.data(),
-                                          sD.lp.data(), sD.info.data(), nullptr, nullptr, nullptr, false, &dgo, allow_lag);
+        const int rc0 = logpdf_batch_impl(c, n, sD.view(), sD.lp.data(), sD.info.data(), nullptr, nullptr, nullptr, false, &dgo, allow_lag);
         if (rc0) return rc0;
         scatter(ix, sD, nullptr);
         return 0;
       };
-      pack_particles(part[1], op_off, ops, prm_off, prm, noise, nullptr, sT);
+      pack_particles(part[1], pp, sT);
       sT.outputs(true);
       Beside side([&] {
-        return toeplitz_grad_sweep(c, n, toep_rank0, sT.size(), sT.op_off.data(), sT.ops.data(), sT.prm_off.data(), sT.prm.data(), sT.noise.data(),
-                                   sT.lp.data(), sT.info.data(), sT.grad.data(), sT.gnoise.data());
+        return toeplitz_grad_sweep(c, n, toep_rank0, sT.view(), sT.lp.data(), sT.info.data(), sT.grad.data(), sT.gnoise.data());
       });
       const int rcD = dense(part[0]);
       const int rcT = side.join();
@@ -1144,7 +1102,7 @@ int logpdf_batch_impl(agp_ctx* c, int64_t n, int32_t P, const int32_t* op_off, c
     any_toep_sweep = use_toep && n_sum > 0;
   }
   hp_cls.stop();
-  const int n_prm_total = prm_off[P];
+  const int n_prm_total = pp.prm_off[P];
   if (go && n == 0) {
     for (int i = 0; i < n_prm_total; ++i) go->grad[i] = 0.0;
     for (int p = 0; p < P; ++p) go->gnoise[p] = 0.0;
@@ -1160,7 +1118,7 @@ int logpdf_batch_impl(agp_ctx* c, int64_t n, int32_t P, const int32_t* op_off, c
   if (go && n > 0 && c->factor_cache && c->store.n_slots > 0) {
     std::vector<std::string> keys((size_t)P);
     for (int p = 0; p < P; ++p)
-      keys[p] = particle_key(ops + op_off[p], op_off[p + 1] - op_off[p], prm + prm_off[p], prm_off[p + 1] - prm_off[p], noise[p]);
+      keys[p] = particle_key(pp, p);
     n_hit = store_lookup(c, keys, bt.order, P, n, (int)((n + NB - 1) / NB), src_slot, i0v, store_lk);
     std::lock_guard<std::mutex> g(c->mu);
     c->grad_reused += n_hit; c->grad_factored += P - n_hit;
@@ -1247,7 +1205,7 @@ int logpdf_batch_impl(agp_ctx* c, int64_t n, int32_t P, const int32_t* op_off, c
       std::memcpy(h + o_hdr, bt.hdr.data(), sizeof(ProgHdr) * (size_t)P);
       if (!bt.prm.empty()) std::memcpy(h + o_prm, bt.prm.data(), sizeof(double) * bt.prm.size());
       double* hn = reinterpret_cast<double*>(h + o_noise);
-      for (int q = 0; q < P; ++q) hn[q] = noise[bt.order[q]];
+      for (int q = 0; q < P; ++q) hn[q] = pp.noise[bt.order[q]];
       std::memcpy(h + o_map, bt.order.data(), sizeof(int32_t) * (size_t)P);
       std::memcpy(h + o_ops, bt.ops.data(), bt.ops.size());
       if (n_hit > 0) {
@@ -1274,7 +1232,7 @@ int logpdf_batch_impl(agp_ctx* c, int64_t n, int32_t P, const int32_t* op_off, c
     std::vector<int32_t> goff_sorted;
     if (go) {
       goff_sorted.resize(P);
-      for (int q = 0; q < P; ++q) goff_sorted[q] = prm_off[bt.order[q]];
+      for (int q = 0; q < P; ++q) goff_sorted[q] = pp.prm_off[bt.order[q]];
       PinnedUploads up;
       up.add(s->ghdr.p, bt.ghdr.data(), sizeof(GProgHdr) * P);
       up.add(s->gops.p, bt.gops.data(), bt.gops.size());
@@ -1622,7 +1580,7 @@ int logpdf_batch_impl(agp_ctx* c, int64_t n, int32_t P, const int32_t* op_off, c
     if (!rp.empty()) {
       const int B = (int)rp.size();
       SubBatch S;
-      pack_particles(rp, op_off, ops, prm_off, prm, noise, nullptr, S);
+      pack_particles(rp, pp, S);
       S.outputs(true);
       GradOut bgo{S.grad.data(), S.gnoise.data()};
       if (store_lk.owns_lock()) store_lk.unlock();
@@ -1630,13 +1588,13 @@ int logpdf_batch_impl(agp_ctx* c, int64_t n, int32_t P, const int32_t* op_off, c
       int rc2;
       {
         TlFlag nested(tl_no_toep);
-        rc2 = logpdf_batch_impl(c, n, B, S.op_off.data(), S.ops.data(), S.prm_off.data(), S.prm.data(), S.noise.data(), S.lp.data(),
+        rc2 = logpdf_batch_impl(c, n, S.view(), S.lp.data(),
                                 S.info.data(), nullptr, nullptr, nullptr, false, &bgo, allow_lag);
       }
       if (rc2) return rc2;
       for (int b = 0; b < B; ++b) {
         const int p = rp[b];
-        std::copy(S.grad.begin() + S.prm_off[b], S.grad.begin() + S.prm_off[b + 1], go->grad + prm_off[p]);
+        std::copy(S.grad.begin() + S.prm_off[b], S.grad.begin() + S.prm_off[b + 1], go->grad + pp.prm_off[p]);
         go->gnoise[p] = S.gnoise[b];
       }
       std::lock_guard<std::mutex> g(c->mu);
@@ -1653,12 +1611,12 @@ int logpdf_batch_impl(agp_ctx* c, int64_t n, int32_t P, const int32_t* op_off, c
     if (!bad.empty()) {
       const int B = (int)bad.size();
       SubBatch S;
-      pack_particles(bad, op_off, ops, prm_off, prm, noise, nullptr, S);
+      pack_particles(bad, pp, S);
       S.outputs(false);
       // (the results are on the host: hand the slot back first — sixteen concurrent callers that each kept theirs while waiting
       // for a second one would wait for ever)
       sg.release();
-      const int rc2 = logpdf_batch_impl(c, n, B, S.op_off.data(), S.ops.data(), S.prm_off.data(), S.prm.data(), S.noise.data(), S.lp.data(),
+      const int rc2 = logpdf_batch_impl(c, n, S.view(), S.lp.data(),
                                         S.info.data(), nullptr, nullptr, nullptr, false, nullptr, /*allow_lag=*/false);
       if (rc2) return rc2;
       for (int b = 0; b < B; ++b) {
@@ -1679,64 +1637,62 @@ extern "C" {
 
 const char* agp_version(void) { return "autogp-hip 0.1.0 (gfx950)"; }
 
-static int init_body(agp_ctx** out, int device_id);
 int agp_init(agp_ctx** out, int device_id) {
-  return abi_guard(nullptr, [&] { return init_body(out, device_id); });
-}
-static int init_body(agp_ctx** out, int device_id) {
-  if (!out) return fail(nullptr, AGP_ERR_ARG, "null out pointer");
-  *out = nullptr;
-  int ndev = 0;
-  hipError_t e = hipGetDeviceCount(&ndev);
-  if (e != hipSuccess || ndev <= 0)
-    return fail(nullptr, AGP_ERR_HIP, "no HIP device available (this engine has no CPU fallback)");
-  if (device_id < 0 || device_id >= ndev) return fail(nullptr, AGP_ERR_ARG, "device id out of range");
-  if (hipSetDevice(device_id) != hipSuccess) return fail(nullptr, AGP_ERR_HIP, "hipSetDevice failed");
-  hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, device_id) != hipSuccess)
-    return fail(nullptr, AGP_ERR_HIP, "hipGetDeviceProperties failed");
-  if (std::string(prop.gcnArchName).rfind("gfx950", 0) != 0) {
-    std::string m = std::string("device is ") + prop.gcnArchName + ", this library is built for gfx950 only";
-    return fail(nullptr, AGP_ERR_HIP, m);
-  }
-  {
-    // raise the dynamic-LDS ceiling of the table-carrying kernels once (launches then never touch function attributes)
-    hipError_t ea = kernels_init();
-    if (ea == hipSuccess) ea = kernels_init_grad();
-    if (ea != hipSuccess) {
-      std::string m = std::string("hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed: ") + hipGetErrorString(ea);
+  return abi_guard(nullptr, [&]() -> int {
+    if (!out) return fail(nullptr, AGP_ERR_ARG, "null out pointer");
+    *out = nullptr;
+    int ndev = 0;
+    hipError_t e = hipGetDeviceCount(&ndev);
+    if (e != hipSuccess || ndev <= 0)
+      return fail(nullptr, AGP_ERR_HIP, "no HIP device available (this engine has no CPU fallback)");
+    if (device_id < 0 || device_id >= ndev) return fail(nullptr, AGP_ERR_ARG, "device id out of range");
+    if (hipSetDevice(device_id) != hipSuccess) return fail(nullptr, AGP_ERR_HIP, "hipSetDevice failed");
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, device_id) != hipSuccess)
+      return fail(nullptr, AGP_ERR_HIP, "hipGetDeviceProperties failed");
+    if (std::string(prop.gcnArchName).rfind("gfx950", 0) != 0) {
+      std::string m = std::string("device is ") + prop.gcnArchName + ", this library is built for gfx950 only";
       return fail(nullptr, AGP_ERR_HIP, m);
     }
-  }
-  agp_ctx* c = new agp_ctx();
-  c->device = device_id;
-  size_t free_b = 0, tot_b = 0;
-  (void)hipMemGetInfo(&free_b, &tot_b);
-  c->total_mem = free_b ? free_b : tot_b;
-  c->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  if (const char* e = getenv("AGP_FUSE")) c->fuse_mode = atoi(e);
-  if (const char* e = getenv("AGP_SPLIT_DIAG")) c->split_diag = atoi(e);
-  if (const char* e = getenv("AGP_GE_TABLE")) c->ge_table = atoi(e) != 0;
-  if (const char* e = getenv("AGP_LAG")) { c->lag_enable = atoi(e) != 0; c->toeplitz = atoi(e) >= 3 ? 2 : atoi(e) >= 2 ? 1 : 0; }
-  if (const char* e = getenv("AGP_LAG_RANK")) c->lag_rank_enable = atoi(e) != 0;
-  if (const char* e = getenv("AGP_LATTICE")) c->lattice_enable = atoi(e) != 0;
-  if (const char* e = getenv("AGP_GRAD_LAGDOM")) c->grad_lagdom = std::max(0, std::min(2, atoi(e)));
-  if (const char* e = getenv("AGP_GRAD_FFT")) { c->grad_fft = std::max(0, std::min(2, atoi(e))); c->grad_struct = atoi(e) >= 4 ? 2 : atoi(e) >= 3 ? 1 : 0; }
-  if (const char* e = getenv("AGP_RIGHT_LOOKING")) c->right_looking = atoi(e);
-  if (const char* e = getenv("AGP_DEDUP")) c->dedup = atoi(e) != 0;
-  if (const char* e = getenv("AGP_PREDICT_REUSE")) c->predict_reuse = atoi(e) != 0;
-  if (const char* e = getenv("AGP_REMOVE_UPDATE")) c->remove_update = std::max(0, std::min(2, atoi(e)));
-  if (const char* e = getenv("AGP_FACTOR_CACHE")) c->factor_cache = atoi(e) != 0;
-  if (const char* e = getenv("AGP_COALESCE_US")) c->coalesce_us = std::max(0, atoi(e));
-  if (const char* e = getenv("AGP_FLOW")) c->flow = atoi(e);
-  if (const char* e = getenv("AGP_EXTEND_FRAC")) c->store.max_frac = std::max(0.0, std::min(0.8, atof(e)));
-  if (const char* e = getenv("AGP_POISON")) c->poison.on = atoi(e) != 0;      // checking switch: no path changes
-  for (DevBuf* b : {&c->store.A, &c->store.W, &c->store.vec, &c->store.partial, &c->store.info, &c->store.ready, &c->store.tflag,
-                    &c->store.flowq, &c->store.Z, &c->store.zalpha, &c->store.zdinv, &c->comm_in, &c->comm_out, &c->comm_all})
-    b->pz = &c->poison;
-  if (const char* e = getenv("AGP_REFERENCE_ARITHMETIC")) { if (atoi(e) != 0) apply_reference_arithmetic(c); }      // (overrides the switches above)
-  *out = c;
-  return AGP_OK;
+    {
+      // raise the dynamic-LDS ceiling of the table-carrying kernels once (launches then never touch function attributes)
+      hipError_t ea = kernels_init();
+      if (ea == hipSuccess) ea = kernels_init_grad();
+      if (ea != hipSuccess) {
+        std::string m = std::string("hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed: ") + hipGetErrorString(ea);
+        return fail(nullptr, AGP_ERR_HIP, m);
+      }
+    }
+    agp_ctx* c = new agp_ctx();
+    c->device = device_id;
+    size_t free_b = 0, tot_b = 0;
+    (void)hipMemGetInfo(&free_b, &tot_b);
+    c->total_mem = free_b ? free_b : tot_b;
+    c->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    if (const char* e = getenv("AGP_FUSE")) c->fuse_mode = atoi(e);
+    if (const char* e = getenv("AGP_SPLIT_DIAG")) c->split_diag = atoi(e);
+    if (const char* e = getenv("AGP_GE_TABLE")) c->ge_table = atoi(e) != 0;
+    if (const char* e = getenv("AGP_LAG")) { c->lag_enable = atoi(e) != 0; c->toeplitz = atoi(e) >= 3 ? 2 : atoi(e) >= 2 ? 1 : 0; }
+    if (const char* e = getenv("AGP_LAG_RANK")) c->lag_rank_enable = atoi(e) != 0;
+    if (const char* e = getenv("AGP_LATTICE")) c->lattice_enable = atoi(e) != 0;
+    if (const char* e = getenv("AGP_GRAD_LAGDOM")) c->grad_lagdom = std::max(0, std::min(2, atoi(e)));
+    if (const char* e = getenv("AGP_GRAD_FFT")) { c->grad_fft = std::max(0, std::min(2, atoi(e))); c->grad_struct = atoi(e) >= 4 ? 2 : atoi(e) >= 3 ? 1 : 0; }
+    if (const char* e = getenv("AGP_RIGHT_LOOKING")) c->right_looking = atoi(e);
+    if (const char* e = getenv("AGP_DEDUP")) c->dedup = atoi(e) != 0;
+    if (const char* e = getenv("AGP_PREDICT_REUSE")) c->predict_reuse = atoi(e) != 0;
+    if (const char* e = getenv("AGP_REMOVE_UPDATE")) c->remove_update = std::max(0, std::min(2, atoi(e)));
+    if (const char* e = getenv("AGP_FACTOR_CACHE")) c->factor_cache = atoi(e) != 0;
+    if (const char* e = getenv("AGP_COALESCE_US")) c->coalesce_us = std::max(0, atoi(e));
+    if (const char* e = getenv("AGP_FLOW")) c->flow = atoi(e);
+    if (const char* e = getenv("AGP_EXTEND_FRAC")) c->store.max_frac = std::max(0.0, std::min(0.8, atof(e)));
+    if (const char* e = getenv("AGP_POISON")) c->poison.on = atoi(e) != 0;      // checking switch: no path changes
+    for (DevBuf* b : {&c->store.A, &c->store.W, &c->store.vec, &c->store.partial, &c->store.info, &c->store.ready, &c->store.tflag,
+                      &c->store.flowq, &c->store.Z, &c->store.zalpha, &c->store.zdinv, &c->comm_in, &c->comm_out, &c->comm_all})
+      b->pz = &c->poison;
+    if (const char* e = getenv("AGP_REFERENCE_ARITHMETIC")) { if (atoi(e) != 0) apply_reference_arithmetic(c); }      // (overrides the switches above)
+    *out = c;
+    return AGP_OK;
+  });
 }
 
 void agp_destroy(agp_ctx* c) {
@@ -1956,15 +1912,7 @@ int agp_probe_lattice(const double* ts, int64_t n, int32_t* kind, int64_t* n_lat
   return AGP_OK;
 }
 
-static int set_data_body(agp_ctx* c, const double* ts, const double* xs, int64_t n_max, const std::vector<uint8_t>* keep = nullptr);
-int agp_set_data(agp_ctx* c, const double* ts, const double* xs, int64_t n_max) {
-  return abi_guard(c, [&] { return set_data_body(c, ts, xs, n_max); });
-}
-extern "C++" int set_data_after_remove(agp_ctx* c, const double* ts, const double* xs, int64_t n_max, const std::vector<uint8_t>& touched) {
-  return set_data_body(c, ts, xs, n_max, &touched);
-}
-// keep (agp_remove_data): slots whose factors were updated to the new series by the caller
-static int set_data_body(agp_ctx* c, const double* ts, const double* xs, int64_t n_max, const std::vector<uint8_t>* keep) {
+static int set_data_body(agp_ctx* c, const double* ts, const double* xs, int64_t n_max, const std::vector<uint8_t>* keep = nullptr) {
   if (!c) return fail(nullptr, AGP_ERR_ARG, "null context");
   if (n_max < 0 || (n_max > 0 && (!ts || !xs))) return fail(c, AGP_ERR_ARG, "bad data arguments");
   HIPCHK(c, hipSetDevice(c->device));
@@ -2180,39 +2128,31 @@ static int set_data_body(agp_ctx* c, const double* ts, const double* xs, int64_t
   }
   return AGP_OK;
 }
+int agp_set_data(agp_ctx* c, const double* ts, const double* xs, int64_t n_max) {
+  return abi_guard(c, [&] { return set_data_body(c, ts, xs, n_max); });
+}
+extern "C++" int set_data_after_remove(agp_ctx* c, const double* ts, const double* xs, int64_t n_max, const std::vector<uint8_t>& touched) {
+  return set_data_body(c, ts, xs, n_max, &touched);
+}
+// keep (agp_remove_data): slots whose factors were updated to the new series by the caller
 
 // Host-output sweeps evaluate each DISTINCT (program, parameters, noise) once: after an SMC resampling
 // step the population holds many copies of the surviving particles (src/inference_smc_anneal_data.jl:198-204
 // resamples, then extends every particle with the new observations), and copies score identically.
-static int logpdf_batch_dedup(agp_ctx* c, int64_t n, int32_t P, const int32_t* op_off, const uint8_t* ops,
-                              const int32_t* prm_off, const double* prm, const double* noise, double* out_logpdf,
-                              int32_t* out_info, GradOut* go) {
-  auto plain = [&] {
-    return logpdf_batch_impl(c, n, P, op_off, ops, prm_off, prm, noise, out_logpdf, out_info, nullptr, nullptr, nullptr, false, go);
-  };
-  if (!c || !c->dedup || P < 2 || !op_off || !ops || !prm_off || !prm || !noise) return plain();
+static int logpdf_batch_dedup(agp_ctx* c, int64_t n, const Particles& pp, double* out_logpdf, int32_t* out_info, GradOut* go) {
   HostProf hp_dd(1);
-  std::vector<int> rep, uniq;
-  if (!distinct_particles(P, op_off, ops, prm_off, prm, noise, nullptr, rep, uniq)) return plain();     // malformed offsets are diagnosed by the sweep itself
-  const int U = (int)uniq.size();
-  { std::lock_guard<std::mutex> g(c->mu); c->n_particles_seen += P; c->n_particles_run += U; }
+  // (malformed offsets are diagnosed by the sweep itself: no dedup, and the call is not counted)
+  Distinct D(pp, c && c->dedup && pp.P >= 2 && pp.complete());
+  if (!D.rep.empty()) { std::lock_guard<std::mutex> g(c->mu); c->n_particles_seen += pp.P; c->n_particles_run += D.U(); }
   hp_dd.stop();
-  if (U == P) return plain();
-  SubBatch S;
-  pack_particles(uniq, op_off, ops, prm_off, prm, noise, nullptr, S);
+  if (!D.packed()) return logpdf_batch_impl(c, n, pp, out_logpdf, out_info, nullptr, nullptr, nullptr, false, go);
+  SubBatch& S = D.S;
   S.outputs(go != nullptr);
   GradOut ugo{S.grad.data(), S.gnoise.data()};
-  const int rc = logpdf_batch_impl(c, n, U, S.op_off.data(), S.ops.data(), S.prm_off.data(), S.prm.data(), S.noise.data(), S.lp.data(),
-                                   S.info.data(), nullptr, nullptr, nullptr, false, go ? &ugo : nullptr);
+  const int rc = logpdf_batch_impl(c, n, D.run(), S.lp.data(), S.info.data(), nullptr, nullptr, nullptr, false, go ? &ugo : nullptr);
   if (rc) return rc;
-  for (int p = 0; p < P; ++p) {
-    const int u = rep[p];
-    out_logpdf[p] = S.lp[u]; out_info[p] = S.info[u];
-    if (go) {
-      go->gnoise[p] = S.gnoise[u];
-      std::copy(S.grad.begin() + S.prm_off[u], S.grad.begin() + S.prm_off[u + 1], go->grad + prm_off[p]);
-    }
-  }
+  D.scatter(S.lp.data(), out_logpdf); D.scatter(S.info.data(), out_info);
+  if (go) { D.scatter(S.gnoise.data(), go->gnoise); D.scatter_csr(S.grad.data(), go->grad); }
   return AGP_OK;
 }
 
@@ -2220,7 +2160,7 @@ int agp_logpdf_batch(agp_ctx* c, int64_t n, int32_t P, const int32_t* op_off, co
                      const int32_t* prm_off, const double* prm, const double* noise, double* out_logpdf,
                      int32_t* out_info) {
   if (c && P > 0 && (!out_logpdf || !out_info)) return fail(c, AGP_ERR_ARG, "null output pointer");
-  return abi_guard(c, [&] { return logpdf_batch_dedup(c, n, P, op_off, ops, prm_off, prm, noise, out_logpdf, out_info, nullptr); });
+  return abi_guard(c, [&] { return logpdf_batch_dedup(c, n, {P, op_off, ops, prm_off, prm, noise, nullptr}, out_logpdf, out_info, nullptr); });
 }
 
 int agp_get_dedup_stats(agp_ctx* c, int64_t* n_particles, int64_t* n_evaluated) {
@@ -2235,7 +2175,7 @@ int agp_logpdf_grad_batch(agp_ctx* c, int64_t n, int32_t P, const int32_t* op_of
                           double* out_grad, double* out_grad_noise, int32_t* out_info) {
   if (c && P > 0 && (!out_logpdf || !out_info || !out_grad || !out_grad_noise)) return fail(c, AGP_ERR_ARG, "null output pointer");
   GradOut go{out_grad, out_grad_noise};
-  return abi_guard(c, [&] { return logpdf_batch_dedup(c, n, P, op_off, ops, prm_off, prm, noise, out_logpdf, out_info, &go); });
+  return abi_guard(c, [&] { return logpdf_batch_dedup(c, n, {P, op_off, ops, prm_off, prm, noise, nullptr}, out_logpdf, out_info, &go); });
 }
 
 int agp_logpdf_batch_device(agp_ctx* c, int64_t n, int32_t P, const int32_t* op_off, const uint8_t* ops,
@@ -2248,8 +2188,8 @@ int agp_logpdf_batch_device(agp_ctx* c, int64_t n, int32_t P, const int32_t* op_
     if (fault) return fail(c, AGP_ERR_HIP, "an earlier asynchronous sweep timed out inside a kernel waiting for a diagonal factor (its info words are < 0)");
   }
   return abi_guard(c, [&] {
-    return logpdf_batch_impl(c, n, P, op_off, ops, prm_off, prm, noise, nullptr, nullptr, d_out_logpdf, d_out_info, (hipStream_t)hip_stream,
-                             hip_stream != nullptr);
+    return logpdf_batch_impl(c, n, {P, op_off, ops, prm_off, prm, noise, nullptr}, nullptr, nullptr, d_out_logpdf, d_out_info,
+                             (hipStream_t)hip_stream, hip_stream != nullptr);
   });
 }
 
@@ -2308,13 +2248,13 @@ static void run_coalesced(agp_ctx* c, std::vector<LpRequest*>& batch) {
       // opt-in (AGP_LAG >= 2): class-aware value sweep — Toeplitz-class particles from the Schur recursion, the others through the store
       return abi_guard(c, [&] {
         TlFlag via_store(tl_dense_via_store);
-        return logpdf_batch_impl(c, n, Pn, oo, o, po, q, nz, out_lp, out_info, nullptr, nullptr, nullptr, false);
+        return logpdf_batch_impl(c, n, {Pn, oo, o, po, q, nz, nullptr}, out_lp, out_info, nullptr, nullptr, nullptr, false);
       });
     }
     if (!c->factor_cache) return agp_logpdf_batch(c, n, Pn, oo, o, po, q, nz, out_lp, out_info);
     struct Scope { const uint64_t* was; ~Scope() { tl_callers = was; } } scope{tl_callers};
     tl_callers = (Pn == P && oo == op_off.data()) ? callers.data() : nullptr;          // (the whole batch, in request order)
-    return extend_impl(c, n, Pn, oo, o, po, q, nz, out_lp, out_info);
+    return extend_impl(c, n, {Pn, oo, o, po, q, nz, nullptr}, out_lp, out_info);
   };
   int rc = sweep(batch[0]->n, P, op_off.data(), ops.data(), prm_off.data(), prm.data(), noise.data(), lp.data(),
                  grad.data(), gn.data(), info.data());

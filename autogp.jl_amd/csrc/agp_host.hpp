@@ -7,6 +7,7 @@
 #include "agp_args.hpp"
 #include "agp_launch.hpp"      // kernels live in agp_kernels.hip / agp_kernels_grad.hip
 #include "agp_comm.hpp"
+#include "agp_particles.hpp"   // Particles, SubBatch, Distinct (host only)
 
 #include <algorithm>
 #include <atomic>
@@ -475,10 +476,17 @@ struct Batch {
   int g_max_nodes = 0, g_max_prm = 0, g_max_cp = 0;
 };
 
-int compile_batch(agp_ctx* c, int P, const int32_t* op_off, const uint8_t* ops, const int32_t* prm_off,
-                  const double* prm, Batch& bt, bool allow_sel = false, bool want_grad = false, bool ge_tab = false,
-                  bool fuse_hint = false, bool flow_limit = false, bool lag = false, int lag_units = 1, int rank_extra = 0,
-                  bool never_fuse = false);
+struct CompileOpts {
+  bool allow_sel = false, want_grad = false, ge_tab = false;
+  bool fuse_hint = false;      // the caller will run the dataflow schedule, which evaluates tiles in-kernel whatever the batch size
+  bool flow_limit = false;
+  bool lag = false;
+  int lag_units = 1;           // LDS footprint of one lag table in 256-double units: 1 on a sorted sweep, n_max / 256 for rank tables
+  int rank_extra = 0;          // > 0: rank / compact tables — that many units for the tile's ranks or keys (in k_cov_tiles: and the exponential
+                               // table behind them; also when n_max <= 256) and, with compact tables, the B entries the tile stages
+  bool never_fuse = false;     // the factor store's sweeps over a series of at most two tile rows, see extend_impl
+};
+int compile_batch(agp_ctx* c, const Particles& pp, Batch& bt, const CompileOpts& o = {});
 
 inline size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
 
@@ -514,24 +522,6 @@ struct LagProgLayout {
     la.n_tables = bt.n_lag_tables;
   }
 };
-
-// Some particles of a caller's batch packed into a batch of their own, in the order of the index list: offsets, concatenated
-// programs / parameters (an empty parameter array holds one 0.0: never a null pointer), noises; noise_pred when the caller passes
-// one.  lp / info / grad / gnoise: the sub-batch's outputs, sized by outputs().
-struct SubBatch {
-  std::vector<int32_t> op_off, prm_off;
-  std::vector<uint8_t> ops;
-  std::vector<double> prm, noise, noise_pred;
-  std::vector<double> lp, grad, gnoise;
-  std::vector<int32_t> info;
-  int size() const { return (int)noise.size(); }
-  void outputs(bool with_grad) {
-    lp.assign(noise.size(), 0.0); info.assign(noise.size(), 0);
-    if (with_grad) { grad.assign(prm.size(), 0.0); gnoise.assign(noise.size(), 0.0); }
-  }
-};
-void pack_particles(const std::vector<int>& ix, const int32_t* op_off, const uint8_t* ops, const int32_t* prm_off, const double* prm,
-                    const double* noise, const double* noise_pred, SubBatch& S);
 
 // A tile evaluation longer than this (cost model op_cost_us: measured per-leaf cost of one 128x128 tile with two workgroups per
 // CU) would set the duration of the short launches; such particles get their tiles from k_cov_tiles.  Measured: per-column
@@ -696,14 +686,17 @@ struct Beside {
 // a sum (top-level + chain) of Linear leaves and subtrees without Linear / ChangePoint: Toeplitz + rank 2 on consecutive grid points
 bool toeplitz_class(const uint8_t* ops, int n_ops);
 
-// key of a particle in the factor store: the bits of (program, parameters, noise)
-std::string particle_key(const uint8_t* ops, int no, const double* prm, int np, double noise);
+static_assert(COMPOSITE_OP_PLUS == OP_PLUS && COMPOSITE_OP_TIMES == OP_TIMES && COMPOSITE_OP_LAST == OP_CP && COMPOSITE_OP_SEL == OP_SEL,
+              "append_composite's opcodes are the engine's");
 
-// Distinct particles of a batch (a resampled population holds copies of its survivors), keyed by particle_key (+ the bits of
-// noise_pred[p] when given): uniq = the first particle of each, in the caller's order; rep[p] = the position in uniq of p's;
-// keys (optional) = uniq's keys.  False, with everything empty, on offsets that are negative or decreasing: the caller decides.
-bool distinct_particles(int P, const int32_t* op_off, const uint8_t* ops, const int32_t* prm_off, const double* prm, const double* noise,
-                        const double* noise_pred, std::vector<int>& rep, std::vector<int>& uniq, std::vector<std::string>* keys = nullptr);
+// A predictive query: the first n resident observations, m query times, the mean function at both (nullable: zero).
+struct PredQuery {
+  int64_t n; const double* ts_pred; int64_t m; const double* mean_train; const double* mean_pred;
+};
+
+// checks the entries share, with their codes and messages
+int check_resident(agp_ctx* c, int64_t n);                            // n observations are resident (agp_set_data)
+int check_y_transform(agp_ctx* c, double slope, double intercept);
 
 // The joint predictive factorisation of agp_predict_logpdf_batch (agp_predict.hip), shared with agp_predict_sample_batch
 // (agp_sample.hip): argument-checked inputs -> dedup, compile, the joint matrix [K11 + noise I, K12; K21, K22 + noise_pred I] factored
@@ -722,10 +715,10 @@ struct JointHooks {
   std::function<int(Slot*, hipStream_t, const CholArgs&, int, int)> chunk;
   std::function<int(Slot*)> done;
 };
-int predict_joint_batch(agp_ctx* c, int64_t n, const double* ts_pred, const double* y_pred, int64_t m, int32_t P,
-                        const int32_t* op_off, const uint8_t* ops, const int32_t* prm_off, const double* prm,
-                        const double* noise, const double* noise_pred, const double* mean_train, const double* mean_pred,
-                        double* out_logpdf, int32_t* out_info, JointHooks* hooks);
+int predict_joint_batch(agp_ctx* c, const PredQuery& q, const double* y_pred, const Particles& pp, double* out_logpdf, int32_t* out_info,
+                        JointHooks* hooks);
+// agp_predict_batch behind its argument checks (the mixture entries stage their marginal pass through it)
+int predict_batch(agp_ctx* c, const PredQuery& q, const Particles& pp, double* out_mean, double* out_var, double* out_cov, int32_t* out_info);
 
 // Mixture moments over the chunks of a pass (agp_mixmom.hip; kernels: agp_mixmom_kernel.hpp).  The caller fills the first block; the
 // pass calls mix_stage before its uploads go out, mix_chunk per chunk of its particle order (while the chunk's device means and
@@ -754,17 +747,14 @@ int mix_finish(agp_ctx* c, Slot* s, hipStream_t st, MixPass& mp);
 // agp_predict_mixture_batch's covariance pass (agp_predict.hip): agp_predict_batch's dense pass with want_cov, the per-particle
 // covariances reduced by `mp` on the device instead of copied out.  weights: per caller particle (copies are added onto their
 // representative); out_info per caller particle.
-int predict_mixture_cov(agp_ctx* c, int64_t n, const double* ts_pred, int64_t m, int32_t P, const int32_t* op_off, const uint8_t* ops,
-                        const int32_t* prm_off, const double* prm, const double* noise, const double* noise_pred,
-                        const double* mean_train, const double* mean_pred, const double* weights, MixPass& mp, int32_t* out_info);
+int predict_mixture_cov(agp_ctx* c, const PredQuery& q, const Particles& pp, const double* weights, MixPass& mp, int32_t* out_info);
 
 // the mixture weights of agp_predict_quantile_batch / agp_predict_sample_batch (agp_quantile.hip): finite, >= 0, summing to 1
 int check_weights(agp_ctx* c, int32_t P, const double* w);
 
 hipError_t run_factor_extend(hipStream_t st, CholArgs ca, int dcov, bool split_diag, int i0min, int nfac = -1);
-int extend_impl(agp_ctx* c, int64_t n, int32_t P, const int32_t* op_off, const uint8_t* ops, const int32_t* prm_off,
-                const double* prm, const double* noise, double* out_lp, int32_t* out_info,
-                double* d_out_caller = nullptr, bool* wrote_device = nullptr);
+int extend_impl(agp_ctx* c, int64_t n, const Particles& pp, double* out_lp, int32_t* out_info, double* d_out_caller = nullptr,
+                bool* wrote_device = nullptr);
 
 
 // agp_set_data's body for agp_remove_data (agp_remove.hip): the reduced series replaces the resident one, the factors of the slots
@@ -776,7 +766,5 @@ int store_lookup(agp_ctx* c, const std::vector<std::string>& keys, const std::ve
                  std::vector<int32_t>& src_slot, std::vector<int32_t>& i0v, std::unique_lock<std::mutex>& lk);
 void launch_gather(agp_ctx* c, hipStream_t st, int Pc, int nt1, double* dstA, long long dst_strideA, double* dstW, int dst_wsteps,
                    double* dstV, long long dst_ldv, double* dstPart, int dst_ntp, const int32_t* d_src, int* ready, bool tiles = true);
-int logpdf_batch_impl(agp_ctx* c, int64_t n, int32_t P, const int32_t* op_off, const uint8_t* ops,
-                      const int32_t* prm_off, const double* prm, const double* noise,
-                      double* h_out_lp, int32_t* h_out_info, double* d_user_lp, int32_t* d_user_info,
+int logpdf_batch_impl(agp_ctx* c, int64_t n, const Particles& pp, double* h_out_lp, int32_t* h_out_info, double* d_user_lp, int32_t* d_user_info,
                       hipStream_t user_stream, bool use_user_stream, GradOut* go = nullptr, bool allow_lag = true);

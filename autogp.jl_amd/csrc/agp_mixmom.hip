@@ -148,71 +148,28 @@ int mixture_core(agp_ctx* c, int64_t m, int32_t P, const double* means, const do
 
 extern "C" {
 
-static int mixture_moments_body(agp_ctx* c, int64_t m, int32_t P, const double* means, const double* vars, const double* covs,
-                                const double* weights, int32_t space, double* out_mean, double* out_var, double* out_cov) {
-  if (const int rc = check_mixture(c, m, P, weights, space, out_cov != nullptr)) return rc;
-  if (!covs && out_cov) return fail(c, AGP_ERR_ARG, "out_cov needs the components' covariances");
-  if (m == 0) return AGP_OK;
-  if (!means || (!vars && !covs) || !out_mean || !out_var) return fail(c, AGP_ERR_ARG, "null pointer argument");
-  MixPass mp;
-  mp.space = space; mp.cov = out_cov != nullptr;
-  mp.out_mean = out_mean; mp.out_var = out_var; mp.out_cov = out_cov;
-  // (covariances given but only mean and var wanted: their diagonals are the variances — nothing but the diagonals travels)
-  std::vector<double> diag;
-  if (covs && !out_cov) {
-    diag.resize((size_t)m * P);
-    for (int32_t p = 0; p < P; ++p)
-      for (int64_t i = 0; i < m; ++i) diag[(size_t)p * m + i] = covs[(size_t)p * m * m + (size_t)i * (m + 1)];
-    vars = diag.data(); covs = nullptr;
-  }
-  return mixture_core(c, m, P, means, vars, covs, weights, mp);
-}
-
 int agp_mixture_moments(agp_ctx* c, int64_t m, int32_t P, const double* means, const double* vars, const double* covs,
                         const double* weights, int32_t space, double* out_mean, double* out_var, double* out_cov) {
-  return abi_guard(c, [&] { return mixture_moments_body(c, m, P, means, vars, covs, weights, space, out_mean, out_var, out_cov); });
+  return abi_guard(c, [&]() -> int {
+    if (const int rc = check_mixture(c, m, P, weights, space, out_cov != nullptr)) return rc;
+    if (!covs && out_cov) return fail(c, AGP_ERR_ARG, "out_cov needs the components' covariances");
+    if (m == 0) return AGP_OK;
+    if (!means || (!vars && !covs) || !out_mean || !out_var) return fail(c, AGP_ERR_ARG, "null pointer argument");
+    MixPass mp;
+    mp.space = space; mp.cov = out_cov != nullptr;
+    mp.out_mean = out_mean; mp.out_var = out_var; mp.out_cov = out_cov;
+    // (covariances given but only mean and var wanted: their diagonals are the variances — nothing but the diagonals travels)
+    std::vector<double> diag;
+    if (covs && !out_cov) {
+      diag.resize((size_t)m * P);
+      for (int32_t p = 0; p < P; ++p)
+        for (int64_t i = 0; i < m; ++i) diag[(size_t)p * m + i] = covs[(size_t)p * m * m + (size_t)i * (m + 1)];
+      vars = diag.data(); covs = nullptr;
+    }
+    return mixture_core(c, m, P, means, vars, covs, weights, mp);
+  });
 }
 
-static int predict_mixture_body(agp_ctx* c, int64_t n, const double* ts_pred, int64_t m, int32_t P, const int32_t* op_off,
-                                const uint8_t* ops, const int32_t* prm_off, const double* prm, const double* noise,
-                                const double* noise_pred, const double* mean_train, const double* mean_pred, const double* weights,
-                                double y_slope, double y_intercept, int32_t space, double* out_mean, double* out_var, double* out_cov,
-                                int32_t* out_info) {
-  if (const int rc = check_mixture(c, m, P, weights, space, out_cov != nullptr)) return rc;
-  if (n < 0) return fail(c, AGP_ERR_ARG, "negative size");
-  if (n > c->n_max) return fail(c, AGP_ERR_NODATA, "n exceeds the data uploaded with agp_set_data");
-  if (!(std::isfinite(y_slope) && y_slope != 0.0 && std::isfinite(y_intercept)))
-    return fail(c, AGP_ERR_ARG, "y_transform must have a finite non-zero slope and a finite intercept");
-  if (m == 0) return AGP_OK;
-  if (!op_off || !ops || !prm_off || !prm || !noise || !ts_pred || !out_mean || !out_var)
-    return fail(c, AGP_ERR_ARG, "null pointer argument");
-  MixPass mp;
-  mp.space = space; mp.slope = y_slope; mp.intercept = y_intercept; mp.cov = out_cov != nullptr;
-  mp.out_mean = out_mean; mp.out_var = out_var; mp.out_cov = out_cov;
-  std::vector<int32_t> info((size_t)P, 0);
-  int rc;
-  if (out_cov) {
-    rc = predict_mixture_cov(c, n, ts_pred, m, P, op_off, ops, prm_off, prm, noise, noise_pred, mean_train, mean_pred, weights, mp,
-                             info.data());
-    if (rc) return rc;
-  } else {
-    // the marginal pass (out_cov = NULL: structured, lattice, store-reuse, duplicate-query and dedup paths as agp_predict_batch),
-    // staged on the host as agp_predict_quantile_batch stages it
-    const size_t nc = (size_t)m * P;
-    std::vector<double> mean(nc), var(nc);
-    rc = agp_predict_batch(c, n, ts_pred, m, P, op_off, ops, prm_off, prm, noise, noise_pred, mean_train, mean_pred, mean.data(),
-                           var.data(), nullptr, info.data());
-    if (rc) return rc;
-    if (std::none_of(info.begin(), info.end(), [](int32_t v) { return v != 0; })) {
-      rc = mixture_core(c, m, P, mean.data(), var.data(), nullptr, weights, mp);
-      if (rc) return rc;
-    }
-  }
-  if (out_info) std::copy(info.begin(), info.end(), out_info);
-  // a particle without a predictive: the mixture is undefined (the reference throws building that particle's MvNormal)
-  if (std::any_of(info.begin(), info.end(), [](int32_t v) { return v != 0; })) fill_nan(mp, m);
-  return AGP_OK;
-}
 
 int agp_get_mixture_stats(agp_ctx* c, int64_t* n_passes, int64_t* n_chunks) {
   if (!c || !n_passes || !n_chunks) return fail(c, AGP_ERR_ARG, "null pointer");
@@ -226,9 +183,40 @@ int agp_predict_mixture_batch(agp_ctx* c, int64_t n, const double* ts_pred, int6
                               const double* noise_pred, const double* mean_train, const double* mean_pred, const double* weights,
                               double y_slope, double y_intercept, int32_t space, double* out_mean, double* out_var, double* out_cov,
                               int32_t* out_info) {
-  return abi_guard(c, [&] { return predict_mixture_body(c, n, ts_pred, m, P, op_off, ops, prm_off, prm, noise, noise_pred, mean_train,
-                                                        mean_pred, weights, y_slope, y_intercept, space, out_mean, out_var, out_cov,
-                                                        out_info); });
+  return abi_guard(c, [&]() -> int {
+    if (const int rc = check_mixture(c, m, P, weights, space, out_cov != nullptr)) return rc;
+    if (n < 0) return fail(c, AGP_ERR_ARG, "negative size");
+    if (const int rc = check_resident(c, n)) return rc;
+    if (const int rc = check_y_transform(c, y_slope, y_intercept)) return rc;
+    if (m == 0) return AGP_OK;
+    const PredQuery q{n, ts_pred, m, mean_train, mean_pred};
+    const Particles pp{P, op_off, ops, prm_off, prm, noise, noise_pred};
+    if (!pp.complete() || !ts_pred || !out_mean || !out_var) return fail(c, AGP_ERR_ARG, "null pointer argument");
+    MixPass mp;
+    mp.space = space; mp.slope = y_slope; mp.intercept = y_intercept; mp.cov = out_cov != nullptr;
+    mp.out_mean = out_mean; mp.out_var = out_var; mp.out_cov = out_cov;
+    std::vector<int32_t> info((size_t)P, 0);
+    int rc;
+    if (out_cov) {
+      rc = predict_mixture_cov(c, q, pp, weights, mp, info.data());
+      if (rc) return rc;
+    } else {
+      // the marginal pass (out_cov = NULL: structured, lattice, store-reuse, duplicate-query and dedup paths as agp_predict_batch),
+      // staged on the host as agp_predict_quantile_batch stages it
+      const size_t nc = (size_t)m * P;
+      std::vector<double> mean(nc), var(nc);
+      rc = predict_batch(c, q, pp, mean.data(), var.data(), nullptr, info.data());
+      if (rc) return rc;
+      if (std::none_of(info.begin(), info.end(), [](int32_t v) { return v != 0; })) {
+        rc = mixture_core(c, m, P, mean.data(), var.data(), nullptr, weights, mp);
+        if (rc) return rc;
+      }
+    }
+    if (out_info) std::copy(info.begin(), info.end(), out_info);
+    // a particle without a predictive: the mixture is undefined (the reference throws building that particle's MvNormal)
+    if (std::any_of(info.begin(), info.end(), [](int32_t v) { return v != 0; })) fill_nan(mp, m);
+    return AGP_OK;
+  });
 }
 
 }  // extern "C"

@@ -86,9 +86,7 @@ int agp_shard_plan(int64_t n, int32_t P, const int32_t* op_off, const uint8_t* o
   if (P < 0 || n_ranks <= 0 || n < 0 || !owner_out || (P > 0 && (!op_off || !ops || !prm_off || !prm || !noise)))
     return fail(nullptr, AGP_ERR_ARG, "bad shard-plan arguments");
   try {
-    for (int p = 0; p < P; ++p)
-      if (op_off[p + 1] < op_off[p] || prm_off[p + 1] < prm_off[p] || op_off[p] < 0 || prm_off[p] < 0)
-        return fail(nullptr, AGP_ERR_ARG, "offsets must be non-decreasing");
+    const Particles pp{P, op_off, ops, prm_off, prm, noise, nullptr};
     const double nn = (double)std::max<int64_t>(n, 1);
     // 0 irregular, 1 regular grid, 2 lattice with gaps; 3 (compact tables: only tile evaluation differs) and anything else: dense-priced
     const int kind = (regular_grid < 0 || regular_grid > 2) ? 0 : regular_grid;
@@ -97,14 +95,13 @@ int agp_shard_plan(int64_t n, int32_t P, const int32_t* op_off, const uint8_t* o
     // On a lattice WITH gaps the class keeps its dense factor, L^-T and K^-1; only its contraction runs over the lattice's lags
     // (measured on 2048 business days: 100.9 -> 96.5 ms per 512-particle gradient sweep)
     const double lagdom_gaps = sweep == 1 ? dense - 0.15 : dense;
-    std::vector<int> rep, uniq;
-    (void)distinct_particles(P, op_off, ops, prm_off, prm, noise, nullptr, rep, uniq);      // (offsets checked above)
+    std::vector<int> rep, uniq;      // (a plan only: nothing is packed)
+    if (!distinct_particles(pp, rep, uniq)) return fail(nullptr, AGP_ERR_ARG, "offsets must be non-decreasing");
     std::vector<double> cost((size_t)P, 0.0);
     std::vector<char> is_cls((size_t)P, 0);
     int64_t n_cls = 0;
     for (int p : uniq) {
-      const int no = op_off[p + 1] - op_off[p];
-      is_cls[(size_t)p] = (kind != 0 && sweep >= 1 && no <= AGP_MAX_OPS_DEV && toeplitz_class(ops + op_off[p], no)) ? 1 : 0;
+      is_cls[(size_t)p] = (kind != 0 && sweep >= 1 && pp.n_ops(p) <= AGP_MAX_OPS_DEV && toeplitz_class(pp.program(p), pp.n_ops(p))) ? 1 : 0;
       n_cls += is_cls[(size_t)p];
     }
     // The structured sweeps are admitted by the ENGINE's own tests (agp_host.hpp: struct_*_admits — the same predicates the sweeps
@@ -183,48 +180,44 @@ int agp_comm_count(agp_ctx* c, int32_t* out_n_ranks) {
   return AGP_OK;
 }
 
-static int init_multi_body(agp_ctx** out, const int32_t* device_ids, int32_t n_dev);
 int agp_init_multi(agp_ctx** out, const int32_t* device_ids, int32_t n_dev) {
-  return abi_guard(nullptr, [&] { return init_multi_body(out, device_ids, n_dev); });
-}
-static int init_multi_body(agp_ctx** out, const int32_t* device_ids, int32_t n_dev) {
-  if (!out || !device_ids || n_dev < 1) return fail(nullptr, AGP_ERR_ARG, "bad arguments");
-  for (int i = 0; i < n_dev; ++i) out[i] = nullptr;
-  for (int i = 0; i < n_dev; ++i)
-    for (int j = 0; j < i; ++j)
-      if (device_ids[i] == device_ids[j]) return fail(nullptr, AGP_ERR_ARG, "duplicate device id");
-  int rc = need_rccl(nullptr);
-  if (rc) return rc;
-  auto undo = [&]() { for (int i = 0; i < n_dev; ++i) { if (out[i]) agp_destroy(out[i]); out[i] = nullptr; } };
-  for (int i = 0; i < n_dev; ++i) {
-    rc = agp_init(&out[i], device_ids[i]);
-    if (rc) { undo(); return rc; }
-  }
-  std::vector<ncclComm_t> comms((size_t)n_dev, nullptr);
-  std::vector<int> devs(device_ids, device_ids + n_dev);
-  ncclResult_t r = rccl().CommInitAll(comms.data(), n_dev, devs.data());
-  if (r != ncclSuccess) {
-    undo();
-    return fail(nullptr, AGP_ERR_COMM, std::string("ncclCommInitAll failed: ") + rccl().GetErrorString(r));
-  }
-  for (int i = 0; i < n_dev; ++i) {
-    out[i]->comm = comms[i]; out[i]->comm_rank = i; out[i]->comm_size = n_dev;
-    if (hipSetDevice(device_ids[i]) != hipSuccess || ensure_comm_stream(out[i]) != AGP_OK) { undo(); return fail(nullptr, AGP_ERR_HIP, "stream creation failed"); }
-  }
-  return AGP_OK;
+  return abi_guard(nullptr, [&]() -> int {
+    if (!out || !device_ids || n_dev < 1) return fail(nullptr, AGP_ERR_ARG, "bad arguments");
+    for (int i = 0; i < n_dev; ++i) out[i] = nullptr;
+    for (int i = 0; i < n_dev; ++i)
+      for (int j = 0; j < i; ++j)
+        if (device_ids[i] == device_ids[j]) return fail(nullptr, AGP_ERR_ARG, "duplicate device id");
+    int rc = need_rccl(nullptr);
+    if (rc) return rc;
+    auto undo = [&]() { for (int i = 0; i < n_dev; ++i) { if (out[i]) agp_destroy(out[i]); out[i] = nullptr; } };
+    for (int i = 0; i < n_dev; ++i) {
+      rc = agp_init(&out[i], device_ids[i]);
+      if (rc) { undo(); return rc; }
+    }
+    std::vector<ncclComm_t> comms((size_t)n_dev, nullptr);
+    std::vector<int> devs(device_ids, device_ids + n_dev);
+    ncclResult_t r = rccl().CommInitAll(comms.data(), n_dev, devs.data());
+    if (r != ncclSuccess) {
+      undo();
+      return fail(nullptr, AGP_ERR_COMM, std::string("ncclCommInitAll failed: ") + rccl().GetErrorString(r));
+    }
+    for (int i = 0; i < n_dev; ++i) {
+      out[i]->comm = comms[i]; out[i]->comm_rank = i; out[i]->comm_size = n_dev;
+      if (hipSetDevice(device_ids[i]) != hipSuccess || ensure_comm_stream(out[i]) != AGP_OK) { undo(); return fail(nullptr, AGP_ERR_HIP, "stream creation failed"); }
+    }
+    return AGP_OK;
+  });
 }
 
-static int set_data_multi_body(agp_ctx* const* ctxs, int32_t n_dev, const double* ts, const double* xs, int64_t n_max);
 int agp_set_data_multi(agp_ctx* const* ctxs, int32_t n_dev, const double* ts, const double* xs, int64_t n_max) {
-  return abi_guard((ctxs && n_dev > 0) ? ctxs[0] : nullptr, [&] { return set_data_multi_body(ctxs, n_dev, ts, xs, n_max); });
-}
-static int set_data_multi_body(agp_ctx* const* ctxs, int32_t n_dev, const double* ts, const double* xs, int64_t n_max) {
-  if (!ctxs || n_dev < 1) return fail(nullptr, AGP_ERR_ARG, "bad arguments");
-  for (int i = 0; i < n_dev; ++i) {
-    const int rc = agp_set_data(ctxs[i], ts, xs, n_max);
-    if (rc) return rc;
-  }
-  return AGP_OK;
+  return abi_guard((ctxs && n_dev > 0) ? ctxs[0] : nullptr, [&]() -> int {
+    if (!ctxs || n_dev < 1) return fail(nullptr, AGP_ERR_ARG, "bad arguments");
+    for (int i = 0; i < n_dev; ++i) {
+      const int rc = agp_set_data(ctxs[i], ts, xs, n_max);
+      if (rc) return rc;
+    }
+    return AGP_OK;
+  });
 }
 
 // (c->comm_mu held by the caller)
@@ -248,20 +241,18 @@ static int allgather_device_locked(agp_ctx* c, const double* d_local, int32_t P,
   return AGP_OK;
 }
 
-static int allgather_logweights_device_body(agp_ctx* c, const double* d_local, int32_t P, double* d_all, void* hip_stream);
 int agp_allgather_logweights_device(agp_ctx* c, const double* d_local, int32_t P, double* d_all, void* hip_stream) {
-  return abi_guard(c, [&] { return allgather_logweights_device_body(c, d_local, P, d_all, hip_stream); });
-}
-static int allgather_logweights_device_body(agp_ctx* c, const double* d_local, int32_t P, double* d_all, void* hip_stream) {
-  if (!c) return fail(nullptr, AGP_ERR_ARG, "null context");
-  if (P < 0 || (P > 0 && !d_all)) return fail(c, AGP_ERR_ARG, "bad arguments");
-  if (P == 0) return AGP_OK;
-  int lo, hi;
-  shard_range(P, c->comm_rank, c->comm_size, &lo, &hi);
-  if (hi > lo && !d_local) return fail(c, AGP_ERR_ARG, "null shard pointer");
-  HIPCHK(c, hipSetDevice(c->device));
-  std::lock_guard<std::mutex> g(c->comm_mu);
-  return allgather_device_locked(c, d_local, P, d_all, hip_stream);
+  return abi_guard(c, [&]() -> int {
+    if (!c) return fail(nullptr, AGP_ERR_ARG, "null context");
+    if (P < 0 || (P > 0 && !d_all)) return fail(c, AGP_ERR_ARG, "bad arguments");
+    if (P == 0) return AGP_OK;
+    int lo, hi;
+    shard_range(P, c->comm_rank, c->comm_size, &lo, &hi);
+    if (hi > lo && !d_local) return fail(c, AGP_ERR_ARG, "null shard pointer");
+    HIPCHK(c, hipSetDevice(c->device));
+    std::lock_guard<std::mutex> g(c->comm_mu);
+    return allgather_device_locked(c, d_local, P, d_all, hip_stream);
+  });
 }
 
 // Test hook for the un-padding step of unequal shards (a one-GPU box can only form a one-rank communicator, where every
@@ -281,29 +272,27 @@ int agp_debug_compact_shards(agp_ctx* c, const double* padded, int32_t P, int32_
   return AGP_OK;
 }
 
-static int allgather_logweights_body(agp_ctx* c, double* inout_lw, int32_t P);
 int agp_allgather_logweights(agp_ctx* c, double* inout_lw, int32_t P) {
-  return abi_guard(c, [&] { return allgather_logweights_body(c, inout_lw, P); });
-}
-static int allgather_logweights_body(agp_ctx* c, double* inout_lw, int32_t P) {
-  if (!c) return fail(nullptr, AGP_ERR_ARG, "null context");
-  if (P < 0 || (P > 0 && !inout_lw)) return fail(c, AGP_ERR_ARG, "bad arguments");
-  if (P == 0 || c->comm_size == 1) return AGP_OK;          // a one-rank population is already complete
-  if (!c->comm) return fail(c, AGP_ERR_COMM, "no communicator: call agp_comm_init_rank or agp_init_multi first");
-  HIPCHK(c, hipSetDevice(c->device));
-  int lo, hi;
-  shard_range(P, c->comm_rank, c->comm_size, &lo, &hi);
-  // the staging buffer belongs to the context: the lock covers its (re)allocation AND its use
-  std::lock_guard<std::mutex> g(c->comm_mu);
-  HIPCHK(c, c->comm_all.ensure(sizeof(double) * (size_t)P * 2));
-  double* d_all = c->comm_all.as<double>();
-  double* d_loc = d_all + P;
-  if (hi > lo) HIPCHK(c, hipMemcpyAsync(d_loc, inout_lw + lo, sizeof(double) * (size_t)(hi - lo), hipMemcpyHostToDevice, c->comm_stream));
-  int rc = allgather_device_locked(c, d_loc, P, d_all, c->comm_stream);
-  if (rc) return rc;
-  HIPCHK(c, hipMemcpyAsync(inout_lw, d_all, sizeof(double) * (size_t)P, hipMemcpyDeviceToHost, c->comm_stream));
-  HIPCHK(c, hipStreamSynchronize(c->comm_stream));
-  return AGP_OK;
+  return abi_guard(c, [&]() -> int {
+    if (!c) return fail(nullptr, AGP_ERR_ARG, "null context");
+    if (P < 0 || (P > 0 && !inout_lw)) return fail(c, AGP_ERR_ARG, "bad arguments");
+    if (P == 0 || c->comm_size == 1) return AGP_OK;          // a one-rank population is already complete
+    if (!c->comm) return fail(c, AGP_ERR_COMM, "no communicator: call agp_comm_init_rank or agp_init_multi first");
+    HIPCHK(c, hipSetDevice(c->device));
+    int lo, hi;
+    shard_range(P, c->comm_rank, c->comm_size, &lo, &hi);
+    // the staging buffer belongs to the context: the lock covers its (re)allocation AND its use
+    std::lock_guard<std::mutex> g(c->comm_mu);
+    HIPCHK(c, c->comm_all.ensure(sizeof(double) * (size_t)P * 2));
+    double* d_all = c->comm_all.as<double>();
+    double* d_loc = d_all + P;
+    if (hi > lo) HIPCHK(c, hipMemcpyAsync(d_loc, inout_lw + lo, sizeof(double) * (size_t)(hi - lo), hipMemcpyHostToDevice, c->comm_stream));
+    int rc = allgather_device_locked(c, d_loc, P, d_all, c->comm_stream);
+    if (rc) return rc;
+    HIPCHK(c, hipMemcpyAsync(inout_lw, d_all, sizeof(double) * (size_t)P, hipMemcpyDeviceToHost, c->comm_stream));
+    HIPCHK(c, hipStreamSynchronize(c->comm_stream));
+    return AGP_OK;
+  });
 }
 
 // One host process driving every GPU of the node (the deployment of a single Julia process): block-shard the P
@@ -334,14 +323,14 @@ static agp_ctx::Worker* ensure_worker(agp_ctx* c) {
   return w;
 }
 
-static int logpdf_batch_multi_impl(agp_ctx* const* ctxs, int32_t n_dev, int64_t n, int32_t P, const int32_t* op_off,
-                                   const uint8_t* ops, const int32_t* prm_off, const double* prm, const double* noise,
-                                   double* out_logpdf, int32_t* out_info, bool extend) {
+static int logpdf_batch_multi_impl(agp_ctx* const* ctxs, int32_t n_dev, int64_t n, const Particles& pp, double* out_logpdf,
+                                   int32_t* out_info, bool extend) {
+  const int P = pp.P;
   if (!ctxs || n_dev < 1 || !ctxs[0]) return fail(nullptr, AGP_ERR_ARG, "bad context list");
   agp_ctx* c0 = ctxs[0];
   if (P < 0 || n < 0) return fail(c0, AGP_ERR_ARG, "negative size");
   if (P == 0) return AGP_OK;
-  if (!op_off || !ops || !prm_off || !prm || !noise || !out_logpdf || !out_info) return fail(c0, AGP_ERR_ARG, "null pointer argument");
+  if (!pp.complete() || !out_logpdf || !out_info) return fail(c0, AGP_ERR_ARG, "null pointer argument");
   for (int d = 0; d < n_dev; ++d)
     if (!ctxs[d] || ctxs[d]->comm_size != n_dev || ctxs[d]->comm_rank != d || (n_dev > 1 && !ctxs[d]->comm))
       return fail(c0, AGP_ERR_ARG, "contexts must come from agp_init_multi, in order");
@@ -362,7 +351,8 @@ static int logpdf_batch_multi_impl(agp_ctx* const* ctxs, int32_t n_dev, int64_t 
     if (hi == lo) return;
     const int Pl = hi - lo;
     std::vector<int32_t> oo((size_t)Pl + 1), po((size_t)Pl + 1);
-    for (int i = 0; i <= Pl; ++i) { oo[i] = op_off[lo + i] - op_off[lo]; po[i] = prm_off[lo + i] - prm_off[lo]; }
+    for (int i = 0; i <= Pl; ++i) { oo[i] = pp.op_off[lo + i] - pp.op_off[lo]; po[i] = pp.prm_off[lo + i] - pp.prm_off[lo]; }
+    const Particles shard{Pl, oo.data(), pp.program(lo), po.data(), pp.params(lo), pp.noise + lo, nullptr};
     double* d_loc = c->comm_all.as<double>() + P;
     if (extend && !c->ref_arith) {
       // (reference arithmetic keeps nothing resident: the shard takes the plain sweep below, as agp_logpdf_batch_extend does)
@@ -371,14 +361,12 @@ static int logpdf_batch_multi_impl(agp_ctx* const* ctxs, int32_t n_dev, int64_t 
       // log-weights are also left on the device, in caller order, for the gather (no host round trip).
       std::vector<double> hl((size_t)Pl);
       bool on_device = false;
-      rcs[d] = extend_impl(c, n, Pl, oo.data(), ops + op_off[lo], po.data(), prm + prm_off[lo], noise + lo, hl.data(), out_info + lo,
-                           d_loc, &on_device);
+      rcs[d] = extend_impl(c, n, shard, hl.data(), out_info + lo, d_loc, &on_device);
       if (rcs[d] == AGP_OK && !on_device &&      // (n = 0, or the sweep fell back to the plain entry: host results only)
           hipMemcpy(d_loc, hl.data(), sizeof(double) * (size_t)Pl, hipMemcpyHostToDevice) != hipSuccess)
         rcs[d] = fail(c, AGP_ERR_HIP, "copy of the shard's log-weights failed");
     } else {
-      rcs[d] = logpdf_batch_impl(c, n, Pl, oo.data(), ops + op_off[lo], po.data(), prm + prm_off[lo], noise + lo, nullptr,
-                                 out_info + lo, d_loc, nullptr, nullptr, false);
+      rcs[d] = logpdf_batch_impl(c, n, shard, nullptr, out_info + lo, d_loc, nullptr, nullptr, false);
     }
   };
   // (no exception leaves a shard: the other devices' jobs refer to this frame until they are done)
@@ -433,7 +421,7 @@ static int logpdf_batch_multi_impl(agp_ctx* const* ctxs, int32_t n_dev, int64_t 
 int agp_logpdf_batch_multi(agp_ctx* const* ctxs, int32_t n_dev, int64_t n, int32_t P, const int32_t* op_off,
                            const uint8_t* ops, const int32_t* prm_off, const double* prm, const double* noise,
                            double* out_logpdf, int32_t* out_info) {
-  return abi_guard((ctxs && n_dev > 0) ? ctxs[0] : nullptr, [&] { return logpdf_batch_multi_impl(ctxs, n_dev, n, P, op_off, ops, prm_off, prm, noise, out_logpdf, out_info, false); });
+  return abi_guard((ctxs && n_dev > 0) ? ctxs[0] : nullptr, [&] { return logpdf_batch_multi_impl(ctxs, n_dev, n, {P, op_off, ops, prm_off, prm, noise, nullptr}, out_logpdf, out_info, false); });
 }
 
 // The same with resident factors: every device runs its shard as an extension sweep (agp_logpdf_batch_extend) — the
@@ -441,7 +429,7 @@ int agp_logpdf_batch_multi(agp_ctx* const* ctxs, int32_t n_dev, int64_t n, int32
 int agp_logpdf_batch_extend_multi(agp_ctx* const* ctxs, int32_t n_dev, int64_t n, int32_t P, const int32_t* op_off,
                                   const uint8_t* ops, const int32_t* prm_off, const double* prm, const double* noise,
                                   double* out_logpdf, int32_t* out_info) {
-  return abi_guard((ctxs && n_dev > 0) ? ctxs[0] : nullptr, [&] { return logpdf_batch_multi_impl(ctxs, n_dev, n, P, op_off, ops, prm_off, prm, noise, out_logpdf, out_info, true); });
+  return abi_guard((ctxs && n_dev > 0) ? ctxs[0] : nullptr, [&] { return logpdf_batch_multi_impl(ctxs, n_dev, n, {P, op_off, ops, prm_off, prm, noise, nullptr}, out_logpdf, out_info, true); });
 }
 
 }  // extern "C"
@@ -457,11 +445,10 @@ int agp_logpdf_batch_extend_multi(agp_ctx* const* ctxs, int32_t n_dev, int64_t n
 namespace {
 
 // the particles device d owns, packed (an empty program array holds one byte: never a null pointer)
-void pack_shard(int32_t P, const int32_t* op_off, const uint8_t* ops, const int32_t* prm_off, const double* prm, const double* noise,
-                const double* noise_pred, const int32_t* owner, int d, std::vector<int>& idx, SubBatch& S) {
+void pack_shard(const Particles& pp, const int32_t* owner, int d, std::vector<int>& idx, SubBatch& S) {
   idx.clear();
-  for (int p = 0; p < P; ++p) if (owner[p] == d) idx.push_back(p);
-  pack_particles(idx, op_off, ops, prm_off, prm, noise, noise_pred, S);
+  for (int p = 0; p < pp.P; ++p) if (owner[p] == d) idx.push_back(p);
+  pack_particles(idx, pp, S);
   if (S.ops.empty()) S.ops.push_back(0);
 }
 
@@ -506,18 +493,17 @@ int first_error(agp_ctx* const* ctxs, int32_t n_dev, const std::vector<int>& rcs
   return AGP_OK;
 }
 
-int grad_batch_multi_impl(agp_ctx* const* ctxs, int32_t n_dev, int64_t n, int32_t P, const int32_t* op_off, const uint8_t* ops,
-                          const int32_t* prm_off, const double* prm, const double* noise, double* out_logpdf, double* out_grad,
+int grad_batch_multi_impl(agp_ctx* const* ctxs, int32_t n_dev, int64_t n, const Particles& pp, double* out_logpdf, double* out_grad,
                           double* out_grad_noise, int32_t* out_info, int32_t* out_owner) {
+  const int P = pp.P;
   int rc = check_ctx_list(ctxs, n_dev);
   if (rc) return rc;
   agp_ctx* c0 = ctxs[0];
   if (P < 0 || n < 0) return fail(c0, AGP_ERR_ARG, "negative size");
   if (P == 0) return AGP_OK;
-  if (!op_off || !ops || !prm_off || !prm || !noise || !out_logpdf || !out_grad || !out_grad_noise || !out_info)
-    return fail(c0, AGP_ERR_ARG, "null pointer argument");
+  if (!pp.complete() || !out_logpdf || !out_grad || !out_grad_noise || !out_info) return fail(c0, AGP_ERR_ARG, "null pointer argument");
   std::vector<int32_t> owner((size_t)P, 0);
-  rc = agp_shard_plan(n, P, op_off, ops, prm_off, prm, noise, 1, lattice_kind_of(c0), 0, n_dev, owner.data(), nullptr, nullptr);
+  rc = agp_shard_plan(n, P, pp.op_off, pp.ops, pp.prm_off, pp.prm, pp.noise, 1, lattice_kind_of(c0), 0, n_dev, owner.data(), nullptr, nullptr);
   if (rc) return fail(c0, rc, agp_last_error(nullptr));
   if (out_owner) std::memcpy(out_owner, owner.data(), sizeof(int32_t) * (size_t)P);
   std::lock_guard<std::mutex> multi_lock(c0->multi_mu);
@@ -526,7 +512,7 @@ int grad_batch_multi_impl(agp_ctx* const* ctxs, int32_t n_dev, int64_t n, int32_
     try {
       std::vector<int> idx;
       SubBatch S;
-      pack_shard(P, op_off, ops, prm_off, prm, noise, nullptr, owner.data(), d, idx, S);
+      pack_shard(pp, owner.data(), d, idx, S);
       const int Pl = S.size();
       if (Pl == 0) return;
       S.outputs(true);
@@ -536,7 +522,7 @@ int grad_batch_multi_impl(agp_ctx* const* ctxs, int32_t n_dev, int64_t n, int32_
       for (int b = 0; b < Pl; ++b) {          // (disjoint index sets: the shards write without a lock)
         const int p = idx[(size_t)b];
         out_logpdf[p] = S.lp[(size_t)b]; out_grad_noise[p] = S.gnoise[(size_t)b]; out_info[p] = S.info[(size_t)b];
-        std::copy(S.grad.begin() + S.prm_off[(size_t)b], S.grad.begin() + S.prm_off[(size_t)b + 1], out_grad + prm_off[p]);
+        std::copy(S.grad.begin() + S.prm_off[(size_t)b], S.grad.begin() + S.prm_off[(size_t)b + 1], out_grad + pp.prm_off[p]);
       }
     } catch (...) { rcs[(size_t)d] = AGP_ERR_HOST; }
   };
@@ -544,17 +530,17 @@ int grad_batch_multi_impl(agp_ctx* const* ctxs, int32_t n_dev, int64_t n, int32_
   return first_error(ctxs, n_dev, rcs);
 }
 
-int predict_batch_multi_impl(agp_ctx* const* ctxs, int32_t n_dev, int64_t n, const double* ts_pred, int64_t m, int32_t P,
-                             const int32_t* op_off, const uint8_t* ops, const int32_t* prm_off, const double* prm,
-                             const double* noise, const double* noise_pred, const double* mean_train, const double* mean_pred,
-                             double* out_mean, double* out_var, double* out_cov, int32_t* out_info, int32_t* out_owner) {
+int predict_batch_multi_impl(agp_ctx* const* ctxs, int32_t n_dev, const PredQuery& q, const Particles& pp, double* out_mean, double* out_var,
+                             double* out_cov, int32_t* out_info, int32_t* out_owner) {
+  const int64_t n = q.n, m = q.m;
+  const int P = pp.P;
+  const double* ts_pred = q.ts_pred;
   int rc = check_ctx_list(ctxs, n_dev);
   if (rc) return rc;
   agp_ctx* c0 = ctxs[0];
   if (P < 0 || n < 0 || m < 0) return fail(c0, AGP_ERR_ARG, "negative size");
   if (P == 0) return AGP_OK;
-  if (!op_off || !ops || !prm_off || !prm || !noise || !out_mean || !out_var || !out_info || (m > 0 && !ts_pred))
-    return fail(c0, AGP_ERR_ARG, "null pointer argument");
+  if (!pp.complete() || !out_mean || !out_var || !out_info || (m > 0 && !ts_pred)) return fail(c0, AGP_ERR_ARG, "null pointer argument");
   // query points that are not training points (the reference's query set starts with model.ds: those cost n^2 each, the others n^2 more)
   int64_t m_future = m;
   {
@@ -568,7 +554,7 @@ int predict_batch_multi_impl(agp_ctx* const* ctxs, int32_t n_dev, int64_t n, con
     }
   }
   std::vector<int32_t> owner((size_t)P, 0);
-  rc = agp_shard_plan(n, P, op_off, ops, prm_off, prm, noise, 2, out_cov ? 0 : lattice_kind_of(c0), m_future, n_dev, owner.data(), nullptr, nullptr);
+  rc = agp_shard_plan(n, P, pp.op_off, pp.ops, pp.prm_off, pp.prm, pp.noise, 2, out_cov ? 0 : lattice_kind_of(c0), m_future, n_dev, owner.data(), nullptr, nullptr);
   if (rc) return fail(c0, rc, agp_last_error(nullptr));
   if (out_owner) std::memcpy(out_owner, owner.data(), sizeof(int32_t) * (size_t)P);
   std::lock_guard<std::mutex> multi_lock(c0->multi_mu);
@@ -577,13 +563,13 @@ int predict_batch_multi_impl(agp_ctx* const* ctxs, int32_t n_dev, int64_t n, con
     try {
       std::vector<int> idx;
       SubBatch S;
-      pack_shard(P, op_off, ops, prm_off, prm, noise, noise_pred, owner.data(), d, idx, S);
+      pack_shard(pp, owner.data(), d, idx, S);
       const int Pl = S.size();
       if (Pl == 0) return;
       std::vector<double> mean((size_t)Pl * (size_t)m), var((size_t)Pl * (size_t)m), cov(out_cov ? (size_t)Pl * (size_t)m * (size_t)m : 0);
       std::vector<int32_t> inf((size_t)Pl, 0);
       rcs[(size_t)d] = agp_predict_batch(ctxs[d], n, ts_pred, m, Pl, S.op_off.data(), S.ops.data(), S.prm_off.data(), S.prm.data(), S.noise.data(),
-                                         noise_pred ? S.noise_pred.data() : nullptr, mean_train, mean_pred, mean.data(), var.data(),
+                                         S.view().noise_pred, q.mean_train, q.mean_pred, mean.data(), var.data(),
                                          out_cov ? cov.data() : nullptr, inf.data());
       if (rcs[(size_t)d]) return;
       for (int b = 0; b < Pl; ++b) {
@@ -607,7 +593,7 @@ int agp_logpdf_grad_batch_multi(agp_ctx* const* ctxs, int32_t n_dev, int64_t n, 
                                 const int32_t* prm_off, const double* prm, const double* noise, double* out_logpdf, double* out_grad,
                                 double* out_grad_noise, int32_t* out_info, int32_t* out_owner) {
   return abi_guard((ctxs && n_dev > 0) ? ctxs[0] : nullptr, [&] {
-    return grad_batch_multi_impl(ctxs, n_dev, n, P, op_off, ops, prm_off, prm, noise, out_logpdf, out_grad, out_grad_noise, out_info, out_owner); });
+    return grad_batch_multi_impl(ctxs, n_dev, n, {P, op_off, ops, prm_off, prm, noise, nullptr}, out_logpdf, out_grad, out_grad_noise, out_info, out_owner); });
 }
 
 int agp_predict_batch_multi(agp_ctx* const* ctxs, int32_t n_dev, int64_t n, const double* ts_pred, int64_t m, int32_t P,
@@ -615,7 +601,7 @@ int agp_predict_batch_multi(agp_ctx* const* ctxs, int32_t n_dev, int64_t n, cons
                             const double* noise, const double* noise_pred, const double* mean_train, const double* mean_pred,
                             double* out_mean, double* out_var, double* out_cov, int32_t* out_info, int32_t* out_owner) {
   return abi_guard((ctxs && n_dev > 0) ? ctxs[0] : nullptr, [&] {
-    return predict_batch_multi_impl(ctxs, n_dev, n, ts_pred, m, P, op_off, ops, prm_off, prm, noise, noise_pred, mean_train, mean_pred,
+    return predict_batch_multi_impl(ctxs, n_dev, {n, ts_pred, m, mean_train, mean_pred}, {P, op_off, ops, prm_off, prm, noise, noise_pred},
                                     out_mean, out_var, out_cov, out_info, out_owner); });
 }
 

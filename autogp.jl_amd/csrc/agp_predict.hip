@@ -86,18 +86,19 @@ void split_queries(agp_ctx* c, int64_t n, const double* ts_pred, int64_t m, bool
 // What predict_core and predict_logpdf_core stage alike for a compiled batch: the joint point list [ts(1:n), pad, tsJ(1:mJ), pad], the
 // programs, the noises in sorted order (noise_pred defaults to noise), the means of the training and of the query points; and the
 // buffers both size alike for chunks of `chunk` particles.
-int stage_joint(agp_ctx* c, Slot* s, PinnedUploads& up, int64_t n, const double* tsJ, int64_t mJ, int P, int chunk, const Batch& bt,
-                const double* noise, const double* noise_pred, const double* mean_train, const double* meanJ,
+int stage_joint(agp_ctx* c, Slot* s, PinnedUploads& up, const PredQuery& qJ, const Particles& pp, int chunk, const Batch& bt,
                 std::vector<double>& noise_sorted, std::vector<double>& npred) {
+  const int64_t n = qJ.n, mJ = qJ.m;
+  const int P = pp.P;
   const int n1_pad = round_up(n, NB), ntot = n1_pad + round_up(mJ, NB), nt = ntot / NB;
   std::vector<double> tt((size_t)ntot, 0.0);
   std::copy(c->h_ts.begin(), c->h_ts.begin() + n, tt.begin());
-  std::copy(tsJ, tsJ + mJ, tt.begin() + n1_pad);
+  std::copy(qJ.ts_pred, qJ.ts_pred + mJ, tt.begin() + n1_pad);
   noise_sorted.resize((size_t)P); npred.resize((size_t)P);
   for (int q = 0; q < P; ++q) {
     const int p = bt.order[q];
-    noise_sorted[q] = noise[p];
-    npred[q] = noise_pred ? noise_pred[p] : noise[p];
+    noise_sorted[q] = pp.noise[p];
+    npred[q] = pp.noise_pred ? pp.noise_pred[p] : pp.noise[p];
   }
   HIPCHK(c, s->vec.ensure(sizeof(double) * (size_t)ntot * chunk));
   HIPCHK(c, s->partial.ensure(sizeof(double) * 2 * (size_t)nt * chunk));
@@ -109,13 +110,13 @@ int stage_joint(agp_ctx* c, Slot* s, PinnedUploads& up, int64_t n, const double*
   HIPCHK(c, s->noise.ensure(sizeof(double) * (size_t)P));
   HIPCHK(c, s->noise_pred.ensure(sizeof(double) * (size_t)P));
   HIPCHK(c, s->tt.ensure(sizeof(double) * (size_t)ntot));
-  if (mean_train && n > 0) {
+  if (qJ.mean_train && n > 0) {
     HIPCHK(c, s->mu1.ensure(sizeof(double) * (size_t)n));
-    up.add(s->mu1.p, mean_train, sizeof(double) * n);
+    up.add(s->mu1.p, qJ.mean_train, sizeof(double) * n);
   }
-  if (meanJ && mJ > 0) {
+  if (qJ.mean_pred && mJ > 0) {
     HIPCHK(c, s->mu2.ensure(sizeof(double) * (size_t)mJ));
-    up.add(s->mu2.p, meanJ, sizeof(double) * mJ);
+    up.add(s->mu2.p, qJ.mean_pred, sizeof(double) * mJ);
   }
   up.add(s->hdr.p, bt.hdr.data(), sizeof(ProgHdr) * P);
   up.add(s->ops.p, bt.ops.data(), bt.ops.size());
@@ -182,11 +183,13 @@ struct SumPass {
   double* out_x = nullptr;
 };
 
-int predict_core(agp_ctx* c, int64_t n, const double* ts_pred, int64_t m, int32_t P, Batch& bt,
-                 const double* noise, const double* noise_pred, const uint8_t* pred_code, const double* diag_add,
-                 const double* mean_train, const double* mean_pred, double* out_mean, double* out_var,
-                 double* out_cov, int32_t* out_info, const std::vector<std::string>* keys = nullptr,
+int predict_core(agp_ctx* c, const PredQuery& q, const Particles& pp, Batch& bt, const uint8_t* pred_code, const double* diag_add,
+                 double* out_mean, double* out_var, double* out_cov, int32_t* out_info, const std::vector<std::string>* keys = nullptr,
                  const PredLattice* pl = nullptr, const SumPass* sum = nullptr, MixPass* mix = nullptr) {
+  // (bt: pp's programs, compiled)
+  const int64_t n = q.n, m = q.m;
+  const int P = pp.P;
+  const double* ts_pred = q.ts_pred; const double* mean_train = q.mean_train; const double* mean_pred = q.mean_pred;
   const int n1_pad = round_up(n, NB);           // 0 when n == 0
   const bool lagr = pl != nullptr && pl->on;
   // `mix` (nullable; agp_predict_mixture_batch): the chunk's device means and covariances go into the mixture's running sums
@@ -255,7 +258,7 @@ int predict_core(agp_ctx* c, int64_t n, const double* ts_pred, int64_t m, int32_
   }
   PinnedUploads up;
   std::vector<double> noise_sorted, npred;
-  if (const int rc = stage_joint(c, s, up, n, tsJ, mJ, P, chunk, bt, noise, noise_pred, mean_train, meanJ, noise_sorted, npred)) return rc;
+  if (const int rc = stage_joint(c, s, up, {n, tsJ, mJ, mean_train, meanJ}, pp, chunk, bt, noise_sorted, npred)) return rc;
   if (pred_code) {
     std::vector<uint8_t> code((size_t)ntot, 0);
     std::copy(pred_code, pred_code + m, code.begin() + n1_pad);
@@ -540,9 +543,11 @@ int predict_core(agp_ctx* c, int64_t n, const double* ts_pred, int64_t m, int32_
 // partials are log|Sigma*| and the Mahalanobis term themselves (k_finish_pred_logpdf) — no Schur step, no read-out, and no
 // difference of two large log-likelihoods.  (No duplicate-query shortcut: it yields diag(Sigma*), not Sigma*.)
 // y_pred == nullptr (agp_predict_sample_batch): the query part of the right-hand side is 0.  `hooks` (nullable): see JointHooks.
-int predict_logpdf_core(agp_ctx* c, int64_t n, const double* ts_pred, const double* y_pred, int64_t m, int32_t P, Batch& bt,
-                        const double* noise, const double* noise_pred, const double* mean_train, const double* mean_pred,
-                        double* out_lp, int32_t* out_info, const PredLattice* pl, JointHooks* hooks) {
+int predict_logpdf_core(agp_ctx* c, const PredQuery& q, const double* y_pred, const Particles& pp, Batch& bt, double* out_lp,
+                        int32_t* out_info, const PredLattice* pl, JointHooks* hooks) {
+  const int64_t n = q.n, m = q.m;
+  const int P = pp.P;
+  const double* mean_train = q.mean_train; const double* mean_pred = q.mean_pred;
   const int n1_pad = round_up(n, NB), m_pad = round_up(m, NB);
   const bool lagr = pl != nullptr && pl->on;
   const int nt1 = n1_pad / NB, nt = nt1 + m_pad / NB;
@@ -564,7 +569,7 @@ int predict_logpdf_core(agp_ctx* c, int64_t n, const double* ts_pred, const doub
   HIPCHK(c, s->out_info.ensure(sizeof(int32_t) * (size_t)P));
   PinnedUploads up;
   std::vector<double> noise_sorted, npred;
-  if (const int rc = stage_joint(c, s, up, n, ts_pred, m, P, chunk, bt, noise, noise_pred, mean_train, mean_pred, noise_sorted, npred)) return rc;
+  if (const int rc = stage_joint(c, s, up, q, pp, chunk, bt, noise_sorted, npred)) return rc;
   if (y_pred) up.add(s->pred_mean.p, y_pred, sizeof(double) * m);
   up.add(s->map.p, bt.order.data(), sizeof(int32_t) * P);
   if (hooks && hooks->stage)
@@ -641,16 +646,19 @@ namespace {
 // (a Gaussian process plus a Bayesian linear model in the basis [1, t]: Rasmussen & Williams (2.42)), S = C (I + N C)^-1, N = U'W;
 // training point u:  mean = x_u - noise alpha_u,  var = noise - noise^2 (K11^-1)_uu + noise_pred  (x: the residual x - mean_train; mean_pred is added to every prediction).
 // qkind[j] >= 0: query j is training point with sorted position qkind[j];  < 0: future point -1 - qkind[j].
-int toeplitz_predict_sweep(agp_ctx* c, int64_t n, int32_t rank0, int mF, const PredLattice& pl, const std::vector<int32_t>& qkind,
-                           const std::vector<double>& xq, int P, const int32_t* op_off, const uint8_t* ops, const int32_t* prm_off,
-                           const double* prm, const double* noise, const double* noise_pred, double* out_mean, double* out_var,
-                           int32_t* out_info, const double* xs_sorted_host = nullptr, const double* mean_pred = nullptr) {
+int toeplitz_predict_sweep(agp_ctx* c, const PredQuery& q, const Particles& pp, int32_t rank0, int mF, const PredLattice& pl,
+                           const std::vector<int32_t>& qkind, const std::vector<double>& xq, double* out_mean, double* out_var,
+                           int32_t* out_info, const double* xs_sorted_host) {
   // xs_sorted_host (nullable): x - mean_train at the n training points in sorted order (mean functions: the recursion then runs on
-  // the residuals; xq holds the same residuals for the observed query points); mean_pred (nullable, per query) is added at the end
+  // the residuals; xq holds the same residuals for the observed query points); q.mean_pred (nullable, per query) is added at the end
   HIPCHK(c, hipSetDevice(c->device));
-  const int64_t m = (int64_t)qkind.size();
+  const int64_t n = q.n, m = q.m;
+  const int P = pp.P;
+  const double* noise = pp.noise; const double* noise_pred = pp.noise_pred; const double* mean_pred = q.mean_pred;
   Batch bt;
-  int rc = compile_batch(c, P, op_off, ops, prm_off, prm, bt, false, false, false, false, false, true, pl.rank_units, true);
+  CompileOpts co;
+  co.lag = true; co.lag_units = pl.rank_units; co.rank_extra = 1;
+  int rc = compile_batch(c, pp, bt, co);
   if (rc) return rc;
   SlotGuard sg(c);
   Slot* s = sg.s;
@@ -788,38 +796,70 @@ int toeplitz_predict_sweep(agp_ctx* c, int64_t n, int32_t rank0, int mF, const P
 
 thread_local bool tl_in_tpredict = false;
 
+// The dense pass of agp_predict_batch.  `mix` (nullable, with the caller particles' `weights`; agp_predict_mixture_batch's covariance
+// pass): the same pass with a covariance request, the per-particle covariances reduced on the device (predict_core's MixPass) and no
+// per-particle output but out_info.
+int predict_dense(agp_ctx* c, const PredQuery& q, const Particles& pp, double* out_mean, double* out_var, double* out_cov, int32_t* out_info,
+                  const double* weights, MixPass* mix) {
+  const int64_t n = q.n, m = q.m;
+  const bool want_cov = out_cov != nullptr || (mix && mix->cov);
+  // A resampled population holds copies of the survivors (src/inference_smc_anneal_data.jl:198-204) and the reference
+  // predicts particle by particle (src/api.jl:508-520): each distinct (program, parameters, noise, noise_pred) runs once.
+  const Distinct D(pp, c->dedup != 0);      // (malformed offsets: no dedup)
+  const Particles run = D.run();
+  const int U = D.U();
+  if (mix) {
+    // (copies: their weights are added, in the caller's order, onto the representative)
+    mix->w.assign((size_t)U, 0.0);
+    for (int p = 0; p < pp.P; ++p) mix->w[(size_t)D.rep_of(p)] += weights[p];
+    std::lock_guard<std::mutex> g(c->mu);
+    c->n_particles_seen += pp.P; c->n_particles_run += U;      // (agp_get_dedup_stats)
+  }
+  // (a store that holds nothing is not consulted: no key strings are built)
+  const bool want_keys = c->predict_reuse && n > 0 && !q.mean_train && c->store.n_slots > 0;
+  PredLattice pl;
+  predict_lattice(c, n, q.ts_pred, m, pl);
+  int64_t m_joint = m;       // query points predict_core keeps in the joint matrix (it makes the same split)
+  {
+    std::vector<int32_t> dq, di, fq;
+    split_queries(c, n, q.ts_pred, m, !want_cov && !c->ref_arith, dq, di, fq);
+    if (!dq.empty()) m_joint = (int64_t)fq.size();
+  }
+  const int nt1_ = (int)((n + NB - 1) / NB), nt_ = nt1_ + (int)((m_joint + NB - 1) / NB);
+  Batch bt;
+  CompileOpts co;
+  co.fuse_hint = co.flow_limit = n > 0 && use_flow(c, U, nt_, nt1_);
+  co.lag = pl.on; co.lag_units = pl.on ? pl.rank_units : 1; co.rank_extra = pl.on;
+  int rc = compile_batch(c, run, bt, co);
+  if (rc) return rc;
+  std::vector<std::string> keys;
+  if (want_keys)
+    for (int u = 0; u < U; ++u) keys.push_back(particle_key(run, u));
+  auto core = [&](double* om, double* ov, double* oc, int32_t* oi) {
+    return predict_core(c, q, run, bt, nullptr, nullptr, om, ov, oc, oi, want_keys ? &keys : nullptr, &pl, nullptr, mix);
+  };
+  if (!D.packed()) return core(out_mean, out_var, out_cov, out_info);
+  std::vector<double> umean(mix ? 0 : (size_t)U * m), uvar(mix ? 0 : (size_t)U * m), ucov(out_cov ? (size_t)U * m * m : 0);
+  std::vector<int32_t> uinfo((size_t)U, 0);
+  rc = core(mix ? nullptr : umean.data(), mix ? nullptr : uvar.data(), out_cov ? ucov.data() : nullptr, uinfo.data());
+  if (rc) return rc;
+  if (!mix) { D.scatter(umean.data(), out_mean, (size_t)m); D.scatter(uvar.data(), out_var, (size_t)m); }
+  if (out_cov) D.scatter(ucov.data(), out_cov, (size_t)m * m);
+  D.scatter(uinfo.data(), out_info);
+  return AGP_OK;
+}
+
 }  // namespace
 
-int predict_dense(agp_ctx* c, int64_t n, const double* ts_pred, int64_t m, int32_t P, const int32_t* op_off, const uint8_t* ops,
-                  const int32_t* prm_off, const double* prm, const double* noise, const double* noise_pred, const double* mean_train,
-                  const double* mean_pred, double* out_mean, double* out_var, double* out_cov, int32_t* out_info, const double* weights,
-                  MixPass* mix);
-
-extern "C" {
-
-static int predict_batch_body(agp_ctx* c, int64_t n, const double* ts_pred, int64_t m, int32_t P,
-                      const int32_t* op_off, const uint8_t* ops, const int32_t* prm_off, const double* prm,
-                      const double* noise, const double* noise_pred, const double* mean_train,
-                      const double* mean_pred, double* out_mean, double* out_var, double* out_cov,
-                      int32_t* out_info);
-int agp_predict_batch(agp_ctx* c, int64_t n, const double* ts_pred, int64_t m, int32_t P,
-                      const int32_t* op_off, const uint8_t* ops, const int32_t* prm_off, const double* prm,
-                      const double* noise, const double* noise_pred, const double* mean_train,
-                      const double* mean_pred, double* out_mean, double* out_var, double* out_cov,
-                      int32_t* out_info) {
-  return abi_guard(c, [&] { return predict_batch_body(c, n, ts_pred, m, P, op_off, ops, prm_off, prm, noise, noise_pred, mean_train, mean_pred, out_mean, out_var, out_cov, out_info); });
-}
-static int predict_batch_body(agp_ctx* c, int64_t n, const double* ts_pred, int64_t m, int32_t P,
-                      const int32_t* op_off, const uint8_t* ops, const int32_t* prm_off, const double* prm,
-                      const double* noise, const double* noise_pred, const double* mean_train,
-                      const double* mean_pred, double* out_mean, double* out_var, double* out_cov,
-                      int32_t* out_info) {
+int predict_batch(agp_ctx* c, const PredQuery& q, const Particles& pp, double* out_mean, double* out_var, double* out_cov, int32_t* out_info) {
+  const int64_t n = q.n, m = q.m;
+  const int P = pp.P;
+  const double* ts_pred = q.ts_pred; const double* mean_train = q.mean_train; const double* mean_pred = q.mean_pred;
   if (!c) return fail(nullptr, AGP_ERR_ARG, "null context");
   if (P < 0 || n < 0 || m < 0) return fail(c, AGP_ERR_ARG, "negative size");
   if (P == 0 || m == 0) return AGP_OK;
-  if (!op_off || !ops || !prm_off || !prm || !noise || !ts_pred || !out_mean || !out_var)
-    return fail(c, AGP_ERR_ARG, "null pointer argument");
-  if (n > c->n_max) return fail(c, AGP_ERR_NODATA, "n exceeds the data uploaded with agp_set_data");
+  if (!pp.complete() || !ts_pred || !out_mean || !out_var) return fail(c, AGP_ERR_ARG, "null pointer argument");
+  if (const int rc = check_resident(c, n)) return rc;
   HIPCHK(c, hipSetDevice(c->device));
   // Structured pass (no dense factor; toeplitz_predict_sweep): marginal predictions, the n training points
   // consecutive grid points, every query one of them or a grid point after them, nothing resident to start from — the Toeplitz +
@@ -861,33 +901,30 @@ static int predict_batch_body(agp_ctx* c, int64_t n, const double* ts_pred, int6
     }
     std::vector<int> part[2];
     if (ok) {
-      bool sane = true;
-      for (int p = 0; p < P && sane; ++p) sane = op_off[p + 1] >= op_off[p] && op_off[p + 1] - op_off[p] <= AGP_MAX_OPS_DEV && prm_off[p + 1] >= prm_off[p];
-      ok = sane;
-      if (ok) for (int p = 0; p < P; ++p) part[toeplitz_class(ops + op_off[p], op_off[p + 1] - op_off[p]) ? 1 : 0].push_back(p);
+      ok = offsets_sane(pp);
+      for (int p = 0; p < P && ok; ++p) ok = pp.n_ops(p) <= AGP_MAX_OPS_DEV;
+      if (ok) for (int p = 0; p < P; ++p) part[toeplitz_class(pp.program(p), pp.n_ops(p)) ? 1 : 0].push_back(p);
     }
     // (two sequential passes over the joint grid: ~1.2 us per point + ~1 us per training point, whatever the class's size)
     if (ok && (int)part[1].size() >= STRUCT_PRED_MIN_CLASS) {
       const int32_t rank0_abs = c->h_rank[0] - (plq.rank[0] - lo);          // rank of the first training point in the resident series
       // (noise_pred defaults to noise in the sub-batches)
-      const double* nzp = noise_pred ? noise_pred : noise;
+      Particles ppn = pp;
+      if (!ppn.noise_pred) ppn.noise_pred = pp.noise;
       SubBatch sT, sD;
-      pack_particles(part[1], op_off, ops, prm_off, prm, noise, nzp, sT);
+      pack_particles(part[1], ppn, sT);
       std::vector<double> tmean(part[1].size() * (size_t)m), tvar(part[1].size() * (size_t)m), dmean, dvar;
       std::vector<int32_t> tinfo(part[1].size(), 0), dinfo;
       Beside side([&] {
-        return toeplitz_predict_sweep(c, n, rank0_abs, mF, plq, qkind, xq, sT.size(), sT.op_off.data(), sT.ops.data(), sT.prm_off.data(),
-                                       sT.prm.data(), sT.noise.data(), sT.noise_pred.data(), tmean.data(), tvar.data(), tinfo.data(),
-                                       mean_train ? xres.data() : nullptr, mean_pred);
+        return toeplitz_predict_sweep(c, q, sT.view(), rank0_abs, mF, plq, qkind, xq, tmean.data(), tvar.data(), tinfo.data(),
+                                       mean_train ? xres.data() : nullptr);
       });
       auto dense = [&](const std::vector<int>& ix) {
         if (ix.empty()) return 0;
-        pack_particles(ix, op_off, ops, prm_off, prm, noise, nzp, sD);
+        pack_particles(ix, ppn, sD);
         dmean.resize(ix.size() * (size_t)m); dvar.resize(ix.size() * (size_t)m); dinfo.assign(ix.size(), 0);
         TlFlag nested(tl_in_tpredict);
-        const int rc0 = agp_predict_batch(c, n, ts_pred, m, sD.size(), sD.op_off.data(), sD.ops.data(), sD.prm_off.data(), sD.prm.data(),
-                                          sD.noise.data(), sD.noise_pred.data(), mean_train, mean_pred, dmean.data(), dvar.data(), nullptr,
-                                          dinfo.data());
+        const int rc0 = predict_batch(c, q, sD.view(), dmean.data(), dvar.data(), nullptr, dinfo.data());
         if (rc0) return rc0;
         for (size_t b = 0; b < ix.size(); ++b) {
           std::memcpy(out_mean + (size_t)ix[b] * m, dmean.data() + b * (size_t)m, sizeof(double) * (size_t)m);
@@ -913,268 +950,82 @@ static int predict_batch_body(agp_ctx* c, int64_t n, const double* ts_pred, int6
       return dense(refused);
     }
   }
-  return predict_dense(c, n, ts_pred, m, P, op_off, ops, prm_off, prm, noise, noise_pred, mean_train, mean_pred, out_mean, out_var, out_cov,
-                       out_info, nullptr, nullptr);
+  return predict_dense(c, q, pp, out_mean, out_var, out_cov, out_info, nullptr, nullptr);
 }
 
-static int predict_logpdf_body(agp_ctx* c, int64_t n, const double* ts_pred, const double* y_pred, int64_t m, int32_t P,
-                               const int32_t* op_off, const uint8_t* ops, const int32_t* prm_off, const double* prm,
-                               const double* noise, const double* noise_pred, const double* mean_train, const double* mean_pred,
-                               double* out_logpdf, int32_t* out_info);
-int agp_predict_logpdf_batch(agp_ctx* c, int64_t n, const double* ts_pred, const double* y_pred, int64_t m, int32_t P,
-                             const int32_t* op_off, const uint8_t* ops, const int32_t* prm_off, const double* prm,
-                             const double* noise, const double* noise_pred, const double* mean_train, const double* mean_pred,
-                             double* out_logpdf, int32_t* out_info) {
-  return abi_guard(c, [&] { return predict_logpdf_body(c, n, ts_pred, y_pred, m, P, op_off, ops, prm_off, prm, noise, noise_pred,
-                                                       mean_train, mean_pred, out_logpdf, out_info); });
-}
-static int predict_logpdf_body(agp_ctx* c, int64_t n, const double* ts_pred, const double* y_pred, int64_t m, int32_t P,
-                               const int32_t* op_off, const uint8_t* ops, const int32_t* prm_off, const double* prm,
-                               const double* noise, const double* noise_pred, const double* mean_train, const double* mean_pred,
-                               double* out_logpdf, int32_t* out_info) {
-  if (!c) return fail(nullptr, AGP_ERR_ARG, "null context");
-  if (P < 0 || n < 0 || m < 0) return fail(c, AGP_ERR_ARG, "negative size");
-  if (n > c->n_max) return fail(c, AGP_ERR_NODATA, "n exceeds the data uploaded with agp_set_data");
-  if (P == 0) return AGP_OK;
-  if (!out_logpdf) return fail(c, AGP_ERR_ARG, "null pointer argument");
-  if (m == 0) {
-    // the empty vector has density 1 under every particle (the reference scores [] as 0.)
-    for (int p = 0; p < P; ++p) { out_logpdf[p] = 0.0; if (out_info) out_info[p] = 0; }
-    return AGP_OK;
-  }
-  if (!op_off || !ops || !prm_off || !prm || !noise || !ts_pred || !y_pred) return fail(c, AGP_ERR_ARG, "null pointer argument");
-  return predict_joint_batch(c, n, ts_pred, y_pred, m, P, op_off, ops, prm_off, prm, noise, noise_pred, mean_train, mean_pred,
-                             out_logpdf, out_info, nullptr);
-}
-
-}  // extern "C"
-
-int predict_joint_batch(agp_ctx* c, int64_t n, const double* ts_pred, const double* y_pred, int64_t m, int32_t P,
-                        const int32_t* op_off, const uint8_t* ops, const int32_t* prm_off, const double* prm,
-                        const double* noise, const double* noise_pred, const double* mean_train, const double* mean_pred,
-                        double* out_logpdf, int32_t* out_info, JointHooks* hooks) {
+int predict_joint_batch(agp_ctx* c, const PredQuery& q, const double* y_pred, const Particles& pp, double* out_logpdf, int32_t* out_info,
+                        JointHooks* hooks) {
   HIPCHK(c, hipSetDevice(c->device));
   // identical particles (a resampled population, src/inference_smc_anneal_data.jl:198-204) are evaluated once, as in agp_predict_batch
   // (malformed offsets, c->dedup off: every particle — compile_batch diagnoses the offsets)
-  std::vector<int> rep, uniq;
-  if (c->dedup && P > 1) (void)distinct_particles(P, op_off, ops, prm_off, prm, noise, noise_pred, rep, uniq);
-  const bool packed = !uniq.empty() && (int)uniq.size() < P;
-  SubBatch S;
-  if (packed) pack_particles(uniq, op_off, ops, prm_off, prm, noise, noise_pred, S);
-  const int U = packed ? (int)uniq.size() : P;
-  const int32_t* bo = packed ? S.op_off.data() : op_off; const int32_t* bpo = packed ? S.prm_off.data() : prm_off;
-  const uint8_t* bops = packed ? S.ops.data() : ops; const double* bprm = packed ? S.prm.data() : prm;
-  const double* bnz = packed ? S.noise.data() : noise; const double* bnzp = packed && noise_pred ? S.noise_pred.data() : noise_pred;
+  const Distinct D(pp, c->dedup != 0);
+  const int U = D.U();
   std::vector<double> ulp((size_t)U);
   std::vector<int32_t> uinfo((size_t)U, 0);
   PredLattice pl;
-  predict_lattice(c, n, ts_pred, m, pl);
-  const bool ff = c->flow != 0;      // (predict_logpdf_core's schedule)
+  predict_lattice(c, q.n, q.ts_pred, q.m, pl);
   Batch bt;
-  int rc = compile_batch(c, U, bo, bops, bpo, bprm, bt, false, false, false, ff, ff, pl.on, pl.on ? pl.rank_units : 1, pl.on);
+  CompileOpts co;
+  co.fuse_hint = co.flow_limit = c->flow != 0;      // (predict_logpdf_core's schedule)
+  co.lag = pl.on; co.lag_units = pl.on ? pl.rank_units : 1; co.rank_extra = pl.on;
+  int rc = compile_batch(c, D.run(), bt, co);
   if (rc) return rc;
   if (hooks && hooks->plan)
-    if ((rc = hooks->plan(U, packed ? rep : std::vector<int>(), bt.order))) return rc;
-  rc = predict_logpdf_core(c, n, ts_pred, y_pred, m, U, bt, bnz, bnzp, mean_train, mean_pred, ulp.data(), uinfo.data(), &pl, hooks);
+    if ((rc = hooks->plan(U, D.packed() ? D.rep : std::vector<int>(), bt.order))) return rc;
+  rc = predict_logpdf_core(c, q, y_pred, D.run(), bt, ulp.data(), uinfo.data(), &pl, hooks);
   if (rc) return rc;
-  for (int p = 0; p < P; ++p) {
-    const size_t u = packed ? (size_t)rep[p] : (size_t)p;
-    out_logpdf[p] = ulp[u];
-    if (out_info) out_info[p] = uinfo[u];
-  }
+  D.scatter(ulp.data(), out_logpdf); D.scatter(uinfo.data(), out_info);
   return AGP_OK;
 }
 
-// The dense pass of agp_predict_batch.  `mix` (nullable, with the caller particles' `weights`; agp_predict_mixture_batch's covariance
-// pass): the same pass with a covariance request, the per-particle covariances reduced on the device (predict_core's MixPass) and no
-// per-particle output but out_info.
-int predict_dense(agp_ctx* c, int64_t n, const double* ts_pred, int64_t m, int32_t P, const int32_t* op_off, const uint8_t* ops,
-                  const int32_t* prm_off, const double* prm, const double* noise, const double* noise_pred, const double* mean_train,
-                  const double* mean_pred, double* out_mean, double* out_var, double* out_cov, int32_t* out_info, const double* weights,
-                  MixPass* mix) {
-  const bool want_cov = out_cov != nullptr || (mix && mix->cov);
-  // A resampled population holds copies of the survivors (src/inference_smc_anneal_data.jl:198-204) and the reference
-  // predicts particle by particle (src/api.jl:508-520): each distinct (program, parameters, noise, noise_pred) runs once.
-  std::vector<int> rep, uniq;
-  if (c->dedup && P > 1) (void)distinct_particles(P, op_off, ops, prm_off, prm, noise, noise_pred, rep, uniq);      // (malformed offsets: no dedup)
-  const int U = (int)uniq.size();
-  const bool packed = U != 0 && U != P;
-  if (mix) {
-    // (copies: their weights are added, in the caller's order, onto the representative)
-    mix->w.assign((size_t)(packed ? U : P), 0.0);
-    for (int p = 0; p < P; ++p) mix->w[packed ? (size_t)rep[p] : (size_t)p] += weights[p];
-    std::lock_guard<std::mutex> g(c->mu);
-    c->n_particles_seen += P; c->n_particles_run += packed ? U : P;      // (agp_get_dedup_stats)
-  }
-  // (a store that holds nothing is not consulted: no key strings are built)
-  const bool want_keys = c->predict_reuse && n > 0 && !mean_train && c->store.n_slots > 0;
-  PredLattice pl;
-  predict_lattice(c, n, ts_pred, m, pl);
-  int64_t m_joint = m;       // query points predict_core keeps in the joint matrix (it makes the same split)
-  {
-    std::vector<int32_t> dq, di, fq;
-    split_queries(c, n, ts_pred, m, !want_cov && !c->ref_arith, dq, di, fq);
-    if (!dq.empty()) m_joint = (int64_t)fq.size();
-  }
-  const int nt1_ = (int)((n + NB - 1) / NB), nt_ = nt1_ + (int)((m_joint + NB - 1) / NB);
-  auto run = [&](int Pb, const int32_t* oo, const uint8_t* so, const int32_t* po, const double* sp, const double* nz, const double* nzp,
-                 double* om, double* ov, double* oc, int32_t* oi) {
-    Batch bt;
-    const bool ff = n > 0 && use_flow(c, Pb, nt_, nt1_);
-    int rc = compile_batch(c, Pb, oo, so, po, sp, bt, false, false, false, ff, ff, pl.on, pl.on ? pl.rank_units : 1, pl.on);
-    if (rc) return rc;
-    std::vector<std::string> keys;
-    if (want_keys)
-      for (int u = 0; u < Pb; ++u) keys.push_back(particle_key(so + oo[u], oo[u + 1] - oo[u], sp + po[u], po[u + 1] - po[u], nz[u]));
-    return predict_core(c, n, ts_pred, m, Pb, bt, nz, nzp, nullptr, nullptr, mean_train, mean_pred, om, ov, oc, oi,
-                        want_keys ? &keys : nullptr, &pl, nullptr, mix);
-  };
-  if (!packed)
-    return run(P, op_off, ops, prm_off, prm, noise, noise_pred, out_mean, out_var, out_cov, out_info);
-  SubBatch S;
-  pack_particles(uniq, op_off, ops, prm_off, prm, noise, noise_pred, S);
-  S.outputs(false);
-  std::vector<double> umean(mix ? 0 : (size_t)U * m), uvar(mix ? 0 : (size_t)U * m), ucov(out_cov ? (size_t)U * m * m : 0);
-  const int rc = run(U, S.op_off.data(), S.ops.data(), S.prm_off.data(), S.prm.data(), S.noise.data(), noise_pred ? S.noise_pred.data() : nullptr,
-                     mix ? nullptr : umean.data(), mix ? nullptr : uvar.data(), out_cov ? ucov.data() : nullptr, S.info.data());
-  if (rc) return rc;
-  for (int p = 0; p < P; ++p) {
-    const size_t u = (size_t)rep[p];
-    if (!mix) {
-      std::memcpy(out_mean + (size_t)p * m, umean.data() + u * m, sizeof(double) * (size_t)m);
-      std::memcpy(out_var + (size_t)p * m, uvar.data() + u * m, sizeof(double) * (size_t)m);
-    }
-    if (out_cov) std::memcpy(out_cov + (size_t)p * m * m, ucov.data() + u * m * m, sizeof(double) * (size_t)m * m);
-    if (out_info) out_info[p] = S.info[u];
-  }
-  return AGP_OK;
-}
-
-int predict_mixture_cov(agp_ctx* c, int64_t n, const double* ts_pred, int64_t m, int32_t P, const int32_t* op_off, const uint8_t* ops,
-                        const int32_t* prm_off, const double* prm, const double* noise, const double* noise_pred,
-                        const double* mean_train, const double* mean_pred, const double* weights, MixPass& mp, int32_t* out_info) {
+int predict_mixture_cov(agp_ctx* c, const PredQuery& q, const Particles& pp, const double* weights, MixPass& mp, int32_t* out_info) {
   HIPCHK(c, hipSetDevice(c->device));
-  return predict_dense(c, n, ts_pred, m, P, op_off, ops, prm_off, prm, noise, noise_pred, mean_train, mean_pred, nullptr, nullptr, nullptr,
-                       out_info, weights, &mp);
+  return predict_dense(c, q, pp, nullptr, nullptr, nullptr, out_info, weights, &mp);
 }
 
-extern "C" {
-
-// infer_gp_sum (src/GP.jl:904-993): posterior over Z = [F_1(T*); ...; F_M(T*); X(T*)] given X(T) = xs, for the
-// sum-of-GPs model X = sum_i F_i + noise.  The joint prior covariance over [X(T); Z] is the single program
-// sum_i SEL_i * K_i evaluated on coded points (SEL_i(a,b) = 1 when both points are the observable or the
-// latent of component i), so the whole computation is one pass of the predictive machinery:
-// Cholesky of Sigma_bb = S_tt + noise I (src/GP.jl:982), Schur complement (984), + JITTER I (986).
-static int infer_gp_sum_body(agp_ctx* c, int64_t n, const double* ts_pred, int64_t p, int32_t M,
-                     const int32_t* op_off, const uint8_t* ops, const int32_t* prm_off, const double* prm,
-                     double noise, double noise_pred, double* out_mean, double* out_cov, int32_t* out_info);
-int agp_infer_gp_sum(agp_ctx* c, int64_t n, const double* ts_pred, int64_t p, int32_t M,
-                     const int32_t* op_off, const uint8_t* ops, const int32_t* prm_off, const double* prm,
-                     double noise, double noise_pred, double* out_mean, double* out_cov, int32_t* out_info) {
-  return abi_guard(c, [&] { return infer_gp_sum_body(c, n, ts_pred, p, M, op_off, ops, prm_off, prm, noise, noise_pred, out_mean, out_cov, out_info); });
-}
-static int infer_gp_sum_body(agp_ctx* c, int64_t n, const double* ts_pred, int64_t p, int32_t M,
-                     const int32_t* op_off, const uint8_t* ops, const int32_t* prm_off, const double* prm,
-                     double noise, double noise_pred, double* out_mean, double* out_cov, int32_t* out_info) {
-  if (!c) return fail(nullptr, AGP_ERR_ARG, "null context");
-  if (n < 0 || p <= 0 || M <= 0 || M > 200) return fail(c, AGP_ERR_ARG, "bad sizes");
-  if (!op_off || !ops || !prm_off || !prm || !ts_pred || !out_mean) return fail(c, AGP_ERR_ARG, "null pointer argument");
-  if (n > c->n_max) return fail(c, AGP_ERR_NODATA, "n exceeds the data uploaded with agp_set_data");
-  HIPCHK(c, hipSetDevice(c->device));
-  // composite program: K_1 SEL_1 *  K_2 SEL_2 * +  ...  K_M SEL_M * +
-  std::vector<uint8_t> cops; std::vector<double> cprm;
-  for (int i = 0; i < M; ++i) {
-    for (int q = op_off[i]; q < op_off[i + 1]; ++q) {
-      if (ops[q] > OP_CP) return fail(c, AGP_ERR_PROGRAM, "unknown opcode");
-      cops.push_back(ops[q]);
-    }
-    cprm.insert(cprm.end(), prm + prm_off[i], prm + prm_off[i + 1]);
-    cops.push_back((uint8_t)OP_SEL); cprm.push_back((double)(i + 1));
-    cops.push_back((uint8_t)OP_TIMES);
-    if (i > 0) cops.push_back((uint8_t)OP_PLUS);
-  }
-  if ((int)cops.size() > AGP_MAX_OPS) return fail(c, AGP_ERR_PROGRAM, "composite program too long");
-  const int32_t coff[2] = {0, (int32_t)cops.size()}, cpoff[2] = {0, (int32_t)cprm.size()};
-  Batch bt;
-  int rc = compile_batch(c, 1, coff, cops.data(), cpoff, cprm.data(), bt, /*allow_sel=*/true);
-  if (rc) return rc;
-  // query points: F_1(T*) ... F_M(T*) (codes 1..M), then X(T*) (code 0)
-  const int64_t ma = (int64_t)(M + 1) * p;
-  std::vector<double> tq((size_t)ma), dadd((size_t)ma), mean((size_t)ma), var((size_t)ma);
-  std::vector<uint8_t> code((size_t)ma);
-  for (int i = 0; i <= M; ++i)
-    for (int64_t j = 0; j < p; ++j) {
-      const size_t g = (size_t)i * p + j;
-      tq[g] = ts_pred[j];
-      code[g] = (uint8_t)(i < M ? i + 1 : 0);
-      dadd[g] = 1e-8 + (i == M ? noise_pred : 0.0);       // JITTER (src/GP.jl:760,986) + noise_pred on X(T*)
-    }
-  const double zero = 0.0;
-  int32_t info = 0;
-  rc = predict_core(c, n, tq.data(), ma, 1, bt, &noise, &zero, code.data(), dadd.data(), nullptr, nullptr, out_mean,
-                    var.data(), out_cov, &info);
-  if (out_info) *out_info = info;
-  return rc;
-}
+namespace {
 
 // infer_gp_sum for a population (agp_infer_gp_sum_batch) and predict_sum's numbers (agp_predict_sum_batch, sp->readout): particle
-// pp's components are CSR entries [pp M, (pp + 1) M).  Each particle's composite program is the single entry's; identical particles
-// (program, parameters, noise, noise_pred: a resampled population) run once; predict_core runs the batch with codes, the
-// single entry's diagonal terms (noise_pred on the observable rows only, see SumPass) and the pinned schedule.
-static int sum_batch_body(agp_ctx* c, int64_t n, const double* ts_pred, int64_t p, int32_t P, int32_t M, const int32_t* op_off,
-                          const uint8_t* ops, const int32_t* prm_off, const double* prm, const double* noise, const double* noise_pred,
-                          double* out_mean, double* out_var, double* out_cov, int32_t* out_info, SumPass* sp) {
+// pp's M components are the CSR entries [pp M, (pp + 1) M) of `comp` (comp.P particles; noises per particle).  Each particle's composite
+// program is the single entry's; identical particles (program, parameters, noise, noise_pred: a resampled population) run once;
+// predict_core runs the batch with codes, the single entry's diagonal terms (noise_pred on the observable rows only, see SumPass) and
+// the pinned schedule.
+int sum_batch_body(agp_ctx* c, int64_t n, const double* ts_pred, int64_t p, int32_t M, const Particles& comp, double* out_mean,
+                   double* out_var, double* out_cov, int32_t* out_info, SumPass* sp) {
+  const int P = comp.P;
   if (!c) return fail(nullptr, AGP_ERR_ARG, "null context");
   if (P < 1) return fail(c, AGP_ERR_ARG, "P must be >= 1");
   if (M < 1 || M > 200) return fail(c, AGP_ERR_ARG, "M must be in 1..200");
   if (p < 0 || n < 0) return fail(c, AGP_ERR_ARG, "negative size");
-  if (n > c->n_max) return fail(c, AGP_ERR_NODATA, "n exceeds the data uploaded with agp_set_data");
+  if (const int rc = check_resident(c, n)) return rc;
   const int64_t nq = (int64_t)sp->z.size();
   const int64_t ma = (int64_t)(M + 1) * p;
   const int64_t lim = (int64_t)1 << 31;
   if ((int64_t)P * ma >= lim || (out_cov && ma > 0 && (int64_t)P * ma >= lim / ma) || (nq > 0 && (int64_t)P * ma >= lim / nq))
     return fail(c, AGP_ERR_ARG, "an output exceeds 2^31 elements");
   if (p == 0) return AGP_OK;
-  if (!op_off || !ops || !prm_off || !prm || !noise || !ts_pred || !out_mean || (!sp->readout && !out_var) || (nq > 0 && !sp->out_x))
+  if (!comp.complete() || !ts_pred || !out_mean || (!sp->readout && !out_var) || (nq > 0 && !sp->out_x))
     return fail(c, AGP_ERR_ARG, "null pointer argument");
   HIPCHK(c, hipSetDevice(c->device));
-  // composite programs, per particle: K_1 SEL_1 *  K_2 SEL_2 * +  ...  K_M SEL_M * +   (as agp_infer_gp_sum)
+  // composite programs, per particle (as agp_infer_gp_sum)
   std::vector<int32_t> coff((size_t)P + 1, 0), cpoff((size_t)P + 1, 0);
   std::vector<uint8_t> cops; std::vector<double> cprm;
   char buf[256];
+  std::string err;
   for (int32_t pp = 0; pp < P; ++pp) {
-    const size_t o0 = cops.size();
-    for (int i = 0; i < M; ++i) {
-      const int64_t k = (int64_t)pp * M + i;
-      if (op_off[k] < 0 || prm_off[k] < 0 || op_off[k + 1] < op_off[k] || prm_off[k + 1] < prm_off[k]) {
-        snprintf(buf, sizeof buf, "particle %d: malformed offsets of component %d", (int)pp, i + 1);
-        return fail(c, AGP_ERR_ARG, buf);
-      }
-      for (int q = op_off[k]; q < op_off[k + 1]; ++q) {
-        if (ops[q] > OP_CP) { snprintf(buf, sizeof buf, "particle %d: unknown opcode", (int)pp); return fail(c, AGP_ERR_PROGRAM, buf); }
-        cops.push_back(ops[q]);
-      }
-      cprm.insert(cprm.end(), prm + prm_off[k], prm + prm_off[k + 1]);
-      cops.push_back((uint8_t)OP_SEL); cprm.push_back((double)(i + 1));
-      cops.push_back((uint8_t)OP_TIMES);
-      if (i > 0) cops.push_back((uint8_t)OP_PLUS);
-      if (cops.size() - o0 > (size_t)AGP_MAX_OPS) {
-        snprintf(buf, sizeof buf, "particle %d: composite program longer than AGP_MAX_OPS (%d) nodes", (int)pp, AGP_MAX_OPS);
-        return fail(c, AGP_ERR_PROGRAM, buf);
-      }
+    if (const int rc = append_composite(comp, (int64_t)pp * M, M, AGP_MAX_OPS, cops, cprm, err)) {
+      snprintf(buf, sizeof buf, "particle %d: ", (int)pp);
+      return fail(c, rc, buf + err);
     }
     coff[(size_t)pp + 1] = (int32_t)cops.size(); cpoff[(size_t)pp + 1] = (int32_t)cprm.size();
   }
   // noise_pred NULL: each particle's own noise (src/GP.jl:913)
-  std::vector<double> npv(noise, noise + P);
-  if (noise_pred) npv.assign(noise_pred, noise_pred + P);
-  std::vector<int> rep, uniq;
-  if (c->dedup && P > 1) (void)distinct_particles(P, coff.data(), cops.data(), cpoff.data(), cprm.data(), noise, npv.data(), rep, uniq);
-  const bool packed = !uniq.empty() && (int)uniq.size() < P;
-  if (!packed) { uniq.resize((size_t)P); for (int pp = 0; pp < P; ++pp) uniq[(size_t)pp] = pp; }
-  SubBatch S;
-  pack_particles(uniq, coff.data(), cops.data(), cpoff.data(), cprm.data(), noise, npv.data(), S);
-  const int U = S.size();
+  const double* npv = comp.noise_pred ? comp.noise_pred : comp.noise;
+  // (always packed: predict_core reads the packed arrays whatever the population; `copies` decides where it writes)
+  const Distinct D({P, coff.data(), cops.data(), cpoff.data(), cprm.data(), comp.noise, npv}, c->dedup != 0, Distinct::Pack::always);
+  const Particles run = D.run();
+  const int U = D.U();
+  const bool copies = D.copies();
   { std::lock_guard<std::mutex> g(c->mu); c->n_particles_seen += P; c->n_particles_run += U; }      // (agp_get_dedup_stats)
   // query points: F_1(T*) ... F_M(T*) (codes 1..M), then X(T*) (code 0); JITTER on every row (noise_pred: k_pred_extract)
   std::vector<double> tq((size_t)ma), dadd((size_t)ma, 1e-8);
@@ -1184,46 +1035,126 @@ static int sum_batch_body(agp_ctx* c, int64_t n, const double* ts_pred, int64_t 
       tq[(size_t)i * p + j] = ts_pred[j];
       code[(size_t)i * p + j] = (uint8_t)(i < M ? i + 1 : 0);
     }
-  const bool ff = c->flow != 0;      // (predict_core's schedule for this pass)
   Batch bt;
-  int rc = compile_batch(c, U, S.op_off.data(), S.ops.data(), S.prm_off.data(), S.prm.data(), bt, /*allow_sel=*/true, false, false, ff, ff);
+  CompileOpts co;
+  co.allow_sel = true; co.fuse_hint = co.flow_limit = c->flow != 0;      // (predict_core's schedule for this pass)
+  int rc = compile_batch(c, run, bt, co);
   if (rc) {
     // name the caller's particle: the first distinct particle that does not compile on its own
+    CompileOpts c1;
+    c1.allow_sel = true;
     for (int u = 0; u < U; ++u) {
       Batch b1;
-      const int32_t o1[2] = {0, S.op_off[(size_t)u + 1] - S.op_off[(size_t)u]}, q1[2] = {0, S.prm_off[(size_t)u + 1] - S.prm_off[(size_t)u]};
+      const int32_t o1[2] = {0, run.n_ops(u)}, q1[2] = {0, run.n_prm(u)};
       const double zero = 0.0;
-      const double* pp1 = q1[1] > 0 ? S.prm.data() + S.prm_off[(size_t)u] : &zero;
-      if (compile_batch(c, 1, o1, S.ops.data() + S.op_off[(size_t)u], q1, pp1, b1, true) == 0) continue;
+      if (compile_batch(c, {1, o1, run.program(u), q1, q1[1] > 0 ? run.params(u) : &zero, nullptr, nullptr}, b1, c1) == 0) continue;
       std::string e;
       { std::lock_guard<std::mutex> g(c->mu); e = c->err; }
       if (e.rfind("particle 0: ", 0) == 0) e = e.substr(12);
-      snprintf(buf, sizeof buf, "particle %d: ", uniq[(size_t)u]);
+      snprintf(buf, sizeof buf, "particle %d: ", D.uniq[(size_t)u]);
       return fail(c, AGP_ERR_PROGRAM, buf + e);
     }
     return rc;
   }
   const size_t ue = (size_t)ma;
-  std::vector<double> umean(packed ? U * ue : 0), uvar(packed && out_var ? U * ue : 0), ucov(packed && out_cov ? U * ue * ue : 0),
-      ux(packed && nq > 0 ? U * ue * (size_t)nq : 0);
+  std::vector<double> umean(copies ? U * ue : 0), uvar(copies && out_var ? U * ue : 0), ucov(copies && out_cov ? U * ue * ue : 0),
+      ux(copies && nq > 0 ? U * ue * (size_t)nq : 0);
   std::vector<int32_t> uinfo((size_t)U, 0);
   double* x_caller = sp->out_x;
-  if (packed && nq > 0) sp->out_x = ux.data();
-  rc = predict_core(c, n, tq.data(), ma, U, bt, S.noise.data(), S.noise_pred.data(), code.data(), dadd.data(), nullptr, nullptr,
-                    packed ? umean.data() : out_mean, packed ? (out_var ? uvar.data() : nullptr) : out_var,
-                    packed ? (out_cov ? ucov.data() : nullptr) : out_cov, uinfo.data(), nullptr, nullptr, sp);
+  if (copies && nq > 0) sp->out_x = ux.data();
+  rc = predict_core(c, {n, tq.data(), ma, nullptr, nullptr}, run, bt, code.data(), dadd.data(), copies ? umean.data() : out_mean,
+                    copies ? (out_var ? uvar.data() : nullptr) : out_var, copies ? (out_cov ? ucov.data() : nullptr) : out_cov,
+                    uinfo.data(), nullptr, nullptr, sp);
   sp->out_x = x_caller;
   if (rc) return rc;
-  for (int pp = 0; pp < P; ++pp) {
-    const size_t u = packed ? (size_t)rep[(size_t)pp] : (size_t)pp;
-    if (out_info) out_info[pp] = uinfo[u];
-    if (!packed) continue;
-    std::memcpy(out_mean + (size_t)pp * ue, umean.data() + u * ue, sizeof(double) * ue);
-    if (out_var) std::memcpy(out_var + (size_t)pp * ue, uvar.data() + u * ue, sizeof(double) * ue);
-    if (out_cov) std::memcpy(out_cov + (size_t)pp * ue * ue, ucov.data() + u * ue * ue, sizeof(double) * ue * ue);
-    if (nq > 0) std::memcpy(x_caller + (size_t)pp * ue * nq, ux.data() + u * ue * nq, sizeof(double) * ue * nq);
-  }
+  D.scatter(uinfo.data(), out_info);
+  if (!copies) return AGP_OK;
+  D.scatter(umean.data(), out_mean, ue);
+  if (out_var) D.scatter(uvar.data(), out_var, ue);
+  if (out_cov) D.scatter(ucov.data(), out_cov, ue * ue);
+  if (nq > 0) D.scatter(ux.data(), x_caller, ue * (size_t)nq);
   return AGP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int agp_predict_batch(agp_ctx* c, int64_t n, const double* ts_pred, int64_t m, int32_t P,
+                      const int32_t* op_off, const uint8_t* ops, const int32_t* prm_off, const double* prm,
+                      const double* noise, const double* noise_pred, const double* mean_train,
+                      const double* mean_pred, double* out_mean, double* out_var, double* out_cov,
+                      int32_t* out_info) {
+  return abi_guard(c, [&] {
+    return predict_batch(c, {n, ts_pred, m, mean_train, mean_pred}, {P, op_off, ops, prm_off, prm, noise, noise_pred}, out_mean, out_var,
+                         out_cov, out_info);
+  });
+}
+
+int agp_predict_logpdf_batch(agp_ctx* c, int64_t n, const double* ts_pred, const double* y_pred, int64_t m, int32_t P,
+                             const int32_t* op_off, const uint8_t* ops, const int32_t* prm_off, const double* prm,
+                             const double* noise, const double* noise_pred, const double* mean_train, const double* mean_pred,
+                             double* out_logpdf, int32_t* out_info) {
+  return abi_guard(c, [&]() -> int {
+    const Particles pp{P, op_off, ops, prm_off, prm, noise, noise_pred};
+    if (!c) return fail(nullptr, AGP_ERR_ARG, "null context");
+    if (P < 0 || n < 0 || m < 0) return fail(c, AGP_ERR_ARG, "negative size");
+    if (const int rc = check_resident(c, n)) return rc;
+    if (P == 0) return AGP_OK;
+    if (!out_logpdf) return fail(c, AGP_ERR_ARG, "null pointer argument");
+    if (m == 0) {
+      // the empty vector has density 1 under every particle (the reference scores [] as 0.)
+      for (int p = 0; p < P; ++p) { out_logpdf[p] = 0.0; if (out_info) out_info[p] = 0; }
+      return AGP_OK;
+    }
+    if (!pp.complete() || !ts_pred || !y_pred) return fail(c, AGP_ERR_ARG, "null pointer argument");
+    return predict_joint_batch(c, {n, ts_pred, m, mean_train, mean_pred}, y_pred, pp, out_logpdf, out_info, nullptr);
+  });
+}
+
+// infer_gp_sum (src/GP.jl:904-993): posterior over Z = [F_1(T*); ...; F_M(T*); X(T*)] given X(T) = xs, for the
+// sum-of-GPs model X = sum_i F_i + noise.  The joint prior covariance over [X(T); Z] is the single program
+// sum_i SEL_i * K_i evaluated on coded points (SEL_i(a,b) = 1 when both points are the observable or the
+// latent of component i), so the whole computation is one pass of the predictive machinery:
+// Cholesky of Sigma_bb = S_tt + noise I (src/GP.jl:982), Schur complement (984), + JITTER I (986).
+int agp_infer_gp_sum(agp_ctx* c, int64_t n, const double* ts_pred, int64_t p, int32_t M,
+                     const int32_t* op_off, const uint8_t* ops, const int32_t* prm_off, const double* prm,
+                     double noise, double noise_pred, double* out_mean, double* out_cov, int32_t* out_info) {
+  return abi_guard(c, [&]() -> int {
+    if (!c) return fail(nullptr, AGP_ERR_ARG, "null context");
+    if (n < 0 || p <= 0 || M <= 0 || M > 200) return fail(c, AGP_ERR_ARG, "bad sizes");
+    if (!op_off || !ops || !prm_off || !prm || !ts_pred || !out_mean) return fail(c, AGP_ERR_ARG, "null pointer argument");
+    if (const int rc = check_resident(c, n)) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    // (every opcode is checked before the length, as this entry always has)
+    std::vector<uint8_t> cops; std::vector<double> cprm;
+    std::string err;
+    if (const int rc = append_composite({M, op_off, ops, prm_off, prm, nullptr, nullptr}, 0, M, INT32_MAX, cops, cprm, err)) return fail(c, rc, err);
+    if ((int)cops.size() > AGP_MAX_OPS) return fail(c, AGP_ERR_PROGRAM, "composite program too long");
+    const int32_t coff[2] = {0, (int32_t)cops.size()}, cpoff[2] = {0, (int32_t)cprm.size()};
+    const double zero = 0.0;
+    const Particles one{1, coff, cops.data(), cpoff, cprm.data(), &noise, &zero};
+    Batch bt;
+    CompileOpts co;
+    co.allow_sel = true;
+    int rc = compile_batch(c, one, bt, co);
+    if (rc) return rc;
+    // query points: F_1(T*) ... F_M(T*) (codes 1..M), then X(T*) (code 0)
+    const int64_t ma = (int64_t)(M + 1) * p;
+    std::vector<double> tq((size_t)ma), dadd((size_t)ma), var((size_t)ma);
+    std::vector<uint8_t> code((size_t)ma);
+    for (int i = 0; i <= M; ++i)
+      for (int64_t j = 0; j < p; ++j) {
+        const size_t g = (size_t)i * p + j;
+        tq[g] = ts_pred[j];
+        code[g] = (uint8_t)(i < M ? i + 1 : 0);
+        dadd[g] = 1e-8 + (i == M ? noise_pred : 0.0);       // JITTER (src/GP.jl:760,986) + noise_pred on X(T*)
+      }
+    int32_t info = 0;
+    rc = predict_core(c, {n, tq.data(), ma, nullptr, nullptr}, one, bt, code.data(), dadd.data(), out_mean, var.data(), out_cov, &info);
+    if (out_info) *out_info = info;
+    return rc;
+  });
 }
 
 int agp_infer_gp_sum_batch(agp_ctx* c, int64_t n, const double* ts_pred, int64_t p, int32_t P, int32_t M, const int32_t* op_off,
@@ -1231,87 +1162,77 @@ int agp_infer_gp_sum_batch(agp_ctx* c, int64_t n, const double* ts_pred, int64_t
                            double* out_mean, double* out_var, double* out_cov, int32_t* out_info) {
   SumPass sp;      // (no read-out: the pinned schedule and the observable-rows noise_pred only)
   sp.p_rows = p;
-  return abi_guard(c, [&] { return sum_batch_body(c, n, ts_pred, p, P, M, op_off, ops, prm_off, prm, noise, noise_pred, out_mean, out_var,
-                                                  out_cov, out_info, &sp); });
-}
-
-static int predict_sum_body(agp_ctx* c, int64_t n, const double* ts_pred, int64_t p, int32_t P, int32_t M, const int32_t* op_off,
-                            const uint8_t* ops, const int32_t* prm_off, const double* prm, const double* noise, const double* noise_pred,
-                            double y_slope, double y_intercept, const double* q, int64_t nq, double* out_mean, double* out_x,
-                            int32_t* out_info) {
-  if (!c) return fail(nullptr, AGP_ERR_ARG, "null context");
-  if (nq < 0) return fail(c, AGP_ERR_ARG, "negative size");
-  if (nq > 0 && !q) return fail(c, AGP_ERR_ARG, "null q");
-  for (int64_t k = 0; k < nq; ++k)
-    if (!(q[k] > 0.0 && q[k] < 1.0)) return fail(c, AGP_ERR_ARG, "quantile must be in (0, 1)");
-  if (!(std::isfinite(y_slope) && y_slope != 0.0 && std::isfinite(y_intercept)))
-    return fail(c, AGP_ERR_ARG, "y_transform must have a finite non-zero slope and a finite intercept");
-  SumPass sp;
-  sp.readout = true; sp.p_rows = p; sp.slope = y_slope; sp.intercept = y_intercept; sp.out_x = out_x;
-  sp.z.resize((size_t)nq);
-  for (int64_t k = 0; k < nq; ++k) sp.z[(size_t)k] = ndtri(q[k]);
-  return sum_batch_body(c, n, ts_pred, p, P, M, op_off, ops, prm_off, prm, noise, noise_pred, out_mean, nullptr, nullptr, out_info, &sp);
+  return abi_guard(c, [&] {
+    return sum_batch_body(c, n, ts_pred, p, M, {P, op_off, ops, prm_off, prm, noise, noise_pred}, out_mean, out_var, out_cov, out_info, &sp);
+  });
 }
 
 int agp_predict_sum_batch(agp_ctx* c, int64_t n, const double* ts_pred, int64_t p, int32_t P, int32_t M, const int32_t* op_off,
                           const uint8_t* ops, const int32_t* prm_off, const double* prm, const double* noise, const double* noise_pred,
                           double y_slope, double y_intercept, const double* q, int64_t nq, double* out_mean, double* out_x,
                           int32_t* out_info) {
-  return abi_guard(c, [&] { return predict_sum_body(c, n, ts_pred, p, P, M, op_off, ops, prm_off, prm, noise, noise_pred, y_slope,
-                                                    y_intercept, q, nq, out_mean, out_x, out_info); });
+  return abi_guard(c, [&]() -> int {
+    if (!c) return fail(nullptr, AGP_ERR_ARG, "null context");
+    if (nq < 0) return fail(c, AGP_ERR_ARG, "negative size");
+    if (nq > 0 && !q) return fail(c, AGP_ERR_ARG, "null q");
+    for (int64_t k = 0; k < nq; ++k)
+      if (!(q[k] > 0.0 && q[k] < 1.0)) return fail(c, AGP_ERR_ARG, "quantile must be in (0, 1)");
+    if (const int rc = check_y_transform(c, y_slope, y_intercept)) return rc;
+    SumPass sp;
+    sp.readout = true; sp.p_rows = p; sp.slope = y_slope; sp.intercept = y_intercept; sp.out_x = out_x;
+    sp.z.resize((size_t)nq);
+    for (int64_t k = 0; k < nq; ++k) sp.z[(size_t)k] = ndtri(q[k]);
+    return sum_batch_body(c, n, ts_pred, p, M, {P, op_off, ops, prm_off, prm, noise, noise_pred}, out_mean, nullptr, nullptr, out_info, &sp);
+  });
 }
 
-static int cov_matrix_body(agp_ctx* c, const double* ts, int64_t n, const uint8_t* ops, int32_t n_ops, const double* prm,
-                   int32_t n_prm, double noise, double* out_K);
 int agp_cov_matrix(agp_ctx* c, const double* ts, int64_t n, const uint8_t* ops, int32_t n_ops, const double* prm,
                    int32_t n_prm, double noise, double* out_K) {
-  return abi_guard(c, [&] { return cov_matrix_body(c, ts, n, ops, n_ops, prm, n_prm, noise, out_K); });
-}
-static int cov_matrix_body(agp_ctx* c, const double* ts, int64_t n, const uint8_t* ops, int32_t n_ops, const double* prm,
-                   int32_t n_prm, double noise, double* out_K) {
-  if (!c) return fail(nullptr, AGP_ERR_ARG, "null context");
-  if (n < 0) return fail(c, AGP_ERR_ARG, "negative size");
-  if (n == 0) return AGP_OK;
-  if (!ts || !ops || !out_K) return fail(c, AGP_ERR_ARG, "null pointer argument");
-  HIPCHK(c, hipSetDevice(c->device));
-  const int32_t op_off[2] = {0, n_ops}, prm_off[2] = {0, n_prm};
-  double dummy = 0.0;
-  Batch bt;
-  int rc = compile_batch(c, 1, op_off, ops, prm_off, prm ? prm : &dummy, bt);
-  if (rc) return rc;
-  SlotGuard sg(c);
-  Slot* s = sg.s;
-  if (!s->stream) HIPCHK(c, hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
-  hipStream_t st = s->stream;
-  const int n_pad = round_up(n, NB), nt = n_pad / NB, ntiles = nt * (nt + 1) / 2;
-  const long long strideA = (long long)ntiles * NB2;
-  std::vector<double> tt((size_t)n_pad, 0.0);
-  std::copy(ts, ts + n, tt.begin());
-  HIPCHK(c, s->A.ensure((size_t)strideA * 8));
-  HIPCHK(c, s->hdr.ensure(sizeof(ProgHdr)));
-  HIPCHK(c, s->ops.ensure(bt.ops.size()));
-  HIPCHK(c, s->prm.ensure(sizeof(double) * std::max<size_t>(1, bt.prm.size())));
-  HIPCHK(c, s->noise.ensure(sizeof(double)));
-  HIPCHK(c, s->tt.ensure(sizeof(double) * (size_t)n_pad));
-  HIPCHK(c, s->dense.ensure(sizeof(double) * (size_t)n * n));
-  HIPCHK(c, hipMemcpyAsync(s->hdr.p, bt.hdr.data(), sizeof(ProgHdr), hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(s->ops.p, bt.ops.data(), bt.ops.size(), hipMemcpyHostToDevice, st));
-  if (!bt.prm.empty())
-    HIPCHK(c, hipMemcpyAsync(s->prm.p, bt.prm.data(), sizeof(double) * bt.prm.size(), hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(s->noise.p, &noise, sizeof(double), hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(s->tt.p, tt.data(), sizeof(double) * n_pad, hipMemcpyHostToDevice, st));
-  CovArgs cv = {};
-  cv.tt = s->tt.as<double>(); cv.n1 = (int)n; cv.n1_pad = n_pad; cv.m2 = 0; cv.nt = nt;
-  cv.hdr = s->hdr.as<ProgHdr>(); cv.ops = s->ops.as<uint8_t>(); cv.prm = s->prm.as<double>();
-  cv.noise = s->noise.as<double>(); cv.A = s->A.as<double>(); cv.strideA = strideA; cv.P = 1;
-  cv.p_off = 0;
-  HIPCHK(c, launch_cov(st, cv, ntiles, 1, bt.max_cp, bt.max_depth));
-  const long long nel = (long long)n * n;
-  launch_unpack_dense(st, s->A.as<double>(), (int)n, 0, s->dense.as<double>());
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(out_K, s->dense.p, sizeof(double) * nel, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipStreamSynchronize(st));
-  return AGP_OK;
+  return abi_guard(c, [&]() -> int {
+    if (!c) return fail(nullptr, AGP_ERR_ARG, "null context");
+    if (n < 0) return fail(c, AGP_ERR_ARG, "negative size");
+    if (n == 0) return AGP_OK;
+    if (!ts || !ops || !out_K) return fail(c, AGP_ERR_ARG, "null pointer argument");
+    HIPCHK(c, hipSetDevice(c->device));
+    const int32_t op_off[2] = {0, n_ops}, prm_off[2] = {0, n_prm};
+    double dummy = 0.0;
+    Batch bt;
+    int rc = compile_batch(c, {1, op_off, ops, prm_off, prm ? prm : &dummy, &noise, nullptr}, bt);
+    if (rc) return rc;
+    SlotGuard sg(c);
+    Slot* s = sg.s;
+    if (!s->stream) HIPCHK(c, hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
+    hipStream_t st = s->stream;
+    const int n_pad = round_up(n, NB), nt = n_pad / NB, ntiles = nt * (nt + 1) / 2;
+    const long long strideA = (long long)ntiles * NB2;
+    std::vector<double> tt((size_t)n_pad, 0.0);
+    std::copy(ts, ts + n, tt.begin());
+    HIPCHK(c, s->A.ensure((size_t)strideA * 8));
+    HIPCHK(c, s->hdr.ensure(sizeof(ProgHdr)));
+    HIPCHK(c, s->ops.ensure(bt.ops.size()));
+    HIPCHK(c, s->prm.ensure(sizeof(double) * std::max<size_t>(1, bt.prm.size())));
+    HIPCHK(c, s->noise.ensure(sizeof(double)));
+    HIPCHK(c, s->tt.ensure(sizeof(double) * (size_t)n_pad));
+    HIPCHK(c, s->dense.ensure(sizeof(double) * (size_t)n * n));
+    HIPCHK(c, hipMemcpyAsync(s->hdr.p, bt.hdr.data(), sizeof(ProgHdr), hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(s->ops.p, bt.ops.data(), bt.ops.size(), hipMemcpyHostToDevice, st));
+    if (!bt.prm.empty())
+      HIPCHK(c, hipMemcpyAsync(s->prm.p, bt.prm.data(), sizeof(double) * bt.prm.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(s->noise.p, &noise, sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(s->tt.p, tt.data(), sizeof(double) * n_pad, hipMemcpyHostToDevice, st));
+    CovArgs cv = {};
+    cv.tt = s->tt.as<double>(); cv.n1 = (int)n; cv.n1_pad = n_pad; cv.m2 = 0; cv.nt = nt;
+    cv.hdr = s->hdr.as<ProgHdr>(); cv.ops = s->ops.as<uint8_t>(); cv.prm = s->prm.as<double>();
+    cv.noise = s->noise.as<double>(); cv.A = s->A.as<double>(); cv.strideA = strideA; cv.P = 1;
+    cv.p_off = 0;
+    HIPCHK(c, launch_cov(st, cv, ntiles, 1, bt.max_cp, bt.max_depth));
+    const long long nel = (long long)n * n;
+    launch_unpack_dense(st, s->A.as<double>(), (int)n, 0, s->dense.as<double>());
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(out_K, s->dense.p, sizeof(double) * nel, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    return AGP_OK;
+  });
 }
 
 int agp_debug_cholesky(agp_ctx* c, const double* K, int64_t n, double* out_L, int32_t* out_info) {

@@ -78,84 +78,71 @@ int mixture_core(agp_ctx* c, int64_t m, int32_t P, const double* means, const do
 
 extern "C" {
 
-static int mixture_quantile_body(agp_ctx* c, int64_t m, int32_t P, const double* means, const double* vars, const double* weights,
-                                 const double* q, int64_t nq, double tol, int64_t max_iter, double* out_x, int32_t* out_converged,
-                                 int32_t* out_iters) {
-  int rc = check_common(c, m, P, weights, q, nq);
-  if (rc) return rc;
-  if (m == 0 || nq == 0) return AGP_OK;
-  if (!means || !vars || !out_x) return fail(c, AGP_ERR_ARG, "null pointer argument");
-  // Normal(mu, sqrt(v)) of the reference throws on these; components at weight 0 are never evaluated
-  for (int32_t p = 0; p < P; ++p) {
-    if (weights[p] == 0.0) continue;
-    for (int64_t i = 0; i < m; ++i) {
-      const double mu = means[(size_t)p * m + i], v = vars[(size_t)p * m + i];
-      if (!std::isfinite(mu)) return fail(c, AGP_ERR_ARG, "non-finite component mean at positive weight");
-      if (!(v >= 0.0)) return fail(c, AGP_ERR_ARG, "negative or NaN component variance at positive weight");
-    }
-  }
-  return mixture_core(c, m, P, means, vars, weights, q, nq, tol, max_iter, out_x, out_converged, out_iters);
-}
-
 int agp_mixture_quantile(agp_ctx* c, int64_t m, int32_t P, const double* means, const double* vars, const double* weights,
                          const double* q, int64_t nq, double tol, int64_t max_iter, double* out_x, int32_t* out_converged,
                          int32_t* out_iters) {
-  return abi_guard(c, [&] { return mixture_quantile_body(c, m, P, means, vars, weights, q, nq, tol, max_iter, out_x, out_converged,
-                                                         out_iters); });
+  return abi_guard(c, [&]() -> int {
+    int rc = check_common(c, m, P, weights, q, nq);
+    if (rc) return rc;
+    if (m == 0 || nq == 0) return AGP_OK;
+    if (!means || !vars || !out_x) return fail(c, AGP_ERR_ARG, "null pointer argument");
+    // Normal(mu, sqrt(v)) of the reference throws on these; components at weight 0 are never evaluated
+    for (int32_t p = 0; p < P; ++p) {
+      if (weights[p] == 0.0) continue;
+      for (int64_t i = 0; i < m; ++i) {
+        const double mu = means[(size_t)p * m + i], v = vars[(size_t)p * m + i];
+        if (!std::isfinite(mu)) return fail(c, AGP_ERR_ARG, "non-finite component mean at positive weight");
+        if (!(v >= 0.0)) return fail(c, AGP_ERR_ARG, "negative or NaN component variance at positive weight");
+      }
+    }
+    return mixture_core(c, m, P, means, vars, weights, q, nq, tol, max_iter, out_x, out_converged, out_iters);
+  });
 }
 
-static int predict_quantile_body(agp_ctx* c, int64_t n, const double* ts_pred, int64_t m, int32_t P, const int32_t* op_off,
-                                 const uint8_t* ops, const int32_t* prm_off, const double* prm, const double* noise,
-                                 const double* noise_pred, const double* mean_train, const double* mean_pred, const double* weights,
-                                 double y_slope, double y_intercept, const double* q, int64_t nq, double tol, int64_t max_iter,
-                                 double* out_x, int32_t* out_converged, int32_t* out_iters, int32_t* out_info) {
-  int rc = check_common(c, m, P, weights, q, nq);
-  if (rc) return rc;
-  if (n < 0) return fail(c, AGP_ERR_ARG, "negative size");
-  if (!(std::isfinite(y_slope) && y_slope != 0.0 && std::isfinite(y_intercept)))
-    return fail(c, AGP_ERR_ARG, "y_transform must have a finite non-zero slope and a finite intercept");
-  if (m == 0 || nq == 0) return AGP_OK;
-  if (!out_x) return fail(c, AGP_ERR_ARG, "null pointer argument");
-  // the marginal pass (out_cov = NULL: structured, lattice, store-reuse and dedup paths as agp_predict_batch), staged on the host
-  const size_t nc = (size_t)m * P;
-  std::vector<double> mean(nc), var(nc);
-  std::vector<int32_t> info((size_t)P, 0);
-  rc = agp_predict_batch(c, n, ts_pred, m, P, op_off, ops, prm_off, prm, noise, noise_pred, mean_train, mean_pred, mean.data(),
-                         var.data(), nullptr, info.data());
-  if (rc) return rc;
-  // raw space (predict_mvn, src/api.jl:513-520; Transforms.jl:44-49): (mu - intercept) / slope, (1 / slope^2) * var
-  const double iv = 1.0 / (y_slope * y_slope);
-  bool bad = false;
-  for (int32_t p = 0; p < P; ++p) {
-    double* mp = mean.data() + (size_t)p * m;
-    double* vp = var.data() + (size_t)p * m;
-    for (int64_t i = 0; i < m; ++i) {
-      mp[i] = (mp[i] - y_intercept) / y_slope;
-      vp[i] = iv * vp[i];
-      if (info[(size_t)p] == 0 && !(std::isfinite(mp[i]) && vp[i] >= 0.0)) info[(size_t)p] = (int32_t)(n + i + 1);
-    }
-    bad = bad || info[(size_t)p] != 0;
-  }
-  if (out_info) std::copy(info.begin(), info.end(), out_info);
-  if (bad) {
-    // a particle without a predictive: the mixture is undefined (the reference throws) — NaN everywhere, nothing converged
-    const size_t no = (size_t)m * nq;
-    std::fill(out_x, out_x + no, std::numeric_limits<double>::quiet_NaN());
-    if (out_converged) std::fill(out_converged, out_converged + no, 0);
-    if (out_iters) std::fill(out_iters, out_iters + no, 0);
-    return AGP_OK;
-  }
-  return mixture_core(c, m, P, mean.data(), var.data(), weights, q, nq, tol, max_iter, out_x, out_converged, out_iters);
-}
 
 int agp_predict_quantile_batch(agp_ctx* c, int64_t n, const double* ts_pred, int64_t m, int32_t P, const int32_t* op_off,
                                const uint8_t* ops, const int32_t* prm_off, const double* prm, const double* noise,
                                const double* noise_pred, const double* mean_train, const double* mean_pred, const double* weights,
                                double y_slope, double y_intercept, const double* q, int64_t nq, double tol, int64_t max_iter,
                                double* out_x, int32_t* out_converged, int32_t* out_iters, int32_t* out_info) {
-  return abi_guard(c, [&] { return predict_quantile_body(c, n, ts_pred, m, P, op_off, ops, prm_off, prm, noise, noise_pred, mean_train,
-                                                         mean_pred, weights, y_slope, y_intercept, q, nq, tol, max_iter, out_x,
-                                                         out_converged, out_iters, out_info); });
+  return abi_guard(c, [&]() -> int {
+    int rc = check_common(c, m, P, weights, q, nq);
+    if (rc) return rc;
+    if (n < 0) return fail(c, AGP_ERR_ARG, "negative size");
+    if ((rc = check_y_transform(c, y_slope, y_intercept))) return rc;
+    if (m == 0 || nq == 0) return AGP_OK;
+    if (!out_x) return fail(c, AGP_ERR_ARG, "null pointer argument");
+    // the marginal pass (out_cov = NULL: structured, lattice, store-reuse and dedup paths as agp_predict_batch), staged on the host
+    const size_t nc = (size_t)m * P;
+    std::vector<double> mean(nc), var(nc);
+    std::vector<int32_t> info((size_t)P, 0);
+    rc = predict_batch(c, {n, ts_pred, m, mean_train, mean_pred}, {P, op_off, ops, prm_off, prm, noise, noise_pred}, mean.data(), var.data(),
+                       nullptr, info.data());
+    if (rc) return rc;
+    // raw space (predict_mvn, src/api.jl:513-520; Transforms.jl:44-49): (mu - intercept) / slope, (1 / slope^2) * var
+    const double iv = 1.0 / (y_slope * y_slope);
+    bool bad = false;
+    for (int32_t p = 0; p < P; ++p) {
+      double* mp = mean.data() + (size_t)p * m;
+      double* vp = var.data() + (size_t)p * m;
+      for (int64_t i = 0; i < m; ++i) {
+        mp[i] = (mp[i] - y_intercept) / y_slope;
+        vp[i] = iv * vp[i];
+        if (info[(size_t)p] == 0 && !(std::isfinite(mp[i]) && vp[i] >= 0.0)) info[(size_t)p] = (int32_t)(n + i + 1);
+      }
+      bad = bad || info[(size_t)p] != 0;
+    }
+    if (out_info) std::copy(info.begin(), info.end(), out_info);
+    if (bad) {
+      // a particle without a predictive: the mixture is undefined (the reference throws) — NaN everywhere, nothing converged
+      const size_t no = (size_t)m * nq;
+      std::fill(out_x, out_x + no, std::numeric_limits<double>::quiet_NaN());
+      if (out_converged) std::fill(out_converged, out_converged + no, 0);
+      if (out_iters) std::fill(out_iters, out_iters + no, 0);
+      return AGP_OK;
+    }
+    return mixture_core(c, m, P, mean.data(), var.data(), weights, q, nq, tol, max_iter, out_x, out_converged, out_iters);
+  });
 }
 
 }  // extern "C"

@@ -113,33 +113,29 @@ hipError_t run_factor_extend(hipStream_t st, CholArgs ca, int dcov, bool split_d
 // d_out_caller (optional, device, P doubles): the log-pdfs in the CALLER's particle order (duplicates expanded) are also left
 // there, ordered behind the sweep on the slot's stream and complete on return; *wrote_device says whether that happened
 // (not for n = 0 or when the sweep fell back to the plain entry).
-int extend_impl(agp_ctx* c, int64_t n, int32_t P, const int32_t* op_off, const uint8_t* ops, const int32_t* prm_off,
-                const double* prm, const double* noise, double* out_lp, int32_t* out_info,
-                double* d_out_caller, bool* wrote_device) {
+int extend_impl(agp_ctx* c, int64_t n, const Particles& pp, double* out_lp, int32_t* out_info, double* d_out_caller, bool* wrote_device) {
+  const int P = pp.P;
   if (wrote_device) *wrote_device = false;
   if (!c) return fail(nullptr, AGP_ERR_ARG, "null context");
   if (P < 0 || n < 0) return fail(c, AGP_ERR_ARG, "negative size");
   if (P == 0) return AGP_OK;
-  if (!op_off || !ops || !prm_off || !prm || !noise || !out_lp || !out_info) return fail(c, AGP_ERR_ARG, "null pointer argument");
-  if (n > c->n_max) return fail(c, AGP_ERR_NODATA, "n exceeds the data uploaded with agp_set_data");
-  for (int p = 0; p < P; ++p)
-    if (op_off[p + 1] < op_off[p] || prm_off[p + 1] < prm_off[p] || op_off[p] < 0 || prm_off[p] < 0)
-      return fail(c, AGP_ERR_ARG, "offsets must be non-decreasing");
+  if (!pp.complete() || !out_lp || !out_info) return fail(c, AGP_ERR_ARG, "null pointer argument");
+  if (const int rc = check_resident(c, n)) return rc;
+  if (!offsets_sane(pp)) return fail(c, AGP_ERR_ARG, "offsets must be non-decreasing");
   if (n == 0) {
     for (int p = 0; p < P; ++p) { out_lp[p] = 0.0; out_info[p] = 0; }
     return AGP_OK;
   }
-  auto plain = [&]() { return agp_logpdf_batch(c, n, P, op_off, ops, prm_off, prm, noise, out_lp, out_info); };
+  auto plain = [&]() { return agp_logpdf_batch(c, n, P, pp.op_off, pp.ops, pp.prm_off, pp.prm, pp.noise, out_lp, out_info); };
   HIPCHK(c, hipSetDevice(c->device));
 
   // distinct particles (a resampled population holds copies; the offsets were checked above)
   HostProf hp_k(10);
-  std::vector<int> rep, uniq;
-  std::vector<std::string> keys;
-  (void)distinct_particles(P, op_off, ops, prm_off, prm, noise, nullptr, rep, uniq, &keys);
-  const int U = (int)uniq.size();
-  SubBatch S;
-  pack_particles(uniq, op_off, ops, prm_off, prm, noise, nullptr, S);
+  const Distinct D(pp, true, Distinct::Pack::always, /*want_keys=*/true);      // (whatever the context's dedup switch: the store is keyed)
+  const std::vector<int>& rep = D.rep;
+  const std::vector<std::string>& keys = D.keys;
+  const SubBatch& S = D.S;
+  const int U = D.U();
 
   const int n_pad = round_up(n, NB), nt = n_pad / NB;
   agp_ctx::FactorStore& fs = c->store;
@@ -274,9 +270,10 @@ int extend_impl(agp_ctx* c, int64_t n, int32_t P, const int32_t* op_off, const u
   // threads 3 171 -> 3 376; from three tile rows on fusing wins again (n = 300: 602 vs 563).  The rule reads the resident series
   // alone — not this sweep's prefix or population — so an extension and a from-scratch sweep of the entry keep one arithmetic.)
   const bool small_series = (c->n_max + NB - 1) / NB <= 2;
-  int rc = compile_batch(c, U, S.op_off.data(), S.ops.data(), S.prm_off.data(), S.prm.data(), bt, false, false, ge_tab, /*fuse_hint=*/true,
-                         /*flow_limit=*/c->flow != 0 && U <= FLOW_MAX_PARTICLES, rankm, rankm ? tab_units : 1, rank_extra,
-                         /*never_fuse=*/small_series);
+  CompileOpts co;
+  co.ge_tab = ge_tab; co.fuse_hint = true; co.flow_limit = c->flow != 0 && U <= FLOW_MAX_PARTICLES;
+  co.lag = rankm; co.lag_units = rankm ? tab_units : 1; co.rank_extra = rank_extra; co.never_fuse = small_series;
+  int rc = compile_batch(c, D.run(), bt, co);
   if (rc) { forget_touched(); return rc; }
   if (cltw) { std::lock_guard<std::mutex> g(c->mu); ++c->n_clt_sweeps; }
   int i0min = nt;
@@ -415,7 +412,7 @@ int extend_impl(agp_ctx* c, int64_t n, int32_t P, const int32_t* op_off, const u
     fs.key[sl] = keys[u]; fs.index[keys[u]] = sl; fs.n_cached[sl] = n; fs.info_h[sl] = hinfo[u];
     if (i0[u] == 0) {          // a fresh factor: nothing has started from it yet
       fs.used[(size_t)sl] = 0; fs.born[(size_t)sl] = call;
-      const uint64_t cid = tl_callers ? tl_callers[uniq[u]] : 0;
+      const uint64_t cid = tl_callers ? tl_callers[D.uniq[u]] : 0;
       fs.slot_caller[(size_t)sl] = cid;
       if (cid != 0) {
         auto pr = fs.caller_slot.find(cid);
@@ -428,7 +425,7 @@ int extend_impl(agp_ctx* c, int64_t n, int32_t P, const int32_t* op_off, const u
     if (i0[u] > 0) ++fs.hits; else ++fs.misses;
   }
   fs.tile_rows_reused += rows_reused; fs.tile_rows_total += (int64_t)U * nt;
-  for (int p = 0; p < P; ++p) { out_lp[p] = hl[rep[p]]; out_info[p] = hinfo[rep[p]]; }
+  D.scatter(hl, out_lp); D.scatter(hinfo, out_info);
   return AGP_OK;
 }
 
@@ -441,7 +438,7 @@ int agp_logpdf_batch_extend(agp_ctx* c, int64_t n, int32_t P, const int32_t* op_
                             int32_t* out_info) {
   // (reference arithmetic keeps nothing resident: the same call is a plain sweep)
   if (c && c->ref_arith) return agp_logpdf_batch(c, n, P, op_off, ops, prm_off, prm, noise, out_logpdf, out_info);
-  return abi_guard(c, [&] { return extend_impl(c, n, P, op_off, ops, prm_off, prm, noise, out_logpdf, out_info); });
+  return abi_guard(c, [&] { return extend_impl(c, n, {P, op_off, ops, prm_off, prm, noise, nullptr}, out_logpdf, out_info); });
 }
 
 int agp_set_reference_arithmetic(agp_ctx* c, int32_t on) {
