@@ -309,6 +309,41 @@ constexpr int FFT_N = 4096;                // transform length of the spectral v
 constexpr int LDS_TAPE_NODES = 8;
 constexpr int FFT_BUF = FFT_N + FFT_N / 16;
 
+// Small-matrix value kernel (k_series_logpdf, agp_series_kernel.hpp): one workgroup per particle, the particle's whole series in LDS.
+constexpr int SERIES_MAX_N = 176;                 // == AGP_SERIES_MAX_N of the C ABI (agp_series.hip checks)
+constexpr int SERIES_LDS_BYTES = 160 * 1024;      // what one workgroup may declare on gfx950
+struct SeriesArgs {
+  const double* ts;          // S series, concatenated: series s is [pt_off[s], pt_off[s + 1])
+  const double* xs;
+  const long long* pt_off;   // [S + 1]
+  const int32_t* series;     // [P] series of particle p
+  const int32_t* wg;         // [grid] particle of workgroup b of this launch (longest series first)
+  const ProgHdr* hdr;        // [P] programs compiled without tables of the resident series (no OP_GE_TAB, no OP_LAG)
+  const uint8_t* ops;
+  const double* prm;
+  const double* noise;       // [P]
+  double* out_lp;            // [P]
+  int32_t* out_info;         // [P]
+};
+// LDS map of one workgroup, in doubles, from the particle's own sizes alone (the launch declares the largest total of its particles;
+// where a workgroup's arrays sit never depends on what else is in the launch):
+//   Wl[256] | tpt[np] | rvec[np] | avec[np] | etab[128] | prm[n_prm + 2, even] | ops[n_ops ints, even] | sig[n_cp][256] | blocks
+// np = 16 nb points, nb = ceil(n / 16) block rows, nb (nb + 1) / 2 lower 16 x 16 blocks of 256 doubles.
+struct SeriesLds {
+  int nb, np, o_tpt, o_rvec, o_avec, o_etab, o_prm, o_ops, o_sig, o_blk, total;      // offsets and total in doubles
+};
+__host__ __device__ inline SeriesLds series_lds(int n, int n_ops, int n_prm, int n_cp) {
+  SeriesLds m;
+  m.nb = (n + BS - 1) / BS; m.np = m.nb * BS;
+  m.o_tpt = 256; m.o_rvec = m.o_tpt + m.np; m.o_avec = m.o_rvec + m.np; m.o_etab = m.o_avec + m.np;
+  m.o_prm = m.o_etab + 128;
+  m.o_ops = m.o_prm + ((n_prm + 3) & ~1);
+  m.o_sig = m.o_ops + (((n_ops + 1) / 2 + 1) & ~1);
+  m.o_blk = m.o_sig + n_cp * 256;
+  m.total = m.o_blk + (m.nb * (m.nb + 1) / 2) * 256;
+  return m;
+}
+
 // k_poison_rows (NaN-poison mode of the store's sweeps): per buffer b, slot u's doubles [row start(i0[u]), pitch) in slot[u]
 struct PoisonRowsArgs {
   double* base[4];

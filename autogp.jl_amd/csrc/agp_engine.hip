@@ -1658,6 +1658,7 @@ int agp_init(agp_ctx** out, int device_id) {
       // raise the dynamic-LDS ceiling of the table-carrying kernels once (launches then never touch function attributes)
       hipError_t ea = kernels_init();
       if (ea == hipSuccess) ea = kernels_init_grad();
+      if (ea == hipSuccess) ea = kernels_init_series();
       if (ea != hipSuccess) {
         std::string m = std::string("hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed: ") + hipGetErrorString(ea);
         return fail(nullptr, AGP_ERR_HIP, m);

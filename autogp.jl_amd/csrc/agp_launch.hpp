@@ -1,7 +1,8 @@
-// Host-side launch interface between the orchestration (agp_engine.hip) and the two kernel translation units:
-//   agp_kernels.hip       covariance evaluation + factorisation + the small service kernels
-//   agp_kernels_grad.hip  gradient sweep (L^-T chains, K^-1 tiles, spectra, contractions)
-// Every template instantiation lives behind one of these plain functions, so the three units compile in parallel and the
+// Host-side launch interface between the orchestration (agp_engine.hip) and the kernel translation units:
+//   agp_kernels.hip         covariance evaluation + factorisation + the small service kernels
+//   agp_kernels_grad.hip    gradient sweep (L^-T chains, K^-1 tiles, spectra, contractions)
+//   agp_kernels_series.hip  small-matrix value kernel (one workgroup per particle of a short series)
+// Every template instantiation lives behind one of these plain functions, so the units compile in parallel and the
 // function attributes (dynamic-LDS ceilings) are set on the copies that are actually launched.
 #pragma once
 #include "agp_args.hpp"
@@ -69,5 +70,11 @@ void launch_kinv_tiles(hipStream_t st, int grid, const GradArgs& ga);
 hipError_t launch_grad_contract(int maxs, hipStream_t st, const GradArgs& ga, int ntiles, int P, size_t lds);      // maxs: 64 / 16 / 0 (LDS tape)
 void launch_lag_grad(hipStream_t st, int P, size_t lds, const GradArgs& ga);
 void launch_grad_finish(hipStream_t st, int P, const GradArgs& ga);
+
+// ---- agp_kernels_series.hip ------------------------------------------------------------------------------------------
+hipError_t kernels_init_series();   // raises the dynamic-LDS ceiling of k_series_logpdf to the whole 160 KiB (once, agp_init)
+// small-matrix value kernel: one workgroup per entry of sa.wg (`grid` of them), evaluation-stack depth 4 / 8, lds_bytes = the largest
+// SeriesLds total of the launch's particles
+hipError_t launch_series_logpdf(hipStream_t st, const SeriesArgs& sa, int grid, int depth, size_t lds_bytes);
 
 }  // namespace agp

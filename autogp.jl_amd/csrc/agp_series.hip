@@ -1,0 +1,173 @@
+// agp_logpdf_series_batch: many SHORT series, each with its own particles, scored in one call by the small-matrix value kernel
+// (agp_series_kernel.hpp: one workgroup per particle, covariance + Cholesky + forward solve + value in LDS).  Stateless: the series
+// travel with the call; the resident series, its tables, the factor store, the coalescer and every counter of the context are
+// neither read nor changed — only a workspace slot (stream, staging buffers) is borrowed, as in every batch entry.
+#include "agp_host.hpp"
+
+static_assert(SERIES_MAX_N == AGP_SERIES_MAX_N, "the kernel's cap is the C ABI's");
+static_assert(AGP_SERIES_MAX_N >= 160, "the reference's 126-, 135-, 143- and 144-point series must fit");
+
+namespace {
+
+// LDS classes of the launches: a launch declares the largest need of its particles, so particles are grouped by how many workgroups
+// of their size share a CU's 160 KiB — 4 (n <= ~80), 2 (n <= ~128) or 1.
+int lds_class(size_t bytes) { return bytes <= (size_t)SERIES_LDS_BYTES / 4 ? 0 : bytes <= (size_t)SERIES_LDS_BYTES / 2 ? 1 : 2; }
+
+int series_batch(agp_ctx* c, int32_t S, const int64_t* pt_off, const double* ts, const double* xs, const Particles& pp,
+                 const int32_t* series, double* out_logpdf, int32_t* out_info) {
+  const int P = pp.P;
+  char buf[256];
+  if (!c) return fail(nullptr, AGP_ERR_ARG, "null context");
+  if (S < 0 || P < 0) return fail(c, AGP_ERR_ARG, "negative number of series or particles");
+  if (P == 0) return AGP_OK;
+  if (!pt_off || !ts || !xs || !series || !pp.complete() || !out_logpdf || !out_info) return fail(c, AGP_ERR_ARG, "null pointer argument");
+  if (S > 0 && pt_off[0] != 0) return fail(c, AGP_ERR_ARG, "pt_off[0] must be 0 (series 0)");
+  for (int32_t s = 0; s < S; ++s) {
+    if (pt_off[s + 1] < pt_off[s]) {
+      snprintf(buf, sizeof buf, "series %d: pt_off decreases (%lld after %lld)", (int)s, (long long)pt_off[s + 1], (long long)pt_off[s]);
+      return fail(c, AGP_ERR_ARG, buf);
+    }
+    if (pt_off[s + 1] - pt_off[s] > AGP_SERIES_MAX_N) {
+      snprintf(buf, sizeof buf, "series %d has %lld points, more than AGP_SERIES_MAX_N (%d)", (int)s, (long long)(pt_off[s + 1] - pt_off[s]),
+               AGP_SERIES_MAX_N);
+      return fail(c, AGP_ERR_ARG, buf);
+    }
+  }
+  for (int p = 0; p < P; ++p)
+    if (series[p] < 0 || series[p] >= S) {
+      snprintf(buf, sizeof buf, "particle %d: series index %d outside [0, %d)", p, (int)series[p], (int)S);
+      return fail(c, AGP_ERR_ARG, buf);
+    }
+  for (int p = 0; p < P; ++p)
+    if (pp.op_off[p] < 0 || pp.prm_off[p] < 0 || pp.op_off[p + 1] < pp.op_off[p] || pp.prm_off[p + 1] < pp.prm_off[p]) {
+      snprintf(buf, sizeof buf, "particle %d: malformed program / parameter offsets", p);
+      return fail(c, AGP_ERR_ARG, buf);
+    }
+  // programs without any table of the resident series (no log|dt| table, no lag tables), in the caller's order
+  Batch bt;
+  CompileOpts co;
+  co.ge_tab = false; co.lag = false; co.never_fuse = true;
+  if (const int rc = compile_batch(c, pp, bt, co)) return rc;
+
+  // per particle: length, LDS need; launch classes (depth 4 / 8) x (LDS class), longest series first inside each
+  std::vector<int> len((size_t)P);
+  std::vector<size_t> need((size_t)P);
+  std::vector<int32_t> list[2][3];
+  for (int p = 0; p < P; ++p) {
+    if (bt.order[(size_t)p] != p) return fail(c, AGP_ERR_HOST, "internal error: compiled batch out of order");
+    const ProgHdr& h = bt.hdr[(size_t)p];
+    const int n = (int)(pt_off[series[p] + 1] - pt_off[series[p]]);
+    len[(size_t)p] = n;
+    if (n == 0) continue;
+    const SeriesLds m = series_lds(n, h.n_ops, h.n_prm, h.n_cp);
+    need[(size_t)p] = sizeof(double) * (size_t)m.total;
+    if (need[(size_t)p] > (size_t)SERIES_LDS_BYTES) {
+      snprintf(buf, sizeof buf, "particle %d: %d per-point tables (ChangePoint nodes) at %d points need %zu bytes of LDS, more than the "
+               "kernel's %d", p, (int)h.n_cp, n, need[(size_t)p], SERIES_LDS_BYTES);
+      return fail(c, AGP_ERR_PROGRAM, buf);
+    }
+    // the evaluation stack this program needs (compile_batch reports the batch's largest only): from the compiled postfix form
+    int sp = 0, depth = 0;
+    for (int i = 0; i < h.n_ops; ++i) {
+      const int o = bt.ops[(size_t)h.op_off + i];
+      if (o == OP_PLUS || o == OP_TIMES || o == OP_CP || o == OP_CP_SWAP) --sp; else ++sp;
+      depth = std::max(depth, sp);
+    }
+    list[depth <= 4 ? 0 : 1][lds_class(need[(size_t)p])].push_back(p);
+  }
+  for (auto& ld : list)
+    for (auto& v : ld) std::stable_sort(v.begin(), v.end(), [&](int32_t x, int32_t y) { return len[(size_t)x] > len[(size_t)y]; });
+  std::vector<int32_t> wg;
+  wg.reserve((size_t)P);
+  for (auto& ld : list) for (auto& v : ld) wg.insert(wg.end(), v.begin(), v.end());
+  if (wg.empty()) {      // every particle scores an empty series (src/inference_smc_anneal_data.jl:185-187)
+    std::fill(out_logpdf, out_logpdf + P, 0.0); std::fill(out_info, out_info + P, 0);
+    return AGP_OK;
+  }
+
+  HIPCHK(c, hipSetDevice(c->device));
+  SlotGuard sg(c);
+  Slot* s = sg.s;
+  if (!s->stream) HIPCHK(c, hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
+  hipStream_t st = s->stream;
+  const size_t npts = (size_t)pt_off[S];
+  // device buffers of the slot: programs as in every sweep; tt = [ts | xs]; map = [pt_off (int64) | series | wg]
+  const size_t o_series = sizeof(long long) * ((size_t)S + 1), o_wg = o_series + sizeof(int32_t) * (size_t)P;
+  HIPCHK(c, s->hdr.ensure(sizeof(ProgHdr) * (size_t)P));
+  HIPCHK(c, s->ops.ensure(bt.ops.size() + 4));
+  HIPCHK(c, s->prm.ensure(sizeof(double) * std::max<size_t>(1, bt.prm.size())));
+  HIPCHK(c, s->noise.ensure(sizeof(double) * (size_t)P));
+  HIPCHK(c, s->tt.ensure(sizeof(double) * 2 * std::max<size_t>(1, npts)));
+  HIPCHK(c, s->map.ensure(o_wg + sizeof(int32_t) * wg.size()));
+  HIPCHK(c, s->out_lp.ensure(sizeof(double) * (size_t)P + sizeof(int32_t) * (size_t)P));
+  std::vector<long long> off64(pt_off, pt_off + S + 1);
+  PinnedUploads up;
+  up.add(s->hdr.p, bt.hdr.data(), sizeof(ProgHdr) * (size_t)P);
+  up.add(s->ops.p, bt.ops.data(), bt.ops.size());
+  up.add(s->prm.p, bt.prm.data(), sizeof(double) * bt.prm.size());
+  up.add(s->noise.p, pp.noise, sizeof(double) * (size_t)P);
+  up.add(s->tt.p, ts, sizeof(double) * npts);
+  up.add(s->tt.as<double>() + npts, xs, sizeof(double) * npts);
+  up.add(s->map.p, off64.data(), o_series);
+  up.add(s->map.as<char>() + o_series, series, sizeof(int32_t) * (size_t)P);
+  up.add(s->map.as<char>() + o_wg, wg.data(), sizeof(int32_t) * wg.size());
+  HIPCHK(c, up.flush(s->h_stage, s->up_blob, st));
+
+  SeriesArgs sa = {};
+  sa.ts = s->tt.as<double>(); sa.xs = s->tt.as<double>() + npts;
+  sa.pt_off = s->map.as<long long>();
+  sa.series = reinterpret_cast<const int32_t*>(s->map.as<char>() + o_series);
+  sa.hdr = s->hdr.as<ProgHdr>(); sa.ops = s->ops.as<uint8_t>(); sa.prm = s->prm.as<double>(); sa.noise = s->noise.as<double>();
+  sa.out_lp = s->out_lp.as<double>(); sa.out_info = reinterpret_cast<int32_t*>(s->out_lp.as<double>() + P);
+  const bool prof = c->profiling;
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  if (prof) {
+    while (s->events.size() < 2) { hipEvent_t e; HIPCHK(c, hipEventCreate(&e)); s->events.push_back(e); }
+    ev[0] = s->events[0]; ev[1] = s->events[1];
+    HIPCHK(c, hipEventRecord(ev[0], st));
+  }
+  size_t w0 = 0;
+  for (int d = 0; d < 2; ++d)
+    for (int k = 0; k < 3; ++k) {
+      const std::vector<int32_t>& v = list[d][k];
+      if (v.empty()) continue;
+      size_t lds = 0;
+      for (int32_t p : v) lds = std::max(lds, need[(size_t)p]);
+      sa.wg = reinterpret_cast<const int32_t*>(s->map.as<char>() + o_wg) + w0;
+      HIPCHK(c, launch_series_logpdf(st, sa, (int)v.size(), d == 0 ? 4 : 8, lds));
+      w0 += v.size();
+    }
+  if (prof) HIPCHK(c, hipEventRecord(ev[1], st));
+  const size_t out_bytes = sizeof(double) * (size_t)P + sizeof(int32_t) * (size_t)P;
+  HIPCHK(c, s->h_out.ensure(out_bytes));
+  HIPCHK(c, hipMemcpyAsync(s->h_out.p, s->out_lp.p, out_bytes, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  const double* hl = static_cast<const double*>(s->h_out.p);
+  const int32_t* hi = reinterpret_cast<const int32_t*>(hl + P);
+  for (int p = 0; p < P; ++p) {
+    const bool empty = len[(size_t)p] == 0;      // (never launched)
+    out_logpdf[p] = empty ? 0.0 : hl[p];
+    out_info[p] = empty ? 0 : hi[p];
+  }
+  if (prof) {
+    // agp_get_timing: out[0] = out[2] = the value kernels of the call (covariance, factorisation, solve and value are one kernel)
+    float ms = 0.f;
+    HIPCHK(c, hipEventElapsedTime(&ms, ev[0], ev[1]));
+    std::lock_guard<std::mutex> g(c->mu);
+    for (double& t : c->timing) t = 0.0;
+    c->timing[0] = ms; c->timing[2] = ms;
+  }
+  return AGP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int agp_logpdf_series_batch(agp_ctx* c, int32_t S, const int64_t* pt_off, const double* ts, const double* xs, int32_t P,
+                            const int32_t* series, const int32_t* op_off, const uint8_t* ops, const int32_t* prm_off, const double* prm,
+                            const double* noise, double* out_logpdf, int32_t* out_info) {
+  return abi_guard(c, [&] { return series_batch(c, S, pt_off, ts, xs, {P, op_off, ops, prm_off, prm, noise, nullptr}, series, out_logpdf, out_info); });
+}
+
+}  // extern "C"

@@ -36,9 +36,10 @@ EXPORTED_SYMBOLS = [
     "agp_mixture_quantile", "agp_predict_quantile_batch", "agp_infer_gp_sum_batch", "agp_predict_sum_batch",
     "agp_predict_sample_batch", "agp_mixture_moments", "agp_predict_mixture_batch", "agp_get_mixture_stats",
     "agp_remove_data", "agp_get_remove_stats", "agp_set_remove_update", "agp_remove_data_multi",
-    "agp_debug_factor_batch",
+    "agp_debug_factor_batch", "agp_logpdf_series_batch",
 ]
 COMM_ID_BYTES = 128
+SERIES_MAX_N = 176      # AGP_SERIES_MAX_N of include/autogp_hip.h: the longest series of logpdf_series_batch
 
 
 class AGPError(RuntimeError):
@@ -100,6 +101,8 @@ def load_library(path=None):
     lib.agp_logpdf.restype = C.c_int
     lib.agp_logpdf_batch.argtypes = [vp, C.c_int64, C.c_int32, ip, u8p, ip, dp, dp, dp, ip]
     lib.agp_logpdf_batch.restype = C.c_int
+    lib.agp_logpdf_series_batch.argtypes = [vp, C.c_int32, C.POINTER(C.c_int64), dp, dp, C.c_int32, ip, ip, u8p, ip, dp, dp, dp, ip]
+    lib.agp_logpdf_series_batch.restype = C.c_int
     lib.agp_logpdf_grad_batch.argtypes = [vp, C.c_int64, C.c_int32, ip, u8p, ip, dp, dp, dp, dp, dp, ip]
     lib.agp_logpdf_grad_batch.restype = C.c_int
     lib.agp_logpdf_grad.argtypes = [vp, C.c_int64, u8p, C.c_int32, dp, C.c_int32, C.c_double, dp, dp, dp, ip]
@@ -223,6 +226,26 @@ def _u8(a):
 
 def _f64(a):
     return np.ascontiguousarray(np.asarray(a, dtype=np.float64))
+
+
+def pack_series(series):
+    """Concatenate a sequence of (ts, xs) pairs for logpdf_series_batch: (pt_off int64[S+1], ts, xs), series s at
+    [pt_off[s], pt_off[s+1]).  Raises ValueError on unequal lengths, input that is not 1-D, or a series of more than SERIES_MAX_N
+    points; a series may be empty."""
+    pt_off = np.zeros(len(series) + 1, dtype=np.int64)
+    tss, xss = [], []
+    for s, (ts, xs) in enumerate(series):
+        ts, xs = _f64(ts), _f64(xs)
+        if ts.ndim != 1 or xs.ndim != 1:
+            raise ValueError(f"series {s}: ts and xs must be vectors")
+        if ts.shape != xs.shape:
+            raise ValueError(f"series {s}: ts and xs must have equal lengths ({ts.shape[0]} and {xs.shape[0]})")
+        if ts.shape[0] > SERIES_MAX_N:
+            raise ValueError(f"series {s} has {ts.shape[0]} points, more than SERIES_MAX_N ({SERIES_MAX_N})")
+        pt_off[s + 1] = pt_off[s] + ts.shape[0]
+        tss.append(ts); xss.append(xs)
+    cat = lambda parts: np.ascontiguousarray(np.concatenate(parts)) if parts else np.zeros(0)
+    return pt_off, cat(tss), cat(xss)
 
 
 def check_remove_indexes(indexes, n_max):
@@ -384,6 +407,31 @@ class GPEngine:
         out = np.empty(P, dtype=np.float64); info = np.empty(P, dtype=np.int32)
         self._check(self._lib.agp_logpdf_batch(self._ctx, n, P, _ip(op_off), _u8(ops), _ip(prm_off), _dp(prm),
                                                _dp(noises), _dp(out), _ip(info)))
+        if check and (info > 0).any():
+            p = int(np.argmax(info > 0))
+            raise PosDefException(int(info[p]), p)
+        return out, info
+
+    def logpdf_series_batch(self, series, nodes, noises, series_index, check=True, programs=None):
+        """agp_logpdf_series_batch: many short series (a sequence of (ts, xs) pairs of at most SERIES_MAX_N points each) scored in one
+        fused launch — particle p scores series[series_index[p]]: log N(xs_s; 0, K_p(ts_s) + noise_p I).  Needs no set_data and leaves
+        the resident series, the factor store and every counter alone.  Returns (logpdf[P], info[P])."""
+        pt_off, ts, xs = pack_series(series)
+        op_off, ops, prm_off, prm = programs if programs is not None else _gp.encode_batch(nodes)
+        P = op_off.shape[0] - 1
+        noises = _f64(noises)
+        if noises.shape != (P,):
+            raise ValueError("one noise per particle required")
+        sidx = np.ascontiguousarray(np.asarray(series_index, dtype=np.int32))
+        if sidx.shape != (P,):
+            raise ValueError("one series index per particle required")
+        out = np.empty(P, dtype=np.float64); info = np.empty(P, dtype=np.int32)
+        ts_arg = ts if ts.size else np.zeros(1)
+        xs_arg = xs if xs.size else np.zeros(1)
+        prm_arg = prm if prm.size else np.zeros(1)
+        self._check(self._lib.agp_logpdf_series_batch(self._ctx, pt_off.shape[0] - 1, pt_off.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                      _dp(ts_arg), _dp(xs_arg), P, _ip(sidx), _ip(op_off), _u8(ops), _ip(prm_off),
+                                                      _dp(prm_arg), _dp(noises), _dp(out), _ip(info)))
         if check and (info > 0).any():
             p = int(np.argmax(info > 0))
             raise PosDefException(int(info[p]), p)

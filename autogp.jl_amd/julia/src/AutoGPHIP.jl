@@ -193,6 +193,33 @@ function logpdf_batch(eng::Engine, nodes::Vector{<:GP.Node}, noises::Vector{Floa
     return out, info
 end
 
+"Longest series of `logpdf_series_batch` (AGP_SERIES_MAX_N)."
+const SERIES_MAX_N = 176
+
+"Many short series in one fused launch (agp_logpdf_series_batch): `series` is a vector of `(ts, xs)` pairs of at most
+`SERIES_MAX_N` points each, particle `p` scores `series[series_index[p]]` (1-based).  Needs no `set_data!` and leaves the
+resident series, the factor store and every counter alone.  Returns `(logpdf, info)`."
+function logpdf_series_batch(eng::Engine, series::Vector{<:Tuple{Vector{Float64},Vector{Float64}}}, nodes::Vector{<:GP.Node},
+                             noises::Vector{Float64}, series_index::Vector{<:Integer})
+    P = length(nodes)
+    (length(noises) == P && length(series_index) == P) || throw(ArgumentError("one noise and one series index per particle required"))
+    pt_off = Int64[0]; ts = Float64[]; xs = Float64[]
+    for (s, (t, x)) in enumerate(series)
+        length(t) == length(x) || throw(ArgumentError("series $s: ts and xs must have equal lengths"))
+        length(t) <= SERIES_MAX_N || throw(ArgumentError("series $s has $(length(t)) points, more than SERIES_MAX_N ($SERIES_MAX_N)"))
+        append!(ts, t); append!(xs, x); push!(pt_off, length(ts))
+    end
+    isempty(ts) && (push!(ts, 0.0); push!(xs, 0.0))
+    sidx = Int32[Int32(i - 1) for i in series_index]
+    op_off, ops, prm_off, prm = encode_batch(nodes)
+    out = Vector{Float64}(undef, P); info = Vector{Int32}(undef, P)
+    GC.@preserve pt_off ts xs sidx op_off ops prm_off prm noises out info check(eng, ccall((:agp_logpdf_series_batch, LIB), Cint,
+        (Ptr{Cvoid}, Int32, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Int32}, Ptr{Int32}, Ptr{UInt8}, Ptr{Int32}, Ptr{Float64},
+         Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
+        eng.ptr, length(series), pt_off, ts, xs, P, sidx, op_off, ops, prm_off, prm, noises, out, info))
+    return out, info
+end
+
 "(extended, from_scratch, tile_rows_reused, tile_rows_total, evicted_before_reuse, slots, callers, occupied, capacity_tile_rows, growth_copies) of the factor store"
 function extend_stats(eng::Engine)
     out = zeros(Int64, 10)

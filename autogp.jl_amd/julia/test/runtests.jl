@@ -72,6 +72,22 @@ kernels() = GP.Node[
         end
     end
 
+    @testset "many short series in one call (stateless)" begin
+        ks = kernels()
+        sers = [(ts[1:n], xs[1:n]) for n in (0, 1, 17, 144, H.SERIES_MAX_N)]
+        nodes = GP.Node[]; sidx = Int[]
+        for s in eachindex(sers), k in ks
+            push!(nodes, k); push!(sidx, s)
+        end
+        lp, info = H.logpdf_series_batch(eng, sers, nodes, fill(noise, length(nodes)), sidx)
+        @test all(info .== 0)
+        for (p, (k, s)) in enumerate(zip(nodes, sidx))
+            t, x = sers[s]
+            @test relerr(lp[p], isempty(t) ? 0.0 : ref_logpdf(k, noise, t, x)) <= 1e-8
+        end
+        @test eng.n_max == 700      # the resident series is untouched
+    end
+
     @testset "not positive definite" begin
         bad = GP.Linear(0.0, 0.0, -0.01)
         @test_throws LinearAlgebra.PosDefException H.logpdf(eng, bad, 0.1, 700)

@@ -97,6 +97,32 @@ int agp_logpdf_batch(agp_ctx* ctx, int64_t n, int32_t P,
                      const double* noise,
                      double* out_logpdf /* P */, int32_t* out_info /* P */);
 
+/* Many SHORT series scored in one call: one workgroup per particle, covariance, Cholesky factor, forward solve and value all in LDS
+ * (a 144-point series is two mostly padded 128 x 128 tile rows on the tiled path; here it is 45 blocks of 16 x 16 in one CU's LDS).
+ * S independent series, concatenated: series s is ts[pt_off[s] .. pt_off[s+1]), xs likewise (already rescaled).
+ * P particles; particle p scores series series[p]:
+ *   out_logpdf[p] = log N(xs_s; 0, K_p(ts_s) + noise[p] I).
+ * Same program encoding, noise meaning and per-particle info conventions as agp_logpdf_batch: out_info[p] = k > 0 is the 1-based index,
+ * within the particle's OWN series, of the first non-positive pivot, and out_logpdf[p] is then NaN; a series of length 0 gives
+ * logpdf 0 and info 0.  P == 0 is AGP_OK and touches nothing.
+ * AGP_SERIES_MAX_N: the LDS budget of one workgroup (160 KiB) holds ceil(n/16) (ceil(n/16) + 1) / 2 blocks of 2 KiB — 132 KiB at 176
+ * points — beside ~7 KiB of vectors, tables and program, which leaves room for 10 ChangePoint tables of 2 KiB at the cap.
+ * The WHOLE call is rejected — there is no fall-back through the resident-series path — with
+ *   AGP_ERR_ARG (the message names the series or particle): null pointers, negative S or P, pt_off[0] != 0, a decreasing pt_off,
+ *     series[p] outside [0, S), a series longer than AGP_SERIES_MAX_N, malformed op_off / prm_off;
+ *   AGP_ERR_PROGRAM (names the particle): a malformed program, as agp_logpdf_batch reports it, or one whose per-point tables
+ *     (ChangePoint nodes) do not fit the LDS budget at that series' length.
+ * Stateless: needs no agp_set_data; reads and changes nothing the context holds for its resident series — the series itself, the
+ * factor store and its statistics, lag / lattice / compact tables, the coalescer, dedup and mixture counters.  (With profiling on,
+ * agp_get_timing's out[0] = out[2] = the call's kernel time, the rest 0.)  Copies of a particle are NOT deduplicated.
+ * As re-entrant as agp_logpdf_batch (a private stream and workspace slot per call).  A particle's result bits depend only on its own
+ * series, program, parameters and noise — not on what else is in the call, its order, or how the call is split into launches. */
+#define AGP_SERIES_MAX_N 176
+int agp_logpdf_series_batch(agp_ctx* ctx, int32_t S, const int64_t* pt_off /* S+1 */, const double* ts, const double* xs,
+                            int32_t P, const int32_t* series /* P */,
+                            const int32_t* op_off, const uint8_t* ops, const int32_t* prm_off, const double* prm,
+                            const double* noise, double* out_logpdf /* P */, int32_t* out_info /* P */);
+
 /* agp_logpdf_batch with BLOCK-EXTENSION of resident factors.  The data-annealing loop re-scores
  * every particle on a longer prefix of the same series with unchanged kernel parameters — the reweight step
  * (src/inference_smc_anneal_data.jl:206-217), add_data! (src/api.jl:426-443), scripts/online.jl:200 — and the
