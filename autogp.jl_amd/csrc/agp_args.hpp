@@ -344,6 +344,19 @@ __host__ __device__ inline SeriesLds series_lds(int n, int n_ops, int n_prm, int
   return m;
 }
 
+// Arguments of the probe instantiation k_series_logpdf<D, true> (agp_debug_series_factor): caller matrices of ONE size take the place
+// of series, programs and noise; the LDS map is series_lds(n, 0, 0, 0); workgroup b factors matrix b.
+struct SeriesProbeArgs {
+  const double* K;           // [P][n][n] row-major; only the lower triangle is read
+  const double* y;           // [P][n] right-hand sides, or null (zeros)
+  int n;
+  double* out_blk;           // [P][nb (nb + 1) / 2][256] the packed blocks as the factorisation leaves them
+  double* out_alpha;         // [P][np] avec
+  double* out_part;          // [P][2] 2 sum log L_ii, alpha'alpha
+  double* out_lp;            // [P]
+  int32_t* out_info;         // [P]
+};
+
 // k_poison_rows (NaN-poison mode of the store's sweeps): per buffer b, slot u's doubles [row start(i0[u]), pitch) in slot[u]
 struct PoisonRowsArgs {
   double* base[4];

@@ -76,5 +76,7 @@ hipError_t kernels_init_series();   // raises the dynamic-LDS ceiling of k_serie
 // small-matrix value kernel: one workgroup per entry of sa.wg (`grid` of them), evaluation-stack depth 4 / 8, lds_bytes = the largest
 // SeriesLds total of the launch's particles
 hipError_t launch_series_logpdf(hipStream_t st, const SeriesArgs& sa, int grid, int depth, size_t lds_bytes);
+// its probe instantiation on caller matrices: workgroup b factors matrix b of `grid`, lds_bytes = series_lds(sa.n, 0, 0, 0).total doubles
+hipError_t launch_series_probe(hipStream_t st, const SeriesProbeArgs& sa, int grid, size_t lds_bytes);
 
 }  // namespace agp

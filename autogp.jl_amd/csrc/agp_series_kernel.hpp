@@ -18,6 +18,10 @@
 //      out_logpdf[p] = -(n log 2 pi + 2 sum log L_ii + alpha'alpha) / 2 (NaN on a bad pivot), out_info[p].
 // No HBM workspace per particle, no finish kernel.
 //
+// k_series_logpdf<4, true> is the probe (agp_debug_series_factor): stages 1-3 are a load of the caller's matrix and right-hand side
+// into the same LDS layout (series_lds(n, 0, 0, 0)), stages 4 and 5 are the statements below — the ones every production
+// instantiation runs — and the packed blocks, alpha and the two partials of the value are written to HBM at the end.
+//
 // LDS budget (SeriesLds, agp_args.hpp): nb (nb + 1) / 2 blocks of 2 KiB — 90 KiB at n = 144 (45 blocks), 132 KiB at n = 176 (66) —
 // + Wl 2 KiB (inverse of the current diagonal block) + ts, rvec, avec 3 x 8 np B (4.1 KiB at 176) + exponential table 1 KiB
 // + parameters and opcodes (a few hundred bytes for the trees the prior draws, 6.6 KiB for a 255-node tree) + 2 KiB per ChangePoint node.
@@ -28,6 +32,7 @@
 // A particle's bits depend on its own series, program, parameters and noise only: the LDS map is a function of the particle's own
 // sizes, no value crosses workgroups, and every reduction runs in a fixed order.
 #pragma once
+#include <type_traits>
 #include "agp_common.hpp"
 #include "agp_args.hpp"
 #include "agp_cov_kernel.hpp"
@@ -35,83 +40,112 @@
 
 namespace agp {
 
-template <int D>
-__global__ __launch_bounds__(256, 2) void k_series_logpdf(SeriesArgs a) {
+template <int D, bool PROBE = false>
+__global__ __launch_bounds__(256, 2) void k_series_logpdf(std::conditional_t<PROBE, SeriesProbeArgs, SeriesArgs> a) {
   constexpr int E = 4;
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const int tid = threadIdx.x, l = tid & 63, w = tid >> 6, l15 = l & 15, lq = l >> 4;
-  const int p = a.wg[blockIdx.x];
-  const int sidx = a.series[p];
-  const long long o0 = a.pt_off[sidx];
-  const int n = (int)(a.pt_off[sidx + 1] - o0);
+  int p, n;
+  long long o0 = 0;
+  if constexpr (PROBE) {
+    p = blockIdx.x;
+    n = a.n;
+  } else {
+    p = a.wg[blockIdx.x];
+    const int sidx = a.series[p];
+    o0 = a.pt_off[sidx];
+    n = (int)(a.pt_off[sidx + 1] - o0);
+  }
   if (n <= 0 || n > SERIES_MAX_N) {      // (the host answers empty series itself and refuses long ones: never launched)
     if (tid == 0) { a.out_lp[p] = 0.0; a.out_info[p] = 0; }
     return;
   }
-  const ProgHdr h = a.hdr[p];
+  const ProgHdr h = [&]() -> ProgHdr { if constexpr (PROBE) return ProgHdr{}; else return a.hdr[p]; }();
   const SeriesLds m = series_lds(n, h.n_ops, h.n_prm, h.n_cp);
   const int nb = m.nb, np = m.np;
   double* Wl = smem;
-  double* tpt = smem + m.o_tpt;
+  [[maybe_unused]] double* tpt = smem + m.o_tpt;      // (tpt, etab, prm, ops, sig: unused by the probe, whose map has none of them)
   double* rvec = smem + m.o_rvec;
   double* avec = smem + m.o_avec;
-  double* etab = smem + m.o_etab;
-  double* prm = smem + m.o_prm;
-  int* ops = reinterpret_cast<int*>(smem + m.o_ops);
-  double* sig = smem + m.o_sig;
+  [[maybe_unused]] double* etab = smem + m.o_etab;
+  [[maybe_unused]] double* prm = smem + m.o_prm;
+  [[maybe_unused]] int* ops = reinterpret_cast<int*>(smem + m.o_ops);
+  [[maybe_unused]] double* sig = smem + m.o_sig;
   double* sm = smem + m.o_blk;
 
-  // ---- 1. inputs ----
-  if (tid < np) {
-    tpt[tid] = a.ts[o0 + (tid < n ? tid : n - 1)];      // (padding points: a finite time; their entries are overwritten with identity)
-    rvec[tid] = tid < n ? a.xs[o0 + tid] : 0.0;
-    avec[tid] = 0.0;
-  }
-  if (AGP_EXP_TABLE && tid < AGP_EXP_TAB_N) etab[tid] = fm::c_exp_tab[tid];
-  for (int i = tid; i < h.n_prm + 2; i += 256) prm[i] = a.prm[h.prm_off + i];      // (the parameter buffer carries two doubles of tail padding)
-  for (int i = tid; i < h.n_ops; i += 256) ops[i] = (int)a.ops[h.op_off + i];
-  __syncthreads();
-
-  // ---- 2. per-point tables (cov_prologue's arithmetic) ----
-  if (h.n_cp > 0) {
+  if constexpr (PROBE) {
+    // ---- 1. - 3. replaced: the caller's right-hand side and the lower triangle of the caller's matrix, block layout as below ----
     if (tid < np) {
-      const double t = tpt[tid];
-      int q = 0, c = 0;
-      for (int ip = 0; ip < h.n_ops; ++ip) {
-        const int o = ops[ip];
-        if (o == OP_CP || o == OP_CP_SWAP) {
-          const double loc = prm[q], sc = prm[q + 1];
-          sig[c * 256 + tid] = 0.5 * (1.0 + tanh((loc - t) / sc));   // sigma_cp, src/GP.jl:481-483
-          ++c;
-        }
-        q += prm_count(o);
-      }
+      rvec[tid] = (tid < n && a.y != nullptr) ? a.y[(long long)p * n + tid] : 0.0;
+      avec[tid] = 0.0;
     }
-    __syncthreads();
-  }
-
-  // ---- 3. K + noise I, lower block triangle; one block per wave and pass, lane (i = l%16, q = l/16) <-> elements (i, q + 4 e) ----
-  {
-    const double noise = a.noise[p];
+    const double* Kp = a.K + (long long)p * n * n;
     const int nblk = nb * (nb + 1) / 2;
     for (int b = w; b < nblk; b += 4) {
       int rb = 0;
       while ((rb + 1) * (rb + 2) / 2 <= b) ++rb;
       const int cb = b - rb * (rb + 1) / 2;
-      double tr[E], tc[E], out[E], lt[E];
-      int ri[E], ci[E];
-#pragma unroll
-      for (int e = 0; e < E; ++e) {
-        ri[e] = rb * 16 + l15;
-        ci[e] = cb * 16 + lq + 4 * e;
-        tr[e] = tpt[ri[e]];
-        tc[e] = tpt[ci[e]];
-        lt[e] = 0.0;
-      }
-      eval_program<D, E, 0>(h, ops, prm, sig, tr, tc, ri, ci, lt, out, etab);
       double* blk = sm + blk_idx(rb, cb) * 256;
 #pragma unroll
-      for (int e = 0; e < E; ++e) blk[64 * e + l] = cov_finalize(out[e], ri[e], ci[e], n, np, 0, noise);
+      for (int e = 0; e < E; ++e) {
+        const int ri = rb * 16 + l15, ci = cb * 16 + lq + 4 * e;
+        const int hi = ri > ci ? ri : ci, lo = ri > ci ? ci : ri;      // (a diagonal block holds both triangles, as cov_finalize leaves it)
+        blk[64 * e + l] = hi < n ? Kp[(long long)hi * n + lo] : (ri == ci ? 1.0 : 0.0);
+      }
+    }
+  } else {
+    // ---- 1. inputs ----
+    if (tid < np) {
+      tpt[tid] = a.ts[o0 + (tid < n ? tid : n - 1)];      // (padding points: a finite time; their entries are overwritten with identity)
+      rvec[tid] = tid < n ? a.xs[o0 + tid] : 0.0;
+      avec[tid] = 0.0;
+    }
+    if (AGP_EXP_TABLE && tid < AGP_EXP_TAB_N) etab[tid] = fm::c_exp_tab[tid];
+    for (int i = tid; i < h.n_prm + 2; i += 256) prm[i] = a.prm[h.prm_off + i];      // (the parameter buffer carries two doubles of tail padding)
+    for (int i = tid; i < h.n_ops; i += 256) ops[i] = (int)a.ops[h.op_off + i];
+    __syncthreads();
+
+    // ---- 2. per-point tables (cov_prologue's arithmetic) ----
+    if (h.n_cp > 0) {
+      if (tid < np) {
+        const double t = tpt[tid];
+        int q = 0, c = 0;
+        for (int ip = 0; ip < h.n_ops; ++ip) {
+          const int o = ops[ip];
+          if (o == OP_CP || o == OP_CP_SWAP) {
+            const double loc = prm[q], sc = prm[q + 1];
+            sig[c * 256 + tid] = 0.5 * (1.0 + tanh((loc - t) / sc));   // sigma_cp, src/GP.jl:481-483
+            ++c;
+          }
+          q += prm_count(o);
+        }
+      }
+      __syncthreads();
+    }
+
+    // ---- 3. K + noise I, lower block triangle; one block per wave and pass, lane (i = l%16, q = l/16) <-> elements (i, q + 4 e) ----
+    {
+      const double noise = a.noise[p];
+      const int nblk = nb * (nb + 1) / 2;
+      for (int b = w; b < nblk; b += 4) {
+        int rb = 0;
+        while ((rb + 1) * (rb + 2) / 2 <= b) ++rb;
+        const int cb = b - rb * (rb + 1) / 2;
+        double tr[E], tc[E], out[E], lt[E];
+        int ri[E], ci[E];
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+          ri[e] = rb * 16 + l15;
+          ci[e] = cb * 16 + lq + 4 * e;
+          tr[e] = tpt[ri[e]];
+          tc[e] = tpt[ci[e]];
+          lt[e] = 0.0;
+        }
+        eval_program<D, E, 0>(h, ops, prm, sig, tr, tc, ri, ci, lt, out, etab);
+        double* blk = sm + blk_idx(rb, cb) * 256;
+#pragma unroll
+        for (int e = 0; e < E; ++e) blk[64 * e + l] = cov_finalize(out[e], ri[e], ci[e], n, np, 0, noise);
+      }
     }
   }
   __syncthreads();
@@ -341,7 +375,13 @@ __global__ __launch_bounds__(256, 2) void k_series_logpdf(SeriesArgs a) {
       const double lp = -0.5 * ((double)n * 1.8378770664093454835606594728112 + ld + ss);
       a.out_lp[p] = bad != 0 ? __builtin_nan("") : lp;
       a.out_info[p] = bad;
+      if constexpr (PROBE) { a.out_part[2 * p] = ld; a.out_part[2 * p + 1] = ss; }
     }
+  }
+  if constexpr (PROBE) {      // the factor as stages 4 and 5 left it: packed blocks (diagonal blocks: zero above the diagonal) and alpha
+    const int nel = nb * (nb + 1) / 2 * 256;
+    for (int i = tid; i < nel; i += 256) a.out_blk[(long long)p * nel + i] = sm[i];
+    if (tid < np) a.out_alpha[(long long)p * np + tid] = avec[tid];
   }
 }
 

@@ -36,7 +36,7 @@ EXPORTED_SYMBOLS = [
     "agp_mixture_quantile", "agp_predict_quantile_batch", "agp_infer_gp_sum_batch", "agp_predict_sum_batch",
     "agp_predict_sample_batch", "agp_mixture_moments", "agp_predict_mixture_batch", "agp_get_mixture_stats",
     "agp_remove_data", "agp_get_remove_stats", "agp_set_remove_update", "agp_remove_data_multi",
-    "agp_debug_factor_batch", "agp_logpdf_series_batch",
+    "agp_debug_factor_batch", "agp_logpdf_series_batch", "agp_debug_series_factor",
 ]
 COMM_ID_BYTES = 128
 SERIES_MAX_N = 176      # AGP_SERIES_MAX_N of include/autogp_hip.h: the longest series of logpdf_series_batch
@@ -138,6 +138,7 @@ def load_library(path=None):
     lib.agp_cov_matrix.restype = C.c_int
     lib.agp_debug_cholesky.argtypes = [vp, dp, C.c_int64, dp, ip]; lib.agp_debug_cholesky.restype = C.c_int
     lib.agp_debug_factor_batch.argtypes = [vp, dp, dp, C.c_int64, C.c_int32, C.c_int32, dp, dp, dp, ip]; lib.agp_debug_factor_batch.restype = C.c_int
+    lib.agp_debug_series_factor.argtypes = [vp, dp, dp, C.c_int64, C.c_int32, dp, dp, dp, dp, ip]; lib.agp_debug_series_factor.restype = C.c_int
     lib.agp_debug_mfma_probe.argtypes = [vp, dp, dp, dp]; lib.agp_debug_mfma_probe.restype = C.c_int
     lib.agp_debug_mfma_peak.argtypes = [vp, C.c_int32, C.c_int32, dp, dp]; lib.agp_debug_mfma_peak.restype = C.c_int
     lib.agp_debug_math.argtypes = [vp, C.c_int32, dp, dp, dp, C.c_int32]; lib.agp_debug_math.restype = C.c_int
@@ -866,6 +867,23 @@ class GPEngine:
                                                      _ip(info)))
         # (column-major blocks: the transpose of each block is the row-major lower factor)
         return np.ascontiguousarray(Lt.transpose(0, 2, 1)), beta, part, info
+
+    def debug_series_factor(self, K, y=None):
+        """Factor the matrices K (P, n, n), 1 <= n <= SERIES_MAX_N (lower triangles read), with the Cholesky of logpdf_series_batch's
+        kernel (agp_debug_series_factor: the kernel's probe instantiation — the production statements on caller matrices) ->
+        L (P, n, n) lower, alpha = L^-1 y (P, n), partial (P, 2) = [2 sum log L_ii, alpha'alpha], logpdf (P), info (P)."""
+        K = np.ascontiguousarray(K, dtype=np.float64)
+        if K.ndim != 3 or K.shape[1] != K.shape[2]:
+            raise ValueError("K must have shape (P, n, n)")
+        P, n = K.shape[0], K.shape[1]
+        if y is not None:
+            y = np.ascontiguousarray(y, dtype=np.float64)
+            if y.shape != (P, n):
+                raise ValueError("y must have shape (P, n)")
+        L = np.empty((P, n, n), dtype=np.float64); alpha = np.empty((P, n), dtype=np.float64)
+        part = np.empty((P, 2), dtype=np.float64); lp = np.empty(P, dtype=np.float64); info = np.zeros(P, dtype=np.int32)
+        self._check(self._lib.agp_debug_series_factor(self._ctx, _dp(K), _dp(y), n, P, _dp(L), _dp(alpha), _dp(part), _dp(lp), _ip(info)))
+        return L, alpha, part, lp, info
 
     def debug_mfma_probe(self, A, B):
         A = _f64(A).reshape(16, 4); B = _f64(B).reshape(4, 16); D = np.empty((16, 16))

@@ -713,6 +713,19 @@ int agp_debug_factor_batch(agp_ctx* ctx, const double* K /* P*n*n */, const doub
                            double* out_L /* P*n*n, lower */, double* out_beta /* P*n or NULL */,
                            double* out_partial /* P*2: logdet, beta'beta; or NULL */, int32_t* out_info /* P */);
 
+/* Factor P caller-supplied matrices of ONE size 1 <= n <= AGP_SERIES_MAX_N with the factorisation of agp_logpdf_series_batch's kernel:
+ * a second instantiation of that kernel loads matrix p (K: P blocks of n x n, row-major; only the lower triangle r >= c at
+ * K[r * n + c] is read) and y (P x n; NULL: zeros) into the LDS layout where the production instantiations evaluate the
+ * covariance (rows and columns past n: identity), then runs the SAME statements — blocked Cholesky in LDS, forward solve with one
+ * refinement step, log-det and quadratic form, first bad pivot — and hands back what they leave:
+ * out_L (P x n x n row-major, exact zeros above the diagonal), out_alpha (P x n) = L^-1 y, out_partial (P x 2) = 2 sum log L_ii and
+ * alpha'alpha, out_lp (P) = -(n log 2 pi + the two partials) / 2 (NaN where out_info != 0), out_info (P) LAPACK info per matrix.
+ * AGP_ERR_ARG: n < 1, n > AGP_SERIES_MAX_N, P < 1 or P > 65536, any null pointer but y.  Borrows a workspace slot like
+ * agp_logpdf_series_batch and reads or changes nothing else the context holds.  A failed matrix leaves the others untouched. */
+int agp_debug_series_factor(agp_ctx* ctx, const double* K /* P*n*n */, const double* y /* P*n or NULL */, int64_t n, int32_t P,
+                            double* out_L /* P*n*n */, double* out_alpha /* P*n */, double* out_partial /* P*2 */,
+                            double* out_lp /* P */, int32_t* out_info /* P */);
+
 /* Probe of the fp64 MFMA fragment layout: D = A(16x4) * B(4x16), row-major host arrays. */
 int agp_debug_mfma_probe(agp_ctx* ctx, const double* A, const double* B, double* D);
 

@@ -6,6 +6,7 @@ import pytest
 import scipy.linalg as sla
 
 import _factor_ref as R
+import _series_cases as S
 
 SIZES = (5, 16, 17, 129, 300)
 # pivots the GPU tests pin (tests/test_gpu_factor_probe.py): every 4 / 16 / 128 boundary of the diagonal tile's sub-steps
@@ -113,3 +114,26 @@ def test_indefinite_fails_at_the_first_negative_pivot(js):
 def test_zero_pivot(j):
     _, info = sla.lapack.dpotrf(R.zero_pivot(300, j), lower=1)
     assert info == j + 1
+
+
+# ---- what tests/test_gpu_series_probe.py takes for granted (sizes up to the short-series kernel's cap) ----
+@pytest.mark.parametrize("n", S.SIZES)
+def test_reference_factor_exists_at_every_series_probe_size(n):
+    """every member of the batch of nine has a longdouble factor (kappa_blk, the per-matrix cap, is computed from it); at n = 1
+    the cap is exactly 1: no explicit inverse excuses anything there"""
+    for name, K in R.batch_of_nine(n):
+        assert (K == K.T).all()
+        L = R.ref_chol(K)
+        kb = R.kappa_blk(L)
+        assert np.isfinite(kb) and kb >= 1.0, (name, n, kb)
+        if n == 1:
+            assert kb == 1.0, (name, kb)
+
+
+def test_series_info_probes_fail_at_the_stated_pivot():
+    for K, want, name in S.info_probes():
+        assert (K == K.T).all() and K.shape[0] <= S.N_CAP
+        with pytest.raises(ArithmeticError, match=rf"pivot {want - 1} is not positive"):
+            R.ref_chol(K)
+        _, info = sla.lapack.dpotrf(K, lower=1)
+        assert info == want, name

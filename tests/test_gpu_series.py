@@ -8,6 +8,7 @@ import threading
 import numpy as np
 import pytest
 
+import _series_cases as S
 from oracle import oracle as O
 from conftest import to_tuple
 
@@ -186,6 +187,48 @@ def test_non_positive_definite(pkg, engine):
     with pytest.raises(G.PosDefException) as ei:
         engine.logpdf_series_batch([(ts, xs), (ts, xs)], [good, bad], [0.1, -0.5], [0, 1], check=True)
     assert ei.value.particle == 1 and ei.value.info == first
+
+
+def test_info_at_every_sub_step_and_block(pkg, engine):
+    """info through the real entry at every 4-wide sub-step of block 0, on both sides of block boundaries and at the last point:
+    thirteen particles that stop being positive definite at a chosen point of one 176-point series, one call, a good particle among
+    them (CPU twin: tests/test_series_cpu.py::test_changepoint_particles_fail_at_the_chosen_point)"""
+    ts = S.CP_TS
+    xs = np.random.default_rng(31).standard_normal(ts.size)
+    good = pkg.SquaredExponential(0.3, 0.8)
+    nodes = [S.changepoint_particle(pkg, k) for k in S.CP_POINTS]
+    first = [S.first_bad_minor(O.compute_cov_matrix_vectorized(nd.to_tuple(), S.CP_NOISE, ts)) for nd in nodes]
+    assert first == [k + 1 for k in S.CP_POINTS]
+    at = 6                                                       # the good particle sits between the failing ones
+    nodes.insert(at, good)
+    noises = np.full(len(nodes), S.CP_NOISE); noises[at] = 0.1
+    lp, info = engine.logpdf_series_batch([(ts, xs)], nodes, noises, np.zeros(len(nodes), dtype=np.int32), check=False)
+    assert np.delete(info, at).tolist() == first, info
+    assert np.isnan(np.delete(lp, at)).all()
+    alone, info1 = engine.logpdf_series_batch([(ts, xs)], [good], [0.1], [0], check=False)
+    assert info[at] == 0 and info1[0] == 0 and bits(alone)[0] == bits(lp)[at]
+    assert close(lp[at], O.gp_logpdf(good.to_tuple(), 0.1, ts, xs))
+
+
+def test_parity_at_the_remaining_block_counts(pkg, engine):
+    """the lengths of ragged_case() end in 1, 2, 3, 8, 9 or 11 blocks of 16: here every other final block count (4, 5, 6, 7, 10), full
+    and ragged, against the oracle"""
+    lens = (49, 80, 81, 97, 112, 145, 161)
+    rng = np.random.default_rng(20261019)
+    series, nodes, noises, sidx = [], [], [], []
+    for s, n in enumerate(lens):
+        ts, xs = pkg.prior.synthetic_series(256, seed=200 + s, shuffle=True)
+        series.append((ts[:n].copy(), xs[:n].copy()))
+        nd, nz = pkg.prior.sample_particles(rng, 6, max_depth=3)
+        nodes += nd; noises += list(nz); sidx += [s] * 6
+    noises = np.array(noises); sidx = np.array(sidx, dtype=np.int32)
+    ref = np.array([O.gp_logpdf(nd.to_tuple(), float(nz), *series[s]) for nd, nz, s in zip(nodes, noises, sidx)])
+    assert len(nodes) == 42 and np.isfinite(ref).all()          # the oracle factorises every particle: none is skipped
+    lp, info = engine.logpdf_series_batch(series, nodes, noises, sidx, check=False)
+    err = np.abs(lp - ref) / np.maximum(1.0, np.abs(ref))
+    print("block-count parity: worst relative error", err.max(), "at particle", int(err.argmax()))
+    assert (info == 0).all()
+    assert close(lp, ref).all(), (int(err.argmax()), err.max())
 
 
 def raw_call(engine, pt_off, ts, xs, sidx, programs, noises):

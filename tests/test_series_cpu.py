@@ -7,6 +7,8 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+import _series_cases as S
+
 ROOT = Path(__file__).resolve().parent.parent
 
 
@@ -55,3 +57,31 @@ def test_pack_series_rejects_bad_input(pkg):
     with pytest.raises(ValueError, match="series 2"):
         pkg.pack_series([ok, ok, (np.zeros(n), np.zeros(n))])
     pkg.pack_series([(np.zeros(n - 1), np.zeros(n - 1))])
+
+
+def test_changepoint_particles_fail_at_the_chosen_point(pkg):
+    """CPU twin of tests/test_gpu_series.py::test_info_at_every_sub_step_and_block: on the oracle's matrix the first leading minor
+    that cannot be factored is k + 1"""
+    from oracle import oracle as O
+    assert pkg.SERIES_MAX_N == S.N_CAP == S.CP_TS.size
+    for k in S.CP_POINTS:
+        K = O.compute_cov_matrix_vectorized(S.changepoint_particle(pkg, k).to_tuple(), S.CP_NOISE, S.CP_TS)
+        d = np.diag(K)
+        assert np.allclose(d[:k], 0.5, atol=1e-12) and np.allclose(d[k:], -0.499, atol=1e-12)
+        assert np.abs(K[:k, k:]).max(initial=0.0) <= 1e-15
+        assert S.first_bad_minor(K) == k + 1, k
+
+
+def test_exact_particles_are_exact(pkg):
+    """the covariance of tests/test_gpu_series_probe.py::test_probe_is_the_production_code does not depend on the order of evaluation:
+    the oracle's float64 matrix equals the one computed in longdouble, entry for entry"""
+    from oracle import oracle as O
+    for n in (1, 17, 176):
+        ts, particles = S.exact_particles(pkg, n)
+        t = ts.astype(np.longdouble)
+        want = [np.full((n, n), 0.5, dtype=np.longdouble) + 0.5 * np.eye(n),
+                0.5 + 2.0 * np.outer(t - 0.25, t - 0.25) + 0.25 * np.eye(n)]
+        for (node, noise), W in zip(particles, want):
+            K = O.compute_cov_matrix_vectorized(node.to_tuple(), noise, ts)
+            assert (K.astype(np.longdouble) == W).all()
+            assert S.first_bad_minor(K) is None
