@@ -670,17 +670,23 @@ __device__ __forceinline__ void chol_tile(const CholArgs& a, const int p_, const
       }
       all_ready = __syncthreads_or(probe);
     }
-    // (Fetching the direct row operand TWO slabs ahead — 16 more VGPRs, still no spills — was measured: the 512-particle
-    // sub-diagonal launch went 1.560 -> 1.664 ms.  The loop is not waiting for its loads; more of them in flight only
-    // crowd the co-resident workgroup's.)
     // Two register sets X / Y take turns as "row fragments of the slab being multiplied" and "row fragments in flight" (the
     // slab loop is unrolled by two; nslab is a multiple of 8): no register copies at the slab boundary.
+    // "Is there a next slab" is a compile-time parameter of slab() and the tail of the loop is peeled.  As a run-time guard
+    // (`if (s + 1 < nslab)` around gload and around lstore) it made the compiler's wait-counter pass merge a "loads issued,
+    // stores skipped" path that never runs: the gfx950 code then carried s_waitcnt vmcnt(3) (2) (1) (0) in front of the four
+    // k-steps of every other slab, i.e. it waited for the eight loads issued a dozen instructions earlier — the prefetch was
+    // none in every second slab.  With the guard resolved at compile time those waits are vmcnt(11) .. (8): only the row
+    // fragments requested one slab earlier are waited for.  tools/check_isa.py (fresh_load_waits) keeps it that way.
+    // (Fetching the direct row operand TWO slabs ahead went 1.560 -> 1.664 ms per sub-diagonal launch, but that was measured
+    // with the conservative waits in place — NOTES_dead_ends.md.)
     d2 fx[NU], fy[NU], rb[NU];
     gload(0, fx, rb);
     lstore(0, fx, rb);
     __syncthreads();
-    auto slab = [&](const int s, const int buf, const d2 (&fr)[NU], d2 (&rn)[NU]) {
-      if (s + 1 < nslab) gload(s + 1, rn, rb);
+    auto slab = [&](const int s, const int buf, const d2 (&fr)[NU], d2 (&rn)[NU], auto last) {
+      constexpr bool LAST = decltype(last)::value;                    // no slab s + 1: nothing to fetch, nothing to stage
+      if constexpr (!LAST) gload(s + 1, rn, rb);
       const double* Bs = sm + buf * SLAB_DOUBLES;
       // waves inside their MFMA block outrank the co-resident workgroup's load/store/barrier phase
       mfma_prio_on();
@@ -705,14 +711,18 @@ __device__ __forceinline__ void chol_tile(const CholArgs& a, const int p_, const
 #pragma unroll
         for (int kk = 0; kk < KS; ++kk) rv = fma(-Bs[kk * LDS_STRIDE + tid], xs_[kk], rv);
       }
-      if (s + 1 < nslab) lstore(buf ^ 1, rn, rb);
+      if constexpr (!LAST) lstore(buf ^ 1, rn, rb);
       if (FLOW && !all_ready && tid == 0 && s + 2 < nslab && (s + 2) % SLABS_PER_TILE == 0) flow_ready(jfirst + (s + 2) / SLABS_PER_TILE);
       __syncthreads();
     };
-    for (int s = 0; s < nslab; s += 2) {
-      slab(s, 0, fx, fy);
-      slab(s + 1, 1, fy, fx);
+    constexpr std::false_type more{};
+    int s = 0;
+    for (; s + 2 < nslab; s += 2) {
+      slab(s, 0, fx, fy, more);
+      slab(s + 1, 1, fy, fx, more);
     }
+    slab(s, 0, fx, fy, more);                      // s == nslab - 2 (nslab is even)
+    slab(s + 1, 1, fy, fx, std::true_type{});
   }
 
   if (FLOW) AGP_PROBE(1);
@@ -1150,13 +1160,21 @@ __device__ __forceinline__ void chol_diag_tile(const CholArgs& a, const int p_, 
   }
 
   if (FLOW) AGP_PROBE(1);
+  // FLOW: what follows the K-loop takes its lane-dependent indices from a second opaque copy of the lane index (see k_chol_flow).
+  // Derived from `tid` they are live across the K-loop, which has no register to spare: k_chol_flow<8,1> spilled lq and
+  // reloaded it at the end of every slab pair, and the s_waitcnt vmcnt(0) guarding that reload in the next MFMA block also
+  // drained the eight slab loads issued just before the block.
+  int te = tid;
+  if constexpr (FLOW) asm volatile("" : "+v"(te));
+  const int l15e = te & 15, lqe = (te & 63) >> 4;
+  const int row0e = 16 * (te >> 6) + l15e, row1e = 16 * (NSB - 1 - (te >> 6)) + l15e;
   if (prebuilt) {
     // resident tile: bring the accumulators to the -C representation
 #pragma unroll
     for (int e = 0; e < NE; ++e) {
-      const int rw = st1[e] ? row1 : row0;
+      const int rw = st1[e] ? row1e : row0e;
 #pragma unroll
-      for (int r = 0; r < 4; ++r) acc[e][r] -= Tt[(cbe[e] * 16 + 4 * r + lq) * NB + rw];
+      for (int r = 0; r < 4; ++r) acc[e][r] -= Tt[(cbe[e] * 16 + 4 * r + lqe) * NB + rw];
       __builtin_amdgcn_sched_barrier(0);
     }
   }
@@ -1167,11 +1185,11 @@ __device__ __forceinline__ void chol_diag_tile(const CholArgs& a, const int p_, 
     const int rbk = st1[e] ? NSB - 1 - wu : wu;           // 16-row block of this entry's rows
     double* blk = sm + blk_idx(rbk, cbe[e]) * 256;
 #pragma unroll
-    for (int r = 0; r < 4; ++r) blk[(4 * r + lq) * 16 + l15] = -acc[e][r];
+    for (int r = 0; r < 4; ++r) blk[(4 * r + lqe) * 16 + l15e] = -acc[e][r];
   }
   if (FLOW) AGP_PROBE(2);
   AGP_DPROBE(1);
-  factor_diag_tile<true>(a, ps, tk, Tt, vecp, sm, rvec, avec, Wl, rv, tid, (FLOW && AGP_TRACE(a) && wait_acc) ? &wait_acc->ph[3] : nullptr);
+  factor_diag_tile<true>(a, ps, tk, Tt, vecp, sm, rvec, avec, Wl, rv, te, (FLOW && AGP_TRACE(a) && wait_acc) ? &wait_acc->ph[3] : nullptr);
 }
 
 template <int DCOV, int GM>

@@ -55,8 +55,11 @@ __device__ __forceinline__ void gemm_slabs(d4 (&acc)[NSB][2], int nslab, const d
   gload(0, fx);
   lstore(0);
   __syncthreads();
-  auto slab = [&](const int s, const int buf, const d2 (&fr)[4], d2 (&rn)[4]) {
-    if (s + 1 < nslab) gload(s + 1, rn);
+  // "is there a next slab" is a compile-time parameter and the tail is peeled (see chol_tile: a run-time guard around
+  // gload / lstore makes the MFMA block wait for the loads just issued)
+  auto slab = [&](const int s, const int buf, const d2 (&fr)[4], d2 (&rn)[4], auto last) {
+    constexpr bool LAST = decltype(last)::value;
+    if constexpr (!LAST) gload(s + 1, rn);
     const double* Bs = sm + buf * U_SLAB;
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
@@ -72,13 +75,18 @@ __device__ __forceinline__ void gemm_slabs(d4 (&acc)[NSB][2], int nslab, const d
       }
     }
     __builtin_amdgcn_s_setprio(0);
-    if (s + 1 < nslab) lstore(buf ^ 1);
+    if constexpr (!LAST) lstore(buf ^ 1);
     __syncthreads();
   };
-  for (int s = 0; s < nslab; s += 2) {
-    slab(s, 0, fx, fy);
-    slab(s + 1, 1, fy, fx);
+  // nslab is even and at least 8 at both call sites (whole 128-column tiles, 8 slabs each)
+  constexpr std::false_type more{};
+  int s = 0;
+  for (; s + 2 < nslab; s += 2) {
+    slab(s, 0, fx, fy, more);
+    slab(s + 1, 1, fy, fx, more);
   }
+  slab(s, 0, fx, fy, more);                        // s == nslab - 2
+  slab(s + 1, 1, fy, fx, std::true_type{});
 }
 
 // Stage +L(k,k) strictly-lower 16x16 blocks and -W blocks in LDS (A-operand order) and solve
