@@ -344,6 +344,41 @@ __host__ __device__ inline SeriesLds series_lds(int n, int n_ops, int n_prm, int
   return m;
 }
 
+// Value-and-gradient twin (k_series_logpdf_grad, agp_logpdf_grad_series_batch): the value kernel's arguments, the particles' gradient
+// programs (compile_batch's tables, caller's order) and the gradient outputs.
+struct SeriesGradArgs : SeriesArgs {
+  const GProgHdr* ghdr;      // [P]
+  const uint8_t* gops;       // opcode / left child / right child per node
+  const uint8_t* glc;
+  const uint8_t* grc;
+  const int32_t* gpoff;      // per node: offset of its parameters inside the particle's parameter block
+  const double* gprm;        // original parameter values, node order (three doubles of tail padding)
+  const int32_t* gmap;       // per parameter slot -> index in the caller's parameter block of the particle
+  const int32_t* out_off;    // [P] offset of the particle's block in out_grad (the caller's prm_off)
+  double* out_grad;          // [prm_off[P]]
+  double* out_gnoise;        // [P]
+};
+// LDS map of the gradient kernel: the value kernel's arrays at the value map's offsets up to the per-point tables, then — in front
+// of the blocks —
+//   csig[n_cp][256] (1 - sigma of every ChangePoint node, directly behind sig) | alpha[np] | gprm[g_n_prm + 3, even] | gpoff[g_n_ops ints] ops, lc, rc, mv[g_n_ops bytes each] (g_n_ops doubles, even) |
+//   red[4][g_n_prm + 1] (even) | blocks
+// i.e. 256 n_cp + np + 5 g_n_prm + g_n_ops + ~8 doubles more than series_lds: 2.1 KiB at 176 points beside a tree of 5 nodes and 9
+// parameters, and 2 KiB more per ChangePoint node.
+struct SeriesGradLds : SeriesLds {
+  int o_alpha, o_gprm, o_gtab, o_red;
+};
+__host__ __device__ inline SeriesGradLds series_grad_lds(int n, int n_ops, int n_prm, int n_cp, int g_n_ops, int g_n_prm) {
+  SeriesGradLds m;
+  static_cast<SeriesLds&>(m) = series_lds(n, n_ops, n_prm, n_cp);
+  m.o_alpha = m.o_blk + n_cp * 256;      // (csig sits at the value map's o_blk = o_sig + n_cp * 256)
+  m.o_gprm = m.o_alpha + m.np;
+  m.o_gtab = m.o_gprm + ((g_n_prm + 4) & ~1);
+  m.o_red = m.o_gtab + ((g_n_ops + 1) & ~1);
+  m.o_blk = m.o_red + ((4 * (g_n_prm + 1) + 1) & ~1);
+  m.total = m.o_blk + (m.nb * (m.nb + 1) / 2) * 256;
+  return m;
+}
+
 // Arguments of the probe instantiation k_series_logpdf<D, true> (agp_debug_series_factor): caller matrices of ONE size take the place
 // of series, programs and noise; the LDS map is series_lds(n, 0, 0, 0); workgroup b factors matrix b.
 struct SeriesProbeArgs {

@@ -1,4 +1,4 @@
-// Kernel translation unit 3: the small-matrix value kernel (agp_series_kernel.hpp), behind agp_launch.hpp.
+// Kernel translation unit 3: the small-matrix value kernel and its value-and-gradient twin (agp_series_kernel.hpp), behind agp_launch.hpp.
 #include "agp_launch.hpp"
 #include "agp_series_kernel.hpp"
 
@@ -6,7 +6,9 @@ namespace agp {
 
 hipError_t kernels_init_series() {
   const void* fns[] = {reinterpret_cast<const void*>(&k_series_logpdf<4>), reinterpret_cast<const void*>(&k_series_logpdf<8>),
-                       reinterpret_cast<const void*>(&k_series_logpdf<4, true>)};
+                       reinterpret_cast<const void*>(&k_series_logpdf<4, true>),
+                       reinterpret_cast<const void*>(&k_series_logpdf_grad<4, 16>), reinterpret_cast<const void*>(&k_series_logpdf_grad<4, 64>),
+                       reinterpret_cast<const void*>(&k_series_logpdf_grad<8, 64>)};
   for (const void* f : fns) {
     hipFuncAttributes fa;
     hipError_t e = hipFuncGetAttributes(&fa, f);
@@ -21,6 +23,15 @@ hipError_t launch_series_logpdf(hipStream_t st, const SeriesArgs& sa, int grid, 
   if (lds_bytes > (size_t)SERIES_LDS_BYTES) return hipErrorInvalidValue;
   if (depth <= 4) hipLaunchKernelGGL(k_series_logpdf<4>, dim3(grid), dim3(256), lds_bytes, st, sa);
   else hipLaunchKernelGGL(k_series_logpdf<8>, dim3(grid), dim3(256), lds_bytes, st, sa);
+  return hipGetLastError();
+}
+
+hipError_t launch_series_logpdf_grad(hipStream_t st, const SeriesGradArgs& sa, int grid, int depth, int tape, size_t lds_bytes) {
+  if (grid <= 0) return hipSuccess;
+  if (lds_bytes > (size_t)SERIES_LDS_BYTES || tape > 64 || (depth > 4 && tape <= 16)) return hipErrorInvalidValue;
+  if (tape <= 16) hipLaunchKernelGGL((k_series_logpdf_grad<4, 16>), dim3(grid), dim3(256), lds_bytes, st, sa);
+  else if (depth <= 4) hipLaunchKernelGGL((k_series_logpdf_grad<4, 64>), dim3(grid), dim3(256), lds_bytes, st, sa);
+  else hipLaunchKernelGGL((k_series_logpdf_grad<8, 64>), dim3(grid), dim3(256), lds_bytes, st, sa);
   return hipGetLastError();
 }
 

@@ -1,7 +1,7 @@
 // Host-side launch interface between the orchestration (agp_engine.hip) and the kernel translation units:
 //   agp_kernels.hip         covariance evaluation + factorisation + the small service kernels
 //   agp_kernels_grad.hip    gradient sweep (L^-T chains, K^-1 tiles, spectra, contractions)
-//   agp_kernels_series.hip  small-matrix value kernel (one workgroup per particle of a short series)
+//   agp_kernels_series.hip  small-matrix value kernel and its value-and-gradient twin (one workgroup per particle of a short series)
 // Every template instantiation lives behind one of these plain functions, so the units compile in parallel and the
 // function attributes (dynamic-LDS ceilings) are set on the copies that are actually launched.
 #pragma once
@@ -72,10 +72,13 @@ void launch_lag_grad(hipStream_t st, int P, size_t lds, const GradArgs& ga);
 void launch_grad_finish(hipStream_t st, int P, const GradArgs& ga);
 
 // ---- agp_kernels_series.hip ------------------------------------------------------------------------------------------
-hipError_t kernels_init_series();   // raises the dynamic-LDS ceiling of k_series_logpdf to the whole 160 KiB (once, agp_init)
+hipError_t kernels_init_series();   // raises the dynamic-LDS ceiling of k_series_logpdf / k_series_logpdf_grad to the whole 160 KiB (once, agp_init)
 // small-matrix value kernel: one workgroup per entry of sa.wg (`grid` of them), evaluation-stack depth 4 / 8, lds_bytes = the largest
 // SeriesLds total of the launch's particles
 hipError_t launch_series_logpdf(hipStream_t st, const SeriesArgs& sa, int grid, int depth, size_t lds_bytes);
+// value-and-gradient twin: tape = nodes of the reverse-mode tape (16 / 64); the evaluation-stack depth is the value kernel's for the same
+// program (a tree of <= 16 nodes never needs more than 4), lds_bytes = the largest SeriesGradLds total of the launch's particles
+hipError_t launch_series_logpdf_grad(hipStream_t st, const SeriesGradArgs& sa, int grid, int depth, int tape, size_t lds_bytes);
 // its probe instantiation on caller matrices: workgroup b factors matrix b of `grid`, lds_bytes = series_lds(sa.n, 0, 0, 0).total doubles
 hipError_t launch_series_probe(hipStream_t st, const SeriesProbeArgs& sa, int grid, size_t lds_bytes);
 

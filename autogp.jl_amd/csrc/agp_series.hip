@@ -1,5 +1,8 @@
 // agp_logpdf_series_batch: many SHORT series, each with its own particles, scored in one call by the small-matrix value kernel
-// (agp_series_kernel.hpp: one workgroup per particle, covariance + Cholesky + forward solve + value in LDS).  Stateless: the series
+// (agp_series_kernel.hpp: one workgroup per particle, covariance + Cholesky + forward solve + value in LDS), and
+// agp_logpdf_grad_series_batch, its value-and-gradient twin (k_series_logpdf_grad: L^-T, alpha and the contraction with dK / d theta
+// behind the value, same workgroup, same LDS).  Both are one host function — validation, series upload, launch classes and the
+// value outputs are the same statements — with the gradient as an option.  Stateless: the series
 // travel with the call; the resident series, its tables, the factor store, the coalescer and every counter of the context are
 // neither read nor changed — only a workspace slot (stream, staging buffers) is borrowed, as in every batch entry.
 #include "agp_host.hpp"
@@ -13,14 +16,18 @@ namespace {
 // of their size share a CU's 160 KiB — 4 (n <= ~80), 2 (n <= ~128) or 1.
 int lds_class(size_t bytes) { return bytes <= (size_t)SERIES_LDS_BYTES / 4 ? 0 : bytes <= (size_t)SERIES_LDS_BYTES / 2 ? 1 : 2; }
 
+// go = null: values only.  go: also out_grad (agp_logpdf_grad_batch's layout) and out_gnoise.
 int series_batch(agp_ctx* c, int32_t S, const int64_t* pt_off, const double* ts, const double* xs, const Particles& pp,
-                 const int32_t* series, double* out_logpdf, int32_t* out_info) {
+                 const int32_t* series, double* out_logpdf, int32_t* out_info, const GradOut* go = nullptr) {
   const int P = pp.P;
   char buf[256];
   if (!c) return fail(nullptr, AGP_ERR_ARG, "null context");
   if (S < 0 || P < 0) return fail(c, AGP_ERR_ARG, "negative number of series or particles");
   if (P == 0) return AGP_OK;
   if (!pt_off || !ts || !xs || !series || !pp.complete() || !out_logpdf || !out_info) return fail(c, AGP_ERR_ARG, "null pointer argument");
+  const size_t n_prm_total = go ? (size_t)std::max(0, pp.prm_off[P]) : 0;
+  if (go && !go->gnoise) return fail(c, AGP_ERR_ARG, "null pointer argument (out_grad_noise)");
+  if (go && !go->grad && pp.prm_off[P] > 0) return fail(c, AGP_ERR_ARG, "null pointer argument (out_grad with parameters present)");
   if (S > 0 && pt_off[0] != 0) return fail(c, AGP_ERR_ARG, "pt_off[0] must be 0 (series 0)");
   for (int32_t s = 0; s < S; ++s) {
     if (pt_off[s + 1] < pt_off[s]) {
@@ -46,21 +53,30 @@ int series_batch(agp_ctx* c, int32_t S, const int64_t* pt_off, const double* ts,
   // programs without any table of the resident series (no log|dt| table, no lag tables), in the caller's order
   Batch bt;
   CompileOpts co;
-  co.ge_tab = false; co.lag = false; co.never_fuse = true;
+  co.ge_tab = false; co.lag = false; co.never_fuse = true; co.want_grad = go != nullptr;
   if (const int rc = compile_batch(c, pp, bt, co)) return rc;
+  if (go)
+    for (int p = 0; p < P; ++p)
+      if (bt.ghdr[(size_t)p].n_ops > 64) {      // (RegTape<64> is the largest tape: agp_logpdf_grad_batch's own limit)
+        snprintf(buf, sizeof buf, "particle %d: gradient supports kernel trees of up to 64 nodes (%d)", p, (int)bt.ghdr[(size_t)p].n_ops);
+        return fail(c, AGP_ERR_PROGRAM, buf);
+      }
 
-  // per particle: length, LDS need; launch classes (depth 4 / 8) x (LDS class), longest series first inside each
+  // per particle: length, LDS need; launch classes (kernel instantiation) x (LDS class), longest series first inside each.
+  // Instantiations: values — evaluation-stack depth 4 / 8; gradient — tape of 16 / 64 nodes, the 64-node tape with the depth the value
+  // entry picks for the same program (<= 16 nodes never need more than 4), so that the value's bits are that entry's
   std::vector<int> len((size_t)P);
   std::vector<size_t> need((size_t)P);
-  std::vector<int32_t> list[2][3];
+  std::vector<int32_t> list[3][3];
   for (int p = 0; p < P; ++p) {
     if (bt.order[(size_t)p] != p) return fail(c, AGP_ERR_HOST, "internal error: compiled batch out of order");
     const ProgHdr& h = bt.hdr[(size_t)p];
     const int n = (int)(pt_off[series[p] + 1] - pt_off[series[p]]);
     len[(size_t)p] = n;
     if (n == 0) continue;
-    const SeriesLds m = series_lds(n, h.n_ops, h.n_prm, h.n_cp);
-    need[(size_t)p] = sizeof(double) * (size_t)m.total;
+    const int m_total = go ? series_grad_lds(n, h.n_ops, h.n_prm, h.n_cp, bt.ghdr[(size_t)p].n_ops, bt.ghdr[(size_t)p].n_prm).total
+                           : series_lds(n, h.n_ops, h.n_prm, h.n_cp).total;
+    need[(size_t)p] = sizeof(double) * (size_t)m_total;
     if (need[(size_t)p] > (size_t)SERIES_LDS_BYTES) {
       snprintf(buf, sizeof buf, "particle %d: %d per-point tables (ChangePoint nodes) at %d points need %zu bytes of LDS, more than the "
                "kernel's %d", p, (int)h.n_cp, n, need[(size_t)p], SERIES_LDS_BYTES);
@@ -73,7 +89,8 @@ int series_batch(agp_ctx* c, int32_t S, const int64_t* pt_off, const double* ts,
       if (o == OP_PLUS || o == OP_TIMES || o == OP_CP || o == OP_CP_SWAP) --sp; else ++sp;
       depth = std::max(depth, sp);
     }
-    list[depth <= 4 ? 0 : 1][lds_class(need[(size_t)p])].push_back(p);
+    const int inst = !go ? (depth <= 4 ? 0 : 1) : bt.ghdr[(size_t)p].n_ops <= 16 && depth <= 4 ? 0 : depth <= 4 ? 1 : 2;
+    list[inst][lds_class(need[(size_t)p])].push_back(p);
   }
   for (auto& ld : list)
     for (auto& v : ld) std::stable_sort(v.begin(), v.end(), [&](int32_t x, int32_t y) { return len[(size_t)x] > len[(size_t)y]; });
@@ -82,6 +99,7 @@ int series_batch(agp_ctx* c, int32_t S, const int64_t* pt_off, const double* ts,
   for (auto& ld : list) for (auto& v : ld) wg.insert(wg.end(), v.begin(), v.end());
   if (wg.empty()) {      // every particle scores an empty series (src/inference_smc_anneal_data.jl:185-187)
     std::fill(out_logpdf, out_logpdf + P, 0.0); std::fill(out_info, out_info + P, 0);
+    if (go) { std::fill(go->gnoise, go->gnoise + P, 0.0); std::fill(go->grad, go->grad + n_prm_total, 0.0); }
     return AGP_OK;
   }
 
@@ -100,6 +118,18 @@ int series_batch(agp_ctx* c, int32_t S, const int64_t* pt_off, const double* ts,
   HIPCHK(c, s->tt.ensure(sizeof(double) * 2 * std::max<size_t>(1, npts)));
   HIPCHK(c, s->map.ensure(o_wg + sizeof(int32_t) * wg.size()));
   HIPCHK(c, s->out_lp.ensure(sizeof(double) * (size_t)P + sizeof(int32_t) * (size_t)P));
+  if (go) {
+    HIPCHK(c, s->ghdr.ensure(sizeof(GProgHdr) * (size_t)P));
+    HIPCHK(c, s->gops.ensure(bt.gops.size() + 4));
+    HIPCHK(c, s->glc.ensure(bt.glc.size() + 4));
+    HIPCHK(c, s->grc.ensure(bt.grc.size() + 4));
+    HIPCHK(c, s->gpoff.ensure(sizeof(int32_t) * (bt.gpoff.size() + 1)));
+    HIPCHK(c, s->gprm.ensure(sizeof(double) * bt.gprm.size()));
+    HIPCHK(c, s->gmap.ensure(sizeof(int32_t) * (bt.gmap.size() + 1)));
+    HIPCHK(c, s->goff.ensure(sizeof(int32_t) * (size_t)P));
+    HIPCHK(c, s->dgrad.ensure(sizeof(double) * std::max<size_t>(1, n_prm_total)));
+    HIPCHK(c, s->dgnoise.ensure(sizeof(double) * (size_t)P));
+  }
   std::vector<long long> off64(pt_off, pt_off + S + 1);
   PinnedUploads up;
   up.add(s->hdr.p, bt.hdr.data(), sizeof(ProgHdr) * (size_t)P);
@@ -111,9 +141,24 @@ int series_batch(agp_ctx* c, int32_t S, const int64_t* pt_off, const double* ts,
   up.add(s->map.p, off64.data(), o_series);
   up.add(s->map.as<char>() + o_series, series, sizeof(int32_t) * (size_t)P);
   up.add(s->map.as<char>() + o_wg, wg.data(), sizeof(int32_t) * wg.size());
+  if (go) {
+    up.add(s->ghdr.p, bt.ghdr.data(), sizeof(GProgHdr) * (size_t)P);
+    up.add(s->gops.p, bt.gops.data(), bt.gops.size());
+    up.add(s->glc.p, bt.glc.data(), bt.glc.size());
+    up.add(s->grc.p, bt.grc.data(), bt.grc.size());
+    up.add(s->gpoff.p, bt.gpoff.data(), sizeof(int32_t) * bt.gpoff.size());
+    up.add(s->gprm.p, bt.gprm.data(), sizeof(double) * bt.gprm.size());
+    up.add(s->gmap.p, bt.gmap.data(), sizeof(int32_t) * bt.gmap.size());
+    up.add(s->goff.p, pp.prm_off, sizeof(int32_t) * (size_t)P);      // the particle's block in out_grad: the caller's own offsets
+  }
   HIPCHK(c, up.flush(s->h_stage, s->up_blob, st));
 
-  SeriesArgs sa = {};
+  SeriesGradArgs sa = {};      // (the value launches take its SeriesArgs part)
+  if (go) {
+    sa.ghdr = s->ghdr.as<GProgHdr>(); sa.gops = s->gops.as<uint8_t>(); sa.glc = s->glc.as<uint8_t>(); sa.grc = s->grc.as<uint8_t>();
+    sa.gpoff = s->gpoff.as<int32_t>(); sa.gprm = s->gprm.as<double>(); sa.gmap = s->gmap.as<int32_t>();
+    sa.out_off = s->goff.as<int32_t>(); sa.out_grad = s->dgrad.as<double>(); sa.out_gnoise = s->dgnoise.as<double>();
+  }
   sa.ts = s->tt.as<double>(); sa.xs = s->tt.as<double>() + npts;
   sa.pt_off = s->map.as<long long>();
   sa.series = reinterpret_cast<const int32_t*>(s->map.as<char>() + o_series);
@@ -127,20 +172,27 @@ int series_batch(agp_ctx* c, int32_t S, const int64_t* pt_off, const double* ts,
     HIPCHK(c, hipEventRecord(ev[0], st));
   }
   size_t w0 = 0;
-  for (int d = 0; d < 2; ++d)
+  for (int d = 0; d < 3; ++d)
     for (int k = 0; k < 3; ++k) {
       const std::vector<int32_t>& v = list[d][k];
       if (v.empty()) continue;
       size_t lds = 0;
       for (int32_t p : v) lds = std::max(lds, need[(size_t)p]);
       sa.wg = reinterpret_cast<const int32_t*>(s->map.as<char>() + o_wg) + w0;
-      HIPCHK(c, launch_series_logpdf(st, sa, (int)v.size(), d == 0 ? 4 : 8, lds));
+      if (go) HIPCHK(c, launch_series_logpdf_grad(st, sa, (int)v.size(), d == 2 ? 8 : 4, d == 0 ? 16 : 64, lds));
+      else HIPCHK(c, launch_series_logpdf(st, sa, (int)v.size(), d == 0 ? 4 : 8, lds));
       w0 += v.size();
     }
   if (prof) HIPCHK(c, hipEventRecord(ev[1], st));
   const size_t out_bytes = sizeof(double) * (size_t)P + sizeof(int32_t) * (size_t)P;
-  HIPCHK(c, s->h_out.ensure(out_bytes));
+  const size_t o_gn = (out_bytes + 7) & ~(size_t)7, o_gr = o_gn + sizeof(double) * (size_t)P;      // gradient outputs behind [logpdf | info]
+  HIPCHK(c, s->h_out.ensure(go ? o_gr + sizeof(double) * n_prm_total : out_bytes));
   HIPCHK(c, hipMemcpyAsync(s->h_out.p, s->out_lp.p, out_bytes, hipMemcpyDeviceToHost, st));
+  if (go) {
+    char* ho = static_cast<char*>(s->h_out.p);
+    HIPCHK(c, hipMemcpyAsync(ho + o_gn, s->dgnoise.p, sizeof(double) * (size_t)P, hipMemcpyDeviceToHost, st));
+    if (n_prm_total > 0) HIPCHK(c, hipMemcpyAsync(ho + o_gr, s->dgrad.p, sizeof(double) * n_prm_total, hipMemcpyDeviceToHost, st));
+  }
   HIPCHK(c, hipStreamSynchronize(st));
   const double* hl = static_cast<const double*>(s->h_out.p);
   const int32_t* hi = reinterpret_cast<const int32_t*>(hl + P);
@@ -148,6 +200,13 @@ int series_batch(agp_ctx* c, int32_t S, const int64_t* pt_off, const double* ts,
     const bool empty = len[(size_t)p] == 0;      // (never launched)
     out_logpdf[p] = empty ? 0.0 : hl[p];
     out_info[p] = empty ? 0 : hi[p];
+    if (go) {
+      // (an empty series: zeros; a bad pivot: NaN in the whole block — the kernel wrote them, slot by slot through gmap)
+      const double* hgn = reinterpret_cast<const double*>(static_cast<const char*>(s->h_out.p) + o_gn);
+      const double* hgr = hgn + P;
+      go->gnoise[p] = empty ? 0.0 : hgn[p];
+      for (int32_t q = pp.prm_off[p]; q < pp.prm_off[p + 1]; ++q) go->grad[q] = empty ? 0.0 : hgr[q];
+    }
   }
   if (prof) {
     // agp_get_timing: out[0] = out[2] = the value kernels of the call (covariance, factorisation, solve and value are one kernel)
@@ -220,6 +279,15 @@ int agp_logpdf_series_batch(agp_ctx* c, int32_t S, const int64_t* pt_off, const 
                             const int32_t* series, const int32_t* op_off, const uint8_t* ops, const int32_t* prm_off, const double* prm,
                             const double* noise, double* out_logpdf, int32_t* out_info) {
   return abi_guard(c, [&] { return series_batch(c, S, pt_off, ts, xs, {P, op_off, ops, prm_off, prm, noise, nullptr}, series, out_logpdf, out_info); });
+}
+
+int agp_logpdf_grad_series_batch(agp_ctx* c, int32_t S, const int64_t* pt_off, const double* ts, const double* xs, int32_t P,
+                                 const int32_t* series, const int32_t* op_off, const uint8_t* ops, const int32_t* prm_off, const double* prm,
+                                 const double* noise, double* out_logpdf, double* out_grad, double* out_grad_noise, int32_t* out_info) {
+  return abi_guard(c, [&] {
+    const GradOut go{out_grad, out_grad_noise};
+    return series_batch(c, S, pt_off, ts, xs, {P, op_off, ops, prm_off, prm, noise, nullptr}, series, out_logpdf, out_info, &go);
+  });
 }
 
 int agp_debug_series_factor(agp_ctx* c, const double* K, const double* y, int64_t n, int32_t P, double* out_L, double* out_alpha,

@@ -31,19 +31,39 @@
 //
 // A particle's bits depend on its own series, program, parameters and noise only: the LDS map is a function of the particle's own
 // sizes, no value crosses workgroups, and every reduction runs in a fixed order.
+//
+// k_series_logpdf_grad<D, GS> (agp_logpdf_grad_series_batch) is the value kernel with the gradient behind it, in the same workgroup and
+// the same LDS: stages 1-5 are the statements of k_series_logpdf (one body, series_body; the value's bits are the value kernel's), then
+//   G1. the diagonal blocks L(i,i)^-T by forward substitution, in place;
+//   G2. Z = L^-T in place, block column by block column: Z(j,i) = -[sum_{j<=k<i} Z(j,k) L(i,k)'] L(i,i)^-T sits where L(i,j) sat (a
+//       second copy of the blocks does not fit at n = 176), so a column's results wait in registers until every wave has read
+//       row i of L; products on v_mfma_f64_16x16x4 with the operand reads of the panel step;
+//   G3. alpha = Z beta into its own vector;
+//   G4. per lower block (rb, cb), one wave: K^-1(rb,cb) = sum_{k>=rb} Z(rb,k) Z(cb,k)' by an MFMA chain into registers — never stored —
+//       G = 1/2 (alpha alpha' - K^-1) on the spot, and grad_elements (the tiled sweep's reverse-mode pass, private tape of GS nodes) on
+//       the lane's four elements; DIAGONAL BLOCKS ARE EVALUATED IN FULL AT WEIGHT 1, off-diagonal blocks at weight 2, rows / columns
+//       past n at weight 0 (Z's padding is identity and must not leak); tr G from the diagonal elements;
+//   G5. thread -> wave -> the four waves in order -> out_grad through gmap (the caller's parameter order), out_gnoise.
+// On a bad pivot G1-G4 are skipped and NaN is written.  The LDS map is series_grad_lds (agp_args.hpp): alpha, the gradient program and
+// the reduction scratch in front of the blocks, and a second per-point table per ChangePoint node (1 - sigma, see grad_elements' CSIG);
+// at n = 176 a chain of 4 ChangePoint nodes (9 nodes, 13 parameters, 8 tables) fits, 5 do not.
+// An LDS tape (LdsTape: 8 nodes x 4 x 256 doubles = 64 KiB) would fit only beside short series' blocks; it is not built — see
+// profiles/series_grad_perf.txt.
 #pragma once
 #include <type_traits>
 #include "agp_common.hpp"
 #include "agp_args.hpp"
 #include "agp_cov_kernel.hpp"
 #include "agp_chol_kernel.hpp"      // mfma, readlane_d, blk_idx
+#include "agp_grad_elements.hpp"    // grad_elements, RegTape, ScratchAcc
 
 namespace agp {
 
-template <int D, bool PROBE = false>
-__global__ __launch_bounds__(256, 2) void k_series_logpdf(std::conditional_t<PROBE, SeriesProbeArgs, SeriesArgs> a) {
+// The body of every instantiation: stages 1-5 (value kernel, probe, gradient kernel alike — the same statements), and with GS > 0
+// (gradient tape of GS nodes) the stages G1-G5 behind them.
+template <int D, bool PROBE, int GS, class ArgsT>
+__device__ __forceinline__ void series_body(const ArgsT& a, double* smem) {
   constexpr int E = 4;
-  extern __shared__ __attribute__((aligned(16))) double smem[];
   const int tid = threadIdx.x, l = tid & 63, w = tid >> 6, l15 = l & 15, lq = l >> 4;
   int p, n;
   long long o0 = 0;
@@ -61,7 +81,10 @@ __global__ __launch_bounds__(256, 2) void k_series_logpdf(std::conditional_t<PRO
     return;
   }
   const ProgHdr h = [&]() -> ProgHdr { if constexpr (PROBE) return ProgHdr{}; else return a.hdr[p]; }();
-  const SeriesLds m = series_lds(n, h.n_ops, h.n_prm, h.n_cp);
+  const auto m = [&]() {
+    if constexpr (GS > 0) return series_grad_lds(n, h.n_ops, h.n_prm, h.n_cp, a.ghdr[p].n_ops, a.ghdr[p].n_prm);
+    else return series_lds(n, h.n_ops, h.n_prm, h.n_cp);
+  }();
   const int nb = m.nb, np = m.np;
   double* Wl = smem;
   [[maybe_unused]] double* tpt = smem + m.o_tpt;      // (tpt, etab, prm, ops, sig: unused by the probe, whose map has none of them)
@@ -383,6 +406,192 @@ __global__ __launch_bounds__(256, 2) void k_series_logpdf(std::conditional_t<PRO
     for (int i = tid; i < nel; i += 256) a.out_blk[(long long)p * nel + i] = sm[i];
     if (tid < np) a.out_alpha[(long long)p * np + tid] = avec[tid];
   }
+
+  if constexpr (GS > 0) {
+    // ================= gradient: d logpdf / d theta = sum_ab G_ab dK_ab / d theta, G = 1/2 (alpha alpha' - K^-1); d / d noise = tr G =================
+    // LDS now: L in the packed blocks (diagonal blocks: zero above the diagonal; rows / columns past n: identity), beta = L^-1 x in
+    // avec (padding: 0), tpt.  rvec and Wl are dead.
+    const GProgHdr g = a.ghdr[p];
+    double* alpha = smem + m.o_alpha;
+    double* gprm = smem + m.o_gprm;
+    int32_t* gpoff = reinterpret_cast<int32_t*>(smem + m.o_gtab);
+    uint8_t* gops = reinterpret_cast<uint8_t*>(gpoff + g.n_ops);
+    uint8_t* glc = gops + g.n_ops;
+    uint8_t* grc = glc + g.n_ops;
+    uint8_t* gmv = grc + g.n_ops;      // 1: stationary leaf with non-zero amplitude (see grad_elements)
+    double* red = smem + m.o_red;
+    if (tid == 0) rvec[0] = (double)bad;      // (wave 0 keeps the first bad pivot)
+    // the gradient program (k_grad_contract's staging)
+    for (int i = tid; i < g.n_prm + 3; i += 256) gprm[i] = a.gprm[g.prm_off + i];
+    for (int i = tid; i < g.n_ops; i += 256) {
+      const int po = a.gpoff[g.node_off + i];
+      const int o = a.gops[g.node_off + i];
+      gpoff[i] = po;
+      gops[i] = (uint8_t)o; glc[i] = a.glc[g.node_off + i]; grc[i] = a.grc[g.node_off + i];
+      const bool stat = (o == OP_SE || o == OP_GE || o == OP_PER);
+      gmv[i] = (stat && a.gprm[g.prm_off + po + (o == OP_SE ? 1 : 2)] != 0.0) ? 1 : 0;
+    }
+    __syncthreads();
+    if (rvec[0] != 0.0) {      // a bad pivot: NaN in the whole gradient block and d / d noise (the value is NaN already), nothing else
+      for (int q = tid; q < g.n_prm; q += 256) a.out_grad[a.out_off[p] + a.gmap[g.prm_off + q]] = __builtin_nan("");
+      if (tid == 0) a.out_gnoise[p] = __builtin_nan("");
+      return;
+    }
+    // per-point tables in the gradient program's node order (the order grad_elements counts ChangePoint nodes in), same arithmetic
+    // as stage 2, each followed — n_cp tables on — by its complement 1 - sigma (the map's csig, directly behind sig)
+    if (g.n_cp > 0 && tid < np) {
+      const double t = tpt[tid];
+      int c = 0;
+      for (int ip = 0; ip < g.n_ops; ++ip)
+        if (gops[ip] == OP_CP) {
+          const double* q = gprm + gpoff[ip];
+          const double th = tanh((q[0] - t) / q[1]);
+          sig[c * 256 + tid] = 0.5 * (1.0 + th);
+          sig[(g.n_cp + c) * 256 + tid] = 0.5 * (1.0 - th);      // 1 - sigma from the same tanh: exact where sigma is near 1 (grad_elements, CSIG)
+          ++c;
+        }
+    }
+    // ---- G1. Z = L^-T in place, block Z(j,i) (j <= i) in the slot of lower block (i,j), column-major: K^-1 = Z Z' then contracts
+    //      over natural (conflict-free) LDS reads exactly like L L' does.  First the diagonal: Z(i,i) = L(i,i)^-T, one block per wave
+    //      and pass, column c of L(i,i)^-1 by forward substitution in lane c (the reads of L are broadcasts) ----
+    for (int i = w; i < nb; i += 4) {
+      double* blk = sm + blk_idx(i, i) * 256;
+      if (l < 16) {
+        double wv[16];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          double s = (r == l) ? 1.0 : 0.0;
+#pragma unroll
+          for (int k = 0; k < r; ++k) s = fma(-blk[k * 16 + r], wv[k], s);
+          wv[r] = s / blk[17 * r];
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) blk[r * 16 + l] = wv[r];      // Z(i,i)[c][r] = W[r][c]: the whole block, zeros below the diagonal
+      }
+    }
+    __syncthreads();
+    // ---- G2. column i of Z (slot row i): Z(j,i) = -[sum_{k=j}^{i-1} Z(j,k) L(i,k)'] L(i,i)^-T, j < i.  Reads row i of L (slots (i,k))
+    //      and finished columns k < i of Z (slots (k,j)); its results replace row i of L, so they wait in registers until every
+    //      wave has read that row: blocks j = w, w + 4, w + 8 per wave (nb <= 11: at most three) ----
+    for (int i = 1; i < nb; ++i) {
+      d4 res[3];
+      double fw[4];
+#pragma unroll
+      for (int s4 = 0; s4 < 4; ++s4) fw[s4] = sm[blk_idx(i, i) * 256 + l15 * 16 + 4 * s4 + lq];      // L(i,i)^-1 (l15, 4 s4 + lq) = Z(i,i)'
+#pragma unroll
+      for (int u = 0; u < 3; ++u) {
+        const int j = w + 4 * u;
+        res[u] = d4{0.0, 0.0, 0.0, 0.0};
+        if (j < i) {
+          d4 acc = d4{0.0, 0.0, 0.0, 0.0};
+          for (int k = j; k < i; ++k) {
+            const double* lb = sm + blk_idx(i, k) * 256;
+            const double* zb = sm + blk_idx(k, j) * 256;
+            double fa[4], fb[4];
+#pragma unroll
+            for (int s4 = 0; s4 < 4; ++s4) { fa[s4] = lb[64 * s4 + l]; fb[s4] = zb[64 * s4 + l]; }
+#pragma unroll
+            for (int s4 = 0; s4 < 4; ++s4) acc = mfma(fa[s4], fb[s4], acc);      // += Z(j,k) L(i,k)'
+          }
+#pragma unroll
+          for (int s4 = 0; s4 < 4; ++s4) res[u] = mfma(fw[s4], -acc[s4], res[u]);      // (-C) L(i,i)^-T
+        }
+      }
+      __syncthreads();
+#pragma unroll
+      for (int u = 0; u < 3; ++u) {
+        const int j = w + 4 * u;
+        if (j < i) {
+          double* blk = sm + blk_idx(i, j) * 256;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) blk[64 * r + l] = res[u][r];
+        }
+      }
+      __syncthreads();
+    }
+    // ---- G3. alpha = Z beta: one row per thread, columns in ascending order ----
+    if (tid < np) {
+      const int j = tid >> 4, r = tid & 15;
+      double s = 0.0;
+      for (int k = j; k < nb; ++k) {
+        const double* zb = sm + blk_idx(k, j) * 256;
+#pragma unroll
+        for (int c = 0; c < 16; ++c) s = fma(zb[c * 16 + r], avec[k * 16 + c], s);
+      }
+      alpha[tid] = s;
+    }
+    __syncthreads();
+    // ---- G4. contraction, K^-1 never stored: lower block (rb, cb) -> wave b % 4 (b its row-major index: a function of nb alone) forms
+    //      K^-1(rb,cb) = sum_{k >= rb} Z(rb,k) Z(cb,k)' in registers — lane (i = l%16, q = l/16) <-> elements (i, q + 4 e), the map of
+    //      stage 3 — turns it into G and runs the reverse-mode pass on its four elements.  Off-diagonal blocks stand for their mirror
+    //      image (weight 2); diagonal blocks are evaluated in full at weight 1; rows / columns past n (identity in Z) weigh 0 ----
+    constexpr int NG = 3 * GS + 2;
+    double gacc[NG];
+    for (int q = 0; q <= g.n_prm + 2 && q < NG; ++q) gacc[q] = 0.0;
+    ScratchAcc<NG> sacc{gacc};
+    RegTape<GS, E> tape;
+    double gnoise = 0.0;
+    {
+      const int nblk = nb * (nb + 1) / 2;
+      for (int b = w; b < nblk; b += 4) {
+        int rb = 0;
+        while ((rb + 1) * (rb + 2) / 2 <= b) ++rb;
+        const int cb = b - rb * (rb + 1) / 2;
+        d4 kin = d4{0.0, 0.0, 0.0, 0.0};
+        for (int k = rb; k < nb; ++k) {
+          const double* za = sm + blk_idx(k, cb) * 256;
+          const double* zb = sm + blk_idx(k, rb) * 256;
+          double fa[4], fb[4];
+#pragma unroll
+          for (int s4 = 0; s4 < 4; ++s4) { fa[s4] = za[64 * s4 + l]; fb[s4] = zb[64 * s4 + l]; }
+#pragma unroll
+          for (int s4 = 0; s4 < 4; ++s4) kin = mfma(fa[s4], fb[s4], kin);
+        }
+        const double wfac = rb == cb ? 1.0 : 2.0;
+        int ri[E], ci[E];
+        double ta[E], tb[E], wg[E], lt[E];
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+          ri[e] = rb * 16 + l15;
+          ci[e] = cb * 16 + lq + 4 * e;
+          const bool valid = ri[e] < n && ci[e] < n;
+          const double G = valid ? 0.5 * (alpha[ri[e]] * alpha[ci[e]] - kin[e]) : 0.0;
+          if (ri[e] == ci[e]) gnoise += G;
+          ta[e] = tpt[ri[e]]; tb[e] = tpt[ci[e]]; wg[e] = wfac * G; lt[e] = 0.0;
+        }
+        grad_elements<GS, E, true>(g, gops, glc, grc, gmv, gpoff, gprm, sig, ri, ci, ta, tb, wg, lt, false, tape, sacc);
+      }
+    }
+    gacc[g.n_prm] = gnoise;
+    // ---- G5. per-thread sums -> lanes of a wave (butterfly) -> the four waves in order -> the caller's parameter order ----
+    const int nq = g.n_prm + 1;
+    for (int q = 0; q < nq; ++q) {
+      double s = gacc[q];
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+      if (l == 0) red[w * nq + q] = s;
+    }
+    __syncthreads();
+    for (int q = tid; q < nq; q += 256) {
+      const double s = ((red[q] + red[nq + q]) + red[2 * nq + q]) + red[3 * nq + q];
+      if (q < g.n_prm) a.out_grad[a.out_off[p] + a.gmap[g.prm_off + q]] = s;
+      else a.out_gnoise[p] = s;
+    }
+  }
+}
+
+template <int D, bool PROBE = false>
+__global__ __launch_bounds__(256, 2) void k_series_logpdf(std::conditional_t<PROBE, SeriesProbeArgs, SeriesArgs> a) {
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  series_body<D, PROBE, 0>(a, smem);
+}
+
+// Value and gradient of one (series, particle) pair by one workgroup: GS = nodes the reverse-mode tape holds (16 or 64; a private
+// array, as in k_grad_contract<GS>), D as above.
+template <int D, int GS>
+__global__ __launch_bounds__(256, 2) void k_series_logpdf_grad(SeriesGradArgs a) {
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  series_body<D, false, GS>(a, smem);
 }
 
 }  // namespace agp

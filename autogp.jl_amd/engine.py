@@ -36,7 +36,7 @@ EXPORTED_SYMBOLS = [
     "agp_mixture_quantile", "agp_predict_quantile_batch", "agp_infer_gp_sum_batch", "agp_predict_sum_batch",
     "agp_predict_sample_batch", "agp_mixture_moments", "agp_predict_mixture_batch", "agp_get_mixture_stats",
     "agp_remove_data", "agp_get_remove_stats", "agp_set_remove_update", "agp_remove_data_multi",
-    "agp_debug_factor_batch", "agp_logpdf_series_batch", "agp_debug_series_factor",
+    "agp_debug_factor_batch", "agp_logpdf_series_batch", "agp_debug_series_factor", "agp_logpdf_grad_series_batch",
 ]
 COMM_ID_BYTES = 128
 SERIES_MAX_N = 176      # AGP_SERIES_MAX_N of include/autogp_hip.h: the longest series of logpdf_series_batch
@@ -103,6 +103,8 @@ def load_library(path=None):
     lib.agp_logpdf_batch.restype = C.c_int
     lib.agp_logpdf_series_batch.argtypes = [vp, C.c_int32, C.POINTER(C.c_int64), dp, dp, C.c_int32, ip, ip, u8p, ip, dp, dp, dp, ip]
     lib.agp_logpdf_series_batch.restype = C.c_int
+    lib.agp_logpdf_grad_series_batch.argtypes = [vp, C.c_int32, C.POINTER(C.c_int64), dp, dp, C.c_int32, ip, ip, u8p, ip, dp, dp, dp, dp, dp, ip]
+    lib.agp_logpdf_grad_series_batch.restype = C.c_int
     lib.agp_logpdf_grad_batch.argtypes = [vp, C.c_int64, C.c_int32, ip, u8p, ip, dp, dp, dp, dp, dp, ip]
     lib.agp_logpdf_grad_batch.restype = C.c_int
     lib.agp_logpdf_grad.argtypes = [vp, C.c_int64, u8p, C.c_int32, dp, C.c_int32, C.c_double, dp, dp, dp, ip]
@@ -247,6 +249,21 @@ def pack_series(series):
         tss.append(ts); xss.append(xs)
     cat = lambda parts: np.ascontiguousarray(np.concatenate(parts)) if parts else np.zeros(0)
     return pt_off, cat(tss), cat(xss)
+
+
+def series_call_args(series, nodes, noises, series_index, programs=None):
+    """The validated arguments the two many-series entries share: (pt_off, ts, xs, (op_off, ops, prm_off, prm), P, noises, sidx).
+    Raises ValueError (pack_series' checks, one noise and one series index per particle) before any library call."""
+    pt_off, ts, xs = pack_series(series)
+    programs = programs if programs is not None else _gp.encode_batch(nodes)
+    P = programs[0].shape[0] - 1
+    noises = _f64(noises)
+    if noises.shape != (P,):
+        raise ValueError("one noise per particle required")
+    sidx = np.ascontiguousarray(np.asarray(series_index, dtype=np.int32))
+    if sidx.shape != (P,):
+        raise ValueError("one series index per particle required")
+    return pt_off, ts, xs, programs, P, noises, sidx
 
 
 def check_remove_indexes(indexes, n_max):
@@ -417,15 +434,7 @@ class GPEngine:
         """agp_logpdf_series_batch: many short series (a sequence of (ts, xs) pairs of at most SERIES_MAX_N points each) scored in one
         fused launch — particle p scores series[series_index[p]]: log N(xs_s; 0, K_p(ts_s) + noise_p I).  Needs no set_data and leaves
         the resident series, the factor store and every counter alone.  Returns (logpdf[P], info[P])."""
-        pt_off, ts, xs = pack_series(series)
-        op_off, ops, prm_off, prm = programs if programs is not None else _gp.encode_batch(nodes)
-        P = op_off.shape[0] - 1
-        noises = _f64(noises)
-        if noises.shape != (P,):
-            raise ValueError("one noise per particle required")
-        sidx = np.ascontiguousarray(np.asarray(series_index, dtype=np.int32))
-        if sidx.shape != (P,):
-            raise ValueError("one series index per particle required")
+        pt_off, ts, xs, (op_off, ops, prm_off, prm), P, noises, sidx = series_call_args(series, nodes, noises, series_index, programs)
         out = np.empty(P, dtype=np.float64); info = np.empty(P, dtype=np.int32)
         ts_arg = ts if ts.size else np.zeros(1)
         xs_arg = xs if xs.size else np.zeros(1)
@@ -437,6 +446,24 @@ class GPEngine:
             p = int(np.argmax(info > 0))
             raise PosDefException(int(info[p]), p)
         return out, info
+
+    def logpdf_grad_series_batch(self, series, nodes, noises, series_index, check=True, programs=None):
+        """agp_logpdf_grad_series_batch: value and gradient of many short series in one fused launch — logpdf_series_batch's twin, same
+        arguments, same statelessness.  Returns (logpdf[P], grads, grad_noise[P], info[P]); grads[p] is d logpdf / d theta in the order
+        of gp.encode(node)[1], as in logpdf_grad_batch; logpdf is bit-identical to logpdf_series_batch's."""
+        pt_off, ts, xs, (op_off, ops, prm_off, prm), P, noises, sidx = series_call_args(series, nodes, noises, series_index, programs)
+        out = np.empty(P, dtype=np.float64); info = np.empty(P, dtype=np.int32); gn = np.empty(P, dtype=np.float64)
+        grad = np.zeros(max(1, int(prm_off[-1])))
+        ts_arg = ts if ts.size else np.zeros(1)
+        xs_arg = xs if xs.size else np.zeros(1)
+        prm_arg = prm if prm.size else np.zeros(1)
+        self._check(self._lib.agp_logpdf_grad_series_batch(self._ctx, pt_off.shape[0] - 1, pt_off.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                           _dp(ts_arg), _dp(xs_arg), P, _ip(sidx), _ip(op_off), _u8(ops), _ip(prm_off),
+                                                           _dp(prm_arg), _dp(noises), _dp(out), _dp(grad), _dp(gn), _ip(info)))
+        if check and (info > 0).any():
+            p = int(np.argmax(info > 0))
+            raise PosDefException(int(info[p]), p)
+        return out, [grad[prm_off[i]:prm_off[i + 1]] for i in range(P)], gn, info
 
     def logpdf_batch_extend(self, nodes, noises, n=None, check=True, programs=None):
         """agp_logpdf_batch_extend: like logpdf_batch, but the factors stay resident and a later call on a longer

@@ -220,6 +220,33 @@ function logpdf_series_batch(eng::Engine, series::Vector{<:Tuple{Vector{Float64}
     return out, info
 end
 
+"Value and gradient of many short series in one fused launch (agp_logpdf_grad_series_batch): `logpdf_series_batch`'s twin for
+`Gen.choice_gradients` / `Gen.map_optimize` of callers that hold one model per short series.  Same arguments, same statelessness.
+Returns `(logpdf, grads, grad_noise, info)`; `grads[p]` is d logpdf / d theta in the order of `encode(kernels[p])[2]`, as in
+`logpdf_grad_batch`; `logpdf` is bit-identical to `logpdf_series_batch`'s."
+function logpdf_grad_series_batch(eng::Engine, series::Vector{<:Tuple{Vector{Float64},Vector{Float64}}}, kernels::Vector{<:GP.Node},
+                                  noises::Vector{Float64}, series_index::Vector{<:Integer})
+    P = length(kernels)
+    (length(noises) == P && length(series_index) == P) || throw(ArgumentError("one noise and one series index per particle required"))
+    pt_off = Int64[0]; ts = Float64[]; xs = Float64[]
+    for (s, (t, x)) in enumerate(series)
+        length(t) == length(x) || throw(ArgumentError("series $s: ts and xs must have equal lengths"))
+        length(t) <= SERIES_MAX_N || throw(ArgumentError("series $s has $(length(t)) points, more than SERIES_MAX_N ($SERIES_MAX_N)"))
+        append!(ts, t); append!(xs, x); push!(pt_off, length(ts))
+    end
+    isempty(ts) && (push!(ts, 0.0); push!(xs, 0.0))
+    sidx = Int32[Int32(i - 1) for i in series_index]
+    op_off, ops, prm_off, prm = encode_batch(kernels)
+    out = Vector{Float64}(undef, P); info = Vector{Int32}(undef, P); gn = Vector{Float64}(undef, P)
+    grad = zeros(Float64, max(1, Int(prm_off[end])))
+    GC.@preserve pt_off ts xs sidx op_off ops prm_off prm noises out grad gn info check(eng, ccall((:agp_logpdf_grad_series_batch, LIB), Cint,
+        (Ptr{Cvoid}, Int32, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Int32}, Ptr{Int32}, Ptr{UInt8}, Ptr{Int32}, Ptr{Float64},
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
+        eng.ptr, length(series), pt_off, ts, xs, P, sidx, op_off, ops, prm_off, prm, noises, out, grad, gn, info))
+    grads = [grad[prm_off[p] + 1:prm_off[p + 1]] for p in 1:P]
+    return out, grads, gn, info
+end
+
 "(extended, from_scratch, tile_rows_reused, tile_rows_total, evicted_before_reuse, slots, callers, occupied, capacity_tile_rows, growth_copies) of the factor store"
 function extend_stats(eng::Engine)
     out = zeros(Int64, 10)

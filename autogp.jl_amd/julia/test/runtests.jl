@@ -172,6 +172,39 @@ kernels() = GP.Node[
         end
     end
 
+    @testset "many short series: value and gradient in one call (stateless)" begin
+        ks = kernels()
+        sers = [(ts[1:n], xs[1:n]) for n in (0, 17, 144)]
+        nodes = GP.Node[]; sidx = Int[]
+        for s in eachindex(sers), k in ks
+            push!(nodes, k); push!(sidx, s)
+        end
+        nz = fill(noise, length(nodes))
+        lp, grads, gn, info = H.logpdf_grad_series_batch(eng, sers, nodes, nz, sidx)
+        lp_v, _ = H.logpdf_series_batch(eng, sers, nodes, nz, sidx)
+        @test all(info .== 0)
+        @test lp == lp_v                                        # the value is the value entry's, bit for bit
+        for (p, (k, s)) in enumerate(zip(nodes, sidx))
+            t, x = sers[s]
+            ops, th = H.encode(k)
+            @test length(grads[p]) == length(th)
+            if isempty(t)
+                @test lp[p] == 0.0 && all(grads[p] .== 0.0) && gn[p] == 0.0
+                continue
+            end
+            f(thv, z) = ref_logpdf(H.node_from_flat(ops, thv), z, t, x)
+            for j in eachindex(th)
+                h = 1e-6 * max(1.0, abs(th[j]))
+                tp_ = copy(th); tm_ = copy(th); tp_[j] += h; tm_[j] -= h
+                fd = (f(tp_, noise) - f(tm_, noise)) / (2h)
+                @test abs(grads[p][j] - fd) <= 1e-5 * max(1.0, abs(fd))
+            end
+            h = 1e-7
+            @test abs(gn[p] - (f(th, noise + h) - f(th, noise - h)) / (2h)) <= 1e-4 * max(1.0, abs(gn[p]))
+        end
+        @test eng.n_max == 700      # the resident series is untouched
+    end
+
     @testset "Gen: value and gradient through gp_marginal_flat; HMC reuses the value call's factor" begin
         k0 = GP.Linear(0.1, 0.3, 0.7) + GP.Periodic(0.96, 0.21, 1.1) * GP.SquaredExponential(0.47, 0.8)
         ops = H.structure(k0)

@@ -123,6 +123,36 @@ int agp_logpdf_series_batch(agp_ctx* ctx, int32_t S, const int64_t* pt_off /* S+
                             const int32_t* op_off, const uint8_t* ops, const int32_t* prm_off, const double* prm,
                             const double* noise, double* out_logpdf /* P */, int32_t* out_info /* P */);
 
+/* Value AND gradient of many short series in one call: agp_logpdf_series_batch's twin for Gen.choice_gradients / Gen.map_optimize of
+ * callers that hold one model per short series.  One workgroup per particle forms, behind the value and in the same LDS, L^-T in place
+ * of L, alpha = K^-1 x, and contracts G = 1/2 (alpha alpha' - K^-1) with dK / d theta block by block; K^-1 is never stored and nothing
+ * but the outputs leaves the compute unit.
+ * Series, program, noise and info conventions are exactly those of agp_logpdf_series_batch; out_logpdf[p] is bit-identical to what
+ * that entry returns for the same particle.  out_grad has agp_logpdf_grad_batch's layout (the caller's parameter order, block p at
+ * prm_off[p]; ChangePoint contributes location and scale); out_grad_noise[p] = d logpdf / d noise = tr G.
+ * A series of length 0 gives logpdf 0, a zero gradient block, grad_noise 0 and info 0.  out_info[p] > 0 gives NaN in out_logpdf[p], in
+ * the particle's whole gradient block and in out_grad_noise[p]; the other particles of the call are untouched.  P == 0 is AGP_OK and
+ * touches nothing.
+ * The WHOLE call is rejected with
+ *   AGP_ERR_ARG: everything agp_logpdf_series_batch lists, a null out_grad when prm_off[P] > 0, a null out_grad_noise;
+ *   AGP_ERR_PROGRAM (names the particle): a malformed program; a tree of more than 64 nodes (agp_logpdf_grad_batch's limit); a
+ *     particle whose LDS need under the gradient kernel's map exceeds 160 KiB at its series' length.  That map holds, beside the
+ *     value kernel's arrays, a second 2 KiB table per ChangePoint node (1 - sigma, kept beside sigma for the derivatives' accuracy),
+ *     alpha (8 bytes per padded point), the gradient program (8 bytes per node and per parameter) and the reduction scratch (32 bytes
+ *     per parameter): at AGP_SERIES_MAX_N points a chain of 4 ChangePoint nodes (9 nodes, 13 parameters,
+ *     4 per-point tables) fits and one of 5 does not, where the value entry takes 10.
+ * Stateless and re-entrant like agp_logpdf_series_batch: needs no agp_set_data; leaves alone the resident series, the factor store and
+ * its statistics, the gradient-reuse, lag-domain, Toeplitz and structured counters, the coalescer, dedup and mixture counters; copies
+ * of a particle are NOT deduplicated; with profiling on agp_get_timing reports as for the value entry (out[0] = out[2] = the call's
+ * kernel time).  A particle's result bits depend only on its own series, program, parameters and noise — not on what else is in the
+ * call, its order, or how the call is split into launches. */
+int agp_logpdf_grad_series_batch(agp_ctx* ctx, int32_t S, const int64_t* pt_off /* S+1 */, const double* ts, const double* xs,
+                                 int32_t P, const int32_t* series /* P */,
+                                 const int32_t* op_off, const uint8_t* ops, const int32_t* prm_off, const double* prm,
+                                 const double* noise,
+                                 double* out_logpdf /* P */, double* out_grad /* prm_off[P] */,
+                                 double* out_grad_noise /* P */, int32_t* out_info /* P */);
+
 /* agp_logpdf_batch with BLOCK-EXTENSION of resident factors.  The data-annealing loop re-scores
  * every particle on a longer prefix of the same series with unchanged kernel parameters — the reweight step
  * (src/inference_smc_anneal_data.jl:206-217), add_data! (src/api.jl:426-443), scripts/online.jl:200 — and the
