@@ -6,7 +6,7 @@ imported through `__graft_entry__.load_package()` (module name ``autogp_jl_amd``
 from .gp import (Node, LeafNode, BinaryOpNode, WhiteNoise, Constant, Linear, SquaredExponential,
                  GammaExponential, Periodic, Plus, Times, ChangePoint, unroll, encode, encode_batch, from_tuple,
                  split_kernel_sop, extract_kernel)
-from .engine import (GPEngine, GPEngineMulti, shard_range, shard_plan, probe_lattice, logpdf_grad_batch_multi, predict_batch_multi, AGPError, PosDefException, load_library, LIB_PATH, EXPORTED_SYMBOLS,
+from .engine import (GPEngine, GPEngineMulti, shard_range, shard_plan, probe_lattice, probe_program, logpdf_grad_batch_multi, predict_batch_multi, AGPError, PosDefException, load_library, LIB_PATH, EXPORTED_SYMBOLS,
                      compute_cov_matrix_vectorized, eval_cov, mvnormal_logpdf, MvNormal, quantile, infer_gp_sum, predict_proba,
                      predict_quantile, predict_quantile_multi, raw_components, predict_mvn_sum, predict_sum, predict_rand,
                      MixtureModel, predict_mvn, pack_series, series_call_args, SERIES_MAX_N)

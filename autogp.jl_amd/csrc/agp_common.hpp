@@ -42,10 +42,12 @@ struct ProgHdr {
   int32_t n_ops;
   int32_t n_cp;     // number of per-point LDS tables: ChangePoint nodes + selector leaves
   int32_t n_prm;    // device parameters of this program
-  int32_t flags;    // bit 0: the program has OP_GE_TAB leaves (reads the log|dt| table)
+  int32_t flags;    // bit 0: the program has OP_GE_TAB leaves (reads the log|dt| table); bit 1 (PROG_CHAIN): leaf (leaf binop)*
   int32_t n_lag;    // number of per-tile lag tables (OP_LAG leaves); they follow the n_cp per-point tables in LDS
   int32_t lag_off;  // index of the program's first lag table in the sweep's table buffer (k_lag_tables)
 };
+
+constexpr int PROG_CHAIN = 2;
 
 // program of one lag table: the stationary subtree in the direct device form (OP_SE with 1/l^2, OP_GE with 1/l, ...)
 struct LagTabHdr {

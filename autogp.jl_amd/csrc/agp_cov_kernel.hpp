@@ -49,6 +49,41 @@ __device__ __forceinline__ int prm_count(int o) {
 // The time points and the lag tables are loaded in ONE round trip and the first barrier below also publishes whatever the caller
 // has just stored to LDS without synchronising (the factorisation kernels stage program and parameters there: three dependent
 // global round trips + barriers per tile became one).
+// NODE RECORDS of k_cov_tiles: {p0, p1, p2, opcode (low word of the fourth double)} per node, staged in LDS once per tile by
+// wave 0, published by cov_prologue's first barrier.  The interpreter then reads a node — opcode AND parameters — in one LDS round
+// trip instead of two dependent global ones per node and pass (opcode, then the parameters at the offset the opcode implies).
+// Slots past a node's own parameter count hold 0.0 (no evaluator reads them); ChangePoint nodes keep (location, scale) for the
+// prologue's sigma tables.
+constexpr int REC_DOUBLES = 4;
+__device__ __forceinline__ int rec_op(const double* rec, int ip) { return __double2loint(rec[REC_DOUBLES * ip + 3]); }
+__device__ __forceinline__ void stage_node_records(const ProgHdr& h, const uint8_t* __restrict__ ops, const double* __restrict__ prm,
+                                                   double* rec, int tid) {
+  if (tid >= 64) return;
+  int base = 0;
+  // (n_ops <= AGP_MAX_OPS_DEV = 4 x 64: unrolled, so that no loop of the kernel waits for a program byte from global memory)
+#pragma unroll
+  for (int i0 = 0; i0 < AGP_MAX_OPS_DEV; i0 += 64) {
+    if (i0 < h.n_ops) {
+      const int i = i0 + tid;
+      const bool live = i < h.n_ops;
+      const int o = live ? (int)ops[i] : OP_PLUS;      // (no parameters)
+      const int c = prm_count(o);
+      int s = c;                                       // inclusive scan of the chunk's parameter counts
+#pragma unroll
+      for (int d = 1; d < 64; d <<= 1) { const int u = __shfl_up(s, d); if (tid >= d) s += u; }
+      const int q = base + s - c;
+      if (live) {
+        d2 a, b;
+        a.x = c > 0 ? prm[q] : 0.0; a.y = c > 1 ? prm[q + 1] : 0.0;
+        b.x = c > 2 ? prm[q + 2] : 0.0; b.y = __hiloint2double(0, o);
+        *reinterpret_cast<d2*>(rec + REC_DOUBLES * i) = a;
+        *reinterpret_cast<d2*>(rec + REC_DOUBLES * i + 2) = b;
+      }
+      base += __shfl(s, 63);
+    }
+  }
+}
+
 template <bool LAG = false, typename OpT>
 __device__ __forceinline__ void cov_prologue(const double* __restrict__ tt, const uint8_t* __restrict__ code,
                                              int ti, int tj, const ProgHdr& h,
@@ -56,7 +91,8 @@ __device__ __forceinline__ void cov_prologue(const double* __restrict__ tt, cons
                                              double* tpt, double* sig, int tid,
                                              const double* __restrict__ lagtab = nullptr, int nt = 0,
                                              const int32_t* __restrict__ rank = nullptr, int lstride = 256, int* xrk = nullptr,
-                                             bool copy_rank_tables = true, const CltArgs clt = CltArgs{}, int* cbl = nullptr) {
+                                             bool copy_rank_tables = true, const CltArgs clt = CltArgs{}, int* cbl = nullptr,
+                                             const double* rec = nullptr) {
   const int g = (tid < NB) ? (ti * NB + tid) : (tj * NB + (tid - NB));
   const double tg = tt[g];
   if (LAG && h.n_lag > 0) {
@@ -98,13 +134,15 @@ __device__ __forceinline__ void cov_prologue(const double* __restrict__ tt, cons
     const int cd = code ? (int)code[g] : 0;
     int q = 0, c = 0;
     for (int ip = 0; ip < h.n_ops; ++ip) {
-      const int o = __builtin_amdgcn_readfirstlane((int)ops[ip]);
+      // (rec: the caller's node records, staged before the barrier above, instead of ops / prm)
+      const int o = __builtin_amdgcn_readfirstlane(rec != nullptr ? rec_op(rec, ip) : (int)ops[ip]);
+      const double* pq = rec != nullptr ? rec + REC_DOUBLES * ip : prm + q;
       if (o == OP_CP || o == OP_CP_SWAP) {
-        const double loc = prm[q], sc = prm[q + 1];
+        const double loc = pq[0], sc = pq[1];
         sig[c * 256 + tid] = 0.5 * (1.0 + tanh((loc - t) / sc));   // sigma_cp, src/GP.jl:481-483
         ++c;
       } else if (o == OP_SEL) {
-        const int id = (int)prm[q];
+        const int id = (int)pq[0];
         sig[c * 256 + tid] = (cd == 0 || cd == id) ? 1.0 : 0.0;
         ++c;
       }
@@ -183,9 +221,34 @@ __device__ __forceinline__ void eval_leaf(const int o, const double p0, const do
   }
 }
 
+// One binary node at E pairs: a = the operand evaluated first, b = the second; the result replaces b.  sg: the node's sigma table
+// (ChangePoint, either operand order).  The one combine step of every evaluator, so that they agree bit for bit.
+template <int E>
+__device__ __forceinline__ void combine_pair(const int o, const double (&a)[E], double (&b)[E], const double* sg,
+                                             const int (&ri)[E], const int (&ci)[E]) {
+  if (o == OP_PLUS) {
+#pragma unroll
+    for (int e = 0; e < E; ++e) b[e] = a[e] + b[e];
+  } else if (o == OP_TIMES) {
+#pragma unroll
+    for (int e = 0; e < E; ++e) b[e] = a[e] * b[e];
+  } else {
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+      const double si = sg[ri[e]];
+      const double sj = sg[ci[e]];
+      const double kl = (o == OP_CP) ? a[e] : b[e];
+      const double kr = (o == OP_CP) ? b[e] : a[e];
+      // K = sig_1 .* k_1 + sig_2 .* k_2   (src/GP.jl:494-501)
+      b[e] = (si * sj) * kl + ((1.0 - si) * (1.0 - sj)) * kr;
+    }
+  }
+}
+
 // Evaluate the program at E (row, column) pairs.  All arrays are statically indexed registers.  lag: the tile's lag tables
 // (after the per-point tables); etab: LDS copy of fm::c_exp_tab (fm::exp_t, 11 fp64 operations instead of exp_f's 21).
-template <int D, int E, int GEMODE = 0, typename OpT>
+// REC: `prm` holds the caller's node records (stage_node_records) and `ops` is not read.
+template <int D, int E, int GEMODE = 0, bool REC = false, typename OpT>
 __device__ __forceinline__ void eval_program(const ProgHdr& h, const OpT* __restrict__ ops,
                                              const double* __restrict__ prm, const double* sig,
                                              const double (&tr)[E], const double (&tc)[E],
@@ -201,12 +264,17 @@ __device__ __forceinline__ void eval_program(const ProgHdr& h, const OpT* __rest
   int q = 0, cpi = 0, li = 0;
   for (int ip = 0; ip < h.n_ops; ++ip) {
     // the opcode is wave-uniform: keep it (and the dispatch on it) on the scalar unit
-    const int o = __builtin_amdgcn_readfirstlane((int)ops[ip]);
+    d2 ra = d2{0.0, 0.0}, rb = d2{0.0, 0.0};
+    if (REC) {      // the whole node in one round trip
+      ra = *reinterpret_cast<const d2*>(prm + REC_DOUBLES * ip);
+      rb = *reinterpret_cast<const d2*>(prm + REC_DOUBLES * ip + 2);
+    }
+    const int o = __builtin_amdgcn_readfirstlane(REC ? __double2loint(rb.y) : (int)ops[ip]);
     if (o <= OP_PER || o >= OP_SEL) {
       // ---------------- leaf: push ----------------
       // every leaf's (up to three) parameters are fetched unconditionally — the parameter buffers
       // carry two doubles of tail padding — and picked by opcode afterwards
-      const double p0 = prm[q], p1 = prm[q + 1], p2 = prm[q + 2];
+      const double p0 = REC ? ra.x : prm[q], p1 = REC ? ra.y : prm[q + 1], p2 = REC ? rb.x : prm[q + 2];
       double v[E];
       eval_leaf<E, GEMODE>(o, p0, p1, p2, sig + cpi * 256, lag + li * lstride, tr, tc, ri, ci, lt, etab, v, rk, cb);
       if (o == OP_SEL) ++cpi;
@@ -219,25 +287,8 @@ __device__ __forceinline__ void eval_program(const ProgHdr& h, const OpT* __rest
       for (int e = 0; e < E; ++e) st[0][e] = v[e];
     } else {
       // ---------------- binary: combine st[1] (first evaluated) and st[0], pop ----------------
-      if (o == OP_PLUS) {
-#pragma unroll
-        for (int e = 0; e < E; ++e) st[0][e] = st[1][e] + st[0][e];
-      } else if (o == OP_TIMES) {
-#pragma unroll
-        for (int e = 0; e < E; ++e) st[0][e] = st[1][e] * st[0][e];
-      } else {
-        const double* sg = sig + cpi * 256;
-#pragma unroll
-        for (int e = 0; e < E; ++e) {
-          const double si = sg[ri[e]];
-          const double sj = sg[ci[e]];
-          const double kl = (o == OP_CP) ? st[1][e] : st[0][e];
-          const double kr = (o == OP_CP) ? st[0][e] : st[1][e];
-          // K = sig_1 .* k_1 + sig_2 .* k_2   (src/GP.jl:494-501)
-          st[0][e] = (si * sj) * kl + ((1.0 - si) * (1.0 - sj)) * kr;
-        }
-        ++cpi;
-      }
+      combine_pair<E>(o, st[1], st[0], sig + cpi * 256, ri, ci);
+      if (o != OP_PLUS && o != OP_TIMES) ++cpi;
 #pragma unroll
       for (int d = 1; d < D - 1; ++d)
 #pragma unroll
@@ -247,6 +298,36 @@ __device__ __forceinline__ void eval_program(const ProgHdr& h, const OpT* __rest
   }
 #pragma unroll
   for (int e = 0; e < E; ++e) out[e] = st[0][e];
+}
+
+// A CHAIN (ProgHdr.flags & PROG_CHAIN: leaf (leaf binop)*, what the host's operand ordering makes of most small trees) from the
+// caller's node records: the running value is combined with one further leaf per step — no evaluation stack, none of its
+// shift-register moves.  Same leaves, same combine step, same order of the per-point and lag tables as eval_program.
+template <int E, int GEMODE>
+__device__ __forceinline__ void eval_chain(const ProgHdr& h, const double* __restrict__ rec, const double* sig,
+                                           const double (&tr)[E], const double (&tc)[E],
+                                           const int (&ri)[E], const int (&ci)[E], const double (&lt)[E],
+                                           double (&out)[E], const double* etab, const double* lag,
+                                           const int* rk, int lstride, const int* cb) {
+  int cpi = 0, li = 0;
+  for (int ip = 0; ip < h.n_ops; ip += 2) {
+    // step ip / 2: the leaf in front of operator ip (step 0: the first leaf alone); leaf and operator in one round trip
+    const int lp = ip > 0 ? ip - 1 : 0;
+    const d2 ra = *reinterpret_cast<const d2*>(rec + REC_DOUBLES * lp);
+    const d2 rb = *reinterpret_cast<const d2*>(rec + REC_DOUBLES * lp + 2);
+    const int o2 = __builtin_amdgcn_readfirstlane(rec_op(rec, ip));
+    const int o = __builtin_amdgcn_readfirstlane(__double2loint(rb.y));
+    double v[E];
+    eval_leaf<E, GEMODE>(o, ra.x, ra.y, rb.x, sig + cpi * 256, lag + li * lstride, tr, tc, ri, ci, lt, etab, v, rk, cb);
+    if (o == OP_SEL) ++cpi;
+    if (o == OP_LAG) ++li;
+    if (ip > 0) {
+      combine_pair<E>(o2, out, v, sig + cpi * 256, ri, ci);
+      if (o2 != OP_PLUS && o2 != OP_TIMES) ++cpi;
+    }
+#pragma unroll
+    for (int e = 0; e < E; ++e) out[e] = v[e];
+  }
 }
 
 // noise on the diagonal of a tile (diag_noise), identity on padding rows / columns
@@ -301,8 +382,10 @@ __global__ __launch_bounds__(256, AGP_COV_WGS) void k_cov_tiles(CovArgs a) {
   const int lstride = rankt ? (a.clt.B != nullptr ? a.clt.gstride : a.lag_stride) : 256;      // (compact tables: whole, in place, with B)
   int* xrk = reinterpret_cast<int*>(sig + h.n_cp * 256 + (rankt ? 0 : h.n_lag * 256));      // [256] ranks (rank tables only)
   double* etab = reinterpret_cast<double*>(xrk) + (rankt ? 128 : 0);      // [128] exp table (launch_cov sizes the dynamic LDS for all of it)
+  double* rec = etab + AGP_EXP_TAB_N;      // [n_ops] node records
   if (AGP_EXP_TABLE && tid < AGP_EXP_TAB_N) etab[tid] = fm::c_exp_tab[tid];
-  cov_prologue<true>(a.tt, a.code, ti, tj, h, ops, prm, tpt, sig, tid, a.lagtab, a.nt, a.lagr, lstride, xrk, false);
+  stage_node_records(h, ops, prm, rec, tid);
+  cov_prologue<true>(a.tt, a.code, ti, tj, h, ops, prm, tpt, sig, tid, a.lagtab, a.nt, a.lagr, lstride, xrk, false, CltArgs{}, nullptr, rec);
   const double* lag = rankt ? a.lagtab + (long long)h.lag_off * lstride : sig + h.n_cp * 256;
   const int* rk = rankt ? xrk : nullptr;
   const int* cb = rankt ? a.clt.B : nullptr;
@@ -324,9 +407,10 @@ __global__ __launch_bounds__(256, AGP_COV_WGS) void k_cov_tiles(CovArgs a) {
 #pragma unroll
     for (int cc = 0; cc < CPP; ++cc) ltn[cc] = *reinterpret_cast<const d2*>(ltile + (long long)(cb0 + cc) * NB + r0);
   }
-  const bool one_node = h.n_ops == 1;
-  const int op1 = one_node ? __builtin_amdgcn_readfirstlane((int)ops[0]) : -1;
-  const double q0 = one_node ? prm[0] : 0.0, q1 = one_node ? prm[1] : 0.0, q2 = one_node ? prm[2] : 0.0;
+  // (chains: in the depth-4 instantiation only — beside the depth-8 stack the second evaluator costs 28 more spilled registers)
+  const bool one_node = h.n_ops == 1, chain = (h.flags & PROG_CHAIN) != 0;
+  const int op1 = one_node ? __builtin_amdgcn_readfirstlane(rec_op(rec, 0)) : -1;
+  const double q0 = one_node ? rec[0] : 0.0, q1 = one_node ? rec[1] : 0.0, q2 = one_node ? rec[2] : 0.0;
   for (int pass = 0; pass < NPASS; ++pass) {
     const int c0 = cb0 + pass * CPP;
     double tr[E], tc[E], out[E], lt[E];
@@ -345,7 +429,8 @@ __global__ __launch_bounds__(256, AGP_COV_WGS) void k_cov_tiles(CovArgs a) {
       ci[e] = NB + c0 + (e >> 1);
     }
     if (one_node) eval_leaf<E, 0>(op1, q0, q1, q2, sig, lag, tr, tc, ri, ci, lt, etab, out, rk, cb);      // (no interpreter: see chol_tile)
-    else eval_program<D, E, 0>(h, ops, prm, sig, tr, tc, ri, ci, lt, out, etab, lag, rk, lstride, cb);
+    else if (D <= 4 && chain) eval_chain<E, 0>(h, rec, sig, tr, tc, ri, ci, lt, out, etab, lag, rk, lstride, cb);
+    else eval_program<D, E, 0, true>(h, ops, rec, sig, tr, tc, ri, ci, lt, out, etab, lag, rk, lstride, cb);
 #pragma unroll
     for (int cc = 0; cc < CPP; ++cc) {
       const int gj = tj * NB + c0 + cc;

@@ -185,8 +185,11 @@ void classify(const std::vector<CNode>& nodes, int id, std::vector<char>& stat, 
 
 // lag: the sweep runs on a sorted regular grid — every maximal stationary subtree with a transcendental leaf becomes ONE OP_LAG
 // leaf, its own program (direct forms, same child order) goes to the table-program arrays (k_lag_tables evaluates it)
+// cneed (lag compilation): the stack need of every node in the COMPILED tree, where a collapsed subtree is one leaf — the children are
+// ordered by it ((Lin + Lin) * S_deep is LIN LIN + LAG *: one value held while the other operand is evaluated, not two).  + and x
+// commute exactly and ChangePoint has OP_CP_SWAP, so the order changes no bit of the result.
 void emit(const std::vector<CNode>& nodes, int id, Compiled& out, bool ge_tab, bool lag = false,
-          const std::vector<char>* stat = nullptr, const std::vector<char>* heavy = nullptr) {
+          const std::vector<char>* stat = nullptr, const std::vector<char>* heavy = nullptr, const std::vector<int>* cneed = nullptr) {
   const CNode& nd = nodes[id];
   if (lag && stat && (*stat)[id] && (*heavy)[id]) {
     Compiled sub;
@@ -222,9 +225,9 @@ void emit(const std::vector<CNode>& nodes, int id, Compiled& out, bool ge_tab, b
     }
     return;
   }
-  const bool swap = nodes[nd.right].need > nodes[nd.left].need;
-  emit(nodes, swap ? nd.right : nd.left, out, ge_tab, lag, stat, heavy);
-  emit(nodes, swap ? nd.left : nd.right, out, ge_tab, lag, stat, heavy);
+  const bool swap = cneed ? (*cneed)[nd.right] > (*cneed)[nd.left] : nodes[nd.right].need > nodes[nd.left].need;
+  emit(nodes, swap ? nd.right : nd.left, out, ge_tab, lag, stat, heavy, cneed);
+  emit(nodes, swap ? nd.left : nd.right, out, ge_tab, lag, stat, heavy, cneed);
   if (nd.op == OP_CP) {
     out.ops.push_back((uint8_t)(swap ? OP_CP_SWAP : OP_CP));
     out.prm.push_back(nd.prm[0]);
@@ -233,6 +236,24 @@ void emit(const std::vector<CNode>& nodes, int id, Compiled& out, bool ge_tab, b
   } else {
     out.ops.push_back((uint8_t)nd.op);
   }
+}
+
+// stack need of the compiled tree (lag compilation): a collapsed stationary subtree counts as a leaf
+int compiled_need(const std::vector<CNode>& nodes, int id, const std::vector<char>& stat, const std::vector<char>& heavy, std::vector<int>& cneed) {
+  const CNode& nd = nodes[id];
+  if (nd.left < 0 || (stat[id] && heavy[id])) return cneed[id] = 1;
+  const int a = compiled_need(nodes, nd.left, stat, heavy, cneed), b = compiled_need(nodes, nd.right, stat, heavy, cneed);
+  return cneed[id] = (a == b) ? a + 1 : std::max(a, b);
+}
+
+// A CHAIN is a compiled postfix of the form leaf (leaf binop)*: every binary node has a leaf as one operand, so the running value
+// needs no stack (ProgHdr.flags bit 1; one-node programs included).
+bool is_chain(const std::vector<uint8_t>& ops) {
+  auto leaf = [](int o) { return o <= OP_PER || o >= OP_SEL; };
+  if (ops.empty() || ops.size() % 2 == 0 || !leaf(ops[0])) return false;
+  for (size_t i = 1; i + 1 < ops.size(); i += 2)
+    if (!leaf(ops[i]) || leaf(ops[i + 1])) return false;
+  return true;
 }
 
 // returns 0 or an error string
@@ -276,11 +297,14 @@ const char* compile_program(const uint8_t* ops, int n_ops, const double* prm, in
   if (lag) {
     std::vector<char> stat(nodes.size(), 0), heavy(nodes.size(), 0);
     classify(nodes, stack[0], stat, heavy);
-    emit(nodes, stack[0], out, false, true, &stat, &heavy);
+    std::vector<int> cneed(nodes.size(), 1);
+    const int need_c = compiled_need(nodes, stack[0], stat, heavy, cneed);
+    emit(nodes, stack[0], out, false, true, &stat, &heavy, &cneed);
+    out.depth_need = need_c;
     if (out.n_cp + out.n_lag > COV_MAX_TABLES) {      // (a 63-node tree has at most 32 leaves + 31 ChangePoints: does not happen below 75 nodes)
       Compiled plain;
       emit(nodes, stack[0], plain, false, false);
-      plain.depth_need = out.depth_need;
+      plain.depth_need = nodes[stack[0]].need;
       out = plain;
     }
   } else {
@@ -371,7 +395,8 @@ int compile_batch(agp_ctx* c, const Particles& pp, Batch& bt, const CompileOpts&
     h.n_ops = (int32_t)cp.ops.size();
     h.n_cp = cp.n_cp;
     h.n_prm = (int32_t)cp.prm.size();
-    h.flags = cp.uses_tab ? 1 : 0;
+    const bool chain = is_chain(cp.ops);
+    h.flags = (cp.uses_tab ? 1 : 0) | (chain ? PROG_CHAIN : 0);
     h.n_lag = cp.n_lag; h.lag_off = bt.n_lag_tables;
     bt.n_lag_tables += cp.n_lag;
     for (LagTabHdr th : cp.thdr) {
@@ -386,12 +411,17 @@ int compile_batch(agp_ctx* c, const Particles& pp, Batch& bt, const CompileOpts&
     const int lds_units = cp.n_cp + cp.n_lag * o.lag_units + o.rank_extra;      // LDS tables of any kind (per-point + lag), 256 doubles each
     bt.max_cp = std::max(bt.max_cp, o.rank_extra > 0 ? cp.n_cp + 1 : lds_units);      // (k_cov_tiles reads rank / compact tables, and B, in place)
     bt.max_depth = std::max(bt.max_depth, cp.depth_need);
+    bt.max_ops = std::max(bt.max_ops, (int)cp.ops.size());
+    // (evaluation classes of the sweep, agp_get_eval_stats)
+    if (!fusable(bt.order[q])) { ++bt.n_eval[3]; if (chain && cp.ops.size() > 1) ++bt.n_eval[4]; }
+    else ++bt.n_eval[cp.ops.size() == 1 ? 0 : 2];
     if (fusable(bt.order[q])) {
       bt.n_fused = q + 1;
       bt.max_cp_fused = std::max(bt.max_cp_fused, lds_units);
       bt.max_depth_fused = std::max(bt.max_depth_fused, cp.depth_need);
     }
   }
+  if (bt.max_depth > 4) bt.n_eval[4] = 0;      // (k_cov_tiles<8> has the stack interpreter only)
   if (o.want_grad) {
     bt.ghdr.resize(P);
     for (int q = 0; q < P; ++q) {
@@ -975,6 +1005,7 @@ int logpdf_batch_impl(agp_ctx* c, int64_t n, const Particles& pp, double* h_out_
   if (go && bt.g_max_nodes > 64) return fail(c, AGP_ERR_PROGRAM, "gradient supports kernel trees of up to 64 nodes");
   if (go && n > 23040) return fail(c, AGP_ERR_ARG, "gradient sweeps address a particle's packed matrix with 32-bit byte offsets: n <= 23040");
   if (lag) { std::lock_guard<std::mutex> g(c->mu); ++c->n_lag_sweeps; }
+  { std::lock_guard<std::mutex> g(c->mu); for (int i = 0; i < 5; ++i) c->eval_stats[i] = bt.n_eval[i]; }
   // Gradient sweeps on a regular grid (any order of the points): particles whose kernel is a sum of stationary subtrees and
   // Linear leaves are contracted in the lag domain (k_kinv_tiles / k_lag_grad, agp_grad_kernel.hpp)
   int32_t toep_rank0 = 0;
@@ -1300,7 +1331,7 @@ int logpdf_batch_impl(agp_ctx* c, int64_t n, const Particles& pp, double* h_out_
         const int dcov = nf > 0 ? bt.max_depth_fused : 0;
         size_t e0 = pf.mark(q);
         cv.p_off = nf;
-        if (!(n_hit > 0 && i0min == nt)) HIPCHK(c, launch_cov(q, cv, ntiles, Pg - nf, bt.max_cp, bt.max_depth));      // (every particle resident: no tile to build)
+        if (!(n_hit > 0 && i0min == nt)) HIPCHK(c, launch_cov(q, cv, ntiles, Pg - nf, bt.max_cp, bt.max_depth, bt.max_ops));      // (every particle resident: no tile to build)
         size_t e1 = pf.mark(q);
         pf.span(1, e0, e1);
 
@@ -1882,6 +1913,29 @@ static CompactFit fit_compact(const std::vector<double>& tss, double lag_tol_h, 
   for (int64_t od = 1; od < n_max; ++od) cf.W = std::max(cf.W, top[(size_t)od] - cf.base[(size_t)od] + 1);
   cf.ok = cf.W <= CLT_MAX_W;
   return cf;
+}
+
+int agp_probe_program(const uint8_t* ops, int32_t n_ops, const double* prm, int32_t n_prm, int32_t* n_compiled, int32_t* chain,
+                      int32_t* depth, int32_t* n_tables) {
+  if (!ops || (n_prm > 0 && !prm)) return AGP_ERR_ARG;
+  try {
+    Compiled cp;
+    if (compile_program(ops, n_ops, prm, n_prm, cp, false, false, true)) return AGP_ERR_PROGRAM;
+    if (n_compiled) *n_compiled = (int32_t)cp.ops.size();
+    if (chain) *chain = is_chain(cp.ops) ? 1 : 0;
+    if (depth) *depth = cp.depth_need;
+    if (n_tables) *n_tables = cp.n_lag;
+  } catch (const std::exception&) {
+    return AGP_ERR_ARG;
+  }
+  return AGP_OK;
+}
+
+int agp_get_eval_stats(agp_ctx* c, int64_t* out5) {
+  if (!c || !out5) return fail(c, AGP_ERR_ARG, "null pointer");
+  std::lock_guard<std::mutex> g(c->mu);
+  for (int i = 0; i < 5; ++i) out5[i] = c->eval_stats[i];
+  return AGP_OK;
 }
 
 int agp_probe_lattice(const double* ts, int64_t n, int32_t* kind, int64_t* n_lattice, double* spacing, int64_t* index_out) {

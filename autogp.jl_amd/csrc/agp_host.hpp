@@ -324,6 +324,7 @@ struct agp_ctx {
   int lag_enable = 1;
   double lag_tol_h = 1e-11;       // admitted deviation of a sorted point from its grid position, in units of the spacing (agp_set_data)
   int64_t n_lag_sweeps = 0;       // sweeps that took the lag path (agp_get_lag_stats)
+  int64_t eval_stats[5] = {0, 0, 0, 0, 0};   // evaluation classes of the last batch sweep's particles (agp_get_eval_stats)
   double* d_logdt = nullptr;      // packed lower tiles, covers the resident data
   size_t logdt_cap = 0;
   bool logdt_ok = false;
@@ -463,7 +464,9 @@ struct Batch {
   int n_fused = 0;                // sorted positions [0, n_fused) are evaluated inside k_chol_update
   int max_cp = 0;
   int max_depth = 1;
+  int max_ops = 1;                // longest compiled program (k_cov_tiles stages one record per node in LDS)
   int max_cp_fused = 0, max_depth_fused = 1;
+  int64_t n_eval[5] = {0, 0, 0, 0, 0};   // particles per evaluation class, see agp_get_eval_stats
   int n_lag_tables = 0;           // OP_LAG leaves of the whole batch (one table set each, k_lag_tables)
   std::vector<LagTabHdr> thdr;    // their programs, offsets into tops / tprm
   std::vector<uint8_t> tops;
@@ -528,6 +531,9 @@ struct LagProgLayout {
 // launches 25 vs 35 us: 29.28 vs 29.6 ms at 512 particles; dataflow schedule 35 / 70 / 150 / 1000 us: config 2 0.99 / 0.92 / 0.92 /
 // 0.91 ms; lag-table sweeps price programs at ~2 us per node: dataflow 2.5 / 5 / 9 / 16 / 70 us: 3.87 / 3.83 / 3.83 / 3.86 / 4.01 ms at
 // n=2048 x 64, per-column launches 2.5 / 5 / 8 / 12 / 20 us: 25.33 / 25.40 / 25.57 / 25.58 / 25.94 ms (one-node programs only).
+// (Those prices are the factorisation kernels' stack interpreter on LDS-staged opcodes + parameters: two dependent LDS round trips
+// and the stack's moves per node and pass.  The tile builder has since lost its own decode latency — node records, chains without a
+// stack, agp_cov_kernel.hpp — which moves the break-even further towards prebuilding: LAG_FUSE_MAX_US stays at one-node programs.)
 constexpr double FUSE_MAX_US = 25.0, FLOW_FUSE_MAX_US = 70.0, FLOW_LAG_FUSE_MAX_US = 10.0, LAG_FUSE_MAX_US = 3.0;
 constexpr int LAG_LDS_MAX_UNITS = 16;     // rank tables of up to 16 x 256 lags are copied into the evaluators' LDS
 constexpr int64_t LATTICE_MAX = LAG_LDS_MAX_UNITS * 256;   // longest lattice admitted: its rank tables must fit that LDS budget (longer tables would be

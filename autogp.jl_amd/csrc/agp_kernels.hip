@@ -40,11 +40,14 @@ hipError_t kernels_init() {
   return hipSuccess;
 }
 
-hipError_t launch_cov(hipStream_t st, const CovArgs& ca, int ntiles, int P, int max_cp, int depth) {
+hipError_t launch_cov(hipStream_t st, const CovArgs& ca, int ntiles, int P, int max_cp, int depth, int max_ops) {
   if (ntiles <= 0 || P <= 0) return hipSuccess;
-  const size_t lds = (256 + (size_t)max_cp * 256 + AGP_EXP_TAB_N) * sizeof(double);      // tpt, sigma tables, exp table
+  if (max_ops < 1 || max_ops > AGP_MAX_OPS_DEV) return hipErrorInvalidValue;
+  // tpt, sigma tables, exp table, node records
+  const size_t lds = (256 + (size_t)max_cp * 256 + AGP_EXP_TAB_N + (size_t)REC_DOUBLES * max_ops) * sizeof(double);
   // A launch that does not fill the GPU (1024 workgroup slots) lasts as long as its largest tree's walk over one tile — ~150 us
   // for a 63-node tree, whatever the batch: four workgroups per tile then
+  if (lds > (size_t)DYN_LDS_MAX_BYTES_K) return hipErrorInvalidValue;
   CovArgs cs = ca;
   cs.csplit = ((long long)ntiles * P < 4096) ? 4 : 1;
   dim3 grid(ntiles, P, cs.csplit), block(256);

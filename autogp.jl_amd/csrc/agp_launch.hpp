@@ -11,8 +11,9 @@ namespace agp {
 
 // ---- agp_kernels.hip -------------------------------------------------------------------------------------------------
 hipError_t kernels_init();          // raises the dynamic-LDS ceiling of the table-carrying covariance kernels (once, agp_init)
-// tile builder: ntiles lower tiles of particles [ca.p_off, ca.p_off + P) (LDS for max_cp per-point tables, stack depth 4 / 8)
-hipError_t launch_cov(hipStream_t st, const CovArgs& ca, int ntiles, int P, int max_cp, int depth);
+// tile builder: ntiles lower tiles of particles [ca.p_off, ca.p_off + P) (LDS for max_cp per-point tables and the node records of
+// programs of up to max_ops nodes, stack depth 4 / 8)
+hipError_t launch_cov(hipStream_t st, const CovArgs& ca, int ntiles, int P, int max_cp, int depth, int max_ops);
 void launch_lag_tables(hipStream_t st, const LagArgs& la, int units, int n_tables);
 hipError_t launch_toep_logpdf(hipStream_t st, const ToepArgs& ta);      // structured value sweep: one workgroup per particle (ta.P)
 void launch_logdt_tiles(hipStream_t st, unsigned ntiles, const double* ts, double* out);

@@ -366,7 +366,7 @@ int predict_core(agp_ctx* c, const PredQuery& q, const Particles& pp, Batch& bt,
     cv.p_off = nf;
     cv.skip_pred_offdiag = want_cov ? 0 : 1;
     cv.i0 = n_hit > 0 ? d_i0 + p0 : nullptr;
-    HIPCHK(c, launch_cov(st, cv, ntiles, Pc - nf, bt.max_cp, bt.max_depth));
+    HIPCHK(c, launch_cov(st, cv, ntiles, Pc - nf, bt.max_cp, bt.max_depth, bt.max_ops));
 
     CholArgs ca = {};
     ca.A = s->A.as<double>(); ca.strideA = strideA; ca.W = s->W.as<double>();
@@ -452,7 +452,7 @@ int predict_core(agp_ctx* c, const PredQuery& q, const Particles& pp, Batch& bt,
         // their other tiles in-kernel come from k_cov_tiles, which reads the rank tables in place)
         CovArgs cp = cv;
         cp.p_off = 0; cp.pred_only = 1; cp.i0 = nullptr;
-        HIPCHK(c, launch_cov(st, cp, ntiles, nf, bt.max_cp, bt.max_depth));
+        HIPCHK(c, launch_cov(st, cp, ntiles, nf, bt.max_cp, bt.max_depth, bt.max_ops));
         ca.n_fused = 0; dcov_s = 0;
       }
       launch_update_schur(dcov_s, 8 * Pg * T, st, ca);
@@ -596,7 +596,7 @@ int predict_logpdf_core(agp_ctx* c, const PredQuery& q, const double* y_pred, co
     const int nf = std::max(0, std::min(Pc, bt.n_fused - p0));
     const int dcov = nf > 0 ? bt.max_depth_fused : 0;
     cv.p_off = nf;
-    HIPCHK(c, launch_cov(st, cv, ntiles, Pc - nf, bt.max_cp, bt.max_depth));
+    HIPCHK(c, launch_cov(st, cv, ntiles, Pc - nf, bt.max_cp, bt.max_depth, bt.max_ops));
 
     CholArgs ca = {};
     ca.A = s->A.as<double>(); ca.strideA = strideA; ca.W = s->W.as<double>();
@@ -1225,7 +1225,7 @@ int agp_cov_matrix(agp_ctx* c, const double* ts, int64_t n, const uint8_t* ops, 
     cv.hdr = s->hdr.as<ProgHdr>(); cv.ops = s->ops.as<uint8_t>(); cv.prm = s->prm.as<double>();
     cv.noise = s->noise.as<double>(); cv.A = s->A.as<double>(); cv.strideA = strideA; cv.P = 1;
     cv.p_off = 0;
-    HIPCHK(c, launch_cov(st, cv, ntiles, 1, bt.max_cp, bt.max_depth));
+    HIPCHK(c, launch_cov(st, cv, ntiles, 1, bt.max_cp, bt.max_depth, bt.max_ops));
     const long long nel = (long long)n * n;
     launch_unpack_dense(st, s->A.as<double>(), (int)n, 0, s->dense.as<double>());
     HIPCHK(c, hipGetLastError());

@@ -366,7 +366,7 @@ int extend_impl(agp_ctx* c, int64_t n, const Particles& pp, double* out_lp, int3
     const int nf = std::max(0, std::min(U, bt.n_fused));
     const int dcov = nf > 0 ? bt.max_depth_fused : 0;
     cv.p_off = nf;
-    EXTCHK(launch_cov(st, cv, nt * (nt + 1) / 2, U - nf, bt.max_cp, bt.max_depth));
+    EXTCHK(launch_cov(st, cv, nt * (nt + 1) / 2, U - nf, bt.max_cp, bt.max_depth, bt.max_ops));
     CholArgs ca = {};
     ca.A = cv.A; ca.strideA = fs.strideA; ca.W = fs.W.as<double>(); ca.wsteps = fs.nt_cap;
     ca.vec = fs.vec.as<double>(); ca.ldv = fs.nt_cap * NB; ca.partial = fs.partial.as<double>(); ca.ntp = fs.nt_cap;

@@ -31,7 +31,7 @@ EXPORTED_SYMBOLS = [
     "agp_shard_range", "agp_comm_get_unique_id", "agp_comm_init_rank", "agp_comm_info", "agp_init_multi", "agp_set_data_multi",
     "agp_allgather_logweights", "agp_allgather_logweights_device", "agp_logpdf_batch_multi", "agp_logpdf_batch_extend_multi",
     "agp_debug_compact_shards", "agp_logpdf_batch_extend", "agp_extend_stats", "agp_extend_reset", "agp_extend_reserve",
-    "agp_predict_reuse_stats", "agp_grad_reuse_stats", "agp_set_factor_cache", "agp_wait", "agp_comm_count", "agp_get_lag_stats", "agp_get_lattice_stats", "agp_get_compact_stats", "agp_set_lattice", "agp_probe_lattice", "agp_set_reference_arithmetic", "agp_shard_plan", "agp_get_coalesce_timing", "agp_set_lag_tables", "agp_set_grad_lag_domain", "agp_get_grad_lag_domain_stats", "agp_get_grad_toeplitz_stats", "agp_get_grad_structured_stats", "agp_get_predict_structured_stats", "agp_get_toeplitz_stats", "agp_set_lag_rank_tables", "agp_get_lag_rank_stats", "agp_get_lag_predict_stats", "agp_get_poison_stats",
+    "agp_predict_reuse_stats", "agp_grad_reuse_stats", "agp_set_factor_cache", "agp_wait", "agp_comm_count", "agp_get_lag_stats", "agp_get_lattice_stats", "agp_get_compact_stats", "agp_set_lattice", "agp_probe_lattice", "agp_probe_program", "agp_get_eval_stats", "agp_set_reference_arithmetic", "agp_shard_plan", "agp_get_coalesce_timing", "agp_set_lag_tables", "agp_set_grad_lag_domain", "agp_get_grad_lag_domain_stats", "agp_get_grad_toeplitz_stats", "agp_get_grad_structured_stats", "agp_get_predict_structured_stats", "agp_get_toeplitz_stats", "agp_set_lag_rank_tables", "agp_get_lag_rank_stats", "agp_get_lag_predict_stats", "agp_get_poison_stats",
     "agp_logpdf_grad_batch_multi", "agp_predict_batch_multi", "agp_extend_stats2", "agp_predict_logpdf_batch",
     "agp_mixture_quantile", "agp_predict_quantile_batch", "agp_infer_gp_sum_batch", "agp_predict_sum_batch",
     "agp_predict_sample_batch", "agp_mixture_moments", "agp_predict_mixture_batch", "agp_get_mixture_stats",
@@ -188,6 +188,8 @@ def load_library(path=None):
     lib.agp_get_poison_stats.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]; lib.agp_get_poison_stats.restype = C.c_int
     lib.agp_set_reference_arithmetic.argtypes = [vp, C.c_int32]; lib.agp_set_reference_arithmetic.restype = C.c_int
     lib.agp_probe_lattice.argtypes = [dp, C.c_int64, i32p, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_int64)]; lib.agp_probe_lattice.restype = C.c_int
+    lib.agp_probe_program.argtypes = [C.POINTER(C.c_uint8), C.c_int32, dp, C.c_int32, i32p, i32p, i32p, i32p]; lib.agp_probe_program.restype = C.c_int
+    lib.agp_get_eval_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]; lib.agp_get_eval_stats.restype = C.c_int
     lib.agp_set_grad_lag_domain.argtypes = [vp, C.c_int32]; lib.agp_set_grad_lag_domain.restype = C.c_int
     lib.agp_set_lag_rank_tables.argtypes = [vp, C.c_int32]; lib.agp_set_lag_rank_tables.restype = C.c_int
     lib.agp_get_lag_rank_stats.argtypes = [vp, C.POINTER(C.c_int64)]; lib.agp_get_lag_rank_stats.restype = C.c_int
@@ -507,6 +509,14 @@ class GPEngine:
         r = C.c_int32(); k = C.c_int64()
         self._check(self._lib.agp_get_lag_stats(self._ctx, C.byref(r), C.byref(k)))
         return bool(r.value), int(k.value)
+
+    def eval_stats(self):
+        """How the particles of the last batch sweep got their covariance tiles (agp_get_eval_stats): dict(one_node, chain, stack:
+        evaluated inside the factorisation kernels as one-node programs / as chains in place / by the stack interpreter; prebuilt:
+        tiles from the tile builder; prebuilt_chain: the multi-node chains among those, which the builder evaluates without a stack)."""
+        out = (C.c_int64 * 5)()
+        self._check(self._lib.agp_get_eval_stats(self._ctx, out))
+        return dict(zip(("one_node", "chain", "stack", "prebuilt", "prebuilt_chain"), (int(v) for v in out)))
 
     def lattice_stats(self):
         """dict(kind, n_lattice, spacing) of the resident series: kind 0 irregular (general path), 1 regular grid, 2 lattice with
@@ -1078,6 +1088,19 @@ def probe_lattice(ts):
     if rc != 0:
         raise AGPError(f"agp_probe_lattice failed ({rc})")
     return {"kind": int(k.value), "n_lattice": int(g.value), "spacing": float(h.value), "index": idx}
+
+
+def probe_program(node):
+    """agp_probe_program: one kernel tree as a table-driven sweep compiles it (host code, no device).  Returns dict(n_compiled, chain,
+    depth, n_tables): length of the compiled postfix program, whether it is a chain (leaf (leaf binop)*: evaluated without a stack),
+    its evaluation stack need and its table leaves."""
+    ops, prm = _gp.encode(node)
+    prm_arg = prm if prm.size else np.zeros(1)
+    n = C.c_int32(); ch = C.c_int32(); d = C.c_int32(); nt = C.c_int32()
+    rc = load_library().agp_probe_program(_u8(ops), ops.size, _dp(prm_arg), prm.size, C.byref(n), C.byref(ch), C.byref(d), C.byref(nt))
+    if rc != 0:
+        raise AGPError(f"agp_probe_program failed ({rc})")
+    return {"n_compiled": int(n.value), "chain": bool(ch.value), "depth": int(d.value), "n_tables": int(nt.value)}
 
 
 def _quantile_shape(q, x, conv, iters):

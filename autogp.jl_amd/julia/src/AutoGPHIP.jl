@@ -666,6 +666,26 @@ end
 "block until every asynchronously enqueued sweep of the engine has completed (reports a latched in-kernel timeout)"
 wait!(eng::Engine) = check(eng, ccall((:agp_wait, LIB), Cint, (Ptr{Cvoid},), eng.ptr))
 """
+How the particles of the last batch sweep got their covariance tiles (`agp_get_eval_stats`): evaluated inside the factorisation
+kernels as one-node programs / as chains in place / by the stack interpreter, prebuilt by the tile builder, and the multi-node chains
+among the prebuilt.
+"""
+function eval_stats(eng::Engine)
+    out = zeros(Int64, 5)
+    check(eng, ccall((:agp_get_eval_stats, LIB), Cint, (Ptr{Cvoid}, Ptr{Int64}), eng.ptr, out))
+    return (one_node = Int(out[1]), chain = Int(out[2]), stack = Int(out[3]), prebuilt = Int(out[4]), prebuilt_chain = Int(out[5]))
+end
+"""
+One kernel program as a table-driven sweep compiles it (`agp_probe_program`; host code only): `(n_compiled, chain, depth, n_tables)`.
+"""
+function probe_program(ops::Vector{UInt8}, prm::Vector{Float64})
+    n = Ref{Int32}(0); ch = Ref{Int32}(0); d = Ref{Int32}(0); nt = Ref{Int32}(0)
+    rc = ccall((:agp_probe_program, LIB), Cint, (Ptr{UInt8}, Int32, Ptr{Float64}, Int32, Ref{Int32}, Ref{Int32}, Ref{Int32}, Ref{Int32}),
+               ops, length(ops), isempty(prm) ? [0.0] : prm, length(prm), n, ch, d, nt)
+    rc == 0 || error("agp_probe_program failed ($rc)")
+    return (n_compiled = Int(n[]), chain = ch[] != 0, depth = Int(d[]), n_tables = Int(nt[]))
+end
+"""
 Regular time grids (include/autogp_hip.h): `(is_regular, sorted_sweeps)`, the sweeps that read rank tables, the particles whose
 gradient was contracted in the lag domain; the switches take effect at the next `set_data!` (lag tables) / sweep (the others).
 """

@@ -289,6 +289,19 @@ int agp_get_poison_stats(agp_ctx* ctx, int64_t* bytes, int64_t* fills);
 /* The admission test alone, on n time points in any order (host code only: no context, no device): kind as above, the lattice's
  * length and spacing, and per point its lattice index (index_out, nullable; -1 when kind = 0). */
 int agp_probe_lattice(const double* ts, int64_t n, int32_t* kind, int64_t* n_lattice, double* spacing, int64_t* index_out);
+/* One kernel program as a table-driven sweep compiles it (host code only: no context, no device): every maximal stationary subtree
+ * with a transcendental leaf collapses into one table leaf, and the children of every binary node are ordered by the stack need of
+ * the COMPILED tree (+ and x commute exactly, ChangePoint has a swapped form: no bit of the result depends on the order).
+ * n_compiled: nodes of the compiled postfix program; chain: 1 when it has the form leaf (leaf binop)* — every binary node has a
+ * leaf as one operand, so evaluating it needs no stack (one-node programs included); depth: its evaluation stack need; n_tables: its
+ * table leaves.  All outputs nullable.  AGP_ERR_PROGRAM for a malformed program. */
+int agp_probe_program(const uint8_t* ops, int32_t n_ops, const double* prm, int32_t n_prm, int32_t* n_compiled, int32_t* chain,
+                      int32_t* depth, int32_t* n_tables);
+/* How the particles of the last batch sweep (agp_logpdf_batch and its siblings, after deduplication) got their covariance tiles:
+ * out5 = {evaluated inside the factorisation kernels as one-node programs, ... as chains in place (none yet: multi-node programs go
+ * through the stack interpreter), ... by the stack interpreter, prebuilt by the tile builder, and of those prebuilt the multi-node
+ * chains (the builder evaluates them without a stack)}. */
+int agp_get_eval_stats(agp_ctx* ctx, int64_t* out5);
 
 /* Reference arithmetic (AGP_REFERENCE_ARITHMETIC=1 at agp_init, or agp_set_reference_arithmetic(ctx, 1) right after it, before
  * agp_set_data).  The default engine picks, per call, among evaluators (direct, lag / rank tables), schedules (per-column,

@@ -3,7 +3,8 @@ readfirstlane / compare / s_and_saveexec loop the compiler wraps around a buffer
 lane-dependent.  The operand streams of every K-loop are raw buffer loads with the descriptor in SGPRs; when an index the
 descriptor is built from stops being provably wave-uniform the kernels stay correct and silently lose ~10 % (seen once: the
 sub-diagonal kernel's slab loop, 31.1 -> 34.1 us per block column).  Nor may an MFMA block of a K-loop wait for the loads issued
-just before it (fresh_load_waits), and the budgeted kernels keep their scratch size.   python tools/check_isa.py  -> exit status 0 / 1"""
+just before it (fresh_load_waits), the budgeted kernels keep their scratch size, and no loop of the tile builder waits for a
+program byte from global memory (decode_waits).   python tools/check_isa.py  -> exit status 0 / 1"""
 import re, shutil, subprocess, sys, tempfile
 from pathlib import Path
 ROOT = Path(__file__).resolve().parent.parent
@@ -108,6 +109,40 @@ def _kernel_fresh_load_waits(lines):
     return report
 
 
+def decode_waits(asm_text, kernel_frag="k_cov_tiles"):
+    """Loops of the tile builder that wait for an opcode from global memory: {kernel: count}.
+    k_cov_tiles walks a particle's program once per pass, 16 times per tile.  Fetching each opcode with a global_load_ubyte and
+    waiting for it (s_waitcnt vmcnt(0)) before the scalar dispatch — and then once more for the parameters — put two exposed L2 round
+    trips on every node of every pass; the kernel stages the program in LDS once per tile instead.  Counted: a global_load_ubyte
+    inside a loop (the compiler's `in Loop:` / `Loop Header:` annotation) that an s_waitcnt vmcnt(0) of the same loop follows.  Wider
+    loads (the log|dt| table values of programs that use it, rank tables read in place) are not program bytes and may stay."""
+    bad = {}
+    cur, in_loop, pending = None, False, False
+    for l in asm_text.split("\n"):
+        m = re.match(r"^(_Z\w+):", l)
+        if m:
+            cur = m.group(1) if kernel_frag in m.group(1) else None
+            in_loop = pending = False
+            continue
+        if cur is None:
+            continue
+        if re.match(r"^\.LBB\w+:", l) or l.startswith("; %bb."):
+            in_loop = "Loop" in l
+            pending = pending and in_loop
+            continue
+        ins = l.split(";")[0].split()
+        if not ins:
+            continue
+        if ins[0] == "s_endpgm":
+            cur = None
+        elif in_loop and ins[0] == "global_load_ubyte":
+            pending = True
+        elif in_loop and pending and ins[0] == "s_waitcnt" and re.search(r"vmcnt\(0\)", l):
+            bad[cur] = bad.get(cur, 0) + 1
+            pending = False
+    return bad
+
+
 KERNEL_UNITS = ("agp_kernels.hip", "agp_kernels_flow.hip", "agp_kernels_grad.hip")
 # scratch (spilled registers) budget in bytes per kernel: the K-loops of the large-population kernels must not spill at all; the
 # dataflow kernel carries both tile bodies and a few hoisted constants (88 - 96 B); a rewrite of the diagonal K-loop once took it
@@ -131,7 +166,7 @@ def scratch_bytes(asm_text):
 
 def main():
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    bad, over, waits, n_kernels = {}, [], {}, 0
+    bad, over, waits, decode, n_kernels = {}, [], {}, {}, 0
     with tempfile.TemporaryDirectory() as td:
         jobs = []
         for u in KERNEL_UNITS:
@@ -144,6 +179,7 @@ def main():
             txt = out.read_text()
             bad.update(waterfalled_accesses(txt))
             waits.update(fresh_load_waits(txt))
+            decode.update(decode_waits(txt))
             sb = scratch_bytes(txt)
             n_kernels += len(sb)
             for k, v in sb.items():
@@ -156,9 +192,11 @@ def main():
         print("register spills over budget:", o)
     for k, v in waits.items():
         print(f"MFMA block waits on loads just issued (vmcnt {' '.join(map(str, v))}): {k}")
-    if bad or over or waits:
+    for k, v in decode.items():
+        print(f"{v} loops wait for an opcode from global memory: {k}")
+    if bad or over or waits or decode:
         return 1
-    print(f"no buffer access inside a waterfall loop, no MFMA block waiting on a fresh load, spills within budget ({n_kernels} kernels of {', '.join(KERNEL_UNITS)})")
+    print(f"no buffer access inside a waterfall loop, no MFMA block waiting on a fresh load, no opcode fetched from global memory in a loop of the tile builder, spills within budget ({n_kernels} kernels of {', '.join(KERNEL_UNITS)})")
     return 0
 
 
