@@ -379,6 +379,24 @@ __host__ __device__ inline SeriesGradLds series_grad_lds(int n, int n_ops, int n
   return m;
 }
 
+// Predictive twin (k_series_predict, agp_predict_series_batch): the value kernel's arguments, every series' own query times and
+// the particle-major outputs.
+struct SeriesPredArgs : SeriesArgs {
+  const long long* q_off;    // [S + 1] series s predicts at ts_pred[q_off[s] .. q_off[s + 1])
+  const double* ts_pred;
+  const double* noise_pred;  // [P]
+  const long long* out_off;  // [P + 1] particle p's block in out_mean / out_var
+  double* out_mean;          // [out_off[P]]
+  double* out_var;
+};
+// LDS map of the predictive kernel: the value kernel's, array for array — the finished query blocks live in registers, the query
+// times come straight from memory, and sigma_cp of a wave's current 16 query times sits in entries SERIES_QSLOT + 16 w .. + 15 of
+// every per-point table, past the at most SERIES_MAX_N entries a series uses.  So the need, and with it the number of ChangePoint
+// tables that fit, is the value entry's.  n = 0 (the prior predictive) is a map without points or blocks.
+constexpr int SERIES_QSLOT = 192;
+static_assert(SERIES_QSLOT >= SERIES_MAX_N && SERIES_QSLOT + 4 * 16 <= 256, "four waves' query entries behind the series' own");
+__host__ __device__ inline SeriesLds series_pred_lds(int n, int n_ops, int n_prm, int n_cp) { return series_lds(n, n_ops, n_prm, n_cp); }
+
 // Arguments of the probe instantiation k_series_logpdf<D, true> (agp_debug_series_factor): caller matrices of ONE size take the place
 // of series, programs and noise; the LDS map is series_lds(n, 0, 0, 0); workgroup b factors matrix b.
 struct SeriesProbeArgs {

@@ -1,4 +1,5 @@
-// Kernel translation unit 3: the small-matrix value kernel and its value-and-gradient twin (agp_series_kernel.hpp), behind agp_launch.hpp.
+// Kernel translation unit 3: the small-matrix value kernel, its value-and-gradient twin and its predictive twin (agp_series_kernel.hpp),
+// behind agp_launch.hpp.
 #include "agp_launch.hpp"
 #include "agp_series_kernel.hpp"
 
@@ -8,7 +9,8 @@ hipError_t kernels_init_series() {
   const void* fns[] = {reinterpret_cast<const void*>(&k_series_logpdf<4>), reinterpret_cast<const void*>(&k_series_logpdf<8>),
                        reinterpret_cast<const void*>(&k_series_logpdf<4, true>),
                        reinterpret_cast<const void*>(&k_series_logpdf_grad<4, 16>), reinterpret_cast<const void*>(&k_series_logpdf_grad<4, 64>),
-                       reinterpret_cast<const void*>(&k_series_logpdf_grad<8, 64>)};
+                       reinterpret_cast<const void*>(&k_series_logpdf_grad<8, 64>),
+                       reinterpret_cast<const void*>(&k_series_predict<4>), reinterpret_cast<const void*>(&k_series_predict<8>)};
   for (const void* f : fns) {
     hipFuncAttributes fa;
     hipError_t e = hipFuncGetAttributes(&fa, f);
@@ -32,6 +34,14 @@ hipError_t launch_series_logpdf_grad(hipStream_t st, const SeriesGradArgs& sa, i
   if (tape <= 16) hipLaunchKernelGGL((k_series_logpdf_grad<4, 16>), dim3(grid), dim3(256), lds_bytes, st, sa);
   else if (depth <= 4) hipLaunchKernelGGL((k_series_logpdf_grad<4, 64>), dim3(grid), dim3(256), lds_bytes, st, sa);
   else hipLaunchKernelGGL((k_series_logpdf_grad<8, 64>), dim3(grid), dim3(256), lds_bytes, st, sa);
+  return hipGetLastError();
+}
+
+hipError_t launch_series_predict(hipStream_t st, const SeriesPredArgs& sa, int grid, int depth, size_t lds_bytes) {
+  if (grid <= 0) return hipSuccess;
+  if (lds_bytes > (size_t)SERIES_LDS_BYTES) return hipErrorInvalidValue;
+  if (depth <= 4) hipLaunchKernelGGL(k_series_predict<4>, dim3(grid), dim3(256), lds_bytes, st, sa);
+  else hipLaunchKernelGGL(k_series_predict<8>, dim3(grid), dim3(256), lds_bytes, st, sa);
   return hipGetLastError();
 }
 

@@ -73,13 +73,15 @@ void launch_lag_grad(hipStream_t st, int P, size_t lds, const GradArgs& ga);
 void launch_grad_finish(hipStream_t st, int P, const GradArgs& ga);
 
 // ---- agp_kernels_series.hip ------------------------------------------------------------------------------------------
-hipError_t kernels_init_series();   // raises the dynamic-LDS ceiling of k_series_logpdf / k_series_logpdf_grad to the whole 160 KiB (once, agp_init)
+hipError_t kernels_init_series();   // raises the dynamic-LDS ceiling of k_series_logpdf / k_series_logpdf_grad / k_series_predict to the whole 160 KiB (once, agp_init)
 // small-matrix value kernel: one workgroup per entry of sa.wg (`grid` of them), evaluation-stack depth 4 / 8, lds_bytes = the largest
 // SeriesLds total of the launch's particles
 hipError_t launch_series_logpdf(hipStream_t st, const SeriesArgs& sa, int grid, int depth, size_t lds_bytes);
 // value-and-gradient twin: tape = nodes of the reverse-mode tape (16 / 64); the evaluation-stack depth is the value kernel's for the same
 // program (a tree of <= 16 nodes never needs more than 4), lds_bytes = the largest SeriesGradLds total of the launch's particles
 hipError_t launch_series_logpdf_grad(hipStream_t st, const SeriesGradArgs& sa, int grid, int depth, int tape, size_t lds_bytes);
+// predictive twin (k_series_predict): depth as for the value kernel, lds_bytes = the largest series_pred_lds total of the launch's particles
+hipError_t launch_series_predict(hipStream_t st, const SeriesPredArgs& sa, int grid, int depth, size_t lds_bytes);
 // its probe instantiation on caller matrices: workgroup b factors matrix b of `grid`, lds_bytes = series_lds(sa.n, 0, 0, 0).total doubles
 hipError_t launch_series_probe(hipStream_t st, const SeriesProbeArgs& sa, int grid, size_t lds_bytes);
 

@@ -1,8 +1,10 @@
 // agp_logpdf_series_batch: many SHORT series, each with its own particles, scored in one call by the small-matrix value kernel
 // (agp_series_kernel.hpp: one workgroup per particle, covariance + Cholesky + forward solve + value in LDS), and
 // agp_logpdf_grad_series_batch, its value-and-gradient twin (k_series_logpdf_grad: L^-T, alpha and the contraction with dK / d theta
-// behind the value, same workgroup, same LDS).  Both are one host function — validation, series upload, launch classes and the
-// value outputs are the same statements — with the gradient as an option.  Stateless: the series
+// behind the value, same workgroup, same LDS), and agp_predict_series_batch, its predictive twin (k_series_predict: posterior mean and
+// marginal variance at every series' own query times from the factor the value has just left in LDS).  All three are one host
+// function — validation, series upload, launch classes and the value outputs are the same statements — with the gradient and the
+// prediction as options.  Stateless: the series
 // travel with the call; the resident series, its tables, the factor store, the coalescer and every counter of the context are
 // neither read nor changed — only a workspace slot (stream, staging buffers) is borrowed, as in every batch entry.
 #include "agp_host.hpp"
@@ -16,15 +18,28 @@ namespace {
 // of their size share a CU's 160 KiB — 4 (n <= ~80), 2 (n <= ~128) or 1.
 int lds_class(size_t bytes) { return bytes <= (size_t)SERIES_LDS_BYTES / 4 ? 0 : bytes <= (size_t)SERIES_LDS_BYTES / 2 ? 1 : 2; }
 
-// go = null: values only.  go: also out_grad (agp_logpdf_grad_batch's layout) and out_gnoise.
+// The prediction of agp_predict_series_batch: every series' query times and the particle-major outputs (host).
+struct SeriesPredOut {
+  const int64_t* q_off;      // [S + 1]
+  const double* ts_pred;
+  double* mean;              // [off[P]]
+  double* var;
+  int64_t* off;              // [P + 1], written by the entry
+};
+
+// go = null, po = null: values only.  go: also out_grad (agp_logpdf_grad_batch's layout) and out_gnoise.  po: also the posterior at
+// the series' query times; out_logpdf may then be null (pp.noise_pred null: the particle's own noise).
 int series_batch(agp_ctx* c, int32_t S, const int64_t* pt_off, const double* ts, const double* xs, const Particles& pp,
-                 const int32_t* series, double* out_logpdf, int32_t* out_info, const GradOut* go = nullptr) {
+                 const int32_t* series, double* out_logpdf, int32_t* out_info, const GradOut* go = nullptr,
+                 const SeriesPredOut* po = nullptr) {
   const int P = pp.P;
   char buf[256];
   if (!c) return fail(nullptr, AGP_ERR_ARG, "null context");
   if (S < 0 || P < 0) return fail(c, AGP_ERR_ARG, "negative number of series or particles");
   if (P == 0) return AGP_OK;
-  if (!pt_off || !ts || !xs || !series || !pp.complete() || !out_logpdf || !out_info) return fail(c, AGP_ERR_ARG, "null pointer argument");
+  if (!pt_off || !ts || !xs || !series || !pp.complete() || (!out_logpdf && !po) || !out_info) return fail(c, AGP_ERR_ARG, "null pointer argument");
+  if (po && (!po->q_off || !po->ts_pred || !po->mean || !po->var || !po->off))
+    return fail(c, AGP_ERR_ARG, "null pointer argument (q_off, ts_pred, out_mean, out_var or out_off)");
   const size_t n_prm_total = go ? (size_t)std::max(0, pp.prm_off[P]) : 0;
   if (go && !go->gnoise) return fail(c, AGP_ERR_ARG, "null pointer argument (out_grad_noise)");
   if (go && !go->grad && pp.prm_off[P] > 0) return fail(c, AGP_ERR_ARG, "null pointer argument (out_grad with parameters present)");
@@ -38,6 +53,19 @@ int series_batch(agp_ctx* c, int32_t S, const int64_t* pt_off, const double* ts,
       snprintf(buf, sizeof buf, "series %d has %lld points, more than AGP_SERIES_MAX_N (%d)", (int)s, (long long)(pt_off[s + 1] - pt_off[s]),
                AGP_SERIES_MAX_N);
       return fail(c, AGP_ERR_ARG, buf);
+    }
+  }
+  if (po) {
+    if (S > 0 && po->q_off[0] != 0) return fail(c, AGP_ERR_ARG, "q_off[0] must be 0 (series 0)");
+    for (int32_t s = 0; s < S; ++s) {
+      if (po->q_off[s + 1] < po->q_off[s]) {
+        snprintf(buf, sizeof buf, "series %d: q_off decreases (%lld after %lld)", (int)s, (long long)po->q_off[s + 1], (long long)po->q_off[s]);
+        return fail(c, AGP_ERR_ARG, buf);
+      }
+      if (po->q_off[s + 1] - po->q_off[s] > (int64_t)1 << 30) {
+        snprintf(buf, sizeof buf, "series %d has %lld query points, more than 2^30", (int)s, (long long)(po->q_off[s + 1] - po->q_off[s]));
+        return fail(c, AGP_ERR_ARG, buf);
+      }
     }
   }
   for (int p = 0; p < P; ++p)
@@ -67,15 +95,18 @@ int series_batch(agp_ctx* c, int32_t S, const int64_t* pt_off, const double* ts,
   // entry picks for the same program (<= 16 nodes never need more than 4), so that the value's bits are that entry's
   std::vector<int> len((size_t)P);
   std::vector<size_t> need((size_t)P);
+  std::vector<int64_t> nq((size_t)P, 0);      // query points of the particle's series (prediction)
   std::vector<int32_t> list[3][3];
   for (int p = 0; p < P; ++p) {
     if (bt.order[(size_t)p] != p) return fail(c, AGP_ERR_HOST, "internal error: compiled batch out of order");
     const ProgHdr& h = bt.hdr[(size_t)p];
     const int n = (int)(pt_off[series[p] + 1] - pt_off[series[p]]);
     len[(size_t)p] = n;
-    if (n == 0) continue;
+    if (po) nq[(size_t)p] = po->q_off[series[p] + 1] - po->q_off[series[p]];
+    if (n == 0 && nq[(size_t)p] == 0) continue;      // (an empty series is launched for its prior predictive only)
     const int m_total = go ? series_grad_lds(n, h.n_ops, h.n_prm, h.n_cp, bt.ghdr[(size_t)p].n_ops, bt.ghdr[(size_t)p].n_prm).total
-                           : series_lds(n, h.n_ops, h.n_prm, h.n_cp).total;
+                        : po ? series_pred_lds(n, h.n_ops, h.n_prm, h.n_cp).total
+                             : series_lds(n, h.n_ops, h.n_prm, h.n_cp).total;
     need[(size_t)p] = sizeof(double) * (size_t)m_total;
     if (need[(size_t)p] > (size_t)SERIES_LDS_BYTES) {
       snprintf(buf, sizeof buf, "particle %d: %d per-point tables (ChangePoint nodes) at %d points need %zu bytes of LDS, more than the "
@@ -97,8 +128,16 @@ int series_batch(agp_ctx* c, int32_t S, const int64_t* pt_off, const double* ts,
   std::vector<int32_t> wg;
   wg.reserve((size_t)P);
   for (auto& ld : list) for (auto& v : ld) wg.insert(wg.end(), v.begin(), v.end());
-  if (wg.empty()) {      // every particle scores an empty series (src/inference_smc_anneal_data.jl:185-187)
-    std::fill(out_logpdf, out_logpdf + P, 0.0); std::fill(out_info, out_info + P, 0);
+  std::vector<long long> ooff;      // out_off: the particle-major layout of the prediction
+  if (po) {
+    ooff.assign((size_t)P + 1, 0);
+    for (int p = 0; p < P; ++p) ooff[(size_t)p + 1] = ooff[(size_t)p] + nq[(size_t)p];
+    std::copy(ooff.begin(), ooff.end(), po->off);
+  }
+  const size_t n_out = po ? (size_t)ooff[(size_t)P] : 0;
+  if (wg.empty()) {      // every particle scores an empty series (src/inference_smc_anneal_data.jl:185-187) and has nothing to predict
+    if (out_logpdf) std::fill(out_logpdf, out_logpdf + P, 0.0);
+    std::fill(out_info, out_info + P, 0);
     if (go) { std::fill(go->gnoise, go->gnoise + P, 0.0); std::fill(go->grad, go->grad + n_prm_total, 0.0); }
     return AGP_OK;
   }
@@ -130,6 +169,15 @@ int series_batch(agp_ctx* c, int32_t S, const int64_t* pt_off, const double* ts,
     HIPCHK(c, s->dgrad.ensure(sizeof(double) * std::max<size_t>(1, n_prm_total)));
     HIPCHK(c, s->dgnoise.ensure(sizeof(double) * (size_t)P));
   }
+  const size_t nqt = po ? (size_t)po->q_off[S] : 0;
+  const size_t o_qoff = (o_wg + sizeof(int32_t) * wg.size() + 7) & ~(size_t)7, o_ooff = o_qoff + sizeof(long long) * ((size_t)S + 1);
+  if (po) {      // tt = [ts | xs | ts_pred]; map = [.. | q_off (int64) | out_off (int64)]; outputs in pred_mean / pred_var
+    HIPCHK(c, s->tt.ensure(sizeof(double) * (2 * std::max<size_t>(1, npts) + std::max<size_t>(1, nqt))));
+    HIPCHK(c, s->map.ensure(o_ooff + sizeof(long long) * ((size_t)P + 1)));
+    HIPCHK(c, s->noise_pred.ensure(sizeof(double) * (size_t)P));
+    HIPCHK(c, s->pred_mean.ensure(sizeof(double) * std::max<size_t>(1, n_out)));
+    HIPCHK(c, s->pred_var.ensure(sizeof(double) * std::max<size_t>(1, n_out)));
+  }
   std::vector<long long> off64(pt_off, pt_off + S + 1);
   PinnedUploads up;
   up.add(s->hdr.p, bt.hdr.data(), sizeof(ProgHdr) * (size_t)P);
@@ -150,6 +198,14 @@ int series_batch(agp_ctx* c, int32_t S, const int64_t* pt_off, const double* ts,
     up.add(s->gprm.p, bt.gprm.data(), sizeof(double) * bt.gprm.size());
     up.add(s->gmap.p, bt.gmap.data(), sizeof(int32_t) * bt.gmap.size());
     up.add(s->goff.p, pp.prm_off, sizeof(int32_t) * (size_t)P);      // the particle's block in out_grad: the caller's own offsets
+  }
+  std::vector<long long> qoff64;
+  if (po) {
+    qoff64.assign(po->q_off, po->q_off + S + 1);
+    up.add(s->map.as<char>() + o_qoff, qoff64.data(), sizeof(long long) * ((size_t)S + 1));
+    up.add(s->map.as<char>() + o_ooff, ooff.data(), sizeof(long long) * ((size_t)P + 1));
+    up.add(s->tt.as<double>() + 2 * npts, po->ts_pred, sizeof(double) * nqt);
+    up.add(s->noise_pred.p, pp.noise_pred ? pp.noise_pred : pp.noise, sizeof(double) * (size_t)P);
   }
   HIPCHK(c, up.flush(s->h_stage, s->up_blob, st));
 
@@ -180,25 +236,38 @@ int series_batch(agp_ctx* c, int32_t S, const int64_t* pt_off, const double* ts,
       for (int32_t p : v) lds = std::max(lds, need[(size_t)p]);
       sa.wg = reinterpret_cast<const int32_t*>(s->map.as<char>() + o_wg) + w0;
       if (go) HIPCHK(c, launch_series_logpdf_grad(st, sa, (int)v.size(), d == 2 ? 8 : 4, d == 0 ? 16 : 64, lds));
-      else HIPCHK(c, launch_series_logpdf(st, sa, (int)v.size(), d == 0 ? 4 : 8, lds));
+      else if (po) {
+        SeriesPredArgs spa = {};
+        static_cast<SeriesArgs&>(spa) = sa;
+        spa.q_off = reinterpret_cast<const long long*>(s->map.as<char>() + o_qoff);
+        spa.out_off = reinterpret_cast<const long long*>(s->map.as<char>() + o_ooff);
+        spa.ts_pred = s->tt.as<double>() + 2 * npts; spa.noise_pred = s->noise_pred.as<double>();
+        spa.out_mean = s->pred_mean.as<double>(); spa.out_var = s->pred_var.as<double>();
+        HIPCHK(c, launch_series_predict(st, spa, (int)v.size(), d == 0 ? 4 : 8, lds));
+      } else HIPCHK(c, launch_series_logpdf(st, sa, (int)v.size(), d == 0 ? 4 : 8, lds));
       w0 += v.size();
     }
   if (prof) HIPCHK(c, hipEventRecord(ev[1], st));
   const size_t out_bytes = sizeof(double) * (size_t)P + sizeof(int32_t) * (size_t)P;
   const size_t o_gn = (out_bytes + 7) & ~(size_t)7, o_gr = o_gn + sizeof(double) * (size_t)P;      // gradient outputs behind [logpdf | info]
-  HIPCHK(c, s->h_out.ensure(go ? o_gr + sizeof(double) * n_prm_total : out_bytes));
+  HIPCHK(c, s->h_out.ensure(go ? o_gr + sizeof(double) * n_prm_total : po ? o_gn + 2 * sizeof(double) * n_out : out_bytes));
   HIPCHK(c, hipMemcpyAsync(s->h_out.p, s->out_lp.p, out_bytes, hipMemcpyDeviceToHost, st));
   if (go) {
     char* ho = static_cast<char*>(s->h_out.p);
     HIPCHK(c, hipMemcpyAsync(ho + o_gn, s->dgnoise.p, sizeof(double) * (size_t)P, hipMemcpyDeviceToHost, st));
     if (n_prm_total > 0) HIPCHK(c, hipMemcpyAsync(ho + o_gr, s->dgrad.p, sizeof(double) * n_prm_total, hipMemcpyDeviceToHost, st));
   }
+  if (po && n_out > 0) {      // [mean | var] behind [logpdf | info]
+    char* ho = static_cast<char*>(s->h_out.p);
+    HIPCHK(c, hipMemcpyAsync(ho + o_gn, s->pred_mean.p, sizeof(double) * n_out, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(ho + o_gn + sizeof(double) * n_out, s->pred_var.p, sizeof(double) * n_out, hipMemcpyDeviceToHost, st));
+  }
   HIPCHK(c, hipStreamSynchronize(st));
   const double* hl = static_cast<const double*>(s->h_out.p);
   const int32_t* hi = reinterpret_cast<const int32_t*>(hl + P);
   for (int p = 0; p < P; ++p) {
-    const bool empty = len[(size_t)p] == 0;      // (never launched)
-    out_logpdf[p] = empty ? 0.0 : hl[p];
+    const bool empty = len[(size_t)p] == 0;      // (never launched, or launched for the prior predictive: the value is 0 either way)
+    if (out_logpdf) out_logpdf[p] = empty ? 0.0 : hl[p];
     out_info[p] = empty ? 0 : hi[p];
     if (go) {
       // (an empty series: zeros; a bad pivot: NaN in the whole block — the kernel wrote them, slot by slot through gmap)
@@ -207,6 +276,11 @@ int series_batch(agp_ctx* c, int32_t S, const int64_t* pt_off, const double* ts,
       go->gnoise[p] = empty ? 0.0 : hgn[p];
       for (int32_t q = pp.prm_off[p]; q < pp.prm_off[p + 1]; ++q) go->grad[q] = empty ? 0.0 : hgr[q];
     }
+  }
+  if (po && n_out > 0) {      // every particle with query points was launched and wrote its whole block
+    const double* hm = reinterpret_cast<const double*>(static_cast<const char*>(s->h_out.p) + o_gn);
+    std::copy(hm, hm + n_out, po->mean);
+    std::copy(hm + n_out, hm + 2 * n_out, po->var);
   }
   if (prof) {
     // agp_get_timing: out[0] = out[2] = the value kernels of the call (covariance, factorisation, solve and value are one kernel)
@@ -287,6 +361,16 @@ int agp_logpdf_grad_series_batch(agp_ctx* c, int32_t S, const int64_t* pt_off, c
   return abi_guard(c, [&] {
     const GradOut go{out_grad, out_grad_noise};
     return series_batch(c, S, pt_off, ts, xs, {P, op_off, ops, prm_off, prm, noise, nullptr}, series, out_logpdf, out_info, &go);
+  });
+}
+
+int agp_predict_series_batch(agp_ctx* c, int32_t S, const int64_t* pt_off, const double* ts, const double* xs, const int64_t* q_off,
+                             const double* ts_pred, int32_t P, const int32_t* series, const int32_t* op_off, const uint8_t* ops,
+                             const int32_t* prm_off, const double* prm, const double* noise, const double* noise_pred, double* out_mean,
+                             double* out_var, int64_t* out_off, double* out_logpdf, int32_t* out_info) {
+  return abi_guard(c, [&] {
+    const SeriesPredOut po{q_off, ts_pred, out_mean, out_var, out_off};
+    return series_batch(c, S, pt_off, ts, xs, {P, op_off, ops, prm_off, prm, noise, noise_pred}, series, out_logpdf, out_info, nullptr, &po);
   });
 }
 

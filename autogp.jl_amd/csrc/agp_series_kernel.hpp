@@ -49,6 +49,15 @@
 // at n = 176 a chain of 4 ChangePoint nodes (9 nodes, 13 parameters, 8 tables) fits, 5 do not.
 // An LDS tape (LdsTape: 8 nodes x 4 x 256 doubles = 64 KiB) would fit only beside short series' blocks; it is not built — see
 // profiles/series_grad_perf.txt.
+//
+// k_series_predict<D> (agp_predict_series_batch) is the value kernel with the posterior at the series' own query times behind it, in the
+// same workgroup and the value kernel's own LDS map (series_pred_lds): stages 1-5 as above, then
+//   P1. the diagonal blocks L(i,i)^-T in place (G1's statements: series_diag_inv_t);
+//   P2. per block of 16 query times, one wave, no workgroup barrier: K21 by the evaluator, VT = K21 L^-T block row by block row on
+//       v_mfma_f64_16x16x4 with the finished blocks in registers, mean = VT beta, var = k(t*,t*) - rowsums(VT^2) + noise_pred
+//       (series_predict_blocks).  sigma_cp at the query times sits in the per-point tables' entries 192 .. 255.
+// The gradient kernel's full Z = L^-T is not formed (n^3 / 3 flops and nb - 1 barrier pairs for n^2 m of work).  An empty series with
+// query points gives the prior predictive (series_prior_predict).  On a bad pivot NaN is written to the particle's whole block.
 #pragma once
 #include <type_traits>
 #include "agp_common.hpp"
@@ -59,11 +68,156 @@
 
 namespace agp {
 
-// The body of every instantiation: stages 1-5 (value kernel, probe, gradient kernel alike — the same statements), and with GS > 0
-// (gradient tape of GS nodes) the stages G1-G5 behind them.
+// G1 / P1: every diagonal block L(i,i) -> L(i,i)^-T in place (the whole block, zeros below the diagonal), one block per wave and
+// pass, column c of L(i,i)^-1 by forward substitution in lane c (the reads of L are broadcasts).  No barrier inside.
+__device__ __forceinline__ void series_diag_inv_t(double* sm, int nb, int w, int l) {
+  for (int i = w; i < nb; i += 4) {
+    double* blk = sm + blk_idx(i, i) * 256;
+    if (l < 16) {
+      double wv[16];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        double s = (r == l) ? 1.0 : 0.0;
+#pragma unroll
+        for (int k = 0; k < r; ++k) s = fma(-blk[k * 16 + r], wv[k], s);
+        wv[r] = s / blk[17 * r];
+      }
+#pragma unroll
+      for (int r = 0; r < 16; ++r) blk[r * 16 + l] = wv[r];      // Z(i,i)[c][r] = W[r][c]: the whole block, zeros below the diagonal
+    }
+  }
+}
+
+// P2: the posterior at the mq query times tq of one particle, from the factor as P1 leaves it (off-diagonal blocks L(i,k), diagonal
+// slots L(i,i)^-T, beta = L^-1 x in avec; nb = 0: the prior).  Query block qb (16 times) belongs to wave qb % 4, which runs its
+// blocks without a workgroup barrier:
+//   sigma_cp of its 16 times -> entries SERIES_QSLOT + 16 w .. of every per-point table (wave-local; stage 2's arithmetic);
+//   for jb = 0 .. nb - 1:  K21(jb) by the evaluator on stage 3's lane map (lane (i = l%16, q = l/16) <-> query i, training points
+//     16 jb + q + 4 e; columns past n: 0), VT(jb) = (K21(jb) - sum_{k<jb} VT(k) L(jb,k)') L(jb,jb)^-T on v_mfma_f64_16x16x4 — a result
+//     register r IS the operand slice s4 = r, so the finished blocks stay in registers (VT[k], statically indexed: the k-loop is
+//     unrolled over the cap's 11 blocks behind wave-uniform guards) — and the lane's share of mean_i = sum_j VT[i][j] beta_j and of
+//     sum_j VT[i][j]^2, ascending in (jb, e);
+//   "block" nb: k(t*_i, t*_i) through the same call of the evaluator, row and column both the query;
+//   the four lane groups of a row in the order ((q0 + q1) + q2) + q3 -> out_mean, out_var = (k** - sum VT^2) + noise_pred.
+// Rows past mq evaluate the last query again and are not written; beta's padding is 0 and VT's columns past n are exactly 0
+// (K21 masked, L's padding identity).
+template <int D>
+__device__ __forceinline__ void series_predict_blocks(const ProgHdr& h, const int* ops, const double* prm, double* sig, const double* tpt,
+                                                      const double* avec, const double* etab, const double* sm, int n, int nb,
+                                                      const double* tq, int mq, double noise_pred, double* om, double* ov) {
+  constexpr int E = 4, EV = D > 4 ? 2 : 4, NBMAX = SERIES_MAX_N / 16;
+  static_assert(NBMAX * 16 == SERIES_MAX_N, "the cap is whole blocks");
+  const int tid = threadIdx.x, l = tid & 63, w = tid >> 6, l15 = l & 15, lq = l >> 4;
+  const int slot = SERIES_QSLOT + 16 * w + l15;
+  for (int qb = w; qb * 16 < mq; qb += 4) {
+    const int qi = qb * 16 + l15;
+    const double t = tq[qi < mq ? qi : mq - 1];
+    if (h.n_cp > 0) {
+      if (l < 16) {
+        int q = 0, c = 0;
+        for (int ip = 0; ip < h.n_ops; ++ip) {
+          const int o = ops[ip];
+          if (o == OP_CP || o == OP_CP_SWAP) {
+            const double loc = prm[q], sc = prm[q + 1];
+            sig[c * 256 + slot] = 0.5 * (1.0 + tanh((loc - t) / sc));
+            ++c;
+          }
+          q += prm_count(o);
+        }
+      }
+      __builtin_amdgcn_wave_barrier();      // (LDS operations of one wave complete in order: its own lanes' entries, no workgroup barrier)
+    }
+    d4 VT[NBMAX];
+#pragma unroll
+    for (int k = 0; k < NBMAX; ++k) VT[k] = d4{0.0, 0.0, 0.0, 0.0};
+    double ms = 0.0, ss = 0.0, kd = 0.0;
+    for (int jb = 0; jb <= nb; ++jb) {
+      const bool self = jb == nb;
+      double out[E];
+      int ci[E];
+#pragma unroll
+      for (int e = 0; e < E; ++e) ci[e] = self ? slot : jb * 16 + lq + 4 * e;
+      // (the deep stack takes its four elements two at a time: its registers and the finished blocks' share one budget)
+#pragma unroll
+      for (int e0 = 0; e0 < E; e0 += EV) {
+        double tr[EV], tc[EV], lt[EV], o2[EV];
+        int ri[EV], c2[EV];
+#pragma unroll
+        for (int e = 0; e < EV; ++e) {
+          tr[e] = t;
+          ri[e] = slot;
+          tc[e] = self ? t : tpt[ci[e0 + e]];
+          c2[e] = ci[e0 + e];
+          lt[e] = 0.0;
+        }
+        eval_program<D, EV, 0>(h, ops, prm, sig, tr, tc, ri, c2, lt, o2, etab);
+#pragma unroll
+        for (int e = 0; e < EV; ++e) out[e0 + e] = o2[e];
+      }
+      if (self) { kd = out[0]; break; }
+      d4 acc = d4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+      for (int k = 0; k < NBMAX - 1; ++k)
+        if (k < jb) {
+          const double* lb = sm + blk_idx(jb, k) * 256;
+          double fa[4];
+#pragma unroll
+          for (int s4 = 0; s4 < 4; ++s4) fa[s4] = lb[64 * s4 + l];
+#pragma unroll
+          for (int s4 = 0; s4 < 4; ++s4) acc = mfma(fa[s4], VT[k][s4], acc);      // += VT(k) L(jb,k)'
+        }
+      const double* zb = sm + blk_idx(jb, jb) * 256;
+      double fw[4];
+#pragma unroll
+      for (int s4 = 0; s4 < 4; ++s4) fw[s4] = zb[l15 * 16 + 4 * s4 + lq];      // L(jb,jb)^-1 (l15, 4 s4 + lq), as in G2
+      d4 res = d4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+      for (int s4 = 0; s4 < 4; ++s4) res = mfma(fw[s4], (ci[s4] < n ? out[s4] : 0.0) - acc[s4], res);
+#pragma unroll
+      for (int k = 0; k < NBMAX; ++k)
+        if (k == jb) VT[k] = res;
+#pragma unroll
+      for (int e = 0; e < E; ++e) {
+        ms = fma(res[e], avec[ci[e]], ms);
+        ss = fma(res[e], res[e], ss);
+      }
+    }
+    const double mean = ((__shfl(ms, l15) + __shfl(ms, l15 + 16)) + __shfl(ms, l15 + 32)) + __shfl(ms, l15 + 48);
+    const double sq = ((__shfl(ss, l15) + __shfl(ss, l15 + 16)) + __shfl(ss, l15 + 32)) + __shfl(ss, l15 + 48);
+    if (l < 16 && qi < mq) {
+      om[qi] = mean;
+      ov[qi] = (kd - sq) + noise_pred;
+    }
+  }
+}
+
+// The prior predictive of a particle on an EMPTY series (n = 0, mq > 0 query times): mean 0, var = k(t*, t*) + noise_pred — the
+// read-out above with no block.  Stages its own program (stage 1's statements without the points).
+template <int D>
+__device__ __forceinline__ void series_prior_predict(const SeriesPredArgs& a, int p, double* smem) {
+  const int tid = threadIdx.x;
+  const ProgHdr h = a.hdr[p];
+  const SeriesLds m = series_pred_lds(0, h.n_ops, h.n_prm, h.n_cp);
+  double* etab = smem + m.o_etab;
+  double* prm = smem + m.o_prm;
+  int* ops = reinterpret_cast<int*>(smem + m.o_ops);
+  double* sig = smem + m.o_sig;
+  if (AGP_EXP_TABLE && tid < AGP_EXP_TAB_N) etab[tid] = fm::c_exp_tab[tid];
+  for (int i = tid; i < h.n_prm + 2; i += 256) prm[i] = a.prm[h.prm_off + i];
+  for (int i = tid; i < h.n_ops; i += 256) ops[i] = (int)a.ops[h.op_off + i];
+  __syncthreads();
+  const long long q0 = a.q_off[a.series[p]];
+  const int mq = (int)(a.q_off[a.series[p] + 1] - q0);
+  series_predict_blocks<D>(h, ops, prm, sig, smem, smem, etab, smem + m.o_blk, 0, 0, a.ts_pred + q0, mq, a.noise_pred[p],
+                           a.out_mean + a.out_off[p], a.out_var + a.out_off[p]);
+}
+
+// The body of every instantiation: stages 1-5 (value kernel, probe, gradient kernel, predictive kernel alike — the same statements),
+// with GS > 0 (gradient tape of GS nodes) the stages G1-G5 behind them, with SeriesPredArgs the stages P1-P2.
 template <int D, bool PROBE, int GS, class ArgsT>
 __device__ __forceinline__ void series_body(const ArgsT& a, double* smem) {
   constexpr int E = 4;
+  constexpr bool PRED = std::is_same_v<ArgsT, SeriesPredArgs>;
   const int tid = threadIdx.x, l = tid & 63, w = tid >> 6, l15 = l & 15, lq = l >> 4;
   int p, n;
   long long o0 = 0;
@@ -76,13 +230,17 @@ __device__ __forceinline__ void series_body(const ArgsT& a, double* smem) {
     o0 = a.pt_off[sidx];
     n = (int)(a.pt_off[sidx + 1] - o0);
   }
-  if (n <= 0 || n > SERIES_MAX_N) {      // (the host answers empty series itself and refuses long ones: never launched)
+  if (n <= 0 || n > SERIES_MAX_N) {      // (the host answers empty series itself and refuses long ones: never launched ...
+    if constexpr (PRED) {                // ... but for the prior predictive of an empty series)
+      if (n == 0) series_prior_predict<D>(a, p, smem);
+    }
     if (tid == 0) { a.out_lp[p] = 0.0; a.out_info[p] = 0; }
     return;
   }
   const ProgHdr h = [&]() -> ProgHdr { if constexpr (PROBE) return ProgHdr{}; else return a.hdr[p]; }();
   const auto m = [&]() {
     if constexpr (GS > 0) return series_grad_lds(n, h.n_ops, h.n_prm, h.n_cp, a.ghdr[p].n_ops, a.ghdr[p].n_prm);
+    else if constexpr (PRED) return series_pred_lds(n, h.n_ops, h.n_prm, h.n_cp);
     else return series_lds(n, h.n_ops, h.n_prm, h.n_cp);
   }();
   const int nb = m.nb, np = m.np;
@@ -407,6 +565,27 @@ __device__ __forceinline__ void series_body(const ArgsT& a, double* smem) {
     if (tid < np) a.out_alpha[(long long)p * np + tid] = avec[tid];
   }
 
+  if constexpr (PRED) {
+    // ================= prediction: mean = K21 K11^-1 x = VT beta, var = diag(K22) - rowsums(VT^2) + noise_pred, VT = K21 L^-T =================
+    // LDS now: as the gradient finds it — L in the packed blocks, beta in avec (padding: 0), tpt, the program and its tables.
+    const int sidx = a.series[p];
+    const long long q0 = a.q_off[sidx];
+    const int mq = (int)(a.q_off[sidx + 1] - q0);
+    if (mq <= 0) return;
+    double* om = a.out_mean + a.out_off[p];
+    double* ov = a.out_var + a.out_off[p];
+    if (tid == 0) rvec[0] = (double)bad;      // (wave 0 keeps the first bad pivot; rvec is dead)
+    // ---- P1. the diagonal blocks L(i,i)^-T in place (G1's statements; the log-det has been read) ----
+    series_diag_inv_t(sm, nb, w, l);
+    __syncthreads();
+    if (rvec[0] != 0.0) {      // a bad pivot: NaN in the particle's whole block (the value is NaN already), nothing else
+      for (int q = tid; q < mq; q += 256) { om[q] = __builtin_nan(""); ov[q] = __builtin_nan(""); }
+      return;
+    }
+    // ---- P2. query blocks, wave by wave ----
+    series_predict_blocks<D>(h, ops, prm, sig, tpt, avec, etab, sm, n, nb, a.ts_pred + q0, mq, a.noise_pred[p], om, ov);
+  }
+
   if constexpr (GS > 0) {
     // ================= gradient: d logpdf / d theta = sum_ab G_ab dK_ab / d theta, G = 1/2 (alpha alpha' - K^-1); d / d noise = tr G =================
     // LDS now: L in the packed blocks (diagonal blocks: zero above the diagonal; rows / columns past n: identity), beta = L^-1 x in
@@ -454,21 +633,7 @@ __device__ __forceinline__ void series_body(const ArgsT& a, double* smem) {
     // ---- G1. Z = L^-T in place, block Z(j,i) (j <= i) in the slot of lower block (i,j), column-major: K^-1 = Z Z' then contracts
     //      over natural (conflict-free) LDS reads exactly like L L' does.  First the diagonal: Z(i,i) = L(i,i)^-T, one block per wave
     //      and pass, column c of L(i,i)^-1 by forward substitution in lane c (the reads of L are broadcasts) ----
-    for (int i = w; i < nb; i += 4) {
-      double* blk = sm + blk_idx(i, i) * 256;
-      if (l < 16) {
-        double wv[16];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          double s = (r == l) ? 1.0 : 0.0;
-#pragma unroll
-          for (int k = 0; k < r; ++k) s = fma(-blk[k * 16 + r], wv[k], s);
-          wv[r] = s / blk[17 * r];
-        }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) blk[r * 16 + l] = wv[r];      // Z(i,i)[c][r] = W[r][c]: the whole block, zeros below the diagonal
-      }
-    }
+    series_diag_inv_t(sm, nb, w, l);
     __syncthreads();
     // ---- G2. column i of Z (slot row i): Z(j,i) = -[sum_{k=j}^{i-1} Z(j,k) L(i,k)'] L(i,i)^-T, j < i.  Reads row i of L (slots (i,k))
     //      and finished columns k < i of Z (slots (k,j)); its results replace row i of L, so they wait in registers until every
@@ -592,6 +757,14 @@ template <int D, int GS>
 __global__ __launch_bounds__(256, 2) void k_series_logpdf_grad(SeriesGradArgs a) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   series_body<D, false, GS>(a, smem);
+}
+
+// Posterior mean and marginal variance of one (series, particle) pair at the series' own query times by one workgroup, behind the
+// value and in the value kernel's LDS (agp_predict_series_batch).
+template <int D>
+__global__ __launch_bounds__(256, 2) void k_series_predict(SeriesPredArgs a) {
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  series_body<D, false, 0>(a, smem);
 }
 
 }  // namespace agp

@@ -37,6 +37,7 @@ EXPORTED_SYMBOLS = [
     "agp_predict_sample_batch", "agp_mixture_moments", "agp_predict_mixture_batch", "agp_get_mixture_stats",
     "agp_remove_data", "agp_get_remove_stats", "agp_set_remove_update", "agp_remove_data_multi",
     "agp_debug_factor_batch", "agp_logpdf_series_batch", "agp_debug_series_factor", "agp_logpdf_grad_series_batch",
+    "agp_predict_series_batch",
 ]
 COMM_ID_BYTES = 128
 SERIES_MAX_N = 176      # AGP_SERIES_MAX_N of include/autogp_hip.h: the longest series of logpdf_series_batch
@@ -105,6 +106,9 @@ def load_library(path=None):
     lib.agp_logpdf_series_batch.restype = C.c_int
     lib.agp_logpdf_grad_series_batch.argtypes = [vp, C.c_int32, C.POINTER(C.c_int64), dp, dp, C.c_int32, ip, ip, u8p, ip, dp, dp, dp, dp, dp, ip]
     lib.agp_logpdf_grad_series_batch.restype = C.c_int
+    lib.agp_predict_series_batch.argtypes = [vp, C.c_int32, C.POINTER(C.c_int64), dp, dp, C.POINTER(C.c_int64), dp, C.c_int32, ip, ip, u8p,
+                                             ip, dp, dp, dp, dp, dp, C.POINTER(C.c_int64), dp, ip]
+    lib.agp_predict_series_batch.restype = C.c_int
     lib.agp_logpdf_grad_batch.argtypes = [vp, C.c_int64, C.c_int32, ip, u8p, ip, dp, dp, dp, dp, dp, ip]
     lib.agp_logpdf_grad_batch.restype = C.c_int
     lib.agp_logpdf_grad.argtypes = [vp, C.c_int64, u8p, C.c_int32, dp, C.c_int32, C.c_double, dp, dp, dp, ip]
@@ -266,6 +270,28 @@ def series_call_args(series, nodes, noises, series_index, programs=None):
     if sidx.shape != (P,):
         raise ValueError("one series index per particle required")
     return pt_off, ts, xs, programs, P, noises, sidx
+
+
+def pack_queries(queries, n_series, noise_pred=None, P=None):
+    """The query side of predict_series_batch: (q_off int64[S+1], ts_pred, noise_pred or None) from one vector of query times per
+    series (a vector may be empty).  Raises ValueError when the number of query vectors differs from the number of series, when one
+    is not 1-D, or when noise_pred is not one value per particle — before any library call."""
+    if len(queries) != n_series:
+        raise ValueError(f"one vector of query times per series required ({len(queries)} for {n_series} series)")
+    q_off = np.zeros(n_series + 1, dtype=np.int64)
+    parts = []
+    for s, q in enumerate(queries):
+        q = _f64(q)
+        if q.ndim != 1:
+            raise ValueError(f"series {s}: the query times must be a vector")
+        q_off[s + 1] = q_off[s] + q.shape[0]
+        parts.append(q)
+    ts_pred = np.ascontiguousarray(np.concatenate(parts)) if parts else np.zeros(0)
+    if noise_pred is not None:
+        noise_pred = _f64(noise_pred)
+        if noise_pred.shape != (P,):
+            raise ValueError("one noise_pred per particle required")
+    return q_off, ts_pred, noise_pred
 
 
 def check_remove_indexes(indexes, n_max):
@@ -466,6 +492,39 @@ class GPEngine:
             p = int(np.argmax(info > 0))
             raise PosDefException(int(info[p]), p)
         return out, [grad[prm_off[i]:prm_off[i + 1]] for i in range(P)], gn, info
+
+    def predict_series_batch(self, series, queries, nodes, noises, series_index, noise_pred=None, want_logpdf=False, check=True,
+                             programs=None):
+        """agp_predict_series_batch: forecasts of many short series in one fused launch — logpdf_series_batch's predictive twin, same
+        series / particle arguments and statelessness.  queries[s] holds series s's own query times; particle p predicts on
+        series[series_index[p]]: mean = K21 K11^-1 x, var = diag(K22 - K21 K11^-1 K12) + noise_pred[p] (None: the particle's noise).
+        Returns (means, vars, info), or (means, vars, logpdf, info) with want_logpdf (the training log marginal likelihood,
+        bit-identical to logpdf_series_batch's); means[p] / vars[p] are views of length len(queries[series_index[p]]) into one
+        particle-major array, so np.stack of the adjacent particles of one series is the block mixture_quantile takes."""
+        pt_off, ts, xs, (op_off, ops, prm_off, prm), P, noises, sidx = series_call_args(series, nodes, noises, series_index, programs)
+        S = pt_off.shape[0] - 1
+        q_off, ts_pred, noise_pred = pack_queries(queries, S, noise_pred, P)
+        m_s = np.diff(q_off)
+        total = int(sum(m_s[i] for i in sidx if 0 <= i < S))      # (an index outside is the library's to report)
+        mean = np.empty(max(1, total)); var = np.empty(max(1, total))
+        out_off = np.zeros(P + 1, dtype=np.int64)
+        lp = np.empty(P, dtype=np.float64) if want_logpdf else None
+        info = np.empty(P, dtype=np.int32)
+        ts_arg = ts if ts.size else np.zeros(1)
+        xs_arg = xs if xs.size else np.zeros(1)
+        tq_arg = ts_pred if ts_pred.size else np.zeros(1)
+        prm_arg = prm if prm.size else np.zeros(1)
+        i64 = C.POINTER(C.c_int64)
+        self._check(self._lib.agp_predict_series_batch(self._ctx, S, pt_off.ctypes.data_as(i64), _dp(ts_arg), _dp(xs_arg),
+                                                       q_off.ctypes.data_as(i64), _dp(tq_arg), P, _ip(sidx), _ip(op_off), _u8(ops),
+                                                       _ip(prm_off), _dp(prm_arg), _dp(noises), _dp(noise_pred), _dp(mean), _dp(var),
+                                                       out_off.ctypes.data_as(i64), _dp(lp), _ip(info)))
+        if check and (info > 0).any():
+            p = int(np.argmax(info > 0))
+            raise PosDefException(int(info[p]), p)
+        means = [mean[out_off[p]:out_off[p + 1]] for p in range(P)]
+        vars_ = [var[out_off[p]:out_off[p + 1]] for p in range(P)]
+        return (means, vars_, lp, info) if want_logpdf else (means, vars_, info)
 
     def logpdf_batch_extend(self, nodes, noises, n=None, check=True, programs=None):
         """agp_logpdf_batch_extend: like logpdf_batch, but the factors stay resident and a later call on a longer

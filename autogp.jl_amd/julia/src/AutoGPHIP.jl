@@ -247,6 +247,44 @@ function logpdf_grad_series_batch(eng::Engine, series::Vector{<:Tuple{Vector{Flo
     return out, grads, gn, info
 end
 
+"Forecasts of many short series in one fused launch (agp_predict_series_batch): `logpdf_series_batch`'s predictive twin, same
+series / particle arguments and statelessness.  `queries[s]` holds series `s`'s own query times; particle `p` predicts on
+`series[series_index[p]]` (1-based): mean = K21 K11^-1 x, var = diag(K22 - K21 K11^-1 K12) + noise_pred[p] (`nothing`: the
+particle's noise).  Returns `(means, vars, logpdf, info)`; `means[p]` / `vars[p]` have the length of the particle's series' query
+vector and `logpdf` is bit-identical to `logpdf_series_batch`'s."
+function predict_series_batch(eng::Engine, series::Vector{<:Tuple{Vector{Float64},Vector{Float64}}}, queries::Vector{Vector{Float64}},
+                              nodes::Vector{<:GP.Node}, noises::Vector{Float64}, series_index::Vector{<:Integer};
+                              noise_pred::Union{Nothing,Vector{Float64}}=nothing)
+    P = length(nodes)
+    (length(noises) == P && length(series_index) == P) || throw(ArgumentError("one noise and one series index per particle required"))
+    length(queries) == length(series) || throw(ArgumentError("one vector of query times per series required"))
+    (noise_pred === nothing || length(noise_pred) == P) || throw(ArgumentError("one noise_pred per particle required"))
+    all(i -> 1 <= i <= length(series), series_index) || throw(ArgumentError("series index outside 1:$(length(series))"))
+    pt_off = Int64[0]; ts = Float64[]; xs = Float64[]; q_off = Int64[0]; tq = Float64[]
+    for (s, (t, x)) in enumerate(series)
+        length(t) == length(x) || throw(ArgumentError("series $s: ts and xs must have equal lengths"))
+        length(t) <= SERIES_MAX_N || throw(ArgumentError("series $s has $(length(t)) points, more than SERIES_MAX_N ($SERIES_MAX_N)"))
+        append!(ts, t); append!(xs, x); push!(pt_off, length(ts))
+        append!(tq, queries[s]); push!(q_off, length(tq))
+    end
+    isempty(ts) && (push!(ts, 0.0); push!(xs, 0.0))
+    isempty(tq) && push!(tq, 0.0)
+    sidx = Int32[Int32(i - 1) for i in series_index]
+    op_off, ops, prm_off, prm = encode_batch(nodes)
+    total = sum(Int[length(queries[i]) for i in series_index])
+    mean = Vector{Float64}(undef, max(1, total)); var = Vector{Float64}(undef, max(1, total))
+    out_off = zeros(Int64, P + 1)
+    out = Vector{Float64}(undef, P); info = Vector{Int32}(undef, P)
+    np = noise_pred === nothing ? noises : noise_pred
+    GC.@preserve pt_off ts xs q_off tq sidx op_off ops prm_off prm noises np mean var out_off out info check(eng, ccall((:agp_predict_series_batch, LIB), Cint,
+        (Ptr{Cvoid}, Int32, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Int32, Ptr{Int32}, Ptr{Int32}, Ptr{UInt8},
+         Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Ptr{Int32}),
+        eng.ptr, length(series), pt_off, ts, xs, q_off, tq, P, sidx, op_off, ops, prm_off, prm, noises, np, mean, var, out_off, out, info))
+    means = [mean[out_off[p] + 1:out_off[p + 1]] for p in 1:P]
+    vars = [var[out_off[p] + 1:out_off[p + 1]] for p in 1:P]
+    return means, vars, out, info
+end
+
 "(extended, from_scratch, tile_rows_reused, tile_rows_total, evicted_before_reuse, slots, callers, occupied, capacity_tile_rows, growth_copies) of the factor store"
 function extend_stats(eng::Engine)
     out = zeros(Int64, 10)

@@ -153,6 +153,43 @@ int agp_logpdf_grad_series_batch(agp_ctx* ctx, int32_t S, const int64_t* pt_off 
                                  double* out_logpdf /* P */, double* out_grad /* prm_off[P] */,
                                  double* out_grad_noise /* P */, int32_t* out_info /* P */);
 
+/* Forecasts of many short series in one call: agp_logpdf_series_batch's predictive twin (predict / predict_mvn, src/api.jl:497-596, on
+ * the predictive of src/GP.jl:731-758) for callers that hold one model per short series.  The workgroup that has just factored
+ * K11 = K_p(ts_s) + noise[p] I in LDS evaluates the cross-covariance K21 at the series' own query times 16 at a time and solves it
+ * against that factor in registers; nothing but the outputs leaves the compute unit.
+ * Series s has the training points [pt_off[s], pt_off[s+1]) and the m_s query times ts_pred[q_off[s] .. q_off[s+1]), which may repeat
+ * and may coincide with training times (WhiteNoise is decided by time equality, as everywhere).  Particle p predicts on series[p]:
+ *   mean = K21 K11^-1 x,   var = diag(K22 - K21 K11^-1 K12) + noise_pred[p]       (noise_pred NULL: noise)
+ * — the marginal part of agp_predict_batch with zero mean functions; no full covariance here.
+ * Output layout, particle-major: the entry writes out_off[p] = sum_{p' < p} m_{series[p']} (P + 1 values); particle p's m means and
+ * variances start at out_off[p]; out_mean and out_var hold out_off[P] doubles each (the caller can size them from q_off and series).
+ * Adjacent particles of one series therefore form the (P_s, m_s) row-major block that agp_mixture_quantile and agp_mixture_moments
+ * take as is.
+ * out_logpdf (P, or NULL): the training log marginal likelihood, bit-identical to agp_logpdf_series_batch's for the same particle.
+ * Program encoding, noise meaning, out_info, AGP_SERIES_MAX_N, statelessness, re-entrancy, no deduplication and profiling timing are
+ * exactly those of agp_logpdf_series_batch.  A series without query points (m_s == 0): nothing is written to out_mean / out_var for
+ * its particles; out_logpdf and out_info are still set.  An EMPTY series with query points gives the prior predictive: mean 0,
+ * var = k(t*, t*) + noise_pred, logpdf 0, info 0.  out_info[p] > 0 gives NaN in the particle's whole mean and variance block and in
+ * out_logpdf[p]; the other particles are untouched.  A computed variance that is not positive (cancellation in K22 - K21 K11^-1 K12
+ * when noise_pred does not lift it) is returned as computed — neither clamped nor reported — exactly as agp_predict_batch's out_var.
+ * P == 0 is AGP_OK and touches nothing.
+ * The WHOLE call is rejected with
+ *   AGP_ERR_ARG (names the series or particle): everything agp_logpdf_series_batch lists, q_off[0] != 0, a decreasing q_off, a series
+ *     with more than 2^30 query points, a null q_off, ts_pred, out_mean, out_var or out_off;
+ *   AGP_ERR_PROGRAM (names the particle): as agp_logpdf_series_batch.  The predictive kernel's LDS map is the value kernel's (the
+ *     solved query blocks live in registers, the ChangePoint tables' unused tail holds the query times' entries): at AGP_SERIES_MAX_N
+ *     points a chain of 10 ChangePoint nodes (21 nodes, 31 parameters, 10 per-point tables) fits and one of 11 does not, as for the
+ *     value entry.
+ * A particle's result bits depend only on its own series, queries, program, parameters and noises — not on what else is in the call,
+ * its order, or how the call is split into launches. */
+int agp_predict_series_batch(agp_ctx* ctx, int32_t S, const int64_t* pt_off /* S+1 */, const double* ts, const double* xs,
+                             const int64_t* q_off /* S+1 */, const double* ts_pred,
+                             int32_t P, const int32_t* series /* P */,
+                             const int32_t* op_off, const uint8_t* ops, const int32_t* prm_off, const double* prm,
+                             const double* noise /* P */, const double* noise_pred /* P or NULL = noise */,
+                             double* out_mean, double* out_var, int64_t* out_off /* P+1 */,
+                             double* out_logpdf /* P or NULL */, int32_t* out_info /* P */);
+
 /* agp_logpdf_batch with BLOCK-EXTENSION of resident factors.  The data-annealing loop re-scores
  * every particle on a longer prefix of the same series with unchanged kernel parameters — the reweight step
  * (src/inference_smc_anneal_data.jl:206-217), add_data! (src/api.jl:426-443), scripts/online.jl:200 — and the
