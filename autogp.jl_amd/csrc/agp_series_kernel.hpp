@@ -12,8 +12,8 @@
 //      straight into LDS as packed lower 16 x 16 column-major blocks — block (rb, cb) at blk_idx(rb, cb) * 256, the layout of
 //      factor_diag_tile with nb = ceil(n / 16) block rows instead of 8; rows / columns past n are identity (cov_finalize);
 //   4. right-looking 16 x 16-blocked Cholesky in LDS over the particle's own nb block steps: diagonal block + its inverse in one wave
-//      (factor16 of agp_chol_kernel.hpp, restated here because that one is a lambda bound to CholArgs), panel and trailing updates
-//      on v_mfma_f64_16x16x4 across the waves, the next diagonal block factored by wave 0 beside the trailing updates;
+//      (factor16), panel and trailing updates on v_mfma_f64_16x16x4 across the waves, the next diagonal block factored by wave 0
+//      beside the trailing updates — lds_chol_steps of agp_lds_chol.hpp, the code factor_diag_tile runs on its eight block rows;
 //   5. alpha = L^-1 xs carried along block by block (W r + one refinement step), sum log L_ii, alpha'alpha, first bad pivot ->
 //      out_logpdf[p] = -(n log 2 pi + 2 sum log L_ii + alpha'alpha) / 2 (NaN on a bad pivot), out_info[p].
 // No HBM workspace per particle, no finish kernel.
@@ -63,10 +63,31 @@
 #include "agp_common.hpp"
 #include "agp_args.hpp"
 #include "agp_cov_kernel.hpp"
-#include "agp_chol_kernel.hpp"      // mfma, readlane_d, blk_idx
+#include "agp_lds_chol.hpp"         // mfma, blk_idx, lds_chol_steps
 #include "agp_grad_elements.hpp"    // grad_elements, RegTape, ScratchAcc
 
 namespace agp {
+
+// block b of the packed lower block triangle, counted row by row -> its block row rb and block column cb
+__device__ __forceinline__ void series_blk_rc(int b, int& rb, int& cb) {
+  rb = 0;
+  while ((rb + 1) * (rb + 2) / 2 <= b) ++rb;
+  cb = b - rb * (rb + 1) / 2;
+}
+
+// sigma_cp (src/GP.jl:481-483) of every ChangePoint node at time t -> entry `slot` of the node's per-point table (cov_prologue's arithmetic)
+__device__ __forceinline__ void series_sigma_cp(const ProgHdr& h, const int* ops, const double* prm, double* sig, int slot, double t) {
+  int q = 0, c = 0;
+  for (int ip = 0; ip < h.n_ops; ++ip) {
+    const int o = ops[ip];
+    if (o == OP_CP || o == OP_CP_SWAP) {
+      const double loc = prm[q], sc = prm[q + 1];
+      sig[c * 256 + slot] = 0.5 * (1.0 + tanh((loc - t) / sc));
+      ++c;
+    }
+    q += prm_count(o);
+  }
+}
 
 // G1 / P1: every diagonal block L(i,i) -> L(i,i)^-T in place (the whole block, zeros below the diagonal), one block per wave and
 // pass, column c of L(i,i)^-1 by forward substitution in lane c (the reads of L are broadcasts).  No barrier inside.
@@ -113,18 +134,7 @@ __device__ __forceinline__ void series_predict_blocks(const ProgHdr& h, const in
     const int qi = qb * 16 + l15;
     const double t = tq[qi < mq ? qi : mq - 1];
     if (h.n_cp > 0) {
-      if (l < 16) {
-        int q = 0, c = 0;
-        for (int ip = 0; ip < h.n_ops; ++ip) {
-          const int o = ops[ip];
-          if (o == OP_CP || o == OP_CP_SWAP) {
-            const double loc = prm[q], sc = prm[q + 1];
-            sig[c * 256 + slot] = 0.5 * (1.0 + tanh((loc - t) / sc));
-            ++c;
-          }
-          q += prm_count(o);
-        }
-      }
+      if (l < 16) series_sigma_cp(h, ops, prm, sig, slot, t);
       __builtin_amdgcn_wave_barrier();      // (LDS operations of one wave complete in order: its own lanes' entries, no workgroup barrier)
     }
     d4 VT[NBMAX];
@@ -263,9 +273,8 @@ __device__ __forceinline__ void series_body(const ArgsT& a, double* smem) {
     const double* Kp = a.K + (long long)p * n * n;
     const int nblk = nb * (nb + 1) / 2;
     for (int b = w; b < nblk; b += 4) {
-      int rb = 0;
-      while ((rb + 1) * (rb + 2) / 2 <= b) ++rb;
-      const int cb = b - rb * (rb + 1) / 2;
+      int rb, cb;
+      series_blk_rc(b, rb, cb);
       double* blk = sm + blk_idx(rb, cb) * 256;
 #pragma unroll
       for (int e = 0; e < E; ++e) {
@@ -288,19 +297,7 @@ __device__ __forceinline__ void series_body(const ArgsT& a, double* smem) {
 
     // ---- 2. per-point tables (cov_prologue's arithmetic) ----
     if (h.n_cp > 0) {
-      if (tid < np) {
-        const double t = tpt[tid];
-        int q = 0, c = 0;
-        for (int ip = 0; ip < h.n_ops; ++ip) {
-          const int o = ops[ip];
-          if (o == OP_CP || o == OP_CP_SWAP) {
-            const double loc = prm[q], sc = prm[q + 1];
-            sig[c * 256 + tid] = 0.5 * (1.0 + tanh((loc - t) / sc));   // sigma_cp, src/GP.jl:481-483
-            ++c;
-          }
-          q += prm_count(o);
-        }
-      }
+      if (tid < np) series_sigma_cp(h, ops, prm, sig, tid, tpt[tid]);
       __syncthreads();
     }
 
@@ -309,9 +306,8 @@ __device__ __forceinline__ void series_body(const ArgsT& a, double* smem) {
       const double noise = a.noise[p];
       const int nblk = nb * (nb + 1) / 2;
       for (int b = w; b < nblk; b += 4) {
-        int rb = 0;
-        while ((rb + 1) * (rb + 2) / 2 <= b) ++rb;
-        const int cb = b - rb * (rb + 1) / 2;
+        int rb, cb;
+        series_blk_rc(b, rb, cb);
         double tr[E], tc[E], out[E], lt[E];
         int ri[E], ci[E];
 #pragma unroll
@@ -331,210 +327,10 @@ __device__ __forceinline__ void series_body(const ArgsT& a, double* smem) {
   }
   __syncthreads();
 
-  // ---- 4. + 5. factorisation with the forward solve carried along (factor_diag_tile with nb block rows) ----
+  // ---- 4. + 5. factorisation with the forward solve carried along: the block steps of factor_diag_tile over nb block rows
+  //      (lds_chol_steps, agp_lds_chol.hpp); r_ib -= L(ib,jb) alpha_jb on one thread per row of waves 1 .. 3 (192 >= np) ----
   int bad = 0;           // first non-positive pivot (1-based index in the series), 0 = none; kept by wave 0
-  auto sqrt_rsqrt = [](double d, double& sq, double& ri) {
-    // v_rsq_f64 + ONE third-order step y (1 + e/2 + 3 e^2 / 8), e = 1 - d y^2; sqrt(d) = d ri corrected once with the residual
-    const double y = __builtin_amdgcn_rsq(d);
-    const double t = d * y;
-    const double e = fma(-t, y, 1.0);
-    const double pq = fma(e, 0.375, 0.5), ye = y * e;
-    ri = fma(ye, pq, y);
-    const double g = d * ri;
-    sq = fma(fma(-g, g, d), 0.5 * ri, g);
-  };
-  // 16 x 16 Cholesky of block (jb, jb) + its inverse (-> Wl), one wave, 4 columns per sub-step: the 4 x 4 diagonal sub-block through
-  // v_readlane to every lane, columns and trailing columns by two MFMAs each, an identity block riding along turns into L^-1
-  auto factor16 = [&](int jb) {
-    double* blk = sm + blk_idx(jb, jb) * 256;
-    d4 Y0, Yw;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) { Y0[r] = blk[64 * r + l]; Yw[r] = (l15 == 4 * r + lq) ? 1.0 : 0.0; }
-    const int dlt = l15 - lq;
-#pragma unroll
-    for (int rp = 0; rp < 4; ++rp) {
-      const int c0 = 4 * rp;
-      // S[c0+a][c0+b], a >= b: register rp of lane 16 b + c0 + a
-      const double d00 = readlane_d(Y0[rp], c0), d10 = readlane_d(Y0[rp], c0 + 1), d20 = readlane_d(Y0[rp], c0 + 2),
-                   d30 = readlane_d(Y0[rp], c0 + 3), d11 = readlane_d(Y0[rp], 16 + c0 + 1), d21 = readlane_d(Y0[rp], 16 + c0 + 2),
-                   d31 = readlane_d(Y0[rp], 16 + c0 + 3), d22 = readlane_d(Y0[rp], 32 + c0 + 2), d32 = readlane_d(Y0[rp], 32 + c0 + 3),
-                   d33 = readlane_d(Y0[rp], 48 + c0 + 3);
-      const int g0 = jb * 16 + c0;       // index in the series of the sub-block's first pivot
-      double l00, r0, l11, r1, l22, r2, l33, r3;
-      if (!(d00 > 0.0) && bad == 0) bad = g0 + 1;
-      sqrt_rsqrt(d00, l00, r0);
-      const double l10 = d10 * r0, l20 = d20 * r0, l30 = d30 * r0;
-      const double e11 = fma(-l10, l10, d11);
-      if (!(e11 > 0.0) && bad == 0) bad = g0 + 2;
-      sqrt_rsqrt(e11, l11, r1);
-      const double l21 = fma(-l20, l10, d21) * r1, l31 = fma(-l30, l10, d31) * r1;
-      const double e22 = fma(-l21, l21, fma(-l20, l20, d22));
-      if (!(e22 > 0.0) && bad == 0) bad = g0 + 3;
-      sqrt_rsqrt(e22, l22, r2);
-      const double l32 = fma(-l31, l21, fma(-l30, l20, d32)) * r2;
-      const double e33 = fma(-l32, l32, fma(-l31, l31, fma(-l30, l30, d33)));
-      if (!(e33 > 0.0) && bad == 0) bad = g0 + 4;
-      sqrt_rsqrt(e33, l33, r3);
-      // W4 = L4^-1 (lower); row 3 carries the factor 1 / l33 of the last pivot, multiplied in after the selection
-      const double w10 = -(l10 * r0) * r1, w21 = -(l21 * r1) * r2;
-      const double w20 = -fma(l21, w10, l20 * r0) * r2;
-      const double u32 = -(l32 * r2), u31 = -fma(l32, w21, l31 * r1), u30 = -fma(l32, w20, fma(l31, w10, l30 * r0));
-      // A operand of the column step: lane 16 k + i <-> W4[i][k]
-      double aW = 0.0;
-      aW = (l == 0) ? r0 : aW;   aW = (l == 1) ? w10 : aW;  aW = (l == 17) ? r1 : aW;
-      aW = (l == 2) ? w20 : aW;  aW = (l == 18) ? w21 : aW; aW = (l == 34) ? r2 : aW;
-      double u3 = 1.0;
-      u3 = (l == 3) ? u30 : u3;  u3 = (l == 19) ? u31 : u3; u3 = (l == 35) ? u32 : u3;
-      aW = (l15 == 3) ? u3 * r3 : aW;
-      const d4 z4 = d4{0.0, 0.0, 0.0, 0.0};
-      const d4 T0 = mfma(aW, Y0[rp], z4);      // T0[0], lane (i, q): L[i][c0 + q] (rows i < c0: upper-triangle debris)
-      const d4 Tw = mfma(aW, Yw[rp], z4);
-      double nl = (dlt >= c0) ? T0[0] : 0.0;      // the finished columns: zero above the diagonal
-      if (rp < 3) {
-        const double nA = (l15 >= c0 + 4) ? -nl : 0.0;
-        Y0 = mfma(nA, nl, Y0);
-        Yw = mfma(nA, Tw[0], Yw);
-      }
-      // ... and the diagonal itself from the scalar factorisation
-      nl = (l == c0) ? l00 : nl; nl = (l == 17 + c0) ? l11 : nl; nl = (l == 34 + c0) ? l22 : nl; nl = (l == 51 + c0) ? l33 : nl;
-      Y0[rp] = nl;
-      Yw[rp] = Tw[0];
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      blk[64 * r + l] = Y0[r];
-      Wl[l15 * 16 + 4 * r + lq] = Yw[r];      // Yw[r], lane (i, q) <-> (L^-1)[4r + q][i]; column-major like every block
-    }
-  };
-
-  if (w == 0) factor16(0);
-  __syncthreads();
-  for (int jb = 0; jb < nb; ++jb) {
-    // ---- (b) panel: L(ib,jb) = S(ib,jb) W^T for ib > jb, two blocks per wave and pass with their MFMA chains interleaved ----
-    for (int ib0 = jb + 1 + w; ib0 < nb; ib0 += 8) {
-      const int ib1 = ib0 + 4;
-      double* blk0 = sm + blk_idx(ib0, jb) * 256;
-      double* blk1 = sm + blk_idx(ib1 < nb ? ib1 : ib0, jb) * 256;
-      double fw[4], fs0[4], fs1[4];
-#pragma unroll
-      for (int s4 = 0; s4 < 4; ++s4) { fw[s4] = Wl[64 * s4 + l]; fs0[s4] = blk0[64 * s4 + l]; fs1[s4] = blk1[64 * s4 + l]; }
-      d4 x0 = d4{0.0, 0.0, 0.0, 0.0}, x1 = d4{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-      for (int s4 = 0; s4 < 4; ++s4) { x0 = mfma(fw[s4], fs0[s4], x0); x1 = mfma(fw[s4], fs1[s4], x1); }
-#pragma unroll
-      for (int r = 0; r < 4; ++r) blk0[64 * r + l] = x0[r];
-      if (ib1 < nb) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) blk1[64 * r + l] = x1[r];
-      }
-    }
-    if (w == 3 && l < 16) {
-      // alpha_jb = W r_jb, then one step of refinement against the block itself: rho = r_jb - L(jb,jb) alpha, alpha += W rho
-      const double* Lb = sm + blk_idx(jb, jb) * 256;
-      double wr[16];
-#pragma unroll
-      for (int q = 0; q < 16; ++q) wr[q] = Wl[q * 16 + l];
-      double t0 = 0.0, t1 = 0.0;
-#pragma unroll
-      for (int q = 0; q < 16; q += 2) {
-        t0 = fma(wr[q], rvec[jb * 16 + q], t0);
-        t1 = fma(wr[q + 1], rvec[jb * 16 + q + 1], t1);
-      }
-      const double a0 = t0 + t1;
-      double r0 = rvec[jb * 16 + l], r1 = 0.0;
-#pragma unroll
-      for (int q = 0; q < 16; q += 2) {
-        r0 = fma(-Lb[q * 16 + l], readlane_d(a0, q), r0);
-        r1 = fma(-Lb[(q + 1) * 16 + l], readlane_d(a0, q + 1), r1);
-      }
-      const double rho = r0 + r1;
-      double c0 = 0.0, c1 = 0.0;
-#pragma unroll
-      for (int q = 0; q < 16; q += 2) {
-        c0 = fma(wr[q], readlane_d(rho, q), c0);
-        c1 = fma(wr[q + 1], readlane_d(rho, q + 1), c1);
-      }
-      avec[jb * 16 + l] = a0 + (c0 + c1);
-    }
-    __syncthreads();
-
-    // ---- (c) trailing blocks (ib,cb), jb < cb <= ib: S(ib,cb) -= L(ib,jb) L(cb,jb)^T;  r_ib -= L(ib,jb) alpha_jb ----
-    {
-      const int nrem = nb - 1 - jb;              // block rows below jb
-      const int npair = nrem * (nrem + 1) / 2;
-      // pair 0 is the next diagonal block: wave 0 takes it and then factors it; waves 1-3 share the rest, three blocks per pass
-      // (pairs e = w, w + 3, ... in row-major order of the trailing triangle)
-      if (w == 0) {
-        if (npair > 0) {
-          double* blk = sm + blk_idx(jb + 1, jb + 1) * 256;
-          const double* la = sm + blk_idx(jb + 1, jb) * 256;
-          d4 x;
-          double f[4];
-#pragma unroll
-          for (int r = 0; r < 4; ++r) { x[r] = blk[64 * r + l]; f[r] = la[64 * r + l]; }
-#pragma unroll
-          for (int s4 = 0; s4 < 4; ++s4) x = mfma(-f[s4], f[s4], x);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) blk[64 * r + l] = x[r];
-        }
-      } else {
-        // position of pair e in the triangle: row ii (0-based below jb+1), column cc <= ii
-        int e = w, ii = 1, cc = w - 1;                     // e = 1, 2, 3 -> (1,0), (1,1), (2,0)
-        if (cc > ii) { cc -= ii + 1; ++ii; }
-        auto advance = [&](int& e_, int& ii_, int& cc_) {  // three pairs on
-          e_ += 3; cc_ += 3;
-          while (cc_ > ii_) { cc_ -= ii_ + 1; ++ii_; }
-        };
-        while (e < npair) {
-          int eb[3], ib3[3], cb3[3];
-#pragma unroll
-          for (int u = 0; u < 3; ++u) {
-            eb[u] = e; ib3[u] = jb + 1 + ii; cb3[u] = jb + 1 + cc;
-            advance(e, ii, cc);
-          }
-          d4 x[3];
-          double fa[3][4], fb[3][4];
-#pragma unroll
-          for (int u = 0; u < 3; ++u) {
-            const bool on = eb[u] < npair;      // (off: a dummy on block (jb+1, jb+1), read only)
-            const int ib = on ? ib3[u] : jb + 1, cb = on ? cb3[u] : jb + 1;
-            const double* blk = sm + blk_idx(ib, cb) * 256;
-            const double* la = sm + blk_idx(cb, jb) * 256;
-            const double* lb = sm + blk_idx(ib, jb) * 256;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) x[u][r] = blk[64 * r + l];
-#pragma unroll
-            for (int s4 = 0; s4 < 4; ++s4) { fa[u][s4] = -la[64 * s4 + l]; fb[u][s4] = lb[64 * s4 + l]; }
-          }
-#pragma unroll
-          for (int s4 = 0; s4 < 4; ++s4)
-#pragma unroll
-            for (int u = 0; u < 3; ++u) x[u] = mfma(fa[u][s4], fb[u][s4], x[u]);
-#pragma unroll
-          for (int u = 0; u < 3; ++u)
-            if (eb[u] < npair) {
-              double* blk = sm + blk_idx(ib3[u], cb3[u]) * 256;
-#pragma unroll
-              for (int r = 0; r < 4; ++r) blk[64 * r + l] = x[u][r];
-            }
-        }
-        // r_ib -= L(ib,jb) alpha_jb: one row per thread of waves 1 .. 3 (192 >= np) — not the wave that carries the serial chain
-        const int ti_ = tid - 64;
-        if (ti_ >= (jb + 1) * 16 && ti_ < np) {
-          const double* lb = sm + blk_idx(ti_ >> 4, jb) * 256;
-          double t0 = rvec[ti_], t1 = 0.0;
-#pragma unroll
-          for (int q = 0; q < 16; q += 2) {
-            t0 = fma(-lb[q * 16 + (ti_ & 15)], avec[jb * 16 + q], t0);
-            t1 = fma(-lb[(q + 1) * 16 + (ti_ & 15)], avec[jb * 16 + q + 1], t1);
-          }
-          rvec[ti_] = t0 + t1;
-        }
-      }
-      if (w == 0 && jb + 1 < nb) factor16(jb + 1);      // (its block was brought up to date by this wave just above)
-    }
-    __syncthreads();
-  }
+  lds_chol_steps<0>(sm, Wl, rvec, avec, nb, nb, 64, np, 0, bad, tid);
 
   // ---- the value: 2 sum log L_ii (padding rows: log 1) and alpha'alpha, reduced in a fixed order ----
   {
@@ -699,9 +495,8 @@ __device__ __forceinline__ void series_body(const ArgsT& a, double* smem) {
     {
       const int nblk = nb * (nb + 1) / 2;
       for (int b = w; b < nblk; b += 4) {
-        int rb = 0;
-        while ((rb + 1) * (rb + 2) / 2 <= b) ++rb;
-        const int cb = b - rb * (rb + 1) / 2;
+        int rb, cb;
+        series_blk_rc(b, rb, cb);
         d4 kin = d4{0.0, 0.0, 0.0, 0.0};
         for (int k = rb; k < nb; ++k) {
           const double* za = sm + blk_idx(k, cb) * 256;

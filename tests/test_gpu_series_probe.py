@@ -4,8 +4,8 @@ of L and of the carried forward solve, the log-det / quadratic-form partials and
 LAPACK info at every 4 / 16 boundary and in a ragged last block, isolation of failed matrices, run-to-run determinism, and bitwise
 agreement of the probe with logpdf_series_batch on particles whose covariance is exact in float64.
 
-Bounds.  The series kernel restates the algorithm of the tile schedules (16 x 16 diagonal blocks with explicit inverses, one
-refinement step per block of the forward solve), so it may lose no more than they do: the margins M, M_SOLVE and BENIGN_CAP are the
+Bounds.  The series kernel shares the block steps of the tile schedules (csrc/agp_lds_chol.hpp: 16 x 16 diagonal blocks with explicit
+inverses, one refinement step per block of the forward solve), so it may lose no more than they do: the margins M, M_SOLVE and BENIGN_CAP are the
 tables of tests/test_gpu_factor_probe.py (8 x what the tile schedules measured at n up to 300), capped per matrix by kappa_blk of
 the longdouble reference factor.  No number here was measured on the kernel under test; what it measures is recorded in
 profiles/series_probe_accuracy.txt (tools/gpu_series_probe_accuracy.py), which nothing reads."""
@@ -16,7 +16,7 @@ import pytest
 
 import _factor_ref as R
 import _series_cases as S
-from test_gpu_factor_probe import M, M_SOLVE, BENIGN_CAP, MEMBERS, batch
+from test_gpu_factor_probe import M, M_SOLVE, BENIGN_CAP, MEMBERS, batch, cases
 
 pytestmark = pytest.mark.gpu
 
@@ -118,6 +118,27 @@ def test_probe_is_the_production_code(pkg, engine, n):
         _, _, _, lp_probe, info_probe = engine.debug_series_factor(K[None], xs[None])
         assert info[0] == 0 and info_probe[0] == 0
         assert bits(lp_probe)[0] == bits(lp)[0], (n, type(node).__name__, lp_probe[0], lp[0])
+
+
+def test_tile_schedules_and_series_kernel_factor_alike(engine):
+    """one blocked LDS Cholesky (csrc/agp_lds_chol.hpp) behind both kernels: up to one tile (n <= 128) every tile schedule and the
+    series kernel run the same statements on the same 16 x 16 blocks, and the tile's identity padding contributes exact zeros, so L,
+    alpha and info agree bit for bit.  Sizes: a lone sub-block, a ragged block, a full block, a full block plus one, a look-ahead
+    step, a ragged and a full tile.  (The partials are not compared: 128 and 256 logs summed in two fixed orders.)"""
+    schedules = sorted({s for s, _, _ in cases()} - {3})      # (the hybrid rule is refused below three tile rows)
+    assert schedules == [-1, 0, 1, 2, 4]
+    differ = []
+    for n in (1, 5, 16, 17, 33, 127, 128):
+        _, K, y, _ = batch(n)
+        idx = list(MEMBERS[3])
+        Ls, als, _, _, infos = engine.debug_series_factor(K[idx], y[idx])
+        for s in schedules:
+            Lt, alt, _, infot = engine.debug_factor_batch(K[idx], y[idx], schedule=s)
+            dL, da = int((bits(Ls) != bits(Lt)).sum()), int((bits(als) != bits(alt)).sum())
+            print(f"n {n} schedule {s}: {dL} entries of L and {da} of alpha differ, info {infos.tolist()} / {infot.tolist()}")
+            if dL or da or not np.array_equal(infos, infot):
+                differ.append(f"n {n} schedule {s}: {dL} entries of L, {da} of alpha differ; info {infos.tolist()} vs {infot.tolist()}")
+    assert not differ, "\n".join(differ)
 
 
 def test_argument_errors(pkg, engine):

@@ -1,5 +1,5 @@
 // Dependent-issue latencies of the instruction kinds on the serial chain of the 128x128 diagonal-tile factorisation
-// (agp_chol_kernel.hpp: factor16), measured with ONE wave on an otherwise idle CU and with two workgroups of four waves per CU (the
+// (agp_lds_chol.hpp: factor16), measured with ONE wave on an otherwise idle CU and with two workgroups of four waves per CU (the
 // production occupancy): core clocks per link of a chain of N dependent instructions.  With tools/native/diag_bench's per-phase
 // clocks this gives the floor the chain can be held against (profiles/r06_diag_chain_floor.md).
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/native/lat_bench.hip -o tools/native/lat_bench
