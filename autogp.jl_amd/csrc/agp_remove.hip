@@ -30,16 +30,24 @@ std::vector<Run> runs_below(const int64_t* idx, int64_t cnt) {
 template <int RH> void launch_panel(hipStream_t st, int Pc, const RemoveArgs& g) { hipLaunchKernelGGL(k_rm_panel<RH>, dim3(Pc), dim3(320), 0, st, g); }
 template <int RH> void launch_apply(hipStream_t st, int nI, int Pc, const RemoveArgs& g) { hipLaunchKernelGGL(k_rm_apply<RH>, dim3(nI, Pc), dim3(256), 0, st, g); }
 
+// The slot-indexed arrays an update rewrites: the factor store's (remove_body) or a probe's own (agp_debug_remove_factor).
+struct FactorView {
+  double* A; long long strideA;
+  double* Winv; int wsteps;
+  double* vec; int ldv;
+  double* partial; int ntp;
+  int* info;
+};
+
 // One run out of the factors (prefix n_old) of the chunk's slots.  Returns the panel steps launched in *panels.
-hipError_t remove_run(agp_ctx* c, Slot* s, hipStream_t st, const int32_t* d_slot, int Pc, int64_t n_old, const Run& run, int64_t* panels) {
-  agp_ctx::FactorStore& fs = c->store;
+hipError_t remove_run(agp_ctx* c, Slot* s, hipStream_t st, const FactorView& fv, const int32_t* d_slot, int Pc, int64_t n_old, const Run& run, int64_t* panels) {
   const int64_t n_new = n_old - run.r;
   const int nt_new = round_up(n_new, NB) / NB, J0 = (int)(run.a / NB);
   if (J0 >= nt_new) return hipSuccess;      // a whole number of trailing tile rows went: what stays is the factor as it is
   RemoveArgs g = {};
-  g.A = fs.A.as<double>(); g.strideA = fs.strideA; g.Winv = fs.W.as<double>(); g.wsteps = fs.nt_cap;
-  g.vec = fs.vec.as<double>(); g.ldv = fs.nt_cap * NB; g.partial = fs.partial.as<double>(); g.ntp = fs.nt_cap;
-  g.info = fs.info.as<int>(); g.slot = d_slot;
+  g.A = fv.A; g.strideA = fv.strideA; g.Winv = fv.Winv; g.wsteps = fv.wsteps;
+  g.vec = fv.vec; g.ldv = fv.ldv; g.partial = fv.partial; g.ntp = fv.ntp;
+  g.info = fv.info; g.slot = d_slot;
   g.off0 = tile_off(J0, 0); g.ws_stride = tile_off(nt_new, 0) - g.off0;
   g.ldw = nt_new * NB; g.ldg = (int)run.r;
   g.a = (int)run.a; g.r = (int)run.r; g.n_new = (int)n_new; g.nt_new = nt_new; g.J0 = J0;
@@ -123,6 +131,8 @@ int remove_body(agp_ctx* c, const int64_t* idx, int64_t k) {
       if (!s->stream) HIPCHK(c, hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
       hipStream_t st = s->stream;
       auto forget_groups = [&]() { for (auto& gr : groups) for (int32_t sl : gr.second) if (!fs.key[(size_t)sl].empty()) drop(sl); };
+      const FactorView fv = {fs.A.as<double>(), fs.strideA, fs.W.as<double>(), fs.nt_cap, fs.vec.as<double>(), fs.nt_cap * NB,
+                             fs.partial.as<double>(), fs.nt_cap, fs.info.as<int>()};
       auto hipfail = [&](hipError_t e, const char* what) {
         forget_groups();
         return fail(c, AGP_ERR_HIP, std::string("HIP error in agp_remove_data (") + what + "): " + hipGetErrorString(e));
@@ -146,7 +156,7 @@ int remove_body(agp_ctx* c, const int64_t* idx, int64_t k) {
           RMCHK(hipMemcpyAsync(s->map.p, s->h_stage.p, sizeof(int32_t) * (size_t)Pc, hipMemcpyHostToDevice, st));
           int64_t n_cur = n_f;
           for (const Run& run : runs) {
-            RMCHK(remove_run(c, s, st, s->map.as<int32_t>(), Pc, n_cur, run, &n_panels));
+            RMCHK(remove_run(c, s, st, fv, s->map.as<int32_t>(), Pc, n_cur, run, &n_panels));
             n_cur -= run.r;
           }
         }
@@ -178,9 +188,93 @@ int remove_body(agp_ctx* c, const int64_t* idx, int64_t k) {
   return rc;
 }
 
+// agp_debug_remove_factor: P caller factors packed into arrays of the store's layout (in slot buffers remove_run does not take as
+// its workspace), every run of idx through remove_run as remove_body sends it, and what the kernels left, at the new size.
+int debug_remove_body(agp_ctx* c, const double* L0, const double* alpha0, int64_t n, int32_t P, const int64_t* idx, int64_t k,
+                      double* out_L, double* out_alpha, double* out_partial, double* out_winv, int32_t* out_info) {
+  if (!c) return fail(nullptr, AGP_ERR_ARG, "null context");
+  if (!L0 || !idx || !out_L || !out_alpha || !out_partial || !out_info) return fail(c, AGP_ERR_ARG, "debug probe: null pointer");
+  if (n < 2 || n > 1024 || P < 1 || k < 1 || k >= n) return fail(c, AGP_ERR_ARG, "debug probe: needs 2 <= n <= 1024, P >= 1, 1 <= k < n");
+  if ((int64_t)P * n * n > ((int64_t)1 << 24)) return fail(c, AGP_ERR_ARG, "debug probe: batch too large");
+  for (int64_t i = 0; i < k; ++i) {
+    if (idx[i] < 0 || idx[i] >= n) return fail(c, AGP_ERR_ARG, "debug probe: position out of range");
+    if (i > 0 && idx[i] <= idx[i - 1]) return fail(c, AGP_ERR_ARG, "positions must be distinct and ascending");
+  }
+  const int nt = round_up(n, NB) / NB;
+  const long long strideA = tile_off(nt, 0);
+  if ((int64_t)P * strideA > ((int64_t)1 << 27)) return fail(c, AGP_ERR_ARG, "debug probe: batch too large (padded tiles)");
+  const int64_t n_new = n - k;
+  const int nt_new = round_up(n_new, NB) / NB, np_new = nt_new * NB, ldv = nt * NB;
+  const size_t nel = (size_t)n * n, nW = (size_t)P * nt * NSB * 256, nPart = (size_t)P * nt * 2;
+  // the caller's lower triangles as launch_pack_dense reads them (element (r, c) at [c * n + r]); zero above the diagonal
+  std::vector<double> Lt(nel * P, 0.0);
+  for (int p = 0; p < P; ++p)
+    for (int64_t r = 0; r < n; ++r)
+      for (int64_t cc = 0; cc <= r; ++cc) Lt[p * nel + (size_t)cc * n + r] = L0[p * nel + (size_t)r * n + cc];
+  HIPCHK(c, hipSetDevice(c->device));
+  SlotGuard sg(c);
+  Slot* s = sg.s;
+  if (!s->stream) HIPCHK(c, hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
+  hipStream_t st = s->stream;
+  // (remove_run's workspace is the slot's A, W, alpha and Z: the factor arrays live in dense, tsol, vec, partial, info)
+  HIPCHK(c, s->pred_cov.ensure(sizeof(double) * nel * P));
+  HIPCHK(c, s->dense.ensure(sizeof(double) * (size_t)strideA * P));
+  HIPCHK(c, s->tsol.ensure(sizeof(double) * nW));
+  HIPCHK(c, s->vec.ensure(sizeof(double) * (size_t)ldv * P));
+  HIPCHK(c, s->partial.ensure(sizeof(double) * nPart));
+  HIPCHK(c, s->info.ensure(sizeof(int) * (size_t)P));
+  HIPCHK(c, s->map.ensure(sizeof(int32_t) * (size_t)P));
+  const FactorView fv = {s->dense.as<double>(), strideA, s->tsol.as<double>(), nt, s->vec.as<double>(), ldv, s->partial.as<double>(), nt,
+                         s->info.as<int>()};
+  std::vector<double> sentinel(std::max(nW, nPart), -7.0);
+  std::vector<int32_t> ident((size_t)P);
+  for (int p = 0; p < P; ++p) ident[(size_t)p] = p;
+  HIPCHK(c, hipMemcpyAsync(s->pred_cov.p, Lt.data(), sizeof(double) * nel * P, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(fv.Winv, sentinel.data(), sizeof(double) * nW, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(fv.partial, sentinel.data(), sizeof(double) * nPart, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(s->map.p, ident.data(), sizeof(int32_t) * (size_t)P, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemsetAsync(fv.vec, 0, sizeof(double) * (size_t)ldv * P, st));
+  if (alpha0)
+    HIPCHK(c, hipMemcpy2DAsync(fv.vec, sizeof(double) * ldv, alpha0, sizeof(double) * n, sizeof(double) * n, P, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemsetAsync(fv.info, 0, sizeof(int) * (size_t)P, st));
+  for (int p = 0; p < P; ++p)
+    launch_pack_dense(st, s->pred_cov.as<double>() + (size_t)p * nel, (int)n, nt, strideA, fv.A + (size_t)p * strideA);
+  HIPCHK(c, hipGetLastError());
+  int64_t n_cur = n, panels = 0;
+  for (const Run& run : runs_below(idx, k)) {
+    HIPCHK(c, remove_run(c, s, st, fv, s->map.as<int32_t>(), P, n_cur, run, &panels));
+    n_cur -= run.r;
+  }
+  std::vector<double> hA((size_t)strideA * P), hv((size_t)ldv * P), hp(nPart), hw(out_winv ? nW : 0);
+  HIPCHK(c, hipMemcpyAsync(hA.data(), fv.A, sizeof(double) * hA.size(), hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(hv.data(), fv.vec, sizeof(double) * hv.size(), hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(hp.data(), fv.partial, sizeof(double) * nPart, hipMemcpyDeviceToHost, st));
+  if (out_winv) HIPCHK(c, hipMemcpyAsync(hw.data(), fv.Winv, sizeof(double) * nW, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(out_info, fv.info, sizeof(int) * (size_t)P, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  // the padded new grid as it lies in the tiles: both triangles of the diagonal tiles, nothing (zero) where the layout has no tile
+  for (int p = 0; p < P; ++p) {
+    double* Lp = out_L + (size_t)p * np_new * np_new;
+    const double* Ap = hA.data() + (size_t)p * strideA;
+    for (int i = 0; i < np_new; ++i)
+      for (int j = 0; j < np_new; ++j)
+        Lp[(size_t)i * np_new + j] = (j >> 7) > (i >> 7) ? 0.0 : Ap[tile_off(i >> 7, j >> 7) + (long long)(j & 127) * NB + (i & 127)];
+    std::memcpy(out_alpha + (size_t)p * np_new, hv.data() + (size_t)p * ldv, sizeof(double) * (size_t)np_new);
+    std::memcpy(out_partial + (size_t)p * nt_new * 2, hp.data() + (size_t)p * nt * 2, sizeof(double) * (size_t)nt_new * 2);
+    if (out_winv)
+      std::memcpy(out_winv + (size_t)p * nt_new * NSB * 256, hw.data() + (size_t)p * nt * NSB * 256, sizeof(double) * (size_t)nt_new * NSB * 256);
+  }
+  return AGP_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int agp_debug_remove_factor(agp_ctx* c, const double* L0, const double* alpha0, int64_t n, int32_t P, const int64_t* idx, int64_t k,
+                            double* out_L, double* out_alpha, double* out_partial, double* out_winv, int32_t* out_info) {
+  return abi_guard(c, [&] { return debug_remove_body(c, L0, alpha0, n, P, idx, k, out_L, out_alpha, out_partial, out_winv, out_info); });
+}
 
 int agp_remove_data(agp_ctx* c, const int64_t* idx, int64_t k) {
   return abi_guard(c, [&] { return remove_body(c, idx, k); });

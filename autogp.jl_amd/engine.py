@@ -37,7 +37,7 @@ EXPORTED_SYMBOLS = [
     "agp_predict_sample_batch", "agp_mixture_moments", "agp_predict_mixture_batch", "agp_get_mixture_stats",
     "agp_remove_data", "agp_get_remove_stats", "agp_set_remove_update", "agp_remove_data_multi",
     "agp_debug_factor_batch", "agp_logpdf_series_batch", "agp_debug_series_factor", "agp_logpdf_grad_series_batch",
-    "agp_predict_series_batch",
+    "agp_predict_series_batch", "agp_debug_remove_factor",
 ]
 COMM_ID_BYTES = 128
 SERIES_MAX_N = 176      # AGP_SERIES_MAX_N of include/autogp_hip.h: the longest series of logpdf_series_batch
@@ -168,6 +168,8 @@ def load_library(path=None):
     lib.agp_extend_reset.argtypes = [vp, C.c_int]; lib.agp_extend_reset.restype = C.c_int
     lib.agp_extend_stats2.argtypes = [vp, C.POINTER(C.c_int64), C.c_int32]; lib.agp_extend_stats2.restype = C.c_int
     lib.agp_remove_data.argtypes = [vp, C.POINTER(C.c_int64), C.c_int64]; lib.agp_remove_data.restype = C.c_int
+    lib.agp_debug_remove_factor.argtypes = [vp, dp, dp, C.c_int64, C.c_int32, C.POINTER(C.c_int64), C.c_int64, dp, dp, dp, dp, ip]
+    lib.agp_debug_remove_factor.restype = C.c_int
     lib.agp_get_remove_stats.argtypes = [vp, C.POINTER(C.c_int64), C.c_int32]; lib.agp_get_remove_stats.restype = C.c_int
     lib.agp_set_remove_update.argtypes = [vp, C.c_int32]; lib.agp_set_remove_update.restype = C.c_int
     lib.agp_remove_data_multi.argtypes = [C.POINTER(vp), C.c_int32, C.POINTER(C.c_int64), C.c_int64]; lib.agp_remove_data_multi.restype = C.c_int
@@ -980,6 +982,31 @@ class GPEngine:
         part = np.empty((P, 2), dtype=np.float64); lp = np.empty(P, dtype=np.float64); info = np.zeros(P, dtype=np.int32)
         self._check(self._lib.agp_debug_series_factor(self._ctx, _dp(K), _dp(y), n, P, _dp(L), _dp(alpha), _dp(part), _dp(lp), _ip(info)))
         return L, alpha, part, lp, info
+
+    def debug_remove_factor(self, L0, alpha0, idx):
+        """The update of remove_data on the caller's factors L0 (P, n, n; lower triangles read) and forward-solve vectors alpha0
+        (P, n) or None (zeros), positions idx ascending (agp_debug_remove_factor: the production host function and kernels on
+        arrays of the store's layout, partials and inverse blocks seeded with the sentinel -7) -> with n' = n - len(idx),
+        nt' = ceil(n' / 128), np' = 128 nt': L (P, np', np') the padded factor as it lies in the tiles, alpha (P, np'),
+        partial (P, nt', 2) = [2 sum log L_ii, sum alpha_i^2] per tile column, winv (P, nt', 8, 16, 16) the inverses of the pivot
+        blocks as matrices, info (P)."""
+        L0 = np.ascontiguousarray(L0, dtype=np.float64)
+        if L0.ndim != 3 or L0.shape[1] != L0.shape[2]:
+            raise ValueError("L0 must have shape (P, n, n)")
+        P, n = L0.shape[0], L0.shape[1]
+        if alpha0 is not None:
+            alpha0 = np.ascontiguousarray(alpha0, dtype=np.float64)
+            if alpha0.shape != (P, n):
+                raise ValueError("alpha0 must have shape (P, n)")
+        idx = np.ascontiguousarray(idx, dtype=np.int64).ravel()
+        nt = max(1, -(-(n - idx.size) // 128)); npad = 128 * nt
+        L = np.empty((P, npad, npad), dtype=np.float64); alpha = np.empty((P, npad), dtype=np.float64)
+        part = np.empty((P, nt, 2), dtype=np.float64); winv = np.empty((P, nt, 8, 16, 16), dtype=np.float64)
+        info = np.zeros(P, dtype=np.int32)
+        self._check(self._lib.agp_debug_remove_factor(self._ctx, _dp(L0), _dp(alpha0), n, P, idx.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                      idx.size, _dp(L), _dp(alpha), _dp(part), _dp(winv), _ip(info)))
+        # (column-major blocks: the transpose of each is the inverse as a matrix)
+        return L, alpha, part, np.ascontiguousarray(winv.transpose(0, 1, 2, 4, 3)), info
 
     def debug_mfma_probe(self, A, B):
         A = _f64(A).reshape(16, 4); B = _f64(B).reshape(4, 16); D = np.empty((16, 16))

@@ -806,6 +806,27 @@ int agp_debug_series_factor(agp_ctx* ctx, const double* K /* P*n*n */, const dou
                             double* out_L /* P*n*n */, double* out_alpha /* P*n */, double* out_partial /* P*2 */,
                             double* out_lp /* P */, int32_t* out_info /* P */);
 
+/* Run agp_remove_data's update of resident factors on P caller-supplied factors of ONE size 2 <= n <= 1024.  Factor p (L0: P blocks of
+ * n x n, row-major; only the lower triangle r >= c at L0[r * n + c] is read) and its forward-solve vector (alpha0: P x n; NULL:
+ * zeros) are packed into arrays of the factor store's layout (tiles with the identity padding of the dense packer, inverse blocks
+ * and partials per tile column, info = 0, slot p = factor p), every partial and every inverse block of the OLD grid is seeded with
+ * the sentinel -7.0, and the positions idx (ascending, distinct, as agp_remove_data takes them) go run after run through the host
+ * function agp_remove_data calls for a chunk of slots: nothing of the update is restated.  With n' = n - k, nt' = ceil(n' / 128)
+ * and np' = 128 nt', what the kernels leave comes back at the new size:
+ *   out_L        P x np' x np' row-major, the PADDED factor as it lies in the tiles: both triangles of the diagonal tiles, rows and
+ *                columns from n' on included; the tile columns right of a tile row's diagonal tile do not exist and read 0
+ *   out_alpha    P x np'
+ *   out_partial  P x nt' x 2: 2 sum log L'_ii and sum alpha'_i^2 per tile column (the sentinel where the update wrote none)
+ *   out_winv     P x nt' x 8 x 256 (nullable): the inverses of the 16 x 16 pivot blocks, block b of tile column J column-major at
+ *                [((p nt' + J) 8 + b) 256 + 16 col + row] (the sentinel where the update wrote none)
+ *   out_info     P: 0, or the 1-based position of the first new diagonal entry that is not finite and positive
+ * AGP_ERR_ARG: n < 2, n > 1024, k < 1, k >= n, P < 1, P n^2 > 2^24 (or more than 2^27 doubles of padded tiles), positions not
+ * ascending or out of range, any null pointer but alpha0 and out_winv.  Borrows a workspace slot and reads or changes nothing
+ * else the context holds: not the store, the series, agp_get_remove_stats or agp_set_remove_update. */
+int agp_debug_remove_factor(agp_ctx* ctx, const double* L0 /* P*n*n */, const double* alpha0 /* P*n or NULL */, int64_t n, int32_t P,
+                            const int64_t* idx, int64_t k, double* out_L /* P*np'*np' */, double* out_alpha /* P*np' */,
+                            double* out_partial /* P*nt'*2 */, double* out_winv /* P*nt'*8*256 or NULL */, int32_t* out_info /* P */);
+
 /* Probe of the fp64 MFMA fragment layout: D = A(16x4) * B(4x16), row-major host arrays. */
 int agp_debug_mfma_probe(agp_ctx* ctx, const double* A, const double* B, double* D);
 

@@ -193,6 +193,29 @@ def test_updated_slot_is_a_first_class_factor(pkg, eng):
     assert (info == 0).all() and lp_err(lp, oracle_lp(pkg, nodes, noises, t2, x2)).max() <= LP_TOL
 
 
+def test_updated_slot_predicts_on_its_own_error_scale(pkg, eng):
+    """The updated factors end to end, output by output: the nine kernels of tests/_predict_cases.py at noise 1e-5, 1e-3 and 0.1 on
+    300 irregular times, [0, 130, 131] removed (the first tile column's panel and applies, a run across the tile boundary), then
+    predict_batch from the updated slots — every mean and variance within the resident route's own multiple of the reference
+    routes' distance from the 80-bit values (oracle/predcheck.py; the multiples of tests/test_gpu_predict_components.py)."""
+    import _predict_cases as PCS
+    import test_gpu_predict_components as TPC
+    n, idx = 300, [0, 130, 131]
+    ts, xs = PCS.irregular_series(n, seed=431)
+    keep = np.setdiff1d(np.arange(n), idx)
+    c = PCS.Case("removed_300", ts[keep].copy(), xs[keep].copy(), keep.size, PCS.general_queries(ts[keep]))
+    eng.set_data(ts, xs)
+    _, info = eng.logpdf_batch_extend(c.nodes, c.noises, check=False)
+    assert (info == 0).all()
+    assert eng.remove_data(idx) == c.n
+    st = eng.remove_stats()
+    assert st["updated"] == len(c.nodes) and st["dropped"] == 0 and st["panel_steps"] > 0
+    r0 = eng.predict_reuse_stats()["reused"]
+    res = TPC.predict(eng, c)
+    assert eng.predict_reuse_stats()["reused"] - r0 == len(c.nodes), eng.predict_reuse_stats()
+    TPC.check_all("resident after remove_data", res, c, key="resident joint_300")
+
+
 def test_sliding_window_of_40_steps(pkg, eng):
     """Remove the oldest point, append one, re-score: 40 steps at n = 300; every step within the tolerance of the oracle (no drift
     beyond it), every step an update followed by an extension."""
