@@ -397,6 +397,40 @@ constexpr int SERIES_QSLOT = 192;
 static_assert(SERIES_QSLOT >= SERIES_MAX_N && SERIES_QSLOT + 4 * 16 <= 256, "four waves' query entries behind the series' own");
 __host__ __device__ inline SeriesLds series_pred_lds(int n, int n_ops, int n_prm, int n_cp) { return series_lds(n, n_ops, n_prm, n_cp); }
 
+// The read-out of agp_predict_quantile_series_batch (agp_series_quantile_kernel.hpp) on the predictive launches' device outputs.
+// Series s's mixture: its P_s = pl_off[s + 1] - pl_off[s] particles plist[pl_off[s] ..] (ascending caller index), their weights
+// w[w_off[s] + j] padded with 0 to Pp_s = w_off[s + 1] - w_off[s] = ceil(P_s / 64) 64, and the packed rows of its m_s query points,
+// row i at row_off[s] + i Pp_s of cm / cs: entry j = particle j's raw mean / standard deviation, (0, 1) in the padding.
+struct SeriesQuantArgs {
+  int S, nq;
+  const long long* pt_off;   // [S + 1]
+  const long long* q_off;    // [S + 1]
+  const long long* out_off;  // [P + 1] particle p's block in mean / var (SeriesPredArgs::out_off)
+  const double* mean;        // the predictive's outputs (scaled space)
+  const double* var;
+  const int32_t* pred_info;  // [P] the predictive's info words (written for every launched particle: n_s > 0 or m_s > 0)
+  const long long* pl_off;   // [S + 1]
+  const long long* w_off;    // [S + 1]
+  const long long* row_off;  // [S + 1]
+  const int32_t* plist;      // [P]
+  const double* w;           // [w_off[S]]
+  const double* slope;       // [S] y_transform of series s: raw mean = (mu - intercept) / slope, raw variance = ivar * var
+  const double* intercept;   // [S]
+  const double* ivar;        // [S] 1 / slope^2
+  const double* q;           // [nq]
+  double tol;
+  long long max_iter;
+  double* cm;                // [row_off[S]]
+  double* cs;
+  int32_t* first_bad;        // [P] 0, or n_s + i + 1 for the first query i whose raw mean is not finite or raw variance negative / NaN
+  int32_t* bad;              // [S] some particle of the series has no predictive or a first_bad word (series with particles only)
+  double* out_x;             // [nq q_off[S]] series s's (nq, m_s) row-major block at nq q_off[s]
+  int32_t* out_conv;
+  int32_t* out_iters;
+  double* out_mean;          // [q_off[S]] or null: the mixture's marginal moments
+  double* out_var;
+};
+
 // Arguments of the probe instantiation k_series_logpdf<D, true> (agp_debug_series_factor): caller matrices of ONE size take the place
 // of series, programs and noise; the LDS map is series_lds(n, 0, 0, 0); workgroup b factors matrix b.
 struct SeriesProbeArgs {

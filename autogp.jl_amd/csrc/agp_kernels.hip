@@ -5,6 +5,7 @@
 #include "agp_chol_kernel.hpp"
 #include "agp_toep_kernel.hpp"
 #include "agp_quantile_kernel.hpp"
+#include "agp_series_quantile_kernel.hpp"
 #include "agp_sum_kernel.hpp"
 #include "agp_sample_kernel.hpp"
 #include "agp_mixmom_kernel.hpp"
@@ -173,6 +174,17 @@ void launch_mixture_quantile(hipStream_t st, const double* cm, const double* cs,
   const long long nw = (long long)m * nq;
   hipLaunchKernelGGL(k_mixture_quantile, dim3((unsigned)((nw + MQ_WAVES - 1) / MQ_WAVES)), dim3(64 * MQ_WAVES), 0, st, cm, cs, cw, Pp, m,
                      q, nq, tol, max_iter, out_x, out_conv, out_iters);
+}
+void launch_series_mix_readout(hipStream_t st, const SeriesQuantArgs& a, long long n_queries, long long max_rows_el) {
+  if (a.S <= 0) return;
+  // pack: a quarter of the largest series' elements per thread and pass, at most 256 workgroups per series
+  long long chunks = (max_rows_el + 1023) / 1024;
+  chunks = chunks < 1 ? 1 : chunks > 256 ? 256 : chunks;
+  hipLaunchKernelGGL(k_series_mix_pack, dim3((unsigned)a.S, (unsigned)chunks), dim3(256), 0, st, a);
+  const long long nw = n_queries * a.nq;
+  if (nw > 0) hipLaunchKernelGGL(k_series_mix_quantile, dim3((unsigned)((nw + MQ_WAVES - 1) / MQ_WAVES)), dim3(64 * MQ_WAVES), 0, st, a);
+  if (n_queries > 0 && (a.out_mean || a.out_var))
+    hipLaunchKernelGGL(k_series_mix_moments, dim3((unsigned)((n_queries + 255) / 256)), dim3(256), 0, st, a);
 }
 void launch_sum_readout(hipStream_t st, int P, const SumReadArgs& a) {
   hipLaunchKernelGGL(k_sum_readout, dim3((unsigned)((a.m + 255) / 256), P), dim3(256), 0, st, a);

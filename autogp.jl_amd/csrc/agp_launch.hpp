@@ -51,6 +51,10 @@ void launch_mfma_peak(int nblk, double* out, long long* cycles, int iters, int m
 void launch_mixture_pack(hipStream_t st, const double* means, const double* vars, int P, int Pp, int m, double* cm, double* cs);
 void launch_mixture_quantile(hipStream_t st, const double* cm, const double* cs, const double* cw, int Pp, int m, const double* q,
                              int nq, double tol, long long max_iter, double* out_x, int32_t* out_conv, int32_t* out_iters);
+// agp_predict_quantile_series_batch's read-out (agp_series.hip; agp_series_quantile_kernel.hpp): pack (always: it also writes the info
+// words), the searches (a.nq > 0) and the marginal moments (a.out_mean or a.out_var) of n_queries = q_off[S] query points;
+// max_rows_el = the largest m_s Pp_s of a series
+void launch_series_mix_readout(hipStream_t st, const SeriesQuantArgs& a, long long n_queries, long long max_rows_el);
 // predict_sum's read-out (agp_predict.hip): raw transform, F_1 intercept, marginal quantiles on a chunk's device marginals
 void launch_sum_readout(hipStream_t st, int P, const SumReadArgs& a);
 // posterior predictive samples (agp_sample.hip): the normals of every sample column, then per chunk one workgroup per (group of

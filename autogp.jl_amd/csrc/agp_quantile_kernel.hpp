@@ -79,19 +79,14 @@ __global__ __launch_bounds__(256) void k_mixture_pack(const double* __restrict__
   cs[g] = sg;
 }
 
-// out_x[k * m + i], out_conv / out_iters (may be null) likewise.  cw: Pp weights (0 in the padding).
-__global__ __launch_bounds__(256) void k_mixture_quantile(const double* __restrict__ cm, const double* __restrict__ cs,
-                                                          const double* __restrict__ cw, int Pp, int m, const double* __restrict__ q,
-                                                          int nq, double tol, long long max_iter, double* __restrict__ out_x,
-                                                          int32_t* __restrict__ out_conv, int32_t* __restrict__ out_iters) {
+// One search: the quantile qk of the mixture whose packed row is (rm, rs) with weights cw (Pp entries each, Pp a multiple of 64, weight
+// 0 in the padding), by all 64 lanes of one wave.  Every argument but `lane` is wave-uniform; x, conv and it come back with the same
+// bits in every lane.  The one body of every search kernel (k_mixture_quantile here, k_series_mix_quantile in
+// agp_series_quantile_kernel.hpp): a point's bits depend on its row, its weights, qk, tol and max_iter alone.
+__device__ __forceinline__ void mq_search(const double* __restrict__ rm, const double* __restrict__ rs, const double* __restrict__ cw,
+                                          int Pp, double qk, double tol, long long max_iter, int lane, double* out_x, int* out_conv,
+                                          long long* out_it) {
 #pragma clang fp contract(off)      // every product and sum rounded on its own, as the reference (and tests/_mixture_quantile_ref.py) do
-  const int lane = threadIdx.x & 63;
-  const unsigned wid = blockIdx.x * MQ_WAVES + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);     // (m * nq < 2^31: the host)
-  if (wid >= (unsigned)m * (unsigned)nq) return;
-  const unsigned i = wid % (unsigned)m, k = wid / (unsigned)m;
-  const double* __restrict__ rm = cm + (long long)i * Pp;
-  const double* __restrict__ rs = cs + (long long)i * Pp;
-  const double qk = q[k];
   double x = 0.0, x_max = __builtin_inf(), x_min = -__builtin_inf();
   long long it = 0;
   int conv = 0;
@@ -129,6 +124,22 @@ __global__ __launch_bounds__(256) void k_mixture_quantile(const double* __restri
       else if (lam == power) { bx = x; bX = x_max; bN = x_min; power *= 2; lam = 0; }
     }
   }
+  *out_x = x; *out_conv = conv; *out_it = it;
+}
+
+// out_x[k * m + i], out_conv / out_iters (may be null) likewise.  cw: Pp weights (0 in the padding).
+__global__ __launch_bounds__(256) void k_mixture_quantile(const double* __restrict__ cm, const double* __restrict__ cs,
+                                                          const double* __restrict__ cw, int Pp, int m, const double* __restrict__ q,
+                                                          int nq, double tol, long long max_iter, double* __restrict__ out_x,
+                                                          int32_t* __restrict__ out_conv, int32_t* __restrict__ out_iters) {
+  const int lane = threadIdx.x & 63;
+  const unsigned wid = blockIdx.x * MQ_WAVES + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);     // (m * nq < 2^31: the host)
+  if (wid >= (unsigned)m * (unsigned)nq) return;
+  const unsigned i = wid % (unsigned)m, k = wid / (unsigned)m;
+  double x;
+  long long it;
+  int conv;
+  mq_search(cm + (long long)i * Pp, cs + (long long)i * Pp, cw, Pp, q[k], tol, max_iter, lane, &x, &conv, &it);
   if (lane == 0) {
     const unsigned o = k * (unsigned)m + i;
     out_x[o] = x;

@@ -2,9 +2,11 @@
 // (agp_series_kernel.hpp: one workgroup per particle, covariance + Cholesky + forward solve + value in LDS), and
 // agp_logpdf_grad_series_batch, its value-and-gradient twin (k_series_logpdf_grad: L^-T, alpha and the contraction with dK / d theta
 // behind the value, same workgroup, same LDS), and agp_predict_series_batch, its predictive twin (k_series_predict: posterior mean and
-// marginal variance at every series' own query times from the factor the value has just left in LDS).  All three are one host
-// function — validation, series upload, launch classes and the value outputs are the same statements — with the gradient and the
-// prediction as options.  Stateless: the series
+// marginal variance at every series' own query times from the factor the value has just left in LDS), and
+// agp_predict_quantile_series_batch, the forecast band on top of it (the predictive launches' device outputs read out by
+// agp_series_quantile_kernel.hpp on the same stream: quantiles and marginal moments of every series' own mixture).  All four are one
+// host function — validation, series upload, launch classes and the value outputs are the same statements — with the gradient, the
+// prediction and the band as options.  Stateless: the series
 // travel with the call; the resident series, its tables, the factor store, the coalescer and every counter of the context are
 // neither read nor changed — only a workspace slot (stream, staging buffers) is borrowed, as in every batch entry.
 #include "agp_host.hpp"
@@ -27,18 +29,108 @@ struct SeriesPredOut {
   int64_t* off;              // [P + 1], written by the entry
 };
 
+// The band of agp_predict_quantile_series_batch: the mixtures' weights and transforms, the quantiles, and the outputs (host).
+struct SeriesQuantOut {
+  const double* weights;     // [P] particle p's weight inside its series' mixture
+  const double* y_slope;     // [S] or null (1)
+  const double* y_intercept; // [S] or null (0)
+  const double* q; int64_t nq; double tol; int64_t max_iter;
+  double* x; int32_t* conv; int32_t* iters;      // [nq q_off[S]]; conv / iters nullable
+  double* mix_mean; double* mix_var;              // [q_off[S]], nullable
+};
+
+// What the read-out kernels index with, built and checked on the host before anything is launched or written.
+struct QuantPlan {
+  std::vector<long long> tab;      // [pl_off (S + 1) | w_off (S + 1) | row_off (S + 1)]
+  std::vector<int32_t> plist;      // [P] the series' particles, series by series, ascending within each
+  std::vector<double> vals;        // [w (w_off[S], 0 in the padding) | slope (S) | intercept (S) | ivar (S) | q (nq)]
+  long long max_rows_el = 0;       // largest m_s Pp_s
+  size_t Q = 0, R = 0, W = 0;      // q_off[S], row_off[S], w_off[S]
+};
+
+// prefixes the message a shared check has just stored with the series it was about
+int fail_series(agp_ctx* c, int rc, int32_t s) {
+  std::string msg;
+  { std::lock_guard<std::mutex> g(c->mu); msg = c->err; }
+  return fail(c, rc, "series " + std::to_string(s) + ": " + msg);
+}
+
+int quant_plan(agp_ctx* c, int32_t S, int P, const int32_t* series, const int64_t* q_off, const SeriesQuantOut& qo, QuantPlan& pl) {
+  if (qo.nq < 0) return fail(c, AGP_ERR_ARG, "negative size");
+  if (!qo.q && qo.nq > 0) return fail(c, AGP_ERR_ARG, "null q");
+  for (int64_t k = 0; k < qo.nq; ++k)
+    if (!(qo.q[k] > 0.0 && qo.q[k] < 1.0)) return fail(c, AGP_ERR_ARG, "quantile must be in (0, 1)");
+  if (!qo.x && qo.nq > 0) return fail(c, AGP_ERR_ARG, "null pointer argument (out_x)");
+  if (!qo.weights && P > 0) return fail(c, AGP_ERR_ARG, "null weights");
+  pl.Q = S > 0 ? (size_t)q_off[S] : 0;
+  if ((int64_t)pl.Q >= ((int64_t)1 << 31) || (qo.nq > 0 && (int64_t)pl.Q * qo.nq >= ((int64_t)1 << 31)))
+    return fail(c, AGP_ERR_ARG, "nq * q_off[S] too large");
+  const size_t S1 = (size_t)S + 1;
+  pl.tab.assign(3 * S1, 0);
+  long long* pl_off = pl.tab.data();
+  long long* w_off = pl_off + S1;
+  long long* row_off = w_off + S1;
+  for (int p = 0; p < P; ++p) ++pl_off[series[p] + 1];
+  for (int32_t s = 0; s < S; ++s) pl_off[s + 1] += pl_off[s];
+  pl.plist.resize((size_t)P);
+  {
+    std::vector<long long> at(pl_off, pl_off + S);
+    for (int p = 0; p < P; ++p) pl.plist[(size_t)at[(size_t)series[p]]++] = p;
+  }
+  for (int32_t s = 0; s < S; ++s) {
+    const long long Ps = pl_off[s + 1] - pl_off[s], Pp = (Ps + 63) / 64 * 64, m = q_off[s + 1] - q_off[s];
+    w_off[s + 1] = w_off[s] + Pp;
+    row_off[s + 1] = row_off[s] + m * Pp;      // (m <= 2^30, Pp < 2^31 + 64: no overflow before the test)
+    if (row_off[s + 1] >= ((long long)1 << 31) || w_off[s + 1] >= ((long long)1 << 31))
+      return fail(c, AGP_ERR_ARG, "sum over the series of m_s * ceil(P_s / 64) * 64 too large");
+    pl.max_rows_el = std::max(pl.max_rows_el, m * Pp);
+  }
+  pl.W = (size_t)w_off[S]; pl.R = (size_t)row_off[S];
+  pl.vals.assign(pl.W + 3 * (size_t)S + (size_t)qo.nq, 0.0);
+  double* w = pl.vals.data();
+  double* slope = w + pl.W;
+  double* icpt = slope + S;
+  double* ivar = icpt + S;
+  std::vector<double> ws;
+  for (int32_t s = 0; s < S; ++s) {
+    slope[s] = qo.y_slope ? qo.y_slope[s] : 1.0;
+    icpt[s] = qo.y_intercept ? qo.y_intercept[s] : 0.0;
+    if (const int rc = check_y_transform(c, slope[s], icpt[s])) return fail_series(c, rc, s);
+    ivar[s] = 1.0 / (slope[s] * slope[s]);
+    const long long Ps = pl_off[s + 1] - pl_off[s];
+    if (Ps == 0) continue;
+    ws.resize((size_t)Ps);
+    for (long long j = 0; j < Ps; ++j) ws[(size_t)j] = qo.weights[pl.plist[(size_t)(pl_off[s] + j)]];
+    if (const int rc = check_weights(c, (int32_t)Ps, ws.data())) return fail_series(c, rc, s);
+    std::copy(ws.begin(), ws.end(), w + w_off[s]);
+  }
+  std::copy(qo.q, qo.q + qo.nq, ivar + S);
+  return AGP_OK;
+}
+
+// a band without a mixture behind it: NaN, nothing converged
+void quant_fill_nan(const SeriesQuantOut& qo, size_t from, size_t to, int64_t nq) {
+  const double nanv = std::numeric_limits<double>::quiet_NaN();
+  if (qo.x) std::fill(qo.x + from * nq, qo.x + to * nq, nanv);
+  if (qo.conv) std::fill(qo.conv + from * nq, qo.conv + to * nq, 0);
+  if (qo.iters) std::fill(qo.iters + from * nq, qo.iters + to * nq, 0);
+  if (qo.mix_mean) std::fill(qo.mix_mean + from, qo.mix_mean + to, nanv);
+  if (qo.mix_var) std::fill(qo.mix_var + from, qo.mix_var + to, nanv);
+}
+
 // go = null, po = null: values only.  go: also out_grad (agp_logpdf_grad_batch's layout) and out_gnoise.  po: also the posterior at
-// the series' query times; out_logpdf may then be null (pp.noise_pred null: the particle's own noise).
+// the series' query times; out_logpdf may then be null (pp.noise_pred null: the particle's own noise).  qo (with po, whose mean / var / off
+// are then null: the per-particle predictive stays on the device): the band of every series' mixture instead.
 int series_batch(agp_ctx* c, int32_t S, const int64_t* pt_off, const double* ts, const double* xs, const Particles& pp,
                  const int32_t* series, double* out_logpdf, int32_t* out_info, const GradOut* go = nullptr,
-                 const SeriesPredOut* po = nullptr) {
+                 const SeriesPredOut* po = nullptr, const SeriesQuantOut* qo = nullptr) {
   const int P = pp.P;
   char buf[256];
   if (!c) return fail(nullptr, AGP_ERR_ARG, "null context");
   if (S < 0 || P < 0) return fail(c, AGP_ERR_ARG, "negative number of series or particles");
-  if (P == 0) return AGP_OK;
+  if (P == 0 && !qo) return AGP_OK;
   if (!pt_off || !ts || !xs || !series || !pp.complete() || (!out_logpdf && !po) || !out_info) return fail(c, AGP_ERR_ARG, "null pointer argument");
-  if (po && (!po->q_off || !po->ts_pred || !po->mean || !po->var || !po->off))
+  if (po && (!po->q_off || !po->ts_pred || (!qo && (!po->mean || !po->var || !po->off))))
     return fail(c, AGP_ERR_ARG, "null pointer argument (q_off, ts_pred, out_mean, out_var or out_off)");
   const size_t n_prm_total = go ? (size_t)std::max(0, pp.prm_off[P]) : 0;
   if (go && !go->gnoise) return fail(c, AGP_ERR_ARG, "null pointer argument (out_grad_noise)");
@@ -78,6 +170,11 @@ int series_batch(agp_ctx* c, int32_t S, const int64_t* pt_off, const double* ts,
       snprintf(buf, sizeof buf, "particle %d: malformed program / parameter offsets", p);
       return fail(c, AGP_ERR_ARG, buf);
     }
+  QuantPlan qp;
+  if (qo) {
+    if (const int rc = quant_plan(c, S, P, series, po->q_off, *qo, qp)) return rc;
+    if (P == 0) { quant_fill_nan(*qo, 0, qp.Q, qo->nq); return AGP_OK; }      // (S series without a particle)
+  }
   // programs without any table of the resident series (no log|dt| table, no lag tables), in the caller's order
   Batch bt;
   CompileOpts co;
@@ -132,13 +229,14 @@ int series_batch(agp_ctx* c, int32_t S, const int64_t* pt_off, const double* ts,
   if (po) {
     ooff.assign((size_t)P + 1, 0);
     for (int p = 0; p < P; ++p) ooff[(size_t)p + 1] = ooff[(size_t)p] + nq[(size_t)p];
-    std::copy(ooff.begin(), ooff.end(), po->off);
+    if (po->off) std::copy(ooff.begin(), ooff.end(), po->off);
   }
   const size_t n_out = po ? (size_t)ooff[(size_t)P] : 0;
   if (wg.empty()) {      // every particle scores an empty series (src/inference_smc_anneal_data.jl:185-187) and has nothing to predict
     if (out_logpdf) std::fill(out_logpdf, out_logpdf + P, 0.0);
     std::fill(out_info, out_info + P, 0);
     if (go) { std::fill(go->gnoise, go->gnoise + P, 0.0); std::fill(go->grad, go->grad + n_prm_total, 0.0); }
+    if (qo) quant_fill_nan(*qo, 0, qp.Q, qo->nq);      // (only series without a particle have query points here)
     return AGP_OK;
   }
 
@@ -178,6 +276,18 @@ int series_batch(agp_ctx* c, int32_t S, const int64_t* pt_off, const double* ts,
     HIPCHK(c, s->pred_mean.ensure(sizeof(double) * std::max<size_t>(1, n_out)));
     HIPCHK(c, s->pred_var.ensure(sizeof(double) * std::max<size_t>(1, n_out)));
   }
+  // the band: x and the moments in sq_out, the flags in sq_flag = [converged | iterations | first_bad (P) | bad (S)]
+  const size_t nx = qo ? qp.Q * (size_t)qo->nq : 0;
+  const bool want_mom = qo && (qo->mix_mean || qo->mix_var);
+  const size_t S1 = (size_t)S + 1, o_plist = sizeof(long long) * 3 * S1;
+  if (qo) {
+    HIPCHK(c, s->sq_tab.ensure(o_plist + sizeof(int32_t) * (size_t)P));
+    HIPCHK(c, s->sq_w.ensure(sizeof(double) * std::max<size_t>(1, qp.vals.size())));
+    HIPCHK(c, s->sq_cm.ensure(sizeof(double) * std::max<size_t>(1, qp.R)));
+    HIPCHK(c, s->sq_cs.ensure(sizeof(double) * std::max<size_t>(1, qp.R)));
+    HIPCHK(c, s->sq_out.ensure(sizeof(double) * std::max<size_t>(1, nx + 2 * qp.Q)));
+    HIPCHK(c, s->sq_flag.ensure(sizeof(int32_t) * (2 * nx + (size_t)P + (size_t)S)));
+  }
   std::vector<long long> off64(pt_off, pt_off + S + 1);
   PinnedUploads up;
   up.add(s->hdr.p, bt.hdr.data(), sizeof(ProgHdr) * (size_t)P);
@@ -207,6 +317,11 @@ int series_batch(agp_ctx* c, int32_t S, const int64_t* pt_off, const double* ts,
     up.add(s->tt.as<double>() + 2 * npts, po->ts_pred, sizeof(double) * nqt);
     up.add(s->noise_pred.p, pp.noise_pred ? pp.noise_pred : pp.noise, sizeof(double) * (size_t)P);
   }
+  if (qo) {
+    up.add(s->sq_tab.p, qp.tab.data(), o_plist);
+    up.add(s->sq_tab.as<char>() + o_plist, qp.plist.data(), sizeof(int32_t) * (size_t)P);
+    up.add(s->sq_w.p, qp.vals.data(), sizeof(double) * qp.vals.size());
+  }
   HIPCHK(c, up.flush(s->h_stage, s->up_blob, st));
 
   SeriesGradArgs sa = {};      // (the value launches take its SeriesArgs part)
@@ -221,10 +336,10 @@ int series_batch(agp_ctx* c, int32_t S, const int64_t* pt_off, const double* ts,
   sa.hdr = s->hdr.as<ProgHdr>(); sa.ops = s->ops.as<uint8_t>(); sa.prm = s->prm.as<double>(); sa.noise = s->noise.as<double>();
   sa.out_lp = s->out_lp.as<double>(); sa.out_info = reinterpret_cast<int32_t*>(s->out_lp.as<double>() + P);
   const bool prof = c->profiling;
-  hipEvent_t ev[2] = {nullptr, nullptr};
+  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
   if (prof) {
-    while (s->events.size() < 2) { hipEvent_t e; HIPCHK(c, hipEventCreate(&e)); s->events.push_back(e); }
-    ev[0] = s->events[0]; ev[1] = s->events[1];
+    while (s->events.size() < 3) { hipEvent_t e; HIPCHK(c, hipEventCreate(&e)); s->events.push_back(e); }
+    ev[0] = s->events[0]; ev[1] = s->events[1]; ev[2] = s->events[2];
     HIPCHK(c, hipEventRecord(ev[0], st));
   }
   size_t w0 = 0;
@@ -248,16 +363,43 @@ int series_batch(agp_ctx* c, int32_t S, const int64_t* pt_off, const double* ts,
       w0 += v.size();
     }
   if (prof) HIPCHK(c, hipEventRecord(ev[1], st));
+  if (qo) {
+    // the read-out, behind the predictive launches on the same stream: their means and variances never leave the device
+    SeriesQuantArgs qa = {};
+    qa.S = S; qa.nq = (int)qo->nq;
+    qa.pt_off = sa.pt_off;
+    qa.q_off = reinterpret_cast<const long long*>(s->map.as<char>() + o_qoff);
+    qa.out_off = reinterpret_cast<const long long*>(s->map.as<char>() + o_ooff);
+    qa.mean = s->pred_mean.as<double>(); qa.var = s->pred_var.as<double>(); qa.pred_info = sa.out_info;
+    qa.pl_off = s->sq_tab.as<long long>(); qa.w_off = qa.pl_off + S1; qa.row_off = qa.w_off + S1;
+    qa.plist = reinterpret_cast<const int32_t*>(s->sq_tab.as<char>() + o_plist);
+    qa.w = s->sq_w.as<double>(); qa.slope = qa.w + qp.W; qa.intercept = qa.slope + S; qa.ivar = qa.intercept + S; qa.q = qa.ivar + S;
+    qa.tol = qo->tol; qa.max_iter = (long long)qo->max_iter;
+    qa.cm = s->sq_cm.as<double>(); qa.cs = s->sq_cs.as<double>();
+    qa.out_x = s->sq_out.as<double>();
+    qa.out_mean = want_mom ? qa.out_x + nx : nullptr; qa.out_var = want_mom ? qa.out_x + nx + qp.Q : nullptr;
+    qa.out_conv = s->sq_flag.as<int32_t>(); qa.out_iters = qa.out_conv + nx;
+    qa.first_bad = qa.out_iters + nx; qa.bad = qa.first_bad + P;
+    launch_series_mix_readout(st, qa, (long long)qp.Q, qp.max_rows_el);
+    HIPCHK(c, hipGetLastError());
+    if (prof) HIPCHK(c, hipEventRecord(ev[2], st));
+  }
   const size_t out_bytes = sizeof(double) * (size_t)P + sizeof(int32_t) * (size_t)P;
   const size_t o_gn = (out_bytes + 7) & ~(size_t)7, o_gr = o_gn + sizeof(double) * (size_t)P;      // gradient outputs behind [logpdf | info]
-  HIPCHK(c, s->h_out.ensure(go ? o_gr + sizeof(double) * n_prm_total : po ? o_gn + 2 * sizeof(double) * n_out : out_bytes));
+  const size_t n_band = nx + (want_mom ? 2 * qp.Q : 0), o_bf = o_gn + sizeof(double) * n_band;     // band: [x | mean | var], then the flags
+  HIPCHK(c, s->h_out.ensure(go ? o_gr + sizeof(double) * n_prm_total : qo ? o_bf + sizeof(int32_t) * (2 * nx + (size_t)P)
+                               : po ? o_gn + 2 * sizeof(double) * n_out : out_bytes));
   HIPCHK(c, hipMemcpyAsync(s->h_out.p, s->out_lp.p, out_bytes, hipMemcpyDeviceToHost, st));
   if (go) {
     char* ho = static_cast<char*>(s->h_out.p);
     HIPCHK(c, hipMemcpyAsync(ho + o_gn, s->dgnoise.p, sizeof(double) * (size_t)P, hipMemcpyDeviceToHost, st));
     if (n_prm_total > 0) HIPCHK(c, hipMemcpyAsync(ho + o_gr, s->dgrad.p, sizeof(double) * n_prm_total, hipMemcpyDeviceToHost, st));
   }
-  if (po && n_out > 0) {      // [mean | var] behind [logpdf | info]
+  if (qo) {      // [x | mean | var | converged | iterations | first_bad] behind [logpdf | info]
+    char* ho = static_cast<char*>(s->h_out.p);
+    if (n_band > 0) HIPCHK(c, hipMemcpyAsync(ho + o_gn, s->sq_out.p, sizeof(double) * n_band, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(ho + o_bf, s->sq_flag.p, sizeof(int32_t) * (2 * nx + (size_t)P), hipMemcpyDeviceToHost, st));
+  } else if (po && n_out > 0) {      // [mean | var] behind [logpdf | info]
     char* ho = static_cast<char*>(s->h_out.p);
     HIPCHK(c, hipMemcpyAsync(ho + o_gn, s->pred_mean.p, sizeof(double) * n_out, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipMemcpyAsync(ho + o_gn + sizeof(double) * n_out, s->pred_var.p, sizeof(double) * n_out, hipMemcpyDeviceToHost, st));
@@ -277,18 +419,32 @@ int series_batch(agp_ctx* c, int32_t S, const int64_t* pt_off, const double* ts,
       for (int32_t q = pp.prm_off[p]; q < pp.prm_off[p + 1]; ++q) go->grad[q] = empty ? 0.0 : hgr[q];
     }
   }
-  if (po && n_out > 0) {      // every particle with query points was launched and wrote its whole block
+  if (qo) {
+    const char* ho = static_cast<const char*>(s->h_out.p);
+    const double* hb = reinterpret_cast<const double*>(ho + o_gn);
+    const int32_t* hf = reinterpret_cast<const int32_t*>(ho + o_bf);
+    // raw_components' rule: a particle whose predictive exists but whose raw mean or variance is unusable at query i reports n_s + i + 1
+    for (int p = 0; p < P; ++p)
+      if (out_info[p] == 0 && nq[(size_t)p] > 0 && hf[2 * nx + (size_t)p] != 0) out_info[p] = hf[2 * nx + (size_t)p];
+    if (qo->x) std::copy(hb, hb + nx, qo->x);
+    if (qo->conv) std::copy(hf, hf + nx, qo->conv);
+    if (qo->iters) std::copy(hf + nx, hf + 2 * nx, qo->iters);
+    if (qo->mix_mean) std::copy(hb + nx, hb + nx + qp.Q, qo->mix_mean);
+    if (qo->mix_var) std::copy(hb + nx + qp.Q, hb + nx + 2 * qp.Q, qo->mix_var);
+  } else if (po && n_out > 0) {      // every particle with query points was launched and wrote its whole block
     const double* hm = reinterpret_cast<const double*>(static_cast<const char*>(s->h_out.p) + o_gn);
     std::copy(hm, hm + n_out, po->mean);
     std::copy(hm + n_out, hm + 2 * n_out, po->var);
   }
   if (prof) {
     // agp_get_timing: out[0] = out[2] = the value kernels of the call (covariance, factorisation, solve and value are one kernel)
-    float ms = 0.f;
+    float ms = 0.f, rd = 0.f;
     HIPCHK(c, hipEventElapsedTime(&ms, ev[0], ev[1]));
+    if (qo) HIPCHK(c, hipEventElapsedTime(&rd, ev[1], ev[2]));
     std::lock_guard<std::mutex> g(c->mu);
     for (double& t : c->timing) t = 0.0;
     c->timing[0] = ms; c->timing[2] = ms;
+    c->timing[4] = rd;      // the band's three read-out kernels (0 in the other entries)
   }
   return AGP_OK;
 }
@@ -371,6 +527,21 @@ int agp_predict_series_batch(agp_ctx* c, int32_t S, const int64_t* pt_off, const
   return abi_guard(c, [&] {
     const SeriesPredOut po{q_off, ts_pred, out_mean, out_var, out_off};
     return series_batch(c, S, pt_off, ts, xs, {P, op_off, ops, prm_off, prm, noise, noise_pred}, series, out_logpdf, out_info, nullptr, &po);
+  });
+}
+
+int agp_predict_quantile_series_batch(agp_ctx* c, int32_t S, const int64_t* pt_off, const double* ts, const double* xs,
+                                      const int64_t* q_off, const double* ts_pred, int32_t P, const int32_t* series, const int32_t* op_off,
+                                      const uint8_t* ops, const int32_t* prm_off, const double* prm, const double* noise,
+                                      const double* noise_pred, const double* weights, const double* y_slope, const double* y_intercept,
+                                      const double* q, int64_t nq, double tol, int64_t max_iter, double* out_x, int32_t* out_converged,
+                                      int32_t* out_iters, double* out_mix_mean, double* out_mix_var, double* out_logpdf,
+                                      int32_t* out_info) {
+  return abi_guard(c, [&] {
+    const SeriesPredOut po{q_off, ts_pred, nullptr, nullptr, nullptr};
+    const SeriesQuantOut qo{weights, y_slope, y_intercept, q, nq, tol, max_iter, out_x, out_converged, out_iters, out_mix_mean, out_mix_var};
+    return series_batch(c, S, pt_off, ts, xs, {P, op_off, ops, prm_off, prm, noise, noise_pred}, series, out_logpdf, out_info, nullptr, &po,
+                        &qo);
   });
 }
 

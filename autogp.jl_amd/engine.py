@@ -12,6 +12,7 @@ construction raises.
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import os
 from pathlib import Path
@@ -37,7 +38,7 @@ EXPORTED_SYMBOLS = [
     "agp_predict_sample_batch", "agp_mixture_moments", "agp_predict_mixture_batch", "agp_get_mixture_stats",
     "agp_remove_data", "agp_get_remove_stats", "agp_set_remove_update", "agp_remove_data_multi",
     "agp_debug_factor_batch", "agp_logpdf_series_batch", "agp_debug_series_factor", "agp_logpdf_grad_series_batch",
-    "agp_predict_series_batch", "agp_debug_remove_factor",
+    "agp_predict_series_batch", "agp_debug_remove_factor", "agp_predict_quantile_series_batch",
 ]
 COMM_ID_BYTES = 128
 SERIES_MAX_N = 176      # AGP_SERIES_MAX_N of include/autogp_hip.h: the longest series of logpdf_series_batch
@@ -109,6 +110,10 @@ def load_library(path=None):
     lib.agp_predict_series_batch.argtypes = [vp, C.c_int32, C.POINTER(C.c_int64), dp, dp, C.POINTER(C.c_int64), dp, C.c_int32, ip, ip, u8p,
                                              ip, dp, dp, dp, dp, dp, C.POINTER(C.c_int64), dp, ip]
     lib.agp_predict_series_batch.restype = C.c_int
+    lib.agp_predict_quantile_series_batch.argtypes = [vp, C.c_int32, C.POINTER(C.c_int64), dp, dp, C.POINTER(C.c_int64), dp, C.c_int32, ip, ip,
+                                                      u8p, ip, dp, dp, dp, dp, dp, dp, dp, C.c_int64, C.c_double, C.c_int64, dp, ip, ip,
+                                                      dp, dp, dp, ip]
+    lib.agp_predict_quantile_series_batch.restype = C.c_int
     lib.agp_logpdf_grad_batch.argtypes = [vp, C.c_int64, C.c_int32, ip, u8p, ip, dp, dp, dp, dp, dp, ip]
     lib.agp_logpdf_grad_batch.restype = C.c_int
     lib.agp_logpdf_grad.argtypes = [vp, C.c_int64, u8p, C.c_int32, dp, C.c_int32, C.c_double, dp, dp, dp, ip]
@@ -294,6 +299,38 @@ def pack_queries(queries, n_series, noise_pred=None, P=None):
         if noise_pred.shape != (P,):
             raise ValueError("one noise_pred per particle required")
     return q_off, ts_pred, noise_pred
+
+
+def pack_series_mixture(series_index, S, weights=None, log_weights=None):
+    """The mixtures of predict_quantile_series_batch: (lists, weights) — lists[s] the particles p with series_index[p] == s in
+    ascending p (int64; empty for a series without particles), and weights (P,) float64, particle p's weight inside ITS series'
+    mixture.  Exactly one of `weights` (returned as given) and `log_weights` (normalised per series by a max-shifted softmax:
+    exp(lw - max lw_s) / sum over the series) must be given.  Raises ValueError on anything but one vector of P entries each, on a
+    series index outside [0, S), and when both or neither of weights / log_weights are given."""
+    if (weights is None) == (log_weights is None):
+        raise ValueError("exactly one of weights and log_weights required")
+    sidx = np.asarray(series_index)
+    if sidx.ndim != 1 or (sidx.size and sidx.dtype.kind not in "iu"):
+        raise ValueError("series_index must be a vector of integers")
+    sidx = sidx.astype(np.int64)
+    S = int(S)
+    if S < 0 or (sidx.size and (sidx.min() < 0 or sidx.max() >= S)):
+        raise ValueError(f"series indexes must lie in [0, {S})")
+    given = _f64(weights if weights is not None else log_weights)
+    if given.shape != sidx.shape:
+        raise ValueError(f"{'weights' if weights is not None else 'log_weights'} has shape {given.shape}, expected {sidx.shape}")
+    lists = [np.flatnonzero(sidx == s) for s in range(S)]
+    if weights is not None:
+        return lists, given.copy()
+    w = np.zeros(sidx.shape[0])
+    for sel in lists:
+        if sel.size:
+            e = np.exp(given[sel] - given[sel].max())
+            w[sel] = e / e.sum()
+    return lists, w
+
+
+SeriesBand = collections.namedtuple("SeriesBand", "x converged iters mean var logpdf info")
 
 
 def check_remove_indexes(indexes, n_max):
@@ -527,6 +564,59 @@ class GPEngine:
         means = [mean[out_off[p]:out_off[p + 1]] for p in range(P)]
         vars_ = [var[out_off[p]:out_off[p + 1]] for p in range(P)]
         return (means, vars_, lp, info) if want_logpdf else (means, vars_, info)
+
+    def predict_quantile_series_batch(self, series, queries, nodes, noises, series_index, weights, q, y_transforms=None, noise_pred=None,
+                                      tol=1e-5, max_iter=10**6, want_moments=False, want_logpdf=False, check=True, programs=None):
+        """agp_predict_quantile_series_batch: the forecast bands of many short series in one call — predict_series_batch, then on the
+        device the quantiles q (a scalar or a vector) of every series' own mixture of its particles' raw-space predictives, and with
+        want_moments that mixture's marginal mean and variance.  weights[p] is particle p's weight inside the mixture of
+        series[series_index[p]] (each series' weights sum to 1; pack_series_mixture normalises log-weights); y_transforms: one
+        (slope, intercept) pair per series (None: (1, 0)).  Returns SeriesBand(x, converged, iters, mean, var, logpdf, info): x,
+        converged and iters are lists over the series, each shaped as mixture_quantile returns it — (m_s, nq), or (m_s,) for a scalar
+        q (views into one array per output, as predict_series_batch's); mean / var (lists of (m_s,) arrays) and logpdf (P,) are None
+        unless asked for.  A series without particles, or with a
+        particle whose info != 0 (PosDefException when check), gets NaN and converged False."""
+        pt_off, ts, xs, (op_off, ops, prm_off, prm), P, noises, sidx = series_call_args(series, nodes, noises, series_index, programs)
+        S = pt_off.shape[0] - 1
+        q_off, ts_pred, noise_pred = pack_queries(queries, S, None if noise_pred is None else np.broadcast_to(noise_pred, (P,)), P)
+        weights = _f64(weights)
+        if weights.shape != (P,):
+            raise ValueError(f"weights has shape {weights.shape}, expected ({P},)")
+        slope = icpt = None
+        if y_transforms is not None:
+            yt = _f64(y_transforms)
+            if yt.shape != (S, 2):
+                raise ValueError(f"y_transforms has shape {yt.shape}, expected ({S}, 2): one (slope, intercept) per series")
+            slope, icpt = np.ascontiguousarray(yt[:, 0]), np.ascontiguousarray(yt[:, 1])
+        qa = _f64(np.atleast_1d(q)); nq = qa.shape[0]
+        Q = int(q_off[-1])
+        x = np.empty(max(1, nq * Q)); conv = np.zeros(max(1, nq * Q), dtype=np.int32); iters = np.zeros(max(1, nq * Q), dtype=np.int32)
+        mean = np.empty(max(1, Q)) if want_moments else None
+        var = np.empty(max(1, Q)) if want_moments else None
+        lp = np.empty(P, dtype=np.float64) if want_logpdf else None
+        info = np.zeros(max(1, P), dtype=np.int32)
+        ts_arg = ts if ts.size else np.zeros(1)
+        xs_arg = xs if xs.size else np.zeros(1)
+        tq_arg = ts_pred if ts_pred.size else np.zeros(1)
+        prm_arg = prm if prm.size else np.zeros(1)
+        i64 = C.POINTER(C.c_int64)
+        self._check(self._lib.agp_predict_quantile_series_batch(
+            self._ctx, S, pt_off.ctypes.data_as(i64), _dp(ts_arg), _dp(xs_arg), q_off.ctypes.data_as(i64), _dp(tq_arg), P, _ip(sidx),
+            _ip(op_off), _u8(ops), _ip(prm_off), _dp(prm_arg), _dp(noises), _dp(noise_pred), _dp(weights), _dp(slope), _dp(icpt), _dp(qa),
+            nq, float(tol), int(max_iter), _dp(x), _ip(conv), _ip(iters), _dp(mean), _dp(var), _dp(lp), _ip(info)))
+        info = info[:P]
+        if check and (info > 0).any():
+            p = int(np.argmax(info > 0))
+            raise PosDefException(int(info[p]), p)
+        # series s's (nq, m_s) row-major block, seen as (m_s, nq) — or (m_s,) for a scalar q: views into the call's arrays
+        conv = conv.astype(bool)
+        lo = (nq * q_off).tolist(); qo = q_off.tolist()
+        if np.ndim(q) == 0:
+            blocks = lambda a: [a[lo[s]:lo[s + 1]] for s in range(S)]
+        else:
+            blocks = lambda a: [a[lo[s]:lo[s + 1]].reshape(nq, qo[s + 1] - qo[s]).T for s in range(S)]
+        cut = lambda a: None if a is None else [a[qo[s]:qo[s + 1]] for s in range(S)]
+        return SeriesBand(blocks(x), blocks(conv), blocks(iters), cut(mean), cut(var), lp, info)
 
     def logpdf_batch_extend(self, nodes, noises, n=None, check=True, programs=None):
         """agp_logpdf_batch_extend: like logpdf_batch, but the factors stay resident and a later call on a longer
@@ -1416,6 +1506,20 @@ def predict_quantile(engine, nodes, noises, log_weights, ts_pred, q, y_transform
     x, conv, _, _ = engine.predict_quantile_batch(nodes, noises, ts_pred, w, q, noise_pred=npred, y_transform=y_transform, tol=tol,
                                                   max_iter=max_iter)
     return x, (bool(conv.all()) if np.ndim(q) == 0 else conv.all(axis=0))
+
+
+def predict_quantile_series(engine, series, queries, nodes, noises, series_index, log_weights, q, y_transforms=None, noise_pred=None,
+                            tol=1e-5, max_iter=10**6):
+    """predict_quantile for callers that hold one model per short series: particle p belongs to the model of
+    series[series_index[p]], whose mixture weighs it by the softmax of log_weights over THAT series' particles
+    (pack_series_mixture); one call of GPEngine.predict_quantile_series_batch serves every series.  y_transforms: one (slope,
+    intercept) per series.  Returns a list over the series of (x, success), each as predict_quantile returns them: x of shape (m_s,)
+    and a bool for a scalar q; (m_s, nq) and an (nq,) bool array for a vector q.  Raises PosDefException when a particle has no
+    predictive."""
+    _, w = pack_series_mixture(series_index, len(series), log_weights=log_weights)
+    band = engine.predict_quantile_series_batch(series, queries, nodes, noises, series_index, w, q, y_transforms=y_transforms,
+                                                noise_pred=noise_pred, tol=tol, max_iter=max_iter)
+    return [(x, (bool(c.all()) if np.ndim(q) == 0 else c.all(axis=0))) for x, c in zip(band.x, band.converged)]
 
 
 def predict_rand(engine, nodes, noises, log_weights, ts_pred, n_samples=None, seed=0, y_transform=(1.0, 0.0), noise_pred=None):

@@ -285,6 +285,58 @@ function predict_series_batch(eng::Engine, series::Vector{<:Tuple{Vector{Float64
     return means, vars, out, info
 end
 
+"Forecast bands of many short series in one call (agp_predict_quantile_series_batch): `predict_series_batch`, then on the device the
+quantiles `q` of every series' own mixture of its particles' raw-space predictives, and that mixture's marginal mean and variance.
+`weights[p]` is particle `p`'s weight inside the mixture of `series[series_index[p]]` (each series' weights sum to 1);
+`y_transforms[s] = (slope, intercept)` of series `s` (`nothing`: (1, 0)).  Returns `(x, converged, iters, mean, var, logpdf, info)`:
+`x[s]` is `m_s x length(q)`, `converged[s]` / `iters[s]` likewise, `mean[s]` / `var[s]` have length `m_s`.  A series without particles,
+or with a particle whose info != 0, gets NaN and nothing converged."
+function predict_quantile_series_batch(eng::Engine, series::Vector{<:Tuple{Vector{Float64},Vector{Float64}}},
+                                       queries::Vector{Vector{Float64}}, nodes::Vector{<:GP.Node}, noises::Vector{Float64},
+                                       series_index::Vector{<:Integer}, weights::Vector{Float64}, q::Vector{Float64};
+                                       y_transforms::Union{Nothing,Vector{Tuple{Float64,Float64}}}=nothing,
+                                       noise_pred::Union{Nothing,Vector{Float64}}=nothing, tol::Float64=1e-5, max_iter::Integer=10^6)
+    P = length(nodes); S = length(series)
+    (length(noises) == P && length(series_index) == P && length(weights) == P) ||
+        throw(ArgumentError("one noise, one series index and one weight per particle required"))
+    length(queries) == S || throw(ArgumentError("one vector of query times per series required"))
+    (noise_pred === nothing || length(noise_pred) == P) || throw(ArgumentError("one noise_pred per particle required"))
+    (y_transforms === nothing || length(y_transforms) == S) || throw(ArgumentError("one (slope, intercept) per series required"))
+    all(i -> 1 <= i <= S, series_index) || throw(ArgumentError("series index outside 1:$S"))
+    pt_off = Int64[0]; ts = Float64[]; xs = Float64[]; q_off = Int64[0]; tq = Float64[]
+    for (s, (t, x)) in enumerate(series)
+        length(t) == length(x) || throw(ArgumentError("series $s: ts and xs must have equal lengths"))
+        length(t) <= SERIES_MAX_N || throw(ArgumentError("series $s has $(length(t)) points, more than SERIES_MAX_N ($SERIES_MAX_N)"))
+        append!(ts, t); append!(xs, x); push!(pt_off, length(ts))
+        append!(tq, queries[s]); push!(q_off, length(tq))
+    end
+    isempty(ts) && (push!(ts, 0.0); push!(xs, 0.0))
+    isempty(tq) && push!(tq, 0.0)
+    sidx = Int32[Int32(i - 1) for i in series_index]
+    op_off, ops, prm_off, prm = encode_batch(nodes)
+    slope = y_transforms === nothing ? ones(Float64, max(1, S)) : Float64[t[1] for t in y_transforms]
+    icpt = y_transforms === nothing ? zeros(Float64, max(1, S)) : Float64[t[2] for t in y_transforms]
+    nq = length(q); Q = Int(q_off[end])
+    x = Vector{Float64}(undef, max(1, nq * Q)); conv = zeros(Int32, max(1, nq * Q)); iters = zeros(Int32, max(1, nq * Q))
+    mean = Vector{Float64}(undef, max(1, Q)); var = Vector{Float64}(undef, max(1, Q))
+    out = Vector{Float64}(undef, max(1, P)); info = zeros(Int32, max(1, P))
+    np = noise_pred === nothing ? noises : noise_pred
+    GC.@preserve pt_off ts xs q_off tq sidx op_off ops prm_off prm noises np weights slope icpt q x conv iters mean var out info check(eng, ccall((:agp_predict_quantile_series_batch, LIB), Cint,
+        (Ptr{Cvoid}, Int32, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Int32, Ptr{Int32}, Ptr{Int32}, Ptr{UInt8},
+         Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Float64,
+         Int64, Ptr{Float64}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
+        eng.ptr, S, pt_off, ts, xs, q_off, tq, P, sidx, op_off, ops, prm_off, prm, noises, np, weights, slope, icpt, q, nq, tol,
+        max_iter, x, conv, iters, mean, var, out, info))
+    # series s's block is (nq, m_s) row-major: column-major it is the m_s x nq matrix
+    block(a, s) = reshape(a[nq * q_off[s] + 1:nq * q_off[s + 1]], Int(q_off[s + 1] - q_off[s]), nq)
+    xs_ = [block(x, s) for s in 1:S]
+    cs_ = [block(conv, s) .!= 0 for s in 1:S]
+    is_ = [block(iters, s) for s in 1:S]
+    means = [mean[q_off[s] + 1:q_off[s + 1]] for s in 1:S]
+    vars = [var[q_off[s] + 1:q_off[s + 1]] for s in 1:S]
+    return xs_, cs_, is_, means, vars, out[1:P], info[1:P]
+end
+
 "(extended, from_scratch, tile_rows_reused, tile_rows_total, evicted_before_reuse, slots, callers, occupied, capacity_tile_rows, growth_copies) of the factor store"
 function extend_stats(eng::Engine)
     out = zeros(Int64, 10)

@@ -190,6 +190,49 @@ int agp_predict_series_batch(agp_ctx* ctx, int32_t S, const int64_t* pt_off /* S
                              double* out_mean, double* out_var, int64_t* out_off /* P+1 */,
                              double* out_logpdf /* P or NULL */, int32_t* out_info /* P */);
 
+/* Forecast BANDS of many short series in one call: predict_quantile (src/api.jl:547-596) and the mixture mean of predict_mvn for
+ * callers that hold one model per short series — agp_predict_series_batch followed, on the device and on the same stream, by the
+ * read-out of every series' own mixture; what comes back is the band, not the P*m per-particle means and variances, and the call
+ * synchronises once.  The resident-series twin is agp_predict_quantile_batch.
+ * Predictive: exactly agp_predict_series_batch — arguments S .. noise_pred, validation and messages, LDS classes and launches, the
+ *   noise_pred rule, the prior predictive of an empty series; out_logpdf (P, or NULL) is bit-identical to that entry's.
+ * Mixture of series s: the particles p with series[p] == s, in ascending p (they need not be adjacent), with weights[p] — the weights
+ *   of ONE series are finite, >= 0 and sum to 1 (rtol sqrt(eps)), as agp_mixture_quantile asks of its own.  A series without a
+ *   particle is no error: its outputs are NaN, converged and iterations 0.
+ * Raw space: agp_predict_quantile_batch's transform with the series' own (y_slope[s], y_intercept[s]) (NULL: 1 and 0):
+ *   mu_raw = (mu - b) / a, var_raw = (1 / (a a)) var, 1 / (a a) formed once in double.
+ * out_info[p]: the predictive's word; where that is 0 and a raw mean is not finite or a raw variance negative or NaN, n_s + i + 1 for
+ *   the first such query i (0-based).  If ANY particle of a series has info != 0 — whatever its weight — that series' x and moments
+ *   are NaN, its converged flags and iteration counts 0; every other series' bits are untouched.
+ * Quantiles: 0 < q[k] < 1.  Series s's block of out_x starts at nq * q_off[s] and is (nq, m_s) row-major — agp_mixture_quantile's
+ *   layout per series — out_converged and out_iters (nullable) likewise; its bits are those of agp_mixture_quantile(tol, max_iter) on
+ *   the series' stacked (P_s, m_s) raw components (one search kernel body serves both).  nq == 0 is valid: moments only.
+ * Moments: out_mix_mean / out_mix_var (q_off[S] each, nullable) at q_off[s] + i: the marginal mean and variance of the raw-space
+ *   mixture (space 0 only), the bits of agp_mixture_moments on the stacked block: sums about the first component of positive weight,
+ *   sequentially in particle order, weight-0 components skipped.
+ * Device: a ragged pack kernel (transform, correctly rounded sqrt, one padded row per (series, query), info words), one wave per
+ *   (series, query, quantile) for the searches, one thread per (series, query) for the moments; every word they read was written
+ *   by the same call.  With profiling on, agp_get_timing's out[0] = out[2] = the predictive kernels as for agp_predict_series_batch
+ *   and out[4] = the three read-out kernels together.
+ * Stateless and re-entrant exactly as agp_predict_series_batch.  A series' result bits depend only on its own data, queries,
+ *   particles (in their order), weights, transform, q, tol and max_iter — not on the other series, their order, or nq.
+ * The WHOLE call is rejected, and nothing is written to any output, with everything agp_predict_series_batch reports, and with
+ *   AGP_ERR_ARG: the weights of one series not finite, negative or not summing to 1, a y_slope that is 0 or not finite, an
+ *   y_intercept that is not finite (each message names the series); q[k] outside (0, 1); nq < 0; a NULL weights, q (nq > 0) or out_x
+ *   (nq > 0); nq * q_off[S] or sum_s m_s * ceil(P_s / 64) * 64 at or above 2^31. */
+int agp_predict_quantile_series_batch(agp_ctx* ctx, int32_t S, const int64_t* pt_off /* S+1 */, const double* ts, const double* xs,
+                                      const int64_t* q_off /* S+1 */, const double* ts_pred,
+                                      int32_t P, const int32_t* series /* P */,
+                                      const int32_t* op_off, const uint8_t* ops, const int32_t* prm_off, const double* prm,
+                                      const double* noise /* P */, const double* noise_pred /* P or NULL = noise */,
+                                      const double* weights /* P: particle p's weight inside ITS series' mixture */,
+                                      const double* y_slope /* S, or NULL: 1 */, const double* y_intercept /* S, or NULL: 0 */,
+                                      const double* q, int64_t nq, double tol, int64_t max_iter,
+                                      double* out_x /* nq * q_off[S] */, int32_t* out_converged /* or NULL */,
+                                      int32_t* out_iters /* or NULL */,
+                                      double* out_mix_mean /* q_off[S], or NULL */, double* out_mix_var /* q_off[S], or NULL */,
+                                      double* out_logpdf /* P, or NULL */, int32_t* out_info /* P */);
+
 /* agp_logpdf_batch with BLOCK-EXTENSION of resident factors.  The data-annealing loop re-scores
  * every particle on a longer prefix of the same series with unchanged kernel parameters — the reweight step
  * (src/inference_smc_anneal_data.jl:206-217), add_data! (src/api.jl:426-443), scripts/online.jl:200 — and the
@@ -851,7 +894,8 @@ int agp_debug_compact_shards(agp_ctx* ctx, const double* padded, int32_t P, int3
  * agp_get_timing fills out[0..7] = { total_ms, cov_build_ms, chol_update_ms, chol_trsm_ms,
  * finish_ms, n_update_launches, n_trsm_launches, h2d_d2h_ms } for the last batch call; a value+gradient sweep also
  * fills out[8..11] = { L^-T chain ms, K^-1 tiles ms, contraction ms, alpha + reductions ms }, agp_predict_sample_batch
- * out[12..13] = { normals ms, read-out ms }, agp_predict_mixture_batch out[14..15] = { pass ms, accumulation ms } (n_out up to 16). */
+ * out[12..13] = { normals ms, read-out ms }, agp_predict_mixture_batch out[14..15] = { pass ms, accumulation ms } (n_out up to 16).  The many-series entries fill
+ * out[0] = out[2] = their fused kernels, and agp_predict_quantile_series_batch out[4] = its three read-out kernels. */
 int agp_set_profiling(agp_ctx* ctx, int enabled);
 int agp_get_timing(agp_ctx* ctx, double* out, int32_t n_out);
 /* per-launch durations (ms) of the last profiled batch call: which = 0 update kernel, 1 trsm kernel;
