@@ -1,15 +1,24 @@
-// agp_logpdf_series_batch: many SHORT series, each with its own particles, scored in one call by the small-matrix value kernel
-// (agp_series_kernel.hpp: one workgroup per particle, covariance + Cholesky + forward solve + value in LDS), and
-// agp_logpdf_grad_series_batch, its value-and-gradient twin (k_series_logpdf_grad: L^-T, alpha and the contraction with dK / d theta
-// behind the value, same workgroup, same LDS), and agp_predict_series_batch, its predictive twin (k_series_predict: posterior mean and
-// marginal variance at every series' own query times from the factor the value has just left in LDS), and
-// agp_predict_quantile_series_batch, the forecast band on top of it (the predictive launches' device outputs read out by
-// agp_series_quantile_kernel.hpp on the same stream: quantiles and marginal moments of every series' own mixture).  All four are one
-// host function — validation, series upload, launch classes and the value outputs are the same statements — with the gradient, the
-// prediction and the band as options.  Stateless: the series
+// The many-series entries: many SHORT series, each with its own particles, in one call of the small-matrix kernels
+// (agp_series_kernel.hpp: one workgroup per particle, covariance + Cholesky + forward solve + value in LDS).
+//   agp_logpdf_series_batch            k_series_logpdf: the values
+//   agp_logpdf_grad_series_batch       k_series_logpdf_grad: L^-T, alpha and the contraction with dK / d theta behind the value
+//   agp_predict_series_batch           k_series_predict: posterior mean and marginal variance at every series' own query times
+//   agp_predict_quantile_series_batch  the predictive launches, their device outputs read out by agp_series_quantile_kernel.hpp on
+//                                      the same stream: quantiles and marginal moments of every series' own mixture
+// Each entry is one function, read top to bottom, over the stages they share (one SeriesCall carries what a stage leaves for the next):
+//   checks          series_check_sizes, series_check_pointers, series_check_layout (the entry's own pointer checks between them)
+//   series_classes  compile, per particle length / LDS need / evaluation stack, launch classes, workgroup order, out_off
+//   series_stage    the slot, its buffers and the uploads every mode needs (and the query side when there are queries), SeriesArgs
+//   series_launch   the class x LDS-class loop, between the profiling events; the entry passes what launches one class
+//   series_fetch_values / series_copy_values   [logpdf | info] into the head of the pinned landing zone, and out of it
+//   series_timing   agp_get_timing's slots
+// and between them the entry's own buffers, uploads, device-to-host copies and copy-out: ONE PinnedUploads::flush and ONE
+// hipStreamSynchronize per call.  Stateless: the series
 // travel with the call; the resident series, its tables, the factor store, the coalescer and every counter of the context are
 // neither read nor changed — only a workspace slot (stream, staging buffers) is borrowed, as in every batch entry.
 #include "agp_host.hpp"
+
+#include <optional>
 
 static_assert(SERIES_MAX_N == AGP_SERIES_MAX_N, "the kernel's cap is the C ABI's");
 static_assert(AGP_SERIES_MAX_N >= 160, "the reference's 126-, 135-, 143- and 144-point series must fit");
@@ -19,15 +28,6 @@ namespace {
 // LDS classes of the launches: a launch declares the largest need of its particles, so particles are grouped by how many workgroups
 // of their size share a CU's 160 KiB — 4 (n <= ~80), 2 (n <= ~128) or 1.
 int lds_class(size_t bytes) { return bytes <= (size_t)SERIES_LDS_BYTES / 4 ? 0 : bytes <= (size_t)SERIES_LDS_BYTES / 2 ? 1 : 2; }
-
-// The prediction of agp_predict_series_batch: every series' query times and the particle-major outputs (host).
-struct SeriesPredOut {
-  const int64_t* q_off;      // [S + 1]
-  const double* ts_pred;
-  double* mean;              // [off[P]]
-  double* var;
-  int64_t* off;              // [P + 1], written by the entry
-};
 
 // The band of agp_predict_quantile_series_batch: the mixtures' weights and transforms, the quantiles, and the outputs (host).
 struct SeriesQuantOut {
@@ -118,23 +118,55 @@ void quant_fill_nan(const SeriesQuantOut& qo, size_t from, size_t to, int64_t nq
   if (qo.mix_var) std::fill(qo.mix_var + from, qo.mix_var + to, nanv);
 }
 
-// go = null, po = null: values only.  go: also out_grad (agp_logpdf_grad_batch's layout) and out_gnoise.  po: also the posterior at
-// the series' query times; out_logpdf may then be null (pp.noise_pred null: the particle's own noise).  qo (with po, whose mean / var / off
-// are then null: the per-particle predictive stays on the device): the band of every series' mixture instead.
-int series_batch(agp_ctx* c, int32_t S, const int64_t* pt_off, const double* ts, const double* xs, const Particles& pp,
-                 const int32_t* series, double* out_logpdf, int32_t* out_info, const GradOut* go = nullptr,
-                 const SeriesPredOut* po = nullptr, const SeriesQuantOut* qo = nullptr) {
-  const int P = pp.P;
-  char buf[256];
+#define STAGE(expr) do { if (const int rc_ = (expr)) return rc_; } while (0)
+
+// Which kernel the call launches: it chooses the LDS map, the instantiation rule and (gradient) the tape's limit.
+enum class SeriesMode { value, gradient, prediction };
+
+// One call of a many-series entry: the caller's inputs and what each shared stage leaves for the later ones.
+struct SeriesCall {
+  // inputs (q_off / ts_pred: null in the entries without queries)
+  int32_t S; const int64_t* pt_off; const double* ts; const double* xs; Particles pp; const int32_t* series;
+  const int64_t* q_off; const double* ts_pred;
+  // series_classes
+  Batch bt;                          // programs without any table of the resident series (no log|dt| table, no lag tables), caller's order
+  std::vector<int> len;              // [P] points of the particle's series
+  std::vector<size_t> need;          // [P] LDS bytes
+  std::vector<int64_t> nq;           // [P] query points of the particle's series (0 without queries)
+  std::vector<int32_t> list[3][3];   // launch classes (kernel instantiation) x (LDS class), longest series first inside each
+  std::vector<int32_t> wg;           // ... one behind the other in launch order; empty: nothing to launch
+  std::vector<long long> ooff;       // [P + 1] with queries: out_off, the particle-major layout of the prediction
+  // series_stage
+  std::optional<SlotGuard> sg;
+  Slot* s = nullptr; hipStream_t st = nullptr;
+  size_t npts = 0, nqt = 0;          // pt_off[S], q_off[S]; tt = [ts | xs | ts_pred]
+  size_t o_series = 0, o_wg = 0, o_qoff = 0, o_ooff = 0;      // bytes; map = [pt_off (int64) | series | wg | q_off (int64) | out_off (int64)]
+  PinnedUploads up;                  // the call's one upload: the stage's arrays, then the entry's own
+  SeriesArgs sa = {};                // all but wg, which every launch sets
+  // series_launch
+  bool prof = false; hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+  size_t n_out() const { return ooff.empty() ? 0 : (size_t)ooff.back(); }
+  // every entry's pinned landing zone begins with [logpdf (P) | info (P)]; its own outputs follow from o_own() on
+  size_t values_bytes() const { return sizeof(double) * (size_t)pp.P + sizeof(int32_t) * (size_t)pp.P; }
+  size_t o_own() const { return (values_bytes() + 7) & ~(size_t)7; }
+  template <class T> T* in_map(size_t off) const { return reinterpret_cast<T*>(s->map.as<char>() + off); }
+};
+
+// The checks, in this order, the entry's own pointer checks between the second and the third.
+int series_check_sizes(agp_ctx* c, const SeriesCall& sc) {
   if (!c) return fail(nullptr, AGP_ERR_ARG, "null context");
-  if (S < 0 || P < 0) return fail(c, AGP_ERR_ARG, "negative number of series or particles");
-  if (P == 0 && !qo) return AGP_OK;
-  if (!pt_off || !ts || !xs || !series || !pp.complete() || (!out_logpdf && !po) || !out_info) return fail(c, AGP_ERR_ARG, "null pointer argument");
-  if (po && (!po->q_off || !po->ts_pred || (!qo && (!po->mean || !po->var || !po->off))))
-    return fail(c, AGP_ERR_ARG, "null pointer argument (q_off, ts_pred, out_mean, out_var or out_off)");
-  const size_t n_prm_total = go ? (size_t)std::max(0, pp.prm_off[P]) : 0;
-  if (go && !go->gnoise) return fail(c, AGP_ERR_ARG, "null pointer argument (out_grad_noise)");
-  if (go && !go->grad && pp.prm_off[P] > 0) return fail(c, AGP_ERR_ARG, "null pointer argument (out_grad with parameters present)");
+  return sc.S < 0 || sc.pp.P < 0 ? fail(c, AGP_ERR_ARG, "negative number of series or particles") : AGP_OK;
+}
+// outputs: the value outputs this entry cannot do without are there
+int series_check_pointers(agp_ctx* c, const SeriesCall& sc, bool outputs) {
+  const bool ok = sc.pt_off && sc.ts && sc.xs && sc.series && sc.pp.complete() && outputs;
+  return ok ? AGP_OK : fail(c, AGP_ERR_ARG, "null pointer argument");
+}
+
+int series_check_layout(agp_ctx* c, const SeriesCall& sc) {
+  const int32_t S = sc.S;
+  const int64_t* pt_off = sc.pt_off;
+  char buf[256];
   if (S > 0 && pt_off[0] != 0) return fail(c, AGP_ERR_ARG, "pt_off[0] must be 0 (series 0)");
   for (int32_t s = 0; s < S; ++s) {
     if (pt_off[s + 1] < pt_off[s]) {
@@ -147,307 +179,437 @@ int series_batch(agp_ctx* c, int32_t S, const int64_t* pt_off, const double* ts,
       return fail(c, AGP_ERR_ARG, buf);
     }
   }
-  if (po) {
-    if (S > 0 && po->q_off[0] != 0) return fail(c, AGP_ERR_ARG, "q_off[0] must be 0 (series 0)");
+  if (const int64_t* q_off = sc.q_off) {
+    if (S > 0 && q_off[0] != 0) return fail(c, AGP_ERR_ARG, "q_off[0] must be 0 (series 0)");
     for (int32_t s = 0; s < S; ++s) {
-      if (po->q_off[s + 1] < po->q_off[s]) {
-        snprintf(buf, sizeof buf, "series %d: q_off decreases (%lld after %lld)", (int)s, (long long)po->q_off[s + 1], (long long)po->q_off[s]);
+      if (q_off[s + 1] < q_off[s]) {
+        snprintf(buf, sizeof buf, "series %d: q_off decreases (%lld after %lld)", (int)s, (long long)q_off[s + 1], (long long)q_off[s]);
         return fail(c, AGP_ERR_ARG, buf);
       }
-      if (po->q_off[s + 1] - po->q_off[s] > (int64_t)1 << 30) {
-        snprintf(buf, sizeof buf, "series %d has %lld query points, more than 2^30", (int)s, (long long)(po->q_off[s + 1] - po->q_off[s]));
+      if (q_off[s + 1] - q_off[s] > (int64_t)1 << 30) {
+        snprintf(buf, sizeof buf, "series %d has %lld query points, more than 2^30", (int)s, (long long)(q_off[s + 1] - q_off[s]));
         return fail(c, AGP_ERR_ARG, buf);
       }
     }
   }
-  for (int p = 0; p < P; ++p)
-    if (series[p] < 0 || series[p] >= S) {
-      snprintf(buf, sizeof buf, "particle %d: series index %d outside [0, %d)", p, (int)series[p], (int)S);
+  for (int p = 0; p < sc.pp.P; ++p)
+    if (sc.series[p] < 0 || sc.series[p] >= S) {
+      snprintf(buf, sizeof buf, "particle %d: series index %d outside [0, %d)", p, (int)sc.series[p], (int)S);
       return fail(c, AGP_ERR_ARG, buf);
     }
-  for (int p = 0; p < P; ++p)
-    if (pp.op_off[p] < 0 || pp.prm_off[p] < 0 || pp.op_off[p + 1] < pp.op_off[p] || pp.prm_off[p + 1] < pp.prm_off[p]) {
+  for (int p = 0; p < sc.pp.P; ++p)
+    if (sc.pp.op_off[p] < 0 || sc.pp.prm_off[p] < 0 || sc.pp.op_off[p + 1] < sc.pp.op_off[p] || sc.pp.prm_off[p + 1] < sc.pp.prm_off[p]) {
       snprintf(buf, sizeof buf, "particle %d: malformed program / parameter offsets", p);
       return fail(c, AGP_ERR_ARG, buf);
     }
-  QuantPlan qp;
-  if (qo) {
-    if (const int rc = quant_plan(c, S, P, series, po->q_off, *qo, qp)) return rc;
-    if (P == 0) { quant_fill_nan(*qo, 0, qp.Q, qo->nq); return AGP_OK; }      // (S series without a particle)
+  return AGP_OK;
+}
+
+// LDS bytes of particle p on a series of n points: the mode's own map
+size_t series_need(SeriesMode mode, const Batch& bt, int p, int n) {
+  const ProgHdr& h = bt.hdr[(size_t)p];
+  const int m_total = mode == SeriesMode::gradient ? series_grad_lds(n, h.n_ops, h.n_prm, h.n_cp, bt.ghdr[(size_t)p].n_ops, bt.ghdr[(size_t)p].n_prm).total
+                      : mode == SeriesMode::prediction ? series_pred_lds(n, h.n_ops, h.n_prm, h.n_cp).total
+                                                       : series_lds(n, h.n_ops, h.n_prm, h.n_cp).total;
+  return sizeof(double) * (size_t)m_total;
+}
+
+// the evaluation stack one program needs (compile_batch reports the batch's largest only): from the compiled postfix form
+int series_stack_depth(const Batch& bt, const ProgHdr& h) {
+  int sp = 0, depth = 0;
+  for (int i = 0; i < h.n_ops; ++i) {
+    const int o = bt.ops[(size_t)h.op_off + i];
+    if (o == OP_PLUS || o == OP_TIMES || o == OP_CP || o == OP_CP_SWAP) --sp; else ++sp;
+    depth = std::max(depth, sp);
   }
-  // programs without any table of the resident series (no log|dt| table, no lag tables), in the caller's order
-  Batch bt;
+  return depth;
+}
+
+// compile; per particle: length, LDS need, instantiation; launch classes, longest series first inside each; wg and out_off.
+// Instantiations: values and predictions — evaluation-stack depth 4 / 8; gradient — tape of 16 / 64 nodes, the 64-node tape with the
+// depth the value entry picks for the same program (<= 16 nodes never need more than 4), so that the value's bits are that entry's
+int series_classes(agp_ctx* c, SeriesCall& sc, SeriesMode mode) {
+  const int P = sc.pp.P;
+  char buf[256];
+  Batch& bt = sc.bt;
   CompileOpts co;
-  co.ge_tab = false; co.lag = false; co.never_fuse = true; co.want_grad = go != nullptr;
-  if (const int rc = compile_batch(c, pp, bt, co)) return rc;
-  if (go)
+  co.ge_tab = false; co.lag = false; co.never_fuse = true; co.want_grad = mode == SeriesMode::gradient;
+  STAGE(compile_batch(c, sc.pp, bt, co));
+  if (mode == SeriesMode::gradient)
     for (int p = 0; p < P; ++p)
       if (bt.ghdr[(size_t)p].n_ops > 64) {      // (RegTape<64> is the largest tape: agp_logpdf_grad_batch's own limit)
         snprintf(buf, sizeof buf, "particle %d: gradient supports kernel trees of up to 64 nodes (%d)", p, (int)bt.ghdr[(size_t)p].n_ops);
         return fail(c, AGP_ERR_PROGRAM, buf);
       }
-
-  // per particle: length, LDS need; launch classes (kernel instantiation) x (LDS class), longest series first inside each.
-  // Instantiations: values — evaluation-stack depth 4 / 8; gradient — tape of 16 / 64 nodes, the 64-node tape with the depth the value
-  // entry picks for the same program (<= 16 nodes never need more than 4), so that the value's bits are that entry's
-  std::vector<int> len((size_t)P);
-  std::vector<size_t> need((size_t)P);
-  std::vector<int64_t> nq((size_t)P, 0);      // query points of the particle's series (prediction)
-  std::vector<int32_t> list[3][3];
+  sc.len.assign((size_t)P, 0);
+  sc.need.assign((size_t)P, 0);
+  sc.nq.assign((size_t)P, 0);
   for (int p = 0; p < P; ++p) {
     if (bt.order[(size_t)p] != p) return fail(c, AGP_ERR_HOST, "internal error: compiled batch out of order");
     const ProgHdr& h = bt.hdr[(size_t)p];
-    const int n = (int)(pt_off[series[p] + 1] - pt_off[series[p]]);
-    len[(size_t)p] = n;
-    if (po) nq[(size_t)p] = po->q_off[series[p] + 1] - po->q_off[series[p]];
-    if (n == 0 && nq[(size_t)p] == 0) continue;      // (an empty series is launched for its prior predictive only)
-    const int m_total = go ? series_grad_lds(n, h.n_ops, h.n_prm, h.n_cp, bt.ghdr[(size_t)p].n_ops, bt.ghdr[(size_t)p].n_prm).total
-                        : po ? series_pred_lds(n, h.n_ops, h.n_prm, h.n_cp).total
-                             : series_lds(n, h.n_ops, h.n_prm, h.n_cp).total;
-    need[(size_t)p] = sizeof(double) * (size_t)m_total;
-    if (need[(size_t)p] > (size_t)SERIES_LDS_BYTES) {
+    const int32_t s = sc.series[p];
+    const int n = (int)(sc.pt_off[s + 1] - sc.pt_off[s]);
+    sc.len[(size_t)p] = n;
+    if (sc.q_off) sc.nq[(size_t)p] = sc.q_off[s + 1] - sc.q_off[s];
+    if (n == 0 && sc.nq[(size_t)p] == 0) continue;      // (an empty series is launched for its prior predictive only)
+    const size_t need = sc.need[(size_t)p] = series_need(mode, bt, p, n);
+    if (need > (size_t)SERIES_LDS_BYTES) {
       snprintf(buf, sizeof buf, "particle %d: %d per-point tables (ChangePoint nodes) at %d points need %zu bytes of LDS, more than the "
-               "kernel's %d", p, (int)h.n_cp, n, need[(size_t)p], SERIES_LDS_BYTES);
+               "kernel's %d", p, (int)h.n_cp, n, need, SERIES_LDS_BYTES);
       return fail(c, AGP_ERR_PROGRAM, buf);
     }
-    // the evaluation stack this program needs (compile_batch reports the batch's largest only): from the compiled postfix form
-    int sp = 0, depth = 0;
-    for (int i = 0; i < h.n_ops; ++i) {
-      const int o = bt.ops[(size_t)h.op_off + i];
-      if (o == OP_PLUS || o == OP_TIMES || o == OP_CP || o == OP_CP_SWAP) --sp; else ++sp;
-      depth = std::max(depth, sp);
-    }
-    const int inst = !go ? (depth <= 4 ? 0 : 1) : bt.ghdr[(size_t)p].n_ops <= 16 && depth <= 4 ? 0 : depth <= 4 ? 1 : 2;
-    list[inst][lds_class(need[(size_t)p])].push_back(p);
+    const int depth = series_stack_depth(bt, h);
+    const int inst = mode != SeriesMode::gradient ? (depth <= 4 ? 0 : 1) : bt.ghdr[(size_t)p].n_ops <= 16 && depth <= 4 ? 0 : depth <= 4 ? 1 : 2;
+    sc.list[inst][lds_class(need)].push_back(p);
   }
-  for (auto& ld : list)
-    for (auto& v : ld) std::stable_sort(v.begin(), v.end(), [&](int32_t x, int32_t y) { return len[(size_t)x] > len[(size_t)y]; });
-  std::vector<int32_t> wg;
-  wg.reserve((size_t)P);
-  for (auto& ld : list) for (auto& v : ld) wg.insert(wg.end(), v.begin(), v.end());
-  std::vector<long long> ooff;      // out_off: the particle-major layout of the prediction
-  if (po) {
-    ooff.assign((size_t)P + 1, 0);
-    for (int p = 0; p < P; ++p) ooff[(size_t)p + 1] = ooff[(size_t)p] + nq[(size_t)p];
-    if (po->off) std::copy(ooff.begin(), ooff.end(), po->off);
+  for (auto& ld : sc.list)
+    for (auto& v : ld) std::stable_sort(v.begin(), v.end(), [&](int32_t x, int32_t y) { return sc.len[(size_t)x] > sc.len[(size_t)y]; });
+  sc.wg.reserve((size_t)P);
+  for (auto& ld : sc.list) for (auto& v : ld) sc.wg.insert(sc.wg.end(), v.begin(), v.end());
+  if (sc.q_off) {
+    sc.ooff.assign((size_t)P + 1, 0);
+    for (int p = 0; p < P; ++p) sc.ooff[(size_t)p + 1] = sc.ooff[(size_t)p] + sc.nq[(size_t)p];
   }
-  const size_t n_out = po ? (size_t)ooff[(size_t)P] : 0;
-  if (wg.empty()) {      // every particle scores an empty series (src/inference_smc_anneal_data.jl:185-187) and has nothing to predict
-    if (out_logpdf) std::fill(out_logpdf, out_logpdf + P, 0.0);
-    std::fill(out_info, out_info + P, 0);
-    if (go) { std::fill(go->gnoise, go->gnoise + P, 0.0); std::fill(go->grad, go->grad + n_prm_total, 0.0); }
-    if (qo) quant_fill_nan(*qo, 0, qp.Q, qo->nq);      // (only series without a particle have query points here)
-    return AGP_OK;
-  }
+  return AGP_OK;
+}
 
+// what every entry writes when no particle is launched: every particle scores an empty series (src/inference_smc_anneal_data.jl:185-187)
+// and has nothing to predict
+void series_zero_values(const SeriesCall& sc, double* out_logpdf, int32_t* out_info) {
+  if (out_logpdf) std::fill(out_logpdf, out_logpdf + sc.pp.P, 0.0);
+  std::fill(out_info, out_info + sc.pp.P, 0);
+}
+
+// The slot, its stream, and the device buffers and uploads every mode uses: programs as in every sweep; tt = [ts | xs];
+// map = [pt_off (int64) | series | wg]; the values in out_lp = [logpdf | info].  With queries: tt = [ts | xs | ts_pred];
+// map = [.. | q_off (int64) | out_off (int64)]; noise_pred (null: the particle's own noise); the outputs in pred_mean / pred_var.
+// Fills sc.sa; the entry adds its own uploads to sc.up and flushes it.
+int series_stage(agp_ctx* c, SeriesCall& sc) {
+  const int P = sc.pp.P;
+  const size_t S1 = (size_t)sc.S + 1;
+  const Batch& bt = sc.bt;
   HIPCHK(c, hipSetDevice(c->device));
-  SlotGuard sg(c);
-  Slot* s = sg.s;
+  sc.sg.emplace(c);
+  Slot* s = sc.s = sc.sg->s;
   if (!s->stream) HIPCHK(c, hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
-  hipStream_t st = s->stream;
-  const size_t npts = (size_t)pt_off[S];
-  // device buffers of the slot: programs as in every sweep; tt = [ts | xs]; map = [pt_off (int64) | series | wg]
-  const size_t o_series = sizeof(long long) * ((size_t)S + 1), o_wg = o_series + sizeof(int32_t) * (size_t)P;
+  sc.st = s->stream;
+  const size_t npts = sc.npts = (size_t)sc.pt_off[sc.S];
+  sc.nqt = sc.q_off ? (size_t)sc.q_off[sc.S] : 0;
+  sc.o_series = sizeof(long long) * S1;
+  sc.o_wg = sc.o_series + sizeof(int32_t) * (size_t)P;
+  sc.o_qoff = (sc.o_wg + sizeof(int32_t) * sc.wg.size() + 7) & ~(size_t)7;
+  sc.o_ooff = sc.o_qoff + sizeof(long long) * S1;
   HIPCHK(c, s->hdr.ensure(sizeof(ProgHdr) * (size_t)P));
   HIPCHK(c, s->ops.ensure(bt.ops.size() + 4));
   HIPCHK(c, s->prm.ensure(sizeof(double) * std::max<size_t>(1, bt.prm.size())));
   HIPCHK(c, s->noise.ensure(sizeof(double) * (size_t)P));
   HIPCHK(c, s->tt.ensure(sizeof(double) * 2 * std::max<size_t>(1, npts)));
-  HIPCHK(c, s->map.ensure(o_wg + sizeof(int32_t) * wg.size()));
-  HIPCHK(c, s->out_lp.ensure(sizeof(double) * (size_t)P + sizeof(int32_t) * (size_t)P));
-  if (go) {
-    HIPCHK(c, s->ghdr.ensure(sizeof(GProgHdr) * (size_t)P));
-    HIPCHK(c, s->gops.ensure(bt.gops.size() + 4));
-    HIPCHK(c, s->glc.ensure(bt.glc.size() + 4));
-    HIPCHK(c, s->grc.ensure(bt.grc.size() + 4));
-    HIPCHK(c, s->gpoff.ensure(sizeof(int32_t) * (bt.gpoff.size() + 1)));
-    HIPCHK(c, s->gprm.ensure(sizeof(double) * bt.gprm.size()));
-    HIPCHK(c, s->gmap.ensure(sizeof(int32_t) * (bt.gmap.size() + 1)));
-    HIPCHK(c, s->goff.ensure(sizeof(int32_t) * (size_t)P));
-    HIPCHK(c, s->dgrad.ensure(sizeof(double) * std::max<size_t>(1, n_prm_total)));
-    HIPCHK(c, s->dgnoise.ensure(sizeof(double) * (size_t)P));
-  }
-  const size_t nqt = po ? (size_t)po->q_off[S] : 0;
-  const size_t o_qoff = (o_wg + sizeof(int32_t) * wg.size() + 7) & ~(size_t)7, o_ooff = o_qoff + sizeof(long long) * ((size_t)S + 1);
-  if (po) {      // tt = [ts | xs | ts_pred]; map = [.. | q_off (int64) | out_off (int64)]; outputs in pred_mean / pred_var
-    HIPCHK(c, s->tt.ensure(sizeof(double) * (2 * std::max<size_t>(1, npts) + std::max<size_t>(1, nqt))));
-    HIPCHK(c, s->map.ensure(o_ooff + sizeof(long long) * ((size_t)P + 1)));
+  HIPCHK(c, s->map.ensure(sc.o_wg + sizeof(int32_t) * sc.wg.size()));
+  HIPCHK(c, s->out_lp.ensure(sc.values_bytes()));
+  if (sc.q_off) {
+    HIPCHK(c, s->tt.ensure(sizeof(double) * (2 * std::max<size_t>(1, npts) + std::max<size_t>(1, sc.nqt))));
+    HIPCHK(c, s->map.ensure(sc.o_ooff + sizeof(long long) * ((size_t)P + 1)));
     HIPCHK(c, s->noise_pred.ensure(sizeof(double) * (size_t)P));
-    HIPCHK(c, s->pred_mean.ensure(sizeof(double) * std::max<size_t>(1, n_out)));
-    HIPCHK(c, s->pred_var.ensure(sizeof(double) * std::max<size_t>(1, n_out)));
+    HIPCHK(c, s->pred_mean.ensure(sizeof(double) * std::max<size_t>(1, sc.n_out())));
+    HIPCHK(c, s->pred_var.ensure(sizeof(double) * std::max<size_t>(1, sc.n_out())));
   }
-  // the band: x and the moments in sq_out, the flags in sq_flag = [converged | iterations | first_bad (P) | bad (S)]
-  const size_t nx = qo ? qp.Q * (size_t)qo->nq : 0;
-  const bool want_mom = qo && (qo->mix_mean || qo->mix_var);
-  const size_t S1 = (size_t)S + 1, o_plist = sizeof(long long) * 3 * S1;
-  if (qo) {
-    HIPCHK(c, s->sq_tab.ensure(o_plist + sizeof(int32_t) * (size_t)P));
-    HIPCHK(c, s->sq_w.ensure(sizeof(double) * std::max<size_t>(1, qp.vals.size())));
-    HIPCHK(c, s->sq_cm.ensure(sizeof(double) * std::max<size_t>(1, qp.R)));
-    HIPCHK(c, s->sq_cs.ensure(sizeof(double) * std::max<size_t>(1, qp.R)));
-    HIPCHK(c, s->sq_out.ensure(sizeof(double) * std::max<size_t>(1, nx + 2 * qp.Q)));
-    HIPCHK(c, s->sq_flag.ensure(sizeof(int32_t) * (2 * nx + (size_t)P + (size_t)S)));
-  }
-  std::vector<long long> off64(pt_off, pt_off + S + 1);
-  PinnedUploads up;
+  const std::vector<long long> off64(sc.pt_off, sc.pt_off + S1);
+  PinnedUploads& up = sc.up;
   up.add(s->hdr.p, bt.hdr.data(), sizeof(ProgHdr) * (size_t)P);
   up.add(s->ops.p, bt.ops.data(), bt.ops.size());
   up.add(s->prm.p, bt.prm.data(), sizeof(double) * bt.prm.size());
-  up.add(s->noise.p, pp.noise, sizeof(double) * (size_t)P);
-  up.add(s->tt.p, ts, sizeof(double) * npts);
-  up.add(s->tt.as<double>() + npts, xs, sizeof(double) * npts);
-  up.add(s->map.p, off64.data(), o_series);
-  up.add(s->map.as<char>() + o_series, series, sizeof(int32_t) * (size_t)P);
-  up.add(s->map.as<char>() + o_wg, wg.data(), sizeof(int32_t) * wg.size());
-  if (go) {
-    up.add(s->ghdr.p, bt.ghdr.data(), sizeof(GProgHdr) * (size_t)P);
-    up.add(s->gops.p, bt.gops.data(), bt.gops.size());
-    up.add(s->glc.p, bt.glc.data(), bt.glc.size());
-    up.add(s->grc.p, bt.grc.data(), bt.grc.size());
-    up.add(s->gpoff.p, bt.gpoff.data(), sizeof(int32_t) * bt.gpoff.size());
-    up.add(s->gprm.p, bt.gprm.data(), sizeof(double) * bt.gprm.size());
-    up.add(s->gmap.p, bt.gmap.data(), sizeof(int32_t) * bt.gmap.size());
-    up.add(s->goff.p, pp.prm_off, sizeof(int32_t) * (size_t)P);      // the particle's block in out_grad: the caller's own offsets
+  up.add(s->noise.p, sc.pp.noise, sizeof(double) * (size_t)P);
+  up.add(s->tt.p, sc.ts, sizeof(double) * npts);
+  up.add(s->tt.as<double>() + npts, sc.xs, sizeof(double) * npts);
+  up.add(s->map.p, off64.data(), sc.o_series);
+  up.add(sc.in_map<char>(sc.o_series), sc.series, sizeof(int32_t) * (size_t)P);
+  up.add(sc.in_map<char>(sc.o_wg), sc.wg.data(), sizeof(int32_t) * sc.wg.size());
+  if (sc.q_off) {
+    const std::vector<long long> qoff64(sc.q_off, sc.q_off + S1);
+    up.add(sc.in_map<char>(sc.o_qoff), qoff64.data(), sizeof(long long) * S1);
+    up.add(sc.in_map<char>(sc.o_ooff), sc.ooff.data(), sizeof(long long) * ((size_t)P + 1));
+    up.add(s->tt.as<double>() + 2 * npts, sc.ts_pred, sizeof(double) * sc.nqt);
+    up.add(s->noise_pred.p, sc.pp.noise_pred ? sc.pp.noise_pred : sc.pp.noise, sizeof(double) * (size_t)P);
   }
-  std::vector<long long> qoff64;
-  if (po) {
-    qoff64.assign(po->q_off, po->q_off + S + 1);
-    up.add(s->map.as<char>() + o_qoff, qoff64.data(), sizeof(long long) * ((size_t)S + 1));
-    up.add(s->map.as<char>() + o_ooff, ooff.data(), sizeof(long long) * ((size_t)P + 1));
-    up.add(s->tt.as<double>() + 2 * npts, po->ts_pred, sizeof(double) * nqt);
-    up.add(s->noise_pred.p, pp.noise_pred ? pp.noise_pred : pp.noise, sizeof(double) * (size_t)P);
-  }
-  if (qo) {
-    up.add(s->sq_tab.p, qp.tab.data(), o_plist);
-    up.add(s->sq_tab.as<char>() + o_plist, qp.plist.data(), sizeof(int32_t) * (size_t)P);
-    up.add(s->sq_w.p, qp.vals.data(), sizeof(double) * qp.vals.size());
-  }
-  HIPCHK(c, up.flush(s->h_stage, s->up_blob, st));
-
-  SeriesGradArgs sa = {};      // (the value launches take its SeriesArgs part)
-  if (go) {
-    sa.ghdr = s->ghdr.as<GProgHdr>(); sa.gops = s->gops.as<uint8_t>(); sa.glc = s->glc.as<uint8_t>(); sa.grc = s->grc.as<uint8_t>();
-    sa.gpoff = s->gpoff.as<int32_t>(); sa.gprm = s->gprm.as<double>(); sa.gmap = s->gmap.as<int32_t>();
-    sa.out_off = s->goff.as<int32_t>(); sa.out_grad = s->dgrad.as<double>(); sa.out_gnoise = s->dgnoise.as<double>();
-  }
+  SeriesArgs& sa = sc.sa;
   sa.ts = s->tt.as<double>(); sa.xs = s->tt.as<double>() + npts;
   sa.pt_off = s->map.as<long long>();
-  sa.series = reinterpret_cast<const int32_t*>(s->map.as<char>() + o_series);
+  sa.series = sc.in_map<const int32_t>(sc.o_series);
   sa.hdr = s->hdr.as<ProgHdr>(); sa.ops = s->ops.as<uint8_t>(); sa.prm = s->prm.as<double>(); sa.noise = s->noise.as<double>();
   sa.out_lp = s->out_lp.as<double>(); sa.out_info = reinterpret_cast<int32_t*>(s->out_lp.as<double>() + P);
-  const bool prof = c->profiling;
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-  if (prof) {
-    while (s->events.size() < 3) { hipEvent_t e; HIPCHK(c, hipEventCreate(&e)); s->events.push_back(e); }
-    ev[0] = s->events[0]; ev[1] = s->events[1]; ev[2] = s->events[2];
-    HIPCHK(c, hipEventRecord(ev[0], st));
-  }
-  size_t w0 = 0;
-  for (int d = 0; d < 3; ++d)
-    for (int k = 0; k < 3; ++k) {
-      const std::vector<int32_t>& v = list[d][k];
-      if (v.empty()) continue;
-      size_t lds = 0;
-      for (int32_t p : v) lds = std::max(lds, need[(size_t)p]);
-      sa.wg = reinterpret_cast<const int32_t*>(s->map.as<char>() + o_wg) + w0;
-      if (go) HIPCHK(c, launch_series_logpdf_grad(st, sa, (int)v.size(), d == 2 ? 8 : 4, d == 0 ? 16 : 64, lds));
-      else if (po) {
-        SeriesPredArgs spa = {};
-        static_cast<SeriesArgs&>(spa) = sa;
-        spa.q_off = reinterpret_cast<const long long*>(s->map.as<char>() + o_qoff);
-        spa.out_off = reinterpret_cast<const long long*>(s->map.as<char>() + o_ooff);
-        spa.ts_pred = s->tt.as<double>() + 2 * npts; spa.noise_pred = s->noise_pred.as<double>();
-        spa.out_mean = s->pred_mean.as<double>(); spa.out_var = s->pred_var.as<double>();
-        HIPCHK(c, launch_series_predict(st, spa, (int)v.size(), d == 0 ? 4 : 8, lds));
-      } else HIPCHK(c, launch_series_logpdf(st, sa, (int)v.size(), d == 0 ? 4 : 8, lds));
-      w0 += v.size();
-    }
-  if (prof) HIPCHK(c, hipEventRecord(ev[1], st));
-  if (qo) {
-    // the read-out, behind the predictive launches on the same stream: their means and variances never leave the device
-    SeriesQuantArgs qa = {};
-    qa.S = S; qa.nq = (int)qo->nq;
-    qa.pt_off = sa.pt_off;
-    qa.q_off = reinterpret_cast<const long long*>(s->map.as<char>() + o_qoff);
-    qa.out_off = reinterpret_cast<const long long*>(s->map.as<char>() + o_ooff);
-    qa.mean = s->pred_mean.as<double>(); qa.var = s->pred_var.as<double>(); qa.pred_info = sa.out_info;
-    qa.pl_off = s->sq_tab.as<long long>(); qa.w_off = qa.pl_off + S1; qa.row_off = qa.w_off + S1;
-    qa.plist = reinterpret_cast<const int32_t*>(s->sq_tab.as<char>() + o_plist);
-    qa.w = s->sq_w.as<double>(); qa.slope = qa.w + qp.W; qa.intercept = qa.slope + S; qa.ivar = qa.intercept + S; qa.q = qa.ivar + S;
-    qa.tol = qo->tol; qa.max_iter = (long long)qo->max_iter;
-    qa.cm = s->sq_cm.as<double>(); qa.cs = s->sq_cs.as<double>();
-    qa.out_x = s->sq_out.as<double>();
-    qa.out_mean = want_mom ? qa.out_x + nx : nullptr; qa.out_var = want_mom ? qa.out_x + nx + qp.Q : nullptr;
-    qa.out_conv = s->sq_flag.as<int32_t>(); qa.out_iters = qa.out_conv + nx;
-    qa.first_bad = qa.out_iters + nx; qa.bad = qa.first_bad + P;
-    launch_series_mix_readout(st, qa, (long long)qp.Q, qp.max_rows_el);
-    HIPCHK(c, hipGetLastError());
-    if (prof) HIPCHK(c, hipEventRecord(ev[2], st));
-  }
-  const size_t out_bytes = sizeof(double) * (size_t)P + sizeof(int32_t) * (size_t)P;
-  const size_t o_gn = (out_bytes + 7) & ~(size_t)7, o_gr = o_gn + sizeof(double) * (size_t)P;      // gradient outputs behind [logpdf | info]
-  const size_t n_band = nx + (want_mom ? 2 * qp.Q : 0), o_bf = o_gn + sizeof(double) * n_band;     // band: [x | mean | var], then the flags
-  HIPCHK(c, s->h_out.ensure(go ? o_gr + sizeof(double) * n_prm_total : qo ? o_bf + sizeof(int32_t) * (2 * nx + (size_t)P)
-                               : po ? o_gn + 2 * sizeof(double) * n_out : out_bytes));
-  HIPCHK(c, hipMemcpyAsync(s->h_out.p, s->out_lp.p, out_bytes, hipMemcpyDeviceToHost, st));
-  if (go) {
-    char* ho = static_cast<char*>(s->h_out.p);
-    HIPCHK(c, hipMemcpyAsync(ho + o_gn, s->dgnoise.p, sizeof(double) * (size_t)P, hipMemcpyDeviceToHost, st));
-    if (n_prm_total > 0) HIPCHK(c, hipMemcpyAsync(ho + o_gr, s->dgrad.p, sizeof(double) * n_prm_total, hipMemcpyDeviceToHost, st));
-  }
-  if (qo) {      // [x | mean | var | converged | iterations | first_bad] behind [logpdf | info]
-    char* ho = static_cast<char*>(s->h_out.p);
-    if (n_band > 0) HIPCHK(c, hipMemcpyAsync(ho + o_gn, s->sq_out.p, sizeof(double) * n_band, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(ho + o_bf, s->sq_flag.p, sizeof(int32_t) * (2 * nx + (size_t)P), hipMemcpyDeviceToHost, st));
-  } else if (po && n_out > 0) {      // [mean | var] behind [logpdf | info]
-    char* ho = static_cast<char*>(s->h_out.p);
-    HIPCHK(c, hipMemcpyAsync(ho + o_gn, s->pred_mean.p, sizeof(double) * n_out, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(ho + o_gn + sizeof(double) * n_out, s->pred_var.p, sizeof(double) * n_out, hipMemcpyDeviceToHost, st));
-  }
-  HIPCHK(c, hipStreamSynchronize(st));
-  const double* hl = static_cast<const double*>(s->h_out.p);
-  const int32_t* hi = reinterpret_cast<const int32_t*>(hl + P);
-  for (int p = 0; p < P; ++p) {
-    const bool empty = len[(size_t)p] == 0;      // (never launched, or launched for the prior predictive: the value is 0 either way)
-    if (out_logpdf) out_logpdf[p] = empty ? 0.0 : hl[p];
-    out_info[p] = empty ? 0 : hi[p];
-    if (go) {
-      // (an empty series: zeros; a bad pivot: NaN in the whole block — the kernel wrote them, slot by slot through gmap)
-      const double* hgn = reinterpret_cast<const double*>(static_cast<const char*>(s->h_out.p) + o_gn);
-      const double* hgr = hgn + P;
-      go->gnoise[p] = empty ? 0.0 : hgn[p];
-      for (int32_t q = pp.prm_off[p]; q < pp.prm_off[p + 1]; ++q) go->grad[q] = empty ? 0.0 : hgr[q];
-    }
-  }
-  if (qo) {
-    const char* ho = static_cast<const char*>(s->h_out.p);
-    const double* hb = reinterpret_cast<const double*>(ho + o_gn);
-    const int32_t* hf = reinterpret_cast<const int32_t*>(ho + o_bf);
-    // raw_components' rule: a particle whose predictive exists but whose raw mean or variance is unusable at query i reports n_s + i + 1
-    for (int p = 0; p < P; ++p)
-      if (out_info[p] == 0 && nq[(size_t)p] > 0 && hf[2 * nx + (size_t)p] != 0) out_info[p] = hf[2 * nx + (size_t)p];
-    if (qo->x) std::copy(hb, hb + nx, qo->x);
-    if (qo->conv) std::copy(hf, hf + nx, qo->conv);
-    if (qo->iters) std::copy(hf + nx, hf + 2 * nx, qo->iters);
-    if (qo->mix_mean) std::copy(hb + nx, hb + nx + qp.Q, qo->mix_mean);
-    if (qo->mix_var) std::copy(hb + nx + qp.Q, hb + nx + 2 * qp.Q, qo->mix_var);
-  } else if (po && n_out > 0) {      // every particle with query points was launched and wrote its whole block
-    const double* hm = reinterpret_cast<const double*>(static_cast<const char*>(s->h_out.p) + o_gn);
-    std::copy(hm, hm + n_out, po->mean);
-    std::copy(hm + n_out, hm + 2 * n_out, po->var);
-  }
-  if (prof) {
-    // agp_get_timing: out[0] = out[2] = the value kernels of the call (covariance, factorisation, solve and value are one kernel)
-    float ms = 0.f, rd = 0.f;
-    HIPCHK(c, hipEventElapsedTime(&ms, ev[0], ev[1]));
-    if (qo) HIPCHK(c, hipEventElapsedTime(&rd, ev[1], ev[2]));
-    std::lock_guard<std::mutex> g(c->mu);
-    for (double& t : c->timing) t = 0.0;
-    c->timing[0] = ms; c->timing[2] = ms;
-    c->timing[4] = rd;      // the band's three read-out kernels (0 in the other entries)
-  }
   return AGP_OK;
 }
+
+// The classes in order, between the first two profiling events.  launch(wg, grid, d, lds_bytes) -> hipError_t launches the `grid`
+// particles wg[0 .. grid) of instantiation class d with the largest LDS need among them.
+template <class Launch> int series_launch(agp_ctx* c, SeriesCall& sc, Launch&& launch) {
+  Slot* s = sc.s;
+  sc.prof = c->profiling;
+  if (sc.prof) {
+    while (s->events.size() < 3) { hipEvent_t e; HIPCHK(c, hipEventCreate(&e)); s->events.push_back(e); }
+    sc.ev[0] = s->events[0]; sc.ev[1] = s->events[1]; sc.ev[2] = s->events[2];
+    HIPCHK(c, hipEventRecord(sc.ev[0], sc.st));
+  }
+  const int32_t* wg = sc.in_map<const int32_t>(sc.o_wg);
+  for (int d = 0; d < 3; ++d)
+    for (int k = 0; k < 3; ++k) {
+      const std::vector<int32_t>& v = sc.list[d][k];
+      if (v.empty()) continue;
+      size_t lds = 0;
+      for (int32_t p : v) lds = std::max(lds, sc.need[(size_t)p]);
+      HIPCHK(c, launch(wg, (int)v.size(), d, lds));
+      wg += v.size();
+    }
+  if (sc.prof) HIPCHK(c, hipEventRecord(sc.ev[1], sc.st));
+  return AGP_OK;
+}
+
+// the predictive launches of a staged call with queries: means and variances into pred_mean / pred_var, where they stay
+int series_launch_predict(agp_ctx* c, SeriesCall& sc) {
+  Slot* s = sc.s;
+  SeriesPredArgs pa = {};
+  static_cast<SeriesArgs&>(pa) = sc.sa;
+  pa.q_off = sc.in_map<const long long>(sc.o_qoff);
+  pa.out_off = sc.in_map<const long long>(sc.o_ooff);
+  pa.ts_pred = s->tt.as<double>() + 2 * sc.npts; pa.noise_pred = s->noise_pred.as<double>();
+  pa.out_mean = s->pred_mean.as<double>(); pa.out_var = s->pred_var.as<double>();
+  return series_launch(c, sc, [&](const int32_t* wg, int grid, int d, size_t lds) {
+    pa.wg = wg;
+    return launch_series_predict(sc.st, pa, grid, d == 0 ? 4 : 8, lds);
+  });
+}
+
+// the pinned landing zone at the entry's size, and [logpdf | info] on their way into its head
+int series_fetch_values(agp_ctx* c, SeriesCall& sc, size_t h_out_bytes) {
+  HIPCHK(c, sc.s->h_out.ensure(h_out_bytes));
+  HIPCHK(c, hipMemcpyAsync(sc.s->h_out.p, sc.s->out_lp.p, sc.values_bytes(), hipMemcpyDeviceToHost, sc.st));
+  return AGP_OK;
+}
+
+// ... and, the stream drained, into the caller's arrays.  An empty series (never launched, or launched for the prior predictive):
+// the value is 0 either way
+void series_copy_values(const SeriesCall& sc, double* out_logpdf, int32_t* out_info) {
+  const int P = sc.pp.P;
+  const double* hl = static_cast<const double*>(sc.s->h_out.p);
+  const int32_t* hi = reinterpret_cast<const int32_t*>(hl + P);
+  for (int p = 0; p < P; ++p) {
+    const bool empty = sc.len[(size_t)p] == 0;
+    if (out_logpdf) out_logpdf[p] = empty ? 0.0 : hl[p];
+    out_info[p] = empty ? 0 : hi[p];
+  }
+}
+
+// agp_get_timing: out[0] = out[2] = the value kernels of the call (covariance, factorisation, solve and value are one kernel);
+// out[4] = the band's three read-out kernels (0 in the other entries)
+int series_timing(agp_ctx* c, const SeriesCall& sc, float readout_ms = 0.f) {
+  if (!sc.prof) return AGP_OK;
+  float ms = 0.f;
+  HIPCHK(c, hipEventElapsedTime(&ms, sc.ev[0], sc.ev[1]));
+  std::lock_guard<std::mutex> g(c->mu);
+  for (double& t : c->timing) t = 0.0;
+  c->timing[0] = ms; c->timing[2] = ms;
+  c->timing[4] = readout_ms;
+  return AGP_OK;
+}
+
+int logpdf_series(agp_ctx* c, SeriesCall& sc, double* out_logpdf, int32_t* out_info) {
+  STAGE(series_check_sizes(c, sc));
+  if (sc.pp.P == 0) return AGP_OK;
+  STAGE(series_check_pointers(c, sc, out_logpdf && out_info));
+  STAGE(series_check_layout(c, sc));
+  STAGE(series_classes(c, sc, SeriesMode::value));
+  if (sc.wg.empty()) { series_zero_values(sc, out_logpdf, out_info); return AGP_OK; }
+  STAGE(series_stage(c, sc));
+  HIPCHK(c, sc.up.flush(sc.s->h_stage, sc.s->up_blob, sc.st));
+  STAGE(series_launch(c, sc, [&](const int32_t* wg, int grid, int d, size_t lds) {
+    SeriesArgs a = sc.sa;
+    a.wg = wg;
+    return launch_series_logpdf(sc.st, a, grid, d == 0 ? 4 : 8, lds);
+  }));
+  // h_out = [logpdf | info]
+  STAGE(series_fetch_values(c, sc, sc.values_bytes()));
+  HIPCHK(c, hipStreamSynchronize(sc.st));
+  series_copy_values(sc, out_logpdf, out_info);
+  return series_timing(c, sc);
+}
+
+// also out_grad (agp_logpdf_grad_batch's layout) and out_gnoise
+int logpdf_grad_series(agp_ctx* c, SeriesCall& sc, double* out_logpdf, double* out_grad, double* out_gnoise, int32_t* out_info) {
+  const int P = sc.pp.P;
+  STAGE(series_check_sizes(c, sc));
+  if (P == 0) return AGP_OK;
+  STAGE(series_check_pointers(c, sc, out_logpdf && out_info));
+  const size_t n_prm_total = (size_t)std::max(0, sc.pp.prm_off[P]);
+  if (!out_gnoise) return fail(c, AGP_ERR_ARG, "null pointer argument (out_grad_noise)");
+  if (!out_grad && sc.pp.prm_off[P] > 0) return fail(c, AGP_ERR_ARG, "null pointer argument (out_grad with parameters present)");
+  STAGE(series_check_layout(c, sc));
+  STAGE(series_classes(c, sc, SeriesMode::gradient));
+  if (sc.wg.empty()) {
+    series_zero_values(sc, out_logpdf, out_info);
+    std::fill(out_gnoise, out_gnoise + P, 0.0); std::fill(out_grad, out_grad + n_prm_total, 0.0);
+    return AGP_OK;
+  }
+  STAGE(series_stage(c, sc));
+  Slot* s = sc.s;
+  const Batch& bt = sc.bt;
+  HIPCHK(c, s->ghdr.ensure(sizeof(GProgHdr) * (size_t)P));
+  HIPCHK(c, s->gops.ensure(bt.gops.size() + 4));
+  HIPCHK(c, s->glc.ensure(bt.glc.size() + 4));
+  HIPCHK(c, s->grc.ensure(bt.grc.size() + 4));
+  HIPCHK(c, s->gpoff.ensure(sizeof(int32_t) * (bt.gpoff.size() + 1)));
+  HIPCHK(c, s->gprm.ensure(sizeof(double) * bt.gprm.size()));
+  HIPCHK(c, s->gmap.ensure(sizeof(int32_t) * (bt.gmap.size() + 1)));
+  HIPCHK(c, s->goff.ensure(sizeof(int32_t) * (size_t)P));
+  HIPCHK(c, s->dgrad.ensure(sizeof(double) * std::max<size_t>(1, n_prm_total)));
+  HIPCHK(c, s->dgnoise.ensure(sizeof(double) * (size_t)P));
+  sc.up.add(s->ghdr.p, bt.ghdr.data(), sizeof(GProgHdr) * (size_t)P);
+  sc.up.add(s->gops.p, bt.gops.data(), bt.gops.size());
+  sc.up.add(s->glc.p, bt.glc.data(), bt.glc.size());
+  sc.up.add(s->grc.p, bt.grc.data(), bt.grc.size());
+  sc.up.add(s->gpoff.p, bt.gpoff.data(), sizeof(int32_t) * bt.gpoff.size());
+  sc.up.add(s->gprm.p, bt.gprm.data(), sizeof(double) * bt.gprm.size());
+  sc.up.add(s->gmap.p, bt.gmap.data(), sizeof(int32_t) * bt.gmap.size());
+  sc.up.add(s->goff.p, sc.pp.prm_off, sizeof(int32_t) * (size_t)P);      // the particle's block in out_grad: the caller's own offsets
+  HIPCHK(c, sc.up.flush(s->h_stage, s->up_blob, sc.st));
+  SeriesGradArgs ga = {};
+  static_cast<SeriesArgs&>(ga) = sc.sa;
+  ga.ghdr = s->ghdr.as<GProgHdr>(); ga.gops = s->gops.as<uint8_t>(); ga.glc = s->glc.as<uint8_t>(); ga.grc = s->grc.as<uint8_t>();
+  ga.gpoff = s->gpoff.as<int32_t>(); ga.gprm = s->gprm.as<double>(); ga.gmap = s->gmap.as<int32_t>();
+  ga.out_off = s->goff.as<int32_t>(); ga.out_grad = s->dgrad.as<double>(); ga.out_gnoise = s->dgnoise.as<double>();
+  STAGE(series_launch(c, sc, [&](const int32_t* wg, int grid, int d, size_t lds) {
+    ga.wg = wg;
+    return launch_series_logpdf_grad(sc.st, ga, grid, d == 2 ? 8 : 4, d == 0 ? 16 : 64, lds);
+  }));
+  // h_out = [logpdf | info | grad_noise (P) | grad (prm_off[P])]
+  const size_t o_gn = sc.o_own(), o_gr = o_gn + sizeof(double) * (size_t)P;
+  STAGE(series_fetch_values(c, sc, o_gr + sizeof(double) * n_prm_total));
+  char* ho = static_cast<char*>(s->h_out.p);
+  HIPCHK(c, hipMemcpyAsync(ho + o_gn, s->dgnoise.p, sizeof(double) * (size_t)P, hipMemcpyDeviceToHost, sc.st));
+  if (n_prm_total > 0) HIPCHK(c, hipMemcpyAsync(ho + o_gr, s->dgrad.p, sizeof(double) * n_prm_total, hipMemcpyDeviceToHost, sc.st));
+  HIPCHK(c, hipStreamSynchronize(sc.st));
+  series_copy_values(sc, out_logpdf, out_info);
+  // (an empty series: zeros; a bad pivot: NaN in the whole block — the kernel wrote them, slot by slot through gmap)
+  const double* hgn = reinterpret_cast<const double*>(ho + o_gn);
+  const double* hgr = reinterpret_cast<const double*>(ho + o_gr);
+  for (int p = 0; p < P; ++p) {
+    const bool empty = sc.len[(size_t)p] == 0;
+    out_gnoise[p] = empty ? 0.0 : hgn[p];
+    for (int32_t q = sc.pp.prm_off[p]; q < sc.pp.prm_off[p + 1]; ++q) out_grad[q] = empty ? 0.0 : hgr[q];
+  }
+  return series_timing(c, sc);
+}
+
+// also the posterior at the series' query times, particle-major behind out_off; out_logpdf may be null
+int predict_series(agp_ctx* c, SeriesCall& sc, double* out_mean, double* out_var, int64_t* out_off, double* out_logpdf,
+                   int32_t* out_info) {
+  STAGE(series_check_sizes(c, sc));
+  if (sc.pp.P == 0) return AGP_OK;
+  STAGE(series_check_pointers(c, sc, out_info != nullptr));
+  if (!sc.q_off || !sc.ts_pred || !out_mean || !out_var || !out_off)
+    return fail(c, AGP_ERR_ARG, "null pointer argument (q_off, ts_pred, out_mean, out_var or out_off)");
+  STAGE(series_check_layout(c, sc));
+  STAGE(series_classes(c, sc, SeriesMode::prediction));
+  std::copy(sc.ooff.begin(), sc.ooff.end(), out_off);      // (no check is left to fail, nothing is launched yet)
+  if (sc.wg.empty()) { series_zero_values(sc, out_logpdf, out_info); return AGP_OK; }
+  STAGE(series_stage(c, sc));
+  Slot* s = sc.s;
+  HIPCHK(c, sc.up.flush(s->h_stage, s->up_blob, sc.st));
+  STAGE(series_launch_predict(c, sc));
+  // h_out = [logpdf | info | mean (out_off[P]) | var (out_off[P])]
+  const size_t n_out = sc.n_out(), o_mean = sc.o_own(), o_var = o_mean + sizeof(double) * n_out;
+  STAGE(series_fetch_values(c, sc, o_var + sizeof(double) * n_out));
+  char* ho = static_cast<char*>(s->h_out.p);
+  if (n_out > 0) {
+    HIPCHK(c, hipMemcpyAsync(ho + o_mean, s->pred_mean.p, sizeof(double) * n_out, hipMemcpyDeviceToHost, sc.st));
+    HIPCHK(c, hipMemcpyAsync(ho + o_var, s->pred_var.p, sizeof(double) * n_out, hipMemcpyDeviceToHost, sc.st));
+  }
+  HIPCHK(c, hipStreamSynchronize(sc.st));
+  series_copy_values(sc, out_logpdf, out_info);
+  if (n_out > 0) {      // every particle with query points was launched and wrote its whole block
+    const double* hm = reinterpret_cast<const double*>(ho + o_mean);
+    std::copy(hm, hm + n_out, out_mean);
+    std::copy(hm + n_out, hm + 2 * n_out, out_var);
+  }
+  return series_timing(c, sc);
+}
+
+// The band of every series' mixture: predict_series' launches, their means and variances left on the device for the read-out
+// kernels behind them on the same stream.  out_logpdf may be null.
+int predict_quantile_series(agp_ctx* c, SeriesCall& sc, const SeriesQuantOut& qo, double* out_logpdf, int32_t* out_info) {
+  const int P = sc.pp.P;
+  const int32_t S = sc.S;
+  STAGE(series_check_sizes(c, sc));
+  STAGE(series_check_pointers(c, sc, out_info != nullptr));
+  if (!sc.q_off || !sc.ts_pred) return fail(c, AGP_ERR_ARG, "null pointer argument (q_off, ts_pred, out_mean, out_var or out_off)");
+  STAGE(series_check_layout(c, sc));
+  QuantPlan qp;
+  STAGE(quant_plan(c, S, P, sc.series, sc.q_off, qo, qp));
+  if (P == 0) { quant_fill_nan(qo, 0, qp.Q, qo.nq); return AGP_OK; }      // (S series without a particle)
+  STAGE(series_classes(c, sc, SeriesMode::prediction));
+  if (sc.wg.empty()) {
+    series_zero_values(sc, out_logpdf, out_info);
+    quant_fill_nan(qo, 0, qp.Q, qo.nq);      // (only series without a particle have query points here)
+    return AGP_OK;
+  }
+  STAGE(series_stage(c, sc));
+  Slot* s = sc.s;
+  // x and the moments in sq_out, the flags in sq_flag = [converged | iterations | first_bad (P) | bad (S)]
+  const size_t nx = qp.Q * (size_t)qo.nq;
+  const bool want_mom = qo.mix_mean || qo.mix_var;
+  const size_t S1 = (size_t)S + 1, o_plist = sizeof(long long) * 3 * S1;
+  HIPCHK(c, s->sq_tab.ensure(o_plist + sizeof(int32_t) * (size_t)P));
+  HIPCHK(c, s->sq_w.ensure(sizeof(double) * std::max<size_t>(1, qp.vals.size())));
+  HIPCHK(c, s->sq_cm.ensure(sizeof(double) * std::max<size_t>(1, qp.R)));
+  HIPCHK(c, s->sq_cs.ensure(sizeof(double) * std::max<size_t>(1, qp.R)));
+  HIPCHK(c, s->sq_out.ensure(sizeof(double) * std::max<size_t>(1, nx + 2 * qp.Q)));
+  HIPCHK(c, s->sq_flag.ensure(sizeof(int32_t) * (2 * nx + (size_t)P + (size_t)S)));
+  sc.up.add(s->sq_tab.p, qp.tab.data(), o_plist);
+  sc.up.add(s->sq_tab.as<char>() + o_plist, qp.plist.data(), sizeof(int32_t) * (size_t)P);
+  sc.up.add(s->sq_w.p, qp.vals.data(), sizeof(double) * qp.vals.size());
+  HIPCHK(c, sc.up.flush(s->h_stage, s->up_blob, sc.st));
+  STAGE(series_launch_predict(c, sc));
+  SeriesQuantArgs qa = {};
+  qa.S = S; qa.nq = (int)qo.nq;
+  qa.pt_off = sc.sa.pt_off;
+  qa.q_off = sc.in_map<const long long>(sc.o_qoff);
+  qa.out_off = sc.in_map<const long long>(sc.o_ooff);
+  qa.mean = s->pred_mean.as<double>(); qa.var = s->pred_var.as<double>(); qa.pred_info = sc.sa.out_info;
+  qa.pl_off = s->sq_tab.as<long long>(); qa.w_off = qa.pl_off + S1; qa.row_off = qa.w_off + S1;
+  qa.plist = reinterpret_cast<const int32_t*>(s->sq_tab.as<char>() + o_plist);
+  qa.w = s->sq_w.as<double>(); qa.slope = qa.w + qp.W; qa.intercept = qa.slope + S; qa.ivar = qa.intercept + S; qa.q = qa.ivar + S;
+  qa.tol = qo.tol; qa.max_iter = (long long)qo.max_iter;
+  qa.cm = s->sq_cm.as<double>(); qa.cs = s->sq_cs.as<double>();
+  qa.out_x = s->sq_out.as<double>();
+  qa.out_mean = want_mom ? qa.out_x + nx : nullptr; qa.out_var = want_mom ? qa.out_x + nx + qp.Q : nullptr;
+  qa.out_conv = s->sq_flag.as<int32_t>(); qa.out_iters = qa.out_conv + nx;
+  qa.first_bad = qa.out_iters + nx; qa.bad = qa.first_bad + P;
+  launch_series_mix_readout(sc.st, qa, (long long)qp.Q, qp.max_rows_el);
+  HIPCHK(c, hipGetLastError());
+  if (sc.prof) HIPCHK(c, hipEventRecord(sc.ev[2], sc.st));
+  // h_out = [logpdf | info | x (nx) | mean (Q) | var (Q) | converged (nx) | iterations (nx) | first_bad (P)], the moments when wanted
+  const size_t n_band = nx + (want_mom ? 2 * qp.Q : 0), o_band = sc.o_own(), o_flag = o_band + sizeof(double) * n_band;
+  STAGE(series_fetch_values(c, sc, o_flag + sizeof(int32_t) * (2 * nx + (size_t)P)));
+  char* ho = static_cast<char*>(s->h_out.p);
+  if (n_band > 0) HIPCHK(c, hipMemcpyAsync(ho + o_band, s->sq_out.p, sizeof(double) * n_band, hipMemcpyDeviceToHost, sc.st));
+  HIPCHK(c, hipMemcpyAsync(ho + o_flag, s->sq_flag.p, sizeof(int32_t) * (2 * nx + (size_t)P), hipMemcpyDeviceToHost, sc.st));
+  HIPCHK(c, hipStreamSynchronize(sc.st));
+  series_copy_values(sc, out_logpdf, out_info);
+  const double* hb = reinterpret_cast<const double*>(ho + o_band);
+  const int32_t* hf = reinterpret_cast<const int32_t*>(ho + o_flag);
+  // raw_components' rule: a particle whose predictive exists but whose raw mean or variance is unusable at query i reports n_s + i + 1
+  for (int p = 0; p < P; ++p)
+    if (out_info[p] == 0 && sc.nq[(size_t)p] > 0 && hf[2 * nx + (size_t)p] != 0) out_info[p] = hf[2 * nx + (size_t)p];
+  if (qo.x) std::copy(hb, hb + nx, qo.x);
+  if (qo.conv) std::copy(hf, hf + nx, qo.conv);
+  if (qo.iters) std::copy(hf + nx, hf + 2 * nx, qo.iters);
+  if (qo.mix_mean) std::copy(hb + nx, hb + nx + qp.Q, qo.mix_mean);
+  if (qo.mix_var) std::copy(hb + nx + qp.Q, hb + nx + 2 * qp.Q, qo.mix_var);
+  float readout_ms = 0.f;
+  if (sc.prof) HIPCHK(c, hipEventElapsedTime(&readout_ms, sc.ev[1], sc.ev[2]));
+  return series_timing(c, sc, readout_ms);
+}
+
+#undef STAGE
 
 // agp_debug_series_factor: P caller matrices of one size through stages 4 and 5 of the value kernel (its probe instantiation).
 int series_factor(agp_ctx* c, const double* K, const double* y, int64_t n, int32_t P, double* out_L, double* out_alpha,
@@ -508,15 +670,18 @@ extern "C" {
 int agp_logpdf_series_batch(agp_ctx* c, int32_t S, const int64_t* pt_off, const double* ts, const double* xs, int32_t P,
                             const int32_t* series, const int32_t* op_off, const uint8_t* ops, const int32_t* prm_off, const double* prm,
                             const double* noise, double* out_logpdf, int32_t* out_info) {
-  return abi_guard(c, [&] { return series_batch(c, S, pt_off, ts, xs, {P, op_off, ops, prm_off, prm, noise, nullptr}, series, out_logpdf, out_info); });
+  return abi_guard(c, [&] {
+    SeriesCall sc{S, pt_off, ts, xs, {P, op_off, ops, prm_off, prm, noise, nullptr}, series, nullptr, nullptr};
+    return logpdf_series(c, sc, out_logpdf, out_info);
+  });
 }
 
 int agp_logpdf_grad_series_batch(agp_ctx* c, int32_t S, const int64_t* pt_off, const double* ts, const double* xs, int32_t P,
                                  const int32_t* series, const int32_t* op_off, const uint8_t* ops, const int32_t* prm_off, const double* prm,
                                  const double* noise, double* out_logpdf, double* out_grad, double* out_grad_noise, int32_t* out_info) {
   return abi_guard(c, [&] {
-    const GradOut go{out_grad, out_grad_noise};
-    return series_batch(c, S, pt_off, ts, xs, {P, op_off, ops, prm_off, prm, noise, nullptr}, series, out_logpdf, out_info, &go);
+    SeriesCall sc{S, pt_off, ts, xs, {P, op_off, ops, prm_off, prm, noise, nullptr}, series, nullptr, nullptr};
+    return logpdf_grad_series(c, sc, out_logpdf, out_grad, out_grad_noise, out_info);
   });
 }
 
@@ -525,8 +690,8 @@ int agp_predict_series_batch(agp_ctx* c, int32_t S, const int64_t* pt_off, const
                              const int32_t* prm_off, const double* prm, const double* noise, const double* noise_pred, double* out_mean,
                              double* out_var, int64_t* out_off, double* out_logpdf, int32_t* out_info) {
   return abi_guard(c, [&] {
-    const SeriesPredOut po{q_off, ts_pred, out_mean, out_var, out_off};
-    return series_batch(c, S, pt_off, ts, xs, {P, op_off, ops, prm_off, prm, noise, noise_pred}, series, out_logpdf, out_info, nullptr, &po);
+    SeriesCall sc{S, pt_off, ts, xs, {P, op_off, ops, prm_off, prm, noise, noise_pred}, series, q_off, ts_pred};
+    return predict_series(c, sc, out_mean, out_var, out_off, out_logpdf, out_info);
   });
 }
 
@@ -538,10 +703,9 @@ int agp_predict_quantile_series_batch(agp_ctx* c, int32_t S, const int64_t* pt_o
                                       int32_t* out_iters, double* out_mix_mean, double* out_mix_var, double* out_logpdf,
                                       int32_t* out_info) {
   return abi_guard(c, [&] {
-    const SeriesPredOut po{q_off, ts_pred, nullptr, nullptr, nullptr};
+    SeriesCall sc{S, pt_off, ts, xs, {P, op_off, ops, prm_off, prm, noise, noise_pred}, series, q_off, ts_pred};
     const SeriesQuantOut qo{weights, y_slope, y_intercept, q, nq, tol, max_iter, out_x, out_converged, out_iters, out_mix_mean, out_mix_var};
-    return series_batch(c, S, pt_off, ts, xs, {P, op_off, ops, prm_off, prm, noise, noise_pred}, series, out_logpdf, out_info, nullptr, &po,
-                        &qo);
+    return predict_quantile_series(c, sc, qo, out_logpdf, out_info);
   });
 }
 

@@ -244,6 +244,28 @@ def _f64(a):
     return np.ascontiguousarray(np.asarray(a, dtype=np.float64))
 
 
+def _raise_first_bad(info, check):
+    """PosDefException for the first particle with info > 0, when `check`."""
+    if check and (info > 0).any():
+        p = int(np.argmax(info > 0))
+        raise PosDefException(int(info[p]), p)
+
+
+def _series_ctypes(packed, queries=None):
+    """The ctypes arguments the four many-series entries share, in the entries' order, from series_call_args' (and pack_queries')
+    results, with a one-element stand-in for every empty array: S, pt_off, ts, xs, [q_off, ts_pred,] P, series, op_off, ops,
+    prm_off, prm, noise [, noise_pred]."""
+    pt_off, ts, xs, (op_off, ops, prm_off, prm), P, noises, sidx = packed
+    i64 = C.POINTER(C.c_int64)
+    some = lambda a: _dp(a if a.size else np.zeros(1))
+    data = (pt_off.shape[0] - 1, pt_off.ctypes.data_as(i64), some(ts), some(xs))
+    particles = (P, _ip(sidx), _ip(op_off), _u8(ops), _ip(prm_off), some(prm), _dp(noises))
+    if queries is None:
+        return data + particles
+    q_off, ts_pred, noise_pred = queries
+    return data + (q_off.ctypes.data_as(i64), some(ts_pred)) + particles + (_dp(noise_pred),)
+
+
 def pack_series(series):
     """Concatenate a sequence of (ts, xs) pairs for logpdf_series_batch: (pt_off int64[S+1], ts, xs), series s at
     [pt_off[s], pt_off[s+1]).  Raises ValueError on unequal lengths, input that is not 1-D, or a series of more than SERIES_MAX_N
@@ -492,44 +514,30 @@ class GPEngine:
         out = np.empty(P, dtype=np.float64); info = np.empty(P, dtype=np.int32)
         self._check(self._lib.agp_logpdf_batch(self._ctx, n, P, _ip(op_off), _u8(ops), _ip(prm_off), _dp(prm),
                                                _dp(noises), _dp(out), _ip(info)))
-        if check and (info > 0).any():
-            p = int(np.argmax(info > 0))
-            raise PosDefException(int(info[p]), p)
+        _raise_first_bad(info, check)
         return out, info
 
     def logpdf_series_batch(self, series, nodes, noises, series_index, check=True, programs=None):
         """agp_logpdf_series_batch: many short series (a sequence of (ts, xs) pairs of at most SERIES_MAX_N points each) scored in one
         fused launch — particle p scores series[series_index[p]]: log N(xs_s; 0, K_p(ts_s) + noise_p I).  Needs no set_data and leaves
         the resident series, the factor store and every counter alone.  Returns (logpdf[P], info[P])."""
-        pt_off, ts, xs, (op_off, ops, prm_off, prm), P, noises, sidx = series_call_args(series, nodes, noises, series_index, programs)
+        packed = series_call_args(series, nodes, noises, series_index, programs)
+        P = packed[4]
         out = np.empty(P, dtype=np.float64); info = np.empty(P, dtype=np.int32)
-        ts_arg = ts if ts.size else np.zeros(1)
-        xs_arg = xs if xs.size else np.zeros(1)
-        prm_arg = prm if prm.size else np.zeros(1)
-        self._check(self._lib.agp_logpdf_series_batch(self._ctx, pt_off.shape[0] - 1, pt_off.ctypes.data_as(C.POINTER(C.c_int64)),
-                                                      _dp(ts_arg), _dp(xs_arg), P, _ip(sidx), _ip(op_off), _u8(ops), _ip(prm_off),
-                                                      _dp(prm_arg), _dp(noises), _dp(out), _ip(info)))
-        if check and (info > 0).any():
-            p = int(np.argmax(info > 0))
-            raise PosDefException(int(info[p]), p)
+        self._check(self._lib.agp_logpdf_series_batch(self._ctx, *_series_ctypes(packed), _dp(out), _ip(info)))
+        _raise_first_bad(info, check)
         return out, info
 
     def logpdf_grad_series_batch(self, series, nodes, noises, series_index, check=True, programs=None):
         """agp_logpdf_grad_series_batch: value and gradient of many short series in one fused launch — logpdf_series_batch's twin, same
         arguments, same statelessness.  Returns (logpdf[P], grads, grad_noise[P], info[P]); grads[p] is d logpdf / d theta in the order
         of gp.encode(node)[1], as in logpdf_grad_batch; logpdf is bit-identical to logpdf_series_batch's."""
-        pt_off, ts, xs, (op_off, ops, prm_off, prm), P, noises, sidx = series_call_args(series, nodes, noises, series_index, programs)
+        packed = series_call_args(series, nodes, noises, series_index, programs)
+        prm_off, P = packed[3][2], packed[4]
         out = np.empty(P, dtype=np.float64); info = np.empty(P, dtype=np.int32); gn = np.empty(P, dtype=np.float64)
         grad = np.zeros(max(1, int(prm_off[-1])))
-        ts_arg = ts if ts.size else np.zeros(1)
-        xs_arg = xs if xs.size else np.zeros(1)
-        prm_arg = prm if prm.size else np.zeros(1)
-        self._check(self._lib.agp_logpdf_grad_series_batch(self._ctx, pt_off.shape[0] - 1, pt_off.ctypes.data_as(C.POINTER(C.c_int64)),
-                                                           _dp(ts_arg), _dp(xs_arg), P, _ip(sidx), _ip(op_off), _u8(ops), _ip(prm_off),
-                                                           _dp(prm_arg), _dp(noises), _dp(out), _dp(grad), _dp(gn), _ip(info)))
-        if check and (info > 0).any():
-            p = int(np.argmax(info > 0))
-            raise PosDefException(int(info[p]), p)
+        self._check(self._lib.agp_logpdf_grad_series_batch(self._ctx, *_series_ctypes(packed), _dp(out), _dp(grad), _dp(gn), _ip(info)))
+        _raise_first_bad(info, check)
         return out, [grad[prm_off[i]:prm_off[i + 1]] for i in range(P)], gn, info
 
     def predict_series_batch(self, series, queries, nodes, noises, series_index, noise_pred=None, want_logpdf=False, check=True,
@@ -540,27 +548,18 @@ class GPEngine:
         Returns (means, vars, info), or (means, vars, logpdf, info) with want_logpdf (the training log marginal likelihood,
         bit-identical to logpdf_series_batch's); means[p] / vars[p] are views of length len(queries[series_index[p]]) into one
         particle-major array, so np.stack of the adjacent particles of one series is the block mixture_quantile takes."""
-        pt_off, ts, xs, (op_off, ops, prm_off, prm), P, noises, sidx = series_call_args(series, nodes, noises, series_index, programs)
-        S = pt_off.shape[0] - 1
-        q_off, ts_pred, noise_pred = pack_queries(queries, S, noise_pred, P)
-        m_s = np.diff(q_off)
+        packed = series_call_args(series, nodes, noises, series_index, programs)
+        S, P, sidx = packed[0].shape[0] - 1, packed[4], packed[6]
+        qpack = pack_queries(queries, S, noise_pred, P)
+        m_s = np.diff(qpack[0])
         total = int(sum(m_s[i] for i in sidx if 0 <= i < S))      # (an index outside is the library's to report)
         mean = np.empty(max(1, total)); var = np.empty(max(1, total))
         out_off = np.zeros(P + 1, dtype=np.int64)
         lp = np.empty(P, dtype=np.float64) if want_logpdf else None
         info = np.empty(P, dtype=np.int32)
-        ts_arg = ts if ts.size else np.zeros(1)
-        xs_arg = xs if xs.size else np.zeros(1)
-        tq_arg = ts_pred if ts_pred.size else np.zeros(1)
-        prm_arg = prm if prm.size else np.zeros(1)
-        i64 = C.POINTER(C.c_int64)
-        self._check(self._lib.agp_predict_series_batch(self._ctx, S, pt_off.ctypes.data_as(i64), _dp(ts_arg), _dp(xs_arg),
-                                                       q_off.ctypes.data_as(i64), _dp(tq_arg), P, _ip(sidx), _ip(op_off), _u8(ops),
-                                                       _ip(prm_off), _dp(prm_arg), _dp(noises), _dp(noise_pred), _dp(mean), _dp(var),
-                                                       out_off.ctypes.data_as(i64), _dp(lp), _ip(info)))
-        if check and (info > 0).any():
-            p = int(np.argmax(info > 0))
-            raise PosDefException(int(info[p]), p)
+        self._check(self._lib.agp_predict_series_batch(self._ctx, *_series_ctypes(packed, qpack), _dp(mean), _dp(var),
+                                                       out_off.ctypes.data_as(C.POINTER(C.c_int64)), _dp(lp), _ip(info)))
+        _raise_first_bad(info, check)
         means = [mean[out_off[p]:out_off[p + 1]] for p in range(P)]
         vars_ = [var[out_off[p]:out_off[p + 1]] for p in range(P)]
         return (means, vars_, lp, info) if want_logpdf else (means, vars_, info)
@@ -576,9 +575,10 @@ class GPEngine:
         q (views into one array per output, as predict_series_batch's); mean / var (lists of (m_s,) arrays) and logpdf (P,) are None
         unless asked for.  A series without particles, or with a
         particle whose info != 0 (PosDefException when check), gets NaN and converged False."""
-        pt_off, ts, xs, (op_off, ops, prm_off, prm), P, noises, sidx = series_call_args(series, nodes, noises, series_index, programs)
-        S = pt_off.shape[0] - 1
-        q_off, ts_pred, noise_pred = pack_queries(queries, S, None if noise_pred is None else np.broadcast_to(noise_pred, (P,)), P)
+        packed = series_call_args(series, nodes, noises, series_index, programs)
+        S, P = packed[0].shape[0] - 1, packed[4]
+        qpack = pack_queries(queries, S, None if noise_pred is None else np.broadcast_to(noise_pred, (P,)), P)
+        q_off = qpack[0]
         weights = _f64(weights)
         if weights.shape != (P,):
             raise ValueError(f"weights has shape {weights.shape}, expected ({P},)")
@@ -595,19 +595,11 @@ class GPEngine:
         var = np.empty(max(1, Q)) if want_moments else None
         lp = np.empty(P, dtype=np.float64) if want_logpdf else None
         info = np.zeros(max(1, P), dtype=np.int32)
-        ts_arg = ts if ts.size else np.zeros(1)
-        xs_arg = xs if xs.size else np.zeros(1)
-        tq_arg = ts_pred if ts_pred.size else np.zeros(1)
-        prm_arg = prm if prm.size else np.zeros(1)
-        i64 = C.POINTER(C.c_int64)
         self._check(self._lib.agp_predict_quantile_series_batch(
-            self._ctx, S, pt_off.ctypes.data_as(i64), _dp(ts_arg), _dp(xs_arg), q_off.ctypes.data_as(i64), _dp(tq_arg), P, _ip(sidx),
-            _ip(op_off), _u8(ops), _ip(prm_off), _dp(prm_arg), _dp(noises), _dp(noise_pred), _dp(weights), _dp(slope), _dp(icpt), _dp(qa),
-            nq, float(tol), int(max_iter), _dp(x), _ip(conv), _ip(iters), _dp(mean), _dp(var), _dp(lp), _ip(info)))
+            self._ctx, *_series_ctypes(packed, qpack), _dp(weights), _dp(slope), _dp(icpt), _dp(qa), nq, float(tol), int(max_iter),
+            _dp(x), _ip(conv), _ip(iters), _dp(mean), _dp(var), _dp(lp), _ip(info)))
         info = info[:P]
-        if check and (info > 0).any():
-            p = int(np.argmax(info > 0))
-            raise PosDefException(int(info[p]), p)
+        _raise_first_bad(info, check)
         # series s's (nq, m_s) row-major block, seen as (m_s, nq) — or (m_s,) for a scalar q: views into the call's arrays
         conv = conv.astype(bool)
         lo = (nq * q_off).tolist(); qo = q_off.tolist()
@@ -630,9 +622,7 @@ class GPEngine:
         out = np.empty(P, dtype=np.float64); info = np.empty(P, dtype=np.int32)
         self._check(self._lib.agp_logpdf_batch_extend(self._ctx, n, P, _ip(op_off), _u8(ops), _ip(prm_off), _dp(prm),
                                                       _dp(noises), _dp(out), _ip(info)))
-        if check and (info > 0).any():
-            p = int(np.argmax(info > 0))
-            raise PosDefException(int(info[p]), p)
+        _raise_first_bad(info, check)
         return out, info
 
     def extend_stats(self):
@@ -771,9 +761,7 @@ class GPEngine:
         grad = np.zeros(max(1, int(prm_off[-1])))
         self._check(self._lib.agp_logpdf_grad_batch(self._ctx, n, P, _ip(op_off), _u8(ops), _ip(prm_off), _dp(prm), _dp(noises),
                                                     _dp(out), _dp(grad), _dp(gn), _ip(info)))
-        if check and (info > 0).any():
-            p = int(np.argmax(info > 0))
-            raise PosDefException(int(info[p]), p)
+        _raise_first_bad(info, check)
         return out, [grad[prm_off[i]:prm_off[i + 1]] for i in range(P)], gn, info
 
     def logpdf_batch_device(self, programs, noises, n, d_out_ptr, d_info_ptr, stream_ptr=0):
@@ -786,24 +774,29 @@ class GPEngine:
                                                       C.c_void_p(d_info_ptr), C.c_void_p(stream_ptr)))
 
     # -- predictive path (src/GP.jl:731-758) -------------------------------------------------
-    def predict_batch(self, nodes, noises, ts_pred, n=None, noise_pred=None, mean_train=None, mean_pred=None,
-                      want_cov=False, check=True):
+    def _predict_args(self, nodes, noises, ts_pred, n, noise_pred, mean_train, mean_pred):
+        """What the resident predict_* methods hand to the library: (n, programs, P, noises, ts_pred, m, noise_pred per particle or None,
+        mean_train, mean_pred)."""
         n = self.n_max if n is None else int(n)
-        op_off, ops, prm_off, prm = _gp.encode_batch(nodes)
-        P = op_off.shape[0] - 1
-        noises = _f64(noises); ts_pred = _f64(ts_pred); m = ts_pred.shape[0]
+        programs = _gp.encode_batch(nodes)
+        P = programs[0].shape[0] - 1
+        noises = _f64(noises); ts_pred = _f64(ts_pred)
         npred = None if noise_pred is None else _f64(np.broadcast_to(noise_pred, (P,)))
         mt = None if mean_train is None else _f64(mean_train)
         mp_ = None if mean_pred is None else _f64(mean_pred)
+        return n, programs, P, noises, ts_pred, ts_pred.shape[0], npred, mt, mp_
+
+    def predict_batch(self, nodes, noises, ts_pred, n=None, noise_pred=None, mean_train=None, mean_pred=None,
+                      want_cov=False, check=True):
+        n, (op_off, ops, prm_off, prm), P, noises, ts_pred, m, npred, mt, mp_ = self._predict_args(nodes, noises, ts_pred, n, noise_pred,
+                                                                                                   mean_train, mean_pred)
         mean = np.empty((P, m)); var = np.empty((P, m))
         cov = np.empty((P, m, m)) if want_cov else None
         info = np.zeros(P, dtype=np.int32)
         self._check(self._lib.agp_predict_batch(self._ctx, n, _dp(ts_pred), m, P, _ip(op_off), _u8(ops),
                                                 _ip(prm_off), _dp(prm), _dp(noises), _dp(npred), _dp(mt), _dp(mp_),
                                                 _dp(mean), _dp(var), _dp(cov), _ip(info)))
-        if check and (info > 0).any():
-            p = int(np.argmax(info > 0))
-            raise PosDefException(int(info[p]), p)
+        _raise_first_bad(info, check)
         return mean, var, cov, info
 
     def predict_logpdf_batch(self, nodes, noises, ts_pred, y_pred, n=None, noise_pred=None, mean_train=None, mean_pred=None,
@@ -811,22 +804,16 @@ class GPEngine:
         """logpdf(MvNormal(node, noise, ts[1:n], xs[1:n], ts_pred; noise_pred, mean), y_pred) per particle (src/api.jl:693,
         test/experiment_hmc.jl:125) without forming the predictive covariance.  Returns (logp[P], info[P]); info = n + k: the
         predictive covariance's leading minor k is not positive definite (logp NaN wherever info != 0)."""
-        n = self.n_max if n is None else int(n)
-        op_off, ops, prm_off, prm = _gp.encode_batch(nodes)
-        P = op_off.shape[0] - 1
-        noises = _f64(noises); ts_pred = _f64(ts_pred); y_pred = _f64(y_pred); m = ts_pred.shape[0]
+        n, (op_off, ops, prm_off, prm), P, noises, ts_pred, m, npred, mt, mp_ = self._predict_args(nodes, noises, ts_pred, n, noise_pred,
+                                                                                                   mean_train, mean_pred)
+        y_pred = _f64(y_pred)
         if y_pred.shape != (m,):
             raise ValueError(f"y_pred has shape {y_pred.shape}, ts_pred {ts_pred.shape}")
-        npred = None if noise_pred is None else _f64(np.broadcast_to(noise_pred, (P,)))
-        mt = None if mean_train is None else _f64(mean_train)
-        mp_ = None if mean_pred is None else _f64(mean_pred)
         logp = np.empty(P); info = np.zeros(P, dtype=np.int32)
         self._check(self._lib.agp_predict_logpdf_batch(self._ctx, n, _dp(ts_pred), _dp(y_pred), m, P, _ip(op_off), _u8(ops),
                                                        _ip(prm_off), _dp(prm), _dp(noises), _dp(npred), _dp(mt), _dp(mp_),
                                                        _dp(logp), _ip(info)))
-        if check and (info > 0).any():
-            p = int(np.argmax(info > 0))
-            raise PosDefException(int(info[p]), p)
+        _raise_first_bad(info, check)
         return logp, info
 
     # -- mixture quantiles (src/api.jl:547-596) -----------------------------------------------
@@ -850,15 +837,11 @@ class GPEngine:
         predictive mapped to the raw space of y_transform = (slope, intercept), searched per point by the device.  Returns (x,
         converged, iters, info), x / converged / iters shaped as mixture_quantile's; info = n + j: the raw marginal variance at
         query j (1-based) is negative or NaN.  If any info != 0, x is NaN (PosDefException when check)."""
-        n = self.n_max if n is None else int(n)
-        op_off, ops, prm_off, prm = _gp.encode_batch(nodes)
-        P = op_off.shape[0] - 1
-        noises = _f64(noises); ts_pred = _f64(ts_pred); m = ts_pred.shape[0]; weights = _f64(weights)
+        n, (op_off, ops, prm_off, prm), P, noises, ts_pred, m, npred, mt, mp_ = self._predict_args(nodes, noises, ts_pred, n, noise_pred,
+                                                                                                   mean_train, mean_pred)
+        weights = _f64(weights)
         if weights.shape != (P,):
             raise ValueError(f"weights has shape {weights.shape}, expected ({P},)")
-        npred = None if noise_pred is None else _f64(np.broadcast_to(noise_pred, (P,)))
-        mt = None if mean_train is None else _f64(mean_train)
-        mp_ = None if mean_pred is None else _f64(mean_pred)
         slope, intercept = (float(v) for v in y_transform)
         qa = _f64(np.atleast_1d(q)); nq = qa.shape[0]
         x = np.empty((nq, m)); conv = np.zeros((nq, m), dtype=np.int32); iters = np.zeros((nq, m), dtype=np.int32)
@@ -867,9 +850,7 @@ class GPEngine:
                                                          _dp(noises), _dp(npred), _dp(mt), _dp(mp_), _dp(weights), slope, intercept,
                                                          _dp(qa), nq, float(tol), int(max_iter), _dp(x), _ip(conv), _ip(iters),
                                                          _ip(info)))
-        if check and (info > 0).any():
-            p = int(np.argmax(info > 0))
-            raise PosDefException(int(info[p]), p)
+        _raise_first_bad(info, check)
         return _quantile_shape(q, x, conv, iters) + (info,)
 
     # -- posterior predictive samples (src/api.jl:497-522 + Distributions' rand) -------------------------------------------
@@ -880,16 +861,12 @@ class GPEngine:
         optional: the components / standard normals to use instead of the seeded draws.  Returns (x, component, info): x of shape
         (m, n_samples) (column s is sample s), the component of each sample, info[P] (n + k: leading minor k of a predictive covariance
         is not positive definite; x is NaN everywhere if any info != 0, PosDefException when check)."""
-        n = self.n_max if n is None else int(n)
-        op_off, ops, prm_off, prm = _gp.encode_batch(nodes)
-        P = op_off.shape[0] - 1
-        noises = _f64(noises); ts_pred = _f64(ts_pred); m = ts_pred.shape[0]; weights = _f64(weights)
+        n, (op_off, ops, prm_off, prm), P, noises, ts_pred, m, npred, mt, mp_ = self._predict_args(nodes, noises, ts_pred, n, noise_pred,
+                                                                                                   mean_train, mean_pred)
+        weights = _f64(weights)
         S = int(n_samples)
         if weights.shape != (P,):
             raise ValueError(f"weights has shape {weights.shape}, expected ({P},)")
-        npred = None if noise_pred is None else _f64(np.broadcast_to(noise_pred, (P,)))
-        mt = None if mean_train is None else _f64(mean_train)
-        mp_ = None if mean_pred is None else _f64(mean_pred)
         cin = None if component is None else np.ascontiguousarray(component, dtype=np.int32)
         if cin is not None and cin.shape != (S,):
             raise ValueError(f"component has shape {cin.shape}, expected ({S},)")
@@ -904,9 +881,7 @@ class GPEngine:
         self._check(self._lib.agp_predict_sample_batch(self._ctx, n, _dp(ts_pred), m, P, _ip(op_off), _u8(ops), _ip(prm_off), _dp(prm),
                                                        _dp(noises), _dp(npred), _dp(mt), _dp(mp_), _dp(weights), slope, intercept,
                                                        S, int(seed) & (2**64 - 1), _ip(cin), _dp(zin), _dp(xt), _ip(comp), _ip(info)))
-        if check and (info > 0).any():
-            p = int(np.argmax(info > 0))
-            raise PosDefException(int(info[p]), p)
+        _raise_first_bad(info, check)
         return xt.T, comp, info
 
     # -- mixture moments (Distributions.mean / var / cov of predict_mvn's MixtureModel) ------------------------------------
@@ -938,24 +913,18 @@ class GPEngine:
         y_transform = (slope, intercept); space 1: of its MvLogNormal re-wrap.  want_cov: the fused covariance pass (no per-particle
         covariance leaves the device).  Returns (mean (m,), var (m,), cov (m, m) or None, info (P,)); everything is NaN if any info != 0
         (PosDefException when check)."""
-        n = self.n_max if n is None else int(n)
-        op_off, ops, prm_off, prm = _gp.encode_batch(nodes)
-        P = op_off.shape[0] - 1
-        noises = _f64(noises); ts_pred = _f64(ts_pred); m = ts_pred.shape[0]; weights = _f64(weights)
+        n, (op_off, ops, prm_off, prm), P, noises, ts_pred, m, npred, mt, mp_ = self._predict_args(nodes, noises, ts_pred, n, noise_pred,
+                                                                                                   mean_train, mean_pred)
+        weights = _f64(weights)
         if weights.shape != (P,):
             raise ValueError(f"weights has shape {weights.shape}, expected ({P},)")
-        npred = None if noise_pred is None else _f64(np.broadcast_to(noise_pred, (P,)))
-        mt = None if mean_train is None else _f64(mean_train)
-        mp_ = None if mean_pred is None else _f64(mean_pred)
         slope, intercept = (float(v) for v in y_transform)
         mean = np.empty(m); var = np.empty(m); cov = np.empty((m, m)) if want_cov else None
         info = np.zeros(P, dtype=np.int32)
         self._check(self._lib.agp_predict_mixture_batch(self._ctx, n, _dp(ts_pred), m, P, _ip(op_off), _u8(ops), _ip(prm_off), _dp(prm),
                                                         _dp(noises), _dp(npred), _dp(mt), _dp(mp_), _dp(weights), slope, intercept,
                                                         int(space), _dp(mean), _dp(var), _dp(cov), _ip(info)))
-        if check and (info > 0).any():
-            p = int(np.argmax(info > 0))
-            raise PosDefException(int(info[p]), p)
+        _raise_first_bad(info, check)
         return mean, var, cov, info
 
     # -- sum-of-GPs posterior (src/GP.jl:904-993) ---------------------------------------------
@@ -998,9 +967,7 @@ class GPEngine:
         info = np.zeros(P, dtype=np.int32)
         self._check(self._lib.agp_infer_gp_sum_batch(self._ctx, n, _dp(ts_pred), p, P, M, _ip(op_off), _u8(ops), _ip(prm_off), _dp(prm),
                                                      _dp(noises), _dp(npred), _dp(mean), _dp(var), _dp(cov), _ip(info)))
-        if check and (info > 0).any():
-            q = int(np.argmax(info > 0))
-            raise PosDefException(int(info[q]), q)
+        _raise_first_bad(info, check)
         return mean, var, cov, info, [slice(i * p, (i + 1) * p) for i in range(M)], slice(M * p, ma)
 
     def predict_sum_batch(self, split_nodes, noises, ts_pred, q=(), n=None, noise_pred=None, y_transform=(1.0, 0.0), check=True):
@@ -1015,9 +982,7 @@ class GPEngine:
         self._check(self._lib.agp_predict_sum_batch(self._ctx, n, _dp(ts_pred), p, P, M, _ip(op_off), _u8(ops), _ip(prm_off), _dp(prm),
                                                     _dp(noises), _dp(npred), slope, intercept, _dp(qa) if nq else None, nq, _dp(mean),
                                                     _dp(x) if nq else None, _ip(info)))
-        if check and (info > 0).any():
-            k = int(np.argmax(info > 0))
-            raise PosDefException(int(info[k]), k)
+        _raise_first_bad(info, check)
         return mean, x, info
 
     # -- matrix assembly (src/GP.jl:666-668) -------------------------------------------------
@@ -1223,9 +1188,7 @@ def logpdf_grad_batch_multi(engines, nodes, noises, n=None, check=True, programs
     rc = lib.agp_logpdf_grad_batch_multi(_ctx_array(engines), len(engines), n, P, _ip(op_off), _u8(ops), _ip(prm_off), _dp(prm), _dp(noises),
                                          _dp(out), _dp(grad), _dp(gn), _ip(info), _ip(owner))
     engines[0]._check(rc)
-    if check and (info > 0).any():
-        p = int(np.argmax(info > 0))
-        raise PosDefException(int(info[p]), p)
+    _raise_first_bad(info, check)
     res = (out, [grad[prm_off[i]:prm_off[i + 1]] for i in range(P)], gn, info)
     return res + (owner[:P],) if want_owner else res
 
@@ -1247,9 +1210,7 @@ def predict_batch_multi(engines, nodes, noises, ts_pred, n=None, noise_pred=None
     rc = lib.agp_predict_batch_multi(_ctx_array(engines), len(engines), n, _dp(ts_pred), m, P, _ip(op_off), _u8(ops), _ip(prm_off), _dp(prm),
                                      _dp(noises), _dp(npred), _dp(mt), _dp(mp_), _dp(mean), _dp(var), _dp(cov), _ip(info), _ip(owner))
     engines[0]._check(rc)
-    if check and (info > 0).any():
-        p = int(np.argmax(info > 0))
-        raise PosDefException(int(info[p]), p)
+    _raise_first_bad(info, check)
     res = (mean, var, cov, info)
     return res + (owner[:P],) if want_owner else res
 
@@ -1313,9 +1274,7 @@ def predict_quantile_multi(multi, nodes, noises, ts_pred, weights, q, n=None, no
     mean, var, _, info = predict_batch_multi(engines, nodes, noises, ts_pred, n=n, noise_pred=noise_pred, mean_train=mean_train,
                                              mean_pred=mean_pred, check=False)
     mr, vr, info = raw_components(mean, var, info, n, y_transform)
-    if check and (info > 0).any():
-        p = int(np.argmax(info > 0))
-        raise PosDefException(int(info[p]), p)
+    _raise_first_bad(info, check)
     if (info != 0).any():
         shape = (len(ts_pred),) + (() if np.ndim(q) == 0 else (len(np.atleast_1d(q)),))
         return np.full(shape, np.nan), np.zeros(shape, dtype=bool), np.zeros(shape, dtype=np.int32), info
@@ -1374,9 +1333,7 @@ class GPEngineMulti:
         fn = self._lib.agp_logpdf_batch_extend_multi if extend else self._lib.agp_logpdf_batch_multi
         self._check(fn(self._arr, self._n, n, P, _ip(op_off), _u8(ops), _ip(prm_off), _dp(prm),
                        _dp(noises), _dp(out), _ip(info)))
-        if check and (info > 0).any():
-            p = int(np.argmax(info > 0))
-            raise PosDefException(int(info[p]), p)
+        _raise_first_bad(info, check)
         return out, info
 
     def logpdf_grad_batch(self, nodes, noises, n=None, check=True, programs=None, want_owner=False):
