@@ -397,6 +397,34 @@ constexpr int SERIES_QSLOT = 192;
 static_assert(SERIES_QSLOT >= SERIES_MAX_N && SERIES_QSLOT + 4 * 16 <= 256, "four waves' query entries behind the series' own");
 __host__ __device__ inline SeriesLds series_pred_lds(int n, int n_ops, int n_prm, int n_cp) { return series_lds(n, n_ops, n_prm, n_cp); }
 
+// Held-out twin (k_series_predict_logpdf, agp_predict_logpdf_series_batch): the value kernel's arguments, every series' own query
+// times and held-out values, and the outputs.  The workgroup factors the JOINT matrix of the series' n training points followed —
+// without padding — by its m query points, N = n + m <= SERIES_MAX_N, in the value kernel's LDS map at N points (series_lds(N, ..)),
+// and reads the query rows' partials: the need, the LDS classes and the host's refusal rule are the value entry's at N.
+struct SeriesProbaArgs : SeriesArgs {
+  const long long* q_off;    // [S + 1] series s is scored at ts_pred[q_off[s] .. q_off[s + 1])
+  const double* ts_pred;
+  const double* y_pred;      // [q_off[S]] held-out values, in the space of xs
+  const double* noise_pred;  // [P] the diagonal addend of the query rows
+  const double* y_slope;     // [S] the Jacobian term: + m log|y_slope[s]| (1: none)
+  const long long* out_off;  // [P + 1] particle p's block in out_terms
+  double* out_terms;         // [out_off[P]] or null: the per-point (prequential) terms
+};
+
+// The mixture read-out of agp_predict_logpdf_series_batch (k_series_mix_logp, agp_series_quantile_kernel.hpp): series s's particles
+// plist[pl_off[s] ..] (ascending caller index) with the weights w[w_off[s] + j] — quant_plan's lists, as SeriesQuantArgs reads them.
+struct SeriesMixLogpArgs {
+  int S;
+  const long long* q_off;    // [S + 1]
+  const long long* pl_off;   // [S + 1]
+  const long long* w_off;    // [S + 1]
+  const int32_t* plist;      // [P]
+  const double* w;           // [w_off[S]]
+  const double* lp;          // [P] the kernel's out_lp (written for every particle of a series with held-out points)
+  const int32_t* info;       // [P]
+  double* out;               // [S]
+};
+
 // The read-out of agp_predict_quantile_series_batch (agp_series_quantile_kernel.hpp) on the predictive launches' device outputs.
 // Series s's mixture: its P_s = pl_off[s + 1] - pl_off[s] particles plist[pl_off[s] ..] (ascending caller index), their weights
 // w[w_off[s] + j] padded with 0 to Pp_s = w_off[s + 1] - w_off[s] = ceil(P_s / 64) 64, and the packed rows of its m_s query points,

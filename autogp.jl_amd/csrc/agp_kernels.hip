@@ -186,6 +186,10 @@ void launch_series_mix_readout(hipStream_t st, const SeriesQuantArgs& a, long lo
   if (n_queries > 0 && (a.out_mean || a.out_var))
     hipLaunchKernelGGL(k_series_mix_moments, dim3((unsigned)((n_queries + 255) / 256)), dim3(256), 0, st, a);
 }
+void launch_series_mix_logp(hipStream_t st, const SeriesMixLogpArgs& a) {
+  if (a.S <= 0) return;
+  hipLaunchKernelGGL(k_series_mix_logp, dim3((unsigned)((a.S + 255) / 256)), dim3(256), 0, st, a);
+}
 void launch_sum_readout(hipStream_t st, int P, const SumReadArgs& a) {
   hipLaunchKernelGGL(k_sum_readout, dim3((unsigned)((a.m + 255) / 256), P), dim3(256), 0, st, a);
 }

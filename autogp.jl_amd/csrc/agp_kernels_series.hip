@@ -10,7 +10,8 @@ hipError_t kernels_init_series() {
                        reinterpret_cast<const void*>(&k_series_logpdf<4, true>),
                        reinterpret_cast<const void*>(&k_series_logpdf_grad<4, 16>), reinterpret_cast<const void*>(&k_series_logpdf_grad<4, 64>),
                        reinterpret_cast<const void*>(&k_series_logpdf_grad<8, 64>),
-                       reinterpret_cast<const void*>(&k_series_predict<4>), reinterpret_cast<const void*>(&k_series_predict<8>)};
+                       reinterpret_cast<const void*>(&k_series_predict<4>), reinterpret_cast<const void*>(&k_series_predict<8>),
+                       reinterpret_cast<const void*>(&k_series_predict_logpdf<4>), reinterpret_cast<const void*>(&k_series_predict_logpdf<8>)};
   for (const void* f : fns) {
     hipFuncAttributes fa;
     hipError_t e = hipFuncGetAttributes(&fa, f);
@@ -42,6 +43,14 @@ hipError_t launch_series_predict(hipStream_t st, const SeriesPredArgs& sa, int g
   if (lds_bytes > (size_t)SERIES_LDS_BYTES) return hipErrorInvalidValue;
   if (depth <= 4) hipLaunchKernelGGL(k_series_predict<4>, dim3(grid), dim3(256), lds_bytes, st, sa);
   else hipLaunchKernelGGL(k_series_predict<8>, dim3(grid), dim3(256), lds_bytes, st, sa);
+  return hipGetLastError();
+}
+
+hipError_t launch_series_predict_logpdf(hipStream_t st, const SeriesProbaArgs& sa, int grid, int depth, size_t lds_bytes) {
+  if (grid <= 0) return hipSuccess;
+  if (lds_bytes > (size_t)SERIES_LDS_BYTES) return hipErrorInvalidValue;
+  if (depth <= 4) hipLaunchKernelGGL(k_series_predict_logpdf<4>, dim3(grid), dim3(256), lds_bytes, st, sa);
+  else hipLaunchKernelGGL(k_series_predict_logpdf<8>, dim3(grid), dim3(256), lds_bytes, st, sa);
   return hipGetLastError();
 }
 

@@ -55,6 +55,8 @@ void launch_mixture_quantile(hipStream_t st, const double* cm, const double* cs,
 // words), the searches (a.nq > 0) and the marginal moments (a.out_mean or a.out_var) of n_queries = q_off[S] query points;
 // max_rows_el = the largest m_s Pp_s of a series
 void launch_series_mix_readout(hipStream_t st, const SeriesQuantArgs& a, long long n_queries, long long max_rows_el);
+// agp_predict_logpdf_series_batch's read-out: the log mixture density of every series' held-out vector, one thread per series
+void launch_series_mix_logp(hipStream_t st, const SeriesMixLogpArgs& a);
 // predict_sum's read-out (agp_predict.hip): raw transform, F_1 intercept, marginal quantiles on a chunk's device marginals
 void launch_sum_readout(hipStream_t st, int P, const SumReadArgs& a);
 // posterior predictive samples (agp_sample.hip): the normals of every sample column, then per chunk one workgroup per (group of
@@ -77,7 +79,7 @@ void launch_lag_grad(hipStream_t st, int P, size_t lds, const GradArgs& ga);
 void launch_grad_finish(hipStream_t st, int P, const GradArgs& ga);
 
 // ---- agp_kernels_series.hip ------------------------------------------------------------------------------------------
-hipError_t kernels_init_series();   // raises the dynamic-LDS ceiling of k_series_logpdf / k_series_logpdf_grad / k_series_predict to the whole 160 KiB (once, agp_init)
+hipError_t kernels_init_series();   // raises the dynamic-LDS ceiling of k_series_logpdf / k_series_logpdf_grad / k_series_predict / k_series_predict_logpdf to the whole 160 KiB (once, agp_init)
 // small-matrix value kernel: one workgroup per entry of sa.wg (`grid` of them), evaluation-stack depth 4 / 8, lds_bytes = the largest
 // SeriesLds total of the launch's particles
 hipError_t launch_series_logpdf(hipStream_t st, const SeriesArgs& sa, int grid, int depth, size_t lds_bytes);
@@ -86,6 +88,9 @@ hipError_t launch_series_logpdf(hipStream_t st, const SeriesArgs& sa, int grid, 
 hipError_t launch_series_logpdf_grad(hipStream_t st, const SeriesGradArgs& sa, int grid, int depth, int tape, size_t lds_bytes);
 // predictive twin (k_series_predict): depth as for the value kernel, lds_bytes = the largest series_pred_lds total of the launch's particles
 hipError_t launch_series_predict(hipStream_t st, const SeriesPredArgs& sa, int grid, int depth, size_t lds_bytes);
+// held-out twin (k_series_predict_logpdf): depth as for the value kernel, lds_bytes = the largest series_lds total of the launch's
+// particles at their JOINT lengths n_s + m_s
+hipError_t launch_series_predict_logpdf(hipStream_t st, const SeriesProbaArgs& sa, int grid, int depth, size_t lds_bytes);
 // its probe instantiation on caller matrices: workgroup b factors matrix b of `grid`, lds_bytes = series_lds(sa.n, 0, 0, 0).total doubles
 hipError_t launch_series_probe(hipStream_t st, const SeriesProbeArgs& sa, int grid, size_t lds_bytes);
 

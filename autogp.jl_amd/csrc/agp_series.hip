@@ -5,6 +5,8 @@
 //   agp_predict_series_batch           k_series_predict: posterior mean and marginal variance at every series' own query times
 //   agp_predict_quantile_series_batch  the predictive launches, their device outputs read out by agp_series_quantile_kernel.hpp on
 //                                      the same stream: quantiles and marginal moments of every series' own mixture
+//   agp_predict_logpdf_series_batch    k_series_predict_logpdf: the value kernel on the joint points, the query rows' partials read out —
+//                                      the log-density of every series' held-out values; k_series_mix_logp behind it for the mixtures
 // Each entry is one function, read top to bottom, over the stages they share (one SeriesCall carries what a stage leaves for the next):
 //   checks          series_check_sizes, series_check_pointers, series_check_layout (the entry's own pointer checks between them)
 //   series_classes  compile, per particle length / LDS need / evaluation stack, launch classes, workgroup order, out_off
@@ -121,7 +123,7 @@ void quant_fill_nan(const SeriesQuantOut& qo, size_t from, size_t to, int64_t nq
 #define STAGE(expr) do { if (const int rc_ = (expr)) return rc_; } while (0)
 
 // Which kernel the call launches: it chooses the LDS map, the instantiation rule and (gradient) the tape's limit.
-enum class SeriesMode { value, gradient, prediction };
+enum class SeriesMode { value, gradient, prediction, held_out };
 
 // One call of a many-series entry: the caller's inputs and what each shared stage leaves for the later ones.
 struct SeriesCall {
@@ -205,7 +207,7 @@ int series_check_layout(agp_ctx* c, const SeriesCall& sc) {
   return AGP_OK;
 }
 
-// LDS bytes of particle p on a series of n points: the mode's own map
+// LDS bytes of particle p on a series of n points (held_out: the joint n_s + m_s points, the value kernel's map): the mode's own map
 size_t series_need(SeriesMode mode, const Batch& bt, int p, int n) {
   const ProgHdr& h = bt.hdr[(size_t)p];
   const int m_total = mode == SeriesMode::gradient ? series_grad_lds(n, h.n_ops, h.n_prm, h.n_cp, bt.ghdr[(size_t)p].n_ops, bt.ghdr[(size_t)p].n_prm).total
@@ -248,9 +250,12 @@ int series_classes(agp_ctx* c, SeriesCall& sc, SeriesMode mode) {
     if (bt.order[(size_t)p] != p) return fail(c, AGP_ERR_HOST, "internal error: compiled batch out of order");
     const ProgHdr& h = bt.hdr[(size_t)p];
     const int32_t s = sc.series[p];
-    const int n = (int)(sc.pt_off[s + 1] - sc.pt_off[s]);
+    int n = (int)(sc.pt_off[s + 1] - sc.pt_off[s]);
     sc.len[(size_t)p] = n;
     if (sc.q_off) sc.nq[(size_t)p] = sc.q_off[s + 1] - sc.q_off[s];
+    // held-out scores: the workgroup factors the JOINT points, so length, LDS need, class and "longest first" are those of
+    // n_s + m_s; nothing held out scores 0 without a launch, as an empty series does in the value entry
+    if (mode == SeriesMode::held_out) sc.len[(size_t)p] = n = sc.nq[(size_t)p] > 0 ? n + (int)sc.nq[(size_t)p] : 0;
     if (n == 0 && sc.nq[(size_t)p] == 0) continue;      // (an empty series is launched for its prior predictive only)
     const size_t need = sc.need[(size_t)p] = series_need(mode, bt, p, n);
     if (need > (size_t)SERIES_LDS_BYTES) {
@@ -400,7 +405,7 @@ void series_copy_values(const SeriesCall& sc, double* out_logpdf, int32_t* out_i
 }
 
 // agp_get_timing: out[0] = out[2] = the value kernels of the call (covariance, factorisation, solve and value are one kernel);
-// out[4] = the band's three read-out kernels (0 in the other entries)
+// out[4] = the band's three read-out kernels, the held-out entry's mixture read-out (0 in the other entries)
 int series_timing(agp_ctx* c, const SeriesCall& sc, float readout_ms = 0.f) {
   if (!sc.prof) return AGP_OK;
   float ms = 0.f;
@@ -609,6 +614,121 @@ int predict_quantile_series(agp_ctx* c, SeriesCall& sc, const SeriesQuantOut& qo
   return series_timing(c, sc, readout_ms);
 }
 
+// The held-out side of agp_predict_logpdf_series_batch: values, transforms, mixture weights, and the outputs beside [logpdf | info].
+struct SeriesProbaOut {
+  const double* y_pred;      // [q_off[S]] held-out values, in the space of xs
+  const double* y_slope;     // [S] or null (1)
+  const double* weights;     // [P] or null: no mixtures
+  double* terms;             // [out_off[P]] or null
+  int64_t* out_off;          // [P + 1] or null
+  double* series_logp;       // [S]; null exactly when weights is
+};
+
+// The log-density of every series' held-out values under each of its particles: the value kernel on the joint points, the
+// mixtures' read-out behind it on the same stream.
+int predict_logpdf_series(agp_ctx* c, SeriesCall& sc, const SeriesProbaOut& po, double* out_logpdf, int32_t* out_info) {
+  const int P = sc.pp.P;
+  const int32_t S = sc.S;
+  char buf[256];
+  STAGE(series_check_sizes(c, sc));
+  if ((po.weights == nullptr) != (po.series_logp == nullptr))
+    return fail(c, AGP_ERR_ARG, "weights and out_series_logp must both be given or both be NULL");
+  if (P == 0 && !po.weights) return AGP_OK;
+  STAGE(series_check_pointers(c, sc, out_logpdf && out_info));
+  if (!sc.q_off || !sc.ts_pred) return fail(c, AGP_ERR_ARG, "null pointer argument (q_off or ts_pred)");
+  STAGE(series_check_layout(c, sc));
+  const size_t Q = S > 0 ? (size_t)sc.q_off[S] : 0;
+  if (!po.y_pred && Q > 0) return fail(c, AGP_ERR_ARG, "null pointer argument (y_pred with held-out points present)");
+  std::vector<double> slope((size_t)S, 1.0);
+  for (int32_t s = 0; s < S; ++s) {
+    const long long n = sc.pt_off[s + 1] - sc.pt_off[s], m = sc.q_off[s + 1] - sc.q_off[s];
+    if (m > 0 && n + m > AGP_SERIES_MAX_N) {
+      snprintf(buf, sizeof buf, "series %d has %lld training and %lld held-out points, together more than AGP_SERIES_MAX_N (%d)", (int)s, n, m,
+               AGP_SERIES_MAX_N);
+      return fail(c, AGP_ERR_ARG, buf);
+    }
+    for (long long j = 0; j < m; ++j)
+      if (!std::isfinite(po.y_pred[sc.q_off[s] + j])) {
+        snprintf(buf, sizeof buf, "series %d: held-out value %lld is not finite", (int)s, j);
+        return fail(c, AGP_ERR_ARG, buf);
+      }
+    if (po.y_slope) slope[(size_t)s] = po.y_slope[s];
+    if (const int rc = check_y_transform(c, slope[(size_t)s], 0.0)) return fail_series(c, rc, s);
+  }
+  QuantPlan qp;      // the band entry's lists and weight checks (no quantiles, no rows read)
+  if (po.weights) {
+    const SeriesQuantOut qo{po.weights, po.y_slope, nullptr, nullptr, 0, 0.0, 0, nullptr, nullptr, nullptr, nullptr, nullptr};
+    STAGE(quant_plan(c, S, P, sc.series, sc.q_off, qo, qp));
+  }
+  const double nanv = std::numeric_limits<double>::quiet_NaN();
+  if (P == 0) { std::fill(po.series_logp, po.series_logp + S, nanv); return AGP_OK; }      // (S series without a particle)
+  STAGE(series_classes(c, sc, SeriesMode::held_out));
+  if (po.out_off) std::copy(sc.ooff.begin(), sc.ooff.end(), po.out_off);      // (no check is left to fail, nothing is launched yet)
+  if (sc.wg.empty()) {      // nothing held out for any particle: every score is 0, and so is every mixture's
+    series_zero_values(sc, out_logpdf, out_info);
+    for (int32_t s = 0; s < S && po.series_logp; ++s) po.series_logp[s] = qp.tab[(size_t)s + 1] > qp.tab[(size_t)s] ? 0.0 : nanv;
+    return AGP_OK;
+  }
+  STAGE(series_stage(c, sc));
+  Slot* s = sc.s;
+  // sq_w = [y_pred (Q) | slope (S) | the plan's values: w (W) ..]; sq_tab = [pl_off | w_off | row_off | plist]; sq_out = the mixtures (S)
+  const size_t S1 = (size_t)S + 1, o_plist = sizeof(long long) * 3 * S1;
+  HIPCHK(c, s->sq_w.ensure(sizeof(double) * std::max<size_t>(1, Q + (size_t)S + qp.vals.size())));
+  sc.up.add(s->sq_w.p, po.y_pred, sizeof(double) * Q);
+  sc.up.add(s->sq_w.as<double>() + Q, slope.data(), sizeof(double) * (size_t)S);
+  if (po.weights) {
+    HIPCHK(c, s->sq_tab.ensure(o_plist + sizeof(int32_t) * (size_t)P));
+    HIPCHK(c, s->sq_out.ensure(sizeof(double) * (size_t)S));
+    sc.up.add(s->sq_w.as<double>() + Q + S, qp.vals.data(), sizeof(double) * qp.vals.size());
+    sc.up.add(s->sq_tab.p, qp.tab.data(), o_plist);
+    sc.up.add(s->sq_tab.as<char>() + o_plist, qp.plist.data(), sizeof(int32_t) * (size_t)P);
+  }
+  HIPCHK(c, sc.up.flush(s->h_stage, s->up_blob, sc.st));
+  SeriesProbaArgs pa = {};
+  static_cast<SeriesArgs&>(pa) = sc.sa;
+  pa.q_off = sc.in_map<const long long>(sc.o_qoff);
+  pa.out_off = sc.in_map<const long long>(sc.o_ooff);
+  pa.ts_pred = s->tt.as<double>() + 2 * sc.npts; pa.noise_pred = s->noise_pred.as<double>();
+  pa.y_pred = s->sq_w.as<double>(); pa.y_slope = s->sq_w.as<double>() + Q;
+  pa.out_terms = po.terms ? s->pred_mean.as<double>() : nullptr;
+  STAGE(series_launch(c, sc, [&](const int32_t* wg, int grid, int d, size_t lds) {
+    pa.wg = wg;
+    return launch_series_predict_logpdf(sc.st, pa, grid, d == 0 ? 4 : 8, lds);
+  }));
+  if (po.weights) {
+    SeriesMixLogpArgs ma = {};
+    ma.S = S;
+    ma.q_off = pa.q_off;
+    ma.pl_off = s->sq_tab.as<long long>(); ma.w_off = ma.pl_off + S1;
+    ma.plist = reinterpret_cast<const int32_t*>(s->sq_tab.as<char>() + o_plist);
+    ma.w = s->sq_w.as<double>() + Q + S;
+    ma.lp = sc.sa.out_lp; ma.info = sc.sa.out_info;
+    ma.out = s->sq_out.as<double>();
+    launch_series_mix_logp(sc.st, ma);
+    HIPCHK(c, hipGetLastError());
+    if (sc.prof) HIPCHK(c, hipEventRecord(sc.ev[2], sc.st));
+  }
+  // h_out = [logpdf | info | terms (out_off[P]) | mixtures (S)], the last two when wanted
+  const size_t n_terms = po.terms ? sc.n_out() : 0, o_terms = sc.o_own(), o_mix = o_terms + sizeof(double) * n_terms;
+  STAGE(series_fetch_values(c, sc, o_mix + sizeof(double) * (po.weights ? (size_t)S : 0)));
+  char* ho = static_cast<char*>(s->h_out.p);
+  if (n_terms > 0) HIPCHK(c, hipMemcpyAsync(ho + o_terms, s->pred_mean.p, sizeof(double) * n_terms, hipMemcpyDeviceToHost, sc.st));
+  if (po.weights) HIPCHK(c, hipMemcpyAsync(ho + o_mix, s->sq_out.p, sizeof(double) * (size_t)S, hipMemcpyDeviceToHost, sc.st));
+  HIPCHK(c, hipStreamSynchronize(sc.st));
+  series_copy_values(sc, out_logpdf, out_info);      // (nothing held out: length 0 here, so 0 and info 0)
+  if (n_terms > 0) {      // every particle with held-out points was launched and wrote its whole block
+    const double* ht = reinterpret_cast<const double*>(ho + o_terms);
+    std::copy(ht, ht + n_terms, po.terms);
+  }
+  if (po.weights) {
+    const double* hm = reinterpret_cast<const double*>(ho + o_mix);
+    std::copy(hm, hm + S, po.series_logp);
+  }
+  float readout_ms = 0.f;
+  if (sc.prof && po.weights) HIPCHK(c, hipEventElapsedTime(&readout_ms, sc.ev[1], sc.ev[2]));
+  return series_timing(c, sc, readout_ms);
+}
+
 #undef STAGE
 
 // agp_debug_series_factor: P caller matrices of one size through stages 4 and 5 of the value kernel (its probe instantiation).
@@ -706,6 +826,18 @@ int agp_predict_quantile_series_batch(agp_ctx* c, int32_t S, const int64_t* pt_o
     SeriesCall sc{S, pt_off, ts, xs, {P, op_off, ops, prm_off, prm, noise, noise_pred}, series, q_off, ts_pred};
     const SeriesQuantOut qo{weights, y_slope, y_intercept, q, nq, tol, max_iter, out_x, out_converged, out_iters, out_mix_mean, out_mix_var};
     return predict_quantile_series(c, sc, qo, out_logpdf, out_info);
+  });
+}
+
+int agp_predict_logpdf_series_batch(agp_ctx* c, int32_t S, const int64_t* pt_off, const double* ts, const double* xs,
+                                    const int64_t* q_off, const double* ts_pred, const double* y_pred, int32_t P, const int32_t* series,
+                                    const int32_t* op_off, const uint8_t* ops, const int32_t* prm_off, const double* prm,
+                                    const double* noise, const double* noise_pred, const double* y_slope, const double* weights,
+                                    double* out_logpdf, double* out_terms, int64_t* out_off, double* out_series_logp, int32_t* out_info) {
+  return abi_guard(c, [&] {
+    SeriesCall sc{S, pt_off, ts, xs, {P, op_off, ops, prm_off, prm, noise, noise_pred}, series, q_off, ts_pred};
+    const SeriesProbaOut po{y_pred, y_slope, weights, out_terms, out_off, out_series_logp};
+    return predict_logpdf_series(c, sc, po, out_logpdf, out_info);
   });
 }
 

@@ -58,6 +58,21 @@
 //       (series_predict_blocks).  sigma_cp at the query times sits in the per-point tables' entries 192 .. 255.
 // The gradient kernel's full Z = L^-T is not formed (n^3 / 3 flops and nb - 1 barrier pairs for n^2 m of work).  An empty series with
 // query points gives the prior predictive (series_prior_predict).  On a bad pivot NaN is written to the particle's whole block.
+//
+// k_series_predict_logpdf<D> (agp_predict_logpdf_series_batch) is the value kernel on the JOINT points of a series — its n training
+// points followed, without padding, by its m query points, N = n + m <= SERIES_MAX_N — read out over the query rows alone: the
+// log-density of the held-out values y under the particle's posterior predictive (predict_proba), by the route of
+// agp_predict_logpdf_batch: with L the factor of [K11 + noise I, K12; K21, K22 + noise_pred I] and z = L^-1 [xs; y],
+//   log p(y | xs) = -(m log 2 pi + 2 sum_{k >= n} log L_kk + sum_{k >= n} z_k^2) / 2.
+// One body (series_body, selected by the argument type SeriesProbaArgs), the value kernel's LDS map at N points; it differs in
+//   1. the loads: tpt = [ts | ts_pred], rvec = [xs | y_pred] (the train / query split falls anywhere inside a 16-block);
+//   3. the diagonal: noise[p] for index < n, noise_pred[p] for index in [n, N); rows / columns past N identity as ever;
+//   the read-out: both reductions (fixed order, as above) over the rows [n, N) alone, + m log|y_slope[s]| (the density of the raw
+//      values), and optionally the per-point terms -(log 2 pi + z_k^2) / 2 - log L_kk + log|y_slope[s]| of those rows — the density of
+//      held-out point k - n given the training data and the held-out points before it — particle-major behind out_off.
+// Stages 2, 4 and 5 are the value kernel's statements over N points.  out_info[p] = the first bad pivot of the joint factor (1 .. n:
+// K11; n + k: leading minor k of the predictive covariance), NaN then in out_lp[p] and the particle's whole terms block.  n = 0 (the
+// prior predictive) takes the same code; m = 0 is never launched (the host answers 0).
 #pragma once
 #include <type_traits>
 #include "agp_common.hpp"
@@ -228,9 +243,12 @@ template <int D, bool PROBE, int GS, class ArgsT>
 __device__ __forceinline__ void series_body(const ArgsT& a, double* smem) {
   constexpr int E = 4;
   constexpr bool PRED = std::is_same_v<ArgsT, SeriesPredArgs>;
+  constexpr bool PROBA = std::is_same_v<ArgsT, SeriesProbaArgs>;      // the held-out twin: n below is the JOINT length
   const int tid = threadIdx.x, l = tid & 63, w = tid >> 6, l15 = l & 15, lq = l >> 4;
   int p, n;
   long long o0 = 0;
+  [[maybe_unused]] int ntr = 0;            // PROBA: training points (rows [ntr, n) are the query rows)
+  [[maybe_unused]] long long q0 = 0;       // PROBA: the series' first query
   if constexpr (PROBE) {
     p = blockIdx.x;
     n = a.n;
@@ -239,6 +257,12 @@ __device__ __forceinline__ void series_body(const ArgsT& a, double* smem) {
     const int sidx = a.series[p];
     o0 = a.pt_off[sidx];
     n = (int)(a.pt_off[sidx + 1] - o0);
+    if constexpr (PROBA) {
+      q0 = a.q_off[sidx];
+      const long long mq = a.q_off[sidx + 1] - q0;
+      ntr = n;
+      n = (mq <= 0 || mq > SERIES_MAX_N) ? 0 : n + (int)mq;      // (nothing held out: never launched, like an empty series)
+    }
   }
   if (n <= 0 || n > SERIES_MAX_N) {      // (the host answers empty series itself and refuses long ones: never launched ...
     if constexpr (PRED) {                // ... but for the prior predictive of an empty series)
@@ -285,7 +309,15 @@ __device__ __forceinline__ void series_body(const ArgsT& a, double* smem) {
     }
   } else {
     // ---- 1. inputs ----
-    if (tid < np) {
+    if constexpr (PROBA) {
+      // the joint points: the series' times, then — directly behind them, no padding between — its query times; xs, then the held-out values
+      if (tid < np) {
+        const int k = tid < n ? tid : n - 1;
+        tpt[tid] = k < ntr ? a.ts[o0 + k] : a.ts_pred[q0 + (k - ntr)];
+        rvec[tid] = tid < ntr ? a.xs[o0 + tid] : tid < n ? a.y_pred[q0 + (tid - ntr)] : 0.0;
+        avec[tid] = 0.0;
+      }
+    } else if (tid < np) {
       tpt[tid] = a.ts[o0 + (tid < n ? tid : n - 1)];      // (padding points: a finite time; their entries are overwritten with identity)
       rvec[tid] = tid < n ? a.xs[o0 + tid] : 0.0;
       avec[tid] = 0.0;
@@ -304,6 +336,8 @@ __device__ __forceinline__ void series_body(const ArgsT& a, double* smem) {
     // ---- 3. K + noise I, lower block triangle; one block per wave and pass, lane (i = l%16, q = l/16) <-> elements (i, q + 4 e) ----
     {
       const double noise = a.noise[p];
+      [[maybe_unused]] double noise_q = 0.0;      // PROBA: the diagonal addend of the query rows
+      if constexpr (PROBA) noise_q = a.noise_pred[p];
       const int nblk = nb * (nb + 1) / 2;
       for (int b = w; b < nblk; b += 4) {
         int rb, cb;
@@ -321,7 +355,10 @@ __device__ __forceinline__ void series_body(const ArgsT& a, double* smem) {
         eval_program<D, E, 0>(h, ops, prm, sig, tr, tc, ri, ci, lt, out, etab);
         double* blk = sm + blk_idx(rb, cb) * 256;
 #pragma unroll
-        for (int e = 0; e < E; ++e) blk[64 * e + l] = cov_finalize(out[e], ri[e], ci[e], n, np, 0, noise);
+        for (int e = 0; e < E; ++e) {
+          if constexpr (PROBA) blk[64 * e + l] = cov_finalize(out[e], ri[e], ci[e], n, np, 0, ri[e] < ntr ? noise : noise_q);
+          else blk[64 * e + l] = cov_finalize(out[e], ri[e], ci[e], n, np, 0, noise);
+        }
       }
     }
   }
@@ -332,24 +369,44 @@ __device__ __forceinline__ void series_body(const ArgsT& a, double* smem) {
   int bad = 0;           // first non-positive pivot (1-based index in the series), 0 = none; kept by wave 0
   lds_chol_steps<0>(sm, Wl, rvec, avec, nb, nb, 64, np, 0, bad, tid);
 
-  // ---- the value: 2 sum log L_ii (padding rows: log 1) and alpha'alpha, reduced in a fixed order ----
+  // ---- the value: 2 sum log L_ii (padding rows: log 1) and alpha'alpha, reduced in a fixed order
+  //      (PROBA: both over the query rows [ntr, n) alone — the conditional density of the held-out values) ----
+  [[maybe_unused]] double lgd = 0.0;      // PROBA: log L_kk of the thread's own row
   {
     double ld = 0.0;
     if (tid < np) {
       const double dii = sm[blk_idx(tid >> 4, tid >> 4) * 256 + 17 * (tid & 15)];
-      ld = 2.0 * log(dii);
+      if constexpr (PROBA) {
+        lgd = log(dii);
+        ld = tid >= ntr ? 2.0 * lgd : 0.0;
+      } else {
+        ld = 2.0 * log(dii);
+      }
     }
     Wl[tid] = ld;      // (the last inverse block has been consumed)
+    if constexpr (PROBA) {
+      if (tid == 0) rvec[0] = (double)bad;      // (wave 0 keeps the first bad pivot; rvec is dead)
+    }
   }
   __syncthreads();
   if (w == 0) {
     double ld = (Wl[l] + Wl[l + 64]) + (Wl[l + 128] + Wl[l + 192]);
     double ss = 0.0;
-    for (int i = l; i < np; i += 64) ss = fma(avec[i], avec[i], ss);
+    if constexpr (PROBA) {
+      for (int i = l; i < np; i += 64) ss = i >= ntr ? fma(avec[i], avec[i], ss) : ss;
+    } else {
+      for (int i = l; i < np; i += 64) ss = fma(avec[i], avec[i], ss);
+    }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) { ss += __shfl_xor(ss, off); ld += __shfl_xor(ld, off); }
     if (l == 0) {
-      const double lp = -0.5 * ((double)n * 1.8378770664093454835606594728112 + ld + ss);
+      double lp;
+      if constexpr (PROBA) {      // m log 2 pi, and the Jacobian of the series' own transform: m log|slope|
+        const double mq = (double)(n - ntr);
+        lp = -0.5 * (mq * 1.8378770664093454835606594728112 + ld + ss) + mq * log(fabs(a.y_slope[a.series[p]]));
+      } else {
+        lp = -0.5 * ((double)n * 1.8378770664093454835606594728112 + ld + ss);
+      }
       a.out_lp[p] = bad != 0 ? __builtin_nan("") : lp;
       a.out_info[p] = bad;
       if constexpr (PROBE) { a.out_part[2 * p] = ld; a.out_part[2 * p + 1] = ss; }
@@ -359,6 +416,15 @@ __device__ __forceinline__ void series_body(const ArgsT& a, double* smem) {
     const int nel = nb * (nb + 1) / 2 * 256;
     for (int i = tid; i < nel; i += 256) a.out_blk[(long long)p * nel + i] = sm[i];
     if (tid < np) a.out_alpha[(long long)p * np + tid] = avec[tid];
+  }
+
+  if constexpr (PROBA) {
+    // ---- the per-point terms: log N(y_j | training data, y_0 .. y_{j-1}) from row ntr + j of the joint factor (chain rule) ----
+    if (a.out_terms != nullptr && tid >= ntr && tid < n) {
+      const double z = avec[tid];
+      const double t = (-0.5 * fma(z, z, 1.8378770664093454835606594728112) - lgd) + log(fabs(a.y_slope[a.series[p]]));
+      a.out_terms[a.out_off[p] + (tid - ntr)] = rvec[0] != 0.0 ? __builtin_nan("") : t;
+    }
   }
 
   if constexpr (PRED) {
@@ -552,6 +618,14 @@ template <int D, int GS>
 __global__ __launch_bounds__(256, 2) void k_series_logpdf_grad(SeriesGradArgs a) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   series_body<D, false, GS>(a, smem);
+}
+
+// Log-density of one series' held-out values under one particle's predictive by one workgroup: the value kernel's body on the
+// joint points (agp_predict_logpdf_series_batch).
+template <int D>
+__global__ __launch_bounds__(256, 2) void k_series_predict_logpdf(SeriesProbaArgs a) {
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  series_body<D, false, 0>(a, smem);
 }
 
 // Posterior mean and marginal variance of one (series, particle) pair at the series' own query times by one workgroup, behind the

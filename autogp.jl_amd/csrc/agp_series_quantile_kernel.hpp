@@ -145,4 +145,38 @@ __global__ __launch_bounds__(256) void k_series_mix_moments(SeriesQuantArgs a) {
   if (a.out_var) a.out_var[g] = var;
 }
 
+// The mixture read-out of agp_predict_logpdf_series_batch, thread s of S: the log of series s's mixture density at its held-out
+// vector, out[s] = M + log sum_{w_j > 0} w_j exp(lp_j - M), M = max_{w_j > 0} lp_j, over the series' list in ascending order (one
+// thread, one order).  NaN when ANY particle of the series has info != 0, whatever its weight, and for a series without particles
+// (the band's rule); exactly 0 for a series with particles and nothing held out (its particles were not launched: lp is not read).
+__global__ __launch_bounds__(256) void k_series_mix_logp(SeriesMixLogpArgs a) {
+  const int s = blockIdx.x * 256 + threadIdx.x;
+  if (s >= a.S) return;
+  const long long pl0 = a.pl_off[s];
+  const int Ps = (int)(a.pl_off[s + 1] - pl0);
+  double r = __builtin_nan("");
+  if (Ps != 0) {
+    if (a.q_off[s + 1] == a.q_off[s]) {
+      r = 0.0;
+    } else {
+      const int32_t* __restrict__ pl = a.plist + pl0;
+      const double* __restrict__ w = a.w + a.w_off[s];
+      int bad = 0;
+      double M = -__builtin_inf();
+      for (int j = 0; j < Ps; ++j) {
+        const int p = pl[j];
+        bad |= a.info[p];
+        if (w[j] > 0.0) M = fmax(M, a.lp[p]);
+      }
+      if (bad == 0) {
+        double sum = 0.0;
+        for (int j = 0; j < Ps; ++j)
+          if (w[j] > 0.0) sum = fma(w[j], exp(a.lp[pl[j]] - M), sum);
+        r = M + log(sum);
+      }
+    }
+  }
+  a.out[s] = r;
+}
+
 }  // namespace agp

@@ -39,6 +39,7 @@ EXPORTED_SYMBOLS = [
     "agp_remove_data", "agp_get_remove_stats", "agp_set_remove_update", "agp_remove_data_multi",
     "agp_debug_factor_batch", "agp_logpdf_series_batch", "agp_debug_series_factor", "agp_logpdf_grad_series_batch",
     "agp_predict_series_batch", "agp_debug_remove_factor", "agp_predict_quantile_series_batch",
+    "agp_predict_logpdf_series_batch",
 ]
 COMM_ID_BYTES = 128
 SERIES_MAX_N = 176      # AGP_SERIES_MAX_N of include/autogp_hip.h: the longest series of logpdf_series_batch
@@ -114,6 +115,9 @@ def load_library(path=None):
                                                       u8p, ip, dp, dp, dp, dp, dp, dp, dp, C.c_int64, C.c_double, C.c_int64, dp, ip, ip,
                                                       dp, dp, dp, ip]
     lib.agp_predict_quantile_series_batch.restype = C.c_int
+    lib.agp_predict_logpdf_series_batch.argtypes = [vp, C.c_int32, C.POINTER(C.c_int64), dp, dp, C.POINTER(C.c_int64), dp, dp, C.c_int32, ip,
+                                                    ip, u8p, ip, dp, dp, dp, dp, dp, dp, dp, C.POINTER(C.c_int64), dp, ip]
+    lib.agp_predict_logpdf_series_batch.restype = C.c_int
     lib.agp_logpdf_grad_batch.argtypes = [vp, C.c_int64, C.c_int32, ip, u8p, ip, dp, dp, dp, dp, dp, ip]
     lib.agp_logpdf_grad_batch.restype = C.c_int
     lib.agp_logpdf_grad.argtypes = [vp, C.c_int64, u8p, C.c_int32, dp, C.c_int32, C.c_double, dp, dp, dp, ip]
@@ -353,6 +357,35 @@ def pack_series_mixture(series_index, S, weights=None, log_weights=None):
 
 
 SeriesBand = collections.namedtuple("SeriesBand", "x converged iters mean var logpdf info")
+
+
+def pack_heldout(heldout, q_off, y_transforms=None):
+    """The held-out side of predict_logpdf_series_batch: (y_pred, slope or None) from one vector of RAW held-out values per series,
+    series s's as long as its vector of query times (q_off: pack_queries').  y_transforms: one (slope, intercept) per series
+    (scaled = slope * raw + intercept; None: the values are passed as they are); y_pred is the concatenation of the SCALED values —
+    the space xs is in — and slope what the library's Jacobian term needs.  Raises ValueError on anything but one vector per series
+    of the query vector's length, and on a y_transforms that is not (S, 2) — before any library call."""
+    S = q_off.shape[0] - 1
+    if len(heldout) != S:
+        raise ValueError(f"one vector of held-out values per series required ({len(heldout)} for {S} series)")
+    slope = icpt = None
+    if y_transforms is not None:
+        yt = _f64(y_transforms)
+        if yt.shape != (S, 2):
+            raise ValueError(f"y_transforms has shape {yt.shape}, expected ({S}, 2): one (slope, intercept) per series")
+        slope, icpt = np.ascontiguousarray(yt[:, 0]), yt[:, 1]
+    parts = []
+    for s, y in enumerate(heldout):
+        y = _f64(y)
+        m = int(q_off[s + 1] - q_off[s])
+        if y.ndim != 1 or y.shape[0] != m:
+            raise ValueError(f"series {s}: {m} held-out values required, one per query time (got shape {y.shape})")
+        parts.append(y if slope is None else slope[s] * y + icpt[s])
+    y_pred = np.ascontiguousarray(np.concatenate(parts)) if parts else np.zeros(0)
+    return y_pred, slope
+
+
+SeriesScores = collections.namedtuple("SeriesScores", "logpdf terms series_logp info")
 
 
 def check_remove_indexes(indexes, n_max):
@@ -609,6 +642,43 @@ class GPEngine:
             blocks = lambda a: [a[lo[s]:lo[s + 1]].reshape(nq, qo[s + 1] - qo[s]).T for s in range(S)]
         cut = lambda a: None if a is None else [a[qo[s]:qo[s + 1]] for s in range(S)]
         return SeriesBand(blocks(x), blocks(conv), blocks(iters), cut(mean), cut(var), lp, info)
+
+    def predict_logpdf_series_batch(self, series, queries, heldout, nodes, noises, series_index, weights=None, y_transforms=None,
+                                    noise_pred=None, want_terms=False, check=True, programs=None):
+        """agp_predict_logpdf_series_batch: the held-out scores of many short series in one fused launch — predict_logpdf_batch's twin
+        for callers that hold one model per short series, with predict_series_batch's series / query / particle arguments and
+        statelessness.  heldout[s] holds the RAW values observed at queries[s]; particle p scores them under its posterior predictive
+        on series[series_index[p]] (len(series[s]) + len(queries[s]) <= SERIES_MAX_N).  y_transforms: one (slope, intercept) per
+        series (scaled = slope * raw + intercept, the space the series' xs are in; None: (1, 0)) — the values are scaled here, as
+        predict_proba does, and the density of the raw values gains m log|slope|.  weights[p] (optional) is particle p's weight inside
+        the mixture of ITS series (pack_series_mixture).  Returns SeriesScores(logpdf, terms, series_logp, info): logpdf (P,); terms
+        (want_terms) a list of views, terms[p][j] the log-density of held-out point j given the training data and the points before
+        it, summing to logpdf[p]; series_logp (S,) with weights — the log of each series' mixture density at its held-out vector
+        (NaN for a series without particles or with a failed particle, 0 where nothing is held out) — else None."""
+        packed = series_call_args(series, nodes, noises, series_index, programs)
+        S, P, sidx = packed[0].shape[0] - 1, packed[4], packed[6]
+        if noise_pred is not None and np.ndim(noise_pred) == 0:
+            noise_pred = np.full(P, float(noise_pred))      # (a scalar serves every particle)
+        qpack = pack_queries(queries, S, noise_pred, P)
+        y_pred, slope = pack_heldout(heldout, qpack[0], y_transforms)
+        if weights is not None:
+            weights = _f64(weights)
+            if weights.shape != (P,):
+                raise ValueError(f"weights has shape {weights.shape}, expected ({P},)")
+        m_s = np.diff(qpack[0])
+        total = int(sum(m_s[i] for i in sidx if 0 <= i < S))      # (an index outside is the library's to report)
+        lp = np.empty(max(1, P), dtype=np.float64); info = np.zeros(max(1, P), dtype=np.int32)
+        terms = np.empty(max(1, total)) if want_terms else None
+        out_off = np.zeros(P + 1, dtype=np.int64)
+        mix = np.empty(max(1, S)) if weights is not None else None
+        a = _series_ctypes(packed, qpack)      # (.., q_off, ts_pred | P, ..): the held-out values travel between the two
+        self._check(self._lib.agp_predict_logpdf_series_batch(
+            self._ctx, *a[:6], _dp(y_pred if y_pred.size else np.zeros(1)), *a[6:], _dp(slope), _dp(weights), _dp(lp), _dp(terms),
+            out_off.ctypes.data_as(C.POINTER(C.c_int64)), _dp(mix), _ip(info)))
+        lp, info = lp[:P], info[:P]
+        _raise_first_bad(info, check)
+        cut = None if terms is None else [terms[out_off[p]:out_off[p + 1]] for p in range(P)]
+        return SeriesScores(lp, cut, None if mix is None else mix[:S], info)
 
     def logpdf_batch_extend(self, nodes, noises, n=None, check=True, programs=None):
         """agp_logpdf_batch_extend: like logpdf_batch, but the factors stay resident and a later call on a longer
@@ -1477,6 +1547,20 @@ def predict_quantile_series(engine, series, queries, nodes, noises, series_index
     band = engine.predict_quantile_series_batch(series, queries, nodes, noises, series_index, w, q, y_transforms=y_transforms,
                                                 noise_pred=noise_pred, tol=tol, max_iter=max_iter)
     return [(x, (bool(c.all()) if np.ndim(q) == 0 else c.all(axis=0))) for x, c in zip(band.x, band.converged)]
+
+
+def predict_proba_series(engine, series, queries, heldout, nodes, noises, series_index, log_weights, y_transforms=None, noise_pred=None):
+    """predict_proba for callers that hold one model per short series: particle p belongs to the model of series[series_index[p]],
+    which weighs it by the softmax of log_weights over THAT series' particles (pack_series_mixture); heldout[s] are the RAW values
+    observed at queries[s]; one call of GPEngine.predict_logpdf_series_batch serves every series.  Returns a list over the series of
+    dicts with the reference's three columns {"particle", "weight", "logp"} — "particle" the 1-based positions inside the series'
+    model, as predict_proba numbers them — plus "mixture_logp", the log-density of the held-out vector under the model's mixture.
+    Raises PosDefException when a particle has no predictive."""
+    lists, w = pack_series_mixture(series_index, len(series), log_weights=log_weights)
+    sc = engine.predict_logpdf_series_batch(series, queries, heldout, nodes, noises, series_index, weights=w, y_transforms=y_transforms,
+                                            noise_pred=noise_pred)
+    return [{"particle": np.arange(1, sel.size + 1), "weight": w[sel], "logp": sc.logpdf[sel], "mixture_logp": float(sc.series_logp[s])}
+            for s, sel in enumerate(lists)]
 
 
 def predict_rand(engine, nodes, noises, log_weights, ts_pred, n_samples=None, seed=0, y_transform=(1.0, 0.0), noise_pred=None):

@@ -337,6 +337,62 @@ function predict_quantile_series_batch(eng::Engine, series::Vector{<:Tuple{Vecto
     return xs_, cs_, is_, means, vars, out[1:P], info[1:P]
 end
 
+"Held-out scores of many short series in one fused launch (agp_predict_logpdf_series_batch): `predict_proba` for callers that hold
+one model per short series, with `predict_series_batch`'s series / query / particle arguments and statelessness.  `heldout[s]` holds
+the RAW values observed at `queries[s]`; particle `p` scores them under its posterior predictive on `series[series_index[p]]`
+(1-based; training plus held-out points of a series at most `SERIES_MAX_N`).  `y_transforms[s] = (slope, intercept)` of series `s`
+(scaled = slope * raw + intercept, the space the series' `xs` are in; `nothing`: (1, 0)): the values are scaled here and the density
+of the raw values gains `m log|slope|`.  `weights[p]` (or `nothing`) is particle `p`'s weight inside ITS series' mixture.  Returns
+`(logpdf, terms, series_logp, info)`: `terms[p][j]` is the log-density of held-out point `j` given the training data and the points
+before it (they sum to `logpdf[p]`); `series_logp[s]` the log of the series' mixture density at its held-out vector (`nothing`
+without weights; NaN for a series without particles or with a failed particle, 0 where nothing is held out)."
+function predict_proba_series_batch(eng::Engine, series::Vector{<:Tuple{Vector{Float64},Vector{Float64}}},
+                                    queries::Vector{Vector{Float64}}, heldout::Vector{Vector{Float64}}, nodes::Vector{<:GP.Node},
+                                    noises::Vector{Float64}, series_index::Vector{<:Integer};
+                                    weights::Union{Nothing,Vector{Float64}}=nothing,
+                                    y_transforms::Union{Nothing,Vector{Tuple{Float64,Float64}}}=nothing,
+                                    noise_pred::Union{Nothing,Vector{Float64}}=nothing)
+    P = length(nodes); S = length(series)
+    (length(noises) == P && length(series_index) == P) || throw(ArgumentError("one noise and one series index per particle required"))
+    (weights === nothing || length(weights) == P) || throw(ArgumentError("one weight per particle required"))
+    (length(queries) == S && length(heldout) == S) ||
+        throw(ArgumentError("one vector of query times and one of held-out values per series required"))
+    (noise_pred === nothing || length(noise_pred) == P) || throw(ArgumentError("one noise_pred per particle required"))
+    (y_transforms === nothing || length(y_transforms) == S) || throw(ArgumentError("one (slope, intercept) per series required"))
+    all(i -> 1 <= i <= S, series_index) || throw(ArgumentError("series index outside 1:$S"))
+    pt_off = Int64[0]; ts = Float64[]; xs = Float64[]; q_off = Int64[0]; tq = Float64[]; yq = Float64[]
+    for (s, (t, x)) in enumerate(series)
+        length(t) == length(x) || throw(ArgumentError("series $s: ts and xs must have equal lengths"))
+        length(t) <= SERIES_MAX_N || throw(ArgumentError("series $s has $(length(t)) points, more than SERIES_MAX_N ($SERIES_MAX_N)"))
+        length(heldout[s]) == length(queries[s]) ||
+            throw(ArgumentError("series $s: $(length(queries[s])) held-out values required, one per query time"))
+        a, b = y_transforms === nothing ? (1.0, 0.0) : y_transforms[s]
+        append!(ts, t); append!(xs, x); push!(pt_off, length(ts))
+        append!(tq, queries[s]); push!(q_off, length(tq))
+        append!(yq, y_transforms === nothing ? heldout[s] : a .* heldout[s] .+ b)
+    end
+    isempty(ts) && (push!(ts, 0.0); push!(xs, 0.0))
+    isempty(tq) && (push!(tq, 0.0); push!(yq, 0.0))
+    sidx = Int32[Int32(i - 1) for i in series_index]
+    op_off, ops, prm_off, prm = encode_batch(nodes)
+    slope = y_transforms === nothing ? ones(Float64, max(1, S)) : Float64[t[1] for t in y_transforms]
+    total = sum(Int[length(queries[i]) for i in series_index])
+    out = Vector{Float64}(undef, max(1, P)); info = zeros(Int32, max(1, P))
+    terms = Vector{Float64}(undef, max(1, total)); out_off = zeros(Int64, P + 1)
+    mix = Vector{Float64}(undef, max(1, S))
+    np = noise_pred === nothing ? noises : noise_pred
+    w = weights === nothing ? Float64[] : weights
+    GC.@preserve pt_off ts xs q_off tq yq sidx op_off ops prm_off prm noises np slope w out terms out_off mix info check(eng, ccall((:agp_predict_logpdf_series_batch, LIB), Cint,
+        (Ptr{Cvoid}, Int32, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Int32}, Ptr{Int32},
+         Ptr{UInt8}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+         Ptr{Int64}, Ptr{Float64}, Ptr{Int32}),
+        eng.ptr, S, pt_off, ts, xs, q_off, tq, yq, P, sidx, op_off, ops, prm_off, prm, noises, np, slope,
+        weights === nothing ? Ptr{Float64}(C_NULL) : pointer(w), out, terms, out_off,
+        weights === nothing ? Ptr{Float64}(C_NULL) : pointer(mix), info))
+    cut = [terms[out_off[p] + 1:out_off[p + 1]] for p in 1:P]
+    return out[1:P], cut, (weights === nothing ? nothing : mix[1:S]), info[1:P]
+end
+
 "(extended, from_scratch, tile_rows_reused, tile_rows_total, evicted_before_reuse, slots, callers, occupied, capacity_tile_rows, growth_copies) of the factor store"
 function extend_stats(eng::Engine)
     out = zeros(Int64, 10)

@@ -88,6 +88,37 @@ kernels() = GP.Node[
         @test eng.n_max == 700      # the resident series is untouched
     end
 
+    @testset "many short series: held-out scores in one call (stateless)" begin
+        ks = kernels()
+        splits = ((0, 5), (17, 5), (126, 18), (144, 32))      # (training points, held-out points)
+        sers = [(ts[1:n], xs[1:n]) for (n, _) in splits]
+        qs = [ts[n + 1:n + m] for (n, m) in splits]
+        a, b = 0.7, -0.2                                       # scaled = a raw + b
+        held = [(xs[n + 1:n + m] .- b) ./ a for (n, m) in splits]
+        nodes = GP.Node[]; sidx = Int[]
+        for s in eachindex(sers), k in ks
+            push!(nodes, k); push!(sidx, s)
+        end
+        P = length(nodes)
+        w = Float64[1 / length(ks) for _ in 1:P]
+        lp, terms, mix, info = H.predict_proba_series_batch(eng, sers, qs, held, nodes, fill(noise, P), sidx; weights=w,
+                                                            y_transforms=fill((a, b), length(sers)))
+        @test all(info .== 0)
+        for (p, (k, s)) in enumerate(zip(nodes, sidx))
+            n, m = splits[s]
+            # the chain rule with noise_pred = noise: log p(joint) - log p(training part), plus the Jacobian of the transform
+            r = ref_logpdf(k, noise, ts[1:n + m], xs[1:n + m]) - (n == 0 ? 0.0 : ref_logpdf(k, noise, ts[1:n], xs[1:n])) + m * log(a)
+            @test relerr(lp[p], r) <= 1e-7
+            @test length(terms[p]) == m && relerr(sum(terms[p]), lp[p]) <= 1e-12
+        end
+        for s in eachindex(sers)
+            sel = findall(==(s), sidx)
+            M = maximum(lp[sel])
+            @test relerr(mix[s], M + log(sum(w[sel] .* exp.(lp[sel] .- M)))) <= 1e-12
+        end
+        @test eng.n_max == 700      # the resident series is untouched
+    end
+
     @testset "not positive definite" begin
         bad = GP.Linear(0.0, 0.0, -0.01)
         @test_throws LinearAlgebra.PosDefException H.logpdf(eng, bad, 0.1, 700)

@@ -233,6 +233,51 @@ int agp_predict_quantile_series_batch(agp_ctx* ctx, int32_t S, const int64_t* pt
                                       double* out_mix_mean /* q_off[S], or NULL */, double* out_mix_var /* q_off[S], or NULL */,
                                       double* out_logpdf /* P, or NULL */, int32_t* out_info /* P */);
 
+/* HELD-OUT SCORES of many short series in one call: predict_proba (src/api.jl:686-699) for callers that hold one model per short
+ * series — the log-density of every series' held-out values y_pred under each of its particles' posterior predictives, and (with
+ * weights) under every series' own mixture.  The resident-series twin is agp_predict_logpdf_batch, and the route is that entry's: one
+ * workgroup per particle factors the JOINT matrix [K11 + noise I, K12; K21, K22 + noise_pred I] of the series' n_s training points
+ * followed by its m_s query points — a short series of N = n_s + m_s <= AGP_SERIES_MAX_N points, in agp_logpdf_series_batch's kernel
+ * body and LDS map at N points — and reads the query rows' partials: with L the joint factor and z = L^-1 [xs; y_pred],
+ *   out_logpdf[p] = -(m log 2pi + 2 sum_{k >= n} log L_kk + sum_{k >= n} z_k^2) / 2 + m log|y_slope[s]|.
+ * Arguments S .. noise_pred as agp_predict_series_batch (series s is scored at ts_pred[q_off[s] .. q_off[s+1]); query times may
+ * repeat and may coincide with training times; noise_pred NULL: each particle's noise).  y_pred: q_off[S] values ALREADY in the
+ * transformed space, as xs is.  y_slope (S, or NULL: 1) enters through the Jacobian term alone: the result is the log-density of the
+ * RAW values (y_pred - intercept) / slope.
+ * out_terms (out_off[P] doubles, or NULL), particle-major behind out_off as in agp_predict_series_batch (out_off: P + 1, or NULL):
+ *   out_terms[out_off[p] + j] = -(log 2pi + z_{n+j}^2) / 2 - log L_{n+j,n+j} + log|y_slope[s]|, the log-density of held-out point j
+ *   given the training data and the held-out points before it in the caller's order (the prequential score); they sum to out_logpdf[p].
+ * out_info[p] (agp_predict_logpdf_batch's convention): 0, or the first bad pivot of the joint factor — 1 .. n_s when K11 fails,
+ *   n_s + k when leading minor k of the predictive covariance fails; NaN is then in out_logpdf[p] and in the particle's whole block of
+ *   out_terms, and no other particle is affected.  An empty training series gives the prior predictive's density.  A particle whose
+ *   series has nothing held out (m_s == 0) is not launched: logpdf 0, info 0.
+ * Mixtures (weights: P values, particle p's weight inside ITS series' mixture; NULL: none, and out_series_logp must then be NULL too):
+ *   out_series_logp[s] = M + log sum_{w_p > 0} w_p exp(out_logpdf[p] - M), M = max_{w_p > 0} out_logpdf[p], over the particles p with
+ *   series[p] == s in ascending p (they need not be adjacent) — the log of predict_mvn's mixture density at the held-out vector, raw
+ *   space — formed on the device behind the kernels, one thread per series.  If ANY particle of a series has info != 0, whatever
+ *   its weight, that series' value is NaN and every other series' is untouched; a series with particles and m_s == 0 gives exactly
+ *   0.0; a series without particles gives NaN and is no error (agp_predict_quantile_series_batch's rule).
+ * Stateless and re-entrant exactly as agp_predict_series_batch: one upload, one synchronisation.  A particle's result bits depend
+ *   only on its own series, queries, held-out values, program, parameters, noises and slope; a series' mixture bits only on its own
+ *   particles (in their order) and weights.  With profiling on, agp_get_timing's out[0] = out[2] = the fused kernels and out[4] = the
+ *   mixture read-out.
+ * The WHOLE call is rejected, and nothing is written to any output, with everything agp_predict_series_batch reports, and with
+ *   AGP_ERR_ARG (each message names the series): a series with m_s > 0 and n_s + m_s > AGP_SERIES_MAX_N (both counts are given); a
+ *     NULL y_pred when q_off[S] > 0; a held-out value that is not finite; a y_slope that is 0 or not finite; the weights of one series
+ *     not finite, negative or not summing to 1 (rtol sqrt(eps)); weights / out_series_logp not both NULL or both given;
+ *   AGP_ERR_PROGRAM (names the particle): a particle whose LDS need at N = n_s + m_s points exceeds 160 KiB — at N = AGP_SERIES_MAX_N
+ *     a chain of 10 ChangePoint nodes fits and one of 11 does not, as in agp_logpdf_series_batch at that length.
+ * Not here: the m x m predictive covariance, mean functions, n_s + m_s > AGP_SERIES_MAX_N, deduplication inside a call. */
+int agp_predict_logpdf_series_batch(agp_ctx* ctx, int32_t S, const int64_t* pt_off /* S+1 */, const double* ts, const double* xs,
+                                    const int64_t* q_off /* S+1 */, const double* ts_pred, const double* y_pred /* q_off[S] */,
+                                    int32_t P, const int32_t* series /* P */,
+                                    const int32_t* op_off, const uint8_t* ops, const int32_t* prm_off, const double* prm,
+                                    const double* noise /* P */, const double* noise_pred /* P or NULL = noise */,
+                                    const double* y_slope /* S, or NULL: 1 */, const double* weights /* P, or NULL */,
+                                    double* out_logpdf /* P */, double* out_terms /* out_off[P], or NULL */,
+                                    int64_t* out_off /* P+1, or NULL */, double* out_series_logp /* S; NULL iff weights is */,
+                                    int32_t* out_info /* P */);
+
 /* agp_logpdf_batch with BLOCK-EXTENSION of resident factors.  The data-annealing loop re-scores
  * every particle on a longer prefix of the same series with unchanged kernel parameters — the reweight step
  * (src/inference_smc_anneal_data.jl:206-217), add_data! (src/api.jl:426-443), scripts/online.jl:200 — and the
@@ -895,7 +940,8 @@ int agp_debug_compact_shards(agp_ctx* ctx, const double* padded, int32_t P, int3
  * finish_ms, n_update_launches, n_trsm_launches, h2d_d2h_ms } for the last batch call; a value+gradient sweep also
  * fills out[8..11] = { L^-T chain ms, K^-1 tiles ms, contraction ms, alpha + reductions ms }, agp_predict_sample_batch
  * out[12..13] = { normals ms, read-out ms }, agp_predict_mixture_batch out[14..15] = { pass ms, accumulation ms } (n_out up to 16).  The many-series entries fill
- * out[0] = out[2] = their fused kernels, and agp_predict_quantile_series_batch out[4] = its three read-out kernels. */
+ * out[0] = out[2] = their fused kernels, and agp_predict_quantile_series_batch out[4] = its three read-out kernels,
+ * agp_predict_logpdf_series_batch out[4] = its mixture read-out. */
 int agp_set_profiling(agp_ctx* ctx, int enabled);
 int agp_get_timing(agp_ctx* ctx, double* out, int32_t n_out);
 /* per-launch durations (ms) of the last profiled batch call: which = 0 update kernel, 1 trsm kernel;
