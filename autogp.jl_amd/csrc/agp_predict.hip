@@ -1,4 +1,5 @@
 // Host side of the C ABI, unit 2: predictive entries (src/GP.jl:731-758, 904-993), matrix assembly and the probe entries.
+// The dense predictive pass (predict_core, predict_logpdf_core) is written as stages over one JointPlan: see the list above split_queries.
 #include "agp_host.hpp"
 #include "agp_ndtri.hpp"
 #ifdef AGP_EXPERIMENTS
@@ -15,11 +16,6 @@ static void launch_variant(hipStream_t st, int grid, const CholArgs& ca) {
 #endif
 namespace {
 
-// Core of the predictive path (src/GP.jl:739-757) for a compiled batch.  `pred_code` / `diag_add`
-// (both per prediction point, nullable) are what infer_gp_sum adds: component codes of the query
-// points and an extra diagonal term.  `keys` (nullable; per particle, caller order) are the factor-store keys of the
-// particles: one whose factor of exactly this prefix is resident (an extension sweep scored it: the per-step callback of
-// the streaming workload, scripts/online.jl:43, predicts right after the reweight) skips K11 and its factorisation.
 // Query points on the series' own lattice.  In every use of the reference the query set is `train + test + future` at the
 // data's cadence (scripts/online.jl:41-43: ds_query = vcat(model.ds, ds_next, ds_test); src/GP.jl:743 evaluates the kernel on
 // [ts; ts_pred]): on a regular grid every joint point then has an integer RANK round((t - t_0) / h) — duplicates of training
@@ -64,7 +60,16 @@ void predict_lattice(agp_ctx* c, int64_t n, const double* ts_pred, int64_t m, Pr
   pl.on = true;
 }
 
-// Query points that are training points (see predict_core): positions in ts_pred + training indices, and the other queries.
+// ---- the dense predictive pass, stage by stage --------------------------------------------------------------------------------------
+//   plan_joint        the joint matrix, planned once per call: which queries it keeps (split_queries), its points, its tile geometry
+//   ResidentFactors   store lookup, the store's lock, the resident Z = L^-T of the training-point route
+//   size_buffers, stage_joint, stage_modes, flush_uploads          buffer sizes and the one flush of every upload
+//   per chunk: landing_zone, chunk_setup + launch_cov (tiles), the factorisation, z_chain, launch_schur, extract_chunk,
+//              sum_readout_chunk / mix_chunk, the copy-back, scatter_chunk
+//   finish_info       the info pass after the last chunk
+// predict_core lists them top to bottom; predict_logpdf_core shares the plan, stage_joint, flush_uploads and chunk_setup.
+
+// Query points that are training points (see JointPlan): positions in ts_pred + training indices, and the other queries.
 // Empty lists when the shortcut does not apply or would not pay.
 void split_queries(agp_ctx* c, int64_t n, const double* ts_pred, int64_t m, bool eligible,
                    std::vector<int32_t>& dq, std::vector<int32_t>& di, std::vector<int32_t>& fq) {
@@ -83,22 +88,80 @@ void split_queries(agp_ctx* c, int64_t n, const double* ts_pred, int64_t m, bool
   if ((int64_t)dq.size() * 3 < n || (int64_t)dq.size() < NB) { dq.clear(); di.clear(); fq.clear(); }
 }
 
+// The joint matrix [K11 + noise I, K12; K21, K22] of a dense pass, planned ONCE per call: the entry makes the plan before it compiles
+// the batch (use_flow and the compile options see the nt, nt1 that will run) and hands the same plan to the pass.
+// ---- query points that ARE training points, no covariance requested, no codes (diag_path) ------------------------------------------
+// For t*_j == t_i the cross-covariance row is K21[j,:] = K11[i,:] - noise e_i^T (src/GP.jl:743-747 evaluates the kernel
+// on the joint list; the noise sits on K11's diagonal only), so with alpha = K11^-1 (y - mu1):
+//     mean*_j = mu2_j + (y - mu1)_i - noise alpha_i,      var*_j = noise - noise^2 (K11^-1)_ii + noise_pred,
+// and (K11^-1)_ii = sum_c Z(i,c)^2 with Z = L^-T: k_trtri_chain forms Z and alpha in n^3/3 flops per particle where the
+// joint path spends n^2 flops PER SUCH POINT on V = L^-1 K12 (the reference's query set is train + test + future,
+// scripts/online.jl:41-43: n of its points are of this kind).  The other query points (fq) stay in the joint matrix.
+struct JointPlan {
+  PredQuery q = {};                        // the caller's query
+  bool want_cov = false, has_codes = false;
+  const PredLattice* pl = nullptr;         // the query's lattice (null or off: the general evaluators)
+  std::vector<int32_t> dq, di, fq;         // duplicates: position in ts_pred, training index; the remaining queries
+  bool diag_path = false;                  // the split is taken
+  int64_t mJ = 0;                          // query points of the joint matrix
+  const double* tsJ = nullptr; const double* meanJ = nullptr; const double* daddJ = nullptr;      // per joint query point (nullable as given)
+  int n1_pad = 0, m_pad = 0, nt1 = 0, nt2 = 0, nt = 0, ntot = 0, ntiles = 0;      // (n1_pad: 0 when n == 0)
+  long long strideA = 0, strideZ = 0;      // per particle: the joint tiles; Z = L11^-T (training tiles only, diag_path)
+  std::vector<double> tsF, meanF, daddF;   // (the filtered lists tsJ / meanJ / daddJ point into)
+  std::vector<int32_t> rankF;              // (the joint layout keeps the ranks of the queries that are not training points only)
+  JointPlan() = default;
+  JointPlan(const JointPlan&) = delete; JointPlan& operator=(const JointPlan&) = delete;
+  bool lagr() const { return pl != nullptr && pl->on; }
+  const std::vector<int32_t>& rank() const { return diag_path ? rankF : pl->rank; }      // lattice ranks, padded joint layout (lagr() only)
+  int chunk(agp_ctx* c, int P) const { return (int)std::max<int64_t>(1, std::min<int64_t>(P, ws_limit_bytes(c) / ((strideA + strideZ) * 8))); }
+};
+
+// `diag_add` (nullable, per query point) is filtered with the split; a pass that forms whole covariances (want_cov) or has coded
+// query points never splits.
+void plan_joint(agp_ctx* c, const PredQuery& q, bool want_cov, bool has_codes, const double* diag_add, const PredLattice* pl, JointPlan& jp) {
+  const int64_t n = q.n, m = q.m;
+  jp.q = q; jp.want_cov = want_cov; jp.has_codes = has_codes; jp.pl = pl;
+  split_queries(c, n, q.ts_pred, m, !want_cov && !has_codes && !c->ref_arith, jp.dq, jp.di, jp.fq);
+  jp.diag_path = !jp.dq.empty();
+  const int64_t mJ = jp.mJ = jp.diag_path ? (int64_t)jp.fq.size() : m;
+  jp.tsJ = q.ts_pred; jp.meanJ = q.mean_pred; jp.daddJ = diag_add;
+  if (jp.diag_path) {
+    const std::vector<int32_t>& fq = jp.fq;
+    auto keep = [&](const double* v, std::vector<double>& f) { f.resize((size_t)mJ); for (int64_t g = 0; g < mJ; ++g) f[(size_t)g] = v[fq[(size_t)g]]; return f.data(); };
+    jp.tsJ = keep(q.ts_pred, jp.tsF);
+    if (q.mean_pred) jp.meanJ = keep(q.mean_pred, jp.meanF);
+    if (diag_add) jp.daddJ = keep(diag_add, jp.daddF);
+  }
+  jp.n1_pad = round_up(n, NB); jp.m_pad = round_up(mJ, NB);
+  jp.nt1 = jp.n1_pad / NB; jp.nt2 = jp.m_pad / NB; jp.nt = jp.nt1 + jp.nt2;
+  jp.ntot = jp.n1_pad + jp.m_pad;
+  jp.ntiles = jp.nt * (jp.nt + 1) / 2;
+  jp.strideA = (long long)jp.ntiles * NB2;
+  jp.strideZ = jp.diag_path ? (long long)(jp.nt1 * (jp.nt1 + 1) / 2) * NB2 : 0;
+  if (jp.diag_path && jp.lagr()) {
+    jp.rankF.assign((size_t)jp.ntot, 0);
+    std::copy(pl->rank.begin(), pl->rank.begin() + jp.n1_pad, jp.rankF.begin());
+    for (int64_t g = 0; g < mJ; ++g) jp.rankF[(size_t)jp.n1_pad + g] = pl->rank[(size_t)jp.n1_pad + jp.fq[(size_t)g]];
+  }
+}
+
+struct SortedNoise { std::vector<double> noise, pred; };      // per sorted position (noise_pred defaults to noise)
+
 // What predict_core and predict_logpdf_core stage alike for a compiled batch: the joint point list [ts(1:n), pad, tsJ(1:mJ), pad], the
-// programs, the noises in sorted order (noise_pred defaults to noise), the means of the training and of the query points; and the
-// buffers both size alike for chunks of `chunk` particles.
-int stage_joint(agp_ctx* c, Slot* s, PinnedUploads& up, const PredQuery& qJ, const Particles& pp, int chunk, const Batch& bt,
-                std::vector<double>& noise_sorted, std::vector<double>& npred) {
-  const int64_t n = qJ.n, mJ = qJ.m;
+// programs, the noises in sorted order, the means of the training and of the query points; and the buffers both size alike for
+// chunks of `chunk` particles.
+int stage_joint(agp_ctx* c, Slot* s, PinnedUploads& up, const JointPlan& jp, const Particles& pp, const Batch& bt, int chunk, SortedNoise& nz) {
+  const int64_t n = jp.q.n, mJ = jp.mJ;
   const int P = pp.P;
-  const int n1_pad = round_up(n, NB), ntot = n1_pad + round_up(mJ, NB), nt = ntot / NB;
+  const int ntot = jp.ntot, nt = jp.nt;
   std::vector<double> tt((size_t)ntot, 0.0);
   std::copy(c->h_ts.begin(), c->h_ts.begin() + n, tt.begin());
-  std::copy(qJ.ts_pred, qJ.ts_pred + mJ, tt.begin() + n1_pad);
-  noise_sorted.resize((size_t)P); npred.resize((size_t)P);
+  std::copy(jp.tsJ, jp.tsJ + mJ, tt.begin() + jp.n1_pad);
+  nz.noise.resize((size_t)P); nz.pred.resize((size_t)P);
   for (int q = 0; q < P; ++q) {
     const int p = bt.order[q];
-    noise_sorted[q] = pp.noise[p];
-    npred[q] = pp.noise_pred ? pp.noise_pred[p] : pp.noise[p];
+    nz.noise[q] = pp.noise[p];
+    nz.pred[q] = pp.noise_pred ? pp.noise_pred[p] : pp.noise[p];
   }
   HIPCHK(c, s->vec.ensure(sizeof(double) * (size_t)ntot * chunk));
   HIPCHK(c, s->partial.ensure(sizeof(double) * 2 * (size_t)nt * chunk));
@@ -110,27 +173,32 @@ int stage_joint(agp_ctx* c, Slot* s, PinnedUploads& up, const PredQuery& qJ, con
   HIPCHK(c, s->noise.ensure(sizeof(double) * (size_t)P));
   HIPCHK(c, s->noise_pred.ensure(sizeof(double) * (size_t)P));
   HIPCHK(c, s->tt.ensure(sizeof(double) * (size_t)ntot));
-  if (qJ.mean_train && n > 0) {
+  if (jp.q.mean_train && n > 0) {
     HIPCHK(c, s->mu1.ensure(sizeof(double) * (size_t)n));
-    up.add(s->mu1.p, qJ.mean_train, sizeof(double) * n);
+    up.add(s->mu1.p, jp.q.mean_train, sizeof(double) * n);
   }
-  if (qJ.mean_pred && mJ > 0) {
+  if (jp.meanJ && mJ > 0) {
     HIPCHK(c, s->mu2.ensure(sizeof(double) * (size_t)mJ));
-    up.add(s->mu2.p, qJ.mean_pred, sizeof(double) * mJ);
+    up.add(s->mu2.p, jp.meanJ, sizeof(double) * mJ);
   }
   up.add(s->hdr.p, bt.hdr.data(), sizeof(ProgHdr) * P);
   up.add(s->ops.p, bt.ops.data(), bt.ops.size());
   up.add(s->prm.p, bt.prm.data(), sizeof(double) * bt.prm.size());
-  up.add(s->noise.p, noise_sorted.data(), sizeof(double) * P);
-  up.add(s->noise_pred.p, npred.data(), sizeof(double) * P);
+  up.add(s->noise.p, nz.noise.data(), sizeof(double) * P);
+  up.add(s->noise_pred.p, nz.pred.data(), sizeof(double) * P);
   up.add(s->tt.p, tt.data(), sizeof(double) * ntot);
   return AGP_OK;
 }
 
-// Query points on the lattice: `up` goes out with the ranks of the joint points (padded joint layout), the lag times and the table
-// programs; then one rank table of R lags per stationary subtree of the batch.
-int flush_lattice(agp_ctx* c, Slot* s, hipStream_t st, PinnedUploads& up, const Batch& bt, const PredLattice& pl,
-                  const std::vector<int32_t>& rank) {
+// The one flush of a pass's uploads.  Query points on the lattice: `up` goes out with the ranks of the joint points (padded joint
+// layout), the lag times and the table programs; then one rank table of R lags per stationary subtree of the batch.
+int flush_uploads(agp_ctx* c, Slot* s, hipStream_t st, PinnedUploads& up, const Batch& bt, const JointPlan& jp) {
+  if (!jp.lagr()) {
+    HIPCHK(c, up.flush(s->h_stage, s->up_blob, st));
+    return AGP_OK;
+  }
+  const PredLattice& pl = *jp.pl;
+  const std::vector<int32_t>& rank = jp.rank();
   const LagProgLayout lpl(bt);
   HIPCHK(c, lpl.upload(up, s->pl_prog));
   HIPCHK(c, s->pl_rank.ensure(sizeof(int32_t) * rank.size()));
@@ -150,6 +218,31 @@ int flush_lattice(agp_ctx* c, Slot* s, hipStream_t st, PinnedUploads& up, const 
   std::lock_guard<std::mutex> g(c->mu);
   ++c->n_lag_pred;
   return AGP_OK;
+}
+
+// CovArgs / CholArgs of sorted positions [p0, p0 + Pc) of a pass over the plan's joint matrix, and the chunk's share of fused
+// particles (nf of them, evaluator depth dcov).  What differs between the passes is left to the caller, on cv and ca alike where both
+// have the field: code, noise_q, i0; cv.skip_pred_offdiag; ca.nt1 (here: the training block), ca.wsteps.
+struct JointChunk { CovArgs cv; CholArgs ca; int nf, dcov; };
+JointChunk chunk_setup(Slot* s, const JointPlan& jp, const Batch& bt, int p0, int Pc) {
+  JointChunk k = {};
+  CovArgs& cv = k.cv;
+  cv.tt = s->tt.as<double>(); cv.n1 = (int)jp.q.n; cv.n1_pad = jp.n1_pad; cv.m2 = (int)jp.mJ; cv.nt = jp.nt;
+  cv.hdr = s->hdr.as<ProgHdr>() + p0; cv.ops = s->ops.as<uint8_t>(); cv.prm = s->prm.as<double>();
+  cv.noise = s->noise.as<double>() + p0; cv.A = s->A.as<double>(); cv.strideA = jp.strideA; cv.P = Pc;
+  if (jp.lagr()) { cv.lagtab = s->lagtab.as<double>(); cv.lagr = s->pl_rank.as<int32_t>(); cv.lag_stride = jp.pl->rank_units * 256; }
+  k.nf = std::max(0, std::min(Pc, bt.n_fused - p0));
+  k.dcov = k.nf > 0 ? bt.max_depth_fused : 0;
+  cv.p_off = k.nf;
+  CholArgs& ca = k.ca;
+  ca.A = s->A.as<double>(); ca.strideA = jp.strideA; ca.W = s->W.as<double>();
+  ca.vec = s->vec.as<double>(); ca.ldv = jp.ntot; ca.partial = s->partial.as<double>();
+  ca.info = s->info.as<int>() + p0; ca.P = Pc; ca.nt = jp.nt; ca.k = 0; ca.nt1 = jp.nt1;
+  set_cov(ca, cv);
+  ca.lag = jp.lagr() ? 1 : 0;
+  ca.n_fused = k.nf;
+  ca.ready = s->ready.as<int>() + p0;
+  return k;
 }
 
 // The dataflow schedule over the joint matrix of ca.P particles: block columns [0, wsteps) factored, every row of them (tile rows below
@@ -173,7 +266,7 @@ int launch_joint_flow(agp_ctx* c, Slot* s, hipStream_t st, CholArgs& ca, int dco
 // What the batched sum-of-GPs entries (agp_infer_gp_sum_batch, agp_predict_sum_batch) ask of predict_core on top of pred_code /
 // diag_add: each particle's noise_pred on the observable (code 0) query rows only, the dataflow schedule whatever the batch
 // (AGP_FLOW=0: the per-column launches) — a particle's bits then do not depend on the batch, its order, copies or chunking — and,
-// for predict_sum, the device read-out k_sum_readout: out_mean receives raw means, out_var is not written, out_x [P][m][nq] the
+// for predict_sum, the device read-out k_sum_readout: out.mean receives raw means, out.var is not written, out_x [P][m][nq] the
 // marginal quantiles, and a particle whose raw marginals fail at row j (0-based) gets info n + j + 1.
 struct SumPass {
   bool readout = false;
@@ -181,359 +274,407 @@ struct SumPass {
   double slope = 1.0, intercept = 0.0;
   std::vector<double> z;                 // ndtri(q)
   double* out_x = nullptr;
+  int nq() const { return readout ? (int)z.size() : 0; }
 };
 
-int predict_core(agp_ctx* c, const PredQuery& q, const Particles& pp, Batch& bt, const uint8_t* pred_code, const double* diag_add,
-                 double* out_mean, double* out_var, double* out_cov, int32_t* out_info, const std::vector<std::string>* keys = nullptr,
-                 const PredLattice* pl = nullptr, const SumPass* sum = nullptr, MixPass* mix = nullptr) {
-  // (bt: pp's programs, compiled)
-  const int64_t n = q.n, m = q.m;
-  const int P = pp.P;
-  const double* ts_pred = q.ts_pred; const double* mean_train = q.mean_train; const double* mean_pred = q.mean_pred;
-  const int n1_pad = round_up(n, NB);           // 0 when n == 0
-  const bool lagr = pl != nullptr && pl->on;
-  // `mix` (nullable; agp_predict_mixture_batch): the chunk's device means and covariances go into the mixture's running sums
-  // (mix_chunk) instead of out_cov — the pass forms every particle's covariance (want_cov) and copies none of them out
-  const bool want_cov = out_cov != nullptr || (mix && mix->cov);
-  // ---- query points that ARE training points, no covariance requested ----------------------------------------------
-  // For t*_j == t_i the cross-covariance row is K21[j,:] = K11[i,:] - noise e_i^T (src/GP.jl:743-747 evaluates the kernel
-  // on the joint list; the noise sits on K11's diagonal only), so with alpha = K11^-1 (y - mu1):
-  //     mean*_j = mu2_j + (y - mu1)_i - noise alpha_i,      var*_j = noise - noise^2 (K11^-1)_ii + noise_pred,
-  // and (K11^-1)_ii = sum_c Z(i,c)^2 with Z = L^-T: k_trtri_chain forms Z and alpha in n^3/3 flops per particle where the
-  // joint path spends n^2 flops PER SUCH POINT on V = L^-1 K12 (the reference's query set is train + test + future,
-  // scripts/online.jl:41-43: n of its points are of this kind).  The other query points take the joint path below.
-  std::vector<int32_t> dq, di, fq;      // duplicates: position in ts_pred, training index; the remaining queries
-  split_queries(c, n, ts_pred, m, !want_cov && !pred_code && !c->ref_arith, dq, di, fq);
-  const bool diag_path = !dq.empty();
-  const int64_t mJ = diag_path ? (int64_t)fq.size() : m;      // query points of the joint matrix
-  std::vector<double> tsF, meanF, daddF;
-  const double* tsJ = ts_pred; const double* meanJ = mean_pred; const double* daddJ = diag_add;
-  if (diag_path) {
-    tsF.resize((size_t)mJ);
-    for (int64_t g = 0; g < mJ; ++g) tsF[(size_t)g] = ts_pred[fq[(size_t)g]];
-    tsJ = tsF.data();
-    if (mean_pred) { meanF.resize((size_t)mJ); for (int64_t g = 0; g < mJ; ++g) meanF[(size_t)g] = mean_pred[fq[(size_t)g]]; meanJ = meanF.data(); }
-    if (diag_add) { daddF.resize((size_t)mJ); for (int64_t g = 0; g < mJ; ++g) daddF[(size_t)g] = diag_add[fq[(size_t)g]]; daddJ = daddF.data(); }
-  }
-  const int m_pad = round_up(mJ, NB);
-  const int nt1 = n1_pad / NB, nt2 = m_pad / NB, nt = nt1 + nt2;
-  // resident factors (sorted order): store slot per particle, first tile row to compute
-  std::vector<int32_t> src_slot, i0v;
-  int n_hit = 0;
-  std::unique_lock<std::mutex> store_lk;
-  if (keys && c->predict_reuse && nt1 > 0 && !mean_train && !pred_code) {
-    n_hit = store_lookup(c, *keys, bt.order, P, n, nt1, src_slot, i0v, store_lk);
+// What a pass is asked to do on top of the plain joint pass (all optional), and where its results go (per particle of the pass, its
+// caller's order).
+//   pred_code / diag_add   (per prediction point) what infer_gp_sum adds: component codes of the query points, an extra diagonal term
+//   keys                   (per particle) the factor-store keys: a particle whose factor of exactly this prefix is resident (an extension
+//                          sweep scored it: the per-step callback of the streaming workload, scripts/online.jl:43, predicts right
+//                          after the reweight) skips K11 and its factorisation
+//   mix                    (agp_predict_mixture_batch) the chunk's device means and covariances go into the mixture's running sums
+//                          (mix_chunk) instead of the outputs: the pass forms every particle's covariance and copies none of them out
+struct PassAsk {
+  const uint8_t* pred_code = nullptr;
+  const double* diag_add = nullptr;
+  const std::vector<std::string>* keys = nullptr;
+  const SumPass* sum = nullptr;
+  MixPass* mix = nullptr;
+};
+struct PassOut { double* mean = nullptr; double* var = nullptr; double* cov = nullptr; int32_t* info = nullptr; };
+
+// The resident factors a pass starts from (sorted order): store slot per particle, first tile row to compute, and the store's lock
+// from the lookup on.
+// Resident L^-T: a pass that starts from resident factors AND serves observed points from alpha / diag(K11^-1) keeps Z = L^-T in
+// the store beside L (same layout) with the rows' running sums — the next pass on a longer prefix (the per-step callback of a
+// stream, scripts/online.jl:43) forms the new tile columns of Z only: nt^2/2 tile products instead of nt^3/6.
+// Two invariants, kept by the structure:
+//   * the chain kernel advances the slots' running sums on the device; their column counts (zrows) are committed on the host only
+//     after the LAST chunk's stream has drained (after_chain).  Any return in between must not leave sums that already include
+//     columns the host does not know of: from the first chain launch to the commit the object is armed, and an armed object zeroes
+//     the touched entries' zrows when it goes;
+//   * that happens under the store's lock: the lock is a member, so the destructor's body runs before the lock is released.
+// Lock order: the store's mutex (lookup) before the workspace slot and before c->mu.  The lock goes once the last copy out of the
+// store has been made (after_gather), or with resident Z once its new columns are in (after_chain).
+struct ResidentFactors {
+  agp_ctx* c;
+  std::unique_lock<std::mutex> lk;
+  int P = 0, n_hit = 0;
+  int64_t n = 0;
+  std::vector<int32_t> src_slot, i0v, zi0v;
+  bool z = false, armed = false;
+  const int32_t* d_src = nullptr; const int32_t* d_i0 = nullptr; const int32_t* d_zi0 = nullptr;
+  explicit ResidentFactors(agp_ctx* c_) : c(c_) {}
+  ~ResidentFactors() { if (armed) for (int32_t sl : src_slot) if (sl >= 0 && (size_t)sl < c->store.zrows.size()) c->store.zrows[(size_t)sl] = 0; }
+  ResidentFactors(const ResidentFactors&) = delete; ResidentFactors& operator=(const ResidentFactors&) = delete;
+
+  void lookup(const std::vector<std::string>& keys, const Batch& bt, int P_, const JointPlan& jp) {
+    P = P_; n = jp.q.n;
+    n_hit = store_lookup(c, keys, bt.order, P, n, jp.nt1, src_slot, i0v, lk);
     std::lock_guard<std::mutex> g(c->mu);
     c->pred_reused += n_hit; c->pred_factored += P - n_hit;
   }
-
-  SlotGuard sg(c);
-  Slot* s = sg.s;
-  if (!s->stream) HIPCHK(c, hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
-  hipStream_t st = s->stream;
-
-  const int ntot = n1_pad + m_pad;
-  const int ntiles = nt * (nt + 1) / 2;
-  const long long strideA = (long long)ntiles * NB2;
-  const long long strideZ = diag_path ? (long long)(nt1 * (nt1 + 1) / 2) * NB2 : 0;      // Z = L11^-T (training tiles only)
-  const int64_t bytes_pp = (strideA + strideZ) * 8;
-  const int chunk = (int)std::max<int64_t>(1, std::min<int64_t>(P, ws_limit_bytes(c) / bytes_pp));
-
-  HIPCHK(c, s->A.ensure((size_t)strideA * 8 * chunk));
-  if (diag_path) {
-    HIPCHK(c, s->Z.ensure((size_t)strideZ * 8 * chunk));
-    HIPCHK(c, s->alpha.ensure(sizeof(double) * (size_t)ntot * chunk));
-    HIPCHK(c, s->gpart.ensure(sizeof(double) * (size_t)ntot * chunk));      // diag(K11^-1) (the gradient path's scratch, idle here)
-  }
-  HIPCHK(c, s->W.ensure(sizeof(double) * NSB * 256 * (size_t)chunk * std::max(1, nt1)));     // (the dataflow schedule keeps every column's inverse blocks)
-  HIPCHK(c, s->pred_mean.ensure(sizeof(double) * (size_t)std::max<int64_t>(1, mJ) * chunk));
-  HIPCHK(c, s->pred_var.ensure(sizeof(double) * (size_t)std::max<int64_t>(1, mJ) * chunk));
-  if (want_cov) HIPCHK(c, s->pred_cov.ensure(sizeof(double) * (size_t)m * m * chunk));
-  const bool ro = sum && sum->readout;
-  const int nq = ro ? (int)sum->z.size() : 0;
-  if (ro) {
-    HIPCHK(c, s->sum_x.ensure(sizeof(double) * (size_t)std::max<int64_t>(1, mJ) * std::max(1, nq) * chunk));
-    HIPCHK(c, s->sum_z.ensure(sizeof(double) * (size_t)std::max(1, nq)));
-    HIPCHK(c, s->out_info.ensure(sizeof(int32_t) * (size_t)P));
-  }
-  PinnedUploads up;
-  std::vector<double> noise_sorted, npred;
-  if (const int rc = stage_joint(c, s, up, {n, tsJ, mJ, mean_train, meanJ}, pp, chunk, bt, noise_sorted, npred)) return rc;
-  if (pred_code) {
-    std::vector<uint8_t> code((size_t)ntot, 0);
-    std::copy(pred_code, pred_code + m, code.begin() + n1_pad);
-    HIPCHK(c, s->code.ensure((size_t)ntot));
-    up.add(s->code.p, code.data(), (size_t)ntot);
-  }
-  if (diag_add && mJ > 0) {
-    HIPCHK(c, s->diag_add.ensure(sizeof(double) * (size_t)mJ));
-    up.add(s->diag_add.p, daddJ, sizeof(double) * mJ);
-  }
-  if (nq > 0) up.add(s->sum_z.p, sum->z.data(), sizeof(double) * nq);
-  if (mix) {
-    std::vector<double> w_pass((size_t)P);
-    for (int q = 0; q < P; ++q) w_pass[(size_t)q] = mix->w[(size_t)bt.order[q]];
-    if (const int rc = mix_stage(c, s, st, up, *mix, m, w_pass)) return rc;
-  }
-
-  const int32_t* d_src = nullptr; const int32_t* d_i0 = nullptr;
-  // Resident L^-T: a pass that starts from resident factors AND serves observed points from alpha / diag(K11^-1) keeps Z = L^-T in
-  // the store beside L (same layout) with the rows' running sums — the next pass on a longer prefix (the per-step callback of a
-  // stream, scripts/online.jl:43) forms the new tile columns of Z only: nt^2/2 tile products instead of nt^3/6.
-  bool zstore = false;
-  // (declared after store_lk: runs first, while the store's lock is still held)
-  struct ZGuard {
-    agp_ctx* c; const std::vector<int32_t>* slots; bool armed = false;
-    ~ZGuard() { if (armed) for (int32_t sl : *slots) if (sl >= 0 && (size_t)sl < c->store.zrows.size()) c->store.zrows[(size_t)sl] = 0; }
-  } zguard{c, &src_slot};
-  std::vector<int32_t> zi0v;
-  const int32_t* d_zi0 = nullptr;
-  if (n_hit > 0 && diag_path) {
+  // the store's Z / zalpha / zdinv (a failed allocation: the pass forms Z in its own scratch), and where each particle's chain starts
+  void begin_z() {
     agp_ctx::FactorStore& fs = c->store;
     const size_t before = fs.Z.cap + fs.zalpha.cap + fs.zdinv.cap;
     const size_t rowb = sizeof(double) * (size_t)fs.nt_cap * NB * (size_t)fs.n_slots;
-    zstore = fs.Z.ensure((size_t)fs.strideA * 8 * (size_t)fs.n_slots) == hipSuccess && fs.zalpha.ensure(rowb) == hipSuccess &&
-             fs.zdinv.ensure(rowb) == hipSuccess;
-    if (!zstore) { (void)hipGetLastError(); fs.z_release(); }
+    z = fs.Z.ensure((size_t)fs.strideA * 8 * (size_t)fs.n_slots) == hipSuccess && fs.zalpha.ensure(rowb) == hipSuccess &&
+        fs.zdinv.ensure(rowb) == hipSuccess;
+    if (!z) { (void)hipGetLastError(); fs.z_release(); }
     const size_t after = fs.Z.cap + fs.zalpha.cap + fs.zdinv.cap;
     fs.footprint = fs.footprint.load() + after - std::min(before, after);
-    if (zstore) {
-      if (fs.zrows.size() != (size_t)fs.n_slots) fs.zrows.assign((size_t)fs.n_slots, 0);
-      // one particle per store entry extends the entry's Z; its copies (a resampled population) work in the sweep's scratch (-1)
-      zi0v.assign((size_t)P, 0);
-      std::vector<char> taken((size_t)fs.n_slots, 0);
-      for (int q = 0; q < P; ++q) {
-        const int sl = src_slot[(size_t)q];
-        if (sl < 0) continue;
-        zi0v[(size_t)q] = taken[(size_t)sl] ? -1 : fs.zrows[(size_t)sl];
-        taken[(size_t)sl] = 1;
-      }
+    if (!z) return;
+    if (fs.zrows.size() != (size_t)fs.n_slots) fs.zrows.assign((size_t)fs.n_slots, 0);
+    // one particle per store entry extends the entry's Z; its copies (a resampled population) work in the sweep's scratch (-1)
+    zi0v.assign((size_t)P, 0);
+    std::vector<char> taken((size_t)fs.n_slots, 0);
+    for (int q = 0; q < P; ++q) {
+      const int sl = src_slot[(size_t)q];
+      if (sl < 0) continue;
+      zi0v[(size_t)q] = taken[(size_t)sl] ? -1 : fs.zrows[(size_t)sl];
+      taken[(size_t)sl] = 1;
     }
   }
-  if (n_hit > 0) {
+  int stage(Slot* s, PinnedUploads& up) {
     HIPCHK(c, s->stage.ensure(sizeof(int32_t) * 3 * (size_t)P));
     int32_t* d = s->stage.as<int32_t>();
     up.add(d, src_slot.data(), sizeof(int32_t) * P);
     up.add(d + P, i0v.data(), sizeof(int32_t) * P);
-    if (zstore) { up.add(d + 2 * P, zi0v.data(), sizeof(int32_t) * P); d_zi0 = d + 2 * P; }
+    if (z) { up.add(d + 2 * P, zi0v.data(), sizeof(int32_t) * P); d_zi0 = d + 2 * P; }
     d_src = d; d_i0 = d + P;
+    return AGP_OK;
   }
-  if (!lagr) {
-    HIPCHK(c, up.flush(s->h_stage, s->up_blob, st));
-  } else {
-    // (the joint layout keeps the queries that are not training points only)
-    std::vector<int32_t> rankF;
-    if (diag_path) {
-      rankF.assign((size_t)ntot, 0);
-      std::copy(pl->rank.begin(), pl->rank.begin() + n1_pad, rankF.begin());
-      for (int64_t g = 0; g < mJ; ++g) rankF[(size_t)n1_pad + g] = pl->rank[(size_t)n1_pad + fq[(size_t)g]];
+  int after_gather(hipStream_t st, int p_end) {
+    if (z || p_end < P) return AGP_OK;
+    HIPCHK(c, hipStreamSynchronize(st));
+    lk.unlock();
+    return AGP_OK;
+  }
+  void point(GradArgs& ga, int p0) const {
+    if (!z) return;
+    agp_ctx::FactorStore& fs = c->store;
+    ga.lslot = d_src + p0; ga.Lsrc = fs.A.as<double>(); ga.Lstride = fs.strideA; ga.Wsrc = fs.W.as<double>(); ga.Wnt = fs.nt_cap;
+    ga.Zsrc = fs.Z.as<double>(); ga.Zstride = fs.strideA; ga.zi0 = d_zi0 + p0;
+    ga.zalpha = fs.zalpha.as<double>(); ga.zdinv = fs.zdinv.as<double>(); ga.zld = (long long)fs.nt_cap * NB;
+    ga.zfull = (int)(n / NB);
+  }
+  // Before each chain launch.  NaN-poison mode: what the chain forms again — tile columns >= zi0 of the entry's Z (column i of Z is
+  // packed row i) and the running sums of rows >= zi0 (rows below it start from theirs) — reads NaN until written.  Copies (zi0 < 0)
+  // are skipped.
+  int poison(hipStream_t st, int p0, int Pc) {
+    if (!z) return AGP_OK;
+    if (c->poison.active()) {
+      agp_ctx::FactorStore& fs = c->store;
+      PoisonRowsArgs pa = {};
+      double* bases[3] = {fs.Z.as<double>(), fs.zalpha.as<double>(), fs.zdinv.as<double>()};
+      const long long pitch[3] = {fs.strideA, (long long)fs.nt_cap * NB, (long long)fs.nt_cap * NB};
+      const long long unit[3] = {NB2, NB, NB};
+      for (int b = 0; b < 3; ++b) { pa.base[b] = bases[b]; pa.pitch[b] = pitch[b]; pa.unit[b] = unit[b]; pa.tri[b] = b == 0; }
+      pa.nt_cap = fs.nt_cap; pa.slot = d_src + p0; pa.i0 = d_zi0 + p0;
+      launch_poison_rows(st, 256, Pc, 3, pa);
+      HIPCHK(c, hipGetLastError());
+      for (int q = p0; q < p0 + Pc; ++q) {
+        if (src_slot[(size_t)q] < 0 || zi0v[(size_t)q] < 0) continue;
+        const long long r0 = std::min<long long>(zi0v[(size_t)q], fs.nt_cap);
+        c->poison.count(sizeof(double) * (size_t)((fs.strideA - r0 * (r0 + 1) / 2 * NB2) + 2 * (fs.nt_cap - r0) * NB));
+      }
     }
-    if (const int rc = flush_lattice(c, s, st, up, bt, *pl, diag_path ? rankF : pl->rank)) return rc;
+    armed = true;
+    return AGP_OK;
   }
+  int after_chain(hipStream_t st, int p_end) {
+    if (!z || p_end < P) return AGP_OK;
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(st));
+    // (complete tile columns only: the column of a partly filled last tile is formed again on a longer prefix)
+    for (int q = 0; q < P; ++q) if (src_slot[(size_t)q] >= 0) c->store.zrows[(size_t)src_slot[(size_t)q]] = (int32_t)(n / NB);
+    armed = false;
+    lk.unlock();
+    return AGP_OK;
+  }
+};
+
+int size_buffers(agp_ctx* c, Slot* s, const JointPlan& jp, const SumPass* sum, int P, int chunk) {
+  const int64_t m = jp.q.m, m1 = std::max<int64_t>(1, jp.mJ);
+  HIPCHK(c, s->A.ensure((size_t)jp.strideA * 8 * chunk));
+  if (jp.diag_path) {
+    HIPCHK(c, s->Z.ensure((size_t)jp.strideZ * 8 * chunk));
+    HIPCHK(c, s->alpha.ensure(sizeof(double) * (size_t)jp.ntot * chunk));
+    HIPCHK(c, s->gpart.ensure(sizeof(double) * (size_t)jp.ntot * chunk));      // diag(K11^-1) (the gradient path's scratch, idle here)
+  }
+  HIPCHK(c, s->W.ensure(sizeof(double) * NSB * 256 * (size_t)chunk * std::max(1, jp.nt1)));     // (the dataflow schedule keeps every column's inverse blocks)
+  HIPCHK(c, s->pred_mean.ensure(sizeof(double) * (size_t)m1 * chunk));
+  HIPCHK(c, s->pred_var.ensure(sizeof(double) * (size_t)m1 * chunk));
+  if (jp.want_cov) HIPCHK(c, s->pred_cov.ensure(sizeof(double) * (size_t)m * m * chunk));
+  if (sum && sum->readout) {
+    HIPCHK(c, s->sum_x.ensure(sizeof(double) * (size_t)m1 * std::max(1, sum->nq()) * chunk));
+    HIPCHK(c, s->sum_z.ensure(sizeof(double) * (size_t)std::max(1, sum->nq())));
+    HIPCHK(c, s->out_info.ensure(sizeof(int32_t) * (size_t)P));
+  }
+  return AGP_OK;
+}
+
+// the uploads of the optional modes: codes (padded joint layout), the extra diagonal, the read-out's quantiles, the mixture's weights
+int stage_modes(agp_ctx* c, Slot* s, hipStream_t st, PinnedUploads& up, const JointPlan& jp, const PassAsk& ask, const Batch& bt) {
+  const int64_t m = jp.q.m, mJ = jp.mJ;
+  if (ask.pred_code) {
+    std::vector<uint8_t> code((size_t)jp.ntot, 0);
+    std::copy(ask.pred_code, ask.pred_code + m, code.begin() + jp.n1_pad);
+    HIPCHK(c, s->code.ensure((size_t)jp.ntot));
+    up.add(s->code.p, code.data(), (size_t)jp.ntot);
+  }
+  if (ask.diag_add && mJ > 0) {
+    HIPCHK(c, s->diag_add.ensure(sizeof(double) * (size_t)mJ));
+    up.add(s->diag_add.p, jp.daddJ, sizeof(double) * mJ);
+  }
+  if (ask.sum && ask.sum->nq() > 0) up.add(s->sum_z.p, ask.sum->z.data(), sizeof(double) * ask.sum->nq());
+  if (ask.mix) {
+    std::vector<double> w_pass(bt.order.size());
+    for (size_t q = 0; q < w_pass.size(); ++q) w_pass[q] = ask.mix->w[(size_t)bt.order[q]];
+    if (const int rc = mix_stage(c, s, st, up, *ask.mix, m, w_pass)) return rc;
+  }
+  return AGP_OK;
+}
+
+// The slot's pinned landing zone for sorted positions [p0, p0 + Pc): [mean | var | alpha | dinv | x], the middle two on the
+// training-point route only, x [Pc][mJ][nq].
+struct Landing { int p0, Pc; double* mean; double* var; double* alpha; double* dinv; double* x; };
+int landing_zone(agp_ctx* c, Slot* s, const JointPlan& jp, int nq, int p0, int Pc, Landing& h) {
+  const size_t nm = (size_t)std::max<int64_t>(1, jp.mJ) * Pc, nd = jp.diag_path ? (size_t)jp.ntot * Pc : 0;
+  HIPCHK(c, s->h_out.ensure(sizeof(double) * (2 * nm + 2 * nd + nm * nq)));
+  double* hz = static_cast<double*>(s->h_out.p);
+  h = {p0, Pc, hz, hz + nm, hz + 2 * nm, hz + 2 * nm + nd, hz + 2 * nm + 2 * nd};
+  return AGP_OK;
+}
+
+// Z = L11^-T row chains; alpha = Z beta and diag(K11^-1) = row sums of Z.^2 come out of the same registers
+int z_chain(agp_ctx* c, Slot* s, hipStream_t st, const JointPlan& jp, ResidentFactors& rf, const Landing& h) {
+  const int Pc = h.Pc, ntot = jp.ntot;
+  GradArgs ga = {};
+  ga.A = s->A.as<double>(); ga.strideA = jp.strideA; ga.Z = s->Z.as<double>(); ga.strideZ = jp.strideZ; ga.W = s->W.as<double>();
+  ga.beta = s->vec.as<double>(); ga.alpha = s->alpha.as<double>(); ga.dinv = s->gpart.as<double>(); ga.ldv = ntot;
+  ga.P = Pc; ga.nt = jp.nt1; ga.n = (int)jp.q.n;
+  rf.point(ga, h.p0);
+  if (const int rc = rf.poison(st, h.p0, Pc)) return rc;
+  launch_trtri_chain(st, 8 * ((Pc + 7) / 8) * jp.nt1, ga);
+  if (const int rc = rf.after_chain(st, h.p0 + Pc)) return rc;
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(h.alpha, s->alpha.p, sizeof(double) * ntot * Pc, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(h.dinv, s->gpart.p, sizeof(double) * ntot * Pc, hipMemcpyDeviceToHost, st));
+  return AGP_OK;
+}
+
+// Schur complement of the prediction block + (-V^T alpha); with nt1 == 0 this just passes K22 through.  Without a covariance request
+// only the diagonal tiles are updated: mean and marginal variances cost n^3/3 + n^2 m instead of n^3/3 + n^2 m + n m^2.
+int launch_schur(agp_ctx* c, hipStream_t st, const JointPlan& jp, const Batch& bt, JointChunk& k) {
+  CholArgs& ca = k.ca;
+  ca.schur_diag_only = jp.want_cov ? 0 : 1;
+  const int T = jp.want_cov ? jp.nt2 * (jp.nt2 + 1) / 2 : jp.nt2;
+  const int Pg = (ca.P + 7) / 8;
+  int dcov_s = k.dcov;
+  if (jp.lagr() && k.nf > 0) {
+    // (the Schur kernel has no table-reading instantiation: the prediction block's tiles of the particles that evaluated
+    // their other tiles in-kernel come from k_cov_tiles, which reads the rank tables in place)
+    CovArgs cp = k.cv;
+    cp.p_off = 0; cp.pred_only = 1; cp.i0 = nullptr;
+    HIPCHK(c, launch_cov(st, cp, jp.ntiles, k.nf, bt.max_cp, bt.max_depth, bt.max_ops));
+    ca.n_fused = 0; dcov_s = 0;
+  }
+  launch_update_schur(dcov_s, 8 * Pg * T, st, ca);
+  return AGP_OK;
+}
+
+// means, variances (covariances) of the chunk's joint query points out of the Schur complement: s->pred_mean / pred_var / pred_cov
+int extract_chunk(agp_ctx* c, Slot* s, hipStream_t st, const JointPlan& jp, const PassAsk& ask, int p0, int Pc) {
+  PredArgs pa = {};
+  pa.A = s->A.as<double>(); pa.strideA = jp.strideA; pa.vec = s->vec.as<double>(); pa.ldv = jp.ntot;
+  pa.mu2 = jp.q.mean_pred ? s->mu2.as<double>() : nullptr; pa.noise_pred = s->noise_pred.as<double>() + p0;
+  pa.nt1 = jp.nt1; pa.n1_pad = jp.n1_pad; pa.m = (int)jp.mJ; pa.P = Pc;
+  pa.diag_add = ask.diag_add ? s->diag_add.as<double>() : nullptr;
+  pa.np_code = ask.sum ? s->code.as<uint8_t>() + jp.n1_pad : nullptr;
+  pa.out_mean = s->pred_mean.as<double>(); pa.out_var = s->pred_var.as<double>();
+  pa.out_cov = jp.want_cov ? s->pred_cov.as<double>() : nullptr;
+  const long long nel = jp.want_cov ? (long long)jp.mJ * jp.mJ : (long long)jp.mJ;
+  launch_pred_extract(st, nel, Pc, pa);
+  HIPCHK(c, hipGetLastError());
+  return AGP_OK;
+}
+
+// predict_sum's device read-out of the chunk (k_sum_readout) and its quantiles on their way to the landing zone
+int sum_readout_chunk(agp_ctx* c, Slot* s, hipStream_t st, const JointPlan& jp, const SumPass& sum, const Landing& h) {
+  const int nq = sum.nq();
+  SumReadArgs ra = {};
+  ra.mean = s->pred_mean.as<double>(); ra.var = s->pred_var.as<double>(); ra.m = (int)jp.mJ; ra.p_rows = (int)sum.p_rows;
+  ra.slope = sum.slope; ra.intercept = sum.intercept; ra.shift = sum.intercept / sum.slope;
+  ra.ivar = 1.0 / (sum.slope * sum.slope);
+  ra.z = s->sum_z.as<double>(); ra.nq = nq; ra.x = s->sum_x.as<double>(); ra.bad = s->out_info.as<int32_t>() + h.p0;
+  launch_sum_readout(st, h.Pc, ra);
+  HIPCHK(c, hipGetLastError());
+  if (nq > 0) HIPCHK(c, hipMemcpyAsync(h.x, s->sum_x.p, sizeof(double) * jp.mJ * nq * h.Pc, hipMemcpyDeviceToHost, st));
+  return AGP_OK;
+}
+
+// The landed chunk (sorted order) to the caller's particle order.  Training-point route: the joint results go to their query
+// positions fq, the training-time queries are recombined on the host,
+//     mean = mu2 + (y - mu1) - noise alpha,      var = noise - noise^2 dinv + noise_pred (+ diag_add).
+void scatter_chunk(agp_ctx* c, const JointPlan& jp, const PassAsk& ask, const PassOut& out, const Batch& bt, const SortedNoise& nz,
+                   const Landing& h) {
+  const int64_t m = jp.q.m, mJ = jp.mJ;
+  const double* mean_train = jp.q.mean_train; const double* mean_pred = jp.q.mean_pred;
+  const bool ro = ask.sum && ask.sum->readout;
+  const int nq = ask.sum ? ask.sum->nq() : 0;
+  for (int q = 0; q < h.Pc; ++q) {
+    const size_t o = (size_t)bt.order[h.p0 + q];
+    if (jp.diag_path) {
+      double* om = out.mean + o * m; double* ov = out.var + o * m;
+      for (int64_t g = 0; g < mJ; ++g) { om[jp.fq[(size_t)g]] = h.mean[(size_t)q * mJ + g]; ov[jp.fq[(size_t)g]] = h.var[(size_t)q * mJ + g]; }
+      const double s2 = nz.noise[(size_t)h.p0 + q], np2 = nz.pred[(size_t)h.p0 + q];
+      const double* al = h.alpha + (size_t)q * jp.ntot; const double* dv = h.dinv + (size_t)q * jp.ntot;
+      for (size_t d = 0; d < jp.dq.size(); ++d) {
+        const int32_t j = jp.dq[d], i = jp.di[d];
+        const double ymu = c->h_xs[(size_t)i] - (mean_train ? mean_train[i] : 0.0);
+        om[j] = (mean_pred ? mean_pred[j] : 0.0) + ymu - s2 * al[i];
+        ov[j] = s2 - s2 * s2 * dv[i] + np2 + (ask.diag_add ? ask.diag_add[j] : 0.0);
+      }
+      continue;
+    }
+    std::memcpy(out.mean + o * m, h.mean + (size_t)q * m, sizeof(double) * m);
+    if (!ro) std::memcpy(out.var + o * m, h.var + (size_t)q * m, sizeof(double) * m);
+    if (nq > 0) std::memcpy(ask.sum->out_x + o * m * nq, h.x + (size_t)q * m * nq, sizeof(double) * m * nq);
+  }
+}
+
+// The info pass after the last chunk.  Always made: a caller that passes out.info = NULL must still never receive unmarked garbage.
+int finish_info(agp_ctx* c, Slot* s, hipStream_t st, const JointPlan& jp, const PassAsk& ask, const PassOut& out, const Batch& bt) {
+  const int64_t n = jp.q.n, m = jp.q.m;
+  const int P = (int)bt.order.size();
+  const bool ro = ask.sum && ask.sum->readout;
+  const int nq = ask.sum ? ask.sum->nq() : 0;
+  std::vector<int32_t> info_sorted(P), bad_sorted(ro ? P : 0);
+  HIPCHK(c, hipStreamSynchronize(st));
+  HIPCHK(c, hipMemcpy(info_sorted.data(), s->info.p, sizeof(int32_t) * P, hipMemcpyDeviceToHost));      // (blocking: nothing in flight towards the local on an error return)
+  if (ro) HIPCHK(c, hipMemcpy(bad_sorted.data(), s->out_info.p, sizeof(int32_t) * P, hipMemcpyDeviceToHost));
+  for (int q = 0; q < P; ++q) {
+    if (info_sorted[q] < 0) return fail(c, AGP_ERR_HIP, "in-kernel panel solve timed out waiting for its diagonal factor");
+    const int p = bt.order[q];
+    // (predict_sum: a factor that failed comes first; then the first row of raw marginals that fails)
+    if (ro && info_sorted[q] == 0 && bad_sorted[q] >= 1 && bad_sorted[q] <= m) info_sorted[q] = (int32_t)(n + bad_sorted[q]);
+    if (out.info) out.info[p] = info_sorted[q];
+    if (info_sorted[q] != 0) {
+      const double nanv = std::nan("");
+      for (int64_t g = 0; g < m && out.mean; ++g) { out.mean[(size_t)p * m + g] = nanv; if (out.var) out.var[(size_t)p * m + g] = nanv; }
+      if (out.cov) for (int64_t g = 0; g < m * m; ++g) out.cov[(size_t)p * m * m + g] = nanv;
+      if (nq > 0) std::fill(ask.sum->out_x + (size_t)p * m * nq, ask.sum->out_x + (size_t)(p + 1) * m * nq, nanv);
+    }
+  }
+  return AGP_OK;
+}
+
+// Core of the predictive path (src/GP.jl:739-757) for a compiled batch (bt: pp's programs, compiled) over the plan `jp` its entry made.
+int predict_core(agp_ctx* c, const Particles& pp, Batch& bt, const JointPlan& jp, const PassAsk& ask, const PassOut& out) {
+  const int64_t n = jp.q.n, m = jp.q.m, mJ = jp.mJ;
+  const int P = pp.P;
+  const int nt1 = jp.nt1, ntot = jp.ntot;
+  const SumPass* sum = ask.sum; MixPass* mix = ask.mix;
+  const bool ro = sum && sum->readout;
+  const int nq = sum ? sum->nq() : 0;
+  if (jp.want_cov != (out.cov != nullptr || (mix && mix->cov)) || jp.has_codes != (ask.pred_code != nullptr) || (int)bt.order.size() != P)
+    return fail(c, AGP_ERR_ARG, "the joint plan was made for another pass");
+  // ---- store lookup (the store's lock before the slot) ----
+  ResidentFactors rf(c);
+  if (ask.keys && c->predict_reuse && nt1 > 0 && !jp.q.mean_train && !ask.pred_code) rf.lookup(*ask.keys, bt, P, jp);
+  const int n_hit = rf.n_hit;
+  // ---- slot and stream ----
+  SlotGuard sg(c);
+  Slot* s = sg.s;
+  if (!s->stream) HIPCHK(c, hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
+  hipStream_t st = s->stream;
+  // ---- buffer sizes, uploads, one flush ----
+  const int chunk = jp.chunk(c, P);
+  if (const int rc = size_buffers(c, s, jp, sum, P, chunk)) return rc;
+  PinnedUploads up;
+  SortedNoise nz;
+  if (const int rc = stage_joint(c, s, up, jp, pp, bt, chunk, nz)) return rc;
+  if (const int rc = stage_modes(c, s, st, up, jp, ask, bt)) return rc;
+  if (n_hit > 0 && jp.diag_path) rf.begin_z();
+  if (n_hit > 0)
+    if (const int rc = rf.stage(s, up)) return rc;
+  if (const int rc = flush_uploads(c, s, st, up, bt, jp)) return rc;
 
   if (ro) HIPCHK(c, hipMemsetAsync(s->out_info.p, 0x7f, sizeof(int32_t) * (size_t)P, st));      // (no failing row: 0x7f7f7f7f)
-  const double* h_mean = nullptr; const double* h_var = nullptr; const double* h_alpha = nullptr; const double* h_dinv = nullptr;      // in the slot's pinned landing zone
-  const double* h_x = nullptr;
   for (int p0 = 0; p0 < P; p0 += chunk) {
     const int Pc = std::min(chunk, P - p0);
-    {
-      const size_t nm = (size_t)std::max<int64_t>(1, mJ) * Pc, nd = diag_path ? (size_t)ntot * Pc : 0;
-      HIPCHK(c, s->h_out.ensure(sizeof(double) * (2 * nm + 2 * nd + nm * nq)));
-      double* hz = static_cast<double*>(s->h_out.p);
-      h_mean = hz; h_var = hz + nm; h_alpha = hz + 2 * nm; h_dinv = hz + 2 * nm + nd; h_x = hz + 2 * nm + 2 * nd;
-    }
-    launch_init_vec(st, ntot, Pc, s->vec.as<double>(), c->d_xs, (mean_train && n > 0) ? s->mu1.as<double>() : (const double*)nullptr, (int)n, s->info.as<int>() + p0, s->ready.as<int>() + p0);
+    Landing h;
+    if (const int rc = landing_zone(c, s, jp, nq, p0, Pc, h)) return rc;
+    // ---- init, gather ----
+    launch_init_vec(st, ntot, Pc, s->vec.as<double>(), c->d_xs, (jp.q.mean_train && n > 0) ? s->mu1.as<double>() : (const double*)nullptr, (int)n, s->info.as<int>() + p0, s->ready.as<int>() + p0);
     if (n_hit > 0) {
-      launch_gather(c, st, Pc, nt1, s->A.as<double>(), strideA, s->W.as<double>(), nt1, s->vec.as<double>(), ntot, nullptr, 0,
-                    d_src + p0, s->ready.as<int>() + p0);
+      launch_gather(c, st, Pc, nt1, s->A.as<double>(), jp.strideA, s->W.as<double>(), nt1, s->vec.as<double>(), ntot, nullptr, 0,
+                    rf.d_src + p0, s->ready.as<int>() + p0);
       HIPCHK(c, hipGetLastError());
       // (Reading L11 and the inverse blocks in place — a second base pointer for the training rows in chol_tile — was
       // measured: the streamed config 5 went 412 -> 406 ms, the dataflow kernel gained 4 spilled VGPRs; the copy stays.)
-      if (p0 + chunk >= P && !zstore) {
-        // the store may change again once the last copy has been made (resident L^-T: once its new columns are in, below)
-        HIPCHK(c, hipStreamSynchronize(st));
-        store_lk.unlock();
-      }
+      if (const int rc = rf.after_gather(st, p0 + Pc)) return rc;
     }
-    CovArgs cv = {};
-    cv.tt = s->tt.as<double>(); cv.n1 = (int)n; cv.n1_pad = n1_pad; cv.m2 = (int)mJ; cv.nt = nt;
-    cv.hdr = s->hdr.as<ProgHdr>() + p0; cv.ops = s->ops.as<uint8_t>(); cv.prm = s->prm.as<double>();
-    cv.noise = s->noise.as<double>() + p0; cv.A = s->A.as<double>(); cv.strideA = strideA; cv.P = Pc;
-    cv.code = pred_code ? s->code.as<uint8_t>() : nullptr;
-    if (lagr) { cv.lagtab = s->lagtab.as<double>(); cv.lagr = s->pl_rank.as<int32_t>(); cv.lag_stride = pl->rank_units * 256; }
-    const int nf = std::max(0, std::min(Pc, bt.n_fused - p0));
-    const int dcov = nf > 0 ? bt.max_depth_fused : 0;
-    cv.p_off = nf;
-    cv.skip_pred_offdiag = want_cov ? 0 : 1;
-    cv.i0 = n_hit > 0 ? d_i0 + p0 : nullptr;
-    HIPCHK(c, launch_cov(st, cv, ntiles, Pc - nf, bt.max_cp, bt.max_depth, bt.max_ops));
-
-    CholArgs ca = {};
-    ca.A = s->A.as<double>(); ca.strideA = strideA; ca.W = s->W.as<double>();
-    ca.vec = s->vec.as<double>(); ca.ldv = ntot; ca.partial = s->partial.as<double>();
-    ca.info = s->info.as<int>() + p0; ca.P = Pc; ca.nt = nt; ca.k = 0; ca.nt1 = nt1;
-    set_cov(ca, cv);
-    ca.lag = lagr ? 1 : 0;
-    ca.n_fused = nf;
-    ca.ready = s->ready.as<int>() + p0;
-    if (n_hit > 0 || diag_path) ca.wsteps = nt1;      // panel solves of the prediction rows / the chains of Z read every column's inverse blocks
-    if (n_hit > 0) ca.i0 = d_i0 + p0;
-    if (nt1 > 0 && (sum ? c->flow != 0 : use_flow(c, Pc, nt, nt1))) {
+    // ---- tiles ----
+    JointChunk k = chunk_setup(s, jp, bt, p0, Pc);
+    CholArgs& ca = k.ca;
+    k.cv.code = ca.code = ask.pred_code ? s->code.as<uint8_t>() : nullptr;
+    k.cv.skip_pred_offdiag = jp.want_cov ? 0 : 1;
+    k.cv.i0 = ca.i0 = n_hit > 0 ? rf.d_i0 + p0 : nullptr;
+    if (n_hit > 0 || jp.diag_path) ca.wsteps = nt1;      // panel solves of the prediction rows / the chains of Z read every column's inverse blocks
+    HIPCHK(c, launch_cov(st, k.cv, jp.ntiles, Pc - k.nf, bt.max_cp, bt.max_depth, bt.max_ops));
+    // ---- factor ----
+    if (nt1 > 0 && (sum ? c->flow != 0 : use_flow(c, Pc, jp.nt, nt1))) {
       // dataflow schedule over the block columns of the training block (all rows: V = L^-1 K12 comes out of the same tiles)
-      if (const int rc = launch_joint_flow(c, s, st, ca, dcov, nt1)) return rc;
+      if (const int rc = launch_joint_flow(c, s, st, ca, k.dcov, nt1)) return rc;
     } else if (n_hit > 0) {
       // (invariant of every branch here: only the training block's nt1 columns are factored, so the diagonal-tile kernel sees
       // tiles with n1 - tk * NB > 0 rows of data; the query rows below them are panel solves, never a diagonal step)
       // per-column launches restricted to the rows some particle still has to compute
       int i0min = nt1;
-      for (int q = 0; q < Pc; ++q) i0min = std::min(i0min, (int)i0v[(size_t)p0 + q]);
-      HIPCHK(c, run_factor_extend(st, ca, dcov, use_split_diag(c, ca.P), i0min, nt1));
+      for (int q = 0; q < Pc; ++q) i0min = std::min(i0min, (int)rf.i0v[(size_t)p0 + q]);
+      HIPCHK(c, run_factor_extend(st, ca, k.dcov, use_split_diag(c, ca.P), i0min, nt1));
     } else {
-      HIPCHK(c, run_factor(st, ca, nt1, dcov, nullptr, nullptr, use_split_diag(c, ca.P)));
+      HIPCHK(c, run_factor(st, ca, nt1, k.dcov, nullptr, nullptr, use_split_diag(c, ca.P)));
     }
-    if (diag_path) {
-      // Z = L11^-T row chains; alpha = Z beta and diag(K11^-1) = row sums of Z.^2 come out of the same registers
-      GradArgs ga = {};
-      ga.A = s->A.as<double>(); ga.strideA = strideA; ga.Z = s->Z.as<double>(); ga.strideZ = strideZ; ga.W = s->W.as<double>();
-      ga.beta = s->vec.as<double>(); ga.alpha = s->alpha.as<double>(); ga.dinv = s->gpart.as<double>(); ga.ldv = ntot;
-      ga.P = Pc; ga.nt = nt1; ga.n = (int)n;
-      if (zstore) {
-        agp_ctx::FactorStore& fs = c->store;
-        ga.lslot = d_src + p0; ga.Lsrc = fs.A.as<double>(); ga.Lstride = fs.strideA; ga.Wsrc = fs.W.as<double>(); ga.Wnt = fs.nt_cap;
-        ga.Zsrc = fs.Z.as<double>(); ga.Zstride = fs.strideA; ga.zi0 = d_zi0 + p0;
-        ga.zalpha = fs.zalpha.as<double>(); ga.zdinv = fs.zdinv.as<double>(); ga.zld = (long long)fs.nt_cap * NB;
-        ga.zfull = (int)(n / NB);
-      }
-      // (the kernel advances the slots' running sums on the device; their column counts are committed on the host only after the
-      // LAST chunk: any return in between must not leave sums that already include columns the host does not know of)
-      if (zstore && c->poison.active()) {
-        // NaN-poison mode: what the chain forms again — tile columns >= zi0 of the entry's Z (column i of Z is packed row i) and the
-        // running sums of rows >= zi0 (rows below it start from theirs) — reads NaN until written.  Copies (zi0 < 0) are skipped.
-        agp_ctx::FactorStore& fs = c->store;
-        PoisonRowsArgs pa = {};
-        double* bases[3] = {fs.Z.as<double>(), fs.zalpha.as<double>(), fs.zdinv.as<double>()};
-        const long long pitch[3] = {fs.strideA, (long long)fs.nt_cap * NB, (long long)fs.nt_cap * NB};
-        const long long unit[3] = {NB2, NB, NB};
-        for (int b = 0; b < 3; ++b) { pa.base[b] = bases[b]; pa.pitch[b] = pitch[b]; pa.unit[b] = unit[b]; pa.tri[b] = b == 0; }
-        pa.nt_cap = fs.nt_cap; pa.slot = d_src + p0; pa.i0 = d_zi0 + p0;
-        launch_poison_rows(st, 256, Pc, 3, pa);
-        HIPCHK(c, hipGetLastError());
-        for (int q = p0; q < p0 + Pc; ++q) {
-          if (src_slot[(size_t)q] < 0 || zi0v[(size_t)q] < 0) continue;
-          const long long r0 = std::min<long long>(zi0v[(size_t)q], fs.nt_cap);
-          c->poison.count(sizeof(double) * (size_t)((fs.strideA - r0 * (r0 + 1) / 2 * NB2) + 2 * (fs.nt_cap - r0) * NB));
-        }
-      }
-      if (zstore) zguard.armed = true;
-      launch_trtri_chain(st, 8 * ((Pc + 7) / 8) * nt1, ga);
-      if (zstore && p0 + chunk >= P) {
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipStreamSynchronize(st));
-        // (complete tile columns only: the column of a partly filled last tile is formed again on a longer prefix)
-        for (int q = 0; q < P; ++q) if (src_slot[(size_t)q] >= 0) c->store.zrows[(size_t)src_slot[(size_t)q]] = (int32_t)(n / NB);
-        zguard.armed = false;
-        store_lk.unlock();
-      }
-      HIPCHK(c, hipGetLastError());
-      HIPCHK(c, hipMemcpyAsync(const_cast<double*>(h_alpha), s->alpha.p, sizeof(double) * ntot * Pc, hipMemcpyDeviceToHost, st));
-      HIPCHK(c, hipMemcpyAsync(const_cast<double*>(h_dinv), s->gpart.p, sizeof(double) * ntot * Pc, hipMemcpyDeviceToHost, st));
-    }
+    // ---- Z chain, Schur, extract, mode read-outs, copy-back ----
+    if (jp.diag_path)
+      if (const int rc = z_chain(c, s, st, jp, rf, h)) return rc;
     if (mJ > 0) {
-      // Schur complement of the prediction block + (-V^T alpha); with nt1 == 0 this just
-      // passes K22 through.
-      // without a covariance request only the diagonal tiles are updated: mean and marginal variances cost
-      // n^3/3 + n^2 m instead of n^3/3 + n^2 m + n m^2
-      ca.schur_diag_only = want_cov ? 0 : 1;
-      const int T = want_cov ? nt2 * (nt2 + 1) / 2 : nt2;
-      const int Pg = (Pc + 7) / 8;
-      int dcov_s = dcov;
-      if (lagr && nf > 0) {
-        // (the Schur kernel has no table-reading instantiation: the prediction block's tiles of the particles that evaluated
-        // their other tiles in-kernel come from k_cov_tiles, which reads the rank tables in place)
-        CovArgs cp = cv;
-        cp.p_off = 0; cp.pred_only = 1; cp.i0 = nullptr;
-        HIPCHK(c, launch_cov(st, cp, ntiles, nf, bt.max_cp, bt.max_depth, bt.max_ops));
-        ca.n_fused = 0; dcov_s = 0;
-      }
-      launch_update_schur(dcov_s, 8 * Pg * T, st, ca);
-    }
-    if (mJ > 0) {
-    PredArgs pa = {};
-    pa.A = s->A.as<double>(); pa.strideA = strideA; pa.vec = s->vec.as<double>(); pa.ldv = ntot;
-    pa.mu2 = mean_pred ? s->mu2.as<double>() : nullptr; pa.noise_pred = s->noise_pred.as<double>() + p0;
-    pa.nt1 = nt1; pa.n1_pad = n1_pad; pa.m = (int)mJ; pa.P = Pc;
-    pa.diag_add = diag_add ? s->diag_add.as<double>() : nullptr;
-    pa.np_code = sum ? s->code.as<uint8_t>() + n1_pad : nullptr;
-    pa.out_mean = s->pred_mean.as<double>(); pa.out_var = s->pred_var.as<double>();
-    pa.out_cov = want_cov ? s->pred_cov.as<double>() : nullptr;
-    const long long nel = want_cov ? (long long)mJ * mJ : (long long)mJ;
-    launch_pred_extract(st, nel, Pc, pa);
-    HIPCHK(c, hipGetLastError());
-    if (mix)      // (before the next chunk overwrites pred_mean / pred_cov)
-      if (const int rc = mix_chunk(c, s, st, *mix, p0, Pc, pa.out_mean, pa.out_var, pa.out_cov)) return rc;
-    if (ro) {
-      SumReadArgs ra = {};
-      ra.mean = s->pred_mean.as<double>(); ra.var = s->pred_var.as<double>(); ra.m = (int)mJ; ra.p_rows = (int)sum->p_rows;
-      ra.slope = sum->slope; ra.intercept = sum->intercept; ra.shift = sum->intercept / sum->slope;
-      ra.ivar = 1.0 / (sum->slope * sum->slope);
-      ra.z = s->sum_z.as<double>(); ra.nq = nq; ra.x = s->sum_x.as<double>(); ra.bad = s->out_info.as<int32_t>() + p0;
-      launch_sum_readout(st, Pc, ra);
-      HIPCHK(c, hipGetLastError());
-      if (nq > 0)
-        HIPCHK(c, hipMemcpyAsync(const_cast<double*>(h_x), s->sum_x.p, sizeof(double) * mJ * nq * Pc, hipMemcpyDeviceToHost, st));
-    }
-    // results come back in sorted order: scatter to the caller's particle order (a mixture pass returns no per-particle marginals)
-    if (!mix) HIPCHK(c, hipMemcpyAsync(const_cast<double*>(h_mean), s->pred_mean.p, sizeof(double) * mJ * Pc, hipMemcpyDeviceToHost, st));
-    if (!ro && !mix) HIPCHK(c, hipMemcpyAsync(const_cast<double*>(h_var), s->pred_var.p, sizeof(double) * mJ * Pc, hipMemcpyDeviceToHost, st));
+      if (const int rc = launch_schur(c, st, jp, bt, k)) return rc;
+      if (const int rc = extract_chunk(c, s, st, jp, ask, p0, Pc)) return rc;
+      if (mix)      // (before the next chunk overwrites pred_mean / pred_cov)
+        if (const int rc = mix_chunk(c, s, st, *mix, p0, Pc, s->pred_mean.as<double>(), s->pred_var.as<double>(),
+                                     jp.want_cov ? s->pred_cov.as<double>() : nullptr)) return rc;
+      if (ro)
+        if (const int rc = sum_readout_chunk(c, s, st, jp, *sum, h)) return rc;
+      // results come back in sorted order (a mixture pass returns no per-particle marginals)
+      if (!mix) HIPCHK(c, hipMemcpyAsync(h.mean, s->pred_mean.p, sizeof(double) * mJ * Pc, hipMemcpyDeviceToHost, st));
+      if (!ro && !mix) HIPCHK(c, hipMemcpyAsync(h.var, s->pred_var.p, sizeof(double) * mJ * Pc, hipMemcpyDeviceToHost, st));
     }
     HIPCHK(c, hipStreamSynchronize(st));
-    for (int q = 0; q < Pc && !mix; ++q) {
-      const size_t o = (size_t)bt.order[p0 + q];
-      if (diag_path) {
-        double* om = out_mean + o * m; double* ov = out_var + o * m;
-        for (int64_t g = 0; g < mJ; ++g) { om[fq[(size_t)g]] = h_mean[(size_t)q * mJ + g]; ov[fq[(size_t)g]] = h_var[(size_t)q * mJ + g]; }
-        const double s2 = noise_sorted[(size_t)p0 + q], np2 = npred[(size_t)p0 + q];
-        const double* al = h_alpha + (size_t)q * ntot; const double* dv = h_dinv + (size_t)q * ntot;
-        for (size_t d = 0; d < dq.size(); ++d) {
-          const int32_t j = dq[d], i = di[d];
-          const double ymu = c->h_xs[(size_t)i] - (mean_train ? mean_train[i] : 0.0);
-          om[j] = (mean_pred ? mean_pred[j] : 0.0) + ymu - s2 * al[i];
-          ov[j] = s2 - s2 * s2 * dv[i] + np2 + (diag_add ? diag_add[j] : 0.0);
-        }
-        continue;
-      }
-      std::memcpy(out_mean + o * m, h_mean + (size_t)q * m, sizeof(double) * m);
-      if (!ro) std::memcpy(out_var + o * m, h_var + (size_t)q * m, sizeof(double) * m);
-      if (nq > 0) std::memcpy(sum->out_x + o * m * nq, h_x + (size_t)q * m * nq, sizeof(double) * m * nq);
-      if (out_cov)
-        HIPCHK(c, hipMemcpyAsync(out_cov + o * m * m, s->pred_cov.as<double>() + (size_t)q * m * m,
-                                 sizeof(double) * m * m, hipMemcpyDeviceToHost, st));
-    }
+    if (!mix) scatter_chunk(c, jp, ask, out, bt, nz, h);
+    for (int q = 0; q < Pc && out.cov && !mix; ++q)
+      HIPCHK(c, hipMemcpyAsync(out.cov + (size_t)bt.order[p0 + q] * m * m, s->pred_cov.as<double>() + (size_t)q * m * m,
+                               sizeof(double) * m * m, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
   }
   if (mix)
     if (const int rc = mix_finish(c, s, st, *mix)) return rc;
-  {
-    // always inspected: a caller that passes out_info = NULL must still never receive unmarked garbage
-    std::vector<int32_t> info_sorted(P), bad_sorted(ro ? P : 0);
-    HIPCHK(c, hipStreamSynchronize(st));
-    HIPCHK(c, hipMemcpy(info_sorted.data(), s->info.p, sizeof(int32_t) * P, hipMemcpyDeviceToHost));      // (blocking: nothing in flight towards the local on an error return)
-    if (ro) HIPCHK(c, hipMemcpy(bad_sorted.data(), s->out_info.p, sizeof(int32_t) * P, hipMemcpyDeviceToHost));
-    for (int q = 0; q < P; ++q) {
-      if (info_sorted[q] < 0) return fail(c, AGP_ERR_HIP, "in-kernel panel solve timed out waiting for its diagonal factor");
-      const int p = bt.order[q];
-      // (predict_sum: a factor that failed comes first; then the first row of raw marginals that fails)
-      if (ro && info_sorted[q] == 0 && bad_sorted[q] >= 1 && bad_sorted[q] <= m) info_sorted[q] = (int32_t)(n + bad_sorted[q]);
-      if (out_info) out_info[p] = info_sorted[q];
-      if (info_sorted[q] != 0) {
-        const double nanv = std::nan("");
-        for (int64_t g = 0; g < m && out_mean; ++g) { out_mean[(size_t)p * m + g] = nanv; if (out_var) out_var[(size_t)p * m + g] = nanv; }
-        if (out_cov) for (int64_t g = 0; g < m * m; ++g) out_cov[(size_t)p * m * m + g] = nanv;
-        if (nq > 0) std::fill(sum->out_x + (size_t)p * m * nq, sum->out_x + (size_t)(p + 1) * m * nq, nanv);
-      }
-    }
-  }
-  return AGP_OK;
+  return finish_info(c, s, st, jp, ask, out, bt);
 }
 
 // Predictive log-density (src/api.jl:686-699, test/experiment_hmc.jl:125): logpdf(MvNormal(node, noise, ts[1:n], xs[1:n], ts_pred;
@@ -541,79 +682,56 @@ int predict_core(agp_ctx* c, const PredQuery& q, const Particles& pp, Batch& bt,
 // factored through ALL nt1 + nt2 block columns with [x - mu1; y_pred - mu2] in the forward solve: the query block of the factor is
 // the Cholesky factor of Sigma* = K22 - K21 K11^-1 K12 + noise_pred I and its forward solve L22^-1 (y* - mu*), so the query columns'
 // partials are log|Sigma*| and the Mahalanobis term themselves (k_finish_pred_logpdf) — no Schur step, no read-out, and no
-// difference of two large log-likelihoods.  (No duplicate-query shortcut: it yields diag(Sigma*), not Sigma*.)
-// y_pred == nullptr (agp_predict_sample_batch): the query part of the right-hand side is 0.  `hooks` (nullable): see JointHooks.
-int predict_logpdf_core(agp_ctx* c, const PredQuery& q, const double* y_pred, const Particles& pp, Batch& bt, double* out_lp,
-                        int32_t* out_info, const PredLattice* pl, JointHooks* hooks) {
-  const int64_t n = q.n, m = q.m;
+// difference of two large log-likelihoods.  (No duplicate-query shortcut: it yields diag(Sigma*), not Sigma* — its plan is made with
+// want_cov.)  y_pred == nullptr (agp_predict_sample_batch): the query part of the right-hand side is 0.  `hooks` (nullable): see
+// JointHooks.
+int predict_logpdf_core(agp_ctx* c, const JointPlan& jp, const double* y_pred, const Particles& pp, Batch& bt, double* out_lp,
+                        int32_t* out_info, JointHooks* hooks) {
+  const int64_t n = jp.q.n, m = jp.q.m;
   const int P = pp.P;
-  const double* mean_train = q.mean_train; const double* mean_pred = q.mean_pred;
-  const int n1_pad = round_up(n, NB), m_pad = round_up(m, NB);
-  const bool lagr = pl != nullptr && pl->on;
-  const int nt1 = n1_pad / NB, nt = nt1 + m_pad / NB;
-  const int ntot = n1_pad + m_pad;
-  const int ntiles = nt * (nt + 1) / 2;
-  const long long strideA = (long long)ntiles * NB2;
-  const int chunk = (int)std::max<int64_t>(1, std::min<int64_t>(P, ws_limit_bytes(c) / (strideA * 8)));
+  const int nt1 = jp.nt1, nt = jp.nt, ntot = jp.ntot;
+  const int chunk = jp.chunk(c, P);
 
   SlotGuard sg(c);
   Slot* s = sg.s;
   if (!s->stream) HIPCHK(c, hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
   hipStream_t st = s->stream;
 
-  HIPCHK(c, s->A.ensure((size_t)strideA * 8 * chunk));
+  HIPCHK(c, s->A.ensure((size_t)jp.strideA * 8 * chunk));
   HIPCHK(c, s->W.ensure(sizeof(double) * NSB * 256 * (size_t)chunk * nt));     // (the dataflow schedule keeps every column's inverse blocks)
   HIPCHK(c, s->pred_mean.ensure(sizeof(double) * (size_t)m));      // y_pred (the read-out buffers are idle in this pass)
   HIPCHK(c, s->map.ensure(sizeof(int32_t) * (size_t)P));
   HIPCHK(c, s->out_lp.ensure(sizeof(double) * (size_t)P));
   HIPCHK(c, s->out_info.ensure(sizeof(int32_t) * (size_t)P));
   PinnedUploads up;
-  std::vector<double> noise_sorted, npred;
-  if (const int rc = stage_joint(c, s, up, q, pp, chunk, bt, noise_sorted, npred)) return rc;
+  SortedNoise nz;
+  if (const int rc = stage_joint(c, s, up, jp, pp, bt, chunk, nz)) return rc;
   if (y_pred) up.add(s->pred_mean.p, y_pred, sizeof(double) * m);
   up.add(s->map.p, bt.order.data(), sizeof(int32_t) * P);
   if (hooks && hooks->stage)
     if (const int rc = hooks->stage(s, up, chunk)) return rc;
-  if (!lagr) {
-    HIPCHK(c, up.flush(s->h_stage, s->up_blob, st));
-  } else if (const int rc = flush_lattice(c, s, st, up, bt, *pl, pl->rank)) {
-    return rc;
-  }
+  if (const int rc = flush_uploads(c, s, st, up, bt, jp)) return rc;
 
   for (int p0 = 0; p0 < P; p0 += chunk) {
     const int Pc = std::min(chunk, P - p0);
-    launch_init_vec(st, ntot, Pc, s->vec.as<double>(), c->d_xs, (mean_train && n > 0) ? s->mu1.as<double>() : (const double*)nullptr,
+    launch_init_vec(st, ntot, Pc, s->vec.as<double>(), c->d_xs, (jp.q.mean_train && n > 0) ? s->mu1.as<double>() : (const double*)nullptr,
                     (int)n, s->info.as<int>() + p0, s->ready.as<int>() + p0);
     if (y_pred)
-      launch_init_query_vec(st, Pc, s->vec.as<double>(), ntot, n1_pad, (int)m, s->pred_mean.as<double>(),
-                            mean_pred ? s->mu2.as<double>() : (const double*)nullptr);
-    CovArgs cv = {};
-    cv.tt = s->tt.as<double>(); cv.n1 = (int)n; cv.n1_pad = n1_pad; cv.m2 = (int)m; cv.nt = nt;
-    cv.hdr = s->hdr.as<ProgHdr>() + p0; cv.ops = s->ops.as<uint8_t>(); cv.prm = s->prm.as<double>();
-    cv.noise = s->noise.as<double>() + p0; cv.noise_q = s->noise_pred.as<double>() + p0;
-    cv.A = s->A.as<double>(); cv.strideA = strideA; cv.P = Pc;
-    if (lagr) { cv.lagtab = s->lagtab.as<double>(); cv.lagr = s->pl_rank.as<int32_t>(); cv.lag_stride = pl->rank_units * 256; }
-    const int nf = std::max(0, std::min(Pc, bt.n_fused - p0));
-    const int dcov = nf > 0 ? bt.max_depth_fused : 0;
-    cv.p_off = nf;
-    HIPCHK(c, launch_cov(st, cv, ntiles, Pc - nf, bt.max_cp, bt.max_depth, bt.max_ops));
-
-    CholArgs ca = {};
-    ca.A = s->A.as<double>(); ca.strideA = strideA; ca.W = s->W.as<double>();
-    ca.vec = s->vec.as<double>(); ca.ldv = ntot; ca.partial = s->partial.as<double>();
-    ca.info = s->info.as<int>() + p0; ca.P = Pc; ca.nt = nt; ca.k = 0; ca.nt1 = nt;      // (every block column is factored)
-    set_cov(ca, cv);
-    ca.lag = lagr ? 1 : 0;
-    ca.n_fused = nf;
-    ca.ready = s->ready.as<int>() + p0;
+      launch_init_query_vec(st, Pc, s->vec.as<double>(), ntot, jp.n1_pad, (int)m, s->pred_mean.as<double>(),
+                            jp.q.mean_pred ? s->mu2.as<double>() : (const double*)nullptr);
+    JointChunk k = chunk_setup(s, jp, bt, p0, Pc);
+    CholArgs& ca = k.ca;
+    k.cv.noise_q = ca.noise_q = s->noise_pred.as<double>() + p0;
+    ca.nt1 = nt;      // (every block column is factored)
+    HIPCHK(c, launch_cov(st, k.cv, jp.ntiles, Pc - k.nf, bt.max_cp, bt.max_depth, bt.max_ops));
     // (one schedule whatever the batch: a particle's log-density does not depend on the particles around it — the per-column
     // launches only where the dataflow schedule is switched off, AGP_FLOW=0)
     if (c->flow != 0) {
-      if (const int rc = launch_joint_flow(c, s, st, ca, dcov, nt)) return rc;
+      if (const int rc = launch_joint_flow(c, s, st, ca, k.dcov, nt)) return rc;
     } else {
-      HIPCHK(c, run_factor(st, ca, nt, dcov, nullptr, nullptr, use_split_diag(c, ca.P)));
+      HIPCHK(c, run_factor(st, ca, nt, k.dcov, nullptr, nullptr, use_split_diag(c, ca.P)));
     }
-    launch_finish_pred_logpdf(st, ca.partial, ca.info, nt1, nt, Pc, (int)m, (int)n, n1_pad, s->map.as<int32_t>() + p0,
+    launch_finish_pred_logpdf(st, ca.partial, ca.info, nt1, nt, Pc, (int)m, (int)n, jp.n1_pad, s->map.as<int32_t>() + p0,
                               s->out_lp.as<double>(), s->out_info.as<int32_t>());
     HIPCHK(c, hipGetLastError());
     if (hooks && hooks->chunk)      // (before the next chunk overwrites A)
@@ -819,16 +937,11 @@ int predict_dense(agp_ctx* c, const PredQuery& q, const Particles& pp, double* o
   const bool want_keys = c->predict_reuse && n > 0 && !q.mean_train && c->store.n_slots > 0;
   PredLattice pl;
   predict_lattice(c, n, q.ts_pred, m, pl);
-  int64_t m_joint = m;       // query points predict_core keeps in the joint matrix (it makes the same split)
-  {
-    std::vector<int32_t> dq, di, fq;
-    split_queries(c, n, q.ts_pred, m, !want_cov && !c->ref_arith, dq, di, fq);
-    if (!dq.empty()) m_joint = (int64_t)fq.size();
-  }
-  const int nt1_ = (int)((n + NB - 1) / NB), nt_ = nt1_ + (int)((m_joint + NB - 1) / NB);
+  JointPlan jp;              // (before the batch is compiled: the schedule hints see the joint matrix that will run)
+  plan_joint(c, q, want_cov, false, nullptr, &pl, jp);
   Batch bt;
   CompileOpts co;
-  co.fuse_hint = co.flow_limit = n > 0 && use_flow(c, U, nt_, nt1_);
+  co.fuse_hint = co.flow_limit = n > 0 && use_flow(c, U, jp.nt, jp.nt1);
   co.lag = pl.on; co.lag_units = pl.on ? pl.rank_units : 1; co.rank_extra = pl.on;
   int rc = compile_batch(c, run, bt, co);
   if (rc) return rc;
@@ -836,7 +949,9 @@ int predict_dense(agp_ctx* c, const PredQuery& q, const Particles& pp, double* o
   if (want_keys)
     for (int u = 0; u < U; ++u) keys.push_back(particle_key(run, u));
   auto core = [&](double* om, double* ov, double* oc, int32_t* oi) {
-    return predict_core(c, q, run, bt, nullptr, nullptr, om, ov, oc, oi, want_keys ? &keys : nullptr, &pl, nullptr, mix);
+    PassAsk ask; ask.keys = want_keys ? &keys : nullptr; ask.mix = mix;
+    PassOut out; out.mean = om; out.var = ov; out.cov = oc; out.info = oi;
+    return predict_core(c, run, bt, jp, ask, out);
   };
   if (!D.packed()) return core(out_mean, out_var, out_cov, out_info);
   std::vector<double> umean(mix ? 0 : (size_t)U * m), uvar(mix ? 0 : (size_t)U * m), ucov(out_cov ? (size_t)U * m * m : 0);
@@ -972,7 +1087,9 @@ int predict_joint_batch(agp_ctx* c, const PredQuery& q, const double* y_pred, co
   if (rc) return rc;
   if (hooks && hooks->plan)
     if ((rc = hooks->plan(U, D.packed() ? D.rep : std::vector<int>(), bt.order))) return rc;
-  rc = predict_logpdf_core(c, q, y_pred, D.run(), bt, ulp.data(), uinfo.data(), &pl, hooks);
+  JointPlan jp;
+  plan_joint(c, q, true, false, nullptr, &pl, jp);      // (the whole of Sigma*: no split)
+  rc = predict_logpdf_core(c, jp, y_pred, D.run(), bt, ulp.data(), uinfo.data(), hooks);
   if (rc) return rc;
   D.scatter(ulp.data(), out_logpdf); D.scatter(uinfo.data(), out_info);
   return AGP_OK;
@@ -1062,9 +1179,12 @@ int sum_batch_body(agp_ctx* c, int64_t n, const double* ts_pred, int64_t p, int3
   std::vector<int32_t> uinfo((size_t)U, 0);
   double* x_caller = sp->out_x;
   if (copies && nq > 0) sp->out_x = ux.data();
-  rc = predict_core(c, {n, tq.data(), ma, nullptr, nullptr}, run, bt, code.data(), dadd.data(), copies ? umean.data() : out_mean,
-                    copies ? (out_var ? uvar.data() : nullptr) : out_var, copies ? (out_cov ? ucov.data() : nullptr) : out_cov,
-                    uinfo.data(), nullptr, nullptr, sp);
+  JointPlan jp;
+  plan_joint(c, {n, tq.data(), ma, nullptr, nullptr}, out_cov != nullptr, true, dadd.data(), nullptr, jp);
+  PassAsk ask; ask.pred_code = code.data(); ask.diag_add = dadd.data(); ask.sum = sp;
+  PassOut out; out.mean = copies ? umean.data() : out_mean; out.var = copies ? (out_var ? uvar.data() : nullptr) : out_var;
+  out.cov = copies ? (out_cov ? ucov.data() : nullptr) : out_cov; out.info = uinfo.data();
+  rc = predict_core(c, run, bt, jp, ask, out);
   sp->out_x = x_caller;
   if (rc) return rc;
   D.scatter(uinfo.data(), out_info);
@@ -1151,7 +1271,11 @@ int agp_infer_gp_sum(agp_ctx* c, int64_t n, const double* ts_pred, int64_t p, in
         dadd[g] = 1e-8 + (i == M ? noise_pred : 0.0);       // JITTER (src/GP.jl:760,986) + noise_pred on X(T*)
       }
     int32_t info = 0;
-    rc = predict_core(c, {n, tq.data(), ma, nullptr, nullptr}, one, bt, code.data(), dadd.data(), out_mean, var.data(), out_cov, &info);
+    JointPlan jp;
+    plan_joint(c, {n, tq.data(), ma, nullptr, nullptr}, out_cov != nullptr, true, dadd.data(), nullptr, jp);
+    PassAsk ask; ask.pred_code = code.data(); ask.diag_add = dadd.data();
+    PassOut out; out.mean = out_mean; out.var = var.data(); out.cov = out_cov; out.info = &info;
+    rc = predict_core(c, one, bt, jp, ask, out);
     if (out_info) *out_info = info;
     return rc;
   });

@@ -488,6 +488,55 @@ def test_predictive_passes_keep_the_inverse_factor_resident(pkg):
         a.close(); b.close()
 
 
+@pytest.mark.parametrize("poison", ["0", "1"])
+def test_resident_inverse_factor_across_chunks(pkg, monkeypatch, poison):
+    """The resident-Z route of the dense predictive pass with MORE THAN ONE chunk, at the smallest shape that takes it (agp_predict.hip
+    split_queries: n >= 2 NB, m >= NB, at least NB and at least n / 3 queries that are training times): a shuffled grid of 384 points,
+    six particles of which two are copies of a third (four distinct ones run), the first n training times plus eight future grid
+    points as queries, and a workspace that holds two particles per chunk — so the chain kernel advances the store's running sums
+    in the first chunk and the column counts are committed after the second.  n = 256 (Z formed whole), then n = 384 (one new tile
+    column).  Same checks as test_predictive_passes_keep_the_inverse_factor_resident; plain and under AGP_POISON=1."""
+    NB = 128
+    ts, xs = pkg.prior.synthetic_series(384, seed=35, shuffle=True)
+    SE = pkg.SquaredExponential
+    kernels = [SE(0.1, 0.8), SE(0.3, 1.0) + pkg.Linear(0.1, 0.3, 0.7), pkg.Periodic(0.7, 0.21, 1.1) * SE(0.5, 0.9),
+               pkg.GammaExponential(0.3, 1.2, 0.7)]
+    nodes = kernels + [kernels[2], kernels[2]]
+    nz = np.array([0.05, 0.02, 0.08, 0.03, 0.08, 0.08])
+    grid = np.sort(ts); h = grid[1] - grid[0]
+    fut = grid[-1] + h * np.arange(1, 9)
+    monkeypatch.setenv("AGP_POISON", poison)
+    a = pkg.GPEngine(0); b = pkg.GPEngine(0)
+    monkeypatch.delenv("AGP_POISON")
+    try:
+        a.set_data(ts, xs); b.set_data(ts, xs)
+        b.set_factor_cache(False)
+        for n in (256, 384):
+            tq = np.concatenate([ts[:n], fut])
+            # the joint matrix keeps the eight future points: nt1 + 1 tile rows, and Z = L11^-T over the nt1 training tile rows
+            nt1 = n // NB; nt = nt1 + 1
+            stride_a = nt * (nt + 1) // 2 * NB * NB; stride_z = nt1 * (nt1 + 1) // 2 * NB * NB
+            for e in (a, b):
+                e.set_workspace_limit(2 * (stride_a + stride_z) * 8)
+            a.logpdf_batch_extend(nodes, nz, n=n, check=False)
+            r0 = a.predict_reuse_stats()["reused"]; f0 = a.poison_stats()["fills"]
+            m1, v1, _, i1 = a.predict_batch(nodes, nz, tq, n=n, check=False)
+            assert a.predict_reuse_stats()["reused"] > r0
+            if poison == "1":
+                assert a.poison_stats()["fills"] > f0 and a.poison_stats()["bytes"] > 0
+            m2, v2, _, i2 = b.predict_batch(nodes, nz, tq, n=n, check=False)
+            assert b.predict_reuse_stats()["reused"] == 0 and np.array_equal(i1, i2) and (i1 == 0).all()
+            sc = np.maximum(1.0, np.abs(m2).max(axis=1))[:, None]
+            em = (np.abs(m1 - m2) / sc).max(); ev = (np.abs(v1 - v2) / np.maximum(1.0, v2)).max()
+            print(f"n={n} poison={poison}: mean err {em:.3e} var err {ev:.3e}")
+            assert em <= 1e-11 and ev <= 1e-11
+            # ... and once more under the same limit: everything resident now, nothing to add (n is a multiple of the tile edge)
+            m3, v3, _, i3 = a.predict_batch(nodes, nz, tq, n=n, check=False)
+            assert np.array_equal(i1, i3) and same(m1, m3) and same(v1, v3)
+    finally:
+        a.close(); b.close()
+
+
 @pytest.mark.parametrize("irregular", [False, True])
 def test_small_series_prebuilt_tiles_and_append_across_the_bound(pkg, irregular):
     """A resident series of at most two tile rows (the reference's tutorial sizes, docs/src/tutorials/assets: 135-442 points): the
