@@ -411,6 +411,33 @@ struct SeriesProbaArgs : SeriesArgs {
   double* out_terms;         // [out_off[P]] or null: the per-point (prequential) terms
 };
 
+// Sampling twin (k_series_predict_sample, agp_predict_sample_series_batch): the held-out twin's arguments (y_pred and out_terms
+// unused: the query rows' right-hand side is 0) and the read-out of the query rows of the joint factor — samples, component means
+// and covariances in the raw space of every series' own transform.
+struct SeriesSampleArgs : SeriesProbaArgs {
+  const double* y_intercept;         // [S]
+  long long R;                       // samples per series
+  const unsigned long long* seeds;   // [S] Philox key (seeds[s], 0) of series s
+  const double* zin;                 // [R q_off[S]] the caller's normals in out_x's layout, or null: Philox4x64-10 + ndtri
+  const long long* smp_off;          // [P + 1] particle p's samples: smp[smp_off[p] .. smp_off[p + 1]), ascending
+  const int32_t* smp;                // [samples of all series] index j in [0, R) inside the particle's series
+  double* out_x;                     // [R q_off[S]] series s at R q_off[s], sample j at + j m_s
+  double* out_mean;                  // [out_off[P]] or null
+  const long long* cov_off;          // [P + 1] particle p's m_s x m_s block in out_cov
+  double* out_cov;                   // [cov_off[P]] or null
+};
+// The read-out behind it (k_series_sample_fill): series s's whole block of out_x becomes NaN when one of its particles
+// plist[pl_off[s] ..] has a non-zero info word.
+struct SeriesSampleFillArgs {
+  int S;
+  long long R;
+  const long long* q_off;    // [S + 1]
+  const long long* pl_off;   // [S + 1]
+  const int32_t* plist;      // [P]
+  const int32_t* info;       // [P] the kernel's out_info (written for every particle of a series with query points)
+  double* out_x;
+};
+
 // The mixture read-out of agp_predict_logpdf_series_batch (k_series_mix_logp, agp_series_quantile_kernel.hpp): series s's particles
 // plist[pl_off[s] ..] (ascending caller index) with the weights w[w_off[s] + j] — quant_plan's lists, as SeriesQuantArgs reads them.
 struct SeriesMixLogpArgs {

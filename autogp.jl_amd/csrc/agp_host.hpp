@@ -759,6 +759,9 @@ int predict_mixture_cov(agp_ctx* c, const PredQuery& q, const Particles& pp, con
 
 // the mixture weights of agp_predict_quantile_batch / agp_predict_sample_batch (agp_quantile.hip): finite, >= 0, summing to 1
 int check_weights(agp_ctx* c, int32_t P, const double* w);
+// the components of agp_predict_sample_batch's S samples under `seed` (agp_sample.hip; agp_predict_sample_series_batch draws every
+// series' with it): comp[s] = the inverse CDF of the cumulative weights w[0 .. P) at the uniform of word 0 of Philox block (s, 0, 0, 0)
+void draw_components(int64_t S, int32_t P, const double* w, uint64_t seed, std::vector<int32_t>& comp);
 
 hipError_t run_factor_extend(hipStream_t st, CholArgs ca, int dcov, bool split_diag, int i0min, int nfac = -1);
 int extend_impl(agp_ctx* c, int64_t n, const Particles& pp, double* out_lp, int32_t* out_info, double* d_out_caller = nullptr,

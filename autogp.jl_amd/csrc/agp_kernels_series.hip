@@ -11,7 +11,8 @@ hipError_t kernels_init_series() {
                        reinterpret_cast<const void*>(&k_series_logpdf_grad<4, 16>), reinterpret_cast<const void*>(&k_series_logpdf_grad<4, 64>),
                        reinterpret_cast<const void*>(&k_series_logpdf_grad<8, 64>),
                        reinterpret_cast<const void*>(&k_series_predict<4>), reinterpret_cast<const void*>(&k_series_predict<8>),
-                       reinterpret_cast<const void*>(&k_series_predict_logpdf<4>), reinterpret_cast<const void*>(&k_series_predict_logpdf<8>)};
+                       reinterpret_cast<const void*>(&k_series_predict_logpdf<4>), reinterpret_cast<const void*>(&k_series_predict_logpdf<8>),
+                       reinterpret_cast<const void*>(&k_series_predict_sample<4>), reinterpret_cast<const void*>(&k_series_predict_sample<8>)};
   for (const void* f : fns) {
     hipFuncAttributes fa;
     hipError_t e = hipFuncGetAttributes(&fa, f);
@@ -51,6 +52,20 @@ hipError_t launch_series_predict_logpdf(hipStream_t st, const SeriesProbaArgs& s
   if (lds_bytes > (size_t)SERIES_LDS_BYTES) return hipErrorInvalidValue;
   if (depth <= 4) hipLaunchKernelGGL(k_series_predict_logpdf<4>, dim3(grid), dim3(256), lds_bytes, st, sa);
   else hipLaunchKernelGGL(k_series_predict_logpdf<8>, dim3(grid), dim3(256), lds_bytes, st, sa);
+  return hipGetLastError();
+}
+
+hipError_t launch_series_predict_sample(hipStream_t st, const SeriesSampleArgs& sa, int grid, int depth, size_t lds_bytes) {
+  if (grid <= 0) return hipSuccess;
+  if (lds_bytes > (size_t)SERIES_LDS_BYTES) return hipErrorInvalidValue;
+  if (depth <= 4) hipLaunchKernelGGL(k_series_predict_sample<4>, dim3(grid), dim3(256), lds_bytes, st, sa);
+  else hipLaunchKernelGGL(k_series_predict_sample<8>, dim3(grid), dim3(256), lds_bytes, st, sa);
+  return hipGetLastError();
+}
+
+hipError_t launch_series_sample_fill(hipStream_t st, const SeriesSampleFillArgs& a) {
+  if (a.S <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_series_sample_fill, dim3(a.S), dim3(256), 0, st, a);
   return hipGetLastError();
 }
 

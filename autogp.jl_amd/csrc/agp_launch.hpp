@@ -79,7 +79,7 @@ void launch_lag_grad(hipStream_t st, int P, size_t lds, const GradArgs& ga);
 void launch_grad_finish(hipStream_t st, int P, const GradArgs& ga);
 
 // ---- agp_kernels_series.hip ------------------------------------------------------------------------------------------
-hipError_t kernels_init_series();   // raises the dynamic-LDS ceiling of k_series_logpdf / k_series_logpdf_grad / k_series_predict / k_series_predict_logpdf to the whole 160 KiB (once, agp_init)
+hipError_t kernels_init_series();   // raises the dynamic-LDS ceiling of k_series_logpdf / k_series_logpdf_grad / k_series_predict / k_series_predict_logpdf / k_series_predict_sample to the whole 160 KiB (once, agp_init)
 // small-matrix value kernel: one workgroup per entry of sa.wg (`grid` of them), evaluation-stack depth 4 / 8, lds_bytes = the largest
 // SeriesLds total of the launch's particles
 hipError_t launch_series_logpdf(hipStream_t st, const SeriesArgs& sa, int grid, int depth, size_t lds_bytes);
@@ -91,6 +91,9 @@ hipError_t launch_series_predict(hipStream_t st, const SeriesPredArgs& sa, int g
 // held-out twin (k_series_predict_logpdf): depth as for the value kernel, lds_bytes = the largest series_lds total of the launch's
 // particles at their JOINT lengths n_s + m_s
 hipError_t launch_series_predict_logpdf(hipStream_t st, const SeriesProbaArgs& sa, int grid, int depth, size_t lds_bytes);
+// sampling twin (k_series_predict_sample): as the held-out twin; k_series_sample_fill behind it, one workgroup per series
+hipError_t launch_series_predict_sample(hipStream_t st, const SeriesSampleArgs& sa, int grid, int depth, size_t lds_bytes);
+hipError_t launch_series_sample_fill(hipStream_t st, const SeriesSampleFillArgs& a);
 // its probe instantiation on caller matrices: workgroup b factors matrix b of `grid`, lds_bytes = series_lds(sa.n, 0, 0, 0).total doubles
 hipError_t launch_series_probe(hipStream_t st, const SeriesProbeArgs& sa, int grid, size_t lds_bytes);
 

@@ -5,8 +5,6 @@
 #include "agp_host.hpp"
 #include "agp_philox.hpp"
 
-namespace {
-
 // component of every sample: the caller's, or the inverse CDF of the cumulative weights (particle order, fp64) at the uniform of word 0
 // of block (s, 0, 0, 0): the first p with u < cum[p] (a weight-0 particle never raises cum, so it is never first), and the last
 // particle of positive weight when rounding leaves u >= cum[P - 1]
@@ -25,8 +23,6 @@ void draw_components(int64_t S, int32_t P, const double* w, uint64_t seed, std::
     comp[(size_t)s] = it == cum.end() ? last : (int32_t)(it - cum.begin());
   }
 }
-
-}  // namespace
 
 extern "C" {
 

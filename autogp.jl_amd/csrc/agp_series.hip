@@ -7,6 +7,8 @@
 //                                      the same stream: quantiles and marginal moments of every series' own mixture
 //   agp_predict_logpdf_series_batch    k_series_predict_logpdf: the value kernel on the joint points, the query rows' partials read out —
 //                                      the log-density of every series' held-out values; k_series_mix_logp behind it for the mixtures
+//   agp_predict_sample_series_batch    k_series_predict_sample: the same joint factorisation with a zero query right-hand side, the query
+//                                      rows read out as samples, component means and covariances; k_series_sample_fill behind it
 // Each entry is one function, read top to bottom, over the stages they share (one SeriesCall carries what a stage leaves for the next):
 //   checks          series_check_sizes, series_check_pointers, series_check_layout (the entry's own pointer checks between them)
 //   series_classes  compile, per particle length / LDS need / evaluation stack, launch classes, workgroup order, out_off
@@ -207,7 +209,8 @@ int series_check_layout(agp_ctx* c, const SeriesCall& sc) {
   return AGP_OK;
 }
 
-// LDS bytes of particle p on a series of n points (held_out: the joint n_s + m_s points, the value kernel's map): the mode's own map
+// LDS bytes of particle p on a series of n points (held_out — the held-out and the sampling entry —: the joint n_s + m_s points, the
+// value kernel's map): the mode's own map
 size_t series_need(SeriesMode mode, const Batch& bt, int p, int n) {
   const ProgHdr& h = bt.hdr[(size_t)p];
   const int m_total = mode == SeriesMode::gradient ? series_grad_lds(n, h.n_ops, h.n_prm, h.n_cp, bt.ghdr[(size_t)p].n_ops, bt.ghdr[(size_t)p].n_prm).total
@@ -405,7 +408,7 @@ void series_copy_values(const SeriesCall& sc, double* out_logpdf, int32_t* out_i
 }
 
 // agp_get_timing: out[0] = out[2] = the value kernels of the call (covariance, factorisation, solve and value are one kernel);
-// out[4] = the band's three read-out kernels, the held-out entry's mixture read-out (0 in the other entries)
+// out[4] = the band's three read-out kernels, the held-out entry's mixture read-out, the sampling entry's NaN fill (0 in the others)
 int series_timing(agp_ctx* c, const SeriesCall& sc, float readout_ms = 0.f) {
   if (!sc.prof) return AGP_OK;
   float ms = 0.f;
@@ -729,6 +732,186 @@ int predict_logpdf_series(agp_ctx* c, SeriesCall& sc, const SeriesProbaOut& po, 
   return series_timing(c, sc, readout_ms);
 }
 
+// The sampling side of agp_predict_sample_series_batch: transforms, mixture weights, the draws, and the outputs beside info.
+struct SeriesSampleOut {
+  const double* y_slope;       // [S] or null (1)
+  const double* y_intercept;   // [S] or null (0)
+  const double* weights;       // [P] particle p's weight inside its series' mixture
+  int64_t R;                   // samples per series
+  const uint64_t* seeds;       // [S]; may be null when both component and z are given (or R == 0)
+  const int32_t* component;    // [S R] global particle indices, or null: drawn
+  const double* z;             // [R q_off[S]] or null: drawn
+  double* x;                   // [R q_off[S]]
+  int32_t* out_component;      // [S R] or null
+  double* mean; int64_t* out_off;      // [out_off[P]], [P + 1]; mean nullable
+  double* cov; int64_t* cov_off;       // [cov_off[P]], [P + 1]; cov nullable
+};
+
+// Samples of every series' mixture and the mixtures' components: the held-out entry's factorisation with a zero query right-hand
+// side, the query rows read out in the same launches, the NaN fill of failed series behind them on the same stream.
+int predict_sample_series(agp_ctx* c, SeriesCall& sc, const SeriesSampleOut& so, int32_t* out_info) {
+  const int P = sc.pp.P;
+  const int32_t S = sc.S;
+  const int64_t R = so.R;
+  char buf[256];
+  STAGE(series_check_sizes(c, sc));
+  if (R < 0) return fail(c, AGP_ERR_ARG, "negative number of samples (R)");
+  if (P == 0 && (S == 0 || R == 0)) return AGP_OK;
+  if (P == 0) return fail(c, AGP_ERR_ARG, "series 0 has no particles to sample from");
+  STAGE(series_check_pointers(c, sc, out_info != nullptr));
+  if (!sc.q_off || !sc.ts_pred) return fail(c, AGP_ERR_ARG, "null pointer argument (q_off or ts_pred)");
+  if ((so.mean && !so.out_off) || (so.cov && !so.cov_off))
+    return fail(c, AGP_ERR_ARG, "null pointer argument (out_off with out_mean, cov_off with out_cov)");
+  STAGE(series_check_layout(c, sc));
+  const size_t Q = S > 0 ? (size_t)sc.q_off[S] : 0;
+  if ((int64_t)Q >= ((int64_t)1 << 31) || (Q > 0 && R > (((int64_t)1 << 31) - 1) / (int64_t)Q))
+    return fail(c, AGP_ERR_ARG, "R * q_off[S] too large (2^31 or more)");
+  const size_t nx = (size_t)R * Q;
+  if (nx > 0 && !so.x) return fail(c, AGP_ERR_ARG, "null pointer argument (out_x)");
+  if (R > 0 && !so.seeds && (!so.component || (!so.z && Q > 0))) return fail(c, AGP_ERR_ARG, "null pointer argument (seeds)");
+  std::vector<double> tr(2 * (size_t)S);      // [slope (S) | intercept (S)]
+  for (int32_t s = 0; s < S; ++s) {
+    const long long n = sc.pt_off[s + 1] - sc.pt_off[s], m = sc.q_off[s + 1] - sc.q_off[s];
+    if (m > 0 && n + m > AGP_SERIES_MAX_N) {
+      snprintf(buf, sizeof buf, "series %d has %lld training and %lld query points, together more than AGP_SERIES_MAX_N (%d)", (int)s, n, m,
+               AGP_SERIES_MAX_N);
+      return fail(c, AGP_ERR_ARG, buf);
+    }
+    tr[(size_t)s] = so.y_slope ? so.y_slope[s] : 1.0;
+    tr[(size_t)S + s] = so.y_intercept ? so.y_intercept[s] : 0.0;
+    if (const int rc = check_y_transform(c, tr[(size_t)s], tr[(size_t)S + s])) return fail_series(c, rc, s);
+    if (so.z)
+      for (long long k = 0; k < R * m; ++k)
+        if (!std::isfinite(so.z[R * sc.q_off[s] + k])) {
+          snprintf(buf, sizeof buf, "series %d: z of sample %lld, point %lld is not finite", (int)s, k / m, k % m);
+          return fail(c, AGP_ERR_ARG, buf);
+        }
+  }
+  QuantPlan qp;      // the band entry's lists and weight checks (no quantiles, no rows read)
+  {
+    const SeriesQuantOut qo{so.weights, nullptr, nullptr, nullptr, 0, 0.0, 0, nullptr, nullptr, nullptr, nullptr, nullptr};
+    STAGE(quant_plan(c, S, P, sc.series, sc.q_off, qo, qp));
+  }
+  const long long* pl_off = qp.tab.data();
+  const long long* w_off = pl_off + (size_t)S + 1;
+  // the component of every sample — the caller's, or drawn series by series as agp_predict_sample_batch draws under seeds[s] — and
+  // from them every particle's list of samples (CSR, ascending)
+  std::vector<int32_t> comp((size_t)S * (size_t)R), local;
+  for (int32_t s = 0; s < S && R > 0; ++s) {
+    const long long Ps = pl_off[s + 1] - pl_off[s];
+    if (Ps == 0) {
+      snprintf(buf, sizeof buf, "series %d has no particles to sample from", (int)s);
+      return fail(c, AGP_ERR_ARG, buf);
+    }
+    int32_t* cs = comp.data() + (size_t)s * (size_t)R;
+    if (so.component) {
+      for (int64_t j = 0; j < R; ++j) {
+        const int32_t g = so.component[(size_t)s * (size_t)R + (size_t)j];
+        if (g < 0 || g >= P || sc.series[g] != s) {
+          snprintf(buf, sizeof buf, "series %d: component %d of sample %lld is not a particle of the series", (int)s, (int)g, (long long)j);
+          return fail(c, AGP_ERR_ARG, buf);
+        }
+        if (!(so.weights[g] > 0.0)) {
+          snprintf(buf, sizeof buf, "series %d: component %d of sample %lld has weight 0", (int)s, (int)g, (long long)j);
+          return fail(c, AGP_ERR_ARG, buf);
+        }
+        cs[j] = g;
+      }
+    } else {
+      local.resize((size_t)R);
+      draw_components(R, (int32_t)Ps, qp.vals.data() + w_off[s], so.seeds[s], local);
+      for (int64_t j = 0; j < R; ++j) cs[j] = qp.plist[(size_t)(pl_off[s] + local[(size_t)j])];
+    }
+  }
+  std::vector<long long> ltab(2 * ((size_t)P + 1), 0);      // [smp_off (P + 1) | cov_off (P + 1)]
+  long long* smp_off = ltab.data();
+  long long* cov_off = smp_off + P + 1;
+  for (int32_t g : comp) ++smp_off[(size_t)g + 1];
+  for (int p = 0; p < P; ++p) smp_off[p + 1] += smp_off[p];
+  std::vector<int32_t> smp(comp.size());
+  {
+    std::vector<long long> at(smp_off, smp_off + P);
+    for (int32_t s = 0; s < S; ++s)
+      for (int64_t j = 0; j < R; ++j) smp[(size_t)at[(size_t)comp[(size_t)s * (size_t)R + (size_t)j]]++] = (int32_t)j;
+  }
+  STAGE(series_classes(c, sc, SeriesMode::held_out));
+  for (int p = 0; p < P; ++p) cov_off[p + 1] = cov_off[p] + sc.nq[(size_t)p] * sc.nq[(size_t)p];
+  // (no check is left to fail, nothing is launched yet)
+  if (so.out_off) std::copy(sc.ooff.begin(), sc.ooff.end(), so.out_off);
+  if (so.cov_off) std::copy(cov_off, cov_off + P + 1, so.cov_off);
+  if (so.out_component) std::copy(comp.begin(), comp.end(), so.out_component);
+  if (sc.wg.empty()) { series_zero_values(sc, nullptr, out_info); return AGP_OK; }      // no series has a query point: nothing to write
+  STAGE(series_stage(c, sc));
+  Slot* s = sc.s;
+  // sq_w = [slope (S) | intercept (S)]; sq_tab = [pl_off (S + 1) | seeds (S) | smp_off | cov_off (P + 1 each) | plist (P) | smp (S R)];
+  // the samples in smp_x, the caller's normals in smp_zin, the components in pred_mean / pred_cov
+  const size_t S1 = (size_t)S + 1, n_mean = so.mean ? sc.n_out() : 0, n_cov = so.cov ? (size_t)cov_off[P] : 0;
+  const size_t o_seed = sizeof(long long) * S1, o_ltab = o_seed + sizeof(uint64_t) * (size_t)S,
+               o_plist = o_ltab + sizeof(long long) * ltab.size(), o_smp = o_plist + sizeof(int32_t) * (size_t)P;
+  const std::vector<uint64_t> seeds0((size_t)S, 0);
+  HIPCHK(c, s->sq_w.ensure(sizeof(double) * tr.size()));
+  HIPCHK(c, s->sq_tab.ensure(o_smp + sizeof(int32_t) * std::max<size_t>(1, smp.size())));
+  HIPCHK(c, s->smp_x.ensure(sizeof(double) * std::max<size_t>(1, nx)));
+  if (so.cov) HIPCHK(c, s->pred_cov.ensure(sizeof(double) * std::max<size_t>(1, n_cov)));
+  sc.up.add(s->sq_w.p, tr.data(), sizeof(double) * tr.size());
+  sc.up.add(s->sq_tab.p, pl_off, sizeof(long long) * S1);
+  sc.up.add(s->sq_tab.as<char>() + o_seed, so.seeds ? so.seeds : seeds0.data(), sizeof(uint64_t) * (size_t)S);
+  sc.up.add(s->sq_tab.as<char>() + o_ltab, ltab.data(), sizeof(long long) * ltab.size());
+  sc.up.add(s->sq_tab.as<char>() + o_plist, qp.plist.data(), sizeof(int32_t) * (size_t)P);
+  sc.up.add(s->sq_tab.as<char>() + o_smp, smp.data(), sizeof(int32_t) * smp.size());
+  if (so.z && nx > 0) {
+    HIPCHK(c, s->smp_zin.ensure(sizeof(double) * nx));
+    sc.up.add(s->smp_zin.p, so.z, sizeof(double) * nx);
+  }
+  HIPCHK(c, sc.up.flush(s->h_stage, s->up_blob, sc.st));
+  SeriesSampleArgs pa = {};
+  static_cast<SeriesArgs&>(pa) = sc.sa;
+  pa.q_off = sc.in_map<const long long>(sc.o_qoff);
+  pa.out_off = sc.in_map<const long long>(sc.o_ooff);
+  pa.ts_pred = s->tt.as<double>() + 2 * sc.npts; pa.noise_pred = s->noise_pred.as<double>();
+  pa.y_slope = s->sq_w.as<double>(); pa.y_intercept = s->sq_w.as<double>() + S;
+  pa.R = R;
+  pa.seeds = reinterpret_cast<const unsigned long long*>(s->sq_tab.as<char>() + o_seed);
+  pa.zin = so.z && nx > 0 ? s->smp_zin.as<double>() : nullptr;
+  pa.smp_off = reinterpret_cast<const long long*>(s->sq_tab.as<char>() + o_ltab);
+  pa.cov_off = pa.smp_off + P + 1;
+  pa.smp = reinterpret_cast<const int32_t*>(s->sq_tab.as<char>() + o_smp);
+  pa.out_x = s->smp_x.as<double>();
+  pa.out_mean = so.mean ? s->pred_mean.as<double>() : nullptr;
+  pa.out_cov = so.cov ? s->pred_cov.as<double>() : nullptr;
+  STAGE(series_launch(c, sc, [&](const int32_t* wg, int grid, int d, size_t lds) {
+    pa.wg = wg;
+    return launch_series_predict_sample(sc.st, pa, grid, d == 0 ? 4 : 8, lds);
+  }));
+  if (nx > 0) {
+    SeriesSampleFillArgs fa = {};
+    fa.S = S; fa.R = R;
+    fa.q_off = pa.q_off;
+    fa.pl_off = s->sq_tab.as<long long>();
+    fa.plist = reinterpret_cast<const int32_t*>(s->sq_tab.as<char>() + o_plist);
+    fa.info = sc.sa.out_info;
+    fa.out_x = pa.out_x;
+    HIPCHK(c, launch_series_sample_fill(sc.st, fa));
+  }
+  if (sc.prof) HIPCHK(c, hipEventRecord(sc.ev[2], sc.st));
+  // h_out = [logpdf | info | x (R q_off[S]) | mean (out_off[P]) | cov (cov_off[P])], the last two when wanted
+  const size_t o_x = sc.o_own(), o_mean = o_x + sizeof(double) * nx, o_cov = o_mean + sizeof(double) * n_mean;
+  STAGE(series_fetch_values(c, sc, o_cov + sizeof(double) * n_cov));
+  char* ho = static_cast<char*>(s->h_out.p);
+  if (nx > 0) HIPCHK(c, hipMemcpyAsync(ho + o_x, s->smp_x.p, sizeof(double) * nx, hipMemcpyDeviceToHost, sc.st));
+  if (n_mean > 0) HIPCHK(c, hipMemcpyAsync(ho + o_mean, s->pred_mean.p, sizeof(double) * n_mean, hipMemcpyDeviceToHost, sc.st));
+  if (n_cov > 0) HIPCHK(c, hipMemcpyAsync(ho + o_cov, s->pred_cov.p, sizeof(double) * n_cov, hipMemcpyDeviceToHost, sc.st));
+  HIPCHK(c, hipStreamSynchronize(sc.st));
+  series_copy_values(sc, nullptr, out_info);      // (no query point: length 0 here, so info 0)
+  // every series with query points has particles, every sample one of them as its component: the whole of x was written
+  if (nx > 0) std::memcpy(so.x, ho + o_x, sizeof(double) * nx);
+  if (n_mean > 0) std::memcpy(so.mean, ho + o_mean, sizeof(double) * n_mean);
+  if (n_cov > 0) std::memcpy(so.cov, ho + o_cov, sizeof(double) * n_cov);
+  float readout_ms = 0.f;
+  if (sc.prof) HIPCHK(c, hipEventElapsedTime(&readout_ms, sc.ev[1], sc.ev[2]));
+  return series_timing(c, sc, readout_ms);
+}
+
 #undef STAGE
 
 // agp_debug_series_factor: P caller matrices of one size through stages 4 and 5 of the value kernel (its probe instantiation).
@@ -838,6 +1021,20 @@ int agp_predict_logpdf_series_batch(agp_ctx* c, int32_t S, const int64_t* pt_off
     SeriesCall sc{S, pt_off, ts, xs, {P, op_off, ops, prm_off, prm, noise, noise_pred}, series, q_off, ts_pred};
     const SeriesProbaOut po{y_pred, y_slope, weights, out_terms, out_off, out_series_logp};
     return predict_logpdf_series(c, sc, po, out_logpdf, out_info);
+  });
+}
+
+int agp_predict_sample_series_batch(agp_ctx* c, int32_t S, const int64_t* pt_off, const double* ts, const double* xs,
+                                    const int64_t* q_off, const double* ts_pred, int32_t P, const int32_t* series, const int32_t* op_off,
+                                    const uint8_t* ops, const int32_t* prm_off, const double* prm, const double* noise,
+                                    const double* noise_pred, const double* y_slope, const double* y_intercept, const double* weights,
+                                    int64_t R, const uint64_t* seeds, const int32_t* component, const double* z, double* out_x,
+                                    int32_t* out_component, double* out_mean, int64_t* out_off, double* out_cov, int64_t* cov_off,
+                                    int32_t* out_info) {
+  return abi_guard(c, [&] {
+    SeriesCall sc{S, pt_off, ts, xs, {P, op_off, ops, prm_off, prm, noise, noise_pred}, series, q_off, ts_pred};
+    const SeriesSampleOut so{y_slope, y_intercept, weights, R, seeds, component, z, out_x, out_component, out_mean, out_off, out_cov, cov_off};
+    return predict_sample_series(c, sc, so, out_info);
   });
 }
 

@@ -73,6 +73,13 @@
 // Stages 2, 4 and 5 are the value kernel's statements over N points.  out_info[p] = the first bad pivot of the joint factor (1 .. n:
 // K11; n + k: leading minor k of the predictive covariance), NaN then in out_lp[p] and the particle's whole terms block.  n = 0 (the
 // prior predictive) takes the same code; m = 0 is never launched (the host answers 0).
+//
+// k_series_predict_sample<D> (agp_predict_sample_series_batch) is the held-out twin with the query rows' right-hand side 0 (the
+// branches of the joint points are shared: the trait JOINT of series_body) and another read-out: after stage 5 the query rows of the
+// packed blocks are [L21 L22] with L22 = chol(Sigma*) and avec[0, n) = L11^-1 xs, so the component mean mu* = L21 a, the component
+// covariance Sigma* = L22 L22' and the samples mu* + L22 z of predict_mvn / rand are read out of rows [n, N) in the same workgroup and
+// the value kernel's LDS map (series_sample_readout); k_series_sample_fill behind the launches turns the block of a series with a
+// failed particle into NaN.
 #pragma once
 #include <type_traits>
 #include "agp_common.hpp"
@@ -80,6 +87,8 @@
 #include "agp_cov_kernel.hpp"
 #include "agp_lds_chol.hpp"         // mfma, blk_idx, lds_chol_steps
 #include "agp_grad_elements.hpp"    // grad_elements, RegTape, ScratchAcc
+#include "agp_ndtri.hpp"
+#include "agp_philox.hpp"
 
 namespace agp {
 
@@ -237,6 +246,144 @@ __device__ __forceinline__ void series_prior_predict(const SeriesPredArgs& a, in
                            a.out_mean + a.out_off[p], a.out_var + a.out_off[p]);
 }
 
+// The read-out of the sampling twin: from the joint factor as stage 5 leaves it (rows [ntr, ntr + m) of the packed blocks are
+// [L21 L22], L22 = chol(Sigma*); a = L11^-1 xs in avec[0, ntr)), in this order:
+//   S1. mu*_i = sum_{k < ntr} L(ntr + i, k) a_k, one thread per query row, k ascending -> mu (LDS) and out_mean = (mu* - b) / slope;
+//   S2. the samples of this particle (its CSR list smp), 16 per wave and pass, groups round-robin over the waves, no workgroup barrier:
+//       x(i, j) = mu*_i + sum_k L22(i, k) sgn z_k(j) on v_mfma_f64_16x16x4 — the accumulator starts at mu*_i (the training columns
+//       contribute the same to every sample: S1's sum is not repeated per sample) and runs over the query columns in 16-blocks of the
+//       QUERY index, whatever ntr % 16 is.  Lane (j = l % 16, q = l / 16) feeds z of query points 16 kb + 4 q + s4 at step s4 — the
+//       four words of ONE Philox block (4 kb + q, j, 1, 0), none wasted — so the L operand runs over k in the same order:
+//       lane (i = l % 16, q) reads L22(16 rb + i, 16 kb + 4 q + s4).  Every element is one chain in a fixed order over k that involves
+//       no other sample: its bits do not depend on R or on which samples share a group.  The accumulators of up to six row blocks live
+//       in registers (statically indexed behind wave-uniform guards, as VT in series_predict_blocks), so z is formed once per block
+//       column for m <= 96 and twice above;
+//   S3. out_cov: per lower 16 x 16 block (rb, cb) of the query range, one wave, Sigma*(rb, cb) = sum_{k <= cb} L22(rb, k) L22(cb, k)'
+//       by an MFMA chain; elements on and below the diagonal are stored at (r, c) AND at (c, r): both triangles, exactly symmetric.
+// L22 is read through ONE accessor on the joint blocks (row / column ntr + i, masked with a select above the diagonal and past m: what
+// sits there — zeros, identity padding or poison — never reaches an operand); no query-aligned copy is staged (it would not fit beside
+// the blocks at the cap).  On a bad pivot the particle's mean and covariance blocks are NaN and no sample is drawn.
+__device__ __forceinline__ void series_sample_readout(const SeriesSampleArgs& a, int p, const double* sm, const double* avec, double* mu,
+                                                      bool isbad, int ntr, int m) {
+  constexpr int RBP = 6;      // row blocks per pass of S2 (the cap has 11)
+  const int tid = threadIdx.x, l = tid & 63, w = tid >> 6, l15 = l & 15, lq = l >> 4;
+  const int sidx = a.series[p];
+  const long long q0 = a.q_off[sidx];
+  const double slope = a.y_slope[sidx], icpt = a.y_intercept[sidx];
+  const double nanv = __builtin_nan("");
+  // ---- S1 ----
+  if (tid < m) {
+    const int row = ntr + tid, rb = row >> 4, r = row & 15;
+    double s = 0.0;
+    for (int k = 0; k < ntr; ++k) s = fma(sm[blk_idx(rb, k >> 4) * 256 + (k & 15) * 16 + r], avec[k], s);
+    mu[tid] = s;
+    if (a.out_mean != nullptr) a.out_mean[a.out_off[p] + tid] = isbad ? nanv : (s - icpt) / slope;
+  }
+  if (isbad) {
+    if (a.out_cov != nullptr)
+      for (int i = tid; i < m * m; i += 256) a.out_cov[a.cov_off[p] + i] = nanv;
+    return;
+  }
+  __syncthreads();
+  auto Lq = [&](int ir, int ic) -> double {      // L22(ir, ic); exactly 0 above the diagonal and for rows past m
+    const bool on = ic <= ir && ir < m;
+    const int jr = ntr + (on ? ir : 0), jc = ntr + (on ? ic : 0);
+    const double v = sm[blk_idx(jr >> 4, jc >> 4) * 256 + (jc & 15) * 16 + (jr & 15)];
+    return on ? v : 0.0;
+  };
+  const int nqb = (m + 15) >> 4;
+  // ---- S2 ----
+  {
+    const long long s0 = a.smp_off[p];
+    const int cnt = (int)(a.smp_off[p + 1] - s0);
+    const double sgn = slope > 0.0 ? 1.0 : -1.0;
+    const unsigned long long seed = a.seeds[sidx];
+    double* ox = a.out_x + a.R * q0;
+    for (int g = w; g * 16 < cnt; g += 4) {
+      const int js = g * 16 + l15;
+      const bool live = js < cnt;
+      const long long j = live ? (long long)a.smp[s0 + js] : 0;
+      // (row blocks in passes of RBP: the accumulators of one pass and the Philox state share the register budget; a series with
+      // more than RBP query blocks forms z a second time for the later rows — every element's chain over k stays what it was)
+      for (int rb0 = 0; rb0 < nqb; rb0 += RBP) {
+        d4 acc[RBP];
+#pragma unroll
+        for (int u = 0; u < RBP; ++u)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int i = (rb0 + u) * 16 + 4 * r + lq;
+            acc[u][r] = i < m ? mu[i] : 0.0;
+          }
+        const int kend = rb0 + RBP < nqb ? rb0 + RBP : nqb;
+        for (int kb = 0; kb < kend; ++kb) {
+          double zz[4];
+          if (a.zin != nullptr) {
+#pragma unroll
+            for (int s4 = 0; s4 < 4; ++s4) {
+              const int i = kb * 16 + 4 * lq + s4;
+              zz[s4] = (live && i < m) ? sgn * a.zin[a.R * q0 + j * m + i] : 0.0;
+            }
+          } else {
+            const Philox4 b = philox4x64_10((uint64_t)(kb * 4 + lq), (uint64_t)j, 1, 0, seed, 0);
+#pragma unroll
+            for (int s4 = 0; s4 < 4; ++s4) {
+              const int i = kb * 16 + 4 * lq + s4;
+              zz[s4] = (live && i < m) ? sgn * ndtri(philox_uniform(b.w[s4])) : 0.0;
+            }
+          }
+#pragma unroll
+          for (int u = 0; u < RBP; ++u)
+            if (rb0 + u >= kb && rb0 + u < nqb) {
+#pragma unroll
+              for (int s4 = 0; s4 < 4; ++s4) acc[u] = mfma(Lq((rb0 + u) * 16 + l15, kb * 16 + 4 * lq + s4), zz[s4], acc[u]);
+            }
+        }
+        // accumulator (lane, reg r) of row block rb: query row 16 rb + 4 r + l / 16 of sample l % 16
+#pragma unroll
+        for (int u = 0; u < RBP; ++u)
+          if (rb0 + u < nqb) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const int i = (rb0 + u) * 16 + 4 * r + lq;
+              if (live && i < m) ox[j * m + i] = (acc[u][r] - icpt) / slope;
+            }
+          }
+      }
+    }
+  }
+  // ---- S3 ----
+  if (a.out_cov != nullptr) {
+    double* oc = a.out_cov + a.cov_off[p];
+    const double s2 = slope * slope;
+    const int nblk = nqb * (nqb + 1) / 2;
+    for (int b = w; b < nblk; b += 4) {
+      int rb, cb;
+      series_blk_rc(b, rb, cb);
+      d4 x = d4{0.0, 0.0, 0.0, 0.0};
+      for (int kb = 0; kb <= cb; ++kb) {
+        double fa[4], fb[4];
+#pragma unroll
+        for (int s4 = 0; s4 < 4; ++s4) {
+          const int k = kb * 16 + 4 * s4 + lq;
+          fa[s4] = Lq(cb * 16 + l15, k);
+          fb[s4] = Lq(rb * 16 + l15, k);
+        }
+#pragma unroll
+        for (int s4 = 0; s4 < 4; ++s4) x = mfma(fa[s4], fb[s4], x);
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int row = rb * 16 + l15, col = cb * 16 + 4 * r + lq;
+        if (row < m && col <= row) {
+          const double v = x[r] / s2;
+          oc[col * m + row] = v;
+          oc[row * m + col] = v;
+        }
+      }
+    }
+  }
+}
+
 // The body of every instantiation: stages 1-5 (value kernel, probe, gradient kernel, predictive kernel alike — the same statements),
 // with GS > 0 (gradient tape of GS nodes) the stages G1-G5 behind them, with SeriesPredArgs the stages P1-P2.
 template <int D, bool PROBE, int GS, class ArgsT>
@@ -244,11 +391,13 @@ __device__ __forceinline__ void series_body(const ArgsT& a, double* smem) {
   constexpr int E = 4;
   constexpr bool PRED = std::is_same_v<ArgsT, SeriesPredArgs>;
   constexpr bool PROBA = std::is_same_v<ArgsT, SeriesProbaArgs>;      // the held-out twin: n below is the JOINT length
+  constexpr bool SAMPLE = std::is_same_v<ArgsT, SeriesSampleArgs>;    // the sampling twin: the same, the query rows' right-hand side 0
+  constexpr bool JOINT = PROBA || SAMPLE;
   const int tid = threadIdx.x, l = tid & 63, w = tid >> 6, l15 = l & 15, lq = l >> 4;
   int p, n;
   long long o0 = 0;
-  [[maybe_unused]] int ntr = 0;            // PROBA: training points (rows [ntr, n) are the query rows)
-  [[maybe_unused]] long long q0 = 0;       // PROBA: the series' first query
+  [[maybe_unused]] int ntr = 0;            // JOINT: training points (rows [ntr, n) are the query rows)
+  [[maybe_unused]] long long q0 = 0;       // JOINT: the series' first query
   if constexpr (PROBE) {
     p = blockIdx.x;
     n = a.n;
@@ -257,7 +406,7 @@ __device__ __forceinline__ void series_body(const ArgsT& a, double* smem) {
     const int sidx = a.series[p];
     o0 = a.pt_off[sidx];
     n = (int)(a.pt_off[sidx + 1] - o0);
-    if constexpr (PROBA) {
+    if constexpr (JOINT) {
       q0 = a.q_off[sidx];
       const long long mq = a.q_off[sidx + 1] - q0;
       ntr = n;
@@ -309,12 +458,13 @@ __device__ __forceinline__ void series_body(const ArgsT& a, double* smem) {
     }
   } else {
     // ---- 1. inputs ----
-    if constexpr (PROBA) {
+    if constexpr (JOINT) {
       // the joint points: the series' times, then — directly behind them, no padding between — its query times; xs, then the held-out values
       if (tid < np) {
         const int k = tid < n ? tid : n - 1;
         tpt[tid] = k < ntr ? a.ts[o0 + k] : a.ts_pred[q0 + (k - ntr)];
-        rvec[tid] = tid < ntr ? a.xs[o0 + tid] : tid < n ? a.y_pred[q0 + (tid - ntr)] : 0.0;
+        if constexpr (SAMPLE) rvec[tid] = tid < ntr ? a.xs[o0 + tid] : 0.0;
+        else rvec[tid] = tid < ntr ? a.xs[o0 + tid] : tid < n ? a.y_pred[q0 + (tid - ntr)] : 0.0;
         avec[tid] = 0.0;
       }
     } else if (tid < np) {
@@ -336,8 +486,8 @@ __device__ __forceinline__ void series_body(const ArgsT& a, double* smem) {
     // ---- 3. K + noise I, lower block triangle; one block per wave and pass, lane (i = l%16, q = l/16) <-> elements (i, q + 4 e) ----
     {
       const double noise = a.noise[p];
-      [[maybe_unused]] double noise_q = 0.0;      // PROBA: the diagonal addend of the query rows
-      if constexpr (PROBA) noise_q = a.noise_pred[p];
+      [[maybe_unused]] double noise_q = 0.0;      // JOINT: the diagonal addend of the query rows
+      if constexpr (JOINT) noise_q = a.noise_pred[p];
       const int nblk = nb * (nb + 1) / 2;
       for (int b = w; b < nblk; b += 4) {
         int rb, cb;
@@ -356,7 +506,7 @@ __device__ __forceinline__ void series_body(const ArgsT& a, double* smem) {
         double* blk = sm + blk_idx(rb, cb) * 256;
 #pragma unroll
         for (int e = 0; e < E; ++e) {
-          if constexpr (PROBA) blk[64 * e + l] = cov_finalize(out[e], ri[e], ci[e], n, np, 0, ri[e] < ntr ? noise : noise_q);
+          if constexpr (JOINT) blk[64 * e + l] = cov_finalize(out[e], ri[e], ci[e], n, np, 0, ri[e] < ntr ? noise : noise_q);
           else blk[64 * e + l] = cov_finalize(out[e], ri[e], ci[e], n, np, 0, noise);
         }
       }
@@ -370,13 +520,13 @@ __device__ __forceinline__ void series_body(const ArgsT& a, double* smem) {
   lds_chol_steps<0>(sm, Wl, rvec, avec, nb, nb, 64, np, 0, bad, tid);
 
   // ---- the value: 2 sum log L_ii (padding rows: log 1) and alpha'alpha, reduced in a fixed order
-  //      (PROBA: both over the query rows [ntr, n) alone — the conditional density of the held-out values) ----
-  [[maybe_unused]] double lgd = 0.0;      // PROBA: log L_kk of the thread's own row
+  //      (JOINT: both over the query rows [ntr, n) alone — the conditional density of the held-out values) ----
+  [[maybe_unused]] double lgd = 0.0;      // JOINT: log L_kk of the thread's own row
   {
     double ld = 0.0;
     if (tid < np) {
       const double dii = sm[blk_idx(tid >> 4, tid >> 4) * 256 + 17 * (tid & 15)];
-      if constexpr (PROBA) {
+      if constexpr (JOINT) {
         lgd = log(dii);
         ld = tid >= ntr ? 2.0 * lgd : 0.0;
       } else {
@@ -384,7 +534,7 @@ __device__ __forceinline__ void series_body(const ArgsT& a, double* smem) {
       }
     }
     Wl[tid] = ld;      // (the last inverse block has been consumed)
-    if constexpr (PROBA) {
+    if constexpr (JOINT) {
       if (tid == 0) rvec[0] = (double)bad;      // (wave 0 keeps the first bad pivot; rvec is dead)
     }
   }
@@ -392,7 +542,7 @@ __device__ __forceinline__ void series_body(const ArgsT& a, double* smem) {
   if (w == 0) {
     double ld = (Wl[l] + Wl[l + 64]) + (Wl[l + 128] + Wl[l + 192]);
     double ss = 0.0;
-    if constexpr (PROBA) {
+    if constexpr (JOINT) {
       for (int i = l; i < np; i += 64) ss = i >= ntr ? fma(avec[i], avec[i], ss) : ss;
     } else {
       for (int i = l; i < np; i += 64) ss = fma(avec[i], avec[i], ss);
@@ -401,13 +551,15 @@ __device__ __forceinline__ void series_body(const ArgsT& a, double* smem) {
     for (int off = 32; off > 0; off >>= 1) { ss += __shfl_xor(ss, off); ld += __shfl_xor(ld, off); }
     if (l == 0) {
       double lp;
-      if constexpr (PROBA) {      // m log 2 pi, and the Jacobian of the series' own transform: m log|slope|
+      if constexpr (JOINT) {      // m log 2 pi, and the Jacobian of the series' own transform: m log|slope|
         const double mq = (double)(n - ntr);
         lp = -0.5 * (mq * 1.8378770664093454835606594728112 + ld + ss) + mq * log(fabs(a.y_slope[a.series[p]]));
       } else {
         lp = -0.5 * ((double)n * 1.8378770664093454835606594728112 + ld + ss);
       }
-      a.out_lp[p] = bad != 0 ? __builtin_nan("") : lp;
+      // (the sampling twin has no density to report — its query right-hand side is 0 — and its entry never reads out_lp: without the
+      // store the two reductions above are dead code in that instantiation)
+      if constexpr (!SAMPLE) a.out_lp[p] = bad != 0 ? __builtin_nan("") : lp;
       a.out_info[p] = bad;
       if constexpr (PROBE) { a.out_part[2 * p] = ld; a.out_part[2 * p + 1] = ss; }
     }
@@ -425,6 +577,11 @@ __device__ __forceinline__ void series_body(const ArgsT& a, double* smem) {
       const double t = (-0.5 * fma(z, z, 1.8378770664093454835606594728112) - lgd) + log(fabs(a.y_slope[a.series[p]]));
       a.out_terms[a.out_off[p] + (tid - ntr)] = rvec[0] != 0.0 ? __builtin_nan("") : t;
     }
+  }
+
+  if constexpr (SAMPLE) {
+    // ================= sampling: rows [ntr, n) of the factor read out (tpt is dead: it takes mu*) =================
+    series_sample_readout(a, p, sm, avec, tpt, rvec[0] != 0.0, ntr, n - ntr);
   }
 
   if constexpr (PRED) {
@@ -626,6 +783,28 @@ template <int D>
 __global__ __launch_bounds__(256, 2) void k_series_predict_logpdf(SeriesProbaArgs a) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   series_body<D, false, 0>(a, smem);
+}
+
+// Samples, component mean and component covariance of one (series, particle) pair at the series' own query times by one workgroup:
+// the held-out twin's factorisation of the joint points, series_sample_readout behind it (agp_predict_sample_series_batch).
+template <int D>
+__global__ __launch_bounds__(256, 2) void k_series_predict_sample(SeriesSampleArgs a) {
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  series_body<D, false, 0>(a, smem);
+}
+
+// ... and behind those launches, on the same stream: one workgroup per series; a series with a failed particle (whatever its weight)
+// has no valid sample — its whole block of out_x becomes NaN.  Series without query points own nothing (and their particles' info
+// words were never written).
+__global__ __launch_bounds__(256) void k_series_sample_fill(SeriesSampleFillArgs a) {
+  const int s = blockIdx.x;
+  const long long q0 = a.q_off[s], m = a.q_off[s + 1] - q0;
+  if (m <= 0) return;
+  int bad = 0;
+  for (long long k = a.pl_off[s] + threadIdx.x; k < a.pl_off[s + 1]; k += 256) bad |= a.info[a.plist[k]] != 0 ? 1 : 0;
+  if (!__syncthreads_or(bad)) return;
+  double* ox = a.out_x + a.R * q0;
+  for (long long i = threadIdx.x; i < a.R * m; i += 256) ox[i] = __builtin_nan("");
 }
 
 // Posterior mean and marginal variance of one (series, particle) pair at the series' own query times by one workgroup, behind the

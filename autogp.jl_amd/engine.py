@@ -39,7 +39,7 @@ EXPORTED_SYMBOLS = [
     "agp_remove_data", "agp_get_remove_stats", "agp_set_remove_update", "agp_remove_data_multi",
     "agp_debug_factor_batch", "agp_logpdf_series_batch", "agp_debug_series_factor", "agp_logpdf_grad_series_batch",
     "agp_predict_series_batch", "agp_debug_remove_factor", "agp_predict_quantile_series_batch",
-    "agp_predict_logpdf_series_batch",
+    "agp_predict_logpdf_series_batch", "agp_predict_sample_series_batch",
 ]
 COMM_ID_BYTES = 128
 SERIES_MAX_N = 176      # AGP_SERIES_MAX_N of include/autogp_hip.h: the longest series of logpdf_series_batch
@@ -118,6 +118,10 @@ def load_library(path=None):
     lib.agp_predict_logpdf_series_batch.argtypes = [vp, C.c_int32, C.POINTER(C.c_int64), dp, dp, C.POINTER(C.c_int64), dp, dp, C.c_int32, ip,
                                                     ip, u8p, ip, dp, dp, dp, dp, dp, dp, dp, C.POINTER(C.c_int64), dp, ip]
     lib.agp_predict_logpdf_series_batch.restype = C.c_int
+    lib.agp_predict_sample_series_batch.argtypes = [vp, C.c_int32, C.POINTER(C.c_int64), dp, dp, C.POINTER(C.c_int64), dp, C.c_int32, ip, ip,
+                                                    u8p, ip, dp, dp, dp, dp, dp, dp, C.c_int64, C.POINTER(C.c_uint64), ip, dp, dp, ip,
+                                                    dp, C.POINTER(C.c_int64), dp, C.POINTER(C.c_int64), ip]
+    lib.agp_predict_sample_series_batch.restype = C.c_int
     lib.agp_logpdf_grad_batch.argtypes = [vp, C.c_int64, C.c_int32, ip, u8p, ip, dp, dp, dp, dp, dp, ip]
     lib.agp_logpdf_grad_batch.restype = C.c_int
     lib.agp_logpdf_grad.argtypes = [vp, C.c_int64, u8p, C.c_int32, dp, C.c_int32, C.c_double, dp, dp, dp, ip]
@@ -386,6 +390,7 @@ def pack_heldout(heldout, q_off, y_transforms=None):
 
 
 SeriesScores = collections.namedtuple("SeriesScores", "logpdf terms series_logp info")
+SeriesSamples = collections.namedtuple("SeriesSamples", "x component mean cov info")
 
 
 def check_remove_indexes(indexes, n_max):
@@ -679,6 +684,75 @@ class GPEngine:
         _raise_first_bad(info, check)
         cut = None if terms is None else [terms[out_off[p]:out_off[p + 1]] for p in range(P)]
         return SeriesScores(lp, cut, None if mix is None else mix[:S], info)
+
+    def predict_sample_series_batch(self, series, queries, nodes, noises, series_index, weights, n_samples, seeds=None, y_transforms=None,
+                                    noise_pred=None, component=None, z=None, want_moments=False, check=True, programs=None):
+        """agp_predict_sample_series_batch: sample paths of many short series in one fused launch — predict_sample_batch's twin for
+        callers that hold one model per short series, with predict_logpdf_series_batch's series / query / particle arguments and
+        statelessness (len(series[s]) + len(queries[s]) <= SERIES_MAX_N).  weights[p] is particle p's weight inside the mixture of
+        ITS series (pack_series_mixture); n_samples (R >= 0) samples are drawn per series, series s under seeds[s] exactly as
+        predict_sample_batch draws under that seed (seeds: one unsigned 64-bit integer per series; None: 0, 1, ..).  y_transforms:
+        one (slope, intercept) per series (scaled = slope * raw + intercept; None: (1, 0)); every output is in raw space.
+        component (S, R) of global particle indices and z (a list over the series of (m_s, R) arrays of normals) replace the draws.
+        Returns SeriesSamples(x, component, mean, cov, info): x a list over the series of (m_s, R) arrays, column j being sample j;
+        component (S, R); with want_moments mean / cov, lists over the PARTICLES of (m_s,) / (m_s, m_s) arrays — the components of
+        predict_mvn's mixture of every series — else None; info (P,).  A series with a failed particle is NaN in x (PosDefException
+        with check)."""
+        packed = series_call_args(series, nodes, noises, series_index, programs)
+        S, P, sidx = packed[0].shape[0] - 1, packed[4], packed[6]
+        if noise_pred is not None and np.ndim(noise_pred) == 0:
+            noise_pred = np.full(P, float(noise_pred))      # (a scalar serves every particle)
+        qpack = pack_queries(queries, S, noise_pred, P)
+        qo = qpack[0]
+        m_s = np.diff(qo)
+        R = int(n_samples)
+        slope = icpt = None
+        if y_transforms is not None:
+            yt = _f64(y_transforms)
+            if yt.shape != (S, 2):
+                raise ValueError(f"y_transforms has shape {yt.shape}, expected ({S}, 2): one (slope, intercept) per series")
+            slope, icpt = np.ascontiguousarray(yt[:, 0]), np.ascontiguousarray(yt[:, 1])
+        weights = _f64(weights)
+        if weights.shape != (P,):
+            raise ValueError(f"weights has shape {weights.shape}, expected ({P},)")
+        seeds = np.arange(S, dtype=np.uint64) if seeds is None else np.ascontiguousarray(np.asarray(seeds, dtype=np.uint64))
+        if seeds.shape != (S,):
+            raise ValueError(f"seeds has shape {seeds.shape}, expected ({S},): one per series")
+        Rp = max(R, 0)
+        if component is not None:
+            component = np.ascontiguousarray(np.asarray(component, dtype=np.int32))
+            if component.shape != (S, Rp):
+                raise ValueError(f"component has shape {component.shape}, expected ({S}, {Rp})")
+        if z is not None:
+            if len(z) != S:
+                raise ValueError(f"one array of normals per series required ({len(z)} for {S} series)")
+            parts = []
+            for s, zs in enumerate(z):
+                zs = np.asarray(zs, dtype=np.float64)
+                if zs.shape != (int(m_s[s]), Rp):
+                    raise ValueError(f"series {s}: z has shape {zs.shape}, expected ({int(m_s[s])}, {Rp})")
+                parts.append(zs.T.ravel())      # sample j is the column of m_s values at j * m_s
+            z = np.ascontiguousarray(np.concatenate(parts)) if parts else np.zeros(0)
+        in_range = [i for i in sidx if 0 <= i < S]      # (an index outside is the library's to report)
+        n_mean = int(sum(m_s[i] for i in in_range)); n_cov = int(sum(m_s[i] * m_s[i] for i in in_range))
+        x = np.empty(max(1, Rp * int(qo[-1]))); comp = np.zeros(max(1, S * Rp), dtype=np.int32)
+        info = np.zeros(max(1, P), dtype=np.int32)
+        mean = np.empty(max(1, n_mean)) if want_moments else None
+        cov = np.empty(max(1, n_cov)) if want_moments else None
+        out_off = np.zeros(P + 1, dtype=np.int64); cov_off = np.zeros(P + 1, dtype=np.int64)
+        i64 = C.POINTER(C.c_int64)
+        self._check(self._lib.agp_predict_sample_series_batch(
+            self._ctx, *_series_ctypes(packed, qpack), _dp(slope), _dp(icpt), _dp(weights), R,
+            (seeds if S else np.zeros(1, dtype=np.uint64)).ctypes.data_as(C.POINTER(C.c_uint64)), _ip(component),
+            _dp(z if z is None or z.size else np.zeros(1)), _dp(x), _ip(comp), _dp(mean), out_off.ctypes.data_as(i64), _dp(cov),
+            cov_off.ctypes.data_as(i64), _ip(info)))
+        info = info[:P]
+        _raise_first_bad(info, check)
+        xs_ = [x[Rp * qo[s]:Rp * qo[s + 1]].reshape(Rp, qo[s + 1] - qo[s]).T for s in range(S)]
+        if want_moments:
+            mean = [mean[out_off[p]:out_off[p + 1]] for p in range(P)]
+            cov = [cov[cov_off[p]:cov_off[p + 1]].reshape(len(mean[p]), len(mean[p])).T for p in range(P)]
+        return SeriesSamples(xs_, comp[:S * Rp].reshape(S, Rp), mean, cov, info)
 
     def logpdf_batch_extend(self, nodes, noises, n=None, check=True, programs=None):
         """agp_logpdf_batch_extend: like logpdf_batch, but the factors stay resident and a later call on a longer
@@ -1675,6 +1749,80 @@ def predict_mvn(engine, nodes, noises, log_weights, ts_pred, y_transform=(1.0, 0
     every particle's posterior predictive at ts_pred (already in the engine's time scale) in the RAW space of y_transform = (slope,
     intercept) (scaled = slope * raw + intercept), weighted by exp of Gen.normalize_weights(log_weights)."""
     return MixtureModel(engine, nodes, noises, log_weights, ts_pred, y_transform=y_transform, noise_pred=noise_pred)
+
+
+def predict_rand_series(engine, series, queries, nodes, noises, series_index, log_weights, n_samples, seeds, y_transforms=None,
+                        noise_pred=None):
+    """predict_rand for callers that hold one model per short series: particle p belongs to the model of series[series_index[p]],
+    whose mixture weighs it by the softmax of log_weights over THAT series' particles (pack_series_mixture); series s draws its
+    n_samples paths under seeds[s], as predict_rand does under that seed on the resident series; one call of
+    GPEngine.predict_sample_series_batch serves every series.  Returns one (m_s, n_samples) array per series, raw space.  Raises
+    PosDefException when a particle has no predictive."""
+    _, w = pack_series_mixture(series_index, len(series), log_weights=log_weights)
+    return engine.predict_sample_series_batch(series, queries, nodes, noises, series_index, w, n_samples, seeds=seeds,
+                                              y_transforms=y_transforms, noise_pred=noise_pred).x
+
+
+class SeriesMixtureModel(MixtureModel):
+    """predict_mvn_series' return value for one series: a MixtureModel of given components (mean / var / cov through
+    agp_mixture_moments) that also knows the short series it came from, so that logpdf, quantile and rand go through the
+    many-series entries instead of the resident series.  Built by from_series; an object made by from_components alone has no
+    series behind it, and its logpdf / quantile / rand raise NotImplementedError as the base class's do for a model built from moments."""
+
+    _series_model = None
+
+    @classmethod
+    def from_series(cls, engine, components, probs, ts, xs, queries, nodes, noises, log_weights, y_transform=None, noise_pred=None):
+        """components / probs as from_components; the rest is the one-series model the other routes are asked with: its (ts, xs),
+        query times, particles, their log-weights, the series' (slope, intercept) or None, noise_pred (None, scalar or per particle)"""
+        d = cls.from_components(components, probs, engine=engine)
+        d._series_model = (ts, xs, queries, list(nodes), noises, log_weights, y_transform, noise_pred)
+        return d
+
+    def _one(self):
+        if self._series_model is None:
+            raise NotImplementedError("logpdf / quantile / rand of a SeriesMixtureModel built from moments alone")
+        ts, xs, q, nodes, noises, lw, yt, npred = self._series_model
+        return ([(ts, xs)], [q], nodes, noises, np.zeros(len(nodes), dtype=np.int32), lw, None if yt is None else [yt], npred)
+
+    def logpdf(self, y):
+        series, queries, nodes, noises, sidx, lw, yts, npred = self._one()
+        return predict_proba_series(self._engine, series, queries, [y], nodes, noises, sidx, lw, y_transforms=yts,
+                                    noise_pred=npred)[0]["mixture_logp"]
+
+    def quantile(self, q, tol=1e-5, max_iter=10**6):
+        series, queries, nodes, noises, sidx, lw, yts, npred = self._one()
+        return predict_quantile_series(self._engine, series, queries, nodes, noises, sidx, lw, q, y_transforms=yts, noise_pred=npred,
+                                       tol=tol, max_iter=max_iter)[0]
+
+    def rand(self, n_samples=None, seed=0):
+        series, queries, nodes, noises, sidx, lw, yts, npred = self._one()
+        x = predict_rand_series(self._engine, series, queries, nodes, noises, sidx, lw, 1 if n_samples is None else n_samples, [seed],
+                                y_transforms=yts, noise_pred=npred)[0]
+        return x[:, 0].copy() if n_samples is None else x
+
+
+def predict_mvn_series(engine, series, queries, nodes, noises, series_index, log_weights, y_transforms=None, noise_pred=None):
+    """predict_mvn for callers that hold one model per short series: one MixtureModel per series (None for a series without
+    particles), its components the posterior predictive MvNormals of the series' particles in raw space — mean and m_s x m_s
+    covariance from ONE call of GPEngine.predict_sample_series_batch (no samples drawn) — and its probs the softmax of log_weights
+    over the series' particles.  mean / var / cov / logpdf / quantile / rand work as on predict_mvn's result.  Raises
+    PosDefException when a particle has no predictive."""
+    S = len(series)
+    lists, w = pack_series_mixture(series_index, S, log_weights=log_weights)
+    r = engine.predict_sample_series_batch(series, queries, nodes, noises, series_index, w, 0, y_transforms=y_transforms,
+                                           noise_pred=noise_pred, want_moments=True)
+    lw = _f64(log_weights); noises = _f64(noises)
+    out = []
+    for s, sel in enumerate(lists):
+        if sel.size == 0:
+            out.append(None)
+            continue
+        npred = None if noise_pred is None else (float(noise_pred) if np.ndim(noise_pred) == 0 else _f64(noise_pred)[sel])
+        out.append(SeriesMixtureModel.from_series(engine, [MvNormal.from_moments(r.mean[p], r.cov[p]) for p in sel], w[sel],
+                                                  series[s][0], series[s][1], queries[s], [nodes[p] for p in sel], noises[sel], lw[sel],
+                                                  None if y_transforms is None else tuple(y_transforms[s]), npred))
+    return out
 
 
 def infer_gp_sum(nodes, noise, ts, xs, ts_pred, noise_pred=None, engine=None):

@@ -393,6 +393,76 @@ function predict_proba_series_batch(eng::Engine, series::Vector{<:Tuple{Vector{F
     return out[1:P], cut, (weights === nothing ? nothing : mix[1:S]), info[1:P]
 end
 
+"Sample paths of many short series in one fused launch (agp_predict_sample_series_batch): `rand(predict_mvn(model, ds), n_samples)`
+for callers that hold one model per short series, with `predict_proba_series_batch`'s series / query / particle arguments and
+statelessness.  `weights[p]` is particle `p`'s weight inside ITS series' mixture; series `s` draws its `n_samples` paths under
+`seeds[s]` exactly as the resident entry does under that seed.  `y_transforms[s] = (slope, intercept)` (`nothing`: (1, 0)); every
+output is in raw space.  With `want_moments` the components of every series' mixture come back too.  Returns
+`(x, component, means, covs, info)`: `x[s]` an `m_s × n_samples` matrix, column `j` being sample `j`; `component[s][j]` the 1-based
+particle of that sample; `means[p]` / `covs[p]` (`nothing` without `want_moments`) the raw-space mean vector and `m_s × m_s`
+covariance of particle `p`'s predictive.  A series with a failed particle is NaN in `x`."
+function predict_rand_series_batch(eng::Engine, series::Vector{<:Tuple{Vector{Float64},Vector{Float64}}},
+                                   queries::Vector{Vector{Float64}}, nodes::Vector{<:GP.Node}, noises::Vector{Float64},
+                                   series_index::Vector{<:Integer}, weights::Vector{Float64}, n_samples::Integer,
+                                   seeds::Vector{UInt64};
+                                   y_transforms::Union{Nothing,Vector{Tuple{Float64,Float64}}}=nothing,
+                                   noise_pred::Union{Nothing,Vector{Float64}}=nothing, want_moments::Bool=false)
+    P = length(nodes); S = length(series); R = Int64(n_samples)
+    R >= 0 || throw(ArgumentError("n_samples must not be negative"))
+    (length(noises) == P && length(series_index) == P && length(weights) == P) ||
+        throw(ArgumentError("one noise, one series index and one weight per particle required"))
+    (length(queries) == S && length(seeds) == S) || throw(ArgumentError("one vector of query times and one seed per series required"))
+    (noise_pred === nothing || length(noise_pred) == P) || throw(ArgumentError("one noise_pred per particle required"))
+    (y_transforms === nothing || length(y_transforms) == S) || throw(ArgumentError("one (slope, intercept) per series required"))
+    all(i -> 1 <= i <= S, series_index) || throw(ArgumentError("series index outside 1:$S"))
+    pt_off = Int64[0]; ts = Float64[]; xs = Float64[]; q_off = Int64[0]; tq = Float64[]
+    for (s, (t, x)) in enumerate(series)
+        length(t) == length(x) || throw(ArgumentError("series $s: ts and xs must have equal lengths"))
+        length(t) <= SERIES_MAX_N || throw(ArgumentError("series $s has $(length(t)) points, more than SERIES_MAX_N ($SERIES_MAX_N)"))
+        append!(ts, t); append!(xs, x); push!(pt_off, length(ts))
+        append!(tq, queries[s]); push!(q_off, length(tq))
+    end
+    isempty(ts) && (push!(ts, 0.0); push!(xs, 0.0))
+    isempty(tq) && push!(tq, 0.0)
+    sidx = Int32[Int32(i - 1) for i in series_index]
+    op_off, ops, prm_off, prm = encode_batch(nodes)
+    slope = y_transforms === nothing ? ones(Float64, max(1, S)) : Float64[t[1] for t in y_transforms]
+    icpt = y_transforms === nothing ? zeros(Float64, max(1, S)) : Float64[t[2] for t in y_transforms]
+    ms = Int[length(queries[i]) for i in series_index]
+    Q = q_off[end]
+    x = Vector{Float64}(undef, max(1, R * Q)); comp = zeros(Int32, max(1, S * R)); info = zeros(Int32, max(1, P))
+    mean = Vector{Float64}(undef, max(1, sum(ms))); cov = Vector{Float64}(undef, max(1, sum(ms .^ 2)))
+    out_off = zeros(Int64, P + 1); cov_off = zeros(Int64, P + 1)
+    np = noise_pred === nothing ? noises : noise_pred
+    sd = isempty(seeds) ? UInt64[0] : seeds
+    GC.@preserve pt_off ts xs q_off tq sidx op_off ops prm_off prm noises np slope icpt weights sd x comp mean out_off cov cov_off info check(eng, ccall((:agp_predict_sample_series_batch, LIB), Cint,
+        (Ptr{Cvoid}, Int32, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Int32, Ptr{Int32}, Ptr{Int32},
+         Ptr{UInt8}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{UInt64},
+         Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Ptr{Int64}, Ptr{Int32}),
+        eng.ptr, S, pt_off, ts, xs, q_off, tq, P, sidx, op_off, ops, prm_off, prm, noises, np, slope, icpt, weights, R, sd,
+        Ptr{Int32}(C_NULL), Ptr{Float64}(C_NULL), x, comp,
+        want_moments ? pointer(mean) : Ptr{Float64}(C_NULL), out_off, want_moments ? pointer(cov) : Ptr{Float64}(C_NULL), cov_off, info))
+    xs_ = [reshape(x[R * q_off[s] + 1:R * q_off[s + 1]], q_off[s + 1] - q_off[s], R) for s in 1:S]
+    cs_ = [Int.(comp[(s - 1) * R + 1:s * R]) .+ 1 for s in 1:S]
+    means = want_moments ? [mean[out_off[p] + 1:out_off[p + 1]] for p in 1:P] : nothing
+    covs = want_moments ? [reshape(cov[cov_off[p] + 1:cov_off[p + 1]], ms[p], ms[p]) for p in 1:P] : nothing
+    return xs_, cs_, means, covs, info[1:P]
+end
+
+"The components of `predict_mvn`'s MixtureModel for many short series in one fused launch: `(means, covs, info)` of
+`predict_rand_series_batch` with no sample drawn — per particle the raw-space mean vector and `m_s × m_s` covariance of its posterior
+predictive on its own series; with the weights they are every series' `MixtureModel(MvNormal.(means, covs), weights)`."
+function predict_mvn_series_batch(eng::Engine, series::Vector{<:Tuple{Vector{Float64},Vector{Float64}}},
+                                  queries::Vector{Vector{Float64}}, nodes::Vector{<:GP.Node}, noises::Vector{Float64},
+                                  series_index::Vector{<:Integer}, weights::Vector{Float64};
+                                  y_transforms::Union{Nothing,Vector{Tuple{Float64,Float64}}}=nothing,
+                                  noise_pred::Union{Nothing,Vector{Float64}}=nothing)
+    _, _, means, covs, info = predict_rand_series_batch(eng, series, queries, nodes, noises, series_index, weights, 0,
+                                                        zeros(UInt64, length(series)); y_transforms=y_transforms,
+                                                        noise_pred=noise_pred, want_moments=true)
+    return means, covs, info
+end
+
 "(extended, from_scratch, tile_rows_reused, tile_rows_total, evicted_before_reuse, slots, callers, occupied, capacity_tile_rows, growth_copies) of the factor store"
 function extend_stats(eng::Engine)
     out = zeros(Int64, 10)

@@ -119,6 +119,51 @@ kernels() = GP.Node[
         @test eng.n_max == 700      # the resident series is untouched
     end
 
+    @testset "many short series: sample paths and joint forecasts in one call (stateless)" begin
+        ks = kernels()
+        splits = ((0, 5), (17, 5), (126, 18), (140, 36))       # (training points, query points)
+        sers = [(ts[1:n], xs[1:n]) for (n, _) in splits]
+        qs = [ts[n + 1:n + m] for (n, m) in splits]
+        a, b = -0.7, 0.2                                       # scaled = a raw + b
+        nodes = GP.Node[]; sidx = Int[]
+        for s in eachindex(sers), k in ks
+            push!(nodes, k); push!(sidx, s)
+        end
+        P = length(nodes); R = 50
+        w = Float64[1 / length(ks) for _ in 1:P]
+        seeds = UInt64[11, 12, 13, 14]
+        yts = fill((a, b), length(sers))
+        x, comp, means, covs, info = H.predict_rand_series_batch(eng, sers, qs, nodes, fill(noise, P), sidx, w, R, seeds;
+                                                                 y_transforms=yts, want_moments=true)
+        @test all(info .== 0)
+        mu2, cv2, info2 = H.predict_mvn_series_batch(eng, sers, qs, nodes, fill(noise, P), sidx, w; y_transforms=yts)
+        @test mu2 == means && cv2 == covs && info2 == info     # the moments do not depend on the samples drawn beside them
+        for (p, (k, s)) in enumerate(zip(nodes, sidx))
+            n, m = splits[s]
+            # the posterior predictive in raw space from the dense formulas
+            K = GP.compute_cov_matrix_vectorized(k, noise, vcat(ts[1:n], qs[s]))
+            K11, K21, K22 = K[1:n, 1:n], K[n + 1:end, 1:n], K[n + 1:end, n + 1:end]
+            mu = n == 0 ? zeros(m) : K21 * (K11 \ xs[1:n])
+            Sg = n == 0 ? K22 : K22 - K21 * (K11 \ K21')
+            @test maximum(abs.(means[p] .- (mu .- b) ./ a)) <= 1e-8 * max(1.0, maximum(abs.(mu ./ a)))
+            @test norm(covs[p] - Sg ./ a^2) <= 1e-8 * norm(Sg ./ a^2)
+            @test covs[p] == covs[p]'
+        end
+        for s in eachindex(sers)
+            sel = findall(==(s), sidx)
+            @test size(x[s]) == (splits[s][2], R) && all(c -> c in sel, comp[s]) && all(isfinite, x[s])
+        end
+        # series 3 alone under its own seed: the same bits
+        sel = findall(==(3), sidx)
+        x3, comp3, _, _, _ = H.predict_rand_series_batch(eng, [sers[3]], [qs[3]], nodes[sel], fill(noise, length(sel)),
+                                                         fill(1, length(sel)), w[sel], R, seeds[3:3]; y_transforms=yts[3:3])
+        @test x3[1] == x[3] && comp3[1] .+ (sel[1] - 1) == comp[3]
+        # 144 training points + 36 queries are 180 joint points: refused
+        @test_throws ErrorException H.predict_rand_series_batch(eng, [(ts[1:144], xs[1:144])], [ts[145:180]], nodes[1:1], [noise], [1],
+                                                                [1.0], 1, UInt64[1])
+        @test eng.n_max == 700      # the resident series is untouched
+    end
+
     @testset "not positive definite" begin
         bad = GP.Linear(0.0, 0.0, -0.01)
         @test_throws LinearAlgebra.PosDefException H.logpdf(eng, bad, 0.1, 700)

@@ -278,6 +278,58 @@ int agp_predict_logpdf_series_batch(agp_ctx* ctx, int32_t S, const int64_t* pt_o
                                     int64_t* out_off /* P+1, or NULL */, double* out_series_logp /* S; NULL iff weights is */,
                                     int32_t* out_info /* P */);
 
+/* SAMPLE PATHS and JOINT FORECASTS of many short series in one call: rand(predict_mvn(model, ds), R) and the components of
+ * predict_mvn's MixtureModel (src/api.jl:497-522) for callers that hold one model per short series.  The resident-series twins are
+ * agp_predict_sample_batch and agp_predict_batch(want_cov); the route is agp_predict_logpdf_series_batch's: one workgroup per
+ * particle factors the joint matrix of the series' n_s training points followed by its m_s query points with a zero query right-hand
+ * side, after which the query rows of the factor are [L21 L22] with L22 = chol(Sigma*) and a = L11^-1 xs, and everything is a
+ * read-out of those rows in the same workgroup: mu* = L21 a, Sigma* = L22 L22', x = mu* + L22 z.
+ * Arguments S .. noise_pred as agp_predict_logpdf_series_batch, without y_pred.  y_slope / y_intercept (S each, or NULL: 1 / 0): the
+ * transform of series s (scaled = slope raw + intercept); every output is in RAW space.  weights (P): particle p's weight inside ITS
+ * series' mixture (the particles of a series need not be adjacent).  R >= 0 samples per series, the same for every series; R == 0:
+ * only out_mean / out_cov / out_info are produced.
+ * Draws: series s draws exactly as agp_predict_sample_batch does under seed = seeds[s] — Philox4x64-10 under the key (seeds[s], 0);
+ *   the component of sample j from the uniform of word 0 of block (j, 0, 0, 0) through the inverse CDF of the cumulative weights of
+ *   the series' particles in ascending p; the uniform of z[j, i] is word i % 4 of block (i / 4, j, 1, 0); normals by ndtri.
+ *   component (S R int32, or NULL): global particle indices, sample j of series s at s R + j; each must be a particle of series s of
+ *   positive weight.  z (R q_off[S] doubles in out_x's layout, or NULL): they replace the normal draws.  seeds may be NULL only when
+ *   nothing is left to draw.
+ * out_x (R q_off[S] doubles): series s owns [R q_off[s], R q_off[s+1]); sample j is the column of m_s values at + j m_s:
+ *   x = (mu*_c - b_s) / a_s + (L22_c z_j) / |a_s|, evaluated as (mu* + sign(a_s) L22 z - b_s) / a_s (c the sample's component).
+ * out_component (S R, or NULL): the components used.
+ * out_mean (out_off[P] doubles, or NULL; out_off: P + 1, written by the entry, particle-major as in agp_predict_series_batch):
+ *   (mu*_p - b) / a.  out_cov (cov_off[P] doubles, or NULL; cov_off: P + 1, written by the entry, the running sum of m_s^2):
+ *   Sigma*_p / a^2, m_s x m_s column-major, both triangles written, exactly symmetric.  Together they are the components of
+ *   predict_mvn's mixture for every series; adjacent particles of one series form the block agp_mixture_moments takes.
+ * out_info[p]: agp_predict_logpdf_series_batch's convention (first bad pivot of the joint factor).  If ANY particle of a series has
+ *   info != 0, whatever its weight, that series' whole block of out_x is NaN (the reference throws); the failed particle's own
+ *   out_mean / out_cov blocks are NaN; no other series and no other particle changes a bit (the fill runs on the device behind the
+ *   kernels, on the same stream).  m_s == 0 writes nothing for the series; n_s == 0 samples the prior K22 + noise_pred I.
+ * Bit contract: the bits of sample j of series s depend only on seeds[s] (or the caller's z and component), j, and the inputs of its
+ *   component — program, parameters, noises, the series, its queries, the transform.  They do not depend on R, on the other series or
+ *   particles, on the order of the batch, or on which samples share a group of 16 on the device.  out_mean / out_cov depend on the
+ *   particle's own inputs only.
+ * Stateless and re-entrant as agp_predict_series_batch: one upload, one synchronisation; neither the resident series nor the factor
+ *   store is touched.  With profiling on, agp_get_timing's out[0] = out[2] = the fused kernels and out[4] = the NaN-fill read-out.
+ * The WHOLE call is rejected, and nothing is written to any output, with everything agp_predict_logpdf_series_batch reports (the cap
+ *   n_s + m_s <= AGP_SERIES_MAX_N and the LDS need at that length included: 144 training points + 36 queries are 180 and refused),
+ *   and with AGP_ERR_ARG (each message names the series): R < 0; R q_off[S] >= 2^31; a series without particles when R > 0; a
+ *   component outside its series or of weight 0; a z that is not finite; a y_slope that is 0 or not finite or a y_intercept that is
+ *   not finite; NULL weights, out_x (with something to write), seeds (with something to draw), out_off with out_mean, cov_off with
+ *   out_cov.
+ * Not here: mean functions, n_s + m_s > AGP_SERIES_MAX_N, deduplication inside a call. */
+int agp_predict_sample_series_batch(agp_ctx* ctx, int32_t S, const int64_t* pt_off /* S+1 */, const double* ts, const double* xs,
+                                    const int64_t* q_off /* S+1 */, const double* ts_pred, int32_t P, const int32_t* series /* P */,
+                                    const int32_t* op_off, const uint8_t* ops, const int32_t* prm_off, const double* prm,
+                                    const double* noise /* P */, const double* noise_pred /* P or NULL = noise */,
+                                    const double* y_slope /* S, or NULL: 1 */, const double* y_intercept /* S, or NULL: 0 */,
+                                    const double* weights /* P */, int64_t R, const uint64_t* seeds /* S */,
+                                    const int32_t* component /* S R, or NULL */, const double* z /* R q_off[S], or NULL */,
+                                    double* out_x /* R q_off[S] */, int32_t* out_component /* S R, or NULL */,
+                                    double* out_mean /* out_off[P], or NULL */, int64_t* out_off /* P+1, or NULL */,
+                                    double* out_cov /* cov_off[P], or NULL */, int64_t* cov_off /* P+1, or NULL */,
+                                    int32_t* out_info /* P */);
+
 /* agp_logpdf_batch with BLOCK-EXTENSION of resident factors.  The data-annealing loop re-scores
  * every particle on a longer prefix of the same series with unchanged kernel parameters — the reweight step
  * (src/inference_smc_anneal_data.jl:206-217), add_data! (src/api.jl:426-443), scripts/online.jl:200 — and the
@@ -941,7 +993,7 @@ int agp_debug_compact_shards(agp_ctx* ctx, const double* padded, int32_t P, int3
  * fills out[8..11] = { L^-T chain ms, K^-1 tiles ms, contraction ms, alpha + reductions ms }, agp_predict_sample_batch
  * out[12..13] = { normals ms, read-out ms }, agp_predict_mixture_batch out[14..15] = { pass ms, accumulation ms } (n_out up to 16).  The many-series entries fill
  * out[0] = out[2] = their fused kernels, and agp_predict_quantile_series_batch out[4] = its three read-out kernels,
- * agp_predict_logpdf_series_batch out[4] = its mixture read-out. */
+ * agp_predict_logpdf_series_batch out[4] = its mixture read-out, agp_predict_sample_series_batch out[4] = its NaN-fill read-out. */
 int agp_set_profiling(agp_ctx* ctx, int enabled);
 int agp_get_timing(agp_ctx* ctx, double* out, int32_t n_out);
 /* per-launch durations (ms) of the last profiled batch call: which = 0 update kernel, 1 trsm kernel;
