@@ -397,6 +397,21 @@ constexpr int SERIES_QSLOT = 192;
 static_assert(SERIES_QSLOT >= SERIES_MAX_N && SERIES_QSLOT + 4 * 16 <= 256, "four waves' query entries behind the series' own");
 __host__ __device__ inline SeriesLds series_pred_lds(int n, int n_ops, int n_prm, int n_cp) { return series_lds(n, n_ops, n_prm, n_cp); }
 
+// Decomposition twin (k_series_predict_sum, agp_predict_sum_series_batch): the predictive twin's arguments on COMPOSITE programs
+// (K_1 SEL_1 * K_2 SEL_2 * + ..: append_composite) and coded joint rows.  Series s with m query times has (M + 1) m rows g in the
+// order F_1(T*) .. F_M(T*), X(T*): row g is component i = g / m at time ts_pred[q_off[s] + g % m], code i < M ? i + 1 : 0, diagonal
+// addend 1e-8 + (i == M ? noise_pred[p] : 0).  out_off counts ROWS ((M + 1) times the predictive twin's); out_mean / out_var take the
+// raw-space marginals of predict_sum (k_sum_readout's statements) and out_x their nq Normal quantiles per row.  The LDS map is
+// series_pred_lds with the M selector tables counted in n_cp (ProgHdr::n_cp does): a query row's selector entries sit in the
+// tables' entries SERIES_QSLOT .. like sigma_cp's.
+struct SeriesSumArgs : SeriesPredArgs {
+  int M, nq;
+  const double* y_slope;     // [S]
+  const double* y_intercept; // [S]
+  const double* z;           // [nq] ndtri(q[k]), from the host
+  double* out_x;             // [nq out_off[P]] row-major (row, k); unused when nq == 0
+};
+
 // Held-out twin (k_series_predict_logpdf, agp_predict_logpdf_series_batch): the value kernel's arguments, every series' own query
 // times and held-out values, and the outputs.  The workgroup factors the JOINT matrix of the series' n training points followed —
 // without padding — by its m query points, N = n + m <= SERIES_MAX_N, in the value kernel's LDS map at N points (series_lds(N, ..)),

@@ -1,5 +1,5 @@
-// Kernel translation unit 3: the small-matrix value kernel, its value-and-gradient twin and its predictive twin (agp_series_kernel.hpp),
-// behind agp_launch.hpp.
+// Kernel translation unit 3: the small-matrix value kernel, its value-and-gradient twin, its predictive twin and the latter's
+// held-out, sampling and decomposition twins (agp_series_kernel.hpp), behind agp_launch.hpp.
 #include "agp_launch.hpp"
 #include "agp_series_kernel.hpp"
 
@@ -12,7 +12,8 @@ hipError_t kernels_init_series() {
                        reinterpret_cast<const void*>(&k_series_logpdf_grad<8, 64>),
                        reinterpret_cast<const void*>(&k_series_predict<4>), reinterpret_cast<const void*>(&k_series_predict<8>),
                        reinterpret_cast<const void*>(&k_series_predict_logpdf<4>), reinterpret_cast<const void*>(&k_series_predict_logpdf<8>),
-                       reinterpret_cast<const void*>(&k_series_predict_sample<4>), reinterpret_cast<const void*>(&k_series_predict_sample<8>)};
+                       reinterpret_cast<const void*>(&k_series_predict_sample<4>), reinterpret_cast<const void*>(&k_series_predict_sample<8>),
+                       reinterpret_cast<const void*>(&k_series_predict_sum<4>), reinterpret_cast<const void*>(&k_series_predict_sum<8>)};
   for (const void* f : fns) {
     hipFuncAttributes fa;
     hipError_t e = hipFuncGetAttributes(&fa, f);
@@ -44,6 +45,14 @@ hipError_t launch_series_predict(hipStream_t st, const SeriesPredArgs& sa, int g
   if (lds_bytes > (size_t)SERIES_LDS_BYTES) return hipErrorInvalidValue;
   if (depth <= 4) hipLaunchKernelGGL(k_series_predict<4>, dim3(grid), dim3(256), lds_bytes, st, sa);
   else hipLaunchKernelGGL(k_series_predict<8>, dim3(grid), dim3(256), lds_bytes, st, sa);
+  return hipGetLastError();
+}
+
+hipError_t launch_series_predict_sum(hipStream_t st, const SeriesSumArgs& sa, int grid, int depth, size_t lds_bytes) {
+  if (grid <= 0) return hipSuccess;
+  if (lds_bytes > (size_t)SERIES_LDS_BYTES || sa.M < 1 || sa.nq < 0) return hipErrorInvalidValue;
+  if (depth <= 4) hipLaunchKernelGGL(k_series_predict_sum<4>, dim3(grid), dim3(256), lds_bytes, st, sa);
+  else hipLaunchKernelGGL(k_series_predict_sum<8>, dim3(grid), dim3(256), lds_bytes, st, sa);
   return hipGetLastError();
 }
 

@@ -79,7 +79,7 @@ void launch_lag_grad(hipStream_t st, int P, size_t lds, const GradArgs& ga);
 void launch_grad_finish(hipStream_t st, int P, const GradArgs& ga);
 
 // ---- agp_kernels_series.hip ------------------------------------------------------------------------------------------
-hipError_t kernels_init_series();   // raises the dynamic-LDS ceiling of k_series_logpdf / k_series_logpdf_grad / k_series_predict / k_series_predict_logpdf / k_series_predict_sample to the whole 160 KiB (once, agp_init)
+hipError_t kernels_init_series();   // raises the dynamic-LDS ceiling of k_series_logpdf / k_series_logpdf_grad / k_series_predict / k_series_predict_logpdf / k_series_predict_sample / k_series_predict_sum to the whole 160 KiB (once, agp_init)
 // small-matrix value kernel: one workgroup per entry of sa.wg (`grid` of them), evaluation-stack depth 4 / 8, lds_bytes = the largest
 // SeriesLds total of the launch's particles
 hipError_t launch_series_logpdf(hipStream_t st, const SeriesArgs& sa, int grid, int depth, size_t lds_bytes);
@@ -88,6 +88,8 @@ hipError_t launch_series_logpdf(hipStream_t st, const SeriesArgs& sa, int grid, 
 hipError_t launch_series_logpdf_grad(hipStream_t st, const SeriesGradArgs& sa, int grid, int depth, int tape, size_t lds_bytes);
 // predictive twin (k_series_predict): depth as for the value kernel, lds_bytes = the largest series_pred_lds total of the launch's particles
 hipError_t launch_series_predict(hipStream_t st, const SeriesPredArgs& sa, int grid, int depth, size_t lds_bytes);
+// decomposition twin (k_series_predict_sum): as the predictive twin, on composite programs (their selector tables counted in lds_bytes)
+hipError_t launch_series_predict_sum(hipStream_t st, const SeriesSumArgs& sa, int grid, int depth, size_t lds_bytes);
 // held-out twin (k_series_predict_logpdf): depth as for the value kernel, lds_bytes = the largest series_lds total of the launch's
 // particles at their JOINT lengths n_s + m_s
 hipError_t launch_series_predict_logpdf(hipStream_t st, const SeriesProbaArgs& sa, int grid, int depth, size_t lds_bytes);

@@ -9,6 +9,8 @@
 //                                      the log-density of every series' held-out values; k_series_mix_logp behind it for the mixtures
 //   agp_predict_sample_series_batch    k_series_predict_sample: the same joint factorisation with a zero query right-hand side, the query
 //                                      rows read out as samples, component means and covariances; k_series_sample_fill behind it
+//   agp_predict_sum_series_batch       k_series_predict_sum: the predictive kernel on every particle's composite program (append_composite)
+//                                      and coded query rows F_1 .. F_M, X, read out as predict_sum's raw marginals and quantiles
 // Each entry is one function, read top to bottom, over the stages they share (one SeriesCall carries what a stage leaves for the next):
 //   checks          series_check_sizes, series_check_pointers, series_check_layout (the entry's own pointer checks between them)
 //   series_classes  compile, per particle length / LDS need / evaluation stack, launch classes, workgroup order, out_off
@@ -21,6 +23,7 @@
 // travel with the call; the resident series, its tables, the factor store, the coalescer and every counter of the context are
 // neither read nor changed — only a workspace slot (stream, staging buffers) is borrowed, as in every batch entry.
 #include "agp_host.hpp"
+#include "agp_ndtri.hpp"
 
 #include <optional>
 
@@ -125,7 +128,7 @@ void quant_fill_nan(const SeriesQuantOut& qo, size_t from, size_t to, int64_t nq
 #define STAGE(expr) do { if (const int rc_ = (expr)) return rc_; } while (0)
 
 // Which kernel the call launches: it chooses the LDS map, the instantiation rule and (gradient) the tape's limit.
-enum class SeriesMode { value, gradient, prediction, held_out };
+enum class SeriesMode { value, gradient, prediction, held_out, sum };
 
 // One call of a many-series entry: the caller's inputs and what each shared stage leaves for the later ones.
 struct SeriesCall {
@@ -214,7 +217,7 @@ int series_check_layout(agp_ctx* c, const SeriesCall& sc) {
 size_t series_need(SeriesMode mode, const Batch& bt, int p, int n) {
   const ProgHdr& h = bt.hdr[(size_t)p];
   const int m_total = mode == SeriesMode::gradient ? series_grad_lds(n, h.n_ops, h.n_prm, h.n_cp, bt.ghdr[(size_t)p].n_ops, bt.ghdr[(size_t)p].n_prm).total
-                      : mode == SeriesMode::prediction ? series_pred_lds(n, h.n_ops, h.n_prm, h.n_cp).total
+                      : mode == SeriesMode::prediction || mode == SeriesMode::sum ? series_pred_lds(n, h.n_ops, h.n_prm, h.n_cp).total
                                                        : series_lds(n, h.n_ops, h.n_prm, h.n_cp).total;
   return sizeof(double) * (size_t)m_total;
 }
@@ -239,6 +242,7 @@ int series_classes(agp_ctx* c, SeriesCall& sc, SeriesMode mode) {
   Batch& bt = sc.bt;
   CompileOpts co;
   co.ge_tab = false; co.lag = false; co.never_fuse = true; co.want_grad = mode == SeriesMode::gradient;
+  co.allow_sel = mode == SeriesMode::sum;      // (the composite programs' selector leaves: one per-point table each, counted in n_cp)
   STAGE(compile_batch(c, sc.pp, bt, co));
   if (mode == SeriesMode::gradient)
     for (int p = 0; p < P; ++p)
@@ -262,8 +266,9 @@ int series_classes(agp_ctx* c, SeriesCall& sc, SeriesMode mode) {
     if (n == 0 && sc.nq[(size_t)p] == 0) continue;      // (an empty series is launched for its prior predictive only)
     const size_t need = sc.need[(size_t)p] = series_need(mode, bt, p, n);
     if (need > (size_t)SERIES_LDS_BYTES) {
-      snprintf(buf, sizeof buf, "particle %d: %d per-point tables (ChangePoint nodes) at %d points need %zu bytes of LDS, more than the "
-               "kernel's %d", p, (int)h.n_cp, n, need, SERIES_LDS_BYTES);
+      snprintf(buf, sizeof buf, "particle %d: %d per-point tables (%s) at %d points need %zu bytes of LDS, more than the "
+               "kernel's %d", p, (int)h.n_cp, mode == SeriesMode::sum ? "ChangePoint nodes and component selectors" : "ChangePoint nodes", n,
+               need, SERIES_LDS_BYTES);
       return fail(c, AGP_ERR_PROGRAM, buf);
     }
     const int depth = series_stack_depth(bt, h);
@@ -912,6 +917,118 @@ int predict_sample_series(agp_ctx* c, SeriesCall& sc, const SeriesSampleOut& so,
   return series_timing(c, sc, readout_ms);
 }
 
+// The decomposition side of agp_predict_sum_series_batch: the components, transforms and quantiles, and the outputs beside [logpdf | info].
+struct SeriesSumOut {
+  int32_t M;                   // components per particle: particle p's are the CSR entries [p M, (p + 1) M) of the call's programs
+  const double* y_slope;       // [S] or null (1)
+  const double* y_intercept;   // [S] or null (0)
+  const double* q; int64_t nq;
+  double* mean; double* var;   // [out_off[P]]; var nullable
+  double* x;                   // [nq out_off[P]]; unused when nq == 0
+  int64_t* out_off;            // [P + 1]
+};
+
+// predict_sum's numbers of every particle on its own series: sc.pp arrives holding the P M COMPONENT programs; the composites
+// K_1 SEL_1 * K_2 SEL_2 * + .. built from them take its place, and the stages run on those.  out_logpdf may be null.
+int predict_sum_series(agp_ctx* c, SeriesCall& sc, const SeriesSumOut& so, double* out_logpdf, int32_t* out_info) {
+  const int P = sc.pp.P;
+  const int32_t S = sc.S, M = so.M;
+  const int64_t nq = so.nq;
+  char buf[256];
+  STAGE(series_check_sizes(c, sc));
+  if (M < 1) return fail(c, AGP_ERR_ARG, "M must be >= 1 (components per particle)");
+  if (nq < 0) return fail(c, AGP_ERR_ARG, "negative size (nq)");
+  if (nq > 0 && !so.q) return fail(c, AGP_ERR_ARG, "null q");
+  for (int64_t k = 0; k < nq; ++k)
+    if (!(so.q[k] > 0.0 && so.q[k] < 1.0)) {
+      snprintf(buf, sizeof buf, "quantile %lld must be in (0, 1)", (long long)k);
+      return fail(c, AGP_ERR_ARG, buf);
+    }
+  if (P == 0) return AGP_OK;
+  STAGE(series_check_pointers(c, sc, out_info != nullptr));
+  if (!sc.q_off || !sc.ts_pred || !so.mean || !so.out_off || (nq > 0 && !so.x))
+    return fail(c, AGP_ERR_ARG, "null pointer argument (q_off, ts_pred, out_mean, out_off, or out_x with quantiles asked)");
+  if ((int64_t)P * M >= ((int64_t)1 << 31)) return fail(c, AGP_ERR_ARG, "P * M too large");
+  // the composite programs, particle by particle (as agp_infer_gp_sum_batch)
+  const Particles comp = sc.pp;
+  std::vector<int32_t> coff((size_t)P + 1, 0), cpoff((size_t)P + 1, 0);
+  std::vector<uint8_t> cops; std::vector<double> cprm;
+  std::string err;
+  for (int p = 0; p < P; ++p) {
+    if (const int rc = append_composite(comp, (int64_t)p * M, M, AGP_MAX_OPS, cops, cprm, err)) {
+      snprintf(buf, sizeof buf, "particle %d: ", p);
+      return fail(c, rc, buf + err);
+    }
+    coff[(size_t)p + 1] = (int32_t)cops.size(); cpoff[(size_t)p + 1] = (int32_t)cprm.size();
+  }
+  sc.pp = {P, coff.data(), cops.data(), cpoff.data(), cprm.data(), comp.noise, comp.noise_pred};
+  STAGE(series_check_layout(c, sc));
+  std::vector<double> vals(2 * (size_t)S + (size_t)nq);      // [slope (S) | intercept (S) | z (nq)]
+  for (int32_t s = 0; s < S; ++s) {
+    vals[(size_t)s] = so.y_slope ? so.y_slope[s] : 1.0;
+    vals[(size_t)S + s] = so.y_intercept ? so.y_intercept[s] : 0.0;
+    if (const int rc = check_y_transform(c, vals[(size_t)s], vals[(size_t)S + s])) return fail_series(c, rc, s);
+  }
+  for (int64_t k = 0; k < nq; ++k) vals[2 * (size_t)S + (size_t)k] = ndtri(so.q[k]);
+  {
+    int64_t rows = 0;      // (M + 1) sum_p m_{series[p]}: m_s <= 2^30 and M < 2^31, so every step stays far inside int64
+    const int64_t lim = (int64_t)1 << 31;
+    for (int p = 0; p < P; ++p) {
+      rows += ((int64_t)M + 1) * (sc.q_off[sc.series[p] + 1] - sc.q_off[sc.series[p]]);
+      if (rows >= lim || (nq > 0 && rows >= lim / nq)) {
+        snprintf(buf, sizeof buf, "particle %d: an output reaches 2^31 elements", p);
+        return fail(c, AGP_ERR_ARG, buf);
+      }
+    }
+  }
+  STAGE(series_classes(c, sc, SeriesMode::sum));
+  for (long long& o : sc.ooff) o *= (long long)M + 1;      // out_off counts rows: M + 1 per query point
+  std::copy(sc.ooff.begin(), sc.ooff.end(), so.out_off);   // (no check is left to fail, nothing is launched yet)
+  if (sc.wg.empty()) { series_zero_values(sc, out_logpdf, out_info); return AGP_OK; }
+  STAGE(series_stage(c, sc));
+  Slot* s = sc.s;
+  // sq_w = [slope (S) | intercept (S) | z (nq)]; the raw marginals in pred_mean / pred_var, the quantiles in sum_x
+  const size_t n_out = sc.n_out(), nx = n_out * (size_t)nq;
+  HIPCHK(c, s->sq_w.ensure(sizeof(double) * std::max<size_t>(1, vals.size())));
+  HIPCHK(c, s->sum_x.ensure(sizeof(double) * std::max<size_t>(1, nx)));
+  sc.up.add(s->sq_w.p, vals.data(), sizeof(double) * vals.size());
+  HIPCHK(c, sc.up.flush(s->h_stage, s->up_blob, sc.st));
+  SeriesSumArgs pa = {};
+  static_cast<SeriesArgs&>(pa) = sc.sa;
+  pa.q_off = sc.in_map<const long long>(sc.o_qoff);
+  pa.out_off = sc.in_map<const long long>(sc.o_ooff);
+  pa.ts_pred = s->tt.as<double>() + 2 * sc.npts; pa.noise_pred = s->noise_pred.as<double>();
+  pa.out_mean = s->pred_mean.as<double>(); pa.out_var = s->pred_var.as<double>();
+  pa.M = M; pa.nq = (int)nq;
+  pa.y_slope = s->sq_w.as<double>(); pa.y_intercept = pa.y_slope + S; pa.z = pa.y_intercept + S;
+  pa.out_x = s->sum_x.as<double>();
+  STAGE(series_launch(c, sc, [&](const int32_t* wg, int grid, int d, size_t lds) {
+    pa.wg = wg;
+    return launch_series_predict_sum(sc.st, pa, grid, d == 0 ? 4 : 8, lds);
+  }));
+  // h_out = [logpdf | info | mean (out_off[P]) | var (out_off[P]) | x (nq out_off[P])]
+  const size_t o_mean = sc.o_own(), o_var = o_mean + sizeof(double) * n_out, o_x = o_var + sizeof(double) * n_out;
+  STAGE(series_fetch_values(c, sc, o_x + sizeof(double) * nx));
+  char* ho = static_cast<char*>(s->h_out.p);
+  if (n_out > 0) {
+    HIPCHK(c, hipMemcpyAsync(ho + o_mean, s->pred_mean.p, sizeof(double) * n_out, hipMemcpyDeviceToHost, sc.st));
+    HIPCHK(c, hipMemcpyAsync(ho + o_var, s->pred_var.p, sizeof(double) * n_out, hipMemcpyDeviceToHost, sc.st));
+  }
+  if (nx > 0) HIPCHK(c, hipMemcpyAsync(ho + o_x, s->sum_x.p, sizeof(double) * nx, hipMemcpyDeviceToHost, sc.st));
+  HIPCHK(c, hipStreamSynchronize(sc.st));
+  series_copy_values(sc, out_logpdf, out_info);
+  // (an empty series with query points was launched for its prior: its value is 0, but a row without a raw marginal still reports)
+  const int32_t* hi = reinterpret_cast<const int32_t*>(static_cast<const double*>(s->h_out.p) + P);
+  for (int p = 0; p < P; ++p)
+    if (sc.len[(size_t)p] == 0 && sc.nq[(size_t)p] > 0) out_info[p] = hi[p];
+  if (n_out > 0) {      // every particle with query points was launched and wrote its whole blocks
+    std::memcpy(so.mean, ho + o_mean, sizeof(double) * n_out);
+    if (so.var) std::memcpy(so.var, ho + o_var, sizeof(double) * n_out);
+  }
+  if (nx > 0) std::memcpy(so.x, ho + o_x, sizeof(double) * nx);
+  return series_timing(c, sc);
+}
+
 #undef STAGE
 
 // agp_debug_series_factor: P caller matrices of one size through stages 4 and 5 of the value kernel (its probe instantiation).
@@ -1035,6 +1152,19 @@ int agp_predict_sample_series_batch(agp_ctx* c, int32_t S, const int64_t* pt_off
     SeriesCall sc{S, pt_off, ts, xs, {P, op_off, ops, prm_off, prm, noise, noise_pred}, series, q_off, ts_pred};
     const SeriesSampleOut so{y_slope, y_intercept, weights, R, seeds, component, z, out_x, out_component, out_mean, out_off, out_cov, cov_off};
     return predict_sample_series(c, sc, so, out_info);
+  });
+}
+
+int agp_predict_sum_series_batch(agp_ctx* c, int32_t S, const int64_t* pt_off, const double* ts, const double* xs, const int64_t* q_off,
+                                 const double* ts_pred, int32_t P, int32_t M, const int32_t* series, const int32_t* op_off,
+                                 const uint8_t* ops, const int32_t* prm_off, const double* prm, const double* noise,
+                                 const double* noise_pred, const double* y_slope, const double* y_intercept, const double* q, int64_t nq,
+                                 double* out_mean, double* out_var, double* out_x, int64_t* out_off, double* out_logpdf,
+                                 int32_t* out_info) {
+  return abi_guard(c, [&] {
+    SeriesCall sc{S, pt_off, ts, xs, {P, op_off, ops, prm_off, prm, noise, noise_pred}, series, q_off, ts_pred};
+    const SeriesSumOut so{M, y_slope, y_intercept, q, nq, out_mean, out_var, out_x, out_off};
+    return predict_sum_series(c, sc, so, out_logpdf, out_info);
   });
 }
 

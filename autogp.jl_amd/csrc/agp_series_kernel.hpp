@@ -80,6 +80,26 @@
 // covariance Sigma* = L22 L22' and the samples mu* + L22 z of predict_mvn / rand are read out of rows [n, N) in the same workgroup and
 // the value kernel's LDS map (series_sample_readout); k_series_sample_fill behind the launches turns the block of a series with a
 // failed particle into NaN.
+//
+// k_series_predict_sum<D> (agp_predict_sum_series_batch) is the predictive kernel on a sum of GPs, X = F_1 + .. + F_M + noise: the
+// posterior of every latent part and of the observable at the series' query times (GP.infer_gp_sum, predict_sum), by the coded-points
+// route of agp_infer_gp_sum_batch.  The particle's program is the composite K_1 SEL_1 * K_2 SEL_2 * + .. (append_composite); a
+// selector leaf reads a per-point table like a ChangePoint node's (eval_program's OP_SEL; ProgHdr::n_cp counts both kinds, tables
+// numbered in program order), so the LDS map is series_pred_lds as it stands.  One body again (argument type SeriesSumArgs; the
+// predictive branches P1, P2 and the map are shared with k_series_predict through the trait PRED).  It differs in
+//   2. the tables: SEL_i holds 1.0 at every training point — they are the observable, code 0 — so K11 is the sum of the parts;
+//   P2. the rows: series s with m query times has (M + 1) m joint rows g in the reference's order F_1(T*) .. F_M(T*), X(T*); row g is
+//       component i = g / m at time tq[g % m] with code i < M ? i + 1 : 0, and SEL_j's entry at the row's query slot is
+//       (code == 0 || code == j).  16 consecutive rows belong to one wave as 16 queries do, whatever their codes: every lane has its own
+//       slot entry.  var = (k** - sum VT^2) + [1e-8 + (i == M ? noise_pred : 0)]: JITTER on every row, noise_pred on the observable's
+//       only.  Code and addend of a row are recomputed from g where they are used, not carried through the block loop;
+//   the read-out, in the lanes that hold the row (k_sum_readout's statements, no further launch): raw mean (mean - b) / a, + b / a on
+//       the F_1 rows, raw variance (1 / (a a)) var, quantiles fma(sqrt(var), z_k, mean); a row whose raw variance is negative or NaN or
+//       whose raw mean is not finite marks the particle with min(g + 1) in an LDS word (ds_min), and behind ONE workgroup barrier a
+//       marked particle's whole blocks become NaN and out_info[p] = n + g + 1 (series_sum_rows).
+// An empty series with query points gives the prior of every part through the same rows (series_prior_predict_sum).  On a bad pivot
+// NaN is written to all of the particle's outputs.  244 / 232 VGPRs (D = 4 / 8), no scratch.  The X rows are not formed as the sum of
+// the F rows' VT: a second set of eleven register blocks does not fit beside the first.
 #pragma once
 #include <type_traits>
 #include "agp_common.hpp"
@@ -100,7 +120,11 @@ __device__ __forceinline__ void series_blk_rc(int b, int& rb, int& cb) {
 }
 
 // sigma_cp (src/GP.jl:481-483) of every ChangePoint node at time t -> entry `slot` of the node's per-point table (cov_prologue's arithmetic)
-__device__ __forceinline__ void series_sigma_cp(const ProgHdr& h, const int* ops, const double* prm, double* sig, int slot, double t) {
+// SEL (composite programs of the decomposition twin): also the selector leaves' entries for a point of component code `code` —
+// 1 where the point is the observable (code 0) or the leaf's own component — tables numbered in program order across both kinds.
+template <bool SEL = false>
+__device__ __forceinline__ void series_sigma_cp(const ProgHdr& h, const int* ops, const double* prm, double* sig, int slot, double t,
+                                                [[maybe_unused]] int code = 0) {
   int q = 0, c = 0;
   for (int ip = 0; ip < h.n_ops; ++ip) {
     const int o = ops[ip];
@@ -109,9 +133,25 @@ __device__ __forceinline__ void series_sigma_cp(const ProgHdr& h, const int* ops
       sig[c * 256 + slot] = 0.5 * (1.0 + tanh((loc - t) / sc));
       ++c;
     }
+    if constexpr (SEL) {
+      if (o == OP_SEL) {
+        sig[c * 256 + slot] = (code == 0 || code == (int)prm[q]) ? 1.0 : 0.0;
+        ++c;
+      }
+    }
     q += prm_count(o);
   }
 }
+
+// What the decomposition twin's rows need beside the predictive twin's arguments (series_predict_blocks<D, true>): the series'
+// query count m and transform, the quantiles, and the LDS word that collects the first row without a raw marginal.
+struct SeriesSumRows {
+  int m, M, nq;              // query times of the series, components, quantiles per row
+  double slope, icpt;        // scaled = slope raw + icpt
+  const double* z;           // [nq]
+  double* ox;                // the particle's (rows, nq) block of out_x
+  int* rowbad;               // LDS: min over the failed rows of g + 1 (INT_MAX: none)
+};
 
 // G1 / P1: every diagonal block L(i,i) -> L(i,i)^-T in place (the whole block, zeros below the diagonal), one block per wave and
 // pass, column c of L(i,i)^-1 by forward substitution in lane c (the reads of L are broadcasts).  No barrier inside.
@@ -146,19 +186,27 @@ __device__ __forceinline__ void series_diag_inv_t(double* sm, int nb, int w, int
 //   the four lane groups of a row in the order ((q0 + q1) + q2) + q3 -> out_mean, out_var = (k** - sum VT^2) + noise_pred.
 // Rows past mq evaluate the last query again and are not written; beta's padding is 0 and VT's columns past n are exactly 0
 // (K21 masked, L's padding identity).
-template <int D>
+template <int D, bool SUM = false>
 __device__ __forceinline__ void series_predict_blocks(const ProgHdr& h, const int* ops, const double* prm, double* sig, const double* tpt,
                                                       const double* avec, const double* etab, const double* sm, int n, int nb,
-                                                      const double* tq, int mq, double noise_pred, double* om, double* ov) {
+                                                      const double* tq, int mq, double noise_pred, double* om, double* ov,
+                                                      [[maybe_unused]] const SeriesSumRows* sr = nullptr) {
   constexpr int E = 4, EV = D > 4 ? 2 : 4, NBMAX = SERIES_MAX_N / 16;
   static_assert(NBMAX * 16 == SERIES_MAX_N, "the cap is whole blocks");
   const int tid = threadIdx.x, l = tid & 63, w = tid >> 6, l15 = l & 15, lq = l >> 4;
   const int slot = SERIES_QSLOT + 16 * w + l15;
   for (int qb = w; qb * 16 < mq; qb += 4) {
     const int qi = qb * 16 + l15;
-    const double t = tq[qi < mq ? qi : mq - 1];
-    if (h.n_cp > 0) {
-      if (l < 16) series_sigma_cp(h, ops, prm, sig, slot, t);
+    int tix = qi < mq ? qi : mq - 1;
+    [[maybe_unused]] int code = 0;
+    if constexpr (SUM) {      // row g of the (M + 1) m coded rows: component i = g / m (code i + 1; the observable, last, 0) at query time g % m
+      const int i = tix / sr->m;
+      tix -= i * sr->m;
+      code = i < sr->M ? i + 1 : 0;
+    }
+    const double t = tq[tix];
+    if (SUM || h.n_cp > 0) {
+      if (l < 16) series_sigma_cp<SUM>(h, ops, prm, sig, slot, t, code);
       __builtin_amdgcn_wave_barrier();      // (LDS operations of one wave complete in order: its own lanes' entries, no workgroup barrier)
     }
     d4 VT[NBMAX];
@@ -218,7 +266,23 @@ __device__ __forceinline__ void series_predict_blocks(const ProgHdr& h, const in
     }
     const double mean = ((__shfl(ms, l15) + __shfl(ms, l15 + 16)) + __shfl(ms, l15 + 32)) + __shfl(ms, l15 + 48);
     const double sq = ((__shfl(ss, l15) + __shfl(ss, l15 + 16)) + __shfl(ss, l15 + 32)) + __shfl(ss, l15 + 48);
-    if (l < 16 && qi < mq) {
+    if constexpr (SUM) {
+      // the read-out in the same lanes (k_sum_readout's statements); code and addend of the row recomputed from g
+      if (l < 16 && qi < mq) {
+        const int i = qi / sr->m;
+        const double var = (kd - sq) + (1e-8 + (i == sr->M ? noise_pred : 0.0));      // JITTER on every row, noise_pred on X(T*)
+        double mr = (mean - sr->icpt) / sr->slope;
+        if (i == 0) mr = mr + sr->icpt / sr->slope;      // (the intercept counted once: on the F_1 rows)
+        const double vr = (1.0 / (sr->slope * sr->slope)) * var;
+        const bool ok = isfinite(mr) && vr >= 0.0;
+        if (!ok) atomicMin(sr->rowbad, qi + 1);
+        const double sd = ok ? sqrt(vr) : __builtin_nan("");
+        om[qi] = mr;
+        ov[qi] = vr;
+        double* xo = sr->ox + (long long)qi * sr->nq;
+        for (int k = 0; k < sr->nq; ++k) xo[k] = fma(sd, sr->z[k], mr);
+      }
+    } else if (l < 16 && qi < mq) {
       om[qi] = mean;
       ov[qi] = (kd - sq) + noise_pred;
     }
@@ -244,6 +308,52 @@ __device__ __forceinline__ void series_prior_predict(const SeriesPredArgs& a, in
   const int mq = (int)(a.q_off[a.series[p] + 1] - q0);
   series_predict_blocks<D>(h, ops, prm, sig, smem, smem, etab, smem + m.o_blk, 0, 0, a.ts_pred + q0, mq, a.noise_pred[p],
                            a.out_mean + a.out_off[p], a.out_var + a.out_off[p]);
+}
+
+// The decomposition twin's rows of one particle (P2 on the (M + 1) mq coded rows, read out in the same lanes) and, behind ONE
+// workgroup barrier, the row-level verdict: a particle with a row whose raw variance is negative or NaN, or whose raw mean is not
+// finite, has NaN in its whole blocks.  Returns 0, or the smallest such g + 1 (the same in every thread).  rowbad: an LDS word no
+// wave still reads (Wl's first: the value's reduction has been read by the wave that sets it).
+template <int D>
+__device__ __forceinline__ int series_sum_rows(const SeriesSumArgs& a, int p, const ProgHdr& h, const int* ops, const double* prm, double* sig,
+                                               const double* tpt, const double* avec, const double* etab, const double* sm, int n, int nb,
+                                               long long q0, int mq, int* rowbad) {
+  const int tid = threadIdx.x;
+  const int sidx = a.series[p];
+  const int rows = (a.M + 1) * mq;
+  double* om = a.out_mean + a.out_off[p];
+  double* ov = a.out_var + a.out_off[p];
+  double* ox = a.out_x + (long long)a.nq * a.out_off[p];
+  const SeriesSumRows sr{mq, a.M, a.nq, a.y_slope[sidx], a.y_intercept[sidx], a.z, ox, rowbad};
+  series_predict_blocks<D, true>(h, ops, prm, sig, tpt, avec, etab, sm, n, nb, a.ts_pred + q0, rows, a.noise_pred[p], om, ov, &sr);
+  __syncthreads();
+  const int rb = *rowbad;
+  if (rb == 0x7fffffff) return 0;
+  for (int g = tid; g < rows; g += 256) { om[g] = __builtin_nan(""); ov[g] = __builtin_nan(""); }
+  for (long long i = tid; i < (long long)rows * a.nq; i += 256) ox[i] = __builtin_nan("");
+  return rb;
+}
+
+// ... on an EMPTY series: the prior of every part — means 0, var_i = K_i(t, t) + 1e-8, X also + noise_pred — through the same rows
+// (series_prior_predict's staging).  Returns series_sum_rows' verdict.
+template <int D>
+__device__ __forceinline__ int series_prior_predict_sum(const SeriesSumArgs& a, int p, double* smem) {
+  const int tid = threadIdx.x;
+  const ProgHdr h = a.hdr[p];
+  const SeriesLds m = series_pred_lds(0, h.n_ops, h.n_prm, h.n_cp);
+  double* etab = smem + m.o_etab;
+  double* prm = smem + m.o_prm;
+  int* ops = reinterpret_cast<int*>(smem + m.o_ops);
+  double* sig = smem + m.o_sig;
+  int* rowbad = reinterpret_cast<int*>(smem);
+  if (AGP_EXP_TABLE && tid < AGP_EXP_TAB_N) etab[tid] = fm::c_exp_tab[tid];
+  for (int i = tid; i < h.n_prm + 2; i += 256) prm[i] = a.prm[h.prm_off + i];
+  for (int i = tid; i < h.n_ops; i += 256) ops[i] = (int)a.ops[h.op_off + i];
+  if (tid == 0) *rowbad = 0x7fffffff;
+  __syncthreads();
+  const long long q0 = a.q_off[a.series[p]];
+  const int mq = (int)(a.q_off[a.series[p] + 1] - q0);
+  return series_sum_rows<D>(a, p, h, ops, prm, sig, smem, smem, etab, smem + m.o_blk, 0, 0, q0, mq, rowbad);
 }
 
 // The read-out of the sampling twin: from the joint factor as stage 5 leaves it (rows [ntr, ntr + m) of the packed blocks are
@@ -385,11 +495,12 @@ __device__ __forceinline__ void series_sample_readout(const SeriesSampleArgs& a,
 }
 
 // The body of every instantiation: stages 1-5 (value kernel, probe, gradient kernel, predictive kernel alike — the same statements),
-// with GS > 0 (gradient tape of GS nodes) the stages G1-G5 behind them, with SeriesPredArgs the stages P1-P2.
+// with GS > 0 (gradient tape of GS nodes) the stages G1-G5 behind them, with SeriesPredArgs or SeriesSumArgs the stages P1-P2.
 template <int D, bool PROBE, int GS, class ArgsT>
 __device__ __forceinline__ void series_body(const ArgsT& a, double* smem) {
   constexpr int E = 4;
-  constexpr bool PRED = std::is_same_v<ArgsT, SeriesPredArgs>;
+  constexpr bool SUM = std::is_same_v<ArgsT, SeriesSumArgs>;         // the decomposition twin: composite programs, coded query rows
+  constexpr bool PRED = std::is_same_v<ArgsT, SeriesPredArgs> || SUM;    // the predictive branches (P1, P2, series_pred_lds) are shared
   constexpr bool PROBA = std::is_same_v<ArgsT, SeriesProbaArgs>;      // the held-out twin: n below is the JOINT length
   constexpr bool SAMPLE = std::is_same_v<ArgsT, SeriesSampleArgs>;    // the sampling twin: the same, the query rows' right-hand side 0
   constexpr bool JOINT = PROBA || SAMPLE;
@@ -414,7 +525,11 @@ __device__ __forceinline__ void series_body(const ArgsT& a, double* smem) {
     }
   }
   if (n <= 0 || n > SERIES_MAX_N) {      // (the host answers empty series itself and refuses long ones: never launched ...
-    if constexpr (PRED) {                // ... but for the prior predictive of an empty series)
+    if constexpr (SUM) {                 // ... but for the prior predictive of an empty series)
+      const int rb = n == 0 ? series_prior_predict_sum<D>(a, p, smem) : 0;
+      if (tid == 0) { a.out_lp[p] = 0.0; a.out_info[p] = rb; }
+      return;
+    } else if constexpr (PRED) {
       if (n == 0) series_prior_predict<D>(a, p, smem);
     }
     if (tid == 0) { a.out_lp[p] = 0.0; a.out_info[p] = 0; }
@@ -479,7 +594,7 @@ __device__ __forceinline__ void series_body(const ArgsT& a, double* smem) {
 
     // ---- 2. per-point tables (cov_prologue's arithmetic) ----
     if (h.n_cp > 0) {
-      if (tid < np) series_sigma_cp(h, ops, prm, sig, tid, tpt[tid]);
+      if (tid < np) series_sigma_cp<SUM>(h, ops, prm, sig, tid, tpt[tid]);      // (SUM: training points are the observable, code 0)
       __syncthreads();
     }
 
@@ -594,15 +709,33 @@ __device__ __forceinline__ void series_body(const ArgsT& a, double* smem) {
     double* om = a.out_mean + a.out_off[p];
     double* ov = a.out_var + a.out_off[p];
     if (tid == 0) rvec[0] = (double)bad;      // (wave 0 keeps the first bad pivot; rvec is dead)
+    [[maybe_unused]] int* rowbad = reinterpret_cast<int*>(Wl);      // SUM: the first row without a raw marginal (Wl is dead: this
+    if constexpr (SUM) {                                            // thread's wave has read the value's reduction out of it)
+      if (tid == 0) *rowbad = 0x7fffffff;
+    }
     // ---- P1. the diagonal blocks L(i,i)^-T in place (G1's statements; the log-det has been read) ----
     series_diag_inv_t(sm, nb, w, l);
     __syncthreads();
-    if (rvec[0] != 0.0) {      // a bad pivot: NaN in the particle's whole block (the value is NaN already), nothing else
-      for (int q = tid; q < mq; q += 256) { om[q] = __builtin_nan(""); ov[q] = __builtin_nan(""); }
+    if constexpr (SUM) {
+      if (rvec[0] != 0.0) {      // a bad pivot: NaN in all of the particle's outputs, info stays the pivot
+        const int rows = (a.M + 1) * mq;
+        double* ox = a.out_x + (long long)a.nq * a.out_off[p];
+        for (int g = tid; g < rows; g += 256) { om[g] = __builtin_nan(""); ov[g] = __builtin_nan(""); }
+        for (long long i = tid; i < (long long)rows * a.nq; i += 256) ox[i] = __builtin_nan("");
+        return;
+      }
+      // ---- P2 on the (M + 1) mq coded rows, read out in the same lanes; a failed row marks the particle: info = n + g + 1 ----
+      const int rb = series_sum_rows<D>(a, p, h, ops, prm, sig, tpt, avec, etab, sm, n, nb, q0, mq, rowbad);
+      if (rb != 0 && tid == 0) a.out_info[p] = n + rb;
       return;
+    } else {
+      if (rvec[0] != 0.0) {      // a bad pivot: NaN in the particle's whole block (the value is NaN already), nothing else
+        for (int q = tid; q < mq; q += 256) { om[q] = __builtin_nan(""); ov[q] = __builtin_nan(""); }
+        return;
+      }
+      // ---- P2. query blocks, wave by wave ----
+      series_predict_blocks<D>(h, ops, prm, sig, tpt, avec, etab, sm, n, nb, a.ts_pred + q0, mq, a.noise_pred[p], om, ov);
     }
-    // ---- P2. query blocks, wave by wave ----
-    series_predict_blocks<D>(h, ops, prm, sig, tpt, avec, etab, sm, n, nb, a.ts_pred + q0, mq, a.noise_pred[p], om, ov);
   }
 
   if constexpr (GS > 0) {
@@ -811,6 +944,15 @@ __global__ __launch_bounds__(256) void k_series_sample_fill(SeriesSampleFillArgs
 // value and in the value kernel's LDS (agp_predict_series_batch).
 template <int D>
 __global__ __launch_bounds__(256, 2) void k_series_predict(SeriesPredArgs a) {
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  series_body<D, false, 0>(a, smem);
+}
+
+// predict_sum's numbers of one (series, particle) pair by one workgroup: the predictive twin on the particle's composite program and
+// the (M + 1) m coded rows F_1(T*) .. F_M(T*), X(T*), raw-space marginals and their Normal quantiles read out in the lanes that
+// formed them (agp_predict_sum_series_batch).
+template <int D>
+__global__ __launch_bounds__(256, 2) void k_series_predict_sum(SeriesSumArgs a) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   series_body<D, false, 0>(a, smem);
 }

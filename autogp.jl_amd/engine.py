@@ -39,7 +39,7 @@ EXPORTED_SYMBOLS = [
     "agp_remove_data", "agp_get_remove_stats", "agp_set_remove_update", "agp_remove_data_multi",
     "agp_debug_factor_batch", "agp_logpdf_series_batch", "agp_debug_series_factor", "agp_logpdf_grad_series_batch",
     "agp_predict_series_batch", "agp_debug_remove_factor", "agp_predict_quantile_series_batch",
-    "agp_predict_logpdf_series_batch", "agp_predict_sample_series_batch",
+    "agp_predict_logpdf_series_batch", "agp_predict_sample_series_batch", "agp_predict_sum_series_batch",
 ]
 COMM_ID_BYTES = 128
 SERIES_MAX_N = 176      # AGP_SERIES_MAX_N of include/autogp_hip.h: the longest series of logpdf_series_batch
@@ -122,6 +122,9 @@ def load_library(path=None):
                                                     u8p, ip, dp, dp, dp, dp, dp, dp, C.c_int64, C.POINTER(C.c_uint64), ip, dp, dp, ip,
                                                     dp, C.POINTER(C.c_int64), dp, C.POINTER(C.c_int64), ip]
     lib.agp_predict_sample_series_batch.restype = C.c_int
+    lib.agp_predict_sum_series_batch.argtypes = [vp, C.c_int32, C.POINTER(C.c_int64), dp, dp, C.POINTER(C.c_int64), dp, C.c_int32, C.c_int32,
+                                                 ip, ip, u8p, ip, dp, dp, dp, dp, dp, dp, C.c_int64, dp, dp, dp, C.POINTER(C.c_int64), dp, ip]
+    lib.agp_predict_sum_series_batch.restype = C.c_int
     lib.agp_logpdf_grad_batch.argtypes = [vp, C.c_int64, C.c_int32, ip, u8p, ip, dp, dp, dp, dp, dp, ip]
     lib.agp_logpdf_grad_batch.restype = C.c_int
     lib.agp_logpdf_grad.argtypes = [vp, C.c_int64, u8p, C.c_int32, dp, C.c_int32, C.c_double, dp, dp, dp, ip]
@@ -391,6 +394,7 @@ def pack_heldout(heldout, q_off, y_transforms=None):
 
 SeriesScores = collections.namedtuple("SeriesScores", "logpdf terms series_logp info")
 SeriesSamples = collections.namedtuple("SeriesSamples", "x component mean cov info")
+SeriesSums = collections.namedtuple("SeriesSums", "mean var x logpdf info")
 
 
 def check_remove_indexes(indexes, n_max):
@@ -753,6 +757,72 @@ class GPEngine:
             mean = [mean[out_off[p]:out_off[p + 1]] for p in range(P)]
             cov = [cov[cov_off[p]:cov_off[p + 1]].reshape(len(mean[p]), len(mean[p])).T for p in range(P)]
         return SeriesSamples(xs_, comp[:S * Rp].reshape(S, Rp), mean, cov, info)
+
+    def predict_sum_series_batch(self, series, queries, split_nodes, noises, series_index, q=(), y_transforms=None, noise_pred=None,
+                                 want_var=False, want_logpdf=False, check=True, programs=None):
+        """agp_predict_sum_series_batch: the decompositions of many short series in one fused launch — predict_sum_batch's twin for
+        callers that hold one model per short series, with predict_series_batch's series / query arguments and statelessness.
+        split_nodes holds each particle's M component kernels (P lists of M nodes, e.g. split_kernel_sop of its kernel); particle p
+        decomposes series[series_index[p]] at queries[series_index[p]].  q: the quantiles (a sequence, possibly empty);
+        y_transforms: one (slope, intercept) per series (scaled = slope * raw + intercept; None: (1, 0)); noise_pred: None (each
+        particle's noise), a scalar or one per particle — it goes on the observable rows only.  Returns SeriesSums(mean, var, x,
+        logpdf, info): mean[p] ((M+1) m_s,) the raw means of the rows F_1 .. F_M, X with predict_mvn_sum's intercept correction on
+        F_1, var[p] their raw variances (want_var, else None), x[p] ((M+1) m_s, nq) their Normal quantiles — views cut from the
+        particle-major arrays, so np.stack of the adjacent particles of one series is the block mixture_quantile takes — logpdf (P,)
+        with want_logpdf; info (P,): a bad pivot, or n_s + j for the first joint row j (1-based) without a raw marginal.
+        programs: the components encoded beforehand — gp.encode_batch of the P M component kernels, particle by particle — in
+        place of split_nodes (then ignored)."""
+        noises = _f64(noises)
+        if programs is not None:
+            P = noises.shape[0] if noises.ndim == 1 else -1
+            M, rest = divmod(programs[0].shape[0] - 1, P) if P > 0 else (1, programs[0].shape[0] - 1)
+            if rest != 0 or M < 1:
+                raise ValueError("programs must hold the same number (>= 1) of components for every particle")
+        else:
+            split_nodes = [list(c) for c in split_nodes]
+            P = len(split_nodes)
+            M = len(split_nodes[0]) if P else 1
+            if M < 1 or any(len(c) != M for c in split_nodes):
+                raise ValueError("every particle must have the same number (>= 1) of components")
+            programs = _gp.encode_batch([nd for c in split_nodes for nd in c]) if P else (np.zeros(1, np.int32), np.zeros(1, np.uint8),
+                                                                                         np.zeros(1, np.int32), np.zeros(1))
+        pt_off, ts, xs = pack_series(series)
+        S = pt_off.shape[0] - 1
+        if noises.shape != (P,):
+            raise ValueError("one noise per particle required")
+        sidx = np.ascontiguousarray(np.asarray(series_index, dtype=np.int32))
+        if sidx.shape != (P,):
+            raise ValueError("one series index per particle required")
+        if noise_pred is not None and np.ndim(noise_pred) == 0:
+            noise_pred = np.full(P, float(noise_pred))      # (a scalar serves every particle)
+        qpack = pack_queries(queries, S, noise_pred, P)
+        slope = icpt = None
+        if y_transforms is not None:
+            yt = _f64(y_transforms)
+            if yt.shape != (S, 2):
+                raise ValueError(f"y_transforms has shape {yt.shape}, expected ({S}, 2): one (slope, intercept) per series")
+            slope, icpt = np.ascontiguousarray(yt[:, 0]), np.ascontiguousarray(yt[:, 1])
+        qa = _f64(np.atleast_1d(np.asarray(q, dtype=np.float64)))
+        if qa.ndim != 1:
+            raise ValueError("q must be a sequence of quantiles")
+        nq = qa.shape[0]
+        m_s = np.diff(qpack[0])
+        total = (M + 1) * int(sum(m_s[i] for i in sidx if 0 <= i < S))      # (an index outside is the library's to report)
+        mean = np.empty(max(1, total)); var = np.empty(max(1, total)) if want_var else None
+        x = np.empty(max(1, total * nq)) if nq else None
+        out_off = np.zeros(P + 1, dtype=np.int64)
+        lp = np.empty(max(1, P), dtype=np.float64) if want_logpdf else None
+        info = np.zeros(max(1, P), dtype=np.int32)
+        a = _series_ctypes((pt_off, ts, xs, programs, P, noises, sidx), qpack)      # (.., ts_pred | P | series, ..): M travels behind P
+        self._check(self._lib.agp_predict_sum_series_batch(
+            self._ctx, *a[:7], M, *a[7:], _dp(slope), _dp(icpt), _dp(qa) if nq else None, nq, _dp(mean), _dp(var), _dp(x),
+            out_off.ctypes.data_as(C.POINTER(C.c_int64)), _dp(lp), _ip(info)))
+        info = info[:P]
+        _raise_first_bad(info, check)
+        oo = out_off.tolist()
+        cut = lambda arr: [arr[oo[p]:oo[p + 1]] for p in range(P)]
+        xs_ = [x[nq * oo[p]:nq * oo[p + 1]].reshape(oo[p + 1] - oo[p], nq) if nq else np.empty((oo[p + 1] - oo[p], 0)) for p in range(P)]
+        return SeriesSums(cut(mean), cut(var) if want_var else None, xs_, lp[:P] if want_logpdf else None, info)
 
     def logpdf_batch_extend(self, nodes, noises, n=None, check=True, programs=None):
         """agp_logpdf_batch_extend: like logpdf_batch, but the factors stay resident and a later call on a longer
@@ -1879,6 +1949,39 @@ def predict_sum(engine, nodes, noises, log_weights, ts_pred, LeafType, y_transfo
     }
     for j, qv in enumerate(qs):
         out[f"y_{qv!r}"] = np.concatenate([x[k, blk, j] for k, _, blk in rows]) if rows else np.zeros(0)
+    return out
+
+
+def predict_sum_series(engine, series, queries, nodes, noises, series_index, log_weights, LeafType, y_transforms=None, noise_pred=None,
+                       quantiles=()):
+    """predict_sum for callers that hold one model per short series: particle p belongs to the model of series[series_index[p]],
+    whose mixture weighs it by the softmax of log_weights over THAT series' particles (pack_series_mixture); every particle's
+    kernel is split by split_kernel_sop(node, LeafType) and ONE call of GPEngine.predict_sum_series_batch decomposes them all.
+    Returns one dict of columns per series — ds, y_mean, component, particle, weight, y_<q> — in predict_sum's row order: per
+    particle of the series (numbered from 1 within it), component 0 (the observable), then 1 (the addends with a LeafType factor),
+    then 2 (the others); a series without particles gives empty columns.  Raises PosDefException when a particle has no result."""
+    S = len(series)
+    lists, w = pack_series_mixture(series_index, S, log_weights=log_weights)
+    split = [_gp.split_kernel_sop(nd, LeafType) for nd in nodes]
+    qs = [float(v) for v in quantiles]
+    r = engine.predict_sum_series_batch(series, queries, split, noises, series_index, q=qs, y_transforms=y_transforms,
+                                        noise_pred=noise_pred)
+    out = []
+    for s, sel in enumerate(lists):
+        tq = _f64(queries[s]); m = tq.shape[0]
+        blocks = [slice(2 * m, 3 * m), slice(0, m), slice(m, 2 * m)]         # Y, F_1, F_2
+        rows = [(k, int(p), c, blk) for k, p in enumerate(sel) for c, blk in enumerate(blocks)]
+        cat = lambda parts: np.concatenate(parts) if parts else np.zeros(0)
+        d = {
+            "ds": cat([tq for _ in rows]),
+            "y_mean": cat([r.mean[p][blk] for _, p, _, blk in rows]),
+            "component": np.repeat([c for _, _, c, _ in rows], m).astype(np.int64),
+            "particle": np.repeat([k + 1 for k, _, _, _ in rows], m).astype(np.int64),
+            "weight": np.repeat([w[p] for _, p, _, _ in rows], m),
+        }
+        for j, qv in enumerate(qs):
+            d[f"y_{qv!r}"] = cat([r.x[p][blk, j] for _, p, _, blk in rows])
+        out.append(d)
     return out
 
 

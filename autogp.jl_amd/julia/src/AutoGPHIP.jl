@@ -860,6 +860,59 @@ function predict_sum_batch(eng::Engine, splits::AbstractVector, noises::Vector{F
     return mu, x, info
 end
 
+"Decompositions of many short series in one fused launch (agp_predict_sum_series_batch): `predict_sum_batch` for callers that hold
+one model per short series, with `predict_series_batch`'s series / query arguments and statelessness.  `splits[p]` holds particle
+`p`'s M component kernels (e.g. `GP.split_kernel_sop` of its kernel); particle `p` decomposes `series[series_index[p]]` (1-based) at
+`queries[series_index[p]]`.  `y_transforms[s] = (slope, intercept)` of series `s` (scaled = slope * raw + intercept; `nothing`:
+(1, 0)); `noise_pred` (`nothing`: each particle's noise) goes on the observable rows only.  Returns `(mean, var, x, logpdf, info)`:
+`mean[p]` / `var[p]` of length (M+1) m_s are the raw means and variances of the rows F_1 .. F_M, X (the intercept counted once, on
+F_1), `x[p]` of size (length(quantiles), (M+1) m_s) their Normal quantiles; throws `PosDefException` where a particle has no result."
+function predict_sum_series_batch(eng::Engine, series::Vector{<:Tuple{Vector{Float64},Vector{Float64}}}, queries::Vector{Vector{Float64}},
+                                  splits::AbstractVector, noises::Vector{Float64}, series_index::Vector{<:Integer};
+                                  quantiles::Vector{Float64}=Float64[],
+                                  y_transforms::Union{Nothing,Vector{Tuple{Float64,Float64}}}=nothing,
+                                  noise_pred::Union{Nothing,Vector{Float64}}=nothing)
+    all(q -> 0 < q < 1, quantiles) || error("Quantile must be in (0,1).")
+    P, M, op_off, ops, prm_off, prm = encode_splits(splits)
+    S = length(series)
+    (length(noises) == P && length(series_index) == P) || throw(ArgumentError("one noise and one series index per particle required"))
+    length(queries) == S || throw(ArgumentError("one vector of query times per series required"))
+    (noise_pred === nothing || length(noise_pred) == P) || throw(ArgumentError("one noise_pred per particle required"))
+    (y_transforms === nothing || length(y_transforms) == S) || throw(ArgumentError("one (slope, intercept) per series required"))
+    all(i -> 1 <= i <= S, series_index) || throw(ArgumentError("series index outside 1:$S"))
+    pt_off = Int64[0]; ts = Float64[]; xs = Float64[]; q_off = Int64[0]; tq = Float64[]
+    for (s, (t, x)) in enumerate(series)
+        length(t) == length(x) || throw(ArgumentError("series $s: ts and xs must have equal lengths"))
+        length(t) <= SERIES_MAX_N || throw(ArgumentError("series $s has $(length(t)) points, more than SERIES_MAX_N ($SERIES_MAX_N)"))
+        append!(ts, t); append!(xs, x); push!(pt_off, length(ts))
+        append!(tq, queries[s]); push!(q_off, length(tq))
+    end
+    isempty(ts) && (push!(ts, 0.0); push!(xs, 0.0))
+    isempty(tq) && push!(tq, 0.0)
+    sidx = Int32[Int32(i - 1) for i in series_index]
+    slope = y_transforms === nothing ? ones(Float64, max(1, S)) : Float64[t[1] for t in y_transforms]
+    icpt = y_transforms === nothing ? zeros(Float64, max(1, S)) : Float64[t[2] for t in y_transforms]
+    nq = length(quantiles)
+    total = (M + 1) * sum(Int[length(queries[i]) for i in series_index])
+    mean = Vector{Float64}(undef, max(1, total)); var = Vector{Float64}(undef, max(1, total))
+    x = Vector{Float64}(undef, max(1, nq * total))
+    out_off = zeros(Int64, P + 1)
+    out = Vector{Float64}(undef, max(1, P)); info = zeros(Int32, max(1, P))
+    np = noise_pred === nothing ? noises : noise_pred
+    GC.@preserve pt_off ts xs q_off tq sidx op_off ops prm_off prm noises np slope icpt quantiles mean var x out_off out info check(eng, ccall((:agp_predict_sum_series_batch, LIB), Cint,
+        (Ptr{Cvoid}, Int32, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Int32, Int32, Ptr{Int32}, Ptr{Int32},
+         Ptr{UInt8}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64,
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Ptr{Int32}),
+        eng.ptr, S, pt_off, ts, xs, q_off, tq, P, M, sidx, op_off, ops, prm_off, prm, noises, np, slope, icpt,
+        nq == 0 ? Ptr{Float64}(C_NULL) : pointer(quantiles), nq, mean, var, nq == 0 ? Ptr{Float64}(C_NULL) : pointer(x), out_off, out, info))
+    k = findfirst(!=(0), info[1:P])
+    isnothing(k) || throw(LinearAlgebra.PosDefException(info[k]))
+    means = [mean[out_off[p] + 1:out_off[p + 1]] for p in 1:P]
+    vars = [var[out_off[p] + 1:out_off[p + 1]] for p in 1:P]
+    xq = [reshape(x[nq * out_off[p] + 1:nq * out_off[p + 1]], nq, Int(out_off[p + 1] - out_off[p])) for p in 1:P]
+    return means, vars, xq, out[1:P], info[1:P]
+end
+
 # ------------------------------------------------------------------------------------------------------------------
 # multi-process deployment: one Julia process per GPU (Distributed / MPI), log-weights all-gathered through the engine
 # ------------------------------------------------------------------------------------------------------------------

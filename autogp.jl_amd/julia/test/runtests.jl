@@ -164,6 +164,43 @@ kernels() = GP.Node[
         @test eng.n_max == 700      # the resident series is untouched
     end
 
+    @testset "many short series: decompositions in one call (stateless)" begin
+        ks = kernels()[[6, 7, 8]]
+        shapes = ((0, 5), (17, 6), (126, 12), (144, 36))       # (training points, query points)
+        sers = [(ts[1:n], xs[1:n]) for (n, _) in shapes]
+        qs = [ts[n + 1:n + m] for (n, m) in shapes]
+        yts = [(1.0 + 0.5 * s, 0.1 * s) for s in eachindex(sers)]
+        quantiles = [0.025, 0.5, 0.975]
+        splits = []; sidx = Int[]
+        for s in eachindex(sers), k in ks
+            push!(splits, collect(GP.split_kernel_sop(k, GP.Periodic))); push!(sidx, s)
+        end
+        P = length(splits)
+        means, vars, x, lp, info = H.predict_sum_series_batch(eng, sers, qs, splits, fill(noise, P), sidx; quantiles=quantiles,
+                                                              y_transforms=yts)
+        @test all(info .== 0)
+        for (p, s) in enumerate(sidx)
+            n, m = shapes[s]
+            a, b = yts[s]
+            @test length(means[p]) == 3m && size(x[p]) == (3, 3m)
+            @test x[p][2, :] == means[p]                       # the median of a Normal is its mean: fma(sd, 0, mean)
+            @test all(x[p][1, :] .<= means[p]) && all(means[p] .<= x[p][3, :])
+            n == 0 && continue
+            # the reference's route on the series' own data
+            mu, S, _ = GP.infer_gp_sum(splits[p], noise, ts[1:n], xs[1:n], qs[s])
+            mr = (mu .- b) ./ a
+            mr[1:m] .+= b / a
+            @test maximum(abs.(means[p] .- mr)) <= 1e-8 * max(1.0, maximum(abs.(mr)))
+            @test maximum(abs.(vars[p] .- diag(S) ./ a^2)) <= 1e-8 * max(1.0, maximum(abs.(diag(S) ./ a^2)))
+        end
+        # series 3 alone: the same bits
+        sel = findall(==(3), sidx)
+        m3, v3, x3, _, _ = H.predict_sum_series_batch(eng, [sers[3]], [qs[3]], splits[sel], fill(noise, length(sel)),
+                                                      fill(1, length(sel)); quantiles=quantiles, y_transforms=yts[3:3])
+        @test m3 == means[sel] && v3 == vars[sel] && x3 == x[sel]
+        @test eng.n_max == 700      # the resident series is untouched
+    end
+
     @testset "not positive definite" begin
         bad = GP.Linear(0.0, 0.0, -0.01)
         @test_throws LinearAlgebra.PosDefException H.logpdf(eng, bad, 0.1, 700)

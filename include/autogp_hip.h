@@ -330,6 +330,47 @@ int agp_predict_sample_series_batch(agp_ctx* ctx, int32_t S, const int64_t* pt_o
                                     double* out_cov /* cov_off[P], or NULL */, int64_t* cov_off /* P+1, or NULL */,
                                     int32_t* out_info /* P */);
 
+/* DECOMPOSITIONS of many short series in one call: predict_sum / predict_mvn_sum's marginals (src/api.jl:898-1034 on GP.infer_gp_sum,
+ * src/GP.jl:904-993) for callers that hold one model per short series — agp_predict_sum_batch's twin, on agp_predict_series_batch's
+ * route: the workgroup that has factored K11 in LDS solves the coded query rows against it in registers and reads them out itself.
+ * Arguments S .. ts_pred as agp_predict_series_batch.  Components: every particle has M >= 1 component kernels (split_kernel_sop
+ * gives M = 2); particle p's are the CSR entries [p M, (p + 1) M) of op_off / prm_off (P M + 1 offsets each), as in
+ * agp_infer_gp_sum_batch; its model is X = F_1 + .. + F_M + noise on series[p], evaluated as the ONE composite program
+ * K_1 SEL_1 * K_2 SEL_2 * + .. on coded points.  noise / noise_pred (P; noise_pred NULL: noise) as agp_predict_series_batch.
+ * y_slope / y_intercept (S each, or NULL: 1 / 0): the transform of series s (scaled = a_s raw + b_s).  q (nq >= 0 values in (0, 1)).
+ * Rows: series s with m_s query times has (M + 1) m_s joint rows g in the reference's order F_1(T*) .. F_M(T*), X(T*); row g is
+ *   component i = g / m_s at query time g % m_s.  Scaled posterior: mean = K21 K11^-1 x, var = (k** - |K21 L^-T|^2) + 1e-8, and
+ *   + noise_pred[p] on the X rows only.  Returned are predict_sum's RAW numbers, formed as agp_predict_sum_batch forms them:
+ *   out_mean = (mean - b_s) / a_s, + b_s / a_s on the F_1 rows (the intercept counted once); out_var = (1 / (a_s a_s)) var;
+ *   out_x[row nq + k] = fma(sqrt(out_var), ndtri(q[k]), out_mean).
+ * Output layout, particle-major: the entry writes out_off[p] = (M + 1) sum_{p' < p} m_{series[p']} (P + 1 values); particle p owns
+ *   (M + 1) m_s means (and variances; out_var may be NULL) from out_off[p] and nq quantiles per row from nq out_off[p] (out_x: NULL
+ *   iff nq == 0).  Adjacent particles of one series form the (P_s, (M + 1) m_s) block agp_mixture_quantile / agp_mixture_moments take.
+ * out_logpdf (P, or NULL): the training log marginal likelihood of the summed model.  out_info[p]: the first bad pivot of K11 (NaN
+ *   then in all of the particle's outputs), else n_s + g + 1 for the first row g whose raw variance is negative or NaN or whose raw
+ *   mean is not finite (NaN then in the particle's whole mean / variance / quantile blocks), else 0; no other particle changes.
+ * m_s == 0 writes nothing for the series' particles but out_logpdf / out_info; an EMPTY series with query points gives the prior of
+ *   every part: mean 0, var_i = K_i(t, t) + 1e-8, X also + noise_pred.  P == 0 is AGP_OK and touches nothing.
+ * Stateless and re-entrant as agp_predict_series_batch: one upload, one synchronisation; the resident series, the factor store and
+ *   every counter are left alone; copies are not deduplicated.  A particle's bits depend only on its own series, queries, components,
+ *   noises and transform — not on the rest of the call, its order, or how it is split into launches.
+ * The WHOLE call is rejected, and nothing is written to any output, with everything agp_predict_series_batch reports, and with
+ *   AGP_ERR_ARG: M < 1, malformed component offsets (names particle and component), nq < 0, a q[k] outside (0, 1) or NaN, a y_slope
+ *     that is 0 or not finite or a y_intercept that is not finite (names the series), an output of 2^31 elements or more;
+ *   AGP_ERR_PROGRAM (names the particle): an unknown opcode, a composite over AGP_MAX_OPS nodes, an evaluation stack deeper than 8, or
+ *     per-point tables that do not fit the kernel's 160 KiB at the series' length — every selector takes one 2 KiB table like a
+ *     ChangePoint node, so at AGP_SERIES_MAX_N points and M = 2 a composite with 8 ChangePoint nodes (23 nodes, 28 parameters,
+ *     10 tables: 163 280 of 163 840 bytes) fits and one with 9 (165 376 bytes) does not; the predictive entry's limit there is 10.
+ * Not here: mean functions, the joint covariance of the parts (predict_mvn_sum's full matrix), n_s > AGP_SERIES_MAX_N. */
+int agp_predict_sum_series_batch(agp_ctx* ctx, int32_t S, const int64_t* pt_off /* S+1 */, const double* ts, const double* xs,
+                                 const int64_t* q_off /* S+1 */, const double* ts_pred, int32_t P, int32_t M,
+                                 const int32_t* series /* P */, const int32_t* op_off /* P*M+1 */, const uint8_t* ops,
+                                 const int32_t* prm_off /* P*M+1 */, const double* prm, const double* noise /* P */,
+                                 const double* noise_pred /* P or NULL = noise */, const double* y_slope /* S or NULL */,
+                                 const double* y_intercept /* S or NULL */, const double* q, int64_t nq,
+                                 double* out_mean, double* out_var /* or NULL */, double* out_x /* NULL iff nq == 0 */,
+                                 int64_t* out_off /* P+1 */, double* out_logpdf /* P or NULL */, int32_t* out_info /* P */);
+
 /* agp_logpdf_batch with BLOCK-EXTENSION of resident factors.  The data-annealing loop re-scores
  * every particle on a longer prefix of the same series with unchanged kernel parameters — the reweight step
  * (src/inference_smc_anneal_data.jl:206-217), add_data! (src/api.jl:426-443), scripts/online.jl:200 — and the
