@@ -1,6 +1,23 @@
 // Host side of the C ABI (include/autogp_hip.h), unit 1: program compilation, workspace slots, the value / gradient sweeps
 // and the core entries (init, data, logpdf, coalescing).  gfx950 only; no CPU fallback — every compute entry fails loudly
 // if the HIP runtime / device is unavailable.  Shared declarations: agp_host.hpp.
+//
+// The resident-series sweep, logpdf_batch_impl, reads as its stages (all in this file, in the order they run):
+//   checks
+//   structured_value_split   the Toeplitz class by the Schur recursion beside a nested dense sweep (consecutive_ranks: the one
+//                            scan of h_rank); behind it, the whole batch through the store under tl_dense_via_store
+//   plan_tables              SweepPlan: the TableMode, its units and strides, ge_tab, flow_hint -> compile_opts -> compile_batch
+//   count_sweep              the sweep's counters, what a compiled gradient batch is still refused for
+//   classify_gradients       GradClasses: lag-domain / Toeplitz / FFT / polynomial flags;  structured_grad_split: the class
+//                            without a dense factor, with its residency and sticky-key lookups
+//   find_store_hits          StoreHits: resident factors; owns the store's lock to the end of the sweep
+//   claim_outputs            SweepSlot: stream and device outputs;  plan_geometry completes the plan (const from there on)
+//   sweep_buffers, pack_stage (SweepStage), upload_stage, sweep_lag_tables
+//   per chunk                chunk_factor;  chunk_gradient, its particle list ordered by order_gradients (GradOrder)
+//   collect_timing           (profiled sweeps)
+//   finish_on_stream | copy_out, repeat_rejected_toeplitz, repeat_sorted_rejects
+// scatter_results hands a nested sweep's results back by an index list; dense_part packs, recurses and scatters for both splits.
+// The body owns what outlives the stages: StoreHits, the SlotGuard and SweepKeep (host memory of the enqueued copies).
 #include "agp_host.hpp"
 
 thread_local std::string g_err_noctx;
@@ -577,8 +594,6 @@ hipError_t run_factor(hipStream_t st, CholArgs ca, int nfac, int dcov, Prof* pf,
 }
 
 
-// Core of agp_logpdf_batch{,_device} and agp_logpdf_grad_batch.  d_out_* may be caller device
-// buffers (user_stream path) or null (results copied to host h_out_*).
 // Factor-store lookup for a compiled batch (sorted order q -> caller index bt.order[q]): src_slot[q] = the slot that holds
 // the POSITIVE DEFINITE factor of particle q for exactly the prefix n (else -1), i0v[q] = nt for those (no tile row left to
 // compute).  Returns the number found; `lk` is held on return iff it is > 0 (the caller copies the factors out, then
@@ -852,120 +867,167 @@ struct TlClear {          // a thread-local switch cleared for a scope (the stor
 // (set around the repeat of particles whose Toeplitz downdate was rejected: the nested sweep takes L^-T for them)
 static thread_local bool tl_no_toep = false;
 
-int logpdf_batch_impl(agp_ctx* c, int64_t n, const Particles& pp, double* h_out_lp, int32_t* h_out_info, double* d_user_lp,
-                      int32_t* d_user_info, hipStream_t user_stream, bool use_user_stream, GradOut* go, bool allow_lag) {
-  const int P = pp.P;
-  if (!c) return fail(nullptr, AGP_ERR_ARG, "null context");
-  if (P < 0 || n < 0) return fail(c, AGP_ERR_ARG, "negative size");
-  if (P == 0) return AGP_OK;
-  if (!pp.complete()) return fail(c, AGP_ERR_ARG, "null program/noise pointer");
-  if (const int rc = check_resident(c, n)) return rc;
-  HIPCHK(c, hipSetDevice(c->device));
+// ---- the stages of logpdf_batch_impl, in the order its body lists them ---------------------------------------------------------
 
-  // Structured value sweep (opt-in): on a regular grid, the particles whose kernel is a sum of stationary subtrees and Linear
-  // leaves need no factorisation at all — Toeplitz + rank 2: Schur algorithm, O(n^2) — the others (and every particle the
-  // structured sweep refuses) take the dense path below.
-  // The sweep's points must be n CONSECUTIVE grid points: the whole series (any order), or a prefix of a series in time order
-  // (scripts/online.jl feeds the observations that way; fit_smc!(shuffle = false)) — a prefix of a shuffled grid is not.
-  int32_t value_rank0 = 0;
-  bool value_consecutive = n == c->n_max;
-  if (!go && c->toeplitz && !tl_in_toeplitz && allow_lag && c->lag_enable && c->lag_ok && c->lag_contig && n > 1 && n < c->n_max &&
-      (int64_t)c->h_rank.size() >= n) {
-    int32_t lo = c->h_rank[0], hi = c->h_rank[0];
-    for (int64_t i = 1; i < n; ++i) { lo = std::min(lo, c->h_rank[(size_t)i]); hi = std::max(hi, c->h_rank[(size_t)i]); }
-    value_consecutive = (int64_t)hi - lo + 1 == n;
-    value_rank0 = lo;
-  }
-  if (!go && c->toeplitz && !tl_in_toeplitz && allow_lag && c->lag_enable && c->lag_ok && c->lag_contig && n > 0 && value_consecutive && c->n_max <= 4096 &&
-      h_out_lp && !d_user_lp && !d_user_info && !use_user_stream && !c->profiling) {
-    std::vector<int> part[2];
-    // (malformed offsets are left to compile_batch's diagnosis on the plain path: the split below indexes with them)
-    bool sane = offsets_sane(pp);
-    for (int p = 0; p < P && sane; ++p) sane = pp.n_ops(p) <= AGP_MAX_OPS_DEV;
-    if (sane)
-      for (int p = 0; p < P; ++p) part[toeplitz_class(pp.program(p), pp.n_ops(p)) ? 1 : 0].push_back(p);
-    // (worth it when the class's share of a dense sweep costs more than the n sequential steps of the recursion:
-    // ~50 us per particle at n = 2048 against ~0.7 us per step + ~0.4 ms of sub-batch overheads; level 3 forces it)
-    const int64_t n_cls_v = (int64_t)part[1].size();
-    // (the coalesced entry's class-aware mode: a class particle scored here stays out of the store, so the gradient call that follows
-    // must take the structured sweep too — the same test as there, or the class would be factored densely by the gradient sweep:
-    // measured with 128 threads, 106 class particles: 294 -> 262 HMC iterations/s with the value sweep's own, lower threshold)
-    const bool pays = tl_dense_via_store ? struct_grad_pays(n_cls_v, n) : struct_value_pays(n_cls_v, n);          // (agp_host.hpp: shared with agp_shard_plan)
-    if (sane && !part[1].empty() && (c->toeplitz >= 2 || pays)) {
-      // the two sub-sweeps (own slots and streams)
-      const bool via_store = tl_dense_via_store;          // (read here: the structured half may run on a helper thread)
-      SubBatch sT, sD;
-      pack_particles(part[1], pp, sT);
-      sT.outputs(false);
-      auto structured = [&] {
-        return toeplitz_sweep(c, n, value_rank0, sT.view(), sT.lp.data(), sT.info.data());
-      };
-      // (measured: 107 recursions beside the dense kernels at n = 4096: 18.1 -> 13.8 ms; 423 of them at n = 2048 fill every SIMD
-      // with their own waves and only delay the dense kernels: 8.6 -> 9.2 ms — those go first, alone)
-      // (the same in the coalesced entry's class-aware mode: value sweeps of the HMC replay 11.9 ms either way)
-      const bool side_by_side = part[1].size() <= 256;
-      std::unique_ptr<Beside> side;
-      int rcT = 0;
-      if (side_by_side) side.reset(new Beside(structured)); else rcT = structured();
-      auto dense = [&](const std::vector<int>& ix) {
-        if (ix.empty()) return 0;
-        pack_particles(ix, pp, sD);
-        sD.outputs(false);
-        TlFlag nested(tl_in_toeplitz);
-        int rc0;
-        if (via_store) {
-          TlClear plain(tl_dense_via_store);
-          rc0 = extend_impl(c, n, sD.view(), sD.lp.data(),
-                            sD.info.data());
-        } else {
-          rc0 = logpdf_batch_impl(c, n, sD.view(), sD.lp.data(), sD.info.data(), nullptr, nullptr, nullptr, false, nullptr, allow_lag);
-        }
-        if (rc0) return rc0;
-        for (size_t b2 = 0; b2 < ix.size(); ++b2) { h_out_lp[ix[b2]] = sD.lp[b2]; if (h_out_info) h_out_info[ix[b2]] = sD.info[b2]; }
-        return 0;
-      };
-      const int rcD = dense(part[0]);
-      if (side) rcT = side->join();
-      if (rcD) return rcD;
-      if (rcT) return rcT;
-      std::vector<int> refused;
-      int64_t n_done = 0;
-      for (size_t b2 = 0; b2 < part[1].size(); ++b2) {
-        if (sT.info[b2] == 0) { h_out_lp[part[1][b2]] = sT.lp[b2]; if (h_out_info) h_out_info[part[1][b2]] = 0; ++n_done; }
-        else refused.push_back(part[1][b2]);          // the dense path decides (and names LAPACK's info)
-      }
-      {
-        std::lock_guard<std::mutex> g(c->mu);
-        c->n_toeplitz_value += n_done;
-        if (via_store) {          // (the gradient call of the same leapfrog step must not re-decide: see agp_ctx::schur_keys)
-          if (c->schur_keys.size() > 32768) c->schur_keys.clear();
-          for (size_t b2 = 0; b2 < part[1].size(); ++b2)
-            if (sT.info[b2] == 0) {
-              const int p = part[1][b2];
-              c->schur_keys.insert(particle_key(pp, p));
-            }
-        }
-      }
-      const int rcR = dense(refused);
-      if (rcR) return rcR;
-      return AGP_OK;
+// The call's arguments, as the stages read them.
+struct SweepCall {
+  agp_ctx* c; int64_t n; const Particles& pp;
+  double* h_out_lp; int32_t* h_out_info; double* d_user_lp; int32_t* d_user_info;
+  hipStream_t user_stream; bool use_user_stream; GradOut* go; bool allow_lag;
+  // results to the caller's host arrays, through the slot's own stream: what a split into nested sweeps needs
+  bool host_results() const { return h_out_lp && !d_user_lp && !d_user_info && !use_user_stream; }
+};
+
+// Results of a nested sweep back into the caller's arrays: the sub-batch's particle b is the caller's ix[b].  A null lp / info / go:
+// that output is not written.  With `refused`, a particle whose info is not 0 is listed there instead and nothing of it is written.
+static void scatter_results(const std::vector<int>& ix, const SubBatch& S, const Particles& pp, double* lp, int32_t* info, GradOut* go,
+                            std::vector<int>* refused) {
+  for (size_t b = 0; b < ix.size(); ++b) {
+    const int p = ix[b];
+    if (refused && S.info[b] != 0) { refused->push_back(p); continue; }
+    if (lp) lp[p] = S.lp[b];
+    if (info) info[p] = S.info[b];
+    if (go) {
+      std::copy(S.grad.begin() + S.prm_off[b], S.grad.begin() + S.prm_off[b + 1], go->grad + pp.prm_off[p]);
+      go->gnoise[p] = S.gnoise[b];
     }
   }
+}
 
-  if (tl_dense_via_store && !go && h_out_lp && h_out_info) {
-    // (no structured split for this batch: the whole of it goes through the store, as the coalesced entry does by default)
+// The dense half of a structured split (value or gradient, by k.go), and afterwards the particles the structured sweep refused:
+// the call's particles `ix` as a nested sweep of their own — through the factor store in the coalesced entry's class-aware mode —
+// and their results back into the caller's arrays.
+static int dense_part(const SweepCall& k, const std::vector<int>& ix, bool via_store) {
+  if (ix.empty()) return 0;
+  SubBatch S;
+  pack_particles(ix, k.pp, S);
+  S.outputs(k.go != nullptr);
+  GradOut sgo{S.grad.data(), S.gnoise.data()};
+  TlFlag nested(k.go ? tl_in_tgrad : tl_in_toeplitz);
+  int rc;
+  if (via_store) {
     TlClear plain(tl_dense_via_store);
-    return extend_impl(c, n, pp, h_out_lp, h_out_info);
+    rc = extend_impl(k.c, k.n, S.view(), S.lp.data(), S.info.data());
+  } else {
+    rc = logpdf_batch_impl(k.c, k.n, S.view(), S.lp.data(), S.info.data(), nullptr, nullptr, nullptr, false, k.go ? &sgo : nullptr, k.allow_lag);
   }
-  Batch bt;
-  std::vector<std::vector<int32_t>> pls;     // per-group particle orders of the gradient contraction
-  pls.reserve(64);
-  // (the log|dt|-table kernels exist for the in-kernel-solve factorisation launches, see launch_update)
-  const bool ge_tab = c->logdt_ok;
-  // (the schedule is chosen per call from P and n; chunked / multi-stream sub-batches re-check with their own size)
-  const bool flow_hint = n > 0 && use_flow(c, P, (int)((n + NB - 1) / NB));
+  if (rc) return rc;
+  scatter_results(ix, S, k.pp, k.h_out_lp, k.h_out_info, k.go, nullptr);
+  return 0;
+}
+
+// Are the sweep's first n points n CONSECUTIVE lattice ranks (c->h_rank holds at least n >= 1 of them)?  rank0 = the lowest.
+static bool consecutive_ranks(const agp_ctx* c, int64_t n, int32_t& rank0) {
+  int32_t lo = c->h_rank[0], hi = c->h_rank[0];
+  for (int64_t i = 1; i < n; ++i) { lo = std::min(lo, c->h_rank[(size_t)i]); hi = std::max(hi, c->h_rank[(size_t)i]); }
+  rank0 = lo;
+  return (int64_t)hi - lo + 1 == n;
+}
+
+// Structured value sweep (opt-in): on a regular grid, the particles whose kernel is a sum of stationary subtrees and Linear
+// leaves need no factorisation at all — Toeplitz + rank 2: Schur algorithm, O(n^2) — the others (and every particle the
+// structured sweep refuses) take the dense path as nested sweeps.  `taken`: the call has been handled here (the code is its result).
+// The sweep's points must be n CONSECUTIVE grid points: the whole series (any order), or a prefix of a series in time order
+// (scripts/online.jl feeds the observations that way; fit_smc!(shuffle = false)) — a prefix of a shuffled grid is not.
+static int structured_value_split(const SweepCall& k, bool& taken) {
+  agp_ctx* c = k.c;
+  const int64_t n = k.n;
+  const Particles& pp = k.pp;
+  const int P = pp.P;
+  taken = false;
+  const bool eligible = !k.go && c->toeplitz && !tl_in_toeplitz && k.allow_lag && c->lag_enable && c->lag_ok && c->lag_contig && n > 0 &&
+                        c->n_max <= 4096 && k.host_results() && !c->profiling;
+  if (!eligible) return AGP_OK;
+  int32_t rank0 = 0;
+  bool consecutive = n == c->n_max;
+  if (n > 1 && n < c->n_max && (int64_t)c->h_rank.size() >= n) consecutive = consecutive_ranks(c, n, rank0);
+  if (!consecutive) return AGP_OK;
+  std::vector<int> part[2];
+  // (malformed offsets are left to compile_batch's diagnosis on the plain path: the split below indexes with them)
+  bool sane = offsets_sane(pp);
+  for (int p = 0; p < P && sane; ++p) sane = pp.n_ops(p) <= AGP_MAX_OPS_DEV;
+  if (sane)
+    for (int p = 0; p < P; ++p) part[toeplitz_class(pp.program(p), pp.n_ops(p)) ? 1 : 0].push_back(p);
+  // (worth it when the class's share of a dense sweep costs more than the n sequential steps of the recursion:
+  // ~50 us per particle at n = 2048 against ~0.7 us per step + ~0.4 ms of sub-batch overheads; level 3 forces it)
+  const int64_t n_cls_v = (int64_t)part[1].size();
+  // (the coalesced entry's class-aware mode: a class particle scored here stays out of the store, so the gradient call that follows
+  // must take the structured sweep too — the same test as there, or the class would be factored densely by the gradient sweep:
+  // measured with 128 threads, 106 class particles: 294 -> 262 HMC iterations/s with the value sweep's own, lower threshold)
+  const bool pays = tl_dense_via_store ? struct_grad_pays(n_cls_v, n) : struct_value_pays(n_cls_v, n);          // (agp_host.hpp: shared with agp_shard_plan)
+  if (!sane || part[1].empty() || !(c->toeplitz >= 2 || pays)) return AGP_OK;
+  taken = true;
+  // the two sub-sweeps (own slots and streams)
+  const bool via_store = tl_dense_via_store;          // (read here: the structured half may run on a helper thread)
+  SubBatch sT;
+  pack_particles(part[1], pp, sT);
+  sT.outputs(false);
+  auto structured = [&] {
+    return toeplitz_sweep(c, n, rank0, sT.view(), sT.lp.data(), sT.info.data());
+  };
+  // (measured: 107 recursions beside the dense kernels at n = 4096: 18.1 -> 13.8 ms; 423 of them at n = 2048 fill every SIMD
+  // with their own waves and only delay the dense kernels: 8.6 -> 9.2 ms — those go first, alone)
+  // (the same in the coalesced entry's class-aware mode: value sweeps of the HMC replay 11.9 ms either way)
+  const bool side_by_side = part[1].size() <= 256;
+  std::unique_ptr<Beside> side;
+  int rcT = 0;
+  if (side_by_side) side.reset(new Beside(structured)); else rcT = structured();
+  const int rcD = dense_part(k, part[0], via_store);
+  if (side) rcT = side->join();
+  if (rcD) return rcD;
+  if (rcT) return rcT;
+  std::vector<int> refused;          // the dense path decides about these (and names LAPACK's info)
+  scatter_results(part[1], sT, pp, k.h_out_lp, k.h_out_info, nullptr, &refused);
+  {
+    std::lock_guard<std::mutex> g(c->mu);
+    c->n_toeplitz_value += (int64_t)part[1].size() - (int64_t)refused.size();
+    if (via_store) {          // (the gradient call of the same leapfrog step must not re-decide: see agp_ctx::schur_keys)
+      if (c->schur_keys.size() > 32768) c->schur_keys.clear();
+      for (size_t b2 = 0; b2 < part[1].size(); ++b2)
+        if (sT.info[b2] == 0) c->schur_keys.insert(particle_key(pp, part[1][b2]));
+    }
+  }
+  return dense_part(k, refused, via_store);
+}
+
+// How a sweep reads its stationary leaves, and on which copy of the series it runs.
+enum class TableMode {
+  None,               // the general evaluator, caller's order
+  SortedLag,          // lag tables per block diagonal, on the sorted copy of the series (d_ts_s / d_xs_s)
+  Rank,               // rank tables, caller's order: |t_a - t_b| = |rank_a - rank_b| h
+  CompactWhole,       // compact tables (CltArgs), whole in LDS, caller's order
+  CompactSorted       // compact tables, a tile's window of them, on the sorted copy
+};
+
+// Everything a sweep decides before its first launch: plan_tables() before the batch is compiled (CompileOpts follow from the
+// table mode), plan_geometry() completes it once the slot is held; const from there on.
+struct SweepPlan {
+  TableMode mode = TableMode::None;
+  bool ge_tab = false;           // (the log|dt|-table kernels exist for the in-kernel-solve factorisation launches, see launch_update)
+  bool flow_hint = false;        // (the schedule is chosen per call from P and n; chunks re-check with their own size)
+  int tab_units = 1;             // LDS units (256 doubles) per table
+  int tab_gstride = 0;           // doubles per table in global memory
+  int clt_nB = 0, rank_extra = 0;
+  // geometry (n > 0)
+  int n_pad = 0, nt = 0, ntiles = 0;
+  long long strideA = 0;
+  int chunk = 1;                 // particles per pass through the workspace
+  int wsteps = 1, gstride = 0, gcsplit = 1;
+  bool tables() const { return mode != TableMode::None; }
+  bool compact() const { return mode == TableMode::CompactWhole || mode == TableMode::CompactSorted; }
+  bool by_rank() const { return mode == TableMode::Rank || compact(); }          // tables read through per-point ranks / keys
+  bool sorted() const { return mode == TableMode::SortedLag || mode == TableMode::CompactSorted; }
+};
+
+static SweepPlan plan_tables(const SweepCall& k) {
+  const agp_ctx* c = k.c;
+  const int64_t n = k.n;
+  SweepPlan sp;
+  sp.ge_tab = c->logdt_ok;
+  sp.flow_hint = n > 0 && use_flow(c, k.pp.P, (int)((n + NB - 1) / NB));
+  const bool tables_ok = k.allow_lag && c->lag_enable && n > 0;
   // value sweeps over the whole of a regular grid run on the sorted copy with lag tables (see agp_ctx::d_ts_s)
-  const bool lag = allow_lag && c->lag_enable && c->lag_ok && c->lag_contig && !go && n > 0 && n == c->n_max;
+  const bool lag = tables_ok && c->lag_ok && c->lag_contig && !k.go && n == c->n_max;
   // ... every other sweep over (a prefix of) a regular grid — annealing prefixes, gradient sweeps — keeps the caller's order and
   // reads the same leaves from RANK tables: |t_a - t_b| = |rank_a - rank_b| h in any order (cov_prologue)
   // (a lattice with gaps — a business-day index, a regular series with missing observations — has n_lat > n_max lags)
@@ -977,687 +1039,855 @@ int logpdf_batch_impl(agp_ctx* c, int64_t n, const Particles& pp, double* h_out_
   // the same on the sorted copy (a tile then reads a window of ~7 800 entries) 27.9 ms, general evaluator 28.1 ms: a divergent 8-byte
   // gather costs the texture path ~64 clocks per wave instruction whatever the locality (NOTES_dead_ends.md, round 5) — so such a
   // series keeps the general evaluator.
-  bool lagr = !lag && allow_lag && c->lag_rank_enable && c->lag_enable && c->lag_ok && n > 0 && rank_units <= LAG_LDS_MAX_UNITS;
+  const bool lagr = !lag && tables_ok && c->lag_rank_enable && c->lag_ok && rank_units <= LAG_LDS_MAX_UNITS;
   // COMPACT tables (CltArgs) for what that bound keeps out — month starts, quarters, years: W entries per ordinal difference instead of
   // one per lattice lag.  Whole tables in LDS while W n_max <= 4096 entries (any order of the points, any prefix: the sweeps Gen drives
   // through the store included); longer series on the batch entry's sorted sweep, where a tile needs the window of its 256 ordinal
   // differences only (W x 2 KiB per table).
-  const bool clt = !lag && !lagr && allow_lag && c->lag_rank_enable && c->lag_enable && c->clt_ok && n > 0;
+  const bool clt = !lag && !lagr && tables_ok && c->lag_rank_enable && c->clt_ok;
   const int clt_wunits = clt ? (int)(((int64_t)c->clt_W * c->n_max + 255) / 256) : 0;
   const bool cltw = clt && clt_wunits <= LAG_LDS_MAX_UNITS;
-  const bool clts = clt && !cltw && !go && n == c->n_max;
-  const bool rankm = lagr || cltw || clts;          // tables read through per-point ranks / keys
-  const int tab_units = cltw ? clt_wunits : clts ? c->clt_W : rank_units;          // LDS units (256 doubles) per table
-  const int tab_gstride = (cltw || clts) ? c->clt_gstride : rank_units * 256;      // doubles per table in global memory
-  const int clt_nB = cltw ? (int)((c->n_max + 1) & ~(int64_t)1) : clts ? 256 : 0;
-  const int rank_extra = (cltw || clts) ? (256 + clt_nB + 511) / 512 : lagr ? 1 : 0;
-  const bool sorted = lag || clts;          // the sweep runs on the sorted copy of the series (d_ts_s / d_xs_s)
-  HostProf hp_cb(2);
+  const bool clts = clt && !cltw && !k.go && n == c->n_max;
+  sp.mode = lag ? TableMode::SortedLag : lagr ? TableMode::Rank : cltw ? TableMode::CompactWhole : clts ? TableMode::CompactSorted : TableMode::None;
+  sp.tab_units = cltw ? clt_wunits : clts ? c->clt_W : rank_units;
+  sp.tab_gstride = sp.compact() ? c->clt_gstride : rank_units * 256;
+  sp.clt_nB = cltw ? (int)((c->n_max + 1) & ~(int64_t)1) : clts ? 256 : 0;
+  sp.rank_extra = sp.compact() ? (256 + sp.clt_nB + 511) / 512 : lagr ? 1 : 0;
+  return sp;
+}
+
+static CompileOpts compile_opts(const SweepCall& k, const SweepPlan& sp) {
   CompileOpts co;
-  co.want_grad = go != nullptr; co.ge_tab = ge_tab; co.fuse_hint = co.flow_limit = flow_hint;
-  co.lag = lag || rankm; co.lag_units = rankm ? tab_units : 1; co.rank_extra = rank_extra;
-  int rc = compile_batch(c, pp, bt, co);
-  hp_cb.stop();
-  if (rc) return rc;
-  HostProf hp_cls(3);
-  if (lagr) { std::lock_guard<std::mutex> g(c->mu); ++c->n_lag_rank_sweeps; }
-  if (cltw || clts) { std::lock_guard<std::mutex> g(c->mu); ++c->n_clt_sweeps; }
-  if (go && bt.g_max_nodes > 64) return fail(c, AGP_ERR_PROGRAM, "gradient supports kernel trees of up to 64 nodes");
-  if (go && n > 23040) return fail(c, AGP_ERR_ARG, "gradient sweeps address a particle's packed matrix with 32-bit byte offsets: n <= 23040");
-  if (lag) { std::lock_guard<std::mutex> g(c->mu); ++c->n_lag_sweeps; }
-  { std::lock_guard<std::mutex> g(c->mu); for (int i = 0; i < 5; ++i) c->eval_stats[i] = bt.n_eval[i]; }
-  // Gradient sweeps on a regular grid (any order of the points): particles whose kernel is a sum of stationary subtrees and
-  // Linear leaves are contracted in the lag domain (k_kinv_tiles / k_lag_grad, agp_grad_kernel.hpp)
-  int32_t toep_rank0 = 0;
-  bool any_toep_sweep = false;                 // some particle of this sweep took the Toeplitz solves
-  std::vector<int32_t> toep_retry;             // ... and (caller order) whether its downdate was rejected on the device
-  // (a lattice with gaps: the lag histograms of k_kinv_tiles over its n_lat lags; the spectral and Toeplitz sources of the lag sums
-  // need consecutive lattice points)
-  if (go && n > 0 && c->grad_lagdom && c->lag_enable && c->lag_ok && c->n_lat <= LAGDOM_MAX_BINS) {
-    int64_t n_cov = 0, n_sum = 0;          // lag-domain particles; of which sums of stationary subtrees and Linear leaves
-    // (the transform has one length, 4096: below ~1000 points the K^-1 tiles are cheaper than n/2 transforms of that length)
-    const bool use_fft = c->lag_contig && c->grad_fft && c->d_fft_tw != nullptr && 2 * c->n_max <= FFT_N && n > GRAD_FFT_MIN_N;      // (n: this sweep's prefix — the number of transforms)
-    // the sweep's points are n consecutive grid points (the whole series; a prefix of a series in time order): K is Toeplitz
-    // plus the Linear leaves' rank-2 term in sorted order — lag sums of K^-1 from four solves (k_toep_solve)
-    bool use_toep = c->lag_contig && !tl_no_toep && c->grad_fft >= 2 && c->d_fft_tw != nullptr && 2 * c->n_max <= FFT_N && n >= GRAD_TOEP_MIN_N && (int64_t)c->h_rank.size() >= n;
-    if (use_toep) {
-      int32_t lo = c->h_rank[0], hi = c->h_rank[0];
-      for (int64_t i = 1; i < n; ++i) { lo = std::min(lo, c->h_rank[(size_t)i]); hi = std::max(hi, c->h_rank[(size_t)i]); }
-      use_toep = (int64_t)hi - lo + 1 == n;
-      toep_rank0 = lo;
-    }
-    for (int q = 0; q < P; ++q) {
-      GProgHdr& g = bt.ghdr[q];
-      if (g.n_cp > 0 || g.n_ops > 64) continue;
-      uint8_t stat[64], cov[64], deg[64];          // deg: most Linear leaves along a product path below the node
-      for (int i = 0; i < g.n_ops; ++i) {
-        const int o = bt.gops[g.node_off + i], li = bt.glc[g.node_off + i], ri = bt.grc[g.node_off + i];
-        if (o == OP_PLUS || o == OP_TIMES) {
-          stat[i] = stat[li] && stat[ri];
-          cov[i] = stat[i] || (o == OP_PLUS && cov[li] && cov[ri]);
-          deg[i] = (uint8_t)std::min(100, o == OP_PLUS ? std::max<int>(deg[li], deg[ri]) : deg[li] + deg[ri]);
-        } else {
-          stat[i] = (o == OP_SE || o == OP_GE || o == OP_PER || o == OP_CONST || o == OP_WN);
-          cov[i] = stat[i] || o == OP_LIN;
-          deg[i] = o == OP_LIN ? 1 : 0;
-        }
-      }
-      if (g.n_ops > 0 && cov[g.n_ops - 1]) { g.flags |= GFLAG_LAGDOM | (use_toep ? GFLAG_LAGTOEP : use_fft ? GFLAG_LAGFFT : 0); ++n_cov; ++n_sum; }
-      else if (g.n_ops > 0 && c->grad_lagdom >= 2 && deg[g.n_ops - 1] >= 1 && deg[g.n_ops - 1] <= 3 &&
-               (2 * deg[g.n_ops - 1] + 1) * c->n_lat + 8 <= NB2) {
-        // Linear leaves inside products: moment histograms of G over the lags (k_kinv_tiles), (2d+1) n virtual elements (k_lag_grad)
-        g.flags |= GFLAG_LAGPOLY | ((int)deg[g.n_ops - 1] << GFLAG_POLY_DEG_SHIFT); ++n_cov;
-      }
-    }
-    // Structured gradient sweep: with no factor resident anywhere, the Toeplitz class needs no dense factorisation at all
-    // (toeplitz_grad_sweep: Schur recursion + backward substitution + k_lag_grad); it runs beside the dense sweep of the others.
-    // (it pays when the class's share of the dense factorisation costs more than the ~2.2 us per point of the two sequential passes)
-    // With factors resident the sweep normally starts from them (Gen.hmc's update -> choice_gradients pair).  At the opt-in level
-    // AGP_LAG >= 2 the coalesced value calls keep the Toeplitz class OUT of the store (run_coalesced: Schur recursion), so here the
-    // class particles that are not resident take the structured sweep and only the others start from their resident factors:
-    // per leapfrog no particle is factored twice, and the class is never factored densely at all.
-    const bool store_live = c->factor_cache && c->store.n_slots > 0;
-    std::vector<char> resident((size_t)P, 0);          // (sorted position) the store holds this particle's factor for exactly this prefix
-    int64_t n_struct = n_sum;
-    if (store_live && c->toeplitz && use_toep && n_sum > 0) {
-      std::lock_guard<std::mutex> g(c->store.mu);
-      agp_ctx::FactorStore& fs = c->store;
-      for (int q = 0; q < P; ++q) {
-        if (!(bt.ghdr[q].flags & GFLAG_LAGTOEP)) continue;
-        const int p = bt.order[q];
-        auto it = fs.index.find(particle_key(pp, p));
-        if (it != fs.index.end() && fs.n_cached[(size_t)it->second] == n && fs.info_h[(size_t)it->second] == 0) { resident[(size_t)q] = 1; --n_struct; }
-      }
-    }
-    // ... and a class particle the value call before this one scored by the recursion takes the structured sweep whatever this
-    // batch's size test says (the decision is sticky per particle: the two batches of a leapfrog step need not have the same size)
-    bool sticky = false;
-    if (store_live && c->toeplitz && use_toep && n_struct > 0) {
-      std::lock_guard<std::mutex> g(c->mu);
-      if (!c->schur_keys.empty())
-        for (int q = 0; q < P && !sticky; ++q) {
-          if (!(bt.ghdr[q].flags & GFLAG_LAGTOEP) || resident[(size_t)q]) continue;
-          const int p = bt.order[q];
-          sticky = c->schur_keys.erase(particle_key(pp, p)) > 0;
-        }
-    }
-    const bool struct_pays = c->grad_struct >= 2 || sticky || struct_grad_pays(n_struct, n);
-    if (use_toep && n_struct > 0 && struct_pays && n <= STRUCT_GRAD_N_MAX && !tl_in_tgrad && !tl_no_toep && !c->profiling && c->grad_struct &&
-        h_out_lp && !d_user_lp && !d_user_info && !use_user_stream && (!store_live || c->toeplitz)) {
-      std::vector<int> part[2];
-      for (int q = 0; q < P; ++q) part[((bt.ghdr[q].flags & GFLAG_LAGTOEP) && !resident[(size_t)q]) ? 1 : 0].push_back(bt.order[q]);
-      SubBatch sT, sD;
-      auto scatter = [&](const std::vector<int>& ix, const SubBatch& S, std::vector<int>* refused) {
-        for (size_t b = 0; b < ix.size(); ++b) {
-          const int p = ix[b];
-          if (refused && S.info[b] != 0) { refused->push_back(p); continue; }
-          h_out_lp[p] = S.lp[b];
-          if (h_out_info) h_out_info[p] = S.info[b];
-          std::copy(S.grad.begin() + S.prm_off[b], S.grad.begin() + S.prm_off[b + 1], go->grad + pp.prm_off[p]);
-          go->gnoise[p] = S.gnoise[b];
-        }
-      };
-      auto dense = [&](const std::vector<int>& ix) {
-        if (ix.empty()) return 0;
-        pack_particles(ix, pp, sD);
-        sD.outputs(true);
-        GradOut dgo{sD.grad.data(), sD.gnoise.data()};
-        TlFlag nested(tl_in_tgrad);
-        const int rc0 = logpdf_batch_impl(c, n, sD.view(), sD.lp.data(), sD.info.data(), nullptr, nullptr, nullptr, false, &dgo, allow_lag);
-        if (rc0) return rc0;
-        scatter(ix, sD, nullptr);
-        return 0;
-      };
-      pack_particles(part[1], pp, sT);
-      sT.outputs(true);
-      Beside side([&] {
-        return toeplitz_grad_sweep(c, n, toep_rank0, sT.view(), sT.lp.data(), sT.info.data(), sT.grad.data(), sT.gnoise.data());
-      });
-      const int rcD = dense(part[0]);
-      const int rcT = side.join();
-      if (lagr) { std::lock_guard<std::mutex> g(c->mu); if (!part[0].empty()) --c->n_lag_rank_sweeps; }          // (one sweep, as far as the counters go)
-      if (rcD) return rcD;
-      if (rcT) return rcT;
-      std::vector<int> refused;
-      scatter(part[1], sT, &refused);
-      {
-        std::lock_guard<std::mutex> g(c->mu);
-        const int64_t done = (int64_t)part[1].size() - (int64_t)refused.size();
-        c->n_lagdom_particles += done; c->n_toep_particles += done; c->n_struct_grad += done;
-      }
-      return dense(refused);
-    }
-    std::lock_guard<std::mutex> g(c->mu);
-    c->n_lagdom_particles += n_cov;
-    if (use_toep) c->n_toep_particles += n_sum;
-    any_toep_sweep = use_toep && n_sum > 0;
-  }
-  hp_cls.stop();
-  const int n_prm_total = pp.prm_off[P];
-  if (go && n == 0) {
-    for (int i = 0; i < n_prm_total; ++i) go->grad[i] = 0.0;
-    for (int p = 0; p < P; ++p) go->gnoise[p] = 0.0;
-  }
+  co.want_grad = k.go != nullptr; co.ge_tab = sp.ge_tab; co.fuse_hint = co.flow_limit = sp.flow_hint;
+  co.lag = sp.tables(); co.lag_units = sp.by_rank() ? sp.tab_units : 1; co.rank_extra = sp.rank_extra;
+  return co;
+}
 
-  // A gradient sweep right after a value call at the same parameters — every leapfrog step of Gen.hmc is `update`, then
-  // `choice_gradients` (src/inference_smc_anneal_data.jl:63-67) — finds the factor in the store (the coalesced value calls
-  // leave it there): covariance build and factorisation are skipped, the sweep starts at L^-T.
-  std::vector<int32_t> src_slot, i0v;
-  int n_hit = 0;
-  std::unique_lock<std::mutex> store_lk;       // held to the end of the sweep when anything is resident
-  HostProf hp_sl(4);
-  if (go && n > 0 && c->factor_cache && c->store.n_slots > 0) {
-    std::vector<std::string> keys((size_t)P);
-    for (int p = 0; p < P; ++p)
-      keys[p] = particle_key(pp, p);
-    n_hit = store_lookup(c, keys, bt.order, P, n, (int)((n + NB - 1) / NB), src_slot, i0v, store_lk);
-    std::lock_guard<std::mutex> g(c->mu);
-    c->grad_reused += n_hit; c->grad_factored += P - n_hit;
-  }
+// The sweep's counters and what a compiled gradient batch may still be refused for.
+static int count_sweep(const SweepCall& k, const SweepPlan& sp, const Batch& bt) {
+  agp_ctx* c = k.c;
+  if (sp.mode == TableMode::Rank) { std::lock_guard<std::mutex> g(c->mu); ++c->n_lag_rank_sweeps; }
+  if (sp.compact()) { std::lock_guard<std::mutex> g(c->mu); ++c->n_clt_sweeps; }
+  if (k.go && bt.g_max_nodes > 64) return fail(c, AGP_ERR_PROGRAM, "gradient supports kernel trees of up to 64 nodes");
+  if (k.go && k.n > 23040) return fail(c, AGP_ERR_ARG, "gradient sweeps address a particle's packed matrix with 32-bit byte offsets: n <= 23040");
+  if (sp.mode == TableMode::SortedLag) { std::lock_guard<std::mutex> g(c->mu); ++c->n_lag_sweeps; }
+  std::lock_guard<std::mutex> g(c->mu);
+  for (int i = 0; i < 5; ++i) c->eval_stats[i] = bt.n_eval[i];
+  return AGP_OK;
+}
 
-  hp_sl.stop();
-  HostProf hp_buf(5);
-  SlotGuard sg(c);
-  Slot* s = sg.s;
-  if (!s->stream) HIPCHK(c, hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
-  hipStream_t st = use_user_stream ? user_stream : s->stream;
+// The tile geometry and the split into chunks (n > 0; read once the slot is held: the workspace limit follows the factor store).
+static SweepPlan plan_geometry(const SweepCall& k, const SweepPlan& tables, const Batch& bt) {
+  agp_ctx* c = k.c;
+  SweepPlan sp = tables;
+  if (k.n == 0) return sp;
+  sp.n_pad = round_up(k.n, NB);
+  sp.nt = sp.n_pad / NB;
+  sp.ntiles = sp.nt * (sp.nt + 1) / 2;
+  sp.strideA = (long long)sp.ntiles * NB2;
+  const int64_t bytes_pp = sp.strideA * 8 * (k.go ? 2 : 1);      // + Z = L^-T for the gradient
+  sp.chunk = (int)std::max<int64_t>(1, std::min<int64_t>(k.pp.P, ws_limit_bytes(c) / bytes_pp));
+  // (the dataflow schedule has several block columns of a particle in flight: every column keeps its inverse blocks)
+  sp.wsteps = (k.go || c->flow != 0) ? sp.nt : 1;
+  sp.gstride = k.go ? bt.g_max_prm + 1 : 0;
+  // k_grad_contract: a sweep with fewer tiles than workgroup slots shares each tile among four workgroups (one rule per sweep: the
+  // partial sums' layout; reference arithmetic keeps one grouping of them whatever the batch)
+  sp.gcsplit = (!c->ref_arith && (long long)sp.ntiles * k.pp.P < 512) ? 4 : 1;      // (by the CALL's population, not the chunk: the workspace limit must not change a bit)
+  return sp;
+}
 
-  double* d_lp = d_user_lp;
-  int32_t* d_info_out = d_user_info;
-  // engine-owned results live in ONE buffer [logpdf (P doubles) | info (P ints)] so that they come back in one copy
-  const bool own_out = !d_lp && !d_info_out;
-  if (own_out) {
-    HIPCHK(c, s->out_lp.ensure(sizeof(double) * P + sizeof(int32_t) * P));
-    d_lp = s->out_lp.as<double>();
-    d_info_out = reinterpret_cast<int32_t*>(d_lp + P);
-  }
-  if (!d_lp) { HIPCHK(c, s->out_lp.ensure(sizeof(double) * P)); d_lp = s->out_lp.as<double>(); }
-  if (!d_info_out) { HIPCHK(c, s->out_info.ensure(sizeof(int32_t) * P)); d_info_out = s->out_info.as<int32_t>(); }
+// What classify_gradients found: lag-domain particles; of which sums of stationary subtrees and Linear leaves (the class of the
+// spectral / Toeplitz sources of the lag sums); whether those take the Toeplitz solves, and from which rank on.
+struct GradClasses {
+  bool lag_domain = false;       // the sweep admits lag-domain contraction at all
+  int64_t n_cov = 0, n_sum = 0;
+  bool use_toep = false;
+  int32_t rank0 = 0;
+  bool any_toep() const { return use_toep && n_sum > 0; }      // some particle of this sweep takes the Toeplitz solves
+};
 
-  if (n == 0) {
-    // 0 x 0 covariance: logpdf = 0, info = 0 (src/inference_smc_anneal_data.jl:185-187)
-    HIPCHK(c, hipMemsetAsync(d_lp, 0, sizeof(double) * P, st));
-    HIPCHK(c, hipMemsetAsync(d_info_out, 0, sizeof(int32_t) * P, st));
-  } else {
-    const int n_pad = round_up(n, NB);
-    const int nt = n_pad / NB;
-    const int ntiles = nt * (nt + 1) / 2;
-    const long long strideA = (long long)ntiles * NB2;
-    const int64_t bytes_pp = strideA * 8 * (go ? 2 : 1);      // + Z = L^-T for the gradient
-    int chunk = (int)std::max<int64_t>(1, std::min<int64_t>(P, ws_limit_bytes(c) / bytes_pp));
-    // (the dataflow schedule has several block columns of a particle in flight: every column keeps its inverse blocks)
-    const int wsteps = (go || c->flow != 0) ? nt : 1;
-    const int gstride = go ? bt.g_max_prm + 1 : 0;
-    // k_grad_contract: a sweep with fewer tiles than workgroup slots shares each tile among four workgroups (one rule per sweep: the
-    // partial sums' layout; reference arithmetic keeps one grouping of them whatever the batch)
-    const int gcsplit = (!c->ref_arith && (long long)ntiles * P < 512) ? 4 : 1;      // (by the CALL's population, not the chunk: the workspace limit must not change a bit)
-
-    HIPCHK(c, s->A.ensure((size_t)strideA * 8 * chunk));
-    HIPCHK(c, s->W.ensure(sizeof(double) * NSB * 256 * (size_t)chunk * wsteps));
-    if (go) {
-      HIPCHK(c, s->Z.ensure((size_t)strideA * 8 * chunk));
-      HIPCHK(c, s->alpha.ensure(sizeof(double) * (size_t)n_pad * chunk));
-      HIPCHK(c, s->tsol.ensure(sizeof(double) * 3 * (size_t)n_pad * chunk));
-      HIPCHK(c, s->tretry.ensure(sizeof(int32_t) * (size_t)P));
-      if (any_toep_sweep) HIPCHK(c, hipMemsetAsync(s->tretry.p, 0, sizeof(int32_t) * (size_t)P, st));      // (only the Toeplitz solves raise these flags)
-      HIPCHK(c, s->gpart.ensure(sizeof(double) * (size_t)chunk * ntiles * gstride * gcsplit));
-      HIPCHK(c, s->ghdr.ensure(sizeof(GProgHdr) * (size_t)P));
-      HIPCHK(c, s->gops.ensure(bt.gops.size() + 4)); HIPCHK(c, s->glc.ensure(bt.glc.size() + 4)); HIPCHK(c, s->grc.ensure(bt.grc.size() + 4));
-      HIPCHK(c, s->gpoff.ensure(sizeof(int32_t) * (bt.gpoff.size() + 1)));
-      HIPCHK(c, s->gprm.ensure(sizeof(double) * bt.gprm.size()));
-      HIPCHK(c, s->gmap.ensure(sizeof(int32_t) * (bt.gmap.size() + 1)));
-      HIPCHK(c, s->goff.ensure(sizeof(int32_t) * (size_t)P));
-      HIPCHK(c, s->dgrad.ensure(sizeof(double) * (size_t)std::max(1, n_prm_total)));
-      HIPCHK(c, s->dgnoise.ensure(sizeof(double) * (size_t)P));
-      HIPCHK(c, s->plist.ensure(sizeof(int32_t) * (size_t)P));
-    }
-    HIPCHK(c, s->vec.ensure(sizeof(double) * (size_t)n_pad * chunk));
-    HIPCHK(c, s->partial.ensure(sizeof(double) * 2 * (size_t)nt * chunk));
-    HIPCHK(c, s->info.ensure(sizeof(int) * (size_t)chunk));
-    HIPCHK(c, s->ready.ensure(sizeof(int) * (size_t)chunk));
-    if (c->flow != 0) {
-      HIPCHK(c, s->tflag.ensure(sizeof(int) * (size_t)chunk * ntiles));
-      HIPCHK(c, s->flowq.ensure(sizeof(int) * 8 * 8));
-    }
-    // ---- one pinned-memory upload: [hdr | prm | noise (sorted) | map | ops], 16-byte aligned sections ----
-    const size_t o_hdr = 0;
-    const size_t o_prm = align16(o_hdr + sizeof(ProgHdr) * (size_t)P);
-    const size_t o_noise = align16(o_prm + sizeof(double) * std::max<size_t>(1, bt.prm.size()));
-    const size_t o_map = align16(o_noise + sizeof(double) * (size_t)P);
-    const size_t o_ops = align16(o_map + sizeof(int32_t) * (size_t)P);
-    const size_t o_src = align16(o_ops + bt.ops.size() + 4);                    // resident-factor slots / first rows (n_hit > 0)
-    const size_t o_i0 = align16(o_src + (n_hit > 0 ? sizeof(int32_t) * (size_t)P : 0));
-    const LagProgLayout lpl(bt, o_i0 + (n_hit > 0 ? sizeof(int32_t) * (size_t)P : 0));      // lag-table programs (lag sweeps)
-    const size_t stage_bytes = lpl.end;
-    HIPCHK(c, s->stage.ensure(stage_bytes));
-    HIPCHK(c, s->h_stage.ensure(stage_bytes));
-    {
-      char* h = static_cast<char*>(s->h_stage.p);
-      std::memcpy(h + o_hdr, bt.hdr.data(), sizeof(ProgHdr) * (size_t)P);
-      if (!bt.prm.empty()) std::memcpy(h + o_prm, bt.prm.data(), sizeof(double) * bt.prm.size());
-      double* hn = reinterpret_cast<double*>(h + o_noise);
-      for (int q = 0; q < P; ++q) hn[q] = pp.noise[bt.order[q]];
-      std::memcpy(h + o_map, bt.order.data(), sizeof(int32_t) * (size_t)P);
-      std::memcpy(h + o_ops, bt.ops.data(), bt.ops.size());
-      if (n_hit > 0) {
-        std::memcpy(h + o_src, src_slot.data(), sizeof(int32_t) * (size_t)P);
-        std::memcpy(h + o_i0, i0v.data(), sizeof(int32_t) * (size_t)P);
-      }
-      lpl.pack(h);
-    }
-    char* dstage = static_cast<char*>(s->stage.p);
-    ProgHdr* d_hdr = reinterpret_cast<ProgHdr*>(dstage + o_hdr);
-    double* d_prm = reinterpret_cast<double*>(dstage + o_prm);
-    double* d_noise = reinterpret_cast<double*>(dstage + o_noise);
-    int32_t* d_map = reinterpret_cast<int32_t*>(dstage + o_map);
-    uint8_t* d_ops = reinterpret_cast<uint8_t*>(dstage + o_ops);
-    const int32_t* d_src = n_hit > 0 ? reinterpret_cast<const int32_t*>(dstage + o_src) : nullptr;
-    const int32_t* d_i0 = n_hit > 0 ? reinterpret_cast<const int32_t*>(dstage + o_i0) : nullptr;
-
-    hp_buf.stop();
-    HostProf hp_launch(go ? 7 : 6);
-    Prof pf{c, s, st, c->profiling};
-    double tacc[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    size_t ev_begin = pf.mark();
-    HIPCHK(c, hipMemcpyAsync(dstage, s->h_stage.p, stage_bytes, hipMemcpyHostToDevice, st));
-    std::vector<int32_t> goff_sorted;
-    if (go) {
-      goff_sorted.resize(P);
-      for (int q = 0; q < P; ++q) goff_sorted[q] = pp.prm_off[bt.order[q]];
-      PinnedUploads up;
-      up.add(s->ghdr.p, bt.ghdr.data(), sizeof(GProgHdr) * P);
-      up.add(s->gops.p, bt.gops.data(), bt.gops.size());
-      up.add(s->glc.p, bt.glc.data(), bt.glc.size());
-      up.add(s->grc.p, bt.grc.data(), bt.grc.size());
-      up.add(s->gpoff.p, bt.gpoff.data(), sizeof(int32_t) * bt.gpoff.size());
-      up.add(s->gprm.p, bt.gprm.data(), sizeof(double) * bt.gprm.size());
-      up.add(s->gmap.p, bt.gmap.data(), sizeof(int32_t) * bt.gmap.size());
-      up.add(s->goff.p, goff_sorted.data(), sizeof(int32_t) * P);
-      HIPCHK(c, up.flush(s->h_stage2, s->up_blob2, st));
-    }
-    if ((lag || rankm) && bt.n_lag_tables > 0) {
-      // the sweep's lag tables: every stationary leaf of every particle at the 255 lags of each of the nt block diagonals
-      // (sorted sweep) / at every lag 0 .. n_max-1 of the series (rank tables)
-      LagArgs la = {};
-      la.tt = (cltw || clts) ? c->d_clt_tt : lagr ? c->d_ts_lat : c->d_ts_s;
-      lpl.point(la, dstage);
-      if (rankm) {
-        // (compact tables: entry e at the "time" d_clt_tt[e] = its lattice lag x h, every entry of the padded table is evaluated)
-        HIPCHK(c, s->lagtab.ensure(sizeof(double) * (size_t)bt.n_lag_tables * tab_gstride));
-        la.tab = s->lagtab.as<double>(); la.nt = lagr ? (int)((c->n_lat + NB - 1) / NB) : tab_gstride / NB; la.full = 1; la.stride = tab_gstride;
-        launch_lag_tables(st, la, tab_gstride / 256, bt.n_lag_tables);
+// Gradient sweeps on a regular grid (any order of the points): particles whose kernel is a sum of stationary subtrees and
+// Linear leaves are contracted in the lag domain (k_kinv_tiles / k_lag_grad, agp_grad_kernel.hpp).  Flags bt.ghdr.
+// (a lattice with gaps: the lag histograms of k_kinv_tiles over its n_lat lags; the spectral and Toeplitz sources of the lag sums
+// need consecutive lattice points)
+static GradClasses classify_gradients(const SweepCall& k, Batch& bt) {
+  const agp_ctx* c = k.c;
+  const int64_t n = k.n;
+  GradClasses gc;
+  gc.lag_domain = k.go && n > 0 && c->grad_lagdom && c->lag_enable && c->lag_ok && c->n_lat <= LAGDOM_MAX_BINS;
+  if (!gc.lag_domain) return gc;
+  // (the transform has one length, 4096: below ~1000 points the K^-1 tiles are cheaper than n/2 transforms of that length)
+  const bool use_fft = c->lag_contig && c->grad_fft && c->d_fft_tw != nullptr && 2 * c->n_max <= FFT_N && n > GRAD_FFT_MIN_N;      // (n: this sweep's prefix — the number of transforms)
+  // the sweep's points are n consecutive grid points (the whole series; a prefix of a series in time order): K is Toeplitz
+  // plus the Linear leaves' rank-2 term in sorted order — lag sums of K^-1 from four solves (k_toep_solve)
+  gc.use_toep = c->lag_contig && !tl_no_toep && c->grad_fft >= 2 && c->d_fft_tw != nullptr && 2 * c->n_max <= FFT_N && n >= GRAD_TOEP_MIN_N &&
+                (int64_t)c->h_rank.size() >= n && consecutive_ranks(c, n, gc.rank0);
+  for (int q = 0; q < k.pp.P; ++q) {
+    GProgHdr& g = bt.ghdr[q];
+    if (g.n_cp > 0 || g.n_ops > 64) continue;
+    uint8_t stat[64], cov[64], deg[64];          // deg: most Linear leaves along a product path below the node
+    for (int i = 0; i < g.n_ops; ++i) {
+      const int o = bt.gops[g.node_off + i], li = bt.glc[g.node_off + i], ri = bt.grc[g.node_off + i];
+      if (o == OP_PLUS || o == OP_TIMES) {
+        stat[i] = stat[li] && stat[ri];
+        cov[i] = stat[i] || (o == OP_PLUS && cov[li] && cov[ri]);
+        deg[i] = (uint8_t)std::min(100, o == OP_PLUS ? std::max<int>(deg[li], deg[ri]) : deg[li] + deg[ri]);
       } else {
-        HIPCHK(c, s->lagtab.ensure(sizeof(double) * (size_t)bt.n_lag_tables * nt * 256));
-        la.tab = s->lagtab.as<double>(); la.nt = nt;
-        launch_lag_tables(st, la, nt, bt.n_lag_tables);
-      }
-      HIPCHK(c, hipGetLastError());
-    }
-    size_t ev_h2d = pf.mark();
-    HostProf hp_fac(16);
-    pf.span(7, ev_begin, ev_h2d);
-
-    for (int p0 = 0; p0 < P; p0 += chunk) {
-      const int Pc = std::min(chunk, P - p0);
-      {
-        // (one group per chunk; sub-batches on several streams were measured: no gain, removed)
-        const int g0 = 0, Pg = Pc;
-        hipStream_t q = st;
-        launch_init_vec(q, n_pad, Pg, s->vec.as<double>() + (size_t)g0 * n_pad, sorted ? c->d_xs_s : c->d_xs, (const double*)nullptr, (int)n, s->info.as<int>() + g0, s->ready.as<int>() + g0);
-        CovArgs cv = {};
-        cv.tt = sorted ? c->d_ts_s : c->d_ts; cv.n1 = (int)n; cv.n1_pad = n_pad; cv.m2 = 0; cv.nt = nt;
-        cv.hdr = d_hdr + p0 + g0; cv.ops = d_ops; cv.prm = d_prm;
-        cv.noise = d_noise + p0 + g0; cv.A = s->A.as<double>() + (size_t)g0 * strideA;
-        cv.strideA = strideA; cv.P = Pg; cv.logdt = (ge_tab && !lag && !rankm) ? c->d_logdt : nullptr;
-        cv.lagtab = (lag || rankm) ? s->lagtab.as<double>() : nullptr;
-        cv.lagr = lagr ? c->d_rank : cltw ? c->d_clt_key : clts ? c->d_clt_key_s : nullptr; cv.lag_stride = tab_units * 256;
-        if (cltw || clts) { cv.clt.B = c->d_clt_B; cv.clt.W = clts ? c->clt_W : 0; cv.clt.nB = clt_nB; cv.clt.gstride = tab_gstride; }
-        int i0min = 0;
-        if (n_hit > 0) {
-          // resident factors: forward-solve vector and partials are copied out of the store; L and the inverse blocks
-          // are read in place by the L^-T kernels (the store mutex is held to the end of the sweep)
-          launch_gather(c, q, Pg, nt, cv.A, strideA, s->W.as<double>() + (size_t)g0 * NSB * 256 * wsteps, wsteps,
-                        s->vec.as<double>() + (size_t)g0 * n_pad, n_pad, s->partial.as<double>() + (size_t)g0 * 2 * nt, nt,
-                        d_src + p0 + g0, s->ready.as<int>() + g0, /*tiles=*/false);
-          cv.i0 = d_i0 + p0 + g0;
-          i0min = nt;
-          for (int r = 0; r < Pg; ++r) i0min = std::min(i0min, (int)i0v[(size_t)p0 + g0 + r]);
-        }
-        // Hybrid build.  Sorted particles [0, n_fused) evaluate their own tiles inside k_chol_update
-        // (only the sub-diagonal tiles of block column 0, which k_chol_trsm(0) reads, are
-        // materialised); the few expensive particles behind them get every tile from k_cov_tiles,
-        // where 136 tiles per particle absorb the cost instead of one workgroup per launch.
-        const int nf = std::max(0, std::min(Pg, bt.n_fused - p0 - g0));
-        const int dcov = nf > 0 ? bt.max_depth_fused : 0;
-        size_t e0 = pf.mark(q);
-        cv.p_off = nf;
-        if (!(n_hit > 0 && i0min == nt)) HIPCHK(c, launch_cov(q, cv, ntiles, Pg - nf, bt.max_cp, bt.max_depth, bt.max_ops));      // (every particle resident: no tile to build)
-        size_t e1 = pf.mark(q);
-        pf.span(1, e0, e1);
-
-        CholArgs ca = {};
-        ca.A = cv.A; ca.strideA = strideA; ca.W = s->W.as<double>() + (size_t)g0 * NSB * 256 * wsteps;
-        ca.wsteps = wsteps;
-        ca.vec = s->vec.as<double>() + (size_t)g0 * n_pad; ca.ldv = n_pad;
-        ca.partial = s->partial.as<double>() + (size_t)g0 * 2 * nt;
-        ca.info = s->info.as<int>() + g0; ca.P = Pg; ca.nt = nt; ca.k = 0; ca.nt1 = nt;
-        set_cov(ca, cv);
-        ca.lag = (lag || rankm) ? 1 : 0;
-        ca.n_fused = nf;
-        ca.ready = s->ready.as<int>() + g0;
-        ca.i0 = cv.i0;
-        if (n_hit > 0 && i0min == nt) {
-          // every particle of this group is resident: nothing to factor
-        } else if (use_flow(c, ca.P, nt)) {      // (value and gradient sweeps alike: every block column keeps its inverse blocks)
-          // dataflow schedule: every tile of the batch in ONE launch of persistent workgroups (2 per CU)
-          const int ntri = nt * (nt + 1) / 2;
-          ca.tflag = s->tflag.as<int>() + (size_t)g0 * ntri; ca.ntri = ntri;
-          ca.qnext = s->flowq.as<int>();
-          {
-            size_t items = 0;
-            for (int x = 0; x < 8; ++x) items += (size_t)((Pg - x + 7) / 8) * ntri;
-            ca.trace = (c->d_flow_trace && items <= c->flow_trace_items && P <= chunk) ? c->d_flow_trace : nullptr;
-          }
-          if (n_hit > 0)
-            launch_init_flow_flags(q, Pg, ca.tflag, ntri, ntri, (const int*)nullptr, ca.i0);
-          else
-            HIPCHK(c, hipMemsetAsync(ca.tflag, 0, sizeof(int) * (size_t)Pg * ntri, q));
-          HIPCHK(c, hipMemsetAsync(ca.qnext, 0, sizeof(int) * 8, q));
-          size_t f0 = pf.mark(q);
-          launch_flow(dcov, 2 * c->n_cu, q, ca);
-          size_t f1 = pf.mark(q);
-          pf.span(2, f0, f1);
-          if (c->profiling) tacc[5] += 1;
-          HIPCHK(c, hipGetLastError());
-        } else if (n_hit > 0) {
-          HIPCHK(c, run_factor_extend(q, ca, dcov, use_split_diag(c, ca.P), i0min));
-        } else {
-          HIPCHK(c, run_factor(q, ca, nt, dcov, c->profiling ? &pf : nullptr, c->profiling ? &tacc[5] : nullptr, use_split_diag(c, ca.P),
-                               use_right_looking(c, ca.P), HYBRID_BLOCKS));
-        }
-
-        size_t e2 = pf.mark(q);
-        launch_finish_logpdf(q, ca.partial, ca.info, nt, Pg, (int)n, d_map + p0 + g0, d_lp, d_info_out);
-        size_t e3 = pf.mark(q);
-        pf.span(4, e2, e3);
-        HIPCHK(c, hipGetLastError());
-        if (go) {
-          hp_fac.stop();
-          HostProf hp_gl(17);
-          // ---- gradient: Z = L^-T, alpha = Z beta, per-tile contraction, fixed-order reduction ----
-          GradArgs ga = {};
-          ga.A = cv.A; ga.Z = s->Z.as<double>() + (size_t)g0 * strideA; ga.strideA = strideA; ga.W = ca.W;
-          ga.beta = ca.vec; ga.alpha = s->alpha.as<double>() + (size_t)g0 * n_pad; ga.ldv = n_pad;
-          ga.P = Pg; ga.nt = nt; ga.n = (int)n;
-          ga.ghdr = s->ghdr.as<GProgHdr>() + p0 + g0; ga.gops = s->gops.as<uint8_t>(); ga.glc = s->glc.as<uint8_t>();
-          ga.grc = s->grc.as<uint8_t>(); ga.gpoff = s->gpoff.as<int32_t>(); ga.gprm = s->gprm.as<double>();
-          ga.tt = c->d_ts; ga.logdt = c->logdt_ok ? c->d_logdt : nullptr; ga.csplit = gcsplit;
-          ga.gpart = s->gpart.as<double>() + (size_t)g0 * ntiles * gstride * ga.csplit; ga.gstride = gstride;
-          ga.gmap = s->gmap.as<int32_t>(); ga.out_off = s->goff.as<int32_t>() + p0 + g0;
-          ga.pmap = d_map + p0 + g0; ga.out_grad = s->dgrad.as<double>(); ga.out_gnoise = s->dgnoise.as<double>();
-          // (lag histograms: one bin per lattice lag, lag g at time t_lat[g] - t_lat[0]; on a regular grid d_ts_lat holds the sorted series)
-          ga.rank = c->d_rank; ga.tts = c->d_ts_lat; ga.nbins = (int)c->n_lat; ga.tref = c->t_ref; ga.tw = c->d_fft_tw; ga.grid_h = c->grid_h; ga.grid_mid = c->grid_mid;
-          if (n_hit > 0) {
-            ga.lslot = d_src + p0 + g0; ga.Lsrc = c->store.A.as<double>(); ga.Lstride = c->store.strideA;
-            ga.Wsrc = c->store.W.as<double>(); ga.Wnt = c->store.nt_cap;
-          }
-          ga.tsol = s->tsol.as<double>() + (size_t)g0 * 3 * n_pad; ga.rank0 = toep_rank0;
-          ga.noise = cv.noise; ga.retry = s->tretry.as<int32_t>(); ga.toep_max_amp = GRAD_TOEP_MAX_AMP;
-          ga.poly_mmax = c->poly_mmax;
-          // Particle list of the group, largest trees first (their workgroups run longest), lag-domain particles behind the
-          // others: the contraction launches below take the first Pn entries, k_lag_grad the rest; the 16-node (800 B private
-          // memory) variant serves groups without a larger tree.
-          pls.emplace_back(Pg);
-          std::vector<int32_t>& pl = pls.back();          // outlives the async upload (synchronised at the end of the call)
-          int max_nodes = 0;
-          for (int r = 0; r < Pg; ++r) { pl[r] = r; max_nodes = std::max(max_nodes, (int)bt.ghdr[p0 + g0 + r].n_ops); }
-          // classes: 0 element-wise contraction, 1 polynomial (K^-1 tiles' moment histograms -> k_lag_grad), 2 lag domain
-          auto lagdom = [&](int r) { return (bt.ghdr[p0 + g0 + r].flags & GFLAG_LAGDOM) != 0; };
-          auto cls = [&](int r) { const int f = bt.ghdr[p0 + g0 + r].flags; return (f & GFLAG_LAGDOM) ? 2 : (f & GFLAG_LAGPOLY) ? 1 : 0; };
-          std::stable_sort(pl.begin(), pl.end(), [&](int a_, int b_) {
-            if (cls(a_) != cls(b_)) return cls(a_) < cls(b_);
-            return bt.ghdr[p0 + g0 + a_].n_ops > bt.ghdr[p0 + g0 + b_].n_ops;
-          });
-          int Pn = 0, Pe = 0;          // Pn: particles that need L^-T and K^-1 tiles (classes 0, 1);  Pe: class 0
-          for (int r = 0; r < Pg; ++r) { Pn += !lagdom(r); Pe += cls(r) == 0; }
-          int32_t* d_pl = s->plist.as<int32_t>() + p0 + g0;
-          {
-            // (from pinned memory: a copy out of the pageable vector goes through the runtime's staging, ~7 us and a hand-over)
-            HIPCHK(c, s->h_pl.ensure(sizeof(int32_t) * (size_t)P));
-            int32_t* hpl = static_cast<int32_t*>(s->h_pl.p) + p0 + g0;
-            std::memcpy(hpl, pl.data(), sizeof(int32_t) * (size_t)Pg);
-            HIPCHK(c, hipMemcpyAsync(d_pl, hpl, sizeof(int32_t) * Pg, hipMemcpyHostToDevice, q));
-          }
-          ga.plist = d_pl;
-          // (all lag-domain particles of a sweep take the same source of their lag sums)
-          const bool any_fft = Pn < Pg && (bt.ghdr[p0 + g0 + pl[Pn]].flags & GFLAG_LAGFFT) != 0;
-          const bool any_toep = Pn < Pg && (bt.ghdr[p0 + g0 + pl[Pn]].flags & GFLAG_LAGTOEP) != 0;
-          // (a sweep with fewer tiles than workgroup slots has nothing to run side by side: its launches stay on one stream, in order —
-          // ten event / wait calls and two cross-stream hand-overs less per sweep, ~50 us of a 350 us sweep at n = 144)
-          const bool fork = (long long)ntiles * P >= 512;
-          hipStream_t qs[4] = {q, q, q, q};
-          if (fork) {
-            for (int i2 = 0; i2 < 3; ++i2) if (!s->gq[i2]) HIPCHK(c, hipStreamCreateWithFlags(&s->gq[i2], hipStreamNonBlocking));
-            for (int i2 = 0; i2 < 5; ++i2) if (!s->gq_ev[i2]) HIPCHK(c, hipEventCreateWithFlags(&s->gq_ev[i2], hipEventDisableTiming));
-            for (int i2 = 0; i2 < 3; ++i2) qs[i2 + 1] = s->gq[i2];
-          }
-          const size_t gm0 = pf.mark(q);
-          if (any_toep) {
-            // Toeplitz particles need no L^-T: their four solves with L run beside the inverse chains of the others
-            if (fork) { HIPCHK(c, hipEventRecord(s->gq_ev[4], q)); HIPCHK(c, hipStreamWaitEvent(qs[3], s->gq_ev[4], 0)); }
-            GradArgs gz = ga; gz.plist = d_pl + Pn;
-            launch_toep_solve(qs[3], Pg - Pn, sizeof(double) * 4 * (size_t)n_pad, gz);
-            HIPCHK(c, hipGetLastError());
-            if (Pn > 0) {
-              GradArgs gt = ga; gt.klist = d_pl; gt.kn = Pn;
-              launch_trtri_chain(q, 8 * ((Pn + 7) / 8) * nt, gt);
-            }
-          } else {
-            launch_trtri_chain(q, 8 * ((Pg + 7) / 8) * nt, ga);      // (forms alpha = Z beta as well)
-          }
-          const size_t gm1 = pf.mark(q);
-          pf.span(8, gm0, gm1);
-          size_t gm2 = pf.mark(q);
-          pf.span(11, gm1, gm2);
-          const size_t lds = sizeof(double) * std::max<size_t>(2 * U_SLAB, 256 + 256 * (size_t)bt.g_max_cp + bt.g_max_prm + 3 + bt.g_max_nodes);
-          const int Pall = ga.P;
-          {
-            // Two independent branches behind the inverse chain: [power spectra of Z -> lag-domain gradients] of the lag-domain
-            // particles and [K^-1 tiles -> element-wise contraction] of the others.  On separate streams a CU holds one workgroup
-            // of each (256 registers x 4 waves each): LDS / vector transforms beside MFMA tile products.
-            if (fork && !any_toep) {
-              HIPCHK(c, hipEventRecord(s->gq_ev[4], q));
-              HIPCHK(c, hipStreamWaitEvent(qs[3], s->gq_ev[4], 0));
-            }
-            if (any_fft) {
-              GradArgs gz = ga; gz.plist = d_pl + Pn;
-              launch_zspec(qs[3], nt, Pg - Pn, gz);
-            }
-            {
-              // (spectral lag-domain particles have no K^-1 tiles: the launch covers the first Pn entries of the list only)
-              GradArgs gk = ga;
-              if (any_fft || any_toep) { gk.klist = d_pl; gk.kn = Pn; }
-              const int nk = (any_fft || any_toep) ? Pn : Pg;
-              if (nk > 0) launch_kinv_tiles(q, 8 * ((nk + 7) / 8) * ntiles, gk);
-            }
-            { const size_t gk = pf.mark(q); pf.span(9, gm2, gk); gm2 = gk; }
-            const size_t lds2 = sizeof(double) * (256 + 256 * (size_t)bt.g_max_cp + bt.g_max_prm + 3 + bt.g_max_nodes + 8);
-            // three classes by tree size (the particle list is sorted by it): > 16 nodes and 9 .. 16 nodes keep their tape
-            // in private memory, trees of <= 8 nodes — the bulk of a prior-sampled population — keep it in LDS
-            int n_big = 0, n_mid = 0;
-            for (int r = 0; r < Pe; ++r) {
-              const int no = bt.ghdr[p0 + g0 + pl[r]].n_ops;
-              n_big += no > 16; n_mid += (no <= 16 && no > LDS_TAPE_NODES);
-            }
-            const int n_small = Pe - n_big - n_mid;
-            // The launch classes are independent and each ends on a few long-running workgroups (the largest trees; the
-            // 64-node class alone: ~2 000 workgroups of ~1 ms at n=2048): they run side by side on three more streams,
-            // forked behind the K^-1 tiles and joined in front of the reduction.
-            if (fork) {
-              HIPCHK(c, hipEventRecord(s->gq_ev[3], q));
-              for (int i2 = 0; i2 < 2; ++i2) HIPCHK(c, hipStreamWaitEvent(qs[i2 + 1], s->gq_ev[3], 0));
-              if (!any_fft && !any_toep) HIPCHK(c, hipStreamWaitEvent(qs[3], s->gq_ev[3], 0));      // (k_lag_grad then reads the tiles' histograms)
-            }
-            GradArgs gs = ga;
-            if (n_big > 0) HIPCHK(c, launch_grad_contract(64, qs[0], gs, ntiles, n_big, lds2));
-            gs.plist = d_pl + n_big;
-            if (n_mid > 0) HIPCHK(c, launch_grad_contract(16, qs[1], gs, ntiles, n_mid, lds2));
-            if (n_small > 0) {
-              gs.plist = d_pl + n_big + n_mid;
-              gs.tape_off = (int)((lds2 + 15) / 16 * 2);                                  // doubles, 16-byte aligned
-              const size_t lds3 = (size_t)gs.tape_off * 8 + sizeof(double) * LDS_TAPE_NODES * 4 * 256;
-              HIPCHK(c, launch_grad_contract(0, qs[2], gs, ntiles, n_small, lds3));
-            }
-            if (Pe < Pn) {
-              // polynomial particles: behind the K^-1 tiles' moment histograms
-              if (fork) HIPCHK(c, hipStreamWaitEvent(qs[3], s->gq_ev[3], 0));
-              GradArgs gp = ga; gp.plist = d_pl + Pe;
-              // (2 d + 1 moment histograms of n_max lags for the class's largest degree d: admission keeps them within one tile of LDS)
-              int dmax = 1;
-              for (int r = Pe; r < Pn; ++r) dmax = std::max(dmax, (bt.ghdr[p0 + g0 + pl[r]].flags >> GFLAG_POLY_DEG_SHIFT) & 3);
-              const size_t ldsp = sizeof(double) * ((size_t)(2 * dmax + 1) * c->n_lat + 40 + bt.g_max_prm + 3 + bt.g_max_nodes + 26 + bt.g_max_prm);
-              launch_lag_grad(qs[3], Pn - Pe, ldsp, gp);
-              HIPCHK(c, hipGetLastError());
-            }
-            if (Pn < Pg) {
-              gs.plist = d_pl + Pn;
-              const size_t lds4 = sizeof(double) * (((any_fft || any_toep) ? 2 * (size_t)FFT_BUF : 0) + (size_t)c->n_lat + 40 + bt.g_max_prm + 3 + bt.g_max_nodes + 26 + bt.g_max_prm);
-              launch_lag_grad(qs[3], Pg - Pn, lds4, gs);
-              HIPCHK(c, hipGetLastError());
-            }
-            if (fork)
-              for (int i2 = 0; i2 < 3; ++i2) { HIPCHK(c, hipEventRecord(s->gq_ev[i2], s->gq[i2])); HIPCHK(c, hipStreamWaitEvent(q, s->gq_ev[i2], 0)); }
-            (void)max_nodes; (void)lds;
-          }
-          ga.P = Pall;
-          const size_t gm3 = pf.mark(q);
-          pf.span(10, gm2, gm3);
-          launch_grad_finish(q, Pg, ga);
-          pf.span(11, gm3, pf.mark(q));
-          HIPCHK(c, hipGetLastError());
-        }
+        stat[i] = (o == OP_SE || o == OP_GE || o == OP_PER || o == OP_CONST || o == OP_WN);
+        cov[i] = stat[i] || o == OP_LIN;
+        deg[i] = o == OP_LIN ? 1 : 0;
       }
     }
-    size_t ev_end = pf.mark();
-    pf.span(0, ev_begin, ev_end);
-    if (c->profiling && !tl_no_toep) {      // (a nested repeat of refused particles keeps the sweep's own figures)
-      HIPCHK(c, hipStreamSynchronize(st));
-      pf.collect(tacc);
-      std::lock_guard<std::mutex> g(c->mu);
-      for (int i = 0; i < 16; ++i) c->timing[i] = tacc[i];
+    if (g.n_ops > 0 && cov[g.n_ops - 1]) { g.flags |= GFLAG_LAGDOM | (gc.use_toep ? GFLAG_LAGTOEP : use_fft ? GFLAG_LAGFFT : 0); ++gc.n_cov; ++gc.n_sum; }
+    else if (g.n_ops > 0 && c->grad_lagdom >= 2 && deg[g.n_ops - 1] >= 1 && deg[g.n_ops - 1] <= 3 &&
+             (2 * deg[g.n_ops - 1] + 1) * c->n_lat + 8 <= NB2) {
+      // Linear leaves inside products: moment histograms of G over the lags (k_kinv_tiles), (2d+1) n virtual elements (k_lag_grad)
+      g.flags |= GFLAG_LAGPOLY | ((int)deg[g.n_ops - 1] << GFLAG_POLY_DEG_SHIFT); ++gc.n_cov;
     }
   }
+  return gc;
+}
 
-  if (use_user_stream && !go && !c->profiling && !h_out_lp && !h_out_info) {
-    // Device-output entry on the caller's stream: everything is enqueued, nothing is waited for — the caller chains
-    // its consumer (the log-weight all-gather) on the same stream.  The slot stays reserved until the event fires.
-    // The info words also travel to pinned memory behind the work: a negative one (the bounded in-kernel wait for a
-    // diagonal factor gave up: -7) is latched when the slot is next claimed and fails the next device-output call or
-    // agp_wait with AGP_ERR_HIP — the caller never has to scan d_out_info for it.
-    if (!s->done) HIPCHK(c, hipEventCreateWithFlags(&s->done, hipEventDisableTiming));
-    HIPCHK(c, s->h_async_info.ensure(sizeof(int32_t) * (size_t)P));
-    HIPCHK(c, hipMemcpyAsync(s->h_async_info.p, d_info_out, sizeof(int32_t) * (size_t)P, hipMemcpyDeviceToHost, st));
-    s->async_P = P;
-    HIPCHK(c, hipEventRecord(s->done, st));
-    sg.async_done = true;
-    return AGP_OK;
+// Structured gradient sweep: with no factor resident anywhere, the Toeplitz class needs no dense factorisation at all
+// (toeplitz_grad_sweep: Schur recursion + backward substitution + k_lag_grad); it runs beside the dense sweep of the others.
+// (it pays when the class's share of the dense factorisation costs more than the ~2.2 us per point of the two sequential passes)
+// With factors resident the sweep normally starts from them (Gen.hmc's update -> choice_gradients pair).  At the opt-in level
+// AGP_LAG >= 2 the coalesced value calls keep the Toeplitz class OUT of the store (run_coalesced: Schur recursion), so here the
+// class particles that are not resident take the structured sweep and only the others start from their resident factors:
+// per leapfrog no particle is factored twice, and the class is never factored densely at all.
+// `taken`: the call has been handled here (the code is its result).
+static int structured_grad_split(const SweepCall& k, const SweepPlan& sp, const Batch& bt, const GradClasses& gc, bool& taken) {
+  agp_ctx* c = k.c;
+  const int64_t n = k.n;
+  const Particles& pp = k.pp;
+  const int P = pp.P;
+  taken = false;
+  if (!gc.lag_domain) return AGP_OK;
+  const bool store_live = c->factor_cache && c->store.n_slots > 0;
+  std::vector<char> resident((size_t)P, 0);          // (sorted position) the store holds this particle's factor for exactly this prefix
+  int64_t n_struct = gc.n_sum;
+  if (store_live && c->toeplitz && gc.use_toep && gc.n_sum > 0) {
+    std::lock_guard<std::mutex> g(c->store.mu);
+    agp_ctx::FactorStore& fs = c->store;
+    for (int q = 0; q < P; ++q) {
+      if (!(bt.ghdr[q].flags & GFLAG_LAGTOEP)) continue;
+      auto it = fs.index.find(particle_key(pp, bt.order[q]));
+      if (it != fs.index.end() && fs.n_cached[(size_t)it->second] == n && fs.info_h[(size_t)it->second] == 0) { resident[(size_t)q] = 1; --n_struct; }
+    }
   }
-  HostProf hp_wait(8);
+  // ... and a class particle the value call before this one scored by the recursion takes the structured sweep whatever this
+  // batch's size test says (the decision is sticky per particle: the two batches of a leapfrog step need not have the same size)
+  bool sticky = false;
+  if (store_live && c->toeplitz && gc.use_toep && n_struct > 0) {
+    std::lock_guard<std::mutex> g(c->mu);
+    if (!c->schur_keys.empty())
+      for (int q = 0; q < P && !sticky; ++q) {
+        if (!(bt.ghdr[q].flags & GFLAG_LAGTOEP) || resident[(size_t)q]) continue;
+        sticky = c->schur_keys.erase(particle_key(pp, bt.order[q])) > 0;
+      }
+  }
+  const bool struct_pays = c->grad_struct >= 2 || sticky || struct_grad_pays(n_struct, n);
+  if (!(gc.use_toep && n_struct > 0 && struct_pays && n <= STRUCT_GRAD_N_MAX && !tl_in_tgrad && !tl_no_toep && !c->profiling && c->grad_struct &&
+        k.host_results() && (!store_live || c->toeplitz))) return AGP_OK;
+  taken = true;
+  std::vector<int> part[2];
+  for (int q = 0; q < P; ++q) part[((bt.ghdr[q].flags & GFLAG_LAGTOEP) && !resident[(size_t)q]) ? 1 : 0].push_back(bt.order[q]);
+  SubBatch sT;
+  pack_particles(part[1], pp, sT);
+  sT.outputs(true);
+  Beside side([&] {
+    return toeplitz_grad_sweep(c, n, gc.rank0, sT.view(), sT.lp.data(), sT.info.data(), sT.grad.data(), sT.gnoise.data());
+  });
+  const int rcD = dense_part(k, part[0], false);
+  const int rcT = side.join();
+  if (sp.mode == TableMode::Rank) { std::lock_guard<std::mutex> g(c->mu); if (!part[0].empty()) --c->n_lag_rank_sweeps; }          // (one sweep, as far as the counters go)
+  if (rcD) return rcD;
+  if (rcT) return rcT;
+  std::vector<int> refused;
+  scatter_results(part[1], sT, pp, k.h_out_lp, k.h_out_info, k.go, &refused);
+  {
+    std::lock_guard<std::mutex> g(c->mu);
+    const int64_t done = (int64_t)part[1].size() - (int64_t)refused.size();
+    c->n_lagdom_particles += done; c->n_toep_particles += done; c->n_struct_grad += done;
+  }
+  return dense_part(k, refused, false);
+}
+
+// A gradient sweep right after a value call at the same parameters — every leapfrog step of Gen.hmc is `update`, then
+// `choice_gradients` (src/inference_smc_anneal_data.jl:63-67) — finds the factor in the store (the coalesced value calls
+// leave it there): covariance build and factorisation are skipped, the sweep starts at L^-T.
+struct StoreHits {
+  std::vector<int32_t> src_slot, i0v;         // (sorted position) the store slot of the resident factor or -1; the first tile row left to compute
+  int n_hit = 0;
+  std::unique_lock<std::mutex> lk;            // the store's mutex: held to the end of the sweep when anything is resident
+};
+static void find_store_hits(const SweepCall& k, const Batch& bt, StoreHits& h) {
+  agp_ctx* c = k.c;
+  const int P = k.pp.P;
+  if (!(k.go && k.n > 0 && c->factor_cache && c->store.n_slots > 0)) return;
+  std::vector<std::string> keys((size_t)P);
+  for (int p = 0; p < P; ++p)
+    keys[p] = particle_key(k.pp, p);
+  h.n_hit = store_lookup(c, keys, bt.order, P, k.n, (int)((k.n + NB - 1) / NB), h.src_slot, h.i0v, h.lk);
+  std::lock_guard<std::mutex> g(c->mu);
+  c->grad_reused += h.n_hit; c->grad_factored += P - h.n_hit;
+}
+
+// The slot's side of a sweep: its stream (or the caller's) and where the results land on the device.
+struct SweepSlot {
+  Slot* s = nullptr;
+  hipStream_t st = nullptr;
+  double* d_lp = nullptr;
+  int32_t* d_info = nullptr;
+  bool own_out = false;       // engine-owned results live in ONE buffer [logpdf (P doubles) | info (P ints)] so that they come back in one copy
+};
+static int claim_outputs(const SweepCall& k, Slot* s, SweepSlot& sl) {
+  agp_ctx* c = k.c;
+  const int P = k.pp.P;
+  if (!s->stream) HIPCHK(c, hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
+  sl.s = s;
+  sl.st = k.use_user_stream ? k.user_stream : s->stream;
+  sl.d_lp = k.d_user_lp;
+  sl.d_info = k.d_user_info;
+  sl.own_out = !sl.d_lp && !sl.d_info;
+  if (sl.own_out) {
+    HIPCHK(c, s->out_lp.ensure(sizeof(double) * P + sizeof(int32_t) * P));
+    sl.d_lp = s->out_lp.as<double>();
+    sl.d_info = reinterpret_cast<int32_t*>(sl.d_lp + P);
+  }
+  if (!sl.d_lp) { HIPCHK(c, s->out_lp.ensure(sizeof(double) * P)); sl.d_lp = s->out_lp.as<double>(); }
+  if (!sl.d_info) { HIPCHK(c, s->out_info.ensure(sizeof(int32_t) * P)); sl.d_info = s->out_info.as<int32_t>(); }
+  return AGP_OK;
+}
+
+// Host memory that the sweep's enqueued work reads or writes: the body owns it until its hipStreamSynchronize (and the slot its
+// pinned h_pl).
+struct SweepKeep {
+  std::vector<std::vector<int32_t>> pls;      // per-chunk particle orders of the gradient contraction
+  std::vector<int32_t> goff_sorted;           // (sorted position) offset of the particle's gradient in the caller's layout
+  std::vector<int32_t> toep_retry;            // (caller order) the particle's Toeplitz downdate was rejected on the device
+  std::vector<int32_t> info_chk;              // the info words of a caller that passes no host array for them
+};
+
+// The slot's buffers for a sweep of n > 0 points.
+static int sweep_buffers(const SweepCall& k, const SweepPlan& sp, const Batch& bt, const SweepSlot& sl, bool any_toep_sweep) {
+  agp_ctx* c = k.c;
+  Slot* s = sl.s;
+  const int P = k.pp.P, chunk = sp.chunk, n_pad = sp.n_pad, nt = sp.nt, ntiles = sp.ntiles;
+  const int n_prm_total = k.pp.prm_off[P];
+  HIPCHK(c, s->A.ensure((size_t)sp.strideA * 8 * chunk));
+  HIPCHK(c, s->W.ensure(sizeof(double) * NSB * 256 * (size_t)chunk * sp.wsteps));
+  if (k.go) {
+    HIPCHK(c, s->Z.ensure((size_t)sp.strideA * 8 * chunk));
+    HIPCHK(c, s->alpha.ensure(sizeof(double) * (size_t)n_pad * chunk));
+    HIPCHK(c, s->tsol.ensure(sizeof(double) * 3 * (size_t)n_pad * chunk));
+    HIPCHK(c, s->tretry.ensure(sizeof(int32_t) * (size_t)P));
+    if (any_toep_sweep) HIPCHK(c, hipMemsetAsync(s->tretry.p, 0, sizeof(int32_t) * (size_t)P, sl.st));      // (only the Toeplitz solves raise these flags)
+    HIPCHK(c, s->gpart.ensure(sizeof(double) * (size_t)chunk * ntiles * sp.gstride * sp.gcsplit));
+    HIPCHK(c, s->ghdr.ensure(sizeof(GProgHdr) * (size_t)P));
+    HIPCHK(c, s->gops.ensure(bt.gops.size() + 4)); HIPCHK(c, s->glc.ensure(bt.glc.size() + 4)); HIPCHK(c, s->grc.ensure(bt.grc.size() + 4));
+    HIPCHK(c, s->gpoff.ensure(sizeof(int32_t) * (bt.gpoff.size() + 1)));
+    HIPCHK(c, s->gprm.ensure(sizeof(double) * bt.gprm.size()));
+    HIPCHK(c, s->gmap.ensure(sizeof(int32_t) * (bt.gmap.size() + 1)));
+    HIPCHK(c, s->goff.ensure(sizeof(int32_t) * (size_t)P));
+    HIPCHK(c, s->dgrad.ensure(sizeof(double) * (size_t)std::max(1, n_prm_total)));
+    HIPCHK(c, s->dgnoise.ensure(sizeof(double) * (size_t)P));
+    HIPCHK(c, s->plist.ensure(sizeof(int32_t) * (size_t)P));
+  }
+  HIPCHK(c, s->vec.ensure(sizeof(double) * (size_t)n_pad * chunk));
+  HIPCHK(c, s->partial.ensure(sizeof(double) * 2 * (size_t)nt * chunk));
+  HIPCHK(c, s->info.ensure(sizeof(int) * (size_t)chunk));
+  HIPCHK(c, s->ready.ensure(sizeof(int) * (size_t)chunk));
+  if (c->flow != 0) {
+    HIPCHK(c, s->tflag.ensure(sizeof(int) * (size_t)chunk * ntiles));
+    HIPCHK(c, s->flowq.ensure(sizeof(int) * 8 * 8));
+  }
+  return AGP_OK;
+}
+
+// The sweep's programs on the device: sections of the slot's staging blob.
+struct SweepStage {
+  char* blob = nullptr;           // s->stage
+  size_t bytes = 0, o_lag = 0;    // its size; where the lag-table programs start (LagProgLayout's base)
+  ProgHdr* hdr = nullptr;
+  double* prm = nullptr;
+  double* noise = nullptr;        // sorted order
+  int32_t* map = nullptr;         // sorted position -> caller's index
+  uint8_t* ops = nullptr;
+  const int32_t* src = nullptr;   // resident-factor slots and first rows to compute: null without store hits
+  const int32_t* i0 = nullptr;
+};
+// ---- one pinned-memory image: [hdr | prm | noise (sorted) | map | ops | src | i0 | lag-table programs], 16-byte aligned sections ----
+static int pack_stage(const SweepCall& k, const Batch& bt, const StoreHits& hits, Slot* s, SweepStage& sg) {
+  agp_ctx* c = k.c;
+  const Particles& pp = k.pp;
+  const int P = pp.P;
+  const bool hit = hits.n_hit > 0;
+  const size_t o_hdr = 0;
+  const size_t o_prm = align16(o_hdr + sizeof(ProgHdr) * (size_t)P);
+  const size_t o_noise = align16(o_prm + sizeof(double) * std::max<size_t>(1, bt.prm.size()));
+  const size_t o_map = align16(o_noise + sizeof(double) * (size_t)P);
+  const size_t o_ops = align16(o_map + sizeof(int32_t) * (size_t)P);
+  const size_t o_src = align16(o_ops + bt.ops.size() + 4);                    // resident-factor slots / first rows (n_hit > 0)
+  const size_t o_i0 = align16(o_src + (hit ? sizeof(int32_t) * (size_t)P : 0));
+  sg.o_lag = o_i0 + (hit ? sizeof(int32_t) * (size_t)P : 0);
+  const LagProgLayout lpl(bt, sg.o_lag);      // lag-table programs (lag sweeps)
+  sg.bytes = lpl.end;
+  HIPCHK(c, s->stage.ensure(sg.bytes));
+  HIPCHK(c, s->h_stage.ensure(sg.bytes));
+  char* h = static_cast<char*>(s->h_stage.p);
+  std::memcpy(h + o_hdr, bt.hdr.data(), sizeof(ProgHdr) * (size_t)P);
+  if (!bt.prm.empty()) std::memcpy(h + o_prm, bt.prm.data(), sizeof(double) * bt.prm.size());
+  double* hn = reinterpret_cast<double*>(h + o_noise);
+  for (int q = 0; q < P; ++q) hn[q] = pp.noise[bt.order[q]];
+  std::memcpy(h + o_map, bt.order.data(), sizeof(int32_t) * (size_t)P);
+  std::memcpy(h + o_ops, bt.ops.data(), bt.ops.size());
+  if (hit) {
+    std::memcpy(h + o_src, hits.src_slot.data(), sizeof(int32_t) * (size_t)P);
+    std::memcpy(h + o_i0, hits.i0v.data(), sizeof(int32_t) * (size_t)P);
+  }
+  lpl.pack(h);
+  sg.blob = static_cast<char*>(s->stage.p);
+  sg.hdr = reinterpret_cast<ProgHdr*>(sg.blob + o_hdr);
+  sg.prm = reinterpret_cast<double*>(sg.blob + o_prm);
+  sg.noise = reinterpret_cast<double*>(sg.blob + o_noise);
+  sg.map = reinterpret_cast<int32_t*>(sg.blob + o_map);
+  sg.ops = reinterpret_cast<uint8_t*>(sg.blob + o_ops);
+  sg.src = hit ? reinterpret_cast<const int32_t*>(sg.blob + o_src) : nullptr;
+  sg.i0 = hit ? reinterpret_cast<const int32_t*>(sg.blob + o_i0) : nullptr;
+  return AGP_OK;
+}
+
+// The staged image to the device; behind it the gradient programs (a blob of their own: the slot's second staging buffer).
+static int upload_stage(const SweepCall& k, const Batch& bt, const SweepSlot& sl, const SweepStage& sg, std::vector<int32_t>& goff_sorted) {
+  agp_ctx* c = k.c;
+  Slot* s = sl.s;
+  const int P = k.pp.P;
+  HIPCHK(c, hipMemcpyAsync(sg.blob, s->h_stage.p, sg.bytes, hipMemcpyHostToDevice, sl.st));
+  if (!k.go) return AGP_OK;
+  goff_sorted.resize(P);
+  for (int q = 0; q < P; ++q) goff_sorted[q] = k.pp.prm_off[bt.order[q]];
+  PinnedUploads up;
+  up.add(s->ghdr.p, bt.ghdr.data(), sizeof(GProgHdr) * P);
+  up.add(s->gops.p, bt.gops.data(), bt.gops.size());
+  up.add(s->glc.p, bt.glc.data(), bt.glc.size());
+  up.add(s->grc.p, bt.grc.data(), bt.grc.size());
+  up.add(s->gpoff.p, bt.gpoff.data(), sizeof(int32_t) * bt.gpoff.size());
+  up.add(s->gprm.p, bt.gprm.data(), sizeof(double) * bt.gprm.size());
+  up.add(s->gmap.p, bt.gmap.data(), sizeof(int32_t) * bt.gmap.size());
+  up.add(s->goff.p, goff_sorted.data(), sizeof(int32_t) * P);
+  HIPCHK(c, up.flush(s->h_stage2, s->up_blob2, sl.st));
+  return AGP_OK;
+}
+
+// The sweep's lag tables: every stationary leaf of every particle at the 255 lags of each of the nt block diagonals (sorted
+// sweep) / at every lag 0 .. n_max-1 of the series (rank tables).
+static int sweep_lag_tables(const SweepCall& k, const SweepPlan& sp, const Batch& bt, const SweepSlot& sl, const SweepStage& sg) {
+  agp_ctx* c = k.c;
+  Slot* s = sl.s;
+  if (!sp.tables() || bt.n_lag_tables <= 0) return AGP_OK;
+  LagArgs la = {};
+  la.tt = sp.compact() ? c->d_clt_tt : sp.mode == TableMode::Rank ? c->d_ts_lat : c->d_ts_s;
+  LagProgLayout(bt, sg.o_lag).point(la, sg.blob);
+  if (sp.by_rank()) {
+    // (compact tables: entry e at the "time" d_clt_tt[e] = its lattice lag x h, every entry of the padded table is evaluated)
+    HIPCHK(c, s->lagtab.ensure(sizeof(double) * (size_t)bt.n_lag_tables * sp.tab_gstride));
+    la.tab = s->lagtab.as<double>(); la.nt = sp.mode == TableMode::Rank ? (int)((c->n_lat + NB - 1) / NB) : sp.tab_gstride / NB; la.full = 1; la.stride = sp.tab_gstride;
+    launch_lag_tables(sl.st, la, sp.tab_gstride / 256, bt.n_lag_tables);
+  } else {
+    HIPCHK(c, s->lagtab.ensure(sizeof(double) * (size_t)bt.n_lag_tables * sp.nt * 256));
+    la.tab = s->lagtab.as<double>(); la.nt = sp.nt;
+    launch_lag_tables(sl.st, la, sp.nt, bt.n_lag_tables);
+  }
+  HIPCHK(c, hipGetLastError());
+  return AGP_OK;
+}
+
+// One sweep's fixed parts, as the per-chunk stages read them.
+struct Sweep {
+  const SweepCall& k; const SweepPlan& sp; const Batch& bt; const GradClasses& gc; const StoreHits& hits; const SweepSlot& sl; const SweepStage& dev;
+};
+
+// Value part of the chunk of sorted particles [p0, p0 + Pc): forward-solve vector, resident factors, covariance tiles, the
+// factorisation by the schedule chosen for the chunk's size, logpdf and info.
+static int chunk_factor(const Sweep& w, Prof& pf, double* tacc, int p0, int Pc) {
+  agp_ctx* c = w.k.c;
+  Slot* s = w.sl.s;
+  hipStream_t q = w.sl.st;
+  const SweepPlan& sp = w.sp;
+  const Batch& bt = w.bt;
+  const int n = (int)w.k.n, nt = sp.nt, n_hit = w.hits.n_hit;
+  launch_init_vec(q, sp.n_pad, Pc, s->vec.as<double>(), sp.sorted() ? c->d_xs_s : c->d_xs, (const double*)nullptr, n, s->info.as<int>(), s->ready.as<int>());
+  CovArgs cv = {};
+  cv.tt = sp.sorted() ? c->d_ts_s : c->d_ts; cv.n1 = n; cv.n1_pad = sp.n_pad; cv.m2 = 0; cv.nt = nt;
+  cv.hdr = w.dev.hdr + p0; cv.ops = w.dev.ops; cv.prm = w.dev.prm;
+  cv.noise = w.dev.noise + p0; cv.A = s->A.as<double>();
+  cv.strideA = sp.strideA; cv.P = Pc; cv.logdt = (sp.ge_tab && !sp.tables()) ? c->d_logdt : nullptr;
+  cv.lagtab = sp.tables() ? s->lagtab.as<double>() : nullptr;
+  cv.lagr = sp.mode == TableMode::Rank ? c->d_rank : sp.mode == TableMode::CompactWhole ? c->d_clt_key :
+            sp.mode == TableMode::CompactSorted ? c->d_clt_key_s : nullptr;
+  cv.lag_stride = sp.tab_units * 256;
+  if (sp.compact()) { cv.clt.B = c->d_clt_B; cv.clt.W = sp.mode == TableMode::CompactSorted ? c->clt_W : 0; cv.clt.nB = sp.clt_nB; cv.clt.gstride = sp.tab_gstride; }
+  int i0min = 0;
+  if (n_hit > 0) {
+    // resident factors: forward-solve vector and partials are copied out of the store; L and the inverse blocks
+    // are read in place by the L^-T kernels (the store mutex is held to the end of the sweep)
+    launch_gather(c, q, Pc, nt, cv.A, sp.strideA, s->W.as<double>(), sp.wsteps, s->vec.as<double>(), sp.n_pad, s->partial.as<double>(), nt,
+                  w.dev.src + p0, s->ready.as<int>(), /*tiles=*/false);
+    cv.i0 = w.dev.i0 + p0;
+    i0min = nt;
+    for (int r = 0; r < Pc; ++r) i0min = std::min(i0min, (int)w.hits.i0v[(size_t)p0 + r]);
+  }
+  const bool all_resident = n_hit > 0 && i0min == nt;      // no tile to build, nothing to factor
+  // Hybrid build.  Sorted particles [0, n_fused) evaluate their own tiles inside k_chol_update
+  // (only the sub-diagonal tiles of block column 0, which k_chol_trsm(0) reads, are
+  // materialised); the few expensive particles behind them get every tile from k_cov_tiles,
+  // where 136 tiles per particle absorb the cost instead of one workgroup per launch.
+  const int nf = std::max(0, std::min(Pc, bt.n_fused - p0));
+  const int dcov = nf > 0 ? bt.max_depth_fused : 0;
+  size_t e0 = pf.mark(q);
+  cv.p_off = nf;
+  if (!all_resident) HIPCHK(c, launch_cov(q, cv, sp.ntiles, Pc - nf, bt.max_cp, bt.max_depth, bt.max_ops));
+  size_t e1 = pf.mark(q);
+  pf.span(1, e0, e1);
+
+  CholArgs ca = {};
+  ca.A = cv.A; ca.strideA = sp.strideA; ca.W = s->W.as<double>();
+  ca.wsteps = sp.wsteps;
+  ca.vec = s->vec.as<double>(); ca.ldv = sp.n_pad;
+  ca.partial = s->partial.as<double>();
+  ca.info = s->info.as<int>(); ca.P = Pc; ca.nt = nt; ca.k = 0; ca.nt1 = nt;
+  set_cov(ca, cv);
+  ca.lag = sp.tables() ? 1 : 0;
+  ca.n_fused = nf;
+  ca.ready = s->ready.as<int>();
+  ca.i0 = cv.i0;
+  if (all_resident) {
+    // every particle of this chunk is resident: nothing to factor
+  } else if (use_flow(c, ca.P, nt)) {      // (value and gradient sweeps alike: every block column keeps its inverse blocks)
+    // dataflow schedule: every tile of the batch in ONE launch of persistent workgroups (2 per CU)
+    const int ntri = nt * (nt + 1) / 2;
+    ca.tflag = s->tflag.as<int>(); ca.ntri = ntri;
+    ca.qnext = s->flowq.as<int>();
+    size_t items = 0;
+    for (int x = 0; x < 8; ++x) items += (size_t)((Pc - x + 7) / 8) * ntri;
+    ca.trace = (c->d_flow_trace && items <= c->flow_trace_items && w.k.pp.P <= sp.chunk) ? c->d_flow_trace : nullptr;
+    if (n_hit > 0)
+      launch_init_flow_flags(q, Pc, ca.tflag, ntri, ntri, (const int*)nullptr, ca.i0);
+    else
+      HIPCHK(c, hipMemsetAsync(ca.tflag, 0, sizeof(int) * (size_t)Pc * ntri, q));
+    HIPCHK(c, hipMemsetAsync(ca.qnext, 0, sizeof(int) * 8, q));
+    size_t f0 = pf.mark(q);
+    launch_flow(dcov, 2 * c->n_cu, q, ca);
+    size_t f1 = pf.mark(q);
+    pf.span(2, f0, f1);
+    if (c->profiling) tacc[5] += 1;
+    HIPCHK(c, hipGetLastError());
+  } else if (n_hit > 0) {
+    HIPCHK(c, run_factor_extend(q, ca, dcov, use_split_diag(c, ca.P), i0min));
+  } else {
+    HIPCHK(c, run_factor(q, ca, nt, dcov, c->profiling ? &pf : nullptr, c->profiling ? &tacc[5] : nullptr, use_split_diag(c, ca.P),
+                         use_right_looking(c, ca.P), HYBRID_BLOCKS));
+  }
+
+  size_t e2 = pf.mark(q);
+  launch_finish_logpdf(q, ca.partial, ca.info, nt, Pc, n, w.dev.map + p0, w.sl.d_lp, w.sl.d_info);
+  size_t e3 = pf.mark(q);
+  pf.span(4, e2, e3);
+  HIPCHK(c, hipGetLastError());
+  return AGP_OK;
+}
+
+// The chunk's particle list for the gradient launches: classes 0 element-wise contraction, 1 polynomial (K^-1 tiles' moment
+// histograms -> k_lag_grad), 2 lag domain, in that order; within a class the largest trees first (their workgroups run longest).
+struct GradOrder {
+  int Pn = 0, Pe = 0;                      // Pn: particles that need L^-T and K^-1 tiles (classes 0, 1);  Pe: class 0
+  // class 0 by tree size: > 16 nodes and 9 .. 16 nodes keep their tape in private memory, trees of <= 8 nodes — the bulk of a
+  // prior-sampled population — keep it in LDS
+  int n_big = 0, n_mid = 0, n_small = 0;
+  int poly_dmax = 1;                       // the polynomial class's largest degree
+  bool any_fft = false, any_toep = false;  // (all lag-domain particles of a sweep take the same source of their lag sums)
+};
+static GradOrder order_gradients(const Batch& bt, int p0, int Pc, std::vector<int32_t>& pl) {
+  const GProgHdr* gh = bt.ghdr.data() + p0;
+  auto cls = [&](int r) { const int f = gh[r].flags; return (f & GFLAG_LAGDOM) ? 2 : (f & GFLAG_LAGPOLY) ? 1 : 0; };
+  pl.resize((size_t)Pc);
+  for (int r = 0; r < Pc; ++r) pl[r] = r;
+  std::stable_sort(pl.begin(), pl.end(), [&](int a_, int b_) {
+    if (cls(a_) != cls(b_)) return cls(a_) < cls(b_);
+    return gh[a_].n_ops > gh[b_].n_ops;
+  });
+  GradOrder o;
+  for (int r = 0; r < Pc; ++r) { o.Pn += cls(r) != 2; o.Pe += cls(r) == 0; }
+  for (int r = 0; r < o.Pe; ++r) {
+    const int no = gh[pl[r]].n_ops;
+    o.n_big += no > 16; o.n_mid += (no <= 16 && no > LDS_TAPE_NODES);
+  }
+  o.n_small = o.Pe - o.n_big - o.n_mid;
+  // (2 d + 1 moment histograms of n_max lags for the class's largest degree d: admission keeps them within one tile of LDS)
+  for (int r = o.Pe; r < o.Pn; ++r) o.poly_dmax = std::max(o.poly_dmax, (gh[pl[r]].flags >> GFLAG_POLY_DEG_SHIFT) & 3);
+  o.any_fft = o.Pn < Pc && (gh[pl[o.Pn]].flags & GFLAG_LAGFFT) != 0;
+  o.any_toep = o.Pn < Pc && (gh[pl[o.Pn]].flags & GFLAG_LAGTOEP) != 0;
+  return o;
+}
+
+// Gradient part of the chunk: Z = L^-T, alpha = Z beta, per-tile contraction, fixed-order reduction.
+static int chunk_gradient(const Sweep& w, Prof& pf, SweepKeep& keep, int p0, int Pc) {
+  HostProf hp_gl(17);
+  agp_ctx* c = w.k.c;
+  Slot* s = w.sl.s;
+  hipStream_t q = w.sl.st;
+  const SweepPlan& sp = w.sp;
+  const Batch& bt = w.bt;
+  const int P = w.k.pp.P, nt = sp.nt, ntiles = sp.ntiles, n_pad = sp.n_pad;
+  GradArgs ga = {};
+  ga.A = s->A.as<double>(); ga.Z = s->Z.as<double>(); ga.strideA = sp.strideA; ga.W = s->W.as<double>();
+  ga.beta = s->vec.as<double>(); ga.alpha = s->alpha.as<double>(); ga.ldv = n_pad;
+  ga.P = Pc; ga.nt = nt; ga.n = (int)w.k.n;
+  ga.ghdr = s->ghdr.as<GProgHdr>() + p0; ga.gops = s->gops.as<uint8_t>(); ga.glc = s->glc.as<uint8_t>();
+  ga.grc = s->grc.as<uint8_t>(); ga.gpoff = s->gpoff.as<int32_t>(); ga.gprm = s->gprm.as<double>();
+  ga.tt = c->d_ts; ga.logdt = c->logdt_ok ? c->d_logdt : nullptr; ga.csplit = sp.gcsplit;
+  ga.gpart = s->gpart.as<double>(); ga.gstride = sp.gstride;
+  ga.gmap = s->gmap.as<int32_t>(); ga.out_off = s->goff.as<int32_t>() + p0;
+  ga.pmap = w.dev.map + p0; ga.out_grad = s->dgrad.as<double>(); ga.out_gnoise = s->dgnoise.as<double>();
+  // (lag histograms: one bin per lattice lag, lag g at time t_lat[g] - t_lat[0]; on a regular grid d_ts_lat holds the sorted series)
+  ga.rank = c->d_rank; ga.tts = c->d_ts_lat; ga.nbins = (int)c->n_lat; ga.tref = c->t_ref; ga.tw = c->d_fft_tw; ga.grid_h = c->grid_h; ga.grid_mid = c->grid_mid;
+  if (w.hits.n_hit > 0) {
+    ga.lslot = w.dev.src + p0; ga.Lsrc = c->store.A.as<double>(); ga.Lstride = c->store.strideA;
+    ga.Wsrc = c->store.W.as<double>(); ga.Wnt = c->store.nt_cap;
+  }
+  ga.tsol = s->tsol.as<double>(); ga.rank0 = w.gc.rank0;
+  ga.noise = w.dev.noise + p0; ga.retry = s->tretry.as<int32_t>(); ga.toep_max_amp = GRAD_TOEP_MAX_AMP;
+  ga.poly_mmax = c->poly_mmax;
+  // the contraction launches below take the first Pn entries of the list, k_lag_grad the rest
+  keep.pls.emplace_back();
+  const std::vector<int32_t>& pl = keep.pls.back();
+  const GradOrder o = order_gradients(bt, p0, Pc, keep.pls.back());
+  const int Pn = o.Pn, Pe = o.Pe;
+  const bool lag_sums = o.any_fft || o.any_toep;      // spectral / Toeplitz lag-domain particles: no K^-1 tiles of their own
+  int32_t* d_pl = s->plist.as<int32_t>() + p0;
+  {
+    // (from pinned memory: a copy out of the pageable vector goes through the runtime's staging, ~7 us and a hand-over)
+    HIPCHK(c, s->h_pl.ensure(sizeof(int32_t) * (size_t)P));
+    int32_t* hpl = static_cast<int32_t*>(s->h_pl.p) + p0;
+    std::memcpy(hpl, pl.data(), sizeof(int32_t) * (size_t)Pc);
+    HIPCHK(c, hipMemcpyAsync(d_pl, hpl, sizeof(int32_t) * Pc, hipMemcpyHostToDevice, q));
+  }
+  ga.plist = d_pl;
+  // (a sweep with fewer tiles than workgroup slots has nothing to run side by side: its launches stay on one stream, in order —
+  // ten event / wait calls and two cross-stream hand-overs less per sweep, ~50 us of a 350 us sweep at n = 144)
+  const bool fork = (long long)ntiles * P >= 512;
+  hipStream_t qs[4] = {q, q, q, q};
+  if (fork) {
+    for (int i2 = 0; i2 < 3; ++i2) if (!s->gq[i2]) HIPCHK(c, hipStreamCreateWithFlags(&s->gq[i2], hipStreamNonBlocking));
+    for (int i2 = 0; i2 < 5; ++i2) if (!s->gq_ev[i2]) HIPCHK(c, hipEventCreateWithFlags(&s->gq_ev[i2], hipEventDisableTiming));
+    for (int i2 = 0; i2 < 3; ++i2) qs[i2 + 1] = s->gq[i2];
+  }
+  const size_t gm0 = pf.mark(q);
+  if (o.any_toep) {
+    // Toeplitz particles need no L^-T: their four solves with L run beside the inverse chains of the others
+    if (fork) { HIPCHK(c, hipEventRecord(s->gq_ev[4], q)); HIPCHK(c, hipStreamWaitEvent(qs[3], s->gq_ev[4], 0)); }
+    GradArgs gz = ga; gz.plist = d_pl + Pn;
+    launch_toep_solve(qs[3], Pc - Pn, sizeof(double) * 4 * (size_t)n_pad, gz);
+    HIPCHK(c, hipGetLastError());
+    if (Pn > 0) {
+      GradArgs gt = ga; gt.klist = d_pl; gt.kn = Pn;
+      launch_trtri_chain(q, 8 * ((Pn + 7) / 8) * nt, gt);
+    }
+  } else {
+    launch_trtri_chain(q, 8 * ((Pc + 7) / 8) * nt, ga);      // (forms alpha = Z beta as well)
+  }
+  const size_t gm1 = pf.mark(q);
+  pf.span(8, gm0, gm1);
+  size_t gm2 = pf.mark(q);
+  pf.span(11, gm1, gm2);          // (an empty span: agp_get_timing's slots are an output)
+  // Two independent branches behind the inverse chain: [power spectra of Z -> lag-domain gradients] of the lag-domain
+  // particles and [K^-1 tiles -> element-wise contraction] of the others.  On separate streams a CU holds one workgroup
+  // of each (256 registers x 4 waves each): LDS / vector transforms beside MFMA tile products.
+  if (fork && !o.any_toep) {
+    HIPCHK(c, hipEventRecord(s->gq_ev[4], q));
+    HIPCHK(c, hipStreamWaitEvent(qs[3], s->gq_ev[4], 0));
+  }
+  if (o.any_fft) {
+    GradArgs gz = ga; gz.plist = d_pl + Pn;
+    launch_zspec(qs[3], nt, Pc - Pn, gz);
+  }
+  {
+    // (spectral lag-domain particles have no K^-1 tiles: the launch covers the first Pn entries of the list only)
+    GradArgs gk = ga;
+    if (lag_sums) { gk.klist = d_pl; gk.kn = Pn; }
+    const int nk = lag_sums ? Pn : Pc;
+    if (nk > 0) launch_kinv_tiles(q, 8 * ((nk + 7) / 8) * ntiles, gk);
+  }
+  { const size_t gk = pf.mark(q); pf.span(9, gm2, gk); gm2 = gk; }
+  const size_t lds2 = sizeof(double) * (256 + 256 * (size_t)bt.g_max_cp + bt.g_max_prm + 3 + bt.g_max_nodes + 8);
+  // The launch classes are independent and each ends on a few long-running workgroups (the largest trees; the
+  // 64-node class alone: ~2 000 workgroups of ~1 ms at n=2048): they run side by side on three more streams,
+  // forked behind the K^-1 tiles and joined in front of the reduction.
+  if (fork) {
+    HIPCHK(c, hipEventRecord(s->gq_ev[3], q));
+    for (int i2 = 0; i2 < 2; ++i2) HIPCHK(c, hipStreamWaitEvent(qs[i2 + 1], s->gq_ev[3], 0));
+    if (!lag_sums) HIPCHK(c, hipStreamWaitEvent(qs[3], s->gq_ev[3], 0));      // (k_lag_grad then reads the tiles' histograms)
+  }
+  GradArgs gs = ga;
+  if (o.n_big > 0) HIPCHK(c, launch_grad_contract(64, qs[0], gs, ntiles, o.n_big, lds2));
+  gs.plist = d_pl + o.n_big;
+  if (o.n_mid > 0) HIPCHK(c, launch_grad_contract(16, qs[1], gs, ntiles, o.n_mid, lds2));
+  if (o.n_small > 0) {
+    gs.plist = d_pl + o.n_big + o.n_mid;
+    gs.tape_off = (int)((lds2 + 15) / 16 * 2);                                  // doubles, 16-byte aligned
+    const size_t lds3 = (size_t)gs.tape_off * 8 + sizeof(double) * LDS_TAPE_NODES * 4 * 256;
+    HIPCHK(c, launch_grad_contract(0, qs[2], gs, ntiles, o.n_small, lds3));
+  }
+  if (Pe < Pn) {
+    // polynomial particles: behind the K^-1 tiles' moment histograms
+    if (fork) HIPCHK(c, hipStreamWaitEvent(qs[3], s->gq_ev[3], 0));
+    GradArgs gp = ga; gp.plist = d_pl + Pe;
+    const size_t ldsp = sizeof(double) * ((size_t)(2 * o.poly_dmax + 1) * c->n_lat + 40 + bt.g_max_prm + 3 + bt.g_max_nodes + 26 + bt.g_max_prm);
+    launch_lag_grad(qs[3], Pn - Pe, ldsp, gp);
+    HIPCHK(c, hipGetLastError());
+  }
+  if (Pn < Pc) {
+    gs.plist = d_pl + Pn;
+    const size_t lds4 = sizeof(double) * ((lag_sums ? 2 * (size_t)FFT_BUF : 0) + (size_t)c->n_lat + 40 + bt.g_max_prm + 3 + bt.g_max_nodes + 26 + bt.g_max_prm);
+    launch_lag_grad(qs[3], Pc - Pn, lds4, gs);
+    HIPCHK(c, hipGetLastError());
+  }
+  if (fork)
+    for (int i2 = 0; i2 < 3; ++i2) { HIPCHK(c, hipEventRecord(s->gq_ev[i2], s->gq[i2])); HIPCHK(c, hipStreamWaitEvent(q, s->gq_ev[i2], 0)); }
+  const size_t gm3 = pf.mark(q);
+  pf.span(10, gm2, gm3);
+  launch_grad_finish(q, Pc, ga);
+  pf.span(11, gm3, pf.mark(q));
+  HIPCHK(c, hipGetLastError());
+  return AGP_OK;
+}
+
+// A profiled sweep's figures (agp_get_timing).
+static int collect_timing(agp_ctx* c, hipStream_t st, Prof& pf, double* tacc) {
+  HIPCHK(c, hipStreamSynchronize(st));
+  pf.collect(tacc);
+  std::lock_guard<std::mutex> g(c->mu);
+  for (int i = 0; i < 16; ++i) c->timing[i] = tacc[i];
+  return AGP_OK;
+}
+
+// Device-output entry on the caller's stream: everything is enqueued, nothing is waited for — the caller chains
+// its consumer (the log-weight all-gather) on the same stream.  The slot stays reserved until the event fires.
+// The info words also travel to pinned memory behind the work: a negative one (the bounded in-kernel wait for a
+// diagonal factor gave up: -7) is latched when the slot is next claimed and fails the next device-output call or
+// agp_wait with AGP_ERR_HIP — the caller never has to scan d_out_info for it.
+static int finish_on_stream(const SweepCall& k, const SweepSlot& sl) {
+  agp_ctx* c = k.c;
+  Slot* s = sl.s;
+  const int P = k.pp.P;
+  if (!s->done) HIPCHK(c, hipEventCreateWithFlags(&s->done, hipEventDisableTiming));
+  HIPCHK(c, s->h_async_info.ensure(sizeof(int32_t) * (size_t)P));
+  HIPCHK(c, hipMemcpyAsync(s->h_async_info.p, sl.d_info, sizeof(int32_t) * (size_t)P, hipMemcpyDeviceToHost, sl.st));
+  s->async_P = P;
+  HIPCHK(c, hipEventRecord(s->done, sl.st));
+  return AGP_OK;
+}
+
+// Results to the host: the copies, the one wait of the sweep, the hand-over to the caller's arrays.  h_info: the info words on
+// the host afterwards (the caller's array, or keep.info_chk).
+static int copy_out(const SweepCall& k, const SweepSlot& sl, bool any_toep_sweep, SweepKeep& keep, int32_t*& h_info) {
+  agp_ctx* c = k.c;
+  Slot* s = sl.s;
+  hipStream_t st = sl.st;
+  const int P = k.pp.P;
+  const int n_prm_total = k.pp.prm_off[P];
+  const bool grad = k.go && k.n > 0;
   const size_t out_bytes = sizeof(double) * P + sizeof(int32_t) * P;
   // (gradients land in the slot's pinned buffer too and are handed to the caller after the synchronisation: a copy straight into the
   // caller's pageable arrays goes through the runtime's own staging, ~20 us of a 230-us sweep at n = 144)
-  size_t h_need = own_out ? out_bytes : 0, o_gn = 0, o_gr = 0;
-  if (go && n > 0) { o_gn = (h_need + 15) & ~(size_t)15; o_gr = o_gn + sizeof(double) * (size_t)P; h_need = o_gr + sizeof(double) * (size_t)n_prm_total; }
+  size_t h_need = sl.own_out ? out_bytes : 0, o_gn = 0, o_gr = 0;
+  if (grad) { o_gn = (h_need + 15) & ~(size_t)15; o_gr = o_gn + sizeof(double) * (size_t)P; h_need = o_gr + sizeof(double) * (size_t)n_prm_total; }
   if (h_need > 0) HIPCHK(c, s->h_out.ensure(h_need));
-  if (own_out) {
-    HIPCHK(c, hipMemcpyAsync(s->h_out.p, d_lp, out_bytes, hipMemcpyDeviceToHost, st));
-  } else if (h_out_lp) {
-    HIPCHK(c, hipMemcpyAsync(h_out_lp, d_lp, sizeof(double) * P, hipMemcpyDeviceToHost, st));
+  if (sl.own_out) {
+    HIPCHK(c, hipMemcpyAsync(s->h_out.p, sl.d_lp, out_bytes, hipMemcpyDeviceToHost, st));
+  } else if (k.h_out_lp) {
+    HIPCHK(c, hipMemcpyAsync(k.h_out_lp, sl.d_lp, sizeof(double) * P, hipMemcpyDeviceToHost, st));
   }
-  if (go && n > 0) {
+  if (grad) {
     char* ho = static_cast<char*>(s->h_out.p);
     if (n_prm_total > 0)
       HIPCHK(c, hipMemcpyAsync(ho + o_gr, s->dgrad.p, sizeof(double) * n_prm_total, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipMemcpyAsync(ho + o_gn, s->dgnoise.p, sizeof(double) * P, hipMemcpyDeviceToHost, st));
     if (any_toep_sweep) {
-      toep_retry.resize((size_t)P);
-      HIPCHK(c, hipMemcpyAsync(toep_retry.data(), s->tretry.p, sizeof(int32_t) * (size_t)P, hipMemcpyDeviceToHost, st));
+      keep.toep_retry.resize((size_t)P);
+      HIPCHK(c, hipMemcpyAsync(keep.toep_retry.data(), s->tretry.p, sizeof(int32_t) * (size_t)P, hipMemcpyDeviceToHost, st));
     }
   }
-  std::vector<int32_t> info_chk;
-  int32_t* h_info = h_out_info;
-  if (!h_info) { info_chk.resize(P); h_info = info_chk.data(); }
-  if (!own_out) HIPCHK(c, hipMemcpyAsync(h_info, d_info_out, sizeof(int32_t) * P, hipMemcpyDeviceToHost, st));
+  h_info = k.h_out_info;
+  if (!h_info) { keep.info_chk.resize(P); h_info = keep.info_chk.data(); }
+  if (!sl.own_out) HIPCHK(c, hipMemcpyAsync(h_info, sl.d_info, sizeof(int32_t) * P, hipMemcpyDeviceToHost, st));
   // The slot's buffers are reused by the next caller, so the work must be complete before the
   // slot is released even on the user-stream path.
   HIPCHK(c, hipStreamSynchronize(st));
-  if (own_out) {
+  if (sl.own_out) {
     const double* hl = static_cast<const double*>(s->h_out.p);
-    if (h_out_lp) std::memcpy(h_out_lp, hl, sizeof(double) * P);
+    if (k.h_out_lp) std::memcpy(k.h_out_lp, hl, sizeof(double) * P);
     std::memcpy(h_info, hl + P, sizeof(int32_t) * P);
   }
-  if (go && n > 0) {
+  if (grad) {
     const char* ho = static_cast<const char*>(s->h_out.p);
-    if (n_prm_total > 0) std::memcpy(go->grad, ho + o_gr, sizeof(double) * (size_t)n_prm_total);
-    std::memcpy(go->gnoise, ho + o_gn, sizeof(double) * (size_t)P);
+    if (n_prm_total > 0) std::memcpy(k.go->grad, ho + o_gr, sizeof(double) * (size_t)n_prm_total);
+    std::memcpy(k.go->gnoise, ho + o_gn, sizeof(double) * (size_t)P);
   }
   for (int p = 0; p < P; ++p)
     if (h_info[p] < 0) return fail(c, AGP_ERR_HIP, "in-kernel panel solve timed out waiting for its diagonal factor");
-  if (go && !toep_retry.empty()) {
-    // Particles whose Linear leaves dominate T so much that T^-1 = K^-1 + V Q V' is not accurate (k_lag_grad measured it): their
-    // gradient is taken once more, from L^-T.  (Rare: a Linear leaf beside a stationary subtree of far smaller amplitude.)
-    std::vector<int> rp;
-    for (int p = 0; p < P; ++p) if (toep_retry[(size_t)p] != 0) rp.push_back(p);
-    if (!rp.empty()) {
-      const int B = (int)rp.size();
-      SubBatch S;
-      pack_particles(rp, pp, S);
-      S.outputs(true);
-      GradOut bgo{S.grad.data(), S.gnoise.data()};
-      if (store_lk.owns_lock()) store_lk.unlock();
-      sg.release();
-      int rc2;
-      {
-        TlFlag nested(tl_no_toep);
-        rc2 = logpdf_batch_impl(c, n, S.view(), S.lp.data(),
-                                S.info.data(), nullptr, nullptr, nullptr, false, &bgo, allow_lag);
-      }
-      if (rc2) return rc2;
-      for (int b = 0; b < B; ++b) {
-        const int p = rp[b];
-        std::copy(S.grad.begin() + S.prm_off[b], S.grad.begin() + S.prm_off[b + 1], go->grad + pp.prm_off[p]);
-        go->gnoise[p] = S.gnoise[b];
-      }
-      std::lock_guard<std::mutex> g(c->mu);
-      c->n_toep_particles -= B;
-      c->n_lagdom_particles -= B;          // (the nested sweep counted them again)
-    }
-  }
-  if (sorted && h_out_info) {
-    // LAPACK's info names the first non-positive leading minor IN THE CALLER'S ORDER of the observations
-    // (LinearAlgebra.PosDefException(info) in the reference); the sorted sweep found the matrix not positive definite
-    // at some minor of the sorted order.  The (rare) rejected particles are factored once more in the caller's order.
-    std::vector<int> bad;
-    for (int p = 0; p < P; ++p) if (h_info[p] > 0) bad.push_back(p);
-    if (!bad.empty()) {
-      const int B = (int)bad.size();
-      SubBatch S;
-      pack_particles(bad, pp, S);
-      S.outputs(false);
-      // (the results are on the host: hand the slot back first — sixteen concurrent callers that each kept theirs while waiting
-      // for a second one would wait for ever)
-      sg.release();
-      const int rc2 = logpdf_batch_impl(c, n, S.view(), S.lp.data(),
-                                        S.info.data(), nullptr, nullptr, nullptr, false, nullptr, /*allow_lag=*/false);
-      if (rc2) return rc2;
-      for (int b = 0; b < B; ++b) {
-        // (a matrix that is indefinite to rounding may factor in one order and not in the other: the caller's order decides)
-        h_out_info[bad[b]] = S.info[b];
-        if (h_out_lp) h_out_lp[bad[b]] = S.lp[b];
-      }
-    }
-  }
   return AGP_OK;
+}
+
+// Particles whose Linear leaves dominate T so much that T^-1 = K^-1 + V Q V' is not accurate (k_lag_grad measured it): their
+// gradient is taken once more, from L^-T.  (Rare: a Linear leaf beside a stationary subtree of far smaller amplitude.)
+// The store's mutex and the slot are handed back in front of the nested sweep.
+static int repeat_rejected_toeplitz(const SweepCall& k, const SweepKeep& keep, StoreHits& hits, SlotGuard& sg) {
+  agp_ctx* c = k.c;
+  if (!k.go || keep.toep_retry.empty()) return AGP_OK;
+  std::vector<int> rp;
+  for (int p = 0; p < k.pp.P; ++p) if (keep.toep_retry[(size_t)p] != 0) rp.push_back(p);
+  if (rp.empty()) return AGP_OK;
+  const int B = (int)rp.size();
+  SubBatch S;
+  pack_particles(rp, k.pp, S);
+  S.outputs(true);
+  GradOut bgo{S.grad.data(), S.gnoise.data()};
+  if (hits.lk.owns_lock()) hits.lk.unlock();
+  sg.release();
+  int rc2;
+  {
+    TlFlag nested(tl_no_toep);
+    rc2 = logpdf_batch_impl(c, k.n, S.view(), S.lp.data(), S.info.data(), nullptr, nullptr, nullptr, false, &bgo, k.allow_lag);
+  }
+  if (rc2) return rc2;
+  scatter_results(rp, S, k.pp, nullptr, nullptr, k.go, nullptr);
+  std::lock_guard<std::mutex> g(c->mu);
+  c->n_toep_particles -= B;
+  c->n_lagdom_particles -= B;          // (the nested sweep counted them again)
+  return AGP_OK;
+}
+
+// LAPACK's info names the first non-positive leading minor IN THE CALLER'S ORDER of the observations
+// (LinearAlgebra.PosDefException(info) in the reference); a sweep on the sorted copy found the matrix not positive definite
+// at some minor of the sorted order.  The (rare) rejected particles are factored once more in the caller's order.
+static int repeat_sorted_rejects(const SweepCall& k, const SweepPlan& sp, const int32_t* h_info, SlotGuard& sg) {
+  if (!sp.sorted() || !k.h_out_info) return AGP_OK;
+  std::vector<int> bad;
+  for (int p = 0; p < k.pp.P; ++p) if (h_info[p] > 0) bad.push_back(p);
+  if (bad.empty()) return AGP_OK;
+  SubBatch S;
+  pack_particles(bad, k.pp, S);
+  S.outputs(false);
+  // (the results are on the host: hand the slot back first — sixteen concurrent callers that each kept theirs while waiting
+  // for a second one would wait for ever)
+  sg.release();
+  const int rc2 = logpdf_batch_impl(k.c, k.n, S.view(), S.lp.data(), S.info.data(), nullptr, nullptr, nullptr, false, nullptr, /*allow_lag=*/false);
+  if (rc2) return rc2;
+  // (a matrix that is indefinite to rounding may factor in one order and not in the other: the caller's order decides)
+  scatter_results(bad, S, k.pp, k.h_out_lp, k.h_out_info, nullptr, nullptr);
+  return AGP_OK;
+}
+
+// Core of agp_logpdf_batch{,_device} and agp_logpdf_grad_batch, of the coalesced single-particle entries and of the multi-device
+// shards.  d_user_* may be caller device buffers (user_stream path) or null (results copied to host h_out_*).  The body lists the
+// stages above top to bottom; it owns what must outlive them: the store's lock (StoreHits), the slot (SlotGuard) and the host
+// memory of the enqueued copies (SweepKeep).
+int logpdf_batch_impl(agp_ctx* c, int64_t n, const Particles& pp, double* h_out_lp, int32_t* h_out_info, double* d_user_lp,
+                      int32_t* d_user_info, hipStream_t user_stream, bool use_user_stream, GradOut* go, bool allow_lag) {
+  const int P = pp.P;
+  if (!c) return fail(nullptr, AGP_ERR_ARG, "null context");
+  if (P < 0 || n < 0) return fail(c, AGP_ERR_ARG, "negative size");
+  if (P == 0) return AGP_OK;
+  if (!pp.complete()) return fail(c, AGP_ERR_ARG, "null program/noise pointer");
+  if (const int rc = check_resident(c, n)) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  const SweepCall k{c, n, pp, h_out_lp, h_out_info, d_user_lp, d_user_info, user_stream, use_user_stream, go, allow_lag};
+
+  bool taken = false;
+  int rc = structured_value_split(k, taken);
+  if (taken) return rc;
+  if (tl_dense_via_store && !go && h_out_lp && h_out_info) {
+    // (no structured split for this batch: the whole of it goes through the store, as the coalesced entry does by default)
+    TlClear plain(tl_dense_via_store);
+    return extend_impl(c, n, pp, h_out_lp, h_out_info);
+  }
+
+  const SweepPlan tables = plan_tables(k);
+  Batch bt;
+  HostProf hp_cb(2);
+  rc = compile_batch(c, pp, bt, compile_opts(k, tables));
+  hp_cb.stop();
+  if (rc) return rc;
+  HostProf hp_cls(3);
+  if ((rc = count_sweep(k, tables, bt))) return rc;
+  const GradClasses gc = classify_gradients(k, bt);
+  rc = structured_grad_split(k, tables, bt, gc, taken);
+  if (taken) return rc;
+  if (gc.lag_domain) {
+    std::lock_guard<std::mutex> g(c->mu);
+    c->n_lagdom_particles += gc.n_cov;
+    if (gc.use_toep) c->n_toep_particles += gc.n_sum;
+  }
+  hp_cls.stop();
+  if (go && n == 0) {
+    std::fill(go->grad, go->grad + pp.prm_off[P], 0.0);
+    std::fill(go->gnoise, go->gnoise + P, 0.0);
+  }
+
+  StoreHits hits;                // (the store's mutex first, the workspace slot second)
+  HostProf hp_sl(4);
+  find_store_hits(k, bt, hits);
+  hp_sl.stop();
+  HostProf hp_buf(5);
+  SlotGuard sg(c);
+  SweepSlot sl;
+  if ((rc = claim_outputs(k, sg.s, sl))) return rc;
+  const SweepPlan sp = plan_geometry(k, tables, bt);
+  SweepKeep keep;
+  keep.pls.reserve(64);
+  if (n == 0) {
+    // 0 x 0 covariance: logpdf = 0, info = 0 (src/inference_smc_anneal_data.jl:185-187)
+    HIPCHK(c, hipMemsetAsync(sl.d_lp, 0, sizeof(double) * P, sl.st));
+    HIPCHK(c, hipMemsetAsync(sl.d_info, 0, sizeof(int32_t) * P, sl.st));
+  } else {
+    SweepStage dev;
+    if ((rc = sweep_buffers(k, sp, bt, sl, gc.any_toep()))) return rc;
+    if ((rc = pack_stage(k, bt, hits, sl.s, dev))) return rc;
+    hp_buf.stop();
+    HostProf hp_launch(go ? 7 : 6);
+    const Sweep w{k, sp, bt, gc, hits, sl, dev};
+    Prof pf{c, sl.s, sl.st, c->profiling};
+    double tacc[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    const size_t ev_begin = pf.mark();
+    if ((rc = upload_stage(k, bt, sl, dev, keep.goff_sorted))) return rc;
+    if ((rc = sweep_lag_tables(k, sp, bt, sl, dev))) return rc;
+    const size_t ev_h2d = pf.mark();
+    HostProf hp_fac(16);
+    pf.span(7, ev_begin, ev_h2d);
+    for (int p0 = 0; p0 < P; p0 += sp.chunk) {
+      const int Pc = std::min(sp.chunk, P - p0);
+      if ((rc = chunk_factor(w, pf, tacc, p0, Pc))) return rc;
+      if (!go) continue;
+      hp_fac.stop();
+      if ((rc = chunk_gradient(w, pf, keep, p0, Pc))) return rc;
+    }
+    pf.span(0, ev_begin, pf.mark());
+    // (a nested repeat of refused particles keeps the sweep's own figures)
+    if (c->profiling && !tl_no_toep && (rc = collect_timing(c, sl.st, pf, tacc))) return rc;
+  }
+
+  if (use_user_stream && !go && !c->profiling && !h_out_lp && !h_out_info) {
+    if ((rc = finish_on_stream(k, sl))) return rc;
+    sg.async_done = true;
+    return AGP_OK;
+  }
+  HostProf hp_wait(8);
+  int32_t* h_info = nullptr;
+  if ((rc = copy_out(k, sl, gc.any_toep(), keep, h_info))) return rc;
+  if ((rc = repeat_rejected_toeplitz(k, keep, hits, sg))) return rc;
+  return repeat_sorted_rejects(k, sp, h_info, sg);
 }
 
 

@@ -14,6 +14,8 @@ from oracle import fast as F
 from oracle import gradcheck as GC
 from oracle import oracle as O
 
+from _sweep_cases import calendar_series
+
 pytestmark = pytest.mark.gpu
 LP_TOL, PRED_TOL, GRAD_TOL = 1e-8, 1e-8, 1e-7
 
@@ -29,17 +31,7 @@ def two_engines(pkg, ts, xs):
     return a, b
 
 
-def series(pkg, freq, n, seed, shuffle=True):
-    if freq == "missing":       # a daily index with ~8 % of the observations missing
-        ts, xs = pkg.prior.calendar_series(n + n // 12, "D", seed=seed)
-        keep = np.sort(np.random.default_rng(seed).permutation(len(ts))[:n])
-        keep[0], keep[-1] = 0, len(ts) - 1
-        ts, xs = ts[keep], xs[keep]
-        if shuffle:
-            perm = np.random.default_rng(seed + 1).permutation(n)
-            ts, xs = ts[perm], xs[perm]
-        return np.ascontiguousarray(ts), np.ascontiguousarray(xs)
-    return pkg.prior.calendar_series(n, freq, seed=seed, shuffle=shuffle)
+series = calendar_series          # (tests/_sweep_cases.py: shared with tools/gpu_sweep_refactor_ab.py)
 
 
 @pytest.mark.parametrize("freq,n,P,depth,shuffle,kind", [("B", 900, 40, 3, True, 2),         # dataflow schedule, n not a tile multiple

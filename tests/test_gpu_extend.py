@@ -395,6 +395,56 @@ def test_gradient_from_resident_factor(pkg, monkeypatch, env, n):
         e.close()
 
 
+@pytest.mark.parametrize("poison", ["0", "1"])
+def test_gradient_from_resident_factors_across_chunks(pkg, monkeypatch, poison):
+    """A gradient sweep that starts from resident factors with MORE THAN ONE chunk, at the smallest shape that has two tile rows: a
+    shuffled grid of 129 points, eight particles of which the first five are resident, and a workspace that holds three particles
+    per chunk (a gradient sweep keeps A and Z = L^-T: 2 x 3 tiles each).  The chunks read the staged store slots and first rows at
+    their own offset: chunk one is resident throughout (no tile built, nothing factored), chunk two holds two resident particles and
+    one that is not, chunk three none.  Workspace chunking is invisible (tests/test_gpu_parity.py): the same bits as the sweep in one
+    chunk; and the gradient the sweep that factors everything itself computes, to the 1e-9 of test_gradient_from_resident_factor.
+    Plain and under AGP_POISON=1 (the chunks' workspace is poisoned when the slot is claimed)."""
+    NB, n, n_res = 128, 129, 5
+    ts, xs = pkg.prior.synthetic_series(n, seed=37, shuffle=True)
+    SE, lin = pkg.SquaredExponential, pkg.Linear(0.3, 0.2, 0.7)
+    nodes = [SE(0.1, 0.8), SE(0.3, 1.0) + lin, pkg.Periodic(0.7, 0.21, 1.1) * SE(0.5, 0.9), pkg.GammaExponential(0.3, 1.2, 0.7),
+             pkg.ChangePoint(SE(0.2, 0.5), pkg.Periodic(0.5, 0.3, 0.9), 0.5, 0.05), lin * SE(0.4, 0.6), SE(0.05, 1.1) + pkg.Constant(0.3),
+             pkg.Periodic(0.4, 0.33, 0.8) + lin]
+    nz = np.array([0.05, 0.02, 0.08, 0.03, 0.06, 0.04, 0.07, 0.09])
+    monkeypatch.setenv("AGP_POISON", poison)
+    a = pkg.GPEngine(0); b = pkg.GPEngine(0)
+    monkeypatch.delenv("AGP_POISON")
+    try:
+        a.set_data(ts, xs); b.set_data(ts, xs)
+        b.set_factor_cache(False)
+        a.logpdf_batch_extend(nodes[:n_res], nz[:n_res], check=False)
+        r0 = a.grad_reuse_stats()["reused"]
+        whole = a.logpdf_grad_batch(nodes, nz, check=False)
+        assert a.grad_reuse_stats()["reused"] == r0 + n_res and (whole[3] == 0).all()
+        nt = -(-n // NB)
+        a.set_workspace_limit(3 * 2 * (nt * (nt + 1) // 2) * NB * NB * 8)
+        f0 = a.poison_stats()["fills"]
+        try:
+            chunked = a.logpdf_grad_batch(nodes, nz, check=False)
+        finally:
+            a.set_workspace_limit(0)
+        assert a.grad_reuse_stats()["reused"] == r0 + 2 * n_res
+        if poison == "1":
+            assert a.poison_stats()["fills"] > f0 and a.poison_stats()["bytes"] > 0
+        assert same(chunked[0], whole[0]) and same(chunked[2], whole[2]) and same(chunked[3], whole[3])
+        assert all(same(g1, g2) for g1, g2 in zip(chunked[1], whole[1]))
+        base = b.logpdf_grad_batch(nodes, nz, check=False)
+        assert b.grad_reuse_stats()["reused"] == 0 and same(base[3], chunked[3])
+        assert lp_err(chunked[0], base[0]).max() <= 1e-10
+        refs = GC.references(nodes, nz, ts, xs)
+        for i in range(len(nodes)):
+            assert grad_err(chunked[1][i], base[1][i]) <= 1e-9 and abs(chunked[2][i] - base[2][i]) <= 1e-9 * max(1.0, abs(base[2][i])), i
+            GC.assert_grad_components(chunked[1][i], chunked[2][i], refs[i], against=(base[1][i], base[2][i]), particle_wide=False, ctx=i)
+            GC.assert_grad_components(chunked[1][i], chunked[2][i], refs[i], ctx=i)
+    finally:
+        a.close(); b.close()
+
+
 def test_single_particle_calls_use_the_store(pkg, monkeypatch):
     """agp_logpdf (Gen's per-particle call, coalesced in the library) leaves its factor in the store: the same particle on
     a longer prefix is an extension, agp_logpdf_grad at the same parameters reuses the factor, a predictive call too.

@@ -10,6 +10,8 @@ from oracle import fast as F
 from oracle import gradcheck as GC
 from oracle.predcheck import predict_80bit
 
+import _sweep_cases as SWEEP_CASES
+
 pytestmark = pytest.mark.gpu
 LP_TOL = 1e-8
 
@@ -527,8 +529,7 @@ def test_lag_path_non_positive_definite_info(pkg):
     order of the observations (the reference raises PosDefException(info) with that index)."""
     n = 256
     ts, xs = pkg.prior.synthetic_series(n, seed=11, shuffle=True)
-    ks = [pkg.SquaredExponential(5.0, 1.0), pkg.SquaredExponential(0.1, 1.0) + pkg.Linear(0.2, 0.1, 1.0)]   # smooth kernel, noise 0: singular to rounding
-    nz = np.array([0.0, 0.05])
+    ks, nz = SWEEP_CASES.non_positive_definite_pair(pkg)   # smooth kernel, noise 0: singular to rounding
     la, ia, lb, ib, took, regular = both_paths(pkg, ks, nz, ts, xs)
     assert regular and took >= 1
     assert ia[0] > 0 and ib[0] > 0 and ia[0] == ib[0] and np.isnan(la[0])
@@ -539,17 +540,7 @@ def test_lag_path_non_positive_definite_info(pkg):
 
 # ---- gradient sweeps: lag-domain contraction (include/autogp_hip.h agp_set_grad_lag_domain; csrc/agp_grad_kernel.hpp) ----
 
-def _grad_shapes(G):
-    se, ge, per = G.SquaredExponential(0.3, 0.8), G.GammaExponential(0.4, 1.3, 0.6), G.Periodic(0.7, 0.21, 1.1)
-    lin, lin2, cst, wn = G.Linear(0.3, 0.2, 0.7), G.Linear(-0.4, 0.1, 0.5), G.Constant(0.4), G.WhiteNoise(0.05)
-    covered = [se, ge, per, cst + wn, per * se, per * se + ge, lin, lin + ge, ge + lin, lin + lin2, (lin + per * se) + (ge + lin2),
-               cst * per + wn]
-    # Linear leaves inside products: moment histograms over the lags, (2d+1) n virtual elements (d = 1, 2, 3)
-    lin3 = G.Linear(0.1, 0.3, 0.4)
-    poly = [lin * se, lin * lin2, (lin + se) * per, se + lin * ge, (lin * per) * (lin2 + se) + wn, cst * lin + ge * lin2, lin * lin2 * lin3,
-            (lin * se + lin2) * (lin3 * per) * lin]
-    elementwise = [G.ChangePoint(se, per, 0.5, 0.05), lin * lin2 * lin3 * lin, G.ChangePoint(lin, se, 0.4, 0.02) + ge]
-    return covered + poly, elementwise, len(poly)
+_grad_shapes = SWEEP_CASES.grad_shapes          # (shared with tools/gpu_sweep_refactor_ab.py)
 
 
 @pytest.mark.parametrize("n_max,n,fft", [(300, 300, 1), (300, 250, 1), (128, 128, 1), (640, 513, 1), (17, 17, 1), (2, 2, 1),
@@ -607,7 +598,7 @@ def test_gradient_toeplitz_lag_sums(pkg, case):
     covered, elementwise, n_poly = _grad_shapes(G)
     # a Linear leaf that dominates its stationary neighbour: the downdate T^-1 = K^-1 + V Q V' is refused on the device and the
     # particle repeated with the explicit inverse
-    dominated = G.Linear(0.3, 0.2, 2000.0) + G.SquaredExponential(0.3, 1e-5)
+    dominated = SWEEP_CASES.dominated_linear(G)
     kernels = covered + elementwise + [dominated]
     n_refused = 1
     noises = np.linspace(0.02, 0.3, len(kernels))
