@@ -849,6 +849,126 @@ static int toeplitz_grad_sweep(agp_ctx* c, int64_t n, int32_t rank0, const Parti
   return AGP_OK;
 }
 
+// agp_debug_toeplitz: caller first columns written into rank-layout lag tables, programs of OP_LAG / OP_CONST / OP_WN / OP_LIN
+// leaves under OP_PLUS built here (no compile_batch, no k_lag_tables), every output seeded with the sentinel -7, then
+// launch_toep_logpdf as the three sweeps above call it — nothing of the kernels or the launcher is restated.
+constexpr double DEBUG_TOEP_SENTINEL = -7.0;
+constexpr int DEBUG_TOEP_LGUARD = 16;      // doubles after every particle's packed triangle: they must keep the sentinel
+static int debug_toeplitz_body(agp_ctx* c, int32_t mode, int64_t n, int64_t nj, int32_t P, const double* r, const double* r2,
+                               const int32_t* leaves, const double* const_v, const double* wn_v, const double* lin,
+                               const double* noise, const double* x, int32_t rank0, double grid_h, double grid_mid, double t_ref,
+                               int32_t raw_particle, int32_t raw_op, double* out_lp, int32_t* out_info, double* out_Lcols,
+                               double* out_fwd, double* out_sol, double* out_pacc) {
+  if (!c) return fail(nullptr, AGP_ERR_ARG, "null context");
+  if (mode < 0 || mode > 2) return fail(c, AGP_ERR_ARG, "debug probe: mode is 0 (value), 1 (gradient) or 2 (predictive)");
+  if (!r || !noise || !x || !out_lp || !out_info) return fail(c, AGP_ERR_ARG, "debug probe: null pointer");
+  if (mode >= 1 && (!out_Lcols || !out_fwd || !out_sol)) return fail(c, AGP_ERR_ARG, "debug probe: null pointer");
+  if (mode == 2 && !out_pacc) return fail(c, AGP_ERR_ARG, "debug probe: null pointer");
+  if (P < 1 || P > 4096 || n < 1) return fail(c, AGP_ERR_ARG, "debug probe: needs n >= 1 and 1 <= P <= 4096");
+  // the probe's own argument error: the joint size belongs to mode 2 (nj >= n); elsewhere it is 0 or n
+  if (mode == 2 ? nj < n : (nj != 0 && nj != n)) return fail(c, AGP_ERR_ARG, "debug probe: n and nj are inconsistent");
+  // the sizes launch_toep_logpdf refuses
+  if (n > STRUCT_JOINT_MAX) return fail(c, AGP_ERR_ARG, "structured sweeps take at most 4096 points");
+  if (mode >= 1 && n > 2048) return fail(c, AGP_ERR_ARG, "structured sweeps that store L take at most 2048 points");
+  if (mode == 2 && nj > STRUCT_JOINT_MAX) return fail(c, AGP_ERR_ARG, "structured predictive sweeps take at most 4096 joint points");
+  if (raw_particle >= P) return fail(c, AGP_ERR_ARG, "debug probe: raw opcode for a particle outside the batch");
+  const int N = mode == 2 ? (int)nj : (int)n, mF = N - (int)n;
+  const long long tri = (long long)n * (n + 1) / 2, Lstride = tri + DEBUG_TOEP_LGUARD;
+  if (mode >= 1 && (int64_t)P * Lstride > ((int64_t)1 << 26)) return fail(c, AGP_ERR_ARG, "debug probe: batch too large");
+  const int ldv = round_up(n, NB), pstride = std::max(NB, round_up(mF, NB)), stride = round_up(N, 256);
+  // programs: [LAG] [LAG +] [CONST +] [WN +] ([LIN +])* [raw +]; parameters in leaf order
+  std::vector<ProgHdr> hdr((size_t)P);
+  std::vector<uint8_t> ops;
+  std::vector<double> prm, tab;
+  int n_tab = 0;
+  for (int p = 0; p < P; ++p) {
+    const int lv = leaves ? leaves[p] : 0, n_lin = (lv >> 3) & 3;
+    if (lv < 0 || lv >= 32 || n_lin > 2) return fail(c, AGP_ERR_ARG, "debug probe: leaves holds bits 0-2 and a Linear count of 0 to 2");
+    if (((lv & 1) && !r2) || ((lv & 2) && !const_v) || ((lv & 4) && !wn_v) || (n_lin && !lin))
+      return fail(c, AGP_ERR_ARG, "debug probe: a leaf is requested without its values");
+    ProgHdr& h = hdr[(size_t)p];
+    h = ProgHdr{};
+    h.op_off = (int32_t)ops.size(); h.prm_off = (int32_t)prm.size(); h.lag_off = n_tab;
+    h.n_lag = (lv & 1) ? 2 : 1;
+    for (int t = 0; t < h.n_lag; ++t) {
+      const double* src = (t == 0 ? r : r2) + (size_t)p * N;
+      tab.insert(tab.end(), src, src + N);
+      tab.resize((size_t)(n_tab + t + 1) * stride, 0.0);
+      ops.push_back((uint8_t)OP_LAG);
+      if (t) ops.push_back((uint8_t)OP_PLUS);
+    }
+    n_tab += h.n_lag;
+    if (lv & 2) { ops.push_back((uint8_t)OP_CONST); ops.push_back((uint8_t)OP_PLUS); prm.push_back(const_v[p]); }
+    if (lv & 4) { ops.push_back((uint8_t)OP_WN); ops.push_back((uint8_t)OP_PLUS); prm.push_back(wn_v[p]); }
+    for (int q = 0; q < n_lin; ++q) {
+      ops.push_back((uint8_t)OP_LIN); ops.push_back((uint8_t)OP_PLUS);
+      prm.insert(prm.end(), lin + ((size_t)p * 2 + q) * 3, lin + ((size_t)p * 2 + q) * 3 + 3);
+    }
+    if (p == raw_particle) {
+      if (raw_op < 0 || raw_op > 255) return fail(c, AGP_ERR_ARG, "debug probe: raw opcode out of range");
+      ops.push_back((uint8_t)raw_op); ops.push_back((uint8_t)OP_PLUS);
+      prm.insert(prm.end(), 3, 0.0);          // (no opcode reads more than three parameters)
+    }
+    h.n_ops = (int32_t)ops.size() - h.op_off; h.n_prm = (int32_t)prm.size() - h.prm_off;
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  SlotGuard sg(c);
+  Slot* s = sg.s;
+  if (!s->stream) HIPCHK(c, hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
+  hipStream_t st = s->stream;
+  const size_t nL = mode >= 1 ? (size_t)P * Lstride : 0, nV = mode >= 1 ? (size_t)P * 4 * ldv : 0, nA = mode == 2 ? (size_t)P * 4 * pstride : 0;
+  HIPCHK(c, s->hdr.ensure(sizeof(ProgHdr) * (size_t)P));
+  HIPCHK(c, s->ops.ensure(ops.size() + 4));
+  HIPCHK(c, s->prm.ensure(sizeof(double) * std::max<size_t>(1, prm.size())));
+  HIPCHK(c, s->noise.ensure(sizeof(double) * (size_t)P));
+  HIPCHK(c, s->mu1.ensure(sizeof(double) * (size_t)n));
+  HIPCHK(c, s->lagtab.ensure(sizeof(double) * tab.size()));
+  HIPCHK(c, s->out_lp.ensure(sizeof(double) * (size_t)P + sizeof(int32_t) * (size_t)P));
+  if (nL) HIPCHK(c, s->A.ensure(sizeof(double) * nL));
+  if (nV) { HIPCHK(c, s->alpha.ensure(sizeof(double) * nV)); HIPCHK(c, s->tsol.ensure(sizeof(double) * nV)); }
+  if (nA) HIPCHK(c, s->pred_mean.ensure(sizeof(double) * nA));
+  std::vector<double> sent(std::max<size_t>({nL, nV, nA, (size_t)P}), DEBUG_TOEP_SENTINEL);
+  std::vector<int32_t> isent((size_t)P, (int32_t)DEBUG_TOEP_SENTINEL);
+  double* d_lp = s->out_lp.as<double>();
+  int32_t* d_info = reinterpret_cast<int32_t*>(d_lp + P);
+  // (pageable sources: the runtime has staged a pageable host-to-device copy when the call returns, so an early error return
+  // below may destroy these vectors before the stream has run)
+  HIPCHK(c, hipMemcpyAsync(s->hdr.p, hdr.data(), sizeof(ProgHdr) * (size_t)P, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(s->ops.p, ops.data(), ops.size(), hipMemcpyHostToDevice, st));
+  if (!prm.empty()) HIPCHK(c, hipMemcpyAsync(s->prm.p, prm.data(), sizeof(double) * prm.size(), hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(s->noise.p, noise, sizeof(double) * (size_t)P, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(s->mu1.p, x, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(s->lagtab.p, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(d_lp, sent.data(), sizeof(double) * (size_t)P, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(d_info, isent.data(), sizeof(int32_t) * (size_t)P, hipMemcpyHostToDevice, st));
+  if (nL) HIPCHK(c, hipMemcpyAsync(s->A.p, sent.data(), sizeof(double) * nL, hipMemcpyHostToDevice, st));
+  if (nV) {
+    HIPCHK(c, hipMemcpyAsync(s->alpha.p, sent.data(), sizeof(double) * nV, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(s->tsol.p, sent.data(), sizeof(double) * nV, hipMemcpyHostToDevice, st));
+  }
+  if (nA) HIPCHK(c, hipMemcpyAsync(s->pred_mean.p, sent.data(), sizeof(double) * nA, hipMemcpyHostToDevice, st));
+  ToepArgs ta = {};
+  ta.xs = s->mu1.as<double>(); ta.n = (int)n; ta.P = P; ta.rank0 = rank0;
+  ta.hdr = s->hdr.as<ProgHdr>(); ta.ops = s->ops.as<uint8_t>(); ta.prm = s->prm.as<double>(); ta.noise = s->noise.as<double>();
+  ta.lagtab = s->lagtab.as<double>(); ta.lag_stride = stride;
+  ta.grid_h = grid_h; ta.grid_mid = grid_mid; ta.tref = t_ref;
+  ta.out_lp = d_lp; ta.out_info = d_info;
+  if (mode >= 1) { ta.Lcols = s->A.as<double>(); ta.Lstride = Lstride; ta.fwd = s->alpha.as<double>(); ta.sol = s->tsol.as<double>(); ta.ldv = ldv; }
+  if (mode == 2) { ta.nj = N; ta.pacc = s->pred_mean.as<double>(); ta.pstride = pstride; }
+  HIPCHK(c, launch_toep_logpdf(st, ta));
+  // (pageable destinations: every copy has completed when the synchronisation returns, and nothing below fails in between)
+  HIPCHK(c, hipMemcpyAsync(out_lp, d_lp, sizeof(double) * (size_t)P, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(out_info, d_info, sizeof(int32_t) * (size_t)P, hipMemcpyDeviceToHost, st));
+  if (nL) HIPCHK(c, hipMemcpyAsync(out_Lcols, s->A.p, sizeof(double) * nL, hipMemcpyDeviceToHost, st));
+  if (nV) {
+    HIPCHK(c, hipMemcpyAsync(out_fwd, s->alpha.p, sizeof(double) * nV, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(out_sol, s->tsol.p, sizeof(double) * nV, hipMemcpyDeviceToHost, st));
+  }
+  if (nA) HIPCHK(c, hipMemcpyAsync(out_pacc, s->pred_mean.p, sizeof(double) * nA, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  return AGP_OK;
+}
+
 static thread_local bool tl_in_toeplitz = false;
 static thread_local bool tl_in_tgrad = false;
 // Class-aware value sweeps of the coalesced single-particle entry (run_coalesced, opt-in level AGP_LAG >= 2): the dense part of the
@@ -1897,6 +2017,17 @@ int logpdf_batch_impl(agp_ctx* c, int64_t n, const Particles& pp, double* h_out_
 extern "C" {
 
 const char* agp_version(void) { return "autogp-hip 0.1.0 (gfx950)"; }
+
+int agp_debug_toeplitz(agp_ctx* c, int32_t mode, int64_t n, int64_t nj, int32_t P, const double* r, const double* r2,
+                       const int32_t* leaves, const double* const_v, const double* wn_v, const double* lin, const double* noise,
+                       const double* x, int32_t rank0, double grid_h, double grid_mid, double t_ref, int32_t raw_particle,
+                       int32_t raw_op, double* out_lp, int32_t* out_info, double* out_Lcols, double* out_fwd, double* out_sol,
+                       double* out_pacc) {
+  return abi_guard(c, [&] {
+    return debug_toeplitz_body(c, mode, n, nj, P, r, r2, leaves, const_v, wn_v, lin, noise, x, rank0, grid_h, grid_mid, t_ref,
+                               raw_particle, raw_op, out_lp, out_info, out_Lcols, out_fwd, out_sol, out_pacc);
+  });
+}
 
 int agp_init(agp_ctx** out, int device_id) {
   return abi_guard(nullptr, [&]() -> int {

@@ -12,7 +12,10 @@
 // coefficient rho_k = v_k / u_k and a shift per column — so L need not be stored: column k updates the right-hand sides
 // (column-oriented forward substitution) and is gone.  O(n^2) flops per particle instead of n^3/3; stable for positive definite
 // Toeplitz matrices (Bojanczyk, Brent, de Hoog, Sweet 1995), measured 5e-12 of |logpdf| against the dense factorisation on the
-// benchmark population (cond up to 1e8).  The reference (src/Model.jl:134-136: Gen.mvnormal = dense Cholesky) is what the default
+// benchmark population (cond up to 1e8).
+// (L, both solves, log|T| and the predictive rows on their own, on caller-supplied first columns up to cond 3e10, against float64
+// restatements of the algorithm with the direct and the mixed rotation: profiles/toeplitz_probe_accuracy.txt, tests/test_gpu_toeplitz_probe.py.)
+// The reference (src/Model.jl:134-136: Gen.mvnormal = dense Cholesky) is what the default
 // value path mirrors; this one is what a regular grid allows.
 //
 //   k_toep_logpdf<NR>                     value sweep: log|T|, L^-1 [x, 1, t], the 2x2 corrections -> logpdf
@@ -25,7 +28,9 @@
 // j % NT (register j / NT): v and the right-hand sides stay in registers in natural coordinates; u lives in LDS at position j - k
 // (it is the vector that shifts: element j reads what element j - 1 wrote one step earlier), pivots and the step's right-hand-side
 // entries go through a double-buffered LDS slot; the pivot L(k,k) and its reciprocal are recurrences every thread carries — ONE
-// barrier per column, no division on the chain.  |rho| >= 1 (not positive definite to rounding) flags the particle: the host repeats
+// barrier per column, no division on the chain; the STORE instantiations write the recurrence's pivot as L(k,k), so that the forward
+// solve (which multiplied by its reciprocal) and k_toep_back (which divides by the stored diagonal) are solves with ONE factor.
+// |rho| >= 1 (not positive definite to rounding) flags the particle: the host repeats
 // it with the dense path in the caller's order, which also supplies LAPACK's info.
 #pragma once
 #include "agp_cov_kernel.hpp"
@@ -119,7 +124,14 @@ __global__ __launch_bounds__(NT) void k_toep_logpdf(ToepArgs a) {
     const double* pk = piv + 8 * (k & 1);
     double* pn = piv + 8 * ((k + 1) & 1);
     const double rho = pk[0] * ipu;
-    const double om = (1.0 - rho) * (1.0 + rho);    // 1 - rho^2 = L(k,k)^2 / L(k-1,k-1)^2
+    // 1 - rho^2 = L(k,k)^2 / L(k-1,k-1)^2, from the ROUNDED rho the rotation below applies: contracted into fma(-pk[0], ipu, 1.0) the
+    // two factors came from the unrounded product, c = om^-1/2 then belonged to a rho one rounding away — an error of cs^2 u in c
+    // (2.5e-12 at rho = 0.99998), and a rotation that does not preserve u^2 - v^2: 35 gamma_n in |T - L L'| where 0.06 is due
+    double om;
+    {
+#pragma clang fp contract(off)
+      om = (1.0 - rho) * (1.0 + rho);
+    }
     if (!(om > 0.0)) { bad = true; break; }         // (uniform: every thread sees the same pivots)
     // c = om^-1/2: v_rsq_f64 + one third-order step (full precision)
     double cs;
@@ -151,8 +163,12 @@ __global__ __launch_bounds__(NT) void k_toep_logpdf(ToepArgs a) {
         const double vn = cs * (vj - rho * uj);
         ul[j - k] = un;                              // (read next step by the owner of element j + 1)
         v[r] = vn;
-        if (STORE && (!JOINT || (ktr && j < n))) Lc[coff + j] = un;
-        if (JOINT && !ktr) be[r] = fma(un, un, be[r]);      // (rows j >= k >= n: the Schur complement's diagonal)
+        // (entry k itself is the recurrence's pivot, the one whose reciprocal the forward solve multiplied by: k_toep_back divides by
+        // the stored diagonal, and u's own entry k — c (u - rho v) with v = rho u, a cancellation — differs from the recurrence by
+        // 1e-10 relative at rho = 0.9999, which made L^-1 b and L^-T L^-1 b solves with two different factors)
+        const double lj = j == k ? pu : un;
+        if (STORE && (!JOINT || (ktr && j < n))) Lc[coff + j] = lj;
+        if (JOINT && !ktr) be[r] = fma(lj, lj, be[r]);      // (rows j >= k >= n: the Schur complement's diagonal)
         if (j > k) {
           bx[r] = fma(-un, yx, bx[r]);
           if (lin) { b1[r] = fma(-un, y1, b1[r]); bt[r] = fma(-un, yt, bt[r]); }

@@ -40,6 +40,7 @@ EXPORTED_SYMBOLS = [
     "agp_debug_factor_batch", "agp_logpdf_series_batch", "agp_debug_series_factor", "agp_logpdf_grad_series_batch",
     "agp_predict_series_batch", "agp_debug_remove_factor", "agp_predict_quantile_series_batch",
     "agp_predict_logpdf_series_batch", "agp_predict_sample_series_batch", "agp_predict_sum_series_batch",
+    "agp_debug_toeplitz",
 ]
 COMM_ID_BYTES = 128
 SERIES_MAX_N = 176      # AGP_SERIES_MAX_N of include/autogp_hip.h: the longest series of logpdf_series_batch
@@ -186,6 +187,9 @@ def load_library(path=None):
     lib.agp_remove_data.argtypes = [vp, C.POINTER(C.c_int64), C.c_int64]; lib.agp_remove_data.restype = C.c_int
     lib.agp_debug_remove_factor.argtypes = [vp, dp, dp, C.c_int64, C.c_int32, C.POINTER(C.c_int64), C.c_int64, dp, dp, dp, dp, ip]
     lib.agp_debug_remove_factor.restype = C.c_int
+    lib.agp_debug_toeplitz.argtypes = [vp, C.c_int32, C.c_int64, C.c_int64, C.c_int32, dp, dp, ip, dp, dp, dp, dp, dp, C.c_int32, C.c_double,
+                                       C.c_double, C.c_double, C.c_int32, C.c_int32, dp, ip, dp, dp, dp, dp]
+    lib.agp_debug_toeplitz.restype = C.c_int
     lib.agp_get_remove_stats.argtypes = [vp, C.POINTER(C.c_int64), C.c_int32]; lib.agp_get_remove_stats.restype = C.c_int
     lib.agp_set_remove_update.argtypes = [vp, C.c_int32]; lib.agp_set_remove_update.restype = C.c_int
     lib.agp_remove_data_multi.argtypes = [C.POINTER(vp), C.c_int32, C.POINTER(C.c_int64), C.c_int64]; lib.agp_remove_data_multi.restype = C.c_int
@@ -1276,6 +1280,61 @@ class GPEngine:
                                                       idx.size, _dp(L), _dp(alpha), _dp(part), _dp(winv), _ip(info)))
         # (column-major blocks: the transpose of each is the inverse as a matrix)
         return L, alpha, part, np.ascontiguousarray(winv.transpose(0, 1, 2, 4, 3)), info
+
+    def debug_toeplitz(self, mode, r, x, noise, m_future=0, r2=None, const=None, wn=None, lin=None, rank0=0, grid_h=1.0, grid_mid=0.0,
+                       t_ref=0.0, raw=None):
+        """The structured sweeps' launcher on caller first columns (agp_debug_toeplitz: launch_toep_logpdf itself, programs and
+        rank-layout tables built from the arguments, every output seeded with the sentinel -7).  mode 0 value, 1 gradient,
+        2 predictive; r (P, N) first columns without noise, N = n + m_future (mode 2) or n = len(x); noise (P).  Per particle,
+        None = absent: r2 = (mask (P) bool, rows (mask.sum(), N)) second tables of the masked particles (the kernel adds the two
+        tables entry by entry), const / wn (P) values with NaN = no leaf, lin a list of P lists of up to two (centre, bias, amp);
+        raw = (particle, opcode) plants one more leaf.  -> dict(lp, info; modes 1, 2: Lcols (P, n(n+1)/2 + 16) packed columns
+        and their guard, fwd, sol (P, 4, ldv); mode 2: pacc (P, 4, pstride))."""
+        r = np.ascontiguousarray(r, dtype=np.float64)
+        x = np.ascontiguousarray(x, dtype=np.float64).ravel()
+        if r.ndim != 2:
+            raise ValueError("r must have shape (P, N)")
+        P, N = r.shape
+        n = x.size
+        if mode == 2:
+            if N != n + m_future:
+                raise ValueError("r must have n + m_future columns")
+        elif N != n or m_future:
+            raise ValueError("r must have n columns (m_future belongs to mode 2)")
+        noise = np.ascontiguousarray(np.broadcast_to(np.asarray(noise, dtype=np.float64), (P,)))
+        leaves = np.zeros(P, dtype=np.int32)
+        r2a = None
+        if r2 is not None:
+            mask, rows = r2
+            mask = np.asarray(mask, dtype=bool)
+            r2a = np.zeros((P, N)); r2a[mask] = rows
+            leaves[mask] |= 1
+        cv = wv = None
+        if const is not None:
+            cv = np.ascontiguousarray(const, dtype=np.float64); leaves[~np.isnan(cv)] |= 2
+        if wn is not None:
+            wv = np.ascontiguousarray(wn, dtype=np.float64); leaves[~np.isnan(wv)] |= 4
+        la = None
+        if lin is not None:
+            la = np.zeros((P, 2, 3))
+            for p, ls in enumerate(lin):
+                if len(ls) > 2:
+                    raise ValueError("at most two Linear leaves per particle")
+                for q, l3 in enumerate(ls):
+                    la[p, q] = l3
+                leaves[p] |= len(ls) << 3
+        rp, ro = (-1, 0) if raw is None else raw
+        ldv = 128 * -(-n // 128); pstride = max(128, 128 * -(-(N - n) // 128))
+        out = dict(lp=np.empty(P), info=np.zeros(P, dtype=np.int32))
+        if mode >= 1:
+            out.update(Lcols=np.empty((P, n * (n + 1) // 2 + 16)), fwd=np.empty((P, 4, ldv)), sol=np.empty((P, 4, ldv)))
+        if mode == 2:
+            out["pacc"] = np.empty((P, 4, pstride))
+        self._check(self._lib.agp_debug_toeplitz(self._ctx, int(mode), n, N if mode == 2 else 0, P, _dp(r), _dp(r2a), _ip(leaves), _dp(cv),
+                                                 _dp(wv), _dp(la), _dp(noise), _dp(x), int(rank0), float(grid_h), float(grid_mid),
+                                                 float(t_ref), int(rp), int(ro), _dp(out["lp"]), _ip(out["info"]), _dp(out.get("Lcols")),
+                                                 _dp(out.get("fwd")), _dp(out.get("sol")), _dp(out.get("pacc"))))
+        return out
 
     def debug_mfma_probe(self, A, B):
         A = _f64(A).reshape(16, 4); B = _f64(B).reshape(4, 16); D = np.empty((16, 16))

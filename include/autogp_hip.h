@@ -1008,6 +1008,35 @@ int agp_debug_remove_factor(agp_ctx* ctx, const double* L0 /* P*n*n */, const do
                             const int64_t* idx, int64_t k, double* out_L /* P*np'*np' */, double* out_alpha /* P*np' */,
                             double* out_partial /* P*nt'*2 */, double* out_winv /* P*nt'*8*256 or NULL */, int32_t* out_info /* P */);
 
+/* Run the structured (Schur / Toeplitz) sweeps' launcher on P caller-supplied first columns of ONE size.  mode 0: the value sweep
+ * (1 <= n <= 4096), 1: the gradient sweep's recursion and backward substitution (n <= 2048), 2: the predictive sweep's (n <= 2048
+ * training points followed by nj - n future points, n <= nj <= 4096); nj is 0 or n in modes 0 and 1.  With N = nj in mode 2 and n
+ * otherwise, particle p's first column r[p * N + g] (g = 0 .. N-1, WITHOUT the noise) is written into a lag table of the rank
+ * layout, and the entry builds the particle's program itself from leaves[p] (NULL: all 0):
+ *   bit 0  a second table r2[p * N + g]: two OP_LAG leaves under OP_PLUS (the kernel adds the tables entry by entry)
+ *   bit 1  a Constant leaf of value const_v[p]          bit 2  a WhiteNoise leaf of value wn_v[p]
+ *   bits 3-4  the number (0 to 2) of Linear leaves, leaf q with (centre, bias, amplitude) = lin[(2 p + q) * 3 + 0 .. 2]
+ * raw_particle >= 0: that particle's program also gets a leaf with opcode raw_op (three zero parameters) — a leaf the kernels
+ * refuse; -1: none.  noise (P), one shared x (n), and rank0, grid_h, grid_mid, t_ref as the sweeps pass them: point j of the
+ * sweep has t - t_ref = (rank0 + j - grid_mid) grid_h.  Every output buffer is filled with the sentinel -7 (out_info: -7) before
+ * the launch, so what a kernel did not store still reads -7:
+ *   out_lp, out_info (P)   the log density and 0, or NaN and 1 for a refused particle (|rho| >= 1, a leaf that is not the kernels')
+ *   out_Lcols    modes 1, 2: P x (n (n + 1) / 2 + 16), column k of L at k n - k (k - 1) / 2 - k + j for rows j = k .. n-1; the 16
+ *                doubles after every triangle are never written
+ *   out_fwd      modes 1, 2: P x 4 x ldv, ldv = 128 ceil(n / 128): L^-1 [x, e_first, 1, t - t_ref]
+ *   out_sol      modes 1, 2: P x 4 x ldv: T^-1 [x, e_first, 1, t - t_ref] (left at the sentinel for a refused particle)
+ *   out_pacc     mode 2: P x 4 x pstride, pstride = max(128, 128 ceil((nj - n) / 128)): per future point L21 L11^-1 [x, 1, t - t_ref]
+ *                and the diagonal of T22 - T21 T11^-1 T12
+ * AGP_ERR_ARG: a size the launcher refuses (above), n and nj inconsistent, P < 1 or P > 4096, more than 2^26 doubles of packed
+ * triangles, leaves outside the bits above or without their values, a raw opcode outside 0 .. 255, any null pointer among the
+ * arrays the mode uses.  Borrows a workspace slot and reads or changes nothing else the context holds. */
+int agp_debug_toeplitz(agp_ctx* ctx, int32_t mode, int64_t n, int64_t nj, int32_t P, const double* r /* P*N */,
+                       const double* r2 /* P*N or NULL */, const int32_t* leaves /* P or NULL */, const double* const_v /* P or NULL */,
+                       const double* wn_v /* P or NULL */, const double* lin /* P*2*3 or NULL */, const double* noise /* P */,
+                       const double* x /* n */, int32_t rank0, double grid_h, double grid_mid, double t_ref, int32_t raw_particle,
+                       int32_t raw_op, double* out_lp /* P */, int32_t* out_info /* P */, double* out_Lcols, double* out_fwd,
+                       double* out_sol, double* out_pacc);
+
 /* Probe of the fp64 MFMA fragment layout: D = A(16x4) * B(4x16), row-major host arrays. */
 int agp_debug_mfma_probe(agp_ctx* ctx, const double* A, const double* B, double* D);
 
