@@ -1183,13 +1183,19 @@ static CompileOpts compile_opts(const SweepCall& k, const SweepPlan& sp) {
   return co;
 }
 
-// The sweep's counters and what a compiled gradient batch may still be refused for.
+// What a compiled gradient batch may still be refused for.
+static int gradient_limits(const SweepCall& k, const Batch& bt) {
+  if (k.go && bt.g_max_nodes > 64) return fail(k.c, AGP_ERR_PROGRAM, "gradient supports kernel trees of up to 64 nodes");
+  if (k.go && k.n > 23040) return fail(k.c, AGP_ERR_ARG, "gradient sweeps address a particle's packed matrix with 32-bit byte offsets: n <= 23040");
+  return AGP_OK;
+}
+
+// The sweep's counters (and gradient_limits, in the order the sweeps always had).
 static int count_sweep(const SweepCall& k, const SweepPlan& sp, const Batch& bt) {
   agp_ctx* c = k.c;
   if (sp.mode == TableMode::Rank) { std::lock_guard<std::mutex> g(c->mu); ++c->n_lag_rank_sweeps; }
   if (sp.compact()) { std::lock_guard<std::mutex> g(c->mu); ++c->n_clt_sweeps; }
-  if (k.go && bt.g_max_nodes > 64) return fail(c, AGP_ERR_PROGRAM, "gradient supports kernel trees of up to 64 nodes");
-  if (k.go && k.n > 23040) return fail(c, AGP_ERR_ARG, "gradient sweeps address a particle's packed matrix with 32-bit byte offsets: n <= 23040");
+  if (const int rc = gradient_limits(k, bt)) return rc;
   if (sp.mode == TableMode::SortedLag) { std::lock_guard<std::mutex> g(c->mu); ++c->n_lag_sweeps; }
   std::lock_guard<std::mutex> g(c->mu);
   for (int i = 0; i < 5; ++i) c->eval_stats[i] = bt.n_eval[i];
@@ -1523,6 +1529,22 @@ static int sweep_lag_tables(const SweepCall& k, const SweepPlan& sp, const Batch
   return AGP_OK;
 }
 
+// The tile builder's arguments for the chunk of sorted particles [p0, p0 + Pc) of a sweep over n points: the series copy, programs
+// and tables the plan chose (chunk_factor adds the resident rows and the fused share; agp_debug_cov_sweep launches it as it is).
+static CovArgs sweep_cov_args(const agp_ctx* c, const SweepPlan& sp, const SweepStage& dev, Slot* s, int n, int p0, int Pc) {
+  CovArgs cv = {};
+  cv.tt = sp.sorted() ? c->d_ts_s : c->d_ts; cv.n1 = n; cv.n1_pad = sp.n_pad; cv.m2 = 0; cv.nt = sp.nt;
+  cv.hdr = dev.hdr + p0; cv.ops = dev.ops; cv.prm = dev.prm;
+  cv.noise = dev.noise + p0; cv.A = s->A.as<double>();
+  cv.strideA = sp.strideA; cv.P = Pc; cv.logdt = (sp.ge_tab && !sp.tables()) ? c->d_logdt : nullptr;
+  cv.lagtab = sp.tables() ? s->lagtab.as<double>() : nullptr;
+  cv.lagr = sp.mode == TableMode::Rank ? c->d_rank : sp.mode == TableMode::CompactWhole ? c->d_clt_key :
+            sp.mode == TableMode::CompactSorted ? c->d_clt_key_s : nullptr;
+  cv.lag_stride = sp.tab_units * 256;
+  if (sp.compact()) { cv.clt.B = c->d_clt_B; cv.clt.W = sp.mode == TableMode::CompactSorted ? c->clt_W : 0; cv.clt.nB = sp.clt_nB; cv.clt.gstride = sp.tab_gstride; }
+  return cv;
+}
+
 // One sweep's fixed parts, as the per-chunk stages read them.
 struct Sweep {
   const SweepCall& k; const SweepPlan& sp; const Batch& bt; const GradClasses& gc; const StoreHits& hits; const SweepSlot& sl; const SweepStage& dev;
@@ -1538,16 +1560,7 @@ static int chunk_factor(const Sweep& w, Prof& pf, double* tacc, int p0, int Pc) 
   const Batch& bt = w.bt;
   const int n = (int)w.k.n, nt = sp.nt, n_hit = w.hits.n_hit;
   launch_init_vec(q, sp.n_pad, Pc, s->vec.as<double>(), sp.sorted() ? c->d_xs_s : c->d_xs, (const double*)nullptr, n, s->info.as<int>(), s->ready.as<int>());
-  CovArgs cv = {};
-  cv.tt = sp.sorted() ? c->d_ts_s : c->d_ts; cv.n1 = n; cv.n1_pad = sp.n_pad; cv.m2 = 0; cv.nt = nt;
-  cv.hdr = w.dev.hdr + p0; cv.ops = w.dev.ops; cv.prm = w.dev.prm;
-  cv.noise = w.dev.noise + p0; cv.A = s->A.as<double>();
-  cv.strideA = sp.strideA; cv.P = Pc; cv.logdt = (sp.ge_tab && !sp.tables()) ? c->d_logdt : nullptr;
-  cv.lagtab = sp.tables() ? s->lagtab.as<double>() : nullptr;
-  cv.lagr = sp.mode == TableMode::Rank ? c->d_rank : sp.mode == TableMode::CompactWhole ? c->d_clt_key :
-            sp.mode == TableMode::CompactSorted ? c->d_clt_key_s : nullptr;
-  cv.lag_stride = sp.tab_units * 256;
-  if (sp.compact()) { cv.clt.B = c->d_clt_B; cv.clt.W = sp.mode == TableMode::CompactSorted ? c->clt_W : 0; cv.clt.nB = sp.clt_nB; cv.clt.gstride = sp.tab_gstride; }
+  CovArgs cv = sweep_cov_args(c, sp, w.dev, s, n, p0, Pc);
   int i0min = 0;
   if (n_hit > 0) {
     // resident factors: forward-solve vector and partials are copied out of the store; L and the inverse blocks
@@ -1910,6 +1923,105 @@ static int repeat_sorted_rejects(const SweepCall& k, const SweepPlan& sp, const 
   return AGP_OK;
 }
 
+// agp_debug_cov_sweep: the stages of a sweep up to its covariance launch, unchanged and in the sweep's order — plan_tables,
+// compile_batch (compile_opts + never_fuse: every tile from k_cov_tiles), plan_geometry, sweep_buffers, pack_stage, upload_stage,
+// sweep_lag_tables, launch_cov with sweep_cov_args — on tiles and tables seeded with the sentinel -7; then the tiles, the tables and
+// the tables' "times" are copied out.  No factorisation, no store lookup (empty StoreHits), no dedup, no counter.
+constexpr double DEBUG_COV_SENTINEL = -7.0;
+constexpr int DEBUG_COV_MODE_WORDS = 8;
+static int debug_cov_sweep_body(agp_ctx* c, int64_t n, const Particles& pp, bool for_gradient, bool allow_tables, double* out_K,
+                                int32_t* out_order, int32_t* out_mode, double* out_tab, double* out_rep) {
+  const int P = pp.P;
+  if (!c) return fail(nullptr, AGP_ERR_ARG, "null context");
+  if (P < 1 || n < 1) return fail(c, AGP_ERR_ARG, "debug probe: needs n >= 1 and P >= 1");
+  if (!pp.complete()) return fail(c, AGP_ERR_ARG, "null program/noise pointer");
+  if (!out_mode || (out_K && !out_order)) return fail(c, AGP_ERR_ARG, "debug probe: null pointer");
+  if (const int rc = check_resident(c, n)) return rc;
+  {
+    const int64_t nt = (n + NB - 1) / NB;
+    if ((int64_t)P * (nt * (nt + 1) / 2) * NB2 > ((int64_t)1 << 27)) return fail(c, AGP_ERR_ARG, "debug probe: batch too large");
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  std::vector<double> gdummy;          // (a gradient plan is selected by k.go != nullptr; nothing is ever written through it)
+  GradOut go{nullptr, nullptr};
+  if (for_gradient) {
+    if (!offsets_sane(pp)) return fail(c, AGP_ERR_ARG, "malformed offsets");
+    gdummy.assign((size_t)std::max(1, pp.prm_off[P]) + (size_t)P, 0.0);
+    go.grad = gdummy.data(); go.gnoise = gdummy.data() + std::max(1, pp.prm_off[P]);
+  }
+  const SweepCall k{c, n, pp, nullptr, nullptr, nullptr, nullptr, nullptr, false, for_gradient ? &go : nullptr, allow_tables};
+  const SweepPlan tables = plan_tables(k);
+  Batch bt;
+  CompileOpts co = compile_opts(k, tables);
+  co.never_fuse = true;
+  int rc = compile_batch(c, pp, bt, co);
+  if (rc) return rc;
+  if ((rc = gradient_limits(k, bt))) return rc;
+  const int nt = (int)((n + NB - 1) / NB);
+  const int tab_len = !tables.tables() || bt.n_lag_tables <= 0 ? 0 : tables.by_rank() ? tables.tab_gstride : nt * 256;
+  const int rep_len = tab_len == 0 ? 0 : tables.by_rank() ? tables.tab_gstride : nt * NB;
+  const bool logdt = tables.ge_tab && !tables.tables() && c->d_logdt != nullptr;
+  out_mode[0] = (int32_t)tables.mode; out_mode[1] = tables.tab_units; out_mode[2] = tables.tab_gstride;
+  out_mode[3] = bt.n_lag_tables; out_mode[4] = tab_len; out_mode[5] = rep_len; out_mode[6] = logdt ? 1 : 0;
+  out_mode[7] = bt.max_depth <= 4 ? 4 : 8;
+  for (int q = 0; q < P; ++q) {
+    const ProgHdr& h = bt.hdr[(size_t)q];
+    out_mode[DEBUG_COV_MODE_WORDS + bt.order[(size_t)q]] = h.n_ops == 1 ? 0 : ((h.flags & PROG_CHAIN) && bt.max_depth <= 4) ? 1 : 2;
+  }
+  if (!out_K) return AGP_OK;          // (a sizing call: the plan and the classes only)
+
+  StoreHits hits;          // (empty: the store is not asked)
+  SlotGuard sg(c);
+  SweepSlot sl;
+  if ((rc = claim_outputs(k, sg.s, sl))) return rc;
+  Slot* s = sl.s;
+  const SweepPlan sp = plan_geometry(k, tables, bt);
+  SweepStage dev;
+  std::vector<int32_t> goff_sorted;
+  if ((rc = sweep_buffers(k, sp, bt, sl, false))) return rc;
+  if ((rc = pack_stage(k, bt, hits, s, dev))) return rc;
+  const size_t nA = (size_t)sp.strideA * (size_t)sp.chunk, nT = (size_t)bt.n_lag_tables * (size_t)tab_len;
+  std::vector<double> sent(std::max(nA, nT), DEBUG_COV_SENTINEL), hA(nA);
+  if (nT) {          // (sweep_lag_tables asks for exactly this size: the buffer it finds is the seeded one)
+    HIPCHK(c, s->lagtab.ensure(sizeof(double) * nT));
+    HIPCHK(c, hipMemcpyAsync(s->lagtab.p, sent.data(), sizeof(double) * nT, hipMemcpyHostToDevice, sl.st));
+  }
+  if ((rc = upload_stage(k, bt, sl, dev, goff_sorted))) return rc;
+  if ((rc = sweep_lag_tables(k, sp, bt, sl, dev))) return rc;
+  const size_t npad = (size_t)sp.n_pad;
+  std::fill(out_K, out_K + (size_t)P * npad * npad, DEBUG_COV_SENTINEL);
+  for (int p0 = 0; p0 < P; p0 += sp.chunk) {
+    const int Pc = std::min(sp.chunk, P - p0);
+    HIPCHK(c, hipMemcpyAsync(s->A.p, sent.data(), sizeof(double) * (size_t)sp.strideA * Pc, hipMemcpyHostToDevice, sl.st));
+    const CovArgs cv = sweep_cov_args(c, sp, dev, s, (int)n, p0, Pc);
+    HIPCHK(c, launch_cov(sl.st, cv, sp.ntiles, Pc, bt.max_cp, bt.max_depth, bt.max_ops));
+    HIPCHK(c, hipMemcpyAsync(hA.data(), s->A.p, sizeof(double) * (size_t)sp.strideA * Pc, hipMemcpyDeviceToHost, sl.st));
+    HIPCHK(c, hipStreamSynchronize(sl.st));
+    for (int r = 0; r < Pc; ++r) {
+      double* K = out_K + (size_t)bt.order[(size_t)(p0 + r)] * npad * npad;
+      const double* A = hA.data() + (size_t)r * (size_t)sp.strideA;
+      for (int ti = 0; ti < sp.nt; ++ti)
+        for (int tj = 0; tj <= ti; ++tj) {
+          const double* T = A + tile_off(ti, tj);
+          for (int cc = 0; cc < NB; ++cc)
+            for (int rr = 0; rr < NB; ++rr) K[((size_t)ti * NB + rr) * npad + (size_t)tj * NB + cc] = T[cc * NB + rr];
+        }
+    }
+  }
+  if (out_tab && nT) HIPCHK(c, hipMemcpyAsync(out_tab, s->lagtab.p, sizeof(double) * nT, hipMemcpyDeviceToHost, sl.st));
+  if (out_rep && rep_len) {
+    const double* tt = sp.compact() ? c->d_clt_tt : sp.mode == TableMode::Rank ? c->d_ts_lat : c->d_ts_s;      // (LagArgs::tt of sweep_lag_tables)
+    HIPCHK(c, hipMemcpyAsync(out_rep, tt, sizeof(double) * (size_t)rep_len, hipMemcpyDeviceToHost, sl.st));
+  }
+  HIPCHK(c, hipStreamSynchronize(sl.st));
+  // row i of the sweep is the caller's point out_order[i]: the identity, or agp_set_data's stable sort by time
+  std::vector<int32_t> perm((size_t)n);
+  for (int64_t i = 0; i < n; ++i) perm[(size_t)i] = (int32_t)i;
+  if (sp.sorted()) std::stable_sort(perm.begin(), perm.end(), [&](int32_t a, int32_t b) { return c->h_ts[(size_t)a] < c->h_ts[(size_t)b]; });
+  std::copy(perm.begin(), perm.end(), out_order);
+  return AGP_OK;
+}
+
 // Core of agp_logpdf_batch{,_device} and agp_logpdf_grad_batch, of the coalesced single-particle entries and of the multi-device
 // shards.  d_user_* may be caller device buffers (user_stream path) or null (results copied to host h_out_*).  The body lists the
 // stages above top to bottom; it owns what must outlive them: the store's lock (StoreHits), the slot (SlotGuard) and the host
@@ -2026,6 +2138,15 @@ int agp_debug_toeplitz(agp_ctx* c, int32_t mode, int64_t n, int64_t nj, int32_t 
   return abi_guard(c, [&] {
     return debug_toeplitz_body(c, mode, n, nj, P, r, r2, leaves, const_v, wn_v, lin, noise, x, rank0, grid_h, grid_mid, t_ref,
                                raw_particle, raw_op, out_lp, out_info, out_Lcols, out_fwd, out_sol, out_pacc);
+  });
+}
+
+int agp_debug_cov_sweep(agp_ctx* c, int64_t n, int32_t P, const int32_t* op_off, const uint8_t* ops, const int32_t* prm_off,
+                        const double* prm, const double* noise, int32_t for_gradient, int32_t allow_tables, double* out_K,
+                        int32_t* out_order, int32_t* out_mode, double* out_tab, double* out_rep) {
+  return abi_guard(c, [&] {
+    return debug_cov_sweep_body(c, n, {P, op_off, ops, prm_off, prm, noise, nullptr}, for_gradient != 0, allow_tables != 0, out_K,
+                                out_order, out_mode, out_tab, out_rep);
   });
 }
 

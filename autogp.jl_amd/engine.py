@@ -40,7 +40,7 @@ EXPORTED_SYMBOLS = [
     "agp_debug_factor_batch", "agp_logpdf_series_batch", "agp_debug_series_factor", "agp_logpdf_grad_series_batch",
     "agp_predict_series_batch", "agp_debug_remove_factor", "agp_predict_quantile_series_batch",
     "agp_predict_logpdf_series_batch", "agp_predict_sample_series_batch", "agp_predict_sum_series_batch",
-    "agp_debug_toeplitz",
+    "agp_debug_toeplitz", "agp_debug_cov_sweep",
 ]
 COMM_ID_BYTES = 128
 SERIES_MAX_N = 176      # AGP_SERIES_MAX_N of include/autogp_hip.h: the longest series of logpdf_series_batch
@@ -190,6 +190,9 @@ def load_library(path=None):
     lib.agp_debug_toeplitz.argtypes = [vp, C.c_int32, C.c_int64, C.c_int64, C.c_int32, dp, dp, ip, dp, dp, dp, dp, dp, C.c_int32, C.c_double,
                                        C.c_double, C.c_double, C.c_int32, C.c_int32, dp, ip, dp, dp, dp, dp]
     lib.agp_debug_toeplitz.restype = C.c_int
+    if hasattr(lib, "agp_debug_cov_sweep"):          # (absent from an older library that an A/B tool drives through AUTOGP_HIP_LIB; build() checks EXPORTED_SYMBOLS)
+        lib.agp_debug_cov_sweep.argtypes = [vp, C.c_int64, C.c_int32, ip, u8p, ip, dp, dp, C.c_int32, C.c_int32, dp, ip, ip, dp, dp]
+        lib.agp_debug_cov_sweep.restype = C.c_int
     lib.agp_get_remove_stats.argtypes = [vp, C.POINTER(C.c_int64), C.c_int32]; lib.agp_get_remove_stats.restype = C.c_int
     lib.agp_set_remove_update.argtypes = [vp, C.c_int32]; lib.agp_set_remove_update.restype = C.c_int
     lib.agp_remove_data_multi.argtypes = [C.POINTER(vp), C.c_int32, C.POINTER(C.c_int64), C.c_int64]; lib.agp_remove_data_multi.restype = C.c_int
@@ -1335,6 +1338,40 @@ class GPEngine:
                                                  float(t_ref), int(rp), int(ro), _dp(out["lp"]), _ip(out["info"]), _dp(out.get("Lcols")),
                                                  _dp(out.get("fwd")), _dp(out.get("sol")), _dp(out.get("pacc"))))
         return out
+
+    COV_SWEEP_MODES = ("general", "sorted_lag", "rank", "compact_whole", "compact_sorted")
+    COV_SWEEP_DECODES = ("one_node", "chain", "stack")
+
+    def debug_cov_sweep(self, nodes, noises, n=None, for_gradient=False, allow_tables=True, want_tables=True, programs=None):
+        """The covariance tiles of a sweep over the first n resident points, on whichever table path that sweep takes
+        (agp_debug_cov_sweep: the sweep's own stages up to its covariance launch with every tile from the tile builder, tiles and
+        tables seeded with the sentinel -7, no factorisation).  -> dict(K (P, n_pad, n_pad) the padded lower tiles as they lie (-7
+        where no tile is stored), order (n) the caller's position of sweep row i, mode (one of COV_SWEEP_MODES), tab_units,
+        tab_gstride, n_tables, logdt (the GammaExponential leaves read the log|dt| table), depth (4 or 8), decode (P names of
+        COV_SWEEP_DECODES); with want_tables also tab (n_tables, entries per table) or None and rep (the entries' times) or None)."""
+        n = self.n_max if n is None else int(n)
+        op_off, ops, prm_off, prm = programs if programs is not None else _gp.encode_batch(nodes)
+        P = op_off.shape[0] - 1
+        noises = _f64(noises)
+        if noises.shape != (P,):
+            raise ValueError("one noise per particle required")
+        mode = np.zeros(8 + max(P, 0), dtype=np.int32)
+
+        def call(K, order, tab, rep):
+            self._check(self._lib.agp_debug_cov_sweep(self._ctx, n, P, _ip(op_off), _u8(ops), _ip(prm_off), _dp(prm), _dp(noises),
+                                                      1 if for_gradient else 0, 1 if allow_tables else 0, _dp(K), _ip(order), _ip(mode),
+                                                      _dp(tab), _dp(rep)))
+        tab = rep = None
+        if want_tables:
+            call(None, None, None, None)          # (the sizing call)
+            if mode[3] > 0 and mode[4] > 0:
+                tab = np.empty((int(mode[3]), int(mode[4]))); rep = np.empty(int(mode[5]))
+        npad = 128 * -(-n // 128)
+        K = np.empty((P, npad, npad)); order = np.empty(n, dtype=np.int32)
+        call(K, order, tab, rep)
+        return dict(K=K, order=order, mode=self.COV_SWEEP_MODES[int(mode[0])], tab_units=int(mode[1]), tab_gstride=int(mode[2]),
+                    n_tables=int(mode[3]), logdt=bool(mode[6]), depth=int(mode[7]),
+                    decode=[self.COV_SWEEP_DECODES[int(v)] for v in mode[8:8 + P]], tab=tab, rep=rep)
 
     def debug_mfma_probe(self, A, B):
         A = _f64(A).reshape(16, 4); B = _f64(B).reshape(4, 16); D = np.empty((16, 16))

@@ -1037,6 +1037,37 @@ int agp_debug_toeplitz(agp_ctx* ctx, int32_t mode, int64_t n, int64_t nj, int32_
                        int32_t raw_op, double* out_lp /* P */, int32_t* out_info /* P */, double* out_Lcols, double* out_fwd,
                        double* out_sol, double* out_pacc);
 
+/* The covariance tiles of a sweep over the first n >= 1 points of the RESIDENT series (agp_set_data first), entry by entry, on
+ * whichever table path that sweep takes.  P >= 1 programs and noises in agp_logpdf_batch's format (no deduplication).  The entry
+ * runs, unchanged and in their order, the stages a sweep runs up to its covariance launch — the table plan, the batch compilation
+ * with the sweep's options plus "never fuse" (every tile then comes from the tile builder, as under AGP_FUSE=0), the geometry, the
+ * slot's buffers, the staged upload, the lag tables — and launches the tile builder with the arguments a sweep's chunk builds.
+ * for_gradient != 0: the plan of a gradient sweep (a whole grid takes rank tables in the caller's order instead of the sorted copy);
+ * allow_tables = 0: the general evaluator whatever the series.  No factorisation runs (a matrix that is not positive definite is
+ * returned like any other); the factor store, the coalescer, the dedup and sweep counters and agp_get_*_stats are neither read nor
+ * changed; a workspace slot is borrowed.  Tiles and tables are filled with the sentinel -7 before the launches:
+ *   out_K      P x n_pad x n_pad row-major, n_pad = 128 ceil(n / 128): the padded LOWER tiles as they lie — both triangles of the
+ *              diagonal tiles, the padding rows and columns (identity: 1 on the diagonal, 0 elsewhere) — and -7 at every position
+ *              of a tile above the diagonal tiles, which no sweep stores.  NULL: a sizing call, only out_mode is written.
+ *   out_order  n: the position in the caller's series of row i of the sweep (the identity unless the plan runs on the sorted copy)
+ *   out_mode   8 + P words: [0] the table mode (0 general evaluator, 1 lag tables on the sorted copy, 2 rank tables, 3 compact tables
+ *              whole, 4 compact tables by tile window on the sorted copy), [1] LDS units of 256 doubles per table, [2] doubles per table
+ *              in global memory (rank / compact layouts), [3] the number T of lag tables of the batch, [4] doubles per table in
+ *              out_tab, [5] doubles in out_rep, [6] 1 when GammaExponential leaves read the log|dt| table, [7] the evaluation-stack
+ *              depth of the tile builder's instantiation (4 or 8), [8 + p] how particle p is decoded: 0 one node, 1 chain, 2 stack
+ *   out_tab    (nullable) T x out_mode[4]: the lag tables as the table kernel left them.  Rank and compact layouts: out_mode[2]
+ *              entries per table; sorted layout: ceil(n / 128) block lags x 256, entry d + 127 of block lag b at lag 128 b + d
+ *              (entry 255 is never read by a tile)
+ *   out_rep    (nullable) out_mode[5]: the "time" every table entry was evaluated at, relative to out_rep[0] — the array the table
+ *              kernel reads: the sorted series (sorted layout), the lattice times (rank), the compact entries' lag x spacing
+ * AGP_ERR_ARG: what agp_logpdf_batch refuses (null context, null program or noise pointers), n < 1, P < 1, more than 2^27 doubles of
+ * tiles, a null out_mode, a null out_order beside out_K; AGP_ERR_NODATA: n exceeds the resident series; AGP_ERR_PROGRAM as
+ * agp_logpdf_batch (with for_gradient: as agp_logpdf_grad_batch). */
+int agp_debug_cov_sweep(agp_ctx* ctx, int64_t n, int32_t P, const int32_t* op_off, const uint8_t* ops, const int32_t* prm_off,
+                        const double* prm, const double* noise, int32_t for_gradient, int32_t allow_tables,
+                        double* out_K /* P*n_pad*n_pad or NULL */, int32_t* out_order /* n */, int32_t* out_mode /* 8+P */,
+                        double* out_tab /* or NULL */, double* out_rep /* or NULL */);
+
 /* Probe of the fp64 MFMA fragment layout: D = A(16x4) * B(4x16), row-major host arrays. */
 int agp_debug_mfma_probe(agp_ctx* ctx, const double* A, const double* B, double* D);
 

@@ -113,7 +113,8 @@ def test_calendar_fixture_kernels(pkg, freq, n, kind):
         assert lp_err(la, lb).max() <= 1e-10
         ref, rinfo = F.gp_logpdf_many(pkg.encode_batch(ks), nz, ts, xs)
         assert (rinfo == 0).all() and lp_err(la, ref).max() <= LP_TOL
-        # the matrix itself (agp_cov_matrix takes the general evaluator; the sweep's tiles are checked through the logpdf above)
+        # the matrix itself (agp_cov_matrix takes the general evaluator; the sweep's own tiles and tables are checked entry by entry
+        # through agp_debug_cov_sweep in tests/test_gpu_cov_probe.py)
         K = a.cov_matrix(ks[-2], 0.07, ts) if hasattr(a, "cov_matrix") else None
         if K is not None:
             Ko = O.compute_cov_matrix_vectorized(ks[-2].to_tuple(), 0.07, ts)
