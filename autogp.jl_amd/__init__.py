@@ -11,7 +11,8 @@ from .engine import (GPEngine, GPEngineMulti, shard_range, shard_plan, probe_lat
                      predict_quantile, predict_quantile_multi, raw_components, predict_mvn_sum, predict_sum, predict_rand,
                      MixtureModel, predict_mvn, pack_series, series_call_args, pack_queries, SERIES_MAX_N,
                      pack_series_mixture, predict_quantile_series, SeriesBand, pack_heldout, predict_proba_series, SeriesScores,
-                     predict_rand_series, predict_mvn_series, SeriesSamples, SeriesMixtureModel, predict_sum_series, SeriesSums)
+                     predict_rand_series, predict_mvn_series, SeriesSamples, SeriesMixtureModel, predict_sum_series, SeriesSums,
+                     mcmc_parameters_series, with_params)
 from . import prior, schedule, dist, stream
 
 __all__ = [n for n in dir() if not n.startswith("_")]

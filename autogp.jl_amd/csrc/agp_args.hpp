@@ -379,6 +379,69 @@ __host__ __device__ inline SeriesGradLds series_grad_lds(int n, int n_ops, int n
   return m;
 }
 
+// HMC twin (k_series_hmc, agp_hmc_series_batch): the gradient kernel's arguments — its programs are compiled from the INITIAL state
+// and give the structure only; the device derives every parameter value from the latent state before each evaluation — the latent
+// state, the transform classes, the move schedule and the chain outputs.  Per-parameter arrays have the caller's layout (out_off).
+struct SeriesHmcParams {
+  const double* z;           // [prm_off[P]] latent coordinates (a FIXED slot: the parameter value itself)
+  const double* z_noise;     // [P]
+  const int32_t* cls;        // [prm_off[P]] transform class of every caller parameter, < 0: FIXED
+  const uint8_t* rule;       // per gradient-program parameter slot (gprm's layout): how the VALUE program's slot follows from the
+                             // caller parameter gmap names — HMC_RULE_* (the value and the gradient program number their slots alike)
+  const double* tf;          // [C][3] (mu, sigma, scale); scale == 0: log-normal, > 0: logit-normal
+  int C, noise_class;
+  double noise_jitter;
+  int n_hmc, L_prm, L_noise, n_exit, flags;      // flags: HMC_FLAG_*
+  double eps_prm, eps_noise;
+  const unsigned long long* seeds;               // [P] Philox key (seeds[p], 0)
+  double* out_z;             // [prm_off[P]]
+  double* out_z_noise;       // [P]
+  double* out_prm;           // [prm_off[P]] transformed parameters of the final state
+  double* out_noise;         // [P]
+  int32_t* out_counts;       // [P][4] parameter moves accepted, tried, noise moves accepted, trajectories rejected as not positive definite
+  double* out_trace;         // [P][n_hmc][2][2] (alpha, log u) of every move, NaN where none was made; or null
+};
+// (the chain's own arguments sit in device memory behind one pointer: the evaluation's statements keep the gradient kernel's
+// argument block and its scalar registers; the chain reads a field where it needs it)
+struct SeriesHmcArgs : SeriesGradArgs {
+  const SeriesHmcParams* hm;
+  int C;                     // == hm->C (the LDS map needs it)
+};
+constexpr int HMC_RULE_COPY = 0, HMC_RULE_INV_SQ = 1, HMC_RULE_INV = 2, HMC_RULE_M2_INV_SQ = 3, HMC_RULE_PI_OVER = 4;
+constexpr int HMC_FLAG_FULL_NOISE_GRAD = 1;      // measurement: noise moves run the whole gradient pass (no tr K^-1 = |Z|_F^2 shortcut)
+constexpr unsigned long long HMC_PHILOX_TAG = 0x484D43ull;      // counter word c3 of every draw ("HMC")
+// compiled value of a value-program slot from the caller parameter v — the operations of emit (agp_engine.hip), IEEE division
+__host__ __device__ inline double hmc_rule_apply(int rule, double v) {
+  switch (rule) {
+    case HMC_RULE_INV_SQ: return 1.0 / (v * v);
+    case HMC_RULE_INV: return 1.0 / v;
+    case HMC_RULE_M2_INV_SQ: return -2.0 / (v * v);
+    case HMC_RULE_PI_OVER: return 3.14159265358979323846 / v;
+    default: return v;
+  }
+}
+// LDS map of the HMC kernel: the gradient kernel's, and in front of the blocks six doubles per caller parameter (npc of them, =
+// g_n_prm: gmap is a permutation) and the chain's scalars —
+//   theta[npc] (the caller-order vector) | z[npc] | zs[npc] (saved) | mom[npc] | grd[npc] (gradient in caller order) |
+//   cls[npc ints] smap[npc ints] (gmap | rule << 16) | tf[3 C] (even) | st[HMC_ST_N] | blocks
+// At 176 points a chain of 4 ChangePoint nodes (9 nodes, 13 parameters, 8 tables) still fits, as in the gradient kernel; 5 do not.
+constexpr int HMC_ST_N = 32;
+struct SeriesHmcLds : SeriesGradLds {
+  int o_th, o_z, o_zs, o_mom, o_grd, o_cls, o_tf, o_st;
+};
+__host__ __device__ inline SeriesHmcLds series_hmc_lds(int n, int n_ops, int n_prm, int n_cp, int g_n_ops, int g_n_prm, int C) {
+  SeriesHmcLds m;
+  static_cast<SeriesGradLds&>(m) = series_grad_lds(n, n_ops, n_prm, n_cp, g_n_ops, g_n_prm);
+  const int npc = (g_n_prm + 1) & ~1;
+  m.o_th = m.o_blk; m.o_z = m.o_th + npc; m.o_zs = m.o_z + npc; m.o_mom = m.o_zs + npc; m.o_grd = m.o_mom + npc;
+  m.o_cls = m.o_grd + npc;
+  m.o_tf = m.o_cls + npc;
+  m.o_st = m.o_tf + ((3 * C + 1) & ~1);
+  m.o_blk = m.o_st + HMC_ST_N;
+  m.total = m.o_blk + (m.nb * (m.nb + 1) / 2) * 256;
+  return m;
+}
+
 // Predictive twin (k_series_predict, agp_predict_series_batch): the value kernel's arguments, every series' own query times and
 // the particle-major outputs.
 struct SeriesPredArgs : SeriesArgs {

@@ -175,18 +175,20 @@ struct Slot {
       alpha{Fill::values}, tsol{Fill::values}, gpart{Fill::values}, dgrad{Fill::values}, dgnoise{Fill::values}, lagtab{Fill::values},
       sum_x{Fill::values}, sum_z{Fill::values}, smp_z{Fill::values}, smp_x{Fill::values}, smp_zin{Fill::values},
       mix_w{Fill::values}, mix_e{Fill::values}, mix_s{Fill::values}, mix_acc{Fill::values}, mix_out{Fill::values},
+      hmc_out{Fill::values},                  // agp_hmc_series_batch: [out_z | out_prm | out_z_noise | out_noise | trace | counts]
       sq_cm{Fill::values}, sq_cs{Fill::values}, sq_w{Fill::values}, sq_out{Fill::values};      // agp_predict_quantile_series_batch: packed rows, [w | slope | intercept | ivar | q], [x | mean | var]
   // addresses, indices, counts, programs (their parameters included: uploaded whole), times, flags
   DevBuf info{Fill::never}, out_info{Fill::never}, hdr{Fill::never}, ops{Fill::never}, prm{Fill::never}, tt{Fill::never}, map{Fill::never},
       ready{Fill::never}, code{Fill::never}, tretry{Fill::never}, ghdr{Fill::never}, gops{Fill::never}, glc{Fill::never},
       grc{Fill::never}, gpoff{Fill::never}, gprm{Fill::never}, gmap{Fill::never}, goff{Fill::never}, plist{Fill::never},
       tflag{Fill::never}, flowq{Fill::never}, pl_rank{Fill::never}, pl_tl{Fill::never}, pl_prog{Fill::never}, smp_idx{Fill::never},
+      hmc_in{Fill::never},                    // agp_hmc_series_batch: [z | z_noise | tf | seeds | SeriesHmcParams | prm_class | rule], uploaded whole
       sq_tab{Fill::never}, sq_flag{Fill::never};      // ... its index tables [pl_off | w_off | row_off | plist], and [converged | iterations | first_bad | bad]
   template <class F> void for_each_dev(F&& f) {
     for (DevBuf* b : {&stage, &up_blob, &up_blob2, &A, &W, &vec, &partial, &out_lp, &out_info, &noise, &noise_pred, &mu1, &mu2,
                       &pred_mean, &pred_var, &pred_cov, &dense, &diag_add, &Z, &alpha, &tsol, &gpart, &dgrad, &dgnoise, &lagtab, &sum_x, &sum_z,
                       &smp_z, &smp_x, &smp_zin, &mix_w, &mix_e, &mix_s, &mix_acc, &mix_out, &sq_cm, &sq_cs, &sq_w, &sq_out, &sq_tab, &sq_flag, &smp_idx, &info, &hdr, &ops, &prm, &tt, &map, &ready, &code, &tretry, &ghdr, &gops, &glc, &grc, &gpoff, &gprm, &gmap,
-                      &goff, &plist, &tflag, &flowq, &pl_rank, &pl_tl, &pl_prog})
+                      &goff, &plist, &tflag, &flowq, &pl_rank, &pl_tl, &pl_prog, &hmc_in, &hmc_out})
       f(*b);
   }
   void attach(PoisonCtl* z) {

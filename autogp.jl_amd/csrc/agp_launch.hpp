@@ -86,6 +86,9 @@ hipError_t launch_series_logpdf(hipStream_t st, const SeriesArgs& sa, int grid, 
 // value-and-gradient twin: tape = nodes of the reverse-mode tape (16 / 64); the evaluation-stack depth is the value kernel's for the same
 // program (a tree of <= 16 nodes never needs more than 4), lds_bytes = the largest SeriesGradLds total of the launch's particles
 hipError_t launch_series_logpdf_grad(hipStream_t st, const SeriesGradArgs& sa, int grid, int depth, int tape, size_t lds_bytes);
+hipError_t kernels_init_series_hmc();   // ... and of k_series_hmc (agp_kernels_series_hmc.hip)
+// HMC twin (k_series_hmc): the same rule; lds_bytes = the largest series_hmc_lds total of the launch's particles
+hipError_t launch_series_hmc(hipStream_t st, const SeriesHmcArgs& sa, int grid, int depth, int tape, size_t lds_bytes);
 // predictive twin (k_series_predict): depth as for the value kernel, lds_bytes = the largest series_pred_lds total of the launch's particles
 hipError_t launch_series_predict(hipStream_t st, const SeriesPredArgs& sa, int grid, int depth, size_t lds_bytes);
 // decomposition twin (k_series_predict_sum): as the predictive twin, on composite programs (their selector tables counted in lds_bytes)

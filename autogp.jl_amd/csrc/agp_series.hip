@@ -2,6 +2,8 @@
 // (agp_series_kernel.hpp: one workgroup per particle, covariance + Cholesky + forward solve + value in LDS).
 //   agp_logpdf_series_batch            k_series_logpdf: the values
 //   agp_logpdf_grad_series_batch       k_series_logpdf_grad: L^-T, alpha and the contraction with dK / d theta behind the value
+//   agp_hmc_series_batch               k_series_hmc: the gradient kernel's statements in a loop — HMC moves of every particle's parameters
+//                                      and noise in the reference's latent space, the whole chain of a particle in one workgroup
 //   agp_predict_series_batch           k_series_predict: posterior mean and marginal variance at every series' own query times
 //   agp_predict_quantile_series_batch  the predictive launches, their device outputs read out by agp_series_quantile_kernel.hpp on
 //                                      the same stream: quantiles and marginal moments of every series' own mixture
@@ -128,13 +130,14 @@ void quant_fill_nan(const SeriesQuantOut& qo, size_t from, size_t to, int64_t nq
 #define STAGE(expr) do { if (const int rc_ = (expr)) return rc_; } while (0)
 
 // Which kernel the call launches: it chooses the LDS map, the instantiation rule and (gradient) the tape's limit.
-enum class SeriesMode { value, gradient, prediction, held_out, sum };
+enum class SeriesMode { value, gradient, prediction, held_out, sum, hmc };
 
 // One call of a many-series entry: the caller's inputs and what each shared stage leaves for the later ones.
 struct SeriesCall {
   // inputs (q_off / ts_pred: null in the entries without queries)
   int32_t S; const int64_t* pt_off; const double* ts; const double* xs; Particles pp; const int32_t* series;
   const int64_t* q_off; const double* ts_pred;
+  int hmc_C = 0;                     // HMC entry: transform classes (the LDS map holds their table)
   // series_classes
   Batch bt;                          // programs without any table of the resident series (no log|dt| table, no lag tables), caller's order
   std::vector<int> len;              // [P] points of the particle's series
@@ -214,9 +217,10 @@ int series_check_layout(agp_ctx* c, const SeriesCall& sc) {
 
 // LDS bytes of particle p on a series of n points (held_out — the held-out and the sampling entry —: the joint n_s + m_s points, the
 // value kernel's map): the mode's own map
-size_t series_need(SeriesMode mode, const Batch& bt, int p, int n) {
+size_t series_need(SeriesMode mode, const Batch& bt, int p, int n, int hmc_C = 0) {
   const ProgHdr& h = bt.hdr[(size_t)p];
-  const int m_total = mode == SeriesMode::gradient ? series_grad_lds(n, h.n_ops, h.n_prm, h.n_cp, bt.ghdr[(size_t)p].n_ops, bt.ghdr[(size_t)p].n_prm).total
+  const int m_total = mode == SeriesMode::hmc ? series_hmc_lds(n, h.n_ops, h.n_prm, h.n_cp, bt.ghdr[(size_t)p].n_ops, bt.ghdr[(size_t)p].n_prm, hmc_C).total
+                      : mode == SeriesMode::gradient ? series_grad_lds(n, h.n_ops, h.n_prm, h.n_cp, bt.ghdr[(size_t)p].n_ops, bt.ghdr[(size_t)p].n_prm).total
                       : mode == SeriesMode::prediction || mode == SeriesMode::sum ? series_pred_lds(n, h.n_ops, h.n_prm, h.n_cp).total
                                                        : series_lds(n, h.n_ops, h.n_prm, h.n_cp).total;
   return sizeof(double) * (size_t)m_total;
@@ -241,10 +245,11 @@ int series_classes(agp_ctx* c, SeriesCall& sc, SeriesMode mode) {
   char buf[256];
   Batch& bt = sc.bt;
   CompileOpts co;
-  co.ge_tab = false; co.lag = false; co.never_fuse = true; co.want_grad = mode == SeriesMode::gradient;
+  co.ge_tab = false; co.lag = false; co.never_fuse = true; co.want_grad = mode == SeriesMode::gradient || mode == SeriesMode::hmc;
   co.allow_sel = mode == SeriesMode::sum;      // (the composite programs' selector leaves: one per-point table each, counted in n_cp)
   STAGE(compile_batch(c, sc.pp, bt, co));
-  if (mode == SeriesMode::gradient)
+  const bool grad_mode = mode == SeriesMode::gradient || mode == SeriesMode::hmc;      // (the HMC kernel is the gradient kernel in a loop)
+  if (grad_mode)
     for (int p = 0; p < P; ++p)
       if (bt.ghdr[(size_t)p].n_ops > 64) {      // (RegTape<64> is the largest tape: agp_logpdf_grad_batch's own limit)
         snprintf(buf, sizeof buf, "particle %d: gradient supports kernel trees of up to 64 nodes (%d)", p, (int)bt.ghdr[(size_t)p].n_ops);
@@ -264,7 +269,7 @@ int series_classes(agp_ctx* c, SeriesCall& sc, SeriesMode mode) {
     // n_s + m_s; nothing held out scores 0 without a launch, as an empty series does in the value entry
     if (mode == SeriesMode::held_out) sc.len[(size_t)p] = n = sc.nq[(size_t)p] > 0 ? n + (int)sc.nq[(size_t)p] : 0;
     if (n == 0 && sc.nq[(size_t)p] == 0) continue;      // (an empty series is launched for its prior predictive only)
-    const size_t need = sc.need[(size_t)p] = series_need(mode, bt, p, n);
+    const size_t need = sc.need[(size_t)p] = series_need(mode, bt, p, n, sc.hmc_C);
     if (need > (size_t)SERIES_LDS_BYTES) {
       snprintf(buf, sizeof buf, "particle %d: %d per-point tables (%s) at %d points need %zu bytes of LDS, more than the "
                "kernel's %d", p, (int)h.n_cp, mode == SeriesMode::sum ? "ChangePoint nodes and component selectors" : "ChangePoint nodes", n,
@@ -272,7 +277,7 @@ int series_classes(agp_ctx* c, SeriesCall& sc, SeriesMode mode) {
       return fail(c, AGP_ERR_PROGRAM, buf);
     }
     const int depth = series_stack_depth(bt, h);
-    const int inst = mode != SeriesMode::gradient ? (depth <= 4 ? 0 : 1) : bt.ghdr[(size_t)p].n_ops <= 16 && depth <= 4 ? 0 : depth <= 4 ? 1 : 2;
+    const int inst = !grad_mode ? (depth <= 4 ? 0 : 1) : bt.ghdr[(size_t)p].n_ops <= 16 && depth <= 4 ? 0 : depth <= 4 ? 1 : 2;
     sc.list[inst][lds_class(need)].push_back(p);
   }
   for (auto& ld : sc.list)
@@ -508,6 +513,176 @@ int logpdf_grad_series(agp_ctx* c, SeriesCall& sc, double* out_logpdf, double* o
     const bool empty = sc.len[(size_t)p] == 0;
     out_gnoise[p] = empty ? 0.0 : hgn[p];
     for (int32_t q = sc.pp.prm_off[p]; q < sc.pp.prm_off[p + 1]; ++q) out_grad[q] = empty ? 0.0 : hgr[q];
+  }
+  return series_timing(c, sc);
+}
+
+// The chain of agp_hmc_series_batch: the latent state, the transform classes, the schedule and the outputs (host).
+struct SeriesHmcCall {
+  const double* z; const double* z_noise; const int32_t* prm_class; int32_t C; const double* tf; int32_t noise_class; double noise_jitter;
+  int32_t n_hmc, L_prm; double eps_prm; int32_t L_noise; double eps_noise; int32_t n_exit; const uint64_t* seeds; int32_t flags;
+  double* out_z; double* out_z_noise; double* out_prm; double* out_noise; int32_t* out_counts; double* out_trace;
+};
+
+// theta = transform(z) on the host (the programs are compiled from the initial state; the device forms every value it uses itself)
+double hmc_transform_host(const double* tf, int c, double z) {
+  const double x = tf[3 * c] + tf[3 * c + 1] * z, sc = tf[3 * c + 2];
+  return sc == 0.0 ? std::exp(x) : sc / (1.0 + std::exp(-x));
+}
+
+// rejuvenate_particle_parameters for every (series, particle) in one call: k_series_hmc, the gradient kernel's statements in a loop.
+// sc.pp carries the programs; its prm / noise are filled here from the initial state.
+int hmc_series(agp_ctx* c, SeriesCall& sc, const SeriesHmcCall& hm, double* out_logpdf, int32_t* out_info) {
+  const int P = sc.pp.P;
+  char buf[256];
+  STAGE(series_check_sizes(c, sc));
+  if (P == 0) return AGP_OK;
+  if (!(sc.pt_off && sc.ts && sc.xs && sc.series && sc.pp.op_off && sc.pp.ops && sc.pp.prm_off)) return fail(c, AGP_ERR_ARG, "null pointer argument");
+  if (!(out_logpdf && out_info && hm.out_z_noise && hm.out_noise && hm.out_counts)) return fail(c, AGP_ERR_ARG, "null pointer argument (outputs)");
+  if (!(hm.z_noise && hm.tf && hm.seeds)) return fail(c, AGP_ERR_ARG, "null pointer argument (z_noise, tf or seeds)");
+  const size_t NT = (size_t)std::max(0, sc.pp.prm_off[P]);
+  if (NT > 0 && !(hm.z && hm.prm_class)) return fail(c, AGP_ERR_ARG, "null pointer argument (z or prm_class with parameters present)");
+  if (NT > 0 && !(hm.out_z && hm.out_prm)) return fail(c, AGP_ERR_ARG, "null pointer argument (out_z or out_prm with parameters present)");
+  if (hm.n_hmc < 0 || hm.L_prm < 0 || hm.L_noise < 0 || !(hm.eps_prm >= 0.0) || !(hm.eps_noise >= 0.0))
+    return fail(c, AGP_ERR_ARG, "n_hmc, L_param, L_noise, eps_param and eps_noise must not be negative");
+  if (hm.n_hmc > (1 << 20) || hm.L_prm > (1 << 20) || hm.L_noise > (1 << 20)) return fail(c, AGP_ERR_ARG, "n_hmc, L_param and L_noise are limited to 2^20");
+  if (hm.C < 1 || hm.C > 4096) return fail(c, AGP_ERR_ARG, "the transform table needs between 1 and 4096 classes");
+  for (int k = 0; k < hm.C; ++k)
+    if (!(hm.tf[3 * k + 1] > 0.0) || !(hm.tf[3 * k + 2] >= 0.0) || !std::isfinite(hm.tf[3 * k]) || !std::isfinite(hm.tf[3 * k + 1]) || !std::isfinite(hm.tf[3 * k + 2])) {
+      snprintf(buf, sizeof buf, "transform class %d: (mu, sigma, scale) must be finite with sigma > 0 and scale >= 0", k);
+      return fail(c, AGP_ERR_ARG, buf);
+    }
+  if (hm.noise_class < 0 || hm.noise_class >= hm.C) {
+    snprintf(buf, sizeof buf, "noise class %d outside [0, %d)", (int)hm.noise_class, (int)hm.C);
+    return fail(c, AGP_ERR_ARG, buf);
+  }
+  STAGE(series_check_layout(c, sc));
+  for (int p = 0; p < P; ++p)
+    for (int32_t q = sc.pp.prm_off[p]; q < sc.pp.prm_off[p + 1]; ++q)
+      if (hm.prm_class[q] >= hm.C) {
+        snprintf(buf, sizeof buf, "particle %d: parameter %d has transform class %d, outside the table's %d", p, (int)(q - sc.pp.prm_off[p]),
+                 (int)hm.prm_class[q], (int)hm.C);
+        return fail(c, AGP_ERR_ARG, buf);
+      }
+  // the initial state in parameter space: what the programs are compiled from, and what a particle that is never launched returns
+  std::vector<double> th0(std::max<size_t>(1, NT)), nz0((size_t)P);
+  for (size_t q = 0; q < NT; ++q) th0[q] = hm.prm_class[q] < 0 ? hm.z[q] : hmc_transform_host(hm.tf, hm.prm_class[q], hm.z[q]);
+  for (int p = 0; p < P; ++p) nz0[(size_t)p] = hmc_transform_host(hm.tf, hm.noise_class, hm.z_noise[p]) + hm.noise_jitter;
+  sc.pp.prm = th0.data(); sc.pp.noise = nz0.data();
+  sc.hmc_C = hm.C;
+  STAGE(series_classes(c, sc, SeriesMode::hmc));
+  const Batch& bt = sc.bt;
+  // the slot map: the value and the gradient program number their parameter slots alike (emit / emit_grad walk the tree in one
+  // order), gmap names the caller parameter of a slot and the node's kind the derivation rule — checked against the compiled values
+  std::vector<uint8_t> rule(bt.gprm.size(), (uint8_t)HMC_RULE_COPY);
+  for (int p = 0; p < P; ++p) {
+    const ProgHdr& h = bt.hdr[(size_t)p];
+    const GProgHdr& g = bt.ghdr[(size_t)p];
+    bool ok = h.n_prm == g.n_prm && g.n_prm == sc.pp.prm_off[p + 1] - sc.pp.prm_off[p];
+    for (int i = 0; ok && i < g.n_ops; ++i) {
+      const int o = bt.gops[(size_t)g.node_off + i];
+      const size_t po = (size_t)g.prm_off + bt.gpoff[(size_t)g.node_off + i];
+      if (o == OP_SE) rule[po] = HMC_RULE_INV_SQ;
+      else if (o == OP_GE) rule[po] = HMC_RULE_INV;
+      else if (o == OP_PER) { rule[po] = HMC_RULE_M2_INV_SQ; rule[po + 1] = HMC_RULE_PI_OVER; }
+    }
+    for (int q = 0; ok && q < g.n_prm; ++q) {
+      const double want = bt.prm[(size_t)h.prm_off + q], got = hmc_rule_apply(rule[(size_t)g.prm_off + q], bt.gprm[(size_t)g.prm_off + q]);
+      ok = std::memcmp(&want, &got, sizeof want) == 0 || (want != want && got != got);
+    }
+    if (!ok) return fail(c, AGP_ERR_HOST, "internal error: the value and the gradient program disagree on their parameter slots");
+  }
+  // what a particle on an empty series returns (never launched): the transformed inputs, value 0, no move
+  const size_t tr_n = hm.out_trace ? (size_t)4 * hm.n_hmc : 0;
+  auto unmoved = [&](int p) {
+    for (int32_t q = sc.pp.prm_off[p]; q < sc.pp.prm_off[p + 1]; ++q) { hm.out_z[q] = hm.z[q]; hm.out_prm[q] = th0[(size_t)q]; }
+    hm.out_z_noise[p] = hm.z_noise[p]; hm.out_noise[p] = nz0[(size_t)p];
+    std::fill(hm.out_counts + 4 * (size_t)p, hm.out_counts + 4 * (size_t)p + 4, 0);
+    if (tr_n) std::fill(hm.out_trace + tr_n * p, hm.out_trace + tr_n * (p + 1), std::numeric_limits<double>::quiet_NaN());
+    out_logpdf[p] = 0.0; out_info[p] = 0;
+  };
+  if (sc.wg.empty()) {
+    for (int p = 0; p < P; ++p) unmoved(p);
+    return AGP_OK;
+  }
+  STAGE(series_stage(c, sc));
+  Slot* s = sc.s;
+  HIPCHK(c, s->ghdr.ensure(sizeof(GProgHdr) * (size_t)P));
+  HIPCHK(c, s->gops.ensure(bt.gops.size() + 4));
+  HIPCHK(c, s->glc.ensure(bt.glc.size() + 4));
+  HIPCHK(c, s->grc.ensure(bt.grc.size() + 4));
+  HIPCHK(c, s->gpoff.ensure(sizeof(int32_t) * (bt.gpoff.size() + 1)));
+  HIPCHK(c, s->gprm.ensure(sizeof(double) * bt.gprm.size()));
+  HIPCHK(c, s->gmap.ensure(sizeof(int32_t) * (bt.gmap.size() + 1)));
+  HIPCHK(c, s->goff.ensure(sizeof(int32_t) * (size_t)P));
+  // hmc_in  = [z (NT) | z_noise (P) | tf (3 C) | seeds (P) | params | prm_class (NT ints) | rule (bytes)]
+  // hmc_out = [out_z (NT) | out_prm (NT) | out_z_noise (P) | out_noise (P) | trace (P tr_n) | counts (4 P ints)]
+  const size_t D = sizeof(double);
+  const size_t i_zn = D * NT, i_tf = i_zn + D * P, i_seed = i_tf + D * 3 * hm.C, i_par = i_seed + D * P;
+  const size_t i_cls = i_par + ((sizeof(SeriesHmcParams) + 7) & ~(size_t)7), i_rule = i_cls + sizeof(int32_t) * NT;
+  const size_t o_prm = D * NT, o_zn = 2 * D * NT, o_nz = o_zn + D * P, o_tr = o_nz + D * P, o_cnt = o_tr + D * tr_n * P;
+  const size_t out_bytes = o_cnt + sizeof(int32_t) * 4 * P;
+  HIPCHK(c, s->hmc_in.ensure(i_rule + rule.size() + 8));
+  HIPCHK(c, s->hmc_out.ensure(out_bytes));
+  char* di = s->hmc_in.as<char>();
+  char* dout = s->hmc_out.as<char>();
+  SeriesHmcParams par = {};
+  par.z = reinterpret_cast<const double*>(di); par.z_noise = reinterpret_cast<const double*>(di + i_zn);
+  par.tf = reinterpret_cast<const double*>(di + i_tf); par.seeds = reinterpret_cast<const unsigned long long*>(di + i_seed);
+  par.cls = reinterpret_cast<const int32_t*>(di + i_cls); par.rule = reinterpret_cast<const uint8_t*>(di + i_rule);
+  par.C = hm.C; par.noise_class = hm.noise_class; par.noise_jitter = hm.noise_jitter;
+  par.n_hmc = hm.n_hmc; par.L_prm = hm.L_prm; par.L_noise = hm.L_noise; par.n_exit = hm.n_exit; par.flags = hm.flags;
+  par.eps_prm = hm.eps_prm; par.eps_noise = hm.eps_noise;
+  par.out_z = reinterpret_cast<double*>(dout); par.out_prm = reinterpret_cast<double*>(dout + o_prm);
+  par.out_z_noise = reinterpret_cast<double*>(dout + o_zn); par.out_noise = reinterpret_cast<double*>(dout + o_nz);
+  par.out_trace = tr_n ? reinterpret_cast<double*>(dout + o_tr) : nullptr;
+  par.out_counts = reinterpret_cast<int32_t*>(dout + o_cnt);
+  sc.up.add(s->ghdr.p, bt.ghdr.data(), sizeof(GProgHdr) * (size_t)P);
+  sc.up.add(s->gops.p, bt.gops.data(), bt.gops.size());
+  sc.up.add(s->glc.p, bt.glc.data(), bt.glc.size());
+  sc.up.add(s->grc.p, bt.grc.data(), bt.grc.size());
+  sc.up.add(s->gpoff.p, bt.gpoff.data(), sizeof(int32_t) * bt.gpoff.size());
+  sc.up.add(s->gprm.p, bt.gprm.data(), sizeof(double) * bt.gprm.size());
+  sc.up.add(s->gmap.p, bt.gmap.data(), sizeof(int32_t) * bt.gmap.size());
+  sc.up.add(s->goff.p, sc.pp.prm_off, sizeof(int32_t) * (size_t)P);
+  sc.up.add(di, hm.z, D * NT);
+  sc.up.add(di + i_zn, hm.z_noise, D * P);
+  sc.up.add(di + i_tf, hm.tf, D * 3 * hm.C);
+  sc.up.add(di + i_seed, hm.seeds, D * P);
+  sc.up.add(di + i_par, &par, sizeof par);
+  sc.up.add(di + i_cls, hm.prm_class, sizeof(int32_t) * NT);
+  sc.up.add(di + i_rule, rule.data(), rule.size());
+  HIPCHK(c, sc.up.flush(s->h_stage, s->up_blob, sc.st));
+  SeriesHmcArgs ha = {};
+  static_cast<SeriesArgs&>(ha) = sc.sa;
+  ha.ghdr = s->ghdr.as<GProgHdr>(); ha.gops = s->gops.as<uint8_t>(); ha.glc = s->glc.as<uint8_t>(); ha.grc = s->grc.as<uint8_t>();
+  ha.gpoff = s->gpoff.as<int32_t>(); ha.gprm = s->gprm.as<double>(); ha.gmap = s->gmap.as<int32_t>();
+  ha.out_off = s->goff.as<int32_t>(); ha.out_grad = nullptr; ha.out_gnoise = nullptr;
+  ha.hm = reinterpret_cast<const SeriesHmcParams*>(di + i_par); ha.C = hm.C;
+  STAGE(series_launch(c, sc, [&](const int32_t* wg, int grid, int d, size_t lds) {
+    ha.wg = wg;
+    return launch_series_hmc(sc.st, ha, grid, d == 2 ? 8 : 4, d == 0 ? 16 : 64, lds);
+  }));
+  // h_out = [logpdf | info | hmc_out]
+  const size_t o_own = sc.o_own();
+  STAGE(series_fetch_values(c, sc, o_own + out_bytes));
+  char* ho = static_cast<char*>(s->h_out.p);
+  HIPCHK(c, hipMemcpyAsync(ho + o_own, dout, out_bytes, hipMemcpyDeviceToHost, sc.st));
+  HIPCHK(c, hipStreamSynchronize(sc.st));
+  series_copy_values(sc, out_logpdf, out_info);
+  const char* hb = ho + o_own;
+  const double* hz = reinterpret_cast<const double*>(hb);
+  const double* hp = reinterpret_cast<const double*>(hb + o_prm);
+  const double* hzn = reinterpret_cast<const double*>(hb + o_zn);
+  const double* hnz = reinterpret_cast<const double*>(hb + o_nz);
+  const double* htr = reinterpret_cast<const double*>(hb + o_tr);
+  const int32_t* hcn = reinterpret_cast<const int32_t*>(hb + o_cnt);
+  for (int p = 0; p < P; ++p) {
+    if (sc.len[(size_t)p] == 0) { unmoved(p); continue; }
+    for (int32_t q = sc.pp.prm_off[p]; q < sc.pp.prm_off[p + 1]; ++q) { hm.out_z[q] = hz[q]; hm.out_prm[q] = hp[q]; }
+    hm.out_z_noise[p] = hzn[p]; hm.out_noise[p] = hnz[p];
+    std::copy(hcn + 4 * (size_t)p, hcn + 4 * (size_t)p + 4, hm.out_counts + 4 * (size_t)p);
+    if (tr_n) std::copy(htr + tr_n * p, htr + tr_n * (p + 1), hm.out_trace + tr_n * p);
   }
   return series_timing(c, sc);
 }
@@ -1165,6 +1340,20 @@ int agp_predict_sum_series_batch(agp_ctx* c, int32_t S, const int64_t* pt_off, c
     SeriesCall sc{S, pt_off, ts, xs, {P, op_off, ops, prm_off, prm, noise, noise_pred}, series, q_off, ts_pred};
     const SeriesSumOut so{M, y_slope, y_intercept, q, nq, out_mean, out_var, out_x, out_off};
     return predict_sum_series(c, sc, so, out_logpdf, out_info);
+  });
+}
+
+int agp_hmc_series_batch(agp_ctx* c, int32_t S, const int64_t* pt_off, const double* ts, const double* xs, int32_t P, const int32_t* series,
+                         const int32_t* op_off, const uint8_t* ops, const int32_t* prm_off, const double* z, const double* z_noise,
+                         const int32_t* prm_class, int32_t C, const double* tf, int32_t noise_class, double noise_jitter, int32_t n_hmc,
+                         int32_t L_param, double eps_param, int32_t L_noise, double eps_noise, int32_t n_exit, const uint64_t* seeds,
+                         int32_t flags, double* out_z, double* out_z_noise, double* out_prm, double* out_noise, double* out_logpdf,
+                         int32_t* out_counts, int32_t* out_info, double* out_trace) {
+  return abi_guard(c, [&] {
+    SeriesCall sc{S, pt_off, ts, xs, {P, op_off, ops, prm_off, nullptr, nullptr, nullptr}, series, nullptr, nullptr};
+    const SeriesHmcCall hm{z, z_noise, prm_class, C, tf, noise_class, noise_jitter, n_hmc, L_param, eps_param, L_noise, eps_noise, n_exit,
+                           seeds, flags, out_z, out_z_noise, out_prm, out_noise, out_counts, out_trace};
+    return hmc_series(c, sc, hm, out_logpdf, out_info);
   });
 }
 

@@ -494,8 +494,292 @@ __device__ __forceinline__ void series_sample_readout(const SeriesSampleArgs& a,
   }
 }
 
+// ---- the HMC twin's chain (k_series_hmc): state in LDS (series_hmc_lds), control in registers — the same in every thread ----
+enum { HMC_ST_NOISE, HMC_ST_ZN, HMC_ST_ZSN, HMC_ST_MN, HMC_ST_GN, HMC_ST_GZN, HMC_ST_LP, HMC_ST_BAD };      // entries of st
+enum { HMC_PH_INIT, HMC_PH_START, HMC_PH_LEAP, HMC_PH_FINAL };      // what the evaluation that has just finished was for
+enum { HMC_EV_GRAD, HMC_EV_GNOISE, HMC_EV_VALUE };                  // what an evaluation must deliver
+struct HmcLds {
+  double *th, *z, *zs, *mom, *grd, *tf, *st;
+  int *cls, *smap;
+};
+struct HmcCtl {
+  int ph = HMC_PH_INIT, mode = HMC_EV_VALUE;
+  int it = 0, mv = 0, step = 0, L = 0, nsel = 0;
+  int nrej = 0, pacc = 0, pmade = 0, stop = 0, moved = 0;
+  int cnt[4] = {0, 0, 0, 0};
+  double eps = 0.0, U0 = 0.0, K0 = 0.0, logu = 0.0;
+};
+// (the control state lives in LDS between two calls of series_hmc_ctl — st[HMC_ST_CTL ..] — not in registers across an evaluation)
+constexpr int HMC_ST_CTL = 8;
+static_assert(sizeof(HmcCtl) <= sizeof(double) * (HMC_ST_N - HMC_ST_CTL), "the control state fits the chain's scalars");
+__device__ __forceinline__ HmcCtl* hmc_ctl_ptr(double* smem, const SeriesHmcLds& m) { return reinterpret_cast<HmcCtl*>(smem + m.o_st + HMC_ST_CTL); }
+__device__ __forceinline__ HmcLds hmc_lds_ptrs(double* smem, const SeriesHmcLds& m) {
+  HmcLds hp;
+  hp.th = smem + m.o_th; hp.z = smem + m.o_z; hp.zs = smem + m.o_zs; hp.mom = smem + m.o_mom; hp.grd = smem + m.o_grd;
+  hp.cls = reinterpret_cast<int*>(smem + m.o_cls); hp.smap = hp.cls + (m.o_tf - m.o_cls);
+  hp.tf = smem + m.o_tf; hp.st = smem + m.o_st;
+  return hp;
+}
+// theta = transform(z) of class c (src/Model.jl:24-49) and d theta / d z at theta
+__device__ __forceinline__ double hmc_transform(const double* tf, int c, double z) {
+  const double mu = tf[3 * c], sg = tf[3 * c + 1], sc = tf[3 * c + 2];
+  const double x = fma(sg, z, mu);
+  return sc == 0.0 ? exp(x) : sc / (1.0 + exp(-x));
+}
+__device__ __forceinline__ double hmc_dtheta(const double* tf, int c, double th) {
+  const double sg = tf[3 * c + 1], sc = tf[3 * c + 2];
+  return sc == 0.0 ? sg * th : sg * th * (1.0 - th / sc);
+}
+
+// Stage 1 of the HMC twin, behind the value kernel's: the particle's latent state, classes and slot map, the class table and the
+// gradient program's tables (k_grad_contract's staging without the parameter values) -> LDS; its block of the trace -> NaN.
+__device__ __forceinline__ void series_hmc_stage(const SeriesHmcArgs& a, int p, const SeriesHmcLds& m, double* smem) {
+  const int tid = threadIdx.x;
+  const SeriesHmcParams& q = *a.hm;
+  const GProgHdr g = a.ghdr[p];
+  const HmcLds hp = hmc_lds_ptrs(smem, m);
+  double* gprm = smem + m.o_gprm;
+  int32_t* gpoff = reinterpret_cast<int32_t*>(smem + m.o_gtab);
+  uint8_t* gops = reinterpret_cast<uint8_t*>(gpoff + g.n_ops);
+  uint8_t* glc = gops + g.n_ops;
+  uint8_t* grc = glc + g.n_ops;
+  const int off = a.out_off[p];
+  for (int c = tid; c < g.n_prm; c += 256) {
+    hp.z[c] = q.z[off + c];
+    hp.cls[c] = q.cls[off + c];
+    hp.smap[c] = a.gmap[g.prm_off + c] | ((int)q.rule[g.prm_off + c] << 16);
+  }
+  for (int i = tid; i < 3 * q.C; i += 256) hp.tf[i] = q.tf[i];
+  for (int i = tid; i < 3; i += 256) gprm[g.n_prm + i] = 0.0;      // (the tail padding the reverse pass may read)
+  for (int i = tid; i < g.n_ops; i += 256) {
+    gpoff[i] = a.gpoff[g.node_off + i];
+    gops[i] = a.gops[g.node_off + i]; glc[i] = a.glc[g.node_off + i]; grc[i] = a.grc[g.node_off + i];
+  }
+  if (tid == 0) hp.st[HMC_ST_ZN] = q.z_noise[p];
+  if (q.out_trace != nullptr)
+    for (int i = tid; i < 4 * q.n_hmc; i += 256) q.out_trace[(long long)p * 4 * q.n_hmc + i] = __builtin_nan("");
+  __syncthreads();
+  if (tid == 0) {
+    HmcCtl hc;
+    for (int c = 0; c < g.n_prm; ++c) hc.nsel += hp.cls[c] >= 0 ? 1 : 0;
+    *hmc_ctl_ptr(smem, m) = hc;
+  }
+}
+
+// The device "recompile" in front of every evaluation: z -> theta (the caller-order vector), noise; the value program's parameters
+// through the slot map by emit's own operations (agp_engine.hip: 1 / (l l), 1 / l, -2 / (l l), pi / p — IEEE division), the gradient
+// program's parameters and its moving-leaf flags; the right-hand side, which the forward solve consumes.  Ends behind a barrier.
+__device__ __forceinline__ void series_hmc_recompile(const SeriesHmcArgs& a, int p, const SeriesHmcLds& m, double* smem, int n, long long o0) {
+  const int tid = threadIdx.x;
+  const SeriesHmcParams& q = *a.hm;
+  const GProgHdr g = a.ghdr[p];
+  const HmcLds hp = hmc_lds_ptrs(smem, m);
+  double* prm = smem + m.o_prm;
+  double* gprm = smem + m.o_gprm;
+  const int32_t* gpoff = reinterpret_cast<const int32_t*>(smem + m.o_gtab);
+  const uint8_t* gops = reinterpret_cast<const uint8_t*>(gpoff + g.n_ops);
+  uint8_t* gmv = const_cast<uint8_t*>(gops) + 3 * g.n_ops;
+  for (int c = tid; c < g.n_prm; c += 256) hp.th[c] = hp.cls[c] < 0 ? hp.z[c] : hmc_transform(hp.tf, hp.cls[c], hp.z[c]);
+  if (tid == 0) hp.st[HMC_ST_NOISE] = hmc_transform(hp.tf, q.noise_class, hp.st[HMC_ST_ZN]) + q.noise_jitter;
+  if (tid < m.np) {
+    smem[m.o_rvec + tid] = tid < n ? a.xs[o0 + tid] : 0.0;
+    smem[m.o_avec + tid] = 0.0;
+  }
+  __syncthreads();
+  for (int i = tid; i < g.n_ops; i += 256) {
+    const int o = gops[i], po = gpoff[i];
+    const int k = prm_count(o);
+    for (int j = 0; j < k; ++j) {
+      const int s = hp.smap[po + j];
+      const double v = hp.th[s & 0xffff];
+      gprm[po + j] = v;
+      prm[po + j] = hmc_rule_apply(s >> 16, v);
+    }
+    const bool stat = (o == OP_SE || o == OP_GE || o == OP_PER);
+    gmv[i] = (stat && gprm[po + (o == OP_SE ? 1 : 2)] != 0.0) ? 1 : 0;
+  }
+  __syncthreads();
+}
+
+// The final state and the counts of particle p (every exit of the chain)
+__device__ __forceinline__ void series_hmc_write(const SeriesHmcArgs& a, int p, const HmcLds& hp, const HmcCtl& hc, int npc) {
+  const int tid = threadIdx.x;
+  const SeriesHmcParams& q = *a.hm;
+  const int off = a.out_off[p];
+  for (int c = tid; c < npc; c += 256) { q.out_z[off + c] = hp.z[c]; q.out_prm[off + c] = hp.th[c]; }
+  if (tid == 0) {
+    q.out_z_noise[p] = hp.st[HMC_ST_ZN];
+    q.out_noise[p] = hp.st[HMC_ST_NOISE];
+    for (int k = 0; k < 4; ++k) q.out_counts[4 * p + k] = hc.cnt[k];
+  }
+}
+
+// Between two evaluations: what the one that has just finished (hc.ph) means for the chain, in every thread alike — the decisions
+// are functions of LDS values every thread reads in the same order; the per-coordinate work is one thread per coordinate.  Returns
+// true when another evaluation (of kind hc.mode, at the state now in LDS) is wanted, false when the particle is done and written.
+// One move is Gen.hmc taken literally: an evaluation at the current state, momenta, L leapfrog steps with an evaluation each,
+// alpha = (U_new - U_0) + (K_new - K_0), accept iff log u < alpha.  Randomness: Philox block (c0, iteration, move, HMC_PHILOX_TAG)
+// under the key (seeds[p], 0): momentum k of the selection (caller order) is word k % 4 of block c0 = k / 4; u is word 0 of c0 = 2^32.
+__device__ __forceinline__ bool series_hmc_ctl(const SeriesHmcArgs& a, int p, const HmcLds& hp, int npc) {
+  const int tid = threadIdx.x;
+  const SeriesHmcParams& q = *a.hm;
+  HmcCtl* const ctl = reinterpret_cast<HmcCtl*>(hp.st + HMC_ST_CTL);
+  __syncthreads();      // the evaluation's results: st[LP], st[BAD], grd, st[GN]
+  HmcCtl hc = *ctl;
+  // every thread carries the same control state; thread 0 puts it back, once every thread has read it
+  auto again = [&]() { __syncthreads(); if (tid == 0) *ctl = hc; return true; };
+  const bool bad = hp.st[HMC_ST_BAD] != 0.0;
+  const unsigned long long seed = q.seeds[p];
+  const bool nz = hc.mv == 1;      // the noise move: z_noise alone
+  const double ninf = -__builtin_inf();
+  if (hc.ph == HMC_PH_FINAL || (hc.ph == HMC_PH_INIT && bad)) {
+    series_hmc_write(a, p, hp, hc, npc);
+    return false;
+  }
+  if (hc.ph != HMC_PH_INIT) {
+    // ---- the gradient in z: -z_i + (d logpdf / d theta_i) (d theta_i / d z_i), in place ----
+    if (!bad) {
+      if (!nz) {
+        for (int c = tid; c < npc; c += 256)
+          hp.grd[c] = hp.cls[c] >= 0 ? fma(hp.grd[c], hmc_dtheta(hp.tf, hp.cls[c], hp.th[c]), -hp.z[c]) : 0.0;
+      } else if (tid == 0) {
+        hp.st[HMC_ST_GZN] = fma(hp.st[HMC_ST_GN], hmc_dtheta(hp.tf, q.noise_class, hp.st[HMC_ST_NOISE] - q.noise_jitter), -hp.st[HMC_ST_ZN]);
+      }
+    }
+    __syncthreads();
+    bool ok = !bad && isfinite(hp.st[HMC_ST_LP]) && isfinite(hp.st[HMC_ST_NOISE]);
+    double zz = 0.0;
+    if (ok) {
+      for (int c = 0; c < npc; ++c) ok = ok && isfinite(hp.th[c]);
+      if (!nz) {
+        for (int c = 0; c < npc; ++c)
+          if (hp.cls[c] >= 0) { ok = ok && isfinite(hp.grd[c]); zz = fma(hp.z[c], hp.z[c], zz); }
+      } else {
+        ok = ok && isfinite(hp.st[HMC_ST_GZN]);
+        zz = hp.st[HMC_ST_ZN] * hp.st[HMC_ST_ZN];
+      }
+    }
+    const double U = hp.st[HMC_ST_LP] - 0.5 * zz;
+    __syncthreads();      // (every thread has read what the updates below overwrite)
+    const double he = 0.5 * hc.eps;
+    bool finish = false, accept = false;
+    double alpha = ninf;
+    if (hc.ph == HMC_PH_START) {
+      hc.logu = log(philox_uniform(philox4x64_10(1ull << 32, (uint64_t)hc.it, (uint64_t)hc.mv, HMC_PHILOX_TAG, seed, 0).w[0]));
+      if (!ok) {
+        finish = true;
+      } else {
+        hc.U0 = U;
+        if (!nz) {
+          for (int c = tid; c < npc; c += 256)
+            if (hp.cls[c] >= 0) {
+              int k = 0;
+              for (int j = 0; j < c; ++j) k += hp.cls[j] >= 0 ? 1 : 0;
+              const Philox4 b = philox4x64_10((uint64_t)(k >> 2), (uint64_t)hc.it, 0, HMC_PHILOX_TAG, seed, 0);
+              hp.mom[c] = ndtri(philox_uniform(b.w[k & 3]));
+              hp.zs[c] = hp.z[c];
+            }
+        } else if (tid == 0) {
+          hp.st[HMC_ST_MN] = ndtri(philox_uniform(philox4x64_10(0, (uint64_t)hc.it, 1, HMC_PHILOX_TAG, seed, 0).w[0]));
+          hp.st[HMC_ST_ZSN] = hp.st[HMC_ST_ZN];
+        }
+        __syncthreads();
+        double mm = 0.0;
+        if (!nz) { for (int c = 0; c < npc; ++c) if (hp.cls[c] >= 0) mm = fma(hp.mom[c], hp.mom[c], mm); }
+        else mm = hp.st[HMC_ST_MN] * hp.st[HMC_ST_MN];
+        hc.K0 = -0.5 * mm;
+        __syncthreads();
+        if (hc.L == 0) {      // (no leapfrog step: the state stands, alpha = 0)
+          finish = true; alpha = 0.0; accept = hc.logu < alpha;
+        } else {
+          if (!nz) {
+            for (int c = tid; c < npc; c += 256)
+              if (hp.cls[c] >= 0) { hp.mom[c] = fma(he, hp.grd[c], hp.mom[c]); hp.z[c] = fma(hc.eps, hp.mom[c], hp.z[c]); }
+          } else if (tid == 0) {
+            hp.st[HMC_ST_MN] = fma(he, hp.st[HMC_ST_GZN], hp.st[HMC_ST_MN]);
+            hp.st[HMC_ST_ZN] = fma(hc.eps, hp.st[HMC_ST_MN], hp.st[HMC_ST_ZN]);
+          }
+          hc.step = 1; hc.ph = HMC_PH_LEAP;
+          return again();
+        }
+      }
+    } else {      // HMC_PH_LEAP: the evaluation at the end of leapfrog step hc.step
+      if (ok) {
+        const bool more = hc.step < hc.L;
+        if (!nz) {
+          for (int c = tid; c < npc; c += 256)
+            if (hp.cls[c] >= 0) {
+              double mo = fma(he, hp.grd[c], hp.mom[c]);
+              if (more) { mo = fma(he, hp.grd[c], mo); hp.z[c] = fma(hc.eps, mo, hp.z[c]); }
+              hp.mom[c] = mo;
+            }
+        } else if (tid == 0) {
+          double mo = fma(he, hp.st[HMC_ST_GZN], hp.st[HMC_ST_MN]);
+          if (more) { mo = fma(he, hp.st[HMC_ST_GZN], mo); hp.st[HMC_ST_ZN] = fma(hc.eps, mo, hp.st[HMC_ST_ZN]); }
+          hp.st[HMC_ST_MN] = mo;
+        }
+        if (more) { ++hc.step; return again(); }
+        __syncthreads();
+        double mm = 0.0;
+        if (!nz) { for (int c = 0; c < npc; ++c) if (hp.cls[c] >= 0) mm = fma(hp.mom[c], hp.mom[c], mm); }
+        else mm = hp.st[HMC_ST_MN] * hp.st[HMC_ST_MN];
+        alpha = (U - hc.U0) + (-0.5 * mm - hc.K0);
+        accept = hc.logu < alpha;
+      }
+      finish = true;
+      if (!accept) {      // back to the saved state (a trajectory that left the positive definite region included)
+        if (!nz) { for (int c = tid; c < npc; c += 256) if (hp.cls[c] >= 0) hp.z[c] = hp.zs[c]; }
+        else if (tid == 0) hp.st[HMC_ST_ZN] = hp.st[HMC_ST_ZSN];
+      }
+    }
+    // ---- the move is over ----
+    if (finish) {
+      hc.moved = 1;
+      if (!ok) ++hc.cnt[3];
+      if (!nz) { ++hc.cnt[1]; hc.cnt[0] += accept ? 1 : 0; hc.pacc = accept ? 1 : 0; hc.pmade = 1; }
+      else hc.cnt[2] += accept ? 1 : 0;
+      if (q.out_trace != nullptr) {
+        const int e = (hc.it * 2 + hc.mv) * 2;      // (the thread that set the entry to NaN writes it)
+        double* t = q.out_trace + (long long)p * 4 * q.n_hmc;
+        if (tid == (e & 255)) t[e] = alpha;
+        if (tid == ((e + 1) & 255)) t[e + 1] = hc.logu;
+      }
+    }
+  }
+  // ---- the next move: parameters, then noise, then the exit check of the iteration ----
+  int it = hc.it, mv = hc.ph == HMC_PH_INIT ? 0 : hc.mv + 1;
+  for (;;) {
+    if (mv == 2) {
+      if (hc.pmade) {
+        hc.nrej = hc.pacc ? 0 : hc.nrej + 1;
+        if (q.n_exit > 0 && hc.nrej >= q.n_exit) hc.stop = 1;
+      }
+      hc.pmade = 0; ++it; mv = 0;
+    }
+    if (it >= q.n_hmc || hc.stop) {
+      if (!hc.moved) {      // no move was made: the first evaluation is the final one
+        series_hmc_write(a, p, hp, hc, npc);
+        return false;
+      }
+      hc.ph = HMC_PH_FINAL; hc.mode = HMC_EV_VALUE;
+      return again();
+    }
+    if (mv == 0 && hc.nsel == 0) { mv = 1; continue; }
+    if (mv == 1 && q.L_noise == 0) { mv = 2; continue; }
+    break;
+  }
+  hc.it = it; hc.mv = mv; hc.ph = HMC_PH_START; hc.step = 0;
+  hc.L = mv == 0 ? q.L_prm : q.L_noise;
+  hc.eps = mv == 0 ? q.eps_prm : q.eps_noise;
+  hc.mode = (mv == 0 || (q.flags & HMC_FLAG_FULL_NOISE_GRAD)) ? HMC_EV_GRAD : HMC_EV_GNOISE;
+  return again();
+}
+
 // The body of every instantiation: stages 1-5 (value kernel, probe, gradient kernel, predictive kernel alike — the same statements),
 // with GS > 0 (gradient tape of GS nodes) the stages G1-G5 behind them, with SeriesPredArgs or SeriesSumArgs the stages P1-P2.
+// With SeriesHmcArgs the statements from stage 2 to G5 are the body of a loop (two labels and their gotos, which only that
+// instantiation has: the other instantiations' statements stand where they stood): series_hmc_recompile in front of stage 2,
+// series_hmc_ctl behind G5, G5 reducing into LDS.
 template <int D, bool PROBE, int GS, class ArgsT>
 __device__ __forceinline__ void series_body(const ArgsT& a, double* smem) {
   constexpr int E = 4;
@@ -504,7 +788,8 @@ __device__ __forceinline__ void series_body(const ArgsT& a, double* smem) {
   constexpr bool PROBA = std::is_same_v<ArgsT, SeriesProbaArgs>;      // the held-out twin: n below is the JOINT length
   constexpr bool SAMPLE = std::is_same_v<ArgsT, SeriesSampleArgs>;    // the sampling twin: the same, the query rows' right-hand side 0
   constexpr bool JOINT = PROBA || SAMPLE;
-  const int tid = threadIdx.x, l = tid & 63, w = tid >> 6, l15 = l & 15, lq = l >> 4;
+  constexpr bool HMC = std::is_same_v<ArgsT, SeriesHmcArgs>;          // the HMC twin: stages 2 .. G5 in a loop, the chain between them
+  int tid = threadIdx.x, l = tid & 63, w = tid >> 6, l15 = l & 15, lq = l >> 4;      // (constant but for the HMC twin's hmc_eval)
   int p, n;
   long long o0 = 0;
   [[maybe_unused]] int ntr = 0;            // JOINT: training points (rows [ntr, n) are the query rows)
@@ -537,7 +822,8 @@ __device__ __forceinline__ void series_body(const ArgsT& a, double* smem) {
   }
   const ProgHdr h = [&]() -> ProgHdr { if constexpr (PROBE) return ProgHdr{}; else return a.hdr[p]; }();
   const auto m = [&]() {
-    if constexpr (GS > 0) return series_grad_lds(n, h.n_ops, h.n_prm, h.n_cp, a.ghdr[p].n_ops, a.ghdr[p].n_prm);
+    if constexpr (HMC) return series_hmc_lds(n, h.n_ops, h.n_prm, h.n_cp, a.ghdr[p].n_ops, a.ghdr[p].n_prm, a.C);
+    else if constexpr (GS > 0) return series_grad_lds(n, h.n_ops, h.n_prm, h.n_cp, a.ghdr[p].n_ops, a.ghdr[p].n_prm);
     else if constexpr (PRED) return series_pred_lds(n, h.n_ops, h.n_prm, h.n_cp);
     else return series_lds(n, h.n_ops, h.n_prm, h.n_cp);
   }();
@@ -591,6 +877,17 @@ __device__ __forceinline__ void series_body(const ArgsT& a, double* smem) {
     for (int i = tid; i < h.n_prm + 2; i += 256) prm[i] = a.prm[h.prm_off + i];      // (the parameter buffer carries two doubles of tail padding)
     for (int i = tid; i < h.n_ops; i += 256) ops[i] = (int)a.ops[h.op_off + i];
     __syncthreads();
+    if constexpr (HMC) series_hmc_stage(a, p, m, smem);
+  }
+hmc_eval: __attribute__((unused));      // HMC: every evaluation of the chain starts here, at the state in LDS (a label cannot stand
+  if constexpr (!PROBE) {               // inside a constexpr if: the production branch is closed in front of it and opened again)
+    if constexpr (HMC) {
+      // (the thread's indices are formed again for every evaluation: what follows from them — the addresses of every stage — is
+      // then computed where it is used, as in the gradient kernel, not kept in registers around the whole loop)
+      asm volatile("" : "+v"(tid));
+      l = tid & 63; w = tid >> 6; l15 = l & 15; lq = l >> 4;
+      series_hmc_recompile(a, p, m, smem, n, o0);
+    }
 
     // ---- 2. per-point tables (cov_prologue's arithmetic) ----
     if (h.n_cp > 0) {
@@ -600,7 +897,7 @@ __device__ __forceinline__ void series_body(const ArgsT& a, double* smem) {
 
     // ---- 3. K + noise I, lower block triangle; one block per wave and pass, lane (i = l%16, q = l/16) <-> elements (i, q + 4 e) ----
     {
-      const double noise = a.noise[p];
+      const double noise = [&]() { if constexpr (HMC) return smem[m.o_st + HMC_ST_NOISE]; else return a.noise[p]; }();
       [[maybe_unused]] double noise_q = 0.0;      // JOINT: the diagonal addend of the query rows
       if constexpr (JOINT) noise_q = a.noise_pred[p];
       const int nblk = nb * (nb + 1) / 2;
@@ -669,6 +966,11 @@ __device__ __forceinline__ void series_body(const ArgsT& a, double* smem) {
       if constexpr (JOINT) {      // m log 2 pi, and the Jacobian of the series' own transform: m log|slope|
         const double mq = (double)(n - ntr);
         lp = -0.5 * (mq * 1.8378770664093454835606594728112 + ld + ss) + mq * log(fabs(a.y_slope[a.series[p]]));
+      } else if constexpr (HMC) {
+        // (the statement below, written as the fused operation it compiles to in the other instantiations: in a loop the compiler
+        // forms the invariant product n log 2 pi once, in front of it, and the sum is then rounded twice — out_logpdf would differ
+        // from the value entry's in the last bit; tests/test_gpu_series_hmc.py compares the bits)
+        lp = -0.5 * (fma((double)n, 1.8378770664093454835606594728112, ld) + ss);
       } else {
         lp = -0.5 * ((double)n * 1.8378770664093454835606594728112 + ld + ss);
       }
@@ -676,6 +978,7 @@ __device__ __forceinline__ void series_body(const ArgsT& a, double* smem) {
       // store the two reductions above are dead code in that instantiation)
       if constexpr (!SAMPLE) a.out_lp[p] = bad != 0 ? __builtin_nan("") : lp;
       a.out_info[p] = bad;
+      if constexpr (HMC) { smem[m.o_st + HMC_ST_LP] = lp; smem[m.o_st + HMC_ST_BAD] = (double)bad; }
       if constexpr (PROBE) { a.out_part[2 * p] = ld; a.out_part[2 * p + 1] = ss; }
     }
   }
@@ -752,18 +1055,22 @@ __device__ __forceinline__ void series_body(const ArgsT& a, double* smem) {
     uint8_t* gmv = grc + g.n_ops;      // 1: stationary leaf with non-zero amplitude (see grad_elements)
     double* red = smem + m.o_red;
     if (tid == 0) rvec[0] = (double)bad;      // (wave 0 keeps the first bad pivot)
-    // the gradient program (k_grad_contract's staging)
-    for (int i = tid; i < g.n_prm + 3; i += 256) gprm[i] = a.gprm[g.prm_off + i];
-    for (int i = tid; i < g.n_ops; i += 256) {
-      const int po = a.gpoff[g.node_off + i];
-      const int o = a.gops[g.node_off + i];
-      gpoff[i] = po;
-      gops[i] = (uint8_t)o; glc[i] = a.glc[g.node_off + i]; grc[i] = a.grc[g.node_off + i];
-      const bool stat = (o == OP_SE || o == OP_GE || o == OP_PER);
-      gmv[i] = (stat && a.gprm[g.prm_off + po + (o == OP_SE ? 1 : 2)] != 0.0) ? 1 : 0;
+    // the gradient program (k_grad_contract's staging; HMC: series_hmc_stage and series_hmc_recompile have done it)
+    if constexpr (!HMC) {
+      for (int i = tid; i < g.n_prm + 3; i += 256) gprm[i] = a.gprm[g.prm_off + i];
+      for (int i = tid; i < g.n_ops; i += 256) {
+        const int po = a.gpoff[g.node_off + i];
+        const int o = a.gops[g.node_off + i];
+        gpoff[i] = po;
+        gops[i] = (uint8_t)o; glc[i] = a.glc[g.node_off + i]; grc[i] = a.grc[g.node_off + i];
+        const bool stat = (o == OP_SE || o == OP_GE || o == OP_PER);
+        gmv[i] = (stat && a.gprm[g.prm_off + po + (o == OP_SE ? 1 : 2)] != 0.0) ? 1 : 0;
+      }
     }
     __syncthreads();
-    if (rvec[0] != 0.0) {      // a bad pivot: NaN in the whole gradient block and d / d noise (the value is NaN already), nothing else
+    if constexpr (HMC) {       // a bad pivot, or the value alone is wanted: the chain decides what follows
+      if (rvec[0] != 0.0 || hmc_ctl_ptr(smem, m)->mode == HMC_EV_VALUE) goto hmc_ctl;
+    } else if (rvec[0] != 0.0) {      // a bad pivot: NaN in the whole gradient block and d / d noise (the value is NaN already), nothing else
       for (int q = tid; q < g.n_prm; q += 256) a.out_grad[a.out_off[p] + a.gmap[g.prm_off + q]] = __builtin_nan("");
       if (tid == 0) a.out_gnoise[p] = __builtin_nan("");
       return;
@@ -842,6 +1149,35 @@ __device__ __forceinline__ void series_body(const ArgsT& a, double* smem) {
     //      K^-1(rb,cb) = sum_{k >= rb} Z(rb,k) Z(cb,k)' in registers — lane (i = l%16, q = l/16) <-> elements (i, q + 4 e), the map of
     //      stage 3 — turns it into G and runs the reverse-mode pass on its four elements.  Off-diagonal blocks stand for their mirror
     //      image (weight 2); diagonal blocks are evaluated in full at weight 1; rows / columns past n (identity in Z) weigh 0 ----
+    if constexpr (HMC) {
+      // a noise move wants d / d noise = tr G = 1/2 (alpha'alpha - tr K^-1) alone, and tr K^-1 = |Z|_F^2 over the rows and columns
+      // below n (slot (rb, cb) holds Z(cb, rb): element 64 e + l is row 16 cb + l % 16, column 16 rb + 4 e + l / 16): no MFMA
+      // chain, no reverse-mode pass.  Fixed order: thread -> wave -> the four waves, then alpha'alpha in one thread.
+      if (hmc_ctl_ptr(smem, m)->mode == HMC_EV_GNOISE) {
+        double s2 = 0.0;
+        const int nblk = nb * (nb + 1) / 2;
+        for (int b = w; b < nblk; b += 4) {
+          int rb, cb;
+          series_blk_rc(b, rb, cb);
+          const double* zb = sm + blk_idx(rb, cb) * 256;
+#pragma unroll
+          for (int e = 0; e < E; ++e) {
+            const double v = zb[64 * e + l];
+            s2 = (cb * 16 + l15 < n && rb * 16 + 4 * e + lq < n) ? fma(v, v, s2) : s2;
+          }
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) s2 += __shfl_xor(s2, off);
+        if (l == 0) red[w] = s2;
+        __syncthreads();
+        if (tid == 0) {
+          double aa = 0.0;
+          for (int i = 0; i < n; ++i) aa = fma(alpha[i], alpha[i], aa);
+          smem[m.o_st + HMC_ST_GN] = 0.5 * (aa - (((red[0] + red[1]) + red[2]) + red[3]));
+        }
+        goto hmc_ctl;
+      }
+    }
     constexpr int NG = 3 * GS + 2;
     double gacc[NG];
     for (int q = 0; q <= g.n_prm + 2 && q < NG; ++q) gacc[q] = 0.0;
@@ -890,9 +1226,19 @@ __device__ __forceinline__ void series_body(const ArgsT& a, double* smem) {
     __syncthreads();
     for (int q = tid; q < nq; q += 256) {
       const double s = ((red[q] + red[nq + q]) + red[2 * nq + q]) + red[3 * nq + q];
-      if (q < g.n_prm) a.out_grad[a.out_off[p] + a.gmap[g.prm_off + q]] = s;
-      else a.out_gnoise[p] = s;
+      if constexpr (HMC) {      // into LDS, the caller's order: the chain reads it
+        if (q < g.n_prm) smem[m.o_grd + (reinterpret_cast<const int*>(smem + m.o_cls)[(m.o_tf - m.o_cls) + q] & 0xffff)] = s;
+        else smem[m.o_st + HMC_ST_GN] = s;
+      } else {
+        if (q < g.n_prm) a.out_grad[a.out_off[p] + a.gmap[g.prm_off + q]] = s;
+        else a.out_gnoise[p] = s;
+      }
     }
+  }
+
+hmc_ctl: __attribute__((unused));
+  if constexpr (HMC) {
+    if (series_hmc_ctl(a, p, hmc_lds_ptrs(smem, m), a.ghdr[p].n_prm)) goto hmc_eval;
   }
 }
 
@@ -906,6 +1252,15 @@ __global__ __launch_bounds__(256, 2) void k_series_logpdf(std::conditional_t<PRO
 // array, as in k_grad_contract<GS>), D as above.
 template <int D, int GS>
 __global__ __launch_bounds__(256, 2) void k_series_logpdf_grad(SeriesGradArgs a) {
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  series_body<D, false, GS>(a, smem);
+}
+
+// rejuvenate_particle_parameters (src/inference_smc_anneal_data.jl:33-76) of one (series, particle) pair by one workgroup: n_hmc
+// iterations of an HMC move on the numeric kernel parameters and one on the noise, in the reference's latent space, every
+// evaluation the gradient kernel's statements (agp_hmc_series_batch); D and GS as in k_series_logpdf_grad.
+template <int D, int GS>
+__global__ __launch_bounds__(256, 2) void k_series_hmc(SeriesHmcArgs a) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   series_body<D, false, GS>(a, smem);
 }
@@ -929,6 +1284,7 @@ __global__ __launch_bounds__(256, 2) void k_series_predict_sample(SeriesSampleAr
 // ... and behind those launches, on the same stream: one workgroup per series; a series with a failed particle (whatever its weight)
 // has no valid sample — its whole block of out_x becomes NaN.  Series without query points own nothing (and their particles' info
 // words were never written).
+#ifndef AGP_SERIES_TEMPLATES_ONLY      // (a plain kernel: defined in ONE unit — agp_kernels_series_hmc.hip includes the templates alone)
 __global__ __launch_bounds__(256) void k_series_sample_fill(SeriesSampleFillArgs a) {
   const int s = blockIdx.x;
   const long long q0 = a.q_off[s], m = a.q_off[s + 1] - q0;
@@ -939,6 +1295,7 @@ __global__ __launch_bounds__(256) void k_series_sample_fill(SeriesSampleFillArgs
   double* ox = a.out_x + a.R * q0;
   for (long long i = threadIdx.x; i < a.R * m; i += 256) ox[i] = __builtin_nan("");
 }
+#endif
 
 // Posterior mean and marginal variance of one (series, particle) pair at the series' own query times by one workgroup, behind the
 // value and in the value kernel's LDS (agp_predict_series_batch).

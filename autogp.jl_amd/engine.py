@@ -40,7 +40,7 @@ EXPORTED_SYMBOLS = [
     "agp_debug_factor_batch", "agp_logpdf_series_batch", "agp_debug_series_factor", "agp_logpdf_grad_series_batch",
     "agp_predict_series_batch", "agp_debug_remove_factor", "agp_predict_quantile_series_batch",
     "agp_predict_logpdf_series_batch", "agp_predict_sample_series_batch", "agp_predict_sum_series_batch",
-    "agp_debug_toeplitz", "agp_debug_cov_sweep",
+    "agp_debug_toeplitz", "agp_debug_cov_sweep", "agp_hmc_series_batch",
 ]
 COMM_ID_BYTES = 128
 SERIES_MAX_N = 176      # AGP_SERIES_MAX_N of include/autogp_hip.h: the longest series of logpdf_series_batch
@@ -109,6 +109,10 @@ def load_library(path=None):
     lib.agp_logpdf_series_batch.restype = C.c_int
     lib.agp_logpdf_grad_series_batch.argtypes = [vp, C.c_int32, C.POINTER(C.c_int64), dp, dp, C.c_int32, ip, ip, u8p, ip, dp, dp, dp, dp, dp, ip]
     lib.agp_logpdf_grad_series_batch.restype = C.c_int
+    lib.agp_hmc_series_batch.argtypes = [vp, C.c_int32, C.POINTER(C.c_int64), dp, dp, C.c_int32, ip, ip, u8p, ip, dp, dp, ip, C.c_int32, dp,
+                                         C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_double, C.c_int32,
+                                         C.POINTER(C.c_uint64), C.c_int32, dp, dp, dp, dp, dp, ip, ip, dp]
+    lib.agp_hmc_series_batch.restype = C.c_int
     lib.agp_predict_series_batch.argtypes = [vp, C.c_int32, C.POINTER(C.c_int64), dp, dp, C.POINTER(C.c_int64), dp, C.c_int32, ip, ip, u8p,
                                              ip, dp, dp, dp, dp, dp, C.POINTER(C.c_int64), dp, ip]
     lib.agp_predict_series_batch.restype = C.c_int
@@ -588,6 +592,49 @@ class GPEngine:
         self._check(self._lib.agp_logpdf_grad_series_batch(self._ctx, *_series_ctypes(packed), _dp(out), _dp(grad), _dp(gn), _ip(info)))
         _raise_first_bad(info, check)
         return out, [grad[prm_off[i]:prm_off[i + 1]] for i in range(P)], gn, info
+
+    def hmc_series_batch(self, series, nodes, z, z_noise, prm_class, tf, series_index, n_hmc, seeds, noise_class=0, noise_jitter=1e-5,
+                         L_param=10, eps_param=0.02, L_noise=10, eps_noise=0.02, n_exit=None, want_trace=False, flags=0, check=True,
+                         programs=None):
+        """agp_hmc_series_batch: the reference's rejuvenate_particle_parameters for every (series, particle) of a family of short
+        series in one call — n_hmc iterations of an HMC move on the kernel parameters and one on the noise, in the latent space
+        (theta = transform(z; tf[class])), the whole chain of a particle in one workgroup.  `nodes` (or `programs`) give the
+        STRUCTURE only (their parameter values are not read); z: one vector per particle in the order of gp.encode(node)[1] (a
+        slot of class < 0 holds the FIXED parameter value); prm_class: one int32 vector per particle; tf: (C, 3) rows
+        (mu, sigma, scale); seeds: one uint64 per particle; n_exit: None = n_hmc (the reference's default), <= 0 = never.
+        Returns a SimpleNamespace: z, prm (lists of per-particle vectors), z_noise[P], noise[P], logpdf[P] (bit-identical to
+        logpdf_series_batch of (prm, noise)), counts[P, 4] (parameter moves accepted, tried, noise moves accepted, trajectories
+        rejected as not positive definite), info[P], trace[P, n_hmc, 2, 2] of (alpha, log u) or None."""
+        from types import SimpleNamespace
+        pt_off, ts, xs = pack_series(series)
+        op_off, ops, prm_off, _ = programs if programs is not None else _gp.encode_batch(nodes)
+        P = op_off.shape[0] - 1
+        nt = int(prm_off[-1])
+        cat = lambda parts, dt: np.ascontiguousarray(np.concatenate([np.asarray(a, dtype=dt).ravel() for a in parts]) if len(parts) else np.zeros(0, dtype=dt))
+        zc = cat(z, np.float64); cls = cat(prm_class, np.int32)
+        if zc.shape != (nt,) or cls.shape != (nt,):
+            raise ValueError("z and prm_class need one entry per program parameter")
+        zn = _f64(z_noise); sidx = np.ascontiguousarray(np.asarray(series_index, dtype=np.int32))
+        seeds = np.ascontiguousarray(np.asarray(seeds, dtype=np.uint64))
+        if zn.shape != (P,) or sidx.shape != (P,) or seeds.shape != (P,):
+            raise ValueError("one z_noise, one series index and one seed per particle required")
+        tf = _f64(tf)
+        if tf.ndim != 2 or tf.shape[1] != 3:
+            raise ValueError("tf must have shape (C, 3): (mu, sigma, scale) per class")
+        n_hmc = int(n_hmc)
+        out_z = np.zeros(max(1, nt)); out_prm = np.zeros(max(1, nt)); out_zn = np.empty(P); out_nz = np.empty(P); lp = np.empty(P)
+        counts = np.zeros((P, 4), dtype=np.int32); info = np.zeros(P, dtype=np.int32)
+        trace = np.empty((P, max(0, n_hmc), 2, 2)) if want_trace else None
+        some = lambda a: a if a.size else np.zeros(1, dtype=a.dtype)
+        self._check(self._lib.agp_hmc_series_batch(
+            self._ctx, pt_off.shape[0] - 1, pt_off.ctypes.data_as(C.POINTER(C.c_int64)), _dp(some(ts)), _dp(some(xs)), P, _ip(some(sidx)),
+            _ip(op_off), _u8(some(ops)), _ip(prm_off), _dp(some(zc)), _dp(some(zn)), _ip(some(cls)), tf.shape[0], _dp(some(tf)), int(noise_class),
+            float(noise_jitter), n_hmc, int(L_param), float(eps_param), int(L_noise), float(eps_noise), int(n_hmc if n_exit is None else n_exit),
+            some(seeds).ctypes.data_as(C.POINTER(C.c_uint64)), int(flags), _dp(out_z), _dp(some(out_zn)), _dp(out_prm), _dp(some(out_nz)),
+            _dp(some(lp)), _ip(some(counts.reshape(-1))), _ip(some(info)), _dp(some(trace.reshape(-1))) if want_trace else None))
+        _raise_first_bad(info, check)
+        split = lambda a: [a[prm_off[i]:prm_off[i + 1]] for i in range(P)]
+        return SimpleNamespace(z=split(out_z), prm=split(out_prm), z_noise=out_zn, noise=out_nz, logpdf=lp, counts=counts, info=info, trace=trace)
 
     def predict_series_batch(self, series, queries, nodes, noises, series_index, noise_pred=None, want_logpdf=False, check=True,
                              programs=None):
@@ -2079,6 +2126,44 @@ def predict_sum_series(engine, series, queries, nodes, noises, series_index, log
             d[f"y_{qv!r}"] = cat([r.x[p][blk, j] for _, p, _, blk in rows])
         out.append(d)
     return out
+
+
+def with_params(node, params):
+    """A copy of a kernel tree with the numeric parameters replaced by `params`, in the order of gp.encode(node)[1]."""
+    it = iter(float(v) for v in params)
+
+    def rec(nd):
+        if isinstance(nd, _gp.LeafNode):
+            return type(nd)(*[next(it) for _ in nd.params()])
+        left, right = rec(nd.left), rec(nd.right)
+        if isinstance(nd, _gp.ChangePoint):
+            return _gp.ChangePoint(left, right, next(it), next(it))
+        return type(nd)(left, right)
+    out = rec(node)
+    if next(it, None) is not None:
+        raise ValueError("more parameters than the tree has")
+    return out
+
+
+def mcmc_parameters_series(engine, series, nodes, noises, series_index, n_hmc, seeds, hmc_config=None, prior=None, infer_noise=True,
+                           want_trace=False, check=True):
+    """mcmc_parameters! / rejuvenate_particle_parameters (src/inference_smc_anneal_data.jl:33-76) for callers that hold one model
+    per short series: every particle's kernel parameters and noise are untransformed to the latent z of the reference's prior
+    (prior: GPConfig.prior's entries "gamma", "period", "wildcard"; ChangePoint scales stay fixed), ONE call of
+    GPEngine.hmc_series_batch runs n_hmc HMC iterations on all of them, and the new trees and noises come back — ready for
+    predict_*_series.  hmc_config: the reference's keys L_param, eps_param, L_noise, eps_noise, n_exit; infer_noise=False skips the
+    noise moves.  Returns (nodes, noises, counts[P, 4], result) with `result` the engine call's namespace (logpdf, z, trace ...)."""
+    from . import prior as _prior
+    cfg = dict(hmc_config or {})
+    tf = _prior.hmc_transform_table(prior)
+    cls = [_prior.hmc_classes(nd) for nd in nodes]
+    z = [np.array([_prior.hmc_untransform(v, c, tf) for v, c in zip(_gp.encode(nd)[1], k)]) for nd, k in zip(nodes, cls)]
+    zn = np.array([_prior.hmc_untransform(float(v) - _prior.JITTER, _prior.HMC_CLASS_WILDCARD, tf) for v in noises])
+    r = engine.hmc_series_batch(series, nodes, z, zn, cls, tf, series_index, n_hmc, seeds, noise_class=_prior.HMC_CLASS_WILDCARD,
+                                noise_jitter=_prior.JITTER, L_param=cfg.get("L_param", 10), eps_param=cfg.get("eps_param", 0.02),
+                                L_noise=cfg.get("L_noise", 10) if infer_noise else 0, eps_noise=cfg.get("eps_noise", 0.02),
+                                n_exit=cfg.get("n_exit", None), want_trace=want_trace, check=check)
+    return [with_params(nd, q) for nd, q in zip(nodes, r.prm)], r.noise.copy(), r.counts, r
 
 
 def quantile(dist: MvNormal, p):

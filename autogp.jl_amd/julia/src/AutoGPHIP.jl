@@ -247,6 +247,65 @@ function logpdf_grad_series_batch(eng::Engine, series::Vector{<:Tuple{Vector{Flo
     return out, grads, gn, info
 end
 
+"Transform classes of `mcmc_parameters_series_batch`: 0 wildcard, 1 period, 2 gamma (GPConfig.prior's entries), -1 FIXED."
+hmc_classes(n::GP.GammaExponential) = Int32[0, 2, 0]
+hmc_classes(n::GP.Periodic) = Int32[0, 1, 0]
+hmc_classes(n::GP.ChangePoint) = Int32[0, -1]              # the scale stays what it is (src/Model.jl:121)
+hmc_classes(n::GP.BinaryOpNode) = Int32[]
+hmc_classes(n::GP.Node) = zeros(Int32, length(params(n)))
+"`tf[class]` = (mu, sigma, scale) from a `GP.GPConfig`'s prior; scale 0: log-normal."
+hmc_transform_table(prior) = Float64[prior[:wildcard][:mu] prior[:wildcard][:sigma] 0.0;
+                                     prior[:period][:mu] prior[:period][:sigma] 0.0;
+                                     prior[:gamma][:mu] prior[:gamma][:sigma] prior[:gamma][:scale]]
+hmc_untransform(v, c, tf) = c < 0 ? v : tf[c + 1, 3] == 0 ? (log(v) - tf[c + 1, 1]) / tf[c + 1, 2] :
+                            (log(v / (tf[c + 1, 3] - v)) - tf[c + 1, 1]) / tf[c + 1, 2]
+
+"`mcmc_parameters!` / `rejuvenate_particle_parameters` (src/inference_smc_anneal_data.jl:33-76) for MANY short series in one call
+(agp_hmc_series_batch): `n_hmc` iterations of an HMC move on every particle's numeric kernel parameters and one on its noise, in the
+latent space of `config.prior`, the whole chain of a particle in one workgroup.  `seeds[p]` keys particle `p`'s Philox stream (not
+Julia's RNG).  `hmc_config`: the reference's keys `:L_param`, `:eps_param`, `:L_noise`, `:eps_noise`, `:n_exit`; `infer_noise = false`
+skips the noise moves.  Returns `(kernels, noises, logpdf, counts, info)`: the moved trees and noises, their log marginal
+likelihoods (bit-identical to `logpdf_series_batch` of the returned trees), `counts[:, p]` = parameter moves accepted, tried, noise
+moves accepted, trajectories rejected as not positive definite."
+function mcmc_parameters_series_batch(eng::Engine, series::Vector{<:Tuple{Vector{Float64},Vector{Float64}}}, kernels::Vector{<:GP.Node},
+                                      noises::Vector{Float64}, series_index::Vector{<:Integer}, n_hmc::Integer, seeds::Vector{<:Integer};
+                                      config = GP.GPConfig(), hmc_config = Dict(), infer_noise::Bool = true, jitter::Float64 = 1e-5)
+    P = length(kernels)
+    (length(noises) == P && length(series_index) == P && length(seeds) == P) ||
+        throw(ArgumentError("one noise, one series index and one seed per particle required"))
+    pt_off = Int64[0]; ts = Float64[]; xs = Float64[]
+    for (s, (t, x)) in enumerate(series)
+        length(t) == length(x) || throw(ArgumentError("series $s: ts and xs must have equal lengths"))
+        length(t) <= SERIES_MAX_N || throw(ArgumentError("series $s has $(length(t)) points, more than SERIES_MAX_N ($SERIES_MAX_N)"))
+        append!(ts, t); append!(xs, x); push!(pt_off, length(ts))
+    end
+    isempty(ts) && (push!(ts, 0.0); push!(xs, 0.0))
+    sidx = Int32[Int32(i - 1) for i in series_index]
+    op_off, ops, prm_off, prm = encode_batch(kernels)
+    tf = hmc_transform_table(config.prior)
+    tfr = collect(vec(permutedims(tf)))                    # row-major (class, 3)
+    cls = Int32[]
+    for k in kernels, nd in GP.unroll(k)
+        append!(cls, hmc_classes(nd))
+    end
+    isempty(cls) && push!(cls, Int32(0))
+    z = Float64[hmc_untransform(prm[i], cls[i], tf) for i in eachindex(cls)]
+    zn = Float64[hmc_untransform(v - jitter, 0, tf) for v in noises]
+    sd = UInt64[UInt64(s) for s in seeds]
+    nt = max(1, Int(prm_off[end]))
+    oz = zeros(Float64, nt); oprm = zeros(Float64, nt); ozn = Vector{Float64}(undef, P); onz = Vector{Float64}(undef, P)
+    lp = Vector{Float64}(undef, P); counts = zeros(Int32, 4, P); info = Vector{Int32}(undef, P)
+    GC.@preserve pt_off ts xs sidx op_off ops prm_off z zn cls tfr sd oz ozn oprm onz lp counts info check(eng, ccall((:agp_hmc_series_batch, LIB), Cint,
+        (Ptr{Cvoid}, Int32, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Int32}, Ptr{Int32}, Ptr{UInt8}, Ptr{Int32}, Ptr{Float64},
+         Ptr{Float64}, Ptr{Int32}, Int32, Ptr{Float64}, Int32, Float64, Int32, Int32, Float64, Int32, Float64, Int32, Ptr{UInt64}, Int32,
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}),
+        eng.ptr, length(series), pt_off, ts, xs, P, sidx, op_off, ops, prm_off, z, zn, cls, 3, tfr, 0, jitter, n_hmc,
+        get(hmc_config, :L_param, 10), get(hmc_config, :eps_param, .02), infer_noise ? get(hmc_config, :L_noise, 10) : 0,
+        get(hmc_config, :eps_noise, .02), get(hmc_config, :n_exit, n_hmc), sd, 0, oz, ozn, oprm, onz, lp, counts, info, C_NULL))
+    moved = GP.Node[node_from_flat(ops[op_off[p] + 1:op_off[p + 1]], oprm[prm_off[p] + 1:prm_off[p + 1]]) for p in 1:P]
+    return moved, onz, lp, counts, info
+end
+
 "Forecasts of many short series in one fused launch (agp_predict_series_batch): `logpdf_series_batch`'s predictive twin, same
 series / particle arguments and statelessness.  `queries[s]` holds series `s`'s own query times; particle `p` predicts on
 `series[series_index[p]]` (1-based): mean = K21 K11^-1 x, var = diag(K22 - K21 K11^-1 K12) + noise_pred[p] (`nothing`: the

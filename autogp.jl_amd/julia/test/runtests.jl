@@ -318,6 +318,32 @@ kernels() = GP.Node[
         @test eng.n_max == 700      # the resident series is untouched
     end
 
+    @testset "many short series: HMC rejuvenation in one call (stateless)" begin
+        ks = kernels()
+        sers = [(ts[1:n], xs[1:n]) for n in (17, 144)]
+        nodes = GP.Node[]; sidx = Int[]
+        for s in eachindex(sers), k in ks
+            push!(nodes, k); push!(sidx, s)
+        end
+        nz = fill(noise, length(nodes))
+        seeds = collect(1:length(nodes))
+        cfg = Dict(:L_param => 3, :L_noise => 3)
+        moved, nz1, lp, counts, info = H.mcmc_parameters_series_batch(eng, sers, nodes, nz, sidx, 3, seeds; hmc_config = cfg)
+        @test all(info .== 0) && all(counts[2, :] .== 3)
+        lp_v, _ = H.logpdf_series_batch(eng, sers, moved, nz1, sidx)
+        @test lp == lp_v                                        # the value entry's bits at the moved state
+        for (p, (k, s)) in enumerate(zip(moved, sidx))          # ... and the reference's own score there
+            t, x = sers[s]
+            @test abs(lp[p] - ref_logpdf(k, nz1[p], t, x)) <= 1e-8 * max(1.0, abs(lp[p]))
+            @test H.structure(k) == H.structure(nodes[p])
+        end
+        again = H.mcmc_parameters_series_batch(eng, sers, nodes, nz, sidx, 3, seeds; hmc_config = cfg)
+        @test again[3] == lp && again[2] == nz1                 # a particle's chain depends on its seed and inputs only
+        same, nz0, lp0, c0, _ = H.mcmc_parameters_series_batch(eng, sers, nodes, nz, sidx, 0, seeds)
+        @test all(c0 .== 0) && all(abs.(nz0 .- nz) .<= 1e-12)
+        @test eng.n_max == 700      # the resident series is untouched
+    end
+
     @testset "Gen: value and gradient through gp_marginal_flat; HMC reuses the value call's factor" begin
         k0 = GP.Linear(0.1, 0.3, 0.7) + GP.Periodic(0.96, 0.21, 1.1) * GP.SquaredExponential(0.47, 0.8)
         ops = H.structure(k0)

@@ -33,6 +33,50 @@ def transform_param(field, z):                        # src/Model.jl:35-49
     return transform_log_normal(z)                    # :period and wildcard share (-1.5, 1)
 
 
+# GPConfig.prior (src/GP.jl:1130-1137): the transform of every numeric parameter by the name of its field
+DEFAULT_PRIOR = {"wildcard": {"mu": -1.5, "sigma": 1.0}, "period": {"mu": -1.5, "sigma": 1.0},
+                 "gamma": {"mu": 0.0, "sigma": 1.0, "scale": 2.0}}
+HMC_CLASS_WILDCARD, HMC_CLASS_PERIOD, HMC_CLASS_GAMMA, HMC_CLASS_FIXED = 0, 1, 2, -1
+HMC_FIELDS = {gp.OP_WN: ("value",), gp.OP_CONST: ("value",), gp.OP_LIN: ("intercept", "bias", "amplitude"),
+              gp.OP_SE: ("lengthscale", "amplitude"), gp.OP_GE: ("lengthscale", "gamma", "amplitude"),
+              gp.OP_PER: ("lengthscale", "period", "amplitude"), gp.OP_CP: ("location", "scale")}
+
+
+def hmc_transform_table(prior=None):
+    """tf[3][3] = (mu, sigma, scale) of agp_hmc_series_batch for the classes wildcard, period, gamma (scale 0: log-normal)."""
+    pr = DEFAULT_PRIOR if prior is None else prior
+    return np.array([[pr["wildcard"]["mu"], pr["wildcard"]["sigma"], 0.0], [pr["period"]["mu"], pr["period"]["sigma"], 0.0],
+                     [pr["gamma"]["mu"], pr["gamma"]["sigma"], pr["gamma"]["scale"]]], dtype=np.float64)
+
+
+def hmc_classes(node):
+    """The transform class of every numeric parameter of a kernel tree, in the order of gp.encode(node)[1]: the field's name decides
+    (transform_param); a ChangePoint's scale is FIXED (src/Model.jl:121)."""
+    out = []
+    for nd in gp.unroll(node):
+        for f in HMC_FIELDS.get(nd.op, ()):
+            out.append(HMC_CLASS_GAMMA if f == "gamma" else HMC_CLASS_PERIOD if f == "period"
+                       else HMC_CLASS_FIXED if (nd.op == gp.OP_CP and f == "scale") else HMC_CLASS_WILDCARD)
+    return np.array(out, dtype=np.int32)
+
+
+def hmc_transform(z, cls, tf):
+    """theta of latent z under class cls (src/Model.jl:24-29); a FIXED slot holds the value itself."""
+    if cls < 0:
+        return float(z)
+    mu, sigma, scale = tf[cls]
+    x = mu + sigma * z
+    return math.exp(x) if scale == 0.0 else scale / (1.0 + math.exp(-x))
+
+
+def hmc_untransform(theta, cls, tf):
+    """untransform_param (src/Model.jl:27-33): the latent z of a parameter value."""
+    if cls < 0:
+        return float(theta)
+    mu, sigma, scale = tf[cls]
+    return (math.log(theta) - mu) / sigma if scale == 0.0 else (math.log(theta / (scale - theta)) - mu) / sigma
+
+
 def idx_to_depth(idx):                                # src/GP.jl:1141
     return 1 + int(math.floor(math.log2(idx)))
 

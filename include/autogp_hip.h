@@ -153,6 +153,58 @@ int agp_logpdf_grad_series_batch(agp_ctx* ctx, int32_t S, const int64_t* pt_off 
                                  double* out_logpdf /* P */, double* out_grad /* prm_off[P] */,
                                  double* out_grad_noise /* P */, int32_t* out_info /* P */);
 
+/* HMC rejuvenation of many short series in one call: rejuvenate_particle_parameters (src/inference_smc_anneal_data.jl:33-76) for every
+ * (series, particle) pair — per iteration one Gen.hmc move on all numeric kernel parameters, then one on the noise.  One workgroup
+ * runs the whole chain of a particle: every evaluation is agp_logpdf_grad_series_batch's kernel body in a loop, with the state in LDS.
+ * Series, program and info conventions are those of agp_logpdf_series_batch; there is no prm / noise argument — the state is latent.
+ *
+ * STATE.  Every moving parameter is z ~ N(0, 1) and theta = transform(z) (src/Model.jl:24-49).  tf[C][3] = (mu, sigma, scale) is the
+ * table of transform classes: scale == 0 is log-normal, theta = exp(mu + sigma z); scale > 0 is logit-normal,
+ * theta = scale / (1 + exp(-(mu + sigma z))).  prm_class[prm_off[P]] gives every caller parameter its class; a value < 0 means FIXED:
+ * the slot of z holds the parameter value itself, it is not moved, has no prior term and comes back bit-identical (the reference's
+ * ChangePoint scale).  noise = transform(z_noise[p]; tf[noise_class]) + noise_jitter (the reference's JITTER, 1e-5).
+ * TARGET.  U = logpdf(xs_s; theta, noise) - 1/2 sum_selected z^2;  dU/dz_i = -z_i + (d logpdf / d theta_i)(d theta_i / d z_i), with
+ * d theta / d z = sigma theta (log-normal), sigma theta (1 - theta / scale) (logit-normal), sigma (noise - noise_jitter) (noise).
+ * ONE MOVE (Gen.hmc): value and gradient at the current state; momenta m; K0 = -1/2 sum m^2; L times { m += (eps/2) g; z += eps m;
+ * value and gradient; m += (eps/2) g }; alpha = (U_new - U_0) + (K_new - K_0); accepted iff log u < alpha.  The parameter move
+ * selects every parameter of class >= 0 (L_param, eps_param), the noise move z_noise alone (L_noise, eps_noise; skipped when
+ * L_noise == 0).  A trajectory on which a pivot fails, or the value, a gradient component of the selection or a transformed parameter
+ * is not finite, is rejected (alpha = -inf) and counted as not positive definite.
+ * ITERATIONS.  i = 0 .. n_hmc - 1: parameter move, noise move, exit check — the particle stops after n_exit consecutive rejected
+ * parameter moves (n_exit <= 0: never); the noise move of the stopping iteration still runs.  A particle without a moving parameter
+ * makes no parameter move and its rejection counter never advances.
+ * RANDOMNESS.  Philox4x64-10 under the key (seeds[p], 0), counter (c0 = block, c1 = i, c2 = move: 0 parameters / 1 noise,
+ * c3 = 0x484D43).  The momentum of the k-th selected coordinate, in caller order, is ndtri(uniform(word k % 4 of block k / 4)); u is
+ * uniform(word 0 of block 2^32) (uniform as in agp_predict_sample_batch).  Not Julia's stream.  A particle's chain depends on its
+ * seed and its own inputs only: not on the batch, the order, copies, or how the call is split into launches.
+ *
+ * OUTPUTS.  out_z (layout prm_off), out_z_noise[P]: the final state.  out_prm: the transformed parameters of the final state in the
+ * caller's order (fixed slots copied), out_noise[P].  out_logpdf[p] is bit-identical to what agp_logpdf_series_batch returns for
+ * (out_prm, out_noise).  out_counts[P][4]: parameter moves accepted, parameter moves tried, noise moves accepted, trajectories
+ * rejected as not positive definite.  out_trace[P][n_hmc][2][2] (or NULL): (alpha, log u) of every move, NaN for a move not made.
+ * INITIAL STATE NOT POSITIVE DEFINITE: out_info[p] = k, out_logpdf[p] = NaN, out_z / out_z_noise the inputs, out_prm / out_noise their
+ * transforms, no move; the other particles are untouched.  n_hmc == 0: the transformed inputs and their log-density.  A particle on
+ * an EMPTY series is returned unmoved (transformed inputs, logpdf 0): moves under the prior alone are not made.  P == 0 is AGP_OK.
+ * flags: bit 0 (measurement) makes noise moves run the whole gradient pass instead of d/d noise = 1/2 (alpha'alpha - |L^-T|_F^2).
+ * The WHOLE call is rejected with
+ *   AGP_ERR_ARG: everything agp_logpdf_grad_series_batch lists; a null output other than out_trace; a class index >= C (names the
+ *     particle); a class with sigma <= 0 or scale < 0; noise_class outside [0, C); negative n_hmc, L_param, L_noise, eps_param, eps_noise;
+ *   AGP_ERR_PROGRAM (names the particle): a malformed program, a tree of more than 64 nodes, or a particle whose LDS need under the
+ *     HMC kernel's map exceeds 160 KiB: the gradient kernel's map plus six doubles per parameter (the caller-order vector, z, saved z,
+ *     momentum, gradient, class and slot map), the class table and 32 doubles of chain state.  At AGP_SERIES_MAX_N points a chain of 4
+ *     ChangePoint nodes still fits and one of 5 does not, as in the gradient entry.
+ * Stateless and re-entrant like the other series entries. */
+int agp_hmc_series_batch(agp_ctx* ctx, int32_t S, const int64_t* pt_off /* S+1 */, const double* ts, const double* xs,
+                         int32_t P, const int32_t* series /* P */,
+                         const int32_t* op_off, const uint8_t* ops, const int32_t* prm_off,
+                         const double* z /* prm_off[P] */, const double* z_noise /* P */, const int32_t* prm_class /* prm_off[P] */,
+                         int32_t C, const double* tf /* C x 3 */, int32_t noise_class, double noise_jitter,
+                         int32_t n_hmc, int32_t L_param, double eps_param, int32_t L_noise, double eps_noise, int32_t n_exit,
+                         const uint64_t* seeds /* P */, int32_t flags,
+                         double* out_z /* prm_off[P] */, double* out_z_noise /* P */, double* out_prm /* prm_off[P] */,
+                         double* out_noise /* P */, double* out_logpdf /* P */, int32_t* out_counts /* P x 4 */,
+                         int32_t* out_info /* P */, double* out_trace /* P x n_hmc x 2 x 2, or NULL */);
+
 /* Forecasts of many short series in one call: agp_logpdf_series_batch's predictive twin (predict / predict_mvn, src/api.jl:497-596, on
  * the predictive of src/GP.jl:731-758) for callers that hold one model per short series.  The workgroup that has just factored
  * K11 = K_p(ts_s) + noise[p] I in LDS evaluates the cross-covariance K21 at the series' own query times 16 at a time and solves it
