@@ -9,7 +9,7 @@ from .gp import (Node, LeafNode, BinaryOpNode, WhiteNoise, Constant, Linear, Squ
 from .engine import (GPEngine, GPEngineMulti, shard_range, shard_plan, probe_lattice, probe_program, logpdf_grad_batch_multi, predict_batch_multi, AGPError, PosDefException, load_library, LIB_PATH, EXPORTED_SYMBOLS,
                      compute_cov_matrix_vectorized, eval_cov, mvnormal_logpdf, MvNormal, quantile, infer_gp_sum, predict_proba,
                      predict_quantile, predict_quantile_multi, raw_components, predict_mvn_sum, predict_sum, predict_rand,
-                     MixtureModel, predict_mvn, pack_series, series_call_args, pack_queries, SERIES_MAX_N,
+                     MixtureModel, predict_mvn, pack_series, series_call_args, pack_queries, SERIES_MAX_N, LONG_SERIES_MAX_N, LONG_SERIES_ALL,
                      pack_series_mixture, predict_quantile_series, SeriesBand, pack_heldout, predict_proba_series, SeriesScores,
                      predict_rand_series, predict_mvn_series, SeriesSamples, SeriesMixtureModel, predict_sum_series, SeriesSums,
                      mcmc_parameters_series, with_params)

@@ -564,6 +564,36 @@ struct SeriesQuantArgs {
   double* out_var;
 };
 
+// Long-series value kernel (k_long_series_logpdf, agp_long_series_kernel.hpp, agp_logpdf_long_series_batch): one workgroup per
+// particle of a series of up to LONG_SERIES_MAX_N points; the factor lives in an HBM workspace, LDS holds vectors, tables and ONE
+// diagonal block.  The value kernel's arguments and the workspace: workgroup b of a launch owns ws[b * ws_stride ..), ws_stride >=
+// 256 nb (nb + 1) / 2 doubles for every particle of the launch.
+constexpr int LONG_SERIES_MAX_N = 512;            // == AGP_LONG_SERIES_MAX_N of the C ABI (agp_series.hip checks)
+constexpr int LONG_SIG_STRIDE = 512;              // entries of one per-point table: the whole series, indexed by the point's position
+struct LongSeriesArgs : SeriesArgs {
+  double* ws;
+  long long ws_stride;       // doubles per workgroup
+};
+// LDS map of one workgroup, in doubles, from the particle's own sizes alone:
+//   Wl[256] | dblk[256] | tpt[np] | rvec[np] | avec[np] | ldg[np] | etab[128] | prm[n_prm + 2, even] | ops[n_ops ints, even] | sig[n_cp][512]
+// Wl = inverse of the current diagonal block, dblk = that block, ldg = 2 log L_ii per row.  At 512 points: 4 KiB + 16 KiB + 1 KiB
+// + the program + 4 KiB per ChangePoint node — 61 KiB beside 10 nodes (two workgroups share a CU); the 160 KiB one workgroup may
+// declare hold 34 nodes beside a small program.
+struct LongSeriesLds {
+  int nb, np, o_dblk, o_tpt, o_rvec, o_avec, o_ldg, o_etab, o_prm, o_ops, o_sig, total;      // offsets and total in doubles
+};
+__host__ __device__ inline LongSeriesLds long_series_lds(int n, int n_ops, int n_prm, int n_cp) {
+  LongSeriesLds m;
+  m.nb = (n + BS - 1) / BS; m.np = m.nb * BS;
+  m.o_dblk = 256; m.o_tpt = 512; m.o_rvec = m.o_tpt + m.np; m.o_avec = m.o_rvec + m.np; m.o_ldg = m.o_avec + m.np;
+  m.o_etab = m.o_ldg + m.np;
+  m.o_prm = m.o_etab + 128;
+  m.o_ops = m.o_prm + ((n_prm + 3) & ~1);
+  m.o_sig = m.o_ops + (((n_ops + 1) / 2 + 1) & ~1);
+  m.total = m.o_sig + n_cp * LONG_SIG_STRIDE;
+  return m;
+}
+
 // Arguments of the probe instantiation k_series_logpdf<D, true> (agp_debug_series_factor): caller matrices of ONE size take the place
 // of series, programs and noise; the LDS map is series_lds(n, 0, 0, 0); workgroup b factors matrix b.
 struct SeriesProbeArgs {

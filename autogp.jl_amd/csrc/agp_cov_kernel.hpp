@@ -247,8 +247,9 @@ __device__ __forceinline__ void combine_pair(const int o, const double (&a)[E], 
 
 // Evaluate the program at E (row, column) pairs.  All arrays are statically indexed registers.  lag: the tile's lag tables
 // (after the per-point tables); etab: LDS copy of fm::c_exp_tab (fm::exp_t, 11 fp64 operations instead of exp_f's 21).
-// REC: `prm` holds the caller's node records (stage_node_records) and `ops` is not read.
-template <int D, int E, int GEMODE = 0, bool REC = false, typename OpT>
+// REC: `prm` holds the caller's node records (stage_node_records) and `ops` is not read.  SIGSTRIDE: entries of one per-point table
+// (256 everywhere but in the long-series kernel, whose tables hold up to 512 points: agp_long_series_kernel.hpp).
+template <int D, int E, int GEMODE = 0, bool REC = false, int SIGSTRIDE = 256, typename OpT>
 __device__ __forceinline__ void eval_program(const ProgHdr& h, const OpT* __restrict__ ops,
                                              const double* __restrict__ prm, const double* sig,
                                              const double (&tr)[E], const double (&tc)[E],
@@ -276,7 +277,7 @@ __device__ __forceinline__ void eval_program(const ProgHdr& h, const OpT* __rest
       // carry two doubles of tail padding — and picked by opcode afterwards
       const double p0 = REC ? ra.x : prm[q], p1 = REC ? ra.y : prm[q + 1], p2 = REC ? rb.x : prm[q + 2];
       double v[E];
-      eval_leaf<E, GEMODE>(o, p0, p1, p2, sig + cpi * 256, lag + li * lstride, tr, tc, ri, ci, lt, etab, v, rk, cb);
+      eval_leaf<E, GEMODE>(o, p0, p1, p2, sig + cpi * SIGSTRIDE, lag + li * lstride, tr, tc, ri, ci, lt, etab, v, rk, cb);
       if (o == OP_SEL) ++cpi;
       if (o == OP_LAG) ++li;
 #pragma unroll
@@ -287,7 +288,7 @@ __device__ __forceinline__ void eval_program(const ProgHdr& h, const OpT* __rest
       for (int e = 0; e < E; ++e) st[0][e] = v[e];
     } else {
       // ---------------- binary: combine st[1] (first evaluated) and st[0], pop ----------------
-      combine_pair<E>(o, st[1], st[0], sig + cpi * 256, ri, ci);
+      combine_pair<E>(o, st[1], st[0], sig + cpi * SIGSTRIDE, ri, ci);
       if (o != OP_PLUS && o != OP_TIMES) ++cpi;
 #pragma unroll
       for (int d = 1; d < D - 1; ++d)

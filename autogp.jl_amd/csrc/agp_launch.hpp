@@ -2,6 +2,7 @@
 //   agp_kernels.hip         covariance evaluation + factorisation + the small service kernels
 //   agp_kernels_grad.hip    gradient sweep (L^-T chains, K^-1 tiles, spectra, contractions)
 //   agp_kernels_series.hip  small-matrix value kernel and its value-and-gradient twin (one workgroup per particle of a short series)
+//   agp_kernels_long_series.hip  long-series value kernel (one workgroup per particle of a series of up to 512 points, factor in HBM)
 // Every template instantiation lives behind one of these plain functions, so the units compile in parallel and the
 // function attributes (dynamic-LDS ceilings) are set on the copies that are actually launched.
 #pragma once
@@ -101,5 +102,11 @@ hipError_t launch_series_predict_sample(hipStream_t st, const SeriesSampleArgs& 
 hipError_t launch_series_sample_fill(hipStream_t st, const SeriesSampleFillArgs& a);
 // its probe instantiation on caller matrices: workgroup b factors matrix b of `grid`, lds_bytes = series_lds(sa.n, 0, 0, 0).total doubles
 hipError_t launch_series_probe(hipStream_t st, const SeriesProbeArgs& sa, int grid, size_t lds_bytes);
+
+// ---- agp_kernels_long_series.hip -------------------------------------------------------------------------------------
+hipError_t kernels_init_long_series();   // raises the dynamic-LDS ceiling of k_long_series_logpdf to the whole 160 KiB (once, agp_init)
+// long-series value kernel: one workgroup per entry of la.wg (`grid` of them), each with la.ws_stride doubles of la.ws for its factor;
+// evaluation-stack depth 4 / 8, lds_bytes = the largest long_series_lds total of the launch's particles
+hipError_t launch_long_series_logpdf(hipStream_t st, const LongSeriesArgs& la, int grid, int depth, size_t lds_bytes);
 
 }  // namespace agp

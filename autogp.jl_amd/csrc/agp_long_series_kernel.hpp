@@ -1,0 +1,321 @@
+// Long-series value kernel: log N(xs_s; 0, K_p(ts_s) + noise_p I) of one particle on one series of 1 <= n <= LONG_SERIES_MAX_N = 512
+// points by ONE workgroup (agp_logpdf_long_series_batch, agp_series.hip) — the value entry of the many-series family above the
+// short kernels' cap (agp_series_kernel.hpp: 176 points, where the packed blocks stop fitting into one workgroup's LDS).  At 512
+// points the lower triangle of L is 528 blocks of 2 KiB (1.03 MiB): the factor lives in a per-workgroup HBM workspace in the family's
+// packed layout — block (rb, cb) column-major at blk_idx(rb, cb) * 256 — and the factorisation runs LEFT-LOOKING by 16-wide block
+// columns, so a block is written once, finished, and afterwards only read.
+//
+// k_long_series_logpdf<D> (256 threads, D = depth of the evaluation stack, 4 or 8), per workgroup:
+//   1. ts, xs of the particle's series, its compiled program and parameters -> LDS (series_body's stage 1);
+//   2. per-point tables: sigma_cp of every ChangePoint node at all points of the series, LONG_SIG_STRIDE = 512 entries per node
+//      (eval_program's SIGSTRIDE; every other kernel keeps its 256);
+//   3. per block column j = 0 .. nb - 1, nb = ceil(n / 16); wave w owns the block rows ib >= j with ib % 4 == w, at most 8, their
+//      16 x 16 accumulators in registers from (b) to (e):
+//      (a) K(ib, j) + noise I by the general evaluator (eval_program<D, 4, 0>) on the short kernel's lane map, which is the MFMA
+//          accumulator layout — lane (i = l % 16, q = l / 16), register r <-> element (i, 4 r + q); rows / columns past n are
+//          identity (cov_finalize).  The block goes to its own slot of the workspace and the same lanes load it back as the
+//          accumulator: held in registers across the evaluator's code, eight accumulators spilled (13 / 48 VGPRs at D = 4 / 8);
+//          2 KiB out and in per block beside the j blocks stage (b) reads for it;
+//      (b) for k < j: acc(ib) -= L(ib, k) L(j, k)' on v_mfma_f64_16x16x4, both operands straight from the workspace in operand
+//          layout (blk[64 s4 + l]: 512 contiguous bytes per wave and slice); L(j, k) is loaded once per wave and k, the wave's up to
+//          eight chains are independent (long_update: one loop body per number of rows, the next step's operands prefetched);
+//      (c) the wave that owns row j puts S(j, j) into LDS and factors it (factor16 on a one-block triangle: L(j, j) in place, its
+//          inverse in Wl); barrier;
+//      (d) panel L(ib, j) = S(ib, j) W' from the registers (lds_chol_steps' stage (b)) -> workspace, L(j, j) -> workspace;
+//          alpha_j = W r_j with one refinement step against L(j, j) (lds_chol_steps' statements) and 2 log L_ii of the block's
+//          rows, by 16 lanes of wave 3; barrier;
+//      (e) r_ib -= L(ib, j) alpha_j from the registers, the four lane groups of a row in the order ((q0 + q1) + q2) + q3.
+//      Two workgroup barriers per block column are all the ordering the workspace needs: every block is written and read by the
+//      same workgroup on one CU, nothing crosses workgroups.  No look-ahead: while one wave factors the diagonal block the other
+//      three wait; a second workgroup on the CU fills the gap (not measured against a look-ahead variant).
+//   4. out_logpdf[p] = -(n log 2 pi + 2 sum log L_ii + alpha'alpha) / 2, both sums in a fixed order; on a bad pivot NaN and
+//      out_info[p] = the first non-positive pivot, 1-based (each wave keeps the first it saw; the smallest is the first).
+// A particle's bits depend on its own series, program, parameters and noise only: the LDS map (long_series_lds, agp_args.hpp) is a
+// function of the particle's own sizes, the workspace is the workgroup's own, no value crosses workgroups.
+//
+// LDS: Wl and the diagonal block 4 KiB, ts / r / alpha / log-diagonal 4 x 8 np B (16 KiB at 512), exponential table 1 KiB, the
+// program, 4 KiB per ChangePoint node: 61 KiB beside 10 nodes, so two workgroups share a CU; one workgroup's 160 KiB hold 34 nodes
+// beside a small program (the host refuses what does not fit).
+// Registers (hipcc -Rpass-analysis=kernel-resource-usage, gfx950), D = 4 and D = 8 alike: 255 VGPRs, no AGPRs, 0 VGPRs spilled,
+// scratch 0 bytes per lane, 2 waves per SIMD (__launch_bounds__(256, 2)); 150 SGPRs are kept in VGPR lanes, as 93 to 114 are in the
+// family's predictive kernels.
+#pragma once
+#include "agp_common.hpp"
+#include "agp_args.hpp"
+#include "agp_cov_kernel.hpp"
+#include "agp_lds_chol.hpp"         // mfma, blk_idx, factor16, readlane_d
+
+namespace agp {
+
+constexpr int LONG_ROWS_PER_WAVE = LONG_SERIES_MAX_N / 16 / 4;      // block rows one wave owns at most
+static_assert(LONG_ROWS_PER_WAVE * 64 == LONG_SERIES_MAX_N, "the cap is whole rounds of the four waves");
+static_assert(LONG_SIG_STRIDE >= LONG_SERIES_MAX_N, "a per-point table holds the whole series");
+
+// sigma_cp (src/GP.jl:481-483) of every ChangePoint node at time t -> entry `slot` of the node's table (series_sigma_cp's arithmetic)
+__device__ __forceinline__ void long_sigma_cp(const ProgHdr& h, const int* ops, const double* prm, double* sig, int slot, double t) {
+  int q = 0, c = 0;
+  for (int ip = 0; ip < h.n_ops; ++ip) {
+    const int o = ops[ip];
+    if (o == OP_CP || o == OP_CP_SWAP) {
+      const double loc = prm[q], sc = prm[q + 1];
+      sig[c * LONG_SIG_STRIDE + slot] = 0.5 * (1.0 + tanh((loc - t) / sc));
+      ++c;
+    }
+    q += prm_count(o);
+  }
+}
+
+// Stage (b) of one wave with C block rows ib0, ib0 + 4, ..: acc(u) -= sum_{k < j} L(ib0 + 4 u, k) L(j, k)', j > 0.  The C chains are
+// independent, interleaved slice by slice as in lds_chol_steps; every element is one chain over k in ascending order.  C <= 6: the
+// operands of step k + 1 are on their way from the workspace while the MFMAs of step k run (the last step loads its own operands
+// again).  With seven or eight rows a second operand set does not fit the 256 registers beside the accumulators (it spilled 10
+// VGPRs); those chains are at most eight steps long.  Tried and dropped: a ring of 6 / 4 / 3 operand sets for waves with one to three
+// rows (the late columns' long chains) measured the same — kernels 1.214 against 1.215 ms at 64 series x 442 points x 8 particles,
+// 0.716 against 0.704 ms for one series — so the workspace's latency is not what a block column waits for: the evaluator (101
+// blocks per wave at 442 points) and the wave-serial factor16 are.  Deeper rings spilled 29 to 59 VGPRs.
+template <int C>
+__device__ __forceinline__ void long_update(d4 (&acc)[LONG_ROWS_PER_WAVE], const double* ws, int j, int ib0, int l) {
+  constexpr bool PREFETCH = C <= 6;
+  const double* la = ws + blk_idx(j, 0) * 256 + l;      // row j's blocks are consecutive
+  const double* lb[C];
+#pragma unroll
+  for (int u = 0; u < C; ++u) lb[u] = ws + blk_idx(ib0 + 4 * u, 0) * 256 + l;
+  double fa[4], fb[C][4];
+  if constexpr (PREFETCH) {
+#pragma unroll
+    for (int s4 = 0; s4 < 4; ++s4) {
+      fa[s4] = la[64 * s4];
+#pragma unroll
+      for (int u = 0; u < C; ++u) fb[u][s4] = lb[u][64 * s4];
+    }
+  }
+  for (int k = 0; k < j; ++k) {
+    if constexpr (PREFETCH) {
+      const int kn = (k + 1 < j ? k + 1 : k) * 256;
+      double na[4], nb[C][4];
+#pragma unroll
+      for (int s4 = 0; s4 < 4; ++s4) {
+        na[s4] = la[kn + 64 * s4];
+#pragma unroll
+        for (int u = 0; u < C; ++u) nb[u][s4] = lb[u][kn + 64 * s4];
+      }
+#pragma unroll
+      for (int s4 = 0; s4 < 4; ++s4)
+#pragma unroll
+        for (int u = 0; u < C; ++u) acc[u] = mfma(-fa[s4], fb[u][s4], acc[u]);
+#pragma unroll
+      for (int s4 = 0; s4 < 4; ++s4) {
+        fa[s4] = na[s4];
+#pragma unroll
+        for (int u = 0; u < C; ++u) fb[u][s4] = nb[u][s4];
+      }
+    } else {
+#pragma unroll
+      for (int s4 = 0; s4 < 4; ++s4) {
+        fa[s4] = la[k * 256 + 64 * s4];
+#pragma unroll
+        for (int u = 0; u < C; ++u) fb[u][s4] = lb[u][k * 256 + 64 * s4];
+      }
+#pragma unroll
+      for (int s4 = 0; s4 < 4; ++s4)
+#pragma unroll
+        for (int u = 0; u < C; ++u) acc[u] = mfma(-fa[s4], fb[u][s4], acc[u]);
+    }
+  }
+}
+
+template <int D>
+__global__ __launch_bounds__(256, 2) void k_long_series_logpdf(LongSeriesArgs a) {
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  constexpr int E = 4, U = LONG_ROWS_PER_WAVE;
+  const int tid = threadIdx.x, l = tid & 63, l15 = l & 15, lq = l >> 4;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);      // (on the scalar unit: which block rows a wave owns is wave-uniform control flow)
+  const int p = a.wg[blockIdx.x];
+  const int sidx = a.series[p];
+  const long long o0 = a.pt_off[sidx];
+  const int n = (int)(a.pt_off[sidx + 1] - o0);
+  if (n <= 0 || n > LONG_SERIES_MAX_N) {      // (the host answers empty series itself and refuses longer ones: never launched)
+    if (tid == 0) { a.out_lp[p] = 0.0; a.out_info[p] = 0; }
+    return;
+  }
+  const ProgHdr h = a.hdr[p];
+  const LongSeriesLds m = long_series_lds(n, h.n_ops, h.n_prm, h.n_cp);
+  const int nb = m.nb, np = m.np;
+  double* Wl = smem;
+  double* dblk = smem + m.o_dblk;
+  double* tpt = smem + m.o_tpt;
+  double* rvec = smem + m.o_rvec;
+  double* avec = smem + m.o_avec;
+  double* ldg = smem + m.o_ldg;
+  double* etab = smem + m.o_etab;
+  double* prm = smem + m.o_prm;
+  int* ops = reinterpret_cast<int*>(smem + m.o_ops);
+  double* sig = smem + m.o_sig;
+  double* ws = a.ws + (long long)blockIdx.x * a.ws_stride;
+
+  // ---- 1. inputs ----
+  for (int i = tid; i < np; i += 256) {
+    tpt[i] = a.ts[o0 + (i < n ? i : n - 1)];      // (padding points: a finite time; their entries are overwritten with identity)
+    rvec[i] = i < n ? a.xs[o0 + i] : 0.0;
+    avec[i] = 0.0;
+  }
+  if (AGP_EXP_TABLE && tid < AGP_EXP_TAB_N) etab[tid] = fm::c_exp_tab[tid];
+  for (int i = tid; i < h.n_prm + 2; i += 256) prm[i] = a.prm[h.prm_off + i];      // (the parameter buffer carries two doubles of tail padding)
+  for (int i = tid; i < h.n_ops; i += 256) ops[i] = (int)a.ops[h.op_off + i];
+  __syncthreads();
+
+  // ---- 2. per-point tables ----
+  if (h.n_cp > 0) {
+    for (int i = tid; i < np; i += 256) long_sigma_cp(h, ops, prm, sig, i, tpt[i]);
+    __syncthreads();
+  }
+
+  // ---- 3. block columns ----
+  const double noise = a.noise[p];
+  int bad = 0;           // first non-positive pivot this wave has seen (1-based index in the series), 0 = none
+  for (int j = 0; j < nb; ++j) {
+    const int ib0 = j + ((w - j) & 3);      // the wave's first block row at or below j
+    // (a) K(ib, j) + noise I -> the block's own slot of the workspace (the lanes that wrote an entry read it back below)
+    for (int ib = ib0; ib < nb; ib += 4) {
+      double tr[E], tc[E], out[E], lt[E];
+      int ri[E], ci[E];
+#pragma unroll
+      for (int e = 0; e < E; ++e) {
+        ri[e] = ib * 16 + l15;
+        ci[e] = j * 16 + lq + 4 * e;
+        tr[e] = tpt[ri[e]];
+        tc[e] = tpt[ci[e]];
+        lt[e] = 0.0;
+      }
+      eval_program<D, E, 0, false, LONG_SIG_STRIDE>(h, ops, prm, sig, tr, tc, ri, ci, lt, out, etab);
+      double* kb = ws + blk_idx(ib, j) * 256;
+#pragma unroll
+      for (int e = 0; e < E; ++e) kb[64 * e + l] = cov_finalize(out[e], ri[e], ci[e], n, np, 0, noise);
+    }
+    d4 acc[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      acc[u] = d4{0.0, 0.0, 0.0, 0.0};
+      if (ib0 + 4 * u < nb) {
+        const double* kb = ws + blk_idx(ib0 + 4 * u, j) * 256;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc[u][r] = kb[64 * r + l];
+      }
+    }
+    // (b) acc(ib) -= sum_{k < j} L(ib, k) L(j, k)': the wave's rows are u = 0 .. cnt - 1; one straight-line loop body per count
+    if (j > 0 && ib0 < nb) {
+      const int cnt = (nb - 1 - ib0) / 4 + 1;
+      switch (cnt) {
+        case 1: long_update<1>(acc, ws, j, ib0, l); break;
+        case 2: long_update<2>(acc, ws, j, ib0, l); break;
+        case 3: long_update<3>(acc, ws, j, ib0, l); break;
+        case 4: long_update<4>(acc, ws, j, ib0, l); break;
+        case 5: long_update<5>(acc, ws, j, ib0, l); break;
+        case 6: long_update<6>(acc, ws, j, ib0, l); break;
+        case 7: long_update<7>(acc, ws, j, ib0, l); break;
+        default: long_update<8>(acc, ws, j, ib0, l); break;
+      }
+    }
+    // (c) the diagonal block: the wave that owns row j holds it in acc[0]
+    if (w == (j & 3)) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) dblk[64 * r + l] = acc[0][r];
+      factor16<false>(dblk, Wl, nullptr, 0, j * 16, bad, l);
+    }
+    __syncthreads();
+    // (d) panel L(ib, j) = S(ib, j) W' -> workspace; alpha_j, 2 log L_ii
+    {
+      double fw[4];
+#pragma unroll
+      for (int s4 = 0; s4 < 4; ++s4) fw[s4] = Wl[64 * s4 + l];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int ib = ib0 + 4 * u;
+        if (ib > j && ib < nb) {
+          d4 x = d4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+          for (int s4 = 0; s4 < 4; ++s4) x = mfma(fw[s4], acc[u][s4], x);
+          acc[u] = x;
+          double* lb = ws + blk_idx(ib, j) * 256;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) lb[64 * r + l] = x[r];
+        }
+      }
+      if (w == (j & 3)) {
+        double* lb = ws + blk_idx(j, j) * 256;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) lb[64 * r + l] = dblk[64 * r + l];
+      }
+    }
+    if (w == 3 && l < 16) {
+      // alpha_j = W r_j, then ONE step of refinement against the block itself (lds_chol_steps' statements)
+      double wr[16];
+#pragma unroll
+      for (int q = 0; q < 16; ++q) wr[q] = Wl[q * 16 + l];
+      double t0 = 0.0, t1 = 0.0;
+#pragma unroll
+      for (int q = 0; q < 16; q += 2) {
+        t0 = fma(wr[q], rvec[j * 16 + q], t0);
+        t1 = fma(wr[q + 1], rvec[j * 16 + q + 1], t1);
+      }
+      const double a0 = t0 + t1;
+      double r0 = rvec[j * 16 + l], r1 = 0.0;
+#pragma unroll
+      for (int q = 0; q < 16; q += 2) {
+        r0 = fma(-dblk[q * 16 + l], readlane_d(a0, q), r0);
+        r1 = fma(-dblk[(q + 1) * 16 + l], readlane_d(a0, q + 1), r1);
+      }
+      const double rho = r0 + r1;
+      double c0 = 0.0, c1 = 0.0;
+#pragma unroll
+      for (int q = 0; q < 16; q += 2) {
+        c0 = fma(wr[q], readlane_d(rho, q), c0);
+        c1 = fma(wr[q + 1], readlane_d(rho, q + 1), c1);
+      }
+      avec[j * 16 + l] = a0 + (c0 + c1);
+      ldg[j * 16 + l] = 2.0 * log(dblk[17 * l]);      // (padding rows: log 1)
+    }
+    __syncthreads();
+    // (e) r_ib -= L(ib, j) alpha_j, from the registers
+    {
+      double al[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) al[r] = avec[j * 16 + 4 * r + lq];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int ib = ib0 + 4 * u;
+        if (ib > j && ib < nb) {
+          double t = 0.0;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) t = fma(acc[u][r], al[r], t);
+          const double s = ((__shfl(t, l15) + __shfl(t, l15 + 16)) + __shfl(t, l15 + 32)) + __shfl(t, l15 + 48);
+          if (l < 16) rvec[ib * 16 + l] -= s;
+        }
+      }
+    }
+  }
+
+  // ---- 4. the value: 2 sum log L_ii and alpha'alpha, reduced in a fixed order; the first bad pivot of the four waves ----
+  if (l == 0) dblk[w] = (double)bad;      // (the last diagonal block has been consumed)
+  Wl[tid] = (tid < np ? ldg[tid] : 0.0) + (tid + 256 < np ? ldg[tid + 256] : 0.0);      // (the last inverse block likewise)
+  __syncthreads();
+  if (w == 0) {
+    double ld = (Wl[l] + Wl[l + 64]) + (Wl[l + 128] + Wl[l + 192]);
+    double ss = 0.0;
+    for (int i = l; i < np; i += 64) ss = fma(avec[i], avec[i], ss);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) { ss += __shfl_xor(ss, off); ld += __shfl_xor(ld, off); }
+    if (l == 0) {
+      int first = 0;
+      for (int k = 0; k < 4; ++k) {
+        const int b = (int)dblk[k];
+        if (b != 0 && (first == 0 || b < first)) first = b;
+      }
+      const double lp = -0.5 * ((double)n * 1.8378770664093454835606594728112 + ld + ss);
+      a.out_lp[p] = first != 0 ? __builtin_nan("") : lp;
+      a.out_info[p] = first;
+    }
+  }
+}
+
+}  // namespace agp

@@ -1,6 +1,8 @@
 // The many-series entries: many SHORT series, each with its own particles, in one call of the small-matrix kernels
 // (agp_series_kernel.hpp: one workgroup per particle, covariance + Cholesky + forward solve + value in LDS).
 //   agp_logpdf_series_batch            k_series_logpdf: the values
+//   agp_logpdf_long_series_batch       the same values for series of up to AGP_LONG_SERIES_MAX_N points: k_series_logpdf up to the short
+//                                      cap, k_long_series_logpdf (agp_long_series_kernel.hpp: the factor in an HBM workspace) above it
 //   agp_logpdf_grad_series_batch       k_series_logpdf_grad: L^-T, alpha and the contraction with dK / d theta behind the value
 //   agp_hmc_series_batch               k_series_hmc: the gradient kernel's statements in a loop — HMC moves of every particle's parameters
 //                                      and noise in the reference's latent space, the whole chain of a particle in one workgroup
@@ -31,6 +33,8 @@
 
 static_assert(SERIES_MAX_N == AGP_SERIES_MAX_N, "the kernel's cap is the C ABI's");
 static_assert(AGP_SERIES_MAX_N >= 160, "the reference's 126-, 135-, 143- and 144-point series must fit");
+static_assert(LONG_SERIES_MAX_N == AGP_LONG_SERIES_MAX_N, "the long kernel's cap is the C ABI's");
+static_assert(AGP_LONG_SERIES_MAX_N >= 442 && AGP_LONG_SERIES_MAX_N > AGP_SERIES_MAX_N, "the reference's 442-point series must fit");
 
 namespace {
 
@@ -130,7 +134,10 @@ void quant_fill_nan(const SeriesQuantOut& qo, size_t from, size_t to, int64_t nq
 #define STAGE(expr) do { if (const int rc_ = (expr)) return rc_; } while (0)
 
 // Which kernel the call launches: it chooses the LDS map, the instantiation rule and (gradient) the tape's limit.
-enum class SeriesMode { value, gradient, prediction, held_out, sum, hmc };
+// long_value: the value entry for series of up to AGP_LONG_SERIES_MAX_N points — a particle above the short cap (or every particle,
+// SeriesCall::all_long) takes k_long_series_logpdf and its map, the others are the value mode's.
+enum class SeriesMode { value, gradient, prediction, held_out, sum, hmc, long_value };
+constexpr int SERIES_LONG_CLASS = 3;      // launch classes 3, 4: k_long_series_logpdf<4 / 8> (0 .. 2: the mode's short kernels)
 
 // One call of a many-series entry: the caller's inputs and what each shared stage leaves for the later ones.
 struct SeriesCall {
@@ -138,12 +145,16 @@ struct SeriesCall {
   int32_t S; const int64_t* pt_off; const double* ts; const double* xs; Particles pp; const int32_t* series;
   const int64_t* q_off; const double* ts_pred;
   int hmc_C = 0;                     // HMC entry: transform classes (the LDS map holds their table)
+  int max_n = AGP_SERIES_MAX_N;      // the entry's cap on a series' length, and the name the refusal quotes
+  const char* max_name = "AGP_SERIES_MAX_N";
+  bool all_long = false;             // long entry: every non-empty series takes the long kernel (AGP_LONG_SERIES_ALL)
+  bool long_route(int n) const { return n > SERIES_MAX_N || (all_long && n > 0); }
   // series_classes
   Batch bt;                          // programs without any table of the resident series (no log|dt| table, no lag tables), caller's order
   std::vector<int> len;              // [P] points of the particle's series
   std::vector<size_t> need;          // [P] LDS bytes
   std::vector<int64_t> nq;           // [P] query points of the particle's series (0 without queries)
-  std::vector<int32_t> list[3][3];   // launch classes (kernel instantiation) x (LDS class), longest series first inside each
+  std::vector<int32_t> list[5][3];   // launch classes (kernel instantiation) x (LDS class), longest series first inside each
   std::vector<int32_t> wg;           // ... one behind the other in launch order; empty: nothing to launch
   std::vector<long long> ooff;       // [P + 1] with queries: out_off, the particle-major layout of the prediction
   // series_stage
@@ -183,9 +194,9 @@ int series_check_layout(agp_ctx* c, const SeriesCall& sc) {
       snprintf(buf, sizeof buf, "series %d: pt_off decreases (%lld after %lld)", (int)s, (long long)pt_off[s + 1], (long long)pt_off[s]);
       return fail(c, AGP_ERR_ARG, buf);
     }
-    if (pt_off[s + 1] - pt_off[s] > AGP_SERIES_MAX_N) {
-      snprintf(buf, sizeof buf, "series %d has %lld points, more than AGP_SERIES_MAX_N (%d)", (int)s, (long long)(pt_off[s + 1] - pt_off[s]),
-               AGP_SERIES_MAX_N);
+    if (pt_off[s + 1] - pt_off[s] > sc.max_n) {
+      snprintf(buf, sizeof buf, "series %d has %lld points, more than %s (%d)", (int)s, (long long)(pt_off[s + 1] - pt_off[s]),
+               sc.max_name, sc.max_n);
       return fail(c, AGP_ERR_ARG, buf);
     }
   }
@@ -217,9 +228,10 @@ int series_check_layout(agp_ctx* c, const SeriesCall& sc) {
 
 // LDS bytes of particle p on a series of n points (held_out — the held-out and the sampling entry —: the joint n_s + m_s points, the
 // value kernel's map): the mode's own map
-size_t series_need(SeriesMode mode, const Batch& bt, int p, int n, int hmc_C = 0) {
+size_t series_need(SeriesMode mode, const Batch& bt, int p, int n, int hmc_C = 0, bool long_route = false) {
   const ProgHdr& h = bt.hdr[(size_t)p];
-  const int m_total = mode == SeriesMode::hmc ? series_hmc_lds(n, h.n_ops, h.n_prm, h.n_cp, bt.ghdr[(size_t)p].n_ops, bt.ghdr[(size_t)p].n_prm, hmc_C).total
+  const int m_total = long_route ? long_series_lds(n, h.n_ops, h.n_prm, h.n_cp).total
+                      : mode == SeriesMode::hmc ? series_hmc_lds(n, h.n_ops, h.n_prm, h.n_cp, bt.ghdr[(size_t)p].n_ops, bt.ghdr[(size_t)p].n_prm, hmc_C).total
                       : mode == SeriesMode::gradient ? series_grad_lds(n, h.n_ops, h.n_prm, h.n_cp, bt.ghdr[(size_t)p].n_ops, bt.ghdr[(size_t)p].n_prm).total
                       : mode == SeriesMode::prediction || mode == SeriesMode::sum ? series_pred_lds(n, h.n_ops, h.n_prm, h.n_cp).total
                                                        : series_lds(n, h.n_ops, h.n_prm, h.n_cp).total;
@@ -269,7 +281,8 @@ int series_classes(agp_ctx* c, SeriesCall& sc, SeriesMode mode) {
     // n_s + m_s; nothing held out scores 0 without a launch, as an empty series does in the value entry
     if (mode == SeriesMode::held_out) sc.len[(size_t)p] = n = sc.nq[(size_t)p] > 0 ? n + (int)sc.nq[(size_t)p] : 0;
     if (n == 0 && sc.nq[(size_t)p] == 0) continue;      // (an empty series is launched for its prior predictive only)
-    const size_t need = sc.need[(size_t)p] = series_need(mode, bt, p, n, sc.hmc_C);
+    const bool lng = mode == SeriesMode::long_value && sc.long_route(n);
+    const size_t need = sc.need[(size_t)p] = series_need(mode, bt, p, n, sc.hmc_C, lng);
     if (need > (size_t)SERIES_LDS_BYTES) {
       snprintf(buf, sizeof buf, "particle %d: %d per-point tables (%s) at %d points need %zu bytes of LDS, more than the "
                "kernel's %d", p, (int)h.n_cp, mode == SeriesMode::sum ? "ChangePoint nodes and component selectors" : "ChangePoint nodes", n,
@@ -278,7 +291,7 @@ int series_classes(agp_ctx* c, SeriesCall& sc, SeriesMode mode) {
     }
     const int depth = series_stack_depth(bt, h);
     const int inst = !grad_mode ? (depth <= 4 ? 0 : 1) : bt.ghdr[(size_t)p].n_ops <= 16 && depth <= 4 ? 0 : depth <= 4 ? 1 : 2;
-    sc.list[inst][lds_class(need)].push_back(p);
+    sc.list[lng ? SERIES_LONG_CLASS + inst : inst][lds_class(need)].push_back(p);
   }
   for (auto& ld : sc.list)
     for (auto& v : ld) std::stable_sort(v.begin(), v.end(), [&](int32_t x, int32_t y) { return sc.len[(size_t)x] > sc.len[(size_t)y]; });
@@ -359,7 +372,7 @@ int series_stage(agp_ctx* c, SeriesCall& sc) {
 }
 
 // The classes in order, between the first two profiling events.  launch(wg, grid, d, lds_bytes) -> hipError_t launches the `grid`
-// particles wg[0 .. grid) of instantiation class d with the largest LDS need among them.
+// particles wg[0 .. grid) of instantiation class d with the largest LDS need among them (d >= SERIES_LONG_CLASS: the long entry's alone).
 template <class Launch> int series_launch(agp_ctx* c, SeriesCall& sc, Launch&& launch) {
   Slot* s = sc.s;
   sc.prof = c->profiling;
@@ -369,7 +382,7 @@ template <class Launch> int series_launch(agp_ctx* c, SeriesCall& sc, Launch&& l
     HIPCHK(c, hipEventRecord(sc.ev[0], sc.st));
   }
   const int32_t* wg = sc.in_map<const int32_t>(sc.o_wg);
-  for (int d = 0; d < 3; ++d)
+  for (int d = 0; d < 5; ++d)
     for (int k = 0; k < 3; ++k) {
       const std::vector<int32_t>& v = sc.list[d][k];
       if (v.empty()) continue;
@@ -430,19 +443,67 @@ int series_timing(agp_ctx* c, const SeriesCall& sc, float readout_ms = 0.f) {
   return AGP_OK;
 }
 
-int logpdf_series(agp_ctx* c, SeriesCall& sc, double* out_logpdf, int32_t* out_info) {
+// The long kernel's launches of one class: the particles hv[0 .. grid) (longest first) in chunks whose factors fit `limit` bytes of
+// workspace together — every workgroup of a chunk gets the chunk's largest triangle, that of its first particle; a chunk is never
+// empty.  f(first, count, stride in doubles) -> hipError_t.
+template <class F> hipError_t long_chunks(const SeriesCall& sc, const int32_t* hv, int grid, int64_t limit, F&& f) {
+  for (int i = 0; i < grid;) {
+    const int nb = (sc.len[(size_t)hv[i]] + BS - 1) / BS;
+    const long long stride = (long long)(nb * (nb + 1) / 2) * 256;
+    const int cnt = (int)std::max<int64_t>(1, std::min<int64_t>(grid - i, limit / (int64_t)(stride * sizeof(double))));
+    if (const hipError_t e = f(i, cnt, stride)) return e;
+    i += cnt;
+  }
+  return hipSuccess;
+}
+
+// mode value: agp_logpdf_series_batch; mode long_value: agp_logpdf_long_series_batch — the same stages, the long particles' launches
+// (classes SERIES_LONG_CLASS ..) with a workspace out of the slot's A, split where the call's workspace limit asks for it
+int logpdf_series(agp_ctx* c, SeriesCall& sc, double* out_logpdf, int32_t* out_info, SeriesMode mode = SeriesMode::value) {
   STAGE(series_check_sizes(c, sc));
   if (sc.pp.P == 0) return AGP_OK;
   STAGE(series_check_pointers(c, sc, out_logpdf && out_info));
   STAGE(series_check_layout(c, sc));
-  STAGE(series_classes(c, sc, SeriesMode::value));
+  STAGE(series_classes(c, sc, mode));
   if (sc.wg.empty()) { series_zero_values(sc, out_logpdf, out_info); return AGP_OK; }
   STAGE(series_stage(c, sc));
+  // (the workspace at the size of the call's largest chunk, before anything is launched: the launches share it in stream order)
+  const int64_t ws_limit = std::min<int64_t>(ws_limit_bytes(c), (int64_t)1 << 30);
+  {
+    size_t ws_bytes = 0;
+    const int32_t* hv = sc.wg.data();
+    for (int d = 0; d < 5; ++d)
+      for (int k = 0; k < 3; ++k) {
+        const int grid = (int)sc.list[d][k].size();
+        if (d >= SERIES_LONG_CLASS)
+          (void)long_chunks(sc, hv, grid, ws_limit, [&](int, int cnt, long long stride) {
+            ws_bytes = std::max(ws_bytes, sizeof(double) * (size_t)cnt * (size_t)stride);
+            return hipSuccess;
+          });
+        hv += grid;
+      }
+    if (ws_bytes > 0) HIPCHK(c, sc.s->A.ensure(ws_bytes));
+  }
   HIPCHK(c, sc.up.flush(sc.s->h_stage, sc.s->up_blob, sc.st));
+  bool ws_used = false;
   STAGE(series_launch(c, sc, [&](const int32_t* wg, int grid, int d, size_t lds) {
-    SeriesArgs a = sc.sa;
-    a.wg = wg;
-    return launch_series_logpdf(sc.st, a, grid, d == 0 ? 4 : 8, lds);
+    if (d < SERIES_LONG_CLASS) {
+      SeriesArgs a = sc.sa;
+      a.wg = wg;
+      return launch_series_logpdf(sc.st, a, grid, d == 0 ? 4 : 8, lds);
+    }
+    const int32_t* hv = sc.wg.data() + (wg - sc.in_map<const int32_t>(sc.o_wg));
+    return long_chunks(sc, hv, grid, ws_limit, [&](int first, int cnt, long long stride) {
+      // (NaN-poison mode: a later launch must not find an earlier one's finished blocks in the workspace)
+      if (ws_used && c->poison.active())
+        if (const hipError_t e = sc.s->A.poison_async(sc.st)) return e;
+      ws_used = true;
+      LongSeriesArgs la = {};
+      static_cast<SeriesArgs&>(la) = sc.sa;
+      la.wg = wg + first;
+      la.ws = sc.s->A.as<double>(); la.ws_stride = stride;
+      return launch_long_series_logpdf(sc.st, la, cnt, d == SERIES_LONG_CLASS ? 4 : 8, lds);
+    });
   }));
   // h_out = [logpdf | info]
   STAGE(series_fetch_values(c, sc, sc.values_bytes()));
@@ -1268,6 +1329,22 @@ int agp_logpdf_series_batch(agp_ctx* c, int32_t S, const int64_t* pt_off, const 
   return abi_guard(c, [&] {
     SeriesCall sc{S, pt_off, ts, xs, {P, op_off, ops, prm_off, prm, noise, nullptr}, series, nullptr, nullptr};
     return logpdf_series(c, sc, out_logpdf, out_info);
+  });
+}
+
+int agp_logpdf_long_series_batch(agp_ctx* c, int32_t S, const int64_t* pt_off, const double* ts, const double* xs, int32_t P,
+                                 const int32_t* series, const int32_t* op_off, const uint8_t* ops, const int32_t* prm_off, const double* prm,
+                                 const double* noise, int32_t flags, double* out_logpdf, int32_t* out_info) {
+  return abi_guard(c, [&] {
+    SeriesCall sc{S, pt_off, ts, xs, {P, op_off, ops, prm_off, prm, noise, nullptr}, series, nullptr, nullptr};
+    sc.max_n = AGP_LONG_SERIES_MAX_N; sc.max_name = "AGP_LONG_SERIES_MAX_N";
+    sc.all_long = (flags & AGP_LONG_SERIES_ALL) != 0;
+    if (c && (flags & ~AGP_LONG_SERIES_ALL) != 0) {
+      char buf[96];
+      snprintf(buf, sizeof buf, "unknown flag bits 0x%x (AGP_LONG_SERIES_ALL is the only flag)", (unsigned)(flags & ~AGP_LONG_SERIES_ALL));
+      return fail(c, AGP_ERR_ARG, buf);
+    }
+    return logpdf_series(c, sc, out_logpdf, out_info, SeriesMode::long_value);
   });
 }
 

@@ -40,10 +40,12 @@ EXPORTED_SYMBOLS = [
     "agp_debug_factor_batch", "agp_logpdf_series_batch", "agp_debug_series_factor", "agp_logpdf_grad_series_batch",
     "agp_predict_series_batch", "agp_debug_remove_factor", "agp_predict_quantile_series_batch",
     "agp_predict_logpdf_series_batch", "agp_predict_sample_series_batch", "agp_predict_sum_series_batch",
-    "agp_debug_toeplitz", "agp_debug_cov_sweep", "agp_hmc_series_batch",
+    "agp_debug_toeplitz", "agp_debug_cov_sweep", "agp_hmc_series_batch", "agp_logpdf_long_series_batch",
 ]
 COMM_ID_BYTES = 128
 SERIES_MAX_N = 176      # AGP_SERIES_MAX_N of include/autogp_hip.h: the longest series of logpdf_series_batch
+LONG_SERIES_MAX_N = 512     # AGP_LONG_SERIES_MAX_N: the longest series of logpdf_long_series_batch
+LONG_SERIES_ALL = 1         # AGP_LONG_SERIES_ALL: every non-empty series takes the long kernel
 
 
 class AGPError(RuntimeError):
@@ -107,6 +109,8 @@ def load_library(path=None):
     lib.agp_logpdf_batch.restype = C.c_int
     lib.agp_logpdf_series_batch.argtypes = [vp, C.c_int32, C.POINTER(C.c_int64), dp, dp, C.c_int32, ip, ip, u8p, ip, dp, dp, dp, ip]
     lib.agp_logpdf_series_batch.restype = C.c_int
+    lib.agp_logpdf_long_series_batch.argtypes = [vp, C.c_int32, C.POINTER(C.c_int64), dp, dp, C.c_int32, ip, ip, u8p, ip, dp, dp, C.c_int32, dp, ip]
+    lib.agp_logpdf_long_series_batch.restype = C.c_int
     lib.agp_logpdf_grad_series_batch.argtypes = [vp, C.c_int32, C.POINTER(C.c_int64), dp, dp, C.c_int32, ip, ip, u8p, ip, dp, dp, dp, dp, dp, ip]
     lib.agp_logpdf_grad_series_batch.restype = C.c_int
     lib.agp_hmc_series_batch.argtypes = [vp, C.c_int32, C.POINTER(C.c_int64), dp, dp, C.c_int32, ip, ip, u8p, ip, dp, dp, ip, C.c_int32, dp,
@@ -288,10 +292,10 @@ def _series_ctypes(packed, queries=None):
     return data + (q_off.ctypes.data_as(i64), some(ts_pred)) + particles + (_dp(noise_pred),)
 
 
-def pack_series(series):
+def pack_series(series, max_n=SERIES_MAX_N):
     """Concatenate a sequence of (ts, xs) pairs for logpdf_series_batch: (pt_off int64[S+1], ts, xs), series s at
-    [pt_off[s], pt_off[s+1]).  Raises ValueError on unequal lengths, input that is not 1-D, or a series of more than SERIES_MAX_N
-    points; a series may be empty."""
+    [pt_off[s], pt_off[s+1]).  Raises ValueError on unequal lengths, input that is not 1-D, or a series of more than max_n points
+    (SERIES_MAX_N; logpdf_long_series_batch passes LONG_SERIES_MAX_N); a series may be empty."""
     pt_off = np.zeros(len(series) + 1, dtype=np.int64)
     tss, xss = [], []
     for s, (ts, xs) in enumerate(series):
@@ -300,18 +304,19 @@ def pack_series(series):
             raise ValueError(f"series {s}: ts and xs must be vectors")
         if ts.shape != xs.shape:
             raise ValueError(f"series {s}: ts and xs must have equal lengths ({ts.shape[0]} and {xs.shape[0]})")
-        if ts.shape[0] > SERIES_MAX_N:
-            raise ValueError(f"series {s} has {ts.shape[0]} points, more than SERIES_MAX_N ({SERIES_MAX_N})")
+        if ts.shape[0] > max_n:
+            name = "LONG_SERIES_MAX_N" if max_n == LONG_SERIES_MAX_N else "SERIES_MAX_N" if max_n == SERIES_MAX_N else "max_n"
+            raise ValueError(f"series {s} has {ts.shape[0]} points, more than {name} ({max_n})")
         pt_off[s + 1] = pt_off[s] + ts.shape[0]
         tss.append(ts); xss.append(xs)
     cat = lambda parts: np.ascontiguousarray(np.concatenate(parts)) if parts else np.zeros(0)
     return pt_off, cat(tss), cat(xss)
 
 
-def series_call_args(series, nodes, noises, series_index, programs=None):
+def series_call_args(series, nodes, noises, series_index, programs=None, max_n=SERIES_MAX_N):
     """The validated arguments the two many-series entries share: (pt_off, ts, xs, (op_off, ops, prm_off, prm), P, noises, sidx).
     Raises ValueError (pack_series' checks, one noise and one series index per particle) before any library call."""
-    pt_off, ts, xs = pack_series(series)
+    pt_off, ts, xs = pack_series(series, max_n)
     programs = programs if programs is not None else _gp.encode_batch(nodes)
     P = programs[0].shape[0] - 1
     noises = _f64(noises)
@@ -578,6 +583,20 @@ class GPEngine:
         P = packed[4]
         out = np.empty(P, dtype=np.float64); info = np.empty(P, dtype=np.int32)
         self._check(self._lib.agp_logpdf_series_batch(self._ctx, *_series_ctypes(packed), _dp(out), _ip(info)))
+        _raise_first_bad(info, check)
+        return out, info
+
+    def logpdf_long_series_batch(self, series, nodes, noises, series_index, all_long=False, check=True, programs=None):
+        """agp_logpdf_long_series_batch: logpdf_series_batch for series of at most LONG_SERIES_MAX_N points — same arguments, same
+        statelessness, one call for a mixed family such as 135, 143 and 442 points.  A series of at most SERIES_MAX_N points runs in
+        logpdf_series_batch's kernel (bit-identical results); a longer one in the long-series kernel, which keeps the factor in an
+        HBM workspace (bounded by set_workspace_limit; more long particles than fit are split into several launches).  all_long:
+        every non-empty series takes the long kernel.  Returns (logpdf[P], info[P])."""
+        packed = series_call_args(series, nodes, noises, series_index, programs, max_n=LONG_SERIES_MAX_N)
+        P = packed[4]
+        out = np.empty(P, dtype=np.float64); info = np.empty(P, dtype=np.int32)
+        self._check(self._lib.agp_logpdf_long_series_batch(self._ctx, *_series_ctypes(packed), LONG_SERIES_ALL if all_long else 0,
+                                                           _dp(out), _ip(info)))
         _raise_first_bad(info, check)
         return out, info
 

@@ -220,6 +220,37 @@ function logpdf_series_batch(eng::Engine, series::Vector{<:Tuple{Vector{Float64}
     return out, info
 end
 
+"Longest series of `logpdf_long_series_batch` (AGP_LONG_SERIES_MAX_N)."
+const LONG_SERIES_MAX_N = 512
+"`flags` bit of agp_logpdf_long_series_batch: every non-empty series takes the long kernel (AGP_LONG_SERIES_ALL)."
+const LONG_SERIES_ALL = Int32(1)
+
+"`logpdf_series_batch` for series of at most `LONG_SERIES_MAX_N` points (agp_logpdf_long_series_batch): same arguments, same
+statelessness, one call for a mixed family such as 135, 143 and 442 points.  A series of at most `SERIES_MAX_N` points runs in
+`logpdf_series_batch`'s kernel (bit-identical results), a longer one in the long-series kernel, which keeps the factor in an HBM
+workspace; `all_long = true` sends every non-empty series through the long kernel.  Returns `(logpdf, info)`."
+function logpdf_long_series_batch(eng::Engine, series::Vector{<:Tuple{Vector{Float64},Vector{Float64}}}, nodes::Vector{<:GP.Node},
+                                  noises::Vector{Float64}, series_index::Vector{<:Integer}; all_long::Bool=false)
+    P = length(nodes)
+    (length(noises) == P && length(series_index) == P) || throw(ArgumentError("one noise and one series index per particle required"))
+    pt_off = Int64[0]; ts = Float64[]; xs = Float64[]
+    for (s, (t, x)) in enumerate(series)
+        length(t) == length(x) || throw(ArgumentError("series $s: ts and xs must have equal lengths"))
+        length(t) <= LONG_SERIES_MAX_N || throw(ArgumentError("series $s has $(length(t)) points, more than LONG_SERIES_MAX_N ($LONG_SERIES_MAX_N)"))
+        append!(ts, t); append!(xs, x); push!(pt_off, length(ts))
+    end
+    isempty(ts) && (push!(ts, 0.0); push!(xs, 0.0))
+    sidx = Int32[Int32(i - 1) for i in series_index]
+    op_off, ops, prm_off, prm = encode_batch(nodes)
+    out = Vector{Float64}(undef, P); info = Vector{Int32}(undef, P)
+    flags = all_long ? LONG_SERIES_ALL : Int32(0)
+    GC.@preserve pt_off ts xs sidx op_off ops prm_off prm noises out info check(eng, ccall((:agp_logpdf_long_series_batch, LIB), Cint,
+        (Ptr{Cvoid}, Int32, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Int32}, Ptr{Int32}, Ptr{UInt8}, Ptr{Int32}, Ptr{Float64},
+         Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Int32}),
+        eng.ptr, length(series), pt_off, ts, xs, P, sidx, op_off, ops, prm_off, prm, noises, flags, out, info))
+    return out, info
+end
+
 "Value and gradient of many short series in one fused launch (agp_logpdf_grad_series_batch): `logpdf_series_batch`'s twin for
 `Gen.choice_gradients` / `Gen.map_optimize` of callers that hold one model per short series.  Same arguments, same statelessness.
 Returns `(logpdf, grads, grad_noise, info)`; `grads[p]` is d logpdf / d theta in the order of `encode(kernels[p])[2]`, as in

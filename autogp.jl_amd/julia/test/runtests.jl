@@ -88,6 +88,31 @@ kernels() = GP.Node[
         @test eng.n_max == 700      # the resident series is untouched
     end
 
+    @testset "series of up to LONG_SERIES_MAX_N points in one call (stateless)" begin
+        ks = kernels()
+        sers = [(ts[1:n], xs[1:n]) for n in (0, 17, 143, H.SERIES_MAX_N, H.SERIES_MAX_N + 1, 442, H.LONG_SERIES_MAX_N)]
+        nodes = GP.Node[]; sidx = Int[]
+        for s in eachindex(sers), k in ks
+            push!(nodes, k); push!(sidx, s)
+        end
+        nz = fill(noise, length(nodes))
+        lp, info = H.logpdf_long_series_batch(eng, sers, nodes, nz, sidx)
+        la, ia = H.logpdf_long_series_batch(eng, sers, nodes, nz, sidx; all_long=true)
+        @test all(info .== 0) && all(ia .== 0)
+        for (p, (k, s)) in enumerate(zip(nodes, sidx))
+            t, x = sers[s]
+            r = isempty(t) ? 0.0 : ref_logpdf(k, noise, t, x)
+            @test relerr(lp[p], r) <= 1e-8
+            @test relerr(la[p], r) <= 1e-8
+        end
+        # up to the short cap the default routing is logpdf_series_batch's kernel: the same bits
+        short = [p for p in eachindex(nodes) if length(sers[sidx[p]][1]) <= H.SERIES_MAX_N]
+        ls, _ = H.logpdf_series_batch(eng, sers[1:4], nodes[short], nz[short], sidx[short])
+        @test lp[short] == ls
+        @test_throws ArgumentError H.logpdf_long_series_batch(eng, [(zeros(513), zeros(513))], ks[1:1], [noise], [1])
+        @test eng.n_max == 700      # the resident series is untouched
+    end
+
     @testset "many short series: held-out scores in one call (stateless)" begin
         ks = kernels()
         splits = ((0, 5), (17, 5), (126, 18), (144, 32))      # (training points, held-out points)

@@ -123,6 +123,37 @@ int agp_logpdf_series_batch(agp_ctx* ctx, int32_t S, const int64_t* pt_off /* S+
                             const int32_t* op_off, const uint8_t* ops, const int32_t* prm_off, const double* prm,
                             const double* noise, double* out_logpdf /* P */, int32_t* out_info /* P */);
 
+/* agp_logpdf_series_batch for series of up to AGP_LONG_SERIES_MAX_N = 512 points (the reference's 442-point data set beside its 135-
+ * and 143-point ones in ONE call).  Every convention is agp_logpdf_series_batch's: program encoding, noise meaning, out_info (the
+ * 1-based first non-positive pivot within the particle's own series, out_logpdf[p] NaN then), an empty series gives logpdf 0 and
+ * info 0, P == 0 is AGP_OK and touches nothing; stateless (no agp_set_data; the resident series, the factor store, the tables and
+ * every counter are neither read nor changed), re-entrant (a private stream and workspace slot per call), copies of a particle are
+ * not deduplicated, and with profiling on agp_get_timing's out[0] = out[2] = the call's kernel time.
+ * Routing: a series of at most AGP_SERIES_MAX_N points runs in agp_logpdf_series_batch's kernel and its result is bit-identical to
+ * that entry's.  A longer series runs in k_long_series_logpdf: one workgroup per particle, the Cholesky factor in a per-workgroup
+ * HBM workspace (packed 16 x 16 blocks, 1.03 MiB at 512 points), left-looking by block columns on v_mfma_f64_16x16x4, the forward
+ * solve carried along.  flags & AGP_LONG_SERIES_ALL: every non-empty series takes that kernel, whatever its length (one arithmetic
+ * for the whole family).
+ * The workspace comes from the call's slot; one launch takes at most min(agp_set_workspace_limit's value, 1 GiB) of it (the default
+ * limit likewise capped at 1 GiB: about 990 particles of 512 points) and a call with more long particles is split into several
+ * launches on its stream.  A particle's result bits depend only on its own series, program, parameters, noise and the flag — not on
+ * what else is in the call, its order, or the split.
+ * The WHOLE call is rejected, outputs untouched, with
+ *   AGP_ERR_ARG (the message names the series or particle): everything agp_logpdf_series_batch lists, the cap now
+ *     AGP_LONG_SERIES_MAX_N (the message gives the series, its length and that name); flag bits other than AGP_LONG_SERIES_ALL;
+ *   AGP_ERR_PROGRAM (names the particle): a malformed program, or one whose per-point tables do not fit the kernel's LDS at that
+ *     series' length.  The long kernel keeps 4 KiB per ChangePoint node (a 512-entry table) beside 21 KiB of vectors, tables and one
+ *     diagonal block and the program: at 512 points a chain of 10 ChangePoint nodes takes 61 KiB (two workgroups share a CU), 34
+ *     nodes beside a small program are the most 160 KiB hold, 40 are refused.
+ * Not here: gradient, forecast, held-out, sampling, decomposition and HMC twins above AGP_SERIES_MAX_N points; series beyond
+ * AGP_LONG_SERIES_MAX_N; deduplication inside a call. */
+#define AGP_LONG_SERIES_MAX_N 512
+#define AGP_LONG_SERIES_ALL 1   /* flags: every non-empty series takes the long kernel */
+int agp_logpdf_long_series_batch(agp_ctx* ctx, int32_t S, const int64_t* pt_off /* S+1 */, const double* ts, const double* xs,
+                                 int32_t P, const int32_t* series /* P */,
+                                 const int32_t* op_off, const uint8_t* ops, const int32_t* prm_off, const double* prm,
+                                 const double* noise, int32_t flags, double* out_logpdf /* P */, int32_t* out_info /* P */);
+
 /* Value AND gradient of many short series in one call: agp_logpdf_series_batch's twin for Gen.choice_gradients / Gen.map_optimize of
  * callers that hold one model per short series.  One workgroup per particle forms, behind the value and in the same LDS, L^-T in place
  * of L, alpha = K^-1 x, and contracts G = 1/2 (alpha alpha' - K^-1) with dK / d theta block by block; K^-1 is never stored and nothing
