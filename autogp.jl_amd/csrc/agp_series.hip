@@ -18,12 +18,18 @@
 // Each entry is one function, read top to bottom, over the stages they share (one SeriesCall carries what a stage leaves for the next):
 //   checks          series_check_sizes, series_check_pointers, series_check_layout (the entry's own pointer checks between them)
 //   series_classes  compile, per particle length / LDS need / evaluation stack, launch classes, workgroup order, out_off
-//   series_stage    the slot, its buffers and the uploads every mode needs (and the query side when there are queries), SeriesArgs
+//   series_stage    the slot, its buffers and the uploads every mode needs (and the query side when there are queries), SeriesArgs;
+//                   behind it series_query_args (the query side of a kernel's arguments), series_grad_tape (the gradient tape: buffers,
+//                   uploads, SeriesGradArgs) and series_stage_mix (a mixture plan's tables in sq_tab)
 //   series_launch   the class x LDS-class loop, between the profiling events; the entry passes what launches one class
-//   series_fetch_values / series_copy_values   [logpdf | info] into the head of the pinned landing zone, and out of it
-//   series_timing   agp_get_timing's slots
-// and between them the entry's own buffers, uploads, device-to-host copies and copy-out: ONE PinnedUploads::flush and ONE
-// hipStreamSynchronize per call.  Stateless: the series
+//   series_fetch / series_copy_values   [logpdf | info] and every device array the entry registered (SeriesCall::want) into the
+//                   pinned landing zone, the stream drained; the values out of it (the entry's own arrays: SeriesCall::got)
+//   series_timing   agp_get_timing's slots (the read-out span when the entry marked one: series_mark_readout)
+// What a series' mixture needs — the particle lists, the checked and padded weights — is one plan (mix_plan) for the band, the held-out
+// and the sampling entry; what is refused series by series (series_check_joint, series_y_transform) is called from each entry's own
+// loop over the series, so that the lowest series with a defect is the one reported.  An entry still owns: its pointer checks, its
+// planning, its buffers and uploads, its kernel's arguments, what it registers for read-back, and the copy-out.  ONE
+// PinnedUploads::flush and ONE hipStreamSynchronize per call.  Stateless: the series
 // travel with the call; the resident series, its tables, the factor store, the coalescer and every counter of the context are
 // neither read nor changed — only a workspace slot (stream, staging buffers) is borrowed, as in every batch entry.
 #include "agp_host.hpp"
@@ -52,13 +58,16 @@ struct SeriesQuantOut {
   double* mix_mean; double* mix_var;              // [q_off[S]], nullable
 };
 
-// What the read-out kernels index with, built and checked on the host before anything is launched or written.
-struct QuantPlan {
+// The mixtures of a call's series — what the read-out kernels index with, built and checked on the host before anything is launched
+// or written: the band's, the held-out and the sampling entry's.
+struct MixPlan {
   std::vector<long long> tab;      // [pl_off (S + 1) | w_off (S + 1) | row_off (S + 1)]
   std::vector<int32_t> plist;      // [P] the series' particles, series by series, ascending within each
-  std::vector<double> vals;        // [w (w_off[S], 0 in the padding) | slope (S) | intercept (S) | ivar (S) | q (nq)]
+  std::vector<double> vals;        // [w (w_off[S], 0 in the padding) | slope (S) | intercept (S)]; the band adds [ivar (S) | q (nq)]
   long long max_rows_el = 0;       // largest m_s Pp_s
   size_t Q = 0, R = 0, W = 0;      // q_off[S], row_off[S], w_off[S]
+  const long long* pl_off() const { return tab.data(); }
+  const long long* w_off() const { return tab.data() + tab.size() / 3; }
 };
 
 // prefixes the message a shared check has just stored with the series it was about
@@ -68,15 +77,24 @@ int fail_series(agp_ctx* c, int rc, int32_t s) {
   return fail(c, rc, "series " + std::to_string(s) + ": " + msg);
 }
 
-int quant_plan(agp_ctx* c, int32_t S, int P, const int32_t* series, const int64_t* q_off, const SeriesQuantOut& qo, QuantPlan& pl) {
-  if (qo.nq < 0) return fail(c, AGP_ERR_ARG, "negative size");
-  if (!qo.q && qo.nq > 0) return fail(c, AGP_ERR_ARG, "null q");
-  for (int64_t k = 0; k < qo.nq; ++k)
-    if (!(qo.q[k] > 0.0 && qo.q[k] < 1.0)) return fail(c, AGP_ERR_ARG, "quantile must be in (0, 1)");
-  if (!qo.x && qo.nq > 0) return fail(c, AGP_ERR_ARG, "null pointer argument (out_x)");
-  if (!qo.weights && P > 0) return fail(c, AGP_ERR_ARG, "null weights");
+// series s' (slope, intercept) — 1 and 0 where the caller gave none — checked; a refusal names the series
+int series_y_transform(agp_ctx* c, int32_t s, const double* y_slope, const double* y_intercept, double& slope, double& icpt) {
+  slope = y_slope ? y_slope[s] : 1.0;
+  icpt = y_intercept ? y_intercept[s] : 0.0;
+  const int rc = check_y_transform(c, slope, icpt);
+  return rc ? fail_series(c, rc, s) : AGP_OK;
+}
+
+// The mixture plan.  nq: outputs per query point (the band's quantiles; 0 elsewhere), for the limit on the largest output.
+// y_slope / y_intercept: the band's transforms, checked series by series in one pass with the weights — the lowest series with a
+// defect of either kind is the one refused (the other entries have checked theirs in their own loop, and pass none).  The limits
+// on w_off and on row_off — the band's rows m_s ceil(P_s / 64) 64, which only the band reads — hold for every caller: the
+// held-out and the sampling entry have always refused what the band refuses here, and go on doing so.
+int mix_plan(agp_ctx* c, int32_t S, int P, const int32_t* series, const int64_t* q_off, const double* weights, const double* y_slope,
+             const double* y_intercept, int64_t nq, MixPlan& pl) {
+  if (!weights && P > 0) return fail(c, AGP_ERR_ARG, "null weights");
   pl.Q = S > 0 ? (size_t)q_off[S] : 0;
-  if ((int64_t)pl.Q >= ((int64_t)1 << 31) || (qo.nq > 0 && (int64_t)pl.Q * qo.nq >= ((int64_t)1 << 31)))
+  if ((int64_t)pl.Q >= ((int64_t)1 << 31) || (nq > 0 && (int64_t)pl.Q * nq >= ((int64_t)1 << 31)))
     return fail(c, AGP_ERR_ARG, "nq * q_off[S] too large");
   const size_t S1 = (size_t)S + 1;
   pl.tab.assign(3 * S1, 0);
@@ -99,25 +117,35 @@ int quant_plan(agp_ctx* c, int32_t S, int P, const int32_t* series, const int64_
     pl.max_rows_el = std::max(pl.max_rows_el, m * Pp);
   }
   pl.W = (size_t)w_off[S]; pl.R = (size_t)row_off[S];
-  pl.vals.assign(pl.W + 3 * (size_t)S + (size_t)qo.nq, 0.0);
+  pl.vals.assign(pl.W + 2 * (size_t)S, 0.0);
   double* w = pl.vals.data();
   double* slope = w + pl.W;
   double* icpt = slope + S;
-  double* ivar = icpt + S;
   std::vector<double> ws;
   for (int32_t s = 0; s < S; ++s) {
-    slope[s] = qo.y_slope ? qo.y_slope[s] : 1.0;
-    icpt[s] = qo.y_intercept ? qo.y_intercept[s] : 0.0;
-    if (const int rc = check_y_transform(c, slope[s], icpt[s])) return fail_series(c, rc, s);
-    ivar[s] = 1.0 / (slope[s] * slope[s]);
+    if (const int rc = series_y_transform(c, s, y_slope, y_intercept, slope[s], icpt[s])) return rc;
     const long long Ps = pl_off[s + 1] - pl_off[s];
     if (Ps == 0) continue;
     ws.resize((size_t)Ps);
-    for (long long j = 0; j < Ps; ++j) ws[(size_t)j] = qo.weights[pl.plist[(size_t)(pl_off[s] + j)]];
+    for (long long j = 0; j < Ps; ++j) ws[(size_t)j] = weights[pl.plist[(size_t)(pl_off[s] + j)]];
     if (const int rc = check_weights(c, (int32_t)Ps, ws.data())) return fail_series(c, rc, s);
     std::copy(ws.begin(), ws.end(), w + w_off[s]);
   }
-  std::copy(qo.q, qo.q + qo.nq, ivar + S);
+  return AGP_OK;
+}
+
+// The band's plan: its own checks, its mixtures', and behind the plan's values its own — vals = [.. | ivar (S) | q (nq)]
+int quant_plan(agp_ctx* c, int32_t S, int P, const int32_t* series, const int64_t* q_off, const SeriesQuantOut& qo, MixPlan& pl) {
+  if (qo.nq < 0) return fail(c, AGP_ERR_ARG, "negative size");
+  if (!qo.q && qo.nq > 0) return fail(c, AGP_ERR_ARG, "null q");
+  for (int64_t k = 0; k < qo.nq; ++k)
+    if (!(qo.q[k] > 0.0 && qo.q[k] < 1.0)) return fail(c, AGP_ERR_ARG, "quantile must be in (0, 1)");
+  if (!qo.x && qo.nq > 0) return fail(c, AGP_ERR_ARG, "null pointer argument (out_x)");
+  if (const int rc = mix_plan(c, S, P, series, q_off, qo.weights, qo.y_slope, qo.y_intercept, qo.nq, pl)) return rc;
+  const size_t o_ivar = pl.vals.size();
+  pl.vals.resize(o_ivar + (size_t)S + (size_t)qo.nq);
+  for (int32_t s = 0; s < S; ++s) pl.vals[o_ivar + s] = 1.0 / (pl.vals[pl.W + s] * pl.vals[pl.W + s]);
+  std::copy(qo.q, qo.q + qo.nq, pl.vals.data() + o_ivar + (size_t)S);
   return AGP_OK;
 }
 
@@ -166,11 +194,16 @@ struct SeriesCall {
   SeriesArgs sa = {};                // all but wg, which every launch sets
   // series_launch
   bool prof = false; hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+  bool readout = false;              // ev[2] was recorded behind the entry's read-out kernels (series_mark_readout)
   size_t n_out() const { return ooff.empty() ? 0 : (size_t)ooff.back(); }
-  // every entry's pinned landing zone begins with [logpdf (P) | info (P)]; its own outputs follow from o_own() on
   size_t values_bytes() const { return sizeof(double) * (size_t)pp.P + sizeof(int32_t) * (size_t)pp.P; }
-  size_t o_own() const { return (values_bytes() + 7) & ~(size_t)7; }
   template <class T> T* in_map(size_t off) const { return reinterpret_cast<T*>(s->map.as<char>() + off); }
+  // series_fetch: the read-back list, PinnedUploads' mirror image.  The pinned landing zone begins with [logpdf (P) | info (P)];
+  // the device arrays the entry wants back follow in the order it asked for them, each at a multiple of 8 bytes
+  struct Back { const void* dev; size_t bytes, off; };
+  std::vector<Back> back;
+  int want(const void* dev, size_t bytes) { back.push_back({dev, bytes, 0}); return (int)back.size() - 1; }
+  template <class T> const T* got(int h) const { return reinterpret_cast<const T*>(static_cast<const char*>(s->h_out.p) + back[(size_t)h].off); }
 };
 
 // The checks, in this order, the entry's own pointer checks between the second and the third.
@@ -224,6 +257,16 @@ int series_check_layout(agp_ctx* c, const SeriesCall& sc) {
       return fail(c, AGP_ERR_ARG, buf);
     }
   return AGP_OK;
+}
+
+// the entries that factor a series' training and query points together (what: "held-out" or "query"): the joint size of series s
+int series_check_joint(agp_ctx* c, const SeriesCall& sc, int32_t s, const char* what) {
+  const long long n = sc.pt_off[s + 1] - sc.pt_off[s], m = sc.q_off[s + 1] - sc.q_off[s];
+  if (m == 0 || n + m <= AGP_SERIES_MAX_N) return AGP_OK;
+  char buf[256];
+  snprintf(buf, sizeof buf, "series %d has %lld training and %lld %s points, together more than AGP_SERIES_MAX_N (%d)", (int)s, n, m, what,
+           AGP_SERIES_MAX_N);
+  return fail(c, AGP_ERR_ARG, buf);
 }
 
 // LDS bytes of particle p on a series of n points (held_out — the held-out and the sampling entry —: the joint n_s + m_s points, the
@@ -371,6 +414,53 @@ int series_stage(agp_ctx* c, SeriesCall& sc) {
   return AGP_OK;
 }
 
+// a kernel's arguments of a staged call with queries: the SeriesArgs base and the query side
+template <class Args> void series_query_args(const SeriesCall& sc, Args& a) {
+  static_cast<SeriesArgs&>(a) = sc.sa;
+  a.q_off = sc.in_map<const long long>(sc.o_qoff);
+  a.out_off = sc.in_map<const long long>(sc.o_ooff);
+  a.ts_pred = sc.s->tt.as<double>() + 2 * sc.npts; a.noise_pred = sc.s->noise_pred.as<double>();
+}
+
+// the gradient tape of a staged call: its buffers, its uploads (into sc.up), and the arguments that name it — all of ga but the
+// gradient's outputs, which are the entry's own
+int series_grad_tape(agp_ctx* c, SeriesCall& sc, SeriesGradArgs& ga) {
+  Slot* s = sc.s;
+  const Batch& bt = sc.bt;
+  const size_t P = (size_t)sc.pp.P;
+  const struct { DevBuf& buf; const void* src; size_t bytes, slack; } parts[] = {      // (slack: bytes of the buffer behind the upload)
+      {s->ghdr, bt.ghdr.data(), sizeof(GProgHdr) * P, 0},
+      {s->gops, bt.gops.data(), bt.gops.size(), 4},
+      {s->glc, bt.glc.data(), bt.glc.size(), 4},
+      {s->grc, bt.grc.data(), bt.grc.size(), 4},
+      {s->gpoff, bt.gpoff.data(), sizeof(int32_t) * bt.gpoff.size(), sizeof(int32_t)},
+      {s->gprm, bt.gprm.data(), sizeof(double) * bt.gprm.size(), 0},
+      {s->gmap, bt.gmap.data(), sizeof(int32_t) * bt.gmap.size(), sizeof(int32_t)},
+      {s->goff, sc.pp.prm_off, sizeof(int32_t) * P, 0}};      // the particle's block in out_grad: the caller's own offsets
+  for (const auto& t : parts) {
+    HIPCHK(c, t.buf.ensure(t.bytes + t.slack));
+    sc.up.add(t.buf.p, t.src, t.bytes);
+  }
+  static_cast<SeriesArgs&>(ga) = sc.sa;
+  ga.ghdr = s->ghdr.as<GProgHdr>(); ga.gops = s->gops.as<uint8_t>(); ga.glc = s->glc.as<uint8_t>(); ga.grc = s->grc.as<uint8_t>();
+  ga.gpoff = s->gpoff.as<int32_t>(); ga.gprm = s->gprm.as<double>(); ga.gmap = s->gmap.as<int32_t>();
+  ga.out_off = s->goff.as<int32_t>();
+  return AGP_OK;
+}
+
+// a mixture plan's tables of a staged call: sq_tab = [pl_off | w_off | row_off (S + 1 each) | plist (P)], uploaded through sc.up
+struct MixTabs { const long long* pl_off; const long long* w_off; const long long* row_off; const int32_t* plist; };
+int series_stage_mix(agp_ctx* c, SeriesCall& sc, const MixPlan& mp, MixTabs& mt) {
+  Slot* s = sc.s;
+  const size_t S1 = (size_t)sc.S + 1, o_plist = sizeof(long long) * 3 * S1;
+  HIPCHK(c, s->sq_tab.ensure(o_plist + sizeof(int32_t) * (size_t)sc.pp.P));
+  sc.up.add(s->sq_tab.p, mp.tab.data(), o_plist);
+  sc.up.add(s->sq_tab.as<char>() + o_plist, mp.plist.data(), sizeof(int32_t) * (size_t)sc.pp.P);
+  mt.pl_off = s->sq_tab.as<long long>(); mt.w_off = mt.pl_off + S1; mt.row_off = mt.w_off + S1;
+  mt.plist = reinterpret_cast<const int32_t*>(s->sq_tab.as<char>() + o_plist);
+  return AGP_OK;
+}
+
 // The classes in order, between the first two profiling events.  launch(wg, grid, d, lds_bytes) -> hipError_t launches the `grid`
 // particles wg[0 .. grid) of instantiation class d with the largest LDS need among them (d >= SERIES_LONG_CLASS: the long entry's alone).
 template <class Launch> int series_launch(agp_ctx* c, SeriesCall& sc, Launch&& launch) {
@@ -399,10 +489,7 @@ template <class Launch> int series_launch(agp_ctx* c, SeriesCall& sc, Launch&& l
 int series_launch_predict(agp_ctx* c, SeriesCall& sc) {
   Slot* s = sc.s;
   SeriesPredArgs pa = {};
-  static_cast<SeriesArgs&>(pa) = sc.sa;
-  pa.q_off = sc.in_map<const long long>(sc.o_qoff);
-  pa.out_off = sc.in_map<const long long>(sc.o_ooff);
-  pa.ts_pred = s->tt.as<double>() + 2 * sc.npts; pa.noise_pred = s->noise_pred.as<double>();
+  series_query_args(sc, pa);
   pa.out_mean = s->pred_mean.as<double>(); pa.out_var = s->pred_var.as<double>();
   return series_launch(c, sc, [&](const int32_t* wg, int grid, int d, size_t lds) {
     pa.wg = wg;
@@ -410,14 +497,28 @@ int series_launch_predict(agp_ctx* c, SeriesCall& sc) {
   });
 }
 
-// the pinned landing zone at the entry's size, and [logpdf | info] on their way into its head
-int series_fetch_values(agp_ctx* c, SeriesCall& sc, size_t h_out_bytes) {
-  HIPCHK(c, sc.s->h_out.ensure(h_out_bytes));
-  HIPCHK(c, hipMemcpyAsync(sc.s->h_out.p, sc.s->out_lp.p, sc.values_bytes(), hipMemcpyDeviceToHost, sc.st));
+// the end of the profiled read-out span: behind the entry's read-out kernels, ahead of the copies
+int series_mark_readout(agp_ctx* c, SeriesCall& sc) {
+  if (sc.prof) HIPCHK(c, hipEventRecord(sc.ev[2], sc.st));
+  sc.readout = sc.prof;
   return AGP_OK;
 }
 
-// ... and, the stream drained, into the caller's arrays.  An empty series (never launched, or launched for the prior predictive):
+// The call's read-back: the pinned landing zone at the size of [logpdf | info] and everything the entry registered, one copy each
+// in that order (an array of 0 bytes: none), and the stream drained.
+int series_fetch(agp_ctx* c, SeriesCall& sc) {
+  size_t total = sc.values_bytes();
+  for (SeriesCall::Back& b : sc.back) { b.off = (total + 7) & ~(size_t)7; total = b.off + b.bytes; }
+  HIPCHK(c, sc.s->h_out.ensure(total));
+  char* ho = static_cast<char*>(sc.s->h_out.p);
+  HIPCHK(c, hipMemcpyAsync(ho, sc.s->out_lp.p, sc.values_bytes(), hipMemcpyDeviceToHost, sc.st));
+  for (const SeriesCall::Back& b : sc.back)
+    if (b.bytes > 0) HIPCHK(c, hipMemcpyAsync(ho + b.off, b.dev, b.bytes, hipMemcpyDeviceToHost, sc.st));
+  HIPCHK(c, hipStreamSynchronize(sc.st));
+  return AGP_OK;
+}
+
+// ... and out of its head into the caller's arrays.  An empty series (never launched, or launched for the prior predictive):
 // the value is 0 either way
 void series_copy_values(const SeriesCall& sc, double* out_logpdf, int32_t* out_info) {
   const int P = sc.pp.P;
@@ -432,9 +533,10 @@ void series_copy_values(const SeriesCall& sc, double* out_logpdf, int32_t* out_i
 
 // agp_get_timing: out[0] = out[2] = the value kernels of the call (covariance, factorisation, solve and value are one kernel);
 // out[4] = the band's three read-out kernels, the held-out entry's mixture read-out, the sampling entry's NaN fill (0 in the others)
-int series_timing(agp_ctx* c, const SeriesCall& sc, float readout_ms = 0.f) {
+int series_timing(agp_ctx* c, const SeriesCall& sc) {
   if (!sc.prof) return AGP_OK;
-  float ms = 0.f;
+  float ms = 0.f, readout_ms = 0.f;
+  if (sc.readout) HIPCHK(c, hipEventElapsedTime(&readout_ms, sc.ev[1], sc.ev[2]));
   HIPCHK(c, hipEventElapsedTime(&ms, sc.ev[0], sc.ev[1]));
   std::lock_guard<std::mutex> g(c->mu);
   for (double& t : c->timing) t = 0.0;
@@ -505,9 +607,7 @@ int logpdf_series(agp_ctx* c, SeriesCall& sc, double* out_logpdf, int32_t* out_i
       return launch_long_series_logpdf(sc.st, la, cnt, d == SERIES_LONG_CLASS ? 4 : 8, lds);
     });
   }));
-  // h_out = [logpdf | info]
-  STAGE(series_fetch_values(c, sc, sc.values_bytes()));
-  HIPCHK(c, hipStreamSynchronize(sc.st));
+  STAGE(series_fetch(c, sc));
   series_copy_values(sc, out_logpdf, out_info);
   return series_timing(c, sc);
 }
@@ -530,46 +630,22 @@ int logpdf_grad_series(agp_ctx* c, SeriesCall& sc, double* out_logpdf, double* o
   }
   STAGE(series_stage(c, sc));
   Slot* s = sc.s;
-  const Batch& bt = sc.bt;
-  HIPCHK(c, s->ghdr.ensure(sizeof(GProgHdr) * (size_t)P));
-  HIPCHK(c, s->gops.ensure(bt.gops.size() + 4));
-  HIPCHK(c, s->glc.ensure(bt.glc.size() + 4));
-  HIPCHK(c, s->grc.ensure(bt.grc.size() + 4));
-  HIPCHK(c, s->gpoff.ensure(sizeof(int32_t) * (bt.gpoff.size() + 1)));
-  HIPCHK(c, s->gprm.ensure(sizeof(double) * bt.gprm.size()));
-  HIPCHK(c, s->gmap.ensure(sizeof(int32_t) * (bt.gmap.size() + 1)));
-  HIPCHK(c, s->goff.ensure(sizeof(int32_t) * (size_t)P));
+  SeriesGradArgs ga = {};
+  STAGE(series_grad_tape(c, sc, ga));
   HIPCHK(c, s->dgrad.ensure(sizeof(double) * std::max<size_t>(1, n_prm_total)));
   HIPCHK(c, s->dgnoise.ensure(sizeof(double) * (size_t)P));
-  sc.up.add(s->ghdr.p, bt.ghdr.data(), sizeof(GProgHdr) * (size_t)P);
-  sc.up.add(s->gops.p, bt.gops.data(), bt.gops.size());
-  sc.up.add(s->glc.p, bt.glc.data(), bt.glc.size());
-  sc.up.add(s->grc.p, bt.grc.data(), bt.grc.size());
-  sc.up.add(s->gpoff.p, bt.gpoff.data(), sizeof(int32_t) * bt.gpoff.size());
-  sc.up.add(s->gprm.p, bt.gprm.data(), sizeof(double) * bt.gprm.size());
-  sc.up.add(s->gmap.p, bt.gmap.data(), sizeof(int32_t) * bt.gmap.size());
-  sc.up.add(s->goff.p, sc.pp.prm_off, sizeof(int32_t) * (size_t)P);      // the particle's block in out_grad: the caller's own offsets
   HIPCHK(c, sc.up.flush(s->h_stage, s->up_blob, sc.st));
-  SeriesGradArgs ga = {};
-  static_cast<SeriesArgs&>(ga) = sc.sa;
-  ga.ghdr = s->ghdr.as<GProgHdr>(); ga.gops = s->gops.as<uint8_t>(); ga.glc = s->glc.as<uint8_t>(); ga.grc = s->grc.as<uint8_t>();
-  ga.gpoff = s->gpoff.as<int32_t>(); ga.gprm = s->gprm.as<double>(); ga.gmap = s->gmap.as<int32_t>();
-  ga.out_off = s->goff.as<int32_t>(); ga.out_grad = s->dgrad.as<double>(); ga.out_gnoise = s->dgnoise.as<double>();
+  ga.out_grad = s->dgrad.as<double>(); ga.out_gnoise = s->dgnoise.as<double>();
   STAGE(series_launch(c, sc, [&](const int32_t* wg, int grid, int d, size_t lds) {
     ga.wg = wg;
     return launch_series_logpdf_grad(sc.st, ga, grid, d == 2 ? 8 : 4, d == 0 ? 16 : 64, lds);
   }));
-  // h_out = [logpdf | info | grad_noise (P) | grad (prm_off[P])]
-  const size_t o_gn = sc.o_own(), o_gr = o_gn + sizeof(double) * (size_t)P;
-  STAGE(series_fetch_values(c, sc, o_gr + sizeof(double) * n_prm_total));
-  char* ho = static_cast<char*>(s->h_out.p);
-  HIPCHK(c, hipMemcpyAsync(ho + o_gn, s->dgnoise.p, sizeof(double) * (size_t)P, hipMemcpyDeviceToHost, sc.st));
-  if (n_prm_total > 0) HIPCHK(c, hipMemcpyAsync(ho + o_gr, s->dgrad.p, sizeof(double) * n_prm_total, hipMemcpyDeviceToHost, sc.st));
-  HIPCHK(c, hipStreamSynchronize(sc.st));
+  const int b_gn = sc.want(s->dgnoise.p, sizeof(double) * (size_t)P), b_gr = sc.want(s->dgrad.p, sizeof(double) * n_prm_total);
+  STAGE(series_fetch(c, sc));
   series_copy_values(sc, out_logpdf, out_info);
   // (an empty series: zeros; a bad pivot: NaN in the whole block — the kernel wrote them, slot by slot through gmap)
-  const double* hgn = reinterpret_cast<const double*>(ho + o_gn);
-  const double* hgr = reinterpret_cast<const double*>(ho + o_gr);
+  const double* hgn = sc.got<double>(b_gn);
+  const double* hgr = sc.got<double>(b_gr);
   for (int p = 0; p < P; ++p) {
     const bool empty = sc.len[(size_t)p] == 0;
     out_gnoise[p] = empty ? 0.0 : hgn[p];
@@ -668,14 +744,8 @@ int hmc_series(agp_ctx* c, SeriesCall& sc, const SeriesHmcCall& hm, double* out_
   }
   STAGE(series_stage(c, sc));
   Slot* s = sc.s;
-  HIPCHK(c, s->ghdr.ensure(sizeof(GProgHdr) * (size_t)P));
-  HIPCHK(c, s->gops.ensure(bt.gops.size() + 4));
-  HIPCHK(c, s->glc.ensure(bt.glc.size() + 4));
-  HIPCHK(c, s->grc.ensure(bt.grc.size() + 4));
-  HIPCHK(c, s->gpoff.ensure(sizeof(int32_t) * (bt.gpoff.size() + 1)));
-  HIPCHK(c, s->gprm.ensure(sizeof(double) * bt.gprm.size()));
-  HIPCHK(c, s->gmap.ensure(sizeof(int32_t) * (bt.gmap.size() + 1)));
-  HIPCHK(c, s->goff.ensure(sizeof(int32_t) * (size_t)P));
+  SeriesHmcArgs ha = {};      // (out_grad, out_gnoise: null — the chain keeps its gradients to itself)
+  STAGE(series_grad_tape(c, sc, ha));
   // hmc_in  = [z (NT) | z_noise (P) | tf (3 C) | seeds (P) | params | prm_class (NT ints) | rule (bytes)]
   // hmc_out = [out_z (NT) | out_prm (NT) | out_z_noise (P) | out_noise (P) | trace (P tr_n) | counts (4 P ints)]
   const size_t D = sizeof(double);
@@ -698,14 +768,6 @@ int hmc_series(agp_ctx* c, SeriesCall& sc, const SeriesHmcCall& hm, double* out_
   par.out_z_noise = reinterpret_cast<double*>(dout + o_zn); par.out_noise = reinterpret_cast<double*>(dout + o_nz);
   par.out_trace = tr_n ? reinterpret_cast<double*>(dout + o_tr) : nullptr;
   par.out_counts = reinterpret_cast<int32_t*>(dout + o_cnt);
-  sc.up.add(s->ghdr.p, bt.ghdr.data(), sizeof(GProgHdr) * (size_t)P);
-  sc.up.add(s->gops.p, bt.gops.data(), bt.gops.size());
-  sc.up.add(s->glc.p, bt.glc.data(), bt.glc.size());
-  sc.up.add(s->grc.p, bt.grc.data(), bt.grc.size());
-  sc.up.add(s->gpoff.p, bt.gpoff.data(), sizeof(int32_t) * bt.gpoff.size());
-  sc.up.add(s->gprm.p, bt.gprm.data(), sizeof(double) * bt.gprm.size());
-  sc.up.add(s->gmap.p, bt.gmap.data(), sizeof(int32_t) * bt.gmap.size());
-  sc.up.add(s->goff.p, sc.pp.prm_off, sizeof(int32_t) * (size_t)P);
   sc.up.add(di, hm.z, D * NT);
   sc.up.add(di + i_zn, hm.z_noise, D * P);
   sc.up.add(di + i_tf, hm.tf, D * 3 * hm.C);
@@ -714,24 +776,15 @@ int hmc_series(agp_ctx* c, SeriesCall& sc, const SeriesHmcCall& hm, double* out_
   sc.up.add(di + i_cls, hm.prm_class, sizeof(int32_t) * NT);
   sc.up.add(di + i_rule, rule.data(), rule.size());
   HIPCHK(c, sc.up.flush(s->h_stage, s->up_blob, sc.st));
-  SeriesHmcArgs ha = {};
-  static_cast<SeriesArgs&>(ha) = sc.sa;
-  ha.ghdr = s->ghdr.as<GProgHdr>(); ha.gops = s->gops.as<uint8_t>(); ha.glc = s->glc.as<uint8_t>(); ha.grc = s->grc.as<uint8_t>();
-  ha.gpoff = s->gpoff.as<int32_t>(); ha.gprm = s->gprm.as<double>(); ha.gmap = s->gmap.as<int32_t>();
-  ha.out_off = s->goff.as<int32_t>(); ha.out_grad = nullptr; ha.out_gnoise = nullptr;
   ha.hm = reinterpret_cast<const SeriesHmcParams*>(di + i_par); ha.C = hm.C;
   STAGE(series_launch(c, sc, [&](const int32_t* wg, int grid, int d, size_t lds) {
     ha.wg = wg;
     return launch_series_hmc(sc.st, ha, grid, d == 2 ? 8 : 4, d == 0 ? 16 : 64, lds);
   }));
-  // h_out = [logpdf | info | hmc_out]
-  const size_t o_own = sc.o_own();
-  STAGE(series_fetch_values(c, sc, o_own + out_bytes));
-  char* ho = static_cast<char*>(s->h_out.p);
-  HIPCHK(c, hipMemcpyAsync(ho + o_own, dout, out_bytes, hipMemcpyDeviceToHost, sc.st));
-  HIPCHK(c, hipStreamSynchronize(sc.st));
+  const int b_out = sc.want(dout, out_bytes);
+  STAGE(series_fetch(c, sc));
   series_copy_values(sc, out_logpdf, out_info);
-  const char* hb = ho + o_own;
+  const char* hb = sc.got<char>(b_out);
   const double* hz = reinterpret_cast<const double*>(hb);
   const double* hp = reinterpret_cast<const double*>(hb + o_prm);
   const double* hzn = reinterpret_cast<const double*>(hb + o_zn);
@@ -764,21 +817,13 @@ int predict_series(agp_ctx* c, SeriesCall& sc, double* out_mean, double* out_var
   Slot* s = sc.s;
   HIPCHK(c, sc.up.flush(s->h_stage, s->up_blob, sc.st));
   STAGE(series_launch_predict(c, sc));
-  // h_out = [logpdf | info | mean (out_off[P]) | var (out_off[P])]
-  const size_t n_out = sc.n_out(), o_mean = sc.o_own(), o_var = o_mean + sizeof(double) * n_out;
-  STAGE(series_fetch_values(c, sc, o_var + sizeof(double) * n_out));
-  char* ho = static_cast<char*>(s->h_out.p);
-  if (n_out > 0) {
-    HIPCHK(c, hipMemcpyAsync(ho + o_mean, s->pred_mean.p, sizeof(double) * n_out, hipMemcpyDeviceToHost, sc.st));
-    HIPCHK(c, hipMemcpyAsync(ho + o_var, s->pred_var.p, sizeof(double) * n_out, hipMemcpyDeviceToHost, sc.st));
-  }
-  HIPCHK(c, hipStreamSynchronize(sc.st));
+  const size_t n_out = sc.n_out();
+  const int b_mean = sc.want(s->pred_mean.p, sizeof(double) * n_out), b_var = sc.want(s->pred_var.p, sizeof(double) * n_out);
+  STAGE(series_fetch(c, sc));
   series_copy_values(sc, out_logpdf, out_info);
-  if (n_out > 0) {      // every particle with query points was launched and wrote its whole block
-    const double* hm = reinterpret_cast<const double*>(ho + o_mean);
-    std::copy(hm, hm + n_out, out_mean);
-    std::copy(hm + n_out, hm + 2 * n_out, out_var);
-  }
+  // every particle with query points was launched and wrote its whole block
+  std::copy_n(sc.got<double>(b_mean), n_out, out_mean);
+  std::copy_n(sc.got<double>(b_var), n_out, out_var);
   return series_timing(c, sc);
 }
 
@@ -791,7 +836,7 @@ int predict_quantile_series(agp_ctx* c, SeriesCall& sc, const SeriesQuantOut& qo
   STAGE(series_check_pointers(c, sc, out_info != nullptr));
   if (!sc.q_off || !sc.ts_pred) return fail(c, AGP_ERR_ARG, "null pointer argument (q_off, ts_pred, out_mean, out_var or out_off)");
   STAGE(series_check_layout(c, sc));
-  QuantPlan qp;
+  MixPlan qp;
   STAGE(quant_plan(c, S, P, sc.series, sc.q_off, qo, qp));
   if (P == 0) { quant_fill_nan(qo, 0, qp.Q, qo.nq); return AGP_OK; }      // (S series without a particle)
   STAGE(series_classes(c, sc, SeriesMode::prediction));
@@ -805,15 +850,13 @@ int predict_quantile_series(agp_ctx* c, SeriesCall& sc, const SeriesQuantOut& qo
   // x and the moments in sq_out, the flags in sq_flag = [converged | iterations | first_bad (P) | bad (S)]
   const size_t nx = qp.Q * (size_t)qo.nq;
   const bool want_mom = qo.mix_mean || qo.mix_var;
-  const size_t S1 = (size_t)S + 1, o_plist = sizeof(long long) * 3 * S1;
-  HIPCHK(c, s->sq_tab.ensure(o_plist + sizeof(int32_t) * (size_t)P));
+  MixTabs mt;
+  STAGE(series_stage_mix(c, sc, qp, mt));
   HIPCHK(c, s->sq_w.ensure(sizeof(double) * std::max<size_t>(1, qp.vals.size())));
   HIPCHK(c, s->sq_cm.ensure(sizeof(double) * std::max<size_t>(1, qp.R)));
   HIPCHK(c, s->sq_cs.ensure(sizeof(double) * std::max<size_t>(1, qp.R)));
   HIPCHK(c, s->sq_out.ensure(sizeof(double) * std::max<size_t>(1, nx + 2 * qp.Q)));
   HIPCHK(c, s->sq_flag.ensure(sizeof(int32_t) * (2 * nx + (size_t)P + (size_t)S)));
-  sc.up.add(s->sq_tab.p, qp.tab.data(), o_plist);
-  sc.up.add(s->sq_tab.as<char>() + o_plist, qp.plist.data(), sizeof(int32_t) * (size_t)P);
   sc.up.add(s->sq_w.p, qp.vals.data(), sizeof(double) * qp.vals.size());
   HIPCHK(c, sc.up.flush(s->h_stage, s->up_blob, sc.st));
   STAGE(series_launch_predict(c, sc));
@@ -823,8 +866,7 @@ int predict_quantile_series(agp_ctx* c, SeriesCall& sc, const SeriesQuantOut& qo
   qa.q_off = sc.in_map<const long long>(sc.o_qoff);
   qa.out_off = sc.in_map<const long long>(sc.o_ooff);
   qa.mean = s->pred_mean.as<double>(); qa.var = s->pred_var.as<double>(); qa.pred_info = sc.sa.out_info;
-  qa.pl_off = s->sq_tab.as<long long>(); qa.w_off = qa.pl_off + S1; qa.row_off = qa.w_off + S1;
-  qa.plist = reinterpret_cast<const int32_t*>(s->sq_tab.as<char>() + o_plist);
+  qa.pl_off = mt.pl_off; qa.w_off = mt.w_off; qa.row_off = mt.row_off; qa.plist = mt.plist;
   qa.w = s->sq_w.as<double>(); qa.slope = qa.w + qp.W; qa.intercept = qa.slope + S; qa.ivar = qa.intercept + S; qa.q = qa.ivar + S;
   qa.tol = qo.tol; qa.max_iter = (long long)qo.max_iter;
   qa.cm = s->sq_cm.as<double>(); qa.cs = s->sq_cs.as<double>();
@@ -834,17 +876,14 @@ int predict_quantile_series(agp_ctx* c, SeriesCall& sc, const SeriesQuantOut& qo
   qa.first_bad = qa.out_iters + nx; qa.bad = qa.first_bad + P;
   launch_series_mix_readout(sc.st, qa, (long long)qp.Q, qp.max_rows_el);
   HIPCHK(c, hipGetLastError());
-  if (sc.prof) HIPCHK(c, hipEventRecord(sc.ev[2], sc.st));
-  // h_out = [logpdf | info | x (nx) | mean (Q) | var (Q) | converged (nx) | iterations (nx) | first_bad (P)], the moments when wanted
-  const size_t n_band = nx + (want_mom ? 2 * qp.Q : 0), o_band = sc.o_own(), o_flag = o_band + sizeof(double) * n_band;
-  STAGE(series_fetch_values(c, sc, o_flag + sizeof(int32_t) * (2 * nx + (size_t)P)));
-  char* ho = static_cast<char*>(s->h_out.p);
-  if (n_band > 0) HIPCHK(c, hipMemcpyAsync(ho + o_band, s->sq_out.p, sizeof(double) * n_band, hipMemcpyDeviceToHost, sc.st));
-  HIPCHK(c, hipMemcpyAsync(ho + o_flag, s->sq_flag.p, sizeof(int32_t) * (2 * nx + (size_t)P), hipMemcpyDeviceToHost, sc.st));
-  HIPCHK(c, hipStreamSynchronize(sc.st));
+  STAGE(series_mark_readout(c, sc));
+  // back: [x (nx) | mean (Q) | var (Q)], the moments when wanted, and [converged (nx) | iterations (nx) | first_bad (P)]
+  const int b_band = sc.want(s->sq_out.p, sizeof(double) * (nx + (want_mom ? 2 * qp.Q : 0)));
+  const int b_flag = sc.want(s->sq_flag.p, sizeof(int32_t) * (2 * nx + (size_t)P));
+  STAGE(series_fetch(c, sc));
   series_copy_values(sc, out_logpdf, out_info);
-  const double* hb = reinterpret_cast<const double*>(ho + o_band);
-  const int32_t* hf = reinterpret_cast<const int32_t*>(ho + o_flag);
+  const double* hb = sc.got<double>(b_band);
+  const int32_t* hf = sc.got<int32_t>(b_flag);
   // raw_components' rule: a particle whose predictive exists but whose raw mean or variance is unusable at query i reports n_s + i + 1
   for (int p = 0; p < P; ++p)
     if (out_info[p] == 0 && sc.nq[(size_t)p] > 0 && hf[2 * nx + (size_t)p] != 0) out_info[p] = hf[2 * nx + (size_t)p];
@@ -853,9 +892,7 @@ int predict_quantile_series(agp_ctx* c, SeriesCall& sc, const SeriesQuantOut& qo
   if (qo.iters) std::copy(hf + nx, hf + 2 * nx, qo.iters);
   if (qo.mix_mean) std::copy(hb + nx, hb + nx + qp.Q, qo.mix_mean);
   if (qo.mix_var) std::copy(hb + nx + qp.Q, hb + nx + 2 * qp.Q, qo.mix_var);
-  float readout_ms = 0.f;
-  if (sc.prof) HIPCHK(c, hipEventElapsedTime(&readout_ms, sc.ev[1], sc.ev[2]));
-  return series_timing(c, sc, readout_ms);
+  return series_timing(c, sc);
 }
 
 // The held-out side of agp_predict_logpdf_series_batch: values, transforms, mixture weights, and the outputs beside [logpdf | info].
@@ -883,27 +920,19 @@ int predict_logpdf_series(agp_ctx* c, SeriesCall& sc, const SeriesProbaOut& po, 
   STAGE(series_check_layout(c, sc));
   const size_t Q = S > 0 ? (size_t)sc.q_off[S] : 0;
   if (!po.y_pred && Q > 0) return fail(c, AGP_ERR_ARG, "null pointer argument (y_pred with held-out points present)");
-  std::vector<double> slope((size_t)S, 1.0);
+  std::vector<double> slope((size_t)S);
   for (int32_t s = 0; s < S; ++s) {
-    const long long n = sc.pt_off[s + 1] - sc.pt_off[s], m = sc.q_off[s + 1] - sc.q_off[s];
-    if (m > 0 && n + m > AGP_SERIES_MAX_N) {
-      snprintf(buf, sizeof buf, "series %d has %lld training and %lld held-out points, together more than AGP_SERIES_MAX_N (%d)", (int)s, n, m,
-               AGP_SERIES_MAX_N);
-      return fail(c, AGP_ERR_ARG, buf);
-    }
-    for (long long j = 0; j < m; ++j)
+    STAGE(series_check_joint(c, sc, s, "held-out"));
+    for (long long j = 0, m = sc.q_off[s + 1] - sc.q_off[s]; j < m; ++j)
       if (!std::isfinite(po.y_pred[sc.q_off[s] + j])) {
         snprintf(buf, sizeof buf, "series %d: held-out value %lld is not finite", (int)s, j);
         return fail(c, AGP_ERR_ARG, buf);
       }
-    if (po.y_slope) slope[(size_t)s] = po.y_slope[s];
-    if (const int rc = check_y_transform(c, slope[(size_t)s], 0.0)) return fail_series(c, rc, s);
+    double icpt;
+    STAGE(series_y_transform(c, s, po.y_slope, nullptr, slope[(size_t)s], icpt));
   }
-  QuantPlan qp;      // the band entry's lists and weight checks (no quantiles, no rows read)
-  if (po.weights) {
-    const SeriesQuantOut qo{po.weights, po.y_slope, nullptr, nullptr, 0, 0.0, 0, nullptr, nullptr, nullptr, nullptr, nullptr};
-    STAGE(quant_plan(c, S, P, sc.series, sc.q_off, qo, qp));
-  }
+  MixPlan qp;      // the mixtures' lists and weights (the transforms: checked above)
+  if (po.weights) STAGE(mix_plan(c, S, P, sc.series, sc.q_off, po.weights, nullptr, nullptr, 0, qp));
   const double nanv = std::numeric_limits<double>::quiet_NaN();
   if (P == 0) { std::fill(po.series_logp, po.series_logp + S, nanv); return AGP_OK; }      // (S series without a particle)
   STAGE(series_classes(c, sc, SeriesMode::held_out));
@@ -916,23 +945,18 @@ int predict_logpdf_series(agp_ctx* c, SeriesCall& sc, const SeriesProbaOut& po, 
   STAGE(series_stage(c, sc));
   Slot* s = sc.s;
   // sq_w = [y_pred (Q) | slope (S) | the plan's values: w (W) ..]; sq_tab = [pl_off | w_off | row_off | plist]; sq_out = the mixtures (S)
-  const size_t S1 = (size_t)S + 1, o_plist = sizeof(long long) * 3 * S1;
+  MixTabs mt = {};
   HIPCHK(c, s->sq_w.ensure(sizeof(double) * std::max<size_t>(1, Q + (size_t)S + qp.vals.size())));
   sc.up.add(s->sq_w.p, po.y_pred, sizeof(double) * Q);
   sc.up.add(s->sq_w.as<double>() + Q, slope.data(), sizeof(double) * (size_t)S);
   if (po.weights) {
-    HIPCHK(c, s->sq_tab.ensure(o_plist + sizeof(int32_t) * (size_t)P));
+    STAGE(series_stage_mix(c, sc, qp, mt));
     HIPCHK(c, s->sq_out.ensure(sizeof(double) * (size_t)S));
     sc.up.add(s->sq_w.as<double>() + Q + S, qp.vals.data(), sizeof(double) * qp.vals.size());
-    sc.up.add(s->sq_tab.p, qp.tab.data(), o_plist);
-    sc.up.add(s->sq_tab.as<char>() + o_plist, qp.plist.data(), sizeof(int32_t) * (size_t)P);
   }
   HIPCHK(c, sc.up.flush(s->h_stage, s->up_blob, sc.st));
   SeriesProbaArgs pa = {};
-  static_cast<SeriesArgs&>(pa) = sc.sa;
-  pa.q_off = sc.in_map<const long long>(sc.o_qoff);
-  pa.out_off = sc.in_map<const long long>(sc.o_ooff);
-  pa.ts_pred = s->tt.as<double>() + 2 * sc.npts; pa.noise_pred = s->noise_pred.as<double>();
+  series_query_args(sc, pa);
   pa.y_pred = s->sq_w.as<double>(); pa.y_slope = s->sq_w.as<double>() + Q;
   pa.out_terms = po.terms ? s->pred_mean.as<double>() : nullptr;
   STAGE(series_launch(c, sc, [&](const int32_t* wg, int grid, int d, size_t lds) {
@@ -943,34 +967,24 @@ int predict_logpdf_series(agp_ctx* c, SeriesCall& sc, const SeriesProbaOut& po, 
     SeriesMixLogpArgs ma = {};
     ma.S = S;
     ma.q_off = pa.q_off;
-    ma.pl_off = s->sq_tab.as<long long>(); ma.w_off = ma.pl_off + S1;
-    ma.plist = reinterpret_cast<const int32_t*>(s->sq_tab.as<char>() + o_plist);
+    ma.pl_off = mt.pl_off; ma.w_off = mt.w_off; ma.plist = mt.plist;
     ma.w = s->sq_w.as<double>() + Q + S;
     ma.lp = sc.sa.out_lp; ma.info = sc.sa.out_info;
     ma.out = s->sq_out.as<double>();
     launch_series_mix_logp(sc.st, ma);
     HIPCHK(c, hipGetLastError());
-    if (sc.prof) HIPCHK(c, hipEventRecord(sc.ev[2], sc.st));
+    STAGE(series_mark_readout(c, sc));
   }
-  // h_out = [logpdf | info | terms (out_off[P]) | mixtures (S)], the last two when wanted
-  const size_t n_terms = po.terms ? sc.n_out() : 0, o_terms = sc.o_own(), o_mix = o_terms + sizeof(double) * n_terms;
-  STAGE(series_fetch_values(c, sc, o_mix + sizeof(double) * (po.weights ? (size_t)S : 0)));
-  char* ho = static_cast<char*>(s->h_out.p);
-  if (n_terms > 0) HIPCHK(c, hipMemcpyAsync(ho + o_terms, s->pred_mean.p, sizeof(double) * n_terms, hipMemcpyDeviceToHost, sc.st));
-  if (po.weights) HIPCHK(c, hipMemcpyAsync(ho + o_mix, s->sq_out.p, sizeof(double) * (size_t)S, hipMemcpyDeviceToHost, sc.st));
-  HIPCHK(c, hipStreamSynchronize(sc.st));
+  // back: the terms and the mixtures, each when wanted
+  const size_t n_terms = po.terms ? sc.n_out() : 0;
+  const int b_terms = sc.want(s->pred_mean.p, sizeof(double) * n_terms);
+  const int b_mix = sc.want(s->sq_out.p, sizeof(double) * (po.weights ? (size_t)S : 0));
+  STAGE(series_fetch(c, sc));
   series_copy_values(sc, out_logpdf, out_info);      // (nothing held out: length 0 here, so 0 and info 0)
-  if (n_terms > 0) {      // every particle with held-out points was launched and wrote its whole block
-    const double* ht = reinterpret_cast<const double*>(ho + o_terms);
-    std::copy(ht, ht + n_terms, po.terms);
-  }
-  if (po.weights) {
-    const double* hm = reinterpret_cast<const double*>(ho + o_mix);
-    std::copy(hm, hm + S, po.series_logp);
-  }
-  float readout_ms = 0.f;
-  if (sc.prof && po.weights) HIPCHK(c, hipEventElapsedTime(&readout_ms, sc.ev[1], sc.ev[2]));
-  return series_timing(c, sc, readout_ms);
+  // every particle with held-out points was launched and wrote its whole block
+  if (n_terms > 0) std::copy_n(sc.got<double>(b_terms), n_terms, po.terms);
+  if (po.weights) std::copy_n(sc.got<double>(b_mix), S, po.series_logp);
+  return series_timing(c, sc);
 }
 
 // The sampling side of agp_predict_sample_series_batch: transforms, mixture weights, the draws, and the outputs beside info.
@@ -1012,29 +1026,19 @@ int predict_sample_series(agp_ctx* c, SeriesCall& sc, const SeriesSampleOut& so,
   if (R > 0 && !so.seeds && (!so.component || (!so.z && Q > 0))) return fail(c, AGP_ERR_ARG, "null pointer argument (seeds)");
   std::vector<double> tr(2 * (size_t)S);      // [slope (S) | intercept (S)]
   for (int32_t s = 0; s < S; ++s) {
-    const long long n = sc.pt_off[s + 1] - sc.pt_off[s], m = sc.q_off[s + 1] - sc.q_off[s];
-    if (m > 0 && n + m > AGP_SERIES_MAX_N) {
-      snprintf(buf, sizeof buf, "series %d has %lld training and %lld query points, together more than AGP_SERIES_MAX_N (%d)", (int)s, n, m,
-               AGP_SERIES_MAX_N);
-      return fail(c, AGP_ERR_ARG, buf);
-    }
-    tr[(size_t)s] = so.y_slope ? so.y_slope[s] : 1.0;
-    tr[(size_t)S + s] = so.y_intercept ? so.y_intercept[s] : 0.0;
-    if (const int rc = check_y_transform(c, tr[(size_t)s], tr[(size_t)S + s])) return fail_series(c, rc, s);
+    STAGE(series_check_joint(c, sc, s, "query"));
+    STAGE(series_y_transform(c, s, so.y_slope, so.y_intercept, tr[(size_t)s], tr[(size_t)S + s]));
     if (so.z)
-      for (long long k = 0; k < R * m; ++k)
+      for (long long k = 0, m = sc.q_off[s + 1] - sc.q_off[s]; k < R * m; ++k)
         if (!std::isfinite(so.z[R * sc.q_off[s] + k])) {
           snprintf(buf, sizeof buf, "series %d: z of sample %lld, point %lld is not finite", (int)s, k / m, k % m);
           return fail(c, AGP_ERR_ARG, buf);
         }
   }
-  QuantPlan qp;      // the band entry's lists and weight checks (no quantiles, no rows read)
-  {
-    const SeriesQuantOut qo{so.weights, nullptr, nullptr, nullptr, 0, 0.0, 0, nullptr, nullptr, nullptr, nullptr, nullptr};
-    STAGE(quant_plan(c, S, P, sc.series, sc.q_off, qo, qp));
-  }
-  const long long* pl_off = qp.tab.data();
-  const long long* w_off = pl_off + (size_t)S + 1;
+  MixPlan qp;      // the mixtures' lists and weights (the transforms: checked above)
+  STAGE(mix_plan(c, S, P, sc.series, sc.q_off, so.weights, nullptr, nullptr, 0, qp));
+  const long long* pl_off = qp.pl_off();
+  const long long* w_off = qp.w_off();
   // the component of every sample — the caller's, or drawn series by series as agp_predict_sample_batch draws under seeds[s] — and
   // from them every particle's list of samples (CSR, ascending)
   std::vector<int32_t> comp((size_t)S * (size_t)R), local;
@@ -1106,10 +1110,7 @@ int predict_sample_series(agp_ctx* c, SeriesCall& sc, const SeriesSampleOut& so,
   }
   HIPCHK(c, sc.up.flush(s->h_stage, s->up_blob, sc.st));
   SeriesSampleArgs pa = {};
-  static_cast<SeriesArgs&>(pa) = sc.sa;
-  pa.q_off = sc.in_map<const long long>(sc.o_qoff);
-  pa.out_off = sc.in_map<const long long>(sc.o_ooff);
-  pa.ts_pred = s->tt.as<double>() + 2 * sc.npts; pa.noise_pred = s->noise_pred.as<double>();
+  series_query_args(sc, pa);
   pa.y_slope = s->sq_w.as<double>(); pa.y_intercept = s->sq_w.as<double>() + S;
   pa.R = R;
   pa.seeds = reinterpret_cast<const unsigned long long*>(s->sq_tab.as<char>() + o_seed);
@@ -1134,23 +1135,17 @@ int predict_sample_series(agp_ctx* c, SeriesCall& sc, const SeriesSampleOut& so,
     fa.out_x = pa.out_x;
     HIPCHK(c, launch_series_sample_fill(sc.st, fa));
   }
-  if (sc.prof) HIPCHK(c, hipEventRecord(sc.ev[2], sc.st));
-  // h_out = [logpdf | info | x (R q_off[S]) | mean (out_off[P]) | cov (cov_off[P])], the last two when wanted
-  const size_t o_x = sc.o_own(), o_mean = o_x + sizeof(double) * nx, o_cov = o_mean + sizeof(double) * n_mean;
-  STAGE(series_fetch_values(c, sc, o_cov + sizeof(double) * n_cov));
-  char* ho = static_cast<char*>(s->h_out.p);
-  if (nx > 0) HIPCHK(c, hipMemcpyAsync(ho + o_x, s->smp_x.p, sizeof(double) * nx, hipMemcpyDeviceToHost, sc.st));
-  if (n_mean > 0) HIPCHK(c, hipMemcpyAsync(ho + o_mean, s->pred_mean.p, sizeof(double) * n_mean, hipMemcpyDeviceToHost, sc.st));
-  if (n_cov > 0) HIPCHK(c, hipMemcpyAsync(ho + o_cov, s->pred_cov.p, sizeof(double) * n_cov, hipMemcpyDeviceToHost, sc.st));
-  HIPCHK(c, hipStreamSynchronize(sc.st));
+  STAGE(series_mark_readout(c, sc));
+  // back: x (R q_off[S]), and mean (out_off[P]) and cov (cov_off[P]) when wanted (pred_cov exists only then: 0 bytes, never read)
+  const int b_x = sc.want(s->smp_x.p, sizeof(double) * nx), b_mean = sc.want(s->pred_mean.p, sizeof(double) * n_mean),
+            b_cov = sc.want(s->pred_cov.p, sizeof(double) * n_cov);
+  STAGE(series_fetch(c, sc));
   series_copy_values(sc, nullptr, out_info);      // (no query point: length 0 here, so info 0)
   // every series with query points has particles, every sample one of them as its component: the whole of x was written
-  if (nx > 0) std::memcpy(so.x, ho + o_x, sizeof(double) * nx);
-  if (n_mean > 0) std::memcpy(so.mean, ho + o_mean, sizeof(double) * n_mean);
-  if (n_cov > 0) std::memcpy(so.cov, ho + o_cov, sizeof(double) * n_cov);
-  float readout_ms = 0.f;
-  if (sc.prof) HIPCHK(c, hipEventElapsedTime(&readout_ms, sc.ev[1], sc.ev[2]));
-  return series_timing(c, sc, readout_ms);
+  if (nx > 0) std::memcpy(so.x, sc.got<char>(b_x), sizeof(double) * nx);
+  if (n_mean > 0) std::memcpy(so.mean, sc.got<char>(b_mean), sizeof(double) * n_mean);
+  if (n_cov > 0) std::memcpy(so.cov, sc.got<char>(b_cov), sizeof(double) * n_cov);
+  return series_timing(c, sc);
 }
 
 // The decomposition side of agp_predict_sum_series_batch: the components, transforms and quantiles, and the outputs beside [logpdf | info].
@@ -1200,11 +1195,7 @@ int predict_sum_series(agp_ctx* c, SeriesCall& sc, const SeriesSumOut& so, doubl
   sc.pp = {P, coff.data(), cops.data(), cpoff.data(), cprm.data(), comp.noise, comp.noise_pred};
   STAGE(series_check_layout(c, sc));
   std::vector<double> vals(2 * (size_t)S + (size_t)nq);      // [slope (S) | intercept (S) | z (nq)]
-  for (int32_t s = 0; s < S; ++s) {
-    vals[(size_t)s] = so.y_slope ? so.y_slope[s] : 1.0;
-    vals[(size_t)S + s] = so.y_intercept ? so.y_intercept[s] : 0.0;
-    if (const int rc = check_y_transform(c, vals[(size_t)s], vals[(size_t)S + s])) return fail_series(c, rc, s);
-  }
+  for (int32_t s = 0; s < S; ++s) STAGE(series_y_transform(c, s, so.y_slope, so.y_intercept, vals[(size_t)s], vals[(size_t)S + s]));
   for (int64_t k = 0; k < nq; ++k) vals[2 * (size_t)S + (size_t)k] = ndtri(so.q[k]);
   {
     int64_t rows = 0;      // (M + 1) sum_p m_{series[p]}: m_s <= 2^30 and M < 2^31, so every step stays far inside int64
@@ -1230,10 +1221,7 @@ int predict_sum_series(agp_ctx* c, SeriesCall& sc, const SeriesSumOut& so, doubl
   sc.up.add(s->sq_w.p, vals.data(), sizeof(double) * vals.size());
   HIPCHK(c, sc.up.flush(s->h_stage, s->up_blob, sc.st));
   SeriesSumArgs pa = {};
-  static_cast<SeriesArgs&>(pa) = sc.sa;
-  pa.q_off = sc.in_map<const long long>(sc.o_qoff);
-  pa.out_off = sc.in_map<const long long>(sc.o_ooff);
-  pa.ts_pred = s->tt.as<double>() + 2 * sc.npts; pa.noise_pred = s->noise_pred.as<double>();
+  series_query_args(sc, pa);
   pa.out_mean = s->pred_mean.as<double>(); pa.out_var = s->pred_var.as<double>();
   pa.M = M; pa.nq = (int)nq;
   pa.y_slope = s->sq_w.as<double>(); pa.y_intercept = pa.y_slope + S; pa.z = pa.y_intercept + S;
@@ -1242,26 +1230,19 @@ int predict_sum_series(agp_ctx* c, SeriesCall& sc, const SeriesSumOut& so, doubl
     pa.wg = wg;
     return launch_series_predict_sum(sc.st, pa, grid, d == 0 ? 4 : 8, lds);
   }));
-  // h_out = [logpdf | info | mean (out_off[P]) | var (out_off[P]) | x (nq out_off[P])]
-  const size_t o_mean = sc.o_own(), o_var = o_mean + sizeof(double) * n_out, o_x = o_var + sizeof(double) * n_out;
-  STAGE(series_fetch_values(c, sc, o_x + sizeof(double) * nx));
-  char* ho = static_cast<char*>(s->h_out.p);
-  if (n_out > 0) {
-    HIPCHK(c, hipMemcpyAsync(ho + o_mean, s->pred_mean.p, sizeof(double) * n_out, hipMemcpyDeviceToHost, sc.st));
-    HIPCHK(c, hipMemcpyAsync(ho + o_var, s->pred_var.p, sizeof(double) * n_out, hipMemcpyDeviceToHost, sc.st));
-  }
-  if (nx > 0) HIPCHK(c, hipMemcpyAsync(ho + o_x, s->sum_x.p, sizeof(double) * nx, hipMemcpyDeviceToHost, sc.st));
-  HIPCHK(c, hipStreamSynchronize(sc.st));
+  const int b_mean = sc.want(s->pred_mean.p, sizeof(double) * n_out), b_var = sc.want(s->pred_var.p, sizeof(double) * n_out),
+            b_x = sc.want(s->sum_x.p, sizeof(double) * nx);
+  STAGE(series_fetch(c, sc));
   series_copy_values(sc, out_logpdf, out_info);
   // (an empty series with query points was launched for its prior: its value is 0, but a row without a raw marginal still reports)
   const int32_t* hi = reinterpret_cast<const int32_t*>(static_cast<const double*>(s->h_out.p) + P);
   for (int p = 0; p < P; ++p)
     if (sc.len[(size_t)p] == 0 && sc.nq[(size_t)p] > 0) out_info[p] = hi[p];
   if (n_out > 0) {      // every particle with query points was launched and wrote its whole blocks
-    std::memcpy(so.mean, ho + o_mean, sizeof(double) * n_out);
-    if (so.var) std::memcpy(so.var, ho + o_var, sizeof(double) * n_out);
+    std::memcpy(so.mean, sc.got<char>(b_mean), sizeof(double) * n_out);
+    if (so.var) std::memcpy(so.var, sc.got<char>(b_var), sizeof(double) * n_out);
   }
-  if (nx > 0) std::memcpy(so.x, ho + o_x, sizeof(double) * nx);
+  if (nx > 0) std::memcpy(so.x, sc.got<char>(b_x), sizeof(double) * nx);
   return series_timing(c, sc);
 }
 

@@ -382,6 +382,31 @@ def pack_series_mixture(series_index, S, weights=None, log_weights=None):
 SeriesBand = collections.namedtuple("SeriesBand", "x converged iters mean var logpdf info")
 
 
+def _series_transforms(y_transforms, S):
+    """(slope, intercept) of a series wrapper's y_transforms, one contiguous (S,) vector each — (None, None) for None (the library's
+    (1, 0)).  Raises ValueError on anything but one (slope, intercept) pair per series."""
+    if y_transforms is None:
+        return None, None
+    yt = _f64(y_transforms)
+    if yt.shape != (S, 2):
+        raise ValueError(f"y_transforms has shape {yt.shape}, expected ({S}, 2): one (slope, intercept) per series")
+    return np.ascontiguousarray(yt[:, 0]), np.ascontiguousarray(yt[:, 1])
+
+
+def _particle_weights(weights, P):
+    """A series wrapper's mixture weights as float64, one per particle (ValueError otherwise)."""
+    weights = _f64(weights)
+    if weights.shape != (P,):
+        raise ValueError(f"weights has shape {weights.shape}, expected ({P},)")
+    return weights
+
+
+def _particle_noise_pred(noise_pred, P):
+    """A series wrapper's noise_pred: a scalar serves every particle; anything else (None, one per particle) is pack_queries' to
+    check.  (predict_quantile_series_batch broadcasts with np.broadcast_to instead, and so also takes a length-1 vector: its own line.)"""
+    return np.full(P, float(noise_pred)) if noise_pred is not None and np.ndim(noise_pred) == 0 else noise_pred
+
+
 def pack_heldout(heldout, q_off, y_transforms=None):
     """The held-out side of predict_logpdf_series_batch: (y_pred, slope or None) from one vector of RAW held-out values per series,
     series s's as long as its vector of query times (q_off: pack_queries').  y_transforms: one (slope, intercept) per series
@@ -391,12 +416,7 @@ def pack_heldout(heldout, q_off, y_transforms=None):
     S = q_off.shape[0] - 1
     if len(heldout) != S:
         raise ValueError(f"one vector of held-out values per series required ({len(heldout)} for {S} series)")
-    slope = icpt = None
-    if y_transforms is not None:
-        yt = _f64(y_transforms)
-        if yt.shape != (S, 2):
-            raise ValueError(f"y_transforms has shape {yt.shape}, expected ({S}, 2): one (slope, intercept) per series")
-        slope, icpt = np.ascontiguousarray(yt[:, 0]), yt[:, 1]
+    slope, icpt = _series_transforms(y_transforms, S)
     parts = []
     for s, y in enumerate(heldout):
         y = _f64(y)
@@ -694,15 +714,8 @@ class GPEngine:
         S, P = packed[0].shape[0] - 1, packed[4]
         qpack = pack_queries(queries, S, None if noise_pred is None else np.broadcast_to(noise_pred, (P,)), P)
         q_off = qpack[0]
-        weights = _f64(weights)
-        if weights.shape != (P,):
-            raise ValueError(f"weights has shape {weights.shape}, expected ({P},)")
-        slope = icpt = None
-        if y_transforms is not None:
-            yt = _f64(y_transforms)
-            if yt.shape != (S, 2):
-                raise ValueError(f"y_transforms has shape {yt.shape}, expected ({S}, 2): one (slope, intercept) per series")
-            slope, icpt = np.ascontiguousarray(yt[:, 0]), np.ascontiguousarray(yt[:, 1])
+        weights = _particle_weights(weights, P)
+        slope, icpt = _series_transforms(y_transforms, S)
         qa = _f64(np.atleast_1d(q)); nq = qa.shape[0]
         Q = int(q_off[-1])
         x = np.empty(max(1, nq * Q)); conv = np.zeros(max(1, nq * Q), dtype=np.int32); iters = np.zeros(max(1, nq * Q), dtype=np.int32)
@@ -739,14 +752,10 @@ class GPEngine:
         (NaN for a series without particles or with a failed particle, 0 where nothing is held out) — else None."""
         packed = series_call_args(series, nodes, noises, series_index, programs)
         S, P, sidx = packed[0].shape[0] - 1, packed[4], packed[6]
-        if noise_pred is not None and np.ndim(noise_pred) == 0:
-            noise_pred = np.full(P, float(noise_pred))      # (a scalar serves every particle)
-        qpack = pack_queries(queries, S, noise_pred, P)
+        qpack = pack_queries(queries, S, _particle_noise_pred(noise_pred, P), P)
         y_pred, slope = pack_heldout(heldout, qpack[0], y_transforms)
         if weights is not None:
-            weights = _f64(weights)
-            if weights.shape != (P,):
-                raise ValueError(f"weights has shape {weights.shape}, expected ({P},)")
+            weights = _particle_weights(weights, P)
         m_s = np.diff(qpack[0])
         total = int(sum(m_s[i] for i in sidx if 0 <= i < S))      # (an index outside is the library's to report)
         lp = np.empty(max(1, P), dtype=np.float64); info = np.zeros(max(1, P), dtype=np.int32)
@@ -777,21 +786,12 @@ class GPEngine:
         with check)."""
         packed = series_call_args(series, nodes, noises, series_index, programs)
         S, P, sidx = packed[0].shape[0] - 1, packed[4], packed[6]
-        if noise_pred is not None and np.ndim(noise_pred) == 0:
-            noise_pred = np.full(P, float(noise_pred))      # (a scalar serves every particle)
-        qpack = pack_queries(queries, S, noise_pred, P)
+        qpack = pack_queries(queries, S, _particle_noise_pred(noise_pred, P), P)
         qo = qpack[0]
         m_s = np.diff(qo)
         R = int(n_samples)
-        slope = icpt = None
-        if y_transforms is not None:
-            yt = _f64(y_transforms)
-            if yt.shape != (S, 2):
-                raise ValueError(f"y_transforms has shape {yt.shape}, expected ({S}, 2): one (slope, intercept) per series")
-            slope, icpt = np.ascontiguousarray(yt[:, 0]), np.ascontiguousarray(yt[:, 1])
-        weights = _f64(weights)
-        if weights.shape != (P,):
-            raise ValueError(f"weights has shape {weights.shape}, expected ({P},)")
+        slope, icpt = _series_transforms(y_transforms, S)
+        weights = _particle_weights(weights, P)
         seeds = np.arange(S, dtype=np.uint64) if seeds is None else np.ascontiguousarray(np.asarray(seeds, dtype=np.uint64))
         if seeds.shape != (S,):
             raise ValueError(f"seeds has shape {seeds.shape}, expected ({S},): one per series")
@@ -866,15 +866,8 @@ class GPEngine:
         sidx = np.ascontiguousarray(np.asarray(series_index, dtype=np.int32))
         if sidx.shape != (P,):
             raise ValueError("one series index per particle required")
-        if noise_pred is not None and np.ndim(noise_pred) == 0:
-            noise_pred = np.full(P, float(noise_pred))      # (a scalar serves every particle)
-        qpack = pack_queries(queries, S, noise_pred, P)
-        slope = icpt = None
-        if y_transforms is not None:
-            yt = _f64(y_transforms)
-            if yt.shape != (S, 2):
-                raise ValueError(f"y_transforms has shape {yt.shape}, expected ({S}, 2): one (slope, intercept) per series")
-            slope, icpt = np.ascontiguousarray(yt[:, 0]), np.ascontiguousarray(yt[:, 1])
+        qpack = pack_queries(queries, S, _particle_noise_pred(noise_pred, P), P)
+        slope, icpt = _series_transforms(y_transforms, S)
         qa = _f64(np.atleast_1d(np.asarray(q, dtype=np.float64)))
         if qa.ndim != 1:
             raise ValueError("q must be a sequence of quantiles")
