@@ -607,6 +607,21 @@ struct SeriesProbeArgs {
   int32_t* out_info;         // [P]
 };
 
+// Arguments of the probe instantiation k_long_series_logpdf<D, true> (agp_debug_long_series_factor): caller matrices of ONE size
+// take the place of series, programs and noise; the LDS map is long_series_lds(n, 0, 0, 0); workgroup b factors matrix b in
+// ws[b * ws_stride ..), which is the packed-block output as well.
+struct LongSeriesProbeArgs {
+  const double* K;           // [P][n][n] row-major; only the lower triangle is read
+  const double* y;           // [P][n] right-hand sides, or null (zeros)
+  int n;
+  double* ws;                // [P][ws_stride] the packed blocks as the factorisation leaves them
+  long long ws_stride;       // doubles per workgroup, >= 256 nb (nb + 1) / 2
+  double* out_alpha;         // [P][np] avec
+  double* out_part;          // [P][2] 2 sum log L_ii, alpha'alpha
+  double* out_lp;            // [P]
+  int32_t* out_info;         // [P]
+};
+
 // k_poison_rows (NaN-poison mode of the store's sweeps): per buffer b, slot u's doubles [row start(i0[u]), pitch) in slot[u]
 struct PoisonRowsArgs {
   double* base[4];

@@ -30,6 +30,13 @@
 //      three wait; a second workgroup on the CU fills the gap (not measured against a look-ahead variant).
 //   4. out_logpdf[p] = -(n log 2 pi + 2 sum log L_ii + alpha'alpha) / 2, both sums in a fixed order; on a bad pivot NaN and
 //      out_info[p] = the first non-positive pivot, 1-based (each wave keeps the first it saw; the smallest is the first).
+// k_long_series_logpdf<4, true> is the probe (agp_debug_long_series_factor, LongSeriesProbeArgs): stage 1 loads the caller's
+// right-hand side, stage 2 is absent and stage 3 (a) writes the caller's block — in the evaluator's lane map, a diagonal block
+// mirrored from the lower triangle, identity past n — into the block's slot; from the accumulator read-back on, (b) - (e) and stage 4
+// are the statements above.  It also writes out the two partials and alpha; the packed blocks are the workspace.  A translation
+// unit of its own (agp_kernels_long_series_probe.hip), so that the production instantiations compile as they did without it.
+// 246 VGPRs, no AGPRs, 0 VGPRs spilled, scratch 0 bytes per lane, 73 SGPRs kept in VGPR lanes, 2 waves per SIMD (hipcc
+// -Rpass-analysis=kernel-resource-usage, gfx950).
 // A particle's bits depend on its own series, program, parameters and noise only: the LDS map (long_series_lds, agp_args.hpp) is a
 // function of the particle's own sizes, the workspace is the workgroup's own, no value crosses workgroups.
 //
@@ -124,73 +131,99 @@ __device__ __forceinline__ void long_update(d4 (&acc)[LONG_ROWS_PER_WAVE], const
   }
 }
 
-template <int D>
-__global__ __launch_bounds__(256, 2) void k_long_series_logpdf(LongSeriesArgs a) {
+template <int D, bool PROBE = false>
+__global__ __launch_bounds__(256, 2) void k_long_series_logpdf(std::conditional_t<PROBE, LongSeriesProbeArgs, LongSeriesArgs> a) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   constexpr int E = 4, U = LONG_ROWS_PER_WAVE;
   const int tid = threadIdx.x, l = tid & 63, l15 = l & 15, lq = l >> 4;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);      // (on the scalar unit: which block rows a wave owns is wave-uniform control flow)
-  const int p = a.wg[blockIdx.x];
-  const int sidx = a.series[p];
-  const long long o0 = a.pt_off[sidx];
-  const int n = (int)(a.pt_off[sidx + 1] - o0);
+  int p, n;
+  [[maybe_unused]] long long o0 = 0;
+  if constexpr (PROBE) {
+    p = blockIdx.x;
+    n = a.n;
+  } else {
+    p = a.wg[blockIdx.x];
+    const int sidx = a.series[p];
+    o0 = a.pt_off[sidx];
+    n = (int)(a.pt_off[sidx + 1] - o0);
+  }
   if (n <= 0 || n > LONG_SERIES_MAX_N) {      // (the host answers empty series itself and refuses longer ones: never launched)
     if (tid == 0) { a.out_lp[p] = 0.0; a.out_info[p] = 0; }
     return;
   }
-  const ProgHdr h = a.hdr[p];
+  const ProgHdr h = [&]() -> ProgHdr { if constexpr (PROBE) return ProgHdr{}; else return a.hdr[p]; }();
   const LongSeriesLds m = long_series_lds(n, h.n_ops, h.n_prm, h.n_cp);
   const int nb = m.nb, np = m.np;
   double* Wl = smem;
   double* dblk = smem + m.o_dblk;
-  double* tpt = smem + m.o_tpt;
+  [[maybe_unused]] double* tpt = smem + m.o_tpt;      // (tpt, etab, prm, ops, sig: unused by the probe)
   double* rvec = smem + m.o_rvec;
   double* avec = smem + m.o_avec;
   double* ldg = smem + m.o_ldg;
-  double* etab = smem + m.o_etab;
-  double* prm = smem + m.o_prm;
-  int* ops = reinterpret_cast<int*>(smem + m.o_ops);
-  double* sig = smem + m.o_sig;
+  [[maybe_unused]] double* etab = smem + m.o_etab;
+  [[maybe_unused]] double* prm = smem + m.o_prm;
+  [[maybe_unused]] int* ops = reinterpret_cast<int*>(smem + m.o_ops);
+  [[maybe_unused]] double* sig = smem + m.o_sig;
   double* ws = a.ws + (long long)blockIdx.x * a.ws_stride;
 
-  // ---- 1. inputs ----
-  for (int i = tid; i < np; i += 256) {
-    tpt[i] = a.ts[o0 + (i < n ? i : n - 1)];      // (padding points: a finite time; their entries are overwritten with identity)
-    rvec[i] = i < n ? a.xs[o0 + i] : 0.0;
-    avec[i] = 0.0;
-  }
-  if (AGP_EXP_TABLE && tid < AGP_EXP_TAB_N) etab[tid] = fm::c_exp_tab[tid];
-  for (int i = tid; i < h.n_prm + 2; i += 256) prm[i] = a.prm[h.prm_off + i];      // (the parameter buffer carries two doubles of tail padding)
-  for (int i = tid; i < h.n_ops; i += 256) ops[i] = (int)a.ops[h.op_off + i];
-  __syncthreads();
-
-  // ---- 2. per-point tables ----
-  if (h.n_cp > 0) {
-    for (int i = tid; i < np; i += 256) long_sigma_cp(h, ops, prm, sig, i, tpt[i]);
+  // ---- 1. inputs (the probe: the caller's right-hand side) ----
+  if constexpr (PROBE) {
+    for (int i = tid; i < np; i += 256) {
+      rvec[i] = (i < n && a.y != nullptr) ? a.y[(long long)p * n + i] : 0.0;
+      avec[i] = 0.0;
+    }
     __syncthreads();
+  } else {
+    for (int i = tid; i < np; i += 256) {
+      tpt[i] = a.ts[o0 + (i < n ? i : n - 1)];      // (padding points: a finite time; their entries are overwritten with identity)
+      rvec[i] = i < n ? a.xs[o0 + i] : 0.0;
+      avec[i] = 0.0;
+    }
+    if (AGP_EXP_TABLE && tid < AGP_EXP_TAB_N) etab[tid] = fm::c_exp_tab[tid];
+    for (int i = tid; i < h.n_prm + 2; i += 256) prm[i] = a.prm[h.prm_off + i];      // (the parameter buffer carries two doubles of tail padding)
+    for (int i = tid; i < h.n_ops; i += 256) ops[i] = (int)a.ops[h.op_off + i];
+    __syncthreads();
+
+    // ---- 2. per-point tables ----
+    if (h.n_cp > 0) {
+      for (int i = tid; i < np; i += 256) long_sigma_cp(h, ops, prm, sig, i, tpt[i]);
+      __syncthreads();
+    }
   }
 
   // ---- 3. block columns ----
-  const double noise = a.noise[p];
+  [[maybe_unused]] const double noise = [&]() { if constexpr (PROBE) return 0.0; else return a.noise[p]; }();
   int bad = 0;           // first non-positive pivot this wave has seen (1-based index in the series), 0 = none
   for (int j = 0; j < nb; ++j) {
     const int ib0 = j + ((w - j) & 3);      // the wave's first block row at or below j
     // (a) K(ib, j) + noise I -> the block's own slot of the workspace (the lanes that wrote an entry read it back below)
+    // (the probe: the caller's block instead, a diagonal block mirrored from the lower triangle, identity past n as cov_finalize makes it)
     for (int ib = ib0; ib < nb; ib += 4) {
-      double tr[E], tc[E], out[E], lt[E];
-      int ri[E], ci[E];
-#pragma unroll
-      for (int e = 0; e < E; ++e) {
-        ri[e] = ib * 16 + l15;
-        ci[e] = j * 16 + lq + 4 * e;
-        tr[e] = tpt[ri[e]];
-        tc[e] = tpt[ci[e]];
-        lt[e] = 0.0;
-      }
-      eval_program<D, E, 0, false, LONG_SIG_STRIDE>(h, ops, prm, sig, tr, tc, ri, ci, lt, out, etab);
       double* kb = ws + blk_idx(ib, j) * 256;
+      if constexpr (PROBE) {
+        const double* Kp = a.K + (long long)p * n * n;
 #pragma unroll
-      for (int e = 0; e < E; ++e) kb[64 * e + l] = cov_finalize(out[e], ri[e], ci[e], n, np, 0, noise);
+        for (int e = 0; e < E; ++e) {
+          const int ri = ib * 16 + l15, ci = j * 16 + lq + 4 * e;
+          const int hi = ri > ci ? ri : ci, lo = ri > ci ? ci : ri;
+          kb[64 * e + l] = hi < n ? Kp[(long long)hi * n + lo] : (ri == ci ? 1.0 : 0.0);
+        }
+      } else {
+        double tr[E], tc[E], out[E], lt[E];
+        int ri[E], ci[E];
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+          ri[e] = ib * 16 + l15;
+          ci[e] = j * 16 + lq + 4 * e;
+          tr[e] = tpt[ri[e]];
+          tc[e] = tpt[ci[e]];
+          lt[e] = 0.0;
+        }
+        eval_program<D, E, 0, false, LONG_SIG_STRIDE>(h, ops, prm, sig, tr, tc, ri, ci, lt, out, etab);
+#pragma unroll
+        for (int e = 0; e < E; ++e) kb[64 * e + l] = cov_finalize(out[e], ri[e], ci[e], n, np, 0, noise);
+      }
     }
     d4 acc[U];
 #pragma unroll
@@ -314,8 +347,11 @@ __global__ __launch_bounds__(256, 2) void k_long_series_logpdf(LongSeriesArgs a)
       const double lp = -0.5 * ((double)n * 1.8378770664093454835606594728112 + ld + ss);
       a.out_lp[p] = first != 0 ? __builtin_nan("") : lp;
       a.out_info[p] = first;
+      if constexpr (PROBE) { a.out_part[2 * p] = ld; a.out_part[2 * p + 1] = ss; }
     }
   }
+  if constexpr (PROBE)      // alpha as stage 3 left it (the packed blocks are in the workspace)
+    for (int i = tid; i < np; i += 256) a.out_alpha[(long long)p * np + i] = avec[i];
 }
 
 }  // namespace agp

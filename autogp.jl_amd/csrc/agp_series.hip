@@ -1248,6 +1248,22 @@ int predict_sum_series(agp_ctx* c, SeriesCall& sc, const SeriesSumOut& so, doubl
 
 #undef STAGE
 
+// The packed blocks (bel doubles per matrix) and padded alpha (np per matrix) of the two factor probes -> row-major L with zeros above
+// the diagonal, and alpha: element (r, col) of block (rb, cb) sits at col * 16 + r of block rb (rb + 1) / 2 + cb (blk_idx).
+void series_unpack_factor(const double* blk, const double* av, int64_t n, int32_t P, int np, size_t bel, double* out_L, double* out_alpha) {
+  const size_t nel = (size_t)n * n;
+  for (int p = 0; p < P; ++p) {
+    const double* b = blk + (size_t)p * bel;
+    double* L = out_L + (size_t)p * nel;
+    for (int64_t r = 0; r < n; ++r)
+      for (int64_t col = 0; col < n; ++col) {
+        const size_t at = ((size_t)(r / 16) * (r / 16 + 1) / 2 + (size_t)(col / 16)) * 256 + (size_t)(col % 16) * 16 + (size_t)(r % 16);
+        L[r * n + col] = col <= r ? b[at] : 0.0;
+      }
+    std::copy(av + (size_t)p * np, av + (size_t)p * np + n, out_alpha + (size_t)p * n);
+  }
+}
+
 // agp_debug_series_factor: P caller matrices of one size through stages 4 and 5 of the value kernel (its probe instantiation).
 int series_factor(agp_ctx* c, const double* K, const double* y, int64_t n, int32_t P, double* out_L, double* out_alpha,
                   double* out_part, double* out_lp, int32_t* out_info) {
@@ -1286,17 +1302,51 @@ int series_factor(agp_ctx* c, const double* K, const double* y, int64_t n, int32
   HIPCHK(c, hipMemcpyAsync(out_lp, s->out_lp.p, sizeof(double) * (size_t)P, hipMemcpyDeviceToHost, st));
   HIPCHK(c, hipMemcpyAsync(out_info, sa.out_info, sizeof(int32_t) * (size_t)P, hipMemcpyDeviceToHost, st));
   HIPCHK(c, hipStreamSynchronize(st));
-  // element (r, col) of block (rb, cb) sits at col * 16 + r of block rb (rb + 1) / 2 + cb (blk_idx): row-major L, zeros above the diagonal
-  for (int p = 0; p < P; ++p) {
-    const double* b = blk.data() + (size_t)p * bel;
-    double* L = out_L + (size_t)p * nel;
-    for (int64_t r = 0; r < n; ++r)
-      for (int64_t col = 0; col < n; ++col) {
-        const size_t at = ((size_t)(r / 16) * (r / 16 + 1) / 2 + (size_t)(col / 16)) * 256 + (size_t)(col % 16) * 16 + (size_t)(r % 16);
-        L[r * n + col] = col <= r ? b[at] : 0.0;
-      }
-    std::copy(av.begin() + (size_t)p * m.np, av.begin() + (size_t)p * m.np + n, out_alpha + (size_t)p * n);
+  series_unpack_factor(blk.data(), av.data(), n, P, m.np, bel, out_L, out_alpha);
+  return AGP_OK;
+}
+
+// agp_debug_long_series_factor: P caller matrices of one size through stage 3 (b) - (e) and stage 4 of the long-series value kernel
+// (its probe instantiation); the workspace the kernel factors in is read back and unpacked as above.
+int long_series_factor(agp_ctx* c, const double* K, const double* y, int64_t n, int32_t P, double* out_L, double* out_alpha,
+                       double* out_part, double* out_lp, int32_t* out_info) {
+  if (!c) return fail(nullptr, AGP_ERR_ARG, "null context");
+  if (n <= 0 || n > AGP_LONG_SERIES_MAX_N) {
+    char buf[128];
+    snprintf(buf, sizeof buf, "long-series probe: n = %lld outside [1, AGP_LONG_SERIES_MAX_N = %d]", (long long)n, AGP_LONG_SERIES_MAX_N);
+    return fail(c, AGP_ERR_ARG, buf);
   }
+  if (P <= 0 || P > 256) return fail(c, AGP_ERR_ARG, "long-series probe: 1 .. 256 matrices per call");
+  if (!K || !out_L || !out_alpha || !out_part || !out_lp || !out_info) return fail(c, AGP_ERR_ARG, "null pointer argument");
+  const LongSeriesLds m = long_series_lds((int)n, 0, 0, 0);
+  const size_t nel = (size_t)n * n, nblk = (size_t)m.nb * (m.nb + 1) / 2, bel = nblk * 256;
+  HIPCHK(c, hipSetDevice(c->device));
+  SlotGuard sg(c);
+  Slot* s = sg.s;
+  if (!s->stream) HIPCHK(c, hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
+  hipStream_t st = s->stream;
+  HIPCHK(c, s->dense.ensure(sizeof(double) * nel * P));
+  if (y) HIPCHK(c, s->vec.ensure(sizeof(double) * (size_t)n * P));
+  HIPCHK(c, s->A.ensure(sizeof(double) * bel * P));
+  HIPCHK(c, s->alpha.ensure(sizeof(double) * (size_t)m.np * P));
+  HIPCHK(c, s->partial.ensure(sizeof(double) * 2 * (size_t)P));
+  HIPCHK(c, s->out_lp.ensure(sizeof(double) * (size_t)P + sizeof(int32_t) * (size_t)P));
+  HIPCHK(c, hipMemcpyAsync(s->dense.p, K, sizeof(double) * nel * P, hipMemcpyHostToDevice, st));
+  if (y) HIPCHK(c, hipMemcpyAsync(s->vec.p, y, sizeof(double) * (size_t)n * P, hipMemcpyHostToDevice, st));
+  LongSeriesProbeArgs la = {};
+  la.K = s->dense.as<double>(); la.y = y ? s->vec.as<double>() : nullptr; la.n = (int)n;
+  la.ws = s->A.as<double>(); la.ws_stride = (long long)bel;
+  la.out_alpha = s->alpha.as<double>(); la.out_part = s->partial.as<double>();
+  la.out_lp = s->out_lp.as<double>(); la.out_info = reinterpret_cast<int32_t*>(s->out_lp.as<double>() + P);
+  HIPCHK(c, launch_long_series_probe(st, la, P, sizeof(double) * (size_t)m.total));
+  std::vector<double> blk(bel * P), av((size_t)m.np * P);
+  HIPCHK(c, hipMemcpyAsync(blk.data(), s->A.p, sizeof(double) * blk.size(), hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(av.data(), s->alpha.p, sizeof(double) * av.size(), hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(out_part, s->partial.p, sizeof(double) * 2 * (size_t)P, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(out_lp, s->out_lp.p, sizeof(double) * (size_t)P, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(out_info, la.out_info, sizeof(int32_t) * (size_t)P, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  series_unpack_factor(blk.data(), av.data(), n, P, m.np, bel, out_L, out_alpha);
   return AGP_OK;
 }
 
@@ -1418,6 +1468,11 @@ int agp_hmc_series_batch(agp_ctx* c, int32_t S, const int64_t* pt_off, const dou
 int agp_debug_series_factor(agp_ctx* c, const double* K, const double* y, int64_t n, int32_t P, double* out_L, double* out_alpha,
                             double* out_partial, double* out_lp, int32_t* out_info) {
   return abi_guard(c, [&] { return series_factor(c, K, y, n, P, out_L, out_alpha, out_partial, out_lp, out_info); });
+}
+
+int agp_debug_long_series_factor(agp_ctx* c, const double* K, const double* y, int64_t n, int32_t P, double* out_L, double* out_alpha,
+                                 double* out_partial, double* out_lp, int32_t* out_info) {
+  return abi_guard(c, [&] { return long_series_factor(c, K, y, n, P, out_L, out_alpha, out_partial, out_lp, out_info); });
 }
 
 }  // extern "C"

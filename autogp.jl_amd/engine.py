@@ -41,6 +41,7 @@ EXPORTED_SYMBOLS = [
     "agp_predict_series_batch", "agp_debug_remove_factor", "agp_predict_quantile_series_batch",
     "agp_predict_logpdf_series_batch", "agp_predict_sample_series_batch", "agp_predict_sum_series_batch",
     "agp_debug_toeplitz", "agp_debug_cov_sweep", "agp_hmc_series_batch", "agp_logpdf_long_series_batch",
+    "agp_debug_long_series_factor",
 ]
 COMM_ID_BYTES = 128
 SERIES_MAX_N = 176      # AGP_SERIES_MAX_N of include/autogp_hip.h: the longest series of logpdf_series_batch
@@ -170,6 +171,7 @@ def load_library(path=None):
     lib.agp_debug_cholesky.argtypes = [vp, dp, C.c_int64, dp, ip]; lib.agp_debug_cholesky.restype = C.c_int
     lib.agp_debug_factor_batch.argtypes = [vp, dp, dp, C.c_int64, C.c_int32, C.c_int32, dp, dp, dp, ip]; lib.agp_debug_factor_batch.restype = C.c_int
     lib.agp_debug_series_factor.argtypes = [vp, dp, dp, C.c_int64, C.c_int32, dp, dp, dp, dp, ip]; lib.agp_debug_series_factor.restype = C.c_int
+    lib.agp_debug_long_series_factor.argtypes = lib.agp_debug_series_factor.argtypes; lib.agp_debug_long_series_factor.restype = C.c_int
     lib.agp_debug_mfma_probe.argtypes = [vp, dp, dp, dp]; lib.agp_debug_mfma_probe.restype = C.c_int
     lib.agp_debug_mfma_peak.argtypes = [vp, C.c_int32, C.c_int32, dp, dp]; lib.agp_debug_mfma_peak.restype = C.c_int
     lib.agp_debug_math.argtypes = [vp, C.c_int32, dp, dp, dp, C.c_int32]; lib.agp_debug_math.restype = C.c_int
@@ -1305,6 +1307,16 @@ class GPEngine:
         """Factor the matrices K (P, n, n), 1 <= n <= SERIES_MAX_N (lower triangles read), with the Cholesky of logpdf_series_batch's
         kernel (agp_debug_series_factor: the kernel's probe instantiation — the production statements on caller matrices) ->
         L (P, n, n) lower, alpha = L^-1 y (P, n), partial (P, 2) = [2 sum log L_ii, alpha'alpha], logpdf (P), info (P)."""
+        return self._series_factor(self._lib.agp_debug_series_factor, K, y)
+
+    def debug_long_series_factor(self, K, y=None):
+        """Factor the matrices K (P, n, n), 1 <= n <= LONG_SERIES_MAX_N, P <= 256 (lower triangles read), with the block Cholesky of
+        logpdf_long_series_batch's long kernel (agp_debug_long_series_factor: the kernel's probe instantiation — the production
+        statements on caller matrices, the factor in the HBM workspace) -> what debug_series_factor returns:
+        L (P, n, n) lower, alpha = L^-1 y (P, n), partial (P, 2) = [2 sum log L_ii, alpha'alpha], logpdf (P), info (P)."""
+        return self._series_factor(self._lib.agp_debug_long_series_factor, K, y)
+
+    def _series_factor(self, entry, K, y):
         K = np.ascontiguousarray(K, dtype=np.float64)
         if K.ndim != 3 or K.shape[1] != K.shape[2]:
             raise ValueError("K must have shape (P, n, n)")
@@ -1315,7 +1327,7 @@ class GPEngine:
                 raise ValueError("y must have shape (P, n)")
         L = np.empty((P, n, n), dtype=np.float64); alpha = np.empty((P, n), dtype=np.float64)
         part = np.empty((P, 2), dtype=np.float64); lp = np.empty(P, dtype=np.float64); info = np.zeros(P, dtype=np.int32)
-        self._check(self._lib.agp_debug_series_factor(self._ctx, _dp(K), _dp(y), n, P, _dp(L), _dp(alpha), _dp(part), _dp(lp), _ip(info)))
+        self._check(entry(self._ctx, _dp(K), _dp(y), n, P, _dp(L), _dp(alpha), _dp(part), _dp(lp), _ip(info)))
         return L, alpha, part, lp, info
 
     def debug_remove_factor(self, L0, alpha0, idx):

@@ -1070,6 +1070,19 @@ int agp_debug_series_factor(agp_ctx* ctx, const double* K /* P*n*n */, const dou
                             double* out_L /* P*n*n */, double* out_alpha /* P*n */, double* out_partial /* P*2 */,
                             double* out_lp /* P */, int32_t* out_info /* P */);
 
+/* Factor P caller-supplied matrices of ONE size 1 <= n <= AGP_LONG_SERIES_MAX_N with the factorisation of
+ * agp_logpdf_long_series_batch's long kernel: a second instantiation of that kernel writes block (ib, j) of matrix p (K, y: as for
+ * agp_debug_series_factor) into the block's slot of the workgroup's HBM workspace where the production instantiations write the
+ * covariance they evaluate (rows and columns past n: identity), then runs the SAME statements — left-looking block columns on the
+ * packed workspace, panel products with the explicit inverse of the diagonal block, forward solve carried from registers with one
+ * refinement step per block, log-det and quadratic form, first bad pivot — and hands back what they leave, in the shapes of
+ * agp_debug_series_factor: out_L, out_alpha, out_partial, out_lp (NaN where out_info != 0), out_info.
+ * AGP_ERR_ARG: n < 1, n > AGP_LONG_SERIES_MAX_N, P < 1 or P > 256, any null pointer but y.  Borrows a workspace slot and reads or
+ * changes nothing else the context holds.  A failed matrix leaves the others untouched. */
+int agp_debug_long_series_factor(agp_ctx* ctx, const double* K /* P*n*n */, const double* y /* P*n or NULL */, int64_t n, int32_t P,
+                                 double* out_L /* P*n*n */, double* out_alpha /* P*n */, double* out_partial /* P*2 */,
+                                 double* out_lp /* P */, int32_t* out_info /* P */);
+
 /* Run agp_remove_data's update of resident factors on P caller-supplied factors of ONE size 2 <= n <= 1024.  Factor p (L0: P blocks of
  * n x n, row-major; only the lower triangle r >= c at L0[r * n + c] is read) and its forward-solve vector (alpha0: P x n; NULL:
  * zeros) are packed into arrays of the factor store's layout (tiles with the identity padding of the dense packer, inverse blocks
