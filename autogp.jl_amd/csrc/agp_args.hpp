@@ -594,6 +594,31 @@ __host__ __device__ inline LongSeriesLds long_series_lds(int n, int n_ops, int n
   return m;
 }
 
+// Long-series predictive twin (k_long_series_predict, agp_predict_long_series_batch): the short predictive twin's arguments and the
+// workspace.  Stage P's query blocks (16 times each) run in rounds of LONG_PRED_C blocks per wave.  Workspace of a particle with
+// nb block rows, in blocks of 256 doubles:
+//   rows 0 .. nb - 1 of the packed triangle | rows nb .. nb + 4 LONG_PRED_C - 1 of the same packing: the round's scratch rows, row
+//   nb + w + 4 u is chain u of wave w (blocks 0 .. nb - 1: VT(q, k); block nb: k(t*, t*)) | nb blocks W(j) = L(j, j)^-1
+// — long_series_pred_ws_blocks(nb); it does not grow with the number of query times.  ws_stride >= 256 times that for every
+// particle of the launch.
+constexpr int LONG_PRED_C = 2;
+constexpr int LONG_PRED_QSLOT = LONG_SERIES_MAX_N;      // per-point tables: the round's query entries behind the series' own
+constexpr int LONG_PRED_SIG_STRIDE = LONG_PRED_QSLOT + 4 * LONG_PRED_C * 16;
+struct LongSeriesPredArgs : SeriesPredArgs {
+  double* ws;
+  long long ws_stride;       // doubles per workgroup
+};
+__host__ __device__ inline long long long_series_ws_blocks(int nb) { return (long long)nb * (nb + 1) / 2; }
+__host__ __device__ inline long long long_series_pred_ws_blocks(int nb) { return long_series_ws_blocks(nb + 4 * LONG_PRED_C) + nb; }
+// LDS map: the value kernel's, array for array, with per-point tables of LONG_PRED_SIG_STRIDE entries — sigma_cp of chain u of wave
+// w at its 16 query times sits in entries LONG_PRED_QSLOT + 16 (LONG_PRED_C w + u) .. + 15.  At 512 points: 21 KiB + the program + 5
+// KiB per ChangePoint node — 71 KiB beside 10 nodes (two workgroups still share a CU); 160 KiB hold 27 nodes beside a small program.
+__host__ __device__ inline LongSeriesLds long_series_pred_lds(int n, int n_ops, int n_prm, int n_cp) {
+  LongSeriesLds m = long_series_lds(n, n_ops, n_prm, 0);
+  m.total = m.o_sig + n_cp * LONG_PRED_SIG_STRIDE;
+  return m;
+}
+
 // Arguments of the probe instantiation k_series_logpdf<D, true> (agp_debug_series_factor): caller matrices of ONE size take the place
 // of series, programs and noise; the LDS map is series_lds(n, 0, 0, 0); workgroup b factors matrix b.
 struct SeriesProbeArgs {

@@ -4,6 +4,7 @@
 //   agp_kernels_series.hip  small-matrix value kernel and its value-and-gradient twin (one workgroup per particle of a short series)
 //   agp_kernels_long_series.hip  long-series value kernel (one workgroup per particle of a series of up to 512 points, factor in HBM)
 //   agp_kernels_long_series_probe.hip  its probe instantiation (caller matrices; agp_debug_long_series_factor)
+//   agp_kernels_long_series_predict.hip  its predictive twin (the posterior at the series' own query times behind the value)
 // Every template instantiation lives behind one of these plain functions, so the units compile in parallel and the
 // function attributes (dynamic-LDS ceilings) are set on the copies that are actually launched.
 #pragma once
@@ -109,6 +110,12 @@ hipError_t kernels_init_long_series();   // raises the dynamic-LDS ceiling of k_
 // long-series value kernel: one workgroup per entry of la.wg (`grid` of them), each with la.ws_stride doubles of la.ws for its factor;
 // evaluation-stack depth 4 / 8, lds_bytes = the largest long_series_lds total of the launch's particles
 hipError_t launch_long_series_logpdf(hipStream_t st, const LongSeriesArgs& la, int grid, int depth, size_t lds_bytes);
+
+// ---- agp_kernels_long_series_predict.hip -----------------------------------------------------------------------------
+hipError_t kernels_init_long_series_predict();   // the same ceiling for k_long_series_predict (once, agp_init)
+// predictive twin: the launch above with the query side; lds_bytes = the largest long_series_pred_lds total of the launch's
+// particles, la.ws_stride >= 256 long_series_pred_ws_blocks(nb) for each of them
+hipError_t launch_long_series_predict(hipStream_t st, const LongSeriesPredArgs& la, int grid, int depth, size_t lds_bytes);
 
 // ---- agp_kernels_long_series_probe.hip -------------------------------------------------------------------------------
 // one workgroup per caller matrix: lds_bytes = long_series_lds(la.n, 0, 0, 0), la.ws_stride >= 256 nb (nb + 1) / 2

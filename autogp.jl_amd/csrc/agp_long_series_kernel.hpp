@@ -37,6 +37,10 @@
 // unit of its own (agp_kernels_long_series_probe.hip), so that the production instantiations compile as they did without it.
 // 246 VGPRs, no AGPRs, 0 VGPRs spilled, scratch 0 bytes per lane, 73 SGPRs kept in VGPR lanes, 2 waves per SIMD (hipcc
 // -Rpass-analysis=kernel-resource-usage, gfx950).
+// k_long_series_predict<D> = k_long_series_logpdf<D, false, LongSeriesPredArgs> is the predictive twin (agp_predict_long_series_batch):
+// per-point tables of LONG_PRED_SIG_STRIDE entries, factor16<true> also leaves W(j) = L(j, j)^-1 behind the triangle, and stage P
+// (below, behind stage 4) forms the posterior at the series' own query times.  A unit of its own as well
+// (agp_kernels_long_series_predict.hip, which records its registers, LDS and workspace).
 // A particle's bits depend on its own series, program, parameters and noise only: the LDS map (long_series_lds, agp_args.hpp) is a
 // function of the particle's own sizes, the workspace is the workgroup's own, no value crosses workgroups.
 //
@@ -59,13 +63,14 @@ static_assert(LONG_ROWS_PER_WAVE * 64 == LONG_SERIES_MAX_N, "the cap is whole ro
 static_assert(LONG_SIG_STRIDE >= LONG_SERIES_MAX_N, "a per-point table holds the whole series");
 
 // sigma_cp (src/GP.jl:481-483) of every ChangePoint node at time t -> entry `slot` of the node's table (series_sigma_cp's arithmetic)
+template <int STRIDE = LONG_SIG_STRIDE>
 __device__ __forceinline__ void long_sigma_cp(const ProgHdr& h, const int* ops, const double* prm, double* sig, int slot, double t) {
   int q = 0, c = 0;
   for (int ip = 0; ip < h.n_ops; ++ip) {
     const int o = ops[ip];
     if (o == OP_CP || o == OP_CP_SWAP) {
       const double loc = prm[q], sc = prm[q + 1];
-      sig[c * LONG_SIG_STRIDE + slot] = 0.5 * (1.0 + tanh((loc - t) / sc));
+      sig[c * STRIDE + slot] = 0.5 * (1.0 + tanh((loc - t) / sc));
       ++c;
     }
     q += prm_count(o);
@@ -131,9 +136,16 @@ __device__ __forceinline__ void long_update(d4 (&acc)[LONG_ROWS_PER_WAVE], const
   }
 }
 
-template <int D, bool PROBE = false>
-__global__ __launch_bounds__(256, 2) void k_long_series_logpdf(std::conditional_t<PROBE, LongSeriesProbeArgs, LongSeriesArgs> a) {
+// One body for the value kernel, its probe and the predictive twin, selected by the argument type (as series_body is for the short
+// family): every statement of the twin's own is behind PRED.  The body is the kernel itself, not a function the three kernels call:
+// inlined from a function its early returns become branches to a common end, and the value and the probe instantiation then
+// allocate their registers differently (tried: by reference, by value, the LDS symbol declared inside).  As it stands their
+// instructions are those of the kernel without the twin; their symbols carry the argument type.
+template <int D, bool PROBE = false, class ArgsT = std::conditional_t<PROBE, LongSeriesProbeArgs, LongSeriesArgs>>
+__global__ __launch_bounds__(256, 2) void k_long_series_logpdf(ArgsT a) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
+  constexpr bool PRED = std::is_same_v<ArgsT, LongSeriesPredArgs>;
+  constexpr int STRIDE = PRED ? LONG_PRED_SIG_STRIDE : LONG_SIG_STRIDE;      // entries of one per-point table
   constexpr int E = 4, U = LONG_ROWS_PER_WAVE;
   const int tid = threadIdx.x, l = tid & 63, l15 = l & 15, lq = l >> 4;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);      // (on the scalar unit: which block rows a wave owns is wave-uniform control flow)
@@ -153,7 +165,7 @@ __global__ __launch_bounds__(256, 2) void k_long_series_logpdf(std::conditional_
     return;
   }
   const ProgHdr h = [&]() -> ProgHdr { if constexpr (PROBE) return ProgHdr{}; else return a.hdr[p]; }();
-  const LongSeriesLds m = long_series_lds(n, h.n_ops, h.n_prm, h.n_cp);
+  const LongSeriesLds m = PRED ? long_series_pred_lds(n, h.n_ops, h.n_prm, h.n_cp) : long_series_lds(n, h.n_ops, h.n_prm, h.n_cp);
   const int nb = m.nb, np = m.np;
   double* Wl = smem;
   double* dblk = smem + m.o_dblk;
@@ -166,6 +178,8 @@ __global__ __launch_bounds__(256, 2) void k_long_series_logpdf(std::conditional_
   [[maybe_unused]] int* ops = reinterpret_cast<int*>(smem + m.o_ops);
   [[maybe_unused]] double* sig = smem + m.o_sig;
   double* ws = a.ws + (long long)blockIdx.x * a.ws_stride;
+  [[maybe_unused]] double* wsW = nullptr;      // PRED: the nb inverses W(j) behind the triangle and the round's scratch rows
+  if constexpr (PRED) wsW = ws + long_series_ws_blocks(nb + 4 * LONG_PRED_C) * 256;
 
   // ---- 1. inputs (the probe: the caller's right-hand side) ----
   if constexpr (PROBE) {
@@ -187,7 +201,7 @@ __global__ __launch_bounds__(256, 2) void k_long_series_logpdf(std::conditional_
 
     // ---- 2. per-point tables ----
     if (h.n_cp > 0) {
-      for (int i = tid; i < np; i += 256) long_sigma_cp(h, ops, prm, sig, i, tpt[i]);
+      for (int i = tid; i < np; i += 256) long_sigma_cp<STRIDE>(h, ops, prm, sig, i, tpt[i]);
       __syncthreads();
     }
   }
@@ -220,7 +234,7 @@ __global__ __launch_bounds__(256, 2) void k_long_series_logpdf(std::conditional_
           tc[e] = tpt[ci[e]];
           lt[e] = 0.0;
         }
-        eval_program<D, E, 0, false, LONG_SIG_STRIDE>(h, ops, prm, sig, tr, tc, ri, ci, lt, out, etab);
+        eval_program<D, E, 0, false, STRIDE>(h, ops, prm, sig, tr, tc, ri, ci, lt, out, etab);
 #pragma unroll
         for (int e = 0; e < E; ++e) kb[64 * e + l] = cov_finalize(out[e], ri[e], ci[e], n, np, 0, noise);
       }
@@ -253,7 +267,8 @@ __global__ __launch_bounds__(256, 2) void k_long_series_logpdf(std::conditional_
     if (w == (j & 3)) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) dblk[64 * r + l] = acc[0][r];
-      factor16<false>(dblk, Wl, nullptr, 0, j * 16, bad, l);
+      if constexpr (PRED) factor16<true>(dblk, Wl, wsW + j * 256, 0, j * 16, bad, l);      // (W(j) also to its slot behind the triangle)
+      else factor16<false>(dblk, Wl, nullptr, 0, j * 16, bad, l);
     }
     __syncthreads();
     // (d) panel L(ib, j) = S(ib, j) W' -> workspace; alpha_j, 2 log L_ii
@@ -352,6 +367,125 @@ __global__ __launch_bounds__(256, 2) void k_long_series_logpdf(std::conditional_
   }
   if constexpr (PROBE)      // alpha as stage 3 left it (the packed blocks are in the workspace)
     for (int i = tid; i < np; i += 256) a.out_alpha[(long long)p * np + i] = avec[i];
+
+  if constexpr (PRED) {
+    // ---- P. the posterior at the series' own query times: mean = VT alpha, var = (k(t*, t*) - rowsums(VT^2)) + noise_pred, VT = K21 L^-T.
+    // Behind stage 4's barrier the factor, the inverses W(j), alpha (avec; padding: 0), tpt, the program and its tables are
+    // read-only and the four first-bad-pivot words in dblk are written: no further workgroup barrier.  Query block qb (16 times)
+    // belongs to wave qb % 4; a wave runs its blocks in rounds of up to LONG_PRED_C chains, chain u in scratch row nb + w + 4 u:
+    //   sigma_cp of the chain's 16 times -> entries LONG_PRED_QSLOT + 16 (LONG_PRED_C w + u) .. of every per-point table (wave-local);
+    //   for j = 0 .. nb - 1: K21(q, j) by the evaluator on stage 3's lane map (columns past n: 0) -> block j of the scratch row, and
+    //     back as the accumulator; S(q, j) = K21(q, j) - sum_{k < j} VT(q, k) L(j, k)' by long_update, the chains sharing L(j, k);
+    //     VT(q, j) = S(q, j) W(j)' -> block j of the scratch row (accumulator and operand layout coincide, blk[64 r + l]: a lane
+    //     reads back only what it stored itself); the lane's share of mean and of rowsums(VT^2), ascending in (j, r);
+    //   "block" nb: k(t*, t*) through the same call of the evaluator, row and column both the query, by way of block nb of the row;
+    //   the four lane groups of a row in the order ((q0 + q1) + q2) + q3.
+    // Rows past mq evaluate the last query time again and are not written; a chain's arithmetic is the same whichever round and
+    // whichever count of chains it runs in (long_update's chains are independent).
+    constexpr int C = LONG_PRED_C;
+    const int sidx = a.series[p];
+    const long long q0 = a.q_off[sidx];
+    const int mq = (int)(a.q_off[sidx + 1] - q0);
+    if (mq <= 0) return;
+    double* om = a.out_mean + a.out_off[p];
+    double* ov = a.out_var + a.out_off[p];
+    if (dblk[0] != 0.0 || dblk[1] != 0.0 || dblk[2] != 0.0 || dblk[3] != 0.0) {      // a bad pivot: NaN in the particle's whole block
+      for (int q = tid; q < mq; q += 256) { om[q] = __builtin_nan(""); ov[q] = __builtin_nan(""); }
+      return;
+    }
+    const double* tq = a.ts_pred + q0;
+    const double noise_pred = a.noise_pred[p];
+    const int row0 = nb + w;      // the wave's first scratch row
+    for (int qb0 = w; qb0 * 16 < mq; qb0 += 4 * C) {
+      const int left = (mq - qb0 * 16 + 63) / 64;      // the wave's query blocks from qb0 on
+      const int cnt = left < C ? left : C;
+      double tqu[C], ms[C], ss[C], kd[C];
+#pragma unroll
+      for (int u = 0; u < C; ++u) {
+        const int qi = (qb0 + 4 * u) * 16 + l15;
+        tqu[u] = tq[qi < mq ? qi : mq - 1];
+        ms[u] = 0.0; ss[u] = 0.0; kd[u] = 0.0;
+        if (h.n_cp > 0 && u < cnt && l < 16) long_sigma_cp<STRIDE>(h, ops, prm, sig, LONG_PRED_QSLOT + 16 * (C * w + u) + l15, tqu[u]);
+      }
+      __builtin_amdgcn_wave_barrier();      // (LDS operations of one wave complete in order: its own lanes' entries)
+      for (int j = 0; j <= nb; ++j) {
+        const bool self = j == nb;
+        // K21(q_u, j) (self: k(t*, t*), every register alike) -> block j of scratch row u
+        for (int u = 0; u < cnt; ++u) {
+          const int slot = LONG_PRED_QSLOT + 16 * (C * w + u) + l15;
+          double tr[E], tc[E], out[E], lt[E];
+          int ri[E], ci[E];
+          double tu = tqu[0];
+#pragma unroll
+          for (int v = 1; v < C; ++v) tu = u == v ? tqu[v] : tu;
+#pragma unroll
+          for (int e = 0; e < E; ++e) {
+            ri[e] = slot;
+            ci[e] = self ? slot : j * 16 + lq + 4 * e;
+            tr[e] = tu;
+            tc[e] = self ? tu : tpt[ci[e]];
+            lt[e] = 0.0;
+          }
+          eval_program<D, E, 0, false, STRIDE>(h, ops, prm, sig, tr, tc, ri, ci, lt, out, etab);
+          double* kb = ws + blk_idx(row0 + 4 * u, j) * 256;
+#pragma unroll
+          for (int e = 0; e < E; ++e) kb[64 * e + l] = (self || ci[e] < n) ? out[e] : 0.0;
+        }
+        if (self) {
+#pragma unroll
+          for (int u = 0; u < C; ++u)
+            if (u < cnt) kd[u] = ws[blk_idx(row0 + 4 * u, j) * 256 + l];
+          break;
+        }
+        d4 acc[U];
+#pragma unroll
+        for (int u = 0; u < C; ++u) {
+          acc[u] = d4{0.0, 0.0, 0.0, 0.0};
+          if (u < cnt) {
+            const double* kb = ws + blk_idx(row0 + 4 * u, j) * 256;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) acc[u][r] = kb[64 * r + l];
+          }
+        }
+        if (j > 0) {
+          static_assert(C == 2, "one loop body per number of chains");
+          if (cnt == 1) long_update<1>(acc, ws, j, row0, l);
+          else long_update<2>(acc, ws, j, row0, l);
+        }
+        double fw[4], al[4];
+#pragma unroll
+        for (int s4 = 0; s4 < 4; ++s4) { fw[s4] = wsW[j * 256 + 64 * s4 + l]; al[s4] = avec[j * 16 + 4 * s4 + lq]; }
+#pragma unroll
+        for (int u = 0; u < C; ++u)
+          if (u < cnt) {
+            d4 x = d4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+            for (int s4 = 0; s4 < 4; ++s4) x = mfma(fw[s4], acc[u][s4], x);
+            double* vb = ws + blk_idx(row0 + 4 * u, j) * 256;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              vb[64 * r + l] = x[r];
+              ms[u] = fma(x[r], al[r], ms[u]);
+              ss[u] = fma(x[r], x[r], ss[u]);
+            }
+          }
+      }
+#pragma unroll
+      for (int u = 0; u < C; ++u)
+        if (u < cnt) {
+          const double mean = ((__shfl(ms[u], l15) + __shfl(ms[u], l15 + 16)) + __shfl(ms[u], l15 + 32)) + __shfl(ms[u], l15 + 48);
+          const double sq = ((__shfl(ss[u], l15) + __shfl(ss[u], l15 + 16)) + __shfl(ss[u], l15 + 32)) + __shfl(ss[u], l15 + 48);
+          const int qi = (qb0 + 4 * u) * 16 + l15;
+          if (l < 16 && qi < mq) {
+            om[qi] = mean;
+            ov[qi] = (kd[u] - sq) + noise_pred;
+          }
+        }
+    }
+  }
 }
+
+// The predictive twin (agp_predict_long_series_batch; agp_kernels_long_series_predict.hip has its figures)
+template <int D> constexpr auto k_long_series_predict = &k_long_series_logpdf<D, false, LongSeriesPredArgs>;
 
 }  // namespace agp

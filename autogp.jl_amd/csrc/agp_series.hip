@@ -7,6 +7,8 @@
 //   agp_hmc_series_batch               k_series_hmc: the gradient kernel's statements in a loop — HMC moves of every particle's parameters
 //                                      and noise in the reference's latent space, the whole chain of a particle in one workgroup
 //   agp_predict_series_batch           k_series_predict: posterior mean and marginal variance at every series' own query times
+//   agp_predict_long_series_batch      the same forecast for series of up to AGP_LONG_SERIES_MAX_N points: k_series_predict up to the short
+//                                      cap, k_long_series_predict above it; agp_predict_quantile_long_series_batch: its band
 //   agp_predict_quantile_series_batch  the predictive launches, their device outputs read out by agp_series_quantile_kernel.hpp on
 //                                      the same stream: quantiles and marginal moments of every series' own mixture
 //   agp_predict_logpdf_series_batch    k_series_predict_logpdf: the value kernel on the joint points, the query rows' partials read out —
@@ -164,8 +166,10 @@ void quant_fill_nan(const SeriesQuantOut& qo, size_t from, size_t to, int64_t nq
 // Which kernel the call launches: it chooses the LDS map, the instantiation rule and (gradient) the tape's limit.
 // long_value: the value entry for series of up to AGP_LONG_SERIES_MAX_N points — a particle above the short cap (or every particle,
 // SeriesCall::all_long) takes k_long_series_logpdf and its map, the others are the value mode's.
-enum class SeriesMode { value, gradient, prediction, held_out, sum, hmc, long_value };
-constexpr int SERIES_LONG_CLASS = 3;      // launch classes 3, 4: k_long_series_logpdf<4 / 8> (0 .. 2: the mode's short kernels)
+// long_prediction: the same routing for the forecast and the band — k_long_series_predict and its map above the short cap, the
+// prediction mode's kernel and map below it.
+enum class SeriesMode { value, gradient, prediction, held_out, sum, hmc, long_value, long_prediction };
+constexpr int SERIES_LONG_CLASS = 3;      // launch classes 3, 4: the long kernel<4 / 8> of the mode (0 .. 2: the mode's short kernels)
 
 // One call of a many-series entry: the caller's inputs and what each shared stage leaves for the later ones.
 struct SeriesCall {
@@ -177,6 +181,7 @@ struct SeriesCall {
   const char* max_name = "AGP_SERIES_MAX_N";
   bool all_long = false;             // long entry: every non-empty series takes the long kernel (AGP_LONG_SERIES_ALL)
   bool long_route(int n) const { return n > SERIES_MAX_N || (all_long && n > 0); }
+  long long (*ws_blocks)(int) = long_series_ws_blocks;      // long entries: workspace blocks of a workgroup with nb block rows
   // series_classes
   Batch bt;                          // programs without any table of the resident series (no log|dt| table, no lag tables), caller's order
   std::vector<int> len;              // [P] points of the particle's series
@@ -195,6 +200,8 @@ struct SeriesCall {
   // series_launch
   bool prof = false; hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
   bool readout = false;              // ev[2] was recorded behind the entry's read-out kernels (series_mark_readout)
+  int64_t ws_limit = 0;              // series_long_workspace: the bytes one long launch's workspace may take
+  bool ws_used = false;              // series_launch_long: a long launch of this call has used the workspace
   size_t n_out() const { return ooff.empty() ? 0 : (size_t)ooff.back(); }
   size_t values_bytes() const { return sizeof(double) * (size_t)pp.P + sizeof(int32_t) * (size_t)pp.P; }
   template <class T> T* in_map(size_t off) const { return reinterpret_cast<T*>(s->map.as<char>() + off); }
@@ -273,7 +280,10 @@ int series_check_joint(agp_ctx* c, const SeriesCall& sc, int32_t s, const char* 
 // value kernel's map): the mode's own map
 size_t series_need(SeriesMode mode, const Batch& bt, int p, int n, int hmc_C = 0, bool long_route = false) {
   const ProgHdr& h = bt.hdr[(size_t)p];
-  const int m_total = long_route ? long_series_lds(n, h.n_ops, h.n_prm, h.n_cp).total
+  const bool long_pred = mode == SeriesMode::long_prediction;
+  if (long_pred && !long_route) mode = SeriesMode::prediction;      // (below the short cap: the prediction mode's kernel and map)
+  const int m_total = long_route ? (long_pred ? long_series_pred_lds(n, h.n_ops, h.n_prm, h.n_cp).total
+                                               : long_series_lds(n, h.n_ops, h.n_prm, h.n_cp).total)
                       : mode == SeriesMode::hmc ? series_hmc_lds(n, h.n_ops, h.n_prm, h.n_cp, bt.ghdr[(size_t)p].n_ops, bt.ghdr[(size_t)p].n_prm, hmc_C).total
                       : mode == SeriesMode::gradient ? series_grad_lds(n, h.n_ops, h.n_prm, h.n_cp, bt.ghdr[(size_t)p].n_ops, bt.ghdr[(size_t)p].n_prm).total
                       : mode == SeriesMode::prediction || mode == SeriesMode::sum ? series_pred_lds(n, h.n_ops, h.n_prm, h.n_cp).total
@@ -324,7 +334,7 @@ int series_classes(agp_ctx* c, SeriesCall& sc, SeriesMode mode) {
     // n_s + m_s; nothing held out scores 0 without a launch, as an empty series does in the value entry
     if (mode == SeriesMode::held_out) sc.len[(size_t)p] = n = sc.nq[(size_t)p] > 0 ? n + (int)sc.nq[(size_t)p] : 0;
     if (n == 0 && sc.nq[(size_t)p] == 0) continue;      // (an empty series is launched for its prior predictive only)
-    const bool lng = mode == SeriesMode::long_value && sc.long_route(n);
+    const bool lng = (mode == SeriesMode::long_value || mode == SeriesMode::long_prediction) && sc.long_route(n);
     const size_t need = sc.need[(size_t)p] = series_need(mode, bt, p, n, sc.hmc_C, lng);
     if (need > (size_t)SERIES_LDS_BYTES) {
       snprintf(buf, sizeof buf, "particle %d: %d per-point tables (%s) at %d points need %zu bytes of LDS, more than the "
@@ -485,18 +495,6 @@ template <class Launch> int series_launch(agp_ctx* c, SeriesCall& sc, Launch&& l
   return AGP_OK;
 }
 
-// the predictive launches of a staged call with queries: means and variances into pred_mean / pred_var, where they stay
-int series_launch_predict(agp_ctx* c, SeriesCall& sc) {
-  Slot* s = sc.s;
-  SeriesPredArgs pa = {};
-  series_query_args(sc, pa);
-  pa.out_mean = s->pred_mean.as<double>(); pa.out_var = s->pred_var.as<double>();
-  return series_launch(c, sc, [&](const int32_t* wg, int grid, int d, size_t lds) {
-    pa.wg = wg;
-    return launch_series_predict(sc.st, pa, grid, d == 0 ? 4 : 8, lds);
-  });
-}
-
 // the end of the profiled read-out span: behind the entry's read-out kernels, ahead of the copies
 int series_mark_readout(agp_ctx* c, SeriesCall& sc) {
   if (sc.prof) HIPCHK(c, hipEventRecord(sc.ev[2], sc.st));
@@ -545,18 +543,74 @@ int series_timing(agp_ctx* c, const SeriesCall& sc) {
   return AGP_OK;
 }
 
-// The long kernel's launches of one class: the particles hv[0 .. grid) (longest first) in chunks whose factors fit `limit` bytes of
-// workspace together — every workgroup of a chunk gets the chunk's largest triangle, that of its first particle; a chunk is never
-// empty.  f(first, count, stride in doubles) -> hipError_t.
+// The long kernel's launches of one class: the particles hv[0 .. grid) (longest first) in chunks whose workspaces fit `limit` bytes
+// together — every workgroup of a chunk gets the chunk's largest workspace, that of its first particle (sc.ws_blocks: the mode's
+// blocks per workgroup); a chunk is never empty.  f(first, count, stride in doubles) -> hipError_t.
 template <class F> hipError_t long_chunks(const SeriesCall& sc, const int32_t* hv, int grid, int64_t limit, F&& f) {
   for (int i = 0; i < grid;) {
     const int nb = (sc.len[(size_t)hv[i]] + BS - 1) / BS;
-    const long long stride = (long long)(nb * (nb + 1) / 2) * 256;
+    const long long stride = sc.ws_blocks(nb) * 256;
     const int cnt = (int)std::max<int64_t>(1, std::min<int64_t>(grid - i, limit / (int64_t)(stride * sizeof(double))));
     if (const hipError_t e = f(i, cnt, stride)) return e;
     i += cnt;
   }
   return hipSuccess;
+}
+
+// the long launches' workspace (the slot's A) at the size of the call's largest chunk, before anything is launched: the launches
+// share it in stream order.  Bounded by the call's workspace limit and 1 GiB.  A call without long classes takes none.
+int series_long_workspace(agp_ctx* c, SeriesCall& sc) {
+  sc.ws_limit = std::min<int64_t>(ws_limit_bytes(c), (int64_t)1 << 30);
+  size_t ws_bytes = 0;
+  const int32_t* hv = sc.wg.data();
+  for (int d = 0; d < 5; ++d)
+    for (int k = 0; k < 3; ++k) {
+      const int grid = (int)sc.list[d][k].size();
+      if (d >= SERIES_LONG_CLASS)
+        (void)long_chunks(sc, hv, grid, sc.ws_limit, [&](int, int cnt, long long stride) {
+          ws_bytes = std::max(ws_bytes, sizeof(double) * (size_t)cnt * (size_t)stride);
+          return hipSuccess;
+        });
+      hv += grid;
+    }
+  if (ws_bytes > 0) HIPCHK(c, sc.s->A.ensure(ws_bytes));
+  return AGP_OK;
+}
+
+// one long class of a staged call (series_launch's wg, grid), chunk by chunk: la is the kernel's arguments but for wg and the
+// workspace; launch(la, count) -> hipError_t
+template <class Args, class Launch>
+hipError_t series_launch_long(agp_ctx* c, SeriesCall& sc, const int32_t* wg, int grid, Args la, Launch&& launch) {
+  const int32_t* hv = sc.wg.data() + (wg - sc.in_map<const int32_t>(sc.o_wg));
+  return long_chunks(sc, hv, grid, sc.ws_limit, [&](int first, int cnt, long long stride) {
+    // (NaN-poison mode: a later launch must not find an earlier one's finished blocks in the workspace)
+    if (sc.ws_used && c->poison.active())
+      if (const hipError_t e = sc.s->A.poison_async(sc.st)) return e;
+    sc.ws_used = true;
+    la.wg = wg + first;
+    la.ws = sc.s->A.as<double>(); la.ws_stride = stride;
+    return launch(la, cnt);
+  });
+}
+
+// the predictive launches of a staged call with queries: means and variances into pred_mean / pred_var, where they stay.  The long
+// classes of mode long_prediction (series_long_workspace has run): k_long_series_predict, chunk by chunk.
+int series_launch_predict(agp_ctx* c, SeriesCall& sc) {
+  Slot* s = sc.s;
+  SeriesPredArgs pa = {};
+  series_query_args(sc, pa);
+  pa.out_mean = s->pred_mean.as<double>(); pa.out_var = s->pred_var.as<double>();
+  return series_launch(c, sc, [&](const int32_t* wg, int grid, int d, size_t lds) {
+    if (d < SERIES_LONG_CLASS) {
+      pa.wg = wg;
+      return launch_series_predict(sc.st, pa, grid, d == 0 ? 4 : 8, lds);
+    }
+    LongSeriesPredArgs la = {};
+    static_cast<SeriesPredArgs&>(la) = pa;
+    return series_launch_long(c, sc, wg, grid, la, [&](const LongSeriesPredArgs& a, int cnt) {
+      return launch_long_series_predict(sc.st, a, cnt, d == SERIES_LONG_CLASS ? 4 : 8, lds);
+    });
+  });
 }
 
 // mode value: agp_logpdf_series_batch; mode long_value: agp_logpdf_long_series_batch — the same stages, the long particles' launches
@@ -569,42 +623,18 @@ int logpdf_series(agp_ctx* c, SeriesCall& sc, double* out_logpdf, int32_t* out_i
   STAGE(series_classes(c, sc, mode));
   if (sc.wg.empty()) { series_zero_values(sc, out_logpdf, out_info); return AGP_OK; }
   STAGE(series_stage(c, sc));
-  // (the workspace at the size of the call's largest chunk, before anything is launched: the launches share it in stream order)
-  const int64_t ws_limit = std::min<int64_t>(ws_limit_bytes(c), (int64_t)1 << 30);
-  {
-    size_t ws_bytes = 0;
-    const int32_t* hv = sc.wg.data();
-    for (int d = 0; d < 5; ++d)
-      for (int k = 0; k < 3; ++k) {
-        const int grid = (int)sc.list[d][k].size();
-        if (d >= SERIES_LONG_CLASS)
-          (void)long_chunks(sc, hv, grid, ws_limit, [&](int, int cnt, long long stride) {
-            ws_bytes = std::max(ws_bytes, sizeof(double) * (size_t)cnt * (size_t)stride);
-            return hipSuccess;
-          });
-        hv += grid;
-      }
-    if (ws_bytes > 0) HIPCHK(c, sc.s->A.ensure(ws_bytes));
-  }
+  STAGE(series_long_workspace(c, sc));
   HIPCHK(c, sc.up.flush(sc.s->h_stage, sc.s->up_blob, sc.st));
-  bool ws_used = false;
   STAGE(series_launch(c, sc, [&](const int32_t* wg, int grid, int d, size_t lds) {
     if (d < SERIES_LONG_CLASS) {
       SeriesArgs a = sc.sa;
       a.wg = wg;
       return launch_series_logpdf(sc.st, a, grid, d == 0 ? 4 : 8, lds);
     }
-    const int32_t* hv = sc.wg.data() + (wg - sc.in_map<const int32_t>(sc.o_wg));
-    return long_chunks(sc, hv, grid, ws_limit, [&](int first, int cnt, long long stride) {
-      // (NaN-poison mode: a later launch must not find an earlier one's finished blocks in the workspace)
-      if (ws_used && c->poison.active())
-        if (const hipError_t e = sc.s->A.poison_async(sc.st)) return e;
-      ws_used = true;
-      LongSeriesArgs la = {};
-      static_cast<SeriesArgs&>(la) = sc.sa;
-      la.wg = wg + first;
-      la.ws = sc.s->A.as<double>(); la.ws_stride = stride;
-      return launch_long_series_logpdf(sc.st, la, cnt, d == SERIES_LONG_CLASS ? 4 : 8, lds);
+    LongSeriesArgs la = {};
+    static_cast<SeriesArgs&>(la) = sc.sa;
+    return series_launch_long(c, sc, wg, grid, la, [&](const LongSeriesArgs& a, int cnt) {
+      return launch_long_series_logpdf(sc.st, a, cnt, d == SERIES_LONG_CLASS ? 4 : 8, lds);
     });
   }));
   STAGE(series_fetch(c, sc));
@@ -801,20 +831,23 @@ int hmc_series(agp_ctx* c, SeriesCall& sc, const SeriesHmcCall& hm, double* out_
   return series_timing(c, sc);
 }
 
-// also the posterior at the series' query times, particle-major behind out_off; out_logpdf may be null
+// also the posterior at the series' query times, particle-major behind out_off; out_logpdf may be null.  mode prediction:
+// agp_predict_series_batch; mode long_prediction: agp_predict_long_series_batch — the same stages, the long particles' launches with
+// their workspace (series_long_workspace, series_launch_predict)
 int predict_series(agp_ctx* c, SeriesCall& sc, double* out_mean, double* out_var, int64_t* out_off, double* out_logpdf,
-                   int32_t* out_info) {
+                   int32_t* out_info, SeriesMode mode = SeriesMode::prediction) {
   STAGE(series_check_sizes(c, sc));
   if (sc.pp.P == 0) return AGP_OK;
   STAGE(series_check_pointers(c, sc, out_info != nullptr));
   if (!sc.q_off || !sc.ts_pred || !out_mean || !out_var || !out_off)
     return fail(c, AGP_ERR_ARG, "null pointer argument (q_off, ts_pred, out_mean, out_var or out_off)");
   STAGE(series_check_layout(c, sc));
-  STAGE(series_classes(c, sc, SeriesMode::prediction));
+  STAGE(series_classes(c, sc, mode));
   std::copy(sc.ooff.begin(), sc.ooff.end(), out_off);      // (no check is left to fail, nothing is launched yet)
   if (sc.wg.empty()) { series_zero_values(sc, out_logpdf, out_info); return AGP_OK; }
   STAGE(series_stage(c, sc));
   Slot* s = sc.s;
+  STAGE(series_long_workspace(c, sc));
   HIPCHK(c, sc.up.flush(s->h_stage, s->up_blob, sc.st));
   STAGE(series_launch_predict(c, sc));
   const size_t n_out = sc.n_out();
@@ -828,8 +861,9 @@ int predict_series(agp_ctx* c, SeriesCall& sc, double* out_mean, double* out_var
 }
 
 // The band of every series' mixture: predict_series' launches, their means and variances left on the device for the read-out
-// kernels behind them on the same stream.  out_logpdf may be null.
-int predict_quantile_series(agp_ctx* c, SeriesCall& sc, const SeriesQuantOut& qo, double* out_logpdf, int32_t* out_info) {
+// kernels behind them on the same stream.  out_logpdf may be null.  mode long_prediction: agp_predict_quantile_long_series_batch.
+int predict_quantile_series(agp_ctx* c, SeriesCall& sc, const SeriesQuantOut& qo, double* out_logpdf, int32_t* out_info,
+                            SeriesMode mode = SeriesMode::prediction) {
   const int P = sc.pp.P;
   const int32_t S = sc.S;
   STAGE(series_check_sizes(c, sc));
@@ -839,7 +873,7 @@ int predict_quantile_series(agp_ctx* c, SeriesCall& sc, const SeriesQuantOut& qo
   MixPlan qp;
   STAGE(quant_plan(c, S, P, sc.series, sc.q_off, qo, qp));
   if (P == 0) { quant_fill_nan(qo, 0, qp.Q, qo.nq); return AGP_OK; }      // (S series without a particle)
-  STAGE(series_classes(c, sc, SeriesMode::prediction));
+  STAGE(series_classes(c, sc, mode));
   if (sc.wg.empty()) {
     series_zero_values(sc, out_logpdf, out_info);
     quant_fill_nan(qo, 0, qp.Q, qo.nq);      // (only series without a particle have query points here)
@@ -847,6 +881,7 @@ int predict_quantile_series(agp_ctx* c, SeriesCall& sc, const SeriesQuantOut& qo
   }
   STAGE(series_stage(c, sc));
   Slot* s = sc.s;
+  STAGE(series_long_workspace(c, sc));
   // x and the moments in sq_out, the flags in sq_flag = [converged | iterations | first_bad (P) | bad (S)]
   const size_t nx = qp.Q * (size_t)qo.nq;
   const bool want_mom = qo.mix_mean || qo.mix_var;
@@ -1350,6 +1385,18 @@ int long_series_factor(agp_ctx* c, const double* K, const double* y, int64_t n, 
   return AGP_OK;
 }
 
+// what the long entries share: the cap, its name, and the flags (AGP_LONG_SERIES_ALL is the only bit)
+int series_long_entry(agp_ctx* c, SeriesCall& sc, uint32_t flags) {
+  sc.max_n = AGP_LONG_SERIES_MAX_N; sc.max_name = "AGP_LONG_SERIES_MAX_N";
+  sc.all_long = (flags & AGP_LONG_SERIES_ALL) != 0;
+  if (c && (flags & ~(uint32_t)AGP_LONG_SERIES_ALL) != 0) {
+    char buf[96];
+    snprintf(buf, sizeof buf, "unknown flag bits 0x%x (AGP_LONG_SERIES_ALL is the only flag)", (unsigned)(flags & ~(uint32_t)AGP_LONG_SERIES_ALL));
+    return fail(c, AGP_ERR_ARG, buf);
+  }
+  return AGP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1368,14 +1415,37 @@ int agp_logpdf_long_series_batch(agp_ctx* c, int32_t S, const int64_t* pt_off, c
                                  const double* noise, int32_t flags, double* out_logpdf, int32_t* out_info) {
   return abi_guard(c, [&] {
     SeriesCall sc{S, pt_off, ts, xs, {P, op_off, ops, prm_off, prm, noise, nullptr}, series, nullptr, nullptr};
-    sc.max_n = AGP_LONG_SERIES_MAX_N; sc.max_name = "AGP_LONG_SERIES_MAX_N";
-    sc.all_long = (flags & AGP_LONG_SERIES_ALL) != 0;
-    if (c && (flags & ~AGP_LONG_SERIES_ALL) != 0) {
-      char buf[96];
-      snprintf(buf, sizeof buf, "unknown flag bits 0x%x (AGP_LONG_SERIES_ALL is the only flag)", (unsigned)(flags & ~AGP_LONG_SERIES_ALL));
-      return fail(c, AGP_ERR_ARG, buf);
-    }
+    if (const int rc = series_long_entry(c, sc, (uint32_t)flags)) return rc;
     return logpdf_series(c, sc, out_logpdf, out_info, SeriesMode::long_value);
+  });
+}
+
+int agp_predict_long_series_batch(agp_ctx* c, int32_t S, const int64_t* pt_off, const double* ts, const double* xs, const int64_t* q_off,
+                                  const double* ts_pred, int32_t P, const int32_t* series, const int32_t* op_off, const uint8_t* ops,
+                                  const int32_t* prm_off, const double* prm, const double* noise, const double* noise_pred,
+                                  double* out_mean, double* out_var, int64_t* out_off, double* out_logpdf, int32_t* out_info,
+                                  uint32_t flags) {
+  return abi_guard(c, [&] {
+    SeriesCall sc{S, pt_off, ts, xs, {P, op_off, ops, prm_off, prm, noise, noise_pred}, series, q_off, ts_pred};
+    if (const int rc = series_long_entry(c, sc, flags)) return rc;
+    sc.ws_blocks = long_series_pred_ws_blocks;
+    return predict_series(c, sc, out_mean, out_var, out_off, out_logpdf, out_info, SeriesMode::long_prediction);
+  });
+}
+
+int agp_predict_quantile_long_series_batch(agp_ctx* c, int32_t S, const int64_t* pt_off, const double* ts, const double* xs,
+                                           const int64_t* q_off, const double* ts_pred, int32_t P, const int32_t* series,
+                                           const int32_t* op_off, const uint8_t* ops, const int32_t* prm_off, const double* prm,
+                                           const double* noise, const double* noise_pred, const double* weights, const double* y_slope,
+                                           const double* y_intercept, const double* q, int64_t nq, double tol, int64_t max_iter,
+                                           double* out_x, int32_t* out_converged, int32_t* out_iters, double* out_mix_mean,
+                                           double* out_mix_var, double* out_logpdf, int32_t* out_info, uint32_t flags) {
+  return abi_guard(c, [&] {
+    SeriesCall sc{S, pt_off, ts, xs, {P, op_off, ops, prm_off, prm, noise, noise_pred}, series, q_off, ts_pred};
+    const SeriesQuantOut qo{weights, y_slope, y_intercept, q, nq, tol, max_iter, out_x, out_converged, out_iters, out_mix_mean, out_mix_var};
+    if (const int rc = series_long_entry(c, sc, flags)) return rc;
+    sc.ws_blocks = long_series_pred_ws_blocks;
+    return predict_quantile_series(c, sc, qo, out_logpdf, out_info, SeriesMode::long_prediction);
   });
 }
 

@@ -41,7 +41,7 @@ EXPORTED_SYMBOLS = [
     "agp_predict_series_batch", "agp_debug_remove_factor", "agp_predict_quantile_series_batch",
     "agp_predict_logpdf_series_batch", "agp_predict_sample_series_batch", "agp_predict_sum_series_batch",
     "agp_debug_toeplitz", "agp_debug_cov_sweep", "agp_hmc_series_batch", "agp_logpdf_long_series_batch",
-    "agp_debug_long_series_factor",
+    "agp_debug_long_series_factor", "agp_predict_long_series_batch", "agp_predict_quantile_long_series_batch",
 ]
 COMM_ID_BYTES = 128
 SERIES_MAX_N = 176      # AGP_SERIES_MAX_N of include/autogp_hip.h: the longest series of logpdf_series_batch
@@ -125,6 +125,10 @@ def load_library(path=None):
                                                       u8p, ip, dp, dp, dp, dp, dp, dp, dp, C.c_int64, C.c_double, C.c_int64, dp, ip, ip,
                                                       dp, dp, dp, ip]
     lib.agp_predict_quantile_series_batch.restype = C.c_int
+    lib.agp_predict_long_series_batch.argtypes = lib.agp_predict_series_batch.argtypes + [C.c_uint32]
+    lib.agp_predict_long_series_batch.restype = C.c_int
+    lib.agp_predict_quantile_long_series_batch.argtypes = lib.agp_predict_quantile_series_batch.argtypes + [C.c_uint32]
+    lib.agp_predict_quantile_long_series_batch.restype = C.c_int
     lib.agp_predict_logpdf_series_batch.argtypes = [vp, C.c_int32, C.POINTER(C.c_int64), dp, dp, C.POINTER(C.c_int64), dp, dp, C.c_int32, ip,
                                                     ip, u8p, ip, dp, dp, dp, dp, dp, dp, dp, C.POINTER(C.c_int64), dp, ip]
     lib.agp_predict_logpdf_series_batch.restype = C.c_int
@@ -685,7 +689,24 @@ class GPEngine:
         Returns (means, vars, info), or (means, vars, logpdf, info) with want_logpdf (the training log marginal likelihood,
         bit-identical to logpdf_series_batch's); means[p] / vars[p] are views of length len(queries[series_index[p]]) into one
         particle-major array, so np.stack of the adjacent particles of one series is the block mixture_quantile takes."""
-        packed = series_call_args(series, nodes, noises, series_index, programs)
+        return self._predict_series("agp_predict_series_batch", (), SERIES_MAX_N, series, queries, nodes, noises, series_index,
+                                    noise_pred, want_logpdf, check, programs)
+
+    def predict_long_series_batch(self, series, queries, nodes, noises, series_index, noise_pred=None, want_logpdf=False, all_long=False,
+                                  check=True, programs=None):
+        """agp_predict_long_series_batch: predict_series_batch for series of at most LONG_SERIES_MAX_N points — same arguments, same
+        returns, same statelessness, one call for a mixed family such as 135, 143 and 442 points.  A series of at most SERIES_MAX_N
+        points runs in predict_series_batch's kernel (bit-identical results); a longer one in the long-series predictive kernel, which
+        keeps the factor and the solved query blocks in an HBM workspace (bounded by set_workspace_limit; more long particles than
+        fit are split into several launches).  all_long: every non-empty series takes the long kernel.  logpdf (want_logpdf) is
+        bit-identical to logpdf_long_series_batch's under the same all_long."""
+        return self._predict_series("agp_predict_long_series_batch", (LONG_SERIES_ALL if all_long else 0,), LONG_SERIES_MAX_N,
+                                    series, queries, nodes, noises, series_index, noise_pred, want_logpdf, check, programs)
+
+    def _predict_series(self, entry, tail, max_n, series, queries, nodes, noises, series_index, noise_pred, want_logpdf, check, programs):
+        """The forecast entries' one call: the library's `entry` (by name: the shape checks below come before the library is touched)
+        with the shared arguments and outputs, then `tail` (the long entry's flags)."""
+        packed = series_call_args(series, nodes, noises, series_index, programs, max_n=max_n)
         S, P, sidx = packed[0].shape[0] - 1, packed[4], packed[6]
         qpack = pack_queries(queries, S, noise_pred, P)
         m_s = np.diff(qpack[0])
@@ -694,8 +715,8 @@ class GPEngine:
         out_off = np.zeros(P + 1, dtype=np.int64)
         lp = np.empty(P, dtype=np.float64) if want_logpdf else None
         info = np.empty(P, dtype=np.int32)
-        self._check(self._lib.agp_predict_series_batch(self._ctx, *_series_ctypes(packed, qpack), _dp(mean), _dp(var),
-                                                       out_off.ctypes.data_as(C.POINTER(C.c_int64)), _dp(lp), _ip(info)))
+        self._check(getattr(self._lib, entry)(self._ctx, *_series_ctypes(packed, qpack), _dp(mean), _dp(var),
+                                              out_off.ctypes.data_as(C.POINTER(C.c_int64)), _dp(lp), _ip(info), *tail))
         _raise_first_bad(info, check)
         means = [mean[out_off[p]:out_off[p + 1]] for p in range(P)]
         vars_ = [var[out_off[p]:out_off[p + 1]] for p in range(P)]
@@ -712,7 +733,25 @@ class GPEngine:
         q (views into one array per output, as predict_series_batch's); mean / var (lists of (m_s,) arrays) and logpdf (P,) are None
         unless asked for.  A series without particles, or with a
         particle whose info != 0 (PosDefException when check), gets NaN and converged False."""
-        packed = series_call_args(series, nodes, noises, series_index, programs)
+        return self._predict_quantile_series("agp_predict_quantile_series_batch", (), SERIES_MAX_N, series, queries, nodes, noises,
+                                             series_index, weights, q, y_transforms, noise_pred, tol, max_iter, want_moments, want_logpdf,
+                                             check, programs)
+
+    def predict_quantile_long_series_batch(self, series, queries, nodes, noises, series_index, weights, q, y_transforms=None,
+                                           noise_pred=None, tol=1e-5, max_iter=10**6, want_moments=False, want_logpdf=False,
+                                           all_long=False, check=True, programs=None):
+        """agp_predict_quantile_long_series_batch: predict_quantile_series_batch for series of at most LONG_SERIES_MAX_N points — same
+        arguments and returns; the predictive launches are predict_long_series_batch's (routing, workspace, all_long), the read-out
+        kernels behind them are predict_quantile_series_batch's, unchanged."""
+        return self._predict_quantile_series("agp_predict_quantile_long_series_batch", (LONG_SERIES_ALL if all_long else 0,),
+                                             LONG_SERIES_MAX_N, series, queries, nodes, noises, series_index, weights, q, y_transforms,
+                                             noise_pred, tol, max_iter, want_moments, want_logpdf, check, programs)
+
+    def _predict_quantile_series(self, entry, tail, max_n, series, queries, nodes, noises, series_index, weights, q, y_transforms,
+                                 noise_pred, tol, max_iter, want_moments, want_logpdf, check, programs):
+        """The band entries' one call: the library's `entry` (by name, as in _predict_series) with the shared arguments and outputs,
+        then `tail` (the long entry's flags)."""
+        packed = series_call_args(series, nodes, noises, series_index, programs, max_n=max_n)
         S, P = packed[0].shape[0] - 1, packed[4]
         qpack = pack_queries(queries, S, None if noise_pred is None else np.broadcast_to(noise_pred, (P,)), P)
         q_off = qpack[0]
@@ -725,9 +764,9 @@ class GPEngine:
         var = np.empty(max(1, Q)) if want_moments else None
         lp = np.empty(P, dtype=np.float64) if want_logpdf else None
         info = np.zeros(max(1, P), dtype=np.int32)
-        self._check(self._lib.agp_predict_quantile_series_batch(
+        self._check(getattr(self._lib, entry)(
             self._ctx, *_series_ctypes(packed, qpack), _dp(weights), _dp(slope), _dp(icpt), _dp(qa), nq, float(tol), int(max_iter),
-            _dp(x), _ip(conv), _ip(iters), _dp(mean), _dp(var), _dp(lp), _ip(info)))
+            _dp(x), _ip(conv), _ip(iters), _dp(mean), _dp(var), _dp(lp), _ip(info), *tail))
         info = info[:P]
         _raise_first_bad(info, check)
         # series s's (nq, m_s) row-major block, seen as (m_s, nq) — or (m_s,) for a scalar q: views into the call's arrays
@@ -1847,16 +1886,23 @@ def predict_quantile(engine, nodes, noises, log_weights, ts_pred, q, y_transform
 
 
 def predict_quantile_series(engine, series, queries, nodes, noises, series_index, log_weights, q, y_transforms=None, noise_pred=None,
-                            tol=1e-5, max_iter=10**6):
+                            tol=1e-5, max_iter=10**6, max_n=SERIES_MAX_N, all_long=False):
     """predict_quantile for callers that hold one model per short series: particle p belongs to the model of
     series[series_index[p]], whose mixture weighs it by the softmax of log_weights over THAT series' particles
     (pack_series_mixture); one call of GPEngine.predict_quantile_series_batch serves every series.  y_transforms: one (slope,
     intercept) per series.  Returns a list over the series of (x, success), each as predict_quantile returns them: x of shape (m_s,)
     and a bool for a scalar q; (m_s, nq) and an (nq,) bool array for a vector q.  Raises PosDefException when a particle has no
-    predictive."""
+    predictive.  max_n=LONG_SERIES_MAX_N (or all_long=True: every non-empty series in the long kernel) takes
+    GPEngine.predict_quantile_long_series_batch instead: series of up to LONG_SERIES_MAX_N points; any other max_n is a ValueError."""
+    if max_n not in (SERIES_MAX_N, LONG_SERIES_MAX_N):
+        raise ValueError(f"max_n must be SERIES_MAX_N ({SERIES_MAX_N}) or LONG_SERIES_MAX_N ({LONG_SERIES_MAX_N})")
     _, w = pack_series_mixture(series_index, len(series), log_weights=log_weights)
-    band = engine.predict_quantile_series_batch(series, queries, nodes, noises, series_index, w, q, y_transforms=y_transforms,
-                                                noise_pred=noise_pred, tol=tol, max_iter=max_iter)
+    if all_long or max_n == LONG_SERIES_MAX_N:
+        band = engine.predict_quantile_long_series_batch(series, queries, nodes, noises, series_index, w, q, y_transforms=y_transforms,
+                                                         noise_pred=noise_pred, tol=tol, max_iter=max_iter, all_long=all_long)
+    else:
+        band = engine.predict_quantile_series_batch(series, queries, nodes, noises, series_index, w, q, y_transforms=y_transforms,
+                                                    noise_pred=noise_pred, tol=tol, max_iter=max_iter)
     return [(x, (bool(c.all()) if np.ndim(q) == 0 else c.all(axis=0))) for x, c in zip(band.x, band.converged)]
 
 

@@ -427,6 +427,96 @@ function predict_quantile_series_batch(eng::Engine, series::Vector{<:Tuple{Vecto
     return xs_, cs_, is_, means, vars, out[1:P], info[1:P]
 end
 
+"`predict_series_batch` for series of at most `LONG_SERIES_MAX_N` points (agp_predict_long_series_batch): same arguments, same
+returns, same statelessness, one call for a mixed family such as 135, 143 and 442 points.  A series of at most `SERIES_MAX_N` points
+runs in `predict_series_batch`'s kernel (bit-identical results), a longer one in the long-series predictive kernel, which keeps the
+factor and the solved query blocks in an HBM workspace; `all_long = true` sends every non-empty series through the long kernel.
+`logpdf` is bit-identical to `logpdf_long_series_batch`'s under the same `all_long`."
+function predict_long_series_batch(eng::Engine, series::Vector{<:Tuple{Vector{Float64},Vector{Float64}}}, queries::Vector{Vector{Float64}},
+                                   nodes::Vector{<:GP.Node}, noises::Vector{Float64}, series_index::Vector{<:Integer};
+                                   noise_pred::Union{Nothing,Vector{Float64}}=nothing, all_long::Bool=false)
+    P = length(nodes)
+    (length(noises) == P && length(series_index) == P) || throw(ArgumentError("one noise and one series index per particle required"))
+    length(queries) == length(series) || throw(ArgumentError("one vector of query times per series required"))
+    (noise_pred === nothing || length(noise_pred) == P) || throw(ArgumentError("one noise_pred per particle required"))
+    all(i -> 1 <= i <= length(series), series_index) || throw(ArgumentError("series index outside 1:$(length(series))"))
+    pt_off = Int64[0]; ts = Float64[]; xs = Float64[]; q_off = Int64[0]; tq = Float64[]
+    for (s, (t, x)) in enumerate(series)
+        length(t) == length(x) || throw(ArgumentError("series $s: ts and xs must have equal lengths"))
+        length(t) <= LONG_SERIES_MAX_N || throw(ArgumentError("series $s has $(length(t)) points, more than LONG_SERIES_MAX_N ($LONG_SERIES_MAX_N)"))
+        append!(ts, t); append!(xs, x); push!(pt_off, length(ts))
+        append!(tq, queries[s]); push!(q_off, length(tq))
+    end
+    isempty(ts) && (push!(ts, 0.0); push!(xs, 0.0))
+    isempty(tq) && push!(tq, 0.0)
+    sidx = Int32[Int32(i - 1) for i in series_index]
+    op_off, ops, prm_off, prm = encode_batch(nodes)
+    total = sum(Int[length(queries[i]) for i in series_index])
+    mean = Vector{Float64}(undef, max(1, total)); var = Vector{Float64}(undef, max(1, total))
+    out_off = zeros(Int64, P + 1)
+    out = Vector{Float64}(undef, P); info = Vector{Int32}(undef, P)
+    np = noise_pred === nothing ? noises : noise_pred
+    flags = all_long ? UInt32(LONG_SERIES_ALL) : UInt32(0)
+    GC.@preserve pt_off ts xs q_off tq sidx op_off ops prm_off prm noises np mean var out_off out info check(eng, ccall((:agp_predict_long_series_batch, LIB), Cint,
+        (Ptr{Cvoid}, Int32, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Int32, Ptr{Int32}, Ptr{Int32}, Ptr{UInt8},
+         Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Ptr{Int32}, UInt32),
+        eng.ptr, length(series), pt_off, ts, xs, q_off, tq, P, sidx, op_off, ops, prm_off, prm, noises, np, mean, var, out_off, out, info, flags))
+    means = [mean[out_off[p] + 1:out_off[p + 1]] for p in 1:P]
+    vars = [var[out_off[p] + 1:out_off[p + 1]] for p in 1:P]
+    return means, vars, out, info
+end
+
+"`predict_quantile_series_batch` for series of at most `LONG_SERIES_MAX_N` points (agp_predict_quantile_long_series_batch): same
+arguments and returns; the predictive launches are `predict_long_series_batch`'s (routing, workspace, `all_long`), the read-out kernels
+behind them are `predict_quantile_series_batch`'s, unchanged."
+function predict_quantile_long_series_batch(eng::Engine, series::Vector{<:Tuple{Vector{Float64},Vector{Float64}}},
+                                            queries::Vector{Vector{Float64}}, nodes::Vector{<:GP.Node}, noises::Vector{Float64},
+                                            series_index::Vector{<:Integer}, weights::Vector{Float64}, q::Vector{Float64};
+                                            y_transforms::Union{Nothing,Vector{Tuple{Float64,Float64}}}=nothing,
+                                            noise_pred::Union{Nothing,Vector{Float64}}=nothing, tol::Float64=1e-5, max_iter::Integer=10^6,
+                                            all_long::Bool=false)
+    P = length(nodes); S = length(series)
+    (length(noises) == P && length(series_index) == P && length(weights) == P) ||
+        throw(ArgumentError("one noise, one series index and one weight per particle required"))
+    length(queries) == S || throw(ArgumentError("one vector of query times per series required"))
+    (noise_pred === nothing || length(noise_pred) == P) || throw(ArgumentError("one noise_pred per particle required"))
+    (y_transforms === nothing || length(y_transforms) == S) || throw(ArgumentError("one (slope, intercept) per series required"))
+    all(i -> 1 <= i <= S, series_index) || throw(ArgumentError("series index outside 1:$S"))
+    pt_off = Int64[0]; ts = Float64[]; xs = Float64[]; q_off = Int64[0]; tq = Float64[]
+    for (s, (t, x)) in enumerate(series)
+        length(t) == length(x) || throw(ArgumentError("series $s: ts and xs must have equal lengths"))
+        length(t) <= LONG_SERIES_MAX_N || throw(ArgumentError("series $s has $(length(t)) points, more than LONG_SERIES_MAX_N ($LONG_SERIES_MAX_N)"))
+        append!(ts, t); append!(xs, x); push!(pt_off, length(ts))
+        append!(tq, queries[s]); push!(q_off, length(tq))
+    end
+    isempty(ts) && (push!(ts, 0.0); push!(xs, 0.0))
+    isempty(tq) && push!(tq, 0.0)
+    sidx = Int32[Int32(i - 1) for i in series_index]
+    op_off, ops, prm_off, prm = encode_batch(nodes)
+    slope = y_transforms === nothing ? ones(Float64, max(1, S)) : Float64[t[1] for t in y_transforms]
+    icpt = y_transforms === nothing ? zeros(Float64, max(1, S)) : Float64[t[2] for t in y_transforms]
+    nq = length(q); Q = Int(q_off[end])
+    x = Vector{Float64}(undef, max(1, nq * Q)); conv = zeros(Int32, max(1, nq * Q)); iters = zeros(Int32, max(1, nq * Q))
+    mean = Vector{Float64}(undef, max(1, Q)); var = Vector{Float64}(undef, max(1, Q))
+    out = Vector{Float64}(undef, max(1, P)); info = zeros(Int32, max(1, P))
+    np = noise_pred === nothing ? noises : noise_pred
+    flags = all_long ? UInt32(LONG_SERIES_ALL) : UInt32(0)
+    GC.@preserve pt_off ts xs q_off tq sidx op_off ops prm_off prm noises np weights slope icpt q x conv iters mean var out info check(eng, ccall((:agp_predict_quantile_long_series_batch, LIB), Cint,
+        (Ptr{Cvoid}, Int32, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Int32, Ptr{Int32}, Ptr{Int32}, Ptr{UInt8},
+         Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Float64,
+         Int64, Ptr{Float64}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, UInt32),
+        eng.ptr, S, pt_off, ts, xs, q_off, tq, P, sidx, op_off, ops, prm_off, prm, noises, np, weights, slope, icpt, q, nq, tol,
+        max_iter, x, conv, iters, mean, var, out, info, flags))
+    # series s's block is (nq, m_s) row-major: column-major it is the m_s x nq matrix
+    block(a, s) = reshape(a[nq * q_off[s] + 1:nq * q_off[s + 1]], Int(q_off[s + 1] - q_off[s]), nq)
+    xs_ = [block(x, s) for s in 1:S]
+    cs_ = [block(conv, s) .!= 0 for s in 1:S]
+    is_ = [block(iters, s) for s in 1:S]
+    means = [mean[q_off[s] + 1:q_off[s + 1]] for s in 1:S]
+    vars = [var[q_off[s] + 1:q_off[s + 1]] for s in 1:S]
+    return xs_, cs_, is_, means, vars, out[1:P], info[1:P]
+end
+
 "Held-out scores of many short series in one fused launch (agp_predict_logpdf_series_batch): `predict_proba` for callers that hold
 one model per short series, with `predict_series_batch`'s series / query / particle arguments and statelessness.  `heldout[s]` holds
 the RAW values observed at `queries[s]`; particle `p` scores them under its posterior predictive on `series[series_index[p]]`

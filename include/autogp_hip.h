@@ -145,7 +145,8 @@ int agp_logpdf_series_batch(agp_ctx* ctx, int32_t S, const int64_t* pt_off /* S+
  *     series' length.  The long kernel keeps 4 KiB per ChangePoint node (a 512-entry table) beside 21 KiB of vectors, tables and one
  *     diagonal block and the program: at 512 points a chain of 10 ChangePoint nodes takes 61 KiB (two workgroups share a CU), 34
  *     nodes beside a small program are the most 160 KiB hold, 40 are refused.
- * Not here: gradient, forecast, held-out, sampling, decomposition and HMC twins above AGP_SERIES_MAX_N points; series beyond
+ * The forecast and its band above AGP_SERIES_MAX_N points: agp_predict_long_series_batch, agp_predict_quantile_long_series_batch.
+ * Not here: gradient, held-out, sampling, decomposition and HMC twins above AGP_SERIES_MAX_N points; series beyond
  * AGP_LONG_SERIES_MAX_N; deduplication inside a call. */
 #define AGP_LONG_SERIES_MAX_N 512
 #define AGP_LONG_SERIES_ALL 1   /* flags: every non-empty series takes the long kernel */
@@ -315,6 +316,53 @@ int agp_predict_quantile_series_batch(agp_ctx* ctx, int32_t S, const int64_t* pt
                                       int32_t* out_iters /* or NULL */,
                                       double* out_mix_mean /* q_off[S], or NULL */, double* out_mix_var /* q_off[S], or NULL */,
                                       double* out_logpdf /* P, or NULL */, int32_t* out_info /* P */);
+
+/* agp_predict_series_batch for series of up to AGP_LONG_SERIES_MAX_N = 512 points: the forecast of the reference's 442-point data
+ * set beside its 135- and 143-point ones in ONE call.  The arguments are agp_predict_series_batch's with a trailing flags word, and
+ * every convention is that entry's: the particle-major layout behind out_off, noise_pred NULL = noise, the optional out_logpdf,
+ * nothing written for a series with m_s == 0, the prior predictive of an EMPTY series, NaN in the whole block and in out_logpdf of
+ * a particle with out_info[p] > 0 (the first non-positive pivot), a variance neither clamped nor reported, P == 0, the error
+ * codes and their messages (the cap now AGP_LONG_SERIES_MAX_N, named in the message); flag bits other than AGP_LONG_SERIES_ALL are
+ * AGP_ERR_ARG.  Stateless and re-entrant like it.
+ * Routing, as in agp_logpdf_long_series_batch: a series of at most AGP_SERIES_MAX_N points (an empty one always) runs in
+ * agp_predict_series_batch's kernel, bit-identical to that entry; a longer one runs in k_long_series_predict — the long value
+ * kernel's statements, then, in the same workgroup, the posterior at the series' own query times: query blocks of 16 times dealt to
+ * the four waves, solved block column by block column against the factor in the workspace (v_mfma_f64_16x16x4), the solved blocks
+ * in scratch rows of that workspace.  flags & AGP_LONG_SERIES_ALL sends every non-empty series through it.  out_logpdf is
+ * bit-identical to agp_logpdf_long_series_batch's under the same flags.
+ * Workspace: from the call's slot, 852 blocks of 2 KiB (1.66 MiB) per workgroup at 512 points whatever m_s is; one launch takes at
+ * most min(agp_set_workspace_limit's value, 1 GiB) and a larger call is split into launches on its stream.  A particle's result
+ * bits depend only on its own series, program, parameters, noises and the flag, and a query's only on its own time beside them —
+ * not on the other query times, their number or order, on what else is in the call, or on the split.
+ * AGP_ERR_PROGRAM (names the particle): the long predictive kernel keeps 5 KiB per ChangePoint node (640 table entries: 512 points
+ * and 128 query slots) beside 21.5 KiB and the program: at 512 points a chain of 10 ChangePoint nodes takes 71.5 KiB (two workgroups
+ * still share a CU); 27 nodes beside a small program are the most 160 KiB hold. */
+int agp_predict_long_series_batch(agp_ctx* ctx, int32_t S, const int64_t* pt_off /* S+1 */, const double* ts, const double* xs,
+                                  const int64_t* q_off /* S+1 */, const double* ts_pred,
+                                  int32_t P, const int32_t* series /* P */,
+                                  const int32_t* op_off, const uint8_t* ops, const int32_t* prm_off, const double* prm,
+                                  const double* noise /* P */, const double* noise_pred /* P or NULL = noise */,
+                                  double* out_mean, double* out_var, int64_t* out_off /* P+1 */,
+                                  double* out_logpdf /* P or NULL */, int32_t* out_info /* P */, uint32_t flags);
+
+/* The forecast BAND for series of up to AGP_LONG_SERIES_MAX_N points: agp_predict_quantile_series_batch's arguments with a trailing
+ * flags word.  The predictive launches are agp_predict_long_series_batch's (routing, workspace, splitting, flags, refusals); behind
+ * them the pack, search and moment kernels of agp_predict_quantile_series_batch run unchanged on the same stream, so a series' band
+ * has the bits of agp_mixture_quantile / agp_mixture_moments on the raw components of that entry's block, and every mixture rule,
+ * output layout and refusal is agp_predict_quantile_series_batch's.  A series with a failed particle is NaN; the others are
+ * untouched. */
+int agp_predict_quantile_long_series_batch(agp_ctx* ctx, int32_t S, const int64_t* pt_off /* S+1 */, const double* ts, const double* xs,
+                                           const int64_t* q_off /* S+1 */, const double* ts_pred,
+                                           int32_t P, const int32_t* series /* P */,
+                                           const int32_t* op_off, const uint8_t* ops, const int32_t* prm_off, const double* prm,
+                                           const double* noise /* P */, const double* noise_pred /* P or NULL = noise */,
+                                           const double* weights /* P: particle p's weight inside ITS series' mixture */,
+                                           const double* y_slope /* S, or NULL: 1 */, const double* y_intercept /* S, or NULL: 0 */,
+                                           const double* q, int64_t nq, double tol, int64_t max_iter,
+                                           double* out_x /* nq * q_off[S] */, int32_t* out_converged /* or NULL */,
+                                           int32_t* out_iters /* or NULL */,
+                                           double* out_mix_mean /* q_off[S], or NULL */, double* out_mix_var /* q_off[S], or NULL */,
+                                           double* out_logpdf /* P, or NULL */, int32_t* out_info /* P */, uint32_t flags);
 
 /* HELD-OUT SCORES of many short series in one call: predict_proba (src/api.jl:686-699) for callers that hold one model per short
  * series — the log-density of every series' held-out values y_pred under each of its particles' posterior predictives, and (with

@@ -24,9 +24,10 @@ ROOT = Path(__file__).resolve().parent.parent
 HEADER = ROOT / "include" / "autogp_hip.h"
 SHIMS = sorted((ROOT / "autogp.jl_amd" / "julia").rglob("*.jl")) + [ROOT / "tools" / "make_golden_reference.jl"]
 
-C_SCALARS = {"int": "i32", "int32_t": "i32", "int64_t": "i64", "double": "f64", "void": "void", "uint8_t": "u8", "uint64_t": "u64", "char": "char"}
+C_SCALARS = {"int": "i32", "int32_t": "i32", "int64_t": "i64", "double": "f64", "void": "void", "uint8_t": "u8", "uint32_t": "u32", "uint64_t": "u64",
+             "char": "char"}
 JL_SCALARS = {"Cint": "i32", "Int32": "i32", "Int64": "i64", "Float64": "f64", "Cdouble": "f64", "Cvoid": "void", "UInt8": "u8",
-              "Cstring": "cstr", "Clonglong": "i64", "UInt64": "u64", "Nothing": "void"}
+              "Cstring": "cstr", "Clonglong": "i64", "UInt32": "u32", "UInt64": "u64", "Nothing": "void"}
 
 
 def split_top(s, sep=","):
