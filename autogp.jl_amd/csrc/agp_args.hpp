@@ -619,6 +619,16 @@ __host__ __device__ inline LongSeriesLds long_series_pred_lds(int n, int n_ops, 
   return m;
 }
 
+// Long-series held-out twin (k_long_series_predict_logpdf, agp_predict_logpdf_long_series_batch): the short held-out twin's arguments
+// and the workspace.  The workgroup factors the JOINT matrix of the series' n training points followed — without padding — by its m
+// query points, N = n + m <= LONG_SERIES_MAX_N, in the long value kernel's LDS map and workspace at N points (long_series_lds(N, ..),
+// long_series_ws_blocks(ceil(N / 16))), and reads the query rows' partials: need, classes, chunks and the host's refusal rule are
+// the long value entry's at N.
+struct LongSeriesProbaArgs : SeriesProbaArgs {
+  double* ws;
+  long long ws_stride;       // doubles per workgroup
+};
+
 // Arguments of the probe instantiation k_series_logpdf<D, true> (agp_debug_series_factor): caller matrices of ONE size take the place
 // of series, programs and noise; the LDS map is series_lds(n, 0, 0, 0); workgroup b factors matrix b.
 struct SeriesProbeArgs {

@@ -2175,6 +2175,7 @@ int agp_init(agp_ctx** out, int device_id) {
       if (ea == hipSuccess) ea = kernels_init_series_hmc();
       if (ea == hipSuccess) ea = kernels_init_long_series();
       if (ea == hipSuccess) ea = kernels_init_long_series_predict();
+      if (ea == hipSuccess) ea = kernels_init_long_series_proba();
       if (ea != hipSuccess) {
         std::string m = std::string("hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed: ") + hipGetErrorString(ea);
         return fail(nullptr, AGP_ERR_HIP, m);

@@ -5,6 +5,7 @@
 //   agp_kernels_long_series.hip  long-series value kernel (one workgroup per particle of a series of up to 512 points, factor in HBM)
 //   agp_kernels_long_series_probe.hip  its probe instantiation (caller matrices; agp_debug_long_series_factor)
 //   agp_kernels_long_series_predict.hip  its predictive twin (the posterior at the series' own query times behind the value)
+//   agp_kernels_long_series_proba.hip  its held-out twin (the joint points factored, the query rows' partials read out)
 // Every template instantiation lives behind one of these plain functions, so the units compile in parallel and the
 // function attributes (dynamic-LDS ceilings) are set on the copies that are actually launched.
 #pragma once
@@ -116,6 +117,12 @@ hipError_t kernels_init_long_series_predict();   // the same ceiling for k_long_
 // predictive twin: the launch above with the query side; lds_bytes = the largest long_series_pred_lds total of the launch's
 // particles, la.ws_stride >= 256 long_series_pred_ws_blocks(nb) for each of them
 hipError_t launch_long_series_predict(hipStream_t st, const LongSeriesPredArgs& la, int grid, int depth, size_t lds_bytes);
+
+// ---- agp_kernels_long_series_proba.hip -------------------------------------------------------------------------------
+hipError_t kernels_init_long_series_proba();   // the same ceiling for k_long_series_predict_logpdf (once, agp_init)
+// held-out twin: the value launch on the JOINT points with the query side; lds_bytes = the largest long_series_lds total of the
+// launch's particles at their joint lengths n_s + m_s, la.ws_stride >= 256 long_series_ws_blocks(nb) for each of them
+hipError_t launch_long_series_predict_logpdf(hipStream_t st, const LongSeriesProbaArgs& la, int grid, int depth, size_t lds_bytes);
 
 // ---- agp_kernels_long_series_probe.hip -------------------------------------------------------------------------------
 // one workgroup per caller matrix: lds_bytes = long_series_lds(la.n, 0, 0, 0), la.ws_stride >= 256 nb (nb + 1) / 2

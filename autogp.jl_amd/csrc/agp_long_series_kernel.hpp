@@ -41,6 +41,17 @@
 // per-point tables of LONG_PRED_SIG_STRIDE entries, factor16<true> also leaves W(j) = L(j, j)^-1 behind the triangle, and stage P
 // (below, behind stage 4) forms the posterior at the series' own query times.  A unit of its own as well
 // (agp_kernels_long_series_predict.hip, which records its registers, LDS and workspace).
+// k_long_series_predict_logpdf<D> = k_long_series_logpdf<D, false, LongSeriesProbaArgs> is the held-out twin
+// (agp_predict_logpdf_long_series_batch): the statements above on the JOINT points of the series — its ntr = n_s training points
+// followed, without padding, by its mq query points, n = ntr + mq <= 512 — in long_series_lds(n, ..) and the value kernel's workspace.
+// Every statement of its own is behind the trait JOINT (which a sampling twin would share, as PROBA and SAMPLE do in series_body):
+// stage 1 reads the query times and the held-out values behind the series' own; stage 3 (a) adds noise to the diagonal of the rows
+// below ntr and noise_pred from there on; stage 4 reduces over the rows [ntr, n) alone, a row in front of them contributing an exact
+// 0.0 in its place of the fixed order — out_lp = -(mq log 2 pi + ld + ss) / 2 + mq log|slope|, the bits of the value kernel when
+// ntr = 0 and the slope is 1 —; out_info is the first bad pivot on the joint index; behind stage 4's barrier the per-point terms
+// (-(z_k^2 + log 2 pi) / 2 - log L_kk) + log|slope| of the rows k = ntr + j are written from avec and ldg, NaN in the whole block
+// after a bad pivot.  No barrier is added to the block-column loop.  A unit of its own as well
+// (agp_kernels_long_series_proba.hip, which records its registers, LDS and workspace).
 // A particle's bits depend on its own series, program, parameters and noise only: the LDS map (long_series_lds, agp_args.hpp) is a
 // function of the particle's own sizes, the workspace is the workgroup's own, no value crosses workgroups.
 //
@@ -136,8 +147,8 @@ __device__ __forceinline__ void long_update(d4 (&acc)[LONG_ROWS_PER_WAVE], const
   }
 }
 
-// One body for the value kernel, its probe and the predictive twin, selected by the argument type (as series_body is for the short
-// family): every statement of the twin's own is behind PRED.  The body is the kernel itself, not a function the three kernels call:
+// One body for the value kernel, its probe, the predictive and the held-out twin, selected by the argument type (as series_body is
+// for the short family): every statement of a twin's own is behind PRED or JOINT.  The body is the kernel itself, not a function the three kernels call:
 // inlined from a function its early returns become branches to a common end, and the value and the probe instantiation then
 // allocate their registers differently (tried: by reference, by value, the LDS symbol declared inside).  As it stands their
 // instructions are those of the kernel without the twin; their symbols carry the argument type.
@@ -145,12 +156,16 @@ template <int D, bool PROBE = false, class ArgsT = std::conditional_t<PROBE, Lon
 __global__ __launch_bounds__(256, 2) void k_long_series_logpdf(ArgsT a) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   constexpr bool PRED = std::is_same_v<ArgsT, LongSeriesPredArgs>;
+  constexpr bool PROBA = std::is_same_v<ArgsT, LongSeriesProbaArgs>;      // the held-out twin: n below is the JOINT length
+  constexpr bool JOINT = PROBA;      // (the branches of the joint points: a sampling twin would share them, as in series_body)
   constexpr int STRIDE = PRED ? LONG_PRED_SIG_STRIDE : LONG_SIG_STRIDE;      // entries of one per-point table
   constexpr int E = 4, U = LONG_ROWS_PER_WAVE;
   const int tid = threadIdx.x, l = tid & 63, l15 = l & 15, lq = l >> 4;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);      // (on the scalar unit: which block rows a wave owns is wave-uniform control flow)
   int p, n;
   [[maybe_unused]] long long o0 = 0;
+  [[maybe_unused]] int ntr = 0;            // JOINT: training points (rows [ntr, n) are the query rows)
+  [[maybe_unused]] long long q0 = 0;       // JOINT: the series' first query
   if constexpr (PROBE) {
     p = blockIdx.x;
     n = a.n;
@@ -159,6 +174,12 @@ __global__ __launch_bounds__(256, 2) void k_long_series_logpdf(ArgsT a) {
     const int sidx = a.series[p];
     o0 = a.pt_off[sidx];
     n = (int)(a.pt_off[sidx + 1] - o0);
+    if constexpr (JOINT) {
+      q0 = a.q_off[sidx];
+      const long long mq = a.q_off[sidx + 1] - q0;
+      ntr = n;
+      n = (mq <= 0 || mq > LONG_SERIES_MAX_N) ? 0 : n + (int)mq;      // (nothing held out: never launched, like an empty series)
+    }
   }
   if (n <= 0 || n > LONG_SERIES_MAX_N) {      // (the host answers empty series itself and refuses longer ones: never launched)
     if (tid == 0) { a.out_lp[p] = 0.0; a.out_info[p] = 0; }
@@ -189,10 +210,20 @@ __global__ __launch_bounds__(256, 2) void k_long_series_logpdf(ArgsT a) {
     }
     __syncthreads();
   } else {
-    for (int i = tid; i < np; i += 256) {
-      tpt[i] = a.ts[o0 + (i < n ? i : n - 1)];      // (padding points: a finite time; their entries are overwritten with identity)
-      rvec[i] = i < n ? a.xs[o0 + i] : 0.0;
-      avec[i] = 0.0;
+    if constexpr (JOINT) {
+      // the joint points: the series' times, then — directly behind them, no padding between — its query times; xs, then the held-out values
+      for (int i = tid; i < np; i += 256) {
+        const int k = i < n ? i : n - 1;
+        tpt[i] = k < ntr ? a.ts[o0 + k] : a.ts_pred[q0 + (k - ntr)];
+        rvec[i] = i < ntr ? a.xs[o0 + i] : i < n ? a.y_pred[q0 + (i - ntr)] : 0.0;
+        avec[i] = 0.0;
+      }
+    } else {
+      for (int i = tid; i < np; i += 256) {
+        tpt[i] = a.ts[o0 + (i < n ? i : n - 1)];      // (padding points: a finite time; their entries are overwritten with identity)
+        rvec[i] = i < n ? a.xs[o0 + i] : 0.0;
+        avec[i] = 0.0;
+      }
     }
     if (AGP_EXP_TABLE && tid < AGP_EXP_TAB_N) etab[tid] = fm::c_exp_tab[tid];
     for (int i = tid; i < h.n_prm + 2; i += 256) prm[i] = a.prm[h.prm_off + i];      // (the parameter buffer carries two doubles of tail padding)
@@ -208,6 +239,8 @@ __global__ __launch_bounds__(256, 2) void k_long_series_logpdf(ArgsT a) {
 
   // ---- 3. block columns ----
   [[maybe_unused]] const double noise = [&]() { if constexpr (PROBE) return 0.0; else return a.noise[p]; }();
+  [[maybe_unused]] double noise_q = 0.0;      // JOINT: the diagonal addend of the query rows
+  if constexpr (JOINT) noise_q = a.noise_pred[p];
   int bad = 0;           // first non-positive pivot this wave has seen (1-based index in the series), 0 = none
   for (int j = 0; j < nb; ++j) {
     const int ib0 = j + ((w - j) & 3);      // the wave's first block row at or below j
@@ -236,7 +269,10 @@ __global__ __launch_bounds__(256, 2) void k_long_series_logpdf(ArgsT a) {
         }
         eval_program<D, E, 0, false, STRIDE>(h, ops, prm, sig, tr, tc, ri, ci, lt, out, etab);
 #pragma unroll
-        for (int e = 0; e < E; ++e) kb[64 * e + l] = cov_finalize(out[e], ri[e], ci[e], n, np, 0, noise);
+        for (int e = 0; e < E; ++e) {
+          if constexpr (JOINT) kb[64 * e + l] = cov_finalize(out[e], ri[e], ci[e], n, np, 0, ri[e] < ntr ? noise : noise_q);
+          else kb[64 * e + l] = cov_finalize(out[e], ri[e], ci[e], n, np, 0, noise);
+        }
       }
     }
     d4 acc[U];
@@ -345,12 +381,19 @@ __global__ __launch_bounds__(256, 2) void k_long_series_logpdf(ArgsT a) {
 
   // ---- 4. the value: 2 sum log L_ii and alpha'alpha, reduced in a fixed order; the first bad pivot of the four waves ----
   if (l == 0) dblk[w] = (double)bad;      // (the last diagonal block has been consumed)
-  Wl[tid] = (tid < np ? ldg[tid] : 0.0) + (tid + 256 < np ? ldg[tid + 256] : 0.0);      // (the last inverse block likewise)
+  // (JOINT: both sums over the query rows [ntr, n) alone — the conditional density of the held-out values; a row in front of them
+  // contributes an exact 0.0 in its place of the same fixed order, so with ntr = 0 the sums are the value kernel's)
+  if constexpr (JOINT) Wl[tid] = (tid >= ntr && tid < np ? ldg[tid] : 0.0) + (tid + 256 >= ntr && tid + 256 < np ? ldg[tid + 256] : 0.0);
+  else Wl[tid] = (tid < np ? ldg[tid] : 0.0) + (tid + 256 < np ? ldg[tid + 256] : 0.0);      // (the last inverse block likewise)
   __syncthreads();
   if (w == 0) {
     double ld = (Wl[l] + Wl[l + 64]) + (Wl[l + 128] + Wl[l + 192]);
     double ss = 0.0;
-    for (int i = l; i < np; i += 64) ss = fma(avec[i], avec[i], ss);
+    if constexpr (JOINT) {
+      for (int i = l; i < np; i += 64) ss = i >= ntr ? fma(avec[i], avec[i], ss) : ss;
+    } else {
+      for (int i = l; i < np; i += 64) ss = fma(avec[i], avec[i], ss);
+    }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) { ss += __shfl_xor(ss, off); ld += __shfl_xor(ld, off); }
     if (l == 0) {
@@ -359,7 +402,16 @@ __global__ __launch_bounds__(256, 2) void k_long_series_logpdf(ArgsT a) {
         const int b = (int)dblk[k];
         if (b != 0 && (first == 0 || b < first)) first = b;
       }
-      const double lp = -0.5 * ((double)n * 1.8378770664093454835606594728112 + ld + ss);
+      double lp;
+      if constexpr (JOINT) {
+        // m log 2 pi, and the Jacobian of the series' own transform: m log|slope|.  The first product and sum are written as the
+        // fused operation the value kernel's statement below compiles to, so that with ntr = 0 and slope 1 the bits are that
+        // kernel's whatever the compiler makes of the longer expression (tests/test_gpu_long_series_proba.py compares them)
+        const double mq = (double)(n - ntr);
+        lp = -0.5 * (fma(mq, 1.8378770664093454835606594728112, ld) + ss) + mq * log(fabs(a.y_slope[a.series[p]]));
+      } else {
+        lp = -0.5 * ((double)n * 1.8378770664093454835606594728112 + ld + ss);
+      }
       a.out_lp[p] = first != 0 ? __builtin_nan("") : lp;
       a.out_info[p] = first;
       if constexpr (PROBE) { a.out_part[2 * p] = ld; a.out_part[2 * p + 1] = ss; }
@@ -367,6 +419,22 @@ __global__ __launch_bounds__(256, 2) void k_long_series_logpdf(ArgsT a) {
   }
   if constexpr (PROBE)      // alpha as stage 3 left it (the packed blocks are in the workspace)
     for (int i = tid; i < np; i += 256) a.out_alpha[(long long)p * np + i] = avec[i];
+
+  if constexpr (PROBA) {
+    // ---- the per-point terms: log N(y_j | training data, y_0 .. y_{j-1}) from row ntr + j of the joint factor (chain rule).  Behind
+    // stage 4's barrier alpha (avec) and the log-diagonal (ldg = 2 log L_kk) are read-only and the four first-bad-pivot words in
+    // dblk are written: no further barrier ----
+    if (a.out_terms != nullptr) {
+      const bool failed = dblk[0] != 0.0 || dblk[1] != 0.0 || dblk[2] != 0.0 || dblk[3] != 0.0;      // NaN in the particle's whole block
+      const double lsl = log(fabs(a.y_slope[a.series[p]]));
+      double* ot = a.out_terms + a.out_off[p];
+      for (int k = ntr + tid; k < n; k += 256) {
+        const double z = avec[k];
+        const double t = (-0.5 * fma(z, z, 1.8378770664093454835606594728112) - 0.5 * ldg[k]) + lsl;
+        ot[k - ntr] = failed ? __builtin_nan("") : t;
+      }
+    }
+  }
 
   if constexpr (PRED) {
     // ---- P. the posterior at the series' own query times: mean = VT alpha, var = (k(t*, t*) - rowsums(VT^2)) + noise_pred, VT = K21 L^-T.
@@ -487,5 +555,7 @@ __global__ __launch_bounds__(256, 2) void k_long_series_logpdf(ArgsT a) {
 
 // The predictive twin (agp_predict_long_series_batch; agp_kernels_long_series_predict.hip has its figures)
 template <int D> constexpr auto k_long_series_predict = &k_long_series_logpdf<D, false, LongSeriesPredArgs>;
+// The held-out twin (agp_predict_logpdf_long_series_batch; agp_kernels_long_series_proba.hip has its figures)
+template <int D> constexpr auto k_long_series_predict_logpdf = &k_long_series_logpdf<D, false, LongSeriesProbaArgs>;
 
 }  // namespace agp

@@ -13,6 +13,8 @@
 //                                      the same stream: quantiles and marginal moments of every series' own mixture
 //   agp_predict_logpdf_series_batch    k_series_predict_logpdf: the value kernel on the joint points, the query rows' partials read out —
 //                                      the log-density of every series' held-out values; k_series_mix_logp behind it for the mixtures
+//   agp_predict_logpdf_long_series_batch  the same scores for n_s + m_s up to AGP_LONG_SERIES_MAX_N joint points: k_series_predict_logpdf
+//                                      up to the short cap, k_long_series_predict_logpdf above it; the same mixture read-out
 //   agp_predict_sample_series_batch    k_series_predict_sample: the same joint factorisation with a zero query right-hand side, the query
 //                                      rows read out as samples, component means and covariances; k_series_sample_fill behind it
 //   agp_predict_sum_series_batch       k_series_predict_sum: the predictive kernel on every particle's composite program (append_composite)
@@ -168,7 +170,9 @@ void quant_fill_nan(const SeriesQuantOut& qo, size_t from, size_t to, int64_t nq
 // SeriesCall::all_long) takes k_long_series_logpdf and its map, the others are the value mode's.
 // long_prediction: the same routing for the forecast and the band — k_long_series_predict and its map above the short cap, the
 // prediction mode's kernel and map below it.
-enum class SeriesMode { value, gradient, prediction, held_out, sum, hmc, long_value, long_prediction };
+// long_held_out: the same routing by the JOINT length n_s + m_s for the held-out scores — k_long_series_predict_logpdf on the long
+// value kernel's map and workspace above the short cap, the held-out mode's kernel and map below it.
+enum class SeriesMode { value, gradient, prediction, held_out, sum, hmc, long_value, long_prediction, long_held_out };
 constexpr int SERIES_LONG_CLASS = 3;      // launch classes 3, 4: the long kernel<4 / 8> of the mode (0 .. 2: the mode's short kernels)
 
 // One call of a many-series entry: the caller's inputs and what each shared stage leaves for the later ones.
@@ -267,17 +271,19 @@ int series_check_layout(agp_ctx* c, const SeriesCall& sc) {
 }
 
 // the entries that factor a series' training and query points together (what: "held-out" or "query"): the joint size of series s
-int series_check_joint(agp_ctx* c, const SeriesCall& sc, int32_t s, const char* what) {
+// against the entry's cap (max_n, named max_name: the short entries' AGP_SERIES_MAX_N, the long held-out entry's AGP_LONG_SERIES_MAX_N)
+int series_check_joint(agp_ctx* c, const SeriesCall& sc, int32_t s, const char* what, int max_n = AGP_SERIES_MAX_N,
+                       const char* max_name = "AGP_SERIES_MAX_N") {
   const long long n = sc.pt_off[s + 1] - sc.pt_off[s], m = sc.q_off[s + 1] - sc.q_off[s];
-  if (m == 0 || n + m <= AGP_SERIES_MAX_N) return AGP_OK;
+  if (m == 0 || n + m <= max_n) return AGP_OK;
   char buf[256];
-  snprintf(buf, sizeof buf, "series %d has %lld training and %lld %s points, together more than AGP_SERIES_MAX_N (%d)", (int)s, n, m, what,
-           AGP_SERIES_MAX_N);
+  snprintf(buf, sizeof buf, "series %d has %lld training and %lld %s points, together more than %s (%d)", (int)s, n, m, what, max_name,
+           max_n);
   return fail(c, AGP_ERR_ARG, buf);
 }
 
 // LDS bytes of particle p on a series of n points (held_out — the held-out and the sampling entry —: the joint n_s + m_s points, the
-// value kernel's map): the mode's own map
+// value kernel's map; long_held_out: the joint points as well, the long value kernel's map on the long route): the mode's own map
 size_t series_need(SeriesMode mode, const Batch& bt, int p, int n, int hmc_C = 0, bool long_route = false) {
   const ProgHdr& h = bt.hdr[(size_t)p];
   const bool long_pred = mode == SeriesMode::long_prediction;
@@ -332,9 +338,11 @@ int series_classes(agp_ctx* c, SeriesCall& sc, SeriesMode mode) {
     if (sc.q_off) sc.nq[(size_t)p] = sc.q_off[s + 1] - sc.q_off[s];
     // held-out scores: the workgroup factors the JOINT points, so length, LDS need, class and "longest first" are those of
     // n_s + m_s; nothing held out scores 0 without a launch, as an empty series does in the value entry
-    if (mode == SeriesMode::held_out) sc.len[(size_t)p] = n = sc.nq[(size_t)p] > 0 ? n + (int)sc.nq[(size_t)p] : 0;
+    if (mode == SeriesMode::held_out || mode == SeriesMode::long_held_out)
+      sc.len[(size_t)p] = n = sc.nq[(size_t)p] > 0 ? n + (int)sc.nq[(size_t)p] : 0;
     if (n == 0 && sc.nq[(size_t)p] == 0) continue;      // (an empty series is launched for its prior predictive only)
-    const bool lng = (mode == SeriesMode::long_value || mode == SeriesMode::long_prediction) && sc.long_route(n);
+    const bool lng = (mode == SeriesMode::long_value || mode == SeriesMode::long_prediction || mode == SeriesMode::long_held_out) &&
+                     sc.long_route(n);
     const size_t need = sc.need[(size_t)p] = series_need(mode, bt, p, n, sc.hmc_C, lng);
     if (need > (size_t)SERIES_LDS_BYTES) {
       snprintf(buf, sizeof buf, "particle %d: %d per-point tables (%s) at %d points need %zu bytes of LDS, more than the "
@@ -941,8 +949,12 @@ struct SeriesProbaOut {
 };
 
 // The log-density of every series' held-out values under each of its particles: the value kernel on the joint points, the
-// mixtures' read-out behind it on the same stream.
-int predict_logpdf_series(agp_ctx* c, SeriesCall& sc, const SeriesProbaOut& po, double* out_logpdf, int32_t* out_info) {
+// mixtures' read-out behind it on the same stream.  mode held_out: agp_predict_logpdf_series_batch; mode long_held_out:
+// agp_predict_logpdf_long_series_batch — the same stages, the joint size checked against the entry's cap (sc.max_n), the long particles'
+// launches (classes SERIES_LONG_CLASS ..) with the value kernel's workspace out of the slot's A, split where the call's workspace
+// limit asks for it
+int predict_logpdf_series(agp_ctx* c, SeriesCall& sc, const SeriesProbaOut& po, double* out_logpdf, int32_t* out_info,
+                          SeriesMode mode = SeriesMode::held_out) {
   const int P = sc.pp.P;
   const int32_t S = sc.S;
   char buf[256];
@@ -957,7 +969,7 @@ int predict_logpdf_series(agp_ctx* c, SeriesCall& sc, const SeriesProbaOut& po, 
   if (!po.y_pred && Q > 0) return fail(c, AGP_ERR_ARG, "null pointer argument (y_pred with held-out points present)");
   std::vector<double> slope((size_t)S);
   for (int32_t s = 0; s < S; ++s) {
-    STAGE(series_check_joint(c, sc, s, "held-out"));
+    STAGE(series_check_joint(c, sc, s, "held-out", sc.max_n, sc.max_name));
     for (long long j = 0, m = sc.q_off[s + 1] - sc.q_off[s]; j < m; ++j)
       if (!std::isfinite(po.y_pred[sc.q_off[s] + j])) {
         snprintf(buf, sizeof buf, "series %d: held-out value %lld is not finite", (int)s, j);
@@ -970,7 +982,7 @@ int predict_logpdf_series(agp_ctx* c, SeriesCall& sc, const SeriesProbaOut& po, 
   if (po.weights) STAGE(mix_plan(c, S, P, sc.series, sc.q_off, po.weights, nullptr, nullptr, 0, qp));
   const double nanv = std::numeric_limits<double>::quiet_NaN();
   if (P == 0) { std::fill(po.series_logp, po.series_logp + S, nanv); return AGP_OK; }      // (S series without a particle)
-  STAGE(series_classes(c, sc, SeriesMode::held_out));
+  STAGE(series_classes(c, sc, mode));
   if (po.out_off) std::copy(sc.ooff.begin(), sc.ooff.end(), po.out_off);      // (no check is left to fail, nothing is launched yet)
   if (sc.wg.empty()) {      // nothing held out for any particle: every score is 0, and so is every mixture's
     series_zero_values(sc, out_logpdf, out_info);
@@ -979,6 +991,7 @@ int predict_logpdf_series(agp_ctx* c, SeriesCall& sc, const SeriesProbaOut& po, 
   }
   STAGE(series_stage(c, sc));
   Slot* s = sc.s;
+  STAGE(series_long_workspace(c, sc));
   // sq_w = [y_pred (Q) | slope (S) | the plan's values: w (W) ..]; sq_tab = [pl_off | w_off | row_off | plist]; sq_out = the mixtures (S)
   MixTabs mt = {};
   HIPCHK(c, s->sq_w.ensure(sizeof(double) * std::max<size_t>(1, Q + (size_t)S + qp.vals.size())));
@@ -995,8 +1008,15 @@ int predict_logpdf_series(agp_ctx* c, SeriesCall& sc, const SeriesProbaOut& po, 
   pa.y_pred = s->sq_w.as<double>(); pa.y_slope = s->sq_w.as<double>() + Q;
   pa.out_terms = po.terms ? s->pred_mean.as<double>() : nullptr;
   STAGE(series_launch(c, sc, [&](const int32_t* wg, int grid, int d, size_t lds) {
-    pa.wg = wg;
-    return launch_series_predict_logpdf(sc.st, pa, grid, d == 0 ? 4 : 8, lds);
+    if (d < SERIES_LONG_CLASS) {
+      pa.wg = wg;
+      return launch_series_predict_logpdf(sc.st, pa, grid, d == 0 ? 4 : 8, lds);
+    }
+    LongSeriesProbaArgs la = {};
+    static_cast<SeriesProbaArgs&>(la) = pa;
+    return series_launch_long(c, sc, wg, grid, la, [&](const LongSeriesProbaArgs& a, int cnt) {
+      return launch_long_series_predict_logpdf(sc.st, a, cnt, d == SERIES_LONG_CLASS ? 4 : 8, lds);
+    });
   }));
   if (po.weights) {
     SeriesMixLogpArgs ma = {};
@@ -1491,6 +1511,20 @@ int agp_predict_logpdf_series_batch(agp_ctx* c, int32_t S, const int64_t* pt_off
     SeriesCall sc{S, pt_off, ts, xs, {P, op_off, ops, prm_off, prm, noise, noise_pred}, series, q_off, ts_pred};
     const SeriesProbaOut po{y_pred, y_slope, weights, out_terms, out_off, out_series_logp};
     return predict_logpdf_series(c, sc, po, out_logpdf, out_info);
+  });
+}
+
+int agp_predict_logpdf_long_series_batch(agp_ctx* c, int32_t S, const int64_t* pt_off, const double* ts, const double* xs,
+                                         const int64_t* q_off, const double* ts_pred, const double* y_pred, int32_t P,
+                                         const int32_t* series, const int32_t* op_off, const uint8_t* ops, const int32_t* prm_off,
+                                         const double* prm, const double* noise, const double* noise_pred, const double* y_slope,
+                                         const double* weights, double* out_logpdf, double* out_terms, int64_t* out_off,
+                                         double* out_series_logp, int32_t* out_info, uint32_t flags) {
+  return abi_guard(c, [&] {
+    SeriesCall sc{S, pt_off, ts, xs, {P, op_off, ops, prm_off, prm, noise, noise_pred}, series, q_off, ts_pred};
+    const SeriesProbaOut po{y_pred, y_slope, weights, out_terms, out_off, out_series_logp};
+    if (const int rc = series_long_entry(c, sc, flags)) return rc;
+    return predict_logpdf_series(c, sc, po, out_logpdf, out_info, SeriesMode::long_held_out);
   });
 }
 

@@ -42,6 +42,7 @@ EXPORTED_SYMBOLS = [
     "agp_predict_logpdf_series_batch", "agp_predict_sample_series_batch", "agp_predict_sum_series_batch",
     "agp_debug_toeplitz", "agp_debug_cov_sweep", "agp_hmc_series_batch", "agp_logpdf_long_series_batch",
     "agp_debug_long_series_factor", "agp_predict_long_series_batch", "agp_predict_quantile_long_series_batch",
+    "agp_predict_logpdf_long_series_batch",
 ]
 COMM_ID_BYTES = 128
 SERIES_MAX_N = 176      # AGP_SERIES_MAX_N of include/autogp_hip.h: the longest series of logpdf_series_batch
@@ -132,6 +133,8 @@ def load_library(path=None):
     lib.agp_predict_logpdf_series_batch.argtypes = [vp, C.c_int32, C.POINTER(C.c_int64), dp, dp, C.POINTER(C.c_int64), dp, dp, C.c_int32, ip,
                                                     ip, u8p, ip, dp, dp, dp, dp, dp, dp, dp, C.POINTER(C.c_int64), dp, ip]
     lib.agp_predict_logpdf_series_batch.restype = C.c_int
+    lib.agp_predict_logpdf_long_series_batch.argtypes = lib.agp_predict_logpdf_series_batch.argtypes + [C.c_uint32]
+    lib.agp_predict_logpdf_long_series_batch.restype = C.c_int
     lib.agp_predict_sample_series_batch.argtypes = [vp, C.c_int32, C.POINTER(C.c_int64), dp, dp, C.POINTER(C.c_int64), dp, C.c_int32, ip, ip,
                                                     u8p, ip, dp, dp, dp, dp, dp, dp, C.c_int64, C.POINTER(C.c_uint64), ip, dp, dp, ip,
                                                     dp, C.POINTER(C.c_int64), dp, C.POINTER(C.c_int64), ip]
@@ -791,9 +794,33 @@ class GPEngine:
         (want_terms) a list of views, terms[p][j] the log-density of held-out point j given the training data and the points before
         it, summing to logpdf[p]; series_logp (S,) with weights — the log of each series' mixture density at its held-out vector
         (NaN for a series without particles or with a failed particle, 0 where nothing is held out) — else None."""
-        packed = series_call_args(series, nodes, noises, series_index, programs)
+        return self._predict_logpdf_series("agp_predict_logpdf_series_batch", (), SERIES_MAX_N, series, queries, heldout, nodes, noises,
+                                           series_index, weights, y_transforms, noise_pred, want_terms, check, programs)
+
+    def predict_logpdf_long_series_batch(self, series, queries, heldout, nodes, noises, series_index, weights=None, y_transforms=None,
+                                         noise_pred=None, want_terms=False, all_long=False, check=True, programs=None):
+        """agp_predict_logpdf_long_series_batch: predict_logpdf_series_batch for len(series[s]) + len(queries[s]) of at most
+        LONG_SERIES_MAX_N joint points — same arguments, same returns.  A series whose joint length is at most SERIES_MAX_N runs in
+        predict_logpdf_series_batch's kernel (bit-identical logpdf, terms, mixtures and info); a longer one runs in the long kernel
+        on the joint points, its factor in an HBM workspace (bounded by set_workspace_limit; more long particles than fit are split
+        into several launches).  all_long: every particle with held-out points takes the long kernel.  A series with held-out points
+        and a joint length above LONG_SERIES_MAX_N is a ValueError that names it, before any library call."""
+        return self._predict_logpdf_series("agp_predict_logpdf_long_series_batch", (LONG_SERIES_ALL if all_long else 0,),
+                                           LONG_SERIES_MAX_N, series, queries, heldout, nodes, noises, series_index, weights, y_transforms,
+                                           noise_pred, want_terms, check, programs)
+
+    def _predict_logpdf_series(self, entry, tail, max_n, series, queries, heldout, nodes, noises, series_index, weights, y_transforms,
+                               noise_pred, want_terms, check, programs):
+        """the two held-out entries: `entry` with the trailing arguments `tail` behind agp_predict_logpdf_series_batch's; max_n: the
+        cap pack_series applies per series and, in the long entry, the cap on the joint length of a series with held-out points"""
+        packed = series_call_args(series, nodes, noises, series_index, programs, max_n=max_n)
         S, P, sidx = packed[0].shape[0] - 1, packed[4], packed[6]
         qpack = pack_queries(queries, S, _particle_noise_pred(noise_pred, P), P)
+        if max_n == LONG_SERIES_MAX_N:      # (the short entry's joint cap is the library's to report, as it always was)
+            for s, (n_s, m_s) in enumerate(zip(np.diff(packed[0]), np.diff(qpack[0]))):
+                if m_s > 0 and n_s + m_s > max_n:
+                    raise ValueError(f"series {s} has {n_s} training and {m_s} held-out points, together more than "
+                                     f"LONG_SERIES_MAX_N ({max_n})")
         y_pred, slope = pack_heldout(heldout, qpack[0], y_transforms)
         if weights is not None:
             weights = _particle_weights(weights, P)
@@ -804,9 +831,9 @@ class GPEngine:
         out_off = np.zeros(P + 1, dtype=np.int64)
         mix = np.empty(max(1, S)) if weights is not None else None
         a = _series_ctypes(packed, qpack)      # (.., q_off, ts_pred | P, ..): the held-out values travel between the two
-        self._check(self._lib.agp_predict_logpdf_series_batch(
+        self._check(getattr(self._lib, entry)(
             self._ctx, *a[:6], _dp(y_pred if y_pred.size else np.zeros(1)), *a[6:], _dp(slope), _dp(weights), _dp(lp), _dp(terms),
-            out_off.ctypes.data_as(C.POINTER(C.c_int64)), _dp(mix), _ip(info)))
+            out_off.ctypes.data_as(C.POINTER(C.c_int64)), _dp(mix), _ip(info), *tail))
         lp, info = lp[:P], info[:P]
         _raise_first_bad(info, check)
         cut = None if terms is None else [terms[out_off[p]:out_off[p + 1]] for p in range(P)]
@@ -1906,16 +1933,25 @@ def predict_quantile_series(engine, series, queries, nodes, noises, series_index
     return [(x, (bool(c.all()) if np.ndim(q) == 0 else c.all(axis=0))) for x, c in zip(band.x, band.converged)]
 
 
-def predict_proba_series(engine, series, queries, heldout, nodes, noises, series_index, log_weights, y_transforms=None, noise_pred=None):
+def predict_proba_series(engine, series, queries, heldout, nodes, noises, series_index, log_weights, y_transforms=None, noise_pred=None,
+                         max_n=SERIES_MAX_N, all_long=False):
     """predict_proba for callers that hold one model per short series: particle p belongs to the model of series[series_index[p]],
     which weighs it by the softmax of log_weights over THAT series' particles (pack_series_mixture); heldout[s] are the RAW values
     observed at queries[s]; one call of GPEngine.predict_logpdf_series_batch serves every series.  Returns a list over the series of
     dicts with the reference's three columns {"particle", "weight", "logp"} — "particle" the 1-based positions inside the series'
     model, as predict_proba numbers them — plus "mixture_logp", the log-density of the held-out vector under the model's mixture.
-    Raises PosDefException when a particle has no predictive."""
+    Raises PosDefException when a particle has no predictive.  max_n=LONG_SERIES_MAX_N (or all_long=True: every particle with held-out
+    points in the long kernel) takes GPEngine.predict_logpdf_long_series_batch instead: training and held-out points of a series
+    together up to LONG_SERIES_MAX_N; any other max_n is a ValueError."""
+    if max_n not in (SERIES_MAX_N, LONG_SERIES_MAX_N):
+        raise ValueError(f"max_n must be SERIES_MAX_N ({SERIES_MAX_N}) or LONG_SERIES_MAX_N ({LONG_SERIES_MAX_N})")
     lists, w = pack_series_mixture(series_index, len(series), log_weights=log_weights)
-    sc = engine.predict_logpdf_series_batch(series, queries, heldout, nodes, noises, series_index, weights=w, y_transforms=y_transforms,
-                                            noise_pred=noise_pred)
+    if all_long or max_n == LONG_SERIES_MAX_N:
+        sc = engine.predict_logpdf_long_series_batch(series, queries, heldout, nodes, noises, series_index, weights=w,
+                                                     y_transforms=y_transforms, noise_pred=noise_pred, all_long=all_long)
+    else:
+        sc = engine.predict_logpdf_series_batch(series, queries, heldout, nodes, noises, series_index, weights=w,
+                                                y_transforms=y_transforms, noise_pred=noise_pred)
     return [{"particle": np.arange(1, sel.size + 1), "weight": w[sel], "logp": sc.logpdf[sel], "mixture_logp": float(sc.series_logp[s])}
             for s, sel in enumerate(lists)]
 

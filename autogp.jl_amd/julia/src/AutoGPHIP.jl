@@ -573,6 +573,61 @@ function predict_proba_series_batch(eng::Engine, series::Vector{<:Tuple{Vector{F
     return out[1:P], cut, (weights === nothing ? nothing : mix[1:S]), info[1:P]
 end
 
+"`predict_proba_series_batch` for training plus held-out points of a series of at most `LONG_SERIES_MAX_N` together
+(agp_predict_logpdf_long_series_batch): same arguments, same returns, same statelessness — the tutorial's split of 144 training and 36
+held-out points, or a held-out tail of the 442-point data set, beside the short series in one call.  A series whose joint length is at
+most `SERIES_MAX_N` runs in `predict_proba_series_batch`'s kernel (bit-identical results), a longer one in the long-series kernel on
+the joint points, its factor in an HBM workspace; `all_long = true` sends every particle with held-out points through the long kernel."
+function predict_proba_long_series_batch(eng::Engine, series::Vector{<:Tuple{Vector{Float64},Vector{Float64}}},
+                                         queries::Vector{Vector{Float64}}, heldout::Vector{Vector{Float64}}, nodes::Vector{<:GP.Node},
+                                         noises::Vector{Float64}, series_index::Vector{<:Integer};
+                                         weights::Union{Nothing,Vector{Float64}}=nothing,
+                                         y_transforms::Union{Nothing,Vector{Tuple{Float64,Float64}}}=nothing,
+                                         noise_pred::Union{Nothing,Vector{Float64}}=nothing, all_long::Bool=false)
+    P = length(nodes); S = length(series)
+    (length(noises) == P && length(series_index) == P) || throw(ArgumentError("one noise and one series index per particle required"))
+    (weights === nothing || length(weights) == P) || throw(ArgumentError("one weight per particle required"))
+    (length(queries) == S && length(heldout) == S) ||
+        throw(ArgumentError("one vector of query times and one of held-out values per series required"))
+    (noise_pred === nothing || length(noise_pred) == P) || throw(ArgumentError("one noise_pred per particle required"))
+    (y_transforms === nothing || length(y_transforms) == S) || throw(ArgumentError("one (slope, intercept) per series required"))
+    all(i -> 1 <= i <= S, series_index) || throw(ArgumentError("series index outside 1:$S"))
+    pt_off = Int64[0]; ts = Float64[]; xs = Float64[]; q_off = Int64[0]; tq = Float64[]; yq = Float64[]
+    for (s, (t, x)) in enumerate(series)
+        length(t) == length(x) || throw(ArgumentError("series $s: ts and xs must have equal lengths"))
+        length(t) <= LONG_SERIES_MAX_N || throw(ArgumentError("series $s has $(length(t)) points, more than LONG_SERIES_MAX_N ($LONG_SERIES_MAX_N)"))
+        length(heldout[s]) == length(queries[s]) ||
+            throw(ArgumentError("series $s: $(length(queries[s])) held-out values required, one per query time"))
+        (isempty(queries[s]) || length(t) + length(queries[s]) <= LONG_SERIES_MAX_N) ||
+            throw(ArgumentError("series $s has $(length(t)) training and $(length(queries[s])) held-out points, together more than LONG_SERIES_MAX_N ($LONG_SERIES_MAX_N)"))
+        a, b = y_transforms === nothing ? (1.0, 0.0) : y_transforms[s]
+        append!(ts, t); append!(xs, x); push!(pt_off, length(ts))
+        append!(tq, queries[s]); push!(q_off, length(tq))
+        append!(yq, y_transforms === nothing ? heldout[s] : a .* heldout[s] .+ b)
+    end
+    isempty(ts) && (push!(ts, 0.0); push!(xs, 0.0))
+    isempty(tq) && (push!(tq, 0.0); push!(yq, 0.0))
+    sidx = Int32[Int32(i - 1) for i in series_index]
+    op_off, ops, prm_off, prm = encode_batch(nodes)
+    slope = y_transforms === nothing ? ones(Float64, max(1, S)) : Float64[t[1] for t in y_transforms]
+    total = sum(Int[length(queries[i]) for i in series_index])
+    out = Vector{Float64}(undef, max(1, P)); info = zeros(Int32, max(1, P))
+    terms = Vector{Float64}(undef, max(1, total)); out_off = zeros(Int64, P + 1)
+    mix = Vector{Float64}(undef, max(1, S))
+    np = noise_pred === nothing ? noises : noise_pred
+    w = weights === nothing ? Float64[] : weights
+    flags = all_long ? UInt32(LONG_SERIES_ALL) : UInt32(0)
+    GC.@preserve pt_off ts xs q_off tq yq sidx op_off ops prm_off prm noises np slope w out terms out_off mix info check(eng, ccall((:agp_predict_logpdf_long_series_batch, LIB), Cint,
+        (Ptr{Cvoid}, Int32, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Int32}, Ptr{Int32},
+         Ptr{UInt8}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+         Ptr{Int64}, Ptr{Float64}, Ptr{Int32}, UInt32),
+        eng.ptr, S, pt_off, ts, xs, q_off, tq, yq, P, sidx, op_off, ops, prm_off, prm, noises, np, slope,
+        weights === nothing ? Ptr{Float64}(C_NULL) : pointer(w), out, terms, out_off,
+        weights === nothing ? Ptr{Float64}(C_NULL) : pointer(mix), info, flags))
+    cut = [terms[out_off[p] + 1:out_off[p + 1]] for p in 1:P]
+    return out[1:P], cut, (weights === nothing ? nothing : mix[1:S]), info[1:P]
+end
+
 "Sample paths of many short series in one fused launch (agp_predict_sample_series_batch): `rand(predict_mvn(model, ds), n_samples)`
 for callers that hold one model per short series, with `predict_proba_series_batch`'s series / query / particle arguments and
 statelessness.  `weights[p]` is particle `p`'s weight inside ITS series' mixture; series `s` draws its `n_samples` paths under

@@ -144,6 +144,41 @@ kernels() = GP.Node[
         @test eng.n_max == 700      # the resident series is untouched
     end
 
+    @testset "series of up to 512 joint points: held-out scores in one call (stateless)" begin
+        ks = kernels()
+        splits = ((0, 5), (126, 18), (144, 36), (406, 36))     # (training points, held-out points): joint lengths 5, 144, 180, 442
+        sers = [(ts[1:n], xs[1:n]) for (n, _) in splits]
+        qs = [ts[n + 1:n + m] for (n, m) in splits]
+        a, b = 0.7, -0.2                                       # scaled = a raw + b
+        held = [(xs[n + 1:n + m] .- b) ./ a for (n, m) in splits]
+        nodes = GP.Node[]; sidx = Int[]
+        for s in eachindex(sers), k in ks
+            push!(nodes, k); push!(sidx, s)
+        end
+        P = length(nodes)
+        w = Float64[1 / length(ks) for _ in 1:P]
+        yts = fill((a, b), length(sers))
+        lp, terms, mix, info = H.predict_proba_long_series_batch(eng, sers, qs, held, nodes, fill(noise, P), sidx; weights=w, y_transforms=yts)
+        la, _, _, ia = H.predict_proba_long_series_batch(eng, sers, qs, held, nodes, fill(noise, P), sidx; weights=w, y_transforms=yts,
+                                                         all_long=true)
+        @test all(info .== 0) && all(ia .== 0)
+        for (p, (k, s)) in enumerate(zip(nodes, sidx))
+            n, m = splits[s]
+            r = ref_logpdf(k, noise, ts[1:n + m], xs[1:n + m]) - (n == 0 ? 0.0 : ref_logpdf(k, noise, ts[1:n], xs[1:n])) + m * log(a)
+            @test relerr(lp[p], r) <= 1e-7
+            @test relerr(la[p], r) <= 1e-7
+            @test length(terms[p]) == m && relerr(sum(terms[p]), lp[p]) <= 1e-12
+        end
+        # up to the short cap on the joint length the default routing is predict_proba_series_batch's kernel: the same bits
+        short = [p for p in eachindex(nodes) if sum(splits[sidx[p]]) <= H.SERIES_MAX_N]
+        ls, _, ms, _ = H.predict_proba_series_batch(eng, sers[1:2], qs[1:2], held[1:2], nodes[short], fill(noise, length(short)),
+                                                    sidx[short]; weights=w[short], y_transforms=yts[1:2])
+        @test lp[short] == ls && mix[1:2] == ms
+        @test_throws ArgumentError H.predict_proba_long_series_batch(eng, [(ts[1:500], xs[1:500])], [ts[501:513]], [xs[501:513]], ks[1:1],
+                                                                     [noise], [1])
+        @test eng.n_max == 700      # the resident series is untouched
+    end
+
     @testset "many short series: sample paths and joint forecasts in one call (stateless)" begin
         ks = kernels()
         splits = ((0, 5), (17, 5), (126, 18), (140, 36))       # (training points, query points)

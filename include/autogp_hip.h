@@ -145,8 +145,9 @@ int agp_logpdf_series_batch(agp_ctx* ctx, int32_t S, const int64_t* pt_off /* S+
  *     series' length.  The long kernel keeps 4 KiB per ChangePoint node (a 512-entry table) beside 21 KiB of vectors, tables and one
  *     diagonal block and the program: at 512 points a chain of 10 ChangePoint nodes takes 61 KiB (two workgroups share a CU), 34
  *     nodes beside a small program are the most 160 KiB hold, 40 are refused.
- * The forecast and its band above AGP_SERIES_MAX_N points: agp_predict_long_series_batch, agp_predict_quantile_long_series_batch.
- * Not here: gradient, held-out, sampling, decomposition and HMC twins above AGP_SERIES_MAX_N points; series beyond
+ * The forecast and its band above AGP_SERIES_MAX_N points: agp_predict_long_series_batch, agp_predict_quantile_long_series_batch;
+ * the held-out scores: agp_predict_logpdf_long_series_batch.
+ * Not here: gradient, sampling, decomposition and HMC twins above AGP_SERIES_MAX_N points; series beyond
  * AGP_LONG_SERIES_MAX_N; deduplication inside a call. */
 #define AGP_LONG_SERIES_MAX_N 512
 #define AGP_LONG_SERIES_ALL 1   /* flags: every non-empty series takes the long kernel */
@@ -398,7 +399,8 @@ int agp_predict_quantile_long_series_batch(agp_ctx* ctx, int32_t S, const int64_
  *     not finite, negative or not summing to 1 (rtol sqrt(eps)); weights / out_series_logp not both NULL or both given;
  *   AGP_ERR_PROGRAM (names the particle): a particle whose LDS need at N = n_s + m_s points exceeds 160 KiB — at N = AGP_SERIES_MAX_N
  *     a chain of 10 ChangePoint nodes fits and one of 11 does not, as in agp_logpdf_series_batch at that length.
- * Not here: the m x m predictive covariance, mean functions, n_s + m_s > AGP_SERIES_MAX_N, deduplication inside a call. */
+ * Not here: the m x m predictive covariance, mean functions, n_s + m_s > AGP_SERIES_MAX_N (agp_predict_logpdf_long_series_batch
+ * below takes up to AGP_LONG_SERIES_MAX_N), deduplication inside a call. */
 int agp_predict_logpdf_series_batch(agp_ctx* ctx, int32_t S, const int64_t* pt_off /* S+1 */, const double* ts, const double* xs,
                                     const int64_t* q_off /* S+1 */, const double* ts_pred, const double* y_pred /* q_off[S] */,
                                     int32_t P, const int32_t* series /* P */,
@@ -408,6 +410,43 @@ int agp_predict_logpdf_series_batch(agp_ctx* ctx, int32_t S, const int64_t* pt_o
                                     double* out_logpdf /* P */, double* out_terms /* out_off[P], or NULL */,
                                     int64_t* out_off /* P+1, or NULL */, double* out_series_logp /* S; NULL iff weights is */,
                                     int32_t* out_info /* P */);
+
+/* agp_predict_logpdf_series_batch for n_s + m_s of up to AGP_LONG_SERIES_MAX_N = 512 JOINT points: the reference tutorial's split of
+ * 144 training + 36 held-out points (180) and held-out tails of its 442-point data set, beside the short series, in ONE call.  The
+ * arguments are agp_predict_logpdf_series_batch's with a trailing flags word, and every convention is that entry's: y_pred in the
+ * space of xs, y_slope through the Jacobian term alone, noise_pred NULL = noise, the optional out_terms behind out_off, out_info on
+ * the JOINT index (1 .. n_s when K11 fails, n_s + k for leading minor k of the predictive covariance; NaN then in out_logpdf[p] and
+ * in the particle's whole block of out_terms), the prior predictive's density for an empty training series, logpdf 0 / info 0
+ * without a launch where m_s == 0, the mixtures' rules (k_series_mix_logp runs unchanged behind the launches on the same stream),
+ * P == 0, one upload and one synchronisation, agp_get_timing's words, the error codes and their messages.  Stateless and
+ * re-entrant like it.
+ * Routing by the JOINT length N = n_s + m_s, as in agp_logpdf_long_series_batch by n_s: N <= AGP_SERIES_MAX_N runs in
+ * agp_predict_logpdf_series_batch's kernel, bit-identical to that entry (logpdf, terms, mixtures, info); a longer one runs in
+ * k_long_series_predict_logpdf — the long value kernel's statements on the joint points with the two-noise diagonal, its two
+ * reductions restricted to the query rows [n_s, N) — in the long value kernel's LDS map and workspace at N points.
+ * flags & AGP_LONG_SERIES_ALL sends every particle with m_s > 0 through it.  With n_s == 0, y_slope NULL and noise_pred NULL,
+ * out_logpdf is bit-identical to agp_logpdf_long_series_batch's on the series (ts_pred, y_pred) under the same flags.
+ * Workspace: from the call's slot, 528 blocks of 2 KiB (1.03 MiB) per workgroup at 512 joint points; one launch takes at most
+ * min(agp_set_workspace_limit's value, 1 GiB) and a larger call is split into launches on its stream.  A particle's result bits
+ * depend only on its own series, queries, held-out values, program, parameters, noises, slope and the flag — not on what else is
+ * in the call, its order, or the split.
+ * The WHOLE call is rejected, and nothing is written to any output, with everything agp_predict_logpdf_series_batch reports, where
+ *   AGP_ERR_ARG: a series of more than AGP_LONG_SERIES_MAX_N training points; a series with m_s > 0 and n_s + m_s >
+ *     AGP_LONG_SERIES_MAX_N (the message names the series, both counts and that constant); flag bits other than AGP_LONG_SERIES_ALL;
+ *   AGP_ERR_PROGRAM (names the particle): a particle whose LDS need at N joint points exceeds 160 KiB.  On the long route that is
+ *     the long value kernel's need, 21 KiB + the program + 4 KiB per ChangePoint node at N = 512: a chain of 10 ChangePoint nodes
+ *     takes 61 KiB, one of 34 is the longest that fits and one of 35 is refused.
+ * Not here: the sampling, gradient, decomposition and HMC twins above AGP_SERIES_MAX_N points; the m x m predictive covariance;
+ * mean functions; n_s + m_s > AGP_LONG_SERIES_MAX_N; deduplication inside a call. */
+int agp_predict_logpdf_long_series_batch(agp_ctx* ctx, int32_t S, const int64_t* pt_off /* S+1 */, const double* ts, const double* xs,
+                                         const int64_t* q_off /* S+1 */, const double* ts_pred, const double* y_pred /* q_off[S] */,
+                                         int32_t P, const int32_t* series /* P */,
+                                         const int32_t* op_off, const uint8_t* ops, const int32_t* prm_off, const double* prm,
+                                         const double* noise /* P */, const double* noise_pred /* P or NULL = noise */,
+                                         const double* y_slope /* S, or NULL: 1 */, const double* weights /* P, or NULL */,
+                                         double* out_logpdf /* P */, double* out_terms /* out_off[P], or NULL */,
+                                         int64_t* out_off /* P+1, or NULL */, double* out_series_logp /* S; NULL iff weights is */,
+                                         int32_t* out_info /* P */, uint32_t flags);
 
 /* SAMPLE PATHS and JOINT FORECASTS of many short series in one call: rand(predict_mvn(model, ds), R) and the components of
  * predict_mvn's MixtureModel (src/api.jl:497-522) for callers that hold one model per short series.  The resident-series twins are
